@@ -92,6 +92,38 @@ def golden_totals(scene: str, w: int, h: int, spp: int, column: str = "oracle_li
     return None
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, image, totals: dict) -> dict:
+    """--dump-outputs: the arrays a caller of the timed path receives from its last frame, as .npy files in out_dir.
+    The reference's estimator yields a NaN contribution about once in 10^7 samples, and in the default (fp32-atomics) mode that
+    NaN reaches its pixel.  Every dumped value is finite so that two dumps compare with plain arithmetic:
+    a non-finite channel is stored as 0 in the image and as 1 in the mask written beside it (0 everywhere else)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    image = np.ascontiguousarray(image, dtype=np.float32)
+    files = {}
+    if 2 * image.nbytes <= DUMP_LIMIT_BYTES - (1 << 20):  # image + mask, 1 MB left for the totals and the .npy headers
+        name, values = "image", image
+    else:  # a fixed, seeded sample of whole pixels (the same pixels for the same width x height)
+        flat = image.reshape(-1, image.shape[-1])
+        n = DUMP_LIMIT_BYTES // 2 // (2 * flat.shape[1] * 4 + 8)
+        idx = np.sort(np.random.default_rng(12345).choice(flat.shape[0], size=n, replace=False))
+        name, values = "image_sample", flat[idx]
+        files["image_sample_pixels"] = idx.astype(np.float64)
+    bad = ~np.isfinite(values)
+    files[name] = np.where(bad, np.float32(0), values)
+    files[name + "_nonfinite"] = bad.astype(np.float32)
+    files["event_totals"] = np.array([totals[k] for k in TOTAL_KEYS], dtype=np.float64)
+    for fname, arr in files.items():
+        np.save(os.path.join(out_dir, fname + ".npy"), arr)
+    return {"dir": out_dir, "files": sorted(f + ".npy" for f in files), "event_totals_keys": list(TOTAL_KEYS),
+            "nonfinite_values": int(bad.sum()),
+            "what": "the last timed step's post-processed framebuffer (non-finite channels as 0, marked 1 in the _nonfinite "
+                    "mask) and event totals"}
+
+
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -107,6 +139,16 @@ def parse_args():
     ap.add_argument("--cpu-spp", type=int, default=16, help="spp of the bounded CPU-baseline sample (~10-15 s of CPU work)")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--save-image", default="")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the LAST timed step computed to DIR/<name>.npy (rank 0): image.npy = "
+                         "the post-processed framebuffer (float32, height x width x 3), image_nonfinite.npy = 1.0 where the "
+                         "framebuffer holds a NaN or inf (the reference's estimator yields a NaN about once in 10^7 samples; "
+                         "image.npy holds 0 there) and 0.0 elsewhere, and event_totals.npy = the frame's event totals summed over "
+                         "the ranks (float64, in the order of event_totals_keys in the JSON line).  An image too large for the "
+                         "64 MB limit is replaced by a fixed, seeded sample of its pixels (image_sample.npy, "
+                         "image_sample_nonfinite.npy, pixel indices in image_sample_pixels.npy as float64).  Same arguments = same "
+                         "inputs, so two builds compare file for file (fp32 atomics: pixels vary between runs at rounding level; "
+                         "--deterministic makes them bit-equal)")
     ap.add_argument("--deterministic", action="store_true",
                     help="accumulate in 64-bit fixed point (order-independent: the N-GPU image equals the 1-GPU image bit for bit)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for rehearsals)")
@@ -121,6 +163,8 @@ def parse_args():
                          "per_sample: NOT the reference's random numbers -- one stream per camera ray, so every rank runs the full "
                          "slot pool on spp / N samples of every pixel (statistically equivalent image; see include/rtcuda_amd.h)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1: the line reports the time of the timed steps")
     if args.debug_flags != 0 and not args.allow_invalid:
         raise SystemExit("--debug-flags changes what the kernels do (e.g. 0x100 drops every framebuffer deposit): the "
                          "number would be invalid.  Pass --allow-invalid to run anyway; the JSON line is then marked.")
@@ -263,6 +307,9 @@ def main():
     if args.save_image and rank == 0:
         scenes.write_ppm(args.save_image, head.fb.view(h, w, 3).cpu().numpy())
     head_totals = head.frame_totals()   # (collective: every rank calls it)
+    dumped = None
+    if args.dump_outputs and rank == 0:  # before anything below reuses the headline's framebuffer
+        dumped = dump_outputs(args.dump_outputs, head.fb.view(h, w, 3).cpu().numpy(), head_totals)
     invalid = ""
 
     # ---- N > 1: what the collective backend saw, every rank's share, the reduce on its own
@@ -669,6 +716,8 @@ def main():
         else:
             out["roofline"] = None
         out["one_off"] = one_off
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if invalid:
             out["invalid"] = invalid
             out["value"] = None  # an invalid line carries no number
