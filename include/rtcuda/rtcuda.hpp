@@ -23,6 +23,7 @@
 #ifndef RTCUDA_HPP
 #define RTCUDA_HPP
 
+#include <algorithm>
 #include <cassert>
 #include <cmath>
 #include <cstdint>
@@ -307,6 +308,28 @@ inline rt_scene *realise(const Scene &scene) {
 // The reference builds and uploads its BVH in the Bvh constructor (bvh.cuh:30-219); here the device scene is created
 // the first time a Scene is rendered.  prepare() does it ahead of time, so a driver can time the two apart.
 inline void prepare(const Scene &scene) { (void)rtcuda_detail::realise(scene); }
+
+// Moving geometry (no reference counterpart: its Bvh is built once): new positions for the Bvh's triangles, same count and
+// order, materials and lights kept.  Bvh::triangles takes them; a scene already realised on the device is refit there
+// (rt_scene_update), otherwise the next prepare() / render() simply builds from the new triangles.
+inline void update(Scene &scene, const std::vector<Triangle> &triangles) {
+    Bvh &bvh = scene.bvh;
+    if ((int)triangles.size() != bvh.num_primitives)
+        throw std::runtime_error("update: " + std::to_string(triangles.size()) + " triangles, the Bvh holds " + std::to_string(bvh.num_primitives));
+    std::copy(triangles.begin(), triangles.end(), bvh.triangles.begin());
+    rtcuda_detail::SceneHandle *sh = bvh.handle.get();
+    if (!sh || !sh->h) return;
+    const int n = bvh.num_primitives;
+    std::vector<float> verts((size_t)9 * (n > 0 ? n : 1));
+    for (int i = 0; i < n; i++) {
+        const Triangle &t = bvh.triangles[(size_t)i];
+        float *q = &verts[9 * (size_t)i];
+        q[0] = t.p0.x; q[1] = t.p0.y; q[2] = t.p0.z;
+        q[3] = t.p1_.x; q[4] = t.p1_.y; q[5] = t.p1_.z;
+        q[6] = t.p2_.x; q[7] = t.p2_.y; q[8] = t.p2_.z;
+    }
+    rtcuda_detail::check(rt_scene_update(sh->h, verts.data(), n), "update");
+}
 
 // A driver that must keep the reference's exact call (main.cu:173) can still reach several GPUs: RTCUDA_DEVICES="0,1,2,3" in
 // the environment sends the seven-argument render() below through the multi-device path (rt_render_multi).

@@ -146,6 +146,23 @@ int rt_scene_info(const rt_scene *scene, int64_t out[4]);
  * on stdout (bvh.cuh:106-201). */
 int rt_scene_build_info(const rt_scene *scene, int *builder, double *seconds);
 
+/* ---- moving geometry (no reference counterpart: its Bvh is built once, bvh.cuh:30-219) ----------------------------
+ * New positions for the scene's triangles: n_tris x 9 floats, the caller's ORIGINAL order, same count as at creation.
+ * Materials, light assignment and topology are kept.  The BVH is refit on the scene's device (same tree, new boxes);
+ * triangle, shading and light-triangle records are recomputed.  No render of this scene may be in flight.
+ * The image is that of a scene created anew from the same vertices, bit for bit, in every mode (hits never depend on the
+ * product's own tree).  What follows an update: the reference's tree (default mode, RT_FLAG_REFERENCE_WALK) is rebuilt on the
+ * host from the new triangles by the next render that needs it (about 0.045 s on the bunny, reported in
+ * seconds_reference_tree; RT_FLAG_WATERTIGHT never pays it), and replicas made by rt_render_multi are dropped and recreated
+ * on their next use.  Errors (null scene or pointer, another triangle count, a 2-wide RT_BVH_WIDE=0 scene) leave the scene
+ * as it was. */
+int rt_scene_update(rt_scene *scene, const float *tri_p0p1p2, int n_tris);
+/* Same, from a DEVICE buffer on the scene's device, ordered on `stream` (NULL = default stream), synchronous on return. */
+int rt_scene_update_device(rt_scene *scene, const float *d_tri_p0p1p2, int n_tris, void *stream);
+/* refits since creation, device seconds of the last refit (HIP events), and the tree's surface-area cost relative to its
+ * value at build time (advisory: when it grows, create the scene anew) */
+int rt_scene_refit_info(const rt_scene *scene, int64_t *refits, double *seconds_last, double *sah_ratio);
+
 /* Replaces Camera::Camera(lookfrom, lookat, up, vfov_deg, aspect) (camera.cuh:15-29). Host only. */
 int rt_camera_make(const float lookfrom[3], const float lookat[3], const float up[3], float vfov_deg,
                    float aspect_ratio, rt_camera *out);

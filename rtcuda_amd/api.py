@@ -28,7 +28,8 @@ FLAG_REFERENCE_WALK = 8  # cross-check mode: every ray walks the reference's own
 FLAG_WATERTIGHT = 16     # the triangle-list definition (no hit lost to a box test, ties by caller index) instead of the reference's
 
 EXPORTS = [
-    "rt_scene_create", "rt_scene_destroy", "rt_scene_info", "rt_scene_build_info", "rt_camera_make", "rt_render", "rt_render_multi",
+    "rt_scene_create", "rt_scene_destroy", "rt_scene_info", "rt_scene_build_info", "rt_scene_update", "rt_scene_update_device",
+    "rt_scene_refit_info", "rt_camera_make", "rt_render", "rt_render_multi",
     "rt_render_shard", "rt_render_shard_fixed", "rt_post_process", "rt_post_process_fixed", "rt_trace_closest", "rt_trace_any",
     "rt_trace_closest_flags", "rt_trace_any_flags", "rt_xorwow_states", "rt_shutdown", "rt_peer_access_log", "rt_last_error", "rt_version", "rt_build_id",
 ]
@@ -121,6 +122,10 @@ def _bind(L):
     L.rt_scene_destroy.restype = None
     L.rt_scene_info.argtypes = [vp, vp]
     L.rt_scene_build_info.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_double)]
+    L.rt_scene_update.argtypes = [vp, vp, ci]
+    L.rt_scene_update_device.argtypes = [vp, vp, ci, vp]
+    L.rt_scene_refit_info.argtypes = [vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_double),
+                                      ctypes.POINTER(ctypes.c_double)]
     L.rt_camera_make.argtypes = [vp, vp, vp, cf, cf, vp]
     L.rt_render.argtypes = [vp, vp, ci, ci, ci, ci, ctypes.c_uint64, ctypes.c_uint32, vp, ctypes.POINTER(RtStats)]
     L.rt_render_multi.argtypes = [vp, vp, ci, ci, ci, ci, ctypes.c_uint64, ctypes.c_uint32, vp, ci, vp, ctypes.POINTER(RtStats)]
@@ -232,6 +237,27 @@ class Scene:
         _check(self.L.rt_scene_build_info(self.h, ctypes.byref(b), ctypes.byref(sec)), "rt_scene_build_info", self.L)
         return {"pairs": int(out[0]), "tris": int(out[1]), "max_depth": int(out[2]), "leaves": int(out[3]),
                 "builder": "lbvh" if b.value else "sah", "build_seconds": sec.value}
+
+    # ---- moving geometry: new vertex positions, same triangles, materials and lights (rt_scene_update)
+    def update(self, tris) -> None:
+        """New positions for every triangle ((n, 9) float32 p0 p1 p2, the creation order and count): the BVH is refit on the
+        device.  Renders afterwards are bit-equal to those of a scene created from the same vertices."""
+        tris = np.ascontiguousarray(tris, np.float32).reshape(-1, 9)
+        _check(self.L.rt_scene_update(self.h, _p(tris), tris.shape[0]), "rt_scene_update", self.L)
+
+    def update_device(self, ptr: int, stream: int = 0, n_tris: int = None) -> None:
+        """The same from a DEVICE buffer of n_tris x 9 float32 on the scene's device (e.g. ``tensor.data_ptr()``), ordered
+        on ``stream`` (0 = default stream; synchronous on return).  n_tris defaults to the scene's count."""
+        n = self.arrays.n_tris if n_tris is None else int(n_tris)
+        _check(self.L.rt_scene_update_device(self.h, ctypes.c_void_p(ptr), n, ctypes.c_void_p(stream)),
+               "rt_scene_update_device", self.L)
+
+    def refit_info(self) -> dict:
+        """Refits since creation, device seconds of the last one, and the tree's surface-area cost relative to build time."""
+        refits, sec, ratio = ctypes.c_int64(0), ctypes.c_double(0.0), ctypes.c_double(0.0)
+        _check(self.L.rt_scene_refit_info(self.h, ctypes.byref(refits), ctypes.byref(sec), ctypes.byref(ratio)),
+               "rt_scene_refit_info", self.L)
+        return {"refits": refits.value, "seconds_last": sec.value, "sah_ratio": ratio.value}
 
     # ---- render(): the drop-in entry point
     def render(self, camera: np.ndarray, width: int, height: int, spp: int, max_bounces: int = 10,

@@ -6,6 +6,8 @@
 //     reachable exactly once, every record box contains what lies beneath it, stack bound) and walks both on the CPU
 //     with the control flow and the fp32 expressions of inner_step / the triangle blocks in rtcuda_amd.hip, comparing
 //     with an exhaustive search.  A malformed tree would hang or fault the GPU; this is where it is caught first.
+//   * rt_bvh_refit_check  the host twin of the device refit (rt_scene_update): the builder's records with new vertices,
+//     checked as above (bit-equal to the builder's with the creation vertices; structure and walk with moved ones).
 //   * rt_hostwalk_*     the same walk for arbitrary rays (closest hit / any hit), with work counters: the traversal
 //     audit (tests/test_traversal_audit.py) replays the rays of an oracle render through it.
 #include <cfloat>
@@ -283,6 +285,44 @@ int64_t validate(const rtbvh::Result &r, const std::vector<rtbvh::Pair> &rec, bo
     for (int i = 0; i < n_nodes; i++) if (seen_node[i] != 1) errors++;
     return errors;
 }
+// ---- host twin of the device refit (k_refit_level in rtcuda_amd.hip): the builder's 4-wide records with new vertices.
+// A node's child boxes are exact -- a leaf child's from the triangles' vertices p0, p1, p2, an inner child's the union of
+// its own children's exact boxes -- and padded by 2 ulps only when written, as rtbvh::build writes them.  Children come
+// after their parent in record order, so one backward sweep is bottom-up.
+std::vector<rtbvh::Pair> refit_quads(const std::vector<rtbvh::Pair> &quads, const std::vector<int32_t> &order, const float *verts) {
+    std::vector<rtbvh::Pair> out = quads;
+    const size_t n_nodes = quads.size() / 2;
+    std::vector<rtbvh::Box> exact(n_nodes);
+    for (size_t j = n_nodes; j-- > 0;) {
+        exact[j].reset();
+        for (int k = 0; k < 4; k++) {
+            rtbvh::Pair &rec = out[2 * j + (k >> 1)];
+            const int32_t link = (k & 1) ? rec.rlink : rec.llink;
+            if (link == rtbvh::kNoChild) continue;
+            rtbvh::Box b;
+            b.reset();
+            if (link < 0) {
+                const int ref = ~link, first = ref >> 3, count = ref & 7;
+                for (int t = first; t < first + count; t++) {
+                    const float *v = verts + 9 * (size_t)order[(size_t)t];
+                    for (int a = 0; a < 3; a++) {
+                        b.lo[a] = std::min(b.lo[a], std::min(v[a], std::min(v[3 + a], v[6 + a])));
+                        b.hi[a] = std::max(b.hi[a], std::max(v[a], std::max(v[3 + a], v[6 + a])));
+                    }
+                }
+            } else {
+                b = exact[(size_t)link / 2];
+            }
+            float *dst = (k & 1) ? rec.rbox : rec.lbox;
+            for (int a = 0; a < 3; a++) {
+                dst[a] = rtbvh::pad_down(b.lo[a], 2);
+                dst[3 + a] = rtbvh::pad_up(b.hi[a], 2);
+            }
+            exact[j].extend(b);
+        }
+    }
+    return out;
+}
 }  // namespace
 
 extern "C" {
@@ -356,6 +396,52 @@ int rt_bvh_selfcheck(const float *verts, int n, int n_rays, const float *o3, con
     if (getenv("RT_BVH_STATS") && n_rays > 0)
         fprintf(stderr, "bvh walk per ray: 4-wide %.2f nodes %.2f tris | 2-wide %.2f nodes %.2f tris | %zu quads records, %zu pairs, depths %d / %d\n",
                 sum_nodes[0] / n_rays, sum_tris[0] / n_rays, sum_nodes[1] / n_rays, sum_tris[1] / n_rays, r.quads.size(), r.pairs.size(), r.max_depth, r.pair_depth);
+    return 0;
+}
+
+// The refit's host twin: build the tree from build_verts (rtbvh::build), refit it to new_verts (same triangle count), then
+// check the result as rt_bvh_selfcheck checks a build.
+// out6: [records, records whose bytes differ from the builder's records of build_verts, structural errors of the refit
+//        records (as built and as padded for this call's ray origins), walk mismatches against exhaustive search over
+//        new_verts (4-wide walk, closest hit), rays walked, the refit tree's surface-area cost x 10^6]
+int rt_bvh_refit_check(const float *build_verts, const float *new_verts, int n, int n_rays, const float *o3, const float *d3,
+                       int64_t *out6) {
+    memset(out6, 0, 6 * sizeof(int64_t));
+    rtbvh::Result r = rtbvh::build(build_verts, n);
+    if (!r.ok || n <= 0) return 1;
+    rtbvh::Result rf = r;
+    rf.quads = refit_quads(r.quads, r.order, new_verts);
+    out6[0] = (int64_t)rf.quads.size();
+    for (size_t k = 0; k < rf.quads.size(); k++) out6[1] += memcmp(&rf.quads[k], &r.quads[k], sizeof(rtbvh::Pair)) != 0;
+    int max_leaf = 0;
+    const std::vector<rtbvh::Pair> padded = padded_quads(rf, n_rays, o3);
+    out6[2] = validate(rf, rf.quads, true, new_verts, n, max_leaf) + validate(rf, padded, true, new_verts, n, max_leaf);
+    const std::vector<Tri> tris = leaf_order_triangles(new_verts, rf, n);
+    for (int i = 0; i < n_rays; i++) {
+        V3 o{o3[3 * i], o3[3 * i + 1], o3[3 * i + 2]}, d{d3[3 * i], d3[3 * i + 1], d3[3 * i + 2]};
+        float bt = FLT_MAX, t;
+        int bb = -1;
+        for (int k = 0; k < n; k++)
+            if (tri_hit(tris[k], o, d, bt, t) && (!(t == bt && bb >= 0) || rf.order[k] > rf.order[bb])) { bt = t; bb = k; }
+        WalkResult w = walk_ray(padded, true, tris, rf.order, rf.stack_bound, 0, o, d, FLT_MAX, -1);
+        if (w.failed || w.best != bb || (bb >= 0 && w.t != bt)) out6[3]++;
+        out6[4]++;
+    }
+    double cost = 0.0;  // (the form of rtbvh::sah_cost over the 4-wide children, relative to the root's bounds)
+    rtbvh::Box root;
+    root.reset();
+    for (size_t k = 0; k < rf.quads.size(); k++)
+        for (int side = 0; side < 2; side++) {
+            const int32_t l = side ? rf.quads[k].rlink : rf.quads[k].llink;
+            if (l == rtbvh::kNoChild) continue;
+            const float *pb = side ? rf.quads[k].rbox : rf.quads[k].lbox;
+            rtbvh::Box b;
+            memcpy(b.lo, pb, 3 * sizeof(float));
+            memcpy(b.hi, pb + 3, 3 * sizeof(float));
+            cost += (double)b.half_area() * (l < 0 ? (double)((~l) & 7) : 1.0);
+            if (k < 2) root.extend(b);
+        }
+    out6[5] = (int64_t)llround(1e6 * cost / std::max((double)root.half_area(), 1e-30));
     return 0;
 }
 

@@ -2500,6 +2500,98 @@ __global__ void k_lbvh_emit(const float *__restrict__ verts, const unsigned long
     rec[15] = 0.f;
 }
 
+// ---- refit (rt_scene_update): new vertex positions for the same tree.  Topology, leaf order, materials and lights stay;
+// triangle records, boxes and the tables derived from the light triangles are recomputed on the scene's device.
+// Triangle records in leaf order with the expressions of rt_scene_create (this file is built with -ffp-contract=off, so a
+// multiplication and a subtraction are each rounded once, on the device as on the host: the same bits).
+__global__ void k_refit_tris(const float *__restrict__ verts, const int *__restrict__ order, int n, float4 *__restrict__ tris) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const float *q = verts + 9 * (size_t)order[k];
+    const float e1x = q[0] - q[3], e1y = q[1] - q[4], e1z = q[2] - q[5];
+    const float e2x = q[6] - q[0], e2y = q[7] - q[1], e2z = q[8] - q[2];
+    const float nx = e1y * e2z - e1z * e2y, ny = e1z * e2x - e1x * e2z, nz = e1x * e2y - e1y * e2x;
+    tris[3 * (size_t)k] = make_float4(q[0], q[1], q[2], e1x);
+    tris[3 * (size_t)k + 1] = make_float4(e1y, e1z, e2x, e2y);
+    tris[3 * (size_t)k + 2] = make_float4(e2z, nx, ny, nz);
+}
+// One level of the 4-wide tree (launched deepest level first, so a launch boundary orders every hand-off between levels).
+// A node's child boxes, EXACT: a leaf child's from the caller's vertices p0, p1, p2 (as rtbvh::build_binary), an inner
+// child's the union the deeper launch left in `exact`.  They are written into the node's two builder records padded by
+// 2 ulps -- once, on write, as rtbvh::build pads the exact unions -- and their union stays exact for the parent.  With the
+// vertices of creation the records are the builder's, bit for bit (min / max are exact; the padding erases the sign of a
+// zero).
+__global__ void k_refit_level(const float *__restrict__ verts, const int *__restrict__ order, const int *__restrict__ nodes,
+                              int count, rtbvh::Pair *__restrict__ recs, float *__restrict__ exact) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const int j = nodes[i];
+    float u[6] = {kFltMax, kFltMax, kFltMax, -kFltMax, -kFltMax, -kFltMax};
+    for (int k = 0; k < 4; k++) {
+        rtbvh::Pair &rec = recs[2 * (size_t)j + (k >> 1)];
+        const int32_t link = (k & 1) ? rec.rlink : rec.llink;
+        if (link == rtbvh::kNoChild) continue;  // (absent: keeps its all-+inf box)
+        float b[6] = {kFltMax, kFltMax, kFltMax, -kFltMax, -kFltMax, -kFltMax};
+        if (link < 0) {
+            const int ref = ~link, first = ref >> 3, cnt = ref & 7;
+            for (int t = first; t < first + cnt; t++) {
+                const float *v = verts + 9 * (size_t)order[t];
+                for (int a = 0; a < 3; a++) {
+                    b[a] = fminf(b[a], fminf(v[a], fminf(v[3 + a], v[6 + a])));
+                    b[3 + a] = fmaxf(b[3 + a], fmaxf(v[a], fmaxf(v[3 + a], v[6 + a])));
+                }
+            }
+        } else {
+            const float *c = exact + 6 * (size_t)(link >> 1);  // (inner links are record indices: 2 x node)
+            for (int a = 0; a < 6; a++) b[a] = c[a];
+        }
+        float *dst = (k & 1) ? rec.rbox : rec.lbox;
+        for (int a = 0; a < 3; a++) {
+            dst[a] = lbvh_pad(b[a], -1);
+            dst[3 + a] = lbvh_pad(b[3 + a], +1);
+            u[a] = fminf(u[a], b[a]);
+            u[3 + a] = fmaxf(u[3 + a], b[3 + a]);
+        }
+    }
+    for (int a = 0; a < 6; a++) exact[6 * (size_t)j + a] = u[a];
+}
+// The records as the kernels read them (upload_node_records): padded for ray origins within the radius (the double
+// arithmetic of rtbvh::pad_quads_for_origins) and laid out by plane, 128 bytes per node.  The radius is the one the
+// records were padded for, grown to the new bounds (rtbvh::quads_abs_bounds): those of the root's children, which contain
+// every box below them.  Node 0's thread reports it.
+__global__ void k_refit_emit(const rtbvh::Pair *__restrict__ recs, int n_nodes, float r0, float r1, float r2,
+                             float *__restrict__ out, float *__restrict__ radius_out) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n_nodes) return;
+    float m[3] = {0.f, 0.f, 0.f};
+    for (int k = 0; k < 4; k++) {
+        const rtbvh::Pair &p = recs[k >> 1];
+        if (((k & 1) ? p.rlink : p.llink) == rtbvh::kNoChild) continue;
+        const float *b = (k & 1) ? p.rbox : p.lbox;
+        for (int a = 0; a < 3; a++) m[a] = fmaxf(m[a], fmaxf(fabsf(b[a]), fabsf(b[3 + a])));
+    }
+    const float radius[3] = {fmaxf(r0, m[0] * 1.001f), fmaxf(r1, m[1] * 1.001f), fmaxf(r2, m[2] * 1.001f)};
+    if (j == 0)
+        for (int a = 0; a < 3; a++) radius_out[a] = radius[a];
+    const rtbvh::Pair &p0 = recs[2 * (size_t)j], &p1 = recs[2 * (size_t)j + 1];
+    const float *box[4] = {p0.lbox, p0.rbox, p1.lbox, p1.rbox};
+    const int32_t link[4] = {p0.llink, p0.rlink, p1.llink, p1.rlink};
+    float *r = out + 32 * (size_t)j;
+    for (int c = 0; c < 4; c++)
+        for (int a = 0; a < 3; a++) {
+            float lo = box[c][a], hi = box[c][3 + a];
+            if (link[c] != rtbvh::kNoChild) {
+                const double pad = (double)radius[a] * 0x1p-23;  // (= ldexp(radius, -23): exact)
+                lo = nextafterf((float)((double)lo - pad), -kFltMax);
+                hi = nextafterf((float)((double)hi + pad), kFltMax);
+            }
+            r[8 * a + c] = lo;
+            r[8 * a + 4 + c] = hi;
+        }
+    for (int c = 0; c < 4; c++) r[24 + c] = __int_as_float(link[c]);
+    r[28] = r[29] = r[30] = r[31] = 0.f;
+}
+
 // ============================================================================ host side
 struct rt_scene {
     int device = 0;
@@ -2542,6 +2634,17 @@ struct rt_scene {
     mutable int ref_nodes_count = 0, ref_depth = 0;
     mutable bool ref_root_leaf = true;
     mutable double build_seconds_ref = 0.0;  // host time of the reference-tree build + upload (one-off, first render that needs it)
+    // rt_scene_update (4-wide only): the tree's nodes grouped by level, deepest level first (refit_level_end[l] = end of level
+    // l's span), the builder records on the device (links fixed at creation, boxes refit), the exact box of every node (scratch
+    // between the level launches) and the radius the refit padded for -- all set up by the first update
+    std::vector<int> refit_level_end;
+    int *d_refit_nodes = nullptr;
+    rtbvh::Pair *d_refit_recs = nullptr;
+    float *d_refit_exact = nullptr;
+    float *d_refit_radius = nullptr;
+    int64_t refits = 0;
+    double refit_seconds = 0.0;                 // device time of the last refit (HIP events)
+    double sah_build = 0.0, sah_now = 0.0;      // surface-area cost of the 4-wide tree at build time / now
     rt_scene() = default;
     rt_scene(const rt_scene &) = delete;
     rt_scene &operator=(const rt_scene &) = delete;
@@ -2559,6 +2662,10 @@ struct rt_scene {
         (void)hipFree(d_ref_prims);
         (void)hipFree(d_ref_leaf_of);
         (void)hipFree(d_ref_parent);
+        (void)hipFree(d_refit_nodes);
+        (void)hipFree(d_refit_recs);
+        (void)hipFree(d_refit_exact);
+        (void)hipFree(d_refit_radius);
     }
     DScene dev() const {
         DScene s;
@@ -2797,8 +2904,10 @@ bool validate_quads(const std::vector<rtbvh::Pair> &quads, int n_tris) {
 // RT_FLAG_REFERENCE_WALK: build the reference's tree from the caller's triangles, check its structure (a malformed tree
 // would hang the walk: every node reached exactly once, children adjacent, every primitive position in exactly one
 // leaf, depth within the walk's private stack) and upload it.  Once per scene, on the scene's device.
-int ensure_ref_tree(const rt_scene *scene) {
+// `built` (may be null): whether THIS call built the tree, decided under the lock (two first renders may race to it).
+int ensure_ref_tree(const rt_scene *scene, bool *built = nullptr) {
     std::lock_guard<std::mutex> lock(scene->ref_mutex);
+    if (built) *built = false;
     if (scene->ref_ready) return 0;
     const auto t_begin = std::chrono::steady_clock::now();
     const int n = scene->n_tris;
@@ -2871,6 +2980,7 @@ int ensure_ref_tree(const rt_scene *scene) {
     scene->ref_depth = t.depth;
     scene->build_seconds_ref = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
     scene->ref_ready = true;
+    if (built) *built = true;
     return 0;
 }
 
@@ -2943,6 +3053,166 @@ int build_lbvh_device(const float *verts_host, int n, std::vector<rtbvh::Pair> &
     HIP_TRY(hipMemcpy(pairs.data(), d_pairs, sizeof(rtbvh::Pair) * (size_t)(n - 1), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(order.data(), d_order, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(&depth, d_depth, sizeof(int), hipMemcpyDeviceToHost));  // depth of the root
+    return 0;
+}
+
+// Surface-area cost of the 4-wide tree (the form of rtbvh::sah_cost): child box areas weighted by the triangles of a leaf
+// child or one node step, relative to the area of the root's bounds.  Advisory (rt_scene_refit_info).
+double quads_sah(const std::vector<rtbvh::Pair> &quads) {
+    auto half_area = [](const float *b) {
+        const double e0 = (double)b[3] - b[0], e1 = (double)b[4] - b[1], e2 = (double)b[5] - b[2];
+        return (e0 + e1) * e2 + e0 * e1;
+    };
+    double cost = 0.0, root[6] = {DBL_MAX, DBL_MAX, DBL_MAX, -DBL_MAX, -DBL_MAX, -DBL_MAX};
+    for (size_t r = 0; r < quads.size(); r++)
+        for (int side = 0; side < 2; side++) {
+            const int32_t l = side ? quads[r].rlink : quads[r].llink;
+            if (l == rtbvh::kNoChild) continue;
+            const float *b = side ? quads[r].rbox : quads[r].lbox;
+            cost += half_area(b) * (l < 0 ? (double)((~l) & 7) : 1.0);
+            if (r < 2)
+                for (int a = 0; a < 3; a++) {
+                    root[a] = std::min(root[a], (double)b[a]);
+                    root[3 + a] = std::max(root[3 + a], (double)b[3 + a]);
+                }
+        }
+    const double e0 = root[3] - root[0], e1 = root[4] - root[1], e2 = root[5] - root[2];
+    return quads.size() < 2 || !(e0 >= 0.0) ? 0.0 : cost / std::max((e0 + e1) * e2 + e0 * e1, 1e-30);
+}
+
+// rt_scene_update / rt_scene_update_device: refit the 4-wide tree on the scene's device (k_refit_*), then bring the host
+// state along -- the builder records ensure_origin_radius re-pads from, the radius they are padded for, the triangle copy the
+// reference's tree and the replicas are made from.  `verts` is a host array or (device_ptr) a buffer on the scene's device.
+int scene_update_impl(rt_scene *sc, const float *verts, int n_tris, bool device_ptr, hipStream_t st, const char *what) {
+    const std::string w(what);
+    if (!sc || !verts) return fail(w + ": null argument");
+    if (n_tris != sc->n_tris) return fail(w + ": " + std::to_string(n_tris) + " triangles, the scene was created with " + std::to_string(sc->n_tris));
+    if (!sc->wide) return fail(w + ": the scene uses the 2-wide experiment format (RT_BVH_WIDE=0), which cannot be refit");
+    int saved = 0;
+    HIP_TRY(hipGetDevice(&saved));
+    if (device_ptr) {
+        hipPointerAttribute_t attr;
+        if (hipPointerGetAttributes(&attr, verts) != hipSuccess || (attr.type != hipMemoryTypeDevice && !attr.isManaged) ||
+            attr.device != sc->device) {
+            (void)hipGetLastError();  // (the failed query leaves its error behind)
+            return fail(w + ": d_tri_p0p1p2 is not device memory on the scene's device " + std::to_string(sc->device));
+        }
+    }
+    if (saved != sc->device) HIP_TRY(hipSetDevice(sc->device));
+    struct Restore {
+        int dev, was;
+        ~Restore() { if (dev != was) (void)hipSetDevice(was); }
+    } restore{sc->device, saved};
+    const int n = n_tris;
+    std::lock_guard<std::mutex> pad_lock(sc->pad_mutex);  // (h_quads and origin_radius change)
+    const int n_nodes = sc->n_nodes / 2;                  // 4-wide nodes: two records each
+    if (n > 0 && !sc->d_refit_nodes) {
+        // the levels of the tree, fixed at creation: breadth-first from the root, then deepest level first
+        std::vector<int> depth((size_t)n_nodes, -1), queue{0};
+        depth[0] = 0;
+        for (size_t h = 0; h < queue.size(); h++)
+            for (int k = 0; k < 4; k++) {
+                const rtbvh::Pair &p = sc->h_quads[2 * (size_t)queue[h] + (k >> 1)];
+                const int32_t l = (k & 1) ? p.rlink : p.llink;
+                if (l >= 0) {
+                    depth[(size_t)l / 2] = depth[(size_t)queue[h]] + 1;
+                    queue.push_back(l / 2);
+                }
+            }
+        if ((int)queue.size() != n_nodes) return fail(w + ": the tree does not reach every node");
+        const int levels = depth[(size_t)queue.back()] + 1;
+        std::vector<int> nodes;
+        nodes.reserve((size_t)n_nodes);
+        std::vector<int> level_end;
+        for (int d = levels - 1; d >= 0; d--) {
+            for (int j : queue)
+                if (depth[(size_t)j] == d) nodes.push_back(j);
+            level_end.push_back((int)nodes.size());
+        }
+        int *dn = nullptr;
+        rtbvh::Pair *dr = nullptr;
+        float *de = nullptr, *drad = nullptr;
+        if (hipMalloc((void **)&dn, sizeof(int) * nodes.size()) != hipSuccess ||
+            hipMalloc((void **)&dr, sizeof(rtbvh::Pair) * sc->h_quads.size()) != hipSuccess ||
+            hipMalloc((void **)&de, sizeof(float) * 6 * (size_t)n_nodes) != hipSuccess ||
+            hipMalloc((void **)&drad, sizeof(float) * 3) != hipSuccess ||
+            hipMemcpy(dn, nodes.data(), sizeof(int) * nodes.size(), hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(dr, sc->h_quads.data(), sizeof(rtbvh::Pair) * sc->h_quads.size(), hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(dn);
+            (void)hipFree(dr);
+            (void)hipFree(de);
+            (void)hipFree(drad);
+            return fail(w + ": device allocation or upload failed");
+        }
+        sc->d_refit_nodes = dn;
+        sc->d_refit_recs = dr;
+        sc->d_refit_exact = de;
+        sc->d_refit_radius = drad;
+        sc->refit_level_end = level_end;
+        sc->sah_build = sc->sah_now = quads_sah(sc->h_quads);
+    }
+    DevScope tmp;
+    std::vector<float> h_new;
+    const float *d_verts = verts;
+    if (n > 0 && !device_ptr) {
+        float *d_v = nullptr;
+        if (tmp.alloc(d_v, 9 * (size_t)n)) return 1;
+        HIP_TRY(hipMemcpyAsync(d_v, verts, sizeof(float) * 9 * (size_t)n, hipMemcpyHostToDevice, st));
+        d_verts = d_v;
+    }
+    float radius[3] = {sc->origin_radius[0], sc->origin_radius[1], sc->origin_radius[2]};
+    double seconds = 0.0;
+    if (n > 0) {
+        HIP_TRY(hipEventCreate(&tmp.e0));
+        HIP_TRY(hipEventCreate(&tmp.e1));
+        HIP_TRY(hipEventRecord(tmp.e0, st));
+        const dim3 blk(256);
+        hipLaunchKernelGGL(k_refit_tris, dim3((n + 255) / 256), blk, 0, st, d_verts, sc->d_order, n, sc->d_tris);
+        hipLaunchKernelGGL(k_build_tri_shade, dim3((n + 255) / 256), blk, 0, st, sc->d_tris, sc->d_tri_info, n, sc->d_tri_shade);
+        const int nt = std::max(std::max(sc->n_mats, sc->n_lights), 1);
+        hipLaunchKernelGGL(k_build_tables, dim3((nt + 63) / 64), dim3(64), 0, st, sc->d_mats, sc->n_mats, sc->d_lights, sc->n_lights,
+                           sc->d_tris, sc->d_tables);
+        for (size_t l = 0; l < sc->refit_level_end.size(); l++) {
+            const int begin = l ? sc->refit_level_end[l - 1] : 0, count = sc->refit_level_end[l] - begin;
+            hipLaunchKernelGGL(k_refit_level, dim3((count + 255) / 256), blk, 0, st, d_verts, sc->d_order, sc->d_refit_nodes + begin,
+                               count, sc->d_refit_recs, sc->d_refit_exact);
+        }
+        hipLaunchKernelGGL(k_refit_emit, dim3((n_nodes + 255) / 256), blk, 0, st, sc->d_refit_recs, n_nodes, radius[0], radius[1],
+                           radius[2], (float *)sc->d_nodes, sc->d_refit_radius);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(tmp.e1, st));
+        HIP_TRY(hipEventSynchronize(tmp.e1));
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, tmp.e0, tmp.e1));
+        seconds = ms * 1e-3;
+        // the host's view of the new geometry: the unpadded records (ensure_origin_radius re-pads from them), the radius the
+        // device copy is padded for, the caller's triangles (the reference's tree and the replicas are made from them)
+        HIP_TRY(hipMemcpy(sc->h_quads.data(), sc->d_refit_recs, sizeof(rtbvh::Pair) * sc->h_quads.size(), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(radius, sc->d_refit_radius, sizeof(float) * 3, hipMemcpyDeviceToHost));
+        if (device_ptr) HIP_TRY(hipMemcpy(sc->h_tri9.data(), verts, sizeof(float) * 9 * (size_t)n, hipMemcpyDeviceToHost));
+        else memcpy(sc->h_tri9.data(), verts, sizeof(float) * 9 * (size_t)n);
+        for (int a = 0; a < 3; a++) sc->origin_radius[a] = radius[a];
+        sc->sah_now = quads_sah(sc->h_quads);
+    }
+    sc->refit_seconds = seconds;
+    sc->refits++;
+    {   // the reference's tree is a function of the triangles: the next render that needs it rebuilds it from h_tri9
+        std::lock_guard<std::mutex> lock(sc->ref_mutex);
+        (void)hipFree(sc->d_ref_nodes);
+        (void)hipFree(sc->d_ref_prims);
+        (void)hipFree(sc->d_ref_leaf_of);
+        (void)hipFree(sc->d_ref_parent);
+        sc->d_ref_nodes = nullptr;
+        sc->d_ref_prims = sc->d_ref_leaf_of = sc->d_ref_parent = nullptr;
+        sc->ref_nodes_count = sc->ref_depth = 0;
+        sc->ref_root_leaf = true;
+        sc->ref_ready = false;
+    }
+    {   // replicas on other devices (rt_render_multi) hold the old geometry: dropped, recreated from h_tri9 on next use
+        std::lock_guard<std::mutex> lock(sc->replica_mutex);
+        for (rt_scene *r : sc->replicas) delete r;
+        sc->replicas.clear();
+    }
     return 0;
 }
 
@@ -3186,9 +3456,9 @@ int render_shard_impl(const rt_scene *scene, const rt_camera *camera, int width,
     if (dev != scene->device) return fail("rt_render_shard: scene was created on another device");
     double ref_tree_seconds = 0.0;
     if (literal || verify) {
-        const bool was_ready = scene->ref_ready;
-        if (ensure_ref_tree(scene)) return 1;
-        if (!was_ready) ref_tree_seconds = scene->build_seconds_ref;  // (this call paid for it)
+        bool built = false;
+        if (ensure_ref_tree(scene, &built)) return 1;
+        if (built) ref_tree_seconds = scene->build_seconds_ref;  // (this call paid for it)
     }
     const int n = per_sample ? kW : kW / shard_count;
     const int slot_lo = per_sample ? 0 : shard_index * n;
@@ -3869,6 +4139,22 @@ int rt_scene_build_info(const rt_scene *scene, int *builder, double *seconds) {
     if (!scene || !builder || !seconds) return fail("rt_scene_build_info: null argument");
     *builder = scene->builder;
     *seconds = scene->build_seconds;
+    return 0;
+}
+
+int rt_scene_update(rt_scene *scene, const float *tri_p0p1p2, int n_tris) {
+    return scene_update_impl(scene, tri_p0p1p2, n_tris, false, nullptr, "rt_scene_update");
+}
+
+int rt_scene_update_device(rt_scene *scene, const float *d_tri_p0p1p2, int n_tris, void *stream) {
+    return scene_update_impl(scene, d_tri_p0p1p2, n_tris, true, (hipStream_t)stream, "rt_scene_update_device");
+}
+
+int rt_scene_refit_info(const rt_scene *scene, int64_t *refits, double *seconds_last, double *sah_ratio) {
+    if (!scene || !refits || !seconds_last || !sah_ratio) return fail("rt_scene_refit_info: null argument");
+    *refits = scene->refits;
+    *seconds_last = scene->refit_seconds;
+    *sah_ratio = scene->sah_build > 0.0 ? scene->sah_now / scene->sah_build : 1.0;
     return 0;
 }
 
