@@ -331,6 +331,27 @@ inline void update(Scene &scene, const std::vector<Triangle> &triangles) {
     rtcuda_detail::check(rt_scene_update(sh->h, verts.data(), n), "update");
 }
 
+// The same with a new tree: a scene already realised on the device gets a BVH built there by the device builder
+// (rt_scene_rebuild) instead of a refit -- for when rt_scene_refit_info's sah_ratio has grown after many update()s.
+inline void rebuild(Scene &scene, const std::vector<Triangle> &triangles) {
+    Bvh &bvh = scene.bvh;
+    if ((int)triangles.size() != bvh.num_primitives)
+        throw std::runtime_error("rebuild: " + std::to_string(triangles.size()) + " triangles, the Bvh holds " + std::to_string(bvh.num_primitives));
+    std::copy(triangles.begin(), triangles.end(), bvh.triangles.begin());
+    rtcuda_detail::SceneHandle *sh = bvh.handle.get();
+    if (!sh || !sh->h) return;
+    const int n = bvh.num_primitives;
+    std::vector<float> verts((size_t)9 * (n > 0 ? n : 1));
+    for (int i = 0; i < n; i++) {
+        const Triangle &t = bvh.triangles[(size_t)i];
+        float *q = &verts[9 * (size_t)i];
+        q[0] = t.p0.x; q[1] = t.p0.y; q[2] = t.p0.z;
+        q[3] = t.p1_.x; q[4] = t.p1_.y; q[5] = t.p1_.z;
+        q[6] = t.p2_.x; q[7] = t.p2_.y; q[8] = t.p2_.z;
+    }
+    rtcuda_detail::check(rt_scene_rebuild(sh->h, verts.data(), n), "rebuild");
+}
+
 // A driver that must keep the reference's exact call (main.cu:173) can still reach several GPUs: RTCUDA_DEVICES="0,1,2,3" in
 // the environment sends the seven-argument render() below through the multi-device path (rt_render_multi).
 inline std::vector<int> devices_from_env() {

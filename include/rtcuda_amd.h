@@ -137,11 +137,22 @@ typedef struct rt_stats {
 int rt_scene_create(const float *tri_p0p1p2, int n_tris, const int32_t *tri_material,
                     const int32_t *tri_light, const rt_material *materials, int n_materials,
                     const rt_light *lights, int n_lights, rt_scene **out_scene);
+/* rt_scene_create with options.  RT_SCENE_DEVICE_BVH: the BVH is built on the current device by PLOC (parallel locally-
+ * ordered clustering over Morton-ordered triangles, surface-area cost model for the leaves, collapsed to the same 4-wide
+ * records) in milliseconds instead of the host SAH build's tenths of a second; traversal quality is close to the host
+ * tree's.  The image is the same, bit for bit, in every mode.  rt_render_multi replicas of such a scene are built on their
+ * own device the same way.  Fails (instead of falling back) if the tree does not fit the traversal stack, or with
+ * RT_BVH_WIDE=0.  scene_flags 0 is rt_scene_create. */
+#define RT_SCENE_DEVICE_BVH 1u
+int rt_scene_create_flags(const float *tri_p0p1p2, int n_tris, const int32_t *tri_material,
+                          const int32_t *tri_light, const rt_material *materials, int n_materials,
+                          const rt_light *lights, int n_lights, uint32_t scene_flags, rt_scene **out_scene);
 void rt_scene_destroy(rt_scene *scene);
 
 /* out[0]=node records, out[1]=triangles, out[2]=max depth, out[3]=leaves */
 int rt_scene_info(const rt_scene *scene, int64_t out[4]);
-/* Which BVH builder made the scene (0 = host SAH, the default; 1 = device LBVH, RT_BVH_BUILDER=lbvh) and
+/* Which BVH builder made the scene (0 = host SAH, the default; 1 = device LBVH, RT_BVH_BUILDER=lbvh; 2 = device PLOC,
+ * RT_SCENE_DEVICE_BVH or rt_scene_rebuild) and
  * how long the build took (host wall clock / HIP events).  The reference times "Top-down constructing BVH"
  * on stdout (bvh.cuh:106-201). */
 int rt_scene_build_info(const rt_scene *scene, int *builder, double *seconds);
@@ -160,8 +171,22 @@ int rt_scene_update(rt_scene *scene, const float *tri_p0p1p2, int n_tris);
 /* Same, from a DEVICE buffer on the scene's device, ordered on `stream` (NULL = default stream), synchronous on return. */
 int rt_scene_update_device(rt_scene *scene, const float *d_tri_p0p1p2, int n_tris, void *stream);
 /* refits since creation, device seconds of the last refit (HIP events), and the tree's surface-area cost relative to its
- * value at build time (advisory: when it grows, create the scene anew) */
+ * value at build time (advisory: when it grows, rebuild the tree with rt_scene_rebuild) */
 int rt_scene_refit_info(const rt_scene *scene, int64_t *refits, double *seconds_last, double *sah_ratio);
+/* A new tree for the scene, built on its device by the RT_SCENE_DEVICE_BVH builder: from the scene's current vertices
+ * (tri_p0p1p2 NULL) or from new ones (as rt_scene_update takes them).  When to call it: a refit keeps the tree's topology,
+ * so as vertices move its quality decays -- rebuild when rt_scene_refit_info's sah_ratio has grown (say past 1.2); the
+ * ratio reads 1.0 again afterwards.  Preconditions are rt_scene_update's: the creation count, a 4-wide scene, no render in
+ * flight.  The image is unchanged, bit for bit, in every mode: it is that of a scene created from the same vertices.  The
+ * leaf order changes; triangle, shading, light and table records are re-emitted on the device.  The reference's tree
+ * (RT_FLAG_REFERENCE_WALK, default mode) is kept when the vertices did not change and rebuilt by the next render that needs
+ * it when they did; rt_render_multi replicas are dropped.  rt_scene_build_info reports builder 2 and the device build time.
+ * Errors (null scene, another count, a 2-wide RT_BVH_WIDE=0 scene, a tree deeper than the traversal stack) leave the scene
+ * rendering as before. */
+int rt_scene_rebuild(rt_scene *scene, const float *tri_p0p1p2, int n_tris);
+/* Same, from a DEVICE buffer on the scene's device (or NULL: the current vertices), ordered on `stream` (NULL = default
+ * stream), synchronous on return. */
+int rt_scene_rebuild_device(rt_scene *scene, const float *d_tri_p0p1p2, int n_tris, void *stream);
 
 /* Replaces Camera::Camera(lookfrom, lookat, up, vfov_deg, aspect) (camera.cuh:15-29). Host only. */
 int rt_camera_make(const float lookfrom[3], const float lookat[3], const float up[3], float vfov_deg,

@@ -65,6 +65,13 @@ enum {
 int rt_split_probe(const rt_scene *scene, const rt_camera *camera, int width, int height, int num_samples,
                    int max_bounces, uint64_t seed, int64_t target_rays, double *out, int n_out);
 
+/* A scene's 4-wide tree as the builder left it: the unpadded node records (two 64-byte records per node, children 0, 1 |
+ * 2, 3, as rt_bvh.h's `quads`) and the leaf order (leaf-order index -> caller's triangle index).  out2 = [records,
+ * triangles]; the records and the order are copied when the buffers are given and large enough.  For comparing the device
+ * builder (RT_SCENE_DEVICE_BVH, rt_scene_rebuild) with its host twin (rt_host_check.cpp).  4-wide scenes only. */
+int rt_scene_tree_copy(const rt_scene *scene, void *records, int64_t cap_records, int32_t *order, int64_t cap_order,
+                       int64_t *out2);
+
 #ifdef __cplusplus
 }
 #endif

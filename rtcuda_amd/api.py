@@ -25,17 +25,19 @@ FLAG_TIME_KERNELS = 1
 FLAG_DETERMINISTIC = 2
 FLAG_RNG_PER_SAMPLE = 4  # NOT the reference's random numbers (see include/rtcuda_amd.h): partition-invariant streams
 FLAG_REFERENCE_WALK = 8  # cross-check mode: every ray walks the reference's own tree literally (slow; the default kernels give the same image)
+SCENE_DEVICE_BVH = 1     # rt_scene_create_flags: build the BVH on the device (PLOC)
 FLAG_WATERTIGHT = 16     # the triangle-list definition (no hit lost to a box test, ties by caller index) instead of the reference's
 
 EXPORTS = [
     "rt_scene_create", "rt_scene_destroy", "rt_scene_info", "rt_scene_build_info", "rt_scene_update", "rt_scene_update_device",
-    "rt_scene_refit_info", "rt_camera_make", "rt_render", "rt_render_multi",
+    "rt_scene_refit_info", "rt_scene_create_flags", "rt_scene_rebuild", "rt_scene_rebuild_device", "rt_camera_make", "rt_render", "rt_render_multi",
     "rt_render_shard", "rt_render_shard_fixed", "rt_post_process", "rt_post_process_fixed", "rt_trace_closest", "rt_trace_any",
     "rt_trace_closest_flags", "rt_trace_any_flags", "rt_xorwow_states", "rt_shutdown", "rt_peer_access_log", "rt_last_error", "rt_version", "rt_build_id",
 ]
 # the lab (include/rtcuda_amd_tools.h, librtcuda_amd_tools.so): measurement tools, not part of the drop-in C-ABI
 TOOLS_LIB_PATH = os.path.join(_PKG, "librtcuda_amd_tools.so")
-TOOLS_EXPORTS = ["rt_measure_copy_bandwidth", "rt_calibrate_valu", "rt_calibrate_valu_packed", "rt_probe_issue", "rt_split_probe"]
+TOOLS_EXPORTS = ["rt_measure_copy_bandwidth", "rt_calibrate_valu", "rt_calibrate_valu_packed", "rt_probe_issue", "rt_split_probe",
+                 "rt_scene_tree_copy"]
 
 
 class RtError(RuntimeError):
@@ -126,6 +128,9 @@ def _bind(L):
     L.rt_scene_update_device.argtypes = [vp, vp, ci, vp]
     L.rt_scene_refit_info.argtypes = [vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_double),
                                       ctypes.POINTER(ctypes.c_double)]
+    L.rt_scene_create_flags.argtypes = [vp, ci, vp, vp, vp, ci, vp, ci, ctypes.c_uint32, ctypes.POINTER(vp)]
+    L.rt_scene_rebuild.argtypes = [vp, vp, ci]
+    L.rt_scene_rebuild_device.argtypes = [vp, vp, ci, vp]
     L.rt_camera_make.argtypes = [vp, vp, vp, cf, cf, vp]
     L.rt_render.argtypes = [vp, vp, ci, ci, ci, ci, ctypes.c_uint64, ctypes.c_uint32, vp, ctypes.POINTER(RtStats)]
     L.rt_render_multi.argtypes = [vp, vp, ci, ci, ci, ci, ctypes.c_uint64, ctypes.c_uint32, vp, ci, vp, ctypes.POINTER(RtStats)]
@@ -163,6 +168,7 @@ def tools_lib():
     L.rt_calibrate_valu_packed.argtypes = [ci, ci, ci, ctypes.POINTER(ctypes.c_double)]
     L.rt_probe_issue.argtypes = [ci, ci, ci, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
     L.rt_split_probe.argtypes = [vp, vp, ci, ci, ci, ci, ctypes.c_uint64, ctypes.c_int64, vp, ci]
+    L.rt_scene_tree_copy.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_int64, vp]
     _tools = L
     return L
 
@@ -203,9 +209,10 @@ def make_camera(lookfrom=(0.5, 0.5, 1.5), lookat=(0.5, 0.5, 0.0), up=(0.0, 1.0, 
 class Scene:
     """Device-resident scene (triangles, materials, lights, BVH) on the current HIP device."""
 
-    def __init__(self, arrays: SceneArrays, library=None):
+    def __init__(self, arrays: SceneArrays, library=None, device_bvh: bool = False):
         """`library`: the loaded library that owns the scene -- the product (default) or `tools_lib()`, whose private copy of
-        the product's entry points is what rt_split_probe works on."""
+        the product's entry points is what rt_split_probe works on.  `device_bvh`: build the BVH on the device
+        (RT_SCENE_DEVICE_BVH, the PLOC builder) instead of the host SAH builder; the image is the same."""
         L = self.L = library or lib()
         self.arrays = arrays
         tris = np.ascontiguousarray(arrays.tris, np.float32)
@@ -215,8 +222,9 @@ class Scene:
         lights = np.ascontiguousarray(arrays.lights)
         assert mats.dtype.itemsize == 20 and lights.dtype.itemsize == 32
         h = ctypes.c_void_p()
-        _check(L.rt_scene_create(_p(tris), tris.shape[0], _p(tm), _p(tl), _p(mats), mats.shape[0], _p(lights),
-                                 lights.shape[0], ctypes.byref(h)), "rt_scene_create", L)
+        _check(L.rt_scene_create_flags(_p(tris), tris.shape[0], _p(tm), _p(tl), _p(mats), mats.shape[0], _p(lights),
+                                       lights.shape[0], SCENE_DEVICE_BVH if device_bvh else 0, ctypes.byref(h)),
+               "rt_scene_create", L)
         self.h = h
 
     def close(self):
@@ -236,7 +244,7 @@ class Scene:
         b, sec = ctypes.c_int(0), ctypes.c_double(0.0)
         _check(self.L.rt_scene_build_info(self.h, ctypes.byref(b), ctypes.byref(sec)), "rt_scene_build_info", self.L)
         return {"pairs": int(out[0]), "tris": int(out[1]), "max_depth": int(out[2]), "leaves": int(out[3]),
-                "builder": "lbvh" if b.value else "sah", "build_seconds": sec.value}
+                "builder": {0: "sah", 1: "lbvh", 2: "ploc"}.get(b.value, str(b.value)), "build_seconds": sec.value}
 
     # ---- moving geometry: new vertex positions, same triangles, materials and lights (rt_scene_update)
     def update(self, tris) -> None:
@@ -251,6 +259,24 @@ class Scene:
         n = self.arrays.n_tris if n_tris is None else int(n_tris)
         _check(self.L.rt_scene_update_device(self.h, ctypes.c_void_p(ptr), n, ctypes.c_void_p(stream)),
                "rt_scene_update_device", self.L)
+
+    # ---- a new tree on the device when the refit one has degraded (rt_scene_rebuild)
+    def rebuild(self, tris=None) -> None:
+        """A new BVH built on the device (the PLOC builder) from the current vertices (tris None) or from new ones (as
+        update() takes them).  Call it when refit_info()["sah_ratio"] has grown.  Renders afterwards are bit-equal to those
+        of a scene created from the same vertices."""
+        if tris is None:
+            _check(self.L.rt_scene_rebuild(self.h, None, self.arrays.n_tris), "rt_scene_rebuild", self.L)
+            return
+        tris = np.ascontiguousarray(tris, np.float32).reshape(-1, 9)
+        _check(self.L.rt_scene_rebuild(self.h, _p(tris), tris.shape[0]), "rt_scene_rebuild", self.L)
+
+    def rebuild_device(self, ptr: int, stream: int = 0, n_tris: int = None) -> None:
+        """The same from a DEVICE buffer of n_tris x 9 float32 on the scene's device (e.g. ``tensor.data_ptr()``; 0 = the
+        current vertices), ordered on ``stream`` (0 = default stream; synchronous on return)."""
+        n = self.arrays.n_tris if n_tris is None else int(n_tris)
+        _check(self.L.rt_scene_rebuild_device(self.h, ctypes.c_void_p(ptr or None), n, ctypes.c_void_p(stream or None)),
+               "rt_scene_rebuild_device", self.L)
 
     def refit_info(self) -> dict:
         """Refits since creation, device seconds of the last one, and the tree's surface-area cost relative to build time."""

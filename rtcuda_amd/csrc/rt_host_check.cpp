@@ -8,6 +8,8 @@
 //     with an exhaustive search.  A malformed tree would hang or fault the GPU; this is where it is caught first.
 //   * rt_bvh_refit_check  the host twin of the device refit (rt_scene_update): the builder's records with new vertices,
 //     checked as above (bit-equal to the builder's with the creation vertices; structure and walk with moved ones).
+//   * rt_ploc_build / rt_ploc_check  the host twin of the device PLOC builder (rt_scene_rebuild, RT_SCENE_DEVICE_BVH):
+//     its records and leaf order (bit-equal to the device's), checked as above, with its surface-area cost next to rtbvh::build's.
 //   * rt_hostwalk_*     the same walk for arbitrary rays (closest hit / any hit), with work counters: the traversal
 //     audit (tests/test_traversal_audit.py) replays the rays of an oracle render through it.
 #include <cfloat>
@@ -19,6 +21,7 @@
 #include <vector>
 
 #include "rt_bvh.h"
+#include "rt_ploc.h"
 #include "rt_ref_tree.h"
 
 namespace {
@@ -323,6 +326,184 @@ std::vector<rtbvh::Pair> refit_quads(const std::vector<rtbvh::Pair> &quads, cons
     }
     return out;
 }
+
+// Surface-area cost of a 4-wide tree, relative to the area of the root's bounds: quads_sah in rtcuda_amd.hip (double sums
+// over the records' padded boxes, a leaf child weighted by its triangles, an inner child by one node step)
+double quads_sah_host(const std::vector<rtbvh::Pair> &quads) {
+    auto half_area = [](const float *b) {
+        const double e0 = (double)b[3] - b[0], e1 = (double)b[4] - b[1], e2 = (double)b[5] - b[2];
+        return (e0 + e1) * e2 + e0 * e1;
+    };
+    double cost = 0.0, root[6] = {DBL_MAX, DBL_MAX, DBL_MAX, -DBL_MAX, -DBL_MAX, -DBL_MAX};
+    for (size_t k = 0; k < quads.size(); k++)
+        for (int side = 0; side < 2; side++) {
+            const int32_t l = side ? quads[k].rlink : quads[k].llink;
+            if (l == rtbvh::kNoChild) continue;
+            const float *b = side ? quads[k].rbox : quads[k].lbox;
+            cost += half_area(b) * (l < 0 ? (double)((~l) & 7) : 1.0);
+            if (k < 2)
+                for (int a = 0; a < 3; a++) {
+                    root[a] = std::min(root[a], (double)b[a]);
+                    root[3 + a] = std::max(root[3 + a], (double)b[3 + a]);
+                }
+        }
+    const double e0 = root[3] - root[0], e1 = root[4] - root[1], e2 = root[5] - root[2];
+    return quads.size() < 2 || !(e0 >= 0.0) ? 0.0 : cost / std::max((e0 + e1) * e2 + e0 * e1, 1e-30);
+}
+
+// ---- host twin of the device PLOC builder (k_ploc_* in rtcuda_amd.hip): the same keys, nearest neighbours, merges, leaves
+// and 4-wide collapse, one after the other, with rt_ploc.h's expressions -- the device's records and leaf order, bit for bit.
+struct PlocHostNodes {
+    int n = 0;
+    std::vector<float> boxes;       // 6 per node, exact
+    std::vector<int> lft, rgt, cnt;  // triangle nodes: lft = -1, rgt = original index
+    std::vector<float> cost;
+    std::vector<char> leaf;
+    bool is_leaf(int i) const { return leaf[(size_t)i] != 0; }
+    bool is_tri(int i) const { return i < n; }
+    int tri(int i) const { return rgt[(size_t)i]; }
+    int left(int i) const { return lft[(size_t)i]; }
+    int right(int i) const { return rgt[(size_t)i]; }
+    int count(int i) const { return cnt[(size_t)i]; }
+    const float *box(int i) const { return &boxes[6 * (size_t)i]; }
+};
+struct PlocTwin {
+    rtbvh::Result r;
+    int iterations = 0;
+    bool ok = false;
+};
+PlocTwin ploc_build(const float *verts, int n) {
+    PlocTwin out;
+    rtbvh::Result &res = out.r;
+    if (n <= 0) {
+        res = rtbvh::build(verts, 0);
+        out.ok = true;
+        return out;
+    }
+    uint32_t lo_b[3] = {~0u, ~0u, ~0u}, hi_b[3] = {0u, 0u, 0u};
+    for (int i = 0; i < n; i++) {
+        float b[6];
+        rtploc::tri_box(verts + 9 * (size_t)i, b);
+        for (int a = 0; a < 3; a++) {
+            lo_b[a] = std::min(lo_b[a], rtploc::ordered_bits(rtploc::centroid(b, a)));
+            hi_b[a] = std::max(hi_b[a], rtploc::ordered_bits(rtploc::centroid(b, a)));
+        }
+    }
+    float lo[3], s[3];
+    for (int a = 0; a < 3; a++) {
+        lo[a] = rtploc::from_ordered_bits(lo_b[a]);
+        s[a] = rtploc::quant_scale(lo[a], rtploc::from_ordered_bits(hi_b[a]));
+    }
+    std::vector<uint64_t> keys((size_t)n);
+    for (int i = 0; i < n; i++) keys[(size_t)i] = rtploc::key(verts + 9 * (size_t)i, i, lo, s);
+    std::sort(keys.begin(), keys.end());
+    const size_t n_all = 2 * (size_t)n - 1;
+    PlocHostNodes nd;
+    nd.n = n;
+    nd.boxes.resize(6 * n_all);
+    nd.lft.assign(n_all, -1);
+    nd.rgt.assign(n_all, -1);
+    nd.cnt.assign(n_all, 0);
+    nd.cost.assign(n_all, 0.f);
+    nd.leaf.assign(n_all, 0);
+    std::vector<int> cl((size_t)n), next, nn((size_t)n);
+    for (int k = 0; k < n; k++) {
+        float *b = &nd.boxes[6 * (size_t)k];
+        rtploc::tri_box(verts + 9 * (size_t)rtploc::key_index(keys[(size_t)k]), b);
+        nd.rgt[(size_t)k] = rtploc::key_index(keys[(size_t)k]);
+        nd.cnt[(size_t)k] = 1;
+        nd.cost[(size_t)k] = rtploc::half_area(b) * 1.f;
+        nd.leaf[(size_t)k] = 1;
+        cl[(size_t)k] = k;
+    }
+    const float trav = rtbvh::trav_cost();
+    const int max_leaf = rtbvh::max_leaf();
+    int inner = 0;
+    while (cl.size() > 1) {
+        if (++out.iterations > rtploc::kMaxIterations) return out;
+        const int m = (int)cl.size();
+        for (int i = 0; i < m; i++) {
+            int best_j = -1;
+            float best = 0.f;
+            for (int j = std::max(0, i - rtploc::kRadius); j <= std::min(m - 1, i + rtploc::kRadius); j++) {
+                if (j == i) continue;
+                const float d = rtploc::distance(nd.box(cl[(size_t)i]), nd.box(cl[(size_t)j]));
+                if (best_j < 0 || d < best) {
+                    best_j = j;
+                    best = d;
+                }
+            }
+            nn[(size_t)i] = best_j;
+        }
+        next.clear();
+        const int inner_before = inner;
+        for (int i = 0; i < m; i++) {
+            const int j = nn[(size_t)i];
+            const bool mutual = nn[(size_t)j] == i;
+            if (mutual && j < i) continue;  // (merged into the cluster at j)
+            if (!mutual) {
+                next.push_back(cl[(size_t)i]);
+                continue;
+            }
+            const int id = n + inner++, a = cl[(size_t)i], b = cl[(size_t)j];
+            rtploc::unite(nd.box(a), nd.box(b), &nd.boxes[6 * (size_t)id]);
+            nd.lft[(size_t)id] = a;
+            nd.rgt[(size_t)id] = b;
+            nd.cnt[(size_t)id] = nd.cnt[(size_t)a] + nd.cnt[(size_t)b];
+            nd.leaf[(size_t)id] = rtploc::node_cost(rtploc::half_area(nd.box(id)), nd.cnt[(size_t)id], nd.cost[(size_t)a],
+                                                    nd.cost[(size_t)b], trav, max_leaf, nd.cost[(size_t)id]);
+            next.push_back(id);
+        }
+        if (inner == inner_before) return out;  // (no mutual pair: cannot happen with finite boxes)
+        cl.swap(next);
+    }
+    // collapse to 4-wide, breadth first from the root
+    std::vector<std::pair<int, int>> level{{cl[0], 0}}, below;  // (binary node, first triangle in leaf order)
+    res.order.assign((size_t)n, -1);
+    res.quads.clear();
+    res.num_leaves = 0;
+    int levels = 0, base = 0;
+    while (!level.empty()) {
+        levels++;
+        below.clear();
+        const int next_base = base + (int)level.size();
+        for (const auto &[node, first] : level) {
+            int kids[4], firsts[4];
+            const int nk = rtploc::expand(nd, node, first, kids, firsts);
+            rtbvh::Pair rec[2] = {rtbvh::absent_quad_record(), rtbvh::absent_quad_record()};
+            for (int k = 0; k < nk; k++) {
+                rtbvh::Pair &p = rec[k >> 1];
+                const float *b = nd.box(kids[k]);
+                float *dst = (k & 1) ? p.rbox : p.lbox;
+                for (int a = 0; a < 3; a++) {
+                    dst[a] = rtbvh::pad_down(b[a], 2);
+                    dst[3 + a] = rtbvh::pad_up(b[3 + a], 2);
+                }
+                int32_t link;
+                if (nd.is_leaf(kids[k])) {
+                    int t[8];
+                    const int c = rtploc::leaf_tris(nd, kids[k], t);
+                    if (c < 1 || c > 7 || firsts[k] + c > n) return out;
+                    for (int q = 0; q < c; q++) res.order[(size_t)firsts[k] + q] = t[q];
+                    link = rtbvh::leaf_ref(firsts[k], c);
+                    res.num_leaves++;
+                } else {
+                    link = 2 * (next_base + (int)below.size());
+                    below.push_back({kids[k], firsts[k]});
+                }
+                ((k & 1) ? p.rlink : p.llink) = link;
+            }
+            res.quads.push_back(rec[0]);
+            res.quads.push_back(rec[1]);
+        }
+        base = next_base;
+        level.swap(below);
+    }
+    res.max_depth = levels;
+    res.stack_bound = 3 * levels + 1;
+    out.ok = true;
+    return out;
+}
 }  // namespace
 
 extern "C" {
@@ -442,6 +623,60 @@ int rt_bvh_refit_check(const float *build_verts, const float *new_verts, int n, 
             if (k < 2) root.extend(b);
         }
     out6[5] = (int64_t)llround(1e6 * cost / std::max((double)root.half_area(), 1e-30));
+    return 0;
+}
+
+// The PLOC twin's records and leaf order.  out4: [records, iterations, depth of the 4-wide tree, leaves].  The records (64 bytes
+// each) and the order are copied out when the buffers are given and large enough.  Returns 1 if the build failed.
+int rt_ploc_build(const float *verts, int n, void *quads_out, int64_t cap_records, int32_t *order_out, int64_t *out4) {
+    memset(out4, 0, 4 * sizeof(int64_t));
+    const PlocTwin t = ploc_build(verts, n);
+    if (!t.ok) return 1;
+    out4[0] = (int64_t)t.r.quads.size();
+    out4[1] = t.iterations;
+    out4[2] = t.r.max_depth;
+    out4[3] = t.r.num_leaves;
+    if (quads_out && cap_records >= (int64_t)t.r.quads.size()) memcpy(quads_out, t.r.quads.data(), sizeof(rtbvh::Pair) * t.r.quads.size());
+    if (order_out && n > 0) memcpy(order_out, t.r.order.data(), sizeof(int32_t) * (size_t)n);
+    return 0;
+}
+
+// The PLOC twin checked as rt_bvh_selfcheck checks the host builder.
+// out8: [records, structural errors (as built and as padded for this call's ray origins; leaf order not a permutation),
+//        walk mismatches against exhaustive search (4-wide walk, closest hit), rays walked, the twin's surface-area cost x 10^6,
+//        rtbvh::build's x 10^6 (when with_host), iterations, largest leaf]
+int rt_ploc_check(const float *verts, int n, int n_rays, const float *o3, const float *d3, int with_host, int64_t *out8) {
+    memset(out8, 0, 8 * sizeof(int64_t));
+    const PlocTwin t = ploc_build(verts, n);
+    if (!t.ok || n <= 0) return 1;
+    const rtbvh::Result &r = t.r;
+    out8[0] = (int64_t)r.quads.size();
+    std::vector<char> seen((size_t)n, 0);
+    for (int k = 0; k < n; k++) {
+        const int i = r.order[(size_t)k];
+        if (i < 0 || i >= n || seen[(size_t)i]) out8[1]++;
+        else seen[(size_t)i] = 1;
+    }
+    if (out8[1]) return 0;
+    int max_leaf = 0;
+    const std::vector<rtbvh::Pair> padded = padded_quads(r, n_rays, o3);
+    out8[1] = validate(r, r.quads, true, verts, n, max_leaf) + validate(r, padded, true, verts, n, max_leaf);
+    out8[7] = max_leaf;
+    if (out8[1]) return 0;
+    const std::vector<Tri> tris = leaf_order_triangles(verts, r, n);
+    for (int i = 0; i < n_rays; i++) {
+        V3 o{o3[3 * i], o3[3 * i + 1], o3[3 * i + 2]}, d{d3[3 * i], d3[3 * i + 1], d3[3 * i + 2]};
+        float bt = FLT_MAX, tt;
+        int bb = -1;
+        for (int k = 0; k < n; k++)
+            if (tri_hit(tris[k], o, d, bt, tt) && (!(tt == bt && bb >= 0) || r.order[k] > r.order[bb])) { bt = tt; bb = k; }
+        WalkResult w = walk_ray(padded, true, tris, r.order, r.stack_bound, 0, o, d, FLT_MAX, -1);
+        if (w.failed || w.best != bb || (bb >= 0 && w.t != bt)) out8[2]++;
+        out8[3]++;
+    }
+    out8[4] = (int64_t)llround(1e6 * quads_sah_host(r.quads));
+    if (with_host) out8[5] = (int64_t)llround(1e6 * quads_sah_host(rtbvh::build(verts, n).quads));
+    out8[6] = t.iterations;
     return 0;
 }
 

@@ -6,6 +6,7 @@
 //   rt_calibrate_valu(_packed)  what the vector ALUs sustain on independent v_fma_f32 / v_pk_* streams
 //   rt_probe_issue              cycles per instruction of one wave, by instruction kind and occupancy
 //   rt_split_probe              "one persistent kernel, or the reference's stage split?" priced on dense ray / shade arrays
+//   rt_scene_tree_copy          a scene's unpadded 4-wide records and leaf order (the device builder against its host twin)
 // The product library (librtcuda_amd.so) contains none of this.  The tools library also carries a private copy of the
 // product's entry points (same source); a scene handed to rt_split_probe must come from THIS library's rt_scene_create
 // (rtcuda_amd/api.py: Scene(arrays, library=tools_lib())).
@@ -626,3 +627,15 @@ int rt_split_probe(const rt_scene *scene, const rt_camera *camera, int width, in
 
 
 }  // extern "C"
+
+int rt_scene_tree_copy(const rt_scene *scene, void *records, int64_t cap_records, int32_t *order, int64_t cap_order,
+                       int64_t *out2) {
+    if (!scene || !out2) return fail("rt_scene_tree_copy: null argument");
+    if (!scene->wide) return fail("rt_scene_tree_copy: a 2-wide scene (RT_BVH_WIDE=0)");
+    std::lock_guard<std::mutex> lock(scene->pad_mutex);
+    out2[0] = (int64_t)scene->h_quads.size();
+    out2[1] = scene->n_tris;
+    if (records && cap_records >= out2[0]) memcpy(records, scene->h_quads.data(), sizeof(rtbvh::Pair) * scene->h_quads.size());
+    if (order && cap_order >= out2[1]) memcpy(order, scene->h_order.data(), sizeof(int32_t) * scene->h_order.size());
+    return 0;
+}

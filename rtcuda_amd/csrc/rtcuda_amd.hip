@@ -59,6 +59,7 @@
 #include "../../include/rtcuda_amd.h"
 #include "rt_bvh.h"
 #include "rt_device.h"
+#include "rt_ploc.h"
 #include "rt_ref_tree.h"
 
 using namespace rt;
@@ -2592,6 +2593,306 @@ __global__ void k_refit_emit(const rtbvh::Pair *__restrict__ recs, int n_nodes, 
     r[28] = r[29] = r[30] = r[31] = 0.f;
 }
 
+// ---- PLOC (rt_scene_rebuild, RT_SCENE_DEVICE_BVH): a surface-area-quality tree built on the device -- parallel locally-
+// ordered clustering (Meister & Bittner 2018) over 63-bit Morton keys, leaves by the cost model of rt_bvh.h, collapsed to the
+// 4-wide records the kernels walk.  Every step is a deterministic function of the vertices (rt_ploc.h holds the expressions
+// and the rules; rt_host_check.cpp a sequential twin that gives the same records bit for bit).
+struct PlocCluster {  // a cluster: the exact box of its subtree and its node
+    float b[6];
+    int id, pad;
+};
+struct PlocNodes {  // the binary tree (rt_ploc.h): ids < n triangles in key order, then the merges
+    float *box;     // 6 per node, exact
+    int2 *child;    // inner: (left, right); triangle: (-1, original index)
+    int *cnt;
+    float *cost;
+    int *leaf;
+    int n;
+    __device__ bool is_leaf(int i) const { return leaf[i] != 0; }
+    __device__ bool is_tri(int i) const { return i < n; }
+    __device__ int tri(int i) const { return child[i].y; }
+    __device__ int left(int i) const { return child[i].x; }
+    __device__ int right(int i) const { return child[i].y; }
+    __device__ int count(int i) const { return cnt[i]; }
+    __device__ const float *box_of(int i) const { return box + 6 * (size_t)i; }
+};
+struct PlocNodesView {  // (rtploc::expand / leaf_tris take box(i) by that name)
+    PlocNodes nd;
+    __device__ bool is_leaf(int i) const { return nd.is_leaf(i); }
+    __device__ bool is_tri(int i) const { return nd.is_tri(i); }
+    __device__ int tri(int i) const { return nd.tri(i); }
+    __device__ int left(int i) const { return nd.left(i); }
+    __device__ int right(int i) const { return nd.right(i); }
+    __device__ int count(int i) const { return nd.count(i); }
+    __device__ const float *box(int i) const { return nd.box_of(i); }
+};
+// exclusive prefix sum of v over the 256 threads of a block (4 waves); every thread must call it.  `total`: the block's sum.
+__device__ __forceinline__ int ploc_block_scan(int v, int &total) {
+    __shared__ int s_wave[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int x = v;
+    for (int d = 1; d < 64; d <<= 1) {
+        const int y = __shfl_up(x, d, 64);
+        if (lane >= d) x += y;
+    }
+    if (lane == 63) s_wave[wave] = x;
+    __syncthreads();
+    int off = 0;
+    total = 0;
+    for (int w = 0; w < 4; w++) {
+        if (w < wave) off += s_wave[w];
+        total += s_wave[w];
+    }
+    __syncthreads();  // (s_wave is reused by the next call)
+    return off + x - v;
+}
+// centroid bounds: min / max of the order-preserving bits (exact in any order); bits[0..2] start at ~0, bits[3..5] at 0
+__global__ void __launch_bounds__(256) k_ploc_bounds(const float *__restrict__ verts, int n, unsigned *__restrict__ bits) {
+    unsigned lo[3] = {~0u, ~0u, ~0u}, hi[3] = {0u, 0u, 0u};
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        float b[6];
+        rtploc::tri_box(verts + 9 * (size_t)i, b);
+        for (int a = 0; a < 3; a++) {
+            const unsigned u = rtploc::ordered_bits(rtploc::centroid(b, a));
+            lo[a] = min(lo[a], u);
+            hi[a] = max(hi[a], u);
+        }
+    }
+    for (int a = 0; a < 3; a++) {
+        for (int d = 32; d > 0; d >>= 1) {
+            lo[a] = min(lo[a], (unsigned)__shfl_xor((int)lo[a], d, 64));
+            hi[a] = max(hi[a], (unsigned)__shfl_xor((int)hi[a], d, 64));
+        }
+    }
+    if ((threadIdx.x & 63) == 0)
+        for (int a = 0; a < 3; a++) {
+            atomicMin(&bits[a], lo[a]);
+            atomicMax(&bits[3 + a], hi[a]);
+        }
+}
+__global__ void k_ploc_keys(const float *__restrict__ verts, int n, int n_pad, float lox, float loy, float loz, float sx, float sy,
+                            float sz, unsigned long long *__restrict__ keys) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_pad) return;
+    const float lo[3] = {lox, loy, loz}, s[3] = {sx, sy, sz};
+    keys[i] = i < n ? (unsigned long long)rtploc::key(verts + 9 * (size_t)i, i, lo, s) : ~0ull;  // (padding sorts last)
+}
+// the triangles as the first n nodes (key order) and the first clusters
+__global__ void k_ploc_leaves(const float *__restrict__ verts, const unsigned long long *__restrict__ keys, int n, PlocNodes nd,
+                              PlocCluster *__restrict__ cl) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const int t = rtploc::key_index(keys[k]);
+    PlocCluster c;
+    rtploc::tri_box(verts + 9 * (size_t)t, c.b);
+    c.id = k;
+    c.pad = 0;
+    for (int a = 0; a < 6; a++) nd.box[6 * (size_t)k + a] = c.b[a];
+    nd.child[k] = make_int2(-1, t);
+    nd.cnt[k] = 1;
+    nd.cost[k] = rtploc::half_area(c.b) * 1.f;
+    nd.leaf[k] = 1;
+    cl[k] = c;
+}
+// nearest neighbour of every cluster within the window (ties: the smaller j); the block's window of boxes is staged in LDS
+__global__ void __launch_bounds__(256) k_ploc_nearest(const PlocCluster *__restrict__ cl, int m, int *__restrict__ nn) {
+    constexpr int R = rtploc::kRadius, W = 256 + 2 * R;
+    __shared__ float s_box[6][W];
+    const int base = blockIdx.x * 256;
+    for (int t = threadIdx.x; t < W; t += 256) {
+        const int g = base - R + t;
+        if (g >= 0 && g < m)
+            for (int a = 0; a < 6; a++) s_box[a][t] = cl[g].b[a];
+    }
+    __syncthreads();
+    const int i = base + threadIdx.x;
+    if (i >= m) return;
+    float bi[6];
+    for (int a = 0; a < 6; a++) bi[a] = s_box[a][threadIdx.x + R];
+    int best_j = -1;
+    float best = 0.f;
+    const int j_end = min(m - 1, i + R);
+    for (int j = max(0, i - R); j <= j_end; j++) {
+        if (j == i) continue;
+        float bj[6];
+        for (int a = 0; a < 6; a++) bj[a] = s_box[a][j - base + R];
+        const float d = rtploc::distance(bi, bj);
+        if (best_j < 0 || d < best) {
+            best_j = j;
+            best = d;
+        }
+    }
+    nn[i] = best_j;
+}
+__device__ __forceinline__ void ploc_roles(const int *nn, int m, int i, bool &survive, bool &merge) {
+    survive = merge = false;
+    if (i >= m) return;
+    const int j = nn[i];
+    const bool mutual = nn[j] == i;
+    survive = !mutual || i < j;
+    merge = mutual && i < j;
+}
+// per block: how many clusters survive and how many merges are made (int2 per block)
+__global__ void __launch_bounds__(256) k_ploc_count(const int *__restrict__ nn, int m, int2 *__restrict__ block_sums) {
+    bool survive, merge;
+    ploc_roles(nn, m, blockIdx.x * 256 + threadIdx.x, survive, merge);
+    int total = 0;
+    ploc_block_scan((survive ? 1 : 0) | (merge ? 1 << 16 : 0), total);  // (two 9-bit counts packed in one scan)
+    if (threadIdx.x == 0) block_sums[blockIdx.x] = make_int2(total & 0xffff, total >> 16);
+}
+// exclusive scan of the per-block sums in place (one block of 1024 threads); totals[0..1] = the sums over all blocks
+__global__ void __launch_bounds__(1024) k_ploc_scan(int2 *__restrict__ sums, int nb, int *__restrict__ totals) {
+    __shared__ int s_x[1024], s_y[1024];
+    const int t = threadIdx.x, per = (nb + 1023) / 1024, b0 = min(nb, t * per), b1 = min(nb, b0 + per);
+    int ax = 0, ay = 0;
+    for (int b = b0; b < b1; b++) {
+        ax += sums[b].x;
+        ay += sums[b].y;
+    }
+    s_x[t] = ax;
+    s_y[t] = ay;
+    __syncthreads();
+    for (int d = 1; d < 1024; d <<= 1) {
+        const int vx = t >= d ? s_x[t - d] : 0, vy = t >= d ? s_y[t - d] : 0;
+        __syncthreads();
+        s_x[t] += vx;
+        s_y[t] += vy;
+        __syncthreads();
+    }
+    int rx = t ? s_x[t - 1] : 0, ry = t ? s_y[t - 1] : 0;
+    for (int b = b0; b < b1; b++) {
+        const int2 v = sums[b];
+        sums[b] = make_int2(rx, ry);
+        rx += v.x;
+        ry += v.y;
+    }
+    if (t == 1023) {
+        totals[0] = s_x[1023];
+        totals[1] = s_y[1023];
+    }
+}
+// merge mutual nearest neighbours into new inner nodes (at the smaller position; ids n + inner_base + rank of the merge) and
+// compact the survivors in order
+__global__ void __launch_bounds__(256) k_ploc_merge(const PlocCluster *__restrict__ in, const int *__restrict__ nn, int m,
+                                                    const int2 *__restrict__ block_offsets, int inner_base, float trav, int max_leaf,
+                                                    PlocNodes nd, PlocCluster *__restrict__ out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    bool survive, merge;
+    ploc_roles(nn, m, i, survive, merge);
+    int total = 0;
+    const int r = ploc_block_scan((survive ? 1 : 0) | (merge ? 1 << 16 : 0), total);
+    if (!survive) return;
+    const int2 off = block_offsets[blockIdx.x];
+    const int pos = off.x + (r & 0xffff);
+    if (!merge) {
+        out[pos] = in[i];
+        return;
+    }
+    const PlocCluster a = in[i], b = in[nn[i]];
+    const int id = nd.n + inner_base + off.y + (r >> 16);
+    PlocCluster c;
+    rtploc::unite(a.b, b.b, c.b);
+    c.id = id;
+    c.pad = 0;
+    const int count = nd.cnt[a.id] + nd.cnt[b.id];
+    float cost;
+    const bool leaf = rtploc::node_cost(rtploc::half_area(c.b), count, nd.cost[a.id], nd.cost[b.id], trav, max_leaf, cost);
+    for (int k = 0; k < 6; k++) nd.box[6 * (size_t)id + k] = c.b[k];
+    nd.child[id] = make_int2(a.id, b.id);
+    nd.cnt[id] = count;
+    nd.cost[id] = cost;
+    nd.leaf[id] = leaf ? 1 : 0;
+    out[pos] = c;
+}
+// collapse, one level of 4-wide nodes per launch pair: how many inner children each node of the level has (per block)
+__global__ void __launch_bounds__(256) k_ploc_level_count(const int2 *__restrict__ level, int count, PlocNodes nd,
+                                                          int2 *__restrict__ block_sums) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    int inner = 0;
+    if (i < count) {
+        const PlocNodesView v{nd};
+        int kids[4], firsts[4];
+        const int nk = rtploc::expand(v, level[i].x, level[i].y, kids, firsts);
+        for (int k = 0; k < nk; k++) inner += v.is_leaf(kids[k]) ? 0 : 1;
+    }
+    int total = 0;
+    ploc_block_scan(inner, total);
+    if (threadIdx.x == 0) block_sums[blockIdx.x] = make_int2(total, 0);
+}
+// ... and its records: node level_base + i = records 2 (level_base + i) and + 1; inner children become the next level's nodes
+// (numbered breadth first: next_base + their rank), leaf children write their triangles into the leaf order
+__global__ void __launch_bounds__(256) k_ploc_level_emit(const int2 *__restrict__ level, int count, int level_base, int next_base,
+                                                         const int2 *__restrict__ block_offsets, PlocNodes nd,
+                                                         rtbvh::Pair *__restrict__ recs, int2 *__restrict__ next_level,
+                                                         int *__restrict__ order, int *__restrict__ error) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const PlocNodesView v{nd};
+    int kids[4], firsts[4], nk = 0, inner = 0;
+    if (i < count) {
+        nk = rtploc::expand(v, level[i].x, level[i].y, kids, firsts);
+        for (int k = 0; k < nk; k++) inner += v.is_leaf(kids[k]) ? 0 : 1;
+    }
+    int total = 0;
+    int rank = ploc_block_scan(inner, total) + block_offsets[blockIdx.x].x;
+    if (i >= count) return;
+    rtbvh::Pair rec[2];
+    for (int h = 0; h < 2; h++) {
+        for (int a = 0; a < 6; a++) rec[h].lbox[a] = rec[h].rbox[a] = INFINITY;
+        rec[h].llink = rec[h].rlink = rtbvh::kNoChild;
+        rec[h].spare[0] = rec[h].spare[1] = 0;
+    }
+    for (int k = 0; k < nk; k++) {
+        rtbvh::Pair &p = rec[k >> 1];
+        const float *b = v.box(kids[k]);
+        float *dst = (k & 1) ? p.rbox : p.lbox;
+        for (int a = 0; a < 3; a++) {
+            dst[a] = lbvh_pad(b[a], -1);
+            dst[3 + a] = lbvh_pad(b[3 + a], +1);
+        }
+        int32_t link;
+        if (v.is_leaf(kids[k])) {
+            int t[8];
+            const int c = rtploc::leaf_tris(v, kids[k], t);
+            if (c < 1 || c > 7 || firsts[k] < 0 || firsts[k] + c > nd.n) {
+                atomicExch(error, 1);
+                return;
+            }
+            for (int q = 0; q < c; q++) order[firsts[k] + q] = t[q];
+            link = ~((firsts[k] << 3) | c);  // (rtbvh::leaf_ref)
+        } else {
+            next_level[rank] = make_int2(kids[k], firsts[k]);
+            link = 2 * (next_base + rank);
+            rank++;
+        }
+        ((k & 1) ? p.rlink : p.llink) = link;
+    }
+    recs[2 * (size_t)(level_base + i)] = rec[0];
+    recs[2 * (size_t)(level_base + i) + 1] = rec[1];
+}
+// ---- re-emitting a scene for a new leaf order (rt_scene_rebuild)
+__global__ void k_ploc_inverse(const int *__restrict__ order, int n, int *__restrict__ inverse) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < n) inverse[order[k]] = k;
+}
+// (material, light) of every triangle in leaf order, from the caller's arrays in their order
+__global__ void k_ploc_tri_info(const int2 *__restrict__ caller_info, const int *__restrict__ order, int n, int2 *__restrict__ info) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < n) info[k] = caller_info[order[k]];
+}
+// area lights name their triangle in the caller's order (rt_light.triangle): the leaf-order index the kernels read
+__global__ void k_ploc_lights(Light *__restrict__ lights, int n_lights, const int *__restrict__ inverse) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_lights && lights[i].type == RT_AREA_LIGHT) lights[i].tri = inverse[lights[i].tri];
+}
+// the reference's tree (a function of the triangles alone) for the new leaf order: its primitives' and leaves' indices
+__global__ void k_ploc_remap_ref(const int *__restrict__ prims, const int *__restrict__ leaf_of, const int *__restrict__ old_order,
+                                 const int *__restrict__ inverse, int n, int *__restrict__ new_prims, int *__restrict__ new_leaf_of) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    new_prims[i] = inverse[old_order[prims[i]]];
+    new_leaf_of[inverse[old_order[i]]] = leaf_of[i];
+}
+
 // ============================================================================ host side
 struct rt_scene {
     int device = 0;
@@ -2605,7 +2906,7 @@ struct rt_scene {
     mutable std::mutex pad_mutex;
     bool top_prefix = true;  // the first records are the top of the tree in level order (host builder)
     double build_seconds = 0.0;  // BVH build time (host wall clock, or device events for the LBVH)
-    int builder = 0;             // 0 host SAH, 1 device LBVH
+    int builder = 0;             // 0 host SAH, 1 device LBVH, 2 device PLOC (RT_SCENE_DEVICE_BVH, rt_scene_rebuild)
     float4 *d_tris = nullptr;
     int2 *d_tri_info = nullptr;
     float4 *d_tri_shade = nullptr;
@@ -3209,6 +3510,287 @@ int scene_update_impl(rt_scene *sc, const float *verts, int n_tris, bool device_
         sc->ref_ready = false;
     }
     {   // replicas on other devices (rt_render_multi) hold the old geometry: dropped, recreated from h_tri9 on next use
+        std::lock_guard<std::mutex> lock(sc->replica_mutex);
+        for (rt_scene *r : sc->replicas) delete r;
+        sc->replicas.clear();
+    }
+    return 0;
+}
+
+// Device PLOC build (k_ploc_*) of n >= 1 triangles from d_verts on the current device, ordered on `st`: the unpadded 4-wide
+// records (breadth-first) and the leaf order, on the device (owned here) and copied to the host.  The host reads the cluster
+// count back after every iteration and the node count after every level.  Fails -- with nothing to undo -- if the tree does
+// not fit the traversal stack.
+struct PlocBuild {
+    rtbvh::Pair *d_recs = nullptr;
+    int *d_order = nullptr;
+    std::vector<rtbvh::Pair> quads;
+    std::vector<int32_t> order;
+    int max_depth = 0, stack_bound = 1, leaves = 0, iterations = 0;
+    double seconds = 0.0;  // device time of the build (HIP events)
+    PlocBuild() = default;
+    PlocBuild(const PlocBuild &) = delete;
+    PlocBuild &operator=(const PlocBuild &) = delete;
+    ~PlocBuild() {
+        (void)hipFree(d_recs);
+        (void)hipFree(d_order);
+    }
+};
+int build_ploc_device(const float *d_verts, int n, hipStream_t st, PlocBuild &out, const std::string &w) {
+    if (n < 1) return fail(w + ": the device builder needs at least one triangle");
+    int n_pad = 1;
+    while (n_pad < n) n_pad <<= 1;
+    const size_t n_all = 2 * (size_t)n - 1, cap_nodes = std::max(n - 1, 1);  // binary nodes; 4-wide nodes at most
+    const int nb = (n + 255) / 256;
+    DevScope tmp;
+    unsigned long long *d_keys = nullptr;
+    unsigned *d_bits = nullptr;
+    float *d_box = nullptr, *d_cost = nullptr;
+    int2 *d_child = nullptr, *d_sums = nullptr, *d_lvl[2] = {nullptr, nullptr};
+    int *d_cnt = nullptr, *d_leaf = nullptr, *d_nn = nullptr, *d_tot = nullptr;
+    PlocCluster *d_cl[2] = {nullptr, nullptr};
+    if (tmp.alloc(d_keys, (size_t)n_pad) || tmp.alloc(d_bits, 6) || tmp.alloc(d_box, 6 * n_all) || tmp.alloc(d_cost, n_all) ||
+        tmp.alloc(d_child, n_all) || tmp.alloc(d_cnt, n_all) || tmp.alloc(d_leaf, n_all) || tmp.alloc(d_nn, (size_t)n) ||
+        tmp.alloc(d_sums, (size_t)nb) || tmp.alloc(d_tot, 4) || tmp.alloc(d_cl[0], (size_t)n) || tmp.alloc(d_cl[1], (size_t)n) ||
+        tmp.alloc(d_lvl[0], cap_nodes) || tmp.alloc(d_lvl[1], cap_nodes))
+        return 1;
+    HIP_TRY(hipMalloc((void **)&out.d_recs, sizeof(rtbvh::Pair) * 2 * cap_nodes));
+    HIP_TRY(hipMalloc((void **)&out.d_order, sizeof(int) * (size_t)n));
+    HIP_TRY(hipEventCreate(&tmp.e0));
+    HIP_TRY(hipEventCreate(&tmp.e1));
+    HIP_TRY(hipEventRecord(tmp.e0, st));
+    const dim3 blk(256);
+    // keys: centroid bounds, quantisation, sort
+    HIP_TRY(hipMemsetAsync(d_bits, 0xff, 3 * sizeof(unsigned), st));
+    HIP_TRY(hipMemsetAsync(d_bits + 3, 0, 3 * sizeof(unsigned), st));
+    hipLaunchKernelGGL(k_ploc_bounds, dim3(std::min(nb, 1024)), blk, 0, st, d_verts, n, d_bits);
+    unsigned bits[6];
+    HIP_TRY(hipMemcpyAsync(bits, d_bits, sizeof(bits), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    float lo[3], sc3[3];
+    for (int a = 0; a < 3; a++) {
+        lo[a] = rtploc::from_ordered_bits(bits[a]);
+        sc3[a] = rtploc::quant_scale(lo[a], rtploc::from_ordered_bits(bits[3 + a]));
+    }
+    hipLaunchKernelGGL(k_ploc_keys, dim3((n_pad + 255) / 256), blk, 0, st, d_verts, n, n_pad, lo[0], lo[1], lo[2], sc3[0], sc3[1],
+                       sc3[2], d_keys);
+    for (int k2 = 2; k2 <= n_pad; k2 <<= 1)
+        for (int j = k2 >> 1; j > 0; j >>= 1)
+            hipLaunchKernelGGL(k_bitonic_step, dim3((n_pad + 255) / 256), blk, 0, st, d_keys, n_pad, j, k2);
+    PlocNodes nd{d_box, d_child, d_cnt, d_cost, d_leaf, n};
+    hipLaunchKernelGGL(k_ploc_leaves, dim3(nb), blk, 0, st, d_verts, d_keys, n, nd, d_cl[0]);
+    HIP_TRY(hipGetLastError());
+    // clustering: until one cluster is left
+    const float trav = rtbvh::trav_cost();
+    const int max_leaf = rtbvh::max_leaf();
+    int m = n, inner = 0, cur = 0;
+    while (m > 1) {
+        if (++out.iterations > rtploc::kMaxIterations) return fail(w + ": the clustering does not converge");
+        const int mb = (m + 255) / 256;
+        hipLaunchKernelGGL(k_ploc_nearest, dim3(mb), blk, 0, st, d_cl[cur], m, d_nn);
+        hipLaunchKernelGGL(k_ploc_count, dim3(mb), blk, 0, st, d_nn, m, d_sums);
+        hipLaunchKernelGGL(k_ploc_scan, dim3(1), dim3(1024), 0, st, d_sums, mb, d_tot);
+        hipLaunchKernelGGL(k_ploc_merge, dim3(mb), blk, 0, st, d_cl[cur], d_nn, m, d_sums, inner, trav, max_leaf, nd, d_cl[cur ^ 1]);
+        HIP_TRY(hipGetLastError());
+        int tot[2];
+        HIP_TRY(hipMemcpyAsync(tot, d_tot, sizeof(tot), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (tot[1] < 1 || tot[0] != m - tot[1] || inner + tot[1] > n - 1)
+            return fail(w + ": the clustering made no progress (non-finite vertices?)");
+        m = tot[0];
+        inner += tot[1];
+        cur ^= 1;
+    }
+    // collapse to 4-wide, one level per step, breadth first from the root (node 2n - 2, or the one triangle)
+    const int2 root = make_int2(n > 1 ? (int)n_all - 1 : 0, 0);
+    HIP_TRY(hipMemcpyAsync(d_lvl[0], &root, sizeof(int2), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(d_tot + 2, 0, sizeof(int), st));
+    int count = 1, base = 0, lv = 0;
+    while (count > 0) {
+        out.max_depth++;
+        if (3 * out.max_depth + 1 > kMaxStackBound)
+            return fail(w + ": the device-built tree is deeper than the traversal stack allows (" + std::to_string(out.max_depth) + " levels)");
+        const int cb = (count + 255) / 256;
+        hipLaunchKernelGGL(k_ploc_level_count, dim3(cb), blk, 0, st, d_lvl[lv], count, nd, d_sums);
+        hipLaunchKernelGGL(k_ploc_scan, dim3(1), dim3(1024), 0, st, d_sums, cb, d_tot);
+        int tot[2];
+        HIP_TRY(hipMemcpyAsync(tot, d_tot, sizeof(tot), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        const int next_base = base + count;
+        if (tot[0] < 0 || (size_t)next_base + (size_t)tot[0] > cap_nodes) return fail(w + ": the 4-wide collapse overran its node count");
+        hipLaunchKernelGGL(k_ploc_level_emit, dim3(cb), blk, 0, st, d_lvl[lv], count, base, next_base, d_sums, nd, out.d_recs,
+                           d_lvl[lv ^ 1], out.d_order, d_tot + 2);
+        HIP_TRY(hipGetLastError());
+        base = next_base;
+        count = tot[0];
+        lv ^= 1;
+    }
+    HIP_TRY(hipEventRecord(tmp.e1, st));
+    HIP_TRY(hipEventSynchronize(tmp.e1));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, tmp.e0, tmp.e1));
+    out.seconds = ms * 1e-3;
+    int err = 0;
+    HIP_TRY(hipMemcpy(&err, d_tot + 2, sizeof(int), hipMemcpyDeviceToHost));
+    if (err) return fail(w + ": the device-built tree has a leaf that cannot be referenced");
+    out.quads.resize(2 * (size_t)base);
+    out.order.resize((size_t)n);
+    HIP_TRY(hipMemcpy(out.quads.data(), out.d_recs, sizeof(rtbvh::Pair) * out.quads.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out.order.data(), out.d_order, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
+    out.stack_bound = 3 * out.max_depth + 1;
+    out.leaves = 0;
+    for (const rtbvh::Pair &p : out.quads) out.leaves += (p.llink < 0 && p.llink != rtbvh::kNoChild) + (p.rlink < 0 && p.rlink != rtbvh::kNoChild);
+    return 0;
+}
+// What the scene may adopt from a build: a well-formed tree over a permutation of its triangles, within the stack
+bool ploc_result_ok(const PlocBuild &b, int n) {
+    if (b.stack_bound > kMaxStackBound || !validate_quads(b.quads, n) || (int)b.order.size() != n) return false;
+    std::vector<char> seen((size_t)n, 0);
+    for (int32_t i : b.order) {
+        if (i < 0 || i >= n || seen[(size_t)i]) return false;
+        seen[(size_t)i] = 1;
+    }
+    return true;
+}
+
+// rt_scene_rebuild / rt_scene_rebuild_device: a new tree for the scene's current or new vertices (build_ploc_device), and
+// everything the kernels index in leaf order re-emitted on the device from the new order, into new buffers that replace the
+// scene's only once the tree has passed its checks.  `verts`: null (the scene's own vertices), a host array or (device_ptr)
+// a buffer on the scene's device.
+int scene_rebuild_impl(rt_scene *sc, const float *verts, int n_tris, bool device_ptr, hipStream_t st, const char *what) {
+    const std::string w(what);
+    if (!sc) return fail(w + ": null scene");
+    if (n_tris != sc->n_tris) return fail(w + ": " + std::to_string(n_tris) + " triangles, the scene was created with " + std::to_string(sc->n_tris));
+    if (!sc->wide) return fail(w + ": the scene uses the 2-wide experiment format (RT_BVH_WIDE=0), which the device builder does not write");
+    if (n_tris < 1) return fail(w + ": the scene has no triangles");
+    int saved = 0;
+    HIP_TRY(hipGetDevice(&saved));
+    if (device_ptr && verts) {
+        hipPointerAttribute_t attr;
+        if (hipPointerGetAttributes(&attr, verts) != hipSuccess || (attr.type != hipMemoryTypeDevice && !attr.isManaged) ||
+            attr.device != sc->device) {
+            (void)hipGetLastError();  // (the failed query leaves its error behind)
+            return fail(w + ": d_tri_p0p1p2 is not device memory on the scene's device " + std::to_string(sc->device));
+        }
+    }
+    if (saved != sc->device) HIP_TRY(hipSetDevice(sc->device));
+    struct Restore {
+        int dev, was;
+        ~Restore() { if (dev != was) (void)hipSetDevice(was); }
+    } restore{sc->device, saved};
+    const int n = n_tris;
+    std::lock_guard<std::mutex> pad_lock(sc->pad_mutex);  // (h_quads and origin_radius change)
+    DevScope tmp;
+    const float *d_verts = verts;
+    if (!verts || !device_ptr) {
+        float *d_v = nullptr;
+        if (tmp.alloc(d_v, 9 * (size_t)n)) return 1;
+        HIP_TRY(hipMemcpyAsync(d_v, verts ? verts : sc->h_tri9.data(), sizeof(float) * 9 * (size_t)n, hipMemcpyHostToDevice, st));
+        d_verts = d_v;
+    }
+    std::vector<float> h_new;
+    if (verts) {
+        h_new.resize(9 * (size_t)n);
+        if (device_ptr) {
+            HIP_TRY(hipMemcpyAsync(h_new.data(), verts, sizeof(float) * h_new.size(), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+        } else {
+            memcpy(h_new.data(), verts, sizeof(float) * h_new.size());
+        }
+    }
+    const bool moved = verts && memcmp(h_new.data(), sc->h_tri9.data(), sizeof(float) * h_new.size()) != 0;
+    PlocBuild b;
+    if (build_ploc_device(d_verts, n, st, b, w)) return 1;
+    if (!ploc_result_ok(b, n)) return fail(w + ": the device-built tree is malformed; the scene is unchanged");
+    // the scene's leaf-order arrays for the new order, into new buffers
+    const int n_nodes = (int)b.quads.size(), n_lights = sc->n_lights;
+    float4 *d_nodes = nullptr, *d_tris = nullptr, *d_shade = nullptr;
+    int2 *d_info = nullptr, *d_caller_info = nullptr;
+    Light *d_lights = nullptr;
+    float *d_tables = nullptr, *d_radius = nullptr;
+    int *d_inverse = nullptr, *d_ref_prims = nullptr, *d_ref_leaf_of = nullptr;
+    DevScope fresh;  // (released unless adopted below)
+    const bool keep_ref = sc->ref_ready && !moved;
+    if (fresh.alloc(d_nodes, 4 * (size_t)n_nodes) || fresh.alloc(d_tris, 3 * (size_t)n) || fresh.alloc(d_shade, (size_t)n) ||
+        fresh.alloc(d_info, (size_t)n) || fresh.alloc(d_lights, (size_t)std::max(n_lights, 1)) ||
+        fresh.alloc(d_tables, (size_t)std::max(sc->tab_dwords, 1)) || tmp.alloc(d_caller_info, (size_t)n) ||
+        tmp.alloc(d_inverse, (size_t)n) || tmp.alloc(d_radius, 3) ||
+        (keep_ref && (fresh.alloc(d_ref_prims, (size_t)n) || fresh.alloc(d_ref_leaf_of, (size_t)n))))
+        return 1;
+    std::vector<int2> caller_info((size_t)n);
+    for (int i = 0; i < n; i++)
+        caller_info[(size_t)i] = make_int2(sc->h_tri_material[(size_t)i], sc->h_tri_light.empty() ? -1 : sc->h_tri_light[(size_t)i]);
+    HIP_TRY(hipMemcpyAsync(d_caller_info, caller_info.data(), sizeof(int2) * (size_t)n, hipMemcpyHostToDevice, st));
+    if (n_lights > 0) HIP_TRY(hipMemcpyAsync(d_lights, sc->h_lights.data(), sizeof(Light) * (size_t)n_lights, hipMemcpyHostToDevice, st));
+    float radius[3] = {sc->origin_radius[0], sc->origin_radius[1], sc->origin_radius[2]};
+    const dim3 blk(256), grid((n + 255) / 256);
+    hipLaunchKernelGGL(k_ploc_inverse, grid, blk, 0, st, b.d_order, n, d_inverse);
+    hipLaunchKernelGGL(k_refit_tris, grid, blk, 0, st, d_verts, b.d_order, n, d_tris);
+    hipLaunchKernelGGL(k_ploc_tri_info, grid, blk, 0, st, d_caller_info, b.d_order, n, d_info);
+    if (n_lights > 0) hipLaunchKernelGGL(k_ploc_lights, dim3((n_lights + 255) / 256), blk, 0, st, d_lights, n_lights, d_inverse);
+    hipLaunchKernelGGL(k_build_tri_shade, grid, blk, 0, st, d_tris, d_info, n, d_shade);
+    const int nt = std::max(std::max(sc->n_mats, n_lights), 1);
+    hipLaunchKernelGGL(k_build_tables, dim3((nt + 63) / 64), dim3(64), 0, st, sc->d_mats, sc->n_mats, d_lights, n_lights, d_tris, d_tables);
+    hipLaunchKernelGGL(k_refit_emit, dim3((n_nodes / 2 + 255) / 256), blk, 0, st, b.d_recs, n_nodes / 2, radius[0], radius[1],
+                       radius[2], (float *)d_nodes, d_radius);
+    if (keep_ref)
+        hipLaunchKernelGGL(k_ploc_remap_ref, grid, blk, 0, st, sc->d_ref_prims, sc->d_ref_leaf_of, sc->d_order, d_inverse, n,
+                           d_ref_prims, d_ref_leaf_of);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(radius, d_radius, sizeof(radius), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    // adopt: the new buffers replace the old ones, the host state follows
+    fresh.ptrs.clear();
+    std::swap(sc->d_nodes, d_nodes);
+    std::swap(sc->d_tris, d_tris);
+    std::swap(sc->d_tri_shade, d_shade);
+    std::swap(sc->d_tri_info, d_info);
+    std::swap(sc->d_lights, d_lights);
+    std::swap(sc->d_tables, d_tables);
+    std::swap(sc->d_order, b.d_order);
+    for (void *q : {(void *)d_nodes, (void *)d_tris, (void *)d_shade, (void *)d_info, (void *)d_lights, (void *)d_tables}) (void)hipFree(q);
+    sc->h_quads = b.quads;
+    sc->h_order.assign(b.order.begin(), b.order.end());
+    for (int k = 0; k < n; k++) sc->h_inverse[(size_t)sc->h_order[(size_t)k]] = k;
+    for (int a = 0; a < 3; a++) sc->origin_radius[a] = radius[a];
+    sc->n_nodes = n_nodes;
+    sc->max_depth = b.max_depth;
+    sc->stack_bound = b.stack_bound;
+    sc->n_leaves = b.leaves;
+    sc->top_prefix = true;  // (breadth-first throughout: every prefix of the records is the top of the tree in level order)
+    sc->builder = 2;
+    sc->build_seconds = b.seconds;
+    // the refit's records and levels belong to the old tree: the next rt_scene_update sets them up for this one
+    (void)hipFree(sc->d_refit_nodes);
+    (void)hipFree(sc->d_refit_recs);
+    (void)hipFree(sc->d_refit_exact);
+    (void)hipFree(sc->d_refit_radius);
+    sc->d_refit_nodes = nullptr;
+    sc->d_refit_recs = nullptr;
+    sc->d_refit_exact = sc->d_refit_radius = nullptr;
+    sc->refit_level_end.clear();
+    sc->sah_build = sc->sah_now = quads_sah(sc->h_quads);
+    {   // the reference's tree is a function of the triangles: kept (renumbered for the new leaf order) unless they moved
+        std::lock_guard<std::mutex> lock(sc->ref_mutex);
+        if (keep_ref) {
+            std::swap(sc->d_ref_prims, d_ref_prims);
+            std::swap(sc->d_ref_leaf_of, d_ref_leaf_of);
+            (void)hipFree(d_ref_prims);
+            (void)hipFree(d_ref_leaf_of);
+        } else if (moved) {
+            (void)hipFree(sc->d_ref_nodes);
+            (void)hipFree(sc->d_ref_prims);
+            (void)hipFree(sc->d_ref_leaf_of);
+            (void)hipFree(sc->d_ref_parent);
+            sc->d_ref_nodes = nullptr;
+            sc->d_ref_prims = sc->d_ref_leaf_of = sc->d_ref_parent = nullptr;
+            sc->ref_nodes_count = sc->ref_depth = 0;
+            sc->ref_root_leaf = true;
+            sc->ref_ready = false;
+        }
+    }
+    if (moved) sc->h_tri9 = h_new;
+    {   // replicas on other devices (rt_render_multi) hold the old tree: dropped, recreated on next use
         std::lock_guard<std::mutex> lock(sc->replica_mutex);
         for (rt_scene *r : sc->replicas) delete r;
         sc->replicas.clear();
@@ -3986,7 +4568,15 @@ const char *rt_build_id(void) { return RT_BUILD_ID; }
 int rt_scene_create(const float *tri_p0p1p2, int n_tris, const int32_t *tri_material, const int32_t *tri_light,
                     const rt_material *materials, int n_materials, const rt_light *lights, int n_lights,
                     rt_scene **out_scene) {
+    return rt_scene_create_flags(tri_p0p1p2, n_tris, tri_material, tri_light, materials, n_materials, lights, n_lights, 0u, out_scene);
+}
+
+int rt_scene_create_flags(const float *tri_p0p1p2, int n_tris, const int32_t *tri_material, const int32_t *tri_light,
+                          const rt_material *materials, int n_materials, const rt_light *lights, int n_lights,
+                          uint32_t scene_flags, rt_scene **out_scene) {
     if (!out_scene) return fail("rt_scene_create: out_scene is null");
+    if (scene_flags & ~(uint32_t)RT_SCENE_DEVICE_BVH) return fail("rt_scene_create_flags: unknown scene flags");
+    const bool device_bvh = (scene_flags & RT_SCENE_DEVICE_BVH) != 0;
     *out_scene = nullptr;
     if (n_tris < 0 || n_materials < 0 || n_lights < 0) return fail("rt_scene_create: negative count");
     if (n_tris >= (1 << 24)) return fail("rt_scene_create: more than 2^24 - 1 triangles (24-bit triangle addressing)");
@@ -4014,7 +4604,28 @@ int rt_scene_create(const float *tri_p0p1p2, int n_tris, const int32_t *tri_mate
     bool use_lbvh = false;
     if (const char *e = knob("RT_BVH_BUILDER")) use_lbvh = std::string(e) == "lbvh";
     rtbvh::Result bvh;
-    if (use_lbvh && n_tris >= 2) {
+    if (device_bvh) {
+        // the device PLOC builder on this device (the scene's); with no triangles there is nothing to build
+        if (n_tris > 0) {
+            float *d_v = nullptr;
+            DevScope tmp;
+            if (tmp.alloc(d_v, 9 * (size_t)n_tris)) return 1;
+            HIP_TRY(hipMemcpy(d_v, tri_p0p1p2, sizeof(float) * 9 * (size_t)n_tris, hipMemcpyHostToDevice));
+            PlocBuild b;
+            if (build_ploc_device(d_v, n_tris, nullptr, b, "rt_scene_create_flags")) return 1;
+            if (!ploc_result_ok(b, n_tris)) return fail("rt_scene_create_flags: the device-built tree is malformed");
+            bvh.quads = b.quads;
+            bvh.order = b.order;
+            bvh.max_depth = b.max_depth;
+            bvh.stack_bound = b.stack_bound;
+            bvh.num_leaves = b.leaves;
+            sc->build_seconds = b.seconds;
+        } else {
+            bvh = rtbvh::build(tri_p0p1p2, 0);
+        }
+        sc->builder = 2;
+        sc->top_prefix = true;
+    } else if (use_lbvh && n_tris >= 2) {
         int depth = 0;
         if (build_lbvh_device(tri_p0p1p2, n_tris, bvh.pairs, bvh.order, depth, sc->build_seconds)) return 1;
         if (!validate_pairs(bvh.pairs, n_tris) || depth < 1) return fail("rt_scene_create: device BVH build produced a malformed tree");
@@ -4044,6 +4655,7 @@ int rt_scene_create(const float *tri_p0p1p2, int n_tris, const int32_t *tri_mate
     if (n_lights > 0) sc->h_lights.assign(lights, lights + n_lights);
     sc->wide = true;  // 4-wide nodes (two pair-style records each): half the dependent fetches per ray; RT_BVH_WIDE=0: 2-wide
     if (const char *e = knob("RT_BVH_WIDE")) sc->wide = atoi(e) != 0;
+    if (device_bvh && !sc->wide) return fail("rt_scene_create_flags: the device builder writes the 4-wide format only (RT_BVH_WIDE=0 is set)");
     // a tree too deep for the 4-wide walk's stack (up to 3 entries per level) may still fit the 2-wide walk's (1 per level):
     // a very deep LBVH, or a host tree the reinsertion pass deepened
     if (sc->wide && bvh.stack_bound > kMaxStackBound) sc->wide = false;
@@ -4148,6 +4760,14 @@ int rt_scene_update(rt_scene *scene, const float *tri_p0p1p2, int n_tris) {
 
 int rt_scene_update_device(rt_scene *scene, const float *d_tri_p0p1p2, int n_tris, void *stream) {
     return scene_update_impl(scene, d_tri_p0p1p2, n_tris, true, (hipStream_t)stream, "rt_scene_update_device");
+}
+
+int rt_scene_rebuild(rt_scene *scene, const float *tri_p0p1p2, int n_tris) {
+    return scene_rebuild_impl(scene, tri_p0p1p2, n_tris, false, nullptr, "rt_scene_rebuild");
+}
+
+int rt_scene_rebuild_device(rt_scene *scene, const float *d_tri_p0p1p2, int n_tris, void *stream) {
+    return scene_rebuild_impl(scene, d_tri_p0p1p2, n_tris, true, (hipStream_t)stream, "rt_scene_rebuild_device");
 }
 
 int rt_scene_refit_info(const rt_scene *scene, int64_t *refits, double *seconds_last, double *sah_ratio) {
@@ -4295,9 +4915,11 @@ static const rt_scene *scene_on_device(const rt_scene *scene, int device) {
         return nullptr;
     }
     rt_scene *rep = nullptr;
-    const int rc = rt_scene_create(scene->h_tri9.data(), scene->n_tris, scene->h_tri_material.data(),
-                                   scene->h_tri_light.empty() ? nullptr : scene->h_tri_light.data(), scene->h_materials.data(),
-                                   scene->n_mats, scene->h_lights.data(), scene->n_lights, &rep);
+    // (a scene whose tree was built on the device gets one built on the replica's device)
+    const int rc = rt_scene_create_flags(scene->h_tri9.data(), scene->n_tris, scene->h_tri_material.data(),
+                                         scene->h_tri_light.empty() ? nullptr : scene->h_tri_light.data(), scene->h_materials.data(),
+                                         scene->n_mats, scene->h_lights.data(), scene->n_lights,
+                                         scene->builder == 2 ? (uint32_t)RT_SCENE_DEVICE_BVH : 0u, &rep);
     (void)hipSetDevice(saved);
     if (rc != 0) return nullptr;
     scene->replicas.push_back(rep);
