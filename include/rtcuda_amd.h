@@ -151,10 +151,9 @@ void rt_scene_destroy(rt_scene *scene);
 
 /* out[0]=node records, out[1]=triangles, out[2]=max depth, out[3]=leaves */
 int rt_scene_info(const rt_scene *scene, int64_t out[4]);
-/* Which BVH builder made the scene (0 = host SAH, the default; 1 = device LBVH, RT_BVH_BUILDER=lbvh; 2 = device PLOC,
- * RT_SCENE_DEVICE_BVH or rt_scene_rebuild) and
- * how long the build took (host wall clock / HIP events).  The reference times "Top-down constructing BVH"
- * on stdout (bvh.cuh:106-201). */
+/* Which BVH builder made the scene (0 = host SAH, the default; 2 = device PLOC, RT_SCENE_DEVICE_BVH or rt_scene_rebuild;
+ * 1 is retired and no longer reported) and how long the build took (host wall clock / HIP events).  The reference times
+ * "Top-down constructing BVH" on stdout (bvh.cuh:106-201). */
 int rt_scene_build_info(const rt_scene *scene, int *builder, double *seconds);
 
 /* ---- moving geometry (no reference counterpart: its Bvh is built once, bvh.cuh:30-219) ----------------------------

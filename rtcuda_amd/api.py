@@ -244,7 +244,7 @@ class Scene:
         b, sec = ctypes.c_int(0), ctypes.c_double(0.0)
         _check(self.L.rt_scene_build_info(self.h, ctypes.byref(b), ctypes.byref(sec)), "rt_scene_build_info", self.L)
         return {"pairs": int(out[0]), "tris": int(out[1]), "max_depth": int(out[2]), "leaves": int(out[3]),
-                "builder": {0: "sah", 1: "lbvh", 2: "ploc"}.get(b.value, str(b.value)), "build_seconds": sec.value}
+                "builder": {0: "sah", 2: "ploc"}.get(b.value, str(b.value)), "build_seconds": sec.value}
 
     # ---- moving geometry: new vertex positions, same triangles, materials and lights (rt_scene_update)
     def update(self, tris) -> None:

@@ -11,8 +11,9 @@
 //      mutual nearest neighbours merge into a new inner node at the smaller position; survivors are compacted in order and
 //      new node ids come from the prefix sum of the merges.  Until one cluster is left.
 //   3. leaves, bottom up at merge time: a node of at most max_leaf triangles is a leaf when n * A <= trav * A + C(l) + C(r).
-//   4. collapse to 4-wide top down, breadth first: the inner child with the largest area is opened until a node has four
-//      children (rtbvh::quads_from_pairs' rule); leaf triangles in depth-first order, the lower position first.
+//   4. collapse to 4-wide top down, breadth first: while a node has fewer than four children, its inner child with the
+//      largest half area (the first of equals) is replaced by that child's two children, appended at the end; leaf
+//      triangles in depth-first order, the lower position first.
 #ifndef RT_PLOC_H
 #define RT_PLOC_H
 

@@ -905,7 +905,7 @@ __device__ __forceinline__ void inner_step(const DScene &sc, V3 o, V3 inv, float
                                            int *over, int stack_cap, const float4 *top = nullptr, int top_n = 0) {
     // (2-wide records) the top of the LDS part of the stack, in case this step ends in a pop: see below
     const int spec_top = SHALLOW ? stack[max(sp - 1, 0) * kBlock] : stack[max(min(sp - 1, stack_cap - 1), 0) * kBlock];
-    // 2-wide: one 64-byte record, q0..q3.  4-wide: the node's 128 bytes are laid out BY PLANE (upload_node_records): per axis a
+    // 2-wide: one 64-byte record, q0..q3.  4-wide: the node's 128 bytes are laid out BY PLANE (k_refit_emit): per axis a
     // 16-byte word with the four children's lower bounds and one with their upper bounds, then the four links.  Which of the two
     // is the NEAR plane of an axis depends on the sign of 1 / d alone, so each lane fetches near and far planes by address
     // (word index 2 * axis + sign, and the other one) and the slab test needs no min / max per axis: 24 instructions fewer per
@@ -1011,7 +1011,7 @@ __device__ __forceinline__ void inner_step(const DScene &sc, V3 o, V3 inv, float
         // instead of three and their scalar ANDs (tmax >= 0 always)
         // plane distance = b * (1 / d) + s, s = -o * (1 / d): ONE packed fma per pair of planes where (b - o) * (1 / d) takes
         // two instructions.  s is rounded on its own, which moves the planes of an axis by up to 2^-24 |o| as the ray sees
-        // them: the records are padded for that (rt_bvh.h, pad_quads_for_origins; ensure_origin_radius on the host).
+        // them: the records are padded for that (k_refit_emit, rt_bvh.h pad_quads_for_origins; ensure_origin_radius).
         // Near and far planes were picked by the sign of 1 / d when they were fetched: monotone rounding makes the near
         // plane's distance the smaller of the two, the very value min() would pick.
         const v2f sx = {-o.x * inv.x, -o.x * inv.x}, sy = {-o.y * inv.y, -o.y * inv.y}, sz = {-o.z * inv.z, -o.z * inv.z};
@@ -2350,37 +2350,12 @@ __global__ void k_test_draw(DPools p, int n, int draws, uint32_t *__restrict__ s
     state6[6 * (size_t)i + 4] = rs.v3;
     state6[6 * (size_t)i + 5] = rs.v4;
 }
-// ============================================================================ device BVH build (LBVH)
-// a BVH build on the GPU.  Optional (RT_BVH_BUILDER=lbvh): a linear BVH --
-// 30-bit Morton codes of the triangle centroids, sorted, binary radix tree by longest common prefix
-// (Karras 2012), bottom-up box fit -- emitted in the same 2-wide record format the kernels walk.  It
-// builds in about a millisecond but has no surface-area heuristic, so traversal is slower than through
-// the host SAH tree; the image is the same (closest accepted triangle does not depend on the tree).
-__device__ __forceinline__ unsigned morton_expand(unsigned v) {  // 10 bits -> every third bit
-    v = (v * 0x00010001u) & 0xFF0000FFu;
-    v = (v * 0x00000101u) & 0x0F00F00Fu;
-    v = (v * 0x00000011u) & 0xC30C30C3u;
-    v = (v * 0x00000005u) & 0x49249249u;
-    return v;
+// ============================================================================ device BVH: refit and build
+__device__ __forceinline__ float pad_ulps2(float v, int dir) {  // 2 ulps outward, as the host builder pads
+    v = nextafterf(v, dir < 0 ? -kFltMax : kFltMax);
+    return nextafterf(v, dir < 0 ? -kFltMax : kFltMax);
 }
-__global__ void k_lbvh_keys(const float *__restrict__ verts, int n, int n_pad, float lox, float loy, float loz, float sx,
-                            float sy, float sz, unsigned long long *__restrict__ keys) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_pad) return;
-    if (i >= n) {
-        keys[i] = ~0ull;  // padding sorts last
-        return;
-    }
-    const float *v = verts + 9 * (size_t)i;
-    float cx = (fminf(v[0], fminf(v[3], v[6])) + fmaxf(v[0], fmaxf(v[3], v[6]))) * 0.5f;
-    float cy = (fminf(v[1], fminf(v[4], v[7])) + fmaxf(v[1], fmaxf(v[4], v[7]))) * 0.5f;
-    float cz = (fminf(v[2], fminf(v[5], v[8])) + fmaxf(v[2], fmaxf(v[5], v[8]))) * 0.5f;
-    unsigned qx = (unsigned)fminf(fmaxf((cx - lox) * sx, 0.f), 1023.f);
-    unsigned qy = (unsigned)fminf(fmaxf((cy - loy) * sy, 0.f), 1023.f);
-    unsigned qz = (unsigned)fminf(fmaxf((cz - loz) * sz, 0.f), 1023.f);
-    unsigned code = (morton_expand(qx) << 2) | (morton_expand(qy) << 1) | morton_expand(qz);
-    keys[i] = ((unsigned long long)code << 32) | (unsigned)i;  // the index makes every key unique
-}
+// one compare-exchange step of a bitonic sort of n_pad (a power of 2) keys
 __global__ void k_bitonic_step(unsigned long long *__restrict__ keys, int n_pad, int j, int k) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_pad) return;
@@ -2394,118 +2369,11 @@ __global__ void k_bitonic_step(unsigned long long *__restrict__ keys, int n_pad,
         }
     }
 }
-__device__ __forceinline__ int lbvh_delta(const unsigned long long *keys, int n, int i, int j) {
-    if (j < 0 || j >= n) return -1;
-    return __clzll((long long)(keys[i] ^ keys[j]));
-}
-// child encoding: internal node k -> k, leaf k (sorted position) -> ~k
-__global__ void k_lbvh_hierarchy(const unsigned long long *__restrict__ keys, int n, int *__restrict__ left,
-                                 int *__restrict__ right, int *__restrict__ parent_int, int *__restrict__ parent_leaf) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n - 1) return;
-    int d = (lbvh_delta(keys, n, i, i + 1) - lbvh_delta(keys, n, i, i - 1)) >= 0 ? 1 : -1;
-    int dmin = lbvh_delta(keys, n, i, i - d);
-    int lmax = 2;
-    while (lbvh_delta(keys, n, i, i + lmax * d) > dmin) lmax *= 2;
-    int l = 0;
-    for (int t = lmax / 2; t >= 1; t /= 2)
-        if (lbvh_delta(keys, n, i, i + (l + t) * d) > dmin) l += t;
-    int j = i + l * d;
-    int dnode = lbvh_delta(keys, n, i, j);
-    int s = 0, t = l;
-    do {
-        t = (t + 1) >> 1;
-        if (lbvh_delta(keys, n, i, i + (s + t) * d) > dnode) s += t;
-    } while (t > 1);
-    int gamma = i + s * d + min(d, 0);
-    int lo = min(i, j), hi = max(i, j);
-    int lc = (lo == gamma) ? ~gamma : gamma;
-    int rc = (hi == gamma + 1) ? ~(gamma + 1) : gamma + 1;
-    left[i] = lc;
-    right[i] = rc;
-    if (lc < 0) parent_leaf[~lc] = i; else parent_int[lc] = i;
-    if (rc < 0) parent_leaf[~rc] = i; else parent_int[rc] = i;
-    if (i == 0) parent_int[0] = -1;
-}
-__device__ __forceinline__ void lbvh_leaf_box(const float *verts, const unsigned long long *keys, int pos, float *b) {
-    const float *v = verts + 9 * (size_t)(unsigned)(keys[pos] & 0xffffffffu);
-    for (int a = 0; a < 3; a++) {
-        b[a] = fminf(v[a], fminf(v[3 + a], v[6 + a]));
-        b[3 + a] = fmaxf(v[a], fmaxf(v[3 + a], v[6 + a]));
-    }
-}
-// bottom-up: the second thread to arrive at an internal node owns it (its sibling subtree is complete)
-__global__ void k_lbvh_fit(const float *__restrict__ verts, const unsigned long long *__restrict__ keys, int n,
-                           const int *__restrict__ left, const int *__restrict__ right, const int *__restrict__ parent_int,
-                           const int *__restrict__ parent_leaf, float *boxes, int *depth, int *arrivals) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    int cur = parent_leaf[i];
-    for (int guard = 0; cur >= 0 && guard < 4096; guard++) {  // (a radix tree over 64-bit keys is at most 64 deep)
-        __threadfence();  // publish what this thread wrote below before announcing arrival
-        if (atomicAdd(&arrivals[cur], 1) == 0) return;
-        __threadfence();  // second arrival: the sibling's box and depth are visible from here on
-        float b[6] = {kFltMax, kFltMax, kFltMax, -kFltMax, -kFltMax, -kFltMax};
-        int dep = 0;
-        const int ch[2] = {left[cur], right[cur]};
-        for (int c = 0; c < 2; c++) {
-            float cb[6];
-            int cd = 0;
-            if (ch[c] < 0) {
-                lbvh_leaf_box(verts, keys, ~ch[c], cb);
-            } else {
-                const volatile float *vb = boxes + 6 * (size_t)ch[c];
-                for (int a = 0; a < 6; a++) cb[a] = vb[a];
-                cd = ((const volatile int *)depth)[ch[c]];
-            }
-            for (int a = 0; a < 3; a++) {
-                b[a] = fminf(b[a], cb[a]);
-                b[3 + a] = fmaxf(b[3 + a], cb[3 + a]);
-            }
-            dep = max(dep, cd);
-        }
-        for (int a = 0; a < 6; a++) boxes[6 * (size_t)cur + a] = b[a];
-        depth[cur] = dep + 1;
-        cur = parent_int[cur];
-    }
-}
-__device__ __forceinline__ float lbvh_pad(float v, int dir) {  // 2 ulps outward, as the host builder pads
-    v = nextafterf(v, dir < 0 ? -kFltMax : kFltMax);
-    return nextafterf(v, dir < 0 ? -kFltMax : kFltMax);
-}
-__global__ void k_lbvh_emit(const float *__restrict__ verts, const unsigned long long *__restrict__ keys, int n,
-                            const int *__restrict__ left, const int *__restrict__ right, const float *__restrict__ boxes,
-                            float *__restrict__ pairs, int *__restrict__ order) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) order[i] = (int)(unsigned)(keys[i] & 0xffffffffu);
-    if (i >= n - 1) return;
-    float *rec = pairs + 16 * (size_t)i;
-    const int ch[2] = {left[i], right[i]};
-    for (int c = 0; c < 2; c++) {
-        float cb[6];
-        int link;
-        if (ch[c] < 0) {
-            lbvh_leaf_box(verts, keys, ~ch[c], cb);
-            link = ~(((~ch[c]) << 3) | 1);  // leaf reference: one triangle at sorted position
-        } else {
-            for (int a = 0; a < 6; a++) cb[a] = boxes[6 * (size_t)ch[c] + a];
-            link = ch[c];
-        }
-        for (int a = 0; a < 3; a++) {
-            rec[6 * c + a] = lbvh_pad(cb[a], -1);
-            rec[6 * c + 3 + a] = lbvh_pad(cb[3 + a], +1);
-        }
-        rec[12 + c] = __int_as_float(link);
-    }
-    rec[14] = 0.f;
-    rec[15] = 0.f;
-}
 
-// ---- refit (rt_scene_update): new vertex positions for the same tree.  Topology, leaf order, materials and lights stay;
-// triangle records, boxes and the tables derived from the light triangles are recomputed on the scene's device.
-// Triangle records in leaf order with the expressions of rt_scene_create (this file is built with -ffp-contract=off, so a
-// multiplication and a subtraction are each rounded once, on the device as on the host: the same bits).
-__global__ void k_refit_tris(const float *__restrict__ verts, const int *__restrict__ order, int n, float4 *__restrict__ tris) {
+// ---- the scene's arrays in leaf order (emit_scene: rt_scene_create, rt_scene_update, rt_scene_rebuild)
+// Triangle records: e1 = p0 - p1, e2 = p2 - p0, n = e1 x e2 (triangle.cuh:6-7), each operation rounded once in fp32 (this
+// file is built with -ffp-contract=off).
+__global__ void k_leaf_tris(const float *__restrict__ verts, const int *__restrict__ order, int n, float4 *__restrict__ tris) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n) return;
     const float *q = verts + 9 * (size_t)order[k];
@@ -2516,6 +2384,8 @@ __global__ void k_refit_tris(const float *__restrict__ verts, const int *__restr
     tris[3 * (size_t)k + 1] = make_float4(e1y, e1z, e2x, e2y);
     tris[3 * (size_t)k + 2] = make_float4(e2z, nx, ny, nz);
 }
+// ---- refit (rt_scene_update): new vertex positions for the same tree.  Topology, leaf order, materials and lights stay;
+// triangle records, boxes and the tables derived from the light triangles are recomputed on the scene's device.
 // One level of the 4-wide tree (launched deepest level first, so a launch boundary orders every hand-off between levels).
 // A node's child boxes, EXACT: a leaf child's from the caller's vertices p0, p1, p2 (as rtbvh::build_binary), an inner
 // child's the union the deeper launch left in `exact`.  They are written into the node's two builder records padded by
@@ -2548,17 +2418,22 @@ __global__ void k_refit_level(const float *__restrict__ verts, const int *__rest
         }
         float *dst = (k & 1) ? rec.rbox : rec.lbox;
         for (int a = 0; a < 3; a++) {
-            dst[a] = lbvh_pad(b[a], -1);
-            dst[3 + a] = lbvh_pad(b[3 + a], +1);
+            dst[a] = pad_ulps2(b[a], -1);
+            dst[3 + a] = pad_ulps2(b[3 + a], +1);
             u[a] = fminf(u[a], b[a]);
             u[3 + a] = fmaxf(u[3 + a], b[3 + a]);
         }
     }
     for (int a = 0; a < 6; a++) exact[6 * (size_t)j + a] = u[a];
 }
-// The records as the kernels read them (upload_node_records): padded for ray origins within the radius (the double
-// arithmetic of rtbvh::pad_quads_for_origins) and laid out by plane, 128 bytes per node.  The radius is the one the
-// records were padded for, grown to the new bounds (rtbvh::quads_abs_bounds): those of the root's children, which contain
+// The 4-wide records as the kernels read them, the only writer of that layout (emit_nodes: creation, refit, rebuild and the
+// re-padding for far ray origins).  The builder's unpadded records are padded for ray origins within the radius -- the same
+// arithmetic as rtbvh::pad_quads_for_origins, its host reference -- and laid out BY PLANE, 128 bytes per node: node j =
+// builder records 2j (children 0, 1) and 2j + 1 (children 2, 3) -> word 2a: the four children's lower bounds of axis a,
+// word 2a + 1: their upper bounds (a = x, y, z), word 6: the four links, word 7: spare.  A node step loads seven 16-byte
+// words (a divergent wave-wide load occupies the CU's texture addresser for about a cycle per active lane:
+// profiles/r05_gather_rate.txt) and picks near and far planes by address instead of by min / max (inner_step).  The radius
+// is the one asked for, grown to the records' bounds (rtbvh::quads_abs_bounds): those of the root's children, which contain
 // every box below them.  Node 0's thread reports it.
 __global__ void k_refit_emit(const rtbvh::Pair *__restrict__ recs, int n_nodes, float r0, float r1, float r2,
                              float *__restrict__ out, float *__restrict__ radius_out) {
@@ -2846,8 +2721,8 @@ __global__ void __launch_bounds__(256) k_ploc_level_emit(const int2 *__restrict_
         const float *b = v.box(kids[k]);
         float *dst = (k & 1) ? p.rbox : p.lbox;
         for (int a = 0; a < 3; a++) {
-            dst[a] = lbvh_pad(b[a], -1);
-            dst[3 + a] = lbvh_pad(b[3 + a], +1);
+            dst[a] = pad_ulps2(b[a], -1);
+            dst[3 + a] = pad_ulps2(b[3 + a], +1);
         }
         int32_t link;
         if (v.is_leaf(kids[k])) {
@@ -2869,18 +2744,18 @@ __global__ void __launch_bounds__(256) k_ploc_level_emit(const int2 *__restrict_
     recs[2 * (size_t)(level_base + i)] = rec[0];
     recs[2 * (size_t)(level_base + i) + 1] = rec[1];
 }
-// ---- re-emitting a scene for a new leaf order (rt_scene_rebuild)
-__global__ void k_ploc_inverse(const int *__restrict__ order, int n, int *__restrict__ inverse) {
+// ---- more of the scene's arrays in leaf order (emit_scene), and the reference's tree for a new one (rt_scene_rebuild)
+__global__ void k_leaf_inverse(const int *__restrict__ order, int n, int *__restrict__ inverse) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k < n) inverse[order[k]] = k;
 }
 // (material, light) of every triangle in leaf order, from the caller's arrays in their order
-__global__ void k_ploc_tri_info(const int2 *__restrict__ caller_info, const int *__restrict__ order, int n, int2 *__restrict__ info) {
+__global__ void k_leaf_tri_info(const int2 *__restrict__ caller_info, const int *__restrict__ order, int n, int2 *__restrict__ info) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k < n) info[k] = caller_info[order[k]];
 }
 // area lights name their triangle in the caller's order (rt_light.triangle): the leaf-order index the kernels read
-__global__ void k_ploc_lights(Light *__restrict__ lights, int n_lights, const int *__restrict__ inverse) {
+__global__ void k_leaf_lights(Light *__restrict__ lights, int n_lights, const int *__restrict__ inverse) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n_lights && lights[i].type == RT_AREA_LIGHT) lights[i].tri = inverse[lights[i].tri];
 }
@@ -2894,19 +2769,33 @@ __global__ void k_ploc_remap_ref(const int *__restrict__ prims, const int *__res
 }
 
 // ============================================================================ host side
+// What the kernels read in leaf order, and the tree: a scene's own arrays (rt_scene_create, rt_scene_update) or new ones that
+// replace them once they are complete (rt_scene_rebuild).  Written by emit_scene.
+struct SceneArrays {
+    const int *order;          // leaf order -> caller's triangle index
+    const rtbvh::Pair *recs;   // 4-wide: the builder's unpadded records
+    int n_records;
+    float4 *nodes, *tris, *shade;
+    int2 *info;
+    Light *lights;
+    float *tables;
+};
+
 struct rt_scene {
     int device = 0;
     int n_tris = 0, n_nodes = 0, max_depth = 0, stack_bound = 1, n_leaves = 0, n_lights = 0, n_mats = 0;
     float4 *d_nodes = nullptr;
     bool wide = false;  // node records: 4-wide (two pair-style records per node, rtbvh::Result::quads) or 2-wide (rtbvh::Pair)
-    // 4-wide records are padded for the ray origins that will be traced (rt_bvh.h, pad_quads_for_origins): the builder's
-    // records, the radius the device copy is padded for at the moment, and a lock for the (rare) re-padding
+    // 4-wide: the builder's unpadded records on the device (links fixed by the build, boxes refit by rt_scene_update) and on
+    // the host; d_nodes holds them padded for the ray origins that will be traced (rt_bvh.h, pad_quads_for_origins) within
+    // origin_radius, which only grows (k_refit_emit reports it in d_radius).  pad_mutex serialises every writer of these.
+    rtbvh::Pair *d_recs = nullptr;
     std::vector<rtbvh::Pair> h_quads;
+    float *d_radius = nullptr;
     mutable float origin_radius[3] = {0.f, 0.f, 0.f};
     mutable std::mutex pad_mutex;
-    bool top_prefix = true;  // the first records are the top of the tree in level order (host builder)
-    double build_seconds = 0.0;  // BVH build time (host wall clock, or device events for the LBVH)
-    int builder = 0;             // 0 host SAH, 1 device LBVH, 2 device PLOC (RT_SCENE_DEVICE_BVH, rt_scene_rebuild)
+    double build_seconds = 0.0;  // BVH build time (host wall clock, or device events for PLOC)
+    int builder = 0;             // 0 host SAH, 2 device PLOC (RT_SCENE_DEVICE_BVH, rt_scene_rebuild)
     float4 *d_tris = nullptr;
     int2 *d_tri_info = nullptr;
     float4 *d_tri_shade = nullptr;
@@ -2921,6 +2810,7 @@ struct rt_scene {
     // for it (ensure_ref_tree) from the caller's triangles kept here
     std::vector<float> h_tri9;
     // rt_render_multi: what a replica of this scene on another device is created from, and the replicas made so far
+    // (emit_scene also reads the materials of the triangles and the lights from here)
     std::vector<int32_t> h_tri_material, h_tri_light;
     std::vector<rt_material> h_materials;
     std::vector<rt_light> h_lights;
@@ -2936,13 +2826,10 @@ struct rt_scene {
     mutable bool ref_root_leaf = true;
     mutable double build_seconds_ref = 0.0;  // host time of the reference-tree build + upload (one-off, first render that needs it)
     // rt_scene_update (4-wide only): the tree's nodes grouped by level, deepest level first (refit_level_end[l] = end of level
-    // l's span), the builder records on the device (links fixed at creation, boxes refit), the exact box of every node (scratch
-    // between the level launches) and the radius the refit padded for -- all set up by the first update
+    // l's span) and the exact box of every node (scratch between the level launches) -- set up by the first update
     std::vector<int> refit_level_end;
     int *d_refit_nodes = nullptr;
-    rtbvh::Pair *d_refit_recs = nullptr;
     float *d_refit_exact = nullptr;
-    float *d_refit_radius = nullptr;
     int64_t refits = 0;
     double refit_seconds = 0.0;                 // device time of the last refit (HIP events)
     double sah_build = 0.0, sah_now = 0.0;      // surface-area cost of the 4-wide tree at build time / now
@@ -2950,24 +2837,43 @@ struct rt_scene {
     rt_scene(const rt_scene &) = delete;
     rt_scene &operator=(const rt_scene &) = delete;
     ~rt_scene() {  // (every early return of rt_scene_create goes through here: nothing leaks on an error path)
-        for (rt_scene *r : replicas) delete r;
-        (void)hipFree(d_nodes);
-        (void)hipFree(d_tris);
-        (void)hipFree(d_tri_info);
-        (void)hipFree(d_tri_shade);
-        (void)hipFree(d_mats);
-        (void)hipFree(d_lights);
-        (void)hipFree(d_order);
-        (void)hipFree(d_tables);
-        (void)hipFree(d_ref_nodes);
-        (void)hipFree(d_ref_prims);
-        (void)hipFree(d_ref_leaf_of);
-        (void)hipFree(d_ref_parent);
-        (void)hipFree(d_refit_nodes);
-        (void)hipFree(d_refit_recs);
-        (void)hipFree(d_refit_exact);
-        (void)hipFree(d_refit_radius);
+        drop_replicas();
+        drop_ref_tree();
+        drop_refit();
+        for (void *q : {(void *)d_nodes, (void *)d_recs, (void *)d_radius, (void *)d_tris, (void *)d_tri_info, (void *)d_tri_shade,
+                        (void *)d_mats, (void *)d_lights, (void *)d_order, (void *)d_tables})
+            (void)hipFree(q);
     }
+    // the reference's tree is a function of the triangles: the next render that needs it builds it again from h_tri9
+    void drop_ref_tree() {
+        std::lock_guard<std::mutex> lock(ref_mutex);
+        for (void *q : {(void *)d_ref_nodes, (void *)d_ref_prims, (void *)d_ref_leaf_of, (void *)d_ref_parent}) (void)hipFree(q);
+        d_ref_nodes = nullptr;
+        d_ref_prims = d_ref_leaf_of = d_ref_parent = nullptr;
+        ref_nodes_count = ref_depth = 0;
+        ref_root_leaf = true;
+        ref_ready = false;
+    }
+    // replicas on other devices (rt_render_multi) hold the old geometry or tree: recreated from the host copies on next use
+    void drop_replicas() {
+        std::lock_guard<std::mutex> lock(replica_mutex);
+        for (rt_scene *r : replicas) delete r;
+        replicas.clear();
+    }
+    // the refit's levels belong to one tree: the next rt_scene_update sets them up for the scene's (caller holds pad_mutex)
+    void drop_refit() {
+        (void)hipFree(d_refit_nodes);
+        (void)hipFree(d_refit_exact);
+        d_refit_nodes = nullptr;
+        d_refit_exact = nullptr;
+        refit_level_end.clear();
+    }
+    void set_order(const std::vector<int32_t> &order) {
+        h_order.assign(order.begin(), order.end());
+        h_inverse.assign(h_order.size(), 0);
+        for (size_t k = 0; k < h_order.size(); k++) h_inverse[(size_t)h_order[k]] = (int)k;
+    }
+    SceneArrays arrays() const { return {d_order, d_recs, n_nodes, d_nodes, d_tris, d_tri_shade, d_tri_info, d_lights, d_tables}; }
     DScene dev() const {
         DScene s;
         s.nodes = d_nodes;
@@ -3050,115 +2956,32 @@ const std::vector<uint32_t> &jump_powers() {
     return table;
 }
 
-// Structural check of 2-wide records before they are uploaded (a malformed tree would hang the GPU):
-// every record reachable from the root exactly once, every triangle position in exactly one leaf.
-bool validate_pairs(const std::vector<rtbvh::Pair> &pairs, int n_tris) {
-    const int np = (int)pairs.size();
-    if (np == 0) return false;
-    std::vector<char> seen_pair(np, 0), seen_tri((size_t)std::max(n_tris, 1), 0);
-    std::vector<int> todo{0};
-    seen_pair[0] = 1;
-    int visited = 0, tris = 0;
-    while (!todo.empty()) {
-        int pi = todo.back();
-        todo.pop_back();
-        visited++;
-        const int links[2] = {pairs[pi].llink, pairs[pi].rlink};
-        for (int l : links) {
-            if (l == rtbvh::kNoChild) continue;
-            if (l >= 0) {
-                if (l >= np || seen_pair[l]) return false;
-                seen_pair[l] = 1;
-                todo.push_back(l);
-            } else {
-                int ref = ~l, first = ref >> 3, count = ref & 7;
-                if (count <= 0 || first < 0 || first + count > n_tris) return false;
-                for (int k = first; k < first + count; k++) {
-                    if (seen_tri[k]) return false;
-                    seen_tri[k] = 1;
-                    tris++;
-                }
-            }
-        }
-    }
-    return visited == np && tris == n_tris;
-}
-
-// The same for the 4-wide format (two consecutive records per node; inner links are even record indices), plus the
-// invariant the kernels' box test rests on: a child is absent (link kNoChild) if and only if its box is all +inf -- the
-// one-comparison slab test of inner_step<true> never looks at links.
-// Device layout.  2-wide: a 64-byte record with the two children's bounds INTERLEAVED --
+// 2-wide nodes (RT_BVH_WIDE=0, or a host tree too deep for the 4-wide walk's stack): a 64-byte record with the two children's
+// bounds INTERLEAVED --
 //   (l.lo.x, r.lo.x, l.lo.y, r.lo.y | l.lo.z, r.lo.z, l.hi.x, r.hi.x | l.hi.y, r.hi.y, l.hi.z, r.hi.z | llink, rlink, spare, spare)
 // -- so that every (left, right) pair of bounds arrives in an aligned register pair and the slab arithmetic of both children
-// runs as packed fp32, see inner_step.  4-wide: a node (two builder records: children 0, 1 | children 2, 3, rt_bvh.h `quads`,
-// padded for ray origins within `radius`: pad_quads_for_origins) is 128 bytes laid out BY PLANE -- see below and inner_step:
-// a node step loads seven 16-byte words (a divergent wave-wide load occupies the CU's texture addresser for about a cycle
-// per active lane: profiles/r05_gather_rate.txt) and picks near and far planes by address instead of by min / max.
-int upload_node_records(const rt_scene *sc, const std::vector<rtbvh::Pair> &base, const float radius[3]) {
-    std::vector<rtbvh::Pair> padded;
-    const std::vector<rtbvh::Pair> *recs = &base;
-    if (sc->wide) {
-        rtbvh::pad_quads_for_origins(base, radius, padded);
-        recs = &padded;
-    }
-    if ((size_t)sc->n_nodes != recs->size()) return fail("upload_node_records: record count changed");
-    std::vector<float> inter(16 * recs->size());
-    if (!sc->wide) {
-        for (size_t k = 0; k < recs->size(); k++) {
-            const rtbvh::Pair &pr = (*recs)[k];
-            float *r = &inter[16 * k];
-            for (int a = 0; a < 6; a++) {
-                r[2 * a] = pr.lbox[a];
-                r[2 * a + 1] = pr.rbox[a];
-            }
-            memcpy(&r[12], &pr.llink, 4);
-            memcpy(&r[13], &pr.rlink, 4);
-            r[14] = r[15] = 0.f;
+// runs as packed fp32, see inner_step.  (The 4-wide layout is k_refit_emit's.)
+int upload_pairs(const rt_scene *sc, const std::vector<rtbvh::Pair> &pairs) {
+    std::vector<float> inter(16 * pairs.size());
+    for (size_t k = 0; k < pairs.size(); k++) {
+        const rtbvh::Pair &pr = pairs[k];
+        float *r = &inter[16 * k];
+        for (int a = 0; a < 6; a++) {
+            r[2 * a] = pr.lbox[a];
+            r[2 * a + 1] = pr.rbox[a];
         }
-    } else {
-        // 4-wide node j = builder records 2j (children 0, 1) and 2j + 1 (children 2, 3) -> 128 bytes BY PLANE:
-        //   word 2a: the four children's lower bounds of axis a, word 2a + 1: their upper bounds (a = x, y, z), word 6: the
-        //   four links, word 7: spare
-        for (size_t j = 0; 2 * j + 1 < recs->size(); j++) {
-            const rtbvh::Pair &p0 = (*recs)[2 * j], &p1 = (*recs)[2 * j + 1];
-            const float *box[4] = {p0.lbox, p0.rbox, p1.lbox, p1.rbox};
-            const int32_t link[4] = {p0.llink, p0.rlink, p1.llink, p1.rlink};
-            float *r = &inter[32 * j];
-            for (int a = 0; a < 3; a++)
-                for (int c = 0; c < 4; c++) {
-                    r[8 * a + c] = box[c][a];
-                    r[8 * a + 4 + c] = box[c][3 + a];
-                }
-            memcpy(&r[24], link, 16);
-            r[28] = r[29] = r[30] = r[31] = 0.f;
-        }
+        memcpy(&r[12], &pr.llink, 4);
+        memcpy(&r[13], &pr.rlink, 4);
+        r[14] = r[15] = 0.f;
     }
-    HIP_TRY(hipMemcpy(sc->d_nodes, inter.data(), 64 * (size_t)sc->n_nodes, hipMemcpyHostToDevice));
-    for (int a = 0; a < 3; a++) sc->origin_radius[a] = radius[a];
+    HIP_TRY(hipMemcpy(sc->d_nodes, inter.data(), 64 * pairs.size(), hipMemcpyHostToDevice));
     return 0;
 }
-// Before rays are traced whose origins may lie outside the radius the 4-wide records are padded for (a camera outside the
-// scene's bounds; the rays of the test hooks): re-pad, generously, and upload.  Renders of the same scene that are in flight
-// on other streams read a mix of the old and the new bounds meanwhile -- both are conservative for THEIR rays.
-int ensure_origin_radius(const rt_scene *sc, const float need[3]) {
-    if (!sc->wide) return 0;
-    std::lock_guard<std::mutex> lock(sc->pad_mutex);
-    bool grow = false;
-    float radius[3];
-    for (int a = 0; a < 3; a++) {
-        const float want = std::isfinite(need[a]) ? std::fabs(need[a]) * 1.001f : 0.f;  // (a non-finite origin hits nothing anyway)
-        grow = grow || want > sc->origin_radius[a];
-        radius[a] = want > sc->origin_radius[a] ? 2.f * want : sc->origin_radius[a];
-    }
-    if (!grow) return 0;
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    if (dev != sc->device) HIP_TRY(hipSetDevice(sc->device));
-    const int rc = upload_node_records(sc, sc->h_quads, radius);
-    if (dev != sc->device) HIP_TRY(hipSetDevice(dev));
-    return rc;
-}
 
+// Structural check of 4-wide records before they are uploaded (a malformed tree would hang the GPU): every node reachable
+// from the root exactly once (two consecutive records per node; inner links are even record indices), every triangle
+// position in exactly one leaf, plus the invariant the kernels' box test rests on: a child is absent (link kNoChild) if and
+// only if its box is all +inf -- the one-comparison slab test of inner_step<true> never looks at links.
 bool validate_quads(const std::vector<rtbvh::Pair> &quads, int n_tris) {
     const int nr = (int)quads.size();
     if (nr < 2 || (nr & 1)) return false;
@@ -3303,57 +3126,118 @@ struct DevScope {
         return 0;
     }
 };
-// Device LBVH build: returns the pair records and the leaf order on the host (the caller uploads them
-// like the host builder's output).  n >= 2.
-int build_lbvh_device(const float *verts_host, int n, std::vector<rtbvh::Pair> &pairs, std::vector<int32_t> &order,
-                      int &depth, double &seconds) {
-    float lo[3] = {kFltMax, kFltMax, kFltMax}, hi[3] = {-kFltMax, -kFltMax, -kFltMax};
-    for (size_t i = 0; i < (size_t)n * 3; i++)
-        for (int a = 0; a < 3; a++) {
-            lo[a] = std::min(lo[a], verts_host[3 * i + a]);
-            hi[a] = std::max(hi[a], verts_host[3 * i + a]);
-        }
-    float sc3[3];
-    for (int a = 0; a < 3; a++) sc3[a] = hi[a] > lo[a] ? 1024.f / (hi[a] - lo[a]) : 0.f;
-    int n_pad = 1;
-    while (n_pad < n) n_pad <<= 1;
-    float *d_verts = nullptr, *d_boxes = nullptr, *d_pairs = nullptr;
-    unsigned long long *d_keys = nullptr;
-    int *d_left = nullptr, *d_right = nullptr, *d_pi = nullptr, *d_pl = nullptr, *d_depth = nullptr, *d_arr = nullptr, *d_order = nullptr;
-    DevScope tmp;  // the eleven temporaries and both events go away on every return path
-    if (tmp.alloc(d_verts, 9 * (size_t)n) || tmp.alloc(d_keys, (size_t)n_pad) || tmp.alloc(d_left, (size_t)n) ||
-        tmp.alloc(d_right, (size_t)n) || tmp.alloc(d_pi, (size_t)n) || tmp.alloc(d_pl, (size_t)n) || tmp.alloc(d_depth, (size_t)n) ||
-        tmp.alloc(d_arr, (size_t)n) || tmp.alloc(d_order, (size_t)n) || tmp.alloc(d_boxes, 6 * (size_t)n) || tmp.alloc(d_pairs, 16 * (size_t)n))
-        return 1;
-    HIP_TRY(hipMemcpy(d_verts, verts_host, sizeof(float) * 9 * (size_t)n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(d_arr, 0, sizeof(int) * (size_t)n));
-    HIP_TRY(hipMemset(d_depth, 0, sizeof(int) * (size_t)n));
-    HIP_TRY(hipEventCreate(&tmp.e0));
-    HIP_TRY(hipEventCreate(&tmp.e1));
-    const hipEvent_t e0 = tmp.e0, e1 = tmp.e1;
-    HIP_TRY(hipEventRecord(e0, nullptr));
-    const dim3 blk(256);
-    hipLaunchKernelGGL(k_lbvh_keys, dim3((n_pad + 255) / 256), blk, 0, nullptr, d_verts, n, n_pad, lo[0], lo[1], lo[2], sc3[0],
-                       sc3[1], sc3[2], d_keys);
-    for (int k2 = 2; k2 <= n_pad; k2 <<= 1)
-        for (int j = k2 >> 1; j > 0; j >>= 1)
-            hipLaunchKernelGGL(k_bitonic_step, dim3((n_pad + 255) / 256), blk, 0, nullptr, d_keys, n_pad, j, k2);
-    hipLaunchKernelGGL(k_lbvh_hierarchy, dim3((n + 255) / 256), blk, 0, nullptr, d_keys, n, d_left, d_right, d_pi, d_pl);
-    hipLaunchKernelGGL(k_lbvh_fit, dim3((n + 255) / 256), blk, 0, nullptr, d_verts, d_keys, n, d_left, d_right, d_pi, d_pl,
-                       d_boxes, d_depth, d_arr);
-    hipLaunchKernelGGL(k_lbvh_emit, dim3((n + 255) / 256), blk, 0, nullptr, d_verts, d_keys, n, d_left, d_right, d_boxes,
-                       d_pairs, d_order);
+// The scene's device made current for the rest of a host call; the caller's is restored on every return path
+struct DeviceGuard {
+    int saved = 0, current = 0;
+    int enter(int device) {
+        HIP_TRY(hipGetDevice(&saved));
+        current = saved;
+        if (device != saved) HIP_TRY(hipSetDevice(device));
+        current = device;
+        return 0;
+    }
+    ~DeviceGuard() {
+        if (current != saved) (void)hipSetDevice(saved);
+    }
+};
+
+// The 4-wide nodes the kernels walk, from the builder's unpadded records: padded for ray origins within `radius`, grown to
+// the records' bounds (k_refit_emit, which leaves the radius it used in sc->d_radius).  Ordered on `st`; the caller holds
+// pad_mutex and has made the scene's device current.
+void emit_nodes(const rt_scene *sc, const rtbvh::Pair *d_recs, int n_records, float4 *d_nodes, const float radius[3], hipStream_t st) {
+    const int n = n_records / 2;
+    hipLaunchKernelGGL(k_refit_emit, dim3((n + 255) / 256), dim3(256), 0, st, d_recs, n, radius[0], radius[1], radius[2],
+                       (float *)d_nodes, sc->d_radius);
+}
+
+// Before rays are traced whose origins may lie outside the radius the 4-wide records are padded for (a camera outside the
+// scene's bounds; the rays of the test hooks): re-pad, generously, on the null stream, and wait for it.  Renders of the same
+// scene that are in flight on other streams read a mix of the old and the new bounds meanwhile -- both are conservative for
+// THEIR rays.
+int ensure_origin_radius(const rt_scene *sc, const float need[3]) {
+    if (!sc->wide) return 0;
+    std::lock_guard<std::mutex> lock(sc->pad_mutex);
+    bool grow = false;
+    float radius[3];
+    for (int a = 0; a < 3; a++) {
+        const float want = std::isfinite(need[a]) ? std::fabs(need[a]) * 1.001f : 0.f;  // (a non-finite origin hits nothing anyway)
+        grow = grow || want > sc->origin_radius[a];
+        radius[a] = want > sc->origin_radius[a] ? 2.f * want : sc->origin_radius[a];
+    }
+    if (!grow) return 0;
+    DeviceGuard dev;
+    if (dev.enter(sc->device)) return 1;
+    emit_nodes(sc, sc->d_recs, sc->n_nodes, sc->d_nodes, radius, nullptr);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(e1, nullptr));
-    HIP_TRY(hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-    seconds = ms * 1e-3;
-    pairs.resize((size_t)n - 1);
-    order.resize((size_t)n);
-    HIP_TRY(hipMemcpy(pairs.data(), d_pairs, sizeof(rtbvh::Pair) * (size_t)(n - 1), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(order.data(), d_order, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(&depth, d_depth, sizeof(int), hipMemcpyDeviceToHost));  // depth of the root
+    HIP_TRY(hipMemcpy(sc->origin_radius, sc->d_radius, sizeof(float) * 3, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// The one writer of the scene's leaf-order arrays, ordered on `st`, from the caller's vertices on the device (d_verts) and
+// the leaf order out.order: the triangle records (k_leaf_tris), the shading records and tables, and -- 4-wide -- the nodes
+// from out.recs, padded for the scene's origin radius (emit_nodes).  For a new leaf order `d_inverse` (n ints of scratch)
+// receives its inverse, and the triangles' (material, light) and the lights, their triangles renumbered, are written too, from
+// the scene's host copies.  Null for a refit: the leaf order is the scene's, and so are tri_info and the lights; the boxes of
+// the scene's records are refit to the vertices before they are padded (k_refit_level, one launch per level, deepest first;
+// launched after k_leaf_tris, which reads the same vertices: 5 us less per refit of the bunny than before it).  Temporaries go
+// to `tmp`.
+int emit_scene(const rt_scene *sc, const float *d_verts, const SceneArrays &out, int *d_inverse, hipStream_t st, DevScope &tmp) {
+    const int n = sc->n_tris, n_lights = sc->n_lights;
+    const dim3 blk(256), grid((n + 255) / 256);
+    if (d_inverse && n > 0) {
+        std::vector<int2> caller_info((size_t)n);
+        for (int i = 0; i < n; i++)
+            caller_info[(size_t)i] = make_int2(sc->h_tri_material[(size_t)i], sc->h_tri_light.empty() ? -1 : sc->h_tri_light[(size_t)i]);
+        int2 *d_caller_info = nullptr;
+        if (tmp.alloc(d_caller_info, (size_t)n)) return 1;
+        HIP_TRY(hipMemcpyAsync(d_caller_info, caller_info.data(), sizeof(int2) * (size_t)n, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));  // (caller_info goes out of scope)
+        hipLaunchKernelGGL(k_leaf_inverse, grid, blk, 0, st, out.order, n, d_inverse);
+        hipLaunchKernelGGL(k_leaf_tri_info, grid, blk, 0, st, d_caller_info, out.order, n, out.info);
+    }
+    if (d_inverse && n_lights > 0) {
+        HIP_TRY(hipMemcpyAsync(out.lights, sc->h_lights.data(), sizeof(Light) * (size_t)n_lights, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_leaf_lights, dim3((n_lights + 255) / 256), blk, 0, st, out.lights, n_lights, d_inverse);
+    }
+    if (n > 0) {
+        hipLaunchKernelGGL(k_leaf_tris, grid, blk, 0, st, d_verts, out.order, n, out.tris);
+        hipLaunchKernelGGL(k_build_tri_shade, grid, blk, 0, st, out.tris, out.info, n, out.shade);
+    }
+    const int nt = std::max(std::max(sc->n_mats, n_lights), 1);
+    hipLaunchKernelGGL(k_build_tables, dim3((nt + 63) / 64), dim3(64), 0, st, sc->d_mats, sc->n_mats, out.lights, n_lights, out.tris,
+                       out.tables);
+    if (!d_inverse)
+        for (size_t l = 0; l < sc->refit_level_end.size(); l++) {
+            const int begin = l ? sc->refit_level_end[l - 1] : 0, count = sc->refit_level_end[l] - begin;
+            hipLaunchKernelGGL(k_refit_level, dim3((count + 255) / 256), blk, 0, st, d_verts, sc->d_order, sc->d_refit_nodes + begin,
+                               count, sc->d_recs, sc->d_refit_exact);
+        }
+    if (sc->wide) emit_nodes(sc, out.recs, out.n_records, out.nodes, sc->origin_radius, st);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// The start of rt_scene_update and rt_scene_rebuild: a device buffer of the caller's checked (on the scene's device), the
+// scene's device made current (until `dev` goes), and the vertices on it in d_verts -- the caller's buffer, or the host
+// array (null: the scene's own copy) staged on `st` into `tmp`.
+int stage_vertices(const rt_scene *sc, const float *verts, bool device_ptr, hipStream_t st, const std::string &w, DeviceGuard &dev,
+                   DevScope &tmp, const float *&d_verts) {
+    if (device_ptr && verts) {
+        hipPointerAttribute_t attr;
+        if (hipPointerGetAttributes(&attr, verts) != hipSuccess || (attr.type != hipMemoryTypeDevice && !attr.isManaged) ||
+            attr.device != sc->device) {
+            (void)hipGetLastError();  // (the failed query leaves its error behind)
+            return fail(w + ": d_tri_p0p1p2 is not device memory on the scene's device " + std::to_string(sc->device));
+        }
+    }
+    if (dev.enter(sc->device)) return 1;
+    d_verts = verts;
+    if (sc->n_tris > 0 && (!verts || !device_ptr)) {
+        float *d_v = nullptr;
+        if (tmp.alloc(d_v, 9 * (size_t)sc->n_tris)) return 1;
+        HIP_TRY(hipMemcpyAsync(d_v, verts ? verts : sc->h_tri9.data(), sizeof(float) * 9 * (size_t)sc->n_tris, hipMemcpyHostToDevice, st));
+        d_verts = d_v;
+    }
     return 0;
 }
 
@@ -3381,32 +3265,21 @@ double quads_sah(const std::vector<rtbvh::Pair> &quads) {
     return quads.size() < 2 || !(e0 >= 0.0) ? 0.0 : cost / std::max((e0 + e1) * e2 + e0 * e1, 1e-30);
 }
 
-// rt_scene_update / rt_scene_update_device: refit the 4-wide tree on the scene's device (k_refit_*), then bring the host
-// state along -- the builder records ensure_origin_radius re-pads from, the radius they are padded for, the triangle copy the
-// reference's tree and the replicas are made from.  `verts` is a host array or (device_ptr) a buffer on the scene's device.
+// rt_scene_update / rt_scene_update_device: refit the 4-wide tree on the scene's device (emit_scene), then
+// bring the host state along -- the builder records, the radius they are padded for, the triangle copy the reference's tree
+// and the replicas are made from.  `verts` is a host array or (device_ptr) a buffer on the scene's device.
 int scene_update_impl(rt_scene *sc, const float *verts, int n_tris, bool device_ptr, hipStream_t st, const char *what) {
     const std::string w(what);
     if (!sc || !verts) return fail(w + ": null argument");
     if (n_tris != sc->n_tris) return fail(w + ": " + std::to_string(n_tris) + " triangles, the scene was created with " + std::to_string(sc->n_tris));
     if (!sc->wide) return fail(w + ": the scene uses the 2-wide experiment format (RT_BVH_WIDE=0), which cannot be refit");
-    int saved = 0;
-    HIP_TRY(hipGetDevice(&saved));
-    if (device_ptr) {
-        hipPointerAttribute_t attr;
-        if (hipPointerGetAttributes(&attr, verts) != hipSuccess || (attr.type != hipMemoryTypeDevice && !attr.isManaged) ||
-            attr.device != sc->device) {
-            (void)hipGetLastError();  // (the failed query leaves its error behind)
-            return fail(w + ": d_tri_p0p1p2 is not device memory on the scene's device " + std::to_string(sc->device));
-        }
-    }
-    if (saved != sc->device) HIP_TRY(hipSetDevice(sc->device));
-    struct Restore {
-        int dev, was;
-        ~Restore() { if (dev != was) (void)hipSetDevice(was); }
-    } restore{sc->device, saved};
+    std::lock_guard<std::mutex> pad_lock(sc->pad_mutex);  // (the records, h_quads and origin_radius change)
+    DeviceGuard dev;
+    DevScope tmp;
+    const float *d_verts = nullptr;
+    if (stage_vertices(sc, verts, device_ptr, st, w, dev, tmp, d_verts)) return 1;
     const int n = n_tris;
-    std::lock_guard<std::mutex> pad_lock(sc->pad_mutex);  // (h_quads and origin_radius change)
-    const int n_nodes = sc->n_nodes / 2;                  // 4-wide nodes: two records each
+    const int n_nodes = sc->n_nodes / 2;  // 4-wide nodes: two records each
     if (n > 0 && !sc->d_refit_nodes) {
         // the levels of the tree, fixed at creation: breadth-first from the root, then deepest level first
         std::vector<int> depth((size_t)n_nodes, -1), queue{0};
@@ -3431,89 +3304,42 @@ int scene_update_impl(rt_scene *sc, const float *verts, int n_tris, bool device_
             level_end.push_back((int)nodes.size());
         }
         int *dn = nullptr;
-        rtbvh::Pair *dr = nullptr;
-        float *de = nullptr, *drad = nullptr;
+        float *de = nullptr;
         if (hipMalloc((void **)&dn, sizeof(int) * nodes.size()) != hipSuccess ||
-            hipMalloc((void **)&dr, sizeof(rtbvh::Pair) * sc->h_quads.size()) != hipSuccess ||
             hipMalloc((void **)&de, sizeof(float) * 6 * (size_t)n_nodes) != hipSuccess ||
-            hipMalloc((void **)&drad, sizeof(float) * 3) != hipSuccess ||
-            hipMemcpy(dn, nodes.data(), sizeof(int) * nodes.size(), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(dr, sc->h_quads.data(), sizeof(rtbvh::Pair) * sc->h_quads.size(), hipMemcpyHostToDevice) != hipSuccess) {
+            hipMemcpy(dn, nodes.data(), sizeof(int) * nodes.size(), hipMemcpyHostToDevice) != hipSuccess) {
             (void)hipFree(dn);
-            (void)hipFree(dr);
             (void)hipFree(de);
-            (void)hipFree(drad);
             return fail(w + ": device allocation or upload failed");
         }
         sc->d_refit_nodes = dn;
-        sc->d_refit_recs = dr;
         sc->d_refit_exact = de;
-        sc->d_refit_radius = drad;
         sc->refit_level_end = level_end;
         sc->sah_build = sc->sah_now = quads_sah(sc->h_quads);
     }
-    DevScope tmp;
-    std::vector<float> h_new;
-    const float *d_verts = verts;
-    if (n > 0 && !device_ptr) {
-        float *d_v = nullptr;
-        if (tmp.alloc(d_v, 9 * (size_t)n)) return 1;
-        HIP_TRY(hipMemcpyAsync(d_v, verts, sizeof(float) * 9 * (size_t)n, hipMemcpyHostToDevice, st));
-        d_verts = d_v;
-    }
-    float radius[3] = {sc->origin_radius[0], sc->origin_radius[1], sc->origin_radius[2]};
     double seconds = 0.0;
     if (n > 0) {
         HIP_TRY(hipEventCreate(&tmp.e0));
         HIP_TRY(hipEventCreate(&tmp.e1));
         HIP_TRY(hipEventRecord(tmp.e0, st));
-        const dim3 blk(256);
-        hipLaunchKernelGGL(k_refit_tris, dim3((n + 255) / 256), blk, 0, st, d_verts, sc->d_order, n, sc->d_tris);
-        hipLaunchKernelGGL(k_build_tri_shade, dim3((n + 255) / 256), blk, 0, st, sc->d_tris, sc->d_tri_info, n, sc->d_tri_shade);
-        const int nt = std::max(std::max(sc->n_mats, sc->n_lights), 1);
-        hipLaunchKernelGGL(k_build_tables, dim3((nt + 63) / 64), dim3(64), 0, st, sc->d_mats, sc->n_mats, sc->d_lights, sc->n_lights,
-                           sc->d_tris, sc->d_tables);
-        for (size_t l = 0; l < sc->refit_level_end.size(); l++) {
-            const int begin = l ? sc->refit_level_end[l - 1] : 0, count = sc->refit_level_end[l] - begin;
-            hipLaunchKernelGGL(k_refit_level, dim3((count + 255) / 256), blk, 0, st, d_verts, sc->d_order, sc->d_refit_nodes + begin,
-                               count, sc->d_refit_recs, sc->d_refit_exact);
-        }
-        hipLaunchKernelGGL(k_refit_emit, dim3((n_nodes + 255) / 256), blk, 0, st, sc->d_refit_recs, n_nodes, radius[0], radius[1],
-                           radius[2], (float *)sc->d_nodes, sc->d_refit_radius);
-        HIP_TRY(hipGetLastError());
+        if (emit_scene(sc, d_verts, sc->arrays(), nullptr, st, tmp)) return 1;
         HIP_TRY(hipEventRecord(tmp.e1, st));
         HIP_TRY(hipEventSynchronize(tmp.e1));
         float ms = 0.f;
         HIP_TRY(hipEventElapsedTime(&ms, tmp.e0, tmp.e1));
         seconds = ms * 1e-3;
-        // the host's view of the new geometry: the unpadded records (ensure_origin_radius re-pads from them), the radius the
-        // device copy is padded for, the caller's triangles (the reference's tree and the replicas are made from them)
-        HIP_TRY(hipMemcpy(sc->h_quads.data(), sc->d_refit_recs, sizeof(rtbvh::Pair) * sc->h_quads.size(), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(radius, sc->d_refit_radius, sizeof(float) * 3, hipMemcpyDeviceToHost));
+        // the host's view of the new geometry: the unpadded records, the radius the device copy is padded for, the caller's
+        // triangles (the reference's tree and the replicas are made from them)
+        HIP_TRY(hipMemcpy(sc->h_quads.data(), sc->d_recs, sizeof(rtbvh::Pair) * sc->h_quads.size(), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(sc->origin_radius, sc->d_radius, sizeof(float) * 3, hipMemcpyDeviceToHost));
         if (device_ptr) HIP_TRY(hipMemcpy(sc->h_tri9.data(), verts, sizeof(float) * 9 * (size_t)n, hipMemcpyDeviceToHost));
         else memcpy(sc->h_tri9.data(), verts, sizeof(float) * 9 * (size_t)n);
-        for (int a = 0; a < 3; a++) sc->origin_radius[a] = radius[a];
         sc->sah_now = quads_sah(sc->h_quads);
     }
     sc->refit_seconds = seconds;
     sc->refits++;
-    {   // the reference's tree is a function of the triangles: the next render that needs it rebuilds it from h_tri9
-        std::lock_guard<std::mutex> lock(sc->ref_mutex);
-        (void)hipFree(sc->d_ref_nodes);
-        (void)hipFree(sc->d_ref_prims);
-        (void)hipFree(sc->d_ref_leaf_of);
-        (void)hipFree(sc->d_ref_parent);
-        sc->d_ref_nodes = nullptr;
-        sc->d_ref_prims = sc->d_ref_leaf_of = sc->d_ref_parent = nullptr;
-        sc->ref_nodes_count = sc->ref_depth = 0;
-        sc->ref_root_leaf = true;
-        sc->ref_ready = false;
-    }
-    {   // replicas on other devices (rt_render_multi) hold the old geometry: dropped, recreated from h_tri9 on next use
-        std::lock_guard<std::mutex> lock(sc->replica_mutex);
-        for (rt_scene *r : sc->replicas) delete r;
-        sc->replicas.clear();
-    }
+    sc->drop_ref_tree();
+    sc->drop_replicas();
     return 0;
 }
 
@@ -3653,41 +3479,37 @@ bool ploc_result_ok(const PlocBuild &b, int n) {
     return true;
 }
 
+// The scene takes a device build's tree: the records and the leaf order on the device (b frees the scene's old ones) and
+// their host copies
+void adopt_tree(rt_scene *sc, PlocBuild &b) {
+    std::swap(sc->d_recs, b.d_recs);
+    std::swap(sc->d_order, b.d_order);
+    sc->h_quads = std::move(b.quads);
+    sc->set_order(b.order);
+    sc->n_nodes = (int)sc->h_quads.size();
+    sc->max_depth = b.max_depth;
+    sc->stack_bound = b.stack_bound;
+    sc->n_leaves = b.leaves;
+    sc->builder = 2;
+    sc->build_seconds = b.seconds;
+}
+
 // rt_scene_rebuild / rt_scene_rebuild_device: a new tree for the scene's current or new vertices (build_ploc_device), and
-// everything the kernels index in leaf order re-emitted on the device from the new order, into new buffers that replace the
-// scene's only once the tree has passed its checks.  `verts`: null (the scene's own vertices), a host array or (device_ptr)
-// a buffer on the scene's device.
+// everything the kernels index in leaf order re-emitted on the device from the new order (emit_scene), into new buffers that
+// replace the scene's only once the tree has passed its checks.  `verts`: null (the scene's own vertices), a host array or
+// (device_ptr) a buffer on the scene's device.
 int scene_rebuild_impl(rt_scene *sc, const float *verts, int n_tris, bool device_ptr, hipStream_t st, const char *what) {
     const std::string w(what);
     if (!sc) return fail(w + ": null scene");
     if (n_tris != sc->n_tris) return fail(w + ": " + std::to_string(n_tris) + " triangles, the scene was created with " + std::to_string(sc->n_tris));
     if (!sc->wide) return fail(w + ": the scene uses the 2-wide experiment format (RT_BVH_WIDE=0), which the device builder does not write");
     if (n_tris < 1) return fail(w + ": the scene has no triangles");
-    int saved = 0;
-    HIP_TRY(hipGetDevice(&saved));
-    if (device_ptr && verts) {
-        hipPointerAttribute_t attr;
-        if (hipPointerGetAttributes(&attr, verts) != hipSuccess || (attr.type != hipMemoryTypeDevice && !attr.isManaged) ||
-            attr.device != sc->device) {
-            (void)hipGetLastError();  // (the failed query leaves its error behind)
-            return fail(w + ": d_tri_p0p1p2 is not device memory on the scene's device " + std::to_string(sc->device));
-        }
-    }
-    if (saved != sc->device) HIP_TRY(hipSetDevice(sc->device));
-    struct Restore {
-        int dev, was;
-        ~Restore() { if (dev != was) (void)hipSetDevice(was); }
-    } restore{sc->device, saved};
-    const int n = n_tris;
-    std::lock_guard<std::mutex> pad_lock(sc->pad_mutex);  // (h_quads and origin_radius change)
+    std::lock_guard<std::mutex> pad_lock(sc->pad_mutex);  // (the records, h_quads and origin_radius change)
+    DeviceGuard dev;
     DevScope tmp;
-    const float *d_verts = verts;
-    if (!verts || !device_ptr) {
-        float *d_v = nullptr;
-        if (tmp.alloc(d_v, 9 * (size_t)n)) return 1;
-        HIP_TRY(hipMemcpyAsync(d_v, verts ? verts : sc->h_tri9.data(), sizeof(float) * 9 * (size_t)n, hipMemcpyHostToDevice, st));
-        d_verts = d_v;
-    }
+    const float *d_verts = nullptr;
+    if (stage_vertices(sc, verts, device_ptr, st, w, dev, tmp, d_verts)) return 1;
+    const int n = n_tris;
     std::vector<float> h_new;
     if (verts) {
         h_new.resize(9 * (size_t)n);
@@ -3702,99 +3524,49 @@ int scene_rebuild_impl(rt_scene *sc, const float *verts, int n_tris, bool device
     PlocBuild b;
     if (build_ploc_device(d_verts, n, st, b, w)) return 1;
     if (!ploc_result_ok(b, n)) return fail(w + ": the device-built tree is malformed; the scene is unchanged");
-    // the scene's leaf-order arrays for the new order, into new buffers
-    const int n_nodes = (int)b.quads.size(), n_lights = sc->n_lights;
-    float4 *d_nodes = nullptr, *d_tris = nullptr, *d_shade = nullptr;
-    int2 *d_info = nullptr, *d_caller_info = nullptr;
-    Light *d_lights = nullptr;
-    float *d_tables = nullptr, *d_radius = nullptr;
+    // the scene's leaf-order arrays for the new tree, into new buffers
+    SceneArrays a{b.d_order, b.d_recs, (int)b.quads.size()};
     int *d_inverse = nullptr, *d_ref_prims = nullptr, *d_ref_leaf_of = nullptr;
     DevScope fresh;  // (released unless adopted below)
     const bool keep_ref = sc->ref_ready && !moved;
-    if (fresh.alloc(d_nodes, 4 * (size_t)n_nodes) || fresh.alloc(d_tris, 3 * (size_t)n) || fresh.alloc(d_shade, (size_t)n) ||
-        fresh.alloc(d_info, (size_t)n) || fresh.alloc(d_lights, (size_t)std::max(n_lights, 1)) ||
-        fresh.alloc(d_tables, (size_t)std::max(sc->tab_dwords, 1)) || tmp.alloc(d_caller_info, (size_t)n) ||
-        tmp.alloc(d_inverse, (size_t)n) || tmp.alloc(d_radius, 3) ||
+    if (fresh.alloc(a.nodes, 4 * (size_t)a.n_records) || fresh.alloc(a.tris, 3 * (size_t)n) || fresh.alloc(a.shade, (size_t)n) ||
+        fresh.alloc(a.info, (size_t)n) || fresh.alloc(a.lights, (size_t)std::max(sc->n_lights, 1)) ||
+        fresh.alloc(a.tables, (size_t)std::max(sc->tab_dwords, 1)) || tmp.alloc(d_inverse, (size_t)n) ||
         (keep_ref && (fresh.alloc(d_ref_prims, (size_t)n) || fresh.alloc(d_ref_leaf_of, (size_t)n))))
         return 1;
-    std::vector<int2> caller_info((size_t)n);
-    for (int i = 0; i < n; i++)
-        caller_info[(size_t)i] = make_int2(sc->h_tri_material[(size_t)i], sc->h_tri_light.empty() ? -1 : sc->h_tri_light[(size_t)i]);
-    HIP_TRY(hipMemcpyAsync(d_caller_info, caller_info.data(), sizeof(int2) * (size_t)n, hipMemcpyHostToDevice, st));
-    if (n_lights > 0) HIP_TRY(hipMemcpyAsync(d_lights, sc->h_lights.data(), sizeof(Light) * (size_t)n_lights, hipMemcpyHostToDevice, st));
-    float radius[3] = {sc->origin_radius[0], sc->origin_radius[1], sc->origin_radius[2]};
-    const dim3 blk(256), grid((n + 255) / 256);
-    hipLaunchKernelGGL(k_ploc_inverse, grid, blk, 0, st, b.d_order, n, d_inverse);
-    hipLaunchKernelGGL(k_refit_tris, grid, blk, 0, st, d_verts, b.d_order, n, d_tris);
-    hipLaunchKernelGGL(k_ploc_tri_info, grid, blk, 0, st, d_caller_info, b.d_order, n, d_info);
-    if (n_lights > 0) hipLaunchKernelGGL(k_ploc_lights, dim3((n_lights + 255) / 256), blk, 0, st, d_lights, n_lights, d_inverse);
-    hipLaunchKernelGGL(k_build_tri_shade, grid, blk, 0, st, d_tris, d_info, n, d_shade);
-    const int nt = std::max(std::max(sc->n_mats, n_lights), 1);
-    hipLaunchKernelGGL(k_build_tables, dim3((nt + 63) / 64), dim3(64), 0, st, sc->d_mats, sc->n_mats, d_lights, n_lights, d_tris, d_tables);
-    hipLaunchKernelGGL(k_refit_emit, dim3((n_nodes / 2 + 255) / 256), blk, 0, st, b.d_recs, n_nodes / 2, radius[0], radius[1],
-                       radius[2], (float *)d_nodes, d_radius);
+    if (emit_scene(sc, d_verts, a, d_inverse, st, tmp)) return 1;
     if (keep_ref)
-        hipLaunchKernelGGL(k_ploc_remap_ref, grid, blk, 0, st, sc->d_ref_prims, sc->d_ref_leaf_of, sc->d_order, d_inverse, n,
-                           d_ref_prims, d_ref_leaf_of);
+        hipLaunchKernelGGL(k_ploc_remap_ref, dim3((n + 255) / 256), dim3(256), 0, st, sc->d_ref_prims, sc->d_ref_leaf_of, sc->d_order,
+                           d_inverse, n, d_ref_prims, d_ref_leaf_of);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(radius, d_radius, sizeof(radius), hipMemcpyDeviceToHost, st));
+    float radius[3];
+    HIP_TRY(hipMemcpyAsync(radius, sc->d_radius, sizeof(radius), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     // adopt: the new buffers replace the old ones, the host state follows
     fresh.ptrs.clear();
-    std::swap(sc->d_nodes, d_nodes);
-    std::swap(sc->d_tris, d_tris);
-    std::swap(sc->d_tri_shade, d_shade);
-    std::swap(sc->d_tri_info, d_info);
-    std::swap(sc->d_lights, d_lights);
-    std::swap(sc->d_tables, d_tables);
-    std::swap(sc->d_order, b.d_order);
-    for (void *q : {(void *)d_nodes, (void *)d_tris, (void *)d_shade, (void *)d_info, (void *)d_lights, (void *)d_tables}) (void)hipFree(q);
-    sc->h_quads = b.quads;
-    sc->h_order.assign(b.order.begin(), b.order.end());
-    for (int k = 0; k < n; k++) sc->h_inverse[(size_t)sc->h_order[(size_t)k]] = k;
-    for (int a = 0; a < 3; a++) sc->origin_radius[a] = radius[a];
-    sc->n_nodes = n_nodes;
-    sc->max_depth = b.max_depth;
-    sc->stack_bound = b.stack_bound;
-    sc->n_leaves = b.leaves;
-    sc->top_prefix = true;  // (breadth-first throughout: every prefix of the records is the top of the tree in level order)
-    sc->builder = 2;
-    sc->build_seconds = b.seconds;
-    // the refit's records and levels belong to the old tree: the next rt_scene_update sets them up for this one
-    (void)hipFree(sc->d_refit_nodes);
-    (void)hipFree(sc->d_refit_recs);
-    (void)hipFree(sc->d_refit_exact);
-    (void)hipFree(sc->d_refit_radius);
-    sc->d_refit_nodes = nullptr;
-    sc->d_refit_recs = nullptr;
-    sc->d_refit_exact = sc->d_refit_radius = nullptr;
-    sc->refit_level_end.clear();
+    std::swap(sc->d_nodes, a.nodes);
+    std::swap(sc->d_tris, a.tris);
+    std::swap(sc->d_tri_shade, a.shade);
+    std::swap(sc->d_tri_info, a.info);
+    std::swap(sc->d_lights, a.lights);
+    std::swap(sc->d_tables, a.tables);
+    for (void *q : {(void *)a.nodes, (void *)a.tris, (void *)a.shade, (void *)a.info, (void *)a.lights, (void *)a.tables}) (void)hipFree(q);
+    adopt_tree(sc, b);
+    for (int k = 0; k < 3; k++) sc->origin_radius[k] = radius[k];
+    sc->drop_refit();
     sc->sah_build = sc->sah_now = quads_sah(sc->h_quads);
-    {   // the reference's tree is a function of the triangles: kept (renumbered for the new leaf order) unless they moved
+    // the reference's tree is a function of the triangles: kept (renumbered for the new leaf order) unless they moved
+    if (keep_ref) {
         std::lock_guard<std::mutex> lock(sc->ref_mutex);
-        if (keep_ref) {
-            std::swap(sc->d_ref_prims, d_ref_prims);
-            std::swap(sc->d_ref_leaf_of, d_ref_leaf_of);
-            (void)hipFree(d_ref_prims);
-            (void)hipFree(d_ref_leaf_of);
-        } else if (moved) {
-            (void)hipFree(sc->d_ref_nodes);
-            (void)hipFree(sc->d_ref_prims);
-            (void)hipFree(sc->d_ref_leaf_of);
-            (void)hipFree(sc->d_ref_parent);
-            sc->d_ref_nodes = nullptr;
-            sc->d_ref_prims = sc->d_ref_leaf_of = sc->d_ref_parent = nullptr;
-            sc->ref_nodes_count = sc->ref_depth = 0;
-            sc->ref_root_leaf = true;
-            sc->ref_ready = false;
-        }
+        std::swap(sc->d_ref_prims, d_ref_prims);
+        std::swap(sc->d_ref_leaf_of, d_ref_leaf_of);
+        (void)hipFree(d_ref_prims);
+        (void)hipFree(d_ref_leaf_of);
+    } else if (moved) {
+        sc->drop_ref_tree();
     }
     if (moved) sc->h_tri9 = h_new;
-    {   // replicas on other devices (rt_render_multi) hold the old tree: dropped, recreated on next use
-        std::lock_guard<std::mutex> lock(sc->replica_mutex);
-        for (rt_scene *r : sc->replicas) delete r;
-        sc->replicas.clear();
-    }
+    sc->drop_replicas();
     return 0;
 }
 
@@ -4206,8 +3978,8 @@ int render_shard_impl(const rt_scene *scene, const rt_camera *camera, int width,
             // (1/8 shard of C2: 2 013 / 2 017 / 2 016 / 2 015 Msamples/s with 0 / 64 / 128 / 224 nodes in LDS -- the
             // first levels are L2 hits the two waves' other work hides), so it is off unless RT_TOP_NODES asks for it
             const int prefix = std::min(scene->n_nodes, (int)rtbvh::kTopPrefix * (scene->wide ? 2 : 1));
-            top_n = scene->top_prefix ? std::min(scene->wide ? 0 : 384, prefix) : 0;
-            if (const char *e = knob("RT_TOP_NODES")) top_n = scene->top_prefix ? std::max(0, std::min(std::min(768, atoi(e)), prefix)) : 0;
+            top_n = std::min(scene->wide ? 0 : 384, prefix);
+            if (const char *e = knob("RT_TOP_NODES")) top_n = std::max(0, std::min(std::min(768, atoi(e)), prefix));
             if (scene->wide) top_n &= ~1;  // whole nodes
             // (never more than the 64 KB of dynamic LDS a launch gets without further ado: scenes with many materials / lights
             // have larger tables)
@@ -4601,137 +4373,80 @@ int rt_scene_create_flags(const float *tri_p0p1p2, int n_tris, const int32_t *tr
     }
     auto sc = std::make_unique<rt_scene>();
     HIP_TRY(hipGetDevice(&sc->device));
-    bool use_lbvh = false;
-    if (const char *e = knob("RT_BVH_BUILDER")) use_lbvh = std::string(e) == "lbvh";
-    rtbvh::Result bvh;
-    if (device_bvh) {
-        // the device PLOC builder on this device (the scene's); with no triangles there is nothing to build
-        if (n_tris > 0) {
-            float *d_v = nullptr;
-            DevScope tmp;
-            if (tmp.alloc(d_v, 9 * (size_t)n_tris)) return 1;
-            HIP_TRY(hipMemcpy(d_v, tri_p0p1p2, sizeof(float) * 9 * (size_t)n_tris, hipMemcpyHostToDevice));
-            PlocBuild b;
-            if (build_ploc_device(d_v, n_tris, nullptr, b, "rt_scene_create_flags")) return 1;
-            if (!ploc_result_ok(b, n_tris)) return fail("rt_scene_create_flags: the device-built tree is malformed");
-            bvh.quads = b.quads;
-            bvh.order = b.order;
-            bvh.max_depth = b.max_depth;
-            bvh.stack_bound = b.stack_bound;
-            bvh.num_leaves = b.leaves;
-            sc->build_seconds = b.seconds;
-        } else {
-            bvh = rtbvh::build(tri_p0p1p2, 0);
-        }
-        sc->builder = 2;
-        sc->top_prefix = true;
-    } else if (use_lbvh && n_tris >= 2) {
-        int depth = 0;
-        if (build_lbvh_device(tri_p0p1p2, n_tris, bvh.pairs, bvh.order, depth, sc->build_seconds)) return 1;
-        if (!validate_pairs(bvh.pairs, n_tris) || depth < 1) return fail("rt_scene_create: device BVH build produced a malformed tree");
-        std::vector<char> seen((size_t)n_tris, 0);
-        for (int k = 0; k < n_tris; k++) {
-            if (bvh.order[k] < 0 || bvh.order[k] >= n_tris || seen[bvh.order[k]]) return fail("rt_scene_create: device BVH build produced a bad triangle order");
-            seen[bvh.order[k]] = 1;
-        }
-        bvh.pair_depth = depth;
-        rtbvh::quads_from_pairs(bvh);  // (host, a few ms: the 4-wide format of the same tree)
-        bvh.num_leaves = n_tris;
-        sc->builder = 1;
-        sc->top_prefix = false;
-    } else {
-        auto t0 = std::chrono::steady_clock::now();
-        bvh = rtbvh::build(tri_p0p1p2, n_tris);
-        sc->build_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    }
-    if (!bvh.ok) return fail("rt_scene_create: BVH build produced an unreferenceable leaf");
-    if (n_tris > 0 && !bvh.quads.empty() && !validate_quads(bvh.quads, n_tris))
-        return fail("rt_scene_create: the 4-wide BVH is malformed (structure, or an absent child without its +inf box)");
+    sc->wide = true;  // 4-wide nodes (two pair-style records each): half the dependent fetches per ray; RT_BVH_WIDE=0: 2-wide
+    if (const char *e = knob("RT_BVH_WIDE")) sc->wide = atoi(e) != 0;
+    if (device_bvh && !sc->wide) return fail("rt_scene_create_flags: the device builder writes the 4-wide format only (RT_BVH_WIDE=0 is set)");
     sc->n_tris = n_tris;
+    sc->n_lights = n_lights;
+    sc->n_mats = n_materials;
     if (n_tris > 0) sc->h_tri9.assign(tri_p0p1p2, tri_p0p1p2 + 9 * (size_t)n_tris);  // (RT_FLAG_REFERENCE_WALK builds its tree from these)
     if (n_tris > 0) sc->h_tri_material.assign(tri_material, tri_material + n_tris);
     if (n_tris > 0 && tri_light) sc->h_tri_light.assign(tri_light, tri_light + n_tris);
     if (n_materials > 0) sc->h_materials.assign(materials, materials + n_materials);
     if (n_lights > 0) sc->h_lights.assign(lights, lights + n_lights);
-    sc->wide = true;  // 4-wide nodes (two pair-style records each): half the dependent fetches per ray; RT_BVH_WIDE=0: 2-wide
-    if (const char *e = knob("RT_BVH_WIDE")) sc->wide = atoi(e) != 0;
-    if (device_bvh && !sc->wide) return fail("rt_scene_create_flags: the device builder writes the 4-wide format only (RT_BVH_WIDE=0 is set)");
-    // a tree too deep for the 4-wide walk's stack (up to 3 entries per level) may still fit the 2-wide walk's (1 per level):
-    // a very deep LBVH, or a host tree the reinsertion pass deepened
-    if (sc->wide && bvh.stack_bound > kMaxStackBound) sc->wide = false;
-    if ((sc->wide ? bvh.stack_bound : bvh.pair_depth + 1) > kMaxStackBound)
-        return fail("rt_scene_create: BVH depth " + std::to_string(sc->wide ? bvh.max_depth : bvh.pair_depth) + " exceeds the traversal stack");
-    sc->n_nodes = sc->wide ? (int)bvh.quads.size() : (int)bvh.pairs.size();  // 64-byte records
-    sc->max_depth = sc->wide ? bvh.max_depth : bvh.pair_depth;
-    sc->stack_bound = sc->wide ? bvh.stack_bound : bvh.pair_depth + 1;
-    sc->n_leaves = bvh.num_leaves;
-    sc->n_lights = n_lights;
-    sc->n_mats = n_materials;
-    sc->h_order.assign(bvh.order.begin(), bvh.order.end());
-    sc->h_inverse.assign(n_tris, 0);
-    for (int k = 0; k < n_tris; k++) sc->h_inverse[sc->h_order[k]] = k;
-    // triangle records in leaf order: e1 = p0 - p1, e2 = p2 - p0, n = e1 x e2 (triangle.cuh:6-7),
-    // computed here in fp32 without contraction (this file is built with -ffp-contract=off)
-    std::vector<float> trec((size_t)12 * std::max(n_tris, 1));
-    std::vector<int2> info(std::max(n_tris, 1));
-    for (int k = 0; k < n_tris; k++) {
-        int i = sc->h_order[k];
-        const float *q = tri_p0p1p2 + 9 * (size_t)i;
-        float p0[3] = {q[0], q[1], q[2]};
-        float e1[3] = {q[0] - q[3], q[1] - q[4], q[2] - q[5]};
-        float e2[3] = {q[6] - q[0], q[7] - q[1], q[8] - q[2]};
-        float nn[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
-        float *r = trec.data() + 12 * (size_t)k;
-        r[0] = p0[0]; r[1] = p0[1]; r[2] = p0[2];
-        r[3] = e1[0]; r[4] = e1[1]; r[5] = e1[2];
-        r[6] = e2[0]; r[7] = e2[1]; r[8] = e2[2];
-        r[9] = nn[0]; r[10] = nn[1]; r[11] = nn[2];
-        info[k] = make_int2(tri_material[i], tri_light ? tri_light[i] : -1);
+    DevScope tmp;
+    float *d_verts = nullptr;
+    if (n_tris > 0) {
+        if (tmp.alloc(d_verts, 9 * (size_t)n_tris)) return 1;
+        HIP_TRY(hipMemcpy(d_verts, tri_p0p1p2, sizeof(float) * 9 * (size_t)n_tris, hipMemcpyHostToDevice));
     }
-    std::vector<Light> dl(std::max(n_lights, 1));
-    for (int i = 0; i < n_lights; i++) {
-        memcpy(&dl[i], &lights[i], sizeof(Light));
-        if (lights[i].type == RT_AREA_LIGHT) dl[i].tri = sc->h_inverse[lights[i].triangle];
+    std::vector<rtbvh::Pair> pairs;  // (2-wide)
+    if (device_bvh && n_tris > 0) {
+        // the device PLOC builder on this device (the scene's)
+        PlocBuild b;
+        if (build_ploc_device(d_verts, n_tris, nullptr, b, "rt_scene_create_flags")) return 1;
+        if (!ploc_result_ok(b, n_tris)) return fail("rt_scene_create_flags: the device-built tree is malformed");
+        adopt_tree(sc.get(), b);
+    } else {
+        // the host SAH builder (also for a device build of no triangles: there is nothing to build)
+        const auto t0 = std::chrono::steady_clock::now();
+        rtbvh::Result bvh = rtbvh::build(tri_p0p1p2, n_tris);
+        if (!device_bvh) sc->build_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        sc->builder = device_bvh ? 2 : 0;
+        if (!bvh.ok) return fail("rt_scene_create: BVH build produced an unreferenceable leaf");
+        if (n_tris > 0 && !bvh.quads.empty() && !validate_quads(bvh.quads, n_tris))
+            return fail("rt_scene_create: the 4-wide BVH is malformed (structure, or an absent child without its +inf box)");
+        // a tree too deep for the 4-wide walk's stack (up to 3 entries per level) may still fit the 2-wide walk's (1 per level):
+        // a host tree the reinsertion pass deepened
+        if (sc->wide && bvh.stack_bound > kMaxStackBound) sc->wide = false;
+        if ((sc->wide ? bvh.stack_bound : bvh.pair_depth + 1) > kMaxStackBound)
+            return fail("rt_scene_create: BVH depth " + std::to_string(sc->wide ? bvh.max_depth : bvh.pair_depth) + " exceeds the traversal stack");
+        sc->n_nodes = sc->wide ? (int)bvh.quads.size() : (int)bvh.pairs.size();  // 64-byte records
+        sc->max_depth = sc->wide ? bvh.max_depth : bvh.pair_depth;
+        sc->stack_bound = sc->wide ? bvh.stack_bound : bvh.pair_depth + 1;
+        sc->n_leaves = bvh.num_leaves;
+        sc->set_order(bvh.order);
+        HIP_TRY(hipMalloc((void **)&sc->d_order, sizeof(int) * std::max(n_tris, 1)));
+        if (n_tris) HIP_TRY(hipMemcpy(sc->d_order, sc->h_order.data(), sizeof(int) * n_tris, hipMemcpyHostToDevice));
+        if (sc->wide) {
+            sc->h_quads = std::move(bvh.quads);
+            HIP_TRY(hipMalloc((void **)&sc->d_recs, sizeof(rtbvh::Pair) * sc->h_quads.size()));
+            HIP_TRY(hipMemcpy(sc->d_recs, sc->h_quads.data(), sizeof(rtbvh::Pair) * sc->h_quads.size(), hipMemcpyHostToDevice));
+        } else {
+            pairs = std::move(bvh.pairs);
+        }
     }
     static_assert(sizeof(Light) == sizeof(rt_light), "light layout");
     static_assert(sizeof(Material) == sizeof(rt_material), "material layout");
     static_assert(sizeof(Camera) == sizeof(rt_camera), "camera layout");
-    HIP_TRY(hipMalloc((void **)&sc->d_nodes, 64 * (size_t)sc->n_nodes));
-    if (sc->wide) {
-        sc->h_quads = bvh.quads;
-        float radius[3];
-        rtbvh::quads_abs_bounds(sc->h_quads, radius);
-        if (int rc = upload_node_records(sc.get(), sc->h_quads, radius)) return rc;
-    } else {
-        const float none[3] = {0.f, 0.f, 0.f};
-        if (int rc = upload_node_records(sc.get(), bvh.pairs, none)) return rc;
-    }
-    HIP_TRY(hipMalloc((void **)&sc->d_tris, sizeof(float) * trec.size()));
-    HIP_TRY(hipMemcpy(sc->d_tris, trec.data(), sizeof(float) * trec.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMalloc((void **)&sc->d_tri_info, sizeof(int2) * info.size()));
-    HIP_TRY(hipMemcpy(sc->d_tri_info, info.data(), sizeof(int2) * info.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMalloc((void **)&sc->d_tri_shade, sizeof(float4) * std::max<size_t>(info.size(), 1)));
-    if (n_tris > 0) {
-        hipLaunchKernelGGL(k_build_tri_shade, dim3((n_tris + 255) / 256), dim3(256), 0, nullptr, sc->d_tris, sc->d_tri_info, n_tris,
-                           sc->d_tri_shade);
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipMalloc((void **)&sc->d_mats, sizeof(Material) * std::max(n_materials, 1)));
-    if (n_materials)
-        HIP_TRY(hipMemcpy(sc->d_mats, materials, sizeof(Material) * n_materials, hipMemcpyHostToDevice));
-    HIP_TRY(hipMalloc((void **)&sc->d_lights, sizeof(Light) * dl.size()));
-    HIP_TRY(hipMemcpy(sc->d_lights, dl.data(), sizeof(Light) * dl.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMalloc((void **)&sc->d_order, sizeof(int) * std::max(n_tris, 1)));
-    if (n_tris) HIP_TRY(hipMemcpy(sc->d_order, sc->h_order.data(), sizeof(int) * n_tris, hipMemcpyHostToDevice));
     sc->tab_dwords = 5 * n_materials + 24 * n_lights;
+    const size_t nt = (size_t)std::max(n_tris, 1);
+    HIP_TRY(hipMalloc((void **)&sc->d_nodes, 64 * (size_t)sc->n_nodes));
+    HIP_TRY(hipMalloc((void **)&sc->d_radius, sizeof(float) * 3));
+    HIP_TRY(hipMalloc((void **)&sc->d_tris, sizeof(float4) * 3 * nt));
+    HIP_TRY(hipMalloc((void **)&sc->d_tri_info, sizeof(int2) * nt));
+    HIP_TRY(hipMalloc((void **)&sc->d_tri_shade, sizeof(float4) * nt));
+    HIP_TRY(hipMalloc((void **)&sc->d_mats, sizeof(Material) * std::max(n_materials, 1)));
+    if (n_materials) HIP_TRY(hipMemcpy(sc->d_mats, materials, sizeof(Material) * n_materials, hipMemcpyHostToDevice));
+    HIP_TRY(hipMalloc((void **)&sc->d_lights, sizeof(Light) * std::max(n_lights, 1)));
     HIP_TRY(hipMalloc((void **)&sc->d_tables, sizeof(float) * (size_t)std::max(sc->tab_dwords, 1)));
-    {
-        int nt = std::max(std::max(n_materials, n_lights), 1);
-        hipLaunchKernelGGL(k_build_tables, dim3((nt + 63) / 64), dim3(64), 0, nullptr, sc->d_mats, n_materials,
-                           sc->d_lights, n_lights, sc->d_tris, sc->d_tables);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipDeviceSynchronize());
-    }
+    if (!sc->wide)
+        if (int rc = upload_pairs(sc.get(), pairs)) return rc;
+    int *d_inverse = nullptr;
+    if (tmp.alloc(d_inverse, nt)) return 1;
+    if (emit_scene(sc.get(), d_verts, sc->arrays(), d_inverse, nullptr, tmp)) return 1;
+    if (sc->wide) HIP_TRY(hipMemcpy(sc->origin_radius, sc->d_radius, sizeof(float) * 3, hipMemcpyDeviceToHost));
+    HIP_TRY(hipDeviceSynchronize());
     *out_scene = sc.release();
     return 0;
 }
@@ -4909,8 +4624,8 @@ static const rt_scene *scene_on_device(const rt_scene *scene, int device) {
     std::lock_guard<std::mutex> lock(scene->replica_mutex);
     for (const rt_scene *r : scene->replicas)
         if (r->device == device) return r;
-    int saved = 0;
-    if (hipGetDevice(&saved) != hipSuccess || hipSetDevice(device) != hipSuccess) {
+    DeviceGuard dev;
+    if (dev.enter(device)) {
         fail("rt_render_multi: cannot select device " + std::to_string(device));
         return nullptr;
     }
@@ -4920,7 +4635,6 @@ static const rt_scene *scene_on_device(const rt_scene *scene, int device) {
                                          scene->h_tri_light.empty() ? nullptr : scene->h_tri_light.data(), scene->h_materials.data(),
                                          scene->n_mats, scene->h_lights.data(), scene->n_lights,
                                          scene->builder == 2 ? (uint32_t)RT_SCENE_DEVICE_BVH : 0u, &rep);
-    (void)hipSetDevice(saved);
     if (rc != 0) return nullptr;
     scene->replicas.push_back(rep);
     return rep;

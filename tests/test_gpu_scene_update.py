@@ -169,12 +169,10 @@ def test_moving_the_area_light_triangle(api, bunny_full_bsdf):
     assert before.tobytes() != after.tobytes()
 
 
-def test_lbvh_built_scene(api, bunny_matte, bunny_full_bsdf, monkeypatch):
-    monkeypatch.setenv("RT_BVH_BUILDER", "lbvh")
-    a = api.Scene(bunny_full_bsdf)
-    am = api.Scene(bunny_matte)
-    monkeypatch.delenv("RT_BVH_BUILDER")
-    assert a.info()["builder"] == "lbvh" and am.info()["builder"] == "lbvh"
+def test_device_built_scene(api, bunny_matte, bunny_full_bsdf):
+    a = api.Scene(bunny_full_bsdf, device_bvh=True)
+    am = api.Scene(bunny_matte, device_bvh=True)
+    assert a.info()["builder"] == "ploc" and am.info()["builder"] == "ploc"
     new_full, new_matte = deform(bunny_full_bsdf.tris), deform(bunny_matte.tris)
     a.update(new_full)
     am.update(new_matte)
