@@ -15,7 +15,10 @@ full BSDF set (glass bunny, mirror back wall), 1920x1080, 256 spp, max_bounces 1
 resident in HBM, one RCCL sum-reduce brings the partial framebuffers to rank 0, and rank 0
 post-processes: total work is fixed, so "scaling" is "strong".
 
-Rank 0 prints ONE JSON line with the contract fields plus
+A plain run does what the headline figure needs and no more: it sets up, warms up, times the K steps, writes --dump-outputs and
+prints ONE JSON line (rank 0) with the contract fields, the frame's event totals against the committed oracle totals (a frame
+that differs carries no value), the per-frame counts and the one-off costs.  The records below take runs of their own (CPU
+oracle renders, extra frames, calibration kernels): --full adds them, and without it they are null or absent.
   roofline      dominant kernel (k_paths: the whole asynchronous part of the frame in one persistent
                 launch).  The kernel keeps rays, hit records and slot state in registers / LDS and gathers
                 a 5.7 MB scene from L2, so HBM cannot bind it (measured traffic: `hbm`); what binds it is
@@ -135,6 +138,10 @@ def parse_args():
     ap.add_argument("--max-bounces", type=int, default=10)
     ap.add_argument("--scene", default="full_bsdf",
                     choices=["matte", "full_bsdf", "four_bunnies", "sixteen_lights"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check everything else (roofline, parity, CPU baseline, the other "
+                         "RNG mode, BASELINE configs 3-5, the reference walk, N > 1 reduce timing); --no-cpu-baseline, --no-parity "
+                         "and --no-extras leave parts of it out")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-spp", type=int, default=16, help="spp of the bounded CPU-baseline sample (~10-15 s of CPU work)")
     ap.add_argument("--no-kernel-timing", action="store_true")
@@ -314,7 +321,7 @@ def main():
 
     # ---- N > 1: what the collective backend saw, every rank's share, the reduce on its own
     multi = None
-    if world > 1:
+    if world > 1 and args.full:
         ones = rtdist.sum_over_ranks([1])[0]
         per_rank = rtdist.gather_from_ranks([int(head.last["camera_rays"]), int(round(1e6 * agg["seconds_trace"] / max(agg["launches_trace"], 1))),
                                              dev_index])
@@ -348,7 +355,7 @@ def main():
     # ---- what making the reference's decisions costs: the same frame under RT_FLAG_WATERTIGHT (the triangle-list definition:
     # no check of the hits), and how often the default kernels' rare paths ran in the timed frame
     decisions = None
-    if not per_sample_headline and args.debug_flags == 0:
+    if args.full and not per_sample_headline and args.debug_flags == 0:
         n_rays = float(head_totals["closest_rays"] + head_totals["any_rays"])
         decisions = {"literal_retraces": head_totals["literal_retraces"], "reference_lost_hits": head_totals["reference_lost_hits"],
                      "exact_ties": head_totals["exact_ties"],
@@ -374,7 +381,7 @@ def main():
 
     # ---- the same frame in the OTHER RNG mode (per-sample streams: NOT the reference's random numbers), same steps
     sub_per_sample = None
-    if not args.no_extras and not per_sample_headline and args.debug_flags == 0 and spp % world == 0:
+    if args.full and not args.no_extras and not per_sample_headline and args.debug_flags == 0 and spp % world == 0:
         ps = Config(env, arrays, w, h, spp, args.max_bounces, base_flags | api.FLAG_RNG_PER_SAMPLE, args.deterministic)
         ps_elapsed, ps_agg, ps_fail = ps.timed(args.steps, args.warmup, True)
         ps_totals = ps.frame_totals()
@@ -393,7 +400,7 @@ def main():
 
     # ---- a per-sample HEADLINE (--rng-mode per_sample) is checked against one untimed reference-mode frame: the same path
     # statistics (a lost or duplicated chunk of camera-ray ids, or a wrong stream key, would move them) -- ADVICE r3
-    if per_sample_headline and args.debug_flags == 0:
+    if args.full and per_sample_headline and args.debug_flags == 0:
         ref = Config(env, arrays, w, h, spp, args.max_bounces, base_flags, args.deterministic)
         ref.step()
         ref_totals = ref.frame_totals()
@@ -404,7 +411,7 @@ def main():
 
     # ---- BASELINE configs 3, 5, 4: a few frames each, totals against the committed oracle totals
     extras = None
-    if not args.no_extras and not per_sample_headline and args.debug_flags == 0 and (w, h) == (1920, 1080):
+    if args.full and not args.no_extras and not per_sample_headline and args.debug_flags == 0 and (w, h) == (1920, 1080):
         extras = []
         for scene_name, e_spp, label in EXTRA_CONFIGS:
             cfg = Config(env, scenes.cornell_bunny(scene_name), w, h, e_spp, 10, base_flags, args.deterministic)
@@ -447,7 +454,7 @@ def main():
     # and tie rule): its event totals against the committed totals of the oracle's LITERAL mode -- the slow cross-check of what
     # the timed kernels produce.  Never the timed kernels.
     ref_walk = None
-    if not args.no_extras and not per_sample_headline and args.debug_flags == 0:
+    if args.full and not args.no_extras and not per_sample_headline and args.debug_flags == 0:
         cfg = Config(env, arrays, w, h, spp, args.max_bounces, base_flags | api.FLAG_REFERENCE_WALK, args.deterministic)
         r_elapsed, r_agg, r_fail = cfg.timed(1, 0, False)
         r_totals = cfg.frame_totals()
@@ -467,7 +474,7 @@ def main():
     # in ONE process, peer copies to devices[0]) -- on rank 0, while the other ranks wait at the final barrier.  This is the
     # path a C++ driver reaches with render(..., devices) / RTCUDA_DEVICES; here it runs on the node's real GPUs.
     in_process = None
-    if world > 1 and not args.no_extras and not per_sample_headline and args.debug_flags == 0 and rank == 0:
+    if world > 1 and args.full and not args.no_extras and not per_sample_headline and args.debug_flags == 0 and rank == 0:
         import subprocess
         devices = [k % n_dev for k in range(world)]
         what = ("rt_render_multi over the same devices, in a CHILD process of rank 0 (the other ranks idle at a barrier; a failure in "
@@ -530,7 +537,7 @@ def main():
         np_c, tt_c, np_a, tt_a = APPX_C[args.scene]
         np_src = "SURVEY.md Appendix C"
         out["parity"] = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             from oracle.oracle import Oracle, usable_cpus
             cores = usable_cpus()  # every CPU this process may use (all host cores; a box's cgroup quota caps it)
             orc = Oracle("pinned")
@@ -628,7 +635,7 @@ def main():
             out["cpu_baseline"] = None
         # ---- roofline of the dominant kernel.  Default pipeline: ONE k_paths launch per frame (init + mat + gen + ch +
         # ah of every slot as phases of a persistent kernel), so "per launch" = per frame.
-        if agg["launches_trace"] > 0 and agg["seconds_trace"] > 0:
+        if args.full and agg["launches_trace"] > 0 and agg["seconds_trace"] > 0:
             launches = agg["launches_trace"]
             persistent = launches == args.steps
             kernel = "k_paths" if persistent else "k_trace<MODE_POOL>"
