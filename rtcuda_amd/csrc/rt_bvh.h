@@ -33,7 +33,7 @@
 
 namespace rtbvh {
 
-// Experiment knobs (RT_PERSISTENT, RT_MAJORITY, RT_BVH_WIDE, RT_BVH_MAX_LEAF, ...: DESIGN.md section 7) are read only when
+// Experiment knobs (RT_PERSISTENT, RT_SPLIT, RT_BVH_WIDE, RT_BVH_MAX_LEAF, ...: DESIGN.md section 7) are read only when
 // the process sets RTCUDA_EXPERIMENTAL=1: a drop-in library must not change behaviour because some RT_* name happens to be
 // set in a user's shell.  Tests and tools set the gate; bench.py never does.
 inline const char *knob(const char *name) {

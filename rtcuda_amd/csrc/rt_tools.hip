@@ -516,9 +516,10 @@ int rt_split_probe(const rt_scene *scene, const rt_camera *camera, int width, in
     const int stack_cap = lds_stack_cap(scene, kLdsStack);
     const size_t lds_bytes = sizeof(int) * (size_t)kBlock * (size_t)(stack_cap + 2);
     if (ensure_overflow(c.d_over, c.over_levels, scene->stack_bound - std::min(stack_cap, lds_stack_cap(scene, kPathsLdsStack)))) return 1;
+    const AdvanceKernel advance = advance_kernel(lds_tables);
+    const TraceKernel trace = trace_kernel<MODE_POOL>(false, false, scene->wide);  // (the watertight build)
     int occ_c = 0;
-    if (scene->wide) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_c, k_trace<MODE_POOL, true>, kBlock, lds_bytes));
-    else HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_c, k_trace<MODE_POOL, false>, kBlock, lds_bytes));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_c, trace, kBlock, lds_bytes));
     const dim3 grid(grid_for(n)), block(kBlock), grid_trace(std::min(grid_for(n), std::max(1, cus * std::max(1, occ_c))));
     TraceParams tpp{};
     tpp.total = n;
@@ -542,13 +543,13 @@ int rt_split_probe(const rt_scene *scene, const rt_camera *camera, int width, in
         ap.round = rounds;
         double t = 0.0;
         HIP_TRY(hipEventRecord(pb.e0, nullptr));
-        RT_LAUNCH_ADVANCE(nullptr, fb);
+        hipLaunchKernelGGL(advance, grid, block, 0, nullptr, sc, c.pools, cam, ap, fb, c.d_ctr, c.d_rows, c.d_lock);
         if (timed(t)) return 1;
         if (rounds == 0) t_adv0 = t;  // every slot generates: gen() alone
         else t_adv += t;
         hipLaunchKernelGGL(k_probe_dump_rays, grid, block, 0, nullptr, c.pools, n, c_o3, c_d3, c_tmax, a_o3, a_d3, a_tmax, a_excl, cap, d_counts);
         HIP_TRY(hipEventRecord(pb.e0, nullptr));
-        RT_LAUNCH_TRACE(MODE_POOL, scene->wide, grid_trace, lds_bytes, nullptr, sc, c.pools, tpp, stack_cap, c.d_over);
+        hipLaunchKernelGGL(trace, grid_trace, block, lds_bytes, nullptr, sc, c.pools, tpp, stack_cap, c.d_over);
         if (timed(t_trace)) return 1;
         hipLaunchKernelGGL(k_probe_dump_shades, grid, block, 0, nullptr, sc, c.pools, n, max_bounces, rec, cap, d_counts);
         HIP_TRY(hipGetLastError());

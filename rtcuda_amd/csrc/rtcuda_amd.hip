@@ -631,18 +631,13 @@ __device__ __forceinline__ void advance_core(const DScene &sc, const float *tab,
 // the flipped unit normal and the material / light ids, so no triangle is gathered here.  The
 // kernel has no atomics on shared words and one barrier (the table staging): the shadow ray goes
 // to the slot's own record, event counts go to the wave's own counter row.
-// SORT (material-sorted shading; opt-in with RT_SORT_SHADE=1): which slot a thread serves is decided per
-// workgroup by the MATERIAL the slot is about to shade with.  The 256 slots of the block are partitioned -- ballot + mbcnt
-// ranks per wave, wave offsets through 16 LDS counters -- into [matte | mirror | glass | nothing to shade] and thread t takes
-// the t-th slot of that order, so a wave runs one branch of Material::sample_f (material.cuh:60-109) instead of all three
-// (the reference shades in compacted-queue order, whatever the material: render.cuh:139-145).  A slot's computation does
-// not depend on the thread that runs it, and every per-slot array is indexed by the slot: results are unchanged (a GPU
-// test holds the fixed-point sums equal).  Measured on C2's whole frame through the round pipeline (RT_PERSISTENT=0):
-// k_advance takes 87 ms sorted against 70 ms in slot order (frame 535 vs 517 ms, profiles/r04_experiments.md) -- the kernel
-// streams 36 arrays of slot state and is bound by that traffic; the sort costs a dependent load phase and two barriers in
-// front of it and scatters the accesses inside the block's window, while the divergence it removes (three short branches of
-// sample_f) was not what the kernel waited for.  So slot order stays the default, here as in the persistent kernel.
-template <bool LDS_TABLES, bool SORT = false>
+// Thread t serves slot t of its block, whatever the material (the reference shades in compacted-queue order too:
+// render.cuh:139-145).  Sorting the block's slots by material, so that a wave runs one branch of Material::sample_f, was
+// measured on C2's whole frame through the round pipeline (RT_PERSISTENT=0): k_advance took 87 ms sorted against 70 ms in
+// slot order (profiles/r04_experiments.md) -- the kernel streams 36 arrays of slot state and is bound by that traffic; the
+// sort costs a dependent load phase and two barriers in front of it, while the divergence it removes was not what the
+// kernel waited for.
+template <bool LDS_TABLES>
 __global__ void __launch_bounds__(kBlock)
 k_advance(DScene sc, DPools p, Camera cam, AdvanceParams ap, float *__restrict__ fb, DCounters *__restrict__ ctr,
           DWaveRow *__restrict__ rows, unsigned int *__restrict__ lock_shades) {
@@ -652,33 +647,7 @@ k_advance(DScene sc, DPools p, Camera cam, AdvanceParams ap, float *__restrict__
     // (round 0 only generates; once a round is skipped it counts nothing, so every later one is skipped too).  No host poll.
     if (ap.lockstep >= 3 && lock_shades[ap.lockstep - 2] == 0u) return;
     __shared__ float s_tab[LDS_TABLES ? kTabDwordsMax : 1];
-    __shared__ int s_perm[SORT ? kBlock : 1];
-    __shared__ int s_count[SORT ? 16 : 1];  // [kind][wave of the block]
-
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (SORT) {
-        int kind = 3;  // nothing to shade: gen(), an idle or finished slot, a thread past the end
-        if (i < ap.n) {
-            const int b = p.bounces(i), hi = p.hit_info(i);
-            if (b != kDone && b != kParked && hi >= 0 && b < ap.max_bounces)  // init() will route it to mat() (render.cuh:109,128-130)
-                kind = min(max(__float_as_int(sc.tables[5 * (hi & 0xffff) + 4]), 0), 2);
-        }
-        const unsigned wave = threadIdx.x >> 6;
-        unsigned rank = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const unsigned long long m = wave_ballot(kind == k);
-            if (kind == k) rank = prefix_popc(m);
-            if (lane_id() == 0) s_count[4 * k + wave] = (int)__popcll(m);
-        }
-        __syncthreads();
-        int base = 0;
-        for (int q = 0; q < 16; q++)  // everything of a smaller kind, and of this kind in the waves before this one
-            base += (q < 4 * kind + (int)wave) ? s_count[q] : 0;
-        s_perm[base + (int)rank] = (int)threadIdx.x;
-        __syncthreads();
-        i = blockIdx.x * blockDim.x + s_perm[threadIdx.x];
-    }
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const bool in_range = i < ap.n;
     // ---- issue all per-slot loads up front
     SlotState st;
@@ -1620,16 +1589,20 @@ constexpr bool kSpeculate = RT_SPECULATE != 0;  // k_paths: postpone a leaf reac
 // ref_visible): a shadow ray's accepted hit counts only if the reference's walk can see its triangle (triangle block); a
 // path ray's closest hit is checked once, at the top of the ADV block that shades it -- visible, and no exact tie at the
 // final distance -- and the ~2 rays in 10^7 that fail are re-traced there by reference_walk.
-template <bool LDS_TABLES, bool WIDE, bool MAJORITY, int MIN_WAVES, bool DRAW_CIDS = false, bool LITERAL = false, bool VERIFY = false>
+template <bool LDS_TABLES, bool WIDE, int MIN_WAVES, bool DRAW_CIDS = false, bool LITERAL = false, bool VERIFY = false>
 __global__ void __launch_bounds__(kBlock, MIN_WAVES)
 k_paths(DScene sc, DPools p, Camera cam_arg, AdvanceParams ap_arg, float *__restrict__ fb, DWaveRow *__restrict__ rows,
         int stack_cap, int *overflow, int adv_batch, int debug_no_deposit, unsigned long long *prof, int top_n,
         int prio_period, int rot_wave, int rot_set, int gen_batch, int tri_follow, unsigned int *__restrict__ next_cid,
-        int half_fill, unsigned long long *__restrict__ vstat) {
+        unsigned long long *__restrict__ vstat) {
     // The GEN block exists where the chip is short of issue slots (4 waves per SIMD): there it takes a third of the
     // lanes out of the long ADV block (+3 %, and the ADV block no longer spills).  On small shards (2 waves per
     // SIMD) a slot-round is a latency chain and one more block in it costs 5 %: gen() stays inside ADV there.
     constexpr bool SPLIT_GEN = MIN_WAVES != 2;
+    // Code placement: where the hot blocks fall within 64-byte instruction-cache lines is worth 0.7 % of the frame.  With
+    // the body 8 bytes earlier than these two s_nop put it, C2's k_paths took 108.7 ms against 107.9 ms (same instructions
+    // otherwise).  Time the frame (tools/ab_bench.py) after any edit that moves the code of this kernel.
+    asm volatile("s_nop 0\n\ts_nop 0");
     extern __shared__ int s_lds[];
     int *stack = s_lds + threadIdx.x;
     float *park = (float *)(s_lds + (stack_cap + 1) * kBlock) + threadIdx.x;  // element k at park[k * kBlock]
@@ -1692,9 +1665,6 @@ k_paths(DScene sc, DPools p, Camera cam_arg, AdvanceParams ap_arg, float *__rest
         // (the grid is a power of two: W is, shard counts divide it, and the host halves from there)
         const unsigned b = (wave_in_grid + (wave_in_grid & 3u) * (unsigned)rot_wave + (unsigned)set * (unsigned)rot_set) &
                            (((unsigned)lanes_in_grid >> 6) - 1u);
-        // half_fill (small shards, experiment): only lanes 0..31 of a wave own slots -- twice the waves, each with half
-        // the chains: a wave's block stream gets shorter where issue slots are to spare
-        if (half_fill) return lane_in_wave < 32u ? set * (lanes_in_grid >> 1) + (int)(b * 32u + lane_in_wave) : 0x7fffffff;
         return set * lanes_in_grid + (int)(b * 64u + lane_in_wave);
     };
     int slot_set = 0;
@@ -1844,15 +1814,12 @@ k_paths(DScene sc, DPools p, Camera cam_arg, AdvanceParams ap_arg, float *__rest
         };
         // Every block is issued for the whole wave whatever the number of lanes that need it.  The ADV
         // block is ~15x longer than a node step or a triangle test, so it waits for `adv_batch` lanes
-        // unless nothing else can run.  MAJORITY additionally runs only the more popular of the two
-        // traversal blocks per iteration (one triangle per lane per iteration).
-        bool run_adv = n_adv > 0 && (n_adv >= adv_batch || n_node + n_tri == 0);
-        // (MAJORITY: the ADV lanes must also be at least half as many as the node and as the triangle lanes.  Requiring
-        // a full majority measured 1 % slower.  Dropping the condition is as fast in logic, but when the kernel sat
-        // exactly at 128 VGPRs that source shape tipped the register allocation into 21 spills: -6 %.  The kernel has
-        // since come down to 115, but `make resource-usage` after any edit here all the same: "VGPRs Spill" of
-        // k_paths<..., 4> must stay 0 (a CPU test checks it).)
-        if (MAJORITY) run_adv = n_adv > 0 && ((n_adv >= adv_batch && 2 * n_adv >= n_node && 2 * n_adv >= n_tri) || n_node + n_tri == 0);
+        // unless nothing else can run, and the ADV lanes must also be at least half as many as the node and as the triangle
+        // lanes.  (Requiring a full majority measured 1 % slower.  Dropping the half condition is as fast in logic, but when
+        // the kernel sat exactly at 128 VGPRs that source shape tipped the register allocation into 21 spills: -6 %.  The
+        // kernel has since come down to 115, but `make resource-usage` after any edit here all the same: "VGPRs Spill" of
+        // k_paths<..., 4, ...> must stay 0 (a CPU test checks it).)
+        const bool run_adv = n_adv > 0 && ((n_adv >= adv_batch && 2 * n_adv >= n_node && 2 * n_adv >= n_tri) || n_node + n_tri == 0);
         // ---------------- GEN block: gen() (render.cuh:250-275) for the lanes whose path certainly ended -- it missed
         // or ran out of bounces (a third of all ADV work), or the ADV block found it Russian-roulette-killed to the
         // last bounce.  A tenth of the ADV block's length, so it runs for far fewer waiting lanes.
@@ -1967,11 +1934,7 @@ k_paths(DScene sc, DPools p, Camera cam_arg, AdvanceParams ap_arg, float *__rest
                     Tri tr = load_tri(sc.tris, tri);
                     float4 sh = sc.tri_shade[(unsigned)tri];
                     RT_MARK("adv.verify");
-#ifdef RT_DBG_NO_ADV_VERIFY  // (timing experiment only: the image is no longer the reference's)
-                    if (false) {
-#else
                     if (VERIFY) {
-#endif
                         // (o, d) are still the path ray that ended on `tri`.  A set sign bit of hv: an exact tie at the final
                         // distance (triangle block) -- or a v of -0.0, which costs a needless, equally exact re-trace
                         bool bad = (__float_as_uint(hv) >> 31) != 0u;
@@ -2095,11 +2058,7 @@ k_paths(DScene sc, DPools p, Camera cam_arg, AdvanceParams ap_arg, float *__rest
                 // 4-wide nodes on the full pool: ONE wave vote per step decides between the step without any overflow
                 // handling (all lanes of the block hold at most stack_cap - 3 entries: 95 % of the steps) and the general one
                 auto step = [&]() {
-#ifdef RT_NO_SHALLOW
-                    if (true) {
-#else
                     if (!WIDE || MIN_WAVES == 2) {
-#endif
                         step_general();
                     } else if (wave_ballot(sp > stack_cap - 3) == 0ull) {
                         if (cur >= 0) {
@@ -2198,7 +2157,6 @@ k_paths(DScene sc, DPools p, Camera cam_arg, AdvanceParams ap_arg, float *__rest
                 }
                 pend = occluded ? kEntryDone : pd;
                 cur = occluded ? kEntryDone : cu;
-#ifndef RT_DBG_NO_TRI_VERIFY  // (timing experiment only)
                 // VERIFY: an occluder only counts if the reference's walk can see its triangle (2 % of the shadow rays get here;
                 // ONE branch behind both tests: inside each test it cost the block's straight-line shape, 2 % of the frame).  An
                 // occluder it cannot see -- ~1 in 10^7 -- says nothing about the rest of the ray: the ray ends here and is
@@ -2212,26 +2170,19 @@ k_paths(DScene sc, DPools p, Camera cam_arg, AdvanceParams ap_arg, float *__rest
                     tq.n = tq.p0;  // (not looked at)
                     if (!ref_visible(sc, o, d, tq, occ_j ? ks[1] : ks[0], vstat)) hu = 2.f;
                 }
-#endif
             }
 #ifdef RT_TRACE_PROFILE
             pf[10] += __builtin_readcyclecounter() - pf_tt;
 #endif
             RT_MARK("tri.end");
         };
-        // Which of the two.  MAJORITY: the more popular block -- and when that is the node block, the triangle block right
-        // behind it for the lanes that hold a leaf BY THEN (at least `tri_follow` of them): a lane that reached a leaf in
-        // the node block has its triangles tested in this scheduling round instead of the next one.  Measured on C2:
-        // +6.6 % at tri_follow = 1, +5.3 % at 12, +0.4 % at 40; the mirror image (a node block behind a triangle block) buys
-        // nothing on top and loses 5 % alone.  Without MAJORITY: both blocks, for the lanes that wanted them at the top.
-        if (!MAJORITY) {
-            if (n_node > 0) node_block(want_node, n_node);
-            if (n_tri > 0) tri_block(want_tri, n_tri);
-        }
-#ifndef RT_TRI_TWO_COPIES
-        else {
-            // (ONE copy of the triangle block in the code: the block behind a node block and the block on its own are the same
-            // instructions for different lanes)
+        // Which of the two: the more popular block -- and when that is the node block, the triangle block right behind it
+        // for the lanes that hold a leaf BY THEN (at least `tri_follow` of them): a lane that reached a leaf in the node
+        // block has its triangles tested in this scheduling round instead of the next one.  Measured on C2: +6.6 % at
+        // tri_follow = 1, +5.3 % at 12, +0.4 % at 40; the mirror image (a node block behind a triangle block) buys nothing on
+        // top and loses 5 % alone.  (ONE copy of the triangle block in the code: the block behind a node block and the block
+        // on its own are the same instructions for different lanes.)
+        {
             const bool run_node = n_node > 0 && n_node >= n_tri;
             bool w = want_tri;
             int nw = n_tri;
@@ -2243,18 +2194,6 @@ k_paths(DScene sc, DPools p, Camera cam_arg, AdvanceParams ap_arg, float *__rest
             }
             if (nw > 0) tri_block(w, nw);
         }
-#else
-        else if (n_node > 0 && n_node >= n_tri) {
-            node_block(want_node, n_node);
-            if (tri_follow > 0) {
-                const bool w = trav && ((cur != kEntryDone && cur < 0) || (kSpeculate && pend != kEntryDone));
-                const int nw = wave_count(w);
-                if (nw >= tri_follow) tri_block(w, nw);
-            }
-        } else if (n_tri > 0) {
-            tri_block(want_tri, n_tri);
-        }
-#endif
         // ---------------- finished rays
         RT_MARK("fin.begin");
         const bool fin = trav && cur == kEntryDone && (!kSpeculate || pend == kEntryDone);
@@ -3676,9 +3615,8 @@ int get_context(int n, int lane, Context **out) {
     if (dev_alloc(*c, p.base, (size_t)A_COUNT * n)) return 1;
     if (dev_alloc(*c, c->rng_backup, (size_t)6 * n)) return 1;
     if (dev_alloc(*c, c->d_ctr, 1)) return 1;
-    // one counter row per wave of the largest grid this context launches: k_advance's (n / 64 waves); the RT_HALF_WAVES
-    // experiment launches k_paths with twice its usual waves, which on a small shard can exceed that
-    c->n_rows = (knob("RT_HALF_WAVES") ? 2 : 1) * ((n + kBlock - 1) / kBlock) * (kBlock / 64);
+    // one counter row per wave of the largest grid this context launches: k_advance's (n / 64 waves)
+    c->n_rows = ((n + kBlock - 1) / kBlock) * (kBlock / 64);
     if (dev_alloc(*c, c->d_rows, (size_t)c->n_rows)) return 1;
     if (dev_alloc(*c, c->d_jump, (size_t)20 * 800)) return 1;
     HIP_TRY(hipMemcpy(c->d_jump, jump_powers().data(), sizeof(uint32_t) * 20 * 800, hipMemcpyHostToDevice));
@@ -3702,34 +3640,40 @@ static int lds_stack_cap(const rt_scene *scene, int limit) {
     return cap;
 }
 
-// launches k_advance<LDS tables?, material-sorted?> for one round (uses grid, block, sc, c, cam, ap, lds_tables of the caller)
-static bool sort_shade() {
-    const char *e = knob("RT_SORT_SHADE");
-    return e ? atoi(e) != 0 : false;  // (measured on C2's round pipeline: 535 ms sorted, 517 ms in slot order -- see k_advance)
-}
-#define RT_LAUNCH_ADVANCE(stream, fbptr)                                                                                         \
-    do {                                                                                                                         \
-        if (lds_tables && sort_shade()) hipLaunchKernelGGL((k_advance<true, true>), grid, block, 0, stream, sc, c.pools, cam, ap, fbptr, c.d_ctr, c.d_rows, c.d_lock);   \
-        else if (lds_tables) hipLaunchKernelGGL((k_advance<true, false>), grid, block, 0, stream, sc, c.pools, cam, ap, fbptr, c.d_ctr, c.d_rows, c.d_lock);             \
-        else if (sort_shade()) hipLaunchKernelGGL((k_advance<false, true>), grid, block, 0, stream, sc, c.pools, cam, ap, fbptr, c.d_ctr, c.d_rows, c.d_lock);           \
-        else hipLaunchKernelGGL((k_advance<false, false>), grid, block, 0, stream, sc, c.pools, cam, ap, fbptr, c.d_ctr, c.d_rows, c.d_lock);                            \
-    } while (0)
+// Kernel selection: every build of one kernel template has the same signature, so the flags pick a function pointer and
+// the caller launches (and sizes the grid with) that pointer.
+using AdvanceKernel = decltype(&k_advance<false>);
+using TraceKernel = decltype(&k_trace<MODE_POOL, false>);
+using PathsKernel = decltype(&k_paths<false, false, 4, false, false, false>);
 
-// launches k_trace<MODE, wide?> -- the node format is a property of the scene
-#define RT_LAUNCH_TRACE(MODE, wide, grid, lds, stream, ...)                                                \
-    do {                                                                                                   \
-        if (wide) hipLaunchKernelGGL((k_trace<MODE, true>), grid, dim3(kBlock), lds, stream, __VA_ARGS__);   \
-        else hipLaunchKernelGGL((k_trace<MODE, false>), grid, dim3(kBlock), lds, stream, __VA_ARGS__);       \
-    } while (0)
-// ... or, with RT_FLAG_REFERENCE_WALK, the build that walks the reference's tree (the node format does not matter then);
-// `verify`: the default build -- the product's walk with the reference's decisions (ref_visible); neither: RT_FLAG_WATERTIGHT
-#define RT_LAUNCH_TRACE_REF(MODE, literal, verify, wide, grid, lds, stream, ...)                                          \
-    do {                                                                                                                  \
-        if (literal) hipLaunchKernelGGL((k_trace<MODE, false, 8, true>), grid, dim3(kBlock), lds, stream, __VA_ARGS__);     \
-        else if ((verify) && (wide)) hipLaunchKernelGGL((k_trace<MODE, true, 8, false, true>), grid, dim3(kBlock), lds, stream, __VA_ARGS__); \
-        else if (verify) hipLaunchKernelGGL((k_trace<MODE, false, 8, false, true>), grid, dim3(kBlock), lds, stream, __VA_ARGS__); \
-        else RT_LAUNCH_TRACE(MODE, wide, grid, lds, stream, __VA_ARGS__);                                                 \
-    } while (0)
+static AdvanceKernel advance_kernel(bool lds_tables) { return lds_tables ? k_advance<true> : k_advance<false>; }
+
+// k_trace<MODE>: with RT_FLAG_REFERENCE_WALK the build that walks the reference's tree (the node format does not matter
+// then); `verify`: the default build -- the product's walk with the reference's decisions (ref_visible); neither:
+// RT_FLAG_WATERTIGHT.  Otherwise the node format is a property of the scene.
+template <int MODE>
+static TraceKernel trace_kernel(bool literal, bool verify, bool wide) {
+    if (literal) return k_trace<MODE, false, 8, true>;
+    if (verify) return wide ? k_trace<MODE, true, 8, false, true> : k_trace<MODE, false, 8, false, true>;
+    return wide ? k_trace<MODE, true> : k_trace<MODE, false>;
+}
+
+// k_paths: MIN_WAVES = 4 waves per SIMD (at most 128 VGPRs) when the grid fills the chip, 2 (up to 256 VGPRs) when the
+// shard is so small that only 2 workgroups per CU exist anyway (8-GPU runs).  RT_FLAG_REFERENCE_WALK: the build whose node
+// block is the reference's own walk (full pool: the 4-wave build although it spills 53 VGPRs -- measured 1 082 ms for C2's
+// frame against 1 412 ms for the spill-free 2-wave build at half the occupancy).  Per-sample streams on the full pool: the
+// build in which the waves draw their camera rays from the frame's counter.
+template <bool LDS_TABLES, bool WIDE>
+static PathsKernel paths_kernel_of(bool few_blocks, bool per_sample, bool literal, bool verify) {
+    if (literal) return few_blocks ? k_paths<LDS_TABLES, false, 2, false, true, false> : k_paths<LDS_TABLES, false, 4, false, true, false>;
+    if (per_sample && !few_blocks) return k_paths<LDS_TABLES, WIDE, 4, true, false, false>;
+    if (few_blocks) return verify ? k_paths<LDS_TABLES, WIDE, 2, false, false, true> : k_paths<LDS_TABLES, WIDE, 2, false, false, false>;
+    return verify ? k_paths<LDS_TABLES, WIDE, 4, false, false, true> : k_paths<LDS_TABLES, WIDE, 4, false, false, false>;
+}
+static PathsKernel paths_kernel(bool lds_tables, bool wide, bool few_blocks, bool per_sample, bool literal, bool verify) {
+    if (lds_tables) return (wide ? paths_kernel_of<true, true> : paths_kernel_of<true, false>)(few_blocks, per_sample, literal, verify);
+    return (wide ? paths_kernel_of<false, true> : paths_kernel_of<false, false>)(few_blocks, per_sample, literal, verify);
+}
 
 // Global overflow part of the traversal stacks: `levels` entries for each of kOverStride lanes.  Every OWNER of
 // concurrently running grids has its own buffer -- a render context (one render at a time: Context::busy), or one
@@ -3900,10 +3844,10 @@ int render_shard_impl(const rt_scene *scene, const rt_camera *camera, int width,
     // advance grid, whose wave count sizes the counter rows)
     int dev_cus = 0, occ_c = 0;
     HIP_TRY(hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, dev));
-    if (scene->wide)
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_c, k_trace<MODE_POOL, true>, kBlock, lds_bytes));
-    else
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_c, k_trace<MODE_POOL, false>, kBlock, lds_bytes));
+    const AdvanceKernel advance = advance_kernel(lds_tables);
+    const TraceKernel trace = trace_kernel<MODE_POOL>(literal, verify, scene->wide);
+    // (every k_trace build runs 8 waves per SIMD without static LDS: the grid does not depend on which one this is)
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_c, trace, kBlock, lds_bytes));
     int per_cu = std::max(1, occ_c);
     if (const char *e = knob("RT_TRACE_BLOCKS_PER_CU")) per_cu = std::max(1, std::min(per_cu, atoi(e)));
     const int resident = std::max(1, dev_cus * per_cu);
@@ -3947,21 +3891,15 @@ int render_shard_impl(const rt_scene *scene, const rt_camera *camera, int width,
         int *const d_over2 = d_over;
         size_t lds_paths = sizeof(int) * (size_t)kBlock * (size_t)(paths_cap + 26) + (lds_tables ? sizeof(float) * (size_t)((scene->tab_dwords + 3) & ~3) : 0) +
                            sizeof(Camera) + sizeof(AdvanceParams);
-        bool majority = true;
-        if (const char *e = knob("RT_MAJORITY")) majority = atoi(e) != 0;
         const int dbg = (flags & 0x100u) ? 1 : 0;
         unsigned long long *paths_prof = nullptr;
 #ifdef RT_TRACE_PROFILE
-        const size_t prof_bytes = 192 + 32 * (size_t)(2 * grid_for(n) * (kBlock / 64));  // (x 2: RT_HALF_WAVES)
+        const size_t prof_bytes = 192 + 32 * (size_t)(grid_for(n) * (kBlock / 64));
         HIP_TRY(hipMalloc((void **)&paths_prof, prof_bytes));
         HIP_TRY(hipMemset(paths_prof, 0, prof_bytes));
 #endif
         // all workgroups resident at once (4 per CU at <= 128 VGPRs), lane count a divisor of n
         int paths_blocks = grid_for(n);
-        // RT_HALF_WAVES=1 (experiment, shards of <= 1/8 of the slots): 32 slots per wave instead of 64, twice the waves
-        int half_fill = 0;
-        if (const char *e = knob("RT_HALF_WAVES")) half_fill = (atoi(e) != 0 && 2 * paths_blocks <= 1024 && !per_sample && 2 * paths_blocks * (kBlock / 64) <= c.n_rows) ? 1 : 0;  // (rows: see get_context)
-        if (half_fill) paths_blocks *= 2;
         {
             int want = 1024;
             if (const char *e = knob("RT_PATHS_BLOCKS")) want = std::max(1, atoi(e));
@@ -3993,10 +3931,6 @@ int render_shard_impl(const rt_scene *scene, const rt_camera *camera, int width,
         // 2-waves-per-SIMD shards want 30..38 (24: -2.5 %)
         int adv_batch = few_blocks ? 34 : 20;
         int gen_batch = 6;  // lanes waiting for the GEN block before it runs (unless nothing else can); flat 4..8
-        if (half_fill) {  // (half the lanes per wave: half the thresholds)
-            adv_batch /= 2;
-            gen_batch /= 2;
-        }
         if (const char *e = knob("RT_ADV_BATCH")) adv_batch = std::max(1, std::min(64, atoi(e)));
         if (const char *e = knob("RT_GEN_BATCH")) gen_batch = std::max(1, std::min(64, atoi(e)));
         int tri_follow = 1;  // a triangle block right behind a node block when this many lanes hold a leaf by then; 0 = never
@@ -4024,61 +3958,11 @@ int render_shard_impl(const rt_scene *scene, const rt_camera *camera, int width,
         }
         if (const char *e = knob("RT_PRIO_ROTATE")) prio_rotate = atoi(e);
         HIP_TRY(hipEventRecord(c.ev_a, st));
-// MIN_WAVES: 4 waves per SIMD (at most 128 VGPRs) when the grid fills the chip, 2 (up to 256 VGPRs) when the
-        // shard is so small that only 2 workgroups per CU exist anyway (8-GPU runs)
-#define RT_LAUNCH_PATHS_V(T, WD, MJ, VER)                                                                              \
-    do {                                                                                                               \
-        if (few_blocks)                                                                                                \
-            hipLaunchKernelGGL((k_paths<T, WD, MJ, 2, false, false, VER>), grid_paths, block, lds_paths, st, sc, c.pools, cam, ap, d_sum,   \
-                               c.d_rows, paths_cap, d_over2, adv_batch, dbg, paths_prof, top_n, prio_rotate, rot_wave, rot_set, gen_batch, tri_follow, &c.d_ctr->pad2[0], half_fill, &c.d_ctr->vstat[0]); \
-        else                                                                                                           \
-            hipLaunchKernelGGL((k_paths<T, WD, MJ, 4, false, false, VER>), grid_paths, block, lds_paths, st, sc, c.pools, cam, ap, d_sum,   \
-                               c.d_rows, paths_cap, d_over2, adv_batch, dbg, paths_prof, 0, prio_rotate, rot_wave, rot_set, gen_batch, tri_follow, &c.d_ctr->pad2[0], half_fill, &c.d_ctr->vstat[0]);     \
-    } while (0)
-#define RT_LAUNCH_PATHS(T, WD, MJ)                 \
-    do {                                           \
-        if (verify) RT_LAUNCH_PATHS_V(T, WD, MJ, true); \
-        else RT_LAUNCH_PATHS_V(T, WD, MJ, false);  \
-    } while (0)
-        if (literal) {
-            // RT_FLAG_REFERENCE_WALK: the build whose node block is the reference's own walk
-            // (full pool: the 4-wave build although it spills 53 VGPRs -- measured 1 082 ms for C2's frame against 1 412 ms
-            // for the spill-free 2-wave build at half the occupancy)
-#define RT_LAUNCH_REF(T)                                                                                               \
-    do {                                                                                                               \
-        if (few_blocks)                                                                                                \
-            hipLaunchKernelGGL((k_paths<T, false, true, 2, false, true>), grid_paths, block, lds_paths, st, sc, c.pools, cam, ap, d_sum, \
-                               c.d_rows, paths_cap, d_over2, adv_batch, dbg, paths_prof, 0, prio_rotate, rot_wave, rot_set, gen_batch, tri_follow, &c.d_ctr->pad2[0], half_fill, &c.d_ctr->vstat[0]); \
-        else                                                                                                           \
-            hipLaunchKernelGGL((k_paths<T, false, true, 4, false, true>), grid_paths, block, lds_paths, st, sc, c.pools, cam, ap, d_sum, \
-                               c.d_rows, paths_cap, d_over2, adv_batch, dbg, paths_prof, 0, prio_rotate, rot_wave, rot_set, gen_batch, tri_follow, &c.d_ctr->pad2[0], half_fill, &c.d_ctr->vstat[0]); \
-    } while (0)
-            if (lds_tables) RT_LAUNCH_REF(true);
-            else RT_LAUNCH_REF(false);
-#undef RT_LAUNCH_REF
-        } else if (per_sample && !few_blocks) {
-            // per-sample streams: the build in which the waves draw their camera rays from the frame's counter
-#define RT_LAUNCH_DRAW(T, WD)                                                                                          \
-    hipLaunchKernelGGL((k_paths<T, WD, true, 4, true>), grid_paths, block, lds_paths, st, sc, c.pools, cam, ap, d_sum,  \
-                       c.d_rows, paths_cap, d_over2, adv_batch, dbg, paths_prof, 0, prio_rotate, rot_wave, rot_set, gen_batch, tri_follow, &c.d_ctr->pad2[0], half_fill, &c.d_ctr->vstat[0])
-            if (lds_tables && scene->wide) RT_LAUNCH_DRAW(true, true);
-            else if (lds_tables) RT_LAUNCH_DRAW(true, false);
-            else if (scene->wide) RT_LAUNCH_DRAW(false, true);
-            else RT_LAUNCH_DRAW(false, false);
-#undef RT_LAUNCH_DRAW
-        } else if (majority) {
-            if (lds_tables && scene->wide) RT_LAUNCH_PATHS(true, true, true);
-            else if (lds_tables) RT_LAUNCH_PATHS(true, false, true);
-            else if (scene->wide) RT_LAUNCH_PATHS(false, true, true);
-            else RT_LAUNCH_PATHS(false, false, true);
-        } else {
-            if (lds_tables && scene->wide) RT_LAUNCH_PATHS(true, true, false);
-            else if (lds_tables) RT_LAUNCH_PATHS(true, false, false);
-            else if (scene->wide) RT_LAUNCH_PATHS(false, true, false);
-            else RT_LAUNCH_PATHS(false, false, false);
-        }
-#undef RT_LAUNCH_PATHS
-#undef RT_LAUNCH_PATHS_V
+        // (the reference-walk build is passed top_n = 0, while top_n * 64 bytes of LDS stay reserved and reported in reserved[2])
+        const PathsKernel paths = paths_kernel(lds_tables, scene->wide, few_blocks, per_sample, literal, verify);
+        hipLaunchKernelGGL(paths, grid_paths, block, lds_paths, st, sc, c.pools, cam, ap, d_sum, c.d_rows, paths_cap, d_over2, adv_batch,
+                           dbg, paths_prof, literal ? 0 : top_n, prio_rotate, rot_wave, rot_set, gen_batch, tri_follow, &c.d_ctr->pad2[0],
+                           &c.d_ctr->vstat[0]);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(c.ev_b, st));
         HIP_TRY(hipEventSynchronize(c.ev_b));
@@ -4120,14 +4004,14 @@ int render_shard_impl(const rt_scene *scene, const rt_camera *camera, int width,
                 hipEvent_t e0, e1, e2, e3;
                 if (next_event(&e0) || next_event(&e1) || next_event(&e2) || next_event(&e3)) return 1;
                 HIP_TRY(hipEventRecord(e0, st));
-                RT_LAUNCH_ADVANCE(st, d_sum);
+                hipLaunchKernelGGL(advance, grid, block, 0, st, sc, c.pools, cam, ap, d_sum, c.d_ctr, c.d_rows, c.d_lock);
                 HIP_TRY(hipEventRecord(e1, st));
-                RT_LAUNCH_TRACE_REF(MODE_POOL, literal, verify, scene->wide, grid_trace, lds_bytes, st, sc, c.pools, tpp, stack_cap, d_over);
+                hipLaunchKernelGGL(trace, grid_trace, block, lds_bytes, st, sc, c.pools, tpp, stack_cap, d_over);
                 HIP_TRY(hipEventRecord(e2, st));
                 HIP_TRY(hipEventRecord(e3, st));
             } else {
-                RT_LAUNCH_ADVANCE(st, d_sum);
-                RT_LAUNCH_TRACE_REF(MODE_POOL, literal, verify, scene->wide, grid_trace, lds_bytes, st, sc, c.pools, tpp, stack_cap, d_over);
+                hipLaunchKernelGGL(advance, grid, block, 0, st, sc, c.pools, cam, ap, d_sum, c.d_ctr, c.d_rows, c.d_lock);
+                hipLaunchKernelGGL(trace, grid_trace, block, lds_bytes, st, sc, c.pools, tpp, stack_cap, d_over);
             }
             rounds++;
         }
@@ -4168,10 +4052,10 @@ int render_shard_impl(const rt_scene *scene, const rt_camera *camera, int width,
             for (int j = lock_enqueued; j < hi; j++) {
                 ap.round = (int)((rounds + j) & 0x3fffffff);
                 ap.lockstep = 1 + j;
-                RT_LAUNCH_ADVANCE(st, d_sum);
+                hipLaunchKernelGGL(advance, grid, block, 0, st, sc, c.pools, cam, ap, d_sum, c.d_ctr, c.d_rows, c.d_lock);
                 tpp.lock_shades = c.d_lock;
                 tpp.lock_round = j;
-                RT_LAUNCH_TRACE_REF(MODE_POOL, literal, verify, scene->wide, grid_trace, lds_bytes, st, sc, c.pools, tpp, stack_cap, d_over);
+                hipLaunchKernelGGL(trace, grid_trace, block, lds_bytes, st, sc, c.pools, tpp, stack_cap, d_over);
             }
             HIP_TRY(hipGetLastError());
             lock_enqueued = hi;
@@ -4321,6 +4205,48 @@ int render_overlapped(const rt_scene *scene, const rt_camera *camera, int width,
         }
         *stats = tot;
     }
+    return 0;
+}
+
+// What rt_trace_closest_flags and rt_trace_any_flags share: the mode flags, the reference tree, the origins' padding, the
+// rays' upload, the overflow stacks and the launch of k_trace<MODE>.  `tp` arrives with the entry point's own buffers set;
+// every device buffer lives in `tmp`.
+template <int MODE>
+static int trace_test_rays(const rt_scene *scene, uint32_t flags, int n, const float *origin_xyz, const float *dir_xyz,
+                           const float *tmax, TraceParams tp, DevScope &tmp) {
+    const bool literal = (flags & RT_FLAG_REFERENCE_WALK) != 0;
+    const bool verify = !literal && (flags & RT_FLAG_WATERTIGHT) == 0;
+    if ((literal || verify) && ensure_ref_tree(scene)) return 1;
+    float *d_o, *d_d, *d_tm;
+    unsigned long long *d_vstat;
+    if (tmp.alloc(d_vstat, 4)) return 1;
+    HIP_TRY(hipMemset(d_vstat, 0, 4 * sizeof(unsigned long long)));
+    if (tmp.alloc(d_o, 3 * (size_t)n) || tmp.alloc(d_d, 3 * (size_t)n) || tmp.alloc(d_tm, (size_t)n)) return 1;
+    {
+        float need[3] = {0.f, 0.f, 0.f};  // the 4-wide records must be padded for these origins (ensure_origin_radius)
+        for (int i = 0; i < n; i++)
+            for (int a = 0; a < 3; a++)
+                if (std::isfinite(origin_xyz[3 * (size_t)i + a])) need[a] = std::max(need[a], std::fabs(origin_xyz[3 * (size_t)i + a]));
+        if (int rc = ensure_origin_radius(scene, need)) return rc;
+    }
+    HIP_TRY(hipMemcpy(d_o, origin_xyz, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_d, dir_xyz, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_tm, tmax, sizeof(float) * (size_t)n, hipMemcpyHostToDevice));
+    const int test_grid = std::min(grid_for(n), 2048);
+    const int stack_cap = lds_stack_cap(scene, kLdsStack);
+    int *d_over = nullptr;
+    int over_levels = 0;
+    if (ensure_overflow(d_over, over_levels, std::max(scene->stack_bound, 32) - stack_cap)) return 1;
+    tmp.ptrs.push_back(d_over);
+    tp.total = n;
+    tp.o3 = d_o;
+    tp.d3 = d_d;
+    tp.tmax = d_tm;
+    tp.vstat = d_vstat;
+    DPools none{};
+    hipLaunchKernelGGL(trace_kernel<MODE>(literal, verify, scene->wide), dim3(test_grid), dim3(kBlock),
+                       sizeof(int) * kBlock * (size_t)(stack_cap + 2), nullptr, scene->dev(), none, tp, stack_cap, d_over);
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 
@@ -4801,51 +4727,17 @@ int rt_trace_closest_flags(const rt_scene *scene, uint32_t flags, int n, const f
     if (!scene || n < 0 || (n > 0 && (!origin_xyz || !dir_xyz || !tmax || !hit_tri || !t || !u || !v)))
         return fail("rt_trace_closest: bad argument");
     if (n == 0) return 0;
-    const bool literal = (flags & RT_FLAG_REFERENCE_WALK) != 0;
-    const bool verify = !literal && (flags & RT_FLAG_WATERTIGHT) == 0;
-    if ((literal || verify) && ensure_ref_tree(scene)) return 1;
-    float *d_o, *d_d, *d_tm, *d_t, *d_u, *d_v;
+    float *d_t, *d_u, *d_v;
     int *d_h;
-    unsigned long long *d_vstat;
     DevScope tmp;
-    if (tmp.alloc(d_vstat, 4)) return 1;
-    HIP_TRY(hipMemset(d_vstat, 0, 4 * sizeof(unsigned long long)));
-    if (tmp.alloc(d_o, 3 * (size_t)n) || tmp.alloc(d_d, 3 * (size_t)n) || tmp.alloc(d_tm, (size_t)n) || tmp.alloc(d_t, (size_t)n) ||
-        tmp.alloc(d_u, (size_t)n) || tmp.alloc(d_v, (size_t)n) || tmp.alloc(d_h, (size_t)n))
-        return 1;
-    {
-        float need[3] = {0.f, 0.f, 0.f};  // the 4-wide records must be padded for these origins (ensure_origin_radius)
-        for (int i = 0; i < n; i++)
-            for (int a = 0; a < 3; a++)
-                if (std::isfinite(origin_xyz[3 * (size_t)i + a])) need[a] = std::max(need[a], std::fabs(origin_xyz[3 * (size_t)i + a]));
-        if (int rc = ensure_origin_radius(scene, need)) return rc;
-    }
-    HIP_TRY(hipMemcpy(d_o, origin_xyz, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_d, dir_xyz, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_tm, tmax, sizeof(float) * (size_t)n, hipMemcpyHostToDevice));
-    const int test_grid = std::min(grid_for(n), 2048);
-    const int stack_cap = lds_stack_cap(scene, kLdsStack);
-    int *d_over = nullptr;
-    int over_levels = 0;
-    if (ensure_overflow(d_over, over_levels, std::max(scene->stack_bound, 32) - stack_cap)) return 1;
-    tmp.ptrs.push_back(d_over);
-    {
-        TraceParams tp{};
-        tp.total = n;
-        tp.o3 = d_o;
-        tp.d3 = d_d;
-        tp.tmax = d_tm;
-        tp.order = scene->d_order;
-        tp.out_i = d_h;
-        tp.out_t = d_t;
-        tp.out_u = d_u;
-        tp.out_v = d_v;
-        tp.vstat = d_vstat;
-        DPools none{};
-        RT_LAUNCH_TRACE_REF(MODE_TEST_CLOSEST, literal, verify, scene->wide, dim3(test_grid), sizeof(int) * kBlock * (size_t)(stack_cap + 2), nullptr,
-                        scene->dev(), none, tp, stack_cap, d_over);
-    }
-    HIP_TRY(hipGetLastError());
+    if (tmp.alloc(d_t, (size_t)n) || tmp.alloc(d_u, (size_t)n) || tmp.alloc(d_v, (size_t)n) || tmp.alloc(d_h, (size_t)n)) return 1;
+    TraceParams tp{};
+    tp.order = scene->d_order;
+    tp.out_i = d_h;
+    tp.out_t = d_t;
+    tp.out_u = d_u;
+    tp.out_v = d_v;
+    if (int rc = trace_test_rays<MODE_TEST_CLOSEST>(scene, flags, n, origin_xyz, dir_xyz, tmax, tp, tmp)) return rc;
     HIP_TRY(hipMemcpy(hit_tri, d_h, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(t, d_t, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(u, d_u, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
@@ -4863,54 +4755,19 @@ int rt_trace_any_flags(const rt_scene *scene, uint32_t flags, int n, const float
     if (!scene || n < 0 || (n > 0 && (!origin_xyz || !dir_xyz || !tmax || !excluded_tri || !occluded)))
         return fail("rt_trace_any: bad argument");
     if (n == 0) return 0;
-    const bool literal = (flags & RT_FLAG_REFERENCE_WALK) != 0;
-    const bool verify = !literal && (flags & RT_FLAG_WATERTIGHT) == 0;
-    if ((literal || verify) && ensure_ref_tree(scene)) return 1;
     std::vector<int> excl(n);
     for (int i = 0; i < n; i++) {
         int e = excluded_tri[i];
         excl[i] = (e >= 0 && e < scene->n_tris) ? scene->h_inverse[e] : -1;
     }
-    float *d_o, *d_d, *d_tm;
     int *d_e, *d_occ;
-    unsigned long long *d_vstat;
     DevScope tmp;
-    if (tmp.alloc(d_vstat, 4)) return 1;
-    HIP_TRY(hipMemset(d_vstat, 0, 4 * sizeof(unsigned long long)));
-    if (tmp.alloc(d_o, 3 * (size_t)n) || tmp.alloc(d_d, 3 * (size_t)n) || tmp.alloc(d_tm, (size_t)n) || tmp.alloc(d_e, (size_t)n) ||
-        tmp.alloc(d_occ, (size_t)n))
-        return 1;
-    {
-        float need[3] = {0.f, 0.f, 0.f};  // the 4-wide records must be padded for these origins (ensure_origin_radius)
-        for (int i = 0; i < n; i++)
-            for (int a = 0; a < 3; a++)
-                if (std::isfinite(origin_xyz[3 * (size_t)i + a])) need[a] = std::max(need[a], std::fabs(origin_xyz[3 * (size_t)i + a]));
-        if (int rc = ensure_origin_radius(scene, need)) return rc;
-    }
-    HIP_TRY(hipMemcpy(d_o, origin_xyz, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_d, dir_xyz, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_tm, tmax, sizeof(float) * (size_t)n, hipMemcpyHostToDevice));
+    if (tmp.alloc(d_e, (size_t)n) || tmp.alloc(d_occ, (size_t)n)) return 1;
     HIP_TRY(hipMemcpy(d_e, excl.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
-    const int test_grid = std::min(grid_for(n), 2048);
-    const int stack_cap = lds_stack_cap(scene, kLdsStack);
-    int *d_over = nullptr;
-    int over_levels = 0;
-    if (ensure_overflow(d_over, over_levels, std::max(scene->stack_bound, 32) - stack_cap)) return 1;
-    tmp.ptrs.push_back(d_over);
-    {
-        TraceParams tp{};
-        tp.total = n;
-        tp.o3 = d_o;
-        tp.d3 = d_d;
-        tp.tmax = d_tm;
-        tp.excluded = d_e;
-        tp.out_i = d_occ;
-        tp.vstat = d_vstat;
-        DPools none{};
-        RT_LAUNCH_TRACE_REF(MODE_TEST_ANY, literal, verify, scene->wide, dim3(test_grid), sizeof(int) * kBlock * (size_t)(stack_cap + 2), nullptr,
-                        scene->dev(), none, tp, stack_cap, d_over);
-    }
-    HIP_TRY(hipGetLastError());
+    TraceParams tp{};
+    tp.excluded = d_e;
+    tp.out_i = d_occ;
+    if (int rc = trace_test_rays<MODE_TEST_ANY>(scene, flags, n, origin_xyz, dir_xyz, tmax, tp, tmp)) return rc;
     HIP_TRY(hipMemcpy(occluded, d_occ, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
     return 0;
 }

@@ -153,7 +153,6 @@ PAD_SETTINGS = {
     "shards8": (0, {}, 8),
     "binary_tree": (0, {"RT_BVH_WIDE": "0"}, 1),                              # (read at scene creation)
     "round_pipeline": (0, {"RT_PERSISTENT": "0"}, 1),                         # k_advance for every generation
-    "sorted_shading": (0, {"RT_PERSISTENT": "0", "RT_SORT_SHADE": "1"}, 1),   # k_advance<*, SORT = true>
 }
 
 

@@ -566,7 +566,6 @@ def test_knobs_are_ignored_without_the_gate(api, gpu_full, monkeypatch):
     cam = api.make_camera(aspect=w / h)
     _, st_default = gpu_full.render(cam, w, h, spp)
     monkeypatch.setenv("RT_PERSISTENT", "0")
-    monkeypatch.setenv("RT_MAJORITY", "0")
     _, st_gated = gpu_full.render(cam, w, h, spp)
     assert st_gated["iterations"] > 3 * st_default["iterations"]
     monkeypatch.delenv("RTCUDA_EXPERIMENTAL")
