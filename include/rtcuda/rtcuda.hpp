@@ -352,6 +352,21 @@ inline void rebuild(Scene &scene, const std::vector<Triangle> &triangles) {
     rtcuda_detail::check(rt_scene_rebuild(sh->h, verts.data(), n), "rebuild");
 }
 
+// Ray queries (no reference counterpart): n rays from DEVICE buffers on the scene's device, ordered on `stream` (a hipStream_t;
+// nullptr = default stream), synchronous on return -- rt_query_closest_device / rt_query_any_device, which document the
+// buffers, the flags and the errors.  The scene is realised on the device like prepare() does; a Scene without a Bvh has no
+// device scene and fails with the library's message.
+inline void query_closest(const Scene &scene, int n, const float *d_origin, const float *d_dir, const float *d_tmax, int32_t *d_hit,
+                          float *d_t, float *d_u, float *d_v, void *stream = nullptr, uint32_t flags = 0) {
+    rt_scene *h = scene.bvh.handle ? rtcuda_detail::realise(scene) : nullptr;
+    rtcuda_detail::check(rt_query_closest_device(h, flags, n, d_origin, d_dir, d_tmax, d_hit, d_t, d_u, d_v, stream), "query_closest");
+}
+inline void query_any(const Scene &scene, int n, const float *d_origin, const float *d_dir, const float *d_tmax,
+                      const int32_t *d_excluded, int32_t *d_occluded, void *stream = nullptr, uint32_t flags = 0) {
+    rt_scene *h = scene.bvh.handle ? rtcuda_detail::realise(scene) : nullptr;
+    rtcuda_detail::check(rt_query_any_device(h, flags, n, d_origin, d_dir, d_tmax, d_excluded, d_occluded, stream), "query_any");
+}
+
 // A driver that must keep the reference's exact call (main.cu:173) can still reach several GPUs: RTCUDA_DEVICES="0,1,2,3" in
 // the environment sends the seven-argument render() below through the multi-device path (rt_render_multi).
 inline std::vector<int> devices_from_env() {

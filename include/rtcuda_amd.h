@@ -242,7 +242,40 @@ int rt_post_process_fixed(const int64_t *d_sum_fixed, float *d_rgb_out, int num_
 /* post_process_framebuffer (render.cuh:330-338) on a DEVICE buffer: c = sqrt(c * (1/spp)). */
 int rt_post_process(float *d_rgb, int num_pixels, int num_samples, void *stream);
 
+/* ---- ray queries (no reference counterpart: its Bvh::traverse is reachable only from render()) ----------------------------
+ * "Trace my rays, from my buffers, on my stream."  All pointers are DEVICE buffers on the scene's device (a buffer on another
+ * device or on the host cannot be told apart from a good one: the call faults instead of failing); origins and directions are
+ * n AoS xyz triples.  d_tmax NULL = FLT_MAX for every ray.  Answers are those of rt_trace_closest_flags / rt_trace_any_flags
+ * with the same flags (0, RT_FLAG_REFERENCE_WALK or RT_FLAG_WATERTIGHT -- see the flags; both together, or any other flag, is
+ * an error):
+ *   closest: d_hit_tri[i] = the hit triangle in the caller's ORIGINAL order or -1; t, u, v as Intersection
+ *       (intersection.hpp:4-6), and t = u = v = 0 on a miss, so every output buffer is fully defined after the call.  Any
+ *       of d_t, d_u, d_v may be NULL (not written).
+ *   any: d_occluded[i] in {0, 1}; d_excluded_tri[i] (caller's order) is the one triangle ray i may pass through -- an index
+ *       < 0 or >= n_tris excludes nothing, and so does d_excluded_tri = NULL.
+ * Directions are unit vectors; what is CHECKED, on the device before anything is written, is that every component is finite
+ * and below 2^126 in magnitude (beyond that the reference's slab arithmetic overflows and a visibility decision would not be
+ * the reference's): otherwise the call fails and names the number of offending rays.  A non-finite ORIGIN is legal: the ray
+ * misses.  0 <= n <= 2^30; n = 0 succeeds and touches nothing.
+ * The work is ordered on `stream` (NULL = default stream) and the call is synchronous on that stream when it returns, as
+ * rt_scene_update_device and rt_render_shard are.  The calling thread's current device is left as it was.  The steady path
+ * allocates nothing: the few words of scratch and the overflow stacks belong to the scene and are made by its first query
+ * (queries of ONE scene therefore take turns).  Origins outside the radius the scene's records are padded for widen the
+ * padding once, as a render from outside the bounds does.  Queries only read the scene: queries and renders of one scene may
+ * overlap; rt_scene_update* / rt_scene_rebuild* may not overlap a query, as for renders.
+ * Errors (null scene, a null pointer that may not be null, n out of range, bad flags, bad directions) return non-zero, set
+ * rt_last_error() and write nothing. */
+int rt_query_closest_device(const rt_scene *scene, uint32_t flags, int n, const float *d_origin_xyz, const float *d_dir_xyz,
+                            const float *d_tmax, int32_t *d_hit_tri, float *d_t, float *d_u, float *d_v, void *stream);
+int rt_query_any_device(const rt_scene *scene, uint32_t flags, int n, const float *d_origin_xyz, const float *d_dir_xyz,
+                        const float *d_tmax, const int32_t *d_excluded_tri, int32_t *d_occluded, void *stream);
+/* The rare path of the LAST query on this scene (flags = 0 only; zero otherwise): out[0] = closest hits re-traced through the
+ * reference's own tree, out[1] = accepted hits the reference's box test loses, out[2] = exact ties at the final distance --
+ * per call what rt_stats.reserved[4..6] are per render. */
+int rt_query_last_counters(const rt_scene *scene, int64_t out[3]);
+
 /* ---- stage-level entry points (parity tests call these; HOST pointers, AoS xyz triples) -----
+ * (Host-pointer forms kept for the parity tests; applications use rt_query_*_device.)
  * Closest hit (Bvh::traverse, bvh.cuh:251-303; ch(), render.cuh:297-328): hit_tri = index of
  * the hit triangle in the caller's ORIGINAL order or -1; t,u,v as Intersection
  * (intersection.hpp:4-6), undefined on a miss. */

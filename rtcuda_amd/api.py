@@ -32,7 +32,8 @@ EXPORTS = [
     "rt_scene_create", "rt_scene_destroy", "rt_scene_info", "rt_scene_build_info", "rt_scene_update", "rt_scene_update_device",
     "rt_scene_refit_info", "rt_scene_create_flags", "rt_scene_rebuild", "rt_scene_rebuild_device", "rt_camera_make", "rt_render", "rt_render_multi",
     "rt_render_shard", "rt_render_shard_fixed", "rt_post_process", "rt_post_process_fixed", "rt_trace_closest", "rt_trace_any",
-    "rt_trace_closest_flags", "rt_trace_any_flags", "rt_xorwow_states", "rt_shutdown", "rt_peer_access_log", "rt_last_error", "rt_version", "rt_build_id",
+    "rt_trace_closest_flags", "rt_trace_any_flags", "rt_query_closest_device", "rt_query_any_device", "rt_query_last_counters",
+    "rt_xorwow_states", "rt_shutdown", "rt_peer_access_log", "rt_last_error", "rt_version", "rt_build_id",
 ]
 # the lab (include/rtcuda_amd_tools.h, librtcuda_amd_tools.so): measurement tools, not part of the drop-in C-ABI
 TOOLS_LIB_PATH = os.path.join(_PKG, "librtcuda_amd_tools.so")
@@ -143,6 +144,9 @@ def _bind(L):
     L.rt_trace_any.argtypes = [vp, ci, vp, vp, vp, vp, vp]
     L.rt_trace_closest_flags.argtypes = [vp, ctypes.c_uint32, ci, vp, vp, vp, vp, vp, vp, vp]
     L.rt_trace_any_flags.argtypes = [vp, ctypes.c_uint32, ci, vp, vp, vp, vp, vp]
+    L.rt_query_closest_device.argtypes = [vp, ctypes.c_uint32, ci, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.rt_query_any_device.argtypes = [vp, ctypes.c_uint32, ci, vp, vp, vp, vp, vp, vp]
+    L.rt_query_last_counters.argtypes = [vp, vp]
     L.rt_xorwow_states.argtypes = [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ci, vp, vp]
     L.rt_shutdown.restype = None
     L.rt_peer_access_log.restype = ctypes.c_char_p
@@ -330,6 +334,81 @@ class Scene:
                                            shard_count, flags, ctypes.c_void_p(d_sum_fixed_ptr), ctypes.c_void_p(stream),
                                            ctypes.byref(st)), "rt_render_shard_fixed", self.L)
         return st.as_dict()
+
+    # ---- ray queries on device buffers (rt_query_*_device)
+    def query_closest_device(self, o_ptr: int, d_ptr: int, tmax_ptr: int, n: int, hit_ptr: int, t_ptr: int = 0, u_ptr: int = 0,
+                             v_ptr: int = 0, flags: int = 0, stream: int = 0) -> None:
+        """Closest hit of n rays from DEVICE buffers on the scene's device (e.g. ``tensor.data_ptr()``; origins and
+        directions n x 3 float32, tmax n float32 or 0 = FLT_MAX) into DEVICE buffers: hit triangle (int32, the caller's
+        order or -1) and t, u, v (float32, zero on a miss; 0 = not wanted).  Ordered on ``stream`` (0 = default stream),
+        synchronous on return."""
+        c = ctypes.c_void_p
+        _check(self.L.rt_query_closest_device(self.h, flags, int(n), c(o_ptr or None), c(d_ptr or None), c(tmax_ptr or None),
+                                              c(hit_ptr or None), c(t_ptr or None), c(u_ptr or None), c(v_ptr or None),
+                                              c(stream or None)), "rt_query_closest_device", self.L)
+
+    def query_any_device(self, o_ptr: int, d_ptr: int, tmax_ptr: int, excluded_ptr: int, n: int, occluded_ptr: int,
+                         flags: int = 0, stream: int = 0) -> None:
+        """Occlusion of n rays from DEVICE buffers: occluded (int32, 0 / 1) <- is there an accepted hit within tmax on a
+        triangle other than excluded[i] (int32, the caller's order; 0 = nothing excluded)."""
+        c = ctypes.c_void_p
+        _check(self.L.rt_query_any_device(self.h, flags, int(n), c(o_ptr or None), c(d_ptr or None), c(tmax_ptr or None),
+                                          c(excluded_ptr or None), c(occluded_ptr or None), c(stream or None)),
+               "rt_query_any_device", self.L)
+
+    def query_counters(self) -> dict:
+        """The rare path of the last query on this scene (rt_query_last_counters)."""
+        out = np.zeros(3, np.int64)
+        _check(self.L.rt_query_last_counters(self.h, _p(out)), "rt_query_last_counters", self.L)
+        return {"retraced": int(out[0]), "lost": int(out[1]), "tied": int(out[2])}
+
+    @staticmethod
+    def _query_rays(what, origins, dirs, tmax, excluded=None):
+        """The checks of query_closest / query_any: torch tensors on one GPU (the scene's), float32 (excluded: int32),
+        contiguous, (n, 3) / (n,).  Nothing is converted or copied: a million rays are not silently duplicated."""
+        import torch
+        n, device = None, None
+        for name, x, dtype, cols in (("origins", origins, torch.float32, 3), ("dirs", dirs, torch.float32, 3),
+                                     ("tmax", tmax, torch.float32, 0), ("excluded", excluded, torch.int32, 0)):
+            if x is None and not cols:
+                continue  # (optional)
+            if not isinstance(x, torch.Tensor):
+                raise RtError(f"{what}: {name} must be a torch tensor, it is a {type(x).__name__}")
+            if not x.is_cuda:
+                raise RtError(f"{what}: {name} must be on the scene's GPU, it is on {x.device}")
+            if x.dtype != dtype:
+                raise RtError(f"{what}: {name} must be {dtype}, it is {x.dtype}")
+            if n is None and x.dim() == 2:
+                n = x.shape[0]
+            if tuple(x.shape) != ((n, 3) if cols else (n,)):
+                raise RtError(f"{what}: {name} must have shape {'(n, 3)' if cols else '(n,)'}, it has {tuple(x.shape)}")
+            if not x.is_contiguous():
+                raise RtError(f"{what}: {name} must be contiguous")
+            device = x.device if device is None else device
+            if x.device != device:
+                raise RtError(f"{what}: {name} is on {x.device}, origins are on {device}")
+        return n, device
+
+    def query_closest(self, origins, dirs, tmax=None, flags: int = 0):
+        """Closest hits of torch rays: origins, dirs (n, 3) float32 and tmax (n,) float32 or None (no limit), contiguous, on
+        the scene's device -> (hit_tri int32, t, u, v float32) tensors there, ordered on ``torch.cuda.current_stream()``."""
+        import torch
+        n, device = self._query_rays("query_closest", origins, dirs, tmax)
+        hit = torch.empty(n, dtype=torch.int32, device=device)
+        t, u, v = (torch.empty(n, dtype=torch.float32, device=device) for _ in range(3))
+        self.query_closest_device(origins.data_ptr(), dirs.data_ptr(), 0 if tmax is None else tmax.data_ptr(), n, hit.data_ptr(),
+                                  t.data_ptr(), u.data_ptr(), v.data_ptr(), flags, torch.cuda.current_stream(device).cuda_stream)
+        return hit, t, u, v
+
+    def query_any(self, origins, dirs, tmax=None, excluded=None, flags: int = 0):
+        """Occlusion of torch rays (as query_closest; excluded (n,) int32 or None) -> occluded int32 tensor (0 / 1)."""
+        import torch
+        n, device = self._query_rays("query_any", origins, dirs, tmax, excluded)
+        occ = torch.empty(n, dtype=torch.int32, device=device)
+        self.query_any_device(origins.data_ptr(), dirs.data_ptr(), 0 if tmax is None else tmax.data_ptr(),
+                              0 if excluded is None else excluded.data_ptr(), n, occ.data_ptr(), flags,
+                              torch.cuda.current_stream(device).cuda_stream)
+        return occ
 
     # ---- stage-level entry points (parity tests)
     def trace_closest(self, o3, d3, tmax, flags: int = 0):

@@ -1526,6 +1526,216 @@ __global__ void __launch_bounds__(kBlock, MINW) k_trace(DScene sc, DPools p, Tra
 #endif
 }
 
+// ============================================================================ k_query: ray queries on device buffers
+// rt_query_closest_device / rt_query_any_device: the caller's rays, from the caller's device buffers, through the same
+// shared device functions as k_trace and k_paths (inv_dir, inner_step, tri_intersect, closest_hit_wins, ref_visible,
+// reference_walk, the stack helpers) -- the hit decisions are theirs, only the way from a buffer to them and back is new.
+enum { Q_CLOSEST = 0, Q_ANY = 1 };
+struct QueryWords {           // the scratch of one query call (rt_scene::QueryState::d_words), zeroed before the prepass
+    unsigned radius_bits[3];  // per axis: max |origin| over the finite origin components, as the bits of that float
+    unsigned bad_dirs;        // rays with a direction component that is not finite or reaches 2^126
+    unsigned long long vstat[4];  // V_OWN_FAIL, V_LOST, V_TIE, V_LITERAL of this call (rt_query_last_counters)
+};
+struct QueryParams {
+    int n, n_tris;
+    const float *o3, *d3, *tmax;         // tmax null: FLT_MAX for every ray
+    const int *excluded, *inverse;       // Q_ANY: the caller's index (may be null) and caller order -> leaf order
+    int *out_i;                          // hit triangle in the caller's order / occluded flag
+    float *out_t, *out_u, *out_v;        // Q_CLOSEST, each may be null
+    unsigned long long *vstat;
+};
+
+// One pass over the rays before the walk: what ensure_origin_radius needs to know about the origins, and whether every
+// direction keeps the precondition of the walk (finite, every component below 2^126 in magnitude: 1 / d and the slab
+// products of the reference's box test stay finite).  A non-negative float orders like its bit pattern, so the maximum is
+// an integer atomicMax: one per wave and axis after a wave reduction.
+__global__ void __launch_bounds__(kBlock) k_query_prepass(const float *__restrict__ o3, const float *__restrict__ d3, int n,
+                                                          QueryWords *__restrict__ words) {
+    float mx = 0.f, my = 0.f, mz = 0.f;
+    unsigned bad = 0;
+    const size_t stride = (size_t)gridDim.x * kBlock;
+    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < (size_t)n; i += stride) {
+        const float ox = fabsf(o3[3 * i]), oy = fabsf(o3[3 * i + 1]), oz = fabsf(o3[3 * i + 2]);
+        if (ox <= kFltMax) mx = fmaxf(mx, ox);  // (false for +inf and NaN)
+        if (oy <= kFltMax) my = fmaxf(my, oy);
+        if (oz <= kFltMax) mz = fmaxf(mz, oz);
+        const float dm = fmaxf(fabsf(d3[3 * i]), fmaxf(fabsf(d3[3 * i + 1]), fabsf(d3[3 * i + 2])));
+        const bool nan = d3[3 * i] != d3[3 * i] || d3[3 * i + 1] != d3[3 * i + 1] || d3[3 * i + 2] != d3[3 * i + 2];
+        bad += (nan || !(dm < 0x1p126f)) ? 1u : 0u;
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        mx = fmaxf(mx, __shfl_xor(mx, off));
+        my = fmaxf(my, __shfl_xor(my, off));
+        mz = fmaxf(mz, __shfl_xor(mz, off));
+        bad += __shfl_xor(bad, off);
+    }
+    if (lane_id() == 0) {
+        if (mx > 0.f) atomicMax(&words->radius_bits[0], __float_as_uint(mx));
+        if (my > 0.f) atomicMax(&words->radius_bits[1], __float_as_uint(my));
+        if (mz > 0.f) atomicMax(&words->radius_bits[2], __float_as_uint(mz));
+        if (bad) atomicAdd(&words->bad_dirs, bad);
+    }
+}
+// caller order -> leaf order of the scene's triangles, on the device (rt_query_any_device maps the excluded triangle when a
+// lane takes its ray, not per candidate in the leaf loop)
+__global__ void k_query_inverse(const int *__restrict__ order, int n, int *__restrict__ inverse) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < n) inverse[order[k]] = k;
+}
+
+// The walk: one persistent launch per call, the grid sized from the device and not from n.  A wave takes chunks of 64
+// consecutive rays round-robin (wave id + k x waves of the grid; no shared head counter, for the reason given in k_trace) and
+// hands the rays of its current chunk to idle lanes by ballot + mbcnt: every ray of a chunk is wanted, so the pending rays are
+// the id range [pend_lo, pend_hi) in two scalars where k_trace compacts slots into LDS.  Once at most kQueryRefillAt lanes
+// still traverse, finished lanes write their result and take the next rays.
+// LDS (dynamic): the stack columns, (stack_cap + 1) x kBlock ints (push_if).
+// Registers: no pool, shading or camera state is carried, but the VERIFY finalisation (ref_visible + the literal re-trace)
+// and the 4-wide node step with its seven 16-byte loads in flight want 71 VGPRs -- over the 64 of 8 waves per SIMD, where
+// k_trace's test modes spill 26.  Measured on C2, 2^22 rays (tools/query_time.py, device time of the whole call): budget 8
+// 0.689 / 0.912 / 0.703 ms for camera / bounce / shadow rays, budgets 4 to 7 (one and the same code: 71 VGPRs, 7 waves per SIMD,
+// no spill, no scratch) 0.565 / 0.730 / 0.680 ms.  kQueryRefillAt: 24, 32, 48 and 56 all land within 1 % of each other on the
+// three batches (the spread of one setting's repetitions is 2 %), so k_trace's 40 stays.
+// KIND / WIDE / LITERAL / VERIFY: as k_trace's MODE_TEST_* / WIDE / LITERAL / VERIFY.
+#ifndef RT_QUERY_MIN_WAVES
+#define RT_QUERY_MIN_WAVES 4
+#endif
+#ifndef RT_QUERY_REFILL_AT
+#define RT_QUERY_REFILL_AT 40
+#endif
+constexpr int kQueryMinWaves = RT_QUERY_MIN_WAVES;
+constexpr int kQueryRefillAt = RT_QUERY_REFILL_AT;
+template <int KIND, bool WIDE, bool LITERAL, bool VERIFY>
+__global__ void __launch_bounds__(kBlock, kQueryMinWaves) k_query(DScene sc, QueryParams qp, int stack_cap, int *overflow) {
+    extern __shared__ int s_lds[];
+    int *stack = s_lds + threadIdx.x;
+    int *over = overflow + (blockIdx.x * kBlock + threadIdx.x);
+    const int n = qp.n;
+    const int n_chunks = (int)(((unsigned)n + 63u) >> 6);
+    const int grid_waves = (int)(gridDim.x * (kBlock / 64));
+    int next_chunk = (int)wave_index();
+    int pend_lo = 0, pend_hi = 0;  // wave-uniform: ray ids of the current chunk that no lane has taken yet
+    // per-lane ray state, as in k_trace: `tri` is the best hit so far (closest) or the excluded triangle (any), leaf order;
+    // `hu` doubles as the occluded flag of an any-hit ray
+    int id = -1, cur = kEntryDone, sp = 0, tri = -1;
+    V3 o = mk(0, 0, 0), d = mk(0, 0, 0), inv = mk(0, 0, 0);
+    float tmax = 0.f, hu = 0.f, hv = 0.f;
+
+    while (true) {
+        unsigned long long act = wave_ballot(id >= 0 && cur != kEntryDone);
+        if (__popcll(act) <= kQueryRefillAt) {
+            // ---- finalise finished lanes
+            const bool fin = id >= 0 && cur == kEntryDone;
+            if (KIND == Q_CLOSEST && VERIFY && !LITERAL && fin && tri >= 0) {
+                // k_trace's rule: the closest hit stands if the reference's walk can see its triangle and nothing tied with it
+                // at the final distance (the sign of hv); otherwise (~2 rays in 10^7) the ray is re-traced literally
+                bool bad = (__float_as_uint(hv) >> 31) != 0u;
+                if (bad) {
+                    atomicAdd(&qp.vstat[V_TIE], 1ull);
+                } else {
+                    const Tri tr = load_tri(sc.tris, tri);
+                    bad = !ref_visible(sc, o, d, tr, tri, qp.vstat);
+                }
+                if (bad) {
+                    atomicAdd(&qp.vstat[V_LITERAL], 1ull);
+                    tmax = qp.tmax ? qp.tmax[id] : kFltMax;
+                    tri = -1;
+                    hu = hv = 0.f;
+                    reference_walk<false>(sc, o, d, tmax, tri, hu, hv, stack, over, stack_cap);
+                }
+            }
+            if (fin) {
+                if (KIND == Q_CLOSEST) {
+                    const bool hit = tri >= 0;
+                    qp.out_i[id] = hit ? sc.order[(unsigned)tri] : -1;
+                    if (qp.out_t) qp.out_t[id] = hit ? tmax : 0.f;
+                    if (qp.out_u) qp.out_u[id] = hit ? hu : 0.f;
+                    if (qp.out_v) qp.out_v[id] = hit ? hv : 0.f;
+                } else {
+                    qp.out_i[id] = hu != 0.f ? 1 : 0;
+                }
+                id = -1;
+            }
+            // ---- refill idle lanes (a second chunk when the current one runs out half-way)
+            for (int tries = 0; tries < 2; tries++) {
+                const unsigned long long idle = wave_ballot(id < 0);
+                const int n_idle = __popcll(idle);
+                if (n_idle == 0) break;
+                if (pend_lo == pend_hi) {
+                    if (next_chunk >= n_chunks) break;
+                    pend_lo = next_chunk << 6;
+                    pend_hi = min(pend_lo + 64, n);
+                    next_chunk += grid_waves;
+                }
+                const int avail = pend_hi - pend_lo, r = (int)prefix_popc(idle);
+                if (id < 0 && r < avail) {
+                    id = pend_lo + r;
+                    const size_t at = 3 * (size_t)id;
+                    o = mk(qp.o3[at], qp.o3[at + 1], qp.o3[at + 2]);
+                    d = mk(qp.d3[at], qp.d3[at + 1], qp.d3[at + 2]);
+                    tmax = qp.tmax ? qp.tmax[id] : kFltMax;
+                    tri = -1;
+                    if (KIND == Q_ANY && qp.excluded) {
+                        const int e = qp.excluded[id];
+                        if (e >= 0 && e < qp.n_tris) tri = qp.inverse[e];
+                    }
+                    inv = inv_dir(d);
+                    cur = 0;  // root
+                    sp = 0;
+                    hu = hv = 0.f;
+                }
+                pend_lo += min(avail, n_idle);
+            }
+            act = wave_ballot(id >= 0 && cur != kEntryDone);
+            if (act == 0) {
+                if (pend_lo == pend_hi && next_chunk >= n_chunks) break;  // nothing in flight, nothing pending, no chunks left
+                continue;
+            }
+        }
+        if (LITERAL) {
+            if (cur >= 0) {
+                reference_walk<KIND == Q_ANY>(sc, o, d, tmax, tri, hu, hv, stack, over, stack_cap);
+                cur = kEntryDone;
+            }
+            continue;
+        }
+        // ---- inner phase: step through node records until no lane holds an inner entry
+        while (wave_ballot(cur >= 0) != 0) {
+            if (cur >= 0) inner_step<WIDE>(sc, o, inv, tmax, cur, sp, stack, over, stack_cap);
+        }
+        // ---- leaf phase: every lane that holds a leaf tests its triangles (triangle.cuh:39-58)
+        if (cur != kEntryDone && cur < 0) {
+            const int ref = ~cur, first = ref >> 3, count = ref & 7;
+            bool stop = false;
+            for (int k = first; k < first + count; k++) {
+                const Tri tr = load_tri(sc.tris, k);
+                float t, u, v;
+                if (tri_intersect(tr, o, d, tmax, t, u, v)) {
+                    if (KIND == Q_ANY) {
+                        // bvh.cuh:243: first accepted hit that is not the excluded triangle (VERIFY: and that the reference's
+                        // walk can see at all)
+                        if (k != tri && (!VERIFY || ref_visible(sc, o, d, tr, k, qp.vstat))) {
+                            hu = 1.f;
+                            stop = true;
+                            break;
+                        }
+                    } else {
+                        const bool tie = t == tmax && tri >= 0;
+                        if (closest_hit_wins(sc, t, tmax, k, tri)) {  // bvh.cuh:227-231 (t <= tmax)
+                            tmax = t;
+                            hu = u;
+                            hv = v;
+                            tri = k;
+                        }
+                        // VERIFY: an exact tie is marked in the sign of hv for the finalisation (see k_trace)
+                        if (VERIFY && tie) hv = __uint_as_float(__float_as_uint(hv) | 0x80000000u);
+                    }
+                }
+            }
+            cur = (!stop && sp > 0) ? stack_pop(stack, over, sp, stack_cap) : kEntryDone;
+        }
+    }
+}
+
 // ============================================================================ k_paths
 // The whole asynchronous part of a frame in ONE launch.  A lane owns one path slot for the entire
 // render and keeps its state in registers; the reference's stage kernels become PHASES of the lane:
@@ -2772,6 +2982,19 @@ struct rt_scene {
     int64_t refits = 0;
     double refit_seconds = 0.0;                 // device time of the last refit (HIP events)
     double sah_build = 0.0, sah_now = 0.0;      // surface-area cost of the 4-wide tree at build time / now
+    // rt_query_*_device: what a query call needs besides the caller's buffers, made by the first query and reused -- the
+    // scratch words on the device and their pinned host copy, the overflow part of the traversal stacks (ensure_overflow),
+    // the inverse leaf order on the device (rt_query_any_device; dropped with the leaf order it belongs to: adopt_tree) and
+    // the rare-path counters of the last query.  `mutex`: queries of one scene take turns (they share these).
+    struct QueryState {
+        std::mutex mutex;
+        QueryWords *d_words = nullptr, *h_words = nullptr;
+        int *d_over = nullptr, over_levels = 0;
+        int *d_inverse = nullptr;
+        int cus = 0;
+        int64_t counters[3] = {0, 0, 0};  // re-traced, lost, tied
+    };
+    mutable QueryState query;
     rt_scene() = default;
     rt_scene(const rt_scene &) = delete;
     rt_scene &operator=(const rt_scene &) = delete;
@@ -2779,9 +3002,16 @@ struct rt_scene {
         drop_replicas();
         drop_ref_tree();
         drop_refit();
+        drop_query_inverse();
         for (void *q : {(void *)d_nodes, (void *)d_recs, (void *)d_radius, (void *)d_tris, (void *)d_tri_info, (void *)d_tri_shade,
-                        (void *)d_mats, (void *)d_lights, (void *)d_order, (void *)d_tables})
+                        (void *)d_mats, (void *)d_lights, (void *)d_order, (void *)d_tables, (void *)query.d_words, (void *)query.d_over})
             (void)hipFree(q);
+        if (query.h_words) (void)hipHostFree(query.h_words);
+    }
+    // the inverse leaf order belongs to one tree: the next rt_query_any_device makes it for the scene's
+    void drop_query_inverse() {
+        (void)hipFree(query.d_inverse);
+        query.d_inverse = nullptr;
     }
     // the reference's tree is a function of the triangles: the next render that needs it builds it again from h_tri9
     void drop_ref_tree() {
@@ -3425,6 +3655,7 @@ void adopt_tree(rt_scene *sc, PlocBuild &b) {
     std::swap(sc->d_order, b.d_order);
     sc->h_quads = std::move(b.quads);
     sc->set_order(b.order);
+    sc->drop_query_inverse();
     sc->n_nodes = (int)sc->h_quads.size();
     sc->max_depth = b.max_depth;
     sc->stack_bound = b.stack_bound;
@@ -4250,6 +4481,88 @@ static int trace_test_rays(const rt_scene *scene, uint32_t flags, int n, const f
     return 0;
 }
 
+// rt_query_closest_device / rt_query_any_device.  Every kernel of a query is ordered on `st`; the host waits twice: for the
+// prepass's four words (validation, and the origin radius the 4-wide records must be padded for) and for the walk.
+using QueryKernel = decltype(&k_query<Q_CLOSEST, false, false, false>);
+template <int KIND>
+static QueryKernel query_kernel(bool literal, bool verify, bool wide) {
+    if (literal) return k_query<KIND, false, true, false>;
+    if (verify) return wide ? k_query<KIND, true, false, true> : k_query<KIND, false, false, true>;
+    return wide ? k_query<KIND, true, false, false> : k_query<KIND, false, false, false>;
+}
+template <int KIND>
+static int query_impl(const rt_scene *scene, uint32_t flags, int n, const float *d_o, const float *d_d, const float *d_tmax,
+                      const int32_t *d_excluded, int32_t *d_out_i, float *d_t, float *d_u, float *d_v, hipStream_t st) {
+    const std::string w(KIND == Q_CLOSEST ? "rt_query_closest_device" : "rt_query_any_device");
+    if (!scene) return fail(w + ": null scene");
+    if (n < 0 || n > (1 << 30)) return fail(w + ": n = " + std::to_string(n) + " is outside 0 .. 2^30");
+    if (flags & ~(uint32_t)(RT_FLAG_REFERENCE_WALK | RT_FLAG_WATERTIGHT)) return fail(w + ": flags other than RT_FLAG_REFERENCE_WALK / RT_FLAG_WATERTIGHT");
+    const bool literal = (flags & RT_FLAG_REFERENCE_WALK) != 0;
+    if (literal && (flags & RT_FLAG_WATERTIGHT)) return fail(w + ": RT_FLAG_REFERENCE_WALK and RT_FLAG_WATERTIGHT exclude each other");
+    if (n > 0 && (!d_o || !d_d || !d_out_i))
+        return fail(w + ": null " + (!d_o ? "d_origin_xyz" : !d_d ? "d_dir_xyz" : KIND == Q_CLOSEST ? "d_hit_tri" : "d_occluded"));
+    if (n == 0) return 0;
+    const bool verify = !literal && (flags & RT_FLAG_WATERTIGHT) == 0;
+    rt_scene::QueryState &q = scene->query;
+    std::lock_guard<std::mutex> lock(q.mutex);
+    DeviceGuard dev;
+    if (dev.enter(scene->device)) return 1;
+    if (!q.d_words) {  // first query of this scene
+        HIP_TRY(hipDeviceGetAttribute(&q.cus, hipDeviceAttributeMultiprocessorCount, scene->device));
+        HIP_TRY(hipHostMalloc((void **)&q.h_words, sizeof(QueryWords), hipHostMallocDefault));
+        HIP_TRY(hipMalloc((void **)&q.d_words, sizeof(QueryWords)));
+    }
+    if ((literal || verify) && ensure_ref_tree(scene)) return 1;
+    HIP_TRY(hipMemsetAsync(q.d_words, 0, sizeof(QueryWords), st));
+    hipLaunchKernelGGL(k_query_prepass, dim3(std::min((n + kBlock - 1) / kBlock, 8 * std::max(q.cus, 1))), dim3(kBlock), 0, st, d_o, d_d, n,
+                       q.d_words);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(q.h_words, q.d_words, 4 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (q.h_words->bad_dirs != 0)
+        return fail(w + ": " + std::to_string(q.h_words->bad_dirs) + " of " + std::to_string(n) + " directions are not finite or reach 2^126");
+    {
+        float need[3];
+        memcpy(need, q.h_words->radius_bits, sizeof(need));
+        if (int rc = ensure_origin_radius(scene, need)) return rc;
+    }
+    if (KIND == Q_ANY && d_excluded && !q.d_inverse && scene->n_tris > 0) {
+        HIP_TRY(hipMalloc((void **)&q.d_inverse, sizeof(int) * (size_t)scene->n_tris));
+        hipLaunchKernelGGL(k_query_inverse, dim3((scene->n_tris + 255) / 256), dim3(256), 0, st, scene->d_order, scene->n_tris, q.d_inverse);
+    }
+    const int stack_cap = lds_stack_cap(scene, kLdsStack);
+    if (ensure_overflow(q.d_over, q.over_levels, std::max(scene->stack_bound, 32) - stack_cap)) return 1;
+    QueryParams qp{};
+    qp.n = n;
+    qp.n_tris = scene->n_tris;
+    qp.o3 = d_o;
+    qp.d3 = d_d;
+    qp.tmax = d_tmax;
+    qp.excluded = d_excluded;
+    qp.inverse = q.d_inverse;
+    qp.out_i = d_out_i;
+    qp.out_t = d_t;
+    qp.out_u = d_u;
+    qp.out_v = d_v;
+    qp.vstat = q.d_words->vstat;
+    const QueryKernel kernel = query_kernel<KIND>(literal, verify, scene->wide);
+    const size_t lds = sizeof(int) * kBlock * (size_t)(stack_cap + 1);
+    int per_cu = 0;
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kBlock, lds));
+    // as many workgroups as the device holds at once (never more lanes than the overflow stacks have columns), fewer when
+    // the rays do not fill them
+    const int resident = std::min(std::max(per_cu, 1) * std::max(q.cus, 1), kOverStride / kBlock);
+    const int grid = std::max(1, std::min(resident, (int)(((size_t)n + kBlock - 1) / kBlock)));
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, st, scene->dev(), qp, stack_cap, q.d_over);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(q.h_words->vstat, q.d_words->vstat, sizeof(q.h_words->vstat), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    q.counters[0] = (int64_t)q.h_words->vstat[V_LITERAL];
+    q.counters[1] = (int64_t)q.h_words->vstat[V_LOST];
+    q.counters[2] = (int64_t)q.h_words->vstat[V_TIE];
+    return 0;
+}
+
 }  // namespace
 
 // ============================================================================ C-ABI
@@ -4769,6 +5082,24 @@ int rt_trace_any_flags(const rt_scene *scene, uint32_t flags, int n, const float
     tp.out_i = d_occ;
     if (int rc = trace_test_rays<MODE_TEST_ANY>(scene, flags, n, origin_xyz, dir_xyz, tmax, tp, tmp)) return rc;
     HIP_TRY(hipMemcpy(occluded, d_occ, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int rt_query_closest_device(const rt_scene *scene, uint32_t flags, int n, const float *d_origin_xyz, const float *d_dir_xyz,
+                            const float *d_tmax, int32_t *d_hit_tri, float *d_t, float *d_u, float *d_v, void *stream) {
+    return query_impl<Q_CLOSEST>(scene, flags, n, d_origin_xyz, d_dir_xyz, d_tmax, nullptr, d_hit_tri, d_t, d_u, d_v, (hipStream_t)stream);
+}
+
+int rt_query_any_device(const rt_scene *scene, uint32_t flags, int n, const float *d_origin_xyz, const float *d_dir_xyz,
+                        const float *d_tmax, const int32_t *d_excluded_tri, int32_t *d_occluded, void *stream) {
+    return query_impl<Q_ANY>(scene, flags, n, d_origin_xyz, d_dir_xyz, d_tmax, d_excluded_tri, d_occluded, nullptr, nullptr, nullptr,
+                             (hipStream_t)stream);
+}
+
+int rt_query_last_counters(const rt_scene *scene, int64_t out[3]) {
+    if (!scene || !out) return fail("rt_query_last_counters: null argument");
+    std::lock_guard<std::mutex> lock(scene->query.mutex);
+    for (int k = 0; k < 3; k++) out[k] = scene->query.counters[k];
     return 0;
 }
 
