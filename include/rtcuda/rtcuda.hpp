@@ -367,6 +367,29 @@ inline void query_any(const Scene &scene, int n, const float *d_origin, const fl
     rtcuda_detail::check(rt_query_any_device(h, flags, n, d_origin, d_dir, d_tmax, d_excluded, d_occluded, stream), "query_any");
 }
 
+// Radiance along the caller's camera rays (no reference counterpart: its render() makes its rays from its pinhole Camera):
+// n_rays rays from DEVICE buffers, raw sums ADDED into d_sum_rgb (n_pixels x 3 floats) or, render_rays_fixed, into int64 sums
+// in units of 2^-30 -- rt_render_rays_device / rt_render_rays_fixed_device, which document the frame, the flags and the
+// errors.  d_pixel nullptr: ray c lands on pixel c / rays_per_pixel.  Post-processing is the caller's (rt_post_process*).
+inline rt_stats render_rays(const Scene &scene, int64_t n_rays, const float *d_origin, const float *d_dir, const int32_t *d_pixel,
+                            int rays_per_pixel, int n_pixels, float *d_sum_rgb, int max_bounces = 10, void *stream = nullptr,
+                            uint32_t flags = 0, uint64_t seed = 1) {
+    rt_scene *h = scene.bvh.handle ? rtcuda_detail::realise(scene) : nullptr;
+    rt_stats st{};
+    rtcuda_detail::check(rt_render_rays_device(h, n_rays, d_origin, d_dir, d_pixel, rays_per_pixel, n_pixels, max_bounces, seed, flags,
+                                               d_sum_rgb, stream, &st), "render_rays");
+    return st;
+}
+inline rt_stats render_rays_fixed(const Scene &scene, int64_t n_rays, const float *d_origin, const float *d_dir, const int32_t *d_pixel,
+                                  int rays_per_pixel, int n_pixels, int64_t *d_sum_fixed, int max_bounces = 10, void *stream = nullptr,
+                                  uint32_t flags = 0, uint64_t seed = 1) {
+    rt_scene *h = scene.bvh.handle ? rtcuda_detail::realise(scene) : nullptr;
+    rt_stats st{};
+    rtcuda_detail::check(rt_render_rays_fixed_device(h, n_rays, d_origin, d_dir, d_pixel, rays_per_pixel, n_pixels, max_bounces, seed,
+                                                     flags, d_sum_fixed, stream, &st), "render_rays_fixed");
+    return st;
+}
+
 // A driver that must keep the reference's exact call (main.cu:173) can still reach several GPUs: RTCUDA_DEVICES="0,1,2,3" in
 // the environment sends the seven-argument render() below through the multi-device path (rt_render_multi).
 inline std::vector<int> devices_from_env() {

@@ -242,6 +242,41 @@ int rt_post_process_fixed(const int64_t *d_sum_fixed, float *d_rgb_out, int num_
 /* post_process_framebuffer (render.cuh:330-338) on a DEVICE buffer: c = sqrt(c * (1/spp)). */
 int rt_post_process(float *d_rgb, int num_pixels, int num_samples, void *stream);
 
+/* ---- render along the caller's camera rays (the reference's render() with camera.get_ray() replaced by a table) ----------
+ * "Radiance along my rays, from my buffers, on my stream": orthographic, fisheye, lat-long, stereo or thin-lens views, probe
+ * and light-map bakes, a pixel filter of one's own.  The estimator never reads the camera after gen() has written (origin,
+ * direction, pixel), so the definition is small and exact.  A frame of n_rays camera rays; camera ray c (0 <= c < n_rays)
+ *   - is served by path slot c % W, in increasing c per slot, on that slot's XORWOW stream -- exactly as rt_render_shard's;
+ *   - starts with the two jitter draws of gen() (x, then y: render.cuh:250-275) made and thrown away.  They cost nothing
+ *     and keep every slot's stream where the reference's is, which is what lets the CPU oracle pin this path bit for bit:
+ *     a table filled with a pinhole camera's own rays gives rt_render_shard's sums;
+ *   - has origin d_origin_xyz[3c ..], direction d_dir_xyz[3c ..] (AoS triples, as the queries take them), tmax = FLT_MAX;
+ *   - deposits into pixel d_pixel[c] if d_pixel is given, else into pixel c / rays_per_pixel (render.cuh:257);
+ *   - everything after gen() -- init(), mat(), next-event estimation, Russian roulette, the lockstep final generation, the
+ *     stop rule, rt_stats -- is unchanged.
+ * d_sum_rgb: n_pixels x 3 floats, ADDED to (zero it first); the fixed variant: n_pixels x 3 int64 in units of 2^-30, as
+ * rt_render_shard_fixed.  Post-processing stays with the caller (rt_post_process / rt_post_process_fixed take the divisor).
+ * All pointers are DEVICE buffers on the scene's device.  The work is ordered on `stream` (NULL = default stream) and the
+ * call is synchronous on that stream when it returns; the calling thread's current device is left as it was; the steady path
+ * allocates nothing beyond what a render context owns.  Rendering only reads the scene: may overlap queries and renders of
+ * the same scene, not rt_scene_update* / rt_scene_rebuild*.
+ * flags: 0, RT_FLAG_WATERTIGHT, RT_FLAG_TIME_KERNELS.  Out of scope (an error that names the flag): RT_FLAG_REFERENCE_WALK and
+ * RT_FLAG_RNG_PER_SAMPLE -- each would be further builds of the persistent kernel.  No shard parameters either: one device,
+ * all W slots.
+ * CHECKED ON THE DEVICE BEFORE ANYTHING IS WRITTEN: every direction component finite and below 2^126 in magnitude, every
+ * d_pixel[c] in [0, n_pixels) -- the error names the number of offending rays.  Origins outside the radius the scene's
+ * records are padded for widen the padding once, as for the queries; a non-finite ORIGIN is legal: that ray misses.
+ * Host-side: non-null scene / origins / directions / sum buffer, 1 <= n_rays (below the int32 camera-ray range of
+ * rt_render_shard), 1 <= n_pixels <= 715827882, 0 <= max_bounces <= 2^24, and with d_pixel NULL rays_per_pixel >= 1 and
+ * (n_rays - 1) / rays_per_pixel < n_pixels.  Every error returns non-zero, sets rt_last_error() and writes nothing. */
+int rt_render_rays_device(const rt_scene *scene, int64_t n_rays, const float *d_origin_xyz, const float *d_dir_xyz,
+                          const int32_t *d_pixel /* may be NULL */, int rays_per_pixel /* used when d_pixel == NULL */,
+                          int n_pixels, int max_bounces, uint64_t seed, uint32_t flags, float *d_sum_rgb, void *stream,
+                          rt_stats *stats);
+int rt_render_rays_fixed_device(const rt_scene *scene, int64_t n_rays, const float *d_origin_xyz, const float *d_dir_xyz,
+                                const int32_t *d_pixel /* may be NULL */, int rays_per_pixel, int n_pixels, int max_bounces,
+                                uint64_t seed, uint32_t flags, int64_t *d_sum_fixed, void *stream, rt_stats *stats);
+
 /* ---- ray queries (no reference counterpart: its Bvh::traverse is reachable only from render()) ----------------------------
  * "Trace my rays, from my buffers, on my stream."  All pointers are DEVICE buffers on the scene's device (a buffer on another
  * device or on the host cannot be told apart from a good one: the call faults instead of failing); origins and directions are

@@ -31,7 +31,7 @@ FLAG_WATERTIGHT = 16     # the triangle-list definition (no hit lost to a box te
 EXPORTS = [
     "rt_scene_create", "rt_scene_destroy", "rt_scene_info", "rt_scene_build_info", "rt_scene_update", "rt_scene_update_device",
     "rt_scene_refit_info", "rt_scene_create_flags", "rt_scene_rebuild", "rt_scene_rebuild_device", "rt_camera_make", "rt_render", "rt_render_multi",
-    "rt_render_shard", "rt_render_shard_fixed", "rt_post_process", "rt_post_process_fixed", "rt_trace_closest", "rt_trace_any",
+    "rt_render_shard", "rt_render_shard_fixed", "rt_render_rays_device", "rt_render_rays_fixed_device", "rt_post_process", "rt_post_process_fixed", "rt_trace_closest", "rt_trace_any",
     "rt_trace_closest_flags", "rt_trace_any_flags", "rt_query_closest_device", "rt_query_any_device", "rt_query_last_counters",
     "rt_xorwow_states", "rt_shutdown", "rt_peer_access_log", "rt_last_error", "rt_version", "rt_build_id",
 ]
@@ -140,6 +140,9 @@ def _bind(L):
     L.rt_post_process.argtypes = [vp, ci, ci, vp]
     L.rt_render_shard_fixed.argtypes = L.rt_render_shard.argtypes
     L.rt_post_process_fixed.argtypes = [vp, vp, ci, ci, vp]
+    L.rt_render_rays_device.argtypes = [vp, ctypes.c_int64, vp, vp, vp, ci, ci, ci, ctypes.c_uint64, ctypes.c_uint32, vp, vp,
+                                        ctypes.POINTER(RtStats)]
+    L.rt_render_rays_fixed_device.argtypes = L.rt_render_rays_device.argtypes
     L.rt_trace_closest.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp]
     L.rt_trace_any.argtypes = [vp, ci, vp, vp, vp, vp, vp]
     L.rt_trace_closest_flags.argtypes = [vp, ctypes.c_uint32, ci, vp, vp, vp, vp, vp, vp, vp]
@@ -335,6 +338,47 @@ class Scene:
                                            ctypes.byref(st)), "rt_render_shard_fixed", self.L)
         return st.as_dict()
 
+    # ---- radiance along the caller's camera rays (rt_render_rays_device / rt_render_rays_fixed_device)
+    def render_rays_device(self, o_ptr: int, d_ptr: int, pixel_ptr: int, n_rays: int, n_pixels: int, d_sum_ptr: int,
+                           rays_per_pixel: int = 1, max_bounces: int = 10, seed: int = 1, flags: int = 0, fixed: bool = False,
+                           stream: int = 0) -> dict:
+        """A frame of n_rays camera rays from DEVICE buffers on the scene's device (origins and directions n_rays x 3 float32;
+        pixel n_rays int32, or 0: ray c lands on pixel c // rays_per_pixel).  Raw sums are ADDED into the DEVICE buffer at
+        ``d_sum_ptr``: n_pixels x 3 float32, or with ``fixed`` int64 in units of 2^-30.  Ordered on ``stream`` (0 = default
+        stream), synchronous on return."""
+        c = ctypes.c_void_p
+        name = "rt_render_rays_fixed_device" if fixed else "rt_render_rays_device"
+        st = RtStats()
+        _check(getattr(self.L, name)(self.h, int(n_rays), c(o_ptr or None), c(d_ptr or None), c(pixel_ptr or None), int(rays_per_pixel),
+                                     int(n_pixels), int(max_bounces), seed, flags, c(d_sum_ptr or None), c(stream or None),
+                                     ctypes.byref(st)), name, self.L)
+        return st.as_dict()
+
+    def render_rays(self, origins, dirs, n_pixels: int, pixel=None, rays_per_pixel: int = 1, max_bounces: int = 10, seed: int = 1,
+                    flags: int = 0, fixed: bool = False, out=None):
+        """Radiance along torch rays: origins, dirs (n, 3) float32 and pixel (n,) int32 or None (ray c lands on pixel
+        c // rays_per_pixel), contiguous, on the scene's device -> (sums, stats): an (n_pixels, 3) tensor of raw sums there --
+        float32, or with ``fixed`` int64 in units of 2^-30 -- ordered on ``torch.cuda.current_stream()``.  ``out``: such a
+        tensor to ADD into instead of a new zeroed one."""
+        import torch
+        n, device = self._query_rays("render_rays", origins, dirs, None)
+        if pixel is not None:
+            self._query_rays("render_rays", origins, dirs, None, pixel, "pixel")
+        dtype = torch.int64 if fixed else torch.float32
+        if out is None:
+            if not isinstance(n_pixels, int) or n_pixels < 1:
+                raise RtError(f"render_rays: n_pixels must be a positive int, it is {n_pixels!r}")
+            out = torch.zeros((n_pixels, 3), dtype=dtype, device=device)
+        else:
+            if not isinstance(out, torch.Tensor) or not out.is_cuda or out.device != device:
+                raise RtError("render_rays: out must be a torch tensor on the rays' GPU")
+            if out.dtype != dtype or tuple(out.shape) != (n_pixels, 3) or not out.is_contiguous():
+                raise RtError(f"render_rays: out must be a contiguous ({n_pixels}, 3) {dtype} tensor, it is {tuple(out.shape)} {out.dtype}")
+        st = self.render_rays_device(origins.data_ptr(), dirs.data_ptr(), 0 if pixel is None else pixel.data_ptr(), n, n_pixels,
+                                     out.data_ptr(), rays_per_pixel, max_bounces, seed, flags, fixed,
+                                     torch.cuda.current_stream(device).cuda_stream)
+        return out, st
+
     # ---- ray queries on device buffers (rt_query_*_device)
     def query_closest_device(self, o_ptr: int, d_ptr: int, tmax_ptr: int, n: int, hit_ptr: int, t_ptr: int = 0, u_ptr: int = 0,
                              v_ptr: int = 0, flags: int = 0, stream: int = 0) -> None:
@@ -363,13 +407,13 @@ class Scene:
         return {"retraced": int(out[0]), "lost": int(out[1]), "tied": int(out[2])}
 
     @staticmethod
-    def _query_rays(what, origins, dirs, tmax, excluded=None):
+    def _query_rays(what, origins, dirs, tmax, excluded=None, excluded_name="excluded"):
         """The checks of query_closest / query_any: torch tensors on one GPU (the scene's), float32 (excluded: int32),
         contiguous, (n, 3) / (n,).  Nothing is converted or copied: a million rays are not silently duplicated."""
         import torch
         n, device = None, None
         for name, x, dtype, cols in (("origins", origins, torch.float32, 3), ("dirs", dirs, torch.float32, 3),
-                                     ("tmax", tmax, torch.float32, 0), ("excluded", excluded, torch.int32, 0)):
+                                     ("tmax", tmax, torch.float32, 0), (excluded_name, excluded, torch.int32, 0)):
             if x is None and not cols:
                 continue  # (optional)
             if not isinstance(x, torch.Tensor):

@@ -53,6 +53,7 @@
 #include <memory>
 #include <mutex>
 #include <thread>
+#include <type_traits>
 #include <string>
 #include <vector>
 
@@ -435,6 +436,19 @@ struct AdvanceOut {
     int s_target;
 };
 
+// The camera rays of a ray-table frame (rt_render_rays_device / rt_render_rays_fixed_device): row c is camera ray c.
+struct RayTable {
+    const float *o3, *d3;  // origins and directions, AoS triples
+    const int *pixel;      // the pixel a ray deposits into; null: c / AdvanceParams::spp
+};
+#ifndef RT_RAYS_NONTEMPORAL
+#define RT_RAYS_NONTEMPORAL 1
+#endif
+template <class T>
+__device__ __forceinline__ T table_load(const T *q) {
+    return RT_RAYS_NONTEMPORAL ? __builtin_nontemporal_load(q) : *q;
+}
+
 // gen() (render.cuh:250-275) for one slot.  Camera ray id = generation * W + slot (see file header).  Leaves
 // st.bounces = kDone (no camera ray left) / kParked (the final generation runs in lockstep) or a new path.
 // `pxy` (optional): the slot's previous pixel as (x | y << 16), or -1.  A slot's pixel index grows by W / spp per
@@ -443,8 +457,10 @@ struct AdvanceOut {
 // from LDS (and so a divergent branch with its merges, as far as the compiler can tell) otherwise.
 // `cid_given` >= 0 (per-sample streams on the persistent kernel only): the camera ray is not the slot's next one but the one
 // the wave drew from the frame's counter -- with a stream of its own per camera ray, any lane can take any camera ray.
-template <bool NEVER_LOCKSTEP = false>
-__device__ __forceinline__ void gen_core(const Camera &cam, const AdvanceParams &ap, int slot_global, SlotState &st,
+// SRC: where camera ray `cid` comes from -- Camera: gen()'s pinhole; RayTable: the caller's table (rt_render_rays_*).  A
+// property of the kernel build (a type, so a compile-time choice): the camera builds carry nothing of the table.
+template <bool NEVER_LOCKSTEP = false, class SRC>
+__device__ __forceinline__ void gen_core(const SRC &cam, const AdvanceParams &ap, int slot_global, SlotState &st,
                                          AdvanceOut &out, int *pxy = nullptr, long long cid_given = -1) {
     const bool lockstep = NEVER_LOCKSTEP ? false : (ap.lockstep != 0);
     long long cid = cid_given >= 0 ? cid_given : (long long)st.gen * kW + slot_global;
@@ -457,6 +473,24 @@ __device__ __forceinline__ void gen_core(const Camera &cam, const AdvanceParams 
         return;
     }
     st.gen = st.gen + 1;
+    if constexpr (std::is_same<SRC, RayTable>::value) {
+        // Ray-table frames: gen()'s two jitter draws are made and dropped (the slot's stream stays where the reference's
+        // is), the ray and its pixel are row `cid` of the table.  No pixel coordinates, no stepping (`pxy` is left alone).
+        // The lanes of a wave serve consecutive slots, so their rows are consecutive: 768 contiguous bytes per array and
+        // wave, read once per frame -- streamed past the caches the BVH lives in (RT_RAYS_NONTEMPORAL).
+        const unsigned c = (unsigned)cid;  // (below 2^31: the host checks the frame)
+        rng_next(st.rs);  // x first, then y (Appendix A.7)
+        rng_next(st.rs);
+        const float *o3 = cam.o3 + 3 * (size_t)c, *d3 = cam.d3 + 3 * (size_t)c;
+        out.ray_o = mk(table_load(o3), table_load(o3 + 1), table_load(o3 + 2));
+        out.ray_d = mk(table_load(d3), table_load(d3 + 1), table_load(d3 + 2));
+        st.pixel = cam.pixel ? table_load(cam.pixel + c) : (int)(c / (unsigned)ap.spp);  // (render.cuh:254-256)
+        out.new_ray = true;
+        st.bounces = 0;
+        st.beta = mk(1.f, 1.f, 1.f);
+        out.did_gen = true;
+        return;
+    } else {
     // pixel = camera_ray_id / spp (render.cuh:254-256).  cid = gen * W + slot, so when spp divides W the quotient
     // splits exactly into two 32-bit terms; the general case keeps the 64-bit division.
     int px, py;
@@ -487,11 +521,12 @@ __device__ __forceinline__ void gen_core(const Camera &cam, const AdvanceParams 
     st.bounces = 0;
     st.beta = mk(1.f, 1.f, 1.f);
     out.did_gen = true;
+    }
 }
 
 // `acc` (USE_ACC, k_paths only): the lane's sample accumulator; otherwise contributions go straight into the framebuffer.
-template <bool DEFER_GEN, bool NEVER_LOCKSTEP = false, bool USE_ACC = false>
-__device__ __forceinline__ void advance_core(const DScene &sc, const float *tab, const Camera &cam,
+template <bool DEFER_GEN, bool NEVER_LOCKSTEP = false, bool USE_ACC = false, class SRC>
+__device__ __forceinline__ void advance_core(const DScene &sc, const float *tab, const SRC &cam,
                                              const AdvanceParams &ap, int slot_global, SlotState &st, AdvanceOut &out,
                                              float *__restrict__ fb, float *acc = nullptr) {
     const bool lockstep = NEVER_LOCKSTEP ? false : (ap.lockstep != 0);
@@ -624,135 +659,7 @@ __device__ __forceinline__ void advance_core(const DScene &sc, const float *tab,
     RT_MARK("adv.mat.end");
 }
 
-// k_advance: one slot per thread, state in the pools.
-// Every per-slot input is indexed by the slot id, so all of a lane's loads are issued together
-// (one memory round trip); the small shared tables are staged in LDS with one more independent
-// round trip; the hit record written by k_trace<MODE_POOL> already carries the shading point,
-// the flipped unit normal and the material / light ids, so no triangle is gathered here.  The
-// kernel has no atomics on shared words and one barrier (the table staging): the shadow ray goes
-// to the slot's own record, event counts go to the wave's own counter row.
-// Thread t serves slot t of its block, whatever the material (the reference shades in compacted-queue order too:
-// render.cuh:139-145).  Sorting the block's slots by material, so that a wave runs one branch of Material::sample_f, was
-// measured on C2's whole frame through the round pipeline (RT_PERSISTENT=0): k_advance took 87 ms sorted against 70 ms in
-// slot order (profiles/r04_experiments.md) -- the kernel streams 36 arrays of slot state and is bound by that traffic; the
-// sort costs a dependent load phase and two barriers in front of it, while the divergence it removes was not what the
-// kernel waited for.
-template <bool LDS_TABLES>
-__global__ void __launch_bounds__(kBlock)
-k_advance(DScene sc, DPools p, Camera cam, AdvanceParams ap, float *__restrict__ fb, DCounters *__restrict__ ctr,
-          DWaveRow *__restrict__ rows, unsigned int *__restrict__ lock_shades) {
-    // Lockstep rounds (final generation): the reference's host loop ends at the first iteration in which nothing shades
-    // (render.cuh:436).  The rounds are all enqueued at once; lock_shades[j] counts the mat() events of round j, and a round
-    // finds out on the device whether the render ended before it: round j >= 2 does nothing if round j - 1 shaded nothing
-    // (round 0 only generates; once a round is skipped it counts nothing, so every later one is skipped too).  No host poll.
-    if (ap.lockstep >= 3 && lock_shades[ap.lockstep - 2] == 0u) return;
-    __shared__ float s_tab[LDS_TABLES ? kTabDwordsMax : 1];
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool in_range = i < ap.n;
-    // ---- issue all per-slot loads up front
-    SlotState st;
-    st.bounces = kDone;
-    st.hit_info = -1;
-    st.pixel = 0;
-    st.gen = 0;
-    st.rs = Rng{0, 0, 0, 0, 0, 0};
-    st.beta = st.wo = st.isect_p = st.isect_n = mk(0, 0, 0);
-    if (in_range) {
-        st.bounces = p.bounces(i);
-        st.hit_info = p.hit_info(i);
-        st.pixel = p.pixel(i);
-        st.gen = p.gen(i);
-        st.rs = Rng{p.rd(i), p.r0(i), p.r1(i), p.r2(i), p.r3(i), p.r4(i)};
-        st.beta = mk(p.br(i), p.bg(i), p.bb(i));
-        st.wo = mk(p.dx(i), p.dy(i), p.dz(i));
-        st.isect_p = mk(p.hpx(i), p.hpy(i), p.hpz(i));
-        st.isect_n = mk(p.hnx(i), p.hny(i), p.hnz(i));
-    }
-    const float *tab = sc.tables;
-    if (LDS_TABLES) {
-        for (int k = threadIdx.x; k < sc.tab_dwords; k += kBlock) s_tab[k] = sc.tables[k];
-        __syncthreads();
-        tab = s_tab;
-    }
-    // Final generation: the reference stops the whole render at the first iteration in which no slot
-    // shades (render.cuh:436), which can cut off slots that Russian roulette would have revived
-    // later.  That is a global condition, so the last generation runs in lockstep: slots that finish
-    // generation last_gen - 1 park, and once all are parked the rounds run one init() per slot each (all enqueued at once:
-    // see the top of this kernel for how a round knows that the render ended before it).
-    if (ap.lockstep && st.bounces == kParked) {
-        st.bounces = ap.max_bounces;  // routes the slot to gen() below
-        st.hit_info = -1;
-    }
-    const bool alive = st.bounces != kDone && st.bounces != kParked;
-    AdvanceOut out;
-    out.did_gen = out.did_shade = out.has_shadow = out.did_emit = out.new_ray = false;
-    out.rr_draws = 0;
-    if (alive) {
-        const int gen_before = st.gen;
-        advance_core<false>(sc, tab, cam, ap, ap.slot_lo + i, st, out, fb);
-        if (out.new_ray) {
-            p.ox(i) = out.ray_o.x;
-            p.oy(i) = out.ray_o.y;
-            p.oz(i) = out.ray_o.z;
-            p.dx(i) = out.ray_d.x;
-            p.dy(i) = out.ray_d.y;
-            p.dz(i) = out.ray_d.z;
-        }
-        if (st.gen != gen_before) {
-            p.gen(i) = st.gen;
-            p.pixel(i) = st.pixel;
-        }
-        if (out.has_shadow) {
-            p.sox(i) = out.s_o.x;
-            p.soy(i) = out.s_o.y;
-            p.soz(i) = out.s_o.z;
-            p.sdx(i) = out.s_d.x;
-            p.sdy(i) = out.s_d.y;
-            p.sdz(i) = out.s_d.z;
-            p.slr(i) = out.s_L.x;
-            p.slg(i) = out.s_L.y;
-            p.slb(i) = out.s_L.z;
-            p.starget(i) = out.s_target;
-            p.stmax(i) = out.s_tmax;
-        }
-        p.br(i) = st.beta.x;
-        p.bg(i) = st.beta.y;
-        p.bb(i) = st.beta.z;
-        p.bounces(i) = st.bounces;
-        p.rd(i) = st.rs.d;
-        p.r0(i) = st.rs.v0;
-        p.r1(i) = st.rs.v1;
-        p.r2(i) = st.rs.v2;
-        p.r3(i) = st.rs.v3;
-        p.r4(i) = st.rs.v4;
-    }
-    if (in_range && !out.has_shadow) p.stmax(i) = -1.f;  // no shadow ray from this slot this round
-
-    // ---- event counters: this wave's own row
-    unsigned long long traced = wave_ballot(out.did_gen || out.did_shade);
-    int rr_tot = out.rr_draws;
-    if (wave_ballot(out.rr_draws != 0)) {
-        for (int off = 32; off > 0; off >>= 1) rr_tot += __shfl_xor(rr_tot, off);
-    } else {
-        rr_tot = 0;
-    }
-    unsigned long long v[C_COUNT] = {(unsigned long long)wave_count((out.did_gen)),
-                                     (unsigned long long)wave_count((out.did_shade)),
-                                     (unsigned long long)__popcll(traced),
-                                     (unsigned long long)wave_count((out.has_shadow)),
-                                     (unsigned long long)wave_count((out.did_emit)),
-                                     0ull,
-                                     (unsigned long long)rr_tot,
-                                     0ull};
-    row_add(rows, v);
-    // liveness is monotone (a finished slot never restarts), so the host only needs it for the
-    // round that closes a batch: one plain store per live wave in 1 round out of 8
-    if ((ap.round & ap.batch_mask) == ap.batch_mask && traced != 0 && lane_id() == 0) ctr->last_live_round = ap.round;
-    if (ap.lockstep) {
-        unsigned long long sm = wave_ballot(out.did_shade);
-        if (sm != 0 && lane_id() == 0) atomicAdd(&lock_shades[ap.lockstep - 1], (unsigned)__popcll(sm));
-    }
-}
+// k_advance (init() + mat() + gen() for all slots of a round) is defined with k_paths in rt_frame_kernels.inc.
 
 // ============================================================================ traversal
 // One wave-wide traversal engine serves the four trace entry points (closest-hit over the path
@@ -1534,6 +1441,8 @@ enum { Q_CLOSEST = 0, Q_ANY = 1 };
 struct QueryWords {           // the scratch of one query call (rt_scene::QueryState::d_words), zeroed before the prepass
     unsigned radius_bits[3];  // per axis: max |origin| over the finite origin components, as the bits of that float
     unsigned bad_dirs;        // rays with a direction component that is not finite or reaches 2^126
+    unsigned bad_pixels;      // rt_render_rays_*: rays whose pixel index is outside the sum buffer (k_pixel_prepass)
+    unsigned pad;
     unsigned long long vstat[4];  // V_OWN_FAIL, V_LOST, V_TIE, V_LITERAL of this call (rt_query_last_counters)
 };
 struct QueryParams {
@@ -1575,6 +1484,15 @@ __global__ void __launch_bounds__(kBlock) k_query_prepass(const float *__restric
         if (mz > 0.f) atomicMax(&words->radius_bits[2], __float_as_uint(mz));
         if (bad) atomicAdd(&words->bad_dirs, bad);
     }
+}
+// rt_render_rays_*: every pixel index of the table inside the sum buffer?  The same pass for the d_pixel array.
+__global__ void __launch_bounds__(kBlock) k_pixel_prepass(const int *__restrict__ pixel, int n, int n_pixels,
+                                                          QueryWords *__restrict__ words) {
+    unsigned bad = 0;
+    const size_t stride = (size_t)gridDim.x * kBlock;
+    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < (size_t)n; i += stride) bad += (unsigned)pixel[i] >= (unsigned)n_pixels ? 1u : 0u;
+    for (int off = 32; off > 0; off >>= 1) bad += __shfl_xor(bad, off);
+    if (lane_id() == 0 && bad) atomicAdd(&words->bad_pixels, bad);
 }
 // caller order -> leaf order of the scene's triangles, on the device (rt_query_any_device maps the excluded triangle when a
 // lane takes its ray, not per candidate in the leaf loop)
@@ -1799,670 +1717,24 @@ constexpr bool kSpeculate = RT_SPECULATE != 0;  // k_paths: postpone a leaf reac
 // ref_visible): a shadow ray's accepted hit counts only if the reference's walk can see its triangle (triangle block); a
 // path ray's closest hit is checked once, at the top of the ADV block that shades it -- visible, and no exact tie at the
 // final distance -- and the ~2 rays in 10^7 that fail are re-traced there by reference_walk.
-template <bool LDS_TABLES, bool WIDE, int MIN_WAVES, bool DRAW_CIDS = false, bool LITERAL = false, bool VERIFY = false>
-__global__ void __launch_bounds__(kBlock, MIN_WAVES)
-k_paths(DScene sc, DPools p, Camera cam_arg, AdvanceParams ap_arg, float *__restrict__ fb, DWaveRow *__restrict__ rows,
-        int stack_cap, int *overflow, int adv_batch, int debug_no_deposit, unsigned long long *prof, int top_n,
-        int prio_period, int rot_wave, int rot_set, int gen_batch, int tri_follow, unsigned int *__restrict__ next_cid,
-        unsigned long long *__restrict__ vstat) {
-    // The GEN block exists where the chip is short of issue slots (4 waves per SIMD): there it takes a third of the
-    // lanes out of the long ADV block (+3 %, and the ADV block no longer spills).  On small shards (2 waves per
-    // SIMD) a slot-round is a latency chain and one more block in it costs 5 %: gen() stays inside ADV there.
-    constexpr bool SPLIT_GEN = MIN_WAVES != 2;
-    // Code placement: where the hot blocks fall within 64-byte instruction-cache lines is worth 0.7 % of the frame.  With
-    // the body 8 bytes earlier than these two s_nop put it, C2's k_paths took 108.7 ms against 107.9 ms (same instructions
-    // otherwise).  Time the frame (tools/ab_bench.py) after any edit that moves the code of this kernel.
-    asm volatile("s_nop 0\n\ts_nop 0");
-    extern __shared__ int s_lds[];
-    int *stack = s_lds + threadIdx.x;
-    float *park = (float *)(s_lds + (stack_cap + 1) * kBlock) + threadIdx.x;  // element k at park[k * kBlock]
-    int *over = overflow + (blockIdx.x * kBlock + threadIdx.x) % kOverStride;
-    int *cold = s_lds + (stack_cap + 10) * kBlock + threadIdx.x;  // element k at cold[k * kBlock]
-    float *acc = (float *)(s_lds + (stack_cap + 23) * kBlock) + threadIdx.x;  // sample accumulator (acc_add / acc_flush)
-    float *s_tab = (float *)(s_lds + (stack_cap + 26) * kBlock);
-    const float *tab = sc.tables;
-    // small shards (MIN_WAVES == 2: at most 2 workgroups per CU, LDS to spare, latency-bound): the top of
-    // the BVH is staged in LDS, so the first levels of every traversal do not leave the CU
-    const float4 *s_top = (const float4 *)(s_tab + (LDS_TABLES ? ((sc.tab_dwords + 3) & ~3) : 0));  // (tables: what the scene needs)
-    if (MIN_WAVES != 2) top_n = 0;
-    for (int k = threadIdx.x; k < top_n * 4; k += kBlock) ((float4 *)s_top)[k] = sc.nodes[k];
-    if (LDS_TABLES) {
-        for (int k = threadIdx.x; k < sc.tab_dwords; k += kBlock) s_tab[k] = sc.tables[k];
-        tab = s_tab;
-    }
-    // The camera and the frame parameters are only needed inside the GEN / ADV blocks: kept as kernel arguments
-    // they occupy ~30 SGPRs for the whole loop and push other scalars out into VGPR lanes (v_readlane /
-    // v_writelane are VALU work).  Staged in LDS they are read where they are used.
-    struct Uniforms {
-        Camera cam;
-        AdvanceParams ap;
-    };
-    static_assert(sizeof(Uniforms) % 4 == 0, "dword copy");
-    Uniforms *s_uni = (Uniforms *)(s_top + 4 * (size_t)top_n);
-    {
-        Uniforms u;
-        u.cam = cam_arg;
-        u.ap = ap_arg;
-        const int *srcw = (const int *)&u;
-        for (int k = threadIdx.x; k < (int)(sizeof(Uniforms) / 4); k += kBlock) ((int *)s_uni)[k] = srcw[k];
-    }
-    __syncthreads();
-    const Camera &cam = s_uni->cam;
-    const AdvanceParams &ap = s_uni->ap;
-    // what the scheduling loop itself needs stays scalar
-    const int ap_n = ap_arg.n, ap_max_bounces = ap_arg.max_bounces, ap_fb_fixed = ap_arg.fb_fixed;
-    // RT_FLAG_RNG_PER_SAMPLE: camera rays are not tied to slots, so the wave DRAWS them -- kCidChunk ids at a time from the
-    // frame's counter (one global atomic per chunk), handed to its lanes as they ask for one -- and no lane is left with more
-    // work than the others at the end of the frame (the static deal of slots costs 6 % there, 23 % on a 1/8 frame)
-    // (a build of its own -- DRAW_CIDS -- so that the reference-mode kernel carries none of it)
-    constexpr bool draw_cids = DRAW_CIDS && SPLIT_GEN;
-    int cid_next = 0, cid_end = 0;
-    // A lane works through the slots i, i + G, i + 2G, ... (G = lanes of the grid), each for the whole
-    // frame, one after the other: with G dividing the slot count every lane gets the same number of
-    // slots, so all lanes -- and all workgroups, which are all resident -- finish together.
-    const int lanes_in_grid = (int)(gridDim.x * blockDim.x);
-    // Which slots.  Slot s works through the pixels (s + g W) / spp, g = 0, 1, ...: a lattice of a few image
-    // columns (every 128th at 1920 x 1080 x 256 spp), the same lattice for slots s and s + 64 * lattice_blocks.
-    // A wave always owns 64 CONSECUTIVE slots (samples of one pixel: coherent primary rays; splitting waves
-    // into quarters was measured and loses more than it balances), but with plain striding the four waves of a
-    // workgroup, the four workgroups of a CU and all successive slot sets of a lane fall on ONE lattice, and
-    // whole CUs differ by +-5 % in work (bunny or no bunny in their columns) -- which the slowest one turns
-    // into frame time.  So the j-th wave of a workgroup is shifted by j quarter periods and the k-th slot set
-    // by k * 5/16 of a period.  A bijection between (set, 64-slot block) and (set, wave).  +6 % at 1 GPU.
-    auto slot_of = [&](int set) {  // (everything recomputed here: nothing of this lives across the main loop)
-        const unsigned lane_in_grid = blockIdx.x * blockDim.x + threadIdx.x;
-        const unsigned wave_in_grid = lane_in_grid >> 6, lane_in_wave = lane_in_grid & 63u;
-        // (the grid is a power of two: W is, shard counts divide it, and the host halves from there)
-        const unsigned b = (wave_in_grid + (wave_in_grid & 3u) * (unsigned)rot_wave + (unsigned)set * (unsigned)rot_set) &
-                           (((unsigned)lanes_in_grid >> 6) - 1u);
-        return set * lanes_in_grid + (int)(b * 64u + lane_in_wave);
-    };
-    int slot_set = 0;
-    int i = slot_of(0);
-    // persistent slot state
-    int bounces = kDone, pixel = 0, gen = 0;
-    Rng rs{0, 0, 0, 0, 0, 0};
-    V3 beta = mk(0, 0, 0);
-    auto load_slot = [&](int k) {
-        bounces = p.bounces(k);
-        pixel = p.pixel(k);
-        gen = p.gen(k);
-        rs = Rng{p.rd(k), p.r0(k), p.r1(k), p.r2(k), p.r3(k), p.r4(k)};
-        beta = mk(p.br(k), p.bg(k), p.bb(k));
-    };
-    // hand a finished slot back to the pools: the lockstep rounds of the final generation continue from there
-    auto store_slot = [&](int k) {
-        p.bounces(k) = bounces;
-        p.pixel(k) = pixel;
-        p.gen(k) = gen;
-        p.hit_info(k) = -1;
-        p.stmax(k) = -1.f;
-        p.br(k) = beta.x;
-        p.bg(k) = beta.y;
-        p.bb(k) = beta.z;
-        p.rd(k) = rs.d;
-        p.r0(k) = rs.v0;
-        p.r1(k) = rs.v1;
-        p.r2(k) = rs.v2;
-        p.r3(k) = rs.v3;
-        p.r4(k) = rs.v4;
-    };
-    auto cold_save = [&]() {
-        cold[0 * kBlock] = bounces;
-        cold[1 * kBlock] = pixel;
-        cold[2 * kBlock] = gen;
-        cold[3 * kBlock] = (int)rs.d;
-        cold[4 * kBlock] = (int)rs.v0;
-        cold[5 * kBlock] = (int)rs.v1;
-        cold[6 * kBlock] = (int)rs.v2;
-        cold[7 * kBlock] = (int)rs.v3;
-        cold[8 * kBlock] = (int)rs.v4;
-        cold[9 * kBlock] = __float_as_int(beta.x);
-        cold[10 * kBlock] = __float_as_int(beta.y);
-        cold[11 * kBlock] = __float_as_int(beta.z);
-    };
-    auto cold_load = [&]() {
-        bounces = cold[0 * kBlock];
-        pixel = cold[1 * kBlock];
-        gen = cold[2 * kBlock];
-        rs = Rng{(uint32_t)cold[3 * kBlock], (uint32_t)cold[4 * kBlock], (uint32_t)cold[5 * kBlock],
-                 (uint32_t)cold[6 * kBlock], (uint32_t)cold[7 * kBlock], (uint32_t)cold[8 * kBlock]};
-        beta = mk(__int_as_float(cold[9 * kBlock]), __int_as_float(cold[10 * kBlock]), __int_as_float(cold[11 * kBlock]));
-    };
-    int phase = PH_IDLE;
-    int tri = -1;
-    // the ray being traced, and the traversal cursor (`tri`: best hit so far / excluded triangle;
-    // `hu` doubles as the occluded flag of a shadow ray, exactly as in k_trace).  Between the end of
-    // a closest-hit trace and the ADV block, (tri, hu, hv, d) ARE the hit record.
-    V3 o = mk(0, 0, 0), d = mk(0, 0, 0), inv = mk(0, 0, 0);
-    float tmax = 0.f, hu = 0.f, hv = 0.f;
-    int cur = kEntryDone, sp = 0;
-    // hand a slot that has no camera ray left (or is parked for the lockstep final generation) back to the pools and take
-    // the lane's next one; `first_phase`: what an untouched slot does first (its bounces = INT_MAX makes that a gen())
-    auto next_slot = [&](int first_phase) {
-        cold_load();
-        store_slot(i);
-        phase = PH_IDLE;
-        tri = -1;
-        slot_set++;
-        i = slot_of(slot_set);
-        if (i < ap_n) {
-            load_slot(i);
-            if (bounces != kDone && bounces != kParked) {
-                phase = first_phase;
-                cold_save();
-                cold[12 * kBlock] = -1;
-            } else {
-                i = ap_n;  // (cannot happen: untouched slots start alive)
-            }
-        }
-    };
-    // Speculative traversal (kSpeculate): a lane that reaches a leaf inside a node block does not stop there -- it sets
-    // the leaf aside in `pend` and goes on with the next stack entry, so the up-to-8 node steps of a block are used by
-    // most lanes to the end (without it half of them idle from the middle of the block on), and the triangle block
-    // finds two leaves per lane.  The triangles of the postponed leaf are tested a little later, with whatever tmax the
-    // ray has then: the closest hit is the minimum over the accepted hits whatever the order (ties: closest_hit_wins),
-    // an occluder is an occluder whenever it is found; the price is a few node visits a fresher tmax would have culled.
-    int pend = kEntryDone;
-    acc[0 * kBlock] = acc[1 * kBlock] = acc[2 * kBlock] = 0.f;
-    if (i < ap_n) {
-        load_slot(i);
-        phase = (bounces != kDone && bounces != kParked) ? (SPLIT_GEN ? PH_GEN : PH_ADV) : PH_IDLE;  // (untouched slots: bounces = INT_MAX)
-        cold_save();
-        cold[12 * kBlock] = -1;  // no previous pixel
-    }
-    // wave-uniform event counters
-    unsigned long long n_gen = 0, n_shade = 0, n_traced = 0, n_shadow = 0, n_emit = 0, n_deposit = 0, n_rr = 0;
-#ifdef RT_TRACE_PROFILE
-    unsigned long long pf[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long pf_gen_cycles = 0, pf_fin_cycles = 0, pf_fin_lanes = 0, pf_fin_iters = 0;
-    const unsigned long long pf_t0 = __builtin_readcyclecounter();
-#endif
-
-    // The SIMD's issue arbiter prefers the OLDEST of its waves.  Left alone, the four waves of a SIMD (one from
-    // each of the CU's four resident workgroups) finish in dispatch order at 0.63 / 0.73 / 0.81 / 0.92 of the
-    // kernel's duration although they carry the same work, and the SIMD spends the last third of the frame with
-    // three, two, one wave -- too few to hide anything.  Rotating the waves' priorities makes them progress
-    // together (0.87 .. 0.92; +7 % throughput): every 2^prio_period scheduling decisions a wave takes the next of
-    // the four levels, starting from its workgroup's residency rank.  (Steering the priority by measured
-    // progress against the grid's average was tried and is worse than the plain rotation.)
-    unsigned prio_tick = 0;
-    const unsigned prio_rank = (4u * blockIdx.x) / gridDim.x;
-    while (true) {
-        RT_MARK("loop.head");
-        if (prio_period && (prio_tick++ & ((1u << prio_period) - 1u)) == 0u) {
-            unsigned lvl = ((prio_tick >> prio_period) + prio_rank) & 3u;
-            // ties go to the older wave, which left the two younger waves of a SIMD 5 % behind the two older ones;
-            // never dropping them to the lowest level evens that out (ranks finish at 0.95 .. 0.97 of the frame)
-            lvl = max(lvl, prio_rank >> 1);
-            switch (lvl) {
-                case 0: __builtin_amdgcn_s_setprio(0); break;
-                case 1: __builtin_amdgcn_s_setprio(1); break;
-                case 2: __builtin_amdgcn_s_setprio(2); break;
-                default: __builtin_amdgcn_s_setprio(3); break;
-            }
-        }
-        // ---- what each lane wants next: the ADV block, a node step, or triangle tests
-        bool trav = phase == PH_ANY || phase == PH_CLOSEST;
-        bool want_node = trav && cur >= 0;
-        bool want_tri = trav && ((cur != kEntryDone && cur < 0) || (kSpeculate && pend != kEntryDone));
-        int n_adv = wave_count((phase == PH_ADV));
-        const int n_genw = wave_count((phase == PH_GEN));
-        int n_node = wave_count((want_node));
-        int n_tri = wave_count((want_tri));
-        if (n_adv + n_genw + n_node + n_tri == 0) break;
-        // After a GEN or ADV block the wave goes straight on to the traversal blocks of this scheduling round (its lanes have
-        // just been given rays at the root): the lanes' wishes are taken again and the round trip through the loop head is
-        // saved (+3.8 % on C2).
-        auto retake = [&]() {
-            trav = phase == PH_ANY || phase == PH_CLOSEST;
-            want_node = trav && cur >= 0;
-            want_tri = trav && ((cur != kEntryDone && cur < 0) || (kSpeculate && pend != kEntryDone));
-            n_adv = wave_count((phase == PH_ADV));
-            n_node = wave_count((want_node));
-            n_tri = wave_count((want_tri));
-        };
-        // Every block is issued for the whole wave whatever the number of lanes that need it.  The ADV
-        // block is ~15x longer than a node step or a triangle test, so it waits for `adv_batch` lanes
-        // unless nothing else can run, and the ADV lanes must also be at least half as many as the node and as the triangle
-        // lanes.  (Requiring a full majority measured 1 % slower.  Dropping the half condition is as fast in logic, but when
-        // the kernel sat exactly at 128 VGPRs that source shape tipped the register allocation into 21 spills: -6 %.  The
-        // kernel has since come down to 115, but `make resource-usage` after any edit here all the same: "VGPRs Spill" of
-        // k_paths<..., 4, ...> must stay 0 (a CPU test checks it).)
-        const bool run_adv = n_adv > 0 && ((n_adv >= adv_batch && 2 * n_adv >= n_node && 2 * n_adv >= n_tri) || n_node + n_tri == 0);
-        // ---------------- GEN block: gen() (render.cuh:250-275) for the lanes whose path certainly ended -- it missed
-        // or ran out of bounces (a third of all ADV work), or the ADV block found it Russian-roulette-killed to the
-        // last bounce.  A tenth of the ADV block's length, so it runs for far fewer waiting lanes.
-        if (SPLIT_GEN && !run_adv && n_genw > 0 && (n_genw >= gen_batch || n_node + n_tri == 0)) {
-            RT_MARK("gen.begin");
-#ifdef RT_TRACE_PROFILE
-            pf[12]++; pf[15] += n_genw;
-            const unsigned long long pf_tg = __builtin_readcyclecounter();
-#endif
-            // (what the block changes in the lane's loop-carried registers is applied by selects after the divergent part,
-            // and the rare hand-back of a finished slot sits behind a wave-uniform branch: as assignments inside the
-            // branches these cost the wave ~45 register moves per GEN block at the merges)
-            AdvanceOut out;
-            out.did_gen = out.new_ray = false;
-            out.ray_o = o;
-            out.ray_d = d;
-            bool hand_back = false;
-            long long my_cid = -1;
-            if (draw_cids) {
-                const unsigned long long m = wave_ballot(phase == PH_GEN);
-                const int need = (int)__popcll(m), rank = (int)prefix_popc(m);
-                int served = 0;
-                while (served < need) {
-                    if (cid_next == cid_end) {
-                        unsigned base = 0;
-                        if (lane_id() == 0) base = atomicAdd(next_cid, (unsigned)kCidChunk);
-                        // (past the frame's end: "none left".  The clamp leaves room for cid_end = cid_next + kCidChunk below
-                        // INT_MAX; ids that large are never rendered anyway: render_shard_impl refuses frames whose camera-ray
-                        // ids come within 13 W of 2^31, and a wave overshoots the frame's end by at most one chunk)
-                        static_assert(0x7ffff000u + (unsigned)kCidChunk < 0x7fffffffu, "cid_end must not overflow int");
-                        cid_next = (int)min(__builtin_amdgcn_readfirstlane(base), 0x7ffff000u);
-                        cid_end = cid_next + kCidChunk;
-                    }
-                    const int take = min(need - served, cid_end - cid_next);
-                    if (phase == PH_GEN && rank >= served && rank < served + take) my_cid = cid_next + (rank - served);
-                    cid_next += take;
-                    served += take;
-                }
-            }
-            if (phase == PH_GEN) {
-                SlotState st;
-                st.gen = cold[2 * kBlock];
-                st.rs = Rng{(uint32_t)cold[3 * kBlock], (uint32_t)cold[4 * kBlock], (uint32_t)cold[5 * kBlock],
-                            (uint32_t)cold[6 * kBlock], (uint32_t)cold[7 * kBlock], (uint32_t)cold[8 * kBlock]};
-                st.bounces = 0;
-                st.pixel = 0;
-                st.beta = mk(0, 0, 0);
-                int pxy = cold[12 * kBlock];
-                acc_flush(acc, fb, ap_fb_fixed, cold[1 * kBlock]);  // the camera ray that ended: its sum -> its pixel
-                gen_core<true>(cam, ap, ap.slot_lo + i, st, out, &pxy, my_cid);
-                // the slot state gen() leaves: bounces (0, or the kDone / kParked sentinel), gen, the RNG; a new path also
-                // has its pixel and beta = 1
-                cold[0 * kBlock] = st.bounces;
-                cold[2 * kBlock] = st.gen;
-                cold[3 * kBlock] = (int)st.rs.d;
-                cold[4 * kBlock] = (int)st.rs.v0;
-                cold[5 * kBlock] = (int)st.rs.v1;
-                cold[6 * kBlock] = (int)st.rs.v2;
-                cold[7 * kBlock] = (int)st.rs.v3;
-                cold[8 * kBlock] = (int)st.rs.v4;
-                if (out.new_ray) {
-                    cold[1 * kBlock] = st.pixel;
-                    cold[9 * kBlock] = __float_as_int(st.beta.x);
-                    cold[10 * kBlock] = __float_as_int(st.beta.y);
-                    cold[11 * kBlock] = __float_as_int(st.beta.z);
-                    cold[12 * kBlock] = pxy;
-                } else {
-                    hand_back = true;  // out of camera rays, or parked for the lockstep final generation
-                }
-            }
-            const bool nr = out.new_ray;
-            o = out.ray_o;
-            d = out.ray_d;
-            inv = inv_dir(d);  // (for every lane, as after the ADV block: the same value for the lanes that keep their ray)
-            phase = nr ? (int)PH_CLOSEST : phase;
-            tmax = nr ? kFltMax : tmax;
-            tri = nr ? -1 : tri;
-            cur = nr ? 0 : cur;
-            sp = nr ? 0 : sp;
-            if (wave_ballot(hand_back)) {  // rare (once per slot and frame): kept out of the merges above
-                if (hand_back) {
-                    if (draw_cids) phase = PH_IDLE;  // (the frame's counter has run out: nothing is tied to this lane's slot)
-                    else next_slot(PH_GEN);
-                }
-            }
-            n_gen += wave_count((out.did_gen));
-            n_traced += wave_count((out.new_ray));
-#ifdef RT_TRACE_PROFILE
-            pf_gen_cycles += __builtin_readcyclecounter() - pf_tg;
-#endif
-            retake();
-            RT_MARK("gen.end");
-        }
-        if (run_adv) {
-#ifdef RT_TRACE_PROFILE
-            pf[0]++; pf[1] += n_adv;
-            const unsigned long long pf_ta = __builtin_readcyclecounter();
-#endif
-            // ---------------- ADV block
-            RT_MARK("adv.head");
-            AdvanceOut out;
-            out.did_gen = out.did_shade = out.has_shadow = out.did_emit = out.new_ray = false;
-            out.rr_draws = 0;
-            if (phase == PH_ADV) {
-                // the slot state is only live between cold_load() and cold_save() below
-                cold_load();
-                SlotState st;
-                st.wo = d;
-                st.hit_info = -1;
-                st.isect_p = st.isect_n = mk(0, 0, 0);
-                if (tri >= 0) {  // hit record in the form mat() consumes (render.cuh:152-153, 311-316)
-                    Tri tr = load_tri(sc.tris, tri);
-                    float4 sh = sc.tri_shade[(unsigned)tri];
-                    RT_MARK("adv.verify");
-                    if (VERIFY) {
-                        // (o, d) are still the path ray that ended on `tri`.  A set sign bit of hv: an exact tie at the final
-                        // distance (triangle block) -- or a v of -0.0, which costs a needless, equally exact re-trace
-                        bool bad = (__float_as_uint(hv) >> 31) != 0u;
-                        if (bad) atomicAdd(&vstat[V_TIE], 1ull);
-                        else bad = !ref_visible(sc, o, d, tr, tri, vstat);
-                        if (bad) {
-                            atomicAdd(&vstat[V_LITERAL], 1ull);
-                            float tm = kFltMax;
-                            tri = -1;
-                            hu = hv = 0.f;
-                            reference_walk<false>(sc, o, d, tm, tri, hu, hv, stack, over, stack_cap);
-                            cold_load();  // (again: what was loaded above need not stay in registers across the walk)
-                            if (tri >= 0) {
-                                tr = load_tri(sc.tris, tri);
-                                sh = sc.tri_shade[(unsigned)tri];
-                            }
-                        }
-                    }
-                    RT_MARK("adv.hit_record");
-                    if (!VERIFY || tri >= 0) {
-                        st.isect_p = tri_point(tr, hu, hv);
-                        st.isect_n = mk(sh.x, sh.y, sh.z);
-                        st.hit_info = __float_as_int(sh.w);
-                    }
-                }
-                st.bounces = bounces;
-                st.pixel = pixel;
-                st.gen = gen;
-                st.rs = rs;
-                st.beta = beta;
-                advance_core<SPLIT_GEN, true, true>(sc, tab, cam, ap, ap.slot_lo + i, st, out, fb, acc);
-                RT_MARK("adv.tail");
-                bounces = st.bounces;
-                pixel = st.pixel;
-                gen = st.gen;
-                rs = st.rs;
-                beta = st.beta;
-                if (out.has_shadow) {
-                    park[0 * kBlock] = out.ray_o.x;
-                    park[1 * kBlock] = out.ray_o.y;
-                    park[2 * kBlock] = out.ray_o.z;
-                    park[3 * kBlock] = out.ray_d.x;
-                    park[4 * kBlock] = out.ray_d.y;
-                    park[5 * kBlock] = out.ray_d.z;
-                    park[6 * kBlock] = out.s_L.x;
-                    park[7 * kBlock] = out.s_L.y;
-                    park[8 * kBlock] = out.s_L.z;
-                    o = out.s_o;
-                    d = out.s_d;
-                    phase = PH_ANY;
-                    tmax = out.s_tmax;
-                    tri = out.s_target;
-                    hu = 0.f;
-                } else if (out.new_ray) {
-                    o = out.ray_o;
-                    d = out.ray_d;
-                    phase = PH_CLOSEST;
-                    tmax = kFltMax;
-                    tri = -1;
-                } else if (SPLIT_GEN) {
-                    phase = PH_GEN;  // out.wants_gen: Russian roulette ended the path (its draws are in rs)
-                    tri = -1;
-                } else {
-                    // this slot is out of camera rays (or parked for the lockstep final generation)
-                    cold_save();
-                    next_slot(PH_ADV);
-                }
-                if (phase == PH_ANY || phase == PH_CLOSEST) {
-                    cur = 0;
-                    sp = 0;
-                }
-                // (the same treatment as in the GEN block -- selects after the divergent part -- was measured here and
-                // loses 1 %: the shading block's exits are three-way and the selects outnumber the moves they replace)
-                if (phase != PH_IDLE) cold_save();
-            }
-            // 1 / d for EVERY lane, also those that only sat through the block: three v_rcp_f32, and 1 / d does not have
-            // to stay in registers across the ~1 100 vector instructions of the block (three registers that decided
-            // between a build with and without spills when the kernel sat at 128 VGPRs)
-            inv = inv_dir(d);
-            if (!SPLIT_GEN) n_gen += wave_count((out.did_gen));
-            n_shade += wave_count((out.did_shade));
-            n_traced += wave_count((out.new_ray));
-            n_shadow += wave_count((out.has_shadow));
-            n_emit += wave_count((out.did_emit));
-            int rr = out.rr_draws;
-            if (wave_ballot(rr != 0)) {
-                for (int off = 32; off > 0; off >>= 1) rr += __shfl_xor(rr, off);
-                n_rr += (unsigned long long)rr;
-            }
-#ifdef RT_TRACE_PROFILE
-            pf[8] += __builtin_readcyclecounter() - pf_ta;
-#endif
-            retake();
-            RT_MARK("adv.after");
-        }
-        const bool is_any = phase == PH_ANY;
-        // ---------------- node steps for the lanes in `want`
-        auto node_block = [&](bool want, int n_want) {
-#ifdef RT_TRACE_PROFILE
-            pf[2]++; pf[3] += n_want; pf[6] += n_adv;
-            const unsigned long long pf_tn = __builtin_readcyclecounter();
-#endif
-            RT_MARK("node.begin");
-            if (LITERAL) {
-                if (want) {
-                    if (is_any) reference_walk<true>(sc, o, d, tmax, tri, hu, hv, stack, over, stack_cap);
-                    else reference_walk<false>(sc, o, d, tmax, tri, hu, hv, stack, over, stack_cap);
-                    cur = kEntryDone;
-                }
-            } else if (want) {
-                // a bounded while-while: up to kNodePerStep consecutive node steps (2 triangle tests in the
-                // triangle block) per scheduling decision -- measured best at 8 / 2 (+22 % over 1 / 1; 4 / 2: +20 %)
-                auto step_general = [&]() {
-                    if (cur >= 0) {
-                        inner_step<WIDE>(sc, o, inv, tmax, cur, sp, stack, over, stack_cap, s_top, top_n);
-                    } else if (kSpeculate && cur != kEntryDone && pend == kEntryDone && sp > 0) {
-                        pend = cur;  // a leaf: set it aside, go on with the next entry
-                        cur = stack_pop(stack, over, sp, stack_cap);
-                    }
-                };
-                // 4-wide nodes on the full pool: ONE wave vote per step decides between the step without any overflow
-                // handling (all lanes of the block hold at most stack_cap - 3 entries: 95 % of the steps) and the general one
-                auto step = [&]() {
-                    if (!WIDE || MIN_WAVES == 2) {
-                        step_general();
-                    } else if (wave_ballot(sp > stack_cap - 3) == 0ull) {
-                        if (cur >= 0) {
-                            inner_step<WIDE, true>(sc, o, inv, tmax, cur, sp, stack, over, stack_cap);
-                        } else if (kSpeculate && cur != kEntryDone && pend == kEntryDone && sp > 0) {
-                            pend = cur;
-                            sp--;
-                            cur = stack[sp * kBlock];
-                        }
-                    } else {
-                        step_general();
-                    }
-                };
-                if (kNodeCont == 0 || !WIDE) {
-#pragma unroll
-                    for (int rep = 0; rep < (WIDE ? kNodePerStepWide : kNodePerStep); rep++) step();
-                } else {
-                    // adaptive: the fixed steps, then kNodeExtra more if enough lanes of the wave still have one to make
-#pragma unroll
-                    for (int rep = 0; rep < kNodePerStepWide; rep++) step();
-                    if (wave_count(cur >= 0) >= kNodeCont) {
-#pragma unroll
-                        for (int rep = 0; rep < kNodeExtra; rep++) step();
-                    }
-                }
-            }
-#ifdef RT_TRACE_PROFILE
-            pf[9] += __builtin_readcyclecounter() - pf_tn;
-#endif
-            RT_MARK("node.end");
-        };
-        // ---------------- triangle tests (triangle.cuh:39-58) for the lanes in `want`: the leaf reference is the cursor
-        auto tri_block = [&](bool want, int n_want) {
-#ifdef RT_TRACE_PROFILE
-            pf[4]++; pf[5] += n_want; pf[7] += n_adv;
-            const unsigned long long pf_tt = __builtin_readcyclecounter();
-#endif
-            RT_MARK("tri.begin");
-            if (want) {
-                // kTriPerStep tests per lane, and ALL their triangle records are fetched before the first test: which
-                // triangles come next does not depend on the outcome of a test (only whether they are still wanted does: an
-                // occluded shadow ray is finished), so the block waits for one memory round trip instead of one per test.
-                // The lane's walk through its leaves is made up front on copies of (pend, cur):
-                //   the postponed leaf first, then the leaf under the cursor; when the cursor's leaf is used up, the next
-                //   stack entry -- popped on the spot: a ray that turns out occluded has no use for its stack any more.
-                // Straight-line bookkeeping: every outcome is a select, not a branch (the merges of the branchy version cost
-                // the wave ~30 register moves per test); the only branches left are the rare ones (a tie between two hits;
-                // a pop from the overflow column).
-                int pd = pend, cu = cur;
-                int ks[kTriPerStep] = {};  // (0 = a valid triangle address for lanes that have nothing to fetch)
-                bool act[kTriPerStep];
-                Tri tr[kTriPerStep];
-#pragma unroll
-                for (int j = 0; j < kTriPerStep; j++) {
-                    const bool fp = kSpeculate && pd != kEntryDone;
-                    const bool leaf = cu != kEntryDone && cu < 0;
-                    act[j] = fp || leaf;
-                    const int enc = fp ? pd : cu;  // ~((first << 3) | count)
-                    ks[j] = act[j] ? (~enc) >> 3 : ks[0];  // (an address that is valid in any case)
-                    const bool more = ((~enc) & 7) > 1;
-                    const int rest = more ? enc - 7 : kEntryDone;  // one triangle further: first + 1, count - 1
-                    int popped = kEntryDone;
-                    // (the same wave vote as in the node step -- no lane has entries in the overflow part -- measured here: +1 %
-                    // SLOWER, it undoes the node step's gain: profiles/r05_experiments.md)
-                    if (act[j] && !fp && !more && sp > 0) popped = stack_pop(stack, over, sp, stack_cap);
-                    pd = (act[j] && fp) ? rest : pd;
-                    cu = (act[j] && !fp) ? (more ? rest : popped) : cu;
-                    tr[j] = load_tri(sc.tris, ks[j]);
-                }
-                // the tests, each with the tmax the earlier ones left.  any-hit: the first accepted hit that is not the
-                // excluded triangle (bvh.cuh:243); closest-hit: bvh.cuh:227-231 (t <= tmax), ties by closest_hit_wins
-                bool occluded = false;
-                int occ_j = 0;  // which of the tests found the occluder
-#pragma unroll
-                for (int j = 0; j < kTriPerStep; j++) {
-                    if (act[j] && !occluded) {
-                        float t, u, v;
-                        const bool hit = tri_intersect(tr[j], o, d, tmax, t, u, v);
-                        occluded = hit && is_any && ks[j] != tri;
-                        occ_j = occluded ? j : occ_j;
-                        bool better = hit && !is_any;
-                        if (VERIFY) {
-                            // an exact tie is the reference's tree order to decide: the ray is re-traced literally in the ADV block
-                            // (the mark is the sign bit of hv; v >= 0 for an accepted hit), so which of the two stays until then
-                            // does not matter -- no branch, no look at the caller order
-                            const bool tie = better && t == tmax && tri >= 0;
-                            v = __uint_as_float(__float_as_uint(v) | (tie ? 0x80000000u : 0u));
-                        } else if (better && t == tmax && tri >= 0) {  // (RT_FLAG_WATERTIGHT: ties go to the larger caller index)
-                            better = sc.order[(unsigned)ks[j]] > sc.order[(unsigned)tri];
-                        }
-                        tmax = better ? t : tmax;
-                        hu = occluded ? 1.f : (better ? u : hu);
-                        hv = better ? v : hv;
-                        tri = better ? ks[j] : tri;
-                    }
-                }
-                pend = occluded ? kEntryDone : pd;
-                cur = occluded ? kEntryDone : cu;
-                // VERIFY: an occluder only counts if the reference's walk can see its triangle (2 % of the shadow rays get here;
-                // ONE branch behind both tests: inside each test it cost the block's straight-line shape, 2 % of the frame).  An
-                // occluder it cannot see -- ~1 in 10^7 -- says nothing about the rest of the ray: the ray ends here and is
-                // re-traced through the reference's own tree in the finished-rays section (hu = 2 marks it)
-                if (VERIFY && occluded) {
-                    static_assert(kTriPerStep == 2, "the occluder is picked from two records");
-                    Tri tq;
-                    tq.p0 = occ_j ? tr[1].p0 : tr[0].p0;
-                    tq.e1 = occ_j ? tr[1].e1 : tr[0].e1;
-                    tq.e2 = occ_j ? tr[1].e2 : tr[0].e2;
-                    tq.n = tq.p0;  // (not looked at)
-                    if (!ref_visible(sc, o, d, tq, occ_j ? ks[1] : ks[0], vstat)) hu = 2.f;
-                }
-            }
-#ifdef RT_TRACE_PROFILE
-            pf[10] += __builtin_readcyclecounter() - pf_tt;
-#endif
-            RT_MARK("tri.end");
-        };
-        // Which of the two: the more popular block -- and when that is the node block, the triangle block right behind it
-        // for the lanes that hold a leaf BY THEN (at least `tri_follow` of them): a lane that reached a leaf in the node
-        // block has its triangles tested in this scheduling round instead of the next one.  Measured on C2: +6.6 % at
-        // tri_follow = 1, +5.3 % at 12, +0.4 % at 40; the mirror image (a node block behind a triangle block) buys nothing on
-        // top and loses 5 % alone.  (ONE copy of the triangle block in the code: the block behind a node block and the block
-        // on its own are the same instructions for different lanes.)
-        {
-            const bool run_node = n_node > 0 && n_node >= n_tri;
-            bool w = want_tri;
-            int nw = n_tri;
-            if (run_node) {
-                node_block(want_node, n_node);
-                w = tri_follow > 0 && trav && ((cur != kEntryDone && cur < 0) || (kSpeculate && pend != kEntryDone));
-                nw = wave_count(w);
-                nw = (tri_follow > 0 && nw >= tri_follow) ? nw : 0;
-            }
-            if (nw > 0) tri_block(w, nw);
-        }
-        // ---------------- finished rays
-        RT_MARK("fin.begin");
-        const bool fin = trav && cur == kEntryDone && (!kSpeculate || pend == kEntryDone);
-#ifdef RT_TRACE_PROFILE
-        const unsigned long long pf_tf = __builtin_readcyclecounter();
-        pf_fin_lanes += wave_count(fin);
-        pf_fin_iters += wave_ballot(fin) != 0 ? 1 : 0;
-#endif
-        if (VERIFY) {  // the shadow rays whose occluder the reference cannot see (triangle block): the literal walk decides
-            const bool lit = fin && is_any && hu == 2.f;
-            if (wave_ballot(lit)) {
-                if (lit) {
-                    atomicAdd(&vstat[V_LITERAL], 1ull);
-                    float tm = tmax, no_v = 0.f;
-                    int excluded = tri;
-                    hu = 0.f;
-                    reference_walk<true>(sc, o, d, tm, excluded, hu, no_v, stack, over, stack_cap);
-                }
-            }
-        }
-        n_deposit += wave_count((fin && is_any && hu == 0.f));
-        if (fin) {
-            if (is_any) {
-                if (hu == 0.f && !debug_no_deposit)  // unoccluded: render.cuh:291-293
-                    acc_add(acc, park[6 * kBlock], park[7 * kBlock], park[8 * kBlock]);
-                // now the slot's path ray
-                o = mk(park[0 * kBlock], park[1 * kBlock], park[2 * kBlock]);
-                d = mk(park[3 * kBlock], park[4 * kBlock], park[5 * kBlock]);
-                phase = PH_CLOSEST;
-                inv = inv_dir(d);
-                tmax = kFltMax;
-                tri = -1;
-                cur = 0;
-                sp = 0;
-            } else {
-                // (tri, hu, hv, d) carry the hit to the ADV block; a path that missed, or has no bounce left (and is not
-                // at bounce 0, where a hit light still emits: render.cuh:98-109), can only generate
-                const int b = cold[0 * kBlock];
-                phase = (SPLIT_GEN && (tri < 0 || (b >= ap_max_bounces && b > 0))) ? PH_GEN : PH_ADV;
-            }
-        }
-#ifdef RT_TRACE_PROFILE
-        pf_fin_cycles += __builtin_readcyclecounter() - pf_tf;
-#endif
-    }
-#ifdef RT_TRACE_PROFILE
-    if (prof && lane_id() == 0) { atomicAdd(&prof[17], pf_fin_cycles); atomicAdd(&prof[18], pf_fin_lanes); atomicAdd(&prof[19], pf_fin_iters); }
-    if (prof && lane_id() == 0)
-        { pf[11] = __builtin_readcyclecounter() - pf_t0; for (int k = 0; k < 16; k++) atomicAdd(&prof[k], pf[k]); atomicMax(&prof[13], pf[11]); atomicAdd(&prof[14], 1ull); atomicAdd(&prof[16], pf_gen_cycles);
-          // per-wave record: where it ran and for how long
-          unsigned long long *rec = prof + 24 + 4 * (size_t)((blockIdx.x * kBlock + threadIdx.x) >> 6);
-          rec[0] = __builtin_amdgcn_s_getreg((31 << 11) | 4);   // HW_ID
-          rec[1] = __builtin_amdgcn_s_getreg((31 << 11) | 20);  // XCC_ID
-          rec[2] = pf[11];
-          rec[3] = pf[0] + pf[2] + pf[4]; }
-#endif
-    unsigned long long v[C_COUNT] = {n_gen, n_shade, n_traced, n_shadow, n_emit, n_deposit, n_rr, 0ull};
-    row_add(rows, v);
-}
+// The two kernels of a frame, once per source of camera rays (see gen_core): the text of rt_frame_kernels.inc compiled with
+// RT_FRAME_SRC = Camera as k_advance / k_paths and with RT_FRAME_SRC = RayTable (rt_render_rays_*) as k_advance_rays /
+// k_paths_rays.  Two compilations of one text rather than a template parameter or a shared device function: the camera
+// builds keep their symbols, their arguments and -- instruction for instruction -- their code.
+#define RT_FRAME_SRC Camera
+#define RT_K_ADVANCE k_advance
+#define RT_K_PATHS k_paths
+#include "rt_frame_kernels.inc"
+#undef RT_FRAME_SRC
+#undef RT_K_ADVANCE
+#undef RT_K_PATHS
+#define RT_FRAME_SRC RayTable
+#define RT_K_ADVANCE k_advance_rays
+#define RT_K_PATHS k_paths_rays
+#include "rt_frame_kernels.inc"
+#undef RT_FRAME_SRC
+#undef RT_K_ADVANCE
+#undef RT_K_PATHS
 
 // post_process_framebuffer (render.cuh:330-338): c = sqrt(c * (1/spp))
 __global__ void k_post_process(float *fb, int n_values, float inv_spp) {
@@ -3906,6 +3178,19 @@ static PathsKernel paths_kernel(bool lds_tables, bool wide, bool few_blocks, boo
     return (wide ? paths_kernel_of<false, true> : paths_kernel_of<false, false>)(few_blocks, per_sample, literal, verify);
 }
 
+// Ray-table frames: k_advance_rays / k_paths_rays (4-wide tree only; a 2-wide scene runs such a frame on the round pipeline).
+using AdvanceRaysKernel = decltype(&k_advance_rays<false>);
+using PathsRaysKernel = decltype(&k_paths_rays<false, true, 4, false, false, false>);
+static AdvanceRaysKernel advance_rays_kernel(bool lds_tables) { return lds_tables ? k_advance_rays<true> : k_advance_rays<false>; }
+template <bool LDS_TABLES>
+static PathsRaysKernel paths_rays_kernel_of(bool few_blocks, bool verify) {
+    if (few_blocks) return verify ? k_paths_rays<LDS_TABLES, true, 2, false, false, true> : k_paths_rays<LDS_TABLES, true, 2, false, false, false>;
+    return verify ? k_paths_rays<LDS_TABLES, true, 4, false, false, true> : k_paths_rays<LDS_TABLES, true, 4, false, false, false>;
+}
+static PathsRaysKernel paths_rays_kernel(bool lds_tables, bool few_blocks, bool verify) {
+    return (lds_tables ? paths_rays_kernel_of<true> : paths_rays_kernel_of<false>)(few_blocks, verify);
+}
+
 // Global overflow part of the traversal stacks: `levels` entries for each of kOverStride lanes.  Every OWNER of
 // concurrently running grids has its own buffer -- a render context (one render at a time: Context::busy), or one
 // call of a stage-level test entry point -- because a lane indexes its column by its position in ITS grid only:
@@ -3952,17 +3237,27 @@ int ensure_rng(Context &c, uint64_t seed, int slot_lo, hipStream_t st, double *s
     return 0;
 }
 
+// One frame of one shard.  `rays` null: the camera's frame (rt_render_shard*).  `rays` set (rt_render_rays_*, which has
+// validated the table on the device; `camera` is not looked at): camera ray c is row c of the table, the frame is
+// rays->n_rays camera rays over width * height = n_pixels x 1 pixels, and `spp` is the rays_per_pixel of the c / spp rule.
+// Everything else -- context, RNG, stacks, launch parameters, the lockstep final generation, stats -- is one body.
+struct RayFrame {
+    RayTable table;
+    long long n_rays;
+};
 int render_shard_impl(const rt_scene *scene, const rt_camera *camera, int width, int height, int spp,
                       int max_bounces, uint64_t seed, int shard_index, int shard_count, uint32_t flags,
-                      float *d_sum, hipStream_t st, rt_stats *stats, int ctx_lane = 0) {
-    if (!scene || !camera || !d_sum) return fail("rt_render_shard: null argument");
+                      float *d_sum, hipStream_t st, rt_stats *stats, int ctx_lane = 0, const RayFrame *rays = nullptr) {
+    if (!scene || (!camera && !rays) || !d_sum) return fail("rt_render_shard: null argument");
     if (width <= 0 || height <= 0 || spp <= 0 || max_bounces < 0) return fail("rt_render_shard: bad dimensions");
     if (max_bounces > (1 << 24)) return fail("rt_render_shard: max_bounces exceeds 16777216");
     if (shard_count <= 0 || kW % shard_count != 0 || shard_index < 0 || shard_index >= shard_count)
         return fail("rt_render_shard: shard_count must divide 1048576 and 0 <= shard_index < shard_count");
     if ((long long)width * height > (long long)(0x7fffffff / 3))  // framebuffer values are indexed with 32 bits
         return fail("rt_render_shard: width*height exceeds 715827882 pixels");
-    if (int rc = ensure_origin_radius(scene, camera->lookfrom)) return rc;  // (camera rays start at lookfrom: camera.cuh:22-26)
+    // (camera rays start at lookfrom: camera.cuh:22-26; a table's origins: rt_render_rays_*'s prepass has seen to them)
+    if (!rays)
+        if (int rc = ensure_origin_radius(scene, camera->lookfrom)) return rc;
     // RT_FLAG_RNG_PER_SAMPLE: this rank renders the whole frame at num_samples / shard_count samples per pixel with ALL W
     // slots; camera ray `cid` of the rank has the global key cid * shard_count + shard_index, so the keys of a pixel's
     // samples are the same set whatever the shard count (see AdvanceParams)
@@ -3977,7 +3272,7 @@ int render_shard_impl(const rt_scene *scene, const rt_camera *camera, int width,
         if (spp % shard_count != 0) return fail("rt_render_shard: RT_FLAG_RNG_PER_SAMPLE needs num_samples divisible by shard_count");
         spp /= shard_count;
     }
-    long long cam_end = (long long)width * height * spp;
+    long long cam_end = rays ? rays->n_rays : (long long)width * height * spp;
     if (cam_end + 13LL * kW >= (1LL << 31))  // the reference's int32 camera_ray ids (render.cuh:370-371,440)
         return fail("rt_render_shard: width*height*spp exceeds the reference's int32 camera-ray range");
     int dev = 0;
@@ -4000,8 +3295,9 @@ int render_shard_impl(const rt_scene *scene, const rt_camera *camera, int width,
 
     const bool time_kernels = (flags & RT_FLAG_TIME_KERNELS) != 0;
     DScene sc = scene->dev();
-    Camera cam;
-    memcpy(&cam, camera, sizeof(Camera));
+    Camera cam{};
+    if (!rays) memcpy(&cam, camera, sizeof(Camera));
+    const RayTable table = rays ? rays->table : RayTable{};
     {
         DCounters zero{};
         zero.last_live_round = -1;
@@ -4044,7 +3340,7 @@ int render_shard_impl(const rt_scene *scene, const rt_camera *camera, int width,
     ap.batch_mask = 7;
     ap.lockstep = 0;
     ap.fb_fixed = (flags & kFlagFixedFb) ? 1 : 0;
-    ap.w_over_spp = (kW % spp == 0) ? kW / spp : 0;
+    ap.w_over_spp = (kW % spp == 0 && !rays) ? kW / spp : 0;  // (the pixel stepping is the camera frames')
     ap.dpx = ap.w_over_spp % width;
     ap.dpy = (ap.w_over_spp > 0 && width < 32768 && height < 32768) ? ap.w_over_spp / width : -1;
     const bool lds_tables = scene->n_mats <= kLdsTable && scene->n_lights <= kLdsTable;
@@ -4075,7 +3371,12 @@ int render_shard_impl(const rt_scene *scene, const rt_camera *camera, int width,
     // advance grid, whose wave count sizes the counter rows)
     int dev_cus = 0, occ_c = 0;
     HIP_TRY(hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, dev));
-    const AdvanceKernel advance = advance_kernel(lds_tables);
+    const AdvanceKernel advance_cam = advance_kernel(lds_tables);
+    const AdvanceRaysKernel advance_tab = advance_rays_kernel(lds_tables);
+    auto launch_advance = [&]() {
+        if (rays) hipLaunchKernelGGL(advance_tab, grid, block, 0, st, sc, c.pools, table, ap, d_sum, c.d_ctr, c.d_rows, c.d_lock);
+        else hipLaunchKernelGGL(advance_cam, grid, block, 0, st, sc, c.pools, cam, ap, d_sum, c.d_ctr, c.d_rows, c.d_lock);
+    };
     const TraceKernel trace = trace_kernel<MODE_POOL>(literal, verify, scene->wide);
     // (every k_trace build runs 8 waves per SIMD without static LDS: the grid does not depend on which one this is)
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_c, trace, kBlock, lds_bytes));
@@ -4114,6 +3415,7 @@ int render_shard_impl(const rt_scene *scene, const rt_camera *camera, int width,
     // round-per-launch pipeline (k_advance + k_trace) that the lockstep final generation also uses
     bool persistent = true;
     if (const char *e = knob("RT_PERSISTENT")) persistent = atoi(e) != 0;
+    if (rays && !scene->wide) persistent = false;  // (k_paths_rays walks 4-wide nodes; the round pipeline walks either format)
     if (per_sample && !persistent) return fail("rt_render_shard: RT_FLAG_RNG_PER_SAMPLE runs on the persistent kernel only");
     float ms_paths = 0.f;
     int top_records_in_lds = 0;
@@ -4173,7 +3475,7 @@ int render_shard_impl(const rt_scene *scene, const rt_camera *camera, int width,
         int rot_wave = 0, rot_set = 0;
         {
             long long period = 0;
-            if (spp % 64 == 0 && kW % spp == 0) {
+            if (!rays && spp % 64 == 0 && kW % spp == 0) {  // (a table's rays follow no pixel lattice: the fallback below)
                 const long long step = (kW / spp) % width;  // columns a slot moves per generation
                 long long a = step, b = width;
                 while (b) { long long t = a % b; a = b; b = t; }
@@ -4190,10 +3492,16 @@ int render_shard_impl(const rt_scene *scene, const rt_camera *camera, int width,
         if (const char *e = knob("RT_PRIO_ROTATE")) prio_rotate = atoi(e);
         HIP_TRY(hipEventRecord(c.ev_a, st));
         // (the reference-walk build is passed top_n = 0, while top_n * 64 bytes of LDS stay reserved and reported in reserved[2])
-        const PathsKernel paths = paths_kernel(lds_tables, scene->wide, few_blocks, per_sample, literal, verify);
-        hipLaunchKernelGGL(paths, grid_paths, block, lds_paths, st, sc, c.pools, cam, ap, d_sum, c.d_rows, paths_cap, d_over2, adv_batch,
-                           dbg, paths_prof, literal ? 0 : top_n, prio_rotate, rot_wave, rot_set, gen_batch, tri_follow, &c.d_ctr->pad2[0],
-                           &c.d_ctr->vstat[0]);
+        if (rays) {
+            hipLaunchKernelGGL(paths_rays_kernel(lds_tables, few_blocks, verify), grid_paths, block, lds_paths, st, sc, c.pools, table, ap, d_sum,
+                               c.d_rows, paths_cap, d_over2, adv_batch, dbg, paths_prof, top_n, prio_rotate, rot_wave, rot_set, gen_batch,
+                               tri_follow, &c.d_ctr->pad2[0], &c.d_ctr->vstat[0]);
+        } else {
+            const PathsKernel paths = paths_kernel(lds_tables, scene->wide, few_blocks, per_sample, literal, verify);
+            hipLaunchKernelGGL(paths, grid_paths, block, lds_paths, st, sc, c.pools, cam, ap, d_sum, c.d_rows, paths_cap, d_over2, adv_batch,
+                               dbg, paths_prof, literal ? 0 : top_n, prio_rotate, rot_wave, rot_set, gen_batch, tri_follow, &c.d_ctr->pad2[0],
+                               &c.d_ctr->vstat[0]);
+        }
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(c.ev_b, st));
         HIP_TRY(hipEventSynchronize(c.ev_b));
@@ -4235,13 +3543,13 @@ int render_shard_impl(const rt_scene *scene, const rt_camera *camera, int width,
                 hipEvent_t e0, e1, e2, e3;
                 if (next_event(&e0) || next_event(&e1) || next_event(&e2) || next_event(&e3)) return 1;
                 HIP_TRY(hipEventRecord(e0, st));
-                hipLaunchKernelGGL(advance, grid, block, 0, st, sc, c.pools, cam, ap, d_sum, c.d_ctr, c.d_rows, c.d_lock);
+                launch_advance();
                 HIP_TRY(hipEventRecord(e1, st));
                 hipLaunchKernelGGL(trace, grid_trace, block, lds_bytes, st, sc, c.pools, tpp, stack_cap, d_over);
                 HIP_TRY(hipEventRecord(e2, st));
                 HIP_TRY(hipEventRecord(e3, st));
             } else {
-                hipLaunchKernelGGL(advance, grid, block, 0, st, sc, c.pools, cam, ap, d_sum, c.d_ctr, c.d_rows, c.d_lock);
+                launch_advance();
                 hipLaunchKernelGGL(trace, grid_trace, block, lds_bytes, st, sc, c.pools, tpp, stack_cap, d_over);
             }
             rounds++;
@@ -4283,7 +3591,7 @@ int render_shard_impl(const rt_scene *scene, const rt_camera *camera, int width,
             for (int j = lock_enqueued; j < hi; j++) {
                 ap.round = (int)((rounds + j) & 0x3fffffff);
                 ap.lockstep = 1 + j;
-                hipLaunchKernelGGL(advance, grid, block, 0, st, sc, c.pools, cam, ap, d_sum, c.d_ctr, c.d_rows, c.d_lock);
+                launch_advance();
                 tpp.lock_shades = c.d_lock;
                 tpp.lock_round = j;
                 hipLaunchKernelGGL(trace, grid_trace, block, lds_bytes, st, sc, c.pools, tpp, stack_cap, d_over);
@@ -4563,6 +3871,60 @@ static int query_impl(const rt_scene *scene, uint32_t flags, int n, const float 
     return 0;
 }
 
+// rt_render_rays_device / rt_render_rays_fixed_device: host-side argument checks, the table's validation on the device
+// (k_query_prepass for directions and origin radius, k_pixel_prepass for the pixel indices; nothing is written before both
+// have passed), then the frame through render_shard_impl.  The prepass borrows the scene's query scratch under its lock.
+static int render_rays_impl(const rt_scene *scene, int64_t n_rays, const float *d_o, const float *d_d, const int32_t *d_pixel,
+                            int rays_per_pixel, int n_pixels, int max_bounces, uint64_t seed, uint32_t flags, float *d_sum,
+                            hipStream_t st, rt_stats *stats) {
+    const std::string w((flags & kFlagFixedFb) ? "rt_render_rays_fixed_device" : "rt_render_rays_device");
+    if (!scene) return fail(w + ": null scene");
+    if (!d_o || !d_d || !d_sum) return fail(w + ": null " + (!d_o ? "d_origin_xyz" : !d_d ? "d_dir_xyz" : "sum buffer"));
+    if (flags & RT_FLAG_REFERENCE_WALK) return fail(w + ": RT_FLAG_REFERENCE_WALK is not supported for ray tables");
+    if (flags & RT_FLAG_RNG_PER_SAMPLE) return fail(w + ": RT_FLAG_RNG_PER_SAMPLE is not supported for ray tables");
+    if (flags & ~(uint32_t)(RT_FLAG_WATERTIGHT | RT_FLAG_TIME_KERNELS | kFlagFixedFb)) return fail(w + ": flags other than RT_FLAG_WATERTIGHT / RT_FLAG_TIME_KERNELS");
+    if (n_rays < 1) return fail(w + ": n_rays = " + std::to_string((long long)n_rays) + " (at least 1)");
+    if (n_rays + 13LL * kW >= (1LL << 31)) return fail(w + ": n_rays exceeds the reference's int32 camera-ray range");
+    if (n_pixels < 1 || n_pixels > 0x7fffffff / 3) return fail(w + ": n_pixels = " + std::to_string(n_pixels) + " is outside 1 .. 715827882");
+    if (max_bounces < 0 || max_bounces > (1 << 24)) return fail(w + ": max_bounces is outside 0 .. 16777216");
+    if (!d_pixel) {
+        if (rays_per_pixel < 1) return fail(w + ": rays_per_pixel = " + std::to_string(rays_per_pixel) + " (at least 1 when d_pixel is null)");
+        if ((n_rays - 1) / rays_per_pixel >= n_pixels)
+            return fail(w + ": ray " + std::to_string((long long)(n_rays - 1)) + " falls on pixel " + std::to_string((long long)((n_rays - 1) / rays_per_pixel)) +
+                        " of " + std::to_string(n_pixels));
+    }
+    DeviceGuard dev;
+    if (dev.enter(scene->device)) return 1;
+    const int n = (int)n_rays;
+    {
+        rt_scene::QueryState &q = scene->query;
+        std::lock_guard<std::mutex> lock(q.mutex);
+        if (!q.d_words) {  // (as the first query of this scene)
+            HIP_TRY(hipDeviceGetAttribute(&q.cus, hipDeviceAttributeMultiprocessorCount, scene->device));
+            HIP_TRY(hipHostMalloc((void **)&q.h_words, sizeof(QueryWords), hipHostMallocDefault));
+            HIP_TRY(hipMalloc((void **)&q.d_words, sizeof(QueryWords)));
+        }
+        const dim3 grid(std::min((n + kBlock - 1) / kBlock, 8 * std::max(q.cus, 1)));
+        HIP_TRY(hipMemsetAsync(q.d_words, 0, sizeof(QueryWords), st));
+        hipLaunchKernelGGL(k_query_prepass, grid, dim3(kBlock), 0, st, d_o, d_d, n, q.d_words);
+        if (d_pixel) hipLaunchKernelGGL(k_pixel_prepass, grid, dim3(kBlock), 0, st, d_pixel, n, n_pixels, q.d_words);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(q.h_words, q.d_words, 6 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (q.h_words->bad_dirs != 0)
+            return fail(w + ": " + std::to_string(q.h_words->bad_dirs) + " of " + std::to_string(n) + " directions are not finite or reach 2^126");
+        if (q.h_words->bad_pixels != 0)
+            return fail(w + ": " + std::to_string(q.h_words->bad_pixels) + " of " + std::to_string(n) + " pixel indices are outside 0 .. " + std::to_string(n_pixels - 1));
+        float need[3];
+        memcpy(need, q.h_words->radius_bits, sizeof(need));
+        if (int rc = ensure_origin_radius(scene, need)) return rc;
+    }
+    RayFrame rays;
+    rays.table = RayTable{d_o, d_d, d_pixel};
+    rays.n_rays = n_rays;
+    return render_shard_impl(scene, nullptr, n_pixels, 1, d_pixel ? 1 : rays_per_pixel, max_bounces, seed, 0, 1, flags, d_sum, st, stats, 0, &rays);
+}
+
 }  // namespace
 
 // ============================================================================ C-ABI
@@ -4779,6 +4141,22 @@ int rt_render_shard_fixed(const rt_scene *scene, const rt_camera *camera, int wi
                           int64_t *d_sum_fixed, void *stream, rt_stats *stats) {
     return render_overlapped(scene, camera, width, height, num_samples, max_bounces, seed, shard_index, shard_count,
                              (flags & ~kFlagFixedFb) | kFlagFixedFb, (float *)d_sum_fixed, (hipStream_t)stream, stats);
+}
+
+int rt_render_rays_device(const rt_scene *scene, int64_t n_rays, const float *d_origin_xyz, const float *d_dir_xyz, const int32_t *d_pixel,
+                          int rays_per_pixel, int n_pixels, int max_bounces, uint64_t seed, uint32_t flags, float *d_sum_rgb, void *stream,
+                          rt_stats *stats) {
+    if (flags & kFlagFixedFb) return fail("rt_render_rays_device: unknown flag 0x200");
+    return render_rays_impl(scene, n_rays, d_origin_xyz, d_dir_xyz, d_pixel, rays_per_pixel, n_pixels, max_bounces, seed, flags, d_sum_rgb,
+                            (hipStream_t)stream, stats);
+}
+
+int rt_render_rays_fixed_device(const rt_scene *scene, int64_t n_rays, const float *d_origin_xyz, const float *d_dir_xyz,
+                                const int32_t *d_pixel, int rays_per_pixel, int n_pixels, int max_bounces, uint64_t seed, uint32_t flags,
+                                int64_t *d_sum_fixed, void *stream, rt_stats *stats) {
+    if (flags & kFlagFixedFb) return fail("rt_render_rays_fixed_device: unknown flag 0x200");
+    return render_rays_impl(scene, n_rays, d_origin_xyz, d_dir_xyz, d_pixel, rays_per_pixel, n_pixels, max_bounces, seed, flags | kFlagFixedFb,
+                            (float *)d_sum_fixed, (hipStream_t)stream, stats);
 }
 
 int rt_post_process_fixed(const int64_t *d_sum_fixed, float *d_rgb_out, int num_pixels, int num_samples, void *stream) {
