@@ -246,16 +246,26 @@ struct Camera {
 };
 
 namespace rtcuda_detail {
-inline rt_scene *realise(const Scene &scene) {
-    SceneHandle &sh = *scene.bvh.handle;
-    if (sh.h && sh.lights_key == scene.d_lights && sh.num_lights_key == scene.num_lights) return sh.h;
-    if (sh.h) { rt_scene_destroy(sh.h); sh.h = nullptr; }
-    const Bvh &bvh = scene.bvh;
-    const int n = bvh.num_primitives;
-    std::vector<float> verts((size_t)9 * (n > 0 ? n : 1));
-    std::vector<int32_t> tri_mat(n > 0 ? n : 1), tri_light(n > 0 ? n : 1);
-    std::vector<const Material *> mat_ptrs;
+// The flat arrays of rt_scene_create from the host description: vertices, per-triangle material and light indices (materials
+// numbered in the order the primitives first name them), the material table and the lights.
+struct FlatScene {
+    std::vector<float> verts;
+    std::vector<int32_t> tri_mat, tri_light;
     std::vector<rt_material> mats;
+    std::vector<rt_light> lights;
+    int n = 0;
+};
+inline FlatScene flatten(const Scene &scene) {
+    FlatScene f;
+    const Bvh &bvh = scene.bvh;
+    const int n = f.n = bvh.num_primitives;
+    f.verts.resize((size_t)9 * (n > 0 ? n : 1));
+    f.tri_mat.resize(n > 0 ? n : 1);
+    f.tri_light.resize(n > 0 ? n : 1);
+    std::vector<float> &verts = f.verts;
+    std::vector<int32_t> &tri_mat = f.tri_mat, &tri_light = f.tri_light;
+    std::vector<const Material *> mat_ptrs;
+    std::vector<rt_material> &mats = f.mats;
     // primitives may come in any order: primitive i describes triangle (d_triangle - base)
     for (int i = 0; i < n; i++) {
         const Primitive &pr = bvh.primitives[i];
@@ -283,7 +293,8 @@ inline rt_scene *realise(const Scene &scene) {
         if (pr.d_area_light && (li < 0 || li >= scene.num_lights)) throw std::runtime_error("render: Primitive::d_area_light does not point into Scene::d_lights");
         tri_light[ti] = (int32_t)li;
     }
-    std::vector<rt_light> lights(scene.num_lights > 0 ? scene.num_lights : 1);
+    std::vector<rt_light> &lights = f.lights;
+    lights.resize(scene.num_lights > 0 ? scene.num_lights : 1);
     for (int k = 0; k < scene.num_lights; k++) {
         const Light &l = scene.d_lights[k];
         rt_light &o = lights[k];
@@ -297,8 +308,15 @@ inline rt_scene *realise(const Scene &scene) {
             o.triangle = (int32_t)ti;
         }
     }
-    check(rt_scene_create(verts.data(), n, tri_mat.data(), tri_light.data(), mats.data(), (int)mats.size(),
-                          lights.data(), scene.num_lights, &sh.h), "rt_scene_create");
+    return f;
+}
+inline rt_scene *realise(const Scene &scene) {
+    SceneHandle &sh = *scene.bvh.handle;
+    if (sh.h && sh.lights_key == scene.d_lights && sh.num_lights_key == scene.num_lights) return sh.h;
+    if (sh.h) { rt_scene_destroy(sh.h); sh.h = nullptr; }
+    FlatScene f = flatten(scene);
+    check(rt_scene_create(f.verts.data(), f.n, f.tri_mat.data(), f.tri_light.data(), f.mats.data(), (int)f.mats.size(),
+                          f.lights.data(), scene.num_lights, &sh.h), "rt_scene_create");
     sh.lights_key = scene.d_lights;
     sh.num_lights_key = scene.num_lights;
     return sh.h;
@@ -350,6 +368,77 @@ inline void rebuild(Scene &scene, const std::vector<Triangle> &triangles) {
         q[6] = t.p2_.x; q[7] = t.p2_.y; q[8] = t.p2_.z;
     }
     rtcuda_detail::check(rt_scene_rebuild(sh->h, verts.data(), n), "rebuild");
+}
+
+// Editing a scene in place (no reference counterpart: its Scene is assembled once) -- rt_scene_set_materials,
+// rt_scene_set_lights, rt_scene_set_triangles*, rt_scene_create_device, which document the contract (the bits of a scene
+// created anew from the same arrays) and the errors.  The host description is the source: change it, then call the matching
+// function; a scene not yet realised on the device simply takes the change when prepare() / render() first builds it.
+//
+// set_materials: the VALUES of the Materials the primitives point to have changed (which Material a primitive points to is
+// part of the triangle set: set_triangles).  The tree is kept.
+inline void set_materials(Scene &scene) {
+    rtcuda_detail::SceneHandle *sh = scene.bvh.handle.get();
+    if (!sh || !sh->h) return;
+    rtcuda_detail::FlatScene f = rtcuda_detail::flatten(scene);
+    rtcuda_detail::check(rt_scene_set_materials(sh->h, f.mats.data(), (int)f.mats.size()), "set_materials");
+}
+// set_lights: new lights for the scene (Scene::d_lights / num_lights take them) and the primitives' d_area_light as they
+// point into them now.  The tree is kept.
+inline void set_lights(Scene &scene, Light *d_lights, int num_lights) {
+    scene.d_lights = d_lights;
+    scene.num_lights = num_lights;
+    rtcuda_detail::SceneHandle *sh = scene.bvh.handle.get();
+    if (!sh || !sh->h) return;
+    rtcuda_detail::FlatScene f = rtcuda_detail::flatten(scene);
+    rtcuda_detail::check(rt_scene_set_lights(sh->h, f.lights.data(), num_lights, f.tri_light.data()), "set_lights");
+    sh->lights_key = d_lights;
+    sh->num_lights_key = num_lights;
+}
+// set_triangles: a new Bvh (any number of triangles >= 1) and new lights for it; the device scene, if there is one, is
+// kept and takes the new set (the tree is built on the device).
+inline void set_triangles(Scene &scene, const std::vector<Triangle> &triangles, const std::vector<Primitive> &primitives,
+                          Light *d_lights, int num_lights) {
+    std::shared_ptr<rtcuda_detail::SceneHandle> handle = scene.bvh.handle;
+    Scene next{Bvh(triangles, primitives), num_lights, d_lights};
+    // (the caller's primitives and lights point into the caller's triangle vector: the copy is addressed from its base)
+    next.bvh.triangle_base = triangles.empty() ? nullptr : &triangles[0];
+    if (handle && handle->h) {
+        rtcuda_detail::FlatScene f = rtcuda_detail::flatten(next);
+        rtcuda_detail::check(rt_scene_set_triangles(handle->h, f.verts.data(), f.n, f.tri_mat.data(), f.tri_light.data(), f.mats.data(),
+                                                    (int)f.mats.size(), f.lights.data(), num_lights), "set_triangles");
+        handle->lights_key = d_lights;
+        handle->num_lights_key = num_lights;
+        next.bvh.handle = handle;
+    }
+    scene = next;
+}
+// The device forms take the flat arrays of the C-ABI: the three per-triangle arrays are DEVICE buffers on the scene's device,
+// ordered on `stream` (a hipStream_t; nullptr = default stream), materials and lights host arrays.  The Bvh's host triangles
+// then no longer describe the device scene (only Bvh::num_primitives follows); a Scene without a Bvh fails with the library's
+// message.
+inline void set_triangles_device(Scene &scene, const float *d_tri_p0p1p2, int n_tris, const int32_t *d_tri_material,
+                                 const int32_t *d_tri_light, const rt_material *materials, int n_materials, const rt_light *lights,
+                                 int n_lights, void *stream = nullptr) {
+    rt_scene *h = scene.bvh.handle ? rtcuda_detail::realise(scene) : nullptr;
+    rtcuda_detail::check(rt_scene_set_triangles_device(h, d_tri_p0p1p2, n_tris, d_tri_material, d_tri_light, materials, n_materials,
+                                                       lights, n_lights, stream), "set_triangles_device");
+    scene.bvh.num_primitives = n_tris;
+}
+// A Scene that exists on the device only (rt_scene_create_device): render(), the queries and set_triangles_device take it.
+inline Scene create_scene_device(const float *d_tri_p0p1p2, int n_tris, const int32_t *d_tri_material, const int32_t *d_tri_light,
+                                 const rt_material *materials, int n_materials, const rt_light *lights, int n_lights,
+                                 void *stream = nullptr) {
+    Scene scene{};
+    scene.bvh.handle = std::make_shared<rtcuda_detail::SceneHandle>();
+    rtcuda_detail::check(rt_scene_create_device(d_tri_p0p1p2, n_tris, d_tri_material, d_tri_light, materials, n_materials, lights,
+                                                n_lights, stream, &scene.bvh.handle->h), "create_scene_device");
+    scene.bvh.num_primitives = n_tris;
+    scene.num_lights = n_lights;
+    scene.d_lights = nullptr;
+    scene.bvh.handle->lights_key = nullptr;
+    scene.bvh.handle->num_lights_key = n_lights;
+    return scene;
 }
 
 // Ray queries (no reference counterpart): n rays from DEVICE buffers on the scene's device, ordered on `stream` (a hipStream_t;

@@ -157,7 +157,8 @@ int rt_scene_info(const rt_scene *scene, int64_t out[4]);
 int rt_scene_build_info(const rt_scene *scene, int *builder, double *seconds);
 
 /* ---- moving geometry (no reference counterpart: its Bvh is built once, bvh.cuh:30-219) ----------------------------
- * New positions for the scene's triangles: n_tris x 9 floats, the caller's ORIGINAL order, same count as at creation.
+ * New positions for the scene's triangles: n_tris x 9 floats, the caller's ORIGINAL order, the scene's count (that of its
+ * creation or of its last rt_scene_set_triangles*).
  * Materials, light assignment and topology are kept.  The BVH is refit on the scene's device (same tree, new boxes);
  * triangle, shading and light-triangle records are recomputed.  No render of this scene may be in flight.
  * The image is that of a scene created anew from the same vertices, bit for bit, in every mode (hits never depend on the
@@ -175,7 +176,7 @@ int rt_scene_refit_info(const rt_scene *scene, int64_t *refits, double *seconds_
 /* A new tree for the scene, built on its device by the RT_SCENE_DEVICE_BVH builder: from the scene's current vertices
  * (tri_p0p1p2 NULL) or from new ones (as rt_scene_update takes them).  When to call it: a refit keeps the tree's topology,
  * so as vertices move its quality decays -- rebuild when rt_scene_refit_info's sah_ratio has grown (say past 1.2); the
- * ratio reads 1.0 again afterwards.  Preconditions are rt_scene_update's: the creation count, a 4-wide scene, no render in
+ * ratio reads 1.0 again afterwards.  Preconditions are rt_scene_update's: the scene's count, a 4-wide scene, no render in
  * flight.  The image is unchanged, bit for bit, in every mode: it is that of a scene created from the same vertices.  The
  * leaf order changes; triangle, shading, light and table records are re-emitted on the device.  The reference's tree
  * (RT_FLAG_REFERENCE_WALK, default mode) is kept when the vertices did not change and rebuilt by the next render that needs
@@ -186,6 +187,49 @@ int rt_scene_rebuild(rt_scene *scene, const float *tri_p0p1p2, int n_tris);
 /* Same, from a DEVICE buffer on the scene's device (or NULL: the current vertices), ordered on `stream` (NULL = default
  * stream), synchronous on return. */
 int rt_scene_rebuild_device(rt_scene *scene, const float *d_tri_p0p1p2, int n_tris, void *stream);
+
+/* ---- editing a scene in place (no reference counterpart: its Scene is assembled once, main.cu:119-137) -------------
+ * What a scene IS may change between frames without rt_scene_destroy + rt_scene_create: its material table, its lights and
+ * its whole triangle set.  THE CONTRACT, for all five entry points: afterwards every render, query and ray-table render of
+ * the scene gives, bit for bit and in every mode, what a scene created by rt_scene_create from the same arrays gives.
+ * Preconditions are rt_scene_rebuild's: no render or query of the scene in flight; the calling thread's current device is
+ * left as it was.  The checks are rt_scene_create's (counts, index ranges, material and light types, an area light's
+ * triangle within the triangle count, at most 65535 materials and 32766 lights, fewer than 2^24 triangles).  Every error
+ * returns non-zero, names the entry point in rt_last_error() and leaves the scene rendering its old bits: new records are
+ * built in fresh buffers and adopted at the end.  After an edit rt_scene_update* / rt_scene_rebuild* take the NEW count.
+ *
+ * rt_scene_set_materials: a new material table (HOST array, any count >= 1 that covers every index the triangles name).
+ * rt_scene_set_lights: new lights (HOST array, n_lights may be 0) and, unless tri_light is NULL, a new light assignment of
+ *   the triangles (HOST array of the scene's triangle count, -1 = none).  With NULL the assignment is kept and must fit
+ *   the new count.
+ * Both keep the tree, the leaf order, rt_scene_build_info, the refit state and the reference's tree (none depends on
+ * materials or lights): they cost table uploads and one or two small launches whatever the triangle count.  The shading
+ * tables are re-made for the new counts, so the next render stages them in LDS or reads them from memory as the counts
+ * allow; rt_render_multi replicas are dropped. */
+int rt_scene_set_materials(rt_scene *scene, const rt_material *materials, int n_materials);
+int rt_scene_set_lights(rt_scene *scene, const rt_light *lights, int n_lights, const int32_t *tri_light);
+/* A new triangle set: any count >= 1, with the per-triangle indices and the tables they index into (all of
+ * rt_scene_create's arguments; materials and lights are HOST arrays in every form, tri_light may be NULL = no area lights).
+ * The tree is built on the scene's device by the RT_SCENE_DEVICE_BVH builder and every record is re-emitted there, as
+ * rt_scene_rebuild does for moved vertices, with every array re-allocated for the new count.  rt_scene_info follows,
+ * rt_scene_build_info reports builder 2 and the device build time, rt_scene_refit_info keeps its refit count and reads
+ * ratio 1.0; the reference's tree is rebuilt by the next render that needs it, replicas are dropped.  Needs a 4-wide scene.
+ * An empty scene stays with rt_scene_create. */
+int rt_scene_set_triangles(rt_scene *scene, const float *tri_p0p1p2, int n_tris, const int32_t *tri_material,
+                           const int32_t *tri_light, const rt_material *materials, int n_materials,
+                           const rt_light *lights, int n_lights);
+/* Same, the three per-triangle arrays from DEVICE buffers on the scene's device (a host pointer is an error), ordered on
+ * `stream` (NULL = default stream), synchronous on return.  The index ranges are checked on the device before anything is
+ * adopted; the error names how many triangles are out of range.  The library's host mirrors (reference tree, replicas) are
+ * filled by one device-to-host copy per array. */
+int rt_scene_set_triangles_device(rt_scene *scene, const float *d_tri_p0p1p2, int n_tris, const int32_t *d_tri_material,
+                                  const int32_t *d_tri_light, const rt_material *materials, int n_materials,
+                                  const rt_light *lights, int n_lights, void *stream);
+/* rt_scene_create_flags(RT_SCENE_DEVICE_BVH) from DEVICE buffers on the current device: no host copy of the triangles is
+ * needed to make a scene.  n_tris >= 1; `stream` as above. */
+int rt_scene_create_device(const float *d_tri_p0p1p2, int n_tris, const int32_t *d_tri_material,
+                           const int32_t *d_tri_light, const rt_material *materials, int n_materials,
+                           const rt_light *lights, int n_lights, void *stream, rt_scene **out_scene);
 
 /* Replaces Camera::Camera(lookfrom, lookat, up, vfov_deg, aspect) (camera.cuh:15-29). Host only. */
 int rt_camera_make(const float lookfrom[3], const float lookat[3], const float up[3], float vfov_deg,

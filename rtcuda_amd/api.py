@@ -9,6 +9,7 @@ library.  Nothing here computes pixels: every call goes to the HIP library and r
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 import os
 import subprocess
 
@@ -30,7 +31,8 @@ FLAG_WATERTIGHT = 16     # the triangle-list definition (no hit lost to a box te
 
 EXPORTS = [
     "rt_scene_create", "rt_scene_destroy", "rt_scene_info", "rt_scene_build_info", "rt_scene_update", "rt_scene_update_device",
-    "rt_scene_refit_info", "rt_scene_create_flags", "rt_scene_rebuild", "rt_scene_rebuild_device", "rt_camera_make", "rt_render", "rt_render_multi",
+    "rt_scene_refit_info", "rt_scene_create_flags", "rt_scene_rebuild", "rt_scene_rebuild_device", "rt_scene_set_materials",
+    "rt_scene_set_lights", "rt_scene_set_triangles", "rt_scene_set_triangles_device", "rt_scene_create_device", "rt_camera_make", "rt_render", "rt_render_multi",
     "rt_render_shard", "rt_render_shard_fixed", "rt_render_rays_device", "rt_render_rays_fixed_device", "rt_post_process", "rt_post_process_fixed", "rt_trace_closest", "rt_trace_any",
     "rt_trace_closest_flags", "rt_trace_any_flags", "rt_query_closest_device", "rt_query_any_device", "rt_query_last_counters",
     "rt_xorwow_states", "rt_shutdown", "rt_peer_access_log", "rt_last_error", "rt_version", "rt_build_id",
@@ -132,6 +134,11 @@ def _bind(L):
     L.rt_scene_create_flags.argtypes = [vp, ci, vp, vp, vp, ci, vp, ci, ctypes.c_uint32, ctypes.POINTER(vp)]
     L.rt_scene_rebuild.argtypes = [vp, vp, ci]
     L.rt_scene_rebuild_device.argtypes = [vp, vp, ci, vp]
+    L.rt_scene_set_materials.argtypes = [vp, vp, ci]
+    L.rt_scene_set_lights.argtypes = [vp, vp, ci, vp]
+    L.rt_scene_set_triangles.argtypes = [vp, vp, ci, vp, vp, vp, ci, vp, ci]
+    L.rt_scene_set_triangles_device.argtypes = [vp, vp, ci, vp, vp, vp, ci, vp, ci, vp]
+    L.rt_scene_create_device.argtypes = [vp, ci, vp, vp, vp, ci, vp, ci, vp, ctypes.POINTER(vp)]
     L.rt_camera_make.argtypes = [vp, vp, vp, cf, cf, vp]
     L.rt_render.argtypes = [vp, vp, ci, ci, ci, ci, ctypes.c_uint64, ctypes.c_uint32, vp, ctypes.POINTER(RtStats)]
     L.rt_render_multi.argtypes = [vp, vp, ci, ci, ci, ci, ctypes.c_uint64, ctypes.c_uint32, vp, ci, vp, ctypes.POINTER(RtStats)]
@@ -253,6 +260,116 @@ class Scene:
         return {"pairs": int(out[0]), "tris": int(out[1]), "max_depth": int(out[2]), "leaves": int(out[3]),
                 "builder": {0: "sah", 2: "ploc"}.get(b.value, str(b.value)), "build_seconds": sec.value}
 
+    def n_tris(self) -> int:
+        """The scene's current triangle count, from the library (rt_scene_info): it follows set_triangles*()."""
+        out = np.zeros(4, np.int64)
+        _check(self.L.rt_scene_info(self.h, _p(out)), "rt_scene_info", self.L)
+        return int(out[1])
+
+    # ---- editing in place: materials, lights, a new triangle set (rt_scene_set_*).  Renders and queries afterwards are
+    # bit-equal to those of a scene created from the same arrays; an RtError leaves the scene as it was.
+    @staticmethod
+    def _tables(materials, lights):
+        mats = np.ascontiguousarray(materials)
+        lights = np.ascontiguousarray(lights)
+        if mats.dtype.itemsize != 20 or lights.dtype.itemsize != 32:
+            raise RtError("materials / lights must be arrays of scenes.MATERIAL_DTYPE / scenes.LIGHT_DTYPE records (20 / 32 bytes)")
+        return mats, lights
+
+    def set_materials(self, materials) -> None:
+        """A new material table (records as in SceneArrays.materials; any count that covers the triangles' indices).  The tree
+        and everything in leaf order stay: the cost is a table upload and one small launch."""
+        mats, _ = self._tables(materials, self.arrays.lights if self.arrays is not None else np.zeros(0, "V32"))
+        _check(self.L.rt_scene_set_materials(self.h, _p(mats), mats.shape[0]), "rt_scene_set_materials", self.L)
+        if self.arrays is not None:
+            self.arrays = dataclasses.replace(self.arrays, materials=mats)
+
+    def set_lights(self, lights, tri_light=None) -> None:
+        """New lights and, unless tri_light is None, a new light assignment of the triangles ((n,) int32, -1 = none)."""
+        _, lights = self._tables(np.zeros(0, "V20"), lights)
+        tl = None if tri_light is None else np.ascontiguousarray(tri_light, np.int32)
+        if tl is not None and tl.shape != (self.n_tris(),):
+            raise RtError(f"set_lights: tri_light must have shape ({self.n_tris()},), it has {tl.shape}")
+        _check(self.L.rt_scene_set_lights(self.h, _p(lights), lights.shape[0], _p(tl)), "rt_scene_set_lights", self.L)
+        if self.arrays is not None:
+            self.arrays = dataclasses.replace(self.arrays, lights=lights, **({} if tl is None else {"tri_light": tl}))
+
+    def set_triangles(self, arrays: SceneArrays) -> None:
+        """A whole new scene description in place (any triangle count >= 1): the tree is built on the device."""
+        tris = np.ascontiguousarray(arrays.tris, np.float32).reshape(-1, 9)
+        tm = np.ascontiguousarray(arrays.tri_material, np.int32)
+        tl = np.ascontiguousarray(arrays.tri_light, np.int32)
+        mats, lights = self._tables(arrays.materials, arrays.lights)
+        if tm.shape != (tris.shape[0],) or tl.shape != (tris.shape[0],):
+            raise RtError(f"set_triangles: {tris.shape[0]} triangles, tri_material {tm.shape}, tri_light {tl.shape}")
+        _check(self.L.rt_scene_set_triangles(self.h, _p(tris), tris.shape[0], _p(tm), _p(tl), _p(mats), mats.shape[0], _p(lights),
+                                             lights.shape[0]), "rt_scene_set_triangles", self.L)
+        self.arrays = arrays
+
+    @staticmethod
+    def _triangle_tensors(what, tris, tri_material, tri_light):
+        """The checks of set_triangles_tensors / from_tensors, in the manner of _query_rays: contiguous CUDA tensors on one
+        GPU, (n, 9) or (n, 3, 3) float32 and (n,) int32 (tri_light may be None).  Nothing is converted or copied."""
+        import torch
+        n, device = None, None
+        for name, x, dtype in (("tris", tris, torch.float32), ("tri_material", tri_material, torch.int32),
+                               ("tri_light", tri_light, torch.int32)):
+            if x is None and name == "tri_light":
+                continue  # (optional: no area lights)
+            if not isinstance(x, torch.Tensor):
+                raise RtError(f"{what}: {name} must be a torch tensor, it is a {type(x).__name__}")
+            if not x.is_cuda:
+                raise RtError(f"{what}: {name} must be on the scene's GPU, it is on {x.device}")
+            if x.dtype != dtype:
+                raise RtError(f"{what}: {name} must be {dtype}, it is {x.dtype}")
+            if name == "tris":
+                if x.dim() not in (2, 3) or tuple(x.shape[1:]) not in ((9,), (3, 3)):
+                    raise RtError(f"{what}: tris must have shape (n, 9) or (n, 3, 3), it has {tuple(x.shape)}")
+                n = x.shape[0]
+            elif tuple(x.shape) != (n,):
+                raise RtError(f"{what}: {name} must have shape ({n},), it has {tuple(x.shape)}")
+            if not x.is_contiguous():
+                raise RtError(f"{what}: {name} must be contiguous")
+            device = x.device if device is None else device
+            if x.device != device:
+                raise RtError(f"{what}: {name} is on {x.device}, tris are on {device}")
+        return n, device
+
+    def set_triangles_tensors(self, tris, tri_material, tri_light, materials, lights) -> None:
+        """set_triangles() from torch tensors on the scene's device (tris (n, 9) or (n, 3, 3) float32; tri_material and
+        tri_light (n,) int32, tri_light may be None), ordered on ``torch.cuda.current_stream()``; materials and lights are
+        host record arrays.  The index ranges are checked on the device.  ``self.arrays`` no longer describes the scene
+        afterwards and is set to None."""
+        import torch
+        n, device = self._triangle_tensors("set_triangles_tensors", tris, tri_material, tri_light)
+        mats, lights = self._tables(materials, lights)
+        c = ctypes.c_void_p
+        _check(self.L.rt_scene_set_triangles_device(self.h, c(tris.data_ptr()), n, c(tri_material.data_ptr()),
+                                                    c(None if tri_light is None else tri_light.data_ptr()), _p(mats), mats.shape[0],
+                                                    _p(lights), lights.shape[0], c(torch.cuda.current_stream(device).cuda_stream or None)),
+               "rt_scene_set_triangles_device", self.L)
+        self.arrays = None
+
+    @classmethod
+    def from_tensors(cls, tris, tri_material, tri_light, materials, lights, library=None) -> "Scene":
+        """A scene made from torch tensors on the current device without a host copy of the triangles
+        (rt_scene_create_device: the device BVH builder); arguments as set_triangles_tensors()."""
+        import torch
+        n, device = cls._triangle_tensors("from_tensors", tris, tri_material, tri_light)
+        mats, lights = cls._tables(materials, lights)
+        self = cls.__new__(cls)
+        L = self.L = library or lib()
+        self.arrays = None
+        self.h = None
+        c, h = ctypes.c_void_p, ctypes.c_void_p()
+        with torch.cuda.device(device):
+            _check(L.rt_scene_create_device(c(tris.data_ptr()), n, c(tri_material.data_ptr()),
+                                            c(None if tri_light is None else tri_light.data_ptr()), _p(mats), mats.shape[0], _p(lights),
+                                            lights.shape[0], c(torch.cuda.current_stream(device).cuda_stream or None), ctypes.byref(h)),
+                   "rt_scene_create_device", L)
+        self.h = h
+        return self
+
     # ---- moving geometry: new vertex positions, same triangles, materials and lights (rt_scene_update)
     def update(self, tris) -> None:
         """New positions for every triangle ((n, 9) float32 p0 p1 p2, the creation order and count): the BVH is refit on the
@@ -263,7 +380,7 @@ class Scene:
     def update_device(self, ptr: int, stream: int = 0, n_tris: int = None) -> None:
         """The same from a DEVICE buffer of n_tris x 9 float32 on the scene's device (e.g. ``tensor.data_ptr()``), ordered
         on ``stream`` (0 = default stream; synchronous on return).  n_tris defaults to the scene's count."""
-        n = self.arrays.n_tris if n_tris is None else int(n_tris)
+        n = self.n_tris() if n_tris is None else int(n_tris)
         _check(self.L.rt_scene_update_device(self.h, ctypes.c_void_p(ptr), n, ctypes.c_void_p(stream)),
                "rt_scene_update_device", self.L)
 
@@ -273,7 +390,7 @@ class Scene:
         update() takes them).  Call it when refit_info()["sah_ratio"] has grown.  Renders afterwards are bit-equal to those
         of a scene created from the same vertices."""
         if tris is None:
-            _check(self.L.rt_scene_rebuild(self.h, None, self.arrays.n_tris), "rt_scene_rebuild", self.L)
+            _check(self.L.rt_scene_rebuild(self.h, None, self.n_tris()), "rt_scene_rebuild", self.L)
             return
         tris = np.ascontiguousarray(tris, np.float32).reshape(-1, 9)
         _check(self.L.rt_scene_rebuild(self.h, _p(tris), tris.shape[0]), "rt_scene_rebuild", self.L)
@@ -281,7 +398,7 @@ class Scene:
     def rebuild_device(self, ptr: int, stream: int = 0, n_tris: int = None) -> None:
         """The same from a DEVICE buffer of n_tris x 9 float32 on the scene's device (e.g. ``tensor.data_ptr()``; 0 = the
         current vertices), ordered on ``stream`` (0 = default stream; synchronous on return)."""
-        n = self.arrays.n_tris if n_tris is None else int(n_tris)
+        n = self.n_tris() if n_tris is None else int(n_tris)
         _check(self.L.rt_scene_rebuild_device(self.h, ctypes.c_void_p(ptr or None), n, ctypes.c_void_p(stream or None)),
                "rt_scene_rebuild_device", self.L)
 

@@ -2170,10 +2170,40 @@ __global__ void k_leaf_inverse(const int *__restrict__ order, int n, int *__rest
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k < n) inverse[order[k]] = k;
 }
-// (material, light) of every triangle in leaf order, from the caller's arrays in their order
-__global__ void k_leaf_tri_info(const int2 *__restrict__ caller_info, const int *__restrict__ order, int n, int2 *__restrict__ info) {
+// (material, light) of every triangle in leaf order, from the caller's two arrays in their order on the device (tri_light
+// null: no triangle carries a light)
+__global__ void k_leaf_tri_info(const int *__restrict__ tri_material, const int *__restrict__ tri_light, const int *__restrict__ order,
+                                int n, int2 *__restrict__ info) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k < n) info[k] = caller_info[order[k]];
+    if (k >= n) return;
+    const int i = order[k];
+    info[k] = make_int2(tri_material[i], tri_light ? tri_light[i] : -1);
+}
+// rt_scene_set_lights: a new light assignment in the caller's order, the materials as they are (already in leaf order)
+__global__ void k_leaf_tri_light(const int2 *__restrict__ old_info, const int *__restrict__ tri_light, const int *__restrict__ order,
+                                 int n, int2 *__restrict__ info) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < n) info[k] = make_int2(old_info[k].x, tri_light[order[k]]);
+}
+// rt_scene_set_triangles_device / rt_scene_create_device: one pass over the caller's index arrays before anything is built
+// from them (in the manner of k_query_prepass) -- how many triangles name a material outside [0, n_mats) (words[0]) or a
+// light outside [-1, n_lights) (words[1]; tri_light may be null).  One atomic per wave and word after a wave reduction.
+__global__ void __launch_bounds__(kBlock) k_index_prepass(const int *__restrict__ tri_material, const int *__restrict__ tri_light, int n,
+                                                          int n_mats, int n_lights, unsigned *__restrict__ words) {
+    unsigned bad_m = 0, bad_l = 0;
+    const size_t stride = (size_t)gridDim.x * kBlock;
+    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < (size_t)n; i += stride) {
+        bad_m += (unsigned)tri_material[i] >= (unsigned)n_mats ? 1u : 0u;
+        if (tri_light) bad_l += (unsigned)tri_light[i] + 1u >= (unsigned)n_lights + 1u ? 1u : 0u;  // (-1 wraps to 0: no light)
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        bad_m += __shfl_xor(bad_m, off);
+        bad_l += __shfl_xor(bad_l, off);
+    }
+    if (lane_id() == 0) {
+        if (bad_m) atomicAdd(&words[0], bad_m);
+        if (bad_l) atomicAdd(&words[1], bad_l);
+    }
 }
 // area lights name their triangle in the caller's order (rt_light.triangle): the leaf-order index the kernels read
 __global__ void k_leaf_lights(Light *__restrict__ lights, int n_lights, const int *__restrict__ inverse) {
@@ -2308,6 +2338,13 @@ struct rt_scene {
         d_refit_nodes = nullptr;
         d_refit_exact = nullptr;
         refit_level_end.clear();
+    }
+    // the largest material and light index a triangle names (-1: none), for rt_scene_set_materials / rt_scene_set_lights
+    int max_tri_material = -1, max_tri_light = -1;
+    void note_index_maxima() {
+        max_tri_material = max_tri_light = -1;
+        for (int32_t m : h_tri_material) max_tri_material = std::max(max_tri_material, (int)m);
+        for (int32_t l : h_tri_light) max_tri_light = std::max(max_tri_light, (int)l);
     }
     void set_order(const std::vector<int32_t> &order) {
         h_order.assign(order.begin(), order.end());
@@ -2549,6 +2586,42 @@ int ensure_ref_tree(const rt_scene *scene, bool *built = nullptr) {
     return 0;
 }
 
+// The argument checks of rt_scene_create, shared with the entry points that edit a scene (`w`: whose message it is):
+// the counts and the table pointers ...
+int check_scene_counts(const std::string &w, int n_tris, bool have_tri_arrays, const rt_material *materials, int n_materials,
+                       const rt_light *lights, int n_lights) {
+    if (n_tris < 0 || n_materials < 0 || n_lights < 0) return fail(w + ": negative count");
+    if (n_tris >= (1 << 24)) return fail(w + ": more than 2^24 - 1 triangles (24-bit triangle addressing)");
+    if (n_tris > 0 && !have_tri_arrays) return fail(w + ": null triangle arrays");
+    if (n_tris > 0 && (n_materials == 0 || !materials)) return fail(w + ": no materials");
+    if (n_lights > 0 && !lights) return fail(w + ": null lights");
+    if (n_materials > 65535 || n_lights > 32766) return fail(w + ": at most 65535 materials and 32766 lights");
+    return 0;
+}
+// ... the index ranges of the per-triangle HOST arrays (tri_light may be null; device arrays: k_index_prepass) ...
+int check_tri_indices(const std::string &w, int n_tris, const int32_t *tri_material, const int32_t *tri_light, int n_materials, int n_lights) {
+    for (int i = 0; i < n_tris; i++) {
+        if (tri_material && (tri_material[i] < 0 || tri_material[i] >= n_materials))
+            return fail(w + ": tri_material[" + std::to_string(i) + "] out of range");
+        if (tri_light && (tri_light[i] < -1 || tri_light[i] >= n_lights))
+            return fail(w + ": tri_light[" + std::to_string(i) + "] out of range");
+    }
+    return 0;
+}
+// ... and the tables themselves
+int check_scene_tables(const std::string &w, int n_tris, const rt_material *materials, int n_materials, const rt_light *lights, int n_lights) {
+    for (int i = 0; i < n_materials; i++)
+        if (materials[i].type < RT_MATTE || materials[i].type > RT_GLASS)
+            return fail(w + ": unknown material type");
+    for (int i = 0; i < n_lights; i++) {
+        if (lights[i].type != RT_POINT_LIGHT && lights[i].type != RT_AREA_LIGHT)
+            return fail(w + ": unknown light type");
+        if (lights[i].type == RT_AREA_LIGHT && (lights[i].triangle < 0 || lights[i].triangle >= n_tris))
+            return fail(w + ": area light triangle out of range");
+    }
+    return 0;
+}
+
 // Device temporaries and events of one host call: released on EVERY return path (HIP_TRY returns early on errors)
 struct DevScope {
     std::vector<void *> ptrs;
@@ -2614,38 +2687,41 @@ int ensure_origin_radius(const rt_scene *sc, const float need[3]) {
     return 0;
 }
 
+// What emit_scene reads besides the vertices: the counts, the material table on the device, the lights on the host and --
+// for a new leaf order -- the caller's per-triangle indices on the device, in the caller's order (tri_light null: -1
+// everywhere).  The scene's own (rt_scene_update, rt_scene_rebuild) or those it is about to adopt (rt_scene_set_*).
+struct EmitSource {
+    int n_tris = 0, n_mats = 0, n_lights = 0;
+    const Material *d_mats = nullptr;
+    const rt_light *h_lights = nullptr;
+    const int *d_tri_material = nullptr, *d_tri_light = nullptr;
+    const float *radius = nullptr;  // the origin radius the 4-wide nodes are padded for at least (3 floats)
+};
+
 // The one writer of the scene's leaf-order arrays, ordered on `st`, from the caller's vertices on the device (d_verts) and
 // the leaf order out.order: the triangle records (k_leaf_tris), the shading records and tables, and -- 4-wide -- the nodes
-// from out.recs, padded for the scene's origin radius (emit_nodes).  For a new leaf order `d_inverse` (n ints of scratch)
-// receives its inverse, and the triangles' (material, light) and the lights, their triangles renumbered, are written too, from
-// the scene's host copies.  Null for a refit: the leaf order is the scene's, and so are tri_info and the lights; the boxes of
+// from out.recs, padded for src.radius (emit_nodes).  For a new leaf order `d_inverse` (n ints of scratch) receives its
+// inverse, and the triangles' (material, light), from the two device arrays of `src`, and the lights, their triangles
+// renumbered, are written too.  Null for a refit: the leaf order is the scene's, and so are tri_info and the lights; the boxes of
 // the scene's records are refit to the vertices before they are padded (k_refit_level, one launch per level, deepest first;
-// launched after k_leaf_tris, which reads the same vertices: 5 us less per refit of the bunny than before it).  Temporaries go
-// to `tmp`.
-int emit_scene(const rt_scene *sc, const float *d_verts, const SceneArrays &out, int *d_inverse, hipStream_t st, DevScope &tmp) {
-    const int n = sc->n_tris, n_lights = sc->n_lights;
+// launched after k_leaf_tris, which reads the same vertices: 5 us less per refit of the bunny than before it).
+int emit_scene(const rt_scene *sc, const EmitSource &src, const float *d_verts, const SceneArrays &out, int *d_inverse, hipStream_t st) {
+    const int n = src.n_tris, n_lights = src.n_lights;
     const dim3 blk(256), grid((n + 255) / 256);
     if (d_inverse && n > 0) {
-        std::vector<int2> caller_info((size_t)n);
-        for (int i = 0; i < n; i++)
-            caller_info[(size_t)i] = make_int2(sc->h_tri_material[(size_t)i], sc->h_tri_light.empty() ? -1 : sc->h_tri_light[(size_t)i]);
-        int2 *d_caller_info = nullptr;
-        if (tmp.alloc(d_caller_info, (size_t)n)) return 1;
-        HIP_TRY(hipMemcpyAsync(d_caller_info, caller_info.data(), sizeof(int2) * (size_t)n, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipStreamSynchronize(st));  // (caller_info goes out of scope)
         hipLaunchKernelGGL(k_leaf_inverse, grid, blk, 0, st, out.order, n, d_inverse);
-        hipLaunchKernelGGL(k_leaf_tri_info, grid, blk, 0, st, d_caller_info, out.order, n, out.info);
+        hipLaunchKernelGGL(k_leaf_tri_info, grid, blk, 0, st, src.d_tri_material, src.d_tri_light, out.order, n, out.info);
     }
     if (d_inverse && n_lights > 0) {
-        HIP_TRY(hipMemcpyAsync(out.lights, sc->h_lights.data(), sizeof(Light) * (size_t)n_lights, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(out.lights, src.h_lights, sizeof(Light) * (size_t)n_lights, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(k_leaf_lights, dim3((n_lights + 255) / 256), blk, 0, st, out.lights, n_lights, d_inverse);
     }
     if (n > 0) {
         hipLaunchKernelGGL(k_leaf_tris, grid, blk, 0, st, d_verts, out.order, n, out.tris);
         hipLaunchKernelGGL(k_build_tri_shade, grid, blk, 0, st, out.tris, out.info, n, out.shade);
     }
-    const int nt = std::max(std::max(sc->n_mats, n_lights), 1);
-    hipLaunchKernelGGL(k_build_tables, dim3((nt + 63) / 64), dim3(64), 0, st, sc->d_mats, sc->n_mats, out.lights, n_lights, out.tris,
+    const int nt = std::max(std::max(src.n_mats, n_lights), 1);
+    hipLaunchKernelGGL(k_build_tables, dim3((nt + 63) / 64), dim3(64), 0, st, src.d_mats, src.n_mats, out.lights, n_lights, out.tris,
                        out.tables);
     if (!d_inverse)
         for (size_t l = 0; l < sc->refit_level_end.size(); l++) {
@@ -2653,8 +2729,30 @@ int emit_scene(const rt_scene *sc, const float *d_verts, const SceneArrays &out,
             hipLaunchKernelGGL(k_refit_level, dim3((count + 255) / 256), blk, 0, st, d_verts, sc->d_order, sc->d_refit_nodes + begin,
                                count, sc->d_recs, sc->d_refit_exact);
         }
-    if (sc->wide) emit_nodes(sc, out.recs, out.n_records, out.nodes, sc->origin_radius, st);
+    if (sc->wide) emit_nodes(sc, out.recs, out.n_records, out.nodes, src.radius, st);
     HIP_TRY(hipGetLastError());
+    return 0;
+}
+// The scene's own source.  For a new leaf order (`with_indices`) its per-triangle indices go to the device first, staged on
+// `st` into `tmp` from the host copies: every caller of emit_scene hands it device arrays, there is one emit path.
+int scene_source(const rt_scene *sc, bool with_indices, hipStream_t st, DevScope &tmp, EmitSource &src) {
+    src.n_tris = sc->n_tris;
+    src.n_mats = sc->n_mats;
+    src.n_lights = sc->n_lights;
+    src.d_mats = sc->d_mats;
+    src.h_lights = sc->h_lights.data();
+    src.radius = sc->origin_radius;
+    if (!with_indices || sc->n_tris < 1) return 0;
+    const size_t n = (size_t)sc->n_tris;
+    int *d_m = nullptr, *d_l = nullptr;
+    if (tmp.alloc(d_m, n)) return 1;
+    HIP_TRY(hipMemcpyAsync(d_m, sc->h_tri_material.data(), sizeof(int) * n, hipMemcpyHostToDevice, st));
+    if (!sc->h_tri_light.empty()) {
+        if (tmp.alloc(d_l, n)) return 1;
+        HIP_TRY(hipMemcpyAsync(d_l, sc->h_tri_light.data(), sizeof(int) * n, hipMemcpyHostToDevice, st));
+    }
+    src.d_tri_material = d_m;
+    src.d_tri_light = d_l;
     return 0;
 }
 
@@ -2763,7 +2861,9 @@ int scene_update_impl(rt_scene *sc, const float *verts, int n_tris, bool device_
         HIP_TRY(hipEventCreate(&tmp.e0));
         HIP_TRY(hipEventCreate(&tmp.e1));
         HIP_TRY(hipEventRecord(tmp.e0, st));
-        if (emit_scene(sc, d_verts, sc->arrays(), nullptr, st, tmp)) return 1;
+        EmitSource src;
+        if (scene_source(sc, false, st, tmp, src)) return 1;
+        if (emit_scene(sc, src, d_verts, sc->arrays(), nullptr, st)) return 1;
         HIP_TRY(hipEventRecord(tmp.e1, st));
         HIP_TRY(hipEventSynchronize(tmp.e1));
         float ms = 0.f;
@@ -2976,7 +3076,9 @@ int scene_rebuild_impl(rt_scene *sc, const float *verts, int n_tris, bool device
         fresh.alloc(a.tables, (size_t)std::max(sc->tab_dwords, 1)) || tmp.alloc(d_inverse, (size_t)n) ||
         (keep_ref && (fresh.alloc(d_ref_prims, (size_t)n) || fresh.alloc(d_ref_leaf_of, (size_t)n))))
         return 1;
-    if (emit_scene(sc, d_verts, a, d_inverse, st, tmp)) return 1;
+    EmitSource src;
+    if (scene_source(sc, true, st, tmp, src)) return 1;
+    if (emit_scene(sc, src, d_verts, a, d_inverse, st)) return 1;
     if (keep_ref)
         hipLaunchKernelGGL(k_ploc_remap_ref, dim3((n + 255) / 256), dim3(256), 0, st, sc->d_ref_prims, sc->d_ref_leaf_of, sc->d_order,
                            d_inverse, n, d_ref_prims, d_ref_leaf_of);
@@ -3008,6 +3110,238 @@ int scene_rebuild_impl(rt_scene *sc, const float *verts, int n_tris, bool device
         sc->drop_ref_tree();
     }
     if (moved) sc->h_tri9 = h_new;
+    sc->drop_replicas();
+    return 0;
+}
+
+// ---- editing a scene in place: rt_scene_set_materials, rt_scene_set_lights, rt_scene_set_triangles*, rt_scene_create_device
+// Every one builds what changes into fresh buffers, waits for the device, and only then adopts them: an error on the way
+// leaves the scene rendering its old bits.
+
+// Is `p` device memory on `device` (as stage_vertices asks of the vertices)?  A host pointer is an error, not a fault.
+bool on_device(const void *p, int device) {
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, p) != hipSuccess || (attr.type != hipMemoryTypeDevice && !attr.isManaged) || attr.device != device) {
+        (void)hipGetLastError();  // (the failed query leaves its error behind)
+        return false;
+    }
+    return true;
+}
+
+// A new material table.  Nothing in leaf order depends on it: the table on the device and the shading tables are re-made
+// (k_build_tables, for the new count), the tree, the records, the refit state and the reference's tree stay.
+int scene_set_materials_impl(rt_scene *sc, const rt_material *materials, int n_materials) {
+    const std::string w("rt_scene_set_materials");
+    if (!sc) return fail(w + ": null scene");
+    if (!materials) return fail(w + ": null materials");
+    if (check_scene_counts(w, sc->n_tris, true, materials, n_materials, sc->h_lights.data(), sc->n_lights) ||
+        check_scene_tables(w, sc->n_tris, materials, n_materials, nullptr, 0))
+        return 1;
+    if (sc->max_tri_material >= n_materials)
+        return fail(w + ": the triangles name materials up to " + std::to_string(sc->max_tri_material) + ", the new table has " + std::to_string(n_materials));
+    std::lock_guard<std::mutex> pad_lock(sc->pad_mutex);
+    DeviceGuard dev;
+    if (dev.enter(sc->device)) return 1;
+    DevScope fresh;  // (released unless adopted below)
+    Material *d_mats = nullptr;
+    float *d_tables = nullptr;
+    const int tab_dwords = 5 * n_materials + 24 * sc->n_lights;
+    if (fresh.alloc(d_mats, (size_t)n_materials) || fresh.alloc(d_tables, (size_t)tab_dwords)) return 1;
+    if (n_materials) HIP_TRY(hipMemcpy(d_mats, materials, sizeof(Material) * (size_t)n_materials, hipMemcpyHostToDevice));
+    const int nt = std::max(std::max(n_materials, sc->n_lights), 1);
+    hipLaunchKernelGGL(k_build_tables, dim3((nt + 63) / 64), dim3(64), 0, nullptr, d_mats, n_materials, sc->d_lights, sc->n_lights,
+                       sc->d_tris, d_tables);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    fresh.ptrs.clear();
+    std::swap(sc->d_mats, d_mats);
+    std::swap(sc->d_tables, d_tables);
+    (void)hipFree(d_mats);
+    (void)hipFree(d_tables);
+    sc->n_mats = n_materials;
+    sc->tab_dwords = tab_dwords;
+    sc->h_materials.assign(materials, materials + n_materials);
+    sc->drop_replicas();
+    return 0;
+}
+
+// New lights and, with `tri_light`, a new light assignment of the triangles.  The lights' triangles are renumbered to leaf
+// order from the host's inverse order (what k_leaf_lights does after a build); a new assignment re-emits tri_info and the
+// shading records (k_leaf_tri_light, k_build_tri_shade).  The tree, the triangle records and the reference's tree stay.
+int scene_set_lights_impl(rt_scene *sc, const rt_light *lights, int n_lights, const int32_t *tri_light) {
+    const std::string w("rt_scene_set_lights");
+    if (!sc) return fail(w + ": null scene");
+    if (check_scene_counts(w, sc->n_tris, true, sc->h_materials.data(), sc->n_mats, lights, n_lights) ||
+        check_tri_indices(w, sc->n_tris, nullptr, tri_light, sc->n_mats, n_lights) ||
+        check_scene_tables(w, sc->n_tris, nullptr, 0, lights, n_lights))
+        return 1;
+    if (!tri_light && sc->max_tri_light >= n_lights)
+        return fail(w + ": the kept assignment names lights up to " + std::to_string(sc->max_tri_light) + ", the new table has " + std::to_string(n_lights));
+    std::lock_guard<std::mutex> pad_lock(sc->pad_mutex);
+    DeviceGuard dev;
+    if (dev.enter(sc->device)) return 1;
+    const int n = sc->n_tris;
+    std::vector<rt_light> leaf_lights(lights, lights + n_lights);
+    for (rt_light &l : leaf_lights)
+        if (l.type == RT_AREA_LIGHT) l.triangle = sc->h_inverse[(size_t)l.triangle];
+    DevScope fresh, tmp;  // (fresh: released unless adopted below)
+    Light *d_lights = nullptr;
+    float *d_tables = nullptr;
+    int2 *d_info = nullptr;
+    float4 *d_shade = nullptr;
+    const int tab_dwords = 5 * sc->n_mats + 24 * n_lights;
+    if (fresh.alloc(d_lights, (size_t)n_lights) || fresh.alloc(d_tables, (size_t)tab_dwords)) return 1;
+    if (n_lights) HIP_TRY(hipMemcpy(d_lights, leaf_lights.data(), sizeof(Light) * (size_t)n_lights, hipMemcpyHostToDevice));
+    const bool assign = tri_light && n > 0;
+    if (assign) {
+        int *d_tl = nullptr;
+        if (fresh.alloc(d_info, (size_t)n) || fresh.alloc(d_shade, (size_t)n) || tmp.alloc(d_tl, (size_t)n)) return 1;
+        HIP_TRY(hipMemcpy(d_tl, tri_light, sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
+        const dim3 blk(256), grid((n + 255) / 256);
+        hipLaunchKernelGGL(k_leaf_tri_light, grid, blk, 0, nullptr, sc->d_tri_info, d_tl, sc->d_order, n, d_info);
+        hipLaunchKernelGGL(k_build_tri_shade, grid, blk, 0, nullptr, sc->d_tris, d_info, n, d_shade);
+    }
+    const int nt = std::max(std::max(sc->n_mats, n_lights), 1);
+    hipLaunchKernelGGL(k_build_tables, dim3((nt + 63) / 64), dim3(64), 0, nullptr, sc->d_mats, sc->n_mats, d_lights, n_lights, sc->d_tris,
+                       d_tables);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    fresh.ptrs.clear();
+    std::swap(sc->d_lights, d_lights);
+    std::swap(sc->d_tables, d_tables);
+    (void)hipFree(d_lights);
+    (void)hipFree(d_tables);
+    if (assign) {
+        std::swap(sc->d_tri_info, d_info);
+        std::swap(sc->d_tri_shade, d_shade);
+        (void)hipFree(d_info);
+        (void)hipFree(d_shade);
+    }
+    sc->n_lights = n_lights;
+    sc->tab_dwords = tab_dwords;
+    sc->h_lights.assign(lights, lights + n_lights);
+    if (tri_light) {
+        sc->h_tri_light.assign(tri_light, tri_light + n);
+        sc->note_index_maxima();
+    }
+    sc->drop_replicas();
+    return 0;
+}
+
+// A new triangle set for the scene (or the first one of a scene just made: rt_scene_create_device): any count >= 1, with
+// its per-triangle indices and the tables they index.  The three per-triangle arrays are host arrays, uploaded first, or
+// (device_ptr) buffers on the scene's device, whose index ranges are then checked there (k_index_prepass); from then on
+// there is one path: the device build, every record emitted into buffers of the new size, the host mirrors, the adoption.
+int scene_set_triangles_impl(rt_scene *sc, const float *verts, int n_tris, const int32_t *tri_material, const int32_t *tri_light,
+                             const rt_material *materials, int n_materials, const rt_light *lights, int n_lights, bool device_ptr,
+                             hipStream_t st, const char *what) {
+    const std::string w(what);
+    if (!sc) return fail(w + ": null scene");
+    if (check_scene_counts(w, n_tris, verts && tri_material, materials, n_materials, lights, n_lights)) return 1;
+    if (n_tris < 1) return fail(w + ": the device builder needs at least one triangle (an empty scene is made by rt_scene_create)");
+    if (!sc->wide) return fail(w + ": the scene uses the 2-wide experiment format (RT_BVH_WIDE=0), which the device builder does not write");
+    if (!device_ptr && check_tri_indices(w, n_tris, tri_material, tri_light, n_materials, n_lights)) return 1;
+    if (check_scene_tables(w, n_tris, materials, n_materials, lights, n_lights)) return 1;
+    if (device_ptr) {
+        const std::string where = " is not device memory on the scene's device " + std::to_string(sc->device);
+        if (!on_device(verts, sc->device)) return fail(w + ": d_tri_p0p1p2" + where);
+        if (!on_device(tri_material, sc->device)) return fail(w + ": d_tri_material" + where);
+        if (tri_light && !on_device(tri_light, sc->device)) return fail(w + ": d_tri_light" + where);
+    }
+    std::lock_guard<std::mutex> pad_lock(sc->pad_mutex);  // (the records, h_quads and origin_radius change)
+    DeviceGuard dev;
+    if (dev.enter(sc->device)) return 1;
+    DevScope tmp;
+    const size_t n = (size_t)n_tris;
+    const float *d_verts = verts;
+    const int *d_m = tri_material, *d_l = tri_light;
+    std::vector<float> h_tri9(9 * n);
+    std::vector<int32_t> h_mat(n), h_light(tri_light ? n : 0);
+    if (!device_ptr) {
+        float *uv = nullptr;
+        int *um = nullptr, *ul = nullptr;
+        if (tmp.alloc(uv, 9 * n) || tmp.alloc(um, n) || (tri_light && tmp.alloc(ul, n))) return 1;
+        HIP_TRY(hipMemcpyAsync(uv, verts, sizeof(float) * 9 * n, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(um, tri_material, sizeof(int) * n, hipMemcpyHostToDevice, st));
+        if (tri_light) HIP_TRY(hipMemcpyAsync(ul, tri_light, sizeof(int) * n, hipMemcpyHostToDevice, st));
+        d_verts = uv;
+        d_m = um;
+        d_l = ul;
+        memcpy(h_tri9.data(), verts, sizeof(float) * 9 * n);
+        memcpy(h_mat.data(), tri_material, sizeof(int32_t) * n);
+        if (tri_light) memcpy(h_light.data(), tri_light, sizeof(int32_t) * n);
+        HIP_TRY(hipStreamSynchronize(st));  // (the caller's arrays are his again on return whatever happens below)
+    } else {
+        unsigned *d_words = nullptr, words[2] = {0, 0};
+        if (tmp.alloc(d_words, 2)) return 1;
+        HIP_TRY(hipMemsetAsync(d_words, 0, sizeof(words), st));
+        hipLaunchKernelGGL(k_index_prepass, dim3((unsigned)std::min<size_t>((n + kBlock - 1) / kBlock, 1024)), dim3(kBlock), 0, st, d_m, d_l,
+                           n_tris, n_materials, n_lights, d_words);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(words, d_words, sizeof(words), hipMemcpyDeviceToHost, st));
+        // the host mirrors: what the reference's tree and rt_render_multi replicas are made from, one copy per array
+        HIP_TRY(hipMemcpyAsync(h_tri9.data(), verts, sizeof(float) * 9 * n, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(h_mat.data(), tri_material, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+        if (tri_light) HIP_TRY(hipMemcpyAsync(h_light.data(), tri_light, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (words[0] || words[1])
+            return fail(w + ": " + std::to_string(words[0]) + " of " + std::to_string(n_tris) + " triangles have d_tri_material out of range and " +
+                        std::to_string(words[1]) + " have d_tri_light out of range");
+    }
+    PlocBuild b;
+    if (build_ploc_device(d_verts, n_tris, st, b, w)) return 1;
+    if (!ploc_result_ok(b, n_tris)) return fail(w + ": the device-built tree is malformed; the scene is unchanged");
+    SceneArrays a{b.d_order, b.d_recs, (int)b.quads.size()};
+    Material *d_mats = nullptr;
+    int *d_inverse = nullptr;
+    DevScope fresh;  // (released unless adopted below)
+    const int tab_dwords = 5 * n_materials + 24 * n_lights;
+    if (fresh.alloc(a.nodes, 4 * (size_t)a.n_records) || fresh.alloc(a.tris, 3 * n) || fresh.alloc(a.shade, n) || fresh.alloc(a.info, n) ||
+        fresh.alloc(a.lights, (size_t)n_lights) || fresh.alloc(a.tables, (size_t)tab_dwords) || fresh.alloc(d_mats, (size_t)n_materials) ||
+        tmp.alloc(d_inverse, n))
+        return 1;
+    if (!sc->d_radius) HIP_TRY(hipMalloc((void **)&sc->d_radius, sizeof(float) * 3));  // (scratch of emit_nodes: a scene just made)
+    HIP_TRY(hipMemcpyAsync(d_mats, materials, sizeof(Material) * (size_t)n_materials, hipMemcpyHostToDevice, st));
+    const float none[3] = {0.f, 0.f, 0.f};  // the new tree's own radius, as at creation: the old triangles' says nothing
+    EmitSource src;
+    src.n_tris = n_tris;
+    src.n_mats = n_materials;
+    src.n_lights = n_lights;
+    src.d_mats = d_mats;
+    src.h_lights = lights;
+    src.d_tri_material = d_m;
+    src.d_tri_light = d_l;
+    src.radius = none;
+    if (emit_scene(sc, src, d_verts, a, d_inverse, st)) return 1;
+    float radius[3];
+    HIP_TRY(hipMemcpyAsync(radius, sc->d_radius, sizeof(radius), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    // adopt: the new buffers replace the old ones, the host state follows
+    fresh.ptrs.clear();
+    std::swap(sc->d_nodes, a.nodes);
+    std::swap(sc->d_tris, a.tris);
+    std::swap(sc->d_tri_shade, a.shade);
+    std::swap(sc->d_tri_info, a.info);
+    std::swap(sc->d_lights, a.lights);
+    std::swap(sc->d_tables, a.tables);
+    std::swap(sc->d_mats, d_mats);
+    for (void *q : {(void *)a.nodes, (void *)a.tris, (void *)a.shade, (void *)a.info, (void *)a.lights, (void *)a.tables, (void *)d_mats})
+        (void)hipFree(q);
+    adopt_tree(sc, b);
+    sc->n_tris = n_tris;
+    sc->n_mats = n_materials;
+    sc->n_lights = n_lights;
+    sc->tab_dwords = tab_dwords;
+    for (int k = 0; k < 3; k++) sc->origin_radius[k] = radius[k];
+    sc->drop_refit();
+    sc->sah_build = sc->sah_now = quads_sah(sc->h_quads);
+    sc->drop_ref_tree();
+    sc->h_tri9 = std::move(h_tri9);
+    sc->h_tri_material = std::move(h_mat);
+    sc->h_tri_light = std::move(h_light);
+    sc->h_materials.assign(materials, materials + n_materials);
+    sc->h_lights.assign(lights, lights + n_lights);
+    sc->note_index_maxima();
     sc->drop_replicas();
     return 0;
 }
@@ -3951,27 +4285,10 @@ int rt_scene_create_flags(const float *tri_p0p1p2, int n_tris, const int32_t *tr
     if (scene_flags & ~(uint32_t)RT_SCENE_DEVICE_BVH) return fail("rt_scene_create_flags: unknown scene flags");
     const bool device_bvh = (scene_flags & RT_SCENE_DEVICE_BVH) != 0;
     *out_scene = nullptr;
-    if (n_tris < 0 || n_materials < 0 || n_lights < 0) return fail("rt_scene_create: negative count");
-    if (n_tris >= (1 << 24)) return fail("rt_scene_create: more than 2^24 - 1 triangles (24-bit triangle addressing)");
-    if (n_tris > 0 && (!tri_p0p1p2 || !tri_material)) return fail("rt_scene_create: null triangle arrays");
-    if (n_tris > 0 && (n_materials == 0 || !materials)) return fail("rt_scene_create: no materials");
-    if (n_lights > 0 && !lights) return fail("rt_scene_create: null lights");
-    if (n_materials > 65535 || n_lights > 32766) return fail("rt_scene_create: at most 65535 materials and 32766 lights");
-    for (int i = 0; i < n_tris; i++) {
-        if (tri_material[i] < 0 || tri_material[i] >= n_materials)
-            return fail("rt_scene_create: tri_material[" + std::to_string(i) + "] out of range");
-        if (tri_light && (tri_light[i] < -1 || tri_light[i] >= n_lights))
-            return fail("rt_scene_create: tri_light[" + std::to_string(i) + "] out of range");
-    }
-    for (int i = 0; i < n_materials; i++)
-        if (materials[i].type < RT_MATTE || materials[i].type > RT_GLASS)
-            return fail("rt_scene_create: unknown material type");
-    for (int i = 0; i < n_lights; i++) {
-        if (lights[i].type != RT_POINT_LIGHT && lights[i].type != RT_AREA_LIGHT)
-            return fail("rt_scene_create: unknown light type");
-        if (lights[i].type == RT_AREA_LIGHT && (lights[i].triangle < 0 || lights[i].triangle >= n_tris))
-            return fail("rt_scene_create: area light triangle out of range");
-    }
+    if (check_scene_counts("rt_scene_create", n_tris, n_tris <= 0 || (tri_p0p1p2 && tri_material), materials, n_materials, lights, n_lights) ||
+        check_tri_indices("rt_scene_create", n_tris, tri_material, tri_light, n_materials, n_lights) ||
+        check_scene_tables("rt_scene_create", n_tris, materials, n_materials, lights, n_lights))
+        return 1;
     auto sc = std::make_unique<rt_scene>();
     HIP_TRY(hipGetDevice(&sc->device));
     sc->wide = true;  // 4-wide nodes (two pair-style records each): half the dependent fetches per ray; RT_BVH_WIDE=0: 2-wide
@@ -3985,6 +4302,7 @@ int rt_scene_create_flags(const float *tri_p0p1p2, int n_tris, const int32_t *tr
     if (n_tris > 0 && tri_light) sc->h_tri_light.assign(tri_light, tri_light + n_tris);
     if (n_materials > 0) sc->h_materials.assign(materials, materials + n_materials);
     if (n_lights > 0) sc->h_lights.assign(lights, lights + n_lights);
+    sc->note_index_maxima();
     DevScope tmp;
     float *d_verts = nullptr;
     if (n_tris > 0) {
@@ -4045,7 +4363,9 @@ int rt_scene_create_flags(const float *tri_p0p1p2, int n_tris, const int32_t *tr
         if (int rc = upload_pairs(sc.get(), pairs)) return rc;
     int *d_inverse = nullptr;
     if (tmp.alloc(d_inverse, nt)) return 1;
-    if (emit_scene(sc.get(), d_verts, sc->arrays(), d_inverse, nullptr, tmp)) return 1;
+    EmitSource src;
+    if (scene_source(sc.get(), true, nullptr, tmp, src)) return 1;
+    if (emit_scene(sc.get(), src, d_verts, sc->arrays(), d_inverse, nullptr)) return 1;
     if (sc->wide) HIP_TRY(hipMemcpy(sc->origin_radius, sc->d_radius, sizeof(float) * 3, hipMemcpyDeviceToHost));
     HIP_TRY(hipDeviceSynchronize());
     *out_scene = sc.release();
@@ -4084,6 +4404,43 @@ int rt_scene_rebuild(rt_scene *scene, const float *tri_p0p1p2, int n_tris) {
 
 int rt_scene_rebuild_device(rt_scene *scene, const float *d_tri_p0p1p2, int n_tris, void *stream) {
     return scene_rebuild_impl(scene, d_tri_p0p1p2, n_tris, true, (hipStream_t)stream, "rt_scene_rebuild_device");
+}
+
+int rt_scene_set_materials(rt_scene *scene, const rt_material *materials, int n_materials) {
+    return scene_set_materials_impl(scene, materials, n_materials);
+}
+
+int rt_scene_set_lights(rt_scene *scene, const rt_light *lights, int n_lights, const int32_t *tri_light) {
+    return scene_set_lights_impl(scene, lights, n_lights, tri_light);
+}
+
+int rt_scene_set_triangles(rt_scene *scene, const float *tri_p0p1p2, int n_tris, const int32_t *tri_material, const int32_t *tri_light,
+                           const rt_material *materials, int n_materials, const rt_light *lights, int n_lights) {
+    return scene_set_triangles_impl(scene, tri_p0p1p2, n_tris, tri_material, tri_light, materials, n_materials, lights, n_lights, false,
+                                    nullptr, "rt_scene_set_triangles");
+}
+
+int rt_scene_set_triangles_device(rt_scene *scene, const float *d_tri_p0p1p2, int n_tris, const int32_t *d_tri_material,
+                                  const int32_t *d_tri_light, const rt_material *materials, int n_materials, const rt_light *lights,
+                                  int n_lights, void *stream) {
+    return scene_set_triangles_impl(scene, d_tri_p0p1p2, n_tris, d_tri_material, d_tri_light, materials, n_materials, lights, n_lights,
+                                    true, (hipStream_t)stream, "rt_scene_set_triangles_device");
+}
+
+int rt_scene_create_device(const float *d_tri_p0p1p2, int n_tris, const int32_t *d_tri_material, const int32_t *d_tri_light,
+                           const rt_material *materials, int n_materials, const rt_light *lights, int n_lights, void *stream,
+                           rt_scene **out_scene) {
+    if (!out_scene) return fail("rt_scene_create_device: out_scene is null");
+    *out_scene = nullptr;
+    auto sc = std::make_unique<rt_scene>();  // an empty scene on the current device that takes its first triangle set
+    HIP_TRY(hipGetDevice(&sc->device));
+    sc->wide = true;
+    if (const char *e = knob("RT_BVH_WIDE")) sc->wide = atoi(e) != 0;
+    if (scene_set_triangles_impl(sc.get(), d_tri_p0p1p2, n_tris, d_tri_material, d_tri_light, materials, n_materials, lights, n_lights,
+                                 true, (hipStream_t)stream, "rt_scene_create_device"))
+        return 1;
+    *out_scene = sc.release();
+    return 0;
 }
 
 int rt_scene_refit_info(const rt_scene *scene, int64_t *refits, double *seconds_last, double *sah_ratio) {
