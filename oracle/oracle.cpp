@@ -4,12 +4,16 @@
 // cpu_baseline leg and __graft_entry__.smoke() may load it.  Nothing under rtcuda_amd/ links,
 // imports or calls it.
 //
-// PARITY UNPINNED.  The reference ships no test, fixture or golden image for this path and its device code
-// cannot be built or run in this image (nvcc, cuRAND, CUB absent), so nothing the reference itself produced pins
-// this restatement of the RENDER path.  (Three of its files are pure host C++ and do build here -- happly.h,
-// matrix4x4.hpp, transform.hpp: oracle/Makefile target _ref_host -- and their output pins the scene
-// preparation, i.e. the geometry this oracle and the product render: tests/golden/ref_host_fixture.npz.)
-// Its pins are the known answers SURVEY.md Appendix C records
+// PINNED TO THE REFERENCE'S SOURCE.  The reference ships no test, fixture or golden image for this path and cannot be built
+// as CUDA in this image (nvcc, cuRAND, CUB absent); its device headers, unmodified, are compiled for the CPU under
+// oracle/ref_shim.h instead (oracle/Makefile: _ref_render, _ref_shade), and what they compute is committed as
+// tests/golden/ref_render_fixture.npz and ref_shade_fixture.npz.  This restatement equals both bit for bit: every shading
+// function on every row, and per frame the float sums, the image, the queue counts and the deposit counts
+// (tests/test_ref_shade_pins.py, tests/test_ref_render_pins.py).  ref_shim.h names what the shim substitutes (own XORWOW,
+// serial select, x-then-y jitter, pinned sincos / x^5, g++ rounding).  (Three of the reference's files are pure host C++
+// and build as they stand -- happly.h, matrix4x4.hpp, transform.hpp: target _ref_host -- and pin the scene
+// preparation: tests/golden/ref_host_fixture.npz.)
+// Further pins are the known answers SURVEY.md Appendix C records
 // (tests/golden/appendix_c.json, tests/test_oracle_pins.py) and the committed outputs of its own two
 // modes (tests/golden/render_goldens.npz).  Of Appendix C's answers, the XORWOW states and draws, the
 // camera / triangle / offset / heuristic bit patterns, the BVH statistics, the per-iteration queue counts,
@@ -44,11 +48,6 @@
 //   * libm/libdevice sincosf, powf: build with -DORC_LIBM to call glibc (reproduces the
 //     SURVEY.md Appendix C image hashes recorded in this container); the default build uses the
 //     pinned fp32 sequences of rtcuda_amd/csrc/rt_pinned_math.h so the GPU can match bit for bit.
-//
-// Parity status: the reference ships no tests, golden images or fixtures, and it cannot be
-// built here (needs nvcc + cuRAND + CUB; none present, and stand-ins are not allowed), so this
-// oracle is pinned ONLY by the known-answer values SURVEY.md Appendix C records (minus its image
-// hashes, see above).
 //
 // Build: see oracle/Makefile (g++ -O2 -std=c++17 -ffp-contract=off -fwrapv -fopenmp).
 
@@ -1441,6 +1440,77 @@ void orc_sample_f(const orc_material *m, const float *wo, const float *n_in, uin
     out10[9] = pdf;
     state6[0] = st.d;
     memcpy(state6 + 1, st.v, 20);
+}
+
+// The rest of the shading functions, one call each, for tests/test_ref_shade_pins.py (which holds every one of them to what
+// the reference's own statements compute: tests/golden/ref_shade_fixture.npz).  They call the code above, not copies.
+static Xorwow state_in(const uint32_t *state6) {
+    Xorwow st;
+    st.d = state6[0];
+    memcpy(st.v, state6 + 1, 20);
+    return st;
+}
+static void state_out(const Xorwow &st, uint32_t *state6) {
+    state6[0] = st.d;
+    memcpy(state6 + 1, st.v, 20);
+}
+static V3 v3(const float *p) { return mk(p[0], p[1], p[2]); }
+// -> 1 / 0; out4 = f(3) pdf, left as the caller set them when the result is 0
+int orc_get_f(const orc_material *m, const float *wo, const float *wi, const float *n, float *out4) {
+    Material mm{v3(m->albedo), m->ior, m->type};
+    V3 f = v3(out4);
+    float pdf = out4[3];
+    bool r = mat_get_f(mm, v3(wo), v3(wi), v3(n), f, pdf);
+    memcpy(out4, &f, 12);
+    out4[3] = pdf;
+    return r ? 1 : 0;
+}
+// a light {type, pos, L} on the triangle p9 -> 1 / 0; out8 = wi(3) Li(3) t pdf; advances the rng state
+int orc_sample_Li(int type, const float *pos, const float *L, const float *p9, const float *p, uint32_t *state6, float *out8) {
+    Scene sc;
+    sc.tris.push_back(Tri(v3(p9), v3(p9 + 3), v3(p9 + 6)));
+    Light l{type, v3(pos), 0, v3(L)};
+    Xorwow st = state_in(state6);
+    V3 wi = mk(0, 0, 0), Li = mk(0, 0, 0);
+    float t = 0, pdf = 0;
+    bool r = light_sample_Li(sc, l, v3(p), st, wi, Li, t, pdf);
+    memcpy(out8, &wi, 12);
+    memcpy(out8 + 3, &Li, 12);
+    out8[6] = t;
+    out8[7] = pdf;
+    state_out(st, state6);
+    return r ? 1 : 0;
+}
+float orc_pdf_Li(int type, const float *pos, const float *L, const float *p9, const float *p, const float *wi) {
+    Scene sc;
+    sc.tris.push_back(Tri(v3(p9), v3(p9 + 3), v3(p9 + 6)));
+    Light l{type, v3(pos), 0, v3(L)};
+    return light_pdf_Li(sc, l, v3(p), v3(wi));
+}
+// out4 = p(3) pdf; advances the rng state
+void orc_sample_p(const float *p9, uint32_t *state6, float *out4) {
+    Tri t(v3(p9), v3(p9 + 3), v3(p9 + 6));
+    Xorwow st = state_in(state6);
+    float pdf = 0;
+    V3 q = t.sample_p(st, pdf);
+    memcpy(out4, &q, 12);
+    out4[3] = pdf;
+    state_out(st, state6);
+}
+int orc_same_hemisphere(const float *wo, const float *wi, const float *n) { return same_hemisphere(v3(wo), v3(wi), v3(n)) ? 1 : 0; }
+void orc_reflect(const float *v, const float *n, float *out3) {
+    V3 r = reflect(v3(v), v3(n));
+    memcpy(out3, &r, 12);
+}
+void orc_refract(const float *v, const float *n, float eta_ratio, float cos_theta, float *out3) {
+    V3 r = refract4(v3(v), v3(n), eta_ratio, cos_theta);
+    memcpy(out3, &r, 12);
+}
+void orc_uniform_sample_sphere(uint32_t *state6, float *out3) {
+    Xorwow st = state_in(state6);
+    V3 r = uniform_sample_sphere(st);
+    memcpy(out3, &r, 12);
+    state_out(st, state6);
 }
 
 // ---- scene

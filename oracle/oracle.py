@@ -80,6 +80,18 @@ class Oracle:
         L.orc_pow5.argtypes = [ctypes.c_float]
         L.orc_pow5.restype = ctypes.c_float
         L.orc_sample_f.argtypes = [ctypes.c_void_p, _fp, _fp, _u32p, _fp]
+        L.orc_get_f.argtypes = [ctypes.c_void_p, _fp, _fp, _fp, _fp]
+        L.orc_get_f.restype = ctypes.c_int
+        L.orc_sample_Li.argtypes = [ctypes.c_int, _fp, _fp, _fp, _fp, _u32p, _fp]
+        L.orc_sample_Li.restype = ctypes.c_int
+        L.orc_pdf_Li.argtypes = [ctypes.c_int, _fp, _fp, _fp, _fp, _fp]
+        L.orc_pdf_Li.restype = ctypes.c_float
+        L.orc_sample_p.argtypes = [_fp, _u32p, _fp]
+        L.orc_same_hemisphere.argtypes = [_fp, _fp, _fp]
+        L.orc_same_hemisphere.restype = ctypes.c_int
+        L.orc_reflect.argtypes = [_fp, _fp, _fp]
+        L.orc_refract.argtypes = [_fp, _fp, ctypes.c_float, ctypes.c_float, _fp]
+        L.orc_uniform_sample_sphere.argtypes = [_u32p, _fp]
         L.orc_scene_create.argtypes = [_fp, ctypes.c_int, _fp, _fp, ctypes.c_void_p, ctypes.c_int,
                                        ctypes.c_void_p, ctypes.c_int]
         L.orc_scene_create.restype = ctypes.c_void_p
@@ -176,6 +188,53 @@ class Oracle:
         material = np.ascontiguousarray(material)
         wo, n = np.asarray(wo, np.float32), np.asarray(n, np.float32)
         self.lib.orc_sample_f(_ptr(material), _ptr(wo), _ptr(n), _ptr(state), _ptr(out))
+        return out
+
+    def get_f(self, material, wo, wi, n):
+        """-> (returned, [f(3), pdf]); f and pdf are zero where the function leaves them unset."""
+        out = np.zeros(4, np.float32)
+        material = np.ascontiguousarray(material)
+        wo, wi, n = (np.ascontiguousarray(v, np.float32) for v in (wo, wi, n))
+        r = self.lib.orc_get_f(_ptr(material), _ptr(wo), _ptr(wi), _ptr(n), _ptr(out))
+        return bool(r), out
+
+    def sample_Li(self, light_type, pos, L, p9, p, state):
+        """-> (returned, [wi(3), Li(3), t, pdf]); advances ``state``."""
+        out = np.zeros(8, np.float32)
+        pos, L, p9, p = (np.ascontiguousarray(v, np.float32) for v in (pos, L, p9, p))
+        r = self.lib.orc_sample_Li(int(light_type), _ptr(pos), _ptr(L), _ptr(p9), _ptr(p), _ptr(state), _ptr(out))
+        return bool(r), out
+
+    def pdf_Li(self, light_type, pos, L, p9, p, wi) -> np.float32:
+        pos, L, p9, p, wi = (np.ascontiguousarray(v, np.float32) for v in (pos, L, p9, p, wi))
+        return np.float32(self.lib.orc_pdf_Li(int(light_type), _ptr(pos), _ptr(L), _ptr(p9), _ptr(p), _ptr(wi)))
+
+    def sample_p(self, p9, state) -> np.ndarray:
+        """-> [p(3), pdf]; advances ``state``."""
+        out = np.zeros(4, np.float32)
+        p9 = np.ascontiguousarray(p9, np.float32)
+        self.lib.orc_sample_p(_ptr(p9), _ptr(state), _ptr(out))
+        return out
+
+    def same_hemisphere(self, wo, wi, n) -> bool:
+        wo, wi, n = (np.ascontiguousarray(v, np.float32) for v in (wo, wi, n))
+        return bool(self.lib.orc_same_hemisphere(_ptr(wo), _ptr(wi), _ptr(n)))
+
+    def reflect(self, v, n) -> np.ndarray:
+        out = np.zeros(3, np.float32)
+        v, n = (np.ascontiguousarray(a, np.float32) for a in (v, n))
+        self.lib.orc_reflect(_ptr(v), _ptr(n), _ptr(out))
+        return out
+
+    def refract(self, v, n, eta_ratio, cos_theta) -> np.ndarray:
+        out = np.zeros(3, np.float32)
+        v, n = (np.ascontiguousarray(a, np.float32) for a in (v, n))
+        self.lib.orc_refract(_ptr(v), _ptr(n), float(eta_ratio), float(cos_theta), _ptr(out))
+        return out
+
+    def uniform_sample_sphere(self, state) -> np.ndarray:
+        out = np.zeros(3, np.float32)
+        self.lib.orc_uniform_sample_sphere(_ptr(state), _ptr(out))
         return out
 
     # ------------------------------------------------------------------ ray log (traversal audit)
