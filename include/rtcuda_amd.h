@@ -94,7 +94,15 @@ typedef struct rt_stats {
 #define RT_FLAG_RNG_PER_SAMPLE 4u /* NOT the reference's random numbers: every camera ray starts a stream of its own, keyed by
                                     (seed, camera ray id), instead of continuing its path SLOT's stream (render.cuh:72,156,263).
                                     The image is a statistically equivalent estimate, not the reference's image sample for
-                                    sample -- parity tests never use it.  What it buys: the frame no longer depends on which
+                                    sample -- no test compares it with the reference's image.  It is exactly defined all the
+                                    same: camera ray G = 0 .. width * height * num_samples - 1 has the
+                                    pixel G / num_samples and the stream curand_init's seed scramble (subsequence 0) makes of
+                                    the 64-bit word splitmix64 yields for (seed, G): z = seed + 0x9E3779B97F4A7C15 * (G + 1),
+                                    finalised; its path is the reference's estimator on that stream alone, run to its own end
+                                    with the RT_FLAG_WATERTIGHT hit definition, and its contributions are summed in float in
+                                    path order and added to the pixel once.  The CPU oracle restates this as a loop over camera
+                                    rays, and the GPU suite holds the mode's fixed-point sums and event totals to that
+                                    restatement bit for bit (tests/test_gpu_per_sample.py).  What it buys: the frame no longer depends on which
                                     slot or GPU serves a camera ray, so with rt_render_shard every rank runs ALL W slots on
                                     num_samples / shard_count samples of every pixel (num_samples % shard_count == 0), the
                                     shards' fixed-point sums add up to the 1-GPU sums exactly, and 8 GPUs are not held to

@@ -1337,6 +1337,223 @@ void render_literal(const Scene &sc, const Camera &cam, int width, int height, i
     if (stats) *stats = st;
 }
 
+// ---------------------------------------------------------------- RT_FLAG_RNG_PER_SAMPLE (the PRODUCT's mode, not the reference's)
+// Restated from its definition (include/rtcuda_amd.h at the flag, DESIGN.md sections 2 and 6), not from the kernel: a loop over
+// camera rays, no slot pool, no generations.  Camera ray G of the frame (0 <= G < width * height * spp):
+//   pixel  = G / spp
+//   stream = curand_init's seed scramble (xorwow_seed, subsequence 0) of splitmix64's output for (seed, G): the word
+//            z = seed + 0x9E3779B97F4A7C15 * (G + 1) mod 2^64 put through splitmix64's finaliser
+//   path   = the reference's estimator on that stream alone: two jitter draws (x, then y), camera_get_ray, then the chain of
+//            init() / mat() events of render.cuh run to the path's own end, with the watertight (triangle-list) hit definition
+//   sum    = the path's contributions (bounce-0 emission, then the unoccluded shadow rays in path order) added in three floats,
+//            converted once per channel by to_fixed and added to the pixel (and, as floats, to the float image)
+// Where a path ends: at the first init() that finds no bounce left (bounces == max_bounces), at a miss
+// (a missed path draws nothing more: its idle init() calls use no random number), or when Russian roulette has killed it in
+// every consecutive init() up to the last bounce (the re-roll quirk of SURVEY Appendix A.1, one draw per init()).  Draws a
+// path leaves unused are dropped with its stream.
+uint64_t sample_stream_word(uint64_t seed, uint64_t key) {
+    uint64_t z = seed + 0x9E3779B97F4A7C15ull * (key + 1ull);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+Xorwow sample_stream(uint64_t seed, uint64_t key) { return xorwow_seed(sample_stream_word(seed, key)); }
+
+struct PathTotals {
+    int64_t shades = 0, any_rays = 0, closest_rays = 0, emission_adds = 0, ah_adds = 0, ch_adds = 0, rr_draws = 0, rr_kills = 0;
+};
+
+// One camera ray from gen() to the end of its path; returns the float sum of its contributions.
+V3 per_sample_path(const Scene &sc, const Camera &cam, int width, int height, int pixel, int max_bounces, Xorwow rs,
+                   PathTotals &tot) {
+    const int num_lights = (int)sc.lights.size();
+    const int i = pixel % width, j = pixel / width;
+    const float jx = rnd(rs);  // x first, then y
+    const float jy = rnd(rs);
+    Ray ray = camera_get_ray(cam, (i + jx) / width, (j + jy) / height);
+    V3 beta = mk(1.f, 1.f, 1.f);
+    V3 sum = mk(0, 0, 0);
+    int bounces = 0;
+    while (true) {
+        // ---- ch() :297-328 for the path ray
+        Isect is;
+        is.t = is.u = is.v = 0.f;
+        int prim_idx = -1;
+        V3 wo = ray.d;
+        const bool hit = traverse_closest(sc, ray, is, prim_idx, nullptr);
+        tot.closest_rays++;
+        // ---- init() :84-137
+        if (bounces == 0 && hit) {
+            const int li = sc.prims[prim_idx].light;
+            if (li >= 0) {
+                sum = add(sum, sc.lights[li].L);
+                tot.emission_adds++;
+            }
+        }
+        if (!(bounces < max_bounces)) break;  // no bounce left
+        if (!hit) break;                      // a miss: the slot would idle, drawing nothing, until gen()
+        if (bounces > kRrStart && max3(beta) < kRrThreshold) {
+            const float pt = fmaxf(0.05f, 1 - max3(beta));
+            bool alive = false;
+            while (true) {  // consecutive init() calls: a killed path is rolled again by the next one (Appendix A.1)
+                tot.rr_draws++;
+                const bool kill = rnd(rs) < pt;
+                bounces++;
+                if (!kill) {
+                    beta = divf(beta, 1 - pt);
+                    alive = true;
+                    break;
+                }
+                tot.rr_kills++;
+                if (!(bounces < max_bounces)) break;
+            }
+            if (!alive) break;
+        } else {
+            bounces++;
+        }
+        // ---- mat() :139-248
+        tot.shades++;
+        const Prim &prim = sc.prims[prim_idx];
+        const Material &m = sc.mats[prim.mat];
+        const Tri &tri = sc.tris[prim.tri];
+        const V3 multiplier = scale(beta, (float)num_lights);
+        const V3 isect_p = tri.p(is.u, is.v);
+        const V3 isect_n = neg(unit(tri.n));
+        {
+            V3 n = isect_n, wi;
+            float pdf;
+            V3 f = mat_sample_f(m, wo, rs, n, wi, pdf);
+            ray = spawn_offset_ray(isect_p, n, wi);
+            beta = mul(beta, divf(scale(f, dot(wi, n)), pdf));
+        }
+        if (num_lights == 0) continue;
+        const int light_idx = std::min((int)(rnd(rs) * num_lights), num_lights - 1);
+        const Light light = sc.lights[light_idx];
+        {
+            V3 wi, Li;
+            float lt, lpdf;
+            if (light_sample_Li(sc, light, isect_p, rs, wi, Li, lt, lpdf)) {
+                V3 n = dot(isect_n, wi) > 0.f ? isect_n : neg(isect_n);
+                V3 f;
+                float spdf;
+                if (mat_get_f(m, wo, wi, n, f, spdf)) {
+                    f = scale(f, dot(wi, n));
+                    const Ray shadow = spawn_offset_ray(isect_p, n, wi, lt);
+                    V3 L;
+                    if (light.type == 0) {
+                        L = divf(mul(mul(multiplier, f), Li), lpdf);
+                    } else {
+                        float weight = power_heuristic(lpdf, spdf);
+                        L = divf(scale(mul(mul(multiplier, f), Li), weight), lpdf);
+                    }
+                    tot.any_rays++;
+                    if (!traverse_any(sc, light.type == 1 ? light.tri : -1, shadow, nullptr)) {  // ah() :278-294
+                        sum = add(sum, L);
+                        tot.ah_adds++;
+                    }
+                }
+            }
+        }
+        if (light.type != 0) {  // the BSDF-sampled shadow ray: its draws count, its target is the SHADING triangle (Appendix A.3)
+            V3 n = isect_n, wi;
+            float spdf;
+            V3 f = mat_sample_f(m, wo, rs, n, wi, spdf);
+            f = scale(f, dot(wi, n));
+            float weight = 1.f;
+            bool spawn = true;
+            if (!(m.type == 1 || m.type == 2)) {
+                float lpdf = light_pdf_Li(sc, light, isect_p, wi);
+                if (lpdf == 0.f) spawn = false;
+                else weight = power_heuristic(spdf, lpdf);
+            }
+            if (spawn) {
+                Ray shadow = spawn_offset_ray(isect_p, n, wi);
+                Isect sis;
+                sis.t = sis.u = sis.v = 0.f;
+                int sprim = -1;
+                tot.closest_rays++;
+                if (traverse_closest(sc, shadow, sis, sprim, nullptr) && sc.prims[sprim].tri == prim.tri) {
+                    sum = add(sum, divf(scale(mul(mul(multiplier, f), light.L), weight), spdf));
+                    tot.ch_adds++;
+                }
+            }
+        }
+    }
+    return sum;
+}
+
+// The frame (or shard `shard_index` of `shard_count`: the camera rays G with G % shard_count == shard_index).  Parallel over
+// PIXELS, the rays of a pixel in ascending G: the float sums are then one well-defined array as well, whatever the thread
+// count.  fb_sum (optional): float sums; fb_out (optional): post-processed; fb_fixed (optional, zeroed by the caller).
+void render_per_sample(const Scene &sc_in, const Camera &cam, int width, int height, int spp, int max_bounces, uint64_t seed,
+                       int shard_index, int shard_count, int threads, float *fb_sum, float *fb_out, RenderStats *stats,
+                       long long *fb_fixed) {
+    Scene sc_wt;
+    const Scene *scp = &sc_in;
+    if (!sc_in.watertight) {  // the mode keeps the triangle-list definition of the hits
+        sc_wt = sc_in;
+        sc_wt.watertight = true;
+        scp = &sc_wt;
+    }
+    const Scene &sc = *scp;
+    const int P = width * height;
+    std::vector<V3> fb(P, mk(0, 0, 0));
+    const double t0 = now_s();
+    int64_t n_rays = 0, shades = 0, any_rays = 0, closest_rays = 0, emission = 0, ah_adds = 0, ch_adds = 0, rr_draws = 0, rr_kills = 0;
+#pragma omp parallel for num_threads(threads) schedule(dynamic, 16) \
+    reduction(+ : n_rays, shades, any_rays, closest_rays, emission, ah_adds, ch_adds, rr_draws, rr_kills)
+    for (int pixel = 0; pixel < P; pixel++) {
+        PathTotals tot;
+        for (int k = 0; k < spp; k++) {
+            const uint64_t G = (uint64_t)pixel * (uint64_t)spp + (uint64_t)k;
+            if ((int)(G % (uint64_t)shard_count) != shard_index) continue;
+            n_rays++;
+            const V3 s = per_sample_path(sc, cam, width, height, pixel, max_bounces, sample_stream(seed, G), tot);
+            if (s.x != 0.f || s.y != 0.f || s.z != 0.f) {  // (a NaN compares unequal to 0: it is passed on)
+                fb[pixel] = add(fb[pixel], s);
+                if (fb_fixed) {
+                    long long *q = fb_fixed + 3 * (size_t)pixel;
+                    q[0] += to_fixed(s.x);
+                    q[1] += to_fixed(s.y);
+                    q[2] += to_fixed(s.z);
+                }
+            }
+        }
+        shades += tot.shades;
+        any_rays += tot.any_rays;
+        closest_rays += tot.closest_rays;
+        emission += tot.emission_adds;
+        ah_adds += tot.ah_adds;
+        ch_adds += tot.ch_adds;
+        rr_draws += tot.rr_draws;
+        rr_kills += tot.rr_kills;
+    }
+    if (fb_sum) memcpy(fb_sum, fb.data(), sizeof(float) * 3 * (size_t)P);
+    if (fb_out) {  // post_process_framebuffer :330-338
+        float inv = 1.f / (float)spp;
+        for (int i = 0; i < P; i++) {
+            fb_out[3 * i + 0] = sqrtf(fb[i].x * inv);
+            fb_out[3 * i + 1] = sqrtf(fb[i].y * inv);
+            fb_out[3 * i + 2] = sqrtf(fb[i].z * inv);
+        }
+    }
+    if (stats) {
+        RenderStats st;
+        memset(&st, 0, sizeof(st));
+        st.sum_mat = shades;
+        st.sum_gen = n_rays;
+        st.sum_ah = any_rays;
+        st.sum_ch = closest_rays;
+        st.emission_adds = emission;
+        st.ah_adds = ah_adds;
+        st.ch_adds = ch_adds;
+        st.rr_draws = rr_draws;
+        st.rr_kills = rr_kills;
+        st.seconds_loop = now_s() - t0;
+        *stats = st;
+    }
+}
+
 }  // namespace
 
 // ================================================================= C interface (ctypes)
@@ -1711,6 +1928,45 @@ void orc_render(orc_scene *h, const float *cam12, int width, int height, int spp
         o[17] = (double)st.ah_tri_tests;
         o[18] = (double)st.max_stack;
         o[19] = (double)st.n_iter_records;
+    }
+}
+
+// RT_FLAG_RNG_PER_SAMPLE: the XORWOW state camera ray `key` of a frame starts from (6 words: d, v0..v4)
+void orc_sample_stream(uint64_t seed, uint64_t key, uint32_t *state6) {
+    Xorwow s = sample_stream(seed, key);
+    state6[0] = s.d;
+    memcpy(state6 + 1, s.v, 20);
+}
+
+// the 64-bit words behind the states of keys first .. first + count - 1 (what xorwow_seed scrambles)
+void orc_sample_stream_words(uint64_t seed, uint64_t first, int64_t count, uint64_t *out) {
+    for (int64_t k = 0; k < count; k++) out[k] = sample_stream_word(seed, first + (uint64_t)k);
+}
+
+// ... and a whole frame (or shard) of that mode: render_per_sample.  stats_out as orc_render's (the schedule's fields are 0);
+// fb_fixed: width * height * 3 int64, zeroed by the caller, or null.
+void orc_render_per_sample(orc_scene *h, const float *cam12, int width, int height, int spp, int max_bounces, uint64_t seed,
+                           int shard_index, int shard_count, int threads, float *fb_sum, float *fb_out, double *stats_out,
+                           long long *fb_fixed) {
+    Camera c;
+    memcpy(&c, cam12, 48);
+    RenderStats st;
+    if (threads < 1) threads = 1;
+    render_per_sample(h->sc, c, width, height, spp, max_bounces, seed, shard_index, shard_count, threads, fb_sum, fb_out, &st,
+                      fb_fixed);
+    if (stats_out) {
+        double *o = stats_out;
+        for (int k = 0; k < 20; k++) o[k] = 0.0;
+        o[1] = (double)st.sum_mat;
+        o[2] = (double)st.sum_gen;
+        o[3] = (double)st.sum_ah;
+        o[4] = (double)st.sum_ch;
+        o[5] = (double)st.emission_adds;
+        o[6] = (double)st.ah_adds;
+        o[7] = (double)st.ch_adds;
+        o[8] = (double)st.rr_draws;
+        o[9] = (double)st.rr_kills;
+        o[10] = st.seconds_loop;
     }
 }
 

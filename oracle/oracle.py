@@ -114,8 +114,25 @@ class Oracle:
         L.orc_render.argtypes = [ctypes.c_void_p, _fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                  ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                  _fp, _fp, _fp, _fp, ctypes.c_int]
+        L.orc_sample_stream.argtypes = [ctypes.c_uint64, ctypes.c_uint64, _u32p]
+        L.orc_sample_stream_words.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int64, ctypes.c_void_p]
+        L.orc_render_per_sample.argtypes = [ctypes.c_void_p, _fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                            ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _fp, _fp, _fp,
+                                            ctypes.c_void_p]
 
     # ------------------------------------------------------------------ RNG
+    def sample_stream(self, seed: int, key: int) -> np.ndarray:
+        """RT_FLAG_RNG_PER_SAMPLE: the XORWOW state (d, v0..v4) that camera ray ``key`` of a frame starts from."""
+        st = np.zeros(6, np.uint32)
+        self.lib.orc_sample_stream(seed, key, _ptr(st))
+        return st
+
+    def sample_stream_words(self, seed: int, first: int, count: int) -> np.ndarray:
+        """The 64-bit words (splitmix64 of (seed, key)) that the seed scramble turns into the states of ``count`` keys."""
+        out = np.zeros(count, np.uint64)
+        self.lib.orc_sample_stream_words(seed, first, count, _ptr(out))
+        return out
+
     def xorwow_init(self, seed: int, subsequence: int) -> np.ndarray:
         st = np.zeros(6, np.uint32)
         self.lib.orc_xorwow_init(seed, subsequence, _ptr(st))
@@ -359,10 +376,14 @@ class OracleScene:
         return occ
 
     def render(self, cam12, width, height, spp, max_bounces=10, seed=1, slot_lo=0, slot_hi=1 << 20,
-               threads=1, collect_stats=False, iter_cap=4096, fixed_out=None):
+               threads=1, collect_stats=False, iter_cap=4096, fixed_out=None, rng_mode="reference", shard=(0, 1)):
         """Literal wavefront render.  Returns (image (h,w,3) post-processed, raw sums (h,w,3), stats).
         ``fixed_out``: a zeroed (h, w, 3) int64 array that also receives the product's fixed-point accumulation of the frame
-        (RT_FLAG_DETERMINISTIC's sums: oracle.cpp render_literal)."""
+        (RT_FLAG_DETERMINISTIC's sums: oracle.cpp render_literal).
+        ``rng_mode="per_sample"``: the product's RT_FLAG_RNG_PER_SAMPLE frame instead (oracle.cpp render_per_sample: a loop over
+        camera rays, one stream each, watertight hits whatever set_watertight says); ``shard=(r, R)`` keeps the camera rays G with
+        G % R == r (spp % R == 0).  No slots and no schedule there: slot_lo / slot_hi / collect_stats do not apply and the
+        schedule's stats are 0."""
         cam12 = np.ascontiguousarray(cam12, np.float32)
         fb_sum = np.zeros((height, width, 3), np.float32)
         fb_out = np.zeros((height, width, 3), np.float32)
@@ -370,11 +391,22 @@ class OracleScene:
         it = np.zeros((iter_cap, 4), np.int32)
         if fixed_out is not None:
             assert fixed_out.dtype == np.int64 and fixed_out.shape == (height, width, 3) and fixed_out.flags["C_CONTIGUOUS"]
-            self.o.lib.orc_render_also_fixed.argtypes = [ctypes.c_void_p]
-            self.o.lib.orc_render_also_fixed(_ptr(fixed_out))
-        self.o.lib.orc_render(self.h, _ptr(cam12), width, height, spp, max_bounces, seed, slot_lo, slot_hi,
-                              threads, int(collect_stats), _ptr(fb_sum), _ptr(fb_out), _ptr(st), _ptr(it),
-                              iter_cap)
+        assert rng_mode in ("reference", "per_sample"), rng_mode
+        if rng_mode == "per_sample":
+            r, R = shard
+            assert R >= 1 and 0 <= r < R and spp % R == 0, (shard, spp)
+            assert (slot_lo, slot_hi) == (0, 1 << 20) and not collect_stats
+            assert width * height * spp < (1 << 31)
+            self.o.lib.orc_render_per_sample(self.h, _ptr(cam12), width, height, spp, max_bounces, seed, r, R, threads,
+                                             _ptr(fb_sum), _ptr(fb_out), _ptr(st), _ptr(fixed_out))
+        else:
+            assert tuple(shard) == (0, 1), "reference mode shards by slot range: slot_lo / slot_hi"
+            if fixed_out is not None:
+                self.o.lib.orc_render_also_fixed.argtypes = [ctypes.c_void_p]
+                self.o.lib.orc_render_also_fixed(_ptr(fixed_out))
+            self.o.lib.orc_render(self.h, _ptr(cam12), width, height, spp, max_bounces, seed, slot_lo, slot_hi,
+                                  threads, int(collect_stats), _ptr(fb_sum), _ptr(fb_out), _ptr(st), _ptr(it),
+                                  iter_cap)
         names = ["iterations", "sum_mat", "sum_gen", "sum_ah", "sum_ch", "emission_adds", "ah_adds", "ch_adds",
                  "rr_draws", "rr_kills", "seconds_loop", "seconds_rng_init", "ch_rays", "ch_node_pairs",
                  "ch_tri_tests", "ah_rays", "ah_node_pairs", "ah_tri_tests", "max_stack", "n_iter_records"]
