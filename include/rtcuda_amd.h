@@ -126,6 +126,16 @@ typedef struct rt_stats {
  *       larger caller index: what exhaustive search over all triangles returns.  About 1 path in 4 * 10^6 differs from the
  *       reference's image (on BASELINE config 5 those paths carry whole light deposits: RMS 3.2e-4); 3 - 4 % faster.
  *
+ * FAR-OFF AND DUPLICATED GEOMETRY.  The rate of the rare path is a property of where the scene sits: the reference's slab test
+ * loses hits in proportion to the size of the coordinates, so a scene shifted by 1e4 sends 42 of 20 000 camera rays (and 20 to 30
+ * of 20 000 bounce rays) through the literal re-trace where the scene in [0, 1]^3 sends none; stretching x by 1e3 or squashing
+ * y by 1e-3: 0 to 5.  The answers hold all the same -- flags 0 and RT_FLAG_REFERENCE_WALK the literal restatement's, RT_FLAG_
+ * WATERTIGHT exhaustive search's, bit for bit on every ray (tests/test_placed_scenes_host.py on the CPU twin of the kernels' procedure, tests/test_gpu_placed_scenes.py on the kernels:
+ * queries, frames and a refit from [0, 1]^3 to 1e4; the bunny at 1e5 host-built, device-built and rebuilt).
+ * Duplicated triangles and triangles that fp32 collapsed to points (the bunny at 1e5: 34 815 distinct of 69 467) are scenes
+ * like any other: both builders cut runs of equal boxes by count, rt_scene_create and rt_scene_rebuild
+ * accept them, and hits at equal t on identical triangles go to the reference's tree order (default) or the larger index.
+ *
  * CAVEAT ("the reference" = its algorithm in separately rounded fp32): this library and the CPU oracle are built with
  * -ffp-contract=off, so inv * bound + scaled_origin is a multiplication and an addition.  The reference's CMake build uses
  * nvcc's defaults (fmad on): a CUDA binary contracts that expression -- and others -- into FMAs and loses a DIFFERENT handful

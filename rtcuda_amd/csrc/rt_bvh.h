@@ -120,6 +120,13 @@ inline int max_leaf() {
 constexpr int kTopPrefix = 1024;  // records laid out breadth-first at the front (LDS-cacheable top of the tree)
 constexpr int kMaxBinDepth = 60;
 
+// A range of `count` triangles at `depth` can still be cut into leaves of at most 7 (what a leaf reference carries) by
+// halving alone: every range the builder makes keeps this true, so `Result::ok` holds for any input.
+inline bool fits_below(int count, int depth) {
+    const int levels = kMaxBinDepth - depth;
+    return levels >= 28 || count <= (7 << levels);
+}
+
 // relative cost of a traversal step (tunable for experiments: RT_BVH_TRAV_COST)
 inline float trav_cost() {
     static float c = [] { const char *e = knob("RT_BVH_TRAV_COST"); return e ? (float)atof(e) : 1.0f; }();
@@ -252,6 +259,14 @@ inline void build_binary(const float *verts, int n, std::vector<BinNode> &bin, s
                 best_axis = 0;
                 best_split = t.begin + cnt / 2;
             }
+            // Equal boxes (duplicated triangles, triangles that fp32 collapsed to points: a mesh far from the origin) make
+            // every split cost the same, or the same but for the rounding of the products; the sweep then peels one triangle
+            // off per level.  That is a valid tree as long as it ends before the depth cap, and it is kept as it is; a split
+            // whose larger side could no longer be halved down to referenceable leaves is replaced by the median.
+            if (best_axis >= 0 && !fits_below(std::max(best_split - t.begin, t.end - best_split), t.depth + 1)) {
+                best_axis = 0;
+                best_split = t.begin + cnt / 2;
+            }
         }
         if (best_axis < 0) {  // leaf (a range longer than kMaxLeaf only at the depth cap)
             bin[t.node].first = out_pos;
@@ -332,7 +347,7 @@ inline void optimize_reinsert(std::vector<BinNode> &bin, int passes) {
         bool operator<(const Cand &o) const { return induced > o.induced; }  // min-heap on induced cost
     };
     std::vector<Cand> heap;
-    std::vector<int> by_area(n);
+    std::vector<int> by_area(n), path;
     for (int pass = 0; pass < passes; pass++) {
         std::iota(by_area.begin(), by_area.end(), 0);
         std::stable_sort(by_area.begin(), by_area.end(),
@@ -374,6 +389,17 @@ inline void optimize_reinsert(std::vector<BinNode> &bin, int passes) {
                     heap.push_back(Cand{child_induced, x.right});
                     std::push_heap(heap.begin(), heap.end());
                 }
+            }
+            // ---- a place that is no better than the one N came from is no reason to move: among equal boxes (duplicated
+            // triangles, triangles collapsed to points) every place costs the same, the search names the first one it sees,
+            // and moving subtree after subtree there strings them into a chain deeper than any traversal stack.  N's old
+            // place beside S, priced as the search prices it: top-down along the path from the root.
+            if (best != S) {
+                path.clear();
+                for (int x = G; x >= 0; x = parent[x]) path.push_back(x);
+                float induced = 0.f;
+                for (size_t k = path.size(); k-- > 0;) induced = induced + unite(bin[path[k]].box, nb).half_area() - bin[path[k]].box.half_area();
+                if (!(best_cost < induced + unite(bin[S].box, nb).half_area())) best = S;
             }
             // ---- P becomes the parent of {best, N} in best's old place
             const int X = best, XP = parent[X];

@@ -422,13 +422,14 @@ PlocTwin ploc_build(const float *verts, int n) {
     while (cl.size() > 1) {
         if (++out.iterations > rtploc::kMaxIterations) return out;
         const int m = (int)cl.size();
+        const bool pair_ties = out.iterations > rtploc::kTieIterations;
         for (int i = 0; i < m; i++) {
             int best_j = -1;
             float best = 0.f;
             for (int j = std::max(0, i - rtploc::kRadius); j <= std::min(m - 1, i + rtploc::kRadius); j++) {
                 if (j == i) continue;
                 const float d = rtploc::distance(nd.box(cl[(size_t)i]), nd.box(cl[(size_t)j]));
-                if (best_j < 0 || d < best) {
+                if (rtploc::nearer(d, j, i, best, best_j, pair_ties)) {
                     best_j = j;
                     best = d;
                 }
@@ -623,6 +624,21 @@ int rt_bvh_refit_check(const float *build_verts, const float *new_verts, int n, 
             if (k < 2) root.extend(b);
         }
     out6[5] = (int64_t)llround(1e6 * cost / std::max((double)root.half_area(), 1e-30));
+    return 0;
+}
+
+// The host builder's 4-wide records and leaf order, as rt_ploc_build gives the twin's.  out4: [records, stack bound, depth of the
+// 4-wide tree, leaves].  Returns 1 if the build failed (a leaf that cannot be referenced).
+int rt_bvh_export(const float *verts, int n, void *quads_out, int64_t cap_records, int32_t *order_out, int64_t *out4) {
+    memset(out4, 0, 4 * sizeof(int64_t));
+    const rtbvh::Result r = rtbvh::build(verts, n);
+    if (!r.ok) return 1;
+    out4[0] = (int64_t)r.quads.size();
+    out4[1] = r.stack_bound;
+    out4[2] = r.max_depth;
+    out4[3] = r.num_leaves;
+    if (quads_out && cap_records >= (int64_t)r.quads.size()) memcpy(quads_out, r.quads.data(), sizeof(rtbvh::Pair) * r.quads.size());
+    if (order_out && n > 0) memcpy(order_out, r.order.data(), sizeof(int32_t) * (size_t)n);
     return 0;
 }
 

@@ -1990,8 +1990,8 @@ __global__ void k_ploc_leaves(const float *__restrict__ verts, const unsigned lo
     nd.leaf[k] = 1;
     cl[k] = c;
 }
-// nearest neighbour of every cluster within the window (ties: the smaller j); the block's window of boxes is staged in LDS
-__global__ void __launch_bounds__(256) k_ploc_nearest(const PlocCluster *__restrict__ cl, int m, int *__restrict__ nn) {
+// nearest neighbour of every cluster within the window (ties: rtploc::nearer); the block's window of boxes is staged in LDS
+__global__ void __launch_bounds__(256) k_ploc_nearest(const PlocCluster *__restrict__ cl, int m, int pair_ties, int *__restrict__ nn) {
     constexpr int R = rtploc::kRadius, W = 256 + 2 * R;
     __shared__ float s_box[6][W];
     const int base = blockIdx.x * 256;
@@ -2013,7 +2013,7 @@ __global__ void __launch_bounds__(256) k_ploc_nearest(const PlocCluster *__restr
         float bj[6];
         for (int a = 0; a < 6; a++) bj[a] = s_box[a][j - base + R];
         const float d = rtploc::distance(bi, bj);
-        if (best_j < 0 || d < best) {
+        if (rtploc::nearer(d, j, i, best, best_j, pair_ties != 0)) {
             best_j = j;
             best = d;
         }
@@ -2954,7 +2954,7 @@ int build_ploc_device(const float *d_verts, int n, hipStream_t st, PlocBuild &ou
     while (m > 1) {
         if (++out.iterations > rtploc::kMaxIterations) return fail(w + ": the clustering does not converge");
         const int mb = (m + 255) / 256;
-        hipLaunchKernelGGL(k_ploc_nearest, dim3(mb), blk, 0, st, d_cl[cur], m, d_nn);
+        hipLaunchKernelGGL(k_ploc_nearest, dim3(mb), blk, 0, st, d_cl[cur], m, out.iterations > rtploc::kTieIterations ? 1 : 0, d_nn);
         hipLaunchKernelGGL(k_ploc_count, dim3(mb), blk, 0, st, d_nn, m, d_sums);
         hipLaunchKernelGGL(k_ploc_scan, dim3(1), dim3(1024), 0, st, d_sums, mb, d_tot);
         hipLaunchKernelGGL(k_ploc_merge, dim3(mb), blk, 0, st, d_cl[cur], d_nn, m, d_sums, inner, trav, max_leaf, nd, d_cl[cur ^ 1]);

@@ -13,6 +13,7 @@ import os
 import numpy as np
 import pytest
 
+import placed_scenes
 import raygen
 from table_scenes import table_scene
 from test_scene_update_host import deform
@@ -227,24 +228,32 @@ def _tiny(arrays, tris):
                                lights=arrays.lights[:0])
 
 
-@pytest.mark.parametrize("case", ["1", "2", "3", "5", "8", "9", "coincident", "bare_box", "deformed_bunny"])
-def test_tiny_and_degenerate_scenes(api, bunny_matte, case):
+TINY_CASES = ["1", "2", "3", "5", "8", "9", "coincident", "bare_box", "deformed_bunny"]
+
+
+def _tiny_case(bunny_matte, case):
     from rtcuda_amd import scenes
     bt = np.asarray(bunny_matte.tris, np.float32).reshape(-1, 9)
     if case.isdigit():
-        arrays = _tiny(bunny_matte, bt[::997][: int(case)])
-    elif case == "coincident":
-        arrays = _tiny(bunny_matte, np.repeat(bt[100:101], 40, axis=0))
-    elif case == "bare_box":
-        arrays = scenes.cornell_bunny("matte", bunny=False)
-    else:
-        arrays = _with(bunny_matte, deform(bt, amp=0.05))
+        return _tiny(bunny_matte, bt[::997][: int(case)])
+    if case == "coincident":
+        return _tiny(bunny_matte, np.repeat(bt[100:101], 40, axis=0))
+    if case == "bare_box":
+        return scenes.cornell_bunny("matte", bunny=False)
+    if case == "deformed_bunny":
+        return _with(bunny_matte, deform(bt, amp=0.05))
+    return placed_scenes.scene(case)[0]  # (equal boxes by the hundred: refused before the builders learned to cut them)
+
+
+@pytest.mark.parametrize("case", TINY_CASES + ["points_200", "copies_1000"])
+def test_tiny_and_degenerate_scenes(api, bunny_matte, case):
+    arrays = _tiny_case(bunny_matte, case)
     recs, order, _ = _twin(arrays.tris)
     a = api.Scene(arrays, library=api.tools_lib(), device_bvh=True)
     r, o = _device_tree(api, a)
     assert np.array_equal(o, order) and np.array_equal(r, recs)
     b = api.Scene(arrays, library=api.tools_lib())
-    o3, d3 = _view_rays(api, n=20_000) if case in ("bare_box", "deformed_bunny") else _aimed_rays(arrays.tris, 20_000, seed=5)
+    o3, d3 = _view_rays(api, n=20_000) if case in ("bare_box", "deformed_bunny", "points_200", "copies_1000") else _aimed_rays(arrays.tris, 20_000, seed=5)
     _assert_same_hits(api, a, b, o3, d3, min_hit=0.2)
     b.rebuild()
     _assert_same_hits(api, a, b, o3, d3, min_hit=0.2)
