@@ -479,6 +479,32 @@ inline rt_stats render_rays_fixed(const Scene &scene, int64_t n_rays, const floa
     return st;
 }
 
+// The same with a stream per ray (rt_render_rays_keyed_device / rt_render_rays_keyed_fixed_device, which document the keys, the
+// flags and the errors): row c has the 64-bit key key_first + c * key_stride and the random numbers of camera ray `key` of an
+// RT_FLAG_RNG_PER_SAMPLE frame; d_pixel nullptr: it lands on pixel key / rays_per_pixel.  With `fixed`-point sums any split of a
+// table -- chunks (key_first = the chunk's first row), rank r of R (key_first = r, key_stride = R) -- adds up to exactly the
+// whole frame's.
+inline rt_stats render_rays_keyed(const Scene &scene, int64_t n_rays, const float *d_origin, const float *d_dir, const int32_t *d_pixel,
+                                  int rays_per_pixel, int n_pixels, float *d_sum_rgb, uint64_t key_first = 0, uint32_t key_stride = 1,
+                                  int max_bounces = 10, void *stream = nullptr, uint32_t flags = 0, uint64_t seed = 1) {
+    rt_scene *h = scene.bvh.handle ? rtcuda_detail::realise(scene) : nullptr;
+    rt_stats st{};
+    rtcuda_detail::check(rt_render_rays_keyed_device(h, n_rays, d_origin, d_dir, d_pixel, rays_per_pixel, n_pixels, max_bounces, seed,
+                                                     key_first, key_stride, flags, d_sum_rgb, stream, &st), "render_rays_keyed");
+    return st;
+}
+inline rt_stats render_rays_keyed_fixed(const Scene &scene, int64_t n_rays, const float *d_origin, const float *d_dir,
+                                        const int32_t *d_pixel, int rays_per_pixel, int n_pixels, int64_t *d_sum_fixed,
+                                        uint64_t key_first = 0, uint32_t key_stride = 1, int max_bounces = 10, void *stream = nullptr,
+                                        uint32_t flags = 0, uint64_t seed = 1) {
+    rt_scene *h = scene.bvh.handle ? rtcuda_detail::realise(scene) : nullptr;
+    rt_stats st{};
+    rtcuda_detail::check(rt_render_rays_keyed_fixed_device(h, n_rays, d_origin, d_dir, d_pixel, rays_per_pixel, n_pixels, max_bounces,
+                                                           seed, key_first, key_stride, flags, d_sum_fixed, stream, &st),
+                         "render_rays_keyed_fixed");
+    return st;
+}
+
 // A driver that must keep the reference's exact call (main.cu:173) can still reach several GPUs: RTCUDA_DEVICES="0,1,2,3" in
 // the environment sends the seven-argument render() below through the multi-device path (rt_render_multi).
 inline std::vector<int> devices_from_env() {

@@ -324,7 +324,7 @@ int rt_post_process(float *d_rgb, int num_pixels, int num_samples, void *stream)
  * the same scene, not rt_scene_update* / rt_scene_rebuild*.
  * flags: 0, RT_FLAG_WATERTIGHT, RT_FLAG_TIME_KERNELS.  Out of scope (an error that names the flag): RT_FLAG_REFERENCE_WALK and
  * RT_FLAG_RNG_PER_SAMPLE -- each would be further builds of the persistent kernel.  No shard parameters either: one device,
- * all W slots.
+ * all W slots.  (A table with a stream per RAY, which splits over calls and devices: rt_render_rays_keyed_device below.)
  * CHECKED ON THE DEVICE BEFORE ANYTHING IS WRITTEN: every direction component finite and below 2^126 in magnitude, every
  * d_pixel[c] in [0, n_pixels) -- the error names the number of offending rays.  Origins outside the radius the scene's
  * records are padded for widen the padding once, as for the queries; a non-finite ORIGIN is legal: that ray misses.
@@ -338,6 +338,37 @@ int rt_render_rays_device(const rt_scene *scene, int64_t n_rays, const float *d_
 int rt_render_rays_fixed_device(const rt_scene *scene, int64_t n_rays, const float *d_origin_xyz, const float *d_dir_xyz,
                                 const int32_t *d_pixel /* may be NULL */, int rays_per_pixel, int n_pixels, int max_bounces,
                                 uint64_t seed, uint32_t flags, int64_t *d_sum_fixed, void *stream, rt_stats *stats);
+
+/* ---- keyed ray tables: a stream per ray, so a table splits by key range or stride and the pieces add up exactly ------------
+ * The two entry points above tie ray c to slot c % W's stream: a frame is one indivisible call.  Here table row c
+ * (0 <= c < n_rays) carries the 64-bit key K = key_first + c * key_stride, and
+ *   - its stream is the per-sample stream of (seed, K): exactly that of camera ray G = K of an RT_FLAG_RNG_PER_SAMPLE frame
+ *     (splitmix64 of the key, then curand_init's seed scramble: see that flag);
+ *   - the first two draws (jitter x, then y) are made and thrown away, as above: a table filled with a pinhole camera's own
+ *     per-sample rays gives rt_render_shard_fixed(RT_FLAG_RNG_PER_SAMPLE)'s sums, draw for draw;
+ *   - origin and direction are row c, tmax = FLT_MAX;
+ *   - it deposits into pixel d_pixel[c] if d_pixel is given, else into pixel K / rays_per_pixel -- by the KEY, not the row:
+ *     a chunk that starts mid-pixel, or rank r of R, lands where the whole frame puts it;
+ *   - everything after gen() is the per-sample mode's: the path runs to its own end (no lockstep final generation), hits are
+ *     RT_FLAG_WATERTIGHT's, a camera ray's contributions are summed in float in path order and added to its pixel once.
+ * Sums are ADDED to the buffer, so ANY split of a table -- chunks streamed through one buffer (key_first = first row of the
+ * chunk, key_stride = 1), rank r of R (key_first = r, key_stride = R, the rows G = r mod R), passes of a progressive render --
+ * gives, in the fixed variant, EXACTLY the int64 sums of the whole frame, in any order.
+ * flags: 0, RT_FLAG_TIME_KERNELS; RT_FLAG_RNG_PER_SAMPLE and RT_FLAG_WATERTIGHT are accepted and change nothing (both are what
+ * the mode is); RT_FLAG_REFERENCE_WALK and any other bit is an error that names the flag.
+ * Checks: those of rt_render_rays_device (host and device, before anything is written), and key_stride >= 1, the last key
+ * key_first + (n_rays - 1) * key_stride does not wrap 2^64, and with d_pixel NULL rays_per_pixel >= 1 and the last key's
+ * pixel < n_pixels.  A scene with 2-wide nodes (RT_BVH_WIDE=0), or a process without the persistent kernel (RT_PERSISTENT=0),
+ * is an error: the per-sample mode runs on k_paths only.  Every error returns non-zero, names the entry point in
+ * rt_last_error() and writes nothing. */
+int rt_render_rays_keyed_device(const rt_scene *scene, int64_t n_rays, const float *d_origin_xyz, const float *d_dir_xyz,
+                                const int32_t *d_pixel /* may be NULL */, int rays_per_pixel /* used when d_pixel == NULL */,
+                                int n_pixels, int max_bounces, uint64_t seed, uint64_t key_first, uint32_t key_stride,
+                                uint32_t flags, float *d_sum_rgb, void *stream, rt_stats *stats);
+int rt_render_rays_keyed_fixed_device(const rt_scene *scene, int64_t n_rays, const float *d_origin_xyz, const float *d_dir_xyz,
+                                      const int32_t *d_pixel /* may be NULL */, int rays_per_pixel, int n_pixels, int max_bounces,
+                                      uint64_t seed, uint64_t key_first, uint32_t key_stride, uint32_t flags,
+                                      int64_t *d_sum_fixed, void *stream, rt_stats *stats);
 
 /* ---- ray queries (no reference counterpart: its Bvh::traverse is reachable only from render()) ----------------------------
  * "Trace my rays, from my buffers, on my stream."  All pointers are DEVICE buffers on the scene's device (a buffer on another

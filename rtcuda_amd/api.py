@@ -33,7 +33,8 @@ EXPORTS = [
     "rt_scene_create", "rt_scene_destroy", "rt_scene_info", "rt_scene_build_info", "rt_scene_update", "rt_scene_update_device",
     "rt_scene_refit_info", "rt_scene_create_flags", "rt_scene_rebuild", "rt_scene_rebuild_device", "rt_scene_set_materials",
     "rt_scene_set_lights", "rt_scene_set_triangles", "rt_scene_set_triangles_device", "rt_scene_create_device", "rt_camera_make", "rt_render", "rt_render_multi",
-    "rt_render_shard", "rt_render_shard_fixed", "rt_render_rays_device", "rt_render_rays_fixed_device", "rt_post_process", "rt_post_process_fixed", "rt_trace_closest", "rt_trace_any",
+    "rt_render_shard", "rt_render_shard_fixed", "rt_render_rays_device", "rt_render_rays_fixed_device",
+    "rt_render_rays_keyed_device", "rt_render_rays_keyed_fixed_device", "rt_post_process", "rt_post_process_fixed", "rt_trace_closest", "rt_trace_any",
     "rt_trace_closest_flags", "rt_trace_any_flags", "rt_query_closest_device", "rt_query_any_device", "rt_query_last_counters",
     "rt_xorwow_states", "rt_shutdown", "rt_peer_access_log", "rt_last_error", "rt_version", "rt_build_id",
 ]
@@ -150,6 +151,9 @@ def _bind(L):
     L.rt_render_rays_device.argtypes = [vp, ctypes.c_int64, vp, vp, vp, ci, ci, ci, ctypes.c_uint64, ctypes.c_uint32, vp, vp,
                                         ctypes.POINTER(RtStats)]
     L.rt_render_rays_fixed_device.argtypes = L.rt_render_rays_device.argtypes
+    L.rt_render_rays_keyed_device.argtypes = [vp, ctypes.c_int64, vp, vp, vp, ci, ci, ci, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32,
+                                              ctypes.c_uint32, vp, vp, ctypes.POINTER(RtStats)]
+    L.rt_render_rays_keyed_fixed_device.argtypes = L.rt_render_rays_keyed_device.argtypes
     L.rt_trace_closest.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp]
     L.rt_trace_any.argtypes = [vp, ci, vp, vp, vp, vp, vp]
     L.rt_trace_closest_flags.argtypes = [vp, ctypes.c_uint32, ci, vp, vp, vp, vp, vp, vp, vp]
@@ -494,6 +498,49 @@ class Scene:
         st = self.render_rays_device(origins.data_ptr(), dirs.data_ptr(), 0 if pixel is None else pixel.data_ptr(), n, n_pixels,
                                      out.data_ptr(), rays_per_pixel, max_bounces, seed, flags, fixed,
                                      torch.cuda.current_stream(device).cuda_stream)
+        return out, st
+
+    # ---- the same with a per-sample stream per ray (rt_render_rays_keyed_device / rt_render_rays_keyed_fixed_device)
+    def render_rays_keyed_device(self, o_ptr: int, d_ptr: int, pixel_ptr: int, n_rays: int, n_pixels: int, d_sum_ptr: int,
+                                 rays_per_pixel: int = 1, key_first: int = 0, key_stride: int = 1, max_bounces: int = 10, seed: int = 1,
+                                 flags: int = 0, fixed: bool = False, stream: int = 0) -> dict:
+        """A keyed frame of n_rays camera rays from DEVICE buffers (as render_rays_device): row c has the 64-bit key
+        K = key_first + c * key_stride, the random numbers of camera ray K of a FLAG_RNG_PER_SAMPLE frame, and lands on pixel
+        pixel[c] or, with pixel_ptr 0, K // rays_per_pixel.  Raw sums are ADDED into the DEVICE buffer at ``d_sum_ptr``; with
+        ``fixed`` any split of a table by key range or stride adds up to exactly the whole frame's sums."""
+        c = ctypes.c_void_p
+        name = "rt_render_rays_keyed_fixed_device" if fixed else "rt_render_rays_keyed_device"
+        for what, v, top in (("key_first", key_first, 1 << 64), ("key_stride", key_stride, 1 << 32), ("seed", seed, 1 << 64)):
+            if not isinstance(v, int) or not 0 <= v < top:  # (ctypes would wrap it silently)
+                raise RtError(f"{name}: {what} must be an int in 0 .. 2^{top.bit_length() - 1} - 1, it is {v!r}")
+        st = RtStats()
+        _check(getattr(self.L, name)(self.h, int(n_rays), c(o_ptr or None), c(d_ptr or None), c(pixel_ptr or None), int(rays_per_pixel),
+                                     int(n_pixels), int(max_bounces), seed, key_first, key_stride, flags, c(d_sum_ptr or None),
+                                     c(stream or None), ctypes.byref(st)), name, self.L)
+        return st.as_dict()
+
+    def render_rays_keyed(self, origins, dirs, n_pixels: int, pixel=None, rays_per_pixel: int = 1, key_first: int = 0, key_stride: int = 1,
+                          max_bounces: int = 10, seed: int = 1, fixed: bool = False, out=None, stream=None):
+        """Radiance along torch rays with a stream per ray (render_rays' tensors and checks; see render_rays_keyed_device for
+        the keys) -> (sums, stats).  ``out``: an (n_pixels, 3) tensor to ADD into -- chunks of one table, rendered with
+        key_first = the chunk's first row, accumulate into one buffer.  ``stream``: a torch stream (default: the current one)."""
+        import torch
+        n, device = self._query_rays("render_rays_keyed", origins, dirs, None)
+        if pixel is not None:
+            self._query_rays("render_rays_keyed", origins, dirs, None, pixel, "pixel")
+        dtype = torch.int64 if fixed else torch.float32
+        if out is None:
+            if not isinstance(n_pixels, int) or n_pixels < 1:
+                raise RtError(f"render_rays_keyed: n_pixels must be a positive int, it is {n_pixels!r}")
+            out = torch.zeros((n_pixels, 3), dtype=dtype, device=device)
+        else:
+            if not isinstance(out, torch.Tensor) or not out.is_cuda or out.device != device:
+                raise RtError("render_rays_keyed: out must be a torch tensor on the rays' GPU")
+            if out.dtype != dtype or tuple(out.shape) != (n_pixels, 3) or not out.is_contiguous():
+                raise RtError(f"render_rays_keyed: out must be a contiguous ({n_pixels}, 3) {dtype} tensor, it is {tuple(out.shape)} {out.dtype}")
+        s = torch.cuda.current_stream(device) if stream is None else stream
+        st = self.render_rays_keyed_device(origins.data_ptr(), dirs.data_ptr(), 0 if pixel is None else pixel.data_ptr(), n, n_pixels,
+                                           out.data_ptr(), rays_per_pixel, key_first, key_stride, max_bounces, seed, 0, fixed, s.cuda_stream)
         return out, st
 
     # ---- ray queries on device buffers (rt_query_*_device)

@@ -1,6 +1,7 @@
 // The kernels of a frame: k_advance (one round of init() + mat() + gen() for all slots, state in the pools) and k_paths (the
 // persistent kernel).  Included by rtcuda_amd.hip once per source of camera rays, with
-//   RT_FRAME_SRC               Camera (gen()'s pinhole) or RayTable (the caller's rays, rt_render_rays_*): see gen_core
+//   RT_FRAME_SRC               Camera (gen()'s pinhole), RayTable (the caller's rays, rt_render_rays_*) or KeyedRayTable (the
+//                              caller's rays with a per-sample stream each, rt_render_rays_keyed_*): see gen_core
 //   RT_K_ADVANCE / RT_K_PATHS  the names of the two kernels of that compilation
 // No include guard: meant to be included more than once.
 

@@ -441,6 +441,22 @@ struct RayTable {
     const float *o3, *d3;  // origins and directions, AoS triples
     const int *pixel;      // the pixel a ray deposits into; null: c / AdvanceParams::spp
 };
+// The camera rays of a KEYED ray-table frame (rt_render_rays_keyed_device / rt_render_rays_keyed_fixed_device): row c is the
+// camera ray with the 64-bit key K = key_first + c * key_stride, and its stream is rng_sample_stream(seed, K) -- camera ray
+// G = K of an RT_FLAG_RNG_PER_SAMPLE frame.  Without a pixel array the ray lands on pixel K / rays_per_pixel (by the key, not
+// by the row), which the host hands over as pix_first + (rem_first + c * key_stride) / rays_per_pixel with
+// pix_first = key_first / rays_per_pixel and rem_first = key_first % rays_per_pixel: the same quotient, and its dividend
+// fits 32 bits for every chunk of a stride-1 table (then the divide is the 32-bit one).
+// Travels in k_paths_keyed's uniforms where the camera builds keep the Camera: no larger than it.
+struct KeyedRayTable {
+    const float *o3, *d3;  // origins and directions, AoS triples
+    const int *pixel;      // the pixel a ray deposits into; null: K / rays_per_pixel
+    unsigned long long key_first;
+    uint32_t key_stride, rays_per_pixel;
+    int pix_first;
+    uint32_t rem_first;
+};
+static_assert(sizeof(KeyedRayTable) <= sizeof(Camera), "k_paths' dynamic LDS is sized for a Camera in the uniforms");
 #ifndef RT_RAYS_NONTEMPORAL
 #define RT_RAYS_NONTEMPORAL 1
 #endif
@@ -473,7 +489,32 @@ __device__ __forceinline__ void gen_core(const SRC &cam, const AdvanceParams &ap
         return;
     }
     st.gen = st.gen + 1;
-    if constexpr (std::is_same<SRC, RayTable>::value) {
+    if constexpr (std::is_same<SRC, KeyedRayTable>::value) {
+        // Keyed ray-table frames: row `cid` starts the per-sample stream of its key (whatever stream the lane held), gen()'s
+        // two jitter draws are made and dropped -- a pinhole's own table reproduces the RT_FLAG_RNG_PER_SAMPLE frame draw for
+        // draw --, the ray is the row.  Rows are read as in the RayTable branch below: the lanes of a wave hold consecutive
+        // ranks of a drawn chunk (or consecutive slots), so consecutive rows.
+        const unsigned c = (unsigned)cid;  // (below 2^31: the host checks the frame)
+        const unsigned long long ck = (unsigned long long)c * cam.key_stride;  // (no wrap: c < 2^31, key_stride < 2^32)
+        st.rs = rng_sample_stream(ap.seed_lo, ap.seed_hi, cam.key_first + ck);  // (the host refuses keys that wrap)
+        rng_next(st.rs);  // x first, then y (Appendix A.7)
+        rng_next(st.rs);
+        const float *o3 = cam.o3 + 3 * (size_t)c, *d3 = cam.d3 + 3 * (size_t)c;
+        out.ray_o = mk(table_load(o3), table_load(o3 + 1), table_load(o3 + 2));
+        out.ray_d = mk(table_load(d3), table_load(d3 + 1), table_load(d3 + 2));
+        if (cam.pixel) {
+            st.pixel = table_load(cam.pixel + c);
+        } else {
+            const unsigned long long t = cam.rem_first + ck;  // K / rays_per_pixel = pix_first + t / rays_per_pixel
+            const unsigned q = (t >> 32) ? (unsigned)(t / cam.rays_per_pixel) : (unsigned)t / cam.rays_per_pixel;
+            st.pixel = cam.pix_first + (int)q;  // (below n_pixels: the host checks the last key)
+        }
+        out.new_ray = true;
+        st.bounces = 0;
+        st.beta = mk(1.f, 1.f, 1.f);
+        out.did_gen = true;
+        return;
+    } else if constexpr (std::is_same<SRC, RayTable>::value) {
         // Ray-table frames: gen()'s two jitter draws are made and dropped (the slot's stream stays where the reference's
         // is), the ray and its pixel are row `cid` of the table.  No pixel coordinates, no stepping (`pxy` is left alone).
         // The lanes of a wave serve consecutive slots, so their rows are consecutive: 768 contiguous bytes per array and
@@ -1731,6 +1772,15 @@ constexpr bool kSpeculate = RT_SPECULATE != 0;  // k_paths: postpone a leaf reac
 #define RT_FRAME_SRC RayTable
 #define RT_K_ADVANCE k_advance_rays
 #define RT_K_PATHS k_paths_rays
+#include "rt_frame_kernels.inc"
+#undef RT_FRAME_SRC
+#undef RT_K_ADVANCE
+#undef RT_K_PATHS
+// and with RT_FRAME_SRC = KeyedRayTable (rt_render_rays_keyed_*) as k_paths_keyed: per-sample streams, so the persistent kernel
+// only (k_advance_keyed is never instantiated)
+#define RT_FRAME_SRC KeyedRayTable
+#define RT_K_ADVANCE k_advance_keyed
+#define RT_K_PATHS k_paths_keyed
 #include "rt_frame_kernels.inc"
 #undef RT_FRAME_SRC
 #undef RT_K_ADVANCE
@@ -3525,6 +3575,14 @@ static PathsRaysKernel paths_rays_kernel(bool lds_tables, bool few_blocks, bool 
     return (lds_tables ? paths_rays_kernel_of<true> : paths_rays_kernel_of<false>)(few_blocks, verify);
 }
 
+// Keyed ray-table frames: k_paths_keyed (4-wide tree, the triangle-list definition of a hit, per-sample streams).  Full pool:
+// the build in which the waves draw their rows from the frame's counter; few blocks: rows tied to slots, gen() inside ADV.
+using PathsKeyedKernel = decltype(&k_paths_keyed<false, true, 4, true, false, false>);
+static PathsKeyedKernel paths_keyed_kernel(bool lds_tables, bool few_blocks) {
+    if (few_blocks) return lds_tables ? k_paths_keyed<true, true, 2, false, false, false> : k_paths_keyed<false, true, 2, false, false, false>;
+    return lds_tables ? k_paths_keyed<true, true, 4, true, false, false> : k_paths_keyed<false, true, 4, true, false, false>;
+}
+
 // Global overflow part of the traversal stacks: `levels` entries for each of kOverStride lanes.  Every OWNER of
 // concurrently running grids has its own buffer -- a render context (one render at a time: Context::busy), or one
 // call of a stage-level test entry point -- because a lane indexes its column by its position in ITS grid only:
@@ -3575,9 +3633,12 @@ int ensure_rng(Context &c, uint64_t seed, int slot_lo, hipStream_t st, double *s
 // validated the table on the device; `camera` is not looked at): camera ray c is row c of the table, the frame is
 // rays->n_rays camera rays over width * height = n_pixels x 1 pixels, and `spp` is the rays_per_pixel of the c / spp rule.
 // Everything else -- context, RNG, stacks, launch parameters, the lockstep final generation, stats -- is one body.
+// `keyed` (rt_render_rays_keyed_*; the caller sets RT_FLAG_RNG_PER_SAMPLE): `keyed_table` instead of `table`, k_paths_keyed.
 struct RayFrame {
     RayTable table;
     long long n_rays;
+    bool keyed = false;
+    KeyedRayTable keyed_table{};
 };
 int render_shard_impl(const rt_scene *scene, const rt_camera *camera, int width, int height, int spp,
                       int max_bounces, uint64_t seed, int shard_index, int shard_count, uint32_t flags,
@@ -3826,7 +3887,11 @@ int render_shard_impl(const rt_scene *scene, const rt_camera *camera, int width,
         if (const char *e = knob("RT_PRIO_ROTATE")) prio_rotate = atoi(e);
         HIP_TRY(hipEventRecord(c.ev_a, st));
         // (the reference-walk build is passed top_n = 0, while top_n * 64 bytes of LDS stay reserved and reported in reserved[2])
-        if (rays) {
+        if (rays && rays->keyed) {
+            hipLaunchKernelGGL(paths_keyed_kernel(lds_tables, few_blocks), grid_paths, block, lds_paths, st, sc, c.pools, rays->keyed_table, ap,
+                               d_sum, c.d_rows, paths_cap, d_over2, adv_batch, dbg, paths_prof, top_n, prio_rotate, rot_wave, rot_set, gen_batch,
+                               tri_follow, &c.d_ctr->pad2[0], &c.d_ctr->vstat[0]);
+        } else if (rays) {
             hipLaunchKernelGGL(paths_rays_kernel(lds_tables, few_blocks, verify), grid_paths, block, lds_paths, st, sc, c.pools, table, ap, d_sum,
                                c.d_rows, paths_cap, d_over2, adv_batch, dbg, paths_prof, top_n, prio_rotate, rot_wave, rot_set, gen_batch,
                                tri_follow, &c.d_ctr->pad2[0], &c.d_ctr->vstat[0]);
@@ -4259,6 +4324,79 @@ static int render_rays_impl(const rt_scene *scene, int64_t n_rays, const float *
     return render_shard_impl(scene, nullptr, n_pixels, 1, d_pixel ? 1 : rays_per_pixel, max_bounces, seed, 0, 1, flags, d_sum, st, stats, 0, &rays);
 }
 
+// rt_render_rays_keyed_device / rt_render_rays_keyed_fixed_device: render_rays_impl's checks and prepass, the checks of the
+// keys, then the frame through render_shard_impl in the per-sample mode (full pool, no parking, no lockstep final
+// generation) with k_paths_keyed: row c's stream is rng_sample_stream(seed, key_first + c * key_stride).
+static int render_rays_keyed_impl(const rt_scene *scene, int64_t n_rays, const float *d_o, const float *d_d, const int32_t *d_pixel,
+                                  int rays_per_pixel, int n_pixels, int max_bounces, uint64_t seed, uint64_t key_first,
+                                  uint32_t key_stride, uint32_t flags, float *d_sum, hipStream_t st, rt_stats *stats) {
+    const std::string w((flags & kFlagFixedFb) ? "rt_render_rays_keyed_fixed_device" : "rt_render_rays_keyed_device");
+    if (!scene) return fail(w + ": null scene");
+    if (!d_o || !d_d || !d_sum) return fail(w + ": null " + (!d_o ? "d_origin_xyz" : !d_d ? "d_dir_xyz" : "sum buffer"));
+    if (flags & RT_FLAG_REFERENCE_WALK) return fail(w + ": RT_FLAG_REFERENCE_WALK is not supported for keyed ray tables");
+    // (RT_FLAG_RNG_PER_SAMPLE and RT_FLAG_WATERTIGHT are what the mode is: accepted, and change nothing)
+    if (flags & ~(uint32_t)(RT_FLAG_RNG_PER_SAMPLE | RT_FLAG_WATERTIGHT | RT_FLAG_TIME_KERNELS | kFlagFixedFb))
+        return fail(w + ": flags other than RT_FLAG_RNG_PER_SAMPLE / RT_FLAG_WATERTIGHT / RT_FLAG_TIME_KERNELS");
+    if (n_rays < 1) return fail(w + ": n_rays = " + std::to_string((long long)n_rays) + " (at least 1)");
+    if (n_rays + 13LL * kW >= (1LL << 31)) return fail(w + ": n_rays exceeds the int32 camera-ray range of one call");
+    if (n_pixels < 1 || n_pixels > 0x7fffffff / 3) return fail(w + ": n_pixels = " + std::to_string(n_pixels) + " is outside 1 .. 715827882");
+    if (max_bounces < 0 || max_bounces > (1 << 24)) return fail(w + ": max_bounces is outside 0 .. 16777216");
+    if (key_stride < 1) return fail(w + ": key_stride = 0 (at least 1)");
+    // the last key, key_first + (n_rays - 1) * key_stride: the product is below 2^63, the sum must not wrap 2^64
+    const unsigned long long span = (unsigned long long)(n_rays - 1) * key_stride;
+    if (span > ~0ull - (unsigned long long)key_first)
+        return fail(w + ": the key of the last ray, " + std::to_string((unsigned long long)key_first) + " + " + std::to_string(span) + ", wraps 2^64");
+    const unsigned long long key_last = (unsigned long long)key_first + span;
+    if (!d_pixel) {
+        if (rays_per_pixel < 1) return fail(w + ": rays_per_pixel = " + std::to_string(rays_per_pixel) + " (at least 1 when d_pixel is null)");
+        if (key_last / (unsigned)rays_per_pixel >= (unsigned long long)n_pixels)
+            return fail(w + ": key " + std::to_string(key_last) + " falls on pixel " + std::to_string(key_last / (unsigned)rays_per_pixel) + " of " +
+                        std::to_string(n_pixels));
+    }
+    if (!scene->wide) return fail(w + ": keyed ray tables need the 4-wide tree (the scene was created with RT_BVH_WIDE=0)");
+    if (const char *e = knob("RT_PERSISTENT"))
+        if (atoi(e) == 0) return fail(w + ": keyed ray tables run on the persistent kernel only (RT_PERSISTENT=0 is set)");
+    DeviceGuard dev;
+    if (dev.enter(scene->device)) return 1;
+    const int n = (int)n_rays;
+    {
+        rt_scene::QueryState &q = scene->query;
+        std::lock_guard<std::mutex> lock(q.mutex);
+        if (!q.d_words) {  // (as the first query of this scene)
+            HIP_TRY(hipDeviceGetAttribute(&q.cus, hipDeviceAttributeMultiprocessorCount, scene->device));
+            HIP_TRY(hipHostMalloc((void **)&q.h_words, sizeof(QueryWords), hipHostMallocDefault));
+            HIP_TRY(hipMalloc((void **)&q.d_words, sizeof(QueryWords)));
+        }
+        const dim3 grid(std::min((n + kBlock - 1) / kBlock, 8 * std::max(q.cus, 1)));
+        HIP_TRY(hipMemsetAsync(q.d_words, 0, sizeof(QueryWords), st));
+        hipLaunchKernelGGL(k_query_prepass, grid, dim3(kBlock), 0, st, d_o, d_d, n, q.d_words);
+        if (d_pixel) hipLaunchKernelGGL(k_pixel_prepass, grid, dim3(kBlock), 0, st, d_pixel, n, n_pixels, q.d_words);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(q.h_words, q.d_words, 6 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (q.h_words->bad_dirs != 0)
+            return fail(w + ": " + std::to_string(q.h_words->bad_dirs) + " of " + std::to_string(n) + " directions are not finite or reach 2^126");
+        if (q.h_words->bad_pixels != 0)
+            return fail(w + ": " + std::to_string(q.h_words->bad_pixels) + " of " + std::to_string(n) + " pixel indices are outside 0 .. " + std::to_string(n_pixels - 1));
+        float need[3];
+        memcpy(need, q.h_words->radius_bits, sizeof(need));
+        if (int rc = ensure_origin_radius(scene, need)) return rc;
+    }
+    const uint32_t rpp = d_pixel ? 1u : (uint32_t)rays_per_pixel;
+    RayFrame rays;
+    rays.table = RayTable{};
+    rays.n_rays = n_rays;
+    rays.keyed = true;
+    rays.keyed_table = KeyedRayTable{d_o, d_d, d_pixel, (unsigned long long)key_first, key_stride, rpp,
+                                     d_pixel ? 0 : (int)(key_first / rpp), d_pixel ? 0u : (uint32_t)(key_first % rpp)};
+    const uint32_t mode = (flags & (RT_FLAG_TIME_KERNELS | kFlagFixedFb)) | RT_FLAG_RNG_PER_SAMPLE;
+    if (int rc = render_shard_impl(scene, nullptr, n_pixels, 1, (int)rpp, max_bounces, seed, 0, 1, mode, d_sum, st, stats, 0, &rays)) {
+        fail(w + ": " + g_last_error);  // (what the frame itself refused, under this entry point's name)
+        return rc;
+    }
+    return 0;
+}
+
 }  // namespace
 
 // ============================================================================ C-ABI
@@ -4506,6 +4644,23 @@ int rt_render_rays_device(const rt_scene *scene, int64_t n_rays, const float *d_
     if (flags & kFlagFixedFb) return fail("rt_render_rays_device: unknown flag 0x200");
     return render_rays_impl(scene, n_rays, d_origin_xyz, d_dir_xyz, d_pixel, rays_per_pixel, n_pixels, max_bounces, seed, flags, d_sum_rgb,
                             (hipStream_t)stream, stats);
+}
+
+int rt_render_rays_keyed_device(const rt_scene *scene, int64_t n_rays, const float *d_origin_xyz, const float *d_dir_xyz,
+                                const int32_t *d_pixel, int rays_per_pixel, int n_pixels, int max_bounces, uint64_t seed,
+                                uint64_t key_first, uint32_t key_stride, uint32_t flags, float *d_sum_rgb, void *stream, rt_stats *stats) {
+    if (flags & kFlagFixedFb) return fail("rt_render_rays_keyed_device: unknown flag 0x200");
+    return render_rays_keyed_impl(scene, n_rays, d_origin_xyz, d_dir_xyz, d_pixel, rays_per_pixel, n_pixels, max_bounces, seed, key_first,
+                                  key_stride, flags, d_sum_rgb, (hipStream_t)stream, stats);
+}
+
+int rt_render_rays_keyed_fixed_device(const rt_scene *scene, int64_t n_rays, const float *d_origin_xyz, const float *d_dir_xyz,
+                                      const int32_t *d_pixel, int rays_per_pixel, int n_pixels, int max_bounces, uint64_t seed,
+                                      uint64_t key_first, uint32_t key_stride, uint32_t flags, int64_t *d_sum_fixed, void *stream,
+                                      rt_stats *stats) {
+    if (flags & kFlagFixedFb) return fail("rt_render_rays_keyed_fixed_device: unknown flag 0x200");
+    return render_rays_keyed_impl(scene, n_rays, d_origin_xyz, d_dir_xyz, d_pixel, rays_per_pixel, n_pixels, max_bounces, seed, key_first,
+                                  key_stride, flags | kFlagFixedFb, (float *)d_sum_fixed, (hipStream_t)stream, stats);
 }
 
 int rt_render_rays_fixed_device(const rt_scene *scene, int64_t n_rays, const float *d_origin_xyz, const float *d_dir_xyz,

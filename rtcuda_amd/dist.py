@@ -27,6 +27,31 @@ def owner_of_camera_ray(camera_ray_id: int, world: int) -> int:
     return (camera_ray_id % W) // (W // world)
 
 
+def ray_chunk(rank: int, world: int, n_rays: int):
+    """(first, count) of the rows of an ``n_rays``-row keyed ray table that ``rank`` of ``world`` renders: contiguous chunks,
+    as even as possible (the first ``n_rays % world`` ranks hold one row more), that cover the table once.  ``count`` is 0
+    for the ranks beyond a table of fewer rows than ranks: such a rank renders nothing and still joins the reduce.
+
+    The N-rank table frame -- every rank holds (or fills) only its own rows, and the frame is the one-GPU frame bit for bit,
+    because row G has the stream of key G whoever renders it (Scene.render_rays_keyed)::
+
+        first, count = ray_chunk(rank, world, n_rays)
+        sums = torch.zeros((n_pixels, 3), dtype=torch.int64, device="cuda")
+        if count:
+            scene.render_rays_keyed(origins[first:first + count], dirs[first:first + count], n_pixels, rays_per_pixel=spp,
+                                    key_first=first, fixed=True, out=sums)
+        reduce_raw_sums(sums)  # ONE reduce(SUM) of the int64 sums; rt_post_process_fixed on rank 0
+    """
+    if world <= 0:
+        raise ValueError("world size must be positive")
+    if not 0 <= rank < world:
+        raise ValueError("rank out of range")
+    if n_rays < 0:
+        raise ValueError("n_rays must not be negative")
+    base, extra = divmod(n_rays, world)
+    return rank * base + min(rank, extra), base + (1 if rank < extra else 0)
+
+
 def reduce_raw_sums(local_sum, dst: int = 0, group=None):
     """Sum-reduce the per-rank raw framebuffers to ``dst`` (in place on ``dst``).  Works on any
     torch.distributed backend: "nccl" (= RCCL) on the GPUs, "gloo" in the CPU tests."""
