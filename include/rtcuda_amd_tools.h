@@ -72,6 +72,37 @@ int rt_split_probe(const rt_scene *scene, const rt_camera *camera, int width, in
 int rt_scene_tree_copy(const rt_scene *scene, void *records, int64_t cap_records, int32_t *order, int64_t cap_order,
                        int64_t *out2);
 
+/* The product's shading FUNCTIONS on a table of inputs, one lane per row: the device side of the reference pins
+ * (tests/golden/ref_shade_fixture.npz).  `func` and the row layouts are those of oracle/ref_shade_driver.cpp, 32-bit words in
+ * and out, for the ten functions the device has as functions of their own:
+ *    1 sample_f, 2 get_f, 6 intersect, 7 offset_ray_origin, 8 power_heuristic, 9 same_hemisphere, 10 reflect,
+ *    11 refract (4 arguments), 12 uniform_sample_sphere, 13 get_ray
+ * with two differences.  Where the driver's row ends in two uniforms (1 and 12), the row here ends in the six words of an
+ * XORWOW state {d, v0 .. v4} instead -- the state the lane's generator starts from (17 and 6 words in); `draws` comes out as
+ * the number of draws made from it.  And sample_f writes one word more, 12 in all: again_draws, what a second call with the
+ * same arguments would consume.  intersect: t, u, v are the device function's, meaningful on a hit only.
+ * in_words and out_words are HOST arrays of n_rows rows; out_words is copied to the device first, so a word no lane writes
+ * keeps the caller's value.  Any other func (3 sample_Li, 4 pdf_Li and 5 sample_p have no device function of their own:
+ * rt_shade_records) is an error; n_rows = 0 succeeds.  No reference counterpart. */
+int rt_shade_table(int func, int n_rows, const uint32_t *in_words, uint32_t *out_words);
+
+/* The product's init() + mat() -- advance_core as the persistent kernel compiles it, through the shading probe of
+ * rt_split_probe -- on n path states of the caller's, one lane each, against a scene of THIS library's rt_scene_create.
+ * records_in: n rows of RT_SHADE_RECORD_IN words: bounces, hit_info (-1 = a miss, else material | (light + 1) << 16),
+ * pixel, gen, XORWOW state d v0 .. v4, beta 3, wo 3, isect_p 3, isect_n 3.  Every row names a pixel of its own in 0 .. n - 1.
+ * records_out: n rows of RT_SHADE_RECORD_OUT words: the next ray o d (0 - 5, written when the state shades), the shadow ray
+ * o d (6 - 11), its tmax (12: -1.0f when there is none), its radiance (13 - 15) and the triangle it must not hit (16: the
+ * caller's index, -1 for a point light), beta (17 - 19), the XORWOW state (20 - 25), bounces (26), and the three floats of
+ * pixel i of a framebuffer that was zero before the launch (27 - 29: the bounce-0 emission of the record that names pixel
+ * i).  Words the kernel does not write (no new ray, no shadow ray) hold RT_SHADE_UNWRITTEN.
+ * lds_tables: 1 = the build that stages the shading tables in LDS (an error with more than 64 materials or lights), 0 = the
+ * build that reads them from global memory.  The BSDF-sampled MIS ray of mat() does not exist on the device (its draws are
+ * burnt), so Light::pdf_Li has no counterpart here.  No reference counterpart. */
+enum { RT_SHADE_RECORD_IN = 22, RT_SHADE_RECORD_OUT = 30 };
+#define RT_SHADE_UNWRITTEN 0xffffffffu
+int rt_shade_records(const rt_scene *scene, int max_bounces, int lds_tables, int n, const uint32_t *records_in,
+                     uint32_t *records_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1363,10 +1363,115 @@ struct PathTotals {
     int64_t shades = 0, any_rays = 0, closest_rays = 0, emission_adds = 0, ah_adds = 0, ch_adds = 0, rr_draws = 0, rr_kills = 0;
 };
 
+// One init() + mat() of the estimator on one path state: everything per_sample_path does between two traversals, and
+// nothing else -- the rays it wants traced are handed back, not traced.  per_sample_path below runs every path through it;
+// orc_mat_step runs it on a single state (the shading-record tests hold the kernels' advance_core to it).
+struct StepIn {
+    bool hit;
+    int mat, light;  // of the hit primitive (light = -1: none); read only when hit
+    V3 wo, isect_p, isect_n;
+};
+struct StepOut {
+    bool ended = false;       // no mat(): no bounce left, a miss, or killed in every init() up to the last bounce
+    bool emitted = false;     // bounce-0 emission (init() :98-103)
+    bool has_shadow = false;  // the light-sampled shadow ray: worth shadow_L if traverse_any(shadow_excluded) finds nothing
+    bool has_mis = false;     // the BSDF-sampled MIS ray: worth mis_L if its closest hit is the SHADING triangle (Appendix A.3)
+    V3 emission, shadow_L, mis_L;
+    Ray ray, shadow, mis;     // ray: the next path ray (valid unless ended)
+    int shadow_excluded = -1;
+    int rr_draws = 0, rr_kills = 0;
+};
+StepOut mat_step(const Scene &sc, int max_bounces, const StepIn &in, V3 &beta, int &bounces, Xorwow &rs) {
+    StepOut out;
+    out.emission = out.shadow_L = out.mis_L = mk(0, 0, 0);
+    const int num_lights = (int)sc.lights.size();
+    // ---- init() :84-137
+    if (bounces == 0 && in.hit && in.light >= 0) {
+        out.emission = sc.lights[in.light].L;
+        out.emitted = true;
+    }
+    out.ended = true;
+    if (!(bounces < max_bounces)) return out;  // no bounce left
+    if (!in.hit) return out;                   // a miss: the slot would idle, drawing nothing, until gen()
+    if (bounces > kRrStart && max3(beta) < kRrThreshold) {
+        const float pt = fmaxf(0.05f, 1 - max3(beta));
+        bool alive = false;
+        while (true) {  // consecutive init() calls: a killed path is rolled again by the next one (Appendix A.1)
+            out.rr_draws++;
+            const bool kill = rnd(rs) < pt;
+            bounces++;
+            if (!kill) {
+                beta = divf(beta, 1 - pt);
+                alive = true;
+                break;
+            }
+            out.rr_kills++;
+            if (!(bounces < max_bounces)) break;
+        }
+        if (!alive) return out;
+    } else {
+        bounces++;
+    }
+    out.ended = false;
+    // ---- mat() :139-248
+    const Material &m = sc.mats[in.mat];
+    const V3 wo = in.wo, isect_p = in.isect_p, isect_n = in.isect_n;
+    const V3 multiplier = scale(beta, (float)num_lights);
+    {
+        V3 n = isect_n, wi;
+        float pdf;
+        V3 f = mat_sample_f(m, wo, rs, n, wi, pdf);
+        out.ray = spawn_offset_ray(isect_p, n, wi);
+        beta = mul(beta, divf(scale(f, dot(wi, n)), pdf));
+    }
+    if (num_lights == 0) return out;
+    const int light_idx = std::min((int)(rnd(rs) * num_lights), num_lights - 1);
+    const Light light = sc.lights[light_idx];
+    {
+        V3 wi, Li;
+        float lt, lpdf;
+        if (light_sample_Li(sc, light, isect_p, rs, wi, Li, lt, lpdf)) {
+            V3 n = dot(isect_n, wi) > 0.f ? isect_n : neg(isect_n);
+            V3 f;
+            float spdf;
+            if (mat_get_f(m, wo, wi, n, f, spdf)) {
+                f = scale(f, dot(wi, n));
+                out.shadow = spawn_offset_ray(isect_p, n, wi, lt);
+                if (light.type == 0) {
+                    out.shadow_L = divf(mul(mul(multiplier, f), Li), lpdf);
+                } else {
+                    float weight = power_heuristic(lpdf, spdf);
+                    out.shadow_L = divf(scale(mul(mul(multiplier, f), Li), weight), lpdf);
+                }
+                out.shadow_excluded = light.type == 1 ? light.tri : -1;
+                out.has_shadow = true;
+            }
+        }
+    }
+    if (light.type != 0) {  // the BSDF-sampled shadow ray: its draws count, its target is the SHADING triangle (Appendix A.3)
+        V3 n = isect_n, wi;
+        float spdf;
+        V3 f = mat_sample_f(m, wo, rs, n, wi, spdf);
+        f = scale(f, dot(wi, n));
+        float weight = 1.f;
+        bool spawn = true;
+        if (!(m.type == 1 || m.type == 2)) {
+            float lpdf = light_pdf_Li(sc, light, isect_p, wi);
+            if (lpdf == 0.f) spawn = false;
+            else weight = power_heuristic(spdf, lpdf);
+        }
+        if (spawn) {
+            out.mis = spawn_offset_ray(isect_p, n, wi);
+            out.mis_L = divf(scale(mul(mul(multiplier, f), light.L), weight), spdf);
+            out.has_mis = true;
+        }
+    }
+    return out;
+}
+
 // One camera ray from gen() to the end of its path; returns the float sum of its contributions.
 V3 per_sample_path(const Scene &sc, const Camera &cam, int width, int height, int pixel, int max_bounces, Xorwow rs,
                    PathTotals &tot) {
-    const int num_lights = (int)sc.lights.size();
     const int i = pixel % width, j = pixel / width;
     const float jx = rnd(rs);  // x first, then y
     const float jy = rnd(rs);
@@ -1379,103 +1484,47 @@ V3 per_sample_path(const Scene &sc, const Camera &cam, int width, int height, in
         Isect is;
         is.t = is.u = is.v = 0.f;
         int prim_idx = -1;
-        V3 wo = ray.d;
-        const bool hit = traverse_closest(sc, ray, is, prim_idx, nullptr);
+        StepIn in;
+        in.wo = ray.d;
+        in.hit = traverse_closest(sc, ray, is, prim_idx, nullptr);
         tot.closest_rays++;
-        // ---- init() :84-137
-        if (bounces == 0 && hit) {
-            const int li = sc.prims[prim_idx].light;
-            if (li >= 0) {
-                sum = add(sum, sc.lights[li].L);
-                tot.emission_adds++;
-            }
+        in.mat = in.light = -1;
+        in.isect_p = in.isect_n = mk(0, 0, 0);
+        if (in.hit) {
+            const Prim &prim = sc.prims[prim_idx];
+            const Tri &tri = sc.tris[prim.tri];
+            in.mat = prim.mat;
+            in.light = prim.light;
+            in.isect_p = tri.p(is.u, is.v);
+            in.isect_n = neg(unit(tri.n));
         }
-        if (!(bounces < max_bounces)) break;  // no bounce left
-        if (!hit) break;                      // a miss: the slot would idle, drawing nothing, until gen()
-        if (bounces > kRrStart && max3(beta) < kRrThreshold) {
-            const float pt = fmaxf(0.05f, 1 - max3(beta));
-            bool alive = false;
-            while (true) {  // consecutive init() calls: a killed path is rolled again by the next one (Appendix A.1)
-                tot.rr_draws++;
-                const bool kill = rnd(rs) < pt;
-                bounces++;
-                if (!kill) {
-                    beta = divf(beta, 1 - pt);
-                    alive = true;
-                    break;
-                }
-                tot.rr_kills++;
-                if (!(bounces < max_bounces)) break;
-            }
-            if (!alive) break;
-        } else {
-            bounces++;
+        // ---- init() + mat()
+        const StepOut so = mat_step(sc, max_bounces, in, beta, bounces, rs);
+        if (so.emitted) {
+            sum = add(sum, so.emission);
+            tot.emission_adds++;
         }
-        // ---- mat() :139-248
+        tot.rr_draws += so.rr_draws;
+        tot.rr_kills += so.rr_kills;
+        if (so.ended) break;
         tot.shades++;
-        const Prim &prim = sc.prims[prim_idx];
-        const Material &m = sc.mats[prim.mat];
-        const Tri &tri = sc.tris[prim.tri];
-        const V3 multiplier = scale(beta, (float)num_lights);
-        const V3 isect_p = tri.p(is.u, is.v);
-        const V3 isect_n = neg(unit(tri.n));
-        {
-            V3 n = isect_n, wi;
-            float pdf;
-            V3 f = mat_sample_f(m, wo, rs, n, wi, pdf);
-            ray = spawn_offset_ray(isect_p, n, wi);
-            beta = mul(beta, divf(scale(f, dot(wi, n)), pdf));
-        }
-        if (num_lights == 0) continue;
-        const int light_idx = std::min((int)(rnd(rs) * num_lights), num_lights - 1);
-        const Light light = sc.lights[light_idx];
-        {
-            V3 wi, Li;
-            float lt, lpdf;
-            if (light_sample_Li(sc, light, isect_p, rs, wi, Li, lt, lpdf)) {
-                V3 n = dot(isect_n, wi) > 0.f ? isect_n : neg(isect_n);
-                V3 f;
-                float spdf;
-                if (mat_get_f(m, wo, wi, n, f, spdf)) {
-                    f = scale(f, dot(wi, n));
-                    const Ray shadow = spawn_offset_ray(isect_p, n, wi, lt);
-                    V3 L;
-                    if (light.type == 0) {
-                        L = divf(mul(mul(multiplier, f), Li), lpdf);
-                    } else {
-                        float weight = power_heuristic(lpdf, spdf);
-                        L = divf(scale(mul(mul(multiplier, f), Li), weight), lpdf);
-                    }
-                    tot.any_rays++;
-                    if (!traverse_any(sc, light.type == 1 ? light.tri : -1, shadow, nullptr)) {  // ah() :278-294
-                        sum = add(sum, L);
-                        tot.ah_adds++;
-                    }
-                }
+        ray = so.ray;
+        if (so.has_shadow) {
+            tot.any_rays++;
+            if (!traverse_any(sc, so.shadow_excluded, so.shadow, nullptr)) {  // ah() :278-294
+                sum = add(sum, so.shadow_L);
+                tot.ah_adds++;
             }
         }
-        if (light.type != 0) {  // the BSDF-sampled shadow ray: its draws count, its target is the SHADING triangle (Appendix A.3)
-            V3 n = isect_n, wi;
-            float spdf;
-            V3 f = mat_sample_f(m, wo, rs, n, wi, spdf);
-            f = scale(f, dot(wi, n));
-            float weight = 1.f;
-            bool spawn = true;
-            if (!(m.type == 1 || m.type == 2)) {
-                float lpdf = light_pdf_Li(sc, light, isect_p, wi);
-                if (lpdf == 0.f) spawn = false;
-                else weight = power_heuristic(spdf, lpdf);
-            }
-            if (spawn) {
-                Ray shadow = spawn_offset_ray(isect_p, n, wi);
-                Isect sis;
-                sis.t = sis.u = sis.v = 0.f;
-                int sprim = -1;
-                tot.closest_rays++;
-                if (traverse_closest(sc, shadow, sis, sprim, nullptr) && sc.prims[sprim].tri == prim.tri) {
-                    sum = add(sum, divf(scale(mul(mul(multiplier, f), light.L), weight), spdf));
-                    tot.ch_adds++;
-                }
+        if (so.has_mis) {
+            Ray shadow = so.mis;
+            Isect sis;
+            sis.t = sis.u = sis.v = 0.f;
+            int sprim = -1;
+            tot.closest_rays++;
+            if (traverse_closest(sc, shadow, sis, sprim, nullptr) && sc.prims[sprim].tri == sc.prims[prim_idx].tri) {
+                sum = add(sum, so.mis_L);
+                tot.ch_adds++;
             }
         }
     }
@@ -1730,6 +1779,37 @@ void orc_uniform_sample_sphere(uint32_t *state6, float *out3) {
     state_out(st, state6);
 }
 
+// uniform_sample_sphere on n rows of two raw draws each: the state that makes exactly those two draws next is built here
+// (as tests/shade_scenes.py xorwow_state_for builds it: d = 0, v4 = 0, word k chosen so that draw k comes out as asked), the
+// oracle's own function runs on it.  out4 = x y z and the draws consumed (d / the Weyl constant).
+static uint32_t xorwow_inv_g(uint32_t a) {  // x with t ^ (t << 1) = a, t = x ^ (x >> 2)
+    uint32_t t = a;
+    for (int s = 1; s < 32; s <<= 1) t ^= t << s;
+    uint32_t x = t;
+    for (int s = 2; s < 32; s <<= 1) x ^= x >> s;
+    return x;
+}
+void orc_uniform_sample_sphere_raws(int64_t n, const uint32_t *raws2, float *out4) {
+    const uint32_t weyl = 362437u, weyl_inv = 945708813u;  // weyl * weyl_inv = 1 mod 2^32
+    static_assert((uint32_t)(362437u * 945708813u) == 1u, "inverse of the Weyl constant");
+    for (int64_t i = 0; i < n; i++) {
+        Xorwow st;
+        st.d = 0;
+        memset(st.v, 0, 20);
+        uint32_t newest = 0, d = 0;
+        for (int k = 0; k < 2; k++) {
+            d += weyl;
+            const uint32_t want = raws2[2 * i + k] - d;
+            st.v[k] = xorwow_inv_g(want ^ (newest ^ (newest << 4)));
+            newest = want;
+        }
+        V3 r = uniform_sample_sphere(st);
+        memcpy(out4 + 4 * i, &r, 12);
+        const uint32_t draws = st.d * weyl_inv;
+        memcpy(out4 + 4 * i + 3, &draws, 4);
+    }
+}
+
 // ---- scene
 struct orc_scene {
     Scene sc;
@@ -1756,6 +1836,59 @@ orc_scene *orc_scene_create(const float *tri_p0p1p2, int n_tris, const int32_t *
     return h;
 }
 void orc_scene_destroy(orc_scene *h) { delete h; }
+
+// One init() + mat() (mat_step: the code per_sample_path runs) on each of n path states against a scene.  A state is 22 words:
+// bounces, hit_info (-1 = a miss, else material | (light + 1) << 16), pixel, gen, rng d v0..v4, beta 3, wo 3, isect_p 3,
+// isect_n 3.  Per state 31 words come back: next ray o d (0-5), shadow ray o d (6-11), its tmax or -1 without one (12), its
+// radiance (13-15) and excluded triangle (16: the caller's index, -1 for a point light), beta (17-19), rng (20-25), bounces
+// (26), the bounce-0 emission or zeros (27-29), flags (30: 1 a new ray, 2 a shadow ray, 4 emitted).  Words that a flag says
+// do not exist are zero.  The BSDF-sampled MIS ray is made (its draws count) and dropped.
+void orc_mat_step(const orc_scene *h, int max_bounces, int n, const uint32_t *in22, uint32_t *out31) {
+    const Scene &sc = h->sc;
+    for (int i = 0; i < n; i++) {
+        const uint32_t *r = in22 + 22 * (size_t)i;
+        uint32_t *w = out31 + 31 * (size_t)i;
+        memset(w, 0, 31 * 4);
+        float f[22];
+        memcpy(f, r, sizeof(f));
+        int bounces = (int32_t)r[0];
+        const int32_t hit_info = (int32_t)r[1];
+        Xorwow rs = state_in(r + 4);
+        V3 beta = mk(f[10], f[11], f[12]);
+        StepIn in;
+        in.hit = hit_info >= 0;
+        in.mat = hit_info & 0xffff;
+        in.light = in.hit ? ((hit_info >> 16) & 0xffff) - 1 : -1;
+        in.wo = mk(f[13], f[14], f[15]);
+        in.isect_p = mk(f[16], f[17], f[18]);
+        in.isect_n = mk(f[19], f[20], f[21]);
+        const StepOut so = mat_step(sc, max_bounces, in, beta, bounces, rs);
+        uint32_t flags = 0;
+        if (!so.ended) {
+            memcpy(w, &so.ray.o, 12);
+            memcpy(w + 3, &so.ray.d, 12);
+            flags |= 1;
+        }
+        float tmax = -1.f;
+        if (so.has_shadow) {
+            memcpy(w + 6, &so.shadow.o, 12);
+            memcpy(w + 9, &so.shadow.d, 12);
+            tmax = so.shadow.tmax;
+            memcpy(w + 13, &so.shadow_L, 12);
+            w[16] = (uint32_t)so.shadow_excluded;
+            flags |= 2;
+        }
+        memcpy(w + 12, &tmax, 4);
+        memcpy(w + 17, &beta, 12);
+        state_out(rs, w + 20);
+        w[26] = (uint32_t)bounces;
+        if (so.emitted) {
+            memcpy(w + 27, &so.emission, 12);
+            flags |= 4;
+        }
+        w[30] = flags;
+    }
+}
 
 // out: [num_nodes, num_prims, max_depth, num_leaves, leaf_hist[1..8]]
 void orc_scene_bvh_stats(const orc_scene *h, int64_t *out12, float *root_bounds6) {

@@ -92,6 +92,8 @@ class Oracle:
         L.orc_reflect.argtypes = [_fp, _fp, _fp]
         L.orc_refract.argtypes = [_fp, _fp, ctypes.c_float, ctypes.c_float, _fp]
         L.orc_uniform_sample_sphere.argtypes = [_u32p, _fp]
+        L.orc_uniform_sample_sphere_raws.argtypes = [ctypes.c_int64, _u32p, _fp]
+        L.orc_mat_step.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, _u32p, _u32p]
         L.orc_scene_create.argtypes = [_fp, ctypes.c_int, _fp, _fp, ctypes.c_void_p, ctypes.c_int,
                                        ctypes.c_void_p, ctypes.c_int]
         L.orc_scene_create.restype = ctypes.c_void_p
@@ -253,6 +255,24 @@ class Oracle:
         out = np.zeros(3, np.float32)
         self.lib.orc_uniform_sample_sphere(_ptr(state), _ptr(out))
         return out
+
+    def uniform_sample_sphere_raws(self, raws2) -> np.ndarray:
+        """uniform_sample_sphere on every row of two raw draws -> (n, 4) uint32: x y z as bit patterns, and the draws consumed."""
+        raws2 = np.ascontiguousarray(raws2, np.uint32)
+        assert raws2.ndim == 2 and raws2.shape[1] == 2, raws2.shape
+        out = np.zeros((raws2.shape[0], 4), np.uint32)
+        self.lib.orc_uniform_sample_sphere_raws(raws2.shape[0], _ptr(raws2), _ptr(out))
+        return out
+
+    def mat_step(self, scene: "OracleScene", records, max_bounces: int):
+        """One init() + mat() (the code per_sample_path runs) on each path state ((n, 22) uint32, the layout of the device's
+        shading records) -> (words (n, 27) uint32 in the device's output layout, emission (n, 3) uint32, flags (n,): 1 a new
+        ray, 2 a shadow ray, 4 emitted).  Words whose flag is off are zero."""
+        records = np.ascontiguousarray(records, np.uint32)
+        assert records.ndim == 2 and records.shape[1] == 22, records.shape
+        out = np.zeros((records.shape[0], 31), np.uint32)
+        self.lib.orc_mat_step(scene.h, int(max_bounces), records.shape[0], _ptr(records), _ptr(out))
+        return out[:, :27].copy(), out[:, 27:30].copy(), out[:, 30].copy()
 
     # ------------------------------------------------------------------ ray log (traversal audit)
     def raylog_enable(self, on: bool = True) -> None:

@@ -41,7 +41,7 @@ EXPORTS = [
 # the lab (include/rtcuda_amd_tools.h, librtcuda_amd_tools.so): measurement tools, not part of the drop-in C-ABI
 TOOLS_LIB_PATH = os.path.join(_PKG, "librtcuda_amd_tools.so")
 TOOLS_EXPORTS = ["rt_measure_copy_bandwidth", "rt_calibrate_valu", "rt_calibrate_valu_packed", "rt_probe_issue", "rt_split_probe",
-                 "rt_scene_tree_copy"]
+                 "rt_scene_tree_copy", "rt_shade_table", "rt_shade_records"]
 
 
 class RtError(RuntimeError):
@@ -187,6 +187,8 @@ def tools_lib():
     L.rt_probe_issue.argtypes = [ci, ci, ci, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
     L.rt_split_probe.argtypes = [vp, vp, ci, ci, ci, ci, ctypes.c_uint64, ctypes.c_int64, vp, ci]
     L.rt_scene_tree_copy.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_int64, vp]
+    L.rt_shade_table.argtypes = [ci, ci, vp, vp]
+    L.rt_shade_records.argtypes = [vp, ci, ci, ci, vp, vp]
     _tools = L
     return L
 
@@ -718,6 +720,37 @@ def split_probe(scene: "Scene", camera: np.ndarray, width: int, height: int, spp
     _check(tools_lib().rt_split_probe(scene.h, _p(cam), width, height, spp, max_bounces, seed, target_rays, _p(out), len(out)),
            "rt_split_probe", tools_lib())
     return dict(zip(PROBE_FIELDS, out.tolist()))
+
+
+# rt_shade_table: words per row in / out, by function id (include/rtcuda_amd_tools.h: the reference pins' layouts, with the
+# two uniforms of sample_f and uniform_sample_sphere replaced by the six words of an XORWOW state, and again_draws added)
+SHADE_TABLE_WORDS_IN = {1: 17, 2: 14, 6: 16, 7: 6, 8: 2, 9: 9, 10: 6, 11: 8, 12: 6, 13: 14}
+SHADE_TABLE_WORDS_OUT = {1: 12, 2: 5, 6: 4, 7: 3, 8: 1, 9: 1, 10: 3, 11: 3, 12: 4, 13: 6}
+SHADE_RECORD_IN, SHADE_RECORD_OUT, SHADE_UNWRITTEN = 22, 30, 0xFFFFFFFF
+
+
+def shade_table(func: int, rows: np.ndarray, fill: int = 0) -> np.ndarray:
+    """The product's shading function `func` on every row of `rows` ((n, words in) uint32), one lane per row (rt_shade_table)
+    -> (n, words out) uint32.  Words no lane writes come back as `fill`."""
+    rows = np.ascontiguousarray(rows, np.uint32)
+    if func in SHADE_TABLE_WORDS_IN and (rows.ndim != 2 or rows.shape[1] != SHADE_TABLE_WORDS_IN[func]):
+        raise RtError(f"shade_table: function {func} takes rows of {SHADE_TABLE_WORDS_IN[func]} words, got {rows.shape}")
+    out = np.full((rows.shape[0], SHADE_TABLE_WORDS_OUT.get(func, 1)), fill, np.uint32)
+    _check(tools_lib().rt_shade_table(int(func), rows.shape[0], _p(rows), _p(out)), "rt_shade_table", tools_lib())
+    return out
+
+
+def shade_records(scene: "Scene", records: np.ndarray, max_bounces: int, lds_tables: bool) -> np.ndarray:
+    """The product's init() + mat() on path states ((n, 22) uint32; rt_shade_records) -> (n, 30) uint32."""
+    if scene.L is not tools_lib():
+        raise RtError("shade_records: the scene must be created with library=tools_lib()")
+    records = np.ascontiguousarray(records, np.uint32)
+    if records.ndim != 2 or records.shape[1] != SHADE_RECORD_IN:
+        raise RtError(f"shade_records: records must have shape (n, {SHADE_RECORD_IN}), got {records.shape}")
+    out = np.zeros((records.shape[0], SHADE_RECORD_OUT), np.uint32)
+    _check(tools_lib().rt_shade_records(scene.h, int(max_bounces), int(bool(lds_tables)), records.shape[0], _p(records), _p(out)),
+           "rt_shade_records", tools_lib())
+    return out
 
 
 def render(width: int, height: int, num_samples: int, max_bounces: int, camera: np.ndarray, scene: Scene,

@@ -7,6 +7,8 @@
 //   rt_probe_issue              cycles per instruction of one wave, by instruction kind and occupancy
 //   rt_split_probe              "one persistent kernel, or the reference's stage split?" priced on dense ray / shade arrays
 //   rt_scene_tree_copy          a scene's unpadded 4-wide records and leaf order (the device builder against its host twin)
+//   rt_shade_table              the product's shading FUNCTIONS (rt_device.h), one lane per row of a function table
+//   rt_shade_records            the product's init() + mat() (advance_core, through k_probe_shade) on the caller's path states
 // The product library (librtcuda_amd.so) contains none of this.  The tools library also carries a private copy of the
 // product's entry points (same source); a scene handed to rt_split_probe must come from THIS library's rt_scene_create
 // (rtcuda_amd/api.py: Scene(arrays, library=tools_lib())).
@@ -292,6 +294,99 @@ k_probe_shade(DScene sc, Camera cam, AdvanceParams ap, const float *__restrict__
     w[24 * (size_t)cap] = __uint_as_float(st.rs.v3);
     w[25 * (size_t)cap] = __uint_as_float(st.rs.v4);
     w[26 * (size_t)cap] = __int_as_float(st.bounces);
+}
+
+
+// ============================================================================ function tables (rt_shade_table)
+// One lane per row of a table of inputs for ONE of the product's shading functions (rt_device.h; camera_get_ray and
+// tri_intersect as the render kernels call them): the rows are those of the reference pins (oracle/ref_shade_driver.cpp
+// lists the layouts), so a wave holds whatever the table holds side by side -- matte, mirror and glass rows, hits and
+// misses.  Nothing is computed here: the words are unpacked, the function is called, its results are packed.
+constexpr uint32_t kWeylInv = 945708813u;  // 362437 * kWeylInv = 1 mod 2^32: draws made = (d - d at the start) * kWeylInv
+static_assert((uint32_t)(362437u * kWeylInv) == 1u, "inverse of XORWOW's Weyl constant");
+constexpr int kShadeTableIn[14] = {0, 17, 14, 0, 0, 0, 16, 6, 2, 9, 6, 8, 6, 14};   // 0: no device function of its own
+constexpr int kShadeTableOut[14] = {0, 12, 5, 0, 0, 0, 4, 3, 1, 1, 3, 3, 4, 6};
+__device__ __forceinline__ V3 tab_v3(const uint32_t *w) { return mk(__uint_as_float(w[0]), __uint_as_float(w[1]), __uint_as_float(w[2])); }
+__device__ __forceinline__ void tab_put(uint32_t *w, V3 v) {
+    w[0] = __float_as_uint(v.x);
+    w[1] = __float_as_uint(v.y);
+    w[2] = __float_as_uint(v.z);
+}
+__device__ __forceinline__ Material tab_row_material(const uint32_t *w) {
+    Material m;
+    m.ax = __uint_as_float(w[0]);
+    m.ay = __uint_as_float(w[1]);
+    m.az = __uint_as_float(w[2]);
+    m.ior = __uint_as_float(w[3]);
+    m.type = (int)w[4];
+    return m;
+}
+__global__ void __launch_bounds__(kBlock)
+k_shade_table(int func, int n, int win, int wout, const uint32_t *__restrict__ in, uint32_t *__restrict__ out,
+              const float4 *__restrict__ tris) {
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (unsigned)n) return;
+    const uint32_t *r = in + (size_t)i * win;
+    uint32_t *w = out + (size_t)i * wout;
+    switch (func) {
+        case 1: {  // Material::sample_f
+            const Material m = tab_row_material(r);
+            V3 nn = tab_v3(r + 8), wi = mk(0.f, 0.f, 0.f);
+            float pdf = 0.f;
+            int again = 0;
+            Rng rs{r[11], r[12], r[13], r[14], r[15], r[16]};
+            const V3 f = mat_sample_f(m, tab_v3(r + 5), rs, nn, wi, pdf, again);
+            tab_put(w, f);
+            tab_put(w + 3, wi);
+            tab_put(w + 6, nn);
+            w[9] = __float_as_uint(pdf);
+            w[10] = (rs.d - r[11]) * kWeylInv;
+            w[11] = (uint32_t)again;
+            break;
+        }
+        case 2: {  // Material::get_f
+            const Material m = tab_row_material(r);
+            V3 f = mk(0.f, 0.f, 0.f);
+            float pdf = 0.f;
+            w[0] = mat_get_f(m, tab_v3(r + 5), tab_v3(r + 8), tab_v3(r + 11), f, pdf) ? 1u : 0u;
+            tab_put(w + 1, f);
+            w[4] = __float_as_uint(pdf);
+            break;
+        }
+        case 6: {  // Triangle::intersect on the record k_leaf_tris made of the row's vertices
+            const Tri tr = load_tri(tris, (int)i);
+            float t, u, v;
+            w[0] = tri_intersect(tr, tab_v3(r + 9), tab_v3(r + 12), __uint_as_float(r[15]), t, u, v) ? 1u : 0u;
+            w[1] = __float_as_uint(t);
+            w[2] = __float_as_uint(u);
+            w[3] = __float_as_uint(v);
+            break;
+        }
+        case 7: tab_put(w, offset_ray_origin(tab_v3(r), tab_v3(r + 3))); break;
+        case 8: w[0] = __float_as_uint(power_heuristic(__uint_as_float(r[0]), __uint_as_float(r[1]))); break;
+        case 9: w[0] = same_hemisphere(tab_v3(r), tab_v3(r + 3), tab_v3(r + 6)) ? 1u : 0u; break;
+        case 10: tab_put(w, reflect(tab_v3(r), tab_v3(r + 3))); break;
+        case 11: tab_put(w, refract4(tab_v3(r), tab_v3(r + 3), __uint_as_float(r[6]), __uint_as_float(r[7]))); break;
+        case 12: {  // uniform_sample_sphere
+            Rng rs{r[0], r[1], r[2], r[3], r[4], r[5]};
+            tab_put(w, uniform_sample_sphere(rs));
+            w[3] = (rs.d - r[0]) * kWeylInv;
+            break;
+        }
+        case 13: {  // Camera::get_ray
+            Camera c;
+            c.lookfrom = tab_v3(r);
+            c.upper_left = tab_v3(r + 3);
+            c.horizontal = tab_v3(r + 6);
+            c.vertical = tab_v3(r + 9);
+            V3 o, d;
+            camera_get_ray(c, __uint_as_float(r[12]), __uint_as_float(r[13]), o, d);
+            tab_put(w, o);
+            tab_put(w + 3, d);
+            break;
+        }
+        default: break;  // (the host refuses every other id)
+    }
 }
 
 
@@ -622,6 +717,96 @@ int rt_split_probe(const rt_scene *scene, const rt_camera *camera, int width, in
             best = std::min(best, t);
         }
         out[RT_PROBE_S_SHADE + mk] = best;
+    }
+    return 0;
+}
+
+int rt_shade_table(int func, int n_rows, const uint32_t *in_words, uint32_t *out_words) {
+    if (func < 1 || func > 13 || kShadeTableIn[func] == 0)
+        return fail("rt_shade_table: function " + std::to_string(func) + " has no device function of its own (1, 2, 6 - 13 have)");
+    if (n_rows < 0 || n_rows > (1 << 22)) return fail("rt_shade_table: row count out of range (0 .. 2^22)");
+    if (n_rows == 0) return 0;
+    if (!in_words || !out_words) return fail("rt_shade_table: null argument");
+    const int win = kShadeTableIn[func], wout = kShadeTableOut[func];
+    const size_t n = (size_t)n_rows;
+    DevScope tmp;
+    uint32_t *d_in = nullptr, *d_out = nullptr;
+    float *d_verts = nullptr;
+    int *d_order = nullptr;
+    float4 *d_tris = nullptr;
+    if (tmp.alloc(d_in, n * win) || tmp.alloc(d_out, n * wout)) return 1;
+    HIP_TRY(hipMemcpy(d_in, in_words, sizeof(uint32_t) * n * win, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_out, out_words, sizeof(uint32_t) * n * wout, hipMemcpyHostToDevice));  // unwritten words stay the caller's
+    const dim3 grid((unsigned)((n + kBlock - 1) / kBlock)), block(kBlock);
+    if (func == 6) {  // the triangle records, made by the kernel that makes a scene's (row k is triangle k)
+        std::vector<float> verts(9 * n);
+        std::vector<int> order(n);
+        for (size_t k = 0; k < n; k++) {
+            memcpy(&verts[9 * k], in_words + k * win, 36);
+            order[k] = (int)k;
+        }
+        if (tmp.alloc(d_verts, 9 * n) || tmp.alloc(d_order, n) || tmp.alloc(d_tris, 3 * n)) return 1;
+        HIP_TRY(hipMemcpy(d_verts, verts.data(), sizeof(float) * 9 * n, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_order, order.data(), sizeof(int) * n, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(k_leaf_tris, grid, block, 0, nullptr, d_verts, d_order, n_rows, d_tris);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_shade_table, grid, block, 0, nullptr, func, n_rows, win, wout, d_in, d_out, d_tris);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out_words, d_out, sizeof(uint32_t) * n * wout, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int rt_shade_records(const rt_scene *scene, int max_bounces, int lds_tables, int n, const uint32_t *records_in,
+                     uint32_t *records_out) {
+    if (!scene) return fail("rt_shade_records: null scene");
+    if (max_bounces < 0 || n < 0 || n > (1 << 20) || (lds_tables != 0 && lds_tables != 1))
+        return fail("rt_shade_records: bad argument");
+    if (lds_tables && (scene->n_mats > kLdsTable || scene->n_lights > kLdsTable))
+        return fail("rt_shade_records: lds_tables = 1 needs at most " + std::to_string(kLdsTable) + " materials and lights");
+    if (n == 0) return 0;
+    if (!records_in || !records_out) return fail("rt_shade_records: null argument");
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    if (dev != scene->device) return fail("rt_shade_records: scene was created on another device");
+    // every index a record names is checked here: the kernel reads the tables and writes the framebuffer by them
+    for (int i = 0; i < n; i++) {
+        const int32_t hit_info = (int32_t)records_in[(size_t)kProbeIn * i + 1], pixel = (int32_t)records_in[(size_t)kProbeIn * i + 2];
+        if (pixel < 0 || pixel >= n) return fail("rt_shade_records: record " + std::to_string(i) + ": pixel outside 0 .. n - 1");
+        if (hit_info >= 0 && ((hit_info & 0xffff) >= scene->n_mats || ((hit_info >> 16) & 0xffff) > scene->n_lights))
+            return fail("rt_shade_records: record " + std::to_string(i) + ": material or light out of range");
+    }
+    const unsigned cap = (unsigned)n;
+    std::vector<uint32_t> soa((size_t)kProbeIn * cap), got((size_t)kProbeOut * cap);
+    for (int i = 0; i < n; i++)
+        for (int a = 0; a < kProbeIn; a++) soa[(size_t)a * cap + i] = records_in[(size_t)kProbeIn * i + a];
+    DevScope tmp;
+    float *rec = nullptr, *outp = nullptr, *fb = nullptr;
+    if (tmp.alloc(rec, soa.size()) || tmp.alloc(outp, got.size()) || tmp.alloc(fb, 3 * (size_t)n)) return 1;
+    HIP_TRY(hipMemcpy(rec, soa.data(), sizeof(uint32_t) * soa.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(outp, 0xff, sizeof(uint32_t) * got.size()));  // RT_SHADE_UNWRITTEN
+    HIP_TRY(hipMemset(fb, 0, sizeof(float) * 3 * (size_t)n));
+    const DScene sc = scene->dev();
+    Camera cam{};
+    AdvanceParams ap{};
+    ap.n = n;
+    ap.max_bounces = max_bounces;
+    const dim3 grid((cap + kBlock - 1) / kBlock), block(kBlock);
+    if (lds_tables) hipLaunchKernelGGL(k_probe_shade<true>, grid, block, 0, nullptr, sc, cam, ap, rec, cap, cap, outp, fb);
+    else hipLaunchKernelGGL(k_probe_shade<false>, grid, block, 0, nullptr, sc, cam, ap, rec, cap, cap, outp, fb);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    std::vector<float> h_fb(3 * (size_t)n);
+    HIP_TRY(hipMemcpy(got.data(), outp, sizeof(uint32_t) * got.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h_fb.data(), fb, sizeof(float) * h_fb.size(), hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; i++) {
+        uint32_t *w = records_out + (size_t)RT_SHADE_RECORD_OUT * i;
+        for (int a = 0; a < kProbeOut; a++) w[a] = got[(size_t)a * cap + i];
+        // the excluded triangle of a shadow ray: the kernels' leaf-order index -> the caller's index
+        const int32_t target = (int32_t)w[16];
+        if (w[12] != 0xbf800000u && target >= 0 && target < scene->n_tris) w[16] = (uint32_t)scene->h_order[(size_t)target];
+        memcpy(w + kProbeOut, &h_fb[3 * (size_t)i], 12);
     }
     return 0;
 }

@@ -282,6 +282,32 @@ def xorwow_state_for(raws):
     return np.array([0] + v, np.uint32)
 
 
+def _inv_g_array(a):
+    """_inv_g on a uint32 array."""
+    t = np.asarray(a, np.uint64) & np.uint64(_M32)
+    s = 1
+    while s < 32:
+        t = (t ^ (t << np.uint64(s))) & np.uint64(_M32)
+        s <<= 1
+    x, s = t, 2
+    while s < 32:
+        x = x ^ (x >> np.uint64(s))
+        s <<= 1
+    return x & np.uint64(_M32)
+
+
+def xorwow_states_for2(raws2):
+    """xorwow_state_for on every row of an (n, 2) table of raw draws at once -> (n, 6) uint32."""
+    r = np.asarray(raws2, np.uint32).astype(np.uint64)
+    m = np.uint64(_M32)
+    out = np.zeros((len(r), 6), np.uint32)
+    want0 = (r[:, 0] - np.uint64(_WEYL)) & m
+    out[:, 1] = _inv_g_array(want0).astype(np.uint32)
+    want1 = (r[:, 1] - np.uint64(2 * _WEYL)) & m
+    out[:, 2] = _inv_g_array(want1 ^ ((want0 ^ (want0 << np.uint64(4))) & m)).astype(np.uint32)
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ function tables
 WORDS_IN = {1: 13, 2: 14, 3: 21, 4: 22, 5: 11, 6: 16, 7: 6, 8: 2, 9: 9, 10: 6, 11: 8, 12: 2, 13: 14}
 WORDS_OUT = {1: 11, 2: 5, 3: 10, 4: 1, 5: 5, 6: 4, 7: 3, 8: 1, 9: 1, 10: 3, 11: 3, 12: 4, 13: 6}
