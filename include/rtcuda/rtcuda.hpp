@@ -505,6 +505,34 @@ inline rt_stats render_rays_keyed_fixed(const Scene &scene, int64_t n_rays, cons
     return st;
 }
 
+// First-hit feature buffers (no reference counterpart): albedo, normal, emission, depth and hit count per pixel as int64
+// fixed-point sums ADDED into d_aov_fixed (n_pixels x RT_AOV_CHANNELS), optionally {triangle, material} of every pixel's first
+// sample in d_ids (n_pixels x 2) -- rt_render_aov_fixed / rt_render_aov_rays_fixed_device / rt_aov_resolve, which document the
+// frame, the channels, the flags and the errors.  render_aov: the camera's own per-sample rays, shard (shard_index,
+// shard_count) of them; render_aov_rays: the caller's rays, row c with the key key_first + c * key_stride; aov_resolve: the
+// sums as n_pixels x RT_AOV_CHANNELS floats (means over the samples, depth over the hits, coverage).
+inline rt_stats render_aov(const Scene &scene, const Camera &camera, int width, int height, int num_samples, int64_t *d_aov_fixed,
+                           int32_t *d_ids = nullptr, uint64_t seed = 1, uint32_t flags = 0, int shard_index = 0, int shard_count = 1,
+                           void *stream = nullptr) {
+    rt_scene *h = scene.bvh.handle ? rtcuda_detail::realise(scene) : nullptr;
+    rt_stats st{};
+    rtcuda_detail::check(rt_render_aov_fixed(h, &camera.pod, width, height, num_samples, seed, shard_index, shard_count, flags,
+                                             d_aov_fixed, d_ids, stream, &st), "render_aov");
+    return st;
+}
+inline rt_stats render_aov_rays(const Scene &scene, int64_t n_rays, const float *d_origin, const float *d_dir, const int32_t *d_pixel,
+                                int rays_per_pixel, int n_pixels, int64_t *d_aov_fixed, int32_t *d_ids = nullptr, uint64_t key_first = 0,
+                                uint32_t key_stride = 1, uint32_t flags = 0, void *stream = nullptr) {
+    rt_scene *h = scene.bvh.handle ? rtcuda_detail::realise(scene) : nullptr;
+    rt_stats st{};
+    rtcuda_detail::check(rt_render_aov_rays_fixed_device(h, n_rays, d_origin, d_dir, d_pixel, rays_per_pixel, n_pixels, key_first,
+                                                         key_stride, flags, d_aov_fixed, d_ids, stream, &st), "render_aov_rays");
+    return st;
+}
+inline void aov_resolve(const int64_t *d_aov_fixed, float *d_out, int n_pixels, int num_samples, void *stream = nullptr) {
+    rtcuda_detail::check(rt_aov_resolve(d_aov_fixed, d_out, n_pixels, num_samples, stream), "aov_resolve");
+}
+
 // A driver that must keep the reference's exact call (main.cu:173) can still reach several GPUs: RTCUDA_DEVICES="0,1,2,3" in
 // the environment sends the seven-argument render() below through the multi-device path (rt_render_multi).
 inline std::vector<int> devices_from_env() {

@@ -370,6 +370,69 @@ int rt_render_rays_keyed_fixed_device(const rt_scene *scene, int64_t n_rays, con
                                       uint64_t seed, uint64_t key_first, uint32_t key_stride, uint32_t flags,
                                       int64_t *d_sum_fixed, void *stream, rt_stats *stats);
 
+/* ---- first-hit feature buffers (AOVs): albedo, normal, emission, depth, coverage per pixel, and object ids ----------------
+ * What a denoiser, a compositor or a learning pipeline takes next to the noisy image, from one kernel that makes the ray,
+ * finds the hit and deposits the features: no ray table, no round trip (no reference counterpart: its render() writes
+ * radiance only).  An AOV frame of (camera, width, height, num_samples, seed) has the samples G = 0 .. width * height *
+ * num_samples - 1:
+ *   1. THE RAY of sample G is camera ray G of an RT_FLAG_RNG_PER_SAMPLE frame: pixel G / num_samples, the stream of (seed, G),
+ *      jitter = its first two draws (x, then y), ray = camera.get_ray((px + jx) / width, (py + jy) / height), operation for
+ *      operation.  No further draw is made.  An AOV frame and an RT_FLAG_RNG_PER_SAMPLE | RT_FLAG_WATERTIGHT beauty frame of the
+ *      same seed therefore use the same camera ray, sample for sample.
+ *   2. SHARDS: shard (r, R) with num_samples % R == 0 serves the samples with G % R == r, as that mode's shards do.
+ *   3. THE HIT is the closest hit with tmax = FLT_MAX under `flags`, exactly as rt_query_closest_device defines them: 0 (the
+ *      reference's decisions: visibility check, tie rule, literal re-trace), RT_FLAG_REFERENCE_WALK or RT_FLAG_WATERTIGHT.
+ *      Both tree widths are served.
+ *   4. THE DEPOSIT: a sample that misses deposits nothing.  A sample that hits triangle k ADDS to its pixel, each value
+ *      converted to fixed point (units of 2^-30, int64, magnitudes clamped to 2^31 as rt_render_shard_fixed's):
+ *        channels 0-2  albedo    the albedo of the triangle's material, whatever its type
+ *        channels 3-5  normal    n = -unit(tri.n), the record mat() shades with (render.cuh:153), faced to the viewer:
+ *                                dot(n, d) > 0 ? -n : n, with dot = x*x + y*y + z*z left to right, every operation rounded
+ *        channels 6-8  emission  L of the area light the triangle carries, else 0: what init() deposits at bounce 0
+ *                                (render.cuh:98-103)
+ *        channel  9    depth     t of the hit
+ *        channel  10   hits      the integer 1 (a count, not scaled)
+ *      d_aov_fixed is n_pixels x RT_AOV_CHANNELS int64, interleaved per pixel, ADDED to (zero it first).  A channel whose
+ *      value is 0 is not added.
+ *   5. IDS (d_ids may be NULL): n_pixels x 2 int32.  The sample with G % num_samples == 0 writes {triangle in the caller's
+ *      order, material index} of its hit, or {-1, -1} on a miss, with a plain store.  Such a sample belongs to shard 0, so
+ *      the other shards write nothing there.  (Mirror and glass are not followed to the first diffuse vertex: the material
+ *      index tells the caller that a pixel is specular.)
+ *   6. THE RAY-TABLE FORM (rt_render_aov_rays_fixed_device): row c has the key K = key_first + c * key_stride, exactly as
+ *      rt_render_rays_keyed_device defines keys and their checks.  Origin and direction are row c; no stream is needed.  The
+ *      pixel is d_pixel[c], else K / rays_per_pixel.  Ids are written by the rows with K % rays_per_pixel == 0, and only when
+ *      d_pixel is NULL: d_ids together with d_pixel is an error.  The device prepasses of the ray tables (directions, pixel
+ *      range, origin radius) run before anything is written.
+ *   7. RESOLVE (rt_aov_resolve): n_pixels x RT_AOV_CHANNELS floats from the sums.  With s = float(double(sum) * 2^-30), as
+ *      rt_post_process_fixed forms it, and inv = 1.f / num_samples: albedo, normal and emission are s * inv (the mean normal
+ *      is not renormalised); depth is hits > 0 ? s / float(hits) : 0; channel 10 is float(hits) * inv (coverage).
+ * WHAT FOLLOWS: the sums are integers, so any split of a frame -- shards, key ranges, chunks in any order -- adds up to
+ * exactly the whole frame; the camera form and a table that holds the pinhole's own per-sample rays give the same integers;
+ * with RT_FLAG_WATERTIGHT the emission channels are the fixed-point sums of the per-sample frame at max_bounces = 0.
+ * The contract is the neighbouring entry points': all buffers are DEVICE buffers on the scene's device; the work is ordered on
+ * `stream` (NULL = default stream) and the call is synchronous on it at return; the calling thread's current device is left
+ * as it was; the steady path allocates nothing (the scratch words, the overflow stacks and the timing events belong to the
+ * scene's query state, so AOV calls and queries of ONE scene take turns); only the scene is read; a camera or origins outside
+ * the radius the records are padded for widen the padding once.
+ * stats (may be NULL): camera_rays and closest_rays = the samples of this call, seconds_render = device time of the kernel,
+ * bvh_nodes, bvh_depth, and with flags 0 reserved[4..6] = the rare-path counters as rt_render_shard fills them.
+ * ERRORS return non-zero, name the entry point in rt_last_error() and write nothing: a null pointer that may not be null;
+ * width, height or num_samples < 1, more than 715827882 pixels, width * height * num_samples beyond the int32 camera-ray range
+ * of rt_render_shard; shard_index outside 0 .. shard_count - 1 or num_samples % shard_count != 0; a flag other than
+ * RT_FLAG_WATERTIGHT, RT_FLAG_REFERENCE_WALK or RT_FLAG_TIME_KERNELS (accepted, changes nothing), or both hit flags together;
+ * the table checks of rt_render_rays_keyed_device (n_rays, n_pixels, key_stride, a key that wraps, the last key's pixel, and on
+ * the device the directions and the pixel indices: the error names the number of offending rays). */
+#define RT_AOV_CHANNELS 11
+enum { RT_AOV_ALBEDO = 0, RT_AOV_NORMAL = 3, RT_AOV_EMISSION = 6, RT_AOV_DEPTH = 9, RT_AOV_HITS = 10 };
+int rt_render_aov_fixed(const rt_scene *scene, const rt_camera *camera, int width, int height, int num_samples, uint64_t seed,
+                        int shard_index, int shard_count, uint32_t flags, int64_t *d_aov_fixed,
+                        int32_t *d_ids /* may be NULL */, void *stream, rt_stats *stats /* may be NULL */);
+int rt_render_aov_rays_fixed_device(const rt_scene *scene, int64_t n_rays, const float *d_origin_xyz, const float *d_dir_xyz,
+                                    const int32_t *d_pixel /* may be NULL */, int rays_per_pixel, int n_pixels,
+                                    uint64_t key_first, uint32_t key_stride, uint32_t flags, int64_t *d_aov_fixed,
+                                    int32_t *d_ids /* may be NULL */, void *stream, rt_stats *stats /* may be NULL */);
+int rt_aov_resolve(const int64_t *d_aov_fixed, float *d_out, int n_pixels, int num_samples, void *stream);
+
 /* ---- ray queries (no reference counterpart: its Bvh::traverse is reachable only from render()) ----------------------------
  * "Trace my rays, from my buffers, on my stream."  All pointers are DEVICE buffers on the scene's device (a buffer on another
  * device or on the host cannot be told apart from a good one: the call faults instead of failing); origins and directions are

@@ -28,6 +28,8 @@ FLAG_RNG_PER_SAMPLE = 4  # NOT the reference's random numbers (see include/rtcud
 FLAG_REFERENCE_WALK = 8  # cross-check mode: every ray walks the reference's own tree literally (slow; the default kernels give the same image)
 SCENE_DEVICE_BVH = 1     # rt_scene_create_flags: build the BVH on the device (PLOC)
 FLAG_WATERTIGHT = 16     # the triangle-list definition (no hit lost to a box test, ties by caller index) instead of the reference's
+AOV_CHANNELS = 11        # rt_render_aov_*: int64 sums per pixel, interleaved
+AOV_ALBEDO, AOV_NORMAL, AOV_EMISSION, AOV_DEPTH, AOV_HITS = 0, 3, 6, 9, 10  # first channel of each feature
 
 EXPORTS = [
     "rt_scene_create", "rt_scene_destroy", "rt_scene_info", "rt_scene_build_info", "rt_scene_update", "rt_scene_update_device",
@@ -36,6 +38,7 @@ EXPORTS = [
     "rt_render_shard", "rt_render_shard_fixed", "rt_render_rays_device", "rt_render_rays_fixed_device",
     "rt_render_rays_keyed_device", "rt_render_rays_keyed_fixed_device", "rt_post_process", "rt_post_process_fixed", "rt_trace_closest", "rt_trace_any",
     "rt_trace_closest_flags", "rt_trace_any_flags", "rt_query_closest_device", "rt_query_any_device", "rt_query_last_counters",
+    "rt_render_aov_fixed", "rt_render_aov_rays_fixed_device", "rt_aov_resolve",
     "rt_xorwow_states", "rt_shutdown", "rt_peer_access_log", "rt_last_error", "rt_version", "rt_build_id",
 ]
 # the lab (include/rtcuda_amd_tools.h, librtcuda_amd_tools.so): measurement tools, not part of the drop-in C-ABI
@@ -154,6 +157,10 @@ def _bind(L):
     L.rt_render_rays_keyed_device.argtypes = [vp, ctypes.c_int64, vp, vp, vp, ci, ci, ci, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32,
                                               ctypes.c_uint32, vp, vp, ctypes.POINTER(RtStats)]
     L.rt_render_rays_keyed_fixed_device.argtypes = L.rt_render_rays_keyed_device.argtypes
+    L.rt_render_aov_fixed.argtypes = [vp, vp, ci, ci, ci, ctypes.c_uint64, ci, ci, ctypes.c_uint32, vp, vp, vp, ctypes.POINTER(RtStats)]
+    L.rt_render_aov_rays_fixed_device.argtypes = [vp, ctypes.c_int64, vp, vp, vp, ci, ci, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                                  vp, vp, vp, ctypes.POINTER(RtStats)]
+    L.rt_aov_resolve.argtypes = [vp, vp, ci, ci, vp]
     L.rt_trace_closest.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp]
     L.rt_trace_any.argtypes = [vp, ci, vp, vp, vp, vp, vp]
     L.rt_trace_closest_flags.argtypes = [vp, ctypes.c_uint32, ci, vp, vp, vp, vp, vp, vp, vp]
@@ -545,6 +552,85 @@ class Scene:
                                            out.data_ptr(), rays_per_pixel, key_first, key_stride, max_bounces, seed, 0, fixed, s.cuda_stream)
         return out, st
 
+    # ---- first-hit feature buffers (rt_render_aov_fixed / rt_render_aov_rays_fixed_device)
+    @staticmethod
+    def _aov_buffers(what, n_pixels, ids, out, device):
+        """The sum buffer (a new zeroed one, or `out` checked) and the id buffer (or None) of an AOV call."""
+        import torch
+        if not isinstance(n_pixels, int) or n_pixels < 1:
+            raise RtError(f"{what}: n_pixels must be a positive int, it is {n_pixels!r}")
+        if out is None:
+            out = torch.zeros((n_pixels, AOV_CHANNELS), dtype=torch.int64, device=device)
+        else:
+            if not isinstance(out, torch.Tensor) or not out.is_cuda or (device is not None and out.device != device):
+                raise RtError(f"{what}: out must be a torch tensor on the scene's GPU")
+            if out.dtype != torch.int64 or tuple(out.shape) != (n_pixels, AOV_CHANNELS) or not out.is_contiguous():
+                raise RtError(f"{what}: out must be a contiguous ({n_pixels}, {AOV_CHANNELS}) torch.int64 tensor, it is {tuple(out.shape)} {out.dtype}")
+        if ids is None or ids is False:
+            return out, None
+        if ids is True:
+            return out, torch.full((n_pixels, 2), -1, dtype=torch.int32, device=out.device)
+        if not isinstance(ids, torch.Tensor) or not ids.is_cuda or ids.device != out.device:
+            raise RtError(f"{what}: ids must be a bool or a torch tensor on the scene's GPU")
+        if ids.dtype != torch.int32 or tuple(ids.shape) != (n_pixels, 2) or not ids.is_contiguous():
+            raise RtError(f"{what}: ids must be a contiguous ({n_pixels}, 2) torch.int32 tensor, it is {tuple(ids.shape)} {ids.dtype}")
+        return out, ids
+
+    def render_aov(self, camera: np.ndarray, width: int, height: int, spp: int, seed: int = 1, flags: int = 0, shard=(0, 1),
+                   ids=False, out=None, stream=None):
+        """First-hit features of the camera's per-sample frame -> (sums, ids or None, stats): an (width * height, 11) int64
+        tensor of fixed-point sums (units of 2^-30; channels AOV_ALBEDO, AOV_NORMAL, AOV_EMISSION, AOV_DEPTH, AOV_HITS) on the
+        current device, ADDED into ``out`` when one is given; with ``ids`` (True, or a (width * height, 2) int32 tensor to
+        write into) {triangle, material} of every pixel's first sample, -1 on a miss.  ``shard=(r, R)``: the samples G with
+        G % R == r (spp % R == 0); the shards' sums add up to the whole frame's.  Sample G is camera ray G of a
+        FLAG_RNG_PER_SAMPLE frame of the same seed.  ``flags``: 0, FLAG_REFERENCE_WALK or FLAG_WATERTIGHT."""
+        import torch
+        what = "render_aov"
+        for name, v in (("width", width), ("height", height), ("spp", spp)):
+            if not isinstance(v, int) or v < 1:
+                raise RtError(f"{what}: {name} must be a positive int, it is {v!r}")
+        if not isinstance(seed, int) or not 0 <= seed < 1 << 64:
+            raise RtError(f"{what}: seed must be an int in 0 .. 2^64 - 1, it is {seed!r}")
+        r, R = shard
+        cam = np.ascontiguousarray(camera, np.float32)
+        if cam.shape != (12,):
+            raise RtError(f"{what}: camera must be the 12 floats of make_camera(), it has shape {cam.shape}")
+        out, ids = self._aov_buffers(what, width * height, ids, out, None if out is not None else torch.device("cuda", torch.cuda.current_device()))
+        s = torch.cuda.current_stream(out.device) if stream is None else stream
+        c = ctypes.c_void_p
+        st = RtStats()
+        _check(self.L.rt_render_aov_fixed(self.h, _p(cam), width, height, spp, seed, int(r), int(R), flags, c(out.data_ptr()),
+                                          c(None if ids is None else ids.data_ptr()), c(s.cuda_stream or None), ctypes.byref(st)),
+               "rt_render_aov_fixed", self.L)
+        return out, ids, st.as_dict()
+
+    def render_aov_rays(self, origins, dirs, n_pixels: int, pixel=None, rays_per_pixel: int = 1, key_first: int = 0, key_stride: int = 1,
+                        flags: int = 0, ids=False, out=None, stream=None):
+        """First-hit features along torch rays (render_rays_keyed's tensors and checks): row c has the key
+        key_first + c * key_stride and lands on pixel[c] or, without a pixel tensor, key // rays_per_pixel -> (sums, ids or
+        None, stats) as render_aov.  ``ids`` needs pixel=None.  Chunks of one table, each with key_first = its first row,
+        accumulate into one ``out``."""
+        what = "render_aov_rays"
+        n, device = self._query_rays(what, origins, dirs, None)
+        if pixel is not None:
+            self._query_rays(what, origins, dirs, None, pixel, "pixel")
+        for name, v, top in (("key_first", key_first, 1 << 64), ("key_stride", key_stride, 1 << 32)):
+            if not isinstance(v, int) or not 0 <= v < top:  # (ctypes would wrap it silently)
+                raise RtError(f"{what}: {name} must be an int in 0 .. 2^{top.bit_length() - 1} - 1, it is {v!r}")
+        if pixel is not None and ids is not None and ids is not False:
+            raise RtError(f"{what}: ids together with a pixel tensor (ids belong to the pixels of the key rule)")
+        out, ids = self._aov_buffers(what, n_pixels, ids, out, device)
+        import torch
+        s = torch.cuda.current_stream(device) if stream is None else stream
+        c = ctypes.c_void_p
+        st = RtStats()
+        _check(self.L.rt_render_aov_rays_fixed_device(self.h, n, c(origins.data_ptr()), c(dirs.data_ptr()),
+                                                      c(None if pixel is None else pixel.data_ptr()), int(rays_per_pixel), n_pixels,
+                                                      key_first, key_stride, flags, c(out.data_ptr()),
+                                                      c(None if ids is None else ids.data_ptr()), c(s.cuda_stream or None),
+                                                      ctypes.byref(st)), "rt_render_aov_rays_fixed_device", self.L)
+        return out, ids, st.as_dict()
+
     # ---- ray queries on device buffers (rt_query_*_device)
     def query_closest_device(self, o_ptr: int, d_ptr: int, tmax_ptr: int, n: int, hit_ptr: int, t_ptr: int = 0, u_ptr: int = 0,
                              v_ptr: int = 0, flags: int = 0, stream: int = 0) -> None:
@@ -660,6 +746,25 @@ def post_process(d_ptr: int, num_pixels: int, spp: int, stream: int = 0) -> None
 def post_process_fixed(d_fixed_ptr: int, d_out_ptr: int, num_pixels: int, spp: int, stream: int = 0) -> None:
     _check(lib().rt_post_process_fixed(ctypes.c_void_p(d_fixed_ptr), ctypes.c_void_p(d_out_ptr), num_pixels, spp,
                                        ctypes.c_void_p(stream)), "rt_post_process_fixed")
+
+
+def aov_resolve(sums, spp: int, stream=None):
+    """The float features of AOV sums ((n_pixels, 11) int64 tensor on a GPU; rt_aov_resolve) -> (n_pixels, 11) float32 tensor:
+    albedo, normal and emission as means over the ``spp`` samples, depth as the mean over the hits (0 where nothing was hit),
+    channel AOV_HITS as coverage."""
+    import torch
+    if not isinstance(sums, torch.Tensor) or not sums.is_cuda:
+        raise RtError("aov_resolve: sums must be a torch tensor on a GPU")
+    if sums.dtype != torch.int64 or sums.dim() != 2 or sums.shape[1] != AOV_CHANNELS or not sums.is_contiguous():
+        raise RtError(f"aov_resolve: sums must be a contiguous (n_pixels, {AOV_CHANNELS}) torch.int64 tensor, it is {tuple(sums.shape)} {sums.dtype}")
+    if not isinstance(spp, int) or spp < 1:
+        raise RtError(f"aov_resolve: spp must be a positive int, it is {spp!r}")
+    out = torch.empty(tuple(sums.shape), dtype=torch.float32, device=sums.device)
+    s = torch.cuda.current_stream(sums.device) if stream is None else stream
+    with torch.cuda.device(sums.device):
+        _check(lib().rt_aov_resolve(ctypes.c_void_p(sums.data_ptr()), ctypes.c_void_p(out.data_ptr()), int(sums.shape[0]), spp,
+                                    ctypes.c_void_p(s.cuda_stream or None)), "rt_aov_resolve")
+    return out
 
 
 def xorwow_states(seed: int, first: int, count: int, draws: int = 0):

@@ -1695,6 +1695,277 @@ __global__ void __launch_bounds__(kBlock, kQueryMinWaves) k_query(DScene sc, Que
     }
 }
 
+// ============================================================================ k_aov: first-hit feature buffers
+// rt_render_aov_fixed / rt_render_aov_rays_fixed_device: per pixel the albedo, the normal, the emission,
+// the depth and the hit count of the FIRST hit of every sample, as int64 fixed-point sums, and optionally the ids of a pixel's
+// first sample.  k_query's scheme -- one persistent launch, chunks of 64 consecutive sample ids per wave, idle lanes refilled
+// by ballot, the shared walk (inv_dir, inner_step, tri_intersect, closest_hit_wins, ref_visible, reference_walk, the stack
+// helpers) -- with the two ends replaced: a lane MAKES its ray (SRC = AovCamera: camera ray G of an RT_FLAG_RNG_PER_SAMPLE
+// frame, formed as gen_core's per-sample branch forms it) or reads row c of a keyed table (SRC = KeyedRayTable, streamed past
+// the caches as gen_core reads it), and a finished lane deposits instead of writing a hit record.
+// Nothing of a sample is carried but its id: the pixel (and whether the sample writes ids) is a function of the id and is
+// recomputed at the deposit, so the register budget is k_query's.
+struct AovCamera {
+    Camera cam;
+    int width, height;
+    unsigned spp;               // samples per pixel of THIS shard (num_samples / shard_count): local sample c -> pixel c / spp
+    unsigned key_mul, key_add;  // global sample G = c * shard_count + shard_index (AdvanceParams::key_mul / key_add)
+    uint32_t seed_lo, seed_hi;
+};
+struct AovParams {
+    int n;                       // samples of this call
+    unsigned long long *sums;    // n_pixels x RT_AOV_CHANNELS int64, ADDED to
+    int *ids;                    // n_pixels x 2 {triangle in the caller's order, material}, or null
+    unsigned long long *vstat;
+};
+__device__ __forceinline__ void aov_ray(const AovCamera &s, int id, V3 &o, V3 &d) {
+    // gen_core, per-sample streams: pixel = id / spp, the stream of the global id, jitter x then y, camera.get_ray
+    const int pixel = (int)((unsigned)id / s.spp);
+    const int py = (int)((unsigned)pixel / (unsigned)s.width);
+    const int px = pixel - py * s.width;
+    Rng rs = rng_sample_stream(s.seed_lo, s.seed_hi, (unsigned long long)id * s.key_mul + s.key_add);
+    const float jx = rng_uniform(rs);  // x first, then y (Appendix A.7)
+    const float jy = rng_uniform(rs);
+    camera_get_ray(s.cam, (px + jx) / s.width, (py + jy) / s.height, o, d);
+}
+__device__ __forceinline__ void aov_ray(const KeyedRayTable &s, int id, V3 &o, V3 &d) {
+    const float *o3 = s.o3 + 3 * (size_t)id, *d3 = s.d3 + 3 * (size_t)id;
+    o = mk(table_load(o3), table_load(o3 + 1), table_load(o3 + 2));
+    d = mk(table_load(d3), table_load(d3 + 1), table_load(d3 + 2));
+}
+// the pixel of sample `id`, and whether it is the sample that writes its pixel's ids (G % spp == 0: shard 0 only, the host
+// passes no id buffer to the others; K % rays_per_pixel == 0, never with a pixel array)
+__device__ __forceinline__ int aov_pixel(const AovCamera &s, int id, bool &first) {
+    const unsigned pixel = (unsigned)id / s.spp;
+    first = (unsigned)id - pixel * s.spp == 0u;
+    return (int)pixel;
+}
+__device__ __forceinline__ int aov_pixel(const KeyedRayTable &s, int id, bool &first) {
+    first = false;
+    if (s.pixel) return table_load(s.pixel + (unsigned)id);
+    const unsigned long long t = s.rem_first + (unsigned long long)(unsigned)id * s.key_stride;  // (as gen_core: K / rpp = pix_first + t / rpp)
+    const unsigned long long q = (t >> 32) ? t / s.rays_per_pixel : (unsigned long long)((unsigned)t / s.rays_per_pixel);
+    first = t - q * s.rays_per_pixel == 0ull;
+    return s.pix_first + (int)q;  // (below n_pixels: the host checks the last key)
+}
+// The deposit of one finalisation, called by the whole wave (the caller's branch is wave-uniform).  `dep`: this lane holds a
+// hit; `pixel` its pixel (-1 otherwise); val[0 .. 9] its fixed-point values.
+// RT_AOV_PRE_REDUCE = 0, the first version: one 64-bit atomic per non-zero channel and hitting lane.  Measured on C2 at
+// 1920 x 1080 x 16 (tools/aov_time.py): 91 % of the kernel -- the samples of a pixel sit in neighbouring lanes, 16 lanes of an
+// atomic instruction on ONE address.
+// RT_AOV_PRE_REDUCE = 1 (the product): the lanes of the wave that hold the same pixel are summed first.  The sums are integers,
+// so the result is the first version's bit for bit whatever is summed where.  The depositing lanes are packed to the front of
+// the wave in lane order (ds_permute: consecutive sample ids, handed out to idle lanes in lane order, become neighbours
+// again), runs of equal pixels are added up by a segmented scan over lane distances 1, 2, 4, ... that stops as soon as no run
+// is longer (none at one sample per pixel, four steps at sixteen), and the last lane of each run issues the atomics.
+#ifndef RT_AOV_PRE_REDUCE
+#define RT_AOV_PRE_REDUCE 1
+#endif
+__device__ __forceinline__ long long aov_pull(int from_lane, long long x) {  // x of lane `from_lane` (ds_bpermute)
+    const int lo = __builtin_amdgcn_ds_bpermute(from_lane << 2, (int)(unsigned)(unsigned long long)x);
+    const int hi = __builtin_amdgcn_ds_bpermute(from_lane << 2, (int)(unsigned)((unsigned long long)x >> 32));
+    return (long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
+}
+__device__ __forceinline__ long long aov_push(int to_lane, long long x) {  // this lane's x to lane `to_lane` (ds_permute; a permutation)
+    const int lo = __builtin_amdgcn_ds_permute(to_lane << 2, (int)(unsigned)(unsigned long long)x);
+    const int hi = __builtin_amdgcn_ds_permute(to_lane << 2, (int)(unsigned)((unsigned long long)x >> 32));
+    return (long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
+}
+__device__ __forceinline__ void aov_deposit(const AovParams &ap, bool dep, int pixel, long long (&val)[RT_AOV_HITS]) {
+#ifdef RT_AOV_NO_DEPOSIT
+    if (ap.n != 0x7fffffff) return;  // measurement build (tools/aov_time.py): always taken, the host refuses such a frame
+#endif
+    int hits = dep ? 1 : 0;
+    if (RT_AOV_PRE_REDUCE) {
+        const unsigned long long dm = wave_ballot(dep);
+        if (dm == 0) return;
+        const int lane = (int)lane_id(), n_dep = __popcll(dm);
+        // pack: depositing lanes to 0 .. n_dep - 1 in lane order, the others behind them (every lane sends, every lane receives)
+        const int to = dep ? (int)prefix_popc(dm) : n_dep + (int)prefix_popc(~dm);
+        pixel = __builtin_amdgcn_ds_permute(to << 2, pixel);
+        hits = __builtin_amdgcn_ds_permute(to << 2, hits);
+#pragma unroll
+        for (int c = 0; c < RT_AOV_HITS; c++) val[c] = aov_push(to, val[c]);
+        // runs of equal pixels: `stop` is set once a lane's sum reaches back to the head of its run
+        const int prev = __builtin_amdgcn_ds_bpermute((lane - 1) << 2, pixel), next = __builtin_amdgcn_ds_bpermute((lane + 1) << 2, pixel);
+        int stop = (lane == 0 || pixel < 0 || prev != pixel) ? 1 : 0;
+        for (int k = 1; k < 64; k <<= 1) {
+            if (wave_ballot(stop == 0) == 0) break;
+            const bool take = stop == 0 && lane >= k;
+            const int stop_k = __builtin_amdgcn_ds_bpermute((lane - k) << 2, stop), hits_k = __builtin_amdgcn_ds_bpermute((lane - k) << 2, hits);
+#pragma unroll
+            for (int c = 0; c < RT_AOV_HITS; c++) {
+                const long long v_k = aov_pull(lane - k, val[c]);
+                if (take) val[c] += v_k;
+            }
+            if (take) {
+                hits += hits_k;
+                stop = stop_k;
+            }
+        }
+        dep = pixel >= 0 && (lane == 63 || next != pixel);  // the last lane of a run holds the run's sums
+    }
+    if (dep) {
+        unsigned long long *p = ap.sums + (size_t)(unsigned)pixel * RT_AOV_CHANNELS;
+#pragma unroll
+        for (int c = 0; c < RT_AOV_HITS; c++)
+            if (val[c] != 0) atomicAdd(p + c, (unsigned long long)val[c]);
+        atomicAdd(p + RT_AOV_HITS, (unsigned long long)hits);
+    }
+}
+template <class SRC, bool WIDE, bool LITERAL, bool VERIFY>
+__global__ void __launch_bounds__(kBlock, kQueryMinWaves) k_aov(DScene sc, SRC src, AovParams ap, int stack_cap, int *overflow) {
+    extern __shared__ int s_lds[];
+    int *stack = s_lds + threadIdx.x;
+    int *over = overflow + (blockIdx.x * kBlock + threadIdx.x);
+    const int n = ap.n;
+    const int n_chunks = (int)(((unsigned)n + 63u) >> 6);
+    const int grid_waves = (int)(gridDim.x * (kBlock / 64));
+    int next_chunk = (int)wave_index();
+    int pend_lo = 0, pend_hi = 0;  // wave-uniform: sample ids of the current chunk that no lane has taken yet
+    int id = -1, cur = kEntryDone, sp = 0, tri = -1;  // per-lane state, as in k_query
+    V3 o = mk(0, 0, 0), d = mk(0, 0, 0), inv = mk(0, 0, 0);
+    float tmax = 0.f, hu = 0.f, hv = 0.f;
+
+    while (true) {
+        unsigned long long act = wave_ballot(id >= 0 && cur != kEntryDone);
+        if (__popcll(act) <= kQueryRefillAt) {
+            // ---- finalise finished lanes: the reference's decisions first (k_query's rule, k_trace's)
+            const bool fin = id >= 0 && cur == kEntryDone;
+            if (VERIFY && !LITERAL && fin && tri >= 0) {
+                bool bad = (__float_as_uint(hv) >> 31) != 0u;
+                if (bad) {
+                    atomicAdd(&ap.vstat[V_TIE], 1ull);
+                } else {
+                    const Tri tr = load_tri(sc.tris, tri);
+                    bad = !ref_visible(sc, o, d, tr, tri, ap.vstat);
+                }
+                if (bad) {
+                    atomicAdd(&ap.vstat[V_LITERAL], 1ull);
+                    tmax = kFltMax;
+                    tri = -1;
+                    hu = hv = 0.f;
+                    reference_walk<false>(sc, o, d, tmax, tri, hu, hv, stack, over, stack_cap);
+                }
+            }
+            // ---- deposit: what mat() would shade with (tri_shade, the material) and what init() deposits at bounce 0
+            {
+                bool first = false;
+                int pixel = -1, mat = -1;
+                long long val[RT_AOV_HITS];  // the ten fixed-point values of this lane's sample (zero: nothing to add)
+#pragma unroll
+                for (int c = 0; c < RT_AOV_HITS; c++) val[c] = 0;
+                if (fin) pixel = aov_pixel(src, id, first);
+                const bool dep = fin && tri >= 0;
+                if (dep) {
+                    const float4 sh = sc.tri_shade[(unsigned)tri];
+                    const int info = __float_as_int(sh.w);
+                    mat = info & 0xffff;
+                    const int light = ((info >> 16) & 0xffff) - 1;
+                    V3 nn = mk(sh.x, sh.y, sh.z);
+                    if (dot(nn, d) > 0.f) nn = neg(nn);  // faced to the viewer (mat_sample_f's flip)
+                    const Material m = tab_material(sc.tables, mat);
+                    val[RT_AOV_ALBEDO + 0] = to_fixed(m.ax);
+                    val[RT_AOV_ALBEDO + 1] = to_fixed(m.ay);
+                    val[RT_AOV_ALBEDO + 2] = to_fixed(m.az);
+                    val[RT_AOV_NORMAL + 0] = to_fixed(nn.x);
+                    val[RT_AOV_NORMAL + 1] = to_fixed(nn.y);
+                    val[RT_AOV_NORMAL + 2] = to_fixed(nn.z);
+                    if (light >= 0) {  // render.cuh:98-103
+                        const Light l = tab_light(sc.tables, sc.num_mats, light);
+                        val[RT_AOV_EMISSION + 0] = to_fixed(l.lx);
+                        val[RT_AOV_EMISSION + 1] = to_fixed(l.ly);
+                        val[RT_AOV_EMISSION + 2] = to_fixed(l.lz);
+                    }
+                    val[RT_AOV_DEPTH] = to_fixed(tmax);
+                }
+                if (fin && ap.ids && first) {
+                    ap.ids[2 * (size_t)(unsigned)pixel] = tri >= 0 ? sc.order[(unsigned)tri] : -1;
+                    ap.ids[2 * (size_t)(unsigned)pixel + 1] = mat;
+                }
+                if (fin) id = -1;
+                aov_deposit(ap, dep, dep ? pixel : -1, val);
+            }
+            // ---- refill idle lanes (a second chunk when the current one runs out half-way)
+            for (int tries = 0; tries < 2; tries++) {
+                const unsigned long long idle = wave_ballot(id < 0);
+                const int n_idle = __popcll(idle);
+                if (n_idle == 0) break;
+                if (pend_lo == pend_hi) {
+                    if (next_chunk >= n_chunks) break;
+                    pend_lo = next_chunk << 6;
+                    pend_hi = min(pend_lo + 64, n);
+                    next_chunk += grid_waves;
+                }
+                const int avail = pend_hi - pend_lo, r = (int)prefix_popc(idle);
+                if (id < 0 && r < avail) {
+                    id = pend_lo + r;
+                    aov_ray(src, id, o, d);
+                    tmax = kFltMax;
+                    tri = -1;
+                    inv = inv_dir(d);
+                    cur = 0;  // root
+                    sp = 0;
+                    hu = hv = 0.f;
+                }
+                pend_lo += min(avail, n_idle);
+            }
+            act = wave_ballot(id >= 0 && cur != kEntryDone);
+            if (act == 0) {
+                if (pend_lo == pend_hi && next_chunk >= n_chunks) break;  // nothing in flight, nothing pending, no chunks left
+                continue;
+            }
+        }
+        if (LITERAL) {
+            if (cur >= 0) {
+                reference_walk<false>(sc, o, d, tmax, tri, hu, hv, stack, over, stack_cap);
+                cur = kEntryDone;
+            }
+            continue;
+        }
+        // ---- inner phase: step through node records until no lane holds an inner entry
+        while (wave_ballot(cur >= 0) != 0) {
+            if (cur >= 0) inner_step<WIDE>(sc, o, inv, tmax, cur, sp, stack, over, stack_cap);
+        }
+        // ---- leaf phase: every lane that holds a leaf tests its triangles (triangle.cuh:39-58)
+        if (cur != kEntryDone && cur < 0) {
+            const int ref = ~cur, first = ref >> 3, count = ref & 7;
+            for (int k = first; k < first + count; k++) {
+                const Tri tr = load_tri(sc.tris, k);
+                float t, u, v;
+                if (tri_intersect(tr, o, d, tmax, t, u, v)) {
+                    const bool tie = t == tmax && tri >= 0;
+                    if (closest_hit_wins(sc, t, tmax, k, tri)) {  // bvh.cuh:227-231 (t <= tmax)
+                        tmax = t;
+                        hu = u;
+                        hv = v;
+                        tri = k;
+                    }
+                    // VERIFY: an exact tie is marked in the sign of hv for the finalisation (see k_trace)
+                    if (VERIFY && tie) hv = __uint_as_float(__float_as_uint(hv) | 0x80000000u);
+                }
+            }
+            cur = sp > 0 ? stack_pop(stack, over, sp, stack_cap) : kEntryDone;
+        }
+    }
+}
+
+// rt_aov_resolve: sums -> floats, one thread per value.  s = float(double(sum) * 2^-30) as k_post_process_fixed forms it;
+// albedo, normal, emission: s / spp (the mean normal is not renormalised); depth: the mean over the HITS; channel 10: coverage.
+__global__ void k_aov_resolve(const long long *__restrict__ sums, float *__restrict__ out, long long n_values, float inv_spp) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_values) return;
+    const long long p = i / RT_AOV_CHANNELS;
+    const int ch = (int)(i - p * RT_AOV_CHANNELS);
+    const long long hits = sums[p * RT_AOV_CHANNELS + RT_AOV_HITS];
+    const float s = (float)((double)sums[i] * (1.0 / 1073741824.0));
+    float r;
+    if (ch == RT_AOV_HITS) r = (float)hits * inv_spp;
+    else if (ch == RT_AOV_DEPTH) r = hits > 0 ? s / (float)hits : 0.f;
+    else r = s * inv_spp;
+    out[i] = r;
+}
+
 // ============================================================================ k_paths
 // The whole asynchronous part of a frame in ONE launch.  A lane owns one path slot for the entire
 // render and keeps its state in registers; the reference's stage kernels become PHASES of the lane:
@@ -2345,6 +2616,7 @@ struct rt_scene {
         int *d_inverse = nullptr;
         int cus = 0;
         int64_t counters[3] = {0, 0, 0};  // re-traced, lost, tied
+        hipEvent_t ev_a = nullptr, ev_b = nullptr;  // rt_render_aov_*: the kernel's bracket (made by the scene's first AOV call)
     };
     mutable QueryState query;
     rt_scene() = default;
@@ -2359,6 +2631,8 @@ struct rt_scene {
                         (void *)d_mats, (void *)d_lights, (void *)d_order, (void *)d_tables, (void *)query.d_words, (void *)query.d_over})
             (void)hipFree(q);
         if (query.h_words) (void)hipHostFree(query.h_words);
+        if (query.ev_a) (void)hipEventDestroy(query.ev_a);
+        if (query.ev_b) (void)hipEventDestroy(query.ev_b);
     }
     // the inverse leaf order belongs to one tree: the next rt_query_any_device makes it for the scene's
     void drop_query_inverse() {
@@ -4397,6 +4671,167 @@ static int render_rays_keyed_impl(const rt_scene *scene, int64_t n_rays, const f
     return 0;
 }
 
+// rt_render_aov_fixed / rt_render_aov_rays_fixed_device: the entry points check their arguments (and, for a table, run the
+// device prepasses) and hand the ray source over; this is the one body behind both -- the reference's tree where the hit
+// definition needs it, the overflow stacks, the launch sized from the device, the kernel's time and the rare-path counters.
+// The caller holds the scene's query lock and has entered the scene's device; q.d_words is zeroed on `st`.
+template <class SRC>
+using AovKernel = void (*)(DScene, SRC, AovParams, int, int *);
+template <class SRC>
+static AovKernel<SRC> aov_kernel(bool literal, bool verify, bool wide) {
+    if (literal) return k_aov<SRC, false, true, false>;
+    if (verify) return wide ? k_aov<SRC, true, false, true> : k_aov<SRC, false, false, true>;
+    return wide ? k_aov<SRC, true, false, false> : k_aov<SRC, false, false, false>;
+}
+static int aov_flags(const std::string &w, uint32_t flags) {
+    if (flags & ~(uint32_t)(RT_FLAG_WATERTIGHT | RT_FLAG_REFERENCE_WALK | RT_FLAG_TIME_KERNELS))
+        return fail(w + ": flags other than RT_FLAG_WATERTIGHT / RT_FLAG_REFERENCE_WALK / RT_FLAG_TIME_KERNELS");
+    if ((flags & RT_FLAG_REFERENCE_WALK) && (flags & RT_FLAG_WATERTIGHT))
+        return fail(w + ": RT_FLAG_REFERENCE_WALK and RT_FLAG_WATERTIGHT exclude each other");
+    return 0;
+}
+static int aov_query_state(const rt_scene *scene) {  // (as the first query of this scene)
+    rt_scene::QueryState &q = scene->query;
+    if (!q.d_words) {
+        HIP_TRY(hipDeviceGetAttribute(&q.cus, hipDeviceAttributeMultiprocessorCount, scene->device));
+        HIP_TRY(hipHostMalloc((void **)&q.h_words, sizeof(QueryWords), hipHostMallocDefault));
+        HIP_TRY(hipMalloc((void **)&q.d_words, sizeof(QueryWords)));
+    }
+    if (!q.ev_a) HIP_TRY(hipEventCreate(&q.ev_a));
+    if (!q.ev_b) HIP_TRY(hipEventCreate(&q.ev_b));
+    return 0;
+}
+template <class SRC>
+static int aov_launch(const rt_scene *scene, const SRC &src, int n, uint32_t flags, int64_t *d_aov, int32_t *d_ids, hipStream_t st,
+                      rt_stats *stats) {
+    rt_scene::QueryState &q = scene->query;
+    const bool literal = (flags & RT_FLAG_REFERENCE_WALK) != 0;
+    const bool verify = !literal && (flags & RT_FLAG_WATERTIGHT) == 0;
+    if ((literal || verify) && ensure_ref_tree(scene)) return 1;
+    const int stack_cap = lds_stack_cap(scene, kLdsStack);
+    if (ensure_overflow(q.d_over, q.over_levels, std::max(scene->stack_bound, 32) - stack_cap)) return 1;
+    AovParams ap{};
+    ap.n = n;
+    ap.sums = (unsigned long long *)d_aov;
+    ap.ids = d_ids;
+    ap.vstat = q.d_words->vstat;
+    const AovKernel<SRC> kernel = aov_kernel<SRC>(literal, verify, scene->wide);
+    const size_t lds = sizeof(int) * kBlock * (size_t)(stack_cap + 1);
+    int per_cu = 0;
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kBlock, lds));
+    // (k_query's grid: what the device holds at once, never more lanes than the overflow stacks have columns)
+    const int resident = std::min(std::max(per_cu, 1) * std::max(q.cus, 1), kOverStride / kBlock);
+    const int grid = std::max(1, std::min(resident, (int)(((size_t)n + kBlock - 1) / kBlock)));
+    HIP_TRY(hipEventRecord(q.ev_a, st));
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, st, scene->dev(), src, ap, stack_cap, q.d_over);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(q.ev_b, st));
+    HIP_TRY(hipMemcpyAsync(q.h_words->vstat, q.d_words->vstat, sizeof(q.h_words->vstat), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, q.ev_a, q.ev_b));
+    if (stats) {
+        memset(stats, 0, sizeof(*stats));
+        stats->camera_rays = n;
+        stats->closest_rays = n;
+        stats->bvh_nodes = scene->n_nodes;
+        stats->bvh_depth = scene->max_depth;
+        stats->seconds_render = ms * 1e-3;
+        stats->seconds_trace = ms * 1e-3;
+        stats->launches_trace = 1;
+        stats->reserved[4] = (int64_t)q.h_words->vstat[V_LITERAL];
+        stats->reserved[5] = (int64_t)q.h_words->vstat[V_LOST];
+        stats->reserved[6] = (int64_t)q.h_words->vstat[V_TIE];
+    }
+    return 0;
+}
+
+static int render_aov_impl(const rt_scene *scene, const rt_camera *camera, int width, int height, int spp, uint64_t seed,
+                           int shard_index, int shard_count, uint32_t flags, int64_t *d_aov, int32_t *d_ids, hipStream_t st,
+                           rt_stats *stats) {
+    const std::string w("rt_render_aov_fixed");
+    if (!scene) return fail(w + ": null scene");
+    if (!camera || !d_aov) return fail(w + ": null " + (!camera ? "camera" : "d_aov_fixed"));
+    if (aov_flags(w, flags)) return 1;
+    if (width < 1 || height < 1 || spp < 1)
+        return fail(w + ": width, height and num_samples must be at least 1 (" + std::to_string(width) + " x " + std::to_string(height) + " x " + std::to_string(spp) + ")");
+    if ((long long)width * height > (long long)(0x7fffffff / 3)) return fail(w + ": width*height exceeds 715827882 pixels");
+    if ((long long)width * height * spp + 13LL * kW >= (1LL << 31)) return fail(w + ": width*height*num_samples exceeds the int32 camera-ray range");
+    if (shard_count < 1 || shard_index < 0 || shard_index >= shard_count)
+        return fail(w + ": shard_index = " + std::to_string(shard_index) + " is outside 0 .. shard_count - 1 (shard_count = " + std::to_string(shard_count) + ")");
+    if (spp % shard_count != 0)
+        return fail(w + ": num_samples = " + std::to_string(spp) + " is not divisible by shard_count = " + std::to_string(shard_count));
+    DeviceGuard dev;
+    if (dev.enter(scene->device)) return 1;
+    // (camera rays start at lookfrom: as render_shard_impl)
+    if (int rc = ensure_origin_radius(scene, camera->lookfrom)) return rc;
+    rt_scene::QueryState &q = scene->query;
+    std::lock_guard<std::mutex> lock(q.mutex);
+    if (aov_query_state(scene)) return 1;
+    HIP_TRY(hipMemsetAsync(q.d_words, 0, sizeof(QueryWords), st));
+    AovCamera src{};
+    memcpy(&src.cam, camera, sizeof(Camera));
+    src.width = width;
+    src.height = height;
+    src.spp = (unsigned)(spp / shard_count);
+    src.key_mul = (unsigned)shard_count;
+    src.key_add = (unsigned)shard_index;
+    src.seed_lo = (uint32_t)seed;
+    src.seed_hi = (uint32_t)(seed >> 32);
+    const int n = (int)((long long)width * height * (spp / shard_count));
+    // the sample with G % num_samples == 0 has G % shard_count == 0: it is shard 0's
+    return aov_launch(scene, src, n, flags, d_aov, shard_index == 0 ? d_ids : nullptr, st, stats);
+}
+
+static int render_aov_rays_impl(const rt_scene *scene, int64_t n_rays, const float *d_o, const float *d_d, const int32_t *d_pixel,
+                                int rays_per_pixel, int n_pixels, uint64_t key_first, uint32_t key_stride, uint32_t flags,
+                                int64_t *d_aov, int32_t *d_ids, hipStream_t st, rt_stats *stats) {
+    const std::string w("rt_render_aov_rays_fixed_device");
+    if (!scene) return fail(w + ": null scene");
+    if (!d_o || !d_d || !d_aov) return fail(w + ": null " + (!d_o ? "d_origin_xyz" : !d_d ? "d_dir_xyz" : "d_aov_fixed"));
+    if (aov_flags(w, flags)) return 1;
+    if (d_ids && d_pixel) return fail(w + ": d_ids together with d_pixel (ids belong to the pixels of the key rule: pass d_pixel = NULL)");
+    // (the checks of render_rays_keyed_impl)
+    if (n_rays < 1) return fail(w + ": n_rays = " + std::to_string((long long)n_rays) + " (at least 1)");
+    if (n_rays + 13LL * kW >= (1LL << 31)) return fail(w + ": n_rays exceeds the int32 camera-ray range of one call");
+    if (n_pixels < 1 || n_pixels > 0x7fffffff / 3) return fail(w + ": n_pixels = " + std::to_string(n_pixels) + " is outside 1 .. 715827882");
+    if (key_stride < 1) return fail(w + ": key_stride = 0 (at least 1)");
+    const unsigned long long span = (unsigned long long)(n_rays - 1) * key_stride;
+    if (span > ~0ull - (unsigned long long)key_first)
+        return fail(w + ": the key of the last ray, " + std::to_string((unsigned long long)key_first) + " + " + std::to_string(span) + ", wraps 2^64");
+    const unsigned long long key_last = (unsigned long long)key_first + span;
+    if (!d_pixel) {
+        if (rays_per_pixel < 1) return fail(w + ": rays_per_pixel = " + std::to_string(rays_per_pixel) + " (at least 1 when d_pixel is null)");
+        if (key_last / (unsigned)rays_per_pixel >= (unsigned long long)n_pixels)
+            return fail(w + ": key " + std::to_string(key_last) + " falls on pixel " + std::to_string(key_last / (unsigned)rays_per_pixel) + " of " +
+                        std::to_string(n_pixels));
+    }
+    DeviceGuard dev;
+    if (dev.enter(scene->device)) return 1;
+    const int n = (int)n_rays;
+    rt_scene::QueryState &q = scene->query;
+    std::lock_guard<std::mutex> lock(q.mutex);
+    if (aov_query_state(scene)) return 1;
+    const dim3 grid(std::min((n + kBlock - 1) / kBlock, 8 * std::max(q.cus, 1)));
+    HIP_TRY(hipMemsetAsync(q.d_words, 0, sizeof(QueryWords), st));
+    hipLaunchKernelGGL(k_query_prepass, grid, dim3(kBlock), 0, st, d_o, d_d, n, q.d_words);
+    if (d_pixel) hipLaunchKernelGGL(k_pixel_prepass, grid, dim3(kBlock), 0, st, d_pixel, n, n_pixels, q.d_words);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(q.h_words, q.d_words, 6 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (q.h_words->bad_dirs != 0)
+        return fail(w + ": " + std::to_string(q.h_words->bad_dirs) + " of " + std::to_string(n) + " directions are not finite or reach 2^126");
+    if (q.h_words->bad_pixels != 0)
+        return fail(w + ": " + std::to_string(q.h_words->bad_pixels) + " of " + std::to_string(n) + " pixel indices are outside 0 .. " + std::to_string(n_pixels - 1));
+    float need[3];
+    memcpy(need, q.h_words->radius_bits, sizeof(need));
+    if (int rc = ensure_origin_radius(scene, need)) return rc;
+    const uint32_t rpp = d_pixel ? 1u : (uint32_t)rays_per_pixel;
+    const KeyedRayTable src{d_o, d_d, d_pixel, (unsigned long long)key_first, key_stride, rpp,
+                            d_pixel ? 0 : (int)(key_first / rpp), d_pixel ? 0u : (uint32_t)(key_first % rpp)};
+    return aov_launch(scene, src, n, flags, d_aov, d_ids, st, stats);
+}
+
 }  // namespace
 
 // ============================================================================ C-ABI
@@ -4678,6 +5113,32 @@ int rt_post_process_fixed(const int64_t *d_sum_fixed, float *d_rgb_out, int num_
     float inv = 1.f / (float)num_samples;
     hipLaunchKernelGGL(k_post_process_fixed, dim3((nv + 255) / 256), dim3(256), 0, (hipStream_t)stream,
                        (const long long *)d_sum_fixed, d_rgb_out, nv, inv);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int rt_render_aov_fixed(const rt_scene *scene, const rt_camera *camera, int width, int height, int num_samples, uint64_t seed,
+                        int shard_index, int shard_count, uint32_t flags, int64_t *d_aov_fixed, int32_t *d_ids, void *stream,
+                        rt_stats *stats) {
+    return render_aov_impl(scene, camera, width, height, num_samples, seed, shard_index, shard_count, flags, d_aov_fixed, d_ids,
+                           (hipStream_t)stream, stats);
+}
+
+int rt_render_aov_rays_fixed_device(const rt_scene *scene, int64_t n_rays, const float *d_origin_xyz, const float *d_dir_xyz,
+                                    const int32_t *d_pixel, int rays_per_pixel, int n_pixels, uint64_t key_first,
+                                    uint32_t key_stride, uint32_t flags, int64_t *d_aov_fixed, int32_t *d_ids, void *stream,
+                                    rt_stats *stats) {
+    return render_aov_rays_impl(scene, n_rays, d_origin_xyz, d_dir_xyz, d_pixel, rays_per_pixel, n_pixels, key_first, key_stride,
+                                flags, d_aov_fixed, d_ids, (hipStream_t)stream, stats);
+}
+
+int rt_aov_resolve(const int64_t *d_aov_fixed, float *d_out, int n_pixels, int num_samples, void *stream) {
+    if (!d_aov_fixed || !d_out) return fail(std::string("rt_aov_resolve: null ") + (!d_aov_fixed ? "d_aov_fixed" : "d_out"));
+    if (n_pixels < 1 || num_samples < 1) return fail("rt_aov_resolve: n_pixels and num_samples must be at least 1");
+    const long long nv = (long long)n_pixels * RT_AOV_CHANNELS;
+    const float inv = 1.f / (float)num_samples;
+    hipLaunchKernelGGL(k_aov_resolve, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const long long *)d_aov_fixed, d_out, nv, inv);
     HIP_TRY(hipGetLastError());
     return 0;
 }
