@@ -12,6 +12,7 @@
 //     its records and leaf order (bit-equal to the device's), checked as above, with its surface-area cost next to rtbvh::build's.
 //   * rt_hostwalk_*     the same walk for arbitrary rays (closest hit / any hit), with work counters: the traversal
 //     audit (tests/test_traversal_audit.py) replays the rays of an oracle render through it.
+//   * rt_plan_paths_launch  the launch geometry of the persistent frame kernels (rt_launch_plan.h), as the library computes it.
 #include <cfloat>
 #include <cmath>
 #include <cstdint>
@@ -21,6 +22,7 @@
 #include <vector>
 
 #include "rt_bvh.h"
+#include "rt_launch_plan.h"
 #include "rt_ploc.h"
 #include "rt_ref_tree.h"
 
@@ -897,5 +899,11 @@ int rt_ref_tree_export(const float *tri9, int n, float *bounds6, int *count, int
         for (size_t i = 0; i < t.prims.size(); i++) prims[i] = t.prims[i];
     }
     return (int)t.nodes.size();
+}
+// The persistent launch as render_shard_impl plans it (tests/test_launch_plan_host.py); out10: PathsLaunch's fields in order.
+void rt_plan_paths_launch(int n, int cus, int wide, int n_nodes, int paths_cap, int lattice, int width, int spp, int64_t fixed_lds_bytes, int64_t *out10) {
+    const rtplan::PathsLaunch p = rtplan::plan_paths_launch(n, cus, wide != 0, n_nodes, paths_cap, lattice != 0, width, spp, (size_t)fixed_lds_bytes);
+    const int64_t v[10] = {p.blocks, p.few_blocks, (int64_t)p.lds_bytes, p.top_n, p.adv_batch, p.gen_batch, p.tri_follow, p.prio_rotate, p.rot_wave, p.rot_set};
+    memcpy(out10, v, sizeof(v));
 }
 }

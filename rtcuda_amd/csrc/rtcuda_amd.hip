@@ -1,4 +1,5 @@
 // rtcuda_amd.hip -- HIP kernels and the C-ABI of the MI355X-native render path (gfx950 only).
+// The root of the one translation unit: kernels and C-ABI; the host side between them is rt_host_scene.inc + rt_host_render.inc.
 //
 // The hot path of lashhw/rtcuda (render.cuh:61-457) re-designed for CDNA4:
 //
@@ -60,6 +61,7 @@
 #include "../../include/rtcuda_amd.h"
 #include "rt_bvh.h"
 #include "rt_device.h"
+#include "rt_launch_plan.h"
 #include "rt_ploc.h"
 #include "rt_ref_tree.h"
 
@@ -86,6 +88,7 @@ using rtbvh::knob;  // (experiment knobs are read only under RTCUDA_EXPERIMENTAL
 constexpr int kW = RT_NUM_WORKING_PATHS;
 constexpr uint32_t kFlagFixedFb = 0x200u;  // internal: d_sum points to int64 fixed-point sums
 constexpr int kBlock = 256;       // 4 waves per workgroup
+static_assert(rtplan::kBlock == kBlock && rtplan::kSlots == kW, "rt_launch_plan.h plans for this workgroup and this pool");
 constexpr int kLdsStack = 16;          // traversal stack entries kept in LDS per lane (k_trace)
 constexpr int kPathsLdsStack = 10;     // ... by k_paths: 10 + 1 + 26 rows = 37 KB per workgroup, four workgroups per CU; with 10 the
                                        // step without overflow handling (inner_step<WIDE, SHALLOW>) serves 95 % of the node steps
@@ -2540,2298 +2543,8 @@ __global__ void k_ploc_remap_ref(const int *__restrict__ prims, const int *__res
     new_leaf_of[inverse[old_order[i]]] = leaf_of[i];
 }
 
-// ============================================================================ host side
-// What the kernels read in leaf order, and the tree: a scene's own arrays (rt_scene_create, rt_scene_update) or new ones that
-// replace them once they are complete (rt_scene_rebuild).  Written by emit_scene.
-struct SceneArrays {
-    const int *order;          // leaf order -> caller's triangle index
-    const rtbvh::Pair *recs;   // 4-wide: the builder's unpadded records
-    int n_records;
-    float4 *nodes, *tris, *shade;
-    int2 *info;
-    Light *lights;
-    float *tables;
-};
-
-struct rt_scene {
-    int device = 0;
-    int n_tris = 0, n_nodes = 0, max_depth = 0, stack_bound = 1, n_leaves = 0, n_lights = 0, n_mats = 0;
-    float4 *d_nodes = nullptr;
-    bool wide = false;  // node records: 4-wide (two pair-style records per node, rtbvh::Result::quads) or 2-wide (rtbvh::Pair)
-    // 4-wide: the builder's unpadded records on the device (links fixed by the build, boxes refit by rt_scene_update) and on
-    // the host; d_nodes holds them padded for the ray origins that will be traced (rt_bvh.h, pad_quads_for_origins) within
-    // origin_radius, which only grows (k_refit_emit reports it in d_radius).  pad_mutex serialises every writer of these.
-    rtbvh::Pair *d_recs = nullptr;
-    std::vector<rtbvh::Pair> h_quads;
-    float *d_radius = nullptr;
-    mutable float origin_radius[3] = {0.f, 0.f, 0.f};
-    mutable std::mutex pad_mutex;
-    double build_seconds = 0.0;  // BVH build time (host wall clock, or device events for PLOC)
-    int builder = 0;             // 0 host SAH, 2 device PLOC (RT_SCENE_DEVICE_BVH, rt_scene_rebuild)
-    float4 *d_tris = nullptr;
-    int2 *d_tri_info = nullptr;
-    float4 *d_tri_shade = nullptr;
-    Material *d_mats = nullptr;
-    Light *d_lights = nullptr;
-    float *d_tables = nullptr;    // shading tables (see DScene)
-    int tab_dwords = 0;
-    int *d_order = nullptr;       // leaf order -> original
-    std::vector<int> h_order;     // leaf order -> original
-    std::vector<int> h_inverse;   // original -> leaf order
-    // RT_FLAG_REFERENCE_WALK: the reference's own tree (rt_ref_tree.h), built and uploaded by the first render that asks
-    // for it (ensure_ref_tree) from the caller's triangles kept here
-    std::vector<float> h_tri9;
-    // rt_render_multi: what a replica of this scene on another device is created from, and the replicas made so far
-    // (emit_scene also reads the materials of the triangles and the lights from here)
-    std::vector<int32_t> h_tri_material, h_tri_light;
-    std::vector<rt_material> h_materials;
-    std::vector<rt_light> h_lights;
-    mutable std::mutex replica_mutex;
-    mutable std::vector<rt_scene *> replicas;  // owned; at most one per device
-    mutable std::mutex ref_mutex;
-    mutable bool ref_ready = false;
-    mutable float4 *d_ref_nodes = nullptr;
-    mutable int *d_ref_prims = nullptr;
-    mutable int *d_ref_leaf_of = nullptr;  // leaf-order triangle index -> node of its leaf in the reference's tree (ref_visible)
-    mutable int *d_ref_parent = nullptr;   // node -> parent node (root: -1)
-    mutable int ref_nodes_count = 0, ref_depth = 0;
-    mutable bool ref_root_leaf = true;
-    mutable double build_seconds_ref = 0.0;  // host time of the reference-tree build + upload (one-off, first render that needs it)
-    // rt_scene_update (4-wide only): the tree's nodes grouped by level, deepest level first (refit_level_end[l] = end of level
-    // l's span) and the exact box of every node (scratch between the level launches) -- set up by the first update
-    std::vector<int> refit_level_end;
-    int *d_refit_nodes = nullptr;
-    float *d_refit_exact = nullptr;
-    int64_t refits = 0;
-    double refit_seconds = 0.0;                 // device time of the last refit (HIP events)
-    double sah_build = 0.0, sah_now = 0.0;      // surface-area cost of the 4-wide tree at build time / now
-    // rt_query_*_device: what a query call needs besides the caller's buffers, made by the first query and reused -- the
-    // scratch words on the device and their pinned host copy, the overflow part of the traversal stacks (ensure_overflow),
-    // the inverse leaf order on the device (rt_query_any_device; dropped with the leaf order it belongs to: adopt_tree) and
-    // the rare-path counters of the last query.  `mutex`: queries of one scene take turns (they share these).
-    struct QueryState {
-        std::mutex mutex;
-        QueryWords *d_words = nullptr, *h_words = nullptr;
-        int *d_over = nullptr, over_levels = 0;
-        int *d_inverse = nullptr;
-        int cus = 0;
-        int64_t counters[3] = {0, 0, 0};  // re-traced, lost, tied
-        hipEvent_t ev_a = nullptr, ev_b = nullptr;  // rt_render_aov_*: the kernel's bracket (made by the scene's first AOV call)
-    };
-    mutable QueryState query;
-    rt_scene() = default;
-    rt_scene(const rt_scene &) = delete;
-    rt_scene &operator=(const rt_scene &) = delete;
-    ~rt_scene() {  // (every early return of rt_scene_create goes through here: nothing leaks on an error path)
-        drop_replicas();
-        drop_ref_tree();
-        drop_refit();
-        drop_query_inverse();
-        for (void *q : {(void *)d_nodes, (void *)d_recs, (void *)d_radius, (void *)d_tris, (void *)d_tri_info, (void *)d_tri_shade,
-                        (void *)d_mats, (void *)d_lights, (void *)d_order, (void *)d_tables, (void *)query.d_words, (void *)query.d_over})
-            (void)hipFree(q);
-        if (query.h_words) (void)hipHostFree(query.h_words);
-        if (query.ev_a) (void)hipEventDestroy(query.ev_a);
-        if (query.ev_b) (void)hipEventDestroy(query.ev_b);
-    }
-    // the inverse leaf order belongs to one tree: the next rt_query_any_device makes it for the scene's
-    void drop_query_inverse() {
-        (void)hipFree(query.d_inverse);
-        query.d_inverse = nullptr;
-    }
-    // the reference's tree is a function of the triangles: the next render that needs it builds it again from h_tri9
-    void drop_ref_tree() {
-        std::lock_guard<std::mutex> lock(ref_mutex);
-        for (void *q : {(void *)d_ref_nodes, (void *)d_ref_prims, (void *)d_ref_leaf_of, (void *)d_ref_parent}) (void)hipFree(q);
-        d_ref_nodes = nullptr;
-        d_ref_prims = d_ref_leaf_of = d_ref_parent = nullptr;
-        ref_nodes_count = ref_depth = 0;
-        ref_root_leaf = true;
-        ref_ready = false;
-    }
-    // replicas on other devices (rt_render_multi) hold the old geometry or tree: recreated from the host copies on next use
-    void drop_replicas() {
-        std::lock_guard<std::mutex> lock(replica_mutex);
-        for (rt_scene *r : replicas) delete r;
-        replicas.clear();
-    }
-    // the refit's levels belong to one tree: the next rt_scene_update sets them up for the scene's (caller holds pad_mutex)
-    void drop_refit() {
-        (void)hipFree(d_refit_nodes);
-        (void)hipFree(d_refit_exact);
-        d_refit_nodes = nullptr;
-        d_refit_exact = nullptr;
-        refit_level_end.clear();
-    }
-    // the largest material and light index a triangle names (-1: none), for rt_scene_set_materials / rt_scene_set_lights
-    int max_tri_material = -1, max_tri_light = -1;
-    void note_index_maxima() {
-        max_tri_material = max_tri_light = -1;
-        for (int32_t m : h_tri_material) max_tri_material = std::max(max_tri_material, (int)m);
-        for (int32_t l : h_tri_light) max_tri_light = std::max(max_tri_light, (int)l);
-    }
-    void set_order(const std::vector<int32_t> &order) {
-        h_order.assign(order.begin(), order.end());
-        h_inverse.assign(h_order.size(), 0);
-        for (size_t k = 0; k < h_order.size(); k++) h_inverse[(size_t)h_order[k]] = (int)k;
-    }
-    SceneArrays arrays() const { return {d_order, d_recs, n_nodes, d_nodes, d_tris, d_tri_shade, d_tri_info, d_lights, d_tables}; }
-    DScene dev() const {
-        DScene s;
-        s.nodes = d_nodes;
-        s.tris = d_tris;
-        s.tri_info = d_tri_info;
-        s.tri_shade = d_tri_shade;
-        s.order = d_order;
-        s.mats = d_mats;
-        s.lights = d_lights;
-        s.num_lights = n_lights;
-        s.num_mats = n_mats;
-        s.tables = d_tables;
-        s.tab_dwords = tab_dwords;
-        s.ref_nodes = d_ref_nodes;
-        s.ref_prims = d_ref_prims;
-        s.ref_n_prims = ref_ready ? n_tris : 0;
-        s.ref_leaf_of = d_ref_leaf_of;
-        s.ref_parent = d_ref_parent;
-        s.ref_root_leaf = ref_root_leaf ? 1 : 0;
-        return s;
-    }
-};
-
-namespace {
-
-// ---- XORWOW host pieces: seed scramble and the 2^67 jump matrices J^(2^k)
-Rng xorwow_seed(uint64_t seed) {  // curand_init's scramble (curand_kernel.h)
-    uint32_t s0 = ((uint32_t)seed) ^ 0xaad26b49u;
-    uint32_t s1 = ((uint32_t)(seed >> 32)) ^ 0xf7dcefddu;
-    uint32_t t0 = 1099087573u * s0;
-    uint32_t t1 = 2591861531u * s1;
-    Rng st;
-    st.d = 6615241u + t1 + t0;
-    st.v0 = 123456789u + t0;
-    st.v1 = 362436069u ^ t0;
-    st.v2 = 521288629u + t1;
-    st.v3 = 88675123u ^ t1;
-    st.v4 = 5783321u + t0;
-    return st;
-}
-typedef uint32_t Mat160[160][5];
-void mat160_apply(const Mat160 &m, const uint32_t in[5], uint32_t out[5]) {
-    uint32_t r[5] = {0, 0, 0, 0, 0};
-    for (int w = 0; w < 5; w++)
-        for (int b = 0; b < 32; b++)
-            if (in[w] & (1u << b))
-                for (int k = 0; k < 5; k++) r[k] ^= m[w * 32 + b][k];
-    memcpy(out, r, sizeof(r));
-}
-void mat160_square(Mat160 &m) {
-    static Mat160 tmp;
-    for (int i = 0; i < 160; i++) mat160_apply(m, m[i], tmp[i]);
-    memcpy(m, tmp, sizeof(Mat160));
-}
-// host table: 20 matrices J^(2^k), J = (one xorwow step)^(2^67)
-const std::vector<uint32_t> &jump_powers() {
-    static std::vector<uint32_t> table;
-    static std::once_flag once;
-    std::call_once(once, [] {
-        static Mat160 a;
-        for (int w = 0; w < 5; w++)
-            for (int b = 0; b < 32; b++) {
-                uint32_t v[5] = {0, 0, 0, 0, 0};
-                v[w] = 1u << b;
-                uint32_t t = v[0] ^ (v[0] >> 2);
-                v[0] = v[1];
-                v[1] = v[2];
-                v[2] = v[3];
-                v[3] = v[4];
-                v[4] = (v[4] ^ (v[4] << 4)) ^ (t ^ (t << 1));
-                memcpy(a[w * 32 + b], v, sizeof(v));
-            }
-        for (int s = 0; s < 67; s++) mat160_square(a);
-        table.resize((size_t)20 * 160 * 5);
-        for (int k = 0; k < 20; k++) {
-            memcpy(table.data() + (size_t)k * 800, a, sizeof(Mat160));
-            mat160_square(a);
-        }
-    });
-    return table;
-}
-
-// 2-wide nodes (RT_BVH_WIDE=0, or a host tree too deep for the 4-wide walk's stack): a 64-byte record with the two children's
-// bounds INTERLEAVED --
-//   (l.lo.x, r.lo.x, l.lo.y, r.lo.y | l.lo.z, r.lo.z, l.hi.x, r.hi.x | l.hi.y, r.hi.y, l.hi.z, r.hi.z | llink, rlink, spare, spare)
-// -- so that every (left, right) pair of bounds arrives in an aligned register pair and the slab arithmetic of both children
-// runs as packed fp32, see inner_step.  (The 4-wide layout is k_refit_emit's.)
-int upload_pairs(const rt_scene *sc, const std::vector<rtbvh::Pair> &pairs) {
-    std::vector<float> inter(16 * pairs.size());
-    for (size_t k = 0; k < pairs.size(); k++) {
-        const rtbvh::Pair &pr = pairs[k];
-        float *r = &inter[16 * k];
-        for (int a = 0; a < 6; a++) {
-            r[2 * a] = pr.lbox[a];
-            r[2 * a + 1] = pr.rbox[a];
-        }
-        memcpy(&r[12], &pr.llink, 4);
-        memcpy(&r[13], &pr.rlink, 4);
-        r[14] = r[15] = 0.f;
-    }
-    HIP_TRY(hipMemcpy(sc->d_nodes, inter.data(), 64 * pairs.size(), hipMemcpyHostToDevice));
-    return 0;
-}
-
-// Structural check of 4-wide records before they are uploaded (a malformed tree would hang the GPU): every node reachable
-// from the root exactly once (two consecutive records per node; inner links are even record indices), every triangle
-// position in exactly one leaf, plus the invariant the kernels' box test rests on: a child is absent (link kNoChild) if and
-// only if its box is all +inf -- the one-comparison slab test of inner_step<true> never looks at links.
-bool validate_quads(const std::vector<rtbvh::Pair> &quads, int n_tris) {
-    const int nr = (int)quads.size();
-    if (nr < 2 || (nr & 1)) return false;
-    std::vector<char> seen_node((size_t)nr / 2, 0), seen_tri((size_t)std::max(n_tris, 1), 0);
-    std::vector<int> todo{0};
-    seen_node[0] = 1;
-    int visited = 0, tris = 0;
-    while (!todo.empty()) {
-        const int rec = todo.back();
-        todo.pop_back();
-        visited++;
-        for (int k = 0; k < 4; k++) {
-            const rtbvh::Pair &p = quads[(size_t)rec + (k >> 1)];
-            const int l = (k & 1) ? p.rlink : p.llink;
-            const float *b = (k & 1) ? p.rbox : p.lbox;
-            bool all_inf = true, finite = true;
-            for (int a = 0; a < 6; a++) {
-                all_inf = all_inf && b[a] == INFINITY;
-                finite = finite && std::isfinite(b[a]);
-            }
-            if (l == rtbvh::kNoChild) {
-                if (!all_inf) return false;
-                continue;
-            }
-            if (!finite || b[0] > b[3] || b[1] > b[4] || b[2] > b[5]) return false;
-            if (l >= 0) {
-                if ((l & 1) || l >= nr || seen_node[l / 2]) return false;
-                seen_node[l / 2] = 1;
-                todo.push_back(l);
-            } else {
-                const int ref = ~l, first = ref >> 3, count = ref & 7;
-                if (count <= 0 || first < 0 || first + count > n_tris) return false;
-                for (int t = first; t < first + count; t++) {
-                    if (seen_tri[t]) return false;
-                    seen_tri[t] = 1;
-                    tris++;
-                }
-            }
-        }
-    }
-    return visited == nr / 2 && tris == n_tris;
-}
-
-// RT_FLAG_REFERENCE_WALK: build the reference's tree from the caller's triangles, check its structure (a malformed tree
-// would hang the walk: every node reached exactly once, children adjacent, every primitive position in exactly one
-// leaf, depth within the walk's private stack) and upload it.  Once per scene, on the scene's device.
-// `built` (may be null): whether THIS call built the tree, decided under the lock (two first renders may race to it).
-int ensure_ref_tree(const rt_scene *scene, bool *built = nullptr) {
-    std::lock_guard<std::mutex> lock(scene->ref_mutex);
-    if (built) *built = false;
-    if (scene->ref_ready) return 0;
-    const auto t_begin = std::chrono::steady_clock::now();
-    const int n = scene->n_tris;
-    if ((int)scene->h_tri9.size() != 9 * n) return fail("RT_FLAG_REFERENCE_WALK: the scene holds no triangle copy");
-    const rtref::Tree t = rtref::build(scene->h_tri9.data(), n);
-    const int nn = (int)t.nodes.size();
-    if (n > 0) {
-        std::vector<char> seen_node((size_t)nn, 0), seen_prim((size_t)n, 0);
-        std::vector<std::pair<int, int>> todo{{0, 0}};  // (node, depth)
-        int visited = 0, prims = 0;
-        seen_node[0] = 1;
-        while (!todo.empty()) {
-            const auto [k, dep] = todo.back();
-            todo.pop_back();
-            visited++;
-            const rtref::Node &nd = t.nodes[(size_t)k];
-            if (nd.count > 0) {
-                if (nd.link < 0 || nd.link + nd.count > n) return fail("RT_FLAG_REFERENCE_WALK: malformed leaf");
-                for (int i = nd.link; i < nd.link + nd.count; i++) {
-                    if (seen_prim[i]) return fail("RT_FLAG_REFERENCE_WALK: primitive in two leaves");
-                    seen_prim[i] = 1;
-                    prims++;
-                }
-            } else {
-                if (nd.count < 0 || nd.link <= 0 || nd.link + 1 >= nn || seen_node[nd.link] || seen_node[nd.link + 1] || dep >= rtref::kMaxDepth)
-                    return fail("RT_FLAG_REFERENCE_WALK: malformed inner node");
-                seen_node[nd.link] = seen_node[nd.link + 1] = 1;
-                todo.push_back({nd.link, dep + 1});
-                todo.push_back({nd.link + 1, dep + 1});
-            }
-        }
-        if (visited != nn || prims != n) return fail("RT_FLAG_REFERENCE_WALK: tree does not cover the scene");
-        for (int i = 0; i < n; i++)
-            if (t.prims[i] < 0 || t.prims[i] >= n) return fail("RT_FLAG_REFERENCE_WALK: bad primitive order");
-    }
-    std::vector<int> prim_leaf((size_t)std::max(n, 1), 0);  // reference primitive position -> this scene's leaf-order index
-    for (int i = 0; i < n; i++) prim_leaf[i] = scene->h_inverse[t.prims[i]];
-    // what ref_visible reads: the leaf of every triangle (leaf-order index -> node) and the way up from there
-    std::vector<int> leaf_of((size_t)std::max(n, 1), 0), parent((size_t)std::max(nn, 1), -1);
-    for (int k = 0; k < nn; k++) {
-        const rtref::Node &nd = t.nodes[(size_t)k];
-        if (nd.count > 0) {
-            for (int i = nd.link; i < nd.link + nd.count; i++) leaf_of[(size_t)prim_leaf[(size_t)i]] = k;
-        } else if (n > 0) {
-            parent[(size_t)nd.link] = parent[(size_t)nd.link + 1] = k;
-        }
-    }
-    float4 *dn = nullptr;
-    int *dp = nullptr, *dl = nullptr, *dpar = nullptr;
-    if (hipMalloc((void **)&dn, sizeof(rtref::Node) * (size_t)std::max(nn, 1)) != hipSuccess ||
-        hipMalloc((void **)&dp, sizeof(int) * prim_leaf.size()) != hipSuccess ||
-        hipMalloc((void **)&dl, sizeof(int) * leaf_of.size()) != hipSuccess ||
-        hipMalloc((void **)&dpar, sizeof(int) * parent.size()) != hipSuccess ||
-        hipMemcpy(dn, t.nodes.data(), sizeof(rtref::Node) * (size_t)nn, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(dp, prim_leaf.data(), sizeof(int) * prim_leaf.size(), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(dl, leaf_of.data(), sizeof(int) * leaf_of.size(), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(dpar, parent.data(), sizeof(int) * parent.size(), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(dn);
-        (void)hipFree(dp);
-        (void)hipFree(dl);
-        (void)hipFree(dpar);
-        return fail("reference tree: device allocation or upload failed");
-    }
-    scene->d_ref_nodes = dn;
-    scene->d_ref_prims = dp;
-    scene->d_ref_leaf_of = dl;
-    scene->d_ref_parent = dpar;
-    scene->ref_root_leaf = n == 0 || t.nodes[0].count > 0;
-    scene->ref_nodes_count = nn;
-    scene->ref_depth = t.depth;
-    scene->build_seconds_ref = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
-    scene->ref_ready = true;
-    if (built) *built = true;
-    return 0;
-}
-
-// The argument checks of rt_scene_create, shared with the entry points that edit a scene (`w`: whose message it is):
-// the counts and the table pointers ...
-int check_scene_counts(const std::string &w, int n_tris, bool have_tri_arrays, const rt_material *materials, int n_materials,
-                       const rt_light *lights, int n_lights) {
-    if (n_tris < 0 || n_materials < 0 || n_lights < 0) return fail(w + ": negative count");
-    if (n_tris >= (1 << 24)) return fail(w + ": more than 2^24 - 1 triangles (24-bit triangle addressing)");
-    if (n_tris > 0 && !have_tri_arrays) return fail(w + ": null triangle arrays");
-    if (n_tris > 0 && (n_materials == 0 || !materials)) return fail(w + ": no materials");
-    if (n_lights > 0 && !lights) return fail(w + ": null lights");
-    if (n_materials > 65535 || n_lights > 32766) return fail(w + ": at most 65535 materials and 32766 lights");
-    return 0;
-}
-// ... the index ranges of the per-triangle HOST arrays (tri_light may be null; device arrays: k_index_prepass) ...
-int check_tri_indices(const std::string &w, int n_tris, const int32_t *tri_material, const int32_t *tri_light, int n_materials, int n_lights) {
-    for (int i = 0; i < n_tris; i++) {
-        if (tri_material && (tri_material[i] < 0 || tri_material[i] >= n_materials))
-            return fail(w + ": tri_material[" + std::to_string(i) + "] out of range");
-        if (tri_light && (tri_light[i] < -1 || tri_light[i] >= n_lights))
-            return fail(w + ": tri_light[" + std::to_string(i) + "] out of range");
-    }
-    return 0;
-}
-// ... and the tables themselves
-int check_scene_tables(const std::string &w, int n_tris, const rt_material *materials, int n_materials, const rt_light *lights, int n_lights) {
-    for (int i = 0; i < n_materials; i++)
-        if (materials[i].type < RT_MATTE || materials[i].type > RT_GLASS)
-            return fail(w + ": unknown material type");
-    for (int i = 0; i < n_lights; i++) {
-        if (lights[i].type != RT_POINT_LIGHT && lights[i].type != RT_AREA_LIGHT)
-            return fail(w + ": unknown light type");
-        if (lights[i].type == RT_AREA_LIGHT && (lights[i].triangle < 0 || lights[i].triangle >= n_tris))
-            return fail(w + ": area light triangle out of range");
-    }
-    return 0;
-}
-
-// Device temporaries and events of one host call: released on EVERY return path (HIP_TRY returns early on errors)
-struct DevScope {
-    std::vector<void *> ptrs;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    ~DevScope() {
-        for (void *q : ptrs) (void)hipFree(q);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-    }
-    template <typename T>
-    int alloc(T *&ptr, size_t count) {
-        void *raw = nullptr;
-        HIP_TRY(hipMalloc(&raw, std::max<size_t>(count, 1) * sizeof(T)));
-        ptrs.push_back(raw);
-        ptr = (T *)raw;
-        return 0;
-    }
-};
-// The scene's device made current for the rest of a host call; the caller's is restored on every return path
-struct DeviceGuard {
-    int saved = 0, current = 0;
-    int enter(int device) {
-        HIP_TRY(hipGetDevice(&saved));
-        current = saved;
-        if (device != saved) HIP_TRY(hipSetDevice(device));
-        current = device;
-        return 0;
-    }
-    ~DeviceGuard() {
-        if (current != saved) (void)hipSetDevice(saved);
-    }
-};
-
-// The 4-wide nodes the kernels walk, from the builder's unpadded records: padded for ray origins within `radius`, grown to
-// the records' bounds (k_refit_emit, which leaves the radius it used in sc->d_radius).  Ordered on `st`; the caller holds
-// pad_mutex and has made the scene's device current.
-void emit_nodes(const rt_scene *sc, const rtbvh::Pair *d_recs, int n_records, float4 *d_nodes, const float radius[3], hipStream_t st) {
-    const int n = n_records / 2;
-    hipLaunchKernelGGL(k_refit_emit, dim3((n + 255) / 256), dim3(256), 0, st, d_recs, n, radius[0], radius[1], radius[2],
-                       (float *)d_nodes, sc->d_radius);
-}
-
-// Before rays are traced whose origins may lie outside the radius the 4-wide records are padded for (a camera outside the
-// scene's bounds; the rays of the test hooks): re-pad, generously, on the null stream, and wait for it.  Renders of the same
-// scene that are in flight on other streams read a mix of the old and the new bounds meanwhile -- both are conservative for
-// THEIR rays.
-int ensure_origin_radius(const rt_scene *sc, const float need[3]) {
-    if (!sc->wide) return 0;
-    std::lock_guard<std::mutex> lock(sc->pad_mutex);
-    bool grow = false;
-    float radius[3];
-    for (int a = 0; a < 3; a++) {
-        const float want = std::isfinite(need[a]) ? std::fabs(need[a]) * 1.001f : 0.f;  // (a non-finite origin hits nothing anyway)
-        grow = grow || want > sc->origin_radius[a];
-        radius[a] = want > sc->origin_radius[a] ? 2.f * want : sc->origin_radius[a];
-    }
-    if (!grow) return 0;
-    DeviceGuard dev;
-    if (dev.enter(sc->device)) return 1;
-    emit_nodes(sc, sc->d_recs, sc->n_nodes, sc->d_nodes, radius, nullptr);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(sc->origin_radius, sc->d_radius, sizeof(float) * 3, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-// What emit_scene reads besides the vertices: the counts, the material table on the device, the lights on the host and --
-// for a new leaf order -- the caller's per-triangle indices on the device, in the caller's order (tri_light null: -1
-// everywhere).  The scene's own (rt_scene_update, rt_scene_rebuild) or those it is about to adopt (rt_scene_set_*).
-struct EmitSource {
-    int n_tris = 0, n_mats = 0, n_lights = 0;
-    const Material *d_mats = nullptr;
-    const rt_light *h_lights = nullptr;
-    const int *d_tri_material = nullptr, *d_tri_light = nullptr;
-    const float *radius = nullptr;  // the origin radius the 4-wide nodes are padded for at least (3 floats)
-};
-
-// The one writer of the scene's leaf-order arrays, ordered on `st`, from the caller's vertices on the device (d_verts) and
-// the leaf order out.order: the triangle records (k_leaf_tris), the shading records and tables, and -- 4-wide -- the nodes
-// from out.recs, padded for src.radius (emit_nodes).  For a new leaf order `d_inverse` (n ints of scratch) receives its
-// inverse, and the triangles' (material, light), from the two device arrays of `src`, and the lights, their triangles
-// renumbered, are written too.  Null for a refit: the leaf order is the scene's, and so are tri_info and the lights; the boxes of
-// the scene's records are refit to the vertices before they are padded (k_refit_level, one launch per level, deepest first;
-// launched after k_leaf_tris, which reads the same vertices: 5 us less per refit of the bunny than before it).
-int emit_scene(const rt_scene *sc, const EmitSource &src, const float *d_verts, const SceneArrays &out, int *d_inverse, hipStream_t st) {
-    const int n = src.n_tris, n_lights = src.n_lights;
-    const dim3 blk(256), grid((n + 255) / 256);
-    if (d_inverse && n > 0) {
-        hipLaunchKernelGGL(k_leaf_inverse, grid, blk, 0, st, out.order, n, d_inverse);
-        hipLaunchKernelGGL(k_leaf_tri_info, grid, blk, 0, st, src.d_tri_material, src.d_tri_light, out.order, n, out.info);
-    }
-    if (d_inverse && n_lights > 0) {
-        HIP_TRY(hipMemcpyAsync(out.lights, src.h_lights, sizeof(Light) * (size_t)n_lights, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_leaf_lights, dim3((n_lights + 255) / 256), blk, 0, st, out.lights, n_lights, d_inverse);
-    }
-    if (n > 0) {
-        hipLaunchKernelGGL(k_leaf_tris, grid, blk, 0, st, d_verts, out.order, n, out.tris);
-        hipLaunchKernelGGL(k_build_tri_shade, grid, blk, 0, st, out.tris, out.info, n, out.shade);
-    }
-    const int nt = std::max(std::max(src.n_mats, n_lights), 1);
-    hipLaunchKernelGGL(k_build_tables, dim3((nt + 63) / 64), dim3(64), 0, st, src.d_mats, src.n_mats, out.lights, n_lights, out.tris,
-                       out.tables);
-    if (!d_inverse)
-        for (size_t l = 0; l < sc->refit_level_end.size(); l++) {
-            const int begin = l ? sc->refit_level_end[l - 1] : 0, count = sc->refit_level_end[l] - begin;
-            hipLaunchKernelGGL(k_refit_level, dim3((count + 255) / 256), blk, 0, st, d_verts, sc->d_order, sc->d_refit_nodes + begin,
-                               count, sc->d_recs, sc->d_refit_exact);
-        }
-    if (sc->wide) emit_nodes(sc, out.recs, out.n_records, out.nodes, src.radius, st);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-// The scene's own source.  For a new leaf order (`with_indices`) its per-triangle indices go to the device first, staged on
-// `st` into `tmp` from the host copies: every caller of emit_scene hands it device arrays, there is one emit path.
-int scene_source(const rt_scene *sc, bool with_indices, hipStream_t st, DevScope &tmp, EmitSource &src) {
-    src.n_tris = sc->n_tris;
-    src.n_mats = sc->n_mats;
-    src.n_lights = sc->n_lights;
-    src.d_mats = sc->d_mats;
-    src.h_lights = sc->h_lights.data();
-    src.radius = sc->origin_radius;
-    if (!with_indices || sc->n_tris < 1) return 0;
-    const size_t n = (size_t)sc->n_tris;
-    int *d_m = nullptr, *d_l = nullptr;
-    if (tmp.alloc(d_m, n)) return 1;
-    HIP_TRY(hipMemcpyAsync(d_m, sc->h_tri_material.data(), sizeof(int) * n, hipMemcpyHostToDevice, st));
-    if (!sc->h_tri_light.empty()) {
-        if (tmp.alloc(d_l, n)) return 1;
-        HIP_TRY(hipMemcpyAsync(d_l, sc->h_tri_light.data(), sizeof(int) * n, hipMemcpyHostToDevice, st));
-    }
-    src.d_tri_material = d_m;
-    src.d_tri_light = d_l;
-    return 0;
-}
-
-// The start of rt_scene_update and rt_scene_rebuild: a device buffer of the caller's checked (on the scene's device), the
-// scene's device made current (until `dev` goes), and the vertices on it in d_verts -- the caller's buffer, or the host
-// array (null: the scene's own copy) staged on `st` into `tmp`.
-int stage_vertices(const rt_scene *sc, const float *verts, bool device_ptr, hipStream_t st, const std::string &w, DeviceGuard &dev,
-                   DevScope &tmp, const float *&d_verts) {
-    if (device_ptr && verts) {
-        hipPointerAttribute_t attr;
-        if (hipPointerGetAttributes(&attr, verts) != hipSuccess || (attr.type != hipMemoryTypeDevice && !attr.isManaged) ||
-            attr.device != sc->device) {
-            (void)hipGetLastError();  // (the failed query leaves its error behind)
-            return fail(w + ": d_tri_p0p1p2 is not device memory on the scene's device " + std::to_string(sc->device));
-        }
-    }
-    if (dev.enter(sc->device)) return 1;
-    d_verts = verts;
-    if (sc->n_tris > 0 && (!verts || !device_ptr)) {
-        float *d_v = nullptr;
-        if (tmp.alloc(d_v, 9 * (size_t)sc->n_tris)) return 1;
-        HIP_TRY(hipMemcpyAsync(d_v, verts ? verts : sc->h_tri9.data(), sizeof(float) * 9 * (size_t)sc->n_tris, hipMemcpyHostToDevice, st));
-        d_verts = d_v;
-    }
-    return 0;
-}
-
-// Surface-area cost of the 4-wide tree (the form of rtbvh::sah_cost): child box areas weighted by the triangles of a leaf
-// child or one node step, relative to the area of the root's bounds.  Advisory (rt_scene_refit_info).
-double quads_sah(const std::vector<rtbvh::Pair> &quads) {
-    auto half_area = [](const float *b) {
-        const double e0 = (double)b[3] - b[0], e1 = (double)b[4] - b[1], e2 = (double)b[5] - b[2];
-        return (e0 + e1) * e2 + e0 * e1;
-    };
-    double cost = 0.0, root[6] = {DBL_MAX, DBL_MAX, DBL_MAX, -DBL_MAX, -DBL_MAX, -DBL_MAX};
-    for (size_t r = 0; r < quads.size(); r++)
-        for (int side = 0; side < 2; side++) {
-            const int32_t l = side ? quads[r].rlink : quads[r].llink;
-            if (l == rtbvh::kNoChild) continue;
-            const float *b = side ? quads[r].rbox : quads[r].lbox;
-            cost += half_area(b) * (l < 0 ? (double)((~l) & 7) : 1.0);
-            if (r < 2)
-                for (int a = 0; a < 3; a++) {
-                    root[a] = std::min(root[a], (double)b[a]);
-                    root[3 + a] = std::max(root[3 + a], (double)b[3 + a]);
-                }
-        }
-    const double e0 = root[3] - root[0], e1 = root[4] - root[1], e2 = root[5] - root[2];
-    return quads.size() < 2 || !(e0 >= 0.0) ? 0.0 : cost / std::max((e0 + e1) * e2 + e0 * e1, 1e-30);
-}
-
-// rt_scene_update / rt_scene_update_device: refit the 4-wide tree on the scene's device (emit_scene), then
-// bring the host state along -- the builder records, the radius they are padded for, the triangle copy the reference's tree
-// and the replicas are made from.  `verts` is a host array or (device_ptr) a buffer on the scene's device.
-int scene_update_impl(rt_scene *sc, const float *verts, int n_tris, bool device_ptr, hipStream_t st, const char *what) {
-    const std::string w(what);
-    if (!sc || !verts) return fail(w + ": null argument");
-    if (n_tris != sc->n_tris) return fail(w + ": " + std::to_string(n_tris) + " triangles, the scene was created with " + std::to_string(sc->n_tris));
-    if (!sc->wide) return fail(w + ": the scene uses the 2-wide experiment format (RT_BVH_WIDE=0), which cannot be refit");
-    std::lock_guard<std::mutex> pad_lock(sc->pad_mutex);  // (the records, h_quads and origin_radius change)
-    DeviceGuard dev;
-    DevScope tmp;
-    const float *d_verts = nullptr;
-    if (stage_vertices(sc, verts, device_ptr, st, w, dev, tmp, d_verts)) return 1;
-    const int n = n_tris;
-    const int n_nodes = sc->n_nodes / 2;  // 4-wide nodes: two records each
-    if (n > 0 && !sc->d_refit_nodes) {
-        // the levels of the tree, fixed at creation: breadth-first from the root, then deepest level first
-        std::vector<int> depth((size_t)n_nodes, -1), queue{0};
-        depth[0] = 0;
-        for (size_t h = 0; h < queue.size(); h++)
-            for (int k = 0; k < 4; k++) {
-                const rtbvh::Pair &p = sc->h_quads[2 * (size_t)queue[h] + (k >> 1)];
-                const int32_t l = (k & 1) ? p.rlink : p.llink;
-                if (l >= 0) {
-                    depth[(size_t)l / 2] = depth[(size_t)queue[h]] + 1;
-                    queue.push_back(l / 2);
-                }
-            }
-        if ((int)queue.size() != n_nodes) return fail(w + ": the tree does not reach every node");
-        const int levels = depth[(size_t)queue.back()] + 1;
-        std::vector<int> nodes;
-        nodes.reserve((size_t)n_nodes);
-        std::vector<int> level_end;
-        for (int d = levels - 1; d >= 0; d--) {
-            for (int j : queue)
-                if (depth[(size_t)j] == d) nodes.push_back(j);
-            level_end.push_back((int)nodes.size());
-        }
-        int *dn = nullptr;
-        float *de = nullptr;
-        if (hipMalloc((void **)&dn, sizeof(int) * nodes.size()) != hipSuccess ||
-            hipMalloc((void **)&de, sizeof(float) * 6 * (size_t)n_nodes) != hipSuccess ||
-            hipMemcpy(dn, nodes.data(), sizeof(int) * nodes.size(), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(dn);
-            (void)hipFree(de);
-            return fail(w + ": device allocation or upload failed");
-        }
-        sc->d_refit_nodes = dn;
-        sc->d_refit_exact = de;
-        sc->refit_level_end = level_end;
-        sc->sah_build = sc->sah_now = quads_sah(sc->h_quads);
-    }
-    double seconds = 0.0;
-    if (n > 0) {
-        HIP_TRY(hipEventCreate(&tmp.e0));
-        HIP_TRY(hipEventCreate(&tmp.e1));
-        HIP_TRY(hipEventRecord(tmp.e0, st));
-        EmitSource src;
-        if (scene_source(sc, false, st, tmp, src)) return 1;
-        if (emit_scene(sc, src, d_verts, sc->arrays(), nullptr, st)) return 1;
-        HIP_TRY(hipEventRecord(tmp.e1, st));
-        HIP_TRY(hipEventSynchronize(tmp.e1));
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, tmp.e0, tmp.e1));
-        seconds = ms * 1e-3;
-        // the host's view of the new geometry: the unpadded records, the radius the device copy is padded for, the caller's
-        // triangles (the reference's tree and the replicas are made from them)
-        HIP_TRY(hipMemcpy(sc->h_quads.data(), sc->d_recs, sizeof(rtbvh::Pair) * sc->h_quads.size(), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(sc->origin_radius, sc->d_radius, sizeof(float) * 3, hipMemcpyDeviceToHost));
-        if (device_ptr) HIP_TRY(hipMemcpy(sc->h_tri9.data(), verts, sizeof(float) * 9 * (size_t)n, hipMemcpyDeviceToHost));
-        else memcpy(sc->h_tri9.data(), verts, sizeof(float) * 9 * (size_t)n);
-        sc->sah_now = quads_sah(sc->h_quads);
-    }
-    sc->refit_seconds = seconds;
-    sc->refits++;
-    sc->drop_ref_tree();
-    sc->drop_replicas();
-    return 0;
-}
-
-// Device PLOC build (k_ploc_*) of n >= 1 triangles from d_verts on the current device, ordered on `st`: the unpadded 4-wide
-// records (breadth-first) and the leaf order, on the device (owned here) and copied to the host.  The host reads the cluster
-// count back after every iteration and the node count after every level.  Fails -- with nothing to undo -- if the tree does
-// not fit the traversal stack.
-struct PlocBuild {
-    rtbvh::Pair *d_recs = nullptr;
-    int *d_order = nullptr;
-    std::vector<rtbvh::Pair> quads;
-    std::vector<int32_t> order;
-    int max_depth = 0, stack_bound = 1, leaves = 0, iterations = 0;
-    double seconds = 0.0;  // device time of the build (HIP events)
-    PlocBuild() = default;
-    PlocBuild(const PlocBuild &) = delete;
-    PlocBuild &operator=(const PlocBuild &) = delete;
-    ~PlocBuild() {
-        (void)hipFree(d_recs);
-        (void)hipFree(d_order);
-    }
-};
-int build_ploc_device(const float *d_verts, int n, hipStream_t st, PlocBuild &out, const std::string &w) {
-    if (n < 1) return fail(w + ": the device builder needs at least one triangle");
-    int n_pad = 1;
-    while (n_pad < n) n_pad <<= 1;
-    const size_t n_all = 2 * (size_t)n - 1, cap_nodes = std::max(n - 1, 1);  // binary nodes; 4-wide nodes at most
-    const int nb = (n + 255) / 256;
-    DevScope tmp;
-    unsigned long long *d_keys = nullptr;
-    unsigned *d_bits = nullptr;
-    float *d_box = nullptr, *d_cost = nullptr;
-    int2 *d_child = nullptr, *d_sums = nullptr, *d_lvl[2] = {nullptr, nullptr};
-    int *d_cnt = nullptr, *d_leaf = nullptr, *d_nn = nullptr, *d_tot = nullptr;
-    PlocCluster *d_cl[2] = {nullptr, nullptr};
-    if (tmp.alloc(d_keys, (size_t)n_pad) || tmp.alloc(d_bits, 6) || tmp.alloc(d_box, 6 * n_all) || tmp.alloc(d_cost, n_all) ||
-        tmp.alloc(d_child, n_all) || tmp.alloc(d_cnt, n_all) || tmp.alloc(d_leaf, n_all) || tmp.alloc(d_nn, (size_t)n) ||
-        tmp.alloc(d_sums, (size_t)nb) || tmp.alloc(d_tot, 4) || tmp.alloc(d_cl[0], (size_t)n) || tmp.alloc(d_cl[1], (size_t)n) ||
-        tmp.alloc(d_lvl[0], cap_nodes) || tmp.alloc(d_lvl[1], cap_nodes))
-        return 1;
-    HIP_TRY(hipMalloc((void **)&out.d_recs, sizeof(rtbvh::Pair) * 2 * cap_nodes));
-    HIP_TRY(hipMalloc((void **)&out.d_order, sizeof(int) * (size_t)n));
-    HIP_TRY(hipEventCreate(&tmp.e0));
-    HIP_TRY(hipEventCreate(&tmp.e1));
-    HIP_TRY(hipEventRecord(tmp.e0, st));
-    const dim3 blk(256);
-    // keys: centroid bounds, quantisation, sort
-    HIP_TRY(hipMemsetAsync(d_bits, 0xff, 3 * sizeof(unsigned), st));
-    HIP_TRY(hipMemsetAsync(d_bits + 3, 0, 3 * sizeof(unsigned), st));
-    hipLaunchKernelGGL(k_ploc_bounds, dim3(std::min(nb, 1024)), blk, 0, st, d_verts, n, d_bits);
-    unsigned bits[6];
-    HIP_TRY(hipMemcpyAsync(bits, d_bits, sizeof(bits), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    float lo[3], sc3[3];
-    for (int a = 0; a < 3; a++) {
-        lo[a] = rtploc::from_ordered_bits(bits[a]);
-        sc3[a] = rtploc::quant_scale(lo[a], rtploc::from_ordered_bits(bits[3 + a]));
-    }
-    hipLaunchKernelGGL(k_ploc_keys, dim3((n_pad + 255) / 256), blk, 0, st, d_verts, n, n_pad, lo[0], lo[1], lo[2], sc3[0], sc3[1],
-                       sc3[2], d_keys);
-    for (int k2 = 2; k2 <= n_pad; k2 <<= 1)
-        for (int j = k2 >> 1; j > 0; j >>= 1)
-            hipLaunchKernelGGL(k_bitonic_step, dim3((n_pad + 255) / 256), blk, 0, st, d_keys, n_pad, j, k2);
-    PlocNodes nd{d_box, d_child, d_cnt, d_cost, d_leaf, n};
-    hipLaunchKernelGGL(k_ploc_leaves, dim3(nb), blk, 0, st, d_verts, d_keys, n, nd, d_cl[0]);
-    HIP_TRY(hipGetLastError());
-    // clustering: until one cluster is left
-    const float trav = rtbvh::trav_cost();
-    const int max_leaf = rtbvh::max_leaf();
-    int m = n, inner = 0, cur = 0;
-    while (m > 1) {
-        if (++out.iterations > rtploc::kMaxIterations) return fail(w + ": the clustering does not converge");
-        const int mb = (m + 255) / 256;
-        hipLaunchKernelGGL(k_ploc_nearest, dim3(mb), blk, 0, st, d_cl[cur], m, out.iterations > rtploc::kTieIterations ? 1 : 0, d_nn);
-        hipLaunchKernelGGL(k_ploc_count, dim3(mb), blk, 0, st, d_nn, m, d_sums);
-        hipLaunchKernelGGL(k_ploc_scan, dim3(1), dim3(1024), 0, st, d_sums, mb, d_tot);
-        hipLaunchKernelGGL(k_ploc_merge, dim3(mb), blk, 0, st, d_cl[cur], d_nn, m, d_sums, inner, trav, max_leaf, nd, d_cl[cur ^ 1]);
-        HIP_TRY(hipGetLastError());
-        int tot[2];
-        HIP_TRY(hipMemcpyAsync(tot, d_tot, sizeof(tot), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (tot[1] < 1 || tot[0] != m - tot[1] || inner + tot[1] > n - 1)
-            return fail(w + ": the clustering made no progress (non-finite vertices?)");
-        m = tot[0];
-        inner += tot[1];
-        cur ^= 1;
-    }
-    // collapse to 4-wide, one level per step, breadth first from the root (node 2n - 2, or the one triangle)
-    const int2 root = make_int2(n > 1 ? (int)n_all - 1 : 0, 0);
-    HIP_TRY(hipMemcpyAsync(d_lvl[0], &root, sizeof(int2), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(d_tot + 2, 0, sizeof(int), st));
-    int count = 1, base = 0, lv = 0;
-    while (count > 0) {
-        out.max_depth++;
-        if (3 * out.max_depth + 1 > kMaxStackBound)
-            return fail(w + ": the device-built tree is deeper than the traversal stack allows (" + std::to_string(out.max_depth) + " levels)");
-        const int cb = (count + 255) / 256;
-        hipLaunchKernelGGL(k_ploc_level_count, dim3(cb), blk, 0, st, d_lvl[lv], count, nd, d_sums);
-        hipLaunchKernelGGL(k_ploc_scan, dim3(1), dim3(1024), 0, st, d_sums, cb, d_tot);
-        int tot[2];
-        HIP_TRY(hipMemcpyAsync(tot, d_tot, sizeof(tot), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        const int next_base = base + count;
-        if (tot[0] < 0 || (size_t)next_base + (size_t)tot[0] > cap_nodes) return fail(w + ": the 4-wide collapse overran its node count");
-        hipLaunchKernelGGL(k_ploc_level_emit, dim3(cb), blk, 0, st, d_lvl[lv], count, base, next_base, d_sums, nd, out.d_recs,
-                           d_lvl[lv ^ 1], out.d_order, d_tot + 2);
-        HIP_TRY(hipGetLastError());
-        base = next_base;
-        count = tot[0];
-        lv ^= 1;
-    }
-    HIP_TRY(hipEventRecord(tmp.e1, st));
-    HIP_TRY(hipEventSynchronize(tmp.e1));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, tmp.e0, tmp.e1));
-    out.seconds = ms * 1e-3;
-    int err = 0;
-    HIP_TRY(hipMemcpy(&err, d_tot + 2, sizeof(int), hipMemcpyDeviceToHost));
-    if (err) return fail(w + ": the device-built tree has a leaf that cannot be referenced");
-    out.quads.resize(2 * (size_t)base);
-    out.order.resize((size_t)n);
-    HIP_TRY(hipMemcpy(out.quads.data(), out.d_recs, sizeof(rtbvh::Pair) * out.quads.size(), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out.order.data(), out.d_order, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
-    out.stack_bound = 3 * out.max_depth + 1;
-    out.leaves = 0;
-    for (const rtbvh::Pair &p : out.quads) out.leaves += (p.llink < 0 && p.llink != rtbvh::kNoChild) + (p.rlink < 0 && p.rlink != rtbvh::kNoChild);
-    return 0;
-}
-// What the scene may adopt from a build: a well-formed tree over a permutation of its triangles, within the stack
-bool ploc_result_ok(const PlocBuild &b, int n) {
-    if (b.stack_bound > kMaxStackBound || !validate_quads(b.quads, n) || (int)b.order.size() != n) return false;
-    std::vector<char> seen((size_t)n, 0);
-    for (int32_t i : b.order) {
-        if (i < 0 || i >= n || seen[(size_t)i]) return false;
-        seen[(size_t)i] = 1;
-    }
-    return true;
-}
-
-// The scene takes a device build's tree: the records and the leaf order on the device (b frees the scene's old ones) and
-// their host copies
-void adopt_tree(rt_scene *sc, PlocBuild &b) {
-    std::swap(sc->d_recs, b.d_recs);
-    std::swap(sc->d_order, b.d_order);
-    sc->h_quads = std::move(b.quads);
-    sc->set_order(b.order);
-    sc->drop_query_inverse();
-    sc->n_nodes = (int)sc->h_quads.size();
-    sc->max_depth = b.max_depth;
-    sc->stack_bound = b.stack_bound;
-    sc->n_leaves = b.leaves;
-    sc->builder = 2;
-    sc->build_seconds = b.seconds;
-}
-
-// rt_scene_rebuild / rt_scene_rebuild_device: a new tree for the scene's current or new vertices (build_ploc_device), and
-// everything the kernels index in leaf order re-emitted on the device from the new order (emit_scene), into new buffers that
-// replace the scene's only once the tree has passed its checks.  `verts`: null (the scene's own vertices), a host array or
-// (device_ptr) a buffer on the scene's device.
-int scene_rebuild_impl(rt_scene *sc, const float *verts, int n_tris, bool device_ptr, hipStream_t st, const char *what) {
-    const std::string w(what);
-    if (!sc) return fail(w + ": null scene");
-    if (n_tris != sc->n_tris) return fail(w + ": " + std::to_string(n_tris) + " triangles, the scene was created with " + std::to_string(sc->n_tris));
-    if (!sc->wide) return fail(w + ": the scene uses the 2-wide experiment format (RT_BVH_WIDE=0), which the device builder does not write");
-    if (n_tris < 1) return fail(w + ": the scene has no triangles");
-    std::lock_guard<std::mutex> pad_lock(sc->pad_mutex);  // (the records, h_quads and origin_radius change)
-    DeviceGuard dev;
-    DevScope tmp;
-    const float *d_verts = nullptr;
-    if (stage_vertices(sc, verts, device_ptr, st, w, dev, tmp, d_verts)) return 1;
-    const int n = n_tris;
-    std::vector<float> h_new;
-    if (verts) {
-        h_new.resize(9 * (size_t)n);
-        if (device_ptr) {
-            HIP_TRY(hipMemcpyAsync(h_new.data(), verts, sizeof(float) * h_new.size(), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-        } else {
-            memcpy(h_new.data(), verts, sizeof(float) * h_new.size());
-        }
-    }
-    const bool moved = verts && memcmp(h_new.data(), sc->h_tri9.data(), sizeof(float) * h_new.size()) != 0;
-    PlocBuild b;
-    if (build_ploc_device(d_verts, n, st, b, w)) return 1;
-    if (!ploc_result_ok(b, n)) return fail(w + ": the device-built tree is malformed; the scene is unchanged");
-    // the scene's leaf-order arrays for the new tree, into new buffers
-    SceneArrays a{b.d_order, b.d_recs, (int)b.quads.size()};
-    int *d_inverse = nullptr, *d_ref_prims = nullptr, *d_ref_leaf_of = nullptr;
-    DevScope fresh;  // (released unless adopted below)
-    const bool keep_ref = sc->ref_ready && !moved;
-    if (fresh.alloc(a.nodes, 4 * (size_t)a.n_records) || fresh.alloc(a.tris, 3 * (size_t)n) || fresh.alloc(a.shade, (size_t)n) ||
-        fresh.alloc(a.info, (size_t)n) || fresh.alloc(a.lights, (size_t)std::max(sc->n_lights, 1)) ||
-        fresh.alloc(a.tables, (size_t)std::max(sc->tab_dwords, 1)) || tmp.alloc(d_inverse, (size_t)n) ||
-        (keep_ref && (fresh.alloc(d_ref_prims, (size_t)n) || fresh.alloc(d_ref_leaf_of, (size_t)n))))
-        return 1;
-    EmitSource src;
-    if (scene_source(sc, true, st, tmp, src)) return 1;
-    if (emit_scene(sc, src, d_verts, a, d_inverse, st)) return 1;
-    if (keep_ref)
-        hipLaunchKernelGGL(k_ploc_remap_ref, dim3((n + 255) / 256), dim3(256), 0, st, sc->d_ref_prims, sc->d_ref_leaf_of, sc->d_order,
-                           d_inverse, n, d_ref_prims, d_ref_leaf_of);
-    HIP_TRY(hipGetLastError());
-    float radius[3];
-    HIP_TRY(hipMemcpyAsync(radius, sc->d_radius, sizeof(radius), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    // adopt: the new buffers replace the old ones, the host state follows
-    fresh.ptrs.clear();
-    std::swap(sc->d_nodes, a.nodes);
-    std::swap(sc->d_tris, a.tris);
-    std::swap(sc->d_tri_shade, a.shade);
-    std::swap(sc->d_tri_info, a.info);
-    std::swap(sc->d_lights, a.lights);
-    std::swap(sc->d_tables, a.tables);
-    for (void *q : {(void *)a.nodes, (void *)a.tris, (void *)a.shade, (void *)a.info, (void *)a.lights, (void *)a.tables}) (void)hipFree(q);
-    adopt_tree(sc, b);
-    for (int k = 0; k < 3; k++) sc->origin_radius[k] = radius[k];
-    sc->drop_refit();
-    sc->sah_build = sc->sah_now = quads_sah(sc->h_quads);
-    // the reference's tree is a function of the triangles: kept (renumbered for the new leaf order) unless they moved
-    if (keep_ref) {
-        std::lock_guard<std::mutex> lock(sc->ref_mutex);
-        std::swap(sc->d_ref_prims, d_ref_prims);
-        std::swap(sc->d_ref_leaf_of, d_ref_leaf_of);
-        (void)hipFree(d_ref_prims);
-        (void)hipFree(d_ref_leaf_of);
-    } else if (moved) {
-        sc->drop_ref_tree();
-    }
-    if (moved) sc->h_tri9 = h_new;
-    sc->drop_replicas();
-    return 0;
-}
-
-// ---- editing a scene in place: rt_scene_set_materials, rt_scene_set_lights, rt_scene_set_triangles*, rt_scene_create_device
-// Every one builds what changes into fresh buffers, waits for the device, and only then adopts them: an error on the way
-// leaves the scene rendering its old bits.
-
-// Is `p` device memory on `device` (as stage_vertices asks of the vertices)?  A host pointer is an error, not a fault.
-bool on_device(const void *p, int device) {
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, p) != hipSuccess || (attr.type != hipMemoryTypeDevice && !attr.isManaged) || attr.device != device) {
-        (void)hipGetLastError();  // (the failed query leaves its error behind)
-        return false;
-    }
-    return true;
-}
-
-// A new material table.  Nothing in leaf order depends on it: the table on the device and the shading tables are re-made
-// (k_build_tables, for the new count), the tree, the records, the refit state and the reference's tree stay.
-int scene_set_materials_impl(rt_scene *sc, const rt_material *materials, int n_materials) {
-    const std::string w("rt_scene_set_materials");
-    if (!sc) return fail(w + ": null scene");
-    if (!materials) return fail(w + ": null materials");
-    if (check_scene_counts(w, sc->n_tris, true, materials, n_materials, sc->h_lights.data(), sc->n_lights) ||
-        check_scene_tables(w, sc->n_tris, materials, n_materials, nullptr, 0))
-        return 1;
-    if (sc->max_tri_material >= n_materials)
-        return fail(w + ": the triangles name materials up to " + std::to_string(sc->max_tri_material) + ", the new table has " + std::to_string(n_materials));
-    std::lock_guard<std::mutex> pad_lock(sc->pad_mutex);
-    DeviceGuard dev;
-    if (dev.enter(sc->device)) return 1;
-    DevScope fresh;  // (released unless adopted below)
-    Material *d_mats = nullptr;
-    float *d_tables = nullptr;
-    const int tab_dwords = 5 * n_materials + 24 * sc->n_lights;
-    if (fresh.alloc(d_mats, (size_t)n_materials) || fresh.alloc(d_tables, (size_t)tab_dwords)) return 1;
-    if (n_materials) HIP_TRY(hipMemcpy(d_mats, materials, sizeof(Material) * (size_t)n_materials, hipMemcpyHostToDevice));
-    const int nt = std::max(std::max(n_materials, sc->n_lights), 1);
-    hipLaunchKernelGGL(k_build_tables, dim3((nt + 63) / 64), dim3(64), 0, nullptr, d_mats, n_materials, sc->d_lights, sc->n_lights,
-                       sc->d_tris, d_tables);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    fresh.ptrs.clear();
-    std::swap(sc->d_mats, d_mats);
-    std::swap(sc->d_tables, d_tables);
-    (void)hipFree(d_mats);
-    (void)hipFree(d_tables);
-    sc->n_mats = n_materials;
-    sc->tab_dwords = tab_dwords;
-    sc->h_materials.assign(materials, materials + n_materials);
-    sc->drop_replicas();
-    return 0;
-}
-
-// New lights and, with `tri_light`, a new light assignment of the triangles.  The lights' triangles are renumbered to leaf
-// order from the host's inverse order (what k_leaf_lights does after a build); a new assignment re-emits tri_info and the
-// shading records (k_leaf_tri_light, k_build_tri_shade).  The tree, the triangle records and the reference's tree stay.
-int scene_set_lights_impl(rt_scene *sc, const rt_light *lights, int n_lights, const int32_t *tri_light) {
-    const std::string w("rt_scene_set_lights");
-    if (!sc) return fail(w + ": null scene");
-    if (check_scene_counts(w, sc->n_tris, true, sc->h_materials.data(), sc->n_mats, lights, n_lights) ||
-        check_tri_indices(w, sc->n_tris, nullptr, tri_light, sc->n_mats, n_lights) ||
-        check_scene_tables(w, sc->n_tris, nullptr, 0, lights, n_lights))
-        return 1;
-    if (!tri_light && sc->max_tri_light >= n_lights)
-        return fail(w + ": the kept assignment names lights up to " + std::to_string(sc->max_tri_light) + ", the new table has " + std::to_string(n_lights));
-    std::lock_guard<std::mutex> pad_lock(sc->pad_mutex);
-    DeviceGuard dev;
-    if (dev.enter(sc->device)) return 1;
-    const int n = sc->n_tris;
-    std::vector<rt_light> leaf_lights(lights, lights + n_lights);
-    for (rt_light &l : leaf_lights)
-        if (l.type == RT_AREA_LIGHT) l.triangle = sc->h_inverse[(size_t)l.triangle];
-    DevScope fresh, tmp;  // (fresh: released unless adopted below)
-    Light *d_lights = nullptr;
-    float *d_tables = nullptr;
-    int2 *d_info = nullptr;
-    float4 *d_shade = nullptr;
-    const int tab_dwords = 5 * sc->n_mats + 24 * n_lights;
-    if (fresh.alloc(d_lights, (size_t)n_lights) || fresh.alloc(d_tables, (size_t)tab_dwords)) return 1;
-    if (n_lights) HIP_TRY(hipMemcpy(d_lights, leaf_lights.data(), sizeof(Light) * (size_t)n_lights, hipMemcpyHostToDevice));
-    const bool assign = tri_light && n > 0;
-    if (assign) {
-        int *d_tl = nullptr;
-        if (fresh.alloc(d_info, (size_t)n) || fresh.alloc(d_shade, (size_t)n) || tmp.alloc(d_tl, (size_t)n)) return 1;
-        HIP_TRY(hipMemcpy(d_tl, tri_light, sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
-        const dim3 blk(256), grid((n + 255) / 256);
-        hipLaunchKernelGGL(k_leaf_tri_light, grid, blk, 0, nullptr, sc->d_tri_info, d_tl, sc->d_order, n, d_info);
-        hipLaunchKernelGGL(k_build_tri_shade, grid, blk, 0, nullptr, sc->d_tris, d_info, n, d_shade);
-    }
-    const int nt = std::max(std::max(sc->n_mats, n_lights), 1);
-    hipLaunchKernelGGL(k_build_tables, dim3((nt + 63) / 64), dim3(64), 0, nullptr, sc->d_mats, sc->n_mats, d_lights, n_lights, sc->d_tris,
-                       d_tables);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    fresh.ptrs.clear();
-    std::swap(sc->d_lights, d_lights);
-    std::swap(sc->d_tables, d_tables);
-    (void)hipFree(d_lights);
-    (void)hipFree(d_tables);
-    if (assign) {
-        std::swap(sc->d_tri_info, d_info);
-        std::swap(sc->d_tri_shade, d_shade);
-        (void)hipFree(d_info);
-        (void)hipFree(d_shade);
-    }
-    sc->n_lights = n_lights;
-    sc->tab_dwords = tab_dwords;
-    sc->h_lights.assign(lights, lights + n_lights);
-    if (tri_light) {
-        sc->h_tri_light.assign(tri_light, tri_light + n);
-        sc->note_index_maxima();
-    }
-    sc->drop_replicas();
-    return 0;
-}
-
-// A new triangle set for the scene (or the first one of a scene just made: rt_scene_create_device): any count >= 1, with
-// its per-triangle indices and the tables they index.  The three per-triangle arrays are host arrays, uploaded first, or
-// (device_ptr) buffers on the scene's device, whose index ranges are then checked there (k_index_prepass); from then on
-// there is one path: the device build, every record emitted into buffers of the new size, the host mirrors, the adoption.
-int scene_set_triangles_impl(rt_scene *sc, const float *verts, int n_tris, const int32_t *tri_material, const int32_t *tri_light,
-                             const rt_material *materials, int n_materials, const rt_light *lights, int n_lights, bool device_ptr,
-                             hipStream_t st, const char *what) {
-    const std::string w(what);
-    if (!sc) return fail(w + ": null scene");
-    if (check_scene_counts(w, n_tris, verts && tri_material, materials, n_materials, lights, n_lights)) return 1;
-    if (n_tris < 1) return fail(w + ": the device builder needs at least one triangle (an empty scene is made by rt_scene_create)");
-    if (!sc->wide) return fail(w + ": the scene uses the 2-wide experiment format (RT_BVH_WIDE=0), which the device builder does not write");
-    if (!device_ptr && check_tri_indices(w, n_tris, tri_material, tri_light, n_materials, n_lights)) return 1;
-    if (check_scene_tables(w, n_tris, materials, n_materials, lights, n_lights)) return 1;
-    if (device_ptr) {
-        const std::string where = " is not device memory on the scene's device " + std::to_string(sc->device);
-        if (!on_device(verts, sc->device)) return fail(w + ": d_tri_p0p1p2" + where);
-        if (!on_device(tri_material, sc->device)) return fail(w + ": d_tri_material" + where);
-        if (tri_light && !on_device(tri_light, sc->device)) return fail(w + ": d_tri_light" + where);
-    }
-    std::lock_guard<std::mutex> pad_lock(sc->pad_mutex);  // (the records, h_quads and origin_radius change)
-    DeviceGuard dev;
-    if (dev.enter(sc->device)) return 1;
-    DevScope tmp;
-    const size_t n = (size_t)n_tris;
-    const float *d_verts = verts;
-    const int *d_m = tri_material, *d_l = tri_light;
-    std::vector<float> h_tri9(9 * n);
-    std::vector<int32_t> h_mat(n), h_light(tri_light ? n : 0);
-    if (!device_ptr) {
-        float *uv = nullptr;
-        int *um = nullptr, *ul = nullptr;
-        if (tmp.alloc(uv, 9 * n) || tmp.alloc(um, n) || (tri_light && tmp.alloc(ul, n))) return 1;
-        HIP_TRY(hipMemcpyAsync(uv, verts, sizeof(float) * 9 * n, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(um, tri_material, sizeof(int) * n, hipMemcpyHostToDevice, st));
-        if (tri_light) HIP_TRY(hipMemcpyAsync(ul, tri_light, sizeof(int) * n, hipMemcpyHostToDevice, st));
-        d_verts = uv;
-        d_m = um;
-        d_l = ul;
-        memcpy(h_tri9.data(), verts, sizeof(float) * 9 * n);
-        memcpy(h_mat.data(), tri_material, sizeof(int32_t) * n);
-        if (tri_light) memcpy(h_light.data(), tri_light, sizeof(int32_t) * n);
-        HIP_TRY(hipStreamSynchronize(st));  // (the caller's arrays are his again on return whatever happens below)
-    } else {
-        unsigned *d_words = nullptr, words[2] = {0, 0};
-        if (tmp.alloc(d_words, 2)) return 1;
-        HIP_TRY(hipMemsetAsync(d_words, 0, sizeof(words), st));
-        hipLaunchKernelGGL(k_index_prepass, dim3((unsigned)std::min<size_t>((n + kBlock - 1) / kBlock, 1024)), dim3(kBlock), 0, st, d_m, d_l,
-                           n_tris, n_materials, n_lights, d_words);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(words, d_words, sizeof(words), hipMemcpyDeviceToHost, st));
-        // the host mirrors: what the reference's tree and rt_render_multi replicas are made from, one copy per array
-        HIP_TRY(hipMemcpyAsync(h_tri9.data(), verts, sizeof(float) * 9 * n, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(h_mat.data(), tri_material, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
-        if (tri_light) HIP_TRY(hipMemcpyAsync(h_light.data(), tri_light, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (words[0] || words[1])
-            return fail(w + ": " + std::to_string(words[0]) + " of " + std::to_string(n_tris) + " triangles have d_tri_material out of range and " +
-                        std::to_string(words[1]) + " have d_tri_light out of range");
-    }
-    PlocBuild b;
-    if (build_ploc_device(d_verts, n_tris, st, b, w)) return 1;
-    if (!ploc_result_ok(b, n_tris)) return fail(w + ": the device-built tree is malformed; the scene is unchanged");
-    SceneArrays a{b.d_order, b.d_recs, (int)b.quads.size()};
-    Material *d_mats = nullptr;
-    int *d_inverse = nullptr;
-    DevScope fresh;  // (released unless adopted below)
-    const int tab_dwords = 5 * n_materials + 24 * n_lights;
-    if (fresh.alloc(a.nodes, 4 * (size_t)a.n_records) || fresh.alloc(a.tris, 3 * n) || fresh.alloc(a.shade, n) || fresh.alloc(a.info, n) ||
-        fresh.alloc(a.lights, (size_t)n_lights) || fresh.alloc(a.tables, (size_t)tab_dwords) || fresh.alloc(d_mats, (size_t)n_materials) ||
-        tmp.alloc(d_inverse, n))
-        return 1;
-    if (!sc->d_radius) HIP_TRY(hipMalloc((void **)&sc->d_radius, sizeof(float) * 3));  // (scratch of emit_nodes: a scene just made)
-    HIP_TRY(hipMemcpyAsync(d_mats, materials, sizeof(Material) * (size_t)n_materials, hipMemcpyHostToDevice, st));
-    const float none[3] = {0.f, 0.f, 0.f};  // the new tree's own radius, as at creation: the old triangles' says nothing
-    EmitSource src;
-    src.n_tris = n_tris;
-    src.n_mats = n_materials;
-    src.n_lights = n_lights;
-    src.d_mats = d_mats;
-    src.h_lights = lights;
-    src.d_tri_material = d_m;
-    src.d_tri_light = d_l;
-    src.radius = none;
-    if (emit_scene(sc, src, d_verts, a, d_inverse, st)) return 1;
-    float radius[3];
-    HIP_TRY(hipMemcpyAsync(radius, sc->d_radius, sizeof(radius), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    // adopt: the new buffers replace the old ones, the host state follows
-    fresh.ptrs.clear();
-    std::swap(sc->d_nodes, a.nodes);
-    std::swap(sc->d_tris, a.tris);
-    std::swap(sc->d_tri_shade, a.shade);
-    std::swap(sc->d_tri_info, a.info);
-    std::swap(sc->d_lights, a.lights);
-    std::swap(sc->d_tables, a.tables);
-    std::swap(sc->d_mats, d_mats);
-    for (void *q : {(void *)a.nodes, (void *)a.tris, (void *)a.shade, (void *)a.info, (void *)a.lights, (void *)a.tables, (void *)d_mats})
-        (void)hipFree(q);
-    adopt_tree(sc, b);
-    sc->n_tris = n_tris;
-    sc->n_mats = n_materials;
-    sc->n_lights = n_lights;
-    sc->tab_dwords = tab_dwords;
-    for (int k = 0; k < 3; k++) sc->origin_radius[k] = radius[k];
-    sc->drop_refit();
-    sc->sah_build = sc->sah_now = quads_sah(sc->h_quads);
-    sc->drop_ref_tree();
-    sc->h_tri9 = std::move(h_tri9);
-    sc->h_tri_material = std::move(h_mat);
-    sc->h_tri_light = std::move(h_light);
-    sc->h_materials.assign(materials, materials + n_materials);
-    sc->h_lights.assign(lights, lights + n_lights);
-    sc->note_index_maxima();
-    sc->drop_replicas();
-    return 0;
-}
-
-// ---- per-device render context: pools are allocated once per (device, n) and reused
-struct Context {
-    int device = -1;
-    int n = 0;
-    int lane = 0;  // concurrent sub-shards of one render use separate contexts (and streams)
-    DPools pools{};
-    std::vector<void *> allocs;
-    DCounters *d_ctr = nullptr;
-    DCounters *h_ctr = nullptr;  // pinned ring of snapshots
-    DWaveRow *d_rows = nullptr;  // one row per wave of the stage grid
-    int n_rows = 0;
-    uint32_t *d_jump = nullptr;
-    hipEvent_t ev_ring[4] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t ev_a = nullptr, ev_b = nullptr, ev_c = nullptr;
-    // RNG states are a pure function of (seed, slot range): keep them cached across renders
-    uint64_t rng_seed = 0;
-    int rng_lo = -1;
-    bool rng_valid = false;
-    uint32_t *rng_backup = nullptr;  // 6 x n words
-    std::vector<hipEvent_t> timing_events;
-    unsigned int *d_lock = nullptr;  // mat() events per lockstep round of the final generation (lock_cap words, grown on demand)
-    int lock_cap = 0;
-    int *d_over = nullptr;  // overflow part of the traversal stacks of this context's grids (ensure_overflow)
-    int over_levels = 0;
-    std::mutex busy;  // a context (pools, counters, events) serves one render at a time
-    Context() = default;
-    Context(const Context &) = delete;
-    Context &operator=(const Context &) = delete;
-    ~Context() {  // (rt_shutdown, or a context that failed half-way through get_context): on the device it lives on
-        int saved = 0;
-        const bool hop = device >= 0 && hipGetDevice(&saved) == hipSuccess && saved != device && hipSetDevice(device) == hipSuccess;
-        for (void *q : allocs) (void)hipFree(q);
-        (void)hipFree(d_lock);
-        (void)hipFree(d_over);
-        if (h_ctr) (void)hipHostFree(h_ctr);
-        for (hipEvent_t e : ev_ring) if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : {ev_a, ev_b, ev_c}) if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : timing_events) (void)hipEventDestroy(e);
-        if (hop) (void)hipSetDevice(saved);
-    }
-};
-std::mutex g_ctx_mutex;
-std::vector<std::unique_ptr<Context>> g_contexts;
-
-// Device buffers of the calls that take HOST output (rt_render, rt_render_multi): raw sums, staging, the post-processed image.
-// Kept per (device, slot) and reused from call to call -- a hipMalloc / hipFree pair per frame cost ~0.3 ms and a device
-// synchronisation each (round 4 allocated them per call); released by rt_shutdown.  The buffers of ONE device serve one call at
-// a time (g_dev_busy[device]); calls on different devices -- one host thread per GPU -- do not wait for each other.
-struct OutBuffer {
-    int device = -1, slot = 0;
-    void *ptr = nullptr;
-    size_t bytes = 0;
-};
-constexpr int kMaxDevices = 64;
-std::mutex g_dev_busy[kMaxDevices];
-std::mutex g_out_mutex;  // the list below
-std::vector<OutBuffer> g_out_buffers;
-// (caller holds g_dev_busy[device]; the current device must be `device`)
-void *out_buffer(int device, int slot, size_t bytes) {
-    std::lock_guard<std::mutex> list_lock(g_out_mutex);
-    for (OutBuffer &b : g_out_buffers)
-        if (b.device == device && b.slot == slot) {
-            if (b.bytes >= bytes) return b.ptr;
-            (void)hipFree(b.ptr);
-            b.ptr = nullptr;
-            b.bytes = 0;
-            if (hipMalloc(&b.ptr, bytes) != hipSuccess) return nullptr;
-            b.bytes = bytes;
-            return b.ptr;
-        }
-    OutBuffer b;
-    b.device = device;
-    b.slot = slot;
-    if (hipMalloc(&b.ptr, bytes) != hipSuccess) return nullptr;
-    b.bytes = bytes;
-    g_out_buffers.push_back(b);
-    return b.ptr;
-}
-
-template <typename T>
-int dev_alloc(Context &c, T *&ptr, size_t count) {
-    void *raw = nullptr;
-    HIP_TRY(hipMalloc(&raw, count * sizeof(T)));
-    c.allocs.push_back(raw);
-    ptr = (T *)raw;
-    return 0;
-}
-
-int get_context(int n, int lane, Context **out) {
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(g_ctx_mutex);
-    for (auto &c : g_contexts)
-        if (c->device == dev && c->n == n && c->lane == lane) {
-            *out = c.get();
-            return 0;
-        }
-    auto c = std::make_unique<Context>();
-    c->device = dev;
-    c->n = n;
-    c->lane = lane;
-    DPools &p = c->pools;
-    p.n = n;
-    if (dev_alloc(*c, p.base, (size_t)A_COUNT * n)) return 1;
-    if (dev_alloc(*c, c->rng_backup, (size_t)6 * n)) return 1;
-    if (dev_alloc(*c, c->d_ctr, 1)) return 1;
-    // one counter row per wave of the largest grid this context launches: k_advance's (n / 64 waves)
-    c->n_rows = ((n + kBlock - 1) / kBlock) * (kBlock / 64);
-    if (dev_alloc(*c, c->d_rows, (size_t)c->n_rows)) return 1;
-    if (dev_alloc(*c, c->d_jump, (size_t)20 * 800)) return 1;
-    HIP_TRY(hipMemcpy(c->d_jump, jump_powers().data(), sizeof(uint32_t) * 20 * 800, hipMemcpyHostToDevice));
-    HIP_TRY(hipHostMalloc((void **)&c->h_ctr, sizeof(DCounters) * 4, hipHostMallocDefault));
-    for (auto &e : c->ev_ring) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipEventCreate(&c->ev_a));
-    HIP_TRY(hipEventCreate(&c->ev_b));
-    HIP_TRY(hipEventCreate(&c->ev_c));
-    *out = c.get();
-    g_contexts.push_back(std::move(c));
-    return 0;
-}
-
-int grid_for(int n) { return (n + kBlock - 1) / kBlock; }
-
-// Entries of a lane's traversal stack kept in LDS (the rest of scene->stack_bound goes to the global overflow column).
-// RT_STACK_CAP lowers it: a test knob that drives every traversal through the overflow path.
-static int lds_stack_cap(const rt_scene *scene, int limit) {
-    int cap = std::min(limit, std::max(1, scene->stack_bound));
-    if (const char *e = knob("RT_STACK_CAP")) cap = std::max(1, std::min(cap, atoi(e)));
-    return cap;
-}
-
-// Kernel selection: every build of one kernel template has the same signature, so the flags pick a function pointer and
-// the caller launches (and sizes the grid with) that pointer.
-using AdvanceKernel = decltype(&k_advance<false>);
-using TraceKernel = decltype(&k_trace<MODE_POOL, false>);
-using PathsKernel = decltype(&k_paths<false, false, 4, false, false, false>);
-
-static AdvanceKernel advance_kernel(bool lds_tables) { return lds_tables ? k_advance<true> : k_advance<false>; }
-
-// k_trace<MODE>: with RT_FLAG_REFERENCE_WALK the build that walks the reference's tree (the node format does not matter
-// then); `verify`: the default build -- the product's walk with the reference's decisions (ref_visible); neither:
-// RT_FLAG_WATERTIGHT.  Otherwise the node format is a property of the scene.
-template <int MODE>
-static TraceKernel trace_kernel(bool literal, bool verify, bool wide) {
-    if (literal) return k_trace<MODE, false, 8, true>;
-    if (verify) return wide ? k_trace<MODE, true, 8, false, true> : k_trace<MODE, false, 8, false, true>;
-    return wide ? k_trace<MODE, true> : k_trace<MODE, false>;
-}
-
-// k_paths: MIN_WAVES = 4 waves per SIMD (at most 128 VGPRs) when the grid fills the chip, 2 (up to 256 VGPRs) when the
-// shard is so small that only 2 workgroups per CU exist anyway (8-GPU runs).  RT_FLAG_REFERENCE_WALK: the build whose node
-// block is the reference's own walk (full pool: the 4-wave build although it spills 53 VGPRs -- measured 1 082 ms for C2's
-// frame against 1 412 ms for the spill-free 2-wave build at half the occupancy).  Per-sample streams on the full pool: the
-// build in which the waves draw their camera rays from the frame's counter.
-template <bool LDS_TABLES, bool WIDE>
-static PathsKernel paths_kernel_of(bool few_blocks, bool per_sample, bool literal, bool verify) {
-    if (literal) return few_blocks ? k_paths<LDS_TABLES, false, 2, false, true, false> : k_paths<LDS_TABLES, false, 4, false, true, false>;
-    if (per_sample && !few_blocks) return k_paths<LDS_TABLES, WIDE, 4, true, false, false>;
-    if (few_blocks) return verify ? k_paths<LDS_TABLES, WIDE, 2, false, false, true> : k_paths<LDS_TABLES, WIDE, 2, false, false, false>;
-    return verify ? k_paths<LDS_TABLES, WIDE, 4, false, false, true> : k_paths<LDS_TABLES, WIDE, 4, false, false, false>;
-}
-static PathsKernel paths_kernel(bool lds_tables, bool wide, bool few_blocks, bool per_sample, bool literal, bool verify) {
-    if (lds_tables) return (wide ? paths_kernel_of<true, true> : paths_kernel_of<true, false>)(few_blocks, per_sample, literal, verify);
-    return (wide ? paths_kernel_of<false, true> : paths_kernel_of<false, false>)(few_blocks, per_sample, literal, verify);
-}
-
-// Ray-table frames: k_advance_rays / k_paths_rays (4-wide tree only; a 2-wide scene runs such a frame on the round pipeline).
-using AdvanceRaysKernel = decltype(&k_advance_rays<false>);
-using PathsRaysKernel = decltype(&k_paths_rays<false, true, 4, false, false, false>);
-static AdvanceRaysKernel advance_rays_kernel(bool lds_tables) { return lds_tables ? k_advance_rays<true> : k_advance_rays<false>; }
-template <bool LDS_TABLES>
-static PathsRaysKernel paths_rays_kernel_of(bool few_blocks, bool verify) {
-    if (few_blocks) return verify ? k_paths_rays<LDS_TABLES, true, 2, false, false, true> : k_paths_rays<LDS_TABLES, true, 2, false, false, false>;
-    return verify ? k_paths_rays<LDS_TABLES, true, 4, false, false, true> : k_paths_rays<LDS_TABLES, true, 4, false, false, false>;
-}
-static PathsRaysKernel paths_rays_kernel(bool lds_tables, bool few_blocks, bool verify) {
-    return (lds_tables ? paths_rays_kernel_of<true> : paths_rays_kernel_of<false>)(few_blocks, verify);
-}
-
-// Keyed ray-table frames: k_paths_keyed (4-wide tree, the triangle-list definition of a hit, per-sample streams).  Full pool:
-// the build in which the waves draw their rows from the frame's counter; few blocks: rows tied to slots, gen() inside ADV.
-using PathsKeyedKernel = decltype(&k_paths_keyed<false, true, 4, true, false, false>);
-static PathsKeyedKernel paths_keyed_kernel(bool lds_tables, bool few_blocks) {
-    if (few_blocks) return lds_tables ? k_paths_keyed<true, true, 2, false, false, false> : k_paths_keyed<false, true, 2, false, false, false>;
-    return lds_tables ? k_paths_keyed<true, true, 4, true, false, false> : k_paths_keyed<false, true, 4, true, false, false>;
-}
-
-// Global overflow part of the traversal stacks: `levels` entries for each of kOverStride lanes.  Every OWNER of
-// concurrently running grids has its own buffer -- a render context (one render at a time: Context::busy), or one
-// call of a stage-level test entry point -- because a lane indexes its column by its position in ITS grid only:
-// two grids in flight on one device (RT_SPLIT sub-shards, host threads rendering different shard sizes) would
-// otherwise push to and pop from the same columns.  Grown on demand under the owner's lock, never shrunk.
-int ensure_overflow(int *&ptr, int &have_levels, int levels) {
-    levels = std::max(levels, 1);
-    if (ptr && have_levels >= levels) return 0;
-    if (ptr) {
-        HIP_TRY(hipDeviceSynchronize());  // (the owner is idle; this only guards against a caller's stray stream)
-        (void)hipFree(ptr);
-        ptr = nullptr;
-        have_levels = 0;
-    }
-    HIP_TRY(hipMalloc((void **)&ptr, sizeof(int) * (size_t)levels * kOverStride));
-    have_levels = levels;
-    return 0;
-}
-
-int ensure_rng(Context &c, uint64_t seed, int slot_lo, hipStream_t st, double *seconds) {
-    const size_t bytes = sizeof(uint32_t) * (size_t)c.n;
-    uint32_t *parts[6];
-    for (int k = 0; k < 6; k++) parts[k] = (uint32_t *)c.pools.array(A_RD + k);
-    *seconds = 0.0;
-    if (!(c.rng_valid && c.rng_seed == seed && c.rng_lo == slot_lo)) {
-        HIP_TRY(hipEventRecord(c.ev_a, st));
-        hipLaunchKernelGGL(k_rng_init, dim3(grid_for(c.n)), dim3(kBlock), 0, st, c.pools, c.n, slot_lo,
-                           xorwow_seed(seed), c.d_jump);
-        HIP_TRY(hipGetLastError());
-        for (int k = 0; k < 6; k++)
-            HIP_TRY(hipMemcpyAsync(c.rng_backup + (size_t)k * c.n, parts[k], bytes, hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipEventRecord(c.ev_b, st));
-        HIP_TRY(hipEventSynchronize(c.ev_b));
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, c.ev_a, c.ev_b));
-        *seconds = ms * 1e-3;
-        c.rng_valid = true;
-        c.rng_seed = seed;
-        c.rng_lo = slot_lo;
-    } else {
-        for (int k = 0; k < 6; k++)
-            HIP_TRY(hipMemcpyAsync(parts[k], c.rng_backup + (size_t)k * c.n, bytes, hipMemcpyDeviceToDevice, st));
-    }
-    return 0;
-}
-
-// One frame of one shard.  `rays` null: the camera's frame (rt_render_shard*).  `rays` set (rt_render_rays_*, which has
-// validated the table on the device; `camera` is not looked at): camera ray c is row c of the table, the frame is
-// rays->n_rays camera rays over width * height = n_pixels x 1 pixels, and `spp` is the rays_per_pixel of the c / spp rule.
-// Everything else -- context, RNG, stacks, launch parameters, the lockstep final generation, stats -- is one body.
-// `keyed` (rt_render_rays_keyed_*; the caller sets RT_FLAG_RNG_PER_SAMPLE): `keyed_table` instead of `table`, k_paths_keyed.
-struct RayFrame {
-    RayTable table;
-    long long n_rays;
-    bool keyed = false;
-    KeyedRayTable keyed_table{};
-};
-int render_shard_impl(const rt_scene *scene, const rt_camera *camera, int width, int height, int spp,
-                      int max_bounces, uint64_t seed, int shard_index, int shard_count, uint32_t flags,
-                      float *d_sum, hipStream_t st, rt_stats *stats, int ctx_lane = 0, const RayFrame *rays = nullptr) {
-    if (!scene || (!camera && !rays) || !d_sum) return fail("rt_render_shard: null argument");
-    if (width <= 0 || height <= 0 || spp <= 0 || max_bounces < 0) return fail("rt_render_shard: bad dimensions");
-    if (max_bounces > (1 << 24)) return fail("rt_render_shard: max_bounces exceeds 16777216");
-    if (shard_count <= 0 || kW % shard_count != 0 || shard_index < 0 || shard_index >= shard_count)
-        return fail("rt_render_shard: shard_count must divide 1048576 and 0 <= shard_index < shard_count");
-    if ((long long)width * height > (long long)(0x7fffffff / 3))  // framebuffer values are indexed with 32 bits
-        return fail("rt_render_shard: width*height exceeds 715827882 pixels");
-    // (camera rays start at lookfrom: camera.cuh:22-26; a table's origins: rt_render_rays_*'s prepass has seen to them)
-    if (!rays)
-        if (int rc = ensure_origin_radius(scene, camera->lookfrom)) return rc;
-    // RT_FLAG_RNG_PER_SAMPLE: this rank renders the whole frame at num_samples / shard_count samples per pixel with ALL W
-    // slots; camera ray `cid` of the rank has the global key cid * shard_count + shard_index, so the keys of a pixel's
-    // samples are the same set whatever the shard count (see AdvanceParams)
-    const bool per_sample = (flags & RT_FLAG_RNG_PER_SAMPLE) != 0;
-    const bool literal = (flags & RT_FLAG_REFERENCE_WALK) != 0;
-    if (literal && per_sample) return fail("rt_render_shard: RT_FLAG_REFERENCE_WALK is a parity mode and RT_FLAG_RNG_PER_SAMPLE is not: pick one");
-    if (literal && (flags & RT_FLAG_WATERTIGHT)) return fail("rt_render_shard: RT_FLAG_REFERENCE_WALK and RT_FLAG_WATERTIGHT exclude each other");
-    // the default: the reference's decisions (which hits its walk can see, who wins a tie) on the product's own walk.  The
-    // per-sample mode is not the reference's image anyway and keeps the triangle-list definition.
-    const bool verify = !literal && !per_sample && (flags & RT_FLAG_WATERTIGHT) == 0;
-    if (per_sample) {
-        if (spp % shard_count != 0) return fail("rt_render_shard: RT_FLAG_RNG_PER_SAMPLE needs num_samples divisible by shard_count");
-        spp /= shard_count;
-    }
-    long long cam_end = rays ? rays->n_rays : (long long)width * height * spp;
-    if (cam_end + 13LL * kW >= (1LL << 31))  // the reference's int32 camera_ray ids (render.cuh:370-371,440)
-        return fail("rt_render_shard: width*height*spp exceeds the reference's int32 camera-ray range");
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    if (dev != scene->device) return fail("rt_render_shard: scene was created on another device");
-    double ref_tree_seconds = 0.0;
-    if (literal || verify) {
-        bool built = false;
-        if (ensure_ref_tree(scene, &built)) return 1;
-        if (built) ref_tree_seconds = scene->build_seconds_ref;  // (this call paid for it)
-    }
-    const int n = per_sample ? kW : kW / shard_count;
-    const int slot_lo = per_sample ? 0 : shard_index * n;
-    Context *cp = nullptr;
-    if (get_context(n, ctx_lane, &cp)) return 1;
-    Context &c = *cp;
-    std::lock_guard<std::mutex> busy_lock(c.busy);  // concurrent callers with the same (device, n) queue up here
-    double rng_seconds = 0.0;
-    if (ensure_rng(c, seed, slot_lo, st, &rng_seconds)) return 1;
-
-    const bool time_kernels = (flags & RT_FLAG_TIME_KERNELS) != 0;
-    DScene sc = scene->dev();
-    Camera cam{};
-    if (!rays) memcpy(&cam, camera, sizeof(Camera));
-    const RayTable table = rays ? rays->table : RayTable{};
-    {
-        DCounters zero{};
-        zero.last_live_round = -1;
-        c.h_ctr[0] = zero;  // pinned staging
-        HIP_TRY(hipMemcpyAsync(c.d_ctr, &c.h_ctr[0], sizeof(DCounters), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemsetAsync(c.d_rows, 0, sizeof(DWaveRow) * (size_t)c.n_rows, st));  // (n / 64 rows of 64 bytes: 1 MB for the full pool)
-        HIP_TRY(hipStreamSynchronize(st));  // h_ctr[0] is reused as a snapshot slot below
-    }
-    const int stack_cap = lds_stack_cap(scene, kLdsStack);
-    const size_t lds_bytes = sizeof(int) * (size_t)kBlock * (size_t)(stack_cap + 2);  // stack (+ 1 row: push_if) + pending
-    // one buffer serves the context's k_trace and k_paths grids (never in flight together); k_paths keeps fewer
-    // entries in LDS, so it needs the deeper overflow
-    // (the literal walk of the reference's tree -- depth <= 30 -- borrows the lane's stack: reference_walk)
-    const int stack_need = std::max(scene->stack_bound, (literal || verify) ? 32 : 0);
-    if (ensure_overflow(c.d_over, c.over_levels, stack_need - std::min(stack_cap, lds_stack_cap(scene, kPathsLdsStack)))) return 1;
-    int *const d_over = c.d_over;
-    // Slots of this shard that ever get a camera ray: slot s serves the camera rays s, s + W, ..., so in a frame of fewer than
-    // W camera rays the slots from cam_end on never do anything -- the kernels of such a frame (it is nothing but the
-    // lockstep rounds: 256 x 256 x 4 uses a quarter of the slots) are launched over the live slots only.  Frames of more
-    // than one generation: all n.  (Per-sample streams: a lane draws its camera rays whatever its slot: all n.)
-    const int n_live = per_sample ? n : (int)std::max<long long>(1, std::min<long long>(n, cam_end - (long long)slot_lo));
-    hipLaunchKernelGGL(k_pool_init, dim3(grid_for(n_live)), dim3(kBlock), 0, st, c.pools, n_live, max_bounces);
-    HIP_TRY(hipGetLastError());
-
-    AdvanceParams ap;
-    ap.n = n_live;
-    ap.slot_lo = slot_lo;
-    ap.width = width;
-    ap.height = height;
-    ap.spp = spp;
-    ap.max_bounces = max_bounces;
-    ap.cam_end = cam_end;
-    ap.last_gen = per_sample ? 0x7fffffff : (int)((cam_end + kW - 1) / kW) - 1;  // (per-sample streams: no lockstep final generation)
-    ap.per_sample = per_sample ? 1 : 0;
-    ap.key_mul = per_sample ? shard_count : 1;
-    ap.key_add = per_sample ? shard_index : 0;
-    ap.seed_lo = (uint32_t)seed;
-    ap.seed_hi = (uint32_t)(seed >> 32);
-    ap.round = 0;
-    ap.batch_mask = 7;
-    ap.lockstep = 0;
-    ap.fb_fixed = (flags & kFlagFixedFb) ? 1 : 0;
-    ap.w_over_spp = (kW % spp == 0 && !rays) ? kW / spp : 0;  // (the pixel stepping is the camera frames')
-    ap.dpx = ap.w_over_spp % width;
-    ap.dpy = (ap.w_over_spp > 0 && width < 32768 && height < 32768) ? ap.w_over_spp / width : -1;
-    const bool lds_tables = scene->n_mats <= kLdsTable && scene->n_lights <= kLdsTable;
-
-    struct EventPair {  // destroyed on every return path
-        hipEvent_t a = nullptr, b = nullptr;
-        ~EventPair() {
-            if (a) (void)hipEventDestroy(a);
-            if (b) (void)hipEventDestroy(b);
-        }
-    } frame_events;
-    HIP_TRY(hipEventCreate(&frame_events.a));
-    HIP_TRY(hipEventCreate(&frame_events.b));
-    const hipEvent_t ev_start = frame_events.a, ev_stop = frame_events.b;
-    HIP_TRY(hipEventRecord(ev_start, st));
-
-    // Rounds are enqueued in batches; after each batch the counters are snapshotted into pinned
-    // host memory.  The host looks at the snapshot of batch b-2 before enqueuing batch b, so the
-    // GPU always has work queued, and stops when a whole batch traced no ray.
-    const int kBatch = 8;  // == ap.batch_mask + 1
-    const long long generations = (cam_end + kW - 1) / kW;
-    const long long max_rounds = (generations + 1) * (long long)(max_bounces + 2) + 64;
-    long long rounds = 0;
-    int batch = 0;
-    bool finished = false;
-    const dim3 grid(grid_for(n_live)), block(kBlock);
-    // persistent trace kernels: as many workgroups as the chip keeps resident (never more than the
-    // advance grid, whose wave count sizes the counter rows)
-    int dev_cus = 0, occ_c = 0;
-    HIP_TRY(hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, dev));
-    const AdvanceKernel advance_cam = advance_kernel(lds_tables);
-    const AdvanceRaysKernel advance_tab = advance_rays_kernel(lds_tables);
-    auto launch_advance = [&]() {
-        if (rays) hipLaunchKernelGGL(advance_tab, grid, block, 0, st, sc, c.pools, table, ap, d_sum, c.d_ctr, c.d_rows, c.d_lock);
-        else hipLaunchKernelGGL(advance_cam, grid, block, 0, st, sc, c.pools, cam, ap, d_sum, c.d_ctr, c.d_rows, c.d_lock);
-    };
-    const TraceKernel trace = trace_kernel<MODE_POOL>(literal, verify, scene->wide);
-    // (every k_trace build runs 8 waves per SIMD without static LDS: the grid does not depend on which one this is)
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_c, trace, kBlock, lds_bytes));
-    int per_cu = std::max(1, occ_c);
-    if (const char *e = knob("RT_TRACE_BLOCKS_PER_CU")) per_cu = std::max(1, std::min(per_cu, atoi(e)));
-    const int resident = std::max(1, dev_cus * per_cu);
-    const dim3 grid_trace(std::min(grid_for(n_live), resident));
-    TraceParams tpp{};
-    tpp.total = n_live;
-    tpp.fb = d_sum;
-    tpp.rows = c.d_rows;
-    tpp.debug_no_deposit = (flags & 0x100u) ? 1 : 0;
-    tpp.fb_fixed = (flags & kFlagFixedFb) ? 1 : 0;
-    tpp.vstat = &c.d_ctr->vstat[0];
-#ifdef RT_TRACE_PROFILE
-    unsigned long long *d_prof = nullptr;
-    HIP_TRY(hipMalloc((void **)&d_prof, sizeof(unsigned long long) * 16));
-    HIP_TRY(hipMemset(d_prof, 0, sizeof(unsigned long long) * 16));
-    tpp.prof = d_prof;
-#endif
-    // RT_FLAG_TIME_KERNELS: every kTimeStride-th round is bracketed with HIP events on the launch
-    // stream (no host synchronisation); the events are resolved after the loop.
-    const int kTimeStride = 4;
-    std::vector<hipEvent_t> &evs = c.timing_events;
-    size_t ev_used = 0;
-    auto next_event = [&](hipEvent_t *out) -> int {
-        if (ev_used == evs.size()) {
-            hipEvent_t e;
-            HIP_TRY(hipEventCreate(&e));
-            evs.push_back(e);
-        }
-        *out = evs[ev_used++];
-        return 0;
-    };
-    // ---- asynchronous part of the frame: ONE persistent launch (k_paths), or -- RT_PERSISTENT=0 -- the
-    // round-per-launch pipeline (k_advance + k_trace) that the lockstep final generation also uses
-    bool persistent = true;
-    if (const char *e = knob("RT_PERSISTENT")) persistent = atoi(e) != 0;
-    if (rays && !scene->wide) persistent = false;  // (k_paths_rays walks 4-wide nodes; the round pipeline walks either format)
-    if (per_sample && !persistent) return fail("rt_render_shard: RT_FLAG_RNG_PER_SAMPLE runs on the persistent kernel only");
-    float ms_paths = 0.f;
-    int top_records_in_lds = 0;
-    if (persistent) {
-        const int paths_cap = lds_stack_cap(scene, kPathsLdsStack);
-        int *const d_over2 = d_over;
-        size_t lds_paths = sizeof(int) * (size_t)kBlock * (size_t)(paths_cap + 26) + (lds_tables ? sizeof(float) * (size_t)((scene->tab_dwords + 3) & ~3) : 0) +
-                           sizeof(Camera) + sizeof(AdvanceParams);
-        const int dbg = (flags & 0x100u) ? 1 : 0;
-        unsigned long long *paths_prof = nullptr;
-#ifdef RT_TRACE_PROFILE
-        const size_t prof_bytes = 192 + 32 * (size_t)(grid_for(n) * (kBlock / 64));
-        HIP_TRY(hipMalloc((void **)&paths_prof, prof_bytes));
-        HIP_TRY(hipMemset(paths_prof, 0, prof_bytes));
-#endif
-        // all workgroups resident at once (4 per CU at <= 128 VGPRs), lane count a divisor of n
-        int paths_blocks = grid_for(n);
-        {
-            int want = 1024;
-            if (const char *e = knob("RT_PATHS_BLOCKS")) want = std::max(1, atoi(e));
-            while (paths_blocks > want && paths_blocks % 2 == 0) paths_blocks /= 2;
-        }
-        const dim3 grid_paths(paths_blocks);
-        int dev_cus_paths = 0;
-        HIP_TRY(hipDeviceGetAttribute(&dev_cus_paths, hipDeviceAttributeMultiprocessorCount, dev));
-        const bool few_blocks = paths_blocks <= 2 * dev_cus_paths;
-        int top_n = 0;
-        if (few_blocks) {
-            // records of the top of the tree kept in LDS (within the 64 KB of dynamic LDS a launch gets without further
-            // ado, ~36 KB of it slot state): 384 records of the binary tree.  For the 4-wide tree the copy buys nothing
-            // (1/8 shard of C2: 2 013 / 2 017 / 2 016 / 2 015 Msamples/s with 0 / 64 / 128 / 224 nodes in LDS -- the
-            // first levels are L2 hits the two waves' other work hides), so it is off unless RT_TOP_NODES asks for it
-            const int prefix = std::min(scene->n_nodes, (int)rtbvh::kTopPrefix * (scene->wide ? 2 : 1));
-            top_n = std::min(scene->wide ? 0 : 384, prefix);
-            if (const char *e = knob("RT_TOP_NODES")) top_n = std::max(0, std::min(std::min(768, atoi(e)), prefix));
-            if (scene->wide) top_n &= ~1;  // whole nodes
-            // (never more than the 64 KB of dynamic LDS a launch gets without further ado: scenes with many materials / lights
-            // have larger tables)
-            const size_t room = lds_paths < 65536 ? (65536 - lds_paths) / 64 : 0;
-            top_n = (int)std::min<size_t>((size_t)top_n, room) & (scene->wide ? ~1 : ~0);
-            lds_paths += (size_t)top_n * 64;
-            top_records_in_lds = top_n;
-        }
-        // lanes waiting for the ADV block before it runs: full pool flat 16..24 (round 3, with the triangle block behind the
-        // node block and no trip through the loop head after ADV / GEN: 20 and GEN 6 are 1 % ahead of 24 and 8); the
-        // 2-waves-per-SIMD shards want 30..38 (24: -2.5 %)
-        int adv_batch = few_blocks ? 34 : 20;
-        int gen_batch = 6;  // lanes waiting for the GEN block before it runs (unless nothing else can); flat 4..8
-        if (const char *e = knob("RT_ADV_BATCH")) adv_batch = std::max(1, std::min(64, atoi(e)));
-        if (const char *e = knob("RT_GEN_BATCH")) gen_batch = std::max(1, std::min(64, atoi(e)));
-        int tri_follow = 1;  // a triangle block right behind a node block when this many lanes hold a leaf by then; 0 = never
-        if (const char *e = knob("RT_TRI_FOLLOW")) tri_follow = std::max(0, std::min(64, atoi(e)));
-        // log2 of the priority-rotation period in scheduling decisions; 0 = off (128 ms for C2's frame).  Full pool: 111.7 - 112.2 /
-        // 111.8 / 111.9 / 112.1 / 112.5 ms at 4 / 5 / 6 / 7 / 8 (late round 5; C3 -0.9 % at 4, C4 flat); 1/8 shards want 8 (+1 % at 4)
-        int prio_rotate = few_blocks ? 8 : 5;
-        // period, in 64-slot blocks, after which slots repeat the same pixel-column lattice (see k_paths)
-        int rot_wave = 0, rot_set = 0;
-        {
-            long long period = 0;
-            if (!rays && spp % 64 == 0 && kW % spp == 0) {  // (a table's rays follow no pixel lattice: the fallback below)
-                const long long step = (kW / spp) % width;  // columns a slot moves per generation
-                long long a = step, b = width;
-                while (b) { long long t = a % b; a = b; b = t; }
-                period = a * (spp / 64);  // gcd(step, width) columns x blocks per pixel
-            }
-            const int waves = paths_blocks * (kBlock / 64);
-            if (period < 16 || period > waves) period = std::max(16, waves / 8);
-            rot_wave = (int)(period / 4);                // measured best on the bunny scenes: 128 / 160 blocks
-            rot_set = (int)(period / 4 + period / 16);
-            if (const char *e = knob("RT_ROT_WAVE")) rot_wave = atoi(e);
-            if (const char *e = knob("RT_ROT_SET")) rot_set = atoi(e);
-            rot_wave &= ~3;  // keeps wave j of a workgroup on blocks = j (mod 4): the map stays a bijection
-        }
-        if (const char *e = knob("RT_PRIO_ROTATE")) prio_rotate = atoi(e);
-        HIP_TRY(hipEventRecord(c.ev_a, st));
-        // (the reference-walk build is passed top_n = 0, while top_n * 64 bytes of LDS stay reserved and reported in reserved[2])
-        if (rays && rays->keyed) {
-            hipLaunchKernelGGL(paths_keyed_kernel(lds_tables, few_blocks), grid_paths, block, lds_paths, st, sc, c.pools, rays->keyed_table, ap,
-                               d_sum, c.d_rows, paths_cap, d_over2, adv_batch, dbg, paths_prof, top_n, prio_rotate, rot_wave, rot_set, gen_batch,
-                               tri_follow, &c.d_ctr->pad2[0], &c.d_ctr->vstat[0]);
-        } else if (rays) {
-            hipLaunchKernelGGL(paths_rays_kernel(lds_tables, few_blocks, verify), grid_paths, block, lds_paths, st, sc, c.pools, table, ap, d_sum,
-                               c.d_rows, paths_cap, d_over2, adv_batch, dbg, paths_prof, top_n, prio_rotate, rot_wave, rot_set, gen_batch,
-                               tri_follow, &c.d_ctr->pad2[0], &c.d_ctr->vstat[0]);
-        } else {
-            const PathsKernel paths = paths_kernel(lds_tables, scene->wide, few_blocks, per_sample, literal, verify);
-            hipLaunchKernelGGL(paths, grid_paths, block, lds_paths, st, sc, c.pools, cam, ap, d_sum, c.d_rows, paths_cap, d_over2, adv_batch,
-                               dbg, paths_prof, literal ? 0 : top_n, prio_rotate, rot_wave, rot_set, gen_batch, tri_follow, &c.d_ctr->pad2[0],
-                               &c.d_ctr->vstat[0]);
-        }
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(c.ev_b, st));
-        HIP_TRY(hipEventSynchronize(c.ev_b));
-        HIP_TRY(hipEventElapsedTime(&ms_paths, c.ev_a, c.ev_b));
-#ifdef RT_TRACE_PROFILE
-        {
-            unsigned long long h[24];
-            HIP_TRY(hipMemcpy(h, paths_prof, 192, hipMemcpyDeviceToHost));
-            fprintf(stderr, "k_paths cycles: ADV %.1f%% (%.0f / block) node %.1f%% (%.0f) tri %.1f%% (%.0f) rest %.1f%%\n",
-                    100.0 * h[8] / h[11], h[0] ? (double)h[8] / h[0] : 0.0, 100.0 * h[9] / h[11], h[2] ? (double)h[9] / h[2] : 0.0,
-                    100.0 * h[10] / h[11], h[4] ? (double)h[10] / h[4] : 0.0, 100.0 * (double)(h[11] - h[8] - h[9] - h[10]) / h[11]);
-            fprintf(stderr, "k_paths GEN blocks: %llu avg lanes %.1f, %.1f %% of wave time (%.0f cycles / block; inside `rest` above)\n", h[12],
-                    h[12] ? (double)h[15] / h[12] : 0.0, 100.0 * h[16] / h[11], h[12] ? (double)h[16] / h[12] : 0.0);
-            fprintf(stderr, "k_paths waves: %llu, mean lifetime %.0f cycles, longest %.0f cycles (x%.3f)\n", h[14], (double)h[11] / h[14], (double)h[13],
-                    (double)h[13] * h[14] / h[11]);
-            fprintf(stderr, "k_paths fin section: %.1f %% of wave time, entered in %llu iterations (avg %.1f finished lanes), %.0f cycles each\n",
-                    100.0 * h[17] / h[11], h[19], h[19] ? (double)h[18] / h[19] : 0.0, h[19] ? (double)h[17] / h[19] : 0.0);
-            fprintf(stderr, "k_paths profile: ADV blocks %llu avg lanes %.1f | node steps %llu avg lanes %.1f (ADV-waiting %.1f) | tri steps %llu avg lanes %.1f (ADV-waiting %.1f)\n",
-                    h[0], h[0] ? (double)h[1] / h[0] : 0.0, h[2], h[2] ? (double)h[3] / h[2] : 0.0, h[2] ? (double)h[6] / h[2] : 0.0, h[4],
-                    h[4] ? (double)h[5] / h[4] : 0.0, h[4] ? (double)h[7] / h[4] : 0.0);
-            if (const char *dump = knob("RT_PROF_DUMP")) {  // per-wave records: hw_id xcc_id cycles blocks
-                std::vector<unsigned long long> recs(4 * (size_t)paths_blocks * (kBlock / 64));
-                HIP_TRY(hipMemcpy(recs.data(), paths_prof + 24, recs.size() * 8, hipMemcpyDeviceToHost));
-                if (FILE *f = fopen(dump, "w")) {
-                    for (size_t k = 0; k < recs.size(); k += 4)
-                        fprintf(f, "%zu %llu %llu %llu %llu\n", k / 4, recs[k], recs[k + 1], recs[k + 2], recs[k + 3]);
-                    fclose(f);
-                }
-            }
-            (void)hipFree(paths_prof);
-        }
-#endif
-        finished = true;
-    }
-    while (!finished && rounds < max_rounds) {
-        for (int k = 0; k < kBatch; k++) {
-            ap.round = (int)(rounds & 0x3fffffff);
-            if (time_kernels && (rounds % kTimeStride) == 0) {
-                hipEvent_t e0, e1, e2, e3;
-                if (next_event(&e0) || next_event(&e1) || next_event(&e2) || next_event(&e3)) return 1;
-                HIP_TRY(hipEventRecord(e0, st));
-                launch_advance();
-                HIP_TRY(hipEventRecord(e1, st));
-                hipLaunchKernelGGL(trace, grid_trace, block, lds_bytes, st, sc, c.pools, tpp, stack_cap, d_over);
-                HIP_TRY(hipEventRecord(e2, st));
-                HIP_TRY(hipEventRecord(e3, st));
-            } else {
-                launch_advance();
-                hipLaunchKernelGGL(trace, grid_trace, block, lds_bytes, st, sc, c.pools, tpp, stack_cap, d_over);
-            }
-            rounds++;
-        }
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(&c.h_ctr[batch & 3], c.d_ctr, sizeof(DCounters), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipEventRecord(c.ev_ring[batch & 3], st));
-        if (batch >= 1) {
-            int prev = (batch - 1) & 3;
-            HIP_TRY(hipEventSynchronize(c.ev_ring[prev]));
-            // k_advance records liveness only in the round that closes a batch (liveness is monotone):
-            // if the closing round of batch b-1 traced nothing, every slot is finished
-            if ((long long)c.h_ctr[prev].last_live_round < (long long)batch * kBatch - 1) finished = true;
-        }
-        batch++;
-    }
-    // ---- final generation in lockstep (see k_advance): round 0 generates, every later round is one
-    // reference iteration; the render ends at the first round in which nothing shades (render.cuh:436)
-    // All max_bounces + 2 rounds are enqueued back to back; which of them still belong to the render is decided on the
-    // device (k_advance / k_trace look at lock_shades), and the host learns the number of rounds that ran afterwards.
-    // The rounds go out in chunks of kLockChunk: the reference's 12 rounds (max_bounces = 10) are ONE chunk -- no host
-    // read-back inside the frame --, and a caller with max_bounces in the thousands does not pay thousands of empty launches
-    // once the render has ended: between chunks the host looks at the last round's counter.
-    const int n_lock = max_bounces + 2;
-    const bool ran_lockstep = finished && !per_sample;
-    int lock_enqueued = 0;
-    if (ran_lockstep) {
-        if (n_lock > c.lock_cap) {  // (the stop rule's counters: one word per round, grown on demand)
-            HIP_TRY(hipStreamSynchronize(st));
-            (void)hipFree(c.d_lock);
-            c.d_lock = nullptr;
-            c.lock_cap = 0;
-            HIP_TRY(hipMalloc((void **)&c.d_lock, sizeof(unsigned) * (size_t)std::max(n_lock, 64)));
-            c.lock_cap = std::max(n_lock, 64);
-        }
-        HIP_TRY(hipMemsetAsync(c.d_lock, 0, sizeof(unsigned) * (size_t)n_lock, st));
-        while (lock_enqueued < n_lock) {
-            const int hi = std::min(n_lock, lock_enqueued + kLockChunk);
-            for (int j = lock_enqueued; j < hi; j++) {
-                ap.round = (int)((rounds + j) & 0x3fffffff);
-                ap.lockstep = 1 + j;
-                launch_advance();
-                tpp.lock_shades = c.d_lock;
-                tpp.lock_round = j;
-                hipLaunchKernelGGL(trace, grid_trace, block, lds_bytes, st, sc, c.pools, tpp, stack_cap, d_over);
-            }
-            HIP_TRY(hipGetLastError());
-            lock_enqueued = hi;
-            if (hi < n_lock) {  // (more than one chunk: max_bounces >= 15)
-                unsigned last = 1u;
-                HIP_TRY(hipMemcpyAsync(&last, c.d_lock + (hi - 1), sizeof(unsigned), hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipStreamSynchronize(st));
-                if (last == 0u && hi - 1 >= 1) break;  // that round shaded nothing: the render is over (render.cuh:436)
-            }
-        }
-    }
-    HIP_TRY(hipEventRecord(ev_stop, st));
-    HIP_TRY(hipEventSynchronize(ev_stop));
-    if (ran_lockstep) {  // rounds that ran: up to and including the first one (after the generating round) that shaded nothing
-        std::vector<unsigned> h_lock((size_t)lock_enqueued);
-        HIP_TRY(hipMemcpy(h_lock.data(), c.d_lock, sizeof(unsigned) * (size_t)lock_enqueued, hipMemcpyDeviceToHost));
-        int ran = lock_enqueued;
-        for (int j = 1; j < lock_enqueued; j++)
-            if (h_lock[(size_t)j] == 0u) {
-                ran = j + 1;
-                break;
-            }
-        rounds += ran;
-    }
-#ifdef RT_TRACE_PROFILE
-    {
-        unsigned long long h[16];
-        HIP_TRY(hipMemcpy(h, d_prof, sizeof(h), hipMemcpyDeviceToHost));
-        fprintf(stderr, "trace profile: waves %llu outer_it %llu refills %llu | inner_it %llu avg_lanes %.1f | leaf_it %llu avg_lanes %.1f | "
-                        "tri_it %llu avg_lanes %.1f | active lanes at loop top %.1f | finalised lanes per refill %.1f\n",
-                h[10], h[0], h[1], h[2], h[2] ? (double)h[3] / h[2] : 0.0, h[4], h[4] ? (double)h[5] / h[4] : 0.0, h[6],
-                h[6] ? (double)h[7] / h[6] : 0.0, h[0] ? (double)h[8] / h[0] : 0.0, h[1] ? (double)h[9] / h[1] : 0.0);
-        (void)hipFree(d_prof);
-    }
-#endif
-    float ms_total = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms_total, ev_start, ev_stop));
-    DCounters h_final{};
-    HIP_TRY(hipMemcpy(&h_final, c.d_ctr, sizeof(DCounters), hipMemcpyDeviceToHost));
-    std::vector<DWaveRow> h_rows((size_t)c.n_rows);
-    HIP_TRY(hipMemcpy(h_rows.data(), c.d_rows, sizeof(DWaveRow) * (size_t)c.n_rows, hipMemcpyDeviceToHost));
-    unsigned long long fin[C_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (const DWaveRow &r : h_rows)
-        for (int k = 0; k < C_COUNT; k++) fin[k] += r.c[k];
-    double t_adv = 0, t_ch = 0, t_ah = 0;
-    long long n_sampled = (long long)(ev_used / 4);
-    for (size_t q = 0; q + 3 < ev_used; q += 4) {
-        float ms;
-        HIP_TRY(hipEventElapsedTime(&ms, evs[q], evs[q + 1]));
-        t_adv += ms;
-        HIP_TRY(hipEventElapsedTime(&ms, evs[q + 1], evs[q + 2]));
-        t_ch += ms;
-        HIP_TRY(hipEventElapsedTime(&ms, evs[q + 2], evs[q + 3]));
-        t_ah += ms;
-    }
-    if (!finished) return fail("rt_render_shard: round limit reached before the path pool drained");
-    if (stats) {
-        memset(stats, 0, sizeof(*stats));
-        stats->camera_rays = (int64_t)fin[C_CAMERA];
-        stats->shade_events = (int64_t)fin[C_SHADE];
-        stats->closest_rays = (int64_t)fin[C_CLOSEST];
-        stats->any_rays = (int64_t)fin[C_ANY];
-        stats->emission_adds = (int64_t)fin[C_EMIT];
-        stats->shadow_adds = (int64_t)fin[C_SHADOW_ADD];
-        stats->rr_draws = (int64_t)fin[C_RR];
-        stats->iterations = rounds;
-        stats->bvh_nodes = scene->n_nodes;
-        stats->bvh_depth = scene->max_depth;
-        stats->seconds_render = ms_total * 1e-3;
-        stats->seconds_rng_init = rng_seconds;
-        // sampled every kTimeStride-th round; scaled to all rounds (average launch duration x launches)
-        double scale_up = n_sampled > 0 ? (double)rounds / (double)n_sampled : 0.0;
-        stats->seconds_trace = t_ch * 1e-3 * scale_up;
-        stats->seconds_reference_tree = ref_tree_seconds;
-        (void)t_ah;
-        stats->seconds_advance = t_adv * 1e-3 * scale_up;
-        stats->launches_trace = rounds;
-        stats->reserved[0] = n_sampled;
-        if (persistent) {  // the frame's dominant kernel is the one k_paths launch
-            stats->seconds_trace = ms_paths * 1e-3;
-            stats->seconds_advance = 0.0;
-            stats->launches_trace = 1;
-            stats->reserved[0] = 1;
-            stats->reserved[1] = 1;
-            stats->reserved[2] = top_records_in_lds;
-        }
-        stats->reserved[4] = (int64_t)h_final.vstat[V_LITERAL];
-        stats->reserved[5] = (int64_t)h_final.vstat[V_LOST];
-        stats->reserved[6] = (int64_t)h_final.vstat[V_TIE];
-    }
-    return 0;
-}
-
-// A shard may be rendered as `split` interleaved sub-shards on separate HIP streams (one host thread
-// each): slot sets are independent, so the sub-shards only meet in the framebuffer atomics, and the
-// tail of one sub-shard's persistent trace kernel overlaps the head of the other's.
-int render_overlapped(const rt_scene *scene, const rt_camera *camera, int width, int height, int spp,
-                      int max_bounces, uint64_t seed, int shard_index, int shard_count, uint32_t flags,
-                      float *d_sum, hipStream_t st, rt_stats *stats) {
-    int split = 1;
-    if (const char *e = knob("RT_SPLIT")) split = std::max(1, std::min(8, atoi(e)));
-    while (split > 1 && (shard_count <= 0 || kW % (shard_count * split) != 0 || kW / (shard_count * split) < 4096)) split >>= 1;
-    if (split <= 1)
-        return render_shard_impl(scene, camera, width, height, spp, max_bounces, seed, shard_index, shard_count, flags,
-                                 d_sum, st, stats);
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    HIP_TRY(hipStreamSynchronize(st));  // the caller zeroed d_sum on its stream
-    std::vector<rt_stats> sub(split);
-    std::vector<int> rc(split, 0);
-    std::vector<std::string> err(split);
-    std::vector<std::thread> th;
-    for (int k = 0; k < split; k++)
-        th.emplace_back([&, k] {
-            if (hipSetDevice(dev) != hipSuccess) { rc[k] = 1; err[k] = "hipSetDevice failed"; return; }
-            hipStream_t s2;
-            if (hipStreamCreateWithFlags(&s2, hipStreamNonBlocking) != hipSuccess) { rc[k] = 1; err[k] = "stream create failed"; return; }
-            rc[k] = render_shard_impl(scene, camera, width, height, spp, max_bounces, seed, shard_index * split + k,
-                                      shard_count * split, flags, d_sum, s2, &sub[k], k + 1);
-            if (rc[k]) err[k] = g_last_error;
-            (void)hipStreamSynchronize(s2);
-            (void)hipStreamDestroy(s2);
-        });
-    for (auto &t : th) t.join();
-    for (int k = 0; k < split; k++)
-        if (rc[k]) return fail(err[k]);
-    if (stats) {
-        rt_stats tot = sub[0];
-        for (int k = 1; k < split; k++) {
-            tot.camera_rays += sub[k].camera_rays;
-            tot.shade_events += sub[k].shade_events;
-            tot.closest_rays += sub[k].closest_rays;
-            tot.any_rays += sub[k].any_rays;
-            tot.emission_adds += sub[k].emission_adds;
-            tot.shadow_adds += sub[k].shadow_adds;
-            tot.rr_draws += sub[k].rr_draws;
-            tot.iterations += sub[k].iterations;
-            tot.launches_trace += sub[k].launches_trace;
-            tot.seconds_trace += sub[k].seconds_trace;
-            tot.seconds_advance += sub[k].seconds_advance;
-            tot.seconds_render = std::max(tot.seconds_render, sub[k].seconds_render);
-            tot.seconds_rng_init = std::max(tot.seconds_rng_init, sub[k].seconds_rng_init);
-            tot.seconds_reference_tree = std::max(tot.seconds_reference_tree, sub[k].seconds_reference_tree);
-            tot.reserved[0] += sub[k].reserved[0];
-            tot.reserved[2] = std::max(tot.reserved[2], sub[k].reserved[2]);
-            for (int q = 4; q < 7; q++) tot.reserved[q] += sub[k].reserved[q];
-        }
-        *stats = tot;
-    }
-    return 0;
-}
-
-// What rt_trace_closest_flags and rt_trace_any_flags share: the mode flags, the reference tree, the origins' padding, the
-// rays' upload, the overflow stacks and the launch of k_trace<MODE>.  `tp` arrives with the entry point's own buffers set;
-// every device buffer lives in `tmp`.
-template <int MODE>
-static int trace_test_rays(const rt_scene *scene, uint32_t flags, int n, const float *origin_xyz, const float *dir_xyz,
-                           const float *tmax, TraceParams tp, DevScope &tmp) {
-    const bool literal = (flags & RT_FLAG_REFERENCE_WALK) != 0;
-    const bool verify = !literal && (flags & RT_FLAG_WATERTIGHT) == 0;
-    if ((literal || verify) && ensure_ref_tree(scene)) return 1;
-    float *d_o, *d_d, *d_tm;
-    unsigned long long *d_vstat;
-    if (tmp.alloc(d_vstat, 4)) return 1;
-    HIP_TRY(hipMemset(d_vstat, 0, 4 * sizeof(unsigned long long)));
-    if (tmp.alloc(d_o, 3 * (size_t)n) || tmp.alloc(d_d, 3 * (size_t)n) || tmp.alloc(d_tm, (size_t)n)) return 1;
-    {
-        float need[3] = {0.f, 0.f, 0.f};  // the 4-wide records must be padded for these origins (ensure_origin_radius)
-        for (int i = 0; i < n; i++)
-            for (int a = 0; a < 3; a++)
-                if (std::isfinite(origin_xyz[3 * (size_t)i + a])) need[a] = std::max(need[a], std::fabs(origin_xyz[3 * (size_t)i + a]));
-        if (int rc = ensure_origin_radius(scene, need)) return rc;
-    }
-    HIP_TRY(hipMemcpy(d_o, origin_xyz, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_d, dir_xyz, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_tm, tmax, sizeof(float) * (size_t)n, hipMemcpyHostToDevice));
-    const int test_grid = std::min(grid_for(n), 2048);
-    const int stack_cap = lds_stack_cap(scene, kLdsStack);
-    int *d_over = nullptr;
-    int over_levels = 0;
-    if (ensure_overflow(d_over, over_levels, std::max(scene->stack_bound, 32) - stack_cap)) return 1;
-    tmp.ptrs.push_back(d_over);
-    tp.total = n;
-    tp.o3 = d_o;
-    tp.d3 = d_d;
-    tp.tmax = d_tm;
-    tp.vstat = d_vstat;
-    DPools none{};
-    hipLaunchKernelGGL(trace_kernel<MODE>(literal, verify, scene->wide), dim3(test_grid), dim3(kBlock),
-                       sizeof(int) * kBlock * (size_t)(stack_cap + 2), nullptr, scene->dev(), none, tp, stack_cap, d_over);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// rt_query_closest_device / rt_query_any_device.  Every kernel of a query is ordered on `st`; the host waits twice: for the
-// prepass's four words (validation, and the origin radius the 4-wide records must be padded for) and for the walk.
-using QueryKernel = decltype(&k_query<Q_CLOSEST, false, false, false>);
-template <int KIND>
-static QueryKernel query_kernel(bool literal, bool verify, bool wide) {
-    if (literal) return k_query<KIND, false, true, false>;
-    if (verify) return wide ? k_query<KIND, true, false, true> : k_query<KIND, false, false, true>;
-    return wide ? k_query<KIND, true, false, false> : k_query<KIND, false, false, false>;
-}
-template <int KIND>
-static int query_impl(const rt_scene *scene, uint32_t flags, int n, const float *d_o, const float *d_d, const float *d_tmax,
-                      const int32_t *d_excluded, int32_t *d_out_i, float *d_t, float *d_u, float *d_v, hipStream_t st) {
-    const std::string w(KIND == Q_CLOSEST ? "rt_query_closest_device" : "rt_query_any_device");
-    if (!scene) return fail(w + ": null scene");
-    if (n < 0 || n > (1 << 30)) return fail(w + ": n = " + std::to_string(n) + " is outside 0 .. 2^30");
-    if (flags & ~(uint32_t)(RT_FLAG_REFERENCE_WALK | RT_FLAG_WATERTIGHT)) return fail(w + ": flags other than RT_FLAG_REFERENCE_WALK / RT_FLAG_WATERTIGHT");
-    const bool literal = (flags & RT_FLAG_REFERENCE_WALK) != 0;
-    if (literal && (flags & RT_FLAG_WATERTIGHT)) return fail(w + ": RT_FLAG_REFERENCE_WALK and RT_FLAG_WATERTIGHT exclude each other");
-    if (n > 0 && (!d_o || !d_d || !d_out_i))
-        return fail(w + ": null " + (!d_o ? "d_origin_xyz" : !d_d ? "d_dir_xyz" : KIND == Q_CLOSEST ? "d_hit_tri" : "d_occluded"));
-    if (n == 0) return 0;
-    const bool verify = !literal && (flags & RT_FLAG_WATERTIGHT) == 0;
-    rt_scene::QueryState &q = scene->query;
-    std::lock_guard<std::mutex> lock(q.mutex);
-    DeviceGuard dev;
-    if (dev.enter(scene->device)) return 1;
-    if (!q.d_words) {  // first query of this scene
-        HIP_TRY(hipDeviceGetAttribute(&q.cus, hipDeviceAttributeMultiprocessorCount, scene->device));
-        HIP_TRY(hipHostMalloc((void **)&q.h_words, sizeof(QueryWords), hipHostMallocDefault));
-        HIP_TRY(hipMalloc((void **)&q.d_words, sizeof(QueryWords)));
-    }
-    if ((literal || verify) && ensure_ref_tree(scene)) return 1;
-    HIP_TRY(hipMemsetAsync(q.d_words, 0, sizeof(QueryWords), st));
-    hipLaunchKernelGGL(k_query_prepass, dim3(std::min((n + kBlock - 1) / kBlock, 8 * std::max(q.cus, 1))), dim3(kBlock), 0, st, d_o, d_d, n,
-                       q.d_words);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(q.h_words, q.d_words, 4 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (q.h_words->bad_dirs != 0)
-        return fail(w + ": " + std::to_string(q.h_words->bad_dirs) + " of " + std::to_string(n) + " directions are not finite or reach 2^126");
-    {
-        float need[3];
-        memcpy(need, q.h_words->radius_bits, sizeof(need));
-        if (int rc = ensure_origin_radius(scene, need)) return rc;
-    }
-    if (KIND == Q_ANY && d_excluded && !q.d_inverse && scene->n_tris > 0) {
-        HIP_TRY(hipMalloc((void **)&q.d_inverse, sizeof(int) * (size_t)scene->n_tris));
-        hipLaunchKernelGGL(k_query_inverse, dim3((scene->n_tris + 255) / 256), dim3(256), 0, st, scene->d_order, scene->n_tris, q.d_inverse);
-    }
-    const int stack_cap = lds_stack_cap(scene, kLdsStack);
-    if (ensure_overflow(q.d_over, q.over_levels, std::max(scene->stack_bound, 32) - stack_cap)) return 1;
-    QueryParams qp{};
-    qp.n = n;
-    qp.n_tris = scene->n_tris;
-    qp.o3 = d_o;
-    qp.d3 = d_d;
-    qp.tmax = d_tmax;
-    qp.excluded = d_excluded;
-    qp.inverse = q.d_inverse;
-    qp.out_i = d_out_i;
-    qp.out_t = d_t;
-    qp.out_u = d_u;
-    qp.out_v = d_v;
-    qp.vstat = q.d_words->vstat;
-    const QueryKernel kernel = query_kernel<KIND>(literal, verify, scene->wide);
-    const size_t lds = sizeof(int) * kBlock * (size_t)(stack_cap + 1);
-    int per_cu = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kBlock, lds));
-    // as many workgroups as the device holds at once (never more lanes than the overflow stacks have columns), fewer when
-    // the rays do not fill them
-    const int resident = std::min(std::max(per_cu, 1) * std::max(q.cus, 1), kOverStride / kBlock);
-    const int grid = std::max(1, std::min(resident, (int)(((size_t)n + kBlock - 1) / kBlock)));
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, st, scene->dev(), qp, stack_cap, q.d_over);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(q.h_words->vstat, q.d_words->vstat, sizeof(q.h_words->vstat), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    q.counters[0] = (int64_t)q.h_words->vstat[V_LITERAL];
-    q.counters[1] = (int64_t)q.h_words->vstat[V_LOST];
-    q.counters[2] = (int64_t)q.h_words->vstat[V_TIE];
-    return 0;
-}
-
-// rt_render_rays_device / rt_render_rays_fixed_device: host-side argument checks, the table's validation on the device
-// (k_query_prepass for directions and origin radius, k_pixel_prepass for the pixel indices; nothing is written before both
-// have passed), then the frame through render_shard_impl.  The prepass borrows the scene's query scratch under its lock.
-static int render_rays_impl(const rt_scene *scene, int64_t n_rays, const float *d_o, const float *d_d, const int32_t *d_pixel,
-                            int rays_per_pixel, int n_pixels, int max_bounces, uint64_t seed, uint32_t flags, float *d_sum,
-                            hipStream_t st, rt_stats *stats) {
-    const std::string w((flags & kFlagFixedFb) ? "rt_render_rays_fixed_device" : "rt_render_rays_device");
-    if (!scene) return fail(w + ": null scene");
-    if (!d_o || !d_d || !d_sum) return fail(w + ": null " + (!d_o ? "d_origin_xyz" : !d_d ? "d_dir_xyz" : "sum buffer"));
-    if (flags & RT_FLAG_REFERENCE_WALK) return fail(w + ": RT_FLAG_REFERENCE_WALK is not supported for ray tables");
-    if (flags & RT_FLAG_RNG_PER_SAMPLE) return fail(w + ": RT_FLAG_RNG_PER_SAMPLE is not supported for ray tables");
-    if (flags & ~(uint32_t)(RT_FLAG_WATERTIGHT | RT_FLAG_TIME_KERNELS | kFlagFixedFb)) return fail(w + ": flags other than RT_FLAG_WATERTIGHT / RT_FLAG_TIME_KERNELS");
-    if (n_rays < 1) return fail(w + ": n_rays = " + std::to_string((long long)n_rays) + " (at least 1)");
-    if (n_rays + 13LL * kW >= (1LL << 31)) return fail(w + ": n_rays exceeds the reference's int32 camera-ray range");
-    if (n_pixels < 1 || n_pixels > 0x7fffffff / 3) return fail(w + ": n_pixels = " + std::to_string(n_pixels) + " is outside 1 .. 715827882");
-    if (max_bounces < 0 || max_bounces > (1 << 24)) return fail(w + ": max_bounces is outside 0 .. 16777216");
-    if (!d_pixel) {
-        if (rays_per_pixel < 1) return fail(w + ": rays_per_pixel = " + std::to_string(rays_per_pixel) + " (at least 1 when d_pixel is null)");
-        if ((n_rays - 1) / rays_per_pixel >= n_pixels)
-            return fail(w + ": ray " + std::to_string((long long)(n_rays - 1)) + " falls on pixel " + std::to_string((long long)((n_rays - 1) / rays_per_pixel)) +
-                        " of " + std::to_string(n_pixels));
-    }
-    DeviceGuard dev;
-    if (dev.enter(scene->device)) return 1;
-    const int n = (int)n_rays;
-    {
-        rt_scene::QueryState &q = scene->query;
-        std::lock_guard<std::mutex> lock(q.mutex);
-        if (!q.d_words) {  // (as the first query of this scene)
-            HIP_TRY(hipDeviceGetAttribute(&q.cus, hipDeviceAttributeMultiprocessorCount, scene->device));
-            HIP_TRY(hipHostMalloc((void **)&q.h_words, sizeof(QueryWords), hipHostMallocDefault));
-            HIP_TRY(hipMalloc((void **)&q.d_words, sizeof(QueryWords)));
-        }
-        const dim3 grid(std::min((n + kBlock - 1) / kBlock, 8 * std::max(q.cus, 1)));
-        HIP_TRY(hipMemsetAsync(q.d_words, 0, sizeof(QueryWords), st));
-        hipLaunchKernelGGL(k_query_prepass, grid, dim3(kBlock), 0, st, d_o, d_d, n, q.d_words);
-        if (d_pixel) hipLaunchKernelGGL(k_pixel_prepass, grid, dim3(kBlock), 0, st, d_pixel, n, n_pixels, q.d_words);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(q.h_words, q.d_words, 6 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (q.h_words->bad_dirs != 0)
-            return fail(w + ": " + std::to_string(q.h_words->bad_dirs) + " of " + std::to_string(n) + " directions are not finite or reach 2^126");
-        if (q.h_words->bad_pixels != 0)
-            return fail(w + ": " + std::to_string(q.h_words->bad_pixels) + " of " + std::to_string(n) + " pixel indices are outside 0 .. " + std::to_string(n_pixels - 1));
-        float need[3];
-        memcpy(need, q.h_words->radius_bits, sizeof(need));
-        if (int rc = ensure_origin_radius(scene, need)) return rc;
-    }
-    RayFrame rays;
-    rays.table = RayTable{d_o, d_d, d_pixel};
-    rays.n_rays = n_rays;
-    return render_shard_impl(scene, nullptr, n_pixels, 1, d_pixel ? 1 : rays_per_pixel, max_bounces, seed, 0, 1, flags, d_sum, st, stats, 0, &rays);
-}
-
-// rt_render_rays_keyed_device / rt_render_rays_keyed_fixed_device: render_rays_impl's checks and prepass, the checks of the
-// keys, then the frame through render_shard_impl in the per-sample mode (full pool, no parking, no lockstep final
-// generation) with k_paths_keyed: row c's stream is rng_sample_stream(seed, key_first + c * key_stride).
-static int render_rays_keyed_impl(const rt_scene *scene, int64_t n_rays, const float *d_o, const float *d_d, const int32_t *d_pixel,
-                                  int rays_per_pixel, int n_pixels, int max_bounces, uint64_t seed, uint64_t key_first,
-                                  uint32_t key_stride, uint32_t flags, float *d_sum, hipStream_t st, rt_stats *stats) {
-    const std::string w((flags & kFlagFixedFb) ? "rt_render_rays_keyed_fixed_device" : "rt_render_rays_keyed_device");
-    if (!scene) return fail(w + ": null scene");
-    if (!d_o || !d_d || !d_sum) return fail(w + ": null " + (!d_o ? "d_origin_xyz" : !d_d ? "d_dir_xyz" : "sum buffer"));
-    if (flags & RT_FLAG_REFERENCE_WALK) return fail(w + ": RT_FLAG_REFERENCE_WALK is not supported for keyed ray tables");
-    // (RT_FLAG_RNG_PER_SAMPLE and RT_FLAG_WATERTIGHT are what the mode is: accepted, and change nothing)
-    if (flags & ~(uint32_t)(RT_FLAG_RNG_PER_SAMPLE | RT_FLAG_WATERTIGHT | RT_FLAG_TIME_KERNELS | kFlagFixedFb))
-        return fail(w + ": flags other than RT_FLAG_RNG_PER_SAMPLE / RT_FLAG_WATERTIGHT / RT_FLAG_TIME_KERNELS");
-    if (n_rays < 1) return fail(w + ": n_rays = " + std::to_string((long long)n_rays) + " (at least 1)");
-    if (n_rays + 13LL * kW >= (1LL << 31)) return fail(w + ": n_rays exceeds the int32 camera-ray range of one call");
-    if (n_pixels < 1 || n_pixels > 0x7fffffff / 3) return fail(w + ": n_pixels = " + std::to_string(n_pixels) + " is outside 1 .. 715827882");
-    if (max_bounces < 0 || max_bounces > (1 << 24)) return fail(w + ": max_bounces is outside 0 .. 16777216");
-    if (key_stride < 1) return fail(w + ": key_stride = 0 (at least 1)");
-    // the last key, key_first + (n_rays - 1) * key_stride: the product is below 2^63, the sum must not wrap 2^64
-    const unsigned long long span = (unsigned long long)(n_rays - 1) * key_stride;
-    if (span > ~0ull - (unsigned long long)key_first)
-        return fail(w + ": the key of the last ray, " + std::to_string((unsigned long long)key_first) + " + " + std::to_string(span) + ", wraps 2^64");
-    const unsigned long long key_last = (unsigned long long)key_first + span;
-    if (!d_pixel) {
-        if (rays_per_pixel < 1) return fail(w + ": rays_per_pixel = " + std::to_string(rays_per_pixel) + " (at least 1 when d_pixel is null)");
-        if (key_last / (unsigned)rays_per_pixel >= (unsigned long long)n_pixels)
-            return fail(w + ": key " + std::to_string(key_last) + " falls on pixel " + std::to_string(key_last / (unsigned)rays_per_pixel) + " of " +
-                        std::to_string(n_pixels));
-    }
-    if (!scene->wide) return fail(w + ": keyed ray tables need the 4-wide tree (the scene was created with RT_BVH_WIDE=0)");
-    if (const char *e = knob("RT_PERSISTENT"))
-        if (atoi(e) == 0) return fail(w + ": keyed ray tables run on the persistent kernel only (RT_PERSISTENT=0 is set)");
-    DeviceGuard dev;
-    if (dev.enter(scene->device)) return 1;
-    const int n = (int)n_rays;
-    {
-        rt_scene::QueryState &q = scene->query;
-        std::lock_guard<std::mutex> lock(q.mutex);
-        if (!q.d_words) {  // (as the first query of this scene)
-            HIP_TRY(hipDeviceGetAttribute(&q.cus, hipDeviceAttributeMultiprocessorCount, scene->device));
-            HIP_TRY(hipHostMalloc((void **)&q.h_words, sizeof(QueryWords), hipHostMallocDefault));
-            HIP_TRY(hipMalloc((void **)&q.d_words, sizeof(QueryWords)));
-        }
-        const dim3 grid(std::min((n + kBlock - 1) / kBlock, 8 * std::max(q.cus, 1)));
-        HIP_TRY(hipMemsetAsync(q.d_words, 0, sizeof(QueryWords), st));
-        hipLaunchKernelGGL(k_query_prepass, grid, dim3(kBlock), 0, st, d_o, d_d, n, q.d_words);
-        if (d_pixel) hipLaunchKernelGGL(k_pixel_prepass, grid, dim3(kBlock), 0, st, d_pixel, n, n_pixels, q.d_words);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(q.h_words, q.d_words, 6 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (q.h_words->bad_dirs != 0)
-            return fail(w + ": " + std::to_string(q.h_words->bad_dirs) + " of " + std::to_string(n) + " directions are not finite or reach 2^126");
-        if (q.h_words->bad_pixels != 0)
-            return fail(w + ": " + std::to_string(q.h_words->bad_pixels) + " of " + std::to_string(n) + " pixel indices are outside 0 .. " + std::to_string(n_pixels - 1));
-        float need[3];
-        memcpy(need, q.h_words->radius_bits, sizeof(need));
-        if (int rc = ensure_origin_radius(scene, need)) return rc;
-    }
-    const uint32_t rpp = d_pixel ? 1u : (uint32_t)rays_per_pixel;
-    RayFrame rays;
-    rays.table = RayTable{};
-    rays.n_rays = n_rays;
-    rays.keyed = true;
-    rays.keyed_table = KeyedRayTable{d_o, d_d, d_pixel, (unsigned long long)key_first, key_stride, rpp,
-                                     d_pixel ? 0 : (int)(key_first / rpp), d_pixel ? 0u : (uint32_t)(key_first % rpp)};
-    const uint32_t mode = (flags & (RT_FLAG_TIME_KERNELS | kFlagFixedFb)) | RT_FLAG_RNG_PER_SAMPLE;
-    if (int rc = render_shard_impl(scene, nullptr, n_pixels, 1, (int)rpp, max_bounces, seed, 0, 1, mode, d_sum, st, stats, 0, &rays)) {
-        fail(w + ": " + g_last_error);  // (what the frame itself refused, under this entry point's name)
-        return rc;
-    }
-    return 0;
-}
-
-// rt_render_aov_fixed / rt_render_aov_rays_fixed_device: the entry points check their arguments (and, for a table, run the
-// device prepasses) and hand the ray source over; this is the one body behind both -- the reference's tree where the hit
-// definition needs it, the overflow stacks, the launch sized from the device, the kernel's time and the rare-path counters.
-// The caller holds the scene's query lock and has entered the scene's device; q.d_words is zeroed on `st`.
-template <class SRC>
-using AovKernel = void (*)(DScene, SRC, AovParams, int, int *);
-template <class SRC>
-static AovKernel<SRC> aov_kernel(bool literal, bool verify, bool wide) {
-    if (literal) return k_aov<SRC, false, true, false>;
-    if (verify) return wide ? k_aov<SRC, true, false, true> : k_aov<SRC, false, false, true>;
-    return wide ? k_aov<SRC, true, false, false> : k_aov<SRC, false, false, false>;
-}
-static int aov_flags(const std::string &w, uint32_t flags) {
-    if (flags & ~(uint32_t)(RT_FLAG_WATERTIGHT | RT_FLAG_REFERENCE_WALK | RT_FLAG_TIME_KERNELS))
-        return fail(w + ": flags other than RT_FLAG_WATERTIGHT / RT_FLAG_REFERENCE_WALK / RT_FLAG_TIME_KERNELS");
-    if ((flags & RT_FLAG_REFERENCE_WALK) && (flags & RT_FLAG_WATERTIGHT))
-        return fail(w + ": RT_FLAG_REFERENCE_WALK and RT_FLAG_WATERTIGHT exclude each other");
-    return 0;
-}
-static int aov_query_state(const rt_scene *scene) {  // (as the first query of this scene)
-    rt_scene::QueryState &q = scene->query;
-    if (!q.d_words) {
-        HIP_TRY(hipDeviceGetAttribute(&q.cus, hipDeviceAttributeMultiprocessorCount, scene->device));
-        HIP_TRY(hipHostMalloc((void **)&q.h_words, sizeof(QueryWords), hipHostMallocDefault));
-        HIP_TRY(hipMalloc((void **)&q.d_words, sizeof(QueryWords)));
-    }
-    if (!q.ev_a) HIP_TRY(hipEventCreate(&q.ev_a));
-    if (!q.ev_b) HIP_TRY(hipEventCreate(&q.ev_b));
-    return 0;
-}
-template <class SRC>
-static int aov_launch(const rt_scene *scene, const SRC &src, int n, uint32_t flags, int64_t *d_aov, int32_t *d_ids, hipStream_t st,
-                      rt_stats *stats) {
-    rt_scene::QueryState &q = scene->query;
-    const bool literal = (flags & RT_FLAG_REFERENCE_WALK) != 0;
-    const bool verify = !literal && (flags & RT_FLAG_WATERTIGHT) == 0;
-    if ((literal || verify) && ensure_ref_tree(scene)) return 1;
-    const int stack_cap = lds_stack_cap(scene, kLdsStack);
-    if (ensure_overflow(q.d_over, q.over_levels, std::max(scene->stack_bound, 32) - stack_cap)) return 1;
-    AovParams ap{};
-    ap.n = n;
-    ap.sums = (unsigned long long *)d_aov;
-    ap.ids = d_ids;
-    ap.vstat = q.d_words->vstat;
-    const AovKernel<SRC> kernel = aov_kernel<SRC>(literal, verify, scene->wide);
-    const size_t lds = sizeof(int) * kBlock * (size_t)(stack_cap + 1);
-    int per_cu = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kBlock, lds));
-    // (k_query's grid: what the device holds at once, never more lanes than the overflow stacks have columns)
-    const int resident = std::min(std::max(per_cu, 1) * std::max(q.cus, 1), kOverStride / kBlock);
-    const int grid = std::max(1, std::min(resident, (int)(((size_t)n + kBlock - 1) / kBlock)));
-    HIP_TRY(hipEventRecord(q.ev_a, st));
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, st, scene->dev(), src, ap, stack_cap, q.d_over);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(q.ev_b, st));
-    HIP_TRY(hipMemcpyAsync(q.h_words->vstat, q.d_words->vstat, sizeof(q.h_words->vstat), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, q.ev_a, q.ev_b));
-    if (stats) {
-        memset(stats, 0, sizeof(*stats));
-        stats->camera_rays = n;
-        stats->closest_rays = n;
-        stats->bvh_nodes = scene->n_nodes;
-        stats->bvh_depth = scene->max_depth;
-        stats->seconds_render = ms * 1e-3;
-        stats->seconds_trace = ms * 1e-3;
-        stats->launches_trace = 1;
-        stats->reserved[4] = (int64_t)q.h_words->vstat[V_LITERAL];
-        stats->reserved[5] = (int64_t)q.h_words->vstat[V_LOST];
-        stats->reserved[6] = (int64_t)q.h_words->vstat[V_TIE];
-    }
-    return 0;
-}
-
-static int render_aov_impl(const rt_scene *scene, const rt_camera *camera, int width, int height, int spp, uint64_t seed,
-                           int shard_index, int shard_count, uint32_t flags, int64_t *d_aov, int32_t *d_ids, hipStream_t st,
-                           rt_stats *stats) {
-    const std::string w("rt_render_aov_fixed");
-    if (!scene) return fail(w + ": null scene");
-    if (!camera || !d_aov) return fail(w + ": null " + (!camera ? "camera" : "d_aov_fixed"));
-    if (aov_flags(w, flags)) return 1;
-    if (width < 1 || height < 1 || spp < 1)
-        return fail(w + ": width, height and num_samples must be at least 1 (" + std::to_string(width) + " x " + std::to_string(height) + " x " + std::to_string(spp) + ")");
-    if ((long long)width * height > (long long)(0x7fffffff / 3)) return fail(w + ": width*height exceeds 715827882 pixels");
-    if ((long long)width * height * spp + 13LL * kW >= (1LL << 31)) return fail(w + ": width*height*num_samples exceeds the int32 camera-ray range");
-    if (shard_count < 1 || shard_index < 0 || shard_index >= shard_count)
-        return fail(w + ": shard_index = " + std::to_string(shard_index) + " is outside 0 .. shard_count - 1 (shard_count = " + std::to_string(shard_count) + ")");
-    if (spp % shard_count != 0)
-        return fail(w + ": num_samples = " + std::to_string(spp) + " is not divisible by shard_count = " + std::to_string(shard_count));
-    DeviceGuard dev;
-    if (dev.enter(scene->device)) return 1;
-    // (camera rays start at lookfrom: as render_shard_impl)
-    if (int rc = ensure_origin_radius(scene, camera->lookfrom)) return rc;
-    rt_scene::QueryState &q = scene->query;
-    std::lock_guard<std::mutex> lock(q.mutex);
-    if (aov_query_state(scene)) return 1;
-    HIP_TRY(hipMemsetAsync(q.d_words, 0, sizeof(QueryWords), st));
-    AovCamera src{};
-    memcpy(&src.cam, camera, sizeof(Camera));
-    src.width = width;
-    src.height = height;
-    src.spp = (unsigned)(spp / shard_count);
-    src.key_mul = (unsigned)shard_count;
-    src.key_add = (unsigned)shard_index;
-    src.seed_lo = (uint32_t)seed;
-    src.seed_hi = (uint32_t)(seed >> 32);
-    const int n = (int)((long long)width * height * (spp / shard_count));
-    // the sample with G % num_samples == 0 has G % shard_count == 0: it is shard 0's
-    return aov_launch(scene, src, n, flags, d_aov, shard_index == 0 ? d_ids : nullptr, st, stats);
-}
-
-static int render_aov_rays_impl(const rt_scene *scene, int64_t n_rays, const float *d_o, const float *d_d, const int32_t *d_pixel,
-                                int rays_per_pixel, int n_pixels, uint64_t key_first, uint32_t key_stride, uint32_t flags,
-                                int64_t *d_aov, int32_t *d_ids, hipStream_t st, rt_stats *stats) {
-    const std::string w("rt_render_aov_rays_fixed_device");
-    if (!scene) return fail(w + ": null scene");
-    if (!d_o || !d_d || !d_aov) return fail(w + ": null " + (!d_o ? "d_origin_xyz" : !d_d ? "d_dir_xyz" : "d_aov_fixed"));
-    if (aov_flags(w, flags)) return 1;
-    if (d_ids && d_pixel) return fail(w + ": d_ids together with d_pixel (ids belong to the pixels of the key rule: pass d_pixel = NULL)");
-    // (the checks of render_rays_keyed_impl)
-    if (n_rays < 1) return fail(w + ": n_rays = " + std::to_string((long long)n_rays) + " (at least 1)");
-    if (n_rays + 13LL * kW >= (1LL << 31)) return fail(w + ": n_rays exceeds the int32 camera-ray range of one call");
-    if (n_pixels < 1 || n_pixels > 0x7fffffff / 3) return fail(w + ": n_pixels = " + std::to_string(n_pixels) + " is outside 1 .. 715827882");
-    if (key_stride < 1) return fail(w + ": key_stride = 0 (at least 1)");
-    const unsigned long long span = (unsigned long long)(n_rays - 1) * key_stride;
-    if (span > ~0ull - (unsigned long long)key_first)
-        return fail(w + ": the key of the last ray, " + std::to_string((unsigned long long)key_first) + " + " + std::to_string(span) + ", wraps 2^64");
-    const unsigned long long key_last = (unsigned long long)key_first + span;
-    if (!d_pixel) {
-        if (rays_per_pixel < 1) return fail(w + ": rays_per_pixel = " + std::to_string(rays_per_pixel) + " (at least 1 when d_pixel is null)");
-        if (key_last / (unsigned)rays_per_pixel >= (unsigned long long)n_pixels)
-            return fail(w + ": key " + std::to_string(key_last) + " falls on pixel " + std::to_string(key_last / (unsigned)rays_per_pixel) + " of " +
-                        std::to_string(n_pixels));
-    }
-    DeviceGuard dev;
-    if (dev.enter(scene->device)) return 1;
-    const int n = (int)n_rays;
-    rt_scene::QueryState &q = scene->query;
-    std::lock_guard<std::mutex> lock(q.mutex);
-    if (aov_query_state(scene)) return 1;
-    const dim3 grid(std::min((n + kBlock - 1) / kBlock, 8 * std::max(q.cus, 1)));
-    HIP_TRY(hipMemsetAsync(q.d_words, 0, sizeof(QueryWords), st));
-    hipLaunchKernelGGL(k_query_prepass, grid, dim3(kBlock), 0, st, d_o, d_d, n, q.d_words);
-    if (d_pixel) hipLaunchKernelGGL(k_pixel_prepass, grid, dim3(kBlock), 0, st, d_pixel, n, n_pixels, q.d_words);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(q.h_words, q.d_words, 6 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (q.h_words->bad_dirs != 0)
-        return fail(w + ": " + std::to_string(q.h_words->bad_dirs) + " of " + std::to_string(n) + " directions are not finite or reach 2^126");
-    if (q.h_words->bad_pixels != 0)
-        return fail(w + ": " + std::to_string(q.h_words->bad_pixels) + " of " + std::to_string(n) + " pixel indices are outside 0 .. " + std::to_string(n_pixels - 1));
-    float need[3];
-    memcpy(need, q.h_words->radius_bits, sizeof(need));
-    if (int rc = ensure_origin_radius(scene, need)) return rc;
-    const uint32_t rpp = d_pixel ? 1u : (uint32_t)rays_per_pixel;
-    const KeyedRayTable src{d_o, d_d, d_pixel, (unsigned long long)key_first, key_stride, rpp,
-                            d_pixel ? 0 : (int)(key_first / rpp), d_pixel ? 0u : (uint32_t)(key_first % rpp)};
-    return aov_launch(scene, src, n, flags, d_aov, d_ids, st, stats);
-}
-
+#include "rt_host_scene.inc"   // (opens the anonymous namespace that is closed below) rt_scene: upload, reference tree, checks, emit, update, rebuild, edits; what the ray entry points share
+#include "rt_host_render.inc"  // Context, kernel selection, frames, test rays, queries, ray tables, AOVs
 }  // namespace
 
 // ============================================================================ C-ABI
