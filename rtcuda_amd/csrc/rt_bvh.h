@@ -151,7 +151,7 @@ inline float pad_up(float v, int k) {
 // 2-ulp-padded ones pushed outward by another 2^-23 R_a, where R_a bounds |o_a| over every ray that will be traced:
 // origins of secondary rays lie on the scene's triangles (offset by at most 256 ulps: offset_ray_origin), the camera and
 // the rays of the test hooks are looked at by the caller, who re-pads for a larger radius when one comes along.
-// The scene's records are padded on the device by k_refit_emit (rtcuda_amd.hip), the same arithmetic as the two functions
+// The scene's records are padded on the device by k_refit_emit (rt_build_kernels.inc), the same arithmetic as the two functions
 // below; they are its host reference (rt_host_check.cpp).  (The kernel takes the bounds of the root's children alone: they
 // contain every box below them, so the maximum is the same.)
 inline void quads_abs_bounds(const std::vector<Pair> &quads, float m[3]) {

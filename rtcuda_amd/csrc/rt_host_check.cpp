@@ -4,7 +4,7 @@
 //   * rt_bvh_selfcheck  validates both record formats the kernels can be given -- `quads` (4-wide, the default: two
 //     pair-style records per node) and `pairs` (2-wide) -- structurally (every triangle in exactly one leaf, every node
 //     reachable exactly once, every record box contains what lies beneath it, stack bound) and walks both on the CPU
-//     with the control flow and the fp32 expressions of inner_step / the triangle blocks in rtcuda_amd.hip, comparing
+//     with the control flow and the fp32 expressions of inner_step (rt_walk.inc) / the triangle blocks of the kernels, comparing
 //     with an exhaustive search.  A malformed tree would hang or fault the GPU; this is where it is caught first.
 //   * rt_bvh_refit_check  the host twin of the device refit (rt_scene_update): the builder's records with new vertices,
 //     checked as above (bit-equal to the builder's with the creation vertices; structure and walk with moved ones).
@@ -44,7 +44,7 @@ inline bool tri_hit(const Tri &tr, V3 o, V3 d, float tmax, float &t) {
     }
     return false;
 }
-// (as box_hit / inner_step in rtcuda_amd.hip; the kernels' 1 / d is v_rcp_f32, 1 ulp, here an exact division)
+// (as box_hit / inner_step in rt_walk.inc; the kernels' 1 / d is v_rcp_f32, 1 ulp, here an exact division)
 inline bool box_hit(V3 o, V3 inv, const float *lo, const float *hi, float tmax, float &entry) {
     float ax = (lo[0] - o.x) * inv.x, bx = (hi[0] - o.x) * inv.x;
     float ay = (lo[1] - o.y) * inv.y, by = (hi[1] - o.y) * inv.y;
@@ -56,7 +56,7 @@ inline bool box_hit(V3 o, V3 inv, const float *lo, const float *hi, float tmax, 
     return t_in <= t_out && t_out >= 0.f && t_in <= tmax * 1.000001f;
 }
 // The 4-wide node step of the kernels: plane distance as ONE fma, b * (1 / d) + s with s = -o * (1 / d) rounded on its own
-// (inner_step<true> in rtcuda_amd.hip); the records it is given are padded for that (rt_bvh.h, pad_quads_for_origins)
+// (inner_step<true> in rt_walk.inc); the records it is given are padded for that (rt_bvh.h, pad_quads_for_origins)
 inline bool box_hit_fma(V3 o, V3 inv, const float *lo, const float *hi, float tmax, float &entry) {
     const float sx = -o.x * inv.x, sy = -o.y * inv.y, sz = -o.z * inv.z;
     float ax = fmaf(lo[0], inv.x, sx), bx = fmaf(hi[0], inv.x, sx);
@@ -96,7 +96,7 @@ struct WalkResult {
     long long own_fail = 0, leaf_fail = 0;  // verified walks: hits whose own box / whose reference leaf box fails the reference's slab test
 };
 
-// ---- the reference's slab test (aabb_intersector.cuh:14-36), as reference_walk / ref_visible in rtcuda_amd.hip
+// ---- the reference's slab test (aabb_intersector.cuh:14-36), as reference_walk / ref_visible in rt_walk.inc
 struct RefSlab {
     bool nx, ny, nz;
     V3 inv, so;
@@ -290,7 +290,7 @@ int64_t validate(const rtbvh::Result &r, const std::vector<rtbvh::Pair> &rec, bo
     for (int i = 0; i < n_nodes; i++) if (seen_node[i] != 1) errors++;
     return errors;
 }
-// ---- host twin of the device refit (k_refit_level in rtcuda_amd.hip): the builder's 4-wide records with new vertices.
+// ---- host twin of the device refit (k_refit_level in rt_build_kernels.inc): the builder's 4-wide records with new vertices.
 // A node's child boxes are exact -- a leaf child's from the triangles' vertices p0, p1, p2, an inner child's the union of
 // its own children's exact boxes -- and padded by 2 ulps only when written, as rtbvh::build writes them.  Children come
 // after their parent in record order, so one backward sweep is bottom-up.
@@ -353,7 +353,7 @@ double quads_sah_host(const std::vector<rtbvh::Pair> &quads) {
     return quads.size() < 2 || !(e0 >= 0.0) ? 0.0 : cost / std::max((e0 + e1) * e2 + e0 * e1, 1e-30);
 }
 
-// ---- host twin of the device PLOC builder (k_ploc_* in rtcuda_amd.hip): the same keys, nearest neighbours, merges, leaves
+// ---- host twin of the device PLOC builder (k_ploc_* in rt_build_kernels.inc): the same keys, nearest neighbours, merges, leaves
 // and 4-wide collapse, one after the other, with rt_ploc.h's expressions -- the device's records and leaf order, bit for bit.
 struct PlocHostNodes {
     int n = 0;
@@ -708,7 +708,7 @@ struct HostWalk {
     int n = 0;
     RefView ref;               // the reference's own tree (rt_ref_tree.h), for the verified walks
 };
-// Bvh::traverse (bvh.cuh:251-303 / :306-357) over the reference's tree, as reference_walk in rtcuda_amd.hip: left child
+// Bvh::traverse (bvh.cuh:251-303 / :306-357) over the reference's tree, as reference_walk in rt_walk.inc: left child
 // before right child, a leaf child intersected on the spot, near inner child first by fp32 entry distance, the later
 // tested triangle wins t <= tmax.  best / excl: leaf-order indices of the product (as everywhere in this file).
 void literal_walk(const HostWalk &hw, int mode, V3 o, V3 d, float tmax, int excl, WalkResult &w) {

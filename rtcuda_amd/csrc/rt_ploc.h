@@ -1,5 +1,5 @@
 // rt_ploc.h -- the arithmetic of the device BVH builder (PLOC, parallel locally-ordered clustering, Meister & Bittner 2018),
-// shared by its kernels (k_ploc_* in rtcuda_amd.hip) and its sequential host twin (rt_host_check.cpp).  Both are built with
+// shared by its kernels (k_ploc_* in rt_build_kernels.inc) and its sequential host twin (rt_host_check.cpp).  Both are built with
 // -ffp-contract=off, so every expression below is rounded operation by operation in the order written, on the device as on
 // the host: the same bits.  (fminf / fmaxf may disagree on the sign of a zero; no result below depends on it.)
 //

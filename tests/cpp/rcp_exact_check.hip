@@ -1,6 +1,6 @@
 // rcp_exact_check.hip -- is rt::rcp_exact_normal (rt_device.h) the correctly rounded 1 / x on THIS chip?
 //
-// The default kernels check every closest hit against the reference's slab test (ref_visible, rtcuda_amd.hip), which
+// The default kernels check every closest hit against the reference's slab test (ref_visible, rt_walk.inc), which
 // needs 1 / d exactly as the reference computes it (an IEEE division, aabb_intersector.cuh:17-19).  The product uses
 // v_rcp_f32 + one FMA Newton step there (rcp_exact_normal<1>); v_rcp_f32 is a hardware approximation, so the only proof of "same bits" is to
 // try every operand the call site can see: the reference clamps |d| to >= FLT_EPSILON and d is a unit vector's component,

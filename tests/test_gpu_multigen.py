@@ -11,7 +11,7 @@ render.cuh:84-137 (init), :139-248 (mat), :250-275 (gen), :278-328 (ah / ch), :4
 
 The oracle runs in its LITERAL mode here -- the reference's own tree, its fp32 slab test on exact boxes and its tree-order
 tie rule (bvh.cuh:221-357, aabb_intersector.cuh:14-36, triangle.cuh:49) -- against the DEFAULT kernels, which make the
-reference's decisions on their own walk (ref_visible in rtcuda_amd.hip).  RT_FLAG_WATERTIGHT (the triangle-list definition)
+reference's decisions on their own walk (ref_visible in rt_walk.inc).  RT_FLAG_WATERTIGHT (the triangle-list definition)
 is held against the oracle's watertight mode by the tests that name it.
 
 Bar: integer event totals EQUAL to the oracle's, image RMS < 2e-6 per channel (only the order of

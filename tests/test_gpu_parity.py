@@ -541,7 +541,7 @@ def test_split_probe_counts_what_the_frame_traces(api, gpu_full, bunny_full_bsdf
 
 
 def test_rcp_exact_normal_is_the_ieee_quotient_on_this_chip(tmp_path):
-    """ref_visible (rtcuda_amd.hip) needs 1 / d exactly as the reference's IEEE division gives it and computes it as
+    """ref_visible (rt_walk.inc) needs 1 / d exactly as the reference's IEEE division gives it and computes it as
     v_rcp_f32 + one FMA Newton step (rt_device.h: rcp_exact_normal).  v_rcp_f32 is a hardware approximation, so the proof is
     exhaustive and runs here: every normal fp32 bit pattern with |x| < 2^126 (4.2 * 10^9 operands), compiled with the
     product's flags, against the compiler's `1.f / x`."""

@@ -214,6 +214,59 @@ def test_four_million_rays_in_one_call(api, oracle, bunny_matte):
     gpu.close()
 
 
+class _GuardedOutputs:
+    """query_closest / query_any of a scene through the device entry points, into buffers of the caller's that are 64
+    elements longer than the batch and pre-filled with SENTINEL: what lies past the batch must come back untouched."""
+
+    def __init__(self, gpu):
+        self.gpu = gpu
+
+    @staticmethod
+    def _buffers(n, dtypes):
+        return [torch.full((n + 64,), SENTINEL, dtype=dt, device="cuda") for dt in dtypes]
+
+    @staticmethod
+    def _cut(n, bufs):
+        torch.cuda.synchronize()
+        for b in bufs:
+            assert bool((b[n:] == SENTINEL).all()), f"{n} rays: an output was written past the batch"
+        return [b[:n] for b in bufs]
+
+    def query_closest(self, o, d, tmax=None, flags=0):
+        n = len(o)
+        bufs = self._buffers(n, [torch.int32, torch.float32, torch.float32, torch.float32])
+        self.gpu.query_closest_device(o.data_ptr(), d.data_ptr(), 0 if tmax is None else tmax.data_ptr(), n,
+                                      *(b.data_ptr() for b in bufs), flags)
+        return tuple(self._cut(n, bufs))
+
+    def query_any(self, o, d, tmax=None, excluded=None, flags=0):
+        n = len(o)
+        bufs = self._buffers(n, [torch.int32])
+        self.gpu.query_any_device(o.data_ptr(), d.data_ptr(), 0 if tmax is None else tmax.data_ptr(),
+                                  0 if excluded is None else excluded.data_ptr(), n, bufs[0].data_ptr(), flags)
+        return self._cut(n, bufs)[0]
+
+
+def test_batches_around_one_chunk_and_one_wave(api, oracle, bunny_matte):
+    """The hand-out of chunks at its edges: one lane, one short of a chunk of 64, exactly one, one over, two chunks and a bit,
+    and a count that gives most waves of the grid nothing and a few of them one chunk.  Closest hit under the three flag
+    modes, any hit with and without the excluded triangles; every answer the oracle's, nothing written past the batch."""
+    gpu = api.Scene(bunny_matte)
+    guarded = _GuardedOutputs(gpu)
+    o_all, d_all = raygen.camera_rays(default_camera(oracle, 16 / 9), 1920, 1080, 4097, seed=71)
+    for n in (1, 63, 64, 65, 129, 4097):
+        o, d = o_all[:n], d_all[:n]
+        for flags, watertight in _flag_modes(api):
+            cpu = oracle_scene(oracle, "matte", watertight)
+            _check_closest(guarded, cpu, o, d, flags=flags, what=f"{n} rays")
+        cpu = oracle_scene(oracle, "matte", False)
+        # (bounce rays leave the hits only -- the first ray of this seed hits --: tiled to the count under test)
+        o2, d2, tm, excl = (np.ascontiguousarray(x[np.arange(n) % len(x)]) for x in _any_batch(cpu, bunny_matte, o, d, seed=72))
+        _check_any(guarded, cpu, o2, d2, tm, excl)
+        _check_any(guarded, cpu, o2, d2, tm, np.full(n, -1, np.int32), excluded_null=True)
+    gpu.close()
+
+
 # ---- 6: stream order
 def test_query_is_ordered_on_the_callers_stream(api, oracle, bunny_matte):
     """On a non-default stream: a torch kernel writes the rays, the query runs on that stream, a torch kernel consumes hit_tri;

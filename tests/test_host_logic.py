@@ -355,7 +355,7 @@ def test_reference_tree_of_the_product_is_the_oracles_node_for_node(oracle, vari
 
 @pytest.mark.parametrize("variant", ["matte", "sixteen_lights", "four_bunnies"])
 def test_reference_tree_boxes_are_nested_exactly(variant):
-    """The premise of the default kernels' visibility test (rtcuda_amd.hip: ref_visible): along every
+    """The premise of the default kernels' visibility test (rt_walk.inc: ref_visible): along every
     root-to-leaf path of the reference's tree the boxes are NESTED EXACTLY -- a child's bounds lie inside its parent's with no
     rounding in between (both are min / max of the same fp32 triangle bounds: bvh.cuh:57-61,150-160) -- and every leaf's box
     contains the own box of each of its triangles as triangle.cuh:22-37 computes it from the stored record (p1 = p0 - e1,

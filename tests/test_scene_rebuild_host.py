@@ -1,6 +1,6 @@
 """The device BVH builder (PLOC: rt_scene_rebuild, RT_SCENE_DEVICE_BVH) checked on the host through its twin.  No GPU needed.
 
-rt_host_check.cpp holds a sequential restatement of the device build (k_ploc_* in rtcuda_amd.hip) with the same fp32
+rt_host_check.cpp holds a sequential restatement of the device build (k_ploc_* in rt_build_kernels.inc) with the same fp32
 expressions (rt_ploc.h): the GPU tests (test_gpu_scene_rebuild.py) show that the device gives the twin's records and leaf
 order bit for bit, and this file shows that those make a valid tree -- every triangle in exactly one leaf, every box
 containing what lies beneath it, the 4-wide walk finding what exhaustive search finds -- of surface-area quality close to

@@ -1,6 +1,6 @@
 """Refit of a scene's BVH to new vertex positions (rt_scene_update), checked on the host.  No GPU needed.
 
-rt_host_check.cpp holds a host twin of the device refit (k_refit_level in rtcuda_amd.hip): the builder's 4-wide records with
+rt_host_check.cpp holds a host twin of the device refit (k_refit_level in rt_build_kernels.inc): the builder's 4-wide records with
 exact child boxes recomputed from new vertices, padded by 2 ulps on write.  With the vertices of creation it must give the
 builder's records bit for bit; with moved vertices the records must pass the builder's structural checks and the 4-wide walk
 must find what exhaustive search finds.

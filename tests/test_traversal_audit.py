@@ -15,7 +15,7 @@ What is checked here, without a GPU:
     the larger caller index wins, where the reference lets its tree order decide -- SURVEY Appendix A.10) agrees with
     the product's walk on EVERY ray, triangle index included, which is why the GPU parity tests can demand equal
     integer event totals against it at any frame size;
-  * round 5 -- the DEFAULT kernels' decision procedure (rtcuda_amd.hip: ref_visible + the rare literal re-trace), as its
+  * round 5 -- the DEFAULT kernels' decision procedure (rt_walk.inc: ref_visible + the rare literal re-trace), as its
     CPU twin `rt_hostwalk_trace_verified`: the product's own walk, every hit checked against what the reference's walk can
     SEE.  The reference's box test ignores tmax, so visibility is a function of the ray alone; the boxes on a root-to-leaf
     path are nested exactly and fp32 rounding is monotone, so a triangle is visible iff its LEAF's box passes the
