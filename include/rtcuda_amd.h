@@ -77,8 +77,9 @@ typedef struct rt_stats {
     double seconds_advance;  /* same for the advance kernel */
     int64_t launches_trace;  /* launches of each stage kernel (= iterations) */
     int64_t reserved[7];     /* reserved[0] = launches actually sampled by the event timer;
-                                reserved[1] = 1 when the frame ran as one persistent k_paths launch (then
-                                seconds_trace is that launch's duration and launches_trace is 1);
+                                reserved[1] = nonzero when the frame ran as one persistent k_paths launch (then
+                                seconds_trace is that launch's duration and launches_trace is 1): 1 + the camera rays
+                                per task of the chunked deal of slots to lanes, so 1 = the static deal;
                                 reserved[2] = BVH node records that launch staged in LDS (small shards only);
                                 reserved[3] = rt_render_multi: number of device shards behind these totals;
                                 default kernels (no RT_FLAG_WATERTIGHT): reserved[4] = rays re-traced through the reference's

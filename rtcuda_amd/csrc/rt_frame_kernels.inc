@@ -3,6 +3,9 @@
 //   RT_FRAME_SRC               Camera (gen()'s pinhole), RayTable (the caller's rays, rt_render_rays_*) or KeyedRayTable (the
 //                              caller's rays with a per-sample stream each, rt_render_rays_keyed_*): see gen_core
 //   RT_K_ADVANCE / RT_K_PATHS  the names of the two kernels of that compilation
+//   RT_PATHS_CHUNKS            1: RT_K_PATHS is the build with the chunked deal (rt_slot_chunks.h), a kernel of its own name so
+//                              that the static deal keeps its code, instruction for instruction; only its 4-waves-per-SIMD
+//                              reference-mode instances are ever launched
 // No include guard: meant to be included more than once.
 
 // k_advance: one slot per thread, state in the pools.
@@ -160,6 +163,22 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
     // small shards (MIN_WAVES == 2: at most 2 workgroups per CU, LDS to spare, latency-bound): the top of
     // the BVH is staged in LDS, so the first levels of every traversal do not leave the CU
     const float4 *s_top = (const float4 *)(s_tab + (LDS_TABLES ? ((sc.tab_dwords + 3) & ~3) : 0));  // (tables: what the scene needs)
+    // The chunked deal (rt_slot_chunks.h) of the 4-waves-per-SIMD reference-mode builds: G > 0 camera rays per task, 0 = the
+    // static deal.  These builds keep no records of the tree in LDS, so G travels in `top_n`.
+    constexpr bool CHUNKS = RT_PATHS_CHUNKS && SPLIT_GEN && !DRAW_CIDS;
+    // [0]: the workgroup's next task; [1]: G; [2 .. 4]: rtchunks::multiple_of(G).  The GEN block reads G and the three words
+    // from here: as scalars kept across the main loop they pushed other scalars out into VGPR lanes (53 more v_readlane in
+    // the default build, and the static deal 2.5 % slower than without this code).
+    __shared__ __attribute__((aligned(16))) unsigned s_task[CHUNKS ? 8 : 1];
+    if (CHUNKS && threadIdx.x == 0) {
+        const rtchunks::Multiple m = rtchunks::multiple_of(top_n > 0 ? (unsigned)top_n : 1u);
+        s_task[0] = 0u;
+        s_task[1] = top_n > 0 ? (unsigned)top_n : 0u;
+        s_task[2] = m.inv;
+        s_task[3] = m.shift;
+        s_task[4] = m.limit;
+    }
+    const bool chunk_start = CHUNKS && top_n > 0;  // (only used before the main loop)
     if (MIN_WAVES != 2) top_n = 0;
     for (int k = threadIdx.x; k < top_n * 4; k += kBlock) ((float4 *)s_top)[k] = sc.nodes[k];
     if (LDS_TABLES) {
@@ -205,16 +224,13 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
     // whole CUs differ by +-5 % in work (bunny or no bunny in their columns) -- which the slowest one turns
     // into frame time.  So the j-th wave of a workgroup is shifted by j quarter periods and the k-th slot set
     // by k * 5/16 of a period.  A bijection between (set, 64-slot block) and (set, wave).  +6 % at 1 GPU.
-    auto slot_of = [&](int set) {  // (everything recomputed here: nothing of this lives across the main loop)
-        const unsigned lane_in_grid = blockIdx.x * blockDim.x + threadIdx.x;
-        const unsigned wave_in_grid = lane_in_grid >> 6, lane_in_wave = lane_in_grid & 63u;
+    // (rtchunks::slot_of, for any lane of the workgroup: the chunked deal hands a lane the slots of the others)
+    auto slot_of = [&](int set, unsigned lane_in_wg) {  // (everything recomputed here: nothing of this lives across the main loop)
         // (the grid is a power of two: W is, shard counts divide it, and the host halves from there)
-        const unsigned b = (wave_in_grid + (wave_in_grid & 3u) * (unsigned)rot_wave + (unsigned)set * (unsigned)rot_set) &
-                           (((unsigned)lanes_in_grid >> 6) - 1u);
-        return set * lanes_in_grid + (int)(b * 64u + lane_in_wave);
+        return rtchunks::slot_of((unsigned)set, blockIdx.x * blockDim.x + lane_in_wg, (unsigned)lanes_in_grid, (unsigned)rot_wave, (unsigned)rot_set);
     };
     int slot_set = 0;
-    int i = slot_of(0);
+    int i = slot_of(0, threadIdx.x);
     // persistent slot state
     int bounces = kDone, pixel = 0, gen = 0;
     Rng rs{0, 0, 0, 0, 0, 0};
@@ -281,7 +297,7 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
         phase = PH_IDLE;
         tri = -1;
         slot_set++;
-        i = slot_of(slot_set);
+        i = slot_of(slot_set, threadIdx.x);
         if (i < ap_n) {
             load_slot(i);
             if (bounces != kDone && bounces != kParked) {
@@ -301,7 +317,11 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
     // an occluder is an occluder whenever it is found; the price is a few node visits a fresher tmax would have culled.
     int pend = kEntryDone;
     acc[0 * kBlock] = acc[1 * kBlock] = acc[2 * kBlock] = 0.f;
-    if (i < ap_n) {
+    if (chunk_start) {
+        i = ap_n;  // no slot yet: a lane in PH_GEN without a slot draws a task in the GEN block
+        phase = PH_GEN;
+        cold[12 * kBlock] = -1;
+    } else if (i < ap_n) {
         load_slot(i);
         phase = (bounces != kDone && bounces != kParked) ? (SPLIT_GEN ? PH_GEN : PH_ADV) : PH_IDLE;  // (untouched slots: bounces = INT_MAX)
         cold_save();
@@ -313,6 +333,9 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
     unsigned long long pf[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long pf_gen_cycles = 0, pf_fin_cycles = 0, pf_fin_lanes = 0, pf_fin_iters = 0;
     const unsigned long long pf_t0 = __builtin_readcyclecounter();
+    // per lane: the start (cycles since pf_t0) of the last fin section it left with work in hand; from there to the wave's
+    // exit the lane sits through whole-wave blocks that do nothing for it (the lane-idle tail)
+    unsigned long long pf_last_work = 0;
 #endif
 
     // The SIMD's issue arbiter prefers the OLDEST of its waves.  Left alone, the four waves of a SIMD (one from
@@ -405,6 +428,62 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
                     served += take;
                 }
             }
+            const unsigned chunk_g = CHUNKS ? __builtin_amdgcn_readfirstlane(s_task[1]) : 0u;
+            if (CHUNKS && chunk_g) {
+                const rtchunks::Multiple chunk_m{s_task[2], s_task[3], s_task[4]};
+                // A lane without a slot takes one; a lane whose slot stands at a chunk's end banks it (or keeps it, if another
+                // lane has left a claim) -- rt_slot_chunks.h.  Behind a wave vote: once per G camera rays of a lane.
+                bool need = phase == PH_GEN && i >= ap_n;
+                const bool at_end = phase == PH_GEN && i < ap_n &&
+                                    rtchunks::chunk_ends((unsigned)cold[2 * kBlock], chunk_m, cold[0 * kBlock] == kChunkFresh);
+                if (wave_ballot(need || at_end)) {
+                    if (at_end) {
+                        cold_load();
+                        // (a chain at its end is not banked: gen() below hands the slot back for good)
+                        const bool ends = gen == ap.last_gen || (long long)gen * kW + (ap.slot_lo + i) >= ap.cam_end;
+                        if (!ends) {
+                            acc_flush(acc, fb, ap_fb_fixed, pixel);  // the camera ray that ended: its sum -> its pixel
+                            bounces = ap_max_bounces;                // alive, starts with gen() (as k_pool_init leaves a slot)
+                            store_slot(i);
+                            const int old = __hip_atomic_fetch_add(&p.sem(i), 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+                            if (!rtchunks::runner_keeps(old)) {
+                                i = ap_n;
+                                need = true;
+                            }
+                        }
+                    }
+                    // slots per lane (lanes_in_grid divides the shard); a slot's chain in this kernel: generations 0 .. last_gen - 1
+                    const unsigned chunk_sets = (unsigned)ap_n / (unsigned)lanes_in_grid;
+                    const unsigned chunk_tasks = rtchunks::task_count(chunk_sets, (unsigned)ap.last_gen, (unsigned)chunk_g);
+                    // (every turn of this loop deals tasks: it ends when the lanes have a slot each or the tasks are out)
+                    unsigned long long m;
+                    while ((m = wave_ballot(need)) != 0ull) {
+                        unsigned base = 0;
+                        if (lane_id() == 0) base = atomicAdd(&s_task[0], (unsigned)__popcll(m));
+                        const unsigned t = __builtin_amdgcn_readfirstlane(base) + prefix_popc(m);
+                        if (need) {
+                            if (t >= chunk_tasks) {
+                                need = false;
+                                phase = PH_IDLE;  // out of tasks: this lane is done (i = ap_n)
+                            } else {
+                                const rtchunks::Entry e = rtchunks::task_entry(t, chunk_sets);
+                                const int k = slot_of((int)e.set, e.lane);
+                                const int old = k < ap_n ? __hip_atomic_fetch_sub(&p.sem(k), 1, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) : 0;
+                                if (rtchunks::taker_runs(old)) {
+                                    i = k;
+                                    load_slot(i);
+                                    cold_save();
+                                    // (gen() is the slot's next step whatever `bounces` says and overwrites it: until then the word
+                                    // marks the slot as fresh on this lane -- a bit of its own, not borrowed from the pixel stepping)
+                                    cold[0 * kBlock] = kChunkFresh;
+                                    cold[12 * kBlock] = -1;  // no previous pixel on this lane
+                                    need = false;
+                                }
+                            }
+                        }
+                    }
+                }
+            }
             if (phase == PH_GEN) {
                 SlotState st;
                 st.gen = cold[2 * kBlock];
@@ -447,8 +526,16 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
             sp = nr ? 0 : sp;
             if (wave_ballot(hand_back)) {  // rare (once per slot and frame): kept out of the merges above
                 if (hand_back) {
-                    if (draw_cids) phase = PH_IDLE;  // (the frame's counter has run out: nothing is tied to this lane's slot)
-                    else next_slot(PH_GEN);
+                    if (draw_cids) {
+                        phase = PH_IDLE;  // (the frame's counter has run out: nothing is tied to this lane's slot)
+                    } else if (CHUNKS && chunk_g) {
+                        cold_load();  // the slot is finished: its final state goes to the pools, the lane draws a task next
+                        store_slot(i);
+                        i = ap_n;
+                        tri = -1;
+                    } else {
+                        next_slot(PH_GEN);
+                    }
                 }
             }
             n_gen += wave_count((out.did_gen));
@@ -783,18 +870,31 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
         }
 #ifdef RT_TRACE_PROFILE
         pf_fin_cycles += __builtin_readcyclecounter() - pf_tf;
+        pf_last_work = phase != PH_IDLE ? pf_tf - pf_t0 : pf_last_work;
 #endif
     }
 #ifdef RT_TRACE_PROFILE
     if (prof && lane_id() == 0) { atomicAdd(&prof[17], pf_fin_cycles); atomicAdd(&prof[18], pf_fin_lanes); atomicAdd(&prof[19], pf_fin_iters); }
+    // the lane-idle tail: lane-cycles between each lane's last work and the wave's exit, and the longest of the 64 tails
+    // (= from the first lane going idle for good to the exit)
+    const unsigned long long pf_life = __builtin_readcyclecounter() - pf_t0;
+    unsigned long long pf_idle = pf_life - pf_last_work, pf_idle_max = pf_idle;
+    for (int off = 32; off > 0; off >>= 1) {
+        pf_idle += __shfl_xor(pf_idle, off);
+        const unsigned long long other = __shfl_xor(pf_idle_max, off);
+        pf_idle_max = other > pf_idle_max ? other : pf_idle_max;
+    }
     if (prof && lane_id() == 0)
-        { pf[11] = __builtin_readcyclecounter() - pf_t0; for (int k = 0; k < 16; k++) atomicAdd(&prof[k], pf[k]); atomicMax(&prof[13], pf[11]); atomicAdd(&prof[14], 1ull); atomicAdd(&prof[16], pf_gen_cycles);
+        { pf[11] = pf_life; for (int k = 0; k < 16; k++) atomicAdd(&prof[k], pf[k]); atomicMax(&prof[13], pf[11]); atomicAdd(&prof[14], 1ull); atomicAdd(&prof[16], pf_gen_cycles);
+          atomicAdd(&prof[20], pf_idle); atomicAdd(&prof[21], pf_idle_max);
           // per-wave record: where it ran and for how long
-          unsigned long long *rec = prof + 24 + 4 * (size_t)((blockIdx.x * kBlock + threadIdx.x) >> 6);
+          unsigned long long *rec = prof + 24 + kProfRec * (size_t)((blockIdx.x * kBlock + threadIdx.x) >> 6);
           rec[0] = __builtin_amdgcn_s_getreg((31 << 11) | 4);   // HW_ID
           rec[1] = __builtin_amdgcn_s_getreg((31 << 11) | 20);  // XCC_ID
           rec[2] = pf[11];
-          rec[3] = pf[0] + pf[2] + pf[4]; }
+          rec[3] = pf[0] + pf[2] + pf[4];
+          rec[4] = pf_idle;
+          rec[5] = pf_idle_max; }
 #endif
     unsigned long long v[C_COUNT] = {n_gen, n_shade, n_traced, n_shadow, n_emit, n_deposit, n_rr, 0ull};
     row_add(rows, v);

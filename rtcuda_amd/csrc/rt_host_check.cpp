@@ -13,6 +13,8 @@
 //   * rt_hostwalk_*     the same walk for arbitrary rays (closest hit / any hit), with work counters: the traversal
 //     audit (tests/test_traversal_audit.py) replays the rays of an oracle render through it.
 //   * rt_plan_paths_launch  the launch geometry of the persistent frame kernels (rt_launch_plan.h), as the library computes it.
+//   * rt_slot_chunk_*   the chunked deal of k_paths (rt_slot_chunks.h): task -> slot, the static deal's slots, the counts and
+//     the decisions, as the kernel makes them.
 #include <cfloat>
 #include <cmath>
 #include <cstdint>
@@ -25,6 +27,7 @@
 #include "rt_launch_plan.h"
 #include "rt_ploc.h"
 #include "rt_ref_tree.h"
+#include "rt_slot_chunks.h"
 
 namespace {
 struct V3 { float x, y, z; };
@@ -905,5 +908,26 @@ void rt_plan_paths_launch(int n, int cus, int wide, int n_nodes, int paths_cap, 
     const rtplan::PathsLaunch p = rtplan::plan_paths_launch(n, cus, wide != 0, n_nodes, paths_cap, lattice != 0, width, spp, (size_t)fixed_lds_bytes);
     const int64_t v[10] = {p.blocks, p.few_blocks, (int64_t)p.lds_bytes, p.top_n, p.adv_batch, p.gen_batch, p.tri_follow, p.prio_rotate, p.rot_wave, p.rot_set};
     memcpy(out10, v, sizeof(v));
+}
+// The chunked deal (tests/test_slot_chunks_host.py).  Tasks t0 .. t0 + count - 1 of workgroup `block`: the slot and the level of each.
+void rt_slot_chunk_tasks(int block, int sets, int lanes_in_grid, int rot_wave, int rot_set, uint32_t t0, int count, int32_t *slots, int32_t *levels) {
+    for (int k = 0; k < count; k++) {
+        const rtchunks::Entry e = rtchunks::task_entry(t0 + (uint32_t)k, (unsigned)sets);
+        slots[k] = rtchunks::slot_of(e.set, (unsigned)block * rtchunks::kLanes + e.lane, (unsigned)lanes_in_grid, (unsigned)rot_wave, (unsigned)rot_set);
+        levels[k] = (int32_t)e.level;
+    }
+}
+// the static deal: the slot of (set, lane of the grid)
+int rt_slot_chunk_static_slot(int set, int lane_in_grid, int lanes_in_grid, int rot_wave, int rot_set) {
+    return rtchunks::slot_of((unsigned)set, (unsigned)lane_in_grid, (unsigned)lanes_in_grid, (unsigned)rot_wave, (unsigned)rot_set);
+}
+uint32_t rt_slot_chunk_levels(uint32_t rays, uint32_t G) { return rtchunks::levels(rays, G); }
+uint32_t rt_slot_chunk_task_count(uint32_t sets, uint32_t rays, uint32_t G) { return rtchunks::task_count(sets, rays, G); }
+int rt_slot_chunk_ends(uint32_t gen, uint32_t G, int fresh) { return rtchunks::chunk_ends(gen, rtchunks::multiple_of(G), fresh != 0); }
+int rt_slot_chunk_taker_runs(int old_sem) { return rtchunks::taker_runs(old_sem); }
+int rt_slot_chunk_runner_keeps(int old_sem) { return rtchunks::runner_keeps(old_sem); }
+// G as the launch plan picks it for a frame whose slots run `chain` camera rays in k_paths (0: the static deal)
+int rt_plan_slot_chunk(int n, int cus, int chain) {
+    return rtplan::slot_chunk_for(rtplan::plan_paths_launch(n, cus, true, 70000, 10, true, 1920, 256, 0), chain);
 }
 }

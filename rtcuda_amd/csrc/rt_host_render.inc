@@ -159,6 +159,16 @@ static PathsKernel paths_kernel_of(bool few_blocks, bool per_sample, bool litera
     if (few_blocks) return verify ? k_paths<LDS_TABLES, WIDE, 2, false, false, true> : k_paths<LDS_TABLES, WIDE, 2, false, false, false>;
     return verify ? k_paths<LDS_TABLES, WIDE, 4, false, false, true> : k_paths<LDS_TABLES, WIDE, 4, false, false, false>;
 }
+// the same 4-waves-per-SIMD reference-mode builds with the chunked deal compiled in (k_paths_chunked: rt_slot_chunks.h)
+template <bool LDS_TABLES, bool WIDE>
+static PathsKernel paths_chunked_kernel_of(bool literal, bool verify) {
+    if (literal) return k_paths_chunked<LDS_TABLES, false, 4, false, true, false>;
+    return verify ? k_paths_chunked<LDS_TABLES, WIDE, 4, false, false, true> : k_paths_chunked<LDS_TABLES, WIDE, 4, false, false, false>;
+}
+static PathsKernel paths_chunked_kernel(bool lds_tables, bool wide, bool literal, bool verify) {
+    if (lds_tables) return (wide ? paths_chunked_kernel_of<true, true> : paths_chunked_kernel_of<true, false>)(literal, verify);
+    return (wide ? paths_chunked_kernel_of<false, true> : paths_chunked_kernel_of<false, false>)(literal, verify);
+}
 static PathsKernel paths_kernel(bool lds_tables, bool wide, bool few_blocks, bool per_sample, bool literal, bool verify) {
     if (lds_tables) return (wide ? paths_kernel_of<true, true> : paths_kernel_of<true, false>)(few_blocks, per_sample, literal, verify);
     return (wide ? paths_kernel_of<false, true> : paths_kernel_of<false, false>)(few_blocks, per_sample, literal, verify);
@@ -254,7 +264,7 @@ struct FrameRun {
     bool per_sample;
     HitMode mode;
     bool lds_tables = false, persistent = true, finished = false, ran_lockstep = false;
-    int cus = 0, stack_cap = 0, top_records_in_lds = 0, lock_enqueued = 0;
+    int cus = 0, stack_cap = 0, top_records_in_lds = 0, slot_chunk = 0, lock_enqueued = 0;
     DScene sc{};
     Camera cam{};
     AdvanceParams ap{};
@@ -299,17 +309,22 @@ static int report_paths_profile(unsigned long long *paths_prof, int paths_blocks
             h[12] ? (double)h[15] / h[12] : 0.0, 100.0 * h[16] / h[11], h[12] ? (double)h[16] / h[12] : 0.0);
     fprintf(stderr, "k_paths waves: %llu, mean lifetime %.0f cycles, longest %.0f cycles (x%.3f)\n", h[14], (double)h[11] / h[14], (double)h[13],
             (double)h[13] * h[14] / h[11]);
+    // lane-idle tail: per wave, the lane-cycles between each lane's last work and the wave's exit -- whole-wave blocks issued
+    // for lanes that have run out of slots -- as a share of wave time x 64; and the wave's longest such tail (from its first
+    // lane going idle for good to its exit)
+    fprintf(stderr, "k_paths lane-idle tail: %.2f %% of wave time x 64 lanes; a wave's first lane is idle for good %.2f %% of the wave's time before its exit\n",
+            100.0 * h[20] / (64.0 * h[11]), 100.0 * h[21] / h[11]);
     fprintf(stderr, "k_paths fin section: %.1f %% of wave time, entered in %llu iterations (avg %.1f finished lanes), %.0f cycles each\n",
             100.0 * h[17] / h[11], h[19], h[19] ? (double)h[18] / h[19] : 0.0, h[19] ? (double)h[17] / h[19] : 0.0);
     fprintf(stderr, "k_paths profile: ADV blocks %llu avg lanes %.1f | node steps %llu avg lanes %.1f (ADV-waiting %.1f) | tri steps %llu avg lanes %.1f (ADV-waiting %.1f)\n",
             h[0], h[0] ? (double)h[1] / h[0] : 0.0, h[2], h[2] ? (double)h[3] / h[2] : 0.0, h[2] ? (double)h[6] / h[2] : 0.0, h[4],
             h[4] ? (double)h[5] / h[4] : 0.0, h[4] ? (double)h[7] / h[4] : 0.0);
-    if (const char *dump = knob("RT_PROF_DUMP")) {  // per-wave records: hw_id xcc_id cycles blocks
-        std::vector<unsigned long long> recs(4 * (size_t)paths_blocks * (kBlock / 64));
+    if (const char *dump = knob("RT_PROF_DUMP")) {  // per-wave records: hw_id xcc_id cycles blocks idle_lane_cycles longest_lane_tail
+        std::vector<unsigned long long> recs(kProfRec * (size_t)paths_blocks * (kBlock / 64));
         HIP_TRY(hipMemcpy(recs.data(), paths_prof + 24, recs.size() * 8, hipMemcpyDeviceToHost));
         if (FILE *f = fopen(dump, "w")) {
-            for (size_t k = 0; k < recs.size(); k += 4)
-                fprintf(f, "%zu %llu %llu %llu %llu\n", k / 4, recs[k], recs[k + 1], recs[k + 2], recs[k + 3]);
+            for (size_t k = 0; k < recs.size(); k += kProfRec)
+                fprintf(f, "%zu %llu %llu %llu %llu %llu %llu\n", k / kProfRec, recs[k], recs[k + 1], recs[k + 2], recs[k + 3], recs[k + 4], recs[k + 5]);
             fclose(f);
         }
     }
@@ -337,7 +352,7 @@ int FrameRun::run_persistent() {
     top_records_in_lds = p.top_n;
     unsigned long long *paths_prof = nullptr;
 #ifdef RT_TRACE_PROFILE
-    const size_t prof_bytes = 192 + 32 * (size_t)(grid_for(c.n) * (kBlock / 64));
+    const size_t prof_bytes = 192 + 8 * kProfRec * (size_t)(grid_for(c.n) * (kBlock / 64));
     HIP_TRY(hipMalloc((void **)&paths_prof, prof_bytes));
     HIP_TRY(hipMemset(paths_prof, 0, prof_bytes));
 #endif
@@ -348,8 +363,14 @@ int FrameRun::run_persistent() {
     };
     HIP_TRY(hipEventRecord(c.ev_a, st));
     // (the reference-walk build is passed top_n = 0, while top_n * 64 bytes of LDS stay reserved and reported in reserved[2])
+    // (a chunk > 0 launches k_paths_chunked, 4-waves-per-SIMD reference-mode builds that keep no records in LDS: their `top_n`
+    // carries the chunk; a frame of one generation runs no chain in k_paths -- every slot parks at once -- and keeps the static
+    // deal, and so do ray tables)
+    const int chunk = (rays || p.few_blocks || per_sample || ap.last_gen < 1 || ap.n != c.n) ? 0 : rtplan::slot_chunk_for(p, ap.last_gen);
+    slot_chunk = chunk;
     if (rays && rays->keyed) launch_paths(paths_keyed_kernel(lds_tables, p.few_blocks), rays->keyed_table, p.top_n);
     else if (rays) launch_paths(paths_rays_kernel(lds_tables, p.few_blocks, mode.verify), rays->table, p.top_n);
+    else if (chunk > 0) launch_paths(paths_chunked_kernel(lds_tables, scene->wide, mode.literal, mode.verify), cam, chunk);
     else launch_paths(paths_kernel(lds_tables, scene->wide, p.few_blocks, per_sample, mode.literal, mode.verify), cam, mode.literal ? 0 : p.top_n);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(c.ev_b, st));
@@ -509,7 +530,7 @@ int FrameRun::frame_stats(rt_stats *stats) {
         stats->seconds_advance = 0.0;
         stats->launches_trace = 1;
         stats->reserved[0] = 1;
-        stats->reserved[1] = 1;
+        stats->reserved[1] = 1 + slot_chunk;
         stats->reserved[2] = top_records_in_lds;
     }
     rare_path_counters(h_final.vstat, &stats->reserved[4]);

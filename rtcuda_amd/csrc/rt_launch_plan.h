@@ -16,7 +16,18 @@ struct PathsLaunch {
     bool few_blocks;   // at most 2 per CU: the 2-waves-per-SIMD builds
     size_t lds_bytes;  // dynamic LDS of a workgroup
     int top_n, adv_batch, gen_batch, tri_follow, prio_rotate, rot_wave, rot_set;  // (see where they are set)
+    int slot_chunk;    // camera rays per task of the chunked deal (rt_slot_chunks.h); 0: the static deal; kSlotChunkAuto: by the
+                       // length of the frame's chains (slot_chunk_for)
 };
+// The hand-over costs the same per chunk whatever the frame, and what it buys -- the spread of the lanes' totals -- shrinks
+// relative to a lane's work as the chains get longer: the best chunk grows with the chain, kChunksPerSlot tasks per slot (the
+// sweeps on 506-, 1 012- and 2 025-ray chains: profiles/slot_chunks.md).  It wins 3 % at 506 rays, 0.6 % at 1 012 -- less than
+// what the kernel with the deal compiled in loses to the plain one on its common path -- and nothing at 2 025; chunks below
+// 48 rays put a hand-over into nearly every GEN block.  So by default the deal is used around the one chain length at which
+// it was timed, 506 rays: chains of kChunkChainLo .. kChunkChainHi rays (G = 48 .. 96), and every other frame runs the plain
+// kernel.  The two edges are NOT measured: they are the range of G that was flat at 506 rays (48 .. 96) turned into chain
+// lengths at 8 tasks per slot; the gain must fall to the loss seen at 1 012 rays somewhere above 506, possibly before 768.
+constexpr int kSlotChunkAuto = -1, kChunksPerSlot = 8, kChunkChainLo = 384, kChunkChainHi = 768;
 
 // `n`: slots of the shard; `paths_cap`: stack entries of a lane kept in LDS; `lattice`: the rays follow the camera's pixel
 // lattice (not a table's); `fixed_lds_bytes`: the shading tables (if staged in LDS) + the camera + the frame's parameters.
@@ -78,6 +89,20 @@ inline PathsLaunch plan_paths_launch(int n, int cus, bool wide, int n_nodes, int
         p.rot_wave &= ~3;  // keeps wave j of a workgroup on blocks = j (mod 4): the map stays a bijection
     }
     if (const char *e = knob("RT_PRIO_ROTATE")) p.prio_rotate = atoi(e);
+    // The 4-waves-per-SIMD reference-mode builds deal a workgroup's slots to its lanes a chunk of camera rays at a time
+    // (the caller drops it for ray tables, for per-sample streams and for frames of one generation, which never run a chain in
+    // k_paths).
+    // The lanes of the grid must divide the shard evenly: a workgroup's entries are (slot set, lane).
+    // With one slot per lane there is nothing to balance (a lane that runs ahead only leaves claims): the static deal, unless asked.
+    p.slot_chunk = (p.few_blocks || n / (p.blocks * kBlock) < 2) ? 0 : kSlotChunkAuto;
+    if (const char *e = knob("RT_SLOT_CHUNK")) p.slot_chunk = p.few_blocks ? 0 : std::max(0, std::min(1 << 20, atoi(e)));
+    if (n % (p.blocks * kBlock) != 0) p.slot_chunk = 0;
     return p;
+}
+// G for a frame whose slots run `chain` camera rays each inside k_paths (= the index of the final generation)
+inline int slot_chunk_for(const PathsLaunch &p, int chain) {
+    if (p.slot_chunk != kSlotChunkAuto) return p.slot_chunk;
+    if (chain < kChunkChainLo || chain > kChunkChainHi) return 0;
+    return (chain + kChunksPerSlot - 1) / kChunksPerSlot;
 }
 }  // namespace rtplan

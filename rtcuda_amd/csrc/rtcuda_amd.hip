@@ -72,6 +72,7 @@
 #include "rt_launch_plan.h"
 #include "rt_ploc.h"
 #include "rt_ref_tree.h"
+#include "rt_slot_chunks.h"
 
 using namespace rt;
 
@@ -151,7 +152,8 @@ __device__ __host__ inline int tab_off_lpre(int n_mats, int n_lights) { return 5
 //   pixel, gen        pixel of the current camera ray; index of the slot's NEXT generation
 //   rd, r0..r4        XORWOW state
 //   sox..slb, starget shadow ray of the slot for this round (stmax < 0: none) + radiance + excluded triangle
-enum { A_OX, A_OY, A_OZ, A_DX, A_DY, A_DZ, A_HPX, A_HPY, A_HPZ, A_HNX, A_HNY, A_HNZ, A_BR, A_BG, A_BB, A_SOX, A_SOY, A_SOZ, A_SDX, A_SDY, A_SDZ, A_STMAX, A_SLR, A_SLG, A_SLB, A_HIT_INFO, A_BOUNCES, A_PIXEL, A_GEN, A_STARGET, A_RD, A_R0, A_R1, A_R2, A_R3, A_R4, A_COUNT };
+//   sem               k_paths' chunked deal (rt_slot_chunks.h): 1 = the slot's state is stored here and no lane runs it
+enum { A_OX, A_OY, A_OZ, A_DX, A_DY, A_DZ, A_HPX, A_HPY, A_HPZ, A_HNX, A_HNY, A_HNZ, A_BR, A_BG, A_BB, A_SOX, A_SOY, A_SOZ, A_SDX, A_SDY, A_SDZ, A_STMAX, A_SLR, A_SLG, A_SLB, A_HIT_INFO, A_BOUNCES, A_PIXEL, A_GEN, A_STARGET, A_RD, A_R0, A_R1, A_R2, A_R3, A_R4, A_SEM, A_COUNT };
 struct DPools {
     float *base;
     int n;
@@ -191,6 +193,7 @@ struct DPools {
     __device__ __forceinline__ uint32_t &r2(int i) const { return ((uint32_t *)base)[(unsigned)(A_R2 * n + i)]; }
     __device__ __forceinline__ uint32_t &r3(int i) const { return ((uint32_t *)base)[(unsigned)(A_R3 * n + i)]; }
     __device__ __forceinline__ uint32_t &r4(int i) const { return ((uint32_t *)base)[(unsigned)(A_R4 * n + i)]; }
+    __device__ __forceinline__ int &sem(int i) const { return ((int *)base)[(unsigned)(A_SEM * n + i)]; }
     // host-side address of array k
     float *array(int k) const { return base + (size_t)k * n; }
 };
@@ -216,6 +219,7 @@ struct DWaveRow {
 
 constexpr int kDone = -0x7fffffff;    // slot has no camera ray left
 constexpr int kParked = -0x7ffffffe;  // slot waits for the lockstep rounds of the final generation
+constexpr int kChunkFresh = 0x7ffffffe;  // k_paths_chunked, in the lane's LDS copy of `bounces` only: the lane has taken the slot and made no ray of it yet
 
 // ============================================================================ wave helpers
 __device__ __forceinline__ unsigned lane_id() {
@@ -288,6 +292,7 @@ __global__ void k_pool_init(DPools p, int n, int max_bounces) {
     p.bounces(i) = max_bounces;
     p.gen(i) = 0;
     p.pixel(i) = 0;
+    p.sem(i) = 1;
 }
 
 // ============================================================================ k_advance
@@ -783,6 +788,10 @@ constexpr bool kSpeculate = RT_SPECULATE != 0;  // k_paths: postpone a leaf reac
 // RT_FRAME_SRC = Camera as k_advance / k_paths and with RT_FRAME_SRC = RayTable (rt_render_rays_*) as k_advance_rays /
 // k_paths_rays.  Two compilations of one text rather than a template parameter or a shared device function: the camera
 // builds keep their symbols, their arguments and -- instruction for instruction -- their code.
+#ifdef RT_TRACE_PROFILE
+constexpr int kProfRec = 6;  // qwords of k_paths' per-wave record (behind the 24 totals)
+#endif
+#define RT_PATHS_CHUNKS 0
 #define RT_FRAME_SRC Camera
 #define RT_K_ADVANCE k_advance
 #define RT_K_PATHS k_paths
@@ -806,6 +815,19 @@ constexpr bool kSpeculate = RT_SPECULATE != 0;  // k_paths: postpone a leaf reac
 #undef RT_FRAME_SRC
 #undef RT_K_ADVANCE
 #undef RT_K_PATHS
+// and once more for the camera with the chunked deal compiled in (rt_slot_chunks.h): k_paths_chunked, launched instead of the
+// 4-waves-per-SIMD reference-mode k_paths when the launch plan picks a chunk (its k_advance twin is never instantiated).  Ray
+// tables keep the static deal: no table frame has been timed with the deal.
+#undef RT_PATHS_CHUNKS
+#define RT_PATHS_CHUNKS 1
+#define RT_FRAME_SRC Camera
+#define RT_K_ADVANCE k_advance_chunked_unused
+#define RT_K_PATHS k_paths_chunked
+#include "rt_frame_kernels.inc"
+#undef RT_FRAME_SRC
+#undef RT_K_ADVANCE
+#undef RT_K_PATHS
+#undef RT_PATHS_CHUNKS
 
 // post_process_framebuffer (render.cuh:330-338): c = sqrt(c * (1/spp))
 __global__ void k_post_process(float *fb, int n_values, float inv_spp) {
