@@ -1,6 +1,13 @@
 // ============================================================================ host side
-// What the kernels read in leaf order, and the tree: a scene's own arrays (rt_scene_create, rt_scene_update) or new ones that
-// replace them once they are complete (rt_scene_rebuild).  Written by emit_scene.
+// The scene side of the host code is one path.  Whoever makes or replaces a tree -- rt_scene_create* with the host or the device
+// builder, rt_scene_set_triangles*, rt_scene_rebuild* -- does the same four things: a builder fills a TreeBuild
+// (build_sah_host, build_ploc_device), emit_tree allocates the leaf-order arrays for it and writes them (emit_scene),
+// adopt_tree waits and hands arrays, tree and host state to the scene.  The table edits (rt_scene_set_materials,
+// rt_scene_set_lights) fill the subset they replace and hand it over the same way: rt_scene::adopt is the one place where
+// the scene's device arrays change hands, FreshArrays the one owner of what is not adopted yet.
+//
+// What the kernels read in leaf order, and the tree: a scene's own arrays (rt_scene_update) or new ones that replace them
+// once they are complete (FreshArrays).  Written by emit_scene.
 struct SceneArrays {
     const int *order;          // leaf order -> caller's triangle index
     const rtbvh::Pair *recs;   // 4-wide: the builder's unpadded records
@@ -9,6 +16,30 @@ struct SceneArrays {
     int2 *info;
     Light *lights;
     float *tables;
+};
+// The arrays for a tree, or the subset an edit replaces, until the scene adopts them (rt_scene::adopt): freed here on every
+// early return, and after the adoption what is freed here is what the scene gave back.
+struct FreshArrays {
+    rtbvh::Pair *recs = nullptr;
+    int *order = nullptr;
+    float4 *nodes = nullptr, *tris = nullptr, *shade = nullptr;
+    int2 *info = nullptr;
+    Material *mats = nullptr;
+    Light *lights = nullptr;
+    float *tables = nullptr;
+    FreshArrays() = default;
+    FreshArrays(const FreshArrays &) = delete;
+    FreshArrays &operator=(const FreshArrays &) = delete;
+    ~FreshArrays() {
+        for (void *q : {(void *)recs, (void *)order, (void *)nodes, (void *)tris, (void *)shade, (void *)info, (void *)mats, (void *)lights, (void *)tables})
+            (void)hipFree(q);
+    }
+    template <typename T>
+    int alloc(T *&ptr, size_t count) {  // (ptr: one of the members)
+        HIP_TRY(hipMalloc((void **)&ptr, std::max<size_t>(count, 1) * sizeof(T)));
+        return 0;
+    }
+    SceneArrays view(int n_records) const { return {order, recs, n_records, nodes, tris, shade, info, lights, tables}; }
 };
 
 struct rt_scene {
@@ -25,7 +56,7 @@ struct rt_scene {
     mutable float origin_radius[3] = {0.f, 0.f, 0.f};
     mutable std::mutex pad_mutex;
     double build_seconds = 0.0;  // BVH build time (host wall clock, or device events for PLOC)
-    int builder = 0;             // 0 host SAH, 2 device PLOC (RT_SCENE_DEVICE_BVH, rt_scene_rebuild)
+    int builder = 0;             // 0 host SAH, 2 device PLOC (RT_SCENE_DEVICE_BVH, rt_scene_rebuild): TreeBuild::builder
     float4 *d_tris = nullptr;
     int2 *d_tri_info = nullptr;
     float4 *d_tri_shade = nullptr;
@@ -134,6 +165,22 @@ struct rt_scene {
         for (size_t k = 0; k < h_order.size(); k++) h_inverse[(size_t)h_order[k]] = (int)k;
     }
     SceneArrays arrays() const { return {d_order, d_recs, n_nodes, d_nodes, d_tris, d_tri_shade, d_tri_info, d_lights, d_tables}; }
+    // The one place where the scene's device arrays change hands: it takes what `f` holds, and `f` releases what it got back.
+    // (The caller has waited for the device work that wrote them, holds pad_mutex, and brings the host state along.)
+    void adopt(FreshArrays &f) {
+        auto take = [](auto *&mine, auto *&fresh) {
+            if (fresh) std::swap(mine, fresh);
+        };
+        take(d_recs, f.recs);
+        take(d_order, f.order);
+        take(d_nodes, f.nodes);
+        take(d_tris, f.tris);
+        take(d_tri_shade, f.shade);
+        take(d_tri_info, f.info);
+        take(d_mats, f.mats);
+        take(d_lights, f.lights);
+        take(d_tables, f.tables);
+    }
     DScene dev() const {
         DScene s;
         s.nodes = d_nodes;
@@ -221,7 +268,7 @@ const std::vector<uint32_t> &jump_powers() {
 //   (l.lo.x, r.lo.x, l.lo.y, r.lo.y | l.lo.z, r.lo.z, l.hi.x, r.hi.x | l.hi.y, r.hi.y, l.hi.z, r.hi.z | llink, rlink, spare, spare)
 // -- so that every (left, right) pair of bounds arrives in an aligned register pair and the slab arithmetic of both children
 // runs as packed fp32, see inner_step.  (The 4-wide layout is k_refit_emit's.)
-int upload_pairs(const rt_scene *sc, const std::vector<rtbvh::Pair> &pairs) {
+int upload_pairs(const std::vector<rtbvh::Pair> &pairs, float4 *d_nodes) {
     std::vector<float> inter(16 * pairs.size());
     for (size_t k = 0; k < pairs.size(); k++) {
         const rtbvh::Pair &pr = pairs[k];
@@ -234,7 +281,7 @@ int upload_pairs(const rt_scene *sc, const std::vector<rtbvh::Pair> &pairs) {
         memcpy(&r[13], &pr.rlink, 4);
         r[14] = r[15] = 0.f;
     }
-    HIP_TRY(hipMemcpy(sc->d_nodes, inter.data(), 64 * pairs.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_nodes, inter.data(), 64 * pairs.size(), hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -422,6 +469,25 @@ struct DevScope {
         return 0;
     }
 };
+// A host array into a temporary device buffer, ordered on `st`.  (The copy may still be reading `host` on return: a caller
+// whose `host` is not its own waits for `st` before it returns.)
+template <typename T>
+int stage(DevScope &tmp, const T *host, size_t count, hipStream_t st, const T *&d_out) {
+    T *d = nullptr;
+    if (tmp.alloc(d, count)) return 1;
+    HIP_TRY(hipMemcpyAsync(d, host, sizeof(T) * count, hipMemcpyHostToDevice, st));
+    d_out = d;
+    return 0;
+}
+// Is `p` device memory on `device`?  A host pointer is an error, not a fault.
+bool on_device(const void *p, int device) {
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, p) != hipSuccess || (attr.type != hipMemoryTypeDevice && !attr.isManaged) || attr.device != device) {
+        (void)hipGetLastError();  // (the failed query leaves its error behind)
+        return false;
+    }
+    return true;
+}
 // The scene's device made current for the rest of a host call; the caller's is restored on every return path
 struct DeviceGuard {
     int saved = 0, current = 0;
@@ -561,16 +627,25 @@ void rare_path_counters(const unsigned long long *vstat, int64_t out[3]) {
     out[2] = (int64_t)vstat[V_TIE];
 }
 
-// What emit_scene reads besides the vertices: the counts, the material table on the device, the lights on the host and --
-// for a new leaf order -- the caller's per-triangle indices on the device, in the caller's order (tri_light null: -1
-// everywhere).  The scene's own (rt_scene_update, rt_scene_rebuild) or those it is about to adopt (rt_scene_set_*).
+// What emit_scene reads besides the vertices: the counts, the material table on the device (null: none there yet, emit_tree
+// uploads h_mats), the lights on the host and -- for a new leaf order -- the caller's per-triangle indices on the device, in
+// the caller's order (tri_light null: -1 everywhere).  The scene's own (scene_source: rt_scene_create, rt_scene_update,
+// rt_scene_rebuild) or those it is about to adopt (rt_scene_set_triangles).
 struct EmitSource {
     int n_tris = 0, n_mats = 0, n_lights = 0;
     const Material *d_mats = nullptr;
+    const rt_material *h_mats = nullptr;
     const rt_light *h_lights = nullptr;
     const int *d_tri_material = nullptr, *d_tri_light = nullptr;
     const float *radius = nullptr;  // the origin radius the 4-wide nodes are padded for at least (3 floats)
 };
+
+// The shading tables of `n_mats` materials and `n_lights` lights (k_build_tables), ordered on `st`
+void launch_build_tables(const Material *d_mats, int n_mats, const Light *d_lights, int n_lights, const float4 *d_tris, float *d_tables,
+                         hipStream_t st) {
+    const int nt = std::max(std::max(n_mats, n_lights), 1);
+    hipLaunchKernelGGL(k_build_tables, dim3((nt + 63) / 64), dim3(64), 0, st, d_mats, n_mats, d_lights, n_lights, d_tris, d_tables);
+}
 
 // The one writer of the scene's leaf-order arrays, ordered on `st`, from the caller's vertices on the device (d_verts) and
 // the leaf order out.order: the triangle records (k_leaf_tris), the shading records and tables, and -- 4-wide -- the nodes
@@ -594,9 +669,7 @@ int emit_scene(const rt_scene *sc, const EmitSource &src, const float *d_verts, 
         hipLaunchKernelGGL(k_leaf_tris, grid, blk, 0, st, d_verts, out.order, n, out.tris);
         hipLaunchKernelGGL(k_build_tri_shade, grid, blk, 0, st, out.tris, out.info, n, out.shade);
     }
-    const int nt = std::max(std::max(src.n_mats, n_lights), 1);
-    hipLaunchKernelGGL(k_build_tables, dim3((nt + 63) / 64), dim3(64), 0, st, src.d_mats, src.n_mats, out.lights, n_lights, out.tris,
-                       out.tables);
+    launch_build_tables(src.d_mats, src.n_mats, out.lights, n_lights, out.tris, out.tables, st);
     if (!d_inverse)
         for (size_t l = 0; l < sc->refit_level_end.size(); l++) {
             const int begin = l ? sc->refit_level_end[l - 1] : 0, count = sc->refit_level_end[l] - begin;
@@ -610,24 +683,12 @@ int emit_scene(const rt_scene *sc, const EmitSource &src, const float *d_verts, 
 // The scene's own source.  For a new leaf order (`with_indices`) its per-triangle indices go to the device first, staged on
 // `st` into `tmp` from the host copies: every caller of emit_scene hands it device arrays, there is one emit path.
 int scene_source(const rt_scene *sc, bool with_indices, hipStream_t st, DevScope &tmp, EmitSource &src) {
-    src.n_tris = sc->n_tris;
-    src.n_mats = sc->n_mats;
-    src.n_lights = sc->n_lights;
-    src.d_mats = sc->d_mats;
-    src.h_lights = sc->h_lights.data();
-    src.radius = sc->origin_radius;
+    src = EmitSource{sc->n_tris, sc->n_mats, sc->n_lights, sc->d_mats, sc->h_materials.data(), sc->h_lights.data(), nullptr, nullptr,
+                     sc->origin_radius};
     if (!with_indices || sc->n_tris < 1) return 0;
     const size_t n = (size_t)sc->n_tris;
-    int *d_m = nullptr, *d_l = nullptr;
-    if (tmp.alloc(d_m, n)) return 1;
-    HIP_TRY(hipMemcpyAsync(d_m, sc->h_tri_material.data(), sizeof(int) * n, hipMemcpyHostToDevice, st));
-    if (!sc->h_tri_light.empty()) {
-        if (tmp.alloc(d_l, n)) return 1;
-        HIP_TRY(hipMemcpyAsync(d_l, sc->h_tri_light.data(), sizeof(int) * n, hipMemcpyHostToDevice, st));
-    }
-    src.d_tri_material = d_m;
-    src.d_tri_light = d_l;
-    return 0;
+    if (stage(tmp, sc->h_tri_material.data(), n, st, src.d_tri_material)) return 1;
+    return sc->h_tri_light.empty() ? 0 : stage(tmp, sc->h_tri_light.data(), n, st, src.d_tri_light);
 }
 
 // The start of rt_scene_update and rt_scene_rebuild: a device buffer of the caller's checked (on the scene's device), the
@@ -635,22 +696,11 @@ int scene_source(const rt_scene *sc, bool with_indices, hipStream_t st, DevScope
 // array (null: the scene's own copy) staged on `st` into `tmp`.
 int stage_vertices(const rt_scene *sc, const float *verts, bool device_ptr, hipStream_t st, const std::string &w, DeviceGuard &dev,
                    DevScope &tmp, const float *&d_verts) {
-    if (device_ptr && verts) {
-        hipPointerAttribute_t attr;
-        if (hipPointerGetAttributes(&attr, verts) != hipSuccess || (attr.type != hipMemoryTypeDevice && !attr.isManaged) ||
-            attr.device != sc->device) {
-            (void)hipGetLastError();  // (the failed query leaves its error behind)
-            return fail(w + ": d_tri_p0p1p2 is not device memory on the scene's device " + std::to_string(sc->device));
-        }
-    }
+    if (device_ptr && verts && !on_device(verts, sc->device))
+        return fail(w + ": d_tri_p0p1p2 is not device memory on the scene's device " + std::to_string(sc->device));
     if (dev.enter(sc->device)) return 1;
     d_verts = verts;
-    if (sc->n_tris > 0 && (!verts || !device_ptr)) {
-        float *d_v = nullptr;
-        if (tmp.alloc(d_v, 9 * (size_t)sc->n_tris)) return 1;
-        HIP_TRY(hipMemcpyAsync(d_v, verts ? verts : sc->h_tri9.data(), sizeof(float) * 9 * (size_t)sc->n_tris, hipMemcpyHostToDevice, st));
-        d_verts = d_v;
-    }
+    if (sc->n_tris > 0 && (!verts || !device_ptr)) return stage(tmp, verts ? verts : sc->h_tri9.data(), 9 * (size_t)sc->n_tris, st, d_verts);
     return 0;
 }
 
@@ -758,26 +808,58 @@ int scene_update_impl(rt_scene *sc, const float *verts, int n_tris, bool device_
     return 0;
 }
 
-// Device PLOC build (k_ploc_*) of n >= 1 triangles from d_verts on the current device, ordered on `st`: the unpadded 4-wide
-// records (breadth-first) and the leaf order, on the device (owned here) and copied to the host.  The host reads the cluster
-// count back after every iteration and the node count after every level.  Fails -- with nothing to undo -- if the tree does
-// not fit the traversal stack.
-struct PlocBuild {
-    rtbvh::Pair *d_recs = nullptr;
-    int *d_order = nullptr;
-    std::vector<rtbvh::Pair> quads;
+// A built tree, whichever builder made it: the unpadded 4-wide records and the leaf order, on the device (a.recs, a.order)
+// and on the host -- or, from the host builder only, the 2-wide records of the experiment format on the host (`pairs`: no
+// a.recs then; emit_tree uploads them as the nodes).  `a` also receives the leaf-order arrays emitted for the tree (emit_tree)
+// and owns all of them until the scene takes them (adopt_tree).
+struct TreeBuild {
+    FreshArrays a;
+    std::vector<rtbvh::Pair> quads, pairs;
     std::vector<int32_t> order;
     int max_depth = 0, stack_bound = 1, leaves = 0, iterations = 0;
-    double seconds = 0.0;  // device time of the build (HIP events)
-    PlocBuild() = default;
-    PlocBuild(const PlocBuild &) = delete;
-    PlocBuild &operator=(const PlocBuild &) = delete;
-    ~PlocBuild() {
-        (void)hipFree(d_recs);
-        (void)hipFree(d_order);
-    }
+    int builder = 2;       // rt_scene::builder
+    double seconds = 0.0;  // device time of the build (HIP events), or the host's wall clock
+    bool wide() const { return pairs.empty(); }
+    int n_records() const { return (int)(wide() ? quads.size() : pairs.size()); }  // 64-byte records
 };
-int build_ploc_device(const float *d_verts, int n, hipStream_t st, PlocBuild &out, const std::string &w) {
+
+// The host SAH builder (rtbvh::build) of n >= 0 triangles, checked and uploaded to the current device.  `wide`: 4-wide
+// wanted; a tree too deep for the 4-wide walk's stack comes out 2-wide.  `for_device`: what RT_SCENE_DEVICE_BVH gets for a scene
+// of no triangles, where there is nothing to build -- reported as the device builder's, in 0 seconds.
+int build_sah_host(const float *verts, int n, bool wide, bool for_device, TreeBuild &out) {
+    const auto t0 = std::chrono::steady_clock::now();
+    rtbvh::Result bvh = rtbvh::build(verts, n);
+    out.seconds = for_device ? 0.0 : std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    out.builder = for_device ? 2 : 0;
+    if (!bvh.ok) return fail("rt_scene_create: BVH build produced an unreferenceable leaf");
+    if (n > 0 && !bvh.quads.empty() && !validate_quads(bvh.quads, n))
+        return fail("rt_scene_create: the 4-wide BVH is malformed (structure, or an absent child without its +inf box)");
+    // a tree too deep for the 4-wide walk's stack (up to 3 entries per level) may still fit the 2-wide walk's (1 per level):
+    // a host tree the reinsertion pass deepened
+    if (wide && bvh.stack_bound > kMaxStackBound) wide = false;
+    if ((wide ? bvh.stack_bound : bvh.pair_depth + 1) > kMaxStackBound)
+        return fail("rt_scene_create: BVH depth " + std::to_string(wide ? bvh.max_depth : bvh.pair_depth) + " exceeds the traversal stack");
+    out.max_depth = wide ? bvh.max_depth : bvh.pair_depth;
+    out.stack_bound = wide ? bvh.stack_bound : bvh.pair_depth + 1;
+    out.leaves = bvh.num_leaves;
+    out.order = std::move(bvh.order);
+    if (out.a.alloc(out.a.order, (size_t)n)) return 1;
+    if (n) HIP_TRY(hipMemcpy(out.a.order, out.order.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
+    if (!wide) {
+        out.pairs = std::move(bvh.pairs);
+        return 0;
+    }
+    out.quads = std::move(bvh.quads);
+    if (out.a.alloc(out.a.recs, out.quads.size())) return 1;
+    HIP_TRY(hipMemcpy(out.a.recs, out.quads.data(), sizeof(rtbvh::Pair) * out.quads.size(), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// Device PLOC build (k_ploc_*) of n >= 1 triangles from d_verts on the current device, ordered on `st`: the unpadded 4-wide
+// records (breadth-first) and the leaf order, on the device and copied to the host.  The host reads the cluster
+// count back after every iteration and the node count after every level.  Fails -- with nothing to undo -- if the tree does
+// not fit the traversal stack.
+int build_ploc_device(const float *d_verts, int n, hipStream_t st, TreeBuild &out, const std::string &w) {
     if (n < 1) return fail(w + ": the device builder needs at least one triangle");
     int n_pad = 1;
     while (n_pad < n) n_pad <<= 1;
@@ -795,8 +877,7 @@ int build_ploc_device(const float *d_verts, int n, hipStream_t st, PlocBuild &ou
         tmp.alloc(d_sums, (size_t)nb) || tmp.alloc(d_tot, 4) || tmp.alloc(d_cl[0], (size_t)n) || tmp.alloc(d_cl[1], (size_t)n) ||
         tmp.alloc(d_lvl[0], cap_nodes) || tmp.alloc(d_lvl[1], cap_nodes))
         return 1;
-    HIP_TRY(hipMalloc((void **)&out.d_recs, sizeof(rtbvh::Pair) * 2 * cap_nodes));
-    HIP_TRY(hipMalloc((void **)&out.d_order, sizeof(int) * (size_t)n));
+    if (out.a.alloc(out.a.recs, 2 * cap_nodes) || out.a.alloc(out.a.order, (size_t)n)) return 1;
     HIP_TRY(hipEventCreate(&tmp.e0));
     HIP_TRY(hipEventCreate(&tmp.e1));
     HIP_TRY(hipEventRecord(tmp.e0, st));
@@ -859,8 +940,8 @@ int build_ploc_device(const float *d_verts, int n, hipStream_t st, PlocBuild &ou
         HIP_TRY(hipStreamSynchronize(st));
         const int next_base = base + count;
         if (tot[0] < 0 || (size_t)next_base + (size_t)tot[0] > cap_nodes) return fail(w + ": the 4-wide collapse overran its node count");
-        hipLaunchKernelGGL(k_ploc_level_emit, dim3(cb), blk, 0, st, d_lvl[lv], count, base, next_base, d_sums, nd, out.d_recs,
-                           d_lvl[lv ^ 1], out.d_order, d_tot + 2);
+        hipLaunchKernelGGL(k_ploc_level_emit, dim3(cb), blk, 0, st, d_lvl[lv], count, base, next_base, d_sums, nd, out.a.recs,
+                           d_lvl[lv ^ 1], out.a.order, d_tot + 2);
         HIP_TRY(hipGetLastError());
         base = next_base;
         count = tot[0];
@@ -876,15 +957,15 @@ int build_ploc_device(const float *d_verts, int n, hipStream_t st, PlocBuild &ou
     if (err) return fail(w + ": the device-built tree has a leaf that cannot be referenced");
     out.quads.resize(2 * (size_t)base);
     out.order.resize((size_t)n);
-    HIP_TRY(hipMemcpy(out.quads.data(), out.d_recs, sizeof(rtbvh::Pair) * out.quads.size(), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out.order.data(), out.d_order, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out.quads.data(), out.a.recs, sizeof(rtbvh::Pair) * out.quads.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out.order.data(), out.a.order, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
     out.stack_bound = 3 * out.max_depth + 1;
     out.leaves = 0;
     for (const rtbvh::Pair &p : out.quads) out.leaves += (p.llink < 0 && p.llink != rtbvh::kNoChild) + (p.rlink < 0 && p.rlink != rtbvh::kNoChild);
     return 0;
 }
-// What the scene may adopt from a build: a well-formed tree over a permutation of its triangles, within the stack
-bool ploc_result_ok(const PlocBuild &b, int n) {
+// What the scene may adopt from a device build: a well-formed tree over a permutation of its triangles, within the stack
+bool ploc_result_ok(const TreeBuild &b, int n) {
     if (b.stack_bound > kMaxStackBound || !validate_quads(b.quads, n) || (int)b.order.size() != n) return false;
     std::vector<char> seen((size_t)n, 0);
     for (int32_t i : b.order) {
@@ -894,24 +975,115 @@ bool ploc_result_ok(const PlocBuild &b, int n) {
     return true;
 }
 
-// The scene takes a device build's tree: the records and the leaf order on the device (b frees the scene's old ones) and
-// their host copies
-void adopt_tree(rt_scene *sc, PlocBuild &b) {
-    std::swap(sc->d_recs, b.d_recs);
-    std::swap(sc->d_order, b.d_order);
+// ---- the one tail after "a tree exists", in two halves (rt_scene_rebuild launches its own kernel between them)
+// The emit half: the leaf-order arrays for the tree `b`, allocated for its size into b.a and written from `src` and the
+// vertices on the device (emit_scene; 2-wide: the nodes are the builder's pairs), ordered on `st`.  A scene that has no
+// material table on the device yet gets the host's.  `d_inverse`: the inverse of the new leaf order, scratch in `tmp`.  The
+// caller holds pad_mutex and has made the scene's device current; the scene still renders its old bits.
+int emit_tree(rt_scene *sc, TreeBuild &b, EmitSource &src, const float *d_verts, hipStream_t st, DevScope &tmp, int *&d_inverse) {
+    FreshArrays &a = b.a;
+    const size_t n = (size_t)src.n_tris;
+    if (a.alloc(a.nodes, 4 * (size_t)b.n_records()) || a.alloc(a.tris, 3 * n) || a.alloc(a.shade, n) || a.alloc(a.info, n) ||
+        a.alloc(a.lights, (size_t)src.n_lights) || a.alloc(a.tables, (size_t)tab_dwords(src.n_mats, src.n_lights)) || tmp.alloc(d_inverse, n))
+        return 1;
+    if (!src.d_mats) {
+        if (a.alloc(a.mats, (size_t)src.n_mats)) return 1;
+        if (src.n_mats) HIP_TRY(hipMemcpyAsync(a.mats, src.h_mats, sizeof(Material) * (size_t)src.n_mats, hipMemcpyHostToDevice, st));
+        src.d_mats = a.mats;
+    }
+    if (!sc->d_radius) HIP_TRY(hipMalloc((void **)&sc->d_radius, sizeof(float) * 3));  // (scratch of emit_nodes: a scene just made)
+    if (!b.wide() && upload_pairs(b.pairs, a.nodes)) return 1;
+    return emit_scene(sc, src, d_verts, a.view(b.n_records()), d_inverse, st);
+}
+// The adopt half: wait for `st`, then the scene takes the arrays, the tree and what the host knows of both -- the counts of
+// `src`, the radius the 4-wide nodes were padded for.  What belongs to the old tree goes (the refit levels, the queries'
+// inverse order); the SAH baselines are the new tree's.  Until the wait has succeeded the scene is untouched.
+int adopt_tree(rt_scene *sc, TreeBuild &b, const EmitSource &src, hipStream_t st) {
+    float radius[3] = {0.f, 0.f, 0.f};
+    if (b.wide()) HIP_TRY(hipMemcpyAsync(radius, sc->d_radius, sizeof(radius), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    sc->adopt(b.a);
+    sc->n_nodes = b.n_records();
     sc->h_quads = std::move(b.quads);
     sc->set_order(b.order);
     sc->drop_query_inverse();
-    sc->n_nodes = (int)sc->h_quads.size();
     sc->max_depth = b.max_depth;
     sc->stack_bound = b.stack_bound;
     sc->n_leaves = b.leaves;
-    sc->builder = 2;
+    sc->builder = b.builder;
     sc->build_seconds = b.seconds;
+    sc->n_tris = src.n_tris;
+    sc->n_mats = src.n_mats;
+    sc->n_lights = src.n_lights;
+    sc->tab_dwords = tab_dwords(src.n_mats, src.n_lights);
+    for (int k = 0; k < 3; k++) sc->origin_radius[k] = radius[k];
+    sc->drop_refit();
+    sc->sah_build = sc->sah_now = quads_sah(sc->h_quads);
+    return 0;
+}
+
+// A new, empty scene on the current device (RT_BVH_WIDE=0: the 2-wide experiment format)
+int new_scene(std::unique_ptr<rt_scene> &sc) {
+    sc = std::make_unique<rt_scene>();
+    HIP_TRY(hipGetDevice(&sc->device));
+    sc->wide = true;  // 4-wide nodes (two pair-style records each): half the dependent fetches per ray; RT_BVH_WIDE=0: 2-wide
+    if (const char *e = knob("RT_BVH_WIDE")) sc->wide = atoi(e) != 0;
+    return 0;
+}
+
+static_assert(sizeof(Light) == sizeof(rt_light), "light layout");
+static_assert(sizeof(Material) == sizeof(rt_material), "material layout");
+static_assert(sizeof(Camera) == sizeof(rt_camera), "camera layout");
+
+// rt_scene_create / rt_scene_create_flags: a scene of any count of triangles from host arrays, its tree from the host SAH
+// builder or (RT_SCENE_DEVICE_BVH) the device builder, on the current device and the null stream.  An error on the way
+// frees the scene with everything it holds.
+int scene_create_impl(const float *tri_p0p1p2, int n_tris, const int32_t *tri_material, const int32_t *tri_light, const rt_material *materials,
+                      int n_materials, const rt_light *lights, int n_lights, uint32_t scene_flags, rt_scene **out_scene) {
+    if (!out_scene) return fail("rt_scene_create: out_scene is null");
+    if (scene_flags & ~(uint32_t)RT_SCENE_DEVICE_BVH) return fail("rt_scene_create_flags: unknown scene flags");
+    const bool device_bvh = (scene_flags & RT_SCENE_DEVICE_BVH) != 0;
+    *out_scene = nullptr;
+    if (check_scene_counts("rt_scene_create", n_tris, n_tris <= 0 || (tri_p0p1p2 && tri_material), materials, n_materials, lights, n_lights) ||
+        check_tri_indices("rt_scene_create", n_tris, tri_material, tri_light, n_materials, n_lights) ||
+        check_scene_tables("rt_scene_create", n_tris, materials, n_materials, lights, n_lights))
+        return 1;
+    std::unique_ptr<rt_scene> sc;
+    if (new_scene(sc)) return 1;
+    if (device_bvh && !sc->wide) return fail("rt_scene_create_flags: the device builder writes the 4-wide format only (RT_BVH_WIDE=0 is set)");
+    // the host mirrors first: the source of the emit is the scene's own (scene_source)
+    sc->n_tris = n_tris;
+    sc->n_lights = n_lights;
+    sc->n_mats = n_materials;
+    if (n_tris > 0) sc->h_tri9.assign(tri_p0p1p2, tri_p0p1p2 + 9 * (size_t)n_tris);  // (RT_FLAG_REFERENCE_WALK builds its tree from these)
+    if (n_tris > 0) sc->h_tri_material.assign(tri_material, tri_material + n_tris);
+    if (n_tris > 0 && tri_light) sc->h_tri_light.assign(tri_light, tri_light + n_tris);
+    if (n_materials > 0) sc->h_materials.assign(materials, materials + n_materials);
+    if (n_lights > 0) sc->h_lights.assign(lights, lights + n_lights);
+    sc->note_index_maxima();
+    DevScope tmp;
+    const float *d_verts = nullptr;
+    if (n_tris > 0 && stage(tmp, tri_p0p1p2, 9 * (size_t)n_tris, nullptr, d_verts)) return 1;
+    TreeBuild b;
+    if (device_bvh && n_tris > 0) {
+        if (build_ploc_device(d_verts, n_tris, nullptr, b, "rt_scene_create_flags")) return 1;
+        if (!ploc_result_ok(b, n_tris)) return fail("rt_scene_create_flags: the device-built tree is malformed");
+    } else if (build_sah_host(tri_p0p1p2, n_tris, sc->wide, device_bvh, b)) {
+        return 1;
+    }
+    sc->wide = b.wide();
+    EmitSource src;
+    int *d_inverse = nullptr;
+    if (scene_source(sc.get(), true, nullptr, tmp, src) || emit_tree(sc.get(), b, src, d_verts, nullptr, tmp, d_inverse) ||
+        adopt_tree(sc.get(), b, src, nullptr))
+        return 1;
+    HIP_TRY(hipDeviceSynchronize());
+    *out_scene = sc.release();
+    return 0;
 }
 
 // rt_scene_rebuild / rt_scene_rebuild_device: a new tree for the scene's current or new vertices (build_ploc_device), and
-// everything the kernels index in leaf order re-emitted on the device from the new order (emit_scene), into new buffers that
+// everything the kernels index in leaf order re-emitted on the device from the new order (emit_tree), into new buffers that
 // replace the scene's only once the tree has passed its checks.  `verts`: null (the scene's own vertices), a host array or
 // (device_ptr) a buffer on the scene's device.
 int scene_rebuild_impl(rt_scene *sc, const float *verts, int n_tris, bool device_ptr, hipStream_t st, const char *what) {
@@ -937,45 +1109,24 @@ int scene_rebuild_impl(rt_scene *sc, const float *verts, int n_tris, bool device
         }
     }
     const bool moved = verts && memcmp(h_new.data(), sc->h_tri9.data(), sizeof(float) * h_new.size()) != 0;
-    PlocBuild b;
+    TreeBuild b;
     if (build_ploc_device(d_verts, n, st, b, w)) return 1;
     if (!ploc_result_ok(b, n)) return fail(w + ": the device-built tree is malformed; the scene is unchanged");
-    // the scene's leaf-order arrays for the new tree, into new buffers
-    SceneArrays a{b.d_order, b.d_recs, (int)b.quads.size()};
-    int *d_inverse = nullptr, *d_ref_prims = nullptr, *d_ref_leaf_of = nullptr;
-    DevScope fresh;  // (released unless adopted below)
+    // the reference's tree is a function of the triangles: kept (renumbered for the new leaf order) unless they moved
     const bool keep_ref = sc->ref_ready && !moved;
-    if (fresh.alloc(a.nodes, 4 * (size_t)a.n_records) || fresh.alloc(a.tris, 3 * (size_t)n) || fresh.alloc(a.shade, (size_t)n) ||
-        fresh.alloc(a.info, (size_t)n) || fresh.alloc(a.lights, (size_t)std::max(sc->n_lights, 1)) ||
-        fresh.alloc(a.tables, (size_t)std::max(sc->tab_dwords, 1)) || tmp.alloc(d_inverse, (size_t)n) ||
-        (keep_ref && (fresh.alloc(d_ref_prims, (size_t)n) || fresh.alloc(d_ref_leaf_of, (size_t)n))))
-        return 1;
+    int *d_inverse = nullptr, *d_ref_prims = nullptr, *d_ref_leaf_of = nullptr;
+    DevScope ref;  // (released unless adopted below)
+    if (keep_ref && (ref.alloc(d_ref_prims, (size_t)n) || ref.alloc(d_ref_leaf_of, (size_t)n))) return 1;
     EmitSource src;
-    if (scene_source(sc, true, st, tmp, src)) return 1;
-    if (emit_scene(sc, src, d_verts, a, d_inverse, st)) return 1;
+    if (scene_source(sc, true, st, tmp, src) || emit_tree(sc, b, src, d_verts, st, tmp, d_inverse)) return 1;
     if (keep_ref)
         hipLaunchKernelGGL(k_ploc_remap_ref, dim3((n + 255) / 256), dim3(256), 0, st, sc->d_ref_prims, sc->d_ref_leaf_of, sc->d_order,
                            d_inverse, n, d_ref_prims, d_ref_leaf_of);
     HIP_TRY(hipGetLastError());
-    float radius[3];
-    HIP_TRY(hipMemcpyAsync(radius, sc->d_radius, sizeof(radius), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    // adopt: the new buffers replace the old ones, the host state follows
-    fresh.ptrs.clear();
-    std::swap(sc->d_nodes, a.nodes);
-    std::swap(sc->d_tris, a.tris);
-    std::swap(sc->d_tri_shade, a.shade);
-    std::swap(sc->d_tri_info, a.info);
-    std::swap(sc->d_lights, a.lights);
-    std::swap(sc->d_tables, a.tables);
-    for (void *q : {(void *)a.nodes, (void *)a.tris, (void *)a.shade, (void *)a.info, (void *)a.lights, (void *)a.tables}) (void)hipFree(q);
-    adopt_tree(sc, b);
-    for (int k = 0; k < 3; k++) sc->origin_radius[k] = radius[k];
-    sc->drop_refit();
-    sc->sah_build = sc->sah_now = quads_sah(sc->h_quads);
-    // the reference's tree is a function of the triangles: kept (renumbered for the new leaf order) unless they moved
+    if (adopt_tree(sc, b, src, st)) return 1;
     if (keep_ref) {
         std::lock_guard<std::mutex> lock(sc->ref_mutex);
+        ref.ptrs.clear();
         std::swap(sc->d_ref_prims, d_ref_prims);
         std::swap(sc->d_ref_leaf_of, d_ref_leaf_of);
         (void)hipFree(d_ref_prims);
@@ -992,16 +1143,6 @@ int scene_rebuild_impl(rt_scene *sc, const float *verts, int n_tris, bool device
 // Every one builds what changes into fresh buffers, waits for the device, and only then adopts them: an error on the way
 // leaves the scene rendering its old bits.
 
-// Is `p` device memory on `device` (as stage_vertices asks of the vertices)?  A host pointer is an error, not a fault.
-bool on_device(const void *p, int device) {
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, p) != hipSuccess || (attr.type != hipMemoryTypeDevice && !attr.isManaged) || attr.device != device) {
-        (void)hipGetLastError();  // (the failed query leaves its error behind)
-        return false;
-    }
-    return true;
-}
-
 // A new material table.  Nothing in leaf order depends on it: the table on the device and the shading tables are re-made
 // (k_build_tables, for the new count), the tree, the records, the refit state and the reference's tree stay.
 int scene_set_materials_impl(rt_scene *sc, const rt_material *materials, int n_materials) {
@@ -1016,24 +1157,16 @@ int scene_set_materials_impl(rt_scene *sc, const rt_material *materials, int n_m
     std::lock_guard<std::mutex> pad_lock(sc->pad_mutex);
     DeviceGuard dev;
     if (dev.enter(sc->device)) return 1;
-    DevScope fresh;  // (released unless adopted below)
-    Material *d_mats = nullptr;
-    float *d_tables = nullptr;
-    const int tab_dwords = 5 * n_materials + 24 * sc->n_lights;
-    if (fresh.alloc(d_mats, (size_t)n_materials) || fresh.alloc(d_tables, (size_t)tab_dwords)) return 1;
-    if (n_materials) HIP_TRY(hipMemcpy(d_mats, materials, sizeof(Material) * (size_t)n_materials, hipMemcpyHostToDevice));
-    const int nt = std::max(std::max(n_materials, sc->n_lights), 1);
-    hipLaunchKernelGGL(k_build_tables, dim3((nt + 63) / 64), dim3(64), 0, nullptr, d_mats, n_materials, sc->d_lights, sc->n_lights,
-                       sc->d_tris, d_tables);
+    FreshArrays a;
+    const int n_tab = tab_dwords(n_materials, sc->n_lights);
+    if (a.alloc(a.mats, (size_t)n_materials) || a.alloc(a.tables, (size_t)n_tab)) return 1;
+    if (n_materials) HIP_TRY(hipMemcpy(a.mats, materials, sizeof(Material) * (size_t)n_materials, hipMemcpyHostToDevice));
+    launch_build_tables(a.mats, n_materials, sc->d_lights, sc->n_lights, sc->d_tris, a.tables, nullptr);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(nullptr));
-    fresh.ptrs.clear();
-    std::swap(sc->d_mats, d_mats);
-    std::swap(sc->d_tables, d_tables);
-    (void)hipFree(d_mats);
-    (void)hipFree(d_tables);
+    sc->adopt(a);
     sc->n_mats = n_materials;
-    sc->tab_dwords = tab_dwords;
+    sc->tab_dwords = n_tab;
     sc->h_materials.assign(materials, materials + n_materials);
     sc->drop_replicas();
     return 0;
@@ -1058,41 +1191,24 @@ int scene_set_lights_impl(rt_scene *sc, const rt_light *lights, int n_lights, co
     std::vector<rt_light> leaf_lights(lights, lights + n_lights);
     for (rt_light &l : leaf_lights)
         if (l.type == RT_AREA_LIGHT) l.triangle = sc->h_inverse[(size_t)l.triangle];
-    DevScope fresh, tmp;  // (fresh: released unless adopted below)
-    Light *d_lights = nullptr;
-    float *d_tables = nullptr;
-    int2 *d_info = nullptr;
-    float4 *d_shade = nullptr;
-    const int tab_dwords = 5 * sc->n_mats + 24 * n_lights;
-    if (fresh.alloc(d_lights, (size_t)n_lights) || fresh.alloc(d_tables, (size_t)tab_dwords)) return 1;
-    if (n_lights) HIP_TRY(hipMemcpy(d_lights, leaf_lights.data(), sizeof(Light) * (size_t)n_lights, hipMemcpyHostToDevice));
-    const bool assign = tri_light && n > 0;
-    if (assign) {
-        int *d_tl = nullptr;
-        if (fresh.alloc(d_info, (size_t)n) || fresh.alloc(d_shade, (size_t)n) || tmp.alloc(d_tl, (size_t)n)) return 1;
-        HIP_TRY(hipMemcpy(d_tl, tri_light, sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
+    FreshArrays a;
+    DevScope tmp;
+    const int n_tab = tab_dwords(sc->n_mats, n_lights);
+    if (a.alloc(a.lights, (size_t)n_lights) || a.alloc(a.tables, (size_t)n_tab)) return 1;
+    if (n_lights) HIP_TRY(hipMemcpy(a.lights, leaf_lights.data(), sizeof(Light) * (size_t)n_lights, hipMemcpyHostToDevice));
+    if (tri_light && n > 0) {
+        const int *d_tl = nullptr;
+        if (a.alloc(a.info, (size_t)n) || a.alloc(a.shade, (size_t)n) || stage(tmp, tri_light, (size_t)n, nullptr, d_tl)) return 1;
         const dim3 blk(256), grid((n + 255) / 256);
-        hipLaunchKernelGGL(k_leaf_tri_light, grid, blk, 0, nullptr, sc->d_tri_info, d_tl, sc->d_order, n, d_info);
-        hipLaunchKernelGGL(k_build_tri_shade, grid, blk, 0, nullptr, sc->d_tris, d_info, n, d_shade);
+        hipLaunchKernelGGL(k_leaf_tri_light, grid, blk, 0, nullptr, sc->d_tri_info, d_tl, sc->d_order, n, a.info);
+        hipLaunchKernelGGL(k_build_tri_shade, grid, blk, 0, nullptr, sc->d_tris, a.info, n, a.shade);
     }
-    const int nt = std::max(std::max(sc->n_mats, n_lights), 1);
-    hipLaunchKernelGGL(k_build_tables, dim3((nt + 63) / 64), dim3(64), 0, nullptr, sc->d_mats, sc->n_mats, d_lights, n_lights, sc->d_tris,
-                       d_tables);
+    launch_build_tables(sc->d_mats, sc->n_mats, a.lights, n_lights, sc->d_tris, a.tables, nullptr);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(nullptr));
-    fresh.ptrs.clear();
-    std::swap(sc->d_lights, d_lights);
-    std::swap(sc->d_tables, d_tables);
-    (void)hipFree(d_lights);
-    (void)hipFree(d_tables);
-    if (assign) {
-        std::swap(sc->d_tri_info, d_info);
-        std::swap(sc->d_tri_shade, d_shade);
-        (void)hipFree(d_info);
-        (void)hipFree(d_shade);
-    }
+    sc->adopt(a);
     sc->n_lights = n_lights;
-    sc->tab_dwords = tab_dwords;
+    sc->tab_dwords = n_tab;
     sc->h_lights.assign(lights, lights + n_lights);
     if (tri_light) {
         sc->h_tri_light.assign(tri_light, tri_light + n);
@@ -1105,7 +1221,7 @@ int scene_set_lights_impl(rt_scene *sc, const rt_light *lights, int n_lights, co
 // A new triangle set for the scene (or the first one of a scene just made: rt_scene_create_device): any count >= 1, with
 // its per-triangle indices and the tables they index.  The three per-triangle arrays are host arrays, uploaded first, or
 // (device_ptr) buffers on the scene's device, whose index ranges are then checked there (k_index_prepass); from then on
-// there is one path: the device build, every record emitted into buffers of the new size, the host mirrors, the adoption.
+// there is one path: the device build, the tail every tree goes through (emit_tree, adopt_tree), the host mirrors.
 int scene_set_triangles_impl(rt_scene *sc, const float *verts, int n_tris, const int32_t *tri_material, const int32_t *tri_light,
                              const rt_material *materials, int n_materials, const rt_light *lights, int n_lights, bool device_ptr,
                              hipStream_t st, const char *what) {
@@ -1127,30 +1243,25 @@ int scene_set_triangles_impl(rt_scene *sc, const float *verts, int n_tris, const
     if (dev.enter(sc->device)) return 1;
     DevScope tmp;
     const size_t n = (size_t)n_tris;
+    const float none[3] = {0.f, 0.f, 0.f};  // the new tree's own radius, as at creation: the old triangles' says nothing
     const float *d_verts = verts;
-    const int *d_m = tri_material, *d_l = tri_light;
+    EmitSource src{n_tris, n_materials, n_lights, nullptr, materials, lights, tri_material, tri_light, none};  // (d_mats null: a new table)
     std::vector<float> h_tri9(9 * n);
     std::vector<int32_t> h_mat(n), h_light(tri_light ? n : 0);
     if (!device_ptr) {
-        float *uv = nullptr;
-        int *um = nullptr, *ul = nullptr;
-        if (tmp.alloc(uv, 9 * n) || tmp.alloc(um, n) || (tri_light && tmp.alloc(ul, n))) return 1;
-        HIP_TRY(hipMemcpyAsync(uv, verts, sizeof(float) * 9 * n, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(um, tri_material, sizeof(int) * n, hipMemcpyHostToDevice, st));
-        if (tri_light) HIP_TRY(hipMemcpyAsync(ul, tri_light, sizeof(int) * n, hipMemcpyHostToDevice, st));
-        d_verts = uv;
-        d_m = um;
-        d_l = ul;
+        if (stage(tmp, verts, 9 * n, st, d_verts) || stage(tmp, tri_material, n, st, src.d_tri_material) ||
+            (tri_light && stage(tmp, tri_light, n, st, src.d_tri_light)))
+            return 1;
         memcpy(h_tri9.data(), verts, sizeof(float) * 9 * n);
         memcpy(h_mat.data(), tri_material, sizeof(int32_t) * n);
         if (tri_light) memcpy(h_light.data(), tri_light, sizeof(int32_t) * n);
-        HIP_TRY(hipStreamSynchronize(st));  // (the caller's arrays are his again on return whatever happens below)
+        HIP_TRY(hipStreamSynchronize(st));  // (the caller's arrays are their own again on return whatever happens below)
     } else {
         unsigned *d_words = nullptr, words[2] = {0, 0};
         if (tmp.alloc(d_words, 2)) return 1;
         HIP_TRY(hipMemsetAsync(d_words, 0, sizeof(words), st));
-        hipLaunchKernelGGL(k_index_prepass, dim3((unsigned)std::min<size_t>((n + kBlock - 1) / kBlock, 1024)), dim3(kBlock), 0, st, d_m, d_l,
-                           n_tris, n_materials, n_lights, d_words);
+        hipLaunchKernelGGL(k_index_prepass, dim3((unsigned)std::min<size_t>((n + kBlock - 1) / kBlock, 1024)), dim3(kBlock), 0, st,
+                           src.d_tri_material, src.d_tri_light, n_tris, n_materials, n_lights, d_words);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(words, d_words, sizeof(words), hipMemcpyDeviceToHost, st));
         // the host mirrors: what the reference's tree and rt_render_multi replicas are made from, one copy per array
@@ -1162,53 +1273,11 @@ int scene_set_triangles_impl(rt_scene *sc, const float *verts, int n_tris, const
             return fail(w + ": " + std::to_string(words[0]) + " of " + std::to_string(n_tris) + " triangles have d_tri_material out of range and " +
                         std::to_string(words[1]) + " have d_tri_light out of range");
     }
-    PlocBuild b;
+    TreeBuild b;
     if (build_ploc_device(d_verts, n_tris, st, b, w)) return 1;
     if (!ploc_result_ok(b, n_tris)) return fail(w + ": the device-built tree is malformed; the scene is unchanged");
-    SceneArrays a{b.d_order, b.d_recs, (int)b.quads.size()};
-    Material *d_mats = nullptr;
     int *d_inverse = nullptr;
-    DevScope fresh;  // (released unless adopted below)
-    const int tab_dwords = 5 * n_materials + 24 * n_lights;
-    if (fresh.alloc(a.nodes, 4 * (size_t)a.n_records) || fresh.alloc(a.tris, 3 * n) || fresh.alloc(a.shade, n) || fresh.alloc(a.info, n) ||
-        fresh.alloc(a.lights, (size_t)n_lights) || fresh.alloc(a.tables, (size_t)tab_dwords) || fresh.alloc(d_mats, (size_t)n_materials) ||
-        tmp.alloc(d_inverse, n))
-        return 1;
-    if (!sc->d_radius) HIP_TRY(hipMalloc((void **)&sc->d_radius, sizeof(float) * 3));  // (scratch of emit_nodes: a scene just made)
-    HIP_TRY(hipMemcpyAsync(d_mats, materials, sizeof(Material) * (size_t)n_materials, hipMemcpyHostToDevice, st));
-    const float none[3] = {0.f, 0.f, 0.f};  // the new tree's own radius, as at creation: the old triangles' says nothing
-    EmitSource src;
-    src.n_tris = n_tris;
-    src.n_mats = n_materials;
-    src.n_lights = n_lights;
-    src.d_mats = d_mats;
-    src.h_lights = lights;
-    src.d_tri_material = d_m;
-    src.d_tri_light = d_l;
-    src.radius = none;
-    if (emit_scene(sc, src, d_verts, a, d_inverse, st)) return 1;
-    float radius[3];
-    HIP_TRY(hipMemcpyAsync(radius, sc->d_radius, sizeof(radius), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    // adopt: the new buffers replace the old ones, the host state follows
-    fresh.ptrs.clear();
-    std::swap(sc->d_nodes, a.nodes);
-    std::swap(sc->d_tris, a.tris);
-    std::swap(sc->d_tri_shade, a.shade);
-    std::swap(sc->d_tri_info, a.info);
-    std::swap(sc->d_lights, a.lights);
-    std::swap(sc->d_tables, a.tables);
-    std::swap(sc->d_mats, d_mats);
-    for (void *q : {(void *)a.nodes, (void *)a.tris, (void *)a.shade, (void *)a.info, (void *)a.lights, (void *)a.tables, (void *)d_mats})
-        (void)hipFree(q);
-    adopt_tree(sc, b);
-    sc->n_tris = n_tris;
-    sc->n_mats = n_materials;
-    sc->n_lights = n_lights;
-    sc->tab_dwords = tab_dwords;
-    for (int k = 0; k < 3; k++) sc->origin_radius[k] = radius[k];
-    sc->drop_refit();
-    sc->sah_build = sc->sah_now = quads_sah(sc->h_quads);
+    if (emit_tree(sc, b, src, d_verts, st, tmp, d_inverse) || adopt_tree(sc, b, src, st)) return 1;
     sc->drop_ref_tree();
     sc->h_tri9 = std::move(h_tri9);
     sc->h_tri_material = std::move(h_mat);
@@ -1217,6 +1286,20 @@ int scene_set_triangles_impl(rt_scene *sc, const float *verts, int n_tris, const
     sc->h_lights.assign(lights, lights + n_lights);
     sc->note_index_maxima();
     sc->drop_replicas();
+    return 0;
+}
+
+// rt_scene_create_device: an empty scene on the current device that takes its first triangle set from device buffers
+int scene_create_device_impl(const float *d_tri_p0p1p2, int n_tris, const int32_t *d_tri_material, const int32_t *d_tri_light,
+                             const rt_material *materials, int n_materials, const rt_light *lights, int n_lights, hipStream_t st,
+                             rt_scene **out_scene) {
+    if (!out_scene) return fail("rt_scene_create_device: out_scene is null");
+    *out_scene = nullptr;
+    std::unique_ptr<rt_scene> sc;
+    if (new_scene(sc) || scene_set_triangles_impl(sc.get(), d_tri_p0p1p2, n_tris, d_tri_material, d_tri_light, materials, n_materials, lights,
+                                                  n_lights, true, st, "rt_scene_create_device"))
+        return 1;
+    *out_scene = sc.release();
     return 0;
 }
 

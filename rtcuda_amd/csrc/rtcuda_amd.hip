@@ -5,7 +5,10 @@
 //   rt_stream_kernels.inc  k_trace; the query prepasses; stream_walk, the persistent loop of k_query and k_aov; k_aov_resolve
 //   rt_frame_kernels.inc   k_advance and k_paths, once per source of camera rays
 //   rt_build_kernels.inc   device BVH: the leaf-order arrays, the refit (k_refit_*), the build (k_ploc_*)
-//   rt_host_scene.inc, rt_host_render.inc   the host side between the kernels and the C-ABI
+//   rt_host_scene.inc      rt_scene and the one way a tree gets into it: build (host SAH, device PLOC), emit, adopt; the entry
+//                          points on top of it (create, update, rebuild, the edits); what the ray entry points share
+//   rt_host_render.inc     Context, kernel selection, frames, test rays, queries, ray tables, AOVs
+// The C-ABI below them only checks arguments and forwards.
 //
 // The hot path of lashhw/rtcuda (render.cuh:61-457) re-designed for CDNA4:
 //
@@ -137,6 +140,8 @@ struct DScene {
 __device__ __host__ inline int tab_off_lights(int n_mats) { return 5 * n_mats; }
 __device__ __host__ inline int tab_off_ltri(int n_mats, int n_lights) { return 5 * n_mats + 8 * n_lights; }
 __device__ __host__ inline int tab_off_lpre(int n_mats, int n_lights) { return 5 * n_mats + 20 * n_lights; }
+constexpr int kTabPerMat = 5, kTabPerLight = 8 + 12 + 4;  // dwords of the block per material and per light
+inline int tab_dwords(int n_mats, int n_lights) { return kTabPerMat * n_mats + kTabPerLight * n_lights; }
 
 // Structure-of-arrays path state for the slots of one shard (n slots each)
 // Structure-of-arrays path state for the slots of one shard: A_COUNT arrays of n dwords in ONE
@@ -316,7 +321,7 @@ struct AdvanceParams {
 };
 
 constexpr int kLdsTable = 64;                   // materials / lights staged in LDS per workgroup
-constexpr int kTabDwordsMax = kLdsTable * 29;   // 5 + 8 + 12 + 4 dwords per (material, light)
+constexpr int kTabDwordsMax = kLdsTable * (kTabPerMat + kTabPerLight);  // tab_dwords(kLdsTable, kLdsTable)
 
 // Per-light values that depend on the light triangle only, computed once per scene on the device
 // with the same operations mat() would redo per shade: 1 / Triangle::area() (triangle.cuh:79,84-86)
@@ -866,7 +871,7 @@ __global__ void k_test_draw(DPools p, int n, int draws, uint32_t *__restrict__ s
 }
 #include "rt_build_kernels.inc"   // device BVH: the leaf-order arrays, refit (k_refit_*), build (k_ploc_*)
 
-#include "rt_host_scene.inc"   // (opens the anonymous namespace that is closed below) rt_scene: upload, reference tree, checks, emit, update, rebuild, edits; what the ray entry points share
+#include "rt_host_scene.inc"   // (opens the anonymous namespace that is closed below) rt_scene: reference tree, checks, build / emit / adopt, create, update, rebuild, edits; what the ray entry points share
 #include "rt_host_render.inc"  // Context, kernel selection, frames, test rays, queries, ray tables, AOVs
 }  // namespace
 
@@ -890,95 +895,7 @@ int rt_scene_create(const float *tri_p0p1p2, int n_tris, const int32_t *tri_mate
 int rt_scene_create_flags(const float *tri_p0p1p2, int n_tris, const int32_t *tri_material, const int32_t *tri_light,
                           const rt_material *materials, int n_materials, const rt_light *lights, int n_lights,
                           uint32_t scene_flags, rt_scene **out_scene) {
-    if (!out_scene) return fail("rt_scene_create: out_scene is null");
-    if (scene_flags & ~(uint32_t)RT_SCENE_DEVICE_BVH) return fail("rt_scene_create_flags: unknown scene flags");
-    const bool device_bvh = (scene_flags & RT_SCENE_DEVICE_BVH) != 0;
-    *out_scene = nullptr;
-    if (check_scene_counts("rt_scene_create", n_tris, n_tris <= 0 || (tri_p0p1p2 && tri_material), materials, n_materials, lights, n_lights) ||
-        check_tri_indices("rt_scene_create", n_tris, tri_material, tri_light, n_materials, n_lights) ||
-        check_scene_tables("rt_scene_create", n_tris, materials, n_materials, lights, n_lights))
-        return 1;
-    auto sc = std::make_unique<rt_scene>();
-    HIP_TRY(hipGetDevice(&sc->device));
-    sc->wide = true;  // 4-wide nodes (two pair-style records each): half the dependent fetches per ray; RT_BVH_WIDE=0: 2-wide
-    if (const char *e = knob("RT_BVH_WIDE")) sc->wide = atoi(e) != 0;
-    if (device_bvh && !sc->wide) return fail("rt_scene_create_flags: the device builder writes the 4-wide format only (RT_BVH_WIDE=0 is set)");
-    sc->n_tris = n_tris;
-    sc->n_lights = n_lights;
-    sc->n_mats = n_materials;
-    if (n_tris > 0) sc->h_tri9.assign(tri_p0p1p2, tri_p0p1p2 + 9 * (size_t)n_tris);  // (RT_FLAG_REFERENCE_WALK builds its tree from these)
-    if (n_tris > 0) sc->h_tri_material.assign(tri_material, tri_material + n_tris);
-    if (n_tris > 0 && tri_light) sc->h_tri_light.assign(tri_light, tri_light + n_tris);
-    if (n_materials > 0) sc->h_materials.assign(materials, materials + n_materials);
-    if (n_lights > 0) sc->h_lights.assign(lights, lights + n_lights);
-    sc->note_index_maxima();
-    DevScope tmp;
-    float *d_verts = nullptr;
-    if (n_tris > 0) {
-        if (tmp.alloc(d_verts, 9 * (size_t)n_tris)) return 1;
-        HIP_TRY(hipMemcpy(d_verts, tri_p0p1p2, sizeof(float) * 9 * (size_t)n_tris, hipMemcpyHostToDevice));
-    }
-    std::vector<rtbvh::Pair> pairs;  // (2-wide)
-    if (device_bvh && n_tris > 0) {
-        // the device PLOC builder on this device (the scene's)
-        PlocBuild b;
-        if (build_ploc_device(d_verts, n_tris, nullptr, b, "rt_scene_create_flags")) return 1;
-        if (!ploc_result_ok(b, n_tris)) return fail("rt_scene_create_flags: the device-built tree is malformed");
-        adopt_tree(sc.get(), b);
-    } else {
-        // the host SAH builder (also for a device build of no triangles: there is nothing to build)
-        const auto t0 = std::chrono::steady_clock::now();
-        rtbvh::Result bvh = rtbvh::build(tri_p0p1p2, n_tris);
-        if (!device_bvh) sc->build_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        sc->builder = device_bvh ? 2 : 0;
-        if (!bvh.ok) return fail("rt_scene_create: BVH build produced an unreferenceable leaf");
-        if (n_tris > 0 && !bvh.quads.empty() && !validate_quads(bvh.quads, n_tris))
-            return fail("rt_scene_create: the 4-wide BVH is malformed (structure, or an absent child without its +inf box)");
-        // a tree too deep for the 4-wide walk's stack (up to 3 entries per level) may still fit the 2-wide walk's (1 per level):
-        // a host tree the reinsertion pass deepened
-        if (sc->wide && bvh.stack_bound > kMaxStackBound) sc->wide = false;
-        if ((sc->wide ? bvh.stack_bound : bvh.pair_depth + 1) > kMaxStackBound)
-            return fail("rt_scene_create: BVH depth " + std::to_string(sc->wide ? bvh.max_depth : bvh.pair_depth) + " exceeds the traversal stack");
-        sc->n_nodes = sc->wide ? (int)bvh.quads.size() : (int)bvh.pairs.size();  // 64-byte records
-        sc->max_depth = sc->wide ? bvh.max_depth : bvh.pair_depth;
-        sc->stack_bound = sc->wide ? bvh.stack_bound : bvh.pair_depth + 1;
-        sc->n_leaves = bvh.num_leaves;
-        sc->set_order(bvh.order);
-        HIP_TRY(hipMalloc((void **)&sc->d_order, sizeof(int) * std::max(n_tris, 1)));
-        if (n_tris) HIP_TRY(hipMemcpy(sc->d_order, sc->h_order.data(), sizeof(int) * n_tris, hipMemcpyHostToDevice));
-        if (sc->wide) {
-            sc->h_quads = std::move(bvh.quads);
-            HIP_TRY(hipMalloc((void **)&sc->d_recs, sizeof(rtbvh::Pair) * sc->h_quads.size()));
-            HIP_TRY(hipMemcpy(sc->d_recs, sc->h_quads.data(), sizeof(rtbvh::Pair) * sc->h_quads.size(), hipMemcpyHostToDevice));
-        } else {
-            pairs = std::move(bvh.pairs);
-        }
-    }
-    static_assert(sizeof(Light) == sizeof(rt_light), "light layout");
-    static_assert(sizeof(Material) == sizeof(rt_material), "material layout");
-    static_assert(sizeof(Camera) == sizeof(rt_camera), "camera layout");
-    sc->tab_dwords = 5 * n_materials + 24 * n_lights;
-    const size_t nt = (size_t)std::max(n_tris, 1);
-    HIP_TRY(hipMalloc((void **)&sc->d_nodes, 64 * (size_t)sc->n_nodes));
-    HIP_TRY(hipMalloc((void **)&sc->d_radius, sizeof(float) * 3));
-    HIP_TRY(hipMalloc((void **)&sc->d_tris, sizeof(float4) * 3 * nt));
-    HIP_TRY(hipMalloc((void **)&sc->d_tri_info, sizeof(int2) * nt));
-    HIP_TRY(hipMalloc((void **)&sc->d_tri_shade, sizeof(float4) * nt));
-    HIP_TRY(hipMalloc((void **)&sc->d_mats, sizeof(Material) * std::max(n_materials, 1)));
-    if (n_materials) HIP_TRY(hipMemcpy(sc->d_mats, materials, sizeof(Material) * n_materials, hipMemcpyHostToDevice));
-    HIP_TRY(hipMalloc((void **)&sc->d_lights, sizeof(Light) * std::max(n_lights, 1)));
-    HIP_TRY(hipMalloc((void **)&sc->d_tables, sizeof(float) * (size_t)std::max(sc->tab_dwords, 1)));
-    if (!sc->wide)
-        if (int rc = upload_pairs(sc.get(), pairs)) return rc;
-    int *d_inverse = nullptr;
-    if (tmp.alloc(d_inverse, nt)) return 1;
-    EmitSource src;
-    if (scene_source(sc.get(), true, nullptr, tmp, src)) return 1;
-    if (emit_scene(sc.get(), src, d_verts, sc->arrays(), d_inverse, nullptr)) return 1;
-    if (sc->wide) HIP_TRY(hipMemcpy(sc->origin_radius, sc->d_radius, sizeof(float) * 3, hipMemcpyDeviceToHost));
-    HIP_TRY(hipDeviceSynchronize());
-    *out_scene = sc.release();
-    return 0;
+    return scene_create_impl(tri_p0p1p2, n_tris, tri_material, tri_light, materials, n_materials, lights, n_lights, scene_flags, out_scene);
 }
 
 void rt_scene_destroy(rt_scene *scene) { delete scene; }  // (~rt_scene frees the device arrays)
@@ -1039,17 +956,8 @@ int rt_scene_set_triangles_device(rt_scene *scene, const float *d_tri_p0p1p2, in
 int rt_scene_create_device(const float *d_tri_p0p1p2, int n_tris, const int32_t *d_tri_material, const int32_t *d_tri_light,
                            const rt_material *materials, int n_materials, const rt_light *lights, int n_lights, void *stream,
                            rt_scene **out_scene) {
-    if (!out_scene) return fail("rt_scene_create_device: out_scene is null");
-    *out_scene = nullptr;
-    auto sc = std::make_unique<rt_scene>();  // an empty scene on the current device that takes its first triangle set
-    HIP_TRY(hipGetDevice(&sc->device));
-    sc->wide = true;
-    if (const char *e = knob("RT_BVH_WIDE")) sc->wide = atoi(e) != 0;
-    if (scene_set_triangles_impl(sc.get(), d_tri_p0p1p2, n_tris, d_tri_material, d_tri_light, materials, n_materials, lights, n_lights,
-                                 true, (hipStream_t)stream, "rt_scene_create_device"))
-        return 1;
-    *out_scene = sc.release();
-    return 0;
+    return scene_create_device_impl(d_tri_p0p1p2, n_tris, d_tri_material, d_tri_light, materials, n_materials, lights, n_lights,
+                                    (hipStream_t)stream, out_scene);
 }
 
 int rt_scene_refit_info(const rt_scene *scene, int64_t *refits, double *seconds_last, double *sah_ratio) {
