@@ -533,6 +533,20 @@ inline void aov_resolve(const int64_t *d_aov_fixed, float *d_out, int n_pixels, 
     rtcuda_detail::check(rt_aov_resolve(d_aov_fixed, d_out, n_pixels, num_samples, stream), "aov_resolve");
 }
 
+// The denoiser (rt_denoise_fixed, which documents the filter, the parameters and the errors): fixed-point beauty sums and AOV
+// sums of one view, DEVICE buffers -> width * height * 3 floats of linear mean radiance in d_rgb_out.  d_scratch: the caller's,
+// denoise_scratch_bytes(width, height) bytes, 16-byte aligned.  params = nullptr: the library's defaults.
+inline int64_t denoise_scratch_bytes(int width, int height) {
+    const int64_t n = rt_denoise_scratch_bytes(width, height);
+    if (n < 0) throw std::runtime_error("denoise_scratch_bytes: bad frame size " + std::to_string(width) + " x " + std::to_string(height));
+    return n;
+}
+inline void denoise(const int64_t *d_sum_fixed, int num_samples, const int64_t *d_aov_fixed, int aov_samples, int width, int height,
+                    void *d_scratch, float *d_rgb_out, const rt_denoise_params *params = nullptr, void *stream = nullptr) {
+    rtcuda_detail::check(rt_denoise_fixed(d_sum_fixed, num_samples, d_aov_fixed, aov_samples, width, height, params, d_scratch,
+                                          d_rgb_out, stream), "denoise");
+}
+
 // A driver that must keep the reference's exact call (main.cu:173) can still reach several GPUs: RTCUDA_DEVICES="0,1,2,3" in
 // the environment sends the seven-argument render() below through the multi-device path (rt_render_multi).
 inline std::vector<int> devices_from_env() {

@@ -434,6 +434,69 @@ int rt_render_aov_rays_fixed_device(const rt_scene *scene, int64_t n_rays, const
                                     int32_t *d_ids /* may be NULL */, void *stream, rt_stats *stats /* may be NULL */);
 int rt_aov_resolve(const int64_t *d_aov_fixed, float *d_out, int n_pixels, int num_samples, void *stream);
 
+/* ---- the denoiser: an AOV-guided a-trous wavelet filter on fixed-point frames ----------------------------------------------
+ * One more call after rt_render_shard_fixed and rt_render_aov_fixed: the beauty sums and the feature sums of one view become
+ * a clean image, on the same device and stream (no reference counterpart).  An edge-avoiding a-trous filter (Dammertz et al.
+ * 2010) on albedo-demodulated radiance, guided by the first-hit normal and depth.  The whole filter is ONE STATED SEQUENCE of
+ * individually rounded fp32 operations (no FMA; the library is built with -ffp-contract=off), so the kernels, the CPU twin
+ * (hc_denoise of librt_hostcheck.so) and the numpy restatement of the tests agree in every bit.
+ * "x > t ? x : t" below is that comparison and selection, not fmax (the inputs cannot be NaN; the sign of a zero is the
+ * selection's).  Sums start at 0.f.
+ *   1. INPUTS per pixel.  c = float(double(sum) * 2^-30) * (1.f / num_samples) per channel of d_sum_fixed (what
+ *      rt_post_process_fixed forms before its sqrt).  The features are exactly what rt_aov_resolve gives for aov_samples:
+ *      albedo a, normal n (the mean, not renormalised), emission e, depth z (the mean over the hits, 0 on a pixel with none).
+ *      Fixed-point sums are finite, so no input is NaN or infinite.
+ *   2. DEMODULATE.  d = a > 2^-10 ? a : 2^-10 per channel; t = c - e; u = (t > 0 ? t : 0) / d, a true division.  First-hit
+ *      emission is free of noise and is kept out of the filter.
+ *   3. PASSES i = 0 .. passes - 1 with stride s = 2^i, each from one buffer of u to another (a pass never reads what it
+ *      writes).  For pixel p visit the 25 taps q = p + s * (dx, dy), dy outer and dx inner, both from -2 to 2; a tap outside
+ *      the image is skipped.  h = k[dx] * k[dy] with k = {1/16, 1/4, 3/8, 1/4, 1/16} (exact products).  The centre tap has the
+ *      weight h.  Every other tap has w = (h * rt_expnegf(-(x_c + x_z))) * w_n with
+ *          x_c = ((du.x * du.x + du.y * du.y) + du.z * du.z) * kc_i,   du = u_q - u_p,
+ *          kc_i = float(4^i) / (sigma_color * sigma_color)   (made on the host: sigma_color halves every pass),
+ *          x_z = (dz * dz) * kz,   dz = z_q - z_p,   kz = 1.f / (sigma_depth * sigma_depth),
+ *          w_n = (t > 0 ? (t < 1 ? t : 1) : 0) squared normal_power_log2 times,
+ *                                                        t = (n_p.x * n_q.x + n_p.y * n_q.y) + n_p.z * n_q.z.
+ *      (Means of unit normals have t <= 1 up to rounding; the upper clamp keeps every weight at or below h whatever the sums
+ *      hold, so no sum overflows and no NaN can arise -- a NaN's bits would differ between processors.)
+ *      sw = sw + w and su = su + w * u_q per channel, in tap order; the pixel's new u is su / sw per channel (the centre
+ *      weight is positive, so sw is).  z and n do not change.
+ *   4. REMODULATE.  out = u * d + e per channel: LINEAR MEAN RADIANCE.  A caller who wants the reference's display transform
+ *      calls rt_post_process(d_rgb_out, width * height, 1, stream) afterwards.
+ *   5. rt_expnegf(x) (rt_pinned_math.h), x <= 0: exactly 0 for x <= -87 and for NaN (an overflowing x_c therefore gives the
+ *      weight 0); else kf = floor(x * 1.44269504f + 0.5f); r = x - kf * 0.693359375f; r = r - kf * -2.12194440e-4f;
+ *      p = 1.9875691500e-4f, then p = p * r + c for c = 1.3981999507e-3f, 8.3334519073e-3f, 4.1665795894e-2f,
+ *      1.6666665459e-1f, 5.0000001201e-1f; y = (p * (r * r) + r) + 1.f; the result is y * 2^kf, 2^kf built from its bits.
+ *      Exactly 1 at 0; within 2 ulp of exp.
+ * rt_denoise_params: NULL = the defaults, which rt_denoise_default_params writes (chosen on the CPU against 1024-spp frames:
+ * profiles/denoise_quality.json).
+ * d_scratch: rt_denoise_scratch_bytes(width, height) bytes (48 per pixel: {u, z} twice, {n} once), 16-byte aligned, the
+ * caller's; its contents before the call do not matter and are undefined after it.
+ * The contract is the neighbouring entry points': all buffers are DEVICE buffers on the current device; the work is ordered on
+ * `stream` (NULL = default stream) and the call is synchronous on it at return; the calling thread's current device is left as
+ * it was; nothing is allocated; the two input buffers are only read; every pixel of d_rgb_out is written.
+ * ERRORS return non-zero, name the entry point in rt_last_error() and write nothing: a null pointer other than params; width or
+ * height < 1 or more than 715827882 pixels; num_samples or aov_samples < 1; a scratch pointer that is not 16-byte aligned;
+ * passes or normal_power_log2 outside 0 .. 8; a sigma that is not finite and positive, or whose kc_i (for an i < passes) or kz
+ * is not finite and positive; flags != 0; with passes >= 1, a frame so narrow or so flat that a pass would need more than
+ * 16777215 workgroups of 32 x 8 pixels (a launch holds fewer than 2^32 threads: a 1 x 7 * 10^8 frame is refused, any frame
+ * with both sides of 32 or more is served).  "Writes nothing" is the guarantee for these ARGUMENT errors, all found before the
+ * first launch; should a launch or the synchronisation itself fail in the runtime, the call returns its message and the
+ * scratch and the output are undefined.  rt_denoise_scratch_bytes returns a negative number for sizes < 1 or beyond the
+ * pixel limit. */
+typedef struct rt_denoise_params {
+    int32_t passes;             /* 0 .. 8; pass i uses tap stride 2^i */
+    float   sigma_color;        /* > 0; halves every pass */
+    float   sigma_depth;        /* > 0; scene units */
+    int32_t normal_power_log2;  /* 0 .. 8: w_n = min(max(0, n_p . n_q), 1) squared this many times */
+    uint32_t flags;             /* must be 0 */
+} rt_denoise_params;
+int64_t rt_denoise_scratch_bytes(int width, int height);
+int rt_denoise_default_params(rt_denoise_params *out);
+int rt_denoise_fixed(const int64_t *d_sum_fixed, int num_samples, const int64_t *d_aov_fixed, int aov_samples, int width,
+                     int height, const rt_denoise_params *params /* NULL = defaults */, void *d_scratch,
+                     float *d_rgb_out /* width * height * 3 */, void *stream);
+
 /* ---- ray queries (no reference counterpart: its Bvh::traverse is reachable only from render()) ----------------------------
  * "Trace my rays, from my buffers, on my stream."  All pointers are DEVICE buffers on the scene's device (a buffer on another
  * device or on the host cannot be told apart from a good one: the call faults instead of failing); origins and directions are

@@ -103,6 +103,13 @@ enum { RT_SHADE_RECORD_IN = 22, RT_SHADE_RECORD_OUT = 30 };
 int rt_shade_records(const rt_scene *scene, int max_bounces, int lds_tables, int n, const uint32_t *records_in,
                      uint32_t *records_out);
 
+/* One pass of rt_denoise_fixed in one form, `reps` launches timed one by one with HIP events (out_ms, a HOST array).  d_scratch:
+ * the scratch an rt_denoise_fixed call with passes = 0 left for the same frame (prepared {u, z} and {n}); the pass of `stride`
+ * (a power of two up to 128, with its kc) reads them and writes the scratch's second array.  form: 1 = the direct form
+ * k_atrous, 2 = the LDS form k_atrous_lds. */
+int rt_denoise_pass_time(void *d_scratch, int width, int height, int stride, int form, float sigma_color, float sigma_depth,
+                         int normal_power_log2, int reps, float *out_ms);
+
 #ifdef __cplusplus
 }
 #endif

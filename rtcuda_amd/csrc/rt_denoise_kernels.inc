@@ -1,0 +1,131 @@
+// rt_denoise_fixed on the device (include/rtcuda_amd.h; DESIGN.md section 2.7).  The arithmetic is rt_denoise.h's, shared with
+// the CPU twin; here is who walks the pixels and where the records live.
+//
+// Scratch: three arrays of one 16-byte record per pixel.  {u.x, u.y, u.z, z} twice -- a pass reads one and writes the other --
+// and {n.x, n.y, n.z, 0} once.  A tap is two dwordx4 loads.  d and e are not kept: k_dn_finish forms them again from the sums
+// (112 bytes per pixel read once, against 32 written and read back).
+//
+// k_atrous, the direct form: a workgroup is a 32 x 8 tile of pixels (kDnTileW x kDnTileH: a wave is two rows of 32, so a tap
+// of the wave reads two runs of 512 contiguous bytes per array), a lane is a pixel and loads its 24 neighbours from global
+// memory; neighbouring lanes' taps overlap, so all but the first touch of a record is served by L1 / L2.  The grid is
+// one-dimensional (tiles in row order).
+//
+// k_atrous_lds, the LDS form: the pixels p = r (mod stride), per residue r = (rx, ry), form a sub-image on which the pass is a
+// 5 x 5 filter of stride 1 (for stride 1 the sub-image is the image).  A workgroup takes a 32 x 8 tile of one sub-image, stages
+// the tile plus its halo of 2 -- 36 x 12 records of each array, 13.5 KiB -- in LDS, and every lane filters its pixel from there:
+// 3.4 global loads per pixel instead of 50, strided by 16 * stride bytes.  Workgroups that follow each other in the grid hold
+// the SAME tile of neighbouring residues, so the lines a strided read leaves half used are used by the neighbours while
+// they are still cached.  Tap order, skip rule and arithmetic are the direct form's: the same bits.
+// Which form a pass runs: dn_lds_wins (rt_host_denoise.inc), from the timings of profiles/denoise_time.json.
+constexpr int kDnTileW = 32, kDnTileH = 8;
+static_assert(kDnTileW * kDnTileH == kBlock, "a tile is a workgroup");
+
+__global__ void __launch_bounds__(kBlock) k_dn_prepare(const long long *__restrict__ sums, const long long *__restrict__ aov,
+                                                        long long n_pixels, float inv_spp, float inv_aov,
+                                                        float4 *__restrict__ uz, float4 *__restrict__ nrm) {
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_pixels) return;
+    DnPixel px;
+    dn_prepare((const int64_t *)sums + 3 * p, (const int64_t *)aov + DN_AOV_CHANNELS * p, inv_spp, inv_aov, &px);
+    uz[p] = make_float4(px.u[0], px.u[1], px.u[2], px.z);
+    nrm[p] = make_float4(px.n[0], px.n[1], px.n[2], 0.f);
+}
+
+__global__ void __launch_bounds__(kBlock) k_atrous(const float4 *__restrict__ src, const float4 *__restrict__ nrm,
+                                                    float4 *__restrict__ dst, int width, int height, int tiles_x, int stride,
+                                                    float kc, float kz, int normal_power_log2) {
+    const int tile_y = (int)(blockIdx.x / (unsigned)tiles_x), tile_x = (int)(blockIdx.x - (unsigned)tile_y * (unsigned)tiles_x);
+    const int x = tile_x * kDnTileW + (int)(threadIdx.x % kDnTileW);
+    const long long y = (long long)tile_y * kDnTileH + (int)(threadIdx.x / kDnTileW);
+    if (x >= width || y >= height) return;
+    const long long p = y * width + x;
+    const float4 c = src[p], cn = nrm[p];
+    const float up[3] = {c.x, c.y, c.z}, np[3] = {cn.x, cn.y, cn.z};
+    float sw = 0.f, su[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+    for (int dy = -2; dy <= 2; dy++) {
+        const long long yy = y + (long long)stride * dy;
+        if (yy < 0 || yy >= height) continue;
+#pragma unroll
+        for (int dx = -2; dx <= 2; dx++) {
+            const long long xx = (long long)x + (long long)stride * dx;
+            if (xx < 0 || xx >= width) continue;
+            const float h = dn_kernel(dx) * dn_kernel(dy);
+            float w = h;
+            float uq[3] = {up[0], up[1], up[2]};
+            if (dx != 0 || dy != 0) {
+                const long long q = yy * width + xx;
+                const float4 t = src[q], tn = nrm[q];
+                const float nq[3] = {tn.x, tn.y, tn.z};
+                uq[0] = t.x, uq[1] = t.y, uq[2] = t.z;
+                w = dn_tap_weight(h, up, c.w, np, uq, t.w, nq, kc, kz, normal_power_log2);
+            }
+            sw = sw + w;
+            for (int k = 0; k < 3; k++) su[k] = su[k] + w * uq[k];
+        }
+    }
+    dst[p] = make_float4(su[0] / sw, su[1] / sw, su[2] / sw, c.w);
+}
+
+constexpr int kDnHalo = 2, kDnLdsW = kDnTileW + 2 * kDnHalo, kDnLdsH = kDnTileH + 2 * kDnHalo;
+
+__global__ void __launch_bounds__(kBlock) k_atrous_lds(const float4 *__restrict__ src, const float4 *__restrict__ nrm,
+                                                        float4 *__restrict__ dst, int width, int height, int stride, int n_rx,
+                                                        int n_res, int lat_tiles_x, float kc, float kz, int normal_power_log2) {
+    __shared__ float4 s_uz[kDnLdsH][kDnLdsW], s_n[kDnLdsH][kDnLdsW];
+    const unsigned tile = blockIdx.x / (unsigned)n_res, res = blockIdx.x - tile * (unsigned)n_res;
+    const int ry = (int)(res / (unsigned)n_rx), rx = (int)(res - (unsigned)ry * (unsigned)n_rx);
+    const int tile_y = (int)(tile / (unsigned)lat_tiles_x), tile_x = (int)(tile - (unsigned)tile_y * (unsigned)lat_tiles_x);
+    // lattice coordinates (lx, ly) of this residue's sub-image <-> pixel (rx + stride * lx, ry + stride * ly)
+    const long long lx0 = (long long)tile_x * kDnTileW - kDnHalo, ly0 = (long long)tile_y * kDnTileH - kDnHalo;
+    for (int i = (int)threadIdx.x; i < kDnLdsW * kDnLdsH; i += kBlock) {
+        const int cy = i / kDnLdsW, cx = i - cy * kDnLdsW;
+        const long long gx = rx + (long long)stride * (lx0 + cx), gy = ry + (long long)stride * (ly0 + cy);
+        if (gx >= 0 && gx < width && gy >= 0 && gy < height) {  // (a cell outside the image is never read: its tap is skipped)
+            const long long q = gy * width + gx;
+            s_uz[cy][cx] = src[q];
+            s_n[cy][cx] = nrm[q];
+        }
+    }
+    __syncthreads();
+    const int tx = (int)(threadIdx.x % kDnTileW), ty = (int)(threadIdx.x / kDnTileW);
+    const long long x = rx + (long long)stride * (lx0 + kDnHalo + tx), y = ry + (long long)stride * (ly0 + kDnHalo + ty);
+    if (x >= width || y >= height) return;
+    const float4 c = s_uz[ty + kDnHalo][tx + kDnHalo], cn = s_n[ty + kDnHalo][tx + kDnHalo];
+    const float up[3] = {c.x, c.y, c.z}, np[3] = {cn.x, cn.y, cn.z};
+    float sw = 0.f, su[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+    for (int dy = -2; dy <= 2; dy++) {
+        const long long yy = y + (long long)stride * dy;
+        if (yy < 0 || yy >= height) continue;
+#pragma unroll
+        for (int dx = -2; dx <= 2; dx++) {
+            const long long xx = x + (long long)stride * dx;
+            if (xx < 0 || xx >= width) continue;
+            const float h = dn_kernel(dx) * dn_kernel(dy);
+            float w = h;
+            float uq[3] = {up[0], up[1], up[2]};
+            if (dx != 0 || dy != 0) {
+                const float4 t = s_uz[ty + kDnHalo + dy][tx + kDnHalo + dx], tn = s_n[ty + kDnHalo + dy][tx + kDnHalo + dx];
+                const float nq[3] = {tn.x, tn.y, tn.z};
+                uq[0] = t.x, uq[1] = t.y, uq[2] = t.z;
+                w = dn_tap_weight(h, up, c.w, np, uq, t.w, nq, kc, kz, normal_power_log2);
+            }
+            sw = sw + w;
+            for (int k = 0; k < 3; k++) su[k] = su[k] + w * uq[k];
+        }
+    }
+    dst[y * width + x] = make_float4(su[0] / sw, su[1] / sw, su[2] / sw, c.w);
+}
+
+__global__ void __launch_bounds__(kBlock) k_dn_finish(const float4 *__restrict__ uz, const long long *__restrict__ sums,
+                                                       const long long *__restrict__ aov, long long n_pixels, float inv_spp,
+                                                       float inv_aov, float *__restrict__ out) {
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_pixels) return;
+    DnPixel px;
+    dn_prepare((const int64_t *)sums + 3 * p, (const int64_t *)aov + DN_AOV_CHANNELS * p, inv_spp, inv_aov, &px);
+    const float4 r = uz[p];
+    const float u[3] = {r.x, r.y, r.z};
+    dn_finish(u, px.d, px.e, out + 3 * p);
+}

@@ -15,6 +15,7 @@
 //   * rt_plan_paths_launch  the launch geometry of the persistent frame kernels (rt_launch_plan.h), as the library computes it.
 //   * rt_slot_chunk_*   the chunked deal of k_paths (rt_slot_chunks.h): task -> slot, the static deal's slots, the counts and
 //     the decisions, as the kernel makes them.
+//   * hc_denoise / hc_expnegf  the CPU twin of rt_denoise_fixed: a serial loop over rt_denoise.h, the arithmetic of the kernels.
 #include <cfloat>
 #include <cmath>
 #include <cstdint>
@@ -24,6 +25,7 @@
 #include <vector>
 
 #include "rt_bvh.h"
+#include "rt_denoise.h"
 #include "rt_launch_plan.h"
 #include "rt_ploc.h"
 #include "rt_ref_tree.h"
@@ -929,5 +931,56 @@ int rt_slot_chunk_runner_keeps(int old_sem) { return rtchunks::runner_keeps(old_
 // G as the launch plan picks it for a frame whose slots run `chain` camera rays in k_paths (0: the static deal)
 int rt_plan_slot_chunk(int n, int cus, int chain) {
     return rtplan::slot_chunk_for(rtplan::plan_paths_launch(n, cus, true, 70000, 10, true, 1920, 256, 0), chain);
+}
+// The CPU twin of rt_denoise_fixed (tests/test_denoise_host.py): a plain serial loop over the arithmetic the kernels use
+// (rt_denoise.h), host buffers throughout, the same checks of the parameters.  Returns 0, or 1 and writes nothing.
+int hc_denoise(const int64_t *sum_fixed, int num_samples, const int64_t *aov_fixed, int aov_samples, int width, int height, int passes,
+               float sigma_color, float sigma_depth, int normal_power_log2, float *rgb_out) {
+    if (!sum_fixed || !aov_fixed || !rgb_out || width < 1 || height < 1 || num_samples < 1 || aov_samples < 1) return 1;
+    if (passes < 0 || passes > DN_MAX_PASSES || normal_power_log2 < 0 || normal_power_log2 > DN_MAX_NORMAL_POWER_LOG2) return 1;
+    if (!(std::isfinite(sigma_color) && sigma_color > 0.f && std::isfinite(sigma_depth) && sigma_depth > 0.f)) return 1;
+    const float sc2 = sigma_color * sigma_color, sd2 = sigma_depth * sigma_depth;
+    const float kz = 1.f / sd2;
+    float kc[DN_MAX_PASSES];
+    for (int i = 0; i < passes; i++) {
+        kc[i] = (float)(1 << (2 * i)) / sc2;
+        if (!(std::isfinite(kc[i]) && kc[i] > 0.f)) return 1;
+    }
+    if (!(std::isfinite(kz) && kz > 0.f)) return 1;
+    const size_t n = (size_t)width * (size_t)height;
+    const float inv_spp = 1.f / (float)num_samples, inv_aov = 1.f / (float)aov_samples;
+    std::vector<DnPixel> px(n);
+    for (size_t p = 0; p < n; p++) dn_prepare(sum_fixed + 3 * p, aov_fixed + DN_AOV_CHANNELS * p, inv_spp, inv_aov, &px[p]);
+    std::vector<float> next(3 * n);
+    for (int i = 0; i < passes; i++) {
+        const long long s = 1ll << i;
+        for (long long y = 0; y < height; y++)
+            for (long long x = 0; x < width; x++) {
+                const DnPixel &c = px[(size_t)(y * width + x)];
+                float sw = 0.f, su[3] = {0.f, 0.f, 0.f};
+                for (int dy = -2; dy <= 2; dy++) {
+                    const long long yy = y + s * dy;
+                    if (yy < 0 || yy >= height) continue;
+                    for (int dx = -2; dx <= 2; dx++) {
+                        const long long xx = x + s * dx;
+                        if (xx < 0 || xx >= width) continue;
+                        const DnPixel &q = px[(size_t)(yy * width + xx)];
+                        const float h = dn_kernel(dx) * dn_kernel(dy);
+                        const float w = (dx == 0 && dy == 0) ? h : dn_tap_weight(h, c.u, c.z, c.n, q.u, q.z, q.n, kc[i], kz, normal_power_log2);
+                        sw = sw + w;
+                        for (int k = 0; k < 3; k++) su[k] = su[k] + w * q.u[k];
+                    }
+                }
+                for (int k = 0; k < 3; k++) next[3 * (size_t)(y * width + x) + k] = su[k] / sw;
+            }
+        for (size_t p = 0; p < n; p++)
+            for (int k = 0; k < 3; k++) px[p].u[k] = next[3 * p + k];
+    }
+    for (size_t p = 0; p < n; p++) dn_finish(px[p].u, px[p].d, px[p].e, rgb_out + 3 * p);
+    return 0;
+}
+// rt_expnegf on n values (tests/test_denoise_host.py holds it to its numpy restatement and to exp)
+void hc_expnegf(const float *x, float *y, int n) {
+    for (int k = 0; k < n; k++) y[k] = rt_expnegf(x[k]);
 }
 }

@@ -52,4 +52,28 @@ RT_HD float rt_pow5f(float x) {
     return x4 * x;
 }
 
+// exp(x) for x <= 0 (the edge-stopping weights of rt_denoise_fixed; stands in for expf).
+//   x <= -87 (the cut-off, where exp leaves the fp32 normal range) and NaN give exactly 0; x = 0 gives exactly 1.
+// In between: k = floor(x * log2(e) + 0.5); Cody-Waite reduction r = (x - k * C1) - k * C2 by ln 2 = C1 + C2 in two fp32
+// pieces (C1 = 0.693359375 has 9 significant bits: k * C1 is exact for |k| <= 126), |r| <= 0.347; the classic degree-5
+// single-precision polynomial in Horner form, exp(r) = (p(r) * r^2 + r) + 1; and 2^k built from its bits (k >= -126: a
+// normal number), so the last product is exact.  Every operation is a separately rounded fp32 op; the result is within 2 ulp.
+RT_HD float rt_expnegf(float x) {
+    if (!(x > -87.0f)) return 0.0f;
+    float kf = floorf(x * 1.44269504f + 0.5f);
+    float r = x - kf * 0.693359375f;
+    r = r - kf * -2.12194440e-4f;
+    float r2 = r * r;
+    float p = 1.9875691500e-4f;
+    p = p * r + 1.3981999507e-3f;
+    p = p * r + 8.3334519073e-3f;
+    p = p * r + 4.1665795894e-2f;
+    p = p * r + 1.6666665459e-1f;
+    p = p * r + 5.0000001201e-1f;
+    float y = (p * r2 + r) + 1.0f;
+    union { unsigned int u; float f; } scale;
+    scale.u = (unsigned int)((int)kf + 127) << 23;
+    return y * scale.f;
+}
+
 #endif  // RT_PINNED_MATH_H

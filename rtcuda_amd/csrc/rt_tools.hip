@@ -7,6 +7,7 @@
 //   rt_probe_issue              cycles per instruction of one wave, by instruction kind and occupancy
 //   rt_split_probe              "one persistent kernel, or the reference's stage split?" priced on dense ray / shade arrays
 //   rt_scene_tree_copy          a scene's unpadded 4-wide records and leaf order (the device builder against its host twin)
+//   rt_denoise_pass_time        one pass of the denoiser in one form, timed launch by launch
 //   rt_shade_table              the product's shading FUNCTIONS (rt_device.h), one lane per row of a function table
 //   rt_shade_records            the product's init() + mat() (advance_core, through k_probe_shade) on the caller's path states
 // The product library (librtcuda_amd.so) contains none of this.  The tools library also carries a private copy of the
@@ -811,6 +812,33 @@ int rt_shade_records(const rt_scene *scene, int max_bounces, int lds_tables, int
     return 0;
 }
 
+
+// One pass of the denoiser, one form, timed launch by launch (tools/denoise_time.py).  d_scratch: the scratch of an
+// rt_denoise_fixed call with passes = 0 of the same frame -- its first array holds the prepared {u, z}, its third {n}; the pass
+// writes the second.  stride = 2^i uses kc_i; form: 1 = k_atrous, 2 = k_atrous_lds.  out_ms: reps device times, HIP events.
+int rt_denoise_pass_time(void *d_scratch, int width, int height, int stride, int form, float sigma_color, float sigma_depth,
+                         int normal_power_log2, int reps, float *out_ms) {
+    if (!d_scratch || !out_ms || width < 1 || height < 1 || reps < 1) return fail("rt_denoise_pass_time: bad argument");
+    if (stride < 1 || stride > 128 || (stride & (stride - 1)) || (form != 1 && form != 2)) return fail("rt_denoise_pass_time: bad stride or form");
+    if (dn_pass_blocks(width, height, stride, form) > kDnMaxBlocks) return fail("rt_denoise_pass_time: the grid of this form is too large");
+    const long long n = (long long)width * height;
+    float4 *uz = (float4 *)d_scratch, *dst = uz + n, *nrm = uz + 2 * n;
+    const float kc = (float)(stride * stride) / (sigma_color * sigma_color), kz = 1.f / (sigma_depth * sigma_depth);
+    hipEvent_t e0, e1;
+    HIP_TRY(hipEventCreate(&e0));
+    HIP_TRY(hipEventCreate(&e1));
+    for (int r = 0; r < reps; r++) {
+        HIP_TRY(hipEventRecord(e0, nullptr));
+        dn_launch_pass(form, uz, nrm, dst, width, height, stride, kc, kz, normal_power_log2, nullptr);
+        HIP_TRY(hipEventRecord(e1, nullptr));
+        HIP_TRY(hipEventSynchronize(e1));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventElapsedTime(&out_ms[r], e0, e1));
+    }
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    return 0;
+}
 
 }  // extern "C"
 

@@ -8,6 +8,8 @@
 //   rt_host_scene.inc      rt_scene and the one way a tree gets into it: build (host SAH, device PLOC), emit, adopt; the entry
 //                          points on top of it (create, update, rebuild, the edits); what the ray entry points share
 //   rt_host_render.inc     Context, kernel selection, frames, test rays, queries, ray tables, AOVs
+//   rt_denoise_kernels.inc k_dn_prepare, k_atrous, k_dn_finish (arithmetic: rt_denoise.h, shared with the CPU twin)
+//   rt_host_denoise.inc    rt_denoise_fixed: checks, pass constants, launches
 // The C-ABI below them only checks arguments and forwards.
 //
 // The hot path of lashhw/rtcuda (render.cuh:61-457) re-designed for CDNA4:
@@ -71,6 +73,7 @@
 
 #include "../../include/rtcuda_amd.h"
 #include "rt_bvh.h"
+#include "rt_denoise.h"
 #include "rt_device.h"
 #include "rt_launch_plan.h"
 #include "rt_ploc.h"
@@ -870,9 +873,11 @@ __global__ void k_test_draw(DPools p, int n, int draws, uint32_t *__restrict__ s
     state6[6 * (size_t)i + 5] = rs.v4;
 }
 #include "rt_build_kernels.inc"   // device BVH: the leaf-order arrays, refit (k_refit_*), build (k_ploc_*)
+#include "rt_denoise_kernels.inc"  // k_dn_prepare, k_atrous, k_dn_finish
 
 #include "rt_host_scene.inc"   // (opens the anonymous namespace that is closed below) rt_scene: reference tree, checks, build / emit / adopt, create, update, rebuild, edits; what the ray entry points share
 #include "rt_host_render.inc"  // Context, kernel selection, frames, test rays, queries, ray tables, AOVs
+#include "rt_host_denoise.inc"  // rt_denoise_fixed
 }  // namespace
 
 // ============================================================================ C-ABI
@@ -1085,6 +1090,20 @@ int rt_aov_resolve(const int64_t *d_aov_fixed, float *d_out, int n_pixels, int n
                        (const long long *)d_aov_fixed, d_out, nv, inv);
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+int64_t rt_denoise_scratch_bytes(int width, int height) { return denoise_scratch_bytes(width, height); }
+
+int rt_denoise_default_params(rt_denoise_params *out) {
+    if (!out) return fail("rt_denoise_default_params: null out");
+    *out = denoise_defaults();
+    return 0;
+}
+
+int rt_denoise_fixed(const int64_t *d_sum_fixed, int num_samples, const int64_t *d_aov_fixed, int aov_samples, int width, int height,
+                     const rt_denoise_params *params, void *d_scratch, float *d_rgb_out, void *stream) {
+    return denoise_impl(d_sum_fixed, num_samples, d_aov_fixed, aov_samples, width, height, params, d_scratch, d_rgb_out,
+                        (hipStream_t)stream);
 }
 
 int rt_post_process(float *d_rgb, int num_pixels, int num_samples, void *stream) {
