@@ -547,6 +547,21 @@ inline void denoise(const int64_t *d_sum_fixed, int num_samples, const int64_t *
                                           d_rgb_out, stream), "denoise");
 }
 
+// The dual-buffer denoiser (rt_denoise_dual_fixed, which documents the filter): two half frames of one view -- shards (0, 2) and
+// (1, 2) of render_shard_fixed with RT_FLAG_RNG_PER_SAMPLE, each into a zeroed buffer -- and the AOV sums, DEVICE buffers ->
+// width * height * 3 floats of linear mean radiance.  d_scratch: denoise_dual_scratch_bytes(width, height) bytes, 16-byte aligned.
+inline int64_t denoise_dual_scratch_bytes(int width, int height) {
+    const int64_t n = rt_denoise_dual_scratch_bytes(width, height);
+    if (n < 0) throw std::runtime_error("denoise_dual_scratch_bytes: bad frame size " + std::to_string(width) + " x " + std::to_string(height));
+    return n;
+}
+inline void denoise_dual(const int64_t *d_sum_a, int samples_a, const int64_t *d_sum_b, int samples_b, const int64_t *d_aov_fixed,
+                         int aov_samples, int width, int height, void *d_scratch, float *d_rgb_out,
+                         const rt_denoise_dual_params *params = nullptr, void *stream = nullptr) {
+    rtcuda_detail::check(rt_denoise_dual_fixed(d_sum_a, samples_a, d_sum_b, samples_b, d_aov_fixed, aov_samples, width, height, params,
+                                               d_scratch, d_rgb_out, stream), "denoise_dual");
+}
+
 // A driver that must keep the reference's exact call (main.cu:173) can still reach several GPUs: RTCUDA_DEVICES="0,1,2,3" in
 // the environment sends the seven-argument render() below through the multi-device path (rt_render_multi).
 inline std::vector<int> devices_from_env() {

@@ -497,6 +497,69 @@ int rt_denoise_fixed(const int64_t *d_sum_fixed, int num_samples, const int64_t 
                      int height, const rt_denoise_params *params /* NULL = defaults */, void *d_scratch,
                      float *d_rgb_out /* width * height * 3 */, void *stream);
 
+/* ---- the dual-buffer denoiser: variance-guided a-trous from two half frames ----------------------------------------------------
+ * rt_denoise_fixed's filter with the fixed sigma_color replaced by a per-pixel noise estimate (the spatial part of SVGF, Schied
+ * et al. 2017).  The caller renders the view as two half frames A and B -- with RT_FLAG_RNG_PER_SAMPLE, shard (r, 2) of
+ * rt_render_shard_fixed into two zeroed buffers: their sum is the whole frame exactly -- and one rt_render_aov_fixed.  The
+ * difference of the halves gives, per pixel, an unbiased estimate of the variance of their mean; a colour distance is then
+ * measured in standard deviations of that estimate, so a firefly (large variance) is absorbed where a fixed colour stop would
+ * protect it as an edge.  ONE STATED SEQUENCE again: every operation below is one rounded fp32 operation, no FMA, every
+ * "x > t ? x : t" a comparison and selection, sums start at 0.f; kernels, CPU twin (hc_denoise_dual) and the tests' numpy
+ * restatement agree in every bit.
+ *   1. INPUTS per pixel.  S = sum_a + sum_b per channel, a two's-complement WRAPPING add (done in uint64_t: every pair of inputs
+ *      is defined); n = samples_a + samples_b.  c, d, e, z, the normal and u are exactly steps 1 and 2 of rt_denoise_fixed for
+ *      (S, n): with passes = 0 the output is rt_denoise_fixed's on the summed buffer, bit for bit.  u_a and u_b are formed the
+ *      same way from (sum_a, samples_a) and (sum_b, samples_b) with the same d and e:
+ *      u_a = (t > 0 ? t : 0) / d, t = float(double(sum_a) * 2^-30) * (1.f / samples_a) - e.
+ *   2. VARIANCE OF THE MEAN, summed over the channels of demodulated radiance:
+ *          v = (((u_a.x - u_b.x)^2 + (u_a.y - u_b.y)^2) + (u_a.z - u_b.z)^2) * kv,
+ *      each difference and each square rounded; kv = float(double(samples_a) * samples_b / (double(n) * n)), made on the host
+ *      (1/4 for equal halves).
+ *   3. PASSES i = 0 .. passes - 1 with stride s = 2^i, each from one buffer of {u, v} to another.  For pixel p:
+ *      a. the 3 x 3 prefilter of the variance on the pass's INPUT: taps at stride 1 whatever s is, dy outer and dx inner, both
+ *         from -1 to 1, taps outside the image skipped, k3 = {1/4, 1/2, 1/4} (exact products):
+ *         sg = sg + (k3[dx] * k3[dy]) * v_q, sk = sk + k3[dx] * k3[dy]; g = sg / sk.
+ *      b. r = 1.f / (ks * g + 2^-26), ks = sigma_variance * sigma_variance made on the host.  One division per pixel.
+ *      c. the 25 taps in rt_denoise_fixed's order with its skip rule, h = k[dx] * k[dy].  The centre tap has the weight h.
+ *         Every other tap has w = (h * rt_expnegf(-(x_v + x_z))) * w_n with
+ *             x_v = ((du.x * du.x + du.y * du.y) + du.z * du.z) * r,   du = u_q - u_p,
+ *         and x_z, w_n as in rt_denoise_fixed (kz = 1.f / (sigma_depth * sigma_depth); w_n clamped to 0 .. 1).
+ *      d. per tap, in order: sw = sw + w; su = su + w * u_q per channel; sv = sv + (w * w) * v_q (the centre tap contributes
+ *         (h * h) * v_p).  New u = su / sw per channel; new v = sv / (sw * sw).  z and n do not change.
+ *   4. REMODULATE.  out = u * d + e per channel: linear mean radiance, as rt_denoise_fixed leaves it.
+ * FINITENESS.  |sum| * 2^-30 <= 2^33 and d >= 2^-10, so 0 <= u, u_a, u_b <= 2^43 and v <= 3 * 2^86 * kv < 2^87.  sk is at
+ * least 1/4 (a one-pixel image) and g is a weighted mean of v: finite and not negative.  ks * g may overflow to +inf (r = 0:
+ * the colour stop vanishes, x_v = 0) or underflow to 0 (r = 2^26), so 0 <= r <= 2^26 and x_v <= 3 * 2^86 * 2^26 < 2^128: no
+ * inf - inf and no 0 * inf anywhere; x_v + x_z may be +inf, which rt_expnegf maps to the weight 0.  Weights are at most h,
+ * sw >= 9/64 (the centre), the new u is a weighted mean of the taps' u, and the new v is at most the largest v of the taps
+ * times (sum of w^2) / (sum of w)^2 <= 1, up to rounding.  Products w * w and (w * w) * v may be denormal or underflow to 0;
+ * that is defined and the same on every processor the library runs on.  No NaN can arise from any finite sums.
+ * d_sum_a == d_sum_b is legal: v = 0 everywhere, r = 2^26, and only taps whose u equals the centre's to within 2^-13 carry weight.
+ * rt_denoise_dual_params: NULL = the defaults, which rt_denoise_dual_default_params writes (chosen on the CPU against 1024-spp
+ * frames: profiles/denoise_dual_quality.json).
+ * d_scratch: rt_denoise_dual_scratch_bytes(width, height) bytes (52 per pixel: {u, v} twice, {n, z} once, r once), 16-byte
+ * aligned, the caller's; its contents before the call do not matter and are undefined after it.  (The r array is written only
+ * by passes that take r from a kernel of their own before the pass -- as built, the pass of stride 2 -- and is otherwise left
+ * untouched; every other pass forms r inside the pass.)
+ * The contract, the size limits and the error style are rt_denoise_fixed's: device buffers on the current device, ordered on
+ * `stream` and synchronous on it at return, nothing allocated, inputs only read, every pixel of d_rgb_out written.  ERRORS
+ * return non-zero, begin "rt_denoise_dual_fixed: " in rt_last_error() and write nothing: rt_denoise_fixed's list with
+ * sigma_variance in the place of sigma_color, and also samples_a or samples_b < 1, samples_a + samples_b beyond int32, a
+ * sigma_variance that is not finite and positive or whose ks is not. */
+typedef struct rt_denoise_dual_params {
+    int32_t passes;             /* 0 .. 8; pass i uses tap stride 2^i */
+    float   sigma_variance;     /* > 0: colour distances are measured in standard deviations of the local estimate */
+    float   sigma_depth;        /* > 0; scene units */
+    int32_t normal_power_log2;  /* 0 .. 8 */
+    uint32_t flags;             /* must be 0 */
+} rt_denoise_dual_params;
+int64_t rt_denoise_dual_scratch_bytes(int width, int height);
+int rt_denoise_dual_default_params(rt_denoise_dual_params *out);
+int rt_denoise_dual_fixed(const int64_t *d_sum_a, int samples_a, const int64_t *d_sum_b, int samples_b,
+                          const int64_t *d_aov_fixed, int aov_samples, int width, int height,
+                          const rt_denoise_dual_params *params /* NULL = defaults */, void *d_scratch,
+                          float *d_rgb_out /* width * height * 3 */, void *stream);
+
 /* ---- ray queries (no reference counterpart: its Bvh::traverse is reachable only from render()) ----------------------------
  * "Trace my rays, from my buffers, on my stream."  All pointers are DEVICE buffers on the scene's device (a buffer on another
  * device or on the host cannot be told apart from a good one: the call faults instead of failing); origins and directions are

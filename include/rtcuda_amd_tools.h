@@ -110,6 +110,14 @@ int rt_shade_records(const rt_scene *scene, int max_bounces, int lds_tables, int
 int rt_denoise_pass_time(void *d_scratch, int width, int height, int stride, int form, float sigma_color, float sigma_depth,
                          int normal_power_log2, int reps, float *out_ms);
 
+/* One pass of rt_denoise_dual_fixed, `reps` launches timed one by one with HIP events (out_ms, a HOST array).  d_scratch: the
+ * scratch an rt_denoise_dual_fixed call with passes = 0 left for the same frame (prepared {u, v} and {n, z}); the pass of `stride`
+ * (a power of two up to 128) reads them and writes the scratch's second array.  form: 1 = the direct form k_atrous_var, 2 = the
+ * LDS form k_atrous_var_lds.  g_place: 1 = the variance prefilter in the pass, 2 = k_dn_var_blur before it, inside the timed
+ * interval. */
+int rt_denoise_dual_pass_time(void *d_scratch, int width, int height, int stride, int form, int g_place, float sigma_variance,
+                              float sigma_depth, int normal_power_log2, int reps, float *out_ms);
+
 #ifdef __cplusplus
 }
 #endif

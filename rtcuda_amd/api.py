@@ -40,12 +40,14 @@ EXPORTS = [
     "rt_trace_closest_flags", "rt_trace_any_flags", "rt_query_closest_device", "rt_query_any_device", "rt_query_last_counters",
     "rt_render_aov_fixed", "rt_render_aov_rays_fixed_device", "rt_aov_resolve",
     "rt_denoise_scratch_bytes", "rt_denoise_default_params", "rt_denoise_fixed",
+    "rt_denoise_dual_scratch_bytes", "rt_denoise_dual_default_params", "rt_denoise_dual_fixed",
     "rt_xorwow_states", "rt_shutdown", "rt_peer_access_log", "rt_last_error", "rt_version", "rt_build_id",
 ]
 # the lab (include/rtcuda_amd_tools.h, librtcuda_amd_tools.so): measurement tools, not part of the drop-in C-ABI
 TOOLS_LIB_PATH = os.path.join(_PKG, "librtcuda_amd_tools.so")
 TOOLS_EXPORTS = ["rt_measure_copy_bandwidth", "rt_calibrate_valu", "rt_calibrate_valu_packed", "rt_probe_issue", "rt_split_probe",
-                 "rt_scene_tree_copy", "rt_shade_table", "rt_shade_records", "rt_denoise_pass_time"]
+                 "rt_scene_tree_copy", "rt_shade_table", "rt_shade_records", "rt_denoise_pass_time",
+                 "rt_denoise_dual_pass_time"]
 
 
 class RtError(RuntimeError):
@@ -74,6 +76,11 @@ class RtStats(ctypes.Structure):
 
 class RtDenoiseParams(ctypes.Structure):
     _fields_ = [("passes", ctypes.c_int32), ("sigma_color", ctypes.c_float), ("sigma_depth", ctypes.c_float),
+                ("normal_power_log2", ctypes.c_int32), ("flags", ctypes.c_uint32)]
+
+
+class RtDenoiseDualParams(ctypes.Structure):
+    _fields_ = [("passes", ctypes.c_int32), ("sigma_variance", ctypes.c_float), ("sigma_depth", ctypes.c_float),
                 ("normal_power_log2", ctypes.c_int32), ("flags", ctypes.c_uint32)]
 
 
@@ -172,6 +179,10 @@ def _bind(L):
     L.rt_denoise_scratch_bytes.restype = ctypes.c_int64
     L.rt_denoise_default_params.argtypes = [ctypes.POINTER(RtDenoiseParams)]
     L.rt_denoise_fixed.argtypes = [vp, ci, vp, ci, ci, ci, ctypes.POINTER(RtDenoiseParams), vp, vp, vp]
+    L.rt_denoise_dual_scratch_bytes.argtypes = [ci, ci]
+    L.rt_denoise_dual_scratch_bytes.restype = ctypes.c_int64
+    L.rt_denoise_dual_default_params.argtypes = [ctypes.POINTER(RtDenoiseDualParams)]
+    L.rt_denoise_dual_fixed.argtypes = [vp, ci, vp, ci, vp, ci, ci, ci, ctypes.POINTER(RtDenoiseDualParams), vp, vp, vp]
     L.rt_trace_closest.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp]
     L.rt_trace_any.argtypes = [vp, ci, vp, vp, vp, vp, vp]
     L.rt_trace_closest_flags.argtypes = [vp, ctypes.c_uint32, ci, vp, vp, vp, vp, vp, vp, vp]
@@ -208,6 +219,7 @@ def tools_lib():
     L.rt_shade_table.argtypes = [ci, ci, vp, vp]
     L.rt_shade_records.argtypes = [vp, ci, ci, ci, vp, vp]
     L.rt_denoise_pass_time.argtypes = [vp, ci, ci, ci, ci, ctypes.c_float, ctypes.c_float, ci, ci, vp]
+    L.rt_denoise_dual_pass_time.argtypes = [vp, ci, ci, ci, ci, ci, ctypes.c_float, ctypes.c_float, ci, ci, vp]
     _tools = L
     return L
 
@@ -848,6 +860,85 @@ def denoise(beauty_sums, spp: int, aov_sums, aov_spp: int, width: int, height: i
         _check(lib().rt_denoise_fixed(ctypes.c_void_p(beauty_sums.data_ptr()), spp, ctypes.c_void_p(aov_sums.data_ptr()), aov_spp,
                                       width, height, ctypes.byref(prm), ctypes.c_void_p(scratch.data_ptr()),
                                       ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(s.cuda_stream or None)), "rt_denoise_fixed")
+    return out
+
+
+def denoise_dual_default_params() -> dict:
+    """The parameters rt_denoise_dual_fixed uses when it is given none (rt_denoise_dual_default_params)."""
+    p = RtDenoiseDualParams()
+    _check(lib().rt_denoise_dual_default_params(ctypes.byref(p)), "rt_denoise_dual_default_params")
+    return dict(passes=int(p.passes), sigma_variance=float(p.sigma_variance), sigma_depth=float(p.sigma_depth),
+                normal_power_log2=int(p.normal_power_log2))
+
+
+def denoise_dual_scratch_bytes(width: int, height: int) -> int:
+    """Bytes of scratch rt_denoise_dual_fixed needs for a width x height frame (rt_denoise_dual_scratch_bytes)."""
+    if not isinstance(width, int) or not isinstance(height, int):
+        raise RtError(f"denoise_dual_scratch_bytes: width and height must be ints, they are {width!r}, {height!r}")
+    n = int(lib().rt_denoise_dual_scratch_bytes(width, height))
+    if n < 0:
+        raise RtError(f"denoise_dual_scratch_bytes: bad frame size {width} x {height}")
+    return n
+
+
+def denoise_dual(beauty_a, spp_a: int, beauty_b, spp_b: int, aov_sums, aov_spp: int, width: int, height: int, *, passes=None,
+                 sigma_variance=None, sigma_depth=None, normal_power_log2=None, scratch=None, out=None, stream=None):
+    """The denoised frame of TWO HALF FRAMES of one view (rt_denoise_dual_fixed: the a-trous filter of ``denoise`` with its colour
+    stop measured in standard deviations of a per-pixel variance estimate, which the difference of the halves supplies).
+    ``beauty_a`` / ``beauty_b``: (h * w, 3) int64 fixed-point sums of ``spp_a`` / ``spp_b`` samples, as
+    Scene.render_shard_fixed(..., rank 0 / 1, 2, ..., flags=FLAG_RNG_PER_SAMPLE) leaves them in two zeroed buffers (their sum is
+    the whole frame); they may be the same tensor (the variance is then 0).  ``aov_sums``: (h * w, 11) int64, as Scene.render_aov
+    leaves them.  All on one GPU -> (h * w, 3) float32 tensor of LINEAR mean radiance.  Parameters left at None are the library's
+    defaults (denoise_dual_default_params).  ``scratch``: a contiguous torch.uint8 tensor of at least
+    denoise_dual_scratch_bytes(width, height) bytes to reuse between calls (made here otherwise); ``out``: the result tensor to
+    fill; ``stream``: a torch.cuda.Stream (the current one otherwise)."""
+    import torch
+    for name, v in (("width", width), ("height", height), ("spp_a", spp_a), ("spp_b", spp_b), ("aov_spp", aov_spp)):
+        if not isinstance(v, int) or isinstance(v, bool) or v < 1:
+            raise RtError(f"denoise_dual: {name} must be a positive int, it is {v!r}")
+    if spp_a + spp_b > 0x7FFFFFFF:
+        raise RtError(f"denoise_dual: spp_a + spp_b must fit an int32, they are {spp_a} + {spp_b}")
+    n = width * height
+    for name, t, ch in (("beauty_a", beauty_a, 3), ("beauty_b", beauty_b, 3), ("aov_sums", aov_sums, AOV_CHANNELS)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RtError(f"denoise_dual: {name} must be a torch tensor on a GPU")
+        if t.dtype != torch.int64 or tuple(t.shape) != (n, ch) or not t.is_contiguous():
+            raise RtError(f"denoise_dual: {name} must be a contiguous ({n}, {ch}) torch.int64 tensor, it is {tuple(t.shape)} {t.dtype}")
+    device = beauty_a.device
+    for name, t in (("beauty_b", beauty_b), ("aov_sums", aov_sums)):
+        if t.device != device:
+            raise RtError(f"denoise_dual: {name} is on {t.device}, beauty_a on {device}")
+    prm = RtDenoiseDualParams()
+    _check(lib().rt_denoise_dual_default_params(ctypes.byref(prm)), "rt_denoise_dual_default_params")
+    for name, v in (("passes", passes), ("normal_power_log2", normal_power_log2)):
+        if v is not None:
+            if not isinstance(v, int) or isinstance(v, bool) or not 0 <= v <= 8:
+                raise RtError(f"denoise_dual: {name} must be an int in 0 .. 8, it is {v!r}")
+            setattr(prm, name, v)
+    for name, v in (("sigma_variance", sigma_variance), ("sigma_depth", sigma_depth)):
+        if v is not None:
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.floating)) or not (np.isfinite(v) and v > 0):
+                raise RtError(f"denoise_dual: {name} must be a finite positive number, it is {v!r}")
+            setattr(prm, name, float(v))
+    need = denoise_dual_scratch_bytes(width, height)
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.uint8, device=device)
+    elif not isinstance(scratch, torch.Tensor) or not scratch.is_cuda or scratch.device != device:
+        raise RtError("denoise_dual: scratch must be a torch tensor on the GPU of the sums")
+    elif scratch.dtype != torch.uint8 or not scratch.is_contiguous() or scratch.numel() < need:
+        raise RtError(f"denoise_dual: scratch must be a contiguous torch.uint8 tensor of at least {need} bytes, it is {tuple(scratch.shape)} {scratch.dtype}")
+    if out is None:
+        out = torch.empty((n, 3), dtype=torch.float32, device=device)
+    elif not isinstance(out, torch.Tensor) or not out.is_cuda or out.device != device:
+        raise RtError("denoise_dual: out must be a torch tensor on the GPU of the sums")
+    elif out.dtype != torch.float32 or tuple(out.shape) != (n, 3) or not out.is_contiguous():
+        raise RtError(f"denoise_dual: out must be a contiguous ({n}, 3) torch.float32 tensor, it is {tuple(out.shape)} {out.dtype}")
+    s = torch.cuda.current_stream(device) if stream is None else stream
+    with torch.cuda.device(device):
+        _check(lib().rt_denoise_dual_fixed(ctypes.c_void_p(beauty_a.data_ptr()), spp_a, ctypes.c_void_p(beauty_b.data_ptr()), spp_b,
+                                           ctypes.c_void_p(aov_sums.data_ptr()), aov_spp, width, height, ctypes.byref(prm),
+                                           ctypes.c_void_p(scratch.data_ptr()), ctypes.c_void_p(out.data_ptr()),
+                                           ctypes.c_void_p(s.cuda_stream or None)), "rt_denoise_dual_fixed")
     return out
 
 

@@ -1,7 +1,7 @@
 // rt_denoise.h -- the per-pixel and per-tap arithmetic of rt_denoise_fixed (include/rtcuda_amd.h), as a
 // fixed sequence of individually rounded fp32 operations (no FMA: every translation unit that includes it is compiled with
 // -ffp-contract=off).  The kernels (rt_denoise_kernels.inc) and the CPU twin (hc_denoise, rt_host_check.cpp) both call these
-// three functions and differ only in who walks the pixels.
+// three functions and differ only in who walks the pixels.  rt_denoise_dual_fixed's additions follow them.
 //
 // Plain C subset; usable from g++ (host) and hipcc (device).
 #ifndef RT_DENOISE_H
@@ -66,6 +66,60 @@ RT_HD float dn_tap_weight(float h, const float *up, float zp, const float *np, c
 // Step 4: out = u * d + e, two operations per channel.
 RT_HD void dn_finish(const float *u, const float *d, const float *e, float *out3) {
     for (int k = 0; k < 3; k++) out3[k] = u[k] * d[k] + e[k];
+}
+
+// ---- rt_denoise_dual_fixed (include/rtcuda_amd.h): two half frames, a variance channel v next to u, a colour stop measured in
+// standard deviations of the local estimate.  Shared by the kernels k_*_dual / k_atrous_var* and the CPU twin hc_denoise_dual.
+// Both keep {u.x, u.y, u.z, v} as four consecutive floats per pixel, which is what dn_var_blur indexes.
+#define DN_VAR_EPS 1.4901161193847656e-08f  // 2^-26
+
+// Steps 1 and 2: the pixel of the wrapped sum S = A + B (exactly dn_prepare's for (S, n)) and the variance of the mean, from
+// u_a and u_b formed like u with the same d and e.  inv_a = 1.f / samples_a, inv_b = 1.f / samples_b, inv_n = 1.f / n.
+RT_HD float dn_prepare_dual(const int64_t *sum_a3, const int64_t *sum_b3, const int64_t *aov11, float inv_a, float inv_b, float inv_n,
+                            float inv_aov, float kv, DnPixel *px) {
+    int64_t s[3];
+    for (int k = 0; k < 3; k++) s[k] = (int64_t)((uint64_t)sum_a3[k] + (uint64_t)sum_b3[k]);
+    dn_prepare(s, aov11, inv_n, inv_aov, px);
+    float sq[3];
+    for (int k = 0; k < 3; k++) {
+        const float ta = dn_fixed_to_float(sum_a3[k]) * inv_a - px->e[k];
+        const float tb = dn_fixed_to_float(sum_b3[k]) * inv_b - px->e[k];
+        const float ua = (ta > 0.f ? ta : 0.f) / px->d[k];
+        const float ub = (tb > 0.f ? tb : 0.f) / px->d[k];
+        const float df = ua - ub;
+        sq[k] = df * df;
+    }
+    return ((sq[0] + sq[1]) + sq[2]) * kv;
+}
+
+// the 3 x 3 prefilter's kernel {1/4, 1/2, 1/4}: every product of two of them is exact
+RT_HD float dn_var_blur_weight(int dx /* -1 .. 1 */, int dy) { return (dx == 0 ? 0.5f : 0.25f) * (dy == 0 ? 0.5f : 0.25f); }
+
+// Step 3, the prefilter: g of pixel (x, y) from the pass's input, taps at stride 1 whatever the pass's stride.
+RT_HD float dn_var_blur(const float *uv /* 4 floats per pixel, v the fourth */, long long x, long long y, int width, int height) {
+    float sg = 0.f, sk = 0.f;
+    for (int dy = -1; dy <= 1; dy++) {
+        const long long yy = y + dy;
+        if (yy < 0 || yy >= height) continue;
+        for (int dx = -1; dx <= 1; dx++) {
+            const long long xx = x + dx;
+            if (xx < 0 || xx >= width) continue;
+            const float k = dn_var_blur_weight(dx, dy);
+            sg = sg + k * uv[4 * (yy * width + xx) + 3];
+            sk = sk + k;
+        }
+    }
+    return sg / sk;
+}
+
+// r = 1.f / (ks * g + 2^-26): what a pixel's colour distances are multiplied by.  One division per pixel.
+RT_HD float dn_var_rcp(float ks, float g) { return 1.f / (ks * g + DN_VAR_EPS); }
+
+// One tap that is not the centre: dn_tap_weight with the pixel's r in the place of the pass's kc -- x_v = (|du|^2) * r is the
+// same three operations as x_c.
+RT_HD float dn_tap_weight_var(float h, const float *up, float zp, const float *np, const float *uq, float zq, const float *nq, float r,
+                              float kz, int normal_power_log2) {
+    return dn_tap_weight(h, up, zp, np, uq, zq, nq, r, kz, normal_power_log2);
 }
 
 #endif  // RT_DENOISE_H

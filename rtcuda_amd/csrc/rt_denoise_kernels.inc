@@ -129,3 +129,137 @@ __global__ void __launch_bounds__(kBlock) k_dn_finish(const float4 *__restrict__
     const float u[3] = {r.x, r.y, r.z};
     dn_finish(u, px.d, px.e, out + 3 * p);
 }
+
+// ---- rt_denoise_dual_fixed: the same machinery with a variance channel.  Scratch: {u.x, u.y, u.z, v} twice, {n.x, n.y, n.z, z}
+// once (a tap is still two dwordx4 loads) and one float r per pixel.  Where a pixel's r = 1 / (ks * g + 2^-26) comes from is a
+// template parameter of both pass forms.  kInlineG = true blurs the nine v around p in the pass itself, nine dword loads from
+// the pass's input in global memory: lines the wave's taps touch anyway in the direct form and in the LDS form at stride 1; in
+// the LDS form at larger strides the stride-1 neighbours are not in the residue's tile and each load touches a line per lane
+// or two.  kInlineG = false reads the r that k_dn_var_blur wrote for the whole frame before the pass.  The same function of the
+// same values: the same bits.  Which placement a pass runs: dn_dual_inline_g_wins (rt_host_denoise.inc), from
+// profiles/denoise_dual_time.json.  (Not built: taking the nine v from the staged tile in the LDS form at stride 1.)
+__global__ void __launch_bounds__(kBlock) k_dn_prepare_dual(const long long *__restrict__ sum_a, const long long *__restrict__ sum_b,
+                                                             const long long *__restrict__ aov, long long n_pixels, float inv_a,
+                                                             float inv_b, float inv_n, float inv_aov, float kv,
+                                                             float4 *__restrict__ uv, float4 *__restrict__ nz) {
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_pixels) return;
+    DnPixel px;
+    const float v = dn_prepare_dual((const int64_t *)sum_a + 3 * p, (const int64_t *)sum_b + 3 * p,
+                                    (const int64_t *)aov + DN_AOV_CHANNELS * p, inv_a, inv_b, inv_n, inv_aov, kv, &px);
+    uv[p] = make_float4(px.u[0], px.u[1], px.u[2], v);
+    nz[p] = make_float4(px.n[0], px.n[1], px.n[2], px.z);
+}
+
+__global__ void __launch_bounds__(kBlock) k_dn_var_blur(const float4 *__restrict__ src, float *__restrict__ r_out, int width, int height,
+                                                         long long n_pixels, float ks) {
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_pixels) return;
+    const long long y = p / width, x = p - y * width;
+    r_out[p] = dn_var_rcp(ks, dn_var_blur((const float *)src, x, y, width, height));
+}
+
+template <bool kInlineG>
+__global__ void __launch_bounds__(kBlock) k_atrous_var(const float4 *__restrict__ src, const float4 *__restrict__ nz,
+                                                        const float *__restrict__ r_in, float4 *__restrict__ dst, int width, int height,
+                                                        int tiles_x, int stride, float ks, float kz, int normal_power_log2) {
+    const int tile_y = (int)(blockIdx.x / (unsigned)tiles_x), tile_x = (int)(blockIdx.x - (unsigned)tile_y * (unsigned)tiles_x);
+    const int x = tile_x * kDnTileW + (int)(threadIdx.x % kDnTileW);
+    const long long y = (long long)tile_y * kDnTileH + (int)(threadIdx.x / kDnTileW);
+    if (x >= width || y >= height) return;
+    const long long p = y * width + x;
+    const float4 c = src[p], cn = nz[p];
+    const float r = kInlineG ? dn_var_rcp(ks, dn_var_blur((const float *)src, x, y, width, height)) : r_in[p];
+    const float up[3] = {c.x, c.y, c.z}, np[3] = {cn.x, cn.y, cn.z};
+    float sw = 0.f, sv = 0.f, su[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+    for (int dy = -2; dy <= 2; dy++) {
+        const long long yy = y + (long long)stride * dy;
+        if (yy < 0 || yy >= height) continue;
+#pragma unroll
+        for (int dx = -2; dx <= 2; dx++) {
+            const long long xx = (long long)x + (long long)stride * dx;
+            if (xx < 0 || xx >= width) continue;
+            const float h = dn_kernel(dx) * dn_kernel(dy);
+            float w = h, vq = c.w;
+            float uq[3] = {up[0], up[1], up[2]};
+            if (dx != 0 || dy != 0) {
+                const long long q = yy * width + xx;
+                const float4 t = src[q], tn = nz[q];
+                const float nq[3] = {tn.x, tn.y, tn.z};
+                uq[0] = t.x, uq[1] = t.y, uq[2] = t.z, vq = t.w;
+                w = dn_tap_weight_var(h, up, cn.w, np, uq, tn.w, nq, r, kz, normal_power_log2);
+            }
+            sw = sw + w;
+            for (int k = 0; k < 3; k++) su[k] = su[k] + w * uq[k];
+            sv = sv + (w * w) * vq;
+        }
+    }
+    dst[p] = make_float4(su[0] / sw, su[1] / sw, su[2] / sw, sv / (sw * sw));
+}
+
+template <bool kInlineG>
+__global__ void __launch_bounds__(kBlock) k_atrous_var_lds(const float4 *__restrict__ src, const float4 *__restrict__ nz,
+                                                            const float *__restrict__ r_in, float4 *__restrict__ dst, int width,
+                                                            int height, int stride, int n_rx, int n_res, int lat_tiles_x, float ks,
+                                                            float kz, int normal_power_log2) {
+    __shared__ float4 s_uv[kDnLdsH][kDnLdsW], s_nz[kDnLdsH][kDnLdsW];
+    const unsigned tile = blockIdx.x / (unsigned)n_res, res = blockIdx.x - tile * (unsigned)n_res;
+    const int ry = (int)(res / (unsigned)n_rx), rx = (int)(res - (unsigned)ry * (unsigned)n_rx);
+    const int tile_y = (int)(tile / (unsigned)lat_tiles_x), tile_x = (int)(tile - (unsigned)tile_y * (unsigned)lat_tiles_x);
+    const long long lx0 = (long long)tile_x * kDnTileW - kDnHalo, ly0 = (long long)tile_y * kDnTileH - kDnHalo;
+    for (int i = (int)threadIdx.x; i < kDnLdsW * kDnLdsH; i += kBlock) {
+        const int cy = i / kDnLdsW, cx = i - cy * kDnLdsW;
+        const long long gx = rx + (long long)stride * (lx0 + cx), gy = ry + (long long)stride * (ly0 + cy);
+        if (gx >= 0 && gx < width && gy >= 0 && gy < height) {  // (a cell outside the image is never read: its tap is skipped)
+            const long long q = gy * width + gx;
+            s_uv[cy][cx] = src[q];
+            s_nz[cy][cx] = nz[q];
+        }
+    }
+    __syncthreads();
+    const int tx = (int)(threadIdx.x % kDnTileW), ty = (int)(threadIdx.x / kDnTileW);
+    const long long x = rx + (long long)stride * (lx0 + kDnHalo + tx), y = ry + (long long)stride * (ly0 + kDnHalo + ty);
+    if (x >= width || y >= height) return;
+    const float4 c = s_uv[ty + kDnHalo][tx + kDnHalo], cn = s_nz[ty + kDnHalo][tx + kDnHalo];
+    const float r = kInlineG ? dn_var_rcp(ks, dn_var_blur((const float *)src, x, y, width, height)) : r_in[y * width + x];
+    const float up[3] = {c.x, c.y, c.z}, np[3] = {cn.x, cn.y, cn.z};
+    float sw = 0.f, sv = 0.f, su[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+    for (int dy = -2; dy <= 2; dy++) {
+        const long long yy = y + (long long)stride * dy;
+        if (yy < 0 || yy >= height) continue;
+#pragma unroll
+        for (int dx = -2; dx <= 2; dx++) {
+            const long long xx = x + (long long)stride * dx;
+            if (xx < 0 || xx >= width) continue;
+            const float h = dn_kernel(dx) * dn_kernel(dy);
+            float w = h, vq = c.w;
+            float uq[3] = {up[0], up[1], up[2]};
+            if (dx != 0 || dy != 0) {
+                const float4 t = s_uv[ty + kDnHalo + dy][tx + kDnHalo + dx], tn = s_nz[ty + kDnHalo + dy][tx + kDnHalo + dx];
+                const float nq[3] = {tn.x, tn.y, tn.z};
+                uq[0] = t.x, uq[1] = t.y, uq[2] = t.z, vq = t.w;
+                w = dn_tap_weight_var(h, up, cn.w, np, uq, tn.w, nq, r, kz, normal_power_log2);
+            }
+            sw = sw + w;
+            for (int k = 0; k < 3; k++) su[k] = su[k] + w * uq[k];
+            sv = sv + (w * w) * vq;
+        }
+    }
+    dst[y * width + x] = make_float4(su[0] / sw, su[1] / sw, su[2] / sw, sv / (sw * sw));
+}
+
+__global__ void __launch_bounds__(kBlock) k_dn_finish_dual(const float4 *__restrict__ uv, const long long *__restrict__ sum_a,
+                                                            const long long *__restrict__ sum_b, const long long *__restrict__ aov,
+                                                            long long n_pixels, float inv_n, float inv_aov, float *__restrict__ out) {
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_pixels) return;
+    int64_t s[3];
+    for (int k = 0; k < 3; k++) s[k] = (int64_t)((uint64_t)sum_a[3 * p + k] + (uint64_t)sum_b[3 * p + k]);
+    DnPixel px;
+    dn_prepare(s, (const int64_t *)aov + DN_AOV_CHANNELS * p, inv_n, inv_aov, &px);
+    const float4 r = uv[p];
+    const float u[3] = {r.x, r.y, r.z};
+    dn_finish(u, px.d, px.e, out + 3 * p);
+}

@@ -16,6 +16,7 @@
 //   * rt_slot_chunk_*   the chunked deal of k_paths (rt_slot_chunks.h): task -> slot, the static deal's slots, the counts and
 //     the decisions, as the kernel makes them.
 //   * hc_denoise / hc_expnegf  the CPU twin of rt_denoise_fixed: a serial loop over rt_denoise.h, the arithmetic of the kernels.
+//   * hc_denoise_dual   the CPU twin of rt_denoise_dual_fixed, likewise.
 #include <cfloat>
 #include <cmath>
 #include <cstdint>
@@ -982,5 +983,62 @@ int hc_denoise(const int64_t *sum_fixed, int num_samples, const int64_t *aov_fix
 // rt_expnegf on n values (tests/test_denoise_host.py holds it to its numpy restatement and to exp)
 void hc_expnegf(const float *x, float *y, int n) {
     for (int k = 0; k < n; k++) y[k] = rt_expnegf(x[k]);
+}
+// The CPU twin of rt_denoise_dual_fixed (tests/test_denoise_dual_host.py, tools/denoise_dual_quality.py): a serial loop over
+// rt_denoise.h, host buffers throughout, the same checks of the parameters.  var_out (may be null): the final v per pixel.
+// Returns 0, or 1 and writes nothing.
+int hc_denoise_dual(const int64_t *sum_a, int samples_a, const int64_t *sum_b, int samples_b, const int64_t *aov_fixed, int aov_samples,
+                    int width, int height, int passes, float sigma_variance, float sigma_depth, int normal_power_log2, float *rgb_out,
+                    float *var_out) {
+    if (!sum_a || !sum_b || !aov_fixed || !rgb_out || width < 1 || height < 1 || samples_a < 1 || samples_b < 1 || aov_samples < 1) return 1;
+    if ((long long)samples_a + samples_b > 0x7fffffffll) return 1;
+    if (passes < 0 || passes > DN_MAX_PASSES || normal_power_log2 < 0 || normal_power_log2 > DN_MAX_NORMAL_POWER_LOG2) return 1;
+    if (!(std::isfinite(sigma_variance) && sigma_variance > 0.f && std::isfinite(sigma_depth) && sigma_depth > 0.f)) return 1;
+    const float ks = sigma_variance * sigma_variance, sd2 = sigma_depth * sigma_depth;
+    const float kz = 1.f / sd2;
+    if (!(std::isfinite(ks) && ks > 0.f && std::isfinite(kz) && kz > 0.f)) return 1;
+    const int ns = samples_a + samples_b;
+    const float kv = (float)((double)samples_a * (double)samples_b / ((double)ns * (double)ns));
+    const float inv_a = 1.f / (float)samples_a, inv_b = 1.f / (float)samples_b, inv_n = 1.f / (float)ns, inv_aov = 1.f / (float)aov_samples;
+    const size_t n = (size_t)width * (size_t)height;
+    std::vector<DnPixel> px(n);
+    std::vector<float> uv(4 * n), next(4 * n);
+    for (size_t p = 0; p < n; p++) {
+        uv[4 * p + 3] = dn_prepare_dual(sum_a + 3 * p, sum_b + 3 * p, aov_fixed + DN_AOV_CHANNELS * p, inv_a, inv_b, inv_n, inv_aov, kv, &px[p]);
+        for (int k = 0; k < 3; k++) uv[4 * p + k] = px[p].u[k];
+    }
+    for (int i = 0; i < passes; i++) {
+        const long long s = 1ll << i;
+        for (long long y = 0; y < height; y++)
+            for (long long x = 0; x < width; x++) {
+                const size_t p = (size_t)(y * width + x);
+                const float r = dn_var_rcp(ks, dn_var_blur(uv.data(), x, y, width, height));
+                float sw = 0.f, sv = 0.f, su[3] = {0.f, 0.f, 0.f};
+                for (int dy = -2; dy <= 2; dy++) {
+                    const long long yy = y + s * dy;
+                    if (yy < 0 || yy >= height) continue;
+                    for (int dx = -2; dx <= 2; dx++) {
+                        const long long xx = x + s * dx;
+                        if (xx < 0 || xx >= width) continue;
+                        const size_t q = (size_t)(yy * width + xx);
+                        const float h = dn_kernel(dx) * dn_kernel(dy);
+                        const float w = (dx == 0 && dy == 0) ? h
+                                                             : dn_tap_weight_var(h, &uv[4 * p], px[p].z, px[p].n, &uv[4 * q], px[q].z, px[q].n, r, kz,
+                                                                                 normal_power_log2);
+                        sw = sw + w;
+                        for (int k = 0; k < 3; k++) su[k] = su[k] + w * uv[4 * q + k];
+                        sv = sv + (w * w) * uv[4 * q + 3];
+                    }
+                }
+                for (int k = 0; k < 3; k++) next[4 * p + k] = su[k] / sw;
+                next[4 * p + 3] = sv / (sw * sw);
+            }
+        uv.swap(next);
+    }
+    for (size_t p = 0; p < n; p++) {
+        dn_finish(&uv[4 * p], px[p].d, px[p].e, rgb_out + 3 * p);
+        if (var_out) var_out[p] = uv[4 * p + 3];
+    }
+    return 0;
 }
 }

@@ -8,6 +8,7 @@
 //   rt_split_probe              "one persistent kernel, or the reference's stage split?" priced on dense ray / shade arrays
 //   rt_scene_tree_copy          a scene's unpadded 4-wide records and leaf order (the device builder against its host twin)
 //   rt_denoise_pass_time        one pass of the denoiser in one form, timed launch by launch
+//   rt_denoise_dual_pass_time   the same for the dual-buffer denoiser: form and placement of the variance prefilter
 //   rt_shade_table              the product's shading FUNCTIONS (rt_device.h), one lane per row of a function table
 //   rt_shade_records            the product's init() + mat() (advance_core, through k_probe_shade) on the caller's path states
 // The product library (librtcuda_amd.so) contains none of this.  The tools library also carries a private copy of the
@@ -830,6 +831,36 @@ int rt_denoise_pass_time(void *d_scratch, int width, int height, int stride, int
     for (int r = 0; r < reps; r++) {
         HIP_TRY(hipEventRecord(e0, nullptr));
         dn_launch_pass(form, uz, nrm, dst, width, height, stride, kc, kz, normal_power_log2, nullptr);
+        HIP_TRY(hipEventRecord(e1, nullptr));
+        HIP_TRY(hipEventSynchronize(e1));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventElapsedTime(&out_ms[r], e0, e1));
+    }
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    return 0;
+}
+
+// One pass of the dual-buffer denoiser, one form and one placement of the variance prefilter, timed launch by launch
+// (tools/denoise_dual_time.py).  d_scratch: the scratch of an rt_denoise_dual_fixed call with passes = 0 of the same frame -- its
+// first array holds the prepared {u, v}, its third {n, z}; the pass writes the second (and, with g_place = 2, the r array).
+int rt_denoise_dual_pass_time(void *d_scratch, int width, int height, int stride, int form, int g_place, float sigma_variance,
+                              float sigma_depth, int normal_power_log2, int reps, float *out_ms) {
+    if (!d_scratch || !out_ms || width < 1 || height < 1 || reps < 1) return fail("rt_denoise_dual_pass_time: bad argument");
+    if (stride < 1 || stride > 128 || (stride & (stride - 1)) || (form != 1 && form != 2) || (g_place != 1 && g_place != 2))
+        return fail("rt_denoise_dual_pass_time: bad stride, form or g_place");
+    if (denoise_dual_scratch_bytes(width, height) < 0) return fail("rt_denoise_dual_pass_time: bad frame size");
+    if (dn_pass_blocks(width, height, stride, form) > kDnMaxBlocks) return fail("rt_denoise_dual_pass_time: the grid of this form is too large");
+    const long long n = (long long)width * height;
+    float4 *uv = (float4 *)d_scratch, *dst = uv + n, *nz = uv + 2 * n;
+    float *r_buf = (float *)(uv + 3 * n);
+    const float ks = sigma_variance * sigma_variance, kz = 1.f / (sigma_depth * sigma_depth);
+    hipEvent_t e0, e1;
+    HIP_TRY(hipEventCreate(&e0));
+    HIP_TRY(hipEventCreate(&e1));
+    for (int r = 0; r < reps; r++) {
+        HIP_TRY(hipEventRecord(e0, nullptr));
+        dn_launch_dual_pass(form, g_place == 1, uv, nz, r_buf, dst, width, height, stride, ks, kz, normal_power_log2, nullptr);
         HIP_TRY(hipEventRecord(e1, nullptr));
         HIP_TRY(hipEventSynchronize(e1));
         HIP_TRY(hipGetLastError());

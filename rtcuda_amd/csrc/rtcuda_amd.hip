@@ -9,7 +9,7 @@
 //                          points on top of it (create, update, rebuild, the edits); what the ray entry points share
 //   rt_host_render.inc     Context, kernel selection, frames, test rays, queries, ray tables, AOVs
 //   rt_denoise_kernels.inc k_dn_prepare, k_atrous, k_dn_finish (arithmetic: rt_denoise.h, shared with the CPU twin)
-//   rt_host_denoise.inc    rt_denoise_fixed: checks, pass constants, launches
+//   rt_host_denoise.inc    rt_denoise_fixed and rt_denoise_dual_fixed: checks, pass constants, launches
 // The C-ABI below them only checks arguments and forwards.
 //
 // The hot path of lashhw/rtcuda (render.cuh:61-457) re-designed for CDNA4:
@@ -873,11 +873,11 @@ __global__ void k_test_draw(DPools p, int n, int draws, uint32_t *__restrict__ s
     state6[6 * (size_t)i + 5] = rs.v4;
 }
 #include "rt_build_kernels.inc"   // device BVH: the leaf-order arrays, refit (k_refit_*), build (k_ploc_*)
-#include "rt_denoise_kernels.inc"  // k_dn_prepare, k_atrous, k_dn_finish
+#include "rt_denoise_kernels.inc"  // k_dn_prepare, k_atrous, k_dn_finish; k_dn_prepare_dual, k_dn_var_blur, k_atrous_var, k_dn_finish_dual
 
 #include "rt_host_scene.inc"   // (opens the anonymous namespace that is closed below) rt_scene: reference tree, checks, build / emit / adopt, create, update, rebuild, edits; what the ray entry points share
 #include "rt_host_render.inc"  // Context, kernel selection, frames, test rays, queries, ray tables, AOVs
-#include "rt_host_denoise.inc"  // rt_denoise_fixed
+#include "rt_host_denoise.inc"  // rt_denoise_fixed, rt_denoise_dual_fixed
 }  // namespace
 
 // ============================================================================ C-ABI
@@ -1104,6 +1104,21 @@ int rt_denoise_fixed(const int64_t *d_sum_fixed, int num_samples, const int64_t 
                      const rt_denoise_params *params, void *d_scratch, float *d_rgb_out, void *stream) {
     return denoise_impl(d_sum_fixed, num_samples, d_aov_fixed, aov_samples, width, height, params, d_scratch, d_rgb_out,
                         (hipStream_t)stream);
+}
+
+int64_t rt_denoise_dual_scratch_bytes(int width, int height) { return denoise_dual_scratch_bytes(width, height); }
+
+int rt_denoise_dual_default_params(rt_denoise_dual_params *out) {
+    if (!out) return fail("rt_denoise_dual_default_params: null out");
+    *out = denoise_dual_defaults();
+    return 0;
+}
+
+int rt_denoise_dual_fixed(const int64_t *d_sum_a, int samples_a, const int64_t *d_sum_b, int samples_b, const int64_t *d_aov_fixed,
+                          int aov_samples, int width, int height, const rt_denoise_dual_params *params, void *d_scratch,
+                          float *d_rgb_out, void *stream) {
+    return denoise_dual_impl(d_sum_a, samples_a, d_sum_b, samples_b, d_aov_fixed, aov_samples, width, height, params, d_scratch,
+                             d_rgb_out, (hipStream_t)stream);
 }
 
 int rt_post_process(float *d_rgb, int num_pixels, int num_samples, void *stream) {
