@@ -791,22 +791,84 @@ def aov_resolve(sums, spp: int, stream=None):
     return out
 
 
+def _dn_default_params(me: str, params, sigma: str) -> dict:
+    _check(getattr(lib(), f"rt_{me}_default_params")(ctypes.byref(params)), f"rt_{me}_default_params")
+    return {"passes": int(params.passes), sigma: float(getattr(params, sigma)), "sigma_depth": float(params.sigma_depth),
+            "normal_power_log2": int(params.normal_power_log2)}
+
+
+def _dn_scratch_bytes(me: str, width, height) -> int:
+    if not isinstance(width, int) or not isinstance(height, int):
+        raise RtError(f"{me}_scratch_bytes: width and height must be ints, they are {width!r}, {height!r}")
+    n = int(getattr(lib(), f"rt_{me}_scratch_bytes")(width, height))
+    if n < 0:
+        raise RtError(f"{me}_scratch_bytes: bad frame size {width} x {height}")
+    return n
+
+
+def _dn_positive_ints(me: str, named) -> None:
+    for name, v in named:
+        if not isinstance(v, int) or isinstance(v, bool) or v < 1:
+            raise RtError(f"{me}: {name} must be a positive int, it is {v!r}")
+
+
+def _dn_sums(me: str, n: int, named):
+    """The checks of the sums tensors ((name, tensor, channels), the first names the GPU of the call) -> that GPU."""
+    import torch
+    for name, t, ch in named:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RtError(f"{me}: {name} must be a torch tensor on a GPU")
+        if t.dtype != torch.int64 or tuple(t.shape) != (n, ch) or not t.is_contiguous():
+            raise RtError(f"{me}: {name} must be a contiguous ({n}, {ch}) torch.int64 tensor, it is {tuple(t.shape)} {t.dtype}")
+    first, device = named[0][0], named[0][1].device
+    for name, t, _ in named[1:]:
+        if t.device != device:
+            raise RtError(f"{me}: {name} is on {t.device}, {first} on {device}")
+    return device
+
+
+def _dn_params(me: str, prm, ints, sigmas):
+    """``prm`` (a ctypes parameter struct) as the library's defaults, overwritten by the (name, value) pairs that are not None."""
+    _check(getattr(lib(), f"rt_{me}_default_params")(ctypes.byref(prm)), f"rt_{me}_default_params")
+    for name, v in ints:
+        if v is not None:
+            if not isinstance(v, int) or isinstance(v, bool) or not 0 <= v <= 8:
+                raise RtError(f"{me}: {name} must be an int in 0 .. 8, it is {v!r}")
+            setattr(prm, name, v)
+    for name, v in sigmas:
+        if v is not None:
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.floating)) or not (np.isfinite(v) and v > 0):
+                raise RtError(f"{me}: {name} must be a finite positive number, it is {v!r}")
+            setattr(prm, name, float(v))
+    return prm
+
+
+def _dn_buffers(me: str, need: int, n: int, device, scratch, out, stream):
+    """``scratch`` and ``out`` checked, or made on ``device``, and the stream of the call."""
+    import torch
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.uint8, device=device)
+    elif not isinstance(scratch, torch.Tensor) or not scratch.is_cuda or scratch.device != device:
+        raise RtError(f"{me}: scratch must be a torch tensor on the GPU of the sums")
+    elif scratch.dtype != torch.uint8 or not scratch.is_contiguous() or scratch.numel() < need:
+        raise RtError(f"{me}: scratch must be a contiguous torch.uint8 tensor of at least {need} bytes, it is {tuple(scratch.shape)} {scratch.dtype}")
+    if out is None:
+        out = torch.empty((n, 3), dtype=torch.float32, device=device)
+    elif not isinstance(out, torch.Tensor) or not out.is_cuda or out.device != device:
+        raise RtError(f"{me}: out must be a torch tensor on the GPU of the sums")
+    elif out.dtype != torch.float32 or tuple(out.shape) != (n, 3) or not out.is_contiguous():
+        raise RtError(f"{me}: out must be a contiguous ({n}, 3) torch.float32 tensor, it is {tuple(out.shape)} {out.dtype}")
+    return scratch, out, torch.cuda.current_stream(device) if stream is None else stream
+
+
 def denoise_default_params() -> dict:
     """The parameters rt_denoise_fixed uses when it is given none (rt_denoise_default_params)."""
-    p = RtDenoiseParams()
-    _check(lib().rt_denoise_default_params(ctypes.byref(p)), "rt_denoise_default_params")
-    return dict(passes=int(p.passes), sigma_color=float(p.sigma_color), sigma_depth=float(p.sigma_depth),
-                normal_power_log2=int(p.normal_power_log2))
+    return _dn_default_params("denoise", RtDenoiseParams(), "sigma_color")
 
 
 def denoise_scratch_bytes(width: int, height: int) -> int:
     """Bytes of scratch rt_denoise_fixed needs for a width x height frame (rt_denoise_scratch_bytes)."""
-    if not isinstance(width, int) or not isinstance(height, int):
-        raise RtError(f"denoise_scratch_bytes: width and height must be ints, they are {width!r}, {height!r}")
-    n = int(lib().rt_denoise_scratch_bytes(width, height))
-    if n < 0:
-        raise RtError(f"denoise_scratch_bytes: bad frame size {width} x {height}")
-    return n
+    return _dn_scratch_bytes("denoise", width, height)
 
 
 def denoise(beauty_sums, spp: int, aov_sums, aov_spp: int, width: int, height: int, *, passes=None, sigma_color=None,
@@ -818,44 +880,13 @@ def denoise(beauty_sums, spp: int, aov_sums, aov_spp: int, width: int, height: i
     torch.uint8 tensor of at least denoise_scratch_bytes(width, height) bytes to reuse between calls (made here otherwise);
     ``out``: the result tensor to fill; ``stream``: a torch.cuda.Stream (the current one otherwise)."""
     import torch
-    for name, v in (("width", width), ("height", height), ("spp", spp), ("aov_spp", aov_spp)):
-        if not isinstance(v, int) or isinstance(v, bool) or v < 1:
-            raise RtError(f"denoise: {name} must be a positive int, it is {v!r}")
+    me = "denoise"
+    _dn_positive_ints(me, (("width", width), ("height", height), ("spp", spp), ("aov_spp", aov_spp)))
     n = width * height
-    for name, t, ch in (("beauty_sums", beauty_sums, 3), ("aov_sums", aov_sums, AOV_CHANNELS)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise RtError(f"denoise: {name} must be a torch tensor on a GPU")
-        if t.dtype != torch.int64 or tuple(t.shape) != (n, ch) or not t.is_contiguous():
-            raise RtError(f"denoise: {name} must be a contiguous ({n}, {ch}) torch.int64 tensor, it is {tuple(t.shape)} {t.dtype}")
-    device = beauty_sums.device
-    if aov_sums.device != device:
-        raise RtError(f"denoise: aov_sums is on {aov_sums.device}, beauty_sums on {device}")
-    prm = RtDenoiseParams()
-    _check(lib().rt_denoise_default_params(ctypes.byref(prm)), "rt_denoise_default_params")
-    for name, v in (("passes", passes), ("normal_power_log2", normal_power_log2)):
-        if v is not None:
-            if not isinstance(v, int) or isinstance(v, bool) or not 0 <= v <= 8:
-                raise RtError(f"denoise: {name} must be an int in 0 .. 8, it is {v!r}")
-            setattr(prm, name, v)
-    for name, v in (("sigma_color", sigma_color), ("sigma_depth", sigma_depth)):
-        if v is not None:
-            if isinstance(v, bool) or not isinstance(v, (int, float, np.floating)) or not (np.isfinite(v) and v > 0):
-                raise RtError(f"denoise: {name} must be a finite positive number, it is {v!r}")
-            setattr(prm, name, float(v))
-    need = denoise_scratch_bytes(width, height)
-    if scratch is None:
-        scratch = torch.empty(need, dtype=torch.uint8, device=device)
-    elif not isinstance(scratch, torch.Tensor) or not scratch.is_cuda or scratch.device != device:
-        raise RtError("denoise: scratch must be a torch tensor on the GPU of the sums")
-    elif scratch.dtype != torch.uint8 or not scratch.is_contiguous() or scratch.numel() < need:
-        raise RtError(f"denoise: scratch must be a contiguous torch.uint8 tensor of at least {need} bytes, it is {tuple(scratch.shape)} {scratch.dtype}")
-    if out is None:
-        out = torch.empty((n, 3), dtype=torch.float32, device=device)
-    elif not isinstance(out, torch.Tensor) or not out.is_cuda or out.device != device:
-        raise RtError("denoise: out must be a torch tensor on the GPU of the sums")
-    elif out.dtype != torch.float32 or tuple(out.shape) != (n, 3) or not out.is_contiguous():
-        raise RtError(f"denoise: out must be a contiguous ({n}, 3) torch.float32 tensor, it is {tuple(out.shape)} {out.dtype}")
-    s = torch.cuda.current_stream(device) if stream is None else stream
+    device = _dn_sums(me, n, (("beauty_sums", beauty_sums, 3), ("aov_sums", aov_sums, AOV_CHANNELS)))
+    prm = _dn_params(me, RtDenoiseParams(), (("passes", passes), ("normal_power_log2", normal_power_log2)),
+                     (("sigma_color", sigma_color), ("sigma_depth", sigma_depth)))
+    scratch, out, s = _dn_buffers(me, denoise_scratch_bytes(width, height), n, device, scratch, out, stream)
     with torch.cuda.device(device):
         _check(lib().rt_denoise_fixed(ctypes.c_void_p(beauty_sums.data_ptr()), spp, ctypes.c_void_p(aov_sums.data_ptr()), aov_spp,
                                       width, height, ctypes.byref(prm), ctypes.c_void_p(scratch.data_ptr()),
@@ -865,20 +896,12 @@ def denoise(beauty_sums, spp: int, aov_sums, aov_spp: int, width: int, height: i
 
 def denoise_dual_default_params() -> dict:
     """The parameters rt_denoise_dual_fixed uses when it is given none (rt_denoise_dual_default_params)."""
-    p = RtDenoiseDualParams()
-    _check(lib().rt_denoise_dual_default_params(ctypes.byref(p)), "rt_denoise_dual_default_params")
-    return dict(passes=int(p.passes), sigma_variance=float(p.sigma_variance), sigma_depth=float(p.sigma_depth),
-                normal_power_log2=int(p.normal_power_log2))
+    return _dn_default_params("denoise_dual", RtDenoiseDualParams(), "sigma_variance")
 
 
 def denoise_dual_scratch_bytes(width: int, height: int) -> int:
     """Bytes of scratch rt_denoise_dual_fixed needs for a width x height frame (rt_denoise_dual_scratch_bytes)."""
-    if not isinstance(width, int) or not isinstance(height, int):
-        raise RtError(f"denoise_dual_scratch_bytes: width and height must be ints, they are {width!r}, {height!r}")
-    n = int(lib().rt_denoise_dual_scratch_bytes(width, height))
-    if n < 0:
-        raise RtError(f"denoise_dual_scratch_bytes: bad frame size {width} x {height}")
-    return n
+    return _dn_scratch_bytes("denoise_dual", width, height)
 
 
 def denoise_dual(beauty_a, spp_a: int, beauty_b, spp_b: int, aov_sums, aov_spp: int, width: int, height: int, *, passes=None,
@@ -893,47 +916,15 @@ def denoise_dual(beauty_a, spp_a: int, beauty_b, spp_b: int, aov_sums, aov_spp: 
     denoise_dual_scratch_bytes(width, height) bytes to reuse between calls (made here otherwise); ``out``: the result tensor to
     fill; ``stream``: a torch.cuda.Stream (the current one otherwise)."""
     import torch
-    for name, v in (("width", width), ("height", height), ("spp_a", spp_a), ("spp_b", spp_b), ("aov_spp", aov_spp)):
-        if not isinstance(v, int) or isinstance(v, bool) or v < 1:
-            raise RtError(f"denoise_dual: {name} must be a positive int, it is {v!r}")
+    me = "denoise_dual"
+    _dn_positive_ints(me, (("width", width), ("height", height), ("spp_a", spp_a), ("spp_b", spp_b), ("aov_spp", aov_spp)))
     if spp_a + spp_b > 0x7FFFFFFF:
         raise RtError(f"denoise_dual: spp_a + spp_b must fit an int32, they are {spp_a} + {spp_b}")
     n = width * height
-    for name, t, ch in (("beauty_a", beauty_a, 3), ("beauty_b", beauty_b, 3), ("aov_sums", aov_sums, AOV_CHANNELS)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise RtError(f"denoise_dual: {name} must be a torch tensor on a GPU")
-        if t.dtype != torch.int64 or tuple(t.shape) != (n, ch) or not t.is_contiguous():
-            raise RtError(f"denoise_dual: {name} must be a contiguous ({n}, {ch}) torch.int64 tensor, it is {tuple(t.shape)} {t.dtype}")
-    device = beauty_a.device
-    for name, t in (("beauty_b", beauty_b), ("aov_sums", aov_sums)):
-        if t.device != device:
-            raise RtError(f"denoise_dual: {name} is on {t.device}, beauty_a on {device}")
-    prm = RtDenoiseDualParams()
-    _check(lib().rt_denoise_dual_default_params(ctypes.byref(prm)), "rt_denoise_dual_default_params")
-    for name, v in (("passes", passes), ("normal_power_log2", normal_power_log2)):
-        if v is not None:
-            if not isinstance(v, int) or isinstance(v, bool) or not 0 <= v <= 8:
-                raise RtError(f"denoise_dual: {name} must be an int in 0 .. 8, it is {v!r}")
-            setattr(prm, name, v)
-    for name, v in (("sigma_variance", sigma_variance), ("sigma_depth", sigma_depth)):
-        if v is not None:
-            if isinstance(v, bool) or not isinstance(v, (int, float, np.floating)) or not (np.isfinite(v) and v > 0):
-                raise RtError(f"denoise_dual: {name} must be a finite positive number, it is {v!r}")
-            setattr(prm, name, float(v))
-    need = denoise_dual_scratch_bytes(width, height)
-    if scratch is None:
-        scratch = torch.empty(need, dtype=torch.uint8, device=device)
-    elif not isinstance(scratch, torch.Tensor) or not scratch.is_cuda or scratch.device != device:
-        raise RtError("denoise_dual: scratch must be a torch tensor on the GPU of the sums")
-    elif scratch.dtype != torch.uint8 or not scratch.is_contiguous() or scratch.numel() < need:
-        raise RtError(f"denoise_dual: scratch must be a contiguous torch.uint8 tensor of at least {need} bytes, it is {tuple(scratch.shape)} {scratch.dtype}")
-    if out is None:
-        out = torch.empty((n, 3), dtype=torch.float32, device=device)
-    elif not isinstance(out, torch.Tensor) or not out.is_cuda or out.device != device:
-        raise RtError("denoise_dual: out must be a torch tensor on the GPU of the sums")
-    elif out.dtype != torch.float32 or tuple(out.shape) != (n, 3) or not out.is_contiguous():
-        raise RtError(f"denoise_dual: out must be a contiguous ({n}, 3) torch.float32 tensor, it is {tuple(out.shape)} {out.dtype}")
-    s = torch.cuda.current_stream(device) if stream is None else stream
+    device = _dn_sums(me, n, (("beauty_a", beauty_a, 3), ("beauty_b", beauty_b, 3), ("aov_sums", aov_sums, AOV_CHANNELS)))
+    prm = _dn_params(me, RtDenoiseDualParams(), (("passes", passes), ("normal_power_log2", normal_power_log2)),
+                     (("sigma_variance", sigma_variance), ("sigma_depth", sigma_depth)))
+    scratch, out, s = _dn_buffers(me, denoise_dual_scratch_bytes(width, height), n, device, scratch, out, stream)
     with torch.cuda.device(device):
         _check(lib().rt_denoise_dual_fixed(ctypes.c_void_p(beauty_a.data_ptr()), spp_a, ctypes.c_void_p(beauty_b.data_ptr()), spp_b,
                                            ctypes.c_void_p(aov_sums.data_ptr()), aov_spp, width, height, ctypes.byref(prm),

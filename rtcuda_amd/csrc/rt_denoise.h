@@ -115,11 +115,7 @@ RT_HD float dn_var_blur(const float *uv /* 4 floats per pixel, v the fourth */, 
 // r = 1.f / (ks * g + 2^-26): what a pixel's colour distances are multiplied by.  One division per pixel.
 RT_HD float dn_var_rcp(float ks, float g) { return 1.f / (ks * g + DN_VAR_EPS); }
 
-// One tap that is not the centre: dn_tap_weight with the pixel's r in the place of the pass's kc -- x_v = (|du|^2) * r is the
+// One tap that is not the centre is dn_tap_weight with the pixel's r in the place of the pass's kc -- x_v = (|du|^2) * r is the
 // same three operations as x_c.
-RT_HD float dn_tap_weight_var(float h, const float *up, float zp, const float *np, const float *uq, float zq, const float *nq, float r,
-                              float kz, int normal_power_log2) {
-    return dn_tap_weight(h, up, zp, np, uq, zq, nq, r, kz, normal_power_log2);
-}
 
 #endif  // RT_DENOISE_H

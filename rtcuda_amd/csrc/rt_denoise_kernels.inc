@@ -31,48 +31,71 @@ __global__ void __launch_bounds__(kBlock) k_dn_prepare(const long long *__restri
     nrm[p] = make_float4(px.n[0], px.n[1], px.n[2], 0.f);
 }
 
-__global__ void __launch_bounds__(kBlock) k_atrous(const float4 *__restrict__ src, const float4 *__restrict__ nrm,
-                                                    float4 *__restrict__ dst, int width, int height, int tiles_x, int stride,
-                                                    float kc, float kz, int normal_power_log2) {
+// The one tap loop: pixel (x, y) of a pass, from its own two records c and cn and whatever `tap` hands back for a neighbour.
+// kVar = false: rt_denoise_fixed, z rides in c.w / t.w and is passed on, k is the pass's kc.  kVar = true: rt_denoise_dual_fixed
+// (below), z rides in cn.w / tn.w, c.w / t.w is v and is filtered with w * w, k is the pixel's r.
+// tap(dx, dy, q, t, tn) fills in the two records of the neighbour (dx, dy), which is pixel q of the frame; x has the caller's type.
+template <bool kVar, typename X, typename Tap>
+__device__ __forceinline__ float4 dn_filter_pixel(X x, long long y, int width, int height, int stride, const float4 c, const float4 cn,
+                                                  float k, float kz, int normal_power_log2, Tap tap) {
+    const float up[3] = {c.x, c.y, c.z}, np[3] = {cn.x, cn.y, cn.z};
+    float sw = 0.f, sv = 0.f, su[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+    for (int dy = -2; dy <= 2; dy++) {
+        const long long yy = y + (long long)stride * dy;
+        if (yy < 0 || yy >= height) continue;
+        const long long row = yy * width;
+#pragma unroll
+        for (int dx = -2; dx <= 2; dx++) {
+            const long long xx = (long long)x + (long long)stride * dx;
+            if (xx < 0 || xx >= width) continue;
+            const float h = dn_kernel(dx) * dn_kernel(dy);
+            float w = h, vq = c.w;
+            float uq[3] = {up[0], up[1], up[2]};
+            if (dx != 0 || dy != 0) {
+                float4 t, tn;
+                tap(dx, dy, row + xx, t, tn);
+                const float nq[3] = {tn.x, tn.y, tn.z};
+                uq[0] = t.x, uq[1] = t.y, uq[2] = t.z, vq = t.w;
+                w = dn_tap_weight(h, up, kVar ? cn.w : c.w, np, uq, kVar ? tn.w : t.w, nq, k, kz, normal_power_log2);
+            }
+            sw = sw + w;
+            for (int i = 0; i < 3; i++) su[i] = su[i] + w * uq[i];
+            if (kVar) sv = sv + (w * w) * vq;
+        }
+    }
+    return make_float4(su[0] / sw, su[1] / sw, su[2] / sw, kVar ? sv / (sw * sw) : c.w);
+}
+
+// What a pixel's colour distances are multiplied by: the pass's kc, or the pixel's r (kInlineG: see rt_denoise_dual_fixed below)
+template <bool kVar, bool kInlineG, typename X>
+__device__ __forceinline__ float dn_colour_scale(const float4 *src, const float *r_in, X x, long long y, int width, int height, float k) {
+    if (!kVar) return k;
+    return kInlineG ? dn_var_rcp(k, dn_var_blur((const float *)src, x, y, width, height)) : r_in[y * width + x];
+}
+
+template <bool kVar, bool kInlineG>
+__device__ __forceinline__ void dn_pass_direct(const float4 *__restrict__ src, const float4 *__restrict__ nrm, const float *__restrict__ r_in,
+                                               float4 *__restrict__ dst, int width, int height, int tiles_x, int stride, float k, float kz,
+                                               int normal_power_log2) {
     const int tile_y = (int)(blockIdx.x / (unsigned)tiles_x), tile_x = (int)(blockIdx.x - (unsigned)tile_y * (unsigned)tiles_x);
     const int x = tile_x * kDnTileW + (int)(threadIdx.x % kDnTileW);
     const long long y = (long long)tile_y * kDnTileH + (int)(threadIdx.x / kDnTileW);
     if (x >= width || y >= height) return;
     const long long p = y * width + x;
     const float4 c = src[p], cn = nrm[p];
-    const float up[3] = {c.x, c.y, c.z}, np[3] = {cn.x, cn.y, cn.z};
-    float sw = 0.f, su[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-    for (int dy = -2; dy <= 2; dy++) {
-        const long long yy = y + (long long)stride * dy;
-        if (yy < 0 || yy >= height) continue;
-#pragma unroll
-        for (int dx = -2; dx <= 2; dx++) {
-            const long long xx = (long long)x + (long long)stride * dx;
-            if (xx < 0 || xx >= width) continue;
-            const float h = dn_kernel(dx) * dn_kernel(dy);
-            float w = h;
-            float uq[3] = {up[0], up[1], up[2]};
-            if (dx != 0 || dy != 0) {
-                const long long q = yy * width + xx;
-                const float4 t = src[q], tn = nrm[q];
-                const float nq[3] = {tn.x, tn.y, tn.z};
-                uq[0] = t.x, uq[1] = t.y, uq[2] = t.z;
-                w = dn_tap_weight(h, up, c.w, np, uq, t.w, nq, kc, kz, normal_power_log2);
-            }
-            sw = sw + w;
-            for (int k = 0; k < 3; k++) su[k] = su[k] + w * uq[k];
-        }
-    }
-    dst[p] = make_float4(su[0] / sw, su[1] / sw, su[2] / sw, c.w);
+    const float kp = dn_colour_scale<kVar, kInlineG>(src, r_in, x, y, width, height, k);
+    dst[p] = dn_filter_pixel<kVar>(x, y, width, height, stride, c, cn, kp, kz, normal_power_log2,
+                                   [&](int, int, long long q, float4 &t, float4 &tn) { t = src[q], tn = nrm[q]; });
 }
 
 constexpr int kDnHalo = 2, kDnLdsW = kDnTileW + 2 * kDnHalo, kDnLdsH = kDnTileH + 2 * kDnHalo;
 
-__global__ void __launch_bounds__(kBlock) k_atrous_lds(const float4 *__restrict__ src, const float4 *__restrict__ nrm,
-                                                        float4 *__restrict__ dst, int width, int height, int stride, int n_rx,
-                                                        int n_res, int lat_tiles_x, float kc, float kz, int normal_power_log2) {
-    __shared__ float4 s_uz[kDnLdsH][kDnLdsW], s_n[kDnLdsH][kDnLdsW];
+template <bool kVar, bool kInlineG>
+__device__ __forceinline__ void dn_pass_lds(const float4 *__restrict__ src, const float4 *__restrict__ nrm, const float *__restrict__ r_in,
+                                            float4 *__restrict__ dst, int width, int height, int stride, int n_rx, int n_res, int lat_tiles_x,
+                                            float k, float kz, int normal_power_log2) {
+    __shared__ float4 s_a[kDnLdsH][kDnLdsW], s_b[kDnLdsH][kDnLdsW];  // src's and nrm's records of the tile and its halo
     const unsigned tile = blockIdx.x / (unsigned)n_res, res = blockIdx.x - tile * (unsigned)n_res;
     const int ry = (int)(res / (unsigned)n_rx), rx = (int)(res - (unsigned)ry * (unsigned)n_rx);
     const int tile_y = (int)(tile / (unsigned)lat_tiles_x), tile_x = (int)(tile - (unsigned)tile_y * (unsigned)lat_tiles_x);
@@ -83,39 +106,33 @@ __global__ void __launch_bounds__(kBlock) k_atrous_lds(const float4 *__restrict_
         const long long gx = rx + (long long)stride * (lx0 + cx), gy = ry + (long long)stride * (ly0 + cy);
         if (gx >= 0 && gx < width && gy >= 0 && gy < height) {  // (a cell outside the image is never read: its tap is skipped)
             const long long q = gy * width + gx;
-            s_uz[cy][cx] = src[q];
-            s_n[cy][cx] = nrm[q];
+            s_a[cy][cx] = src[q];
+            s_b[cy][cx] = nrm[q];
         }
     }
     __syncthreads();
     const int tx = (int)(threadIdx.x % kDnTileW), ty = (int)(threadIdx.x / kDnTileW);
     const long long x = rx + (long long)stride * (lx0 + kDnHalo + tx), y = ry + (long long)stride * (ly0 + kDnHalo + ty);
     if (x >= width || y >= height) return;
-    const float4 c = s_uz[ty + kDnHalo][tx + kDnHalo], cn = s_n[ty + kDnHalo][tx + kDnHalo];
-    const float up[3] = {c.x, c.y, c.z}, np[3] = {cn.x, cn.y, cn.z};
-    float sw = 0.f, su[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-    for (int dy = -2; dy <= 2; dy++) {
-        const long long yy = y + (long long)stride * dy;
-        if (yy < 0 || yy >= height) continue;
-#pragma unroll
-        for (int dx = -2; dx <= 2; dx++) {
-            const long long xx = x + (long long)stride * dx;
-            if (xx < 0 || xx >= width) continue;
-            const float h = dn_kernel(dx) * dn_kernel(dy);
-            float w = h;
-            float uq[3] = {up[0], up[1], up[2]};
-            if (dx != 0 || dy != 0) {
-                const float4 t = s_uz[ty + kDnHalo + dy][tx + kDnHalo + dx], tn = s_n[ty + kDnHalo + dy][tx + kDnHalo + dx];
-                const float nq[3] = {tn.x, tn.y, tn.z};
-                uq[0] = t.x, uq[1] = t.y, uq[2] = t.z;
-                w = dn_tap_weight(h, up, c.w, np, uq, t.w, nq, kc, kz, normal_power_log2);
-            }
-            sw = sw + w;
-            for (int k = 0; k < 3; k++) su[k] = su[k] + w * uq[k];
-        }
-    }
-    dst[y * width + x] = make_float4(su[0] / sw, su[1] / sw, su[2] / sw, c.w);
+    const float4 *pa = &s_a[ty + kDnHalo][tx + kDnHalo], *pb = &s_b[ty + kDnHalo][tx + kDnHalo];  // the pixel's own cell
+    const float4 c = *pa, cn = *pb;
+    const float kp = dn_colour_scale<kVar, kInlineG>(src, r_in, x, y, width, height, k);
+    dst[y * width + x] = dn_filter_pixel<kVar>(x, y, width, height, stride, c, cn, kp, kz, normal_power_log2,
+                                               [&](int dx, int dy, long long, float4 &t, float4 &tn) {
+                                                   t = pa[dy * kDnLdsW + dx], tn = pb[dy * kDnLdsW + dx];
+                                               });
+}
+
+__global__ void __launch_bounds__(kBlock) k_atrous(const float4 *__restrict__ src, const float4 *__restrict__ nrm,
+                                                    float4 *__restrict__ dst, int width, int height, int tiles_x, int stride,
+                                                    float kc, float kz, int normal_power_log2) {
+    dn_pass_direct<false, false>(src, nrm, nullptr, dst, width, height, tiles_x, stride, kc, kz, normal_power_log2);
+}
+
+__global__ void __launch_bounds__(kBlock) k_atrous_lds(const float4 *__restrict__ src, const float4 *__restrict__ nrm,
+                                                        float4 *__restrict__ dst, int width, int height, int stride, int n_rx,
+                                                        int n_res, int lat_tiles_x, float kc, float kz, int normal_power_log2) {
+    dn_pass_lds<false, false>(src, nrm, nullptr, dst, width, height, stride, n_rx, n_res, lat_tiles_x, kc, kz, normal_power_log2);
 }
 
 __global__ void __launch_bounds__(kBlock) k_dn_finish(const float4 *__restrict__ uz, const long long *__restrict__ sums,
@@ -163,39 +180,7 @@ template <bool kInlineG>
 __global__ void __launch_bounds__(kBlock) k_atrous_var(const float4 *__restrict__ src, const float4 *__restrict__ nz,
                                                         const float *__restrict__ r_in, float4 *__restrict__ dst, int width, int height,
                                                         int tiles_x, int stride, float ks, float kz, int normal_power_log2) {
-    const int tile_y = (int)(blockIdx.x / (unsigned)tiles_x), tile_x = (int)(blockIdx.x - (unsigned)tile_y * (unsigned)tiles_x);
-    const int x = tile_x * kDnTileW + (int)(threadIdx.x % kDnTileW);
-    const long long y = (long long)tile_y * kDnTileH + (int)(threadIdx.x / kDnTileW);
-    if (x >= width || y >= height) return;
-    const long long p = y * width + x;
-    const float4 c = src[p], cn = nz[p];
-    const float r = kInlineG ? dn_var_rcp(ks, dn_var_blur((const float *)src, x, y, width, height)) : r_in[p];
-    const float up[3] = {c.x, c.y, c.z}, np[3] = {cn.x, cn.y, cn.z};
-    float sw = 0.f, sv = 0.f, su[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-    for (int dy = -2; dy <= 2; dy++) {
-        const long long yy = y + (long long)stride * dy;
-        if (yy < 0 || yy >= height) continue;
-#pragma unroll
-        for (int dx = -2; dx <= 2; dx++) {
-            const long long xx = (long long)x + (long long)stride * dx;
-            if (xx < 0 || xx >= width) continue;
-            const float h = dn_kernel(dx) * dn_kernel(dy);
-            float w = h, vq = c.w;
-            float uq[3] = {up[0], up[1], up[2]};
-            if (dx != 0 || dy != 0) {
-                const long long q = yy * width + xx;
-                const float4 t = src[q], tn = nz[q];
-                const float nq[3] = {tn.x, tn.y, tn.z};
-                uq[0] = t.x, uq[1] = t.y, uq[2] = t.z, vq = t.w;
-                w = dn_tap_weight_var(h, up, cn.w, np, uq, tn.w, nq, r, kz, normal_power_log2);
-            }
-            sw = sw + w;
-            for (int k = 0; k < 3; k++) su[k] = su[k] + w * uq[k];
-            sv = sv + (w * w) * vq;
-        }
-    }
-    dst[p] = make_float4(su[0] / sw, su[1] / sw, su[2] / sw, sv / (sw * sw));
+    dn_pass_direct<true, kInlineG>(src, nz, r_in, dst, width, height, tiles_x, stride, ks, kz, normal_power_log2);
 }
 
 template <bool kInlineG>
@@ -203,51 +188,7 @@ __global__ void __launch_bounds__(kBlock) k_atrous_var_lds(const float4 *__restr
                                                             const float *__restrict__ r_in, float4 *__restrict__ dst, int width,
                                                             int height, int stride, int n_rx, int n_res, int lat_tiles_x, float ks,
                                                             float kz, int normal_power_log2) {
-    __shared__ float4 s_uv[kDnLdsH][kDnLdsW], s_nz[kDnLdsH][kDnLdsW];
-    const unsigned tile = blockIdx.x / (unsigned)n_res, res = blockIdx.x - tile * (unsigned)n_res;
-    const int ry = (int)(res / (unsigned)n_rx), rx = (int)(res - (unsigned)ry * (unsigned)n_rx);
-    const int tile_y = (int)(tile / (unsigned)lat_tiles_x), tile_x = (int)(tile - (unsigned)tile_y * (unsigned)lat_tiles_x);
-    const long long lx0 = (long long)tile_x * kDnTileW - kDnHalo, ly0 = (long long)tile_y * kDnTileH - kDnHalo;
-    for (int i = (int)threadIdx.x; i < kDnLdsW * kDnLdsH; i += kBlock) {
-        const int cy = i / kDnLdsW, cx = i - cy * kDnLdsW;
-        const long long gx = rx + (long long)stride * (lx0 + cx), gy = ry + (long long)stride * (ly0 + cy);
-        if (gx >= 0 && gx < width && gy >= 0 && gy < height) {  // (a cell outside the image is never read: its tap is skipped)
-            const long long q = gy * width + gx;
-            s_uv[cy][cx] = src[q];
-            s_nz[cy][cx] = nz[q];
-        }
-    }
-    __syncthreads();
-    const int tx = (int)(threadIdx.x % kDnTileW), ty = (int)(threadIdx.x / kDnTileW);
-    const long long x = rx + (long long)stride * (lx0 + kDnHalo + tx), y = ry + (long long)stride * (ly0 + kDnHalo + ty);
-    if (x >= width || y >= height) return;
-    const float4 c = s_uv[ty + kDnHalo][tx + kDnHalo], cn = s_nz[ty + kDnHalo][tx + kDnHalo];
-    const float r = kInlineG ? dn_var_rcp(ks, dn_var_blur((const float *)src, x, y, width, height)) : r_in[y * width + x];
-    const float up[3] = {c.x, c.y, c.z}, np[3] = {cn.x, cn.y, cn.z};
-    float sw = 0.f, sv = 0.f, su[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-    for (int dy = -2; dy <= 2; dy++) {
-        const long long yy = y + (long long)stride * dy;
-        if (yy < 0 || yy >= height) continue;
-#pragma unroll
-        for (int dx = -2; dx <= 2; dx++) {
-            const long long xx = x + (long long)stride * dx;
-            if (xx < 0 || xx >= width) continue;
-            const float h = dn_kernel(dx) * dn_kernel(dy);
-            float w = h, vq = c.w;
-            float uq[3] = {up[0], up[1], up[2]};
-            if (dx != 0 || dy != 0) {
-                const float4 t = s_uv[ty + kDnHalo + dy][tx + kDnHalo + dx], tn = s_nz[ty + kDnHalo + dy][tx + kDnHalo + dx];
-                const float nq[3] = {tn.x, tn.y, tn.z};
-                uq[0] = t.x, uq[1] = t.y, uq[2] = t.z, vq = t.w;
-                w = dn_tap_weight_var(h, up, cn.w, np, uq, tn.w, nq, r, kz, normal_power_log2);
-            }
-            sw = sw + w;
-            for (int k = 0; k < 3; k++) su[k] = su[k] + w * uq[k];
-            sv = sv + (w * w) * vq;
-        }
-    }
-    dst[y * width + x] = make_float4(su[0] / sw, su[1] / sw, su[2] / sw, sv / (sw * sw));
+    dn_pass_lds<true, kInlineG>(src, nz, r_in, dst, width, height, stride, n_rx, n_res, lat_tiles_x, ks, kz, normal_power_log2);
 }
 
 __global__ void __launch_bounds__(kBlock) k_dn_finish_dual(const float4 *__restrict__ uv, const long long *__restrict__ sum_a,

@@ -16,7 +16,7 @@
 //   * rt_slot_chunk_*   the chunked deal of k_paths (rt_slot_chunks.h): task -> slot, the static deal's slots, the counts and
 //     the decisions, as the kernel makes them.
 //   * hc_denoise / hc_expnegf  the CPU twin of rt_denoise_fixed: a serial loop over rt_denoise.h, the arithmetic of the kernels.
-//   * hc_denoise_dual   the CPU twin of rt_denoise_dual_fixed, likewise.
+//   * hc_denoise_dual   the CPU twin of rt_denoise_dual_fixed, likewise; both walk the pixels with dn_walk, the twins' own loop.
 #include <cfloat>
 #include <cmath>
 #include <cstdint>
@@ -513,6 +513,42 @@ PlocTwin ploc_build(const float *verts, int n) {
     out.ok = true;
     return out;
 }
+
+// The serial walk of both denoiser twins: `passes` a-trous passes over uv, four floats {u.x, u.y, u.z, v} per pixel (v is carried
+// only with kVar), guided by px's z and n.  k[i]: pass i's kc, or with kVar ks, from which every pixel's r is formed.
+template <bool kVar>
+void dn_walk(std::vector<float> &uv, const std::vector<DnPixel> &px, int width, int height, int passes, const float *k, float kz,
+                    int normal_power_log2) {
+    std::vector<float> next(uv.size());
+    for (int i = 0; i < passes; i++) {
+        const long long s = 1ll << i;
+        for (long long y = 0; y < height; y++)
+            for (long long x = 0; x < width; x++) {
+                const size_t p = (size_t)(y * width + x);
+                const float kp = kVar ? dn_var_rcp(k[i], dn_var_blur(uv.data(), x, y, width, height)) : k[i];
+                float sw = 0.f, sv = 0.f, su[3] = {0.f, 0.f, 0.f};
+                for (int dy = -2; dy <= 2; dy++) {
+                    const long long yy = y + s * dy;
+                    if (yy < 0 || yy >= height) continue;
+                    for (int dx = -2; dx <= 2; dx++) {
+                        const long long xx = x + s * dx;
+                        if (xx < 0 || xx >= width) continue;
+                        const size_t q = (size_t)(yy * width + xx);
+                        const float h = dn_kernel(dx) * dn_kernel(dy);
+                        const float w = (dx == 0 && dy == 0) ? h
+                                                             : dn_tap_weight(h, &uv[4 * p], px[p].z, px[p].n, &uv[4 * q], px[q].z, px[q].n, kp, kz,
+                                                                             normal_power_log2);
+                        sw = sw + w;
+                        for (int c = 0; c < 3; c++) su[c] = su[c] + w * uv[4 * q + c];
+                        if (kVar) sv = sv + (w * w) * uv[4 * q + 3];
+                    }
+                }
+                for (int c = 0; c < 3; c++) next[4 * p + c] = su[c] / sw;
+                next[4 * p + 3] = kVar ? sv / (sw * sw) : 0.f;
+            }
+        uv.swap(next);
+    }
+}
 }  // namespace
 
 extern "C" {
@@ -951,33 +987,13 @@ int hc_denoise(const int64_t *sum_fixed, int num_samples, const int64_t *aov_fix
     const size_t n = (size_t)width * (size_t)height;
     const float inv_spp = 1.f / (float)num_samples, inv_aov = 1.f / (float)aov_samples;
     std::vector<DnPixel> px(n);
-    for (size_t p = 0; p < n; p++) dn_prepare(sum_fixed + 3 * p, aov_fixed + DN_AOV_CHANNELS * p, inv_spp, inv_aov, &px[p]);
-    std::vector<float> next(3 * n);
-    for (int i = 0; i < passes; i++) {
-        const long long s = 1ll << i;
-        for (long long y = 0; y < height; y++)
-            for (long long x = 0; x < width; x++) {
-                const DnPixel &c = px[(size_t)(y * width + x)];
-                float sw = 0.f, su[3] = {0.f, 0.f, 0.f};
-                for (int dy = -2; dy <= 2; dy++) {
-                    const long long yy = y + s * dy;
-                    if (yy < 0 || yy >= height) continue;
-                    for (int dx = -2; dx <= 2; dx++) {
-                        const long long xx = x + s * dx;
-                        if (xx < 0 || xx >= width) continue;
-                        const DnPixel &q = px[(size_t)(yy * width + xx)];
-                        const float h = dn_kernel(dx) * dn_kernel(dy);
-                        const float w = (dx == 0 && dy == 0) ? h : dn_tap_weight(h, c.u, c.z, c.n, q.u, q.z, q.n, kc[i], kz, normal_power_log2);
-                        sw = sw + w;
-                        for (int k = 0; k < 3; k++) su[k] = su[k] + w * q.u[k];
-                    }
-                }
-                for (int k = 0; k < 3; k++) next[3 * (size_t)(y * width + x) + k] = su[k] / sw;
-            }
-        for (size_t p = 0; p < n; p++)
-            for (int k = 0; k < 3; k++) px[p].u[k] = next[3 * p + k];
+    std::vector<float> uv(4 * n, 0.f);
+    for (size_t p = 0; p < n; p++) {
+        dn_prepare(sum_fixed + 3 * p, aov_fixed + DN_AOV_CHANNELS * p, inv_spp, inv_aov, &px[p]);
+        for (int k = 0; k < 3; k++) uv[4 * p + k] = px[p].u[k];
     }
-    for (size_t p = 0; p < n; p++) dn_finish(px[p].u, px[p].d, px[p].e, rgb_out + 3 * p);
+    dn_walk<false>(uv, px, width, height, passes, kc, kz, normal_power_log2);
+    for (size_t p = 0; p < n; p++) dn_finish(&uv[4 * p], px[p].d, px[p].e, rgb_out + 3 * p);
     return 0;
 }
 // rt_expnegf on n values (tests/test_denoise_host.py holds it to its numpy restatement and to exp)
@@ -1002,39 +1018,13 @@ int hc_denoise_dual(const int64_t *sum_a, int samples_a, const int64_t *sum_b, i
     const float inv_a = 1.f / (float)samples_a, inv_b = 1.f / (float)samples_b, inv_n = 1.f / (float)ns, inv_aov = 1.f / (float)aov_samples;
     const size_t n = (size_t)width * (size_t)height;
     std::vector<DnPixel> px(n);
-    std::vector<float> uv(4 * n), next(4 * n);
+    std::vector<float> uv(4 * n);
     for (size_t p = 0; p < n; p++) {
         uv[4 * p + 3] = dn_prepare_dual(sum_a + 3 * p, sum_b + 3 * p, aov_fixed + DN_AOV_CHANNELS * p, inv_a, inv_b, inv_n, inv_aov, kv, &px[p]);
         for (int k = 0; k < 3; k++) uv[4 * p + k] = px[p].u[k];
     }
-    for (int i = 0; i < passes; i++) {
-        const long long s = 1ll << i;
-        for (long long y = 0; y < height; y++)
-            for (long long x = 0; x < width; x++) {
-                const size_t p = (size_t)(y * width + x);
-                const float r = dn_var_rcp(ks, dn_var_blur(uv.data(), x, y, width, height));
-                float sw = 0.f, sv = 0.f, su[3] = {0.f, 0.f, 0.f};
-                for (int dy = -2; dy <= 2; dy++) {
-                    const long long yy = y + s * dy;
-                    if (yy < 0 || yy >= height) continue;
-                    for (int dx = -2; dx <= 2; dx++) {
-                        const long long xx = x + s * dx;
-                        if (xx < 0 || xx >= width) continue;
-                        const size_t q = (size_t)(yy * width + xx);
-                        const float h = dn_kernel(dx) * dn_kernel(dy);
-                        const float w = (dx == 0 && dy == 0) ? h
-                                                             : dn_tap_weight_var(h, &uv[4 * p], px[p].z, px[p].n, &uv[4 * q], px[q].z, px[q].n, r, kz,
-                                                                                 normal_power_log2);
-                        sw = sw + w;
-                        for (int k = 0; k < 3; k++) su[k] = su[k] + w * uv[4 * q + k];
-                        sv = sv + (w * w) * uv[4 * q + 3];
-                    }
-                }
-                for (int k = 0; k < 3; k++) next[4 * p + k] = su[k] / sw;
-                next[4 * p + 3] = sv / (sw * sw);
-            }
-        uv.swap(next);
-    }
+    const float k[DN_MAX_PASSES] = {ks, ks, ks, ks, ks, ks, ks, ks};
+    dn_walk<true>(uv, px, width, height, passes, k, kz, normal_power_log2);
     for (size_t p = 0; p < n; p++) {
         dn_finish(&uv[4 * p], px[p].d, px[p].e, rgb_out + 3 * p);
         if (var_out) var_out[p] = uv[4 * p + 3];

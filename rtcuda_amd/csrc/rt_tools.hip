@@ -814,23 +814,28 @@ int rt_shade_records(const rt_scene *scene, int max_bounces, int lds_tables, int
 }
 
 
-// One pass of the denoiser, one form, timed launch by launch (tools/denoise_time.py).  d_scratch: the scratch of an
-// rt_denoise_fixed call with passes = 0 of the same frame -- its first array holds the prepared {u, z}, its third {n}; the pass
-// writes the second.  stride = 2^i uses kc_i; form: 1 = k_atrous, 2 = k_atrous_lds.  out_ms: reps device times, HIP events.
-int rt_denoise_pass_time(void *d_scratch, int width, int height, int stride, int form, float sigma_color, float sigma_depth,
-                         int normal_power_log2, int reps, float *out_ms) {
-    if (!d_scratch || !out_ms || width < 1 || height < 1 || reps < 1) return fail("rt_denoise_pass_time: bad argument");
-    if (stride < 1 || stride > 128 || (stride & (stride - 1)) || (form != 1 && form != 2)) return fail("rt_denoise_pass_time: bad stride or form");
-    if (dn_pass_blocks(width, height, stride, form) > kDnMaxBlocks) return fail("rt_denoise_pass_time: the grid of this form is too large");
+// The two pass timers below time one pass, launch by launch, over the scratch of a call of their entry point with passes = 0 of
+// the same frame: its first array holds the prepared records, its third the guides, the pass writes the second (and, with
+// g = 2, the r array).  out_ms: reps device times, HIP events.  Their shared checks (choices_ok: the caller's own check of form
+// and placement, `choices` what it names them; frame_ok: its check of the frame size), and their shared loop.
+static int dn_pass_time_check(const std::string &me, const char *choices, bool choices_ok, bool frame_ok, const void *d_scratch,
+                              const float *out_ms, int width, int height, int stride, int form, int reps) {
+    if (!d_scratch || !out_ms || width < 1 || height < 1 || reps < 1) return fail(me + "bad argument");
+    if (stride < 1 || stride > 128 || (stride & (stride - 1)) || (form != 1 && form != 2) || !choices_ok) return fail(me + "bad " + choices);
+    if (!frame_ok) return fail(me + "bad frame size");
+    if (dn_pass_blocks(width, height, stride, form) > kDnMaxBlocks) return fail(me + "the grid of this form is too large");
+    return 0;
+}
+static int dn_pass_time_run(void *d_scratch, int width, int height, int stride, int form, int g, float k, float kz, int normal_power_log2,
+                            int reps, float *out_ms) {
     const long long n = (long long)width * height;
-    float4 *uz = (float4 *)d_scratch, *dst = uz + n, *nrm = uz + 2 * n;
-    const float kc = (float)(stride * stride) / (sigma_color * sigma_color), kz = 1.f / (sigma_depth * sigma_depth);
+    float4 *src = (float4 *)d_scratch, *dst = src + n, *nrm = src + 2 * n;
     hipEvent_t e0, e1;
     HIP_TRY(hipEventCreate(&e0));
     HIP_TRY(hipEventCreate(&e1));
     for (int r = 0; r < reps; r++) {
         HIP_TRY(hipEventRecord(e0, nullptr));
-        dn_launch_pass(form, uz, nrm, dst, width, height, stride, kc, kz, normal_power_log2, nullptr);
+        dn_launch_pass(form, g, src, nrm, g ? (float *)(src + 3 * n) : nullptr, dst, width, height, stride, k, kz, normal_power_log2, nullptr);
         HIP_TRY(hipEventRecord(e1, nullptr));
         HIP_TRY(hipEventSynchronize(e1));
         HIP_TRY(hipGetLastError());
@@ -841,34 +846,22 @@ int rt_denoise_pass_time(void *d_scratch, int width, int height, int stride, int
     return 0;
 }
 
-// One pass of the dual-buffer denoiser, one form and one placement of the variance prefilter, timed launch by launch
-// (tools/denoise_dual_time.py).  d_scratch: the scratch of an rt_denoise_dual_fixed call with passes = 0 of the same frame -- its
-// first array holds the prepared {u, v}, its third {n, z}; the pass writes the second (and, with g_place = 2, the r array).
+// One pass of the denoiser, one form (tools/denoise_time.py).  stride = 2^i uses kc_i; form: 1 = k_atrous, 2 = k_atrous_lds.
+int rt_denoise_pass_time(void *d_scratch, int width, int height, int stride, int form, float sigma_color, float sigma_depth,
+                         int normal_power_log2, int reps, float *out_ms) {
+    if (dn_pass_time_check("rt_denoise_pass_time: ", "stride or form", true, true, d_scratch, out_ms, width, height, stride, form, reps)) return 1;
+    return dn_pass_time_run(d_scratch, width, height, stride, form, 0, (float)(stride * stride) / (sigma_color * sigma_color),
+                            1.f / (sigma_depth * sigma_depth), normal_power_log2, reps, out_ms);
+}
+
+// One pass of the dual-buffer denoiser, one form and one placement of the variance prefilter (tools/denoise_dual_time.py).
 int rt_denoise_dual_pass_time(void *d_scratch, int width, int height, int stride, int form, int g_place, float sigma_variance,
                               float sigma_depth, int normal_power_log2, int reps, float *out_ms) {
-    if (!d_scratch || !out_ms || width < 1 || height < 1 || reps < 1) return fail("rt_denoise_dual_pass_time: bad argument");
-    if (stride < 1 || stride > 128 || (stride & (stride - 1)) || (form != 1 && form != 2) || (g_place != 1 && g_place != 2))
-        return fail("rt_denoise_dual_pass_time: bad stride, form or g_place");
-    if (denoise_dual_scratch_bytes(width, height) < 0) return fail("rt_denoise_dual_pass_time: bad frame size");
-    if (dn_pass_blocks(width, height, stride, form) > kDnMaxBlocks) return fail("rt_denoise_dual_pass_time: the grid of this form is too large");
-    const long long n = (long long)width * height;
-    float4 *uv = (float4 *)d_scratch, *dst = uv + n, *nz = uv + 2 * n;
-    float *r_buf = (float *)(uv + 3 * n);
-    const float ks = sigma_variance * sigma_variance, kz = 1.f / (sigma_depth * sigma_depth);
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
-    for (int r = 0; r < reps; r++) {
-        HIP_TRY(hipEventRecord(e0, nullptr));
-        dn_launch_dual_pass(form, g_place == 1, uv, nz, r_buf, dst, width, height, stride, ks, kz, normal_power_log2, nullptr);
-        HIP_TRY(hipEventRecord(e1, nullptr));
-        HIP_TRY(hipEventSynchronize(e1));
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventElapsedTime(&out_ms[r], e0, e1));
-    }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    return 0;
+    if (dn_pass_time_check("rt_denoise_dual_pass_time: ", "stride, form or g_place", g_place == 1 || g_place == 2,
+                           denoise_dual_scratch_bytes(width, height) >= 0, d_scratch, out_ms, width, height, stride, form, reps))
+        return 1;
+    return dn_pass_time_run(d_scratch, width, height, stride, form, g_place, sigma_variance * sigma_variance, 1.f / (sigma_depth * sigma_depth),
+                            normal_power_log2, reps, out_ms);
 }
 
 }  // extern "C"

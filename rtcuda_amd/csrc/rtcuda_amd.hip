@@ -8,8 +8,9 @@
 //   rt_host_scene.inc      rt_scene and the one way a tree gets into it: build (host SAH, device PLOC), emit, adopt; the entry
 //                          points on top of it (create, update, rebuild, the edits); what the ray entry points share
 //   rt_host_render.inc     Context, kernel selection, frames, test rays, queries, ray tables, AOVs
-//   rt_denoise_kernels.inc k_dn_prepare, k_atrous, k_dn_finish (arithmetic: rt_denoise.h, shared with the CPU twin)
-//   rt_host_denoise.inc    rt_denoise_fixed and rt_denoise_dual_fixed: checks, pass constants, launches
+//   rt_denoise_kernels.inc the denoisers' kernels: one tap loop (dn_filter_pixel) and two pass bodies (dn_pass_direct, dn_pass_lds) under
+//                          k_atrous* / k_atrous_var*; prepare, finish, k_dn_var_blur (arithmetic: rt_denoise.h, shared with the CPU twin)
+//   rt_host_denoise.inc    rt_denoise_fixed and rt_denoise_dual_fixed: one set of checks (dn_check), one pass launcher, one run (dn_run)
 // The C-ABI below them only checks arguments and forwards.
 //
 // The hot path of lashhw/rtcuda (render.cuh:61-457) re-designed for CDNA4:
@@ -873,7 +874,7 @@ __global__ void k_test_draw(DPools p, int n, int draws, uint32_t *__restrict__ s
     state6[6 * (size_t)i + 5] = rs.v4;
 }
 #include "rt_build_kernels.inc"   // device BVH: the leaf-order arrays, refit (k_refit_*), build (k_ploc_*)
-#include "rt_denoise_kernels.inc"  // k_dn_prepare, k_atrous, k_dn_finish; k_dn_prepare_dual, k_dn_var_blur, k_atrous_var, k_dn_finish_dual
+#include "rt_denoise_kernels.inc"  // dn_filter_pixel under k_atrous* and k_atrous_var*; k_dn_prepare*, k_dn_var_blur, k_dn_finish*
 
 #include "rt_host_scene.inc"   // (opens the anonymous namespace that is closed below) rt_scene: reference tree, checks, build / emit / adopt, create, update, rebuild, edits; what the ray entry points share
 #include "rt_host_render.inc"  // Context, kernel selection, frames, test rays, queries, ray tables, AOVs

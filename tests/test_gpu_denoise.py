@@ -3,7 +3,8 @@
 What the call must return comes from tests/denoise_expected.py, the numpy restatement of the header's text that
 tests/test_denoise_host.py holds the CPU twin to.  Every comparison of an image is EQUALITY of all output floats as bit patterns:
 no tolerance, no masked pixel.  The pass has two forms, the direct k_atrous and the LDS k_atrous_lds (a 32 x 8 tile per workgroup in
-both, of pixels and of one residue's sub-image); the sizes put the image edge, the tile edge and every stride on both sides of
+both, of pixels and of one residue's sub-image; both are wrappers of one tap loop, dn_filter_pixel, which the dual filter's pass
+kernels share); the sizes put the image edge, the tile edge and every stride on both sides of
 each other, and test_both_forms_at_every_stride forces each form (the RT_DENOISE_FORM knob) whatever the library would choose."""
 import ctypes
 

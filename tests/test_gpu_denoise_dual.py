@@ -3,7 +3,8 @@
 What the call must return comes from tests/denoise_dual_expected.py, the numpy restatement of the header's text that
 tests/test_denoise_dual_host.py holds the CPU twin to.  Every comparison of an image is EQUALITY of all output floats as bit
 patterns: no tolerance, no masked pixel.  A pass has two forms (the direct k_atrous_var and the LDS k_atrous_var_lds, a 32 x 8
-tile per workgroup in both) and two placements of the 3 x 3 variance prefilter (in the pass, or k_dn_var_blur before it); the
+tile per workgroup in both: rt_denoise_fixed's pass bodies and tap loop, dn_filter_pixel, with the variance channel switched on)
+and two placements of the 3 x 3 variance prefilter (in the pass, or k_dn_var_blur before it); the
 knobs RT_DENOISE_FORM and RT_DENOISE_DUAL_G force each, and test_every_form_and_placement_at_every_stride runs all four at
 strides 1 to 128 on 33 x 17 and 97 x 19: below, at and beyond a tile, halos and 3 x 3 taps across the image edge, strides beyond
 the image."""
