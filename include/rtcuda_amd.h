@@ -563,9 +563,9 @@ int rt_denoise_dual_fixed(const int64_t *d_sum_a, int samples_a, const int64_t *
 /* ---- ray queries (no reference counterpart: its Bvh::traverse is reachable only from render()) ----------------------------
  * "Trace my rays, from my buffers, on my stream."  All pointers are DEVICE buffers on the scene's device (a buffer on another
  * device or on the host cannot be told apart from a good one: the call faults instead of failing); origins and directions are
- * n AoS xyz triples.  d_tmax NULL = FLT_MAX for every ray.  Answers are those of rt_trace_closest_flags / rt_trace_any_flags
- * with the same flags (0, RT_FLAG_REFERENCE_WALK or RT_FLAG_WATERTIGHT -- see the flags; both together, or any other flag, is
- * an error):
+ * n AoS xyz triples.  d_tmax NULL = FLT_MAX for every ray.  flags: 0, RT_FLAG_REFERENCE_WALK or RT_FLAG_WATERTIGHT (see the
+ * flags; both together, or any other flag, is an error).  rt_trace_closest_flags / rt_trace_any_flags below are the host-pointer
+ * form of these two calls -- one implementation, so their answers are these, bit for bit:
  *   closest: d_hit_tri[i] = the hit triangle in the caller's ORIGINAL order or -1; t, u, v as Intersection
  *       (intersection.hpp:4-6), and t = u = v = 0 on a miss, so every output buffer is fully defined after the call.  Any
  *       of d_t, d_u, d_v may be NULL (not written).
@@ -593,13 +593,17 @@ int rt_query_any_device(const rt_scene *scene, uint32_t flags, int n, const floa
 int rt_query_last_counters(const rt_scene *scene, int64_t out[3]);
 
 /* ---- stage-level entry points (parity tests call these; HOST pointers, AoS xyz triples) -----
- * (Host-pointer forms kept for the parity tests; applications use rt_query_*_device.)
+ * The host-pointer form of the queries above, kept for the parity tests; applications use rt_query_*_device.  A call uploads
+ * the caller's arrays, runs the query's walk on the default stream and copies the answers back; calls on ONE scene take turns
+ * with its queries.  Unlike the queries they check no direction (the precondition below is the caller's to keep) and leave
+ * rt_query_last_counters alone.
  * Closest hit (Bvh::traverse, bvh.cuh:251-303; ch(), render.cuh:297-328): hit_tri = index of
  * the hit triangle in the caller's ORIGINAL order or -1; t,u,v as Intersection
- * (intersection.hpp:4-6), undefined on a miss. */
+ * (intersection.hpp:4-6), t = u = v = 0 on a miss. */
 int rt_trace_closest(const rt_scene *scene, int n, const float *origin_xyz, const float *dir_xyz,
                      const float *tmax, int32_t *hit_tri, float *t, float *u, float *v);
-/* Any hit excluding one triangle (bvh.cuh:306-357; ah(), render.cuh:278-294): occluded[i] in {0,1}. */
+/* Any hit excluding one triangle (bvh.cuh:306-357; ah(), render.cuh:278-294): occluded[i] in {0,1}; excluded_tri[i] in the
+ * caller's order, an index < 0 or >= n_tris excludes nothing. */
 int rt_trace_any(const rt_scene *scene, int n, const float *origin_xyz, const float *dir_xyz,
                  const float *tmax, const int32_t *excluded_tri, int32_t *occluded);
 /* The same two entry points with a flags word (RT_FLAG_REFERENCE_WALK / RT_FLAG_WATERTIGHT: see the flags).  flags = 0 is

@@ -44,7 +44,9 @@ int rt_probe_issue(int kind, int waves_per_simd, int iters, double *out_seconds,
  * init/mat/gen kernels and ah/ch kernels with dense queues between them)?".  Runs the round-per-launch pipeline of the
  * frame from its start until `target_rays` rays have been traced, copying every round's rays (closest-hit and any-hit
  * apart) and every round's shading inputs (by material kind) into dense device arrays; then times, on those arrays,
- *   - the trace kernel alone (stage-level modes of the product's trace kernel) at 8 / 6 / 5 / 4 waves per SIMD,
+ *   - the trace kernel alone at 8 / 6 / 5 / 4 waves per SIMD: the walker the product ships for dense ray arrays (k_query's
+ *     ends on stream_walk, watertight build) compiled at each budget -- so the eight trace-only entries price the stage
+ *     split with that kernel (up to commit 78db776: with dense-array modes of the pool kernel k_trace, which are gone),
  *   - the shading code alone (the product's init() + mat()), one material kind per launch, every lane shading,
  * each as the best of three launches (HIP events).  out[] is indexed by the RT_PROBE_* enum; times in seconds.
  * No reference counterpart. */

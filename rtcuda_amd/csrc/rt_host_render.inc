@@ -132,19 +132,18 @@ static int lds_stack_cap(const rt_scene *scene, int limit) {
 // Kernel selection: every build of one kernel template has the same signature, so the flags pick a function pointer and
 // the caller launches (and sizes the grid with) that pointer.
 using AdvanceKernel = decltype(&k_advance<false>);
-using TraceKernel = decltype(&k_trace<MODE_POOL, false>);
+using TraceKernel = decltype(&k_trace<false>);
 using PathsKernel = decltype(&k_paths<false, false, 4, false, false, false>);
 
 static AdvanceKernel advance_kernel(bool lds_tables) { return lds_tables ? k_advance<true> : k_advance<false>; }
 
-// k_trace<MODE>: with RT_FLAG_REFERENCE_WALK the build that walks the reference's tree (the node format does not matter
+// k_trace: with RT_FLAG_REFERENCE_WALK the build that walks the reference's tree (the node format does not matter
 // then); `verify`: the default build -- the product's walk with the reference's decisions (ref_visible); neither:
 // RT_FLAG_WATERTIGHT.  Otherwise the node format is a property of the scene.
-template <int MODE>
 static TraceKernel trace_kernel(bool literal, bool verify, bool wide) {
-    if (literal) return k_trace<MODE, false, 8, true>;
-    if (verify) return wide ? k_trace<MODE, true, 8, false, true> : k_trace<MODE, false, 8, false, true>;
-    return wide ? k_trace<MODE, true> : k_trace<MODE, false>;
+    if (literal) return k_trace<false, true>;
+    if (verify) return wide ? k_trace<true, false, true> : k_trace<false, false, true>;
+    return wide ? k_trace<true> : k_trace<false>;
 }
 
 // k_paths: MIN_WAVES = 4 waves per SIMD (at most 128 VGPRs) when the grid fills the chip, 2 (up to 256 VGPRs) when the
@@ -196,10 +195,10 @@ static PathsKeyedKernel paths_keyed_kernel(bool lds_tables, bool few_blocks) {
 }
 
 // Global overflow part of the traversal stacks: `levels` entries for each of kOverStride lanes.  Every OWNER of
-// concurrently running grids has its own buffer -- a render context (one render at a time: Context::busy), or one
-// call of a stage-level test entry point -- because a lane indexes its column by its position in ITS grid only:
-// two grids in flight on one device (RT_SPLIT sub-shards, host threads rendering different shard sizes) would
-// otherwise push to and pop from the same columns.  Grown on demand under the owner's lock, never shrunk.
+// concurrently running grids has its own buffer -- a render context (one render at a time: Context::busy), or a
+// scene's query state (queries, trace hooks and AOVs of one scene take turns: QueryState::mutex) -- because a lane
+// indexes its column by its position in ITS grid only: two grids in flight on one device (RT_SPLIT sub-shards, host
+// threads rendering different shard sizes) would otherwise push to and pop from the same columns.  Grown on demand under the owner's lock, never shrunk.
 int ensure_overflow(int *&ptr, int &have_levels, int levels) {
     levels = std::max(levels, 1);
     if (ptr && have_levels >= levels) return 0;
@@ -637,7 +636,7 @@ int render_shard_impl(const rt_scene *scene, const rt_camera *camera, int width,
     // advance grid, whose wave count sizes the counter rows)
     int occ_c = 0;
     HIP_TRY(hipDeviceGetAttribute(&f.cus, hipDeviceAttributeMultiprocessorCount, dev));
-    f.trace = trace_kernel<MODE_POOL>(mode.literal, mode.verify, scene->wide);
+    f.trace = trace_kernel(mode.literal, mode.verify, scene->wide);
     // (every k_trace build runs 8 waves per SIMD without static LDS: the grid does not depend on which one this is)
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_c, f.trace, kBlock, f.lds_bytes));
     int per_cu = std::max(1, occ_c);
@@ -723,47 +722,6 @@ int render_overlapped(const rt_scene *scene, const rt_camera *camera, int width,
     return 0;
 }
 
-// What rt_trace_closest_flags and rt_trace_any_flags share: the mode flags, the reference tree, the origins' padding, the
-// rays' upload, the overflow stacks and the launch of k_trace<MODE>.  `tp` arrives with the entry point's own buffers set;
-// every device buffer lives in `tmp`.
-template <int MODE>
-static int trace_test_rays(const rt_scene *scene, uint32_t flags, int n, const float *origin_xyz, const float *dir_xyz,
-                           const float *tmax, TraceParams tp, DevScope &tmp) {
-    const HitMode mode = hit_mode(flags);
-    if (mode.ref_tree() && ensure_ref_tree(scene)) return 1;
-    float *d_o, *d_d, *d_tm;
-    unsigned long long *d_vstat;
-    if (tmp.alloc(d_vstat, 4)) return 1;
-    HIP_TRY(hipMemset(d_vstat, 0, 4 * sizeof(unsigned long long)));
-    if (tmp.alloc(d_o, 3 * (size_t)n) || tmp.alloc(d_d, 3 * (size_t)n) || tmp.alloc(d_tm, (size_t)n)) return 1;
-    {
-        float need[3] = {0.f, 0.f, 0.f};  // the 4-wide records must be padded for these origins (ensure_origin_radius)
-        for (int i = 0; i < n; i++)
-            for (int a = 0; a < 3; a++)
-                if (std::isfinite(origin_xyz[3 * (size_t)i + a])) need[a] = std::max(need[a], std::fabs(origin_xyz[3 * (size_t)i + a]));
-        if (int rc = ensure_origin_radius(scene, need)) return rc;
-    }
-    HIP_TRY(hipMemcpy(d_o, origin_xyz, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_d, dir_xyz, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_tm, tmax, sizeof(float) * (size_t)n, hipMemcpyHostToDevice));
-    const int test_grid = std::min(grid_for(n), 2048);
-    const int stack_cap = lds_stack_cap(scene, kLdsStack);
-    int *d_over = nullptr;
-    int over_levels = 0;
-    if (ensure_overflow(d_over, over_levels, std::max(scene->stack_bound, 32) - stack_cap)) return 1;
-    tmp.ptrs.push_back(d_over);
-    tp.total = n;
-    tp.o3 = d_o;
-    tp.d3 = d_d;
-    tp.tmax = d_tm;
-    tp.vstat = d_vstat;
-    DPools none{};
-    hipLaunchKernelGGL(trace_kernel<MODE>(mode.literal, mode.verify, scene->wide), dim3(test_grid), dim3(kBlock),
-                       sizeof(int) * kBlock * (size_t)(stack_cap + 2), nullptr, scene->dev(), none, tp, stack_cap, d_over);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
 // A persistent query-style grid: what the device holds at once (never more lanes than the overflow stacks' columns) or n needs.
 template <class KERNEL>
 static int resident_grid(KERNEL kernel, size_t lds_bytes, int cus, int n, int *grid) {
@@ -774,9 +732,11 @@ static int resident_grid(KERNEL kernel, size_t lds_bytes, int cus, int n, int *g
     return 0;
 }
 
-// rt_query_closest_device / rt_query_any_device.  Every kernel of a query is ordered on `st`; the host waits twice: for the
-// table's validation (validate_table: the directions, and the origin radius the 4-wide records must be padded for) and for
-// the walk.
+// The walk of a query on `st`, after whatever the entry point checks: `qp` arrives with the rays, the caller's exclusions and
+// the answers' buffers, all on the device.  The inverse leaf order (made by the first any-hit call that excludes), the
+// overflow stacks, the kernel for the scene and the hit definition, the launch sized from the device, one wait, and the
+// rare-path counters of this call into `counters_out`.  The caller holds the scene's query lock, has entered the scene's
+// device and has zeroed q.d_words->vstat on `st` (validate_table does).
 using QueryKernel = decltype(&k_query<Q_CLOSEST, false, false, false>);
 template <int KIND>
 static QueryKernel query_kernel(bool literal, bool verify, bool wide) {
@@ -784,6 +744,33 @@ static QueryKernel query_kernel(bool literal, bool verify, bool wide) {
     if (verify) return wide ? k_query<KIND, true, false, true> : k_query<KIND, false, false, true>;
     return wide ? k_query<KIND, true, false, false> : k_query<KIND, false, false, false>;
 }
+template <int KIND>
+static int run_query(const rt_scene *scene, HitMode mode, QueryParams qp, hipStream_t st, int64_t counters_out[3]) {
+    rt_scene::QueryState &q = scene->query;
+    if (KIND == Q_ANY && qp.excluded && !q.d_inverse && scene->n_tris > 0) {
+        HIP_TRY(hipMalloc((void **)&q.d_inverse, sizeof(int) * (size_t)scene->n_tris));
+        hipLaunchKernelGGL(k_query_inverse, dim3((scene->n_tris + 255) / 256), dim3(256), 0, st, scene->d_order, scene->n_tris, q.d_inverse);
+    }
+    const int stack_cap = lds_stack_cap(scene, kLdsStack);
+    if (ensure_overflow(q.d_over, q.over_levels, std::max(scene->stack_bound, 32) - stack_cap)) return 1;
+    qp.n_tris = scene->n_tris;
+    qp.inverse = q.d_inverse;
+    qp.vstat = q.d_words->vstat;
+    const QueryKernel kernel = query_kernel<KIND>(mode.literal, mode.verify, scene->wide);
+    const size_t lds = sizeof(int) * kBlock * (size_t)(stack_cap + 1);
+    int grid = 0;
+    if (resident_grid(kernel, lds, q.cus, qp.n, &grid)) return 1;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, st, scene->dev(), qp, stack_cap, q.d_over);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(q.h_words->vstat, q.d_words->vstat, sizeof(q.h_words->vstat), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    rare_path_counters(q.h_words->vstat, counters_out);
+    return 0;
+}
+
+// rt_query_closest_device / rt_query_any_device.  Every kernel of a query is ordered on `st`; the host waits twice: for the
+// table's validation (validate_table: the directions, and the origin radius the 4-wide records must be padded for) and for
+// the walk.
 template <int KIND>
 static int query_impl(const rt_scene *scene, uint32_t flags, int n, const float *d_o, const float *d_d, const float *d_tmax,
                       const int32_t *d_excluded, int32_t *d_out_i, float *d_t, float *d_u, float *d_v, hipStream_t st) {
@@ -803,34 +790,60 @@ static int query_impl(const rt_scene *scene, uint32_t flags, int n, const float 
     if (ensure_query_state(scene, false)) return 1;
     if (mode.ref_tree() && ensure_ref_tree(scene)) return 1;
     if (int rc = validate_table(scene, w, n, d_o, d_d, nullptr, 0, st)) return rc;
-    if (KIND == Q_ANY && d_excluded && !q.d_inverse && scene->n_tris > 0) {
-        HIP_TRY(hipMalloc((void **)&q.d_inverse, sizeof(int) * (size_t)scene->n_tris));
-        hipLaunchKernelGGL(k_query_inverse, dim3((scene->n_tris + 255) / 256), dim3(256), 0, st, scene->d_order, scene->n_tris, q.d_inverse);
-    }
-    const int stack_cap = lds_stack_cap(scene, kLdsStack);
-    if (ensure_overflow(q.d_over, q.over_levels, std::max(scene->stack_bound, 32) - stack_cap)) return 1;
     QueryParams qp{};
     qp.n = n;
-    qp.n_tris = scene->n_tris;
     qp.o3 = d_o;
     qp.d3 = d_d;
     qp.tmax = d_tmax;
     qp.excluded = d_excluded;
-    qp.inverse = q.d_inverse;
     qp.out_i = d_out_i;
     qp.out_t = d_t;
     qp.out_u = d_u;
     qp.out_v = d_v;
-    qp.vstat = q.d_words->vstat;
-    const QueryKernel kernel = query_kernel<KIND>(mode.literal, mode.verify, scene->wide);
-    const size_t lds = sizeof(int) * kBlock * (size_t)(stack_cap + 1);
-    int grid = 0;
-    if (resident_grid(kernel, lds, q.cus, n, &grid)) return 1;
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, st, scene->dev(), qp, stack_cap, q.d_over);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(q.h_words->vstat, q.d_words->vstat, sizeof(q.h_words->vstat), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    rare_path_counters(q.h_words->vstat, q.counters);
+    return run_query<KIND>(scene, mode, qp, st, q.counters);
+}
+
+// rt_trace_closest_flags / rt_trace_any_flags, the host-pointer form of the queries (the entry points have checked their
+// pointers): the caller's arrays go to the device as they are, the walk is run_query's on the null stream, the answers come
+// back.  The uploads are waited for before the walk, the copies back are synchronous.  What differs from query_impl: the
+// origins' radius is taken on the host, the directions are the caller's to keep within the header's precondition (no
+// validate_table: nothing is refused for them), and the counters of the call stay local -- rt_query_last_counters speaks
+// of the last QUERY.
+template <int KIND>
+static int trace_hook(const rt_scene *scene, uint32_t flags, int n, const float *origin_xyz, const float *dir_xyz, const float *tmax,
+                      const int32_t *excluded_tri, int32_t *out_i, float *t, float *u, float *v) {
+    const HitMode mode = hit_mode(flags);
+    rt_scene::QueryState &q = scene->query;
+    std::lock_guard<std::mutex> lock(q.mutex);
+    DeviceGuard dev;
+    if (dev.enter(scene->device)) return 1;
+    if (ensure_query_state(scene, false)) return 1;
+    if (mode.ref_tree() && ensure_ref_tree(scene)) return 1;
+    {
+        float need[3] = {0.f, 0.f, 0.f};  // the 4-wide records must be padded for these origins (ensure_origin_radius)
+        for (int i = 0; i < n; i++)
+            for (int a = 0; a < 3; a++)
+                if (std::isfinite(origin_xyz[3 * (size_t)i + a])) need[a] = std::max(need[a], std::fabs(origin_xyz[3 * (size_t)i + a]));
+        if (int rc = ensure_origin_radius(scene, need)) return rc;
+    }
+    DevScope tmp;
+    QueryParams qp{};
+    qp.n = n;
+    if (stage(tmp, origin_xyz, 3 * (size_t)n, nullptr, qp.o3) || stage(tmp, dir_xyz, 3 * (size_t)n, nullptr, qp.d3) ||
+        stage(tmp, tmax, (size_t)n, nullptr, qp.tmax) || (KIND == Q_ANY && stage(tmp, excluded_tri, (size_t)n, nullptr, qp.excluded)))
+        return 1;
+    if (tmp.alloc(qp.out_i, (size_t)n)) return 1;
+    if (KIND == Q_CLOSEST && (tmp.alloc(qp.out_t, (size_t)n) || tmp.alloc(qp.out_u, (size_t)n) || tmp.alloc(qp.out_v, (size_t)n))) return 1;
+    HIP_TRY(hipMemsetAsync(q.d_words, 0, sizeof(QueryWords), nullptr));
+    HIP_TRY(hipStreamSynchronize(nullptr));  // (the caller's arrays have been read)
+    int64_t counters[3];
+    if (int rc = run_query<KIND>(scene, mode, qp, nullptr, counters)) return rc;
+    HIP_TRY(hipMemcpy(out_i, qp.out_i, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
+    if (KIND == Q_CLOSEST) {
+        HIP_TRY(hipMemcpy(t, qp.out_t, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(u, qp.out_u, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(v, qp.out_v, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
+    }
     return 0;
 }
 

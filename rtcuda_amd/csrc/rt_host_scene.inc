@@ -535,7 +535,7 @@ int ensure_origin_radius(const rt_scene *sc, const float need[3]) {
     return 0;
 }
 
-// ---- what the entry points that take rays share (frames, test rays, queries, ray tables, AOVs): each written once
+// ---- what the entry points that take rays share (frames, queries, trace hooks, ray tables, AOVs): each written once
 // The definition of a hit.  `literal` (RT_FLAG_REFERENCE_WALK): every ray through the reference's own tree.  `verify`, the
 // default: the reference's decisions on the product's own walk.  Neither (RT_FLAG_WATERTIGHT; per-sample): the triangle list's.
 struct HitMode {

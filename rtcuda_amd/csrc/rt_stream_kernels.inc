@@ -1,46 +1,38 @@
-// rt_stream_kernels.inc -- the kernels that walk a stream of rays: k_trace (the pools of a round, the stage-level test rays),
-// the query prepasses, k_query (rays from device buffers) and k_aov (first-hit feature buffers).  Included by rtcuda_amd.hip, once,
-// after rt_walk.inc.
-enum { MODE_POOL = 0, MODE_TEST_CLOSEST = 2, MODE_TEST_ANY = 3 };
-
+// rt_stream_kernels.inc -- the kernels that walk a stream of rays: k_trace (the pools of a round), the query prepasses, the
+// stream walker of every dense ray array with its two kernels, k_query (rays from device buffers: the queries and their
+// host-pointer form, the trace hooks) and k_aov (first-hit feature buffers).  Included by rtcuda_amd.hip, once, after rt_walk.inc.
 struct TraceParams {
-    int total;             // number of slots (MODE_POOL) or test rays
+    int total;             // number of slots
     int debug_no_deposit;  // perf experiments only: skip the framebuffer atomics
     int fb_fixed;          // framebuffer holds 64-bit fixed-point sums (see deposit())
-    float *fb;             // MODE_POOL: raw-sum framebuffer
-    DWaveRow *rows;        // MODE_POOL: counter rows
+    float *fb;             // raw-sum framebuffer
+    DWaveRow *rows;        // counter rows
     unsigned long long *prof;  // RT_TRACE_PROFILE builds only
     // lockstep rounds: nothing to trace in a round that shaded nothing (see k_advance); null / 0 otherwise
     const unsigned int *lock_shades;
     int lock_round;
-    // test modes
-    const float *o3, *d3, *tmax;
-    const int *order, *excluded;
-    int *out_i;
-    float *out_t, *out_u, *out_v;
     unsigned long long *vstat;  // VERIFY builds: DCounters::vstat
 };
 
-// MODE_POOL traces BOTH ray kinds of a round in one launch: the path ray of every live slot
+// k_trace traces BOTH ray kinds of a round in one launch: the path ray of every live slot
 // (closest hit, ch()) and the shadow ray of every slot that spawned one (any hit, ah()).  A lane
 // carries its kind with its ray, so closest-hit and any-hit rays share waves; the two kinds differ
 // only in what a triangle hit does and in how the finished ray is finalised.
 // LDS layout (dynamic): [stack: (stack_cap + 1) x kBlock ints (push_if)][pending: kBlock ints]
-// MINW: minimum waves per SIMD the register budget is sized for (8 = 64 VGPRs: the renderer's build; the split probe
-// also times the builds with 80 / 96 / 128 VGPRs).
+// The register budget is 8 waves per SIMD (64 VGPRs).
 // LITERAL (RT_FLAG_REFERENCE_WALK): a lane traverses its whole ray with reference_walk -- the scheduling around it
 // (chunks, refill, finalisation) is unchanged, WIDE is not looked at.
 // VERIFY (the default; off with RT_FLAG_WATERTIGHT): the product's walk with the reference's decisions -- see ref_visible.
-template <int MODE, bool WIDE, int MINW = 8, bool LITERAL = false, bool VERIFY = false>
-__global__ void __launch_bounds__(kBlock, MINW) k_trace(DScene sc, DPools p, TraceParams tp, int stack_cap, int *overflow) {
-    if (MODE == MODE_POOL && tp.lock_shades != nullptr && tp.lock_round >= 1 && tp.lock_shades[tp.lock_round] == 0u) return;
+template <bool WIDE, bool LITERAL = false, bool VERIFY = false>
+__global__ void __launch_bounds__(kBlock, 8) k_trace(DScene sc, DPools p, TraceParams tp, int stack_cap, int *overflow) {
+    if (tp.lock_shades != nullptr && tp.lock_round >= 1 && tp.lock_shades[tp.lock_round] == 0u) return;
     extern __shared__ int s_lds[];
     int *stack = s_lds + threadIdx.x;
     int *over = overflow + (blockIdx.x * kBlock + threadIdx.x);
     volatile int *pend = s_lds + (stack_cap + 1) * kBlock + (threadIdx.x & ~63);  // this wave's 64 entries
     const int total = tp.total;
-    const int n_chunks = (total + 63) >> 6;                            // chunks per ray kind
-    const int all_chunks = MODE == MODE_POOL ? 2 * n_chunks : n_chunks;  // [closest chunks][any chunks]
+    const int n_chunks = (total + 63) >> 6;  // chunks per ray kind
+    const int all_chunks = 2 * n_chunks;     // [closest chunks][any chunks]
     const unsigned lane = lane_id();
     constexpr int kAnyBit = 1 << 30;  // ray id = slot | kAnyBit for shadow rays
 
@@ -79,57 +71,33 @@ __global__ void __launch_bounds__(kBlock, MINW) k_trace(DScene sc, DPools p, Tra
             pf_refill++;
             pf_fin_lanes += wave_count((fin));
 #endif
-            const bool is_any = MODE == MODE_POOL ? (id & kAnyBit) != 0 : MODE == MODE_TEST_ANY;
-            if (VERIFY && !LITERAL && fin && !is_any && tri >= 0) {
-                // the closest hit stands if the reference's walk can see its triangle and nothing tied with it at the final
-                // distance (the sign of hv: see the leaf phase); otherwise (~2 rays in 10^7) the ray is re-traced literally
-                bool bad = (__float_as_uint(hv) >> 31) != 0u;
-                if (bad) {
-                    atomicAdd(&tp.vstat[V_TIE], 1ull);
-                } else {
-                    const Tri tr = load_tri(sc.tris, tri);
-                    bad = !ref_visible(sc, o, d, tr, tri, tp.vstat);
-                }
-                if (bad) {
-                    atomicAdd(&tp.vstat[V_LITERAL], 1ull);
-                    tmax = MODE == MODE_POOL ? kFltMax : tp.tmax[id & (kAnyBit - 1)];
-                    tri = -1;
-                    hu = hv = 0.f;
-                    reference_walk<false>(sc, o, d, tmax, tri, hu, hv, stack, over, stack_cap);
-                }
-            }
-            if (MODE == MODE_POOL) deposits += wave_count((fin && is_any && hu == 0.f));
+            const bool is_any = (id & kAnyBit) != 0;
+            // a path ray started with no limit: that is where its literal re-trace starts again
+            if (VERIFY && !LITERAL && fin && !is_any && tri >= 0)
+                verify_closest(sc, o, d, [] { return kFltMax; }, tmax, tri, hu, hv, tp.vstat, stack, over, stack_cap);
+            deposits += wave_count((fin && is_any && hu == 0.f));
             if (fin) {
                 const int slot = id & (kAnyBit - 1);
-                if (MODE == MODE_POOL) {
-                    if (!is_any) {
-                        // hit record in the form mat() consumes (render.cuh:152-153, 311-316)
-                        int info = -1;
-                        if (tri >= 0) {
-                            Tri tr = load_tri(sc.tris, tri);
-                            int2 ml = sc.tri_info[(unsigned)tri];
-                            V3 hp = tri_point(tr, hu, hv);
-                            V3 hn = neg(unit(tr.n));
-                            p.hpx(slot) = hp.x;
-                            p.hpy(slot) = hp.y;
-                            p.hpz(slot) = hp.z;
-                            p.hnx(slot) = hn.x;
-                            p.hny(slot) = hn.y;
-                            p.hnz(slot) = hn.z;
-                            info = (ml.x & 0xffff) | ((ml.y + 1) << 16);
-                        }
-                        p.hit_info(slot) = info;
-                    } else if (hu == 0.f && !tp.debug_no_deposit) {  // unoccluded: render.cuh:291-293
-                        int pixel = p.pixel(slot);
-                        deposit(tp.fb, tp.fb_fixed, pixel, p.slr(slot), p.slg(slot), p.slb(slot));
+                if (!is_any) {
+                    // hit record in the form mat() consumes (render.cuh:152-153, 311-316)
+                    int info = -1;
+                    if (tri >= 0) {
+                        Tri tr = load_tri(sc.tris, tri);
+                        int2 ml = sc.tri_info[(unsigned)tri];
+                        V3 hp = tri_point(tr, hu, hv);
+                        V3 hn = neg(unit(tr.n));
+                        p.hpx(slot) = hp.x;
+                        p.hpy(slot) = hp.y;
+                        p.hpz(slot) = hp.z;
+                        p.hnx(slot) = hn.x;
+                        p.hny(slot) = hn.y;
+                        p.hnz(slot) = hn.z;
+                        info = (ml.x & 0xffff) | ((ml.y + 1) << 16);
                     }
-                } else if (MODE == MODE_TEST_CLOSEST) {
-                    tp.out_i[slot] = tri >= 0 ? tp.order[tri] : -1;
-                    tp.out_t[slot] = tri >= 0 ? tmax : 0.f;
-                    tp.out_u[slot] = hu;
-                    tp.out_v[slot] = hv;
-                } else {
-                    tp.out_i[slot] = hu != 0.f ? 1 : 0;
+                    p.hit_info(slot) = info;
+                } else if (hu == 0.f && !tp.debug_no_deposit) {  // unoccluded: render.cuh:291-293
+                    int pixel = p.pixel(slot);
+                    deposit(tp.fb, tp.fb_fixed, pixel, p.slr(slot), p.slg(slot), p.slb(slot));
                 }
                 id = -1;
             }
@@ -144,11 +112,10 @@ __global__ void __launch_bounds__(kBlock, MINW) k_trace(DScene sc, DPools p, Tra
                     if (chunk >= all_chunks) {
                         exhausted = true;
                     } else {
-                        const bool any_chunk = MODE == MODE_POOL && chunk >= n_chunks;
+                        const bool any_chunk = chunk >= n_chunks;
                         int cand = (any_chunk ? chunk - n_chunks : chunk) * 64 + (int)lane;
                         bool valid = cand < total;
-                        if (MODE == MODE_POOL && valid)
-                            valid = any_chunk ? p.stmax(cand) >= 0.f : (p.bounces(cand) != kDone && p.bounces(cand) != kParked);
+                        if (valid) valid = any_chunk ? p.stmax(cand) >= 0.f : (p.bounces(cand) != kDone && p.bounces(cand) != kParked);
                         unsigned long long vm = wave_ballot(valid);
                         if (valid) pend[prefix_popc(vm)] = any_chunk ? (cand | kAnyBit) : cand;
                         pend_lo = 0;
@@ -161,23 +128,16 @@ __global__ void __launch_bounds__(kBlock, MINW) k_trace(DScene sc, DPools p, Tra
                     if (id < 0 && r < avail) {
                         int my = pend[pend_lo + r];
                         int slot = my & (kAnyBit - 1);
-                        if (MODE == MODE_POOL) {
-                            if (my & kAnyBit) {
-                                o = mk(p.sox(slot), p.soy(slot), p.soz(slot));
-                                d = mk(p.sdx(slot), p.sdy(slot), p.sdz(slot));
-                                tmax = p.stmax(slot);
-                                tri = p.starget(slot);
-                            } else {
-                                o = mk(p.ox(slot), p.oy(slot), p.oz(slot));
-                                d = mk(p.dx(slot), p.dy(slot), p.dz(slot));
-                                tmax = kFltMax;
-                                tri = -1;
-                            }
+                        if (my & kAnyBit) {
+                            o = mk(p.sox(slot), p.soy(slot), p.soz(slot));
+                            d = mk(p.sdx(slot), p.sdy(slot), p.sdz(slot));
+                            tmax = p.stmax(slot);
+                            tri = p.starget(slot);
                         } else {
-                            o = mk(tp.o3[3 * slot], tp.o3[3 * slot + 1], tp.o3[3 * slot + 2]);
-                            d = mk(tp.d3[3 * slot], tp.d3[3 * slot + 1], tp.d3[3 * slot + 2]);
-                            tmax = tp.tmax[slot];
-                            tri = MODE == MODE_TEST_ANY ? tp.excluded[slot] : -1;
+                            o = mk(p.ox(slot), p.oy(slot), p.oz(slot));
+                            d = mk(p.dx(slot), p.dy(slot), p.dz(slot));
+                            tmax = kFltMax;
+                            tri = -1;
                         }
                         id = my;
                         inv = inv_dir(d);
@@ -198,8 +158,7 @@ __global__ void __launch_bounds__(kBlock, MINW) k_trace(DScene sc, DPools p, Tra
         }
         if (LITERAL) {
             if (cur >= 0) {
-                const bool is_any = MODE == MODE_POOL ? (id & kAnyBit) != 0 : MODE == MODE_TEST_ANY;
-                if (is_any) reference_walk<true>(sc, o, d, tmax, tri, hu, hv, stack, over, stack_cap);
+                if ((id & kAnyBit) != 0) reference_walk<true>(sc, o, d, tmax, tri, hu, hv, stack, over, stack_cap);
                 else reference_walk<false>(sc, o, d, tmax, tri, hu, hv, stack, over, stack_cap);
                 cur = kEntryDone;
             }
@@ -213,7 +172,8 @@ __global__ void __launch_bounds__(kBlock, MINW) k_trace(DScene sc, DPools p, Tra
 #endif
             if (cur >= 0) inner_step<WIDE>(sc, o, inv, tmax, cur, sp, stack, over, stack_cap);
         }
-        // ---- leaf phase: every lane that holds a leaf tests its triangles (triangle.cuh:39-58)
+        // ---- leaf phase: every lane that holds a leaf tests its triangles (triangle.cuh:39-58).  The ray kind is a run-time
+        // value of the lane here, so the two hit rules of leaf_hits (rt_walk.inc) stand side by side in one loop.
 #ifdef RT_TRACE_PROFILE
         {
             unsigned long long lm = wave_ballot(cur != kEntryDone && cur < 0);
@@ -229,7 +189,7 @@ __global__ void __launch_bounds__(kBlock, MINW) k_trace(DScene sc, DPools p, Tra
         }
 #endif
         if (cur != kEntryDone && cur < 0) {
-            const bool is_any = MODE == MODE_POOL ? (id & kAnyBit) != 0 : MODE == MODE_TEST_ANY;
+            const bool is_any = (id & kAnyBit) != 0;
             int ref = ~cur;
             int first = ref >> 3, count = ref & 7;
             bool stop = false;
@@ -268,11 +228,9 @@ __global__ void __launch_bounds__(kBlock, MINW) k_trace(DScene sc, DPools p, Tra
             }
         }
     }
-    if (MODE == MODE_POOL) {
-        if (deposits != 0 && lane == 0) atomicAdd(&tp.rows[wave_index()].c[C_SHADOW_ADD], deposits);
-    }
+    if (deposits != 0 && lane == 0) atomicAdd(&tp.rows[wave_index()].c[C_SHADOW_ADD], deposits);
 #ifdef RT_TRACE_PROFILE
-    if (MODE == MODE_POOL && lane == 0 && tp.prof) {
+    if (lane == 0 && tp.prof) {
         atomicAdd(&tp.prof[0], pf_outer); atomicAdd(&tp.prof[1], pf_refill); atomicAdd(&tp.prof[2], pf_inner_it);
         atomicAdd(&tp.prof[3], pf_inner_lanes); atomicAdd(&tp.prof[4], pf_leaf_it); atomicAdd(&tp.prof[5], pf_leaf_lanes);
         atomicAdd(&tp.prof[6], pf_tri_it); atomicAdd(&tp.prof[7], pf_tri_lanes); atomicAdd(&tp.prof[8], pf_act_at_top);
@@ -282,9 +240,10 @@ __global__ void __launch_bounds__(kBlock, MINW) k_trace(DScene sc, DPools p, Tra
 }
 
 // ============================================================================ k_query: ray queries on device buffers
-// rt_query_closest_device / rt_query_any_device: the caller's rays, from the caller's device buffers, through the same
-// shared device functions as k_trace and k_paths (inv_dir, inner_step, tri_intersect, closest_hit_wins, ref_visible,
-// reference_walk, the stack helpers) -- the hit decisions are theirs, only the way from a buffer to them and back is new.
+// rt_query_closest_device / rt_query_any_device and their host-pointer form, rt_trace_closest / rt_trace_any: the caller's rays,
+// from device buffers, through the same shared device functions as k_trace and k_paths (inv_dir, inner_step, tri_intersect,
+// closest_hit_wins, ref_visible, reference_walk, the stack helpers) -- the hit decisions are theirs, only the way from a buffer
+// to them and back is this kernel's.
 enum { Q_CLOSEST = 0, Q_ANY = 1 };
 struct QueryWords {           // the scratch of one query call (rt_scene::QueryState::d_words), zeroed before the prepass
     unsigned radius_bits[3];  // per axis: max |origin| over the finite origin components, as the bits of that float
@@ -368,7 +327,7 @@ __global__ void k_query_inverse(const int *__restrict__ order, int n, int *__res
 // LDS (dynamic): the stack columns, (stack_cap + 1) x kBlock ints (push_if).
 // Registers: no pool, shading or camera state is carried, but the VERIFY finalisation (ref_visible + the literal re-trace)
 // and the 4-wide node step with its seven 16-byte loads in flight want 71 VGPRs -- over the 64 of 8 waves per SIMD, where
-// k_trace's test modes spill 26.  Measured on C2, 2^22 rays (tools/query_time.py, device time of the whole call): budget 8
+// the dense-array modes k_trace once had spilled 26.  Measured on C2, 2^22 rays (tools/query_time.py, device time of the whole call): budget 8
 // 0.689 / 0.912 / 0.703 ms for camera / bounce / shadow rays, budgets 4 to 7 (one and the same code: 71 VGPRs, 7 waves per SIMD,
 // no spill, no scratch) 0.565 / 0.730 / 0.680 ms.  kQueryRefillAt: 24, 32, 48 and 56 all land within 1 % of each other on the
 // three batches (the spread of one setting's repetitions is 2 %), so k_trace's 40 stays.
@@ -455,7 +414,9 @@ __device__ __forceinline__ void stream_walk(const DScene &sc, ENDS &ends, int n,
 }
 
 // k_query: the rays come from the caller's buffers and the answers go back into them.
-// KIND / WIDE / LITERAL / VERIFY: as k_trace's MODE_TEST_* / WIDE / LITERAL / VERIFY.
+// KIND: Q_CLOSEST (the hit triangle in the caller's order, t, u, v; zeros on a miss) or Q_ANY (the occluded flag; the caller's
+// excluded triangle goes through `inverse` to leaf order, an index outside 0 .. n_tris - 1 excludes nothing).
+// WIDE / LITERAL / VERIFY: as k_trace's.
 template <int KIND>
 struct QueryEnds {
     const DScene &sc;

@@ -1,7 +1,8 @@
 // rt_tools.hip -- the LAB: measurement tools that are not part of the product's C-ABI (include/rtcuda_amd_tools.h).
 //
 // librtcuda_amd_tools.so is built from this file, which includes the product's translation unit -- so the tools measure the
-// product's own kernels (the split probe runs k_advance / k_trace and the product's advance_core on dumped rays) -- and adds:
+// product's own kernels (the split probe runs k_advance / k_trace, the product's stream walker on dumped rays and its
+// advance_core on dumped shading records) -- and adds:
 //   rt_measure_copy_bandwidth   device copy bandwidth (the HBM roof SURVEY 8d wants measured in the same run)
 //   rt_calibrate_valu(_packed)  what the vector ALUs sustain on independent v_fma_f32 / v_pk_* streams
 //   rt_probe_issue              cycles per instruction of one wave, by instruction kind and occupancy
@@ -159,7 +160,8 @@ __global__ void __launch_bounds__(256) k_probe_issue(float *__restrict__ out, in
 // (render.cuh:428-449) with dense queues -- beat k_paths?".  The round pipeline's pools are copied, round after round,
 // into DENSE arrays: the rays k_trace is about to trace (closest-hit and any-hit apart), and the slot records
 // k_advance is about to shade (one bucket per material kind: a wave of the shading probe sees one material).
-// The trace side is then timed with k_trace's stage-level modes on those arrays, the shade side with k_probe_shade.
+// The trace side is then timed with the walker the project ships for dense ray arrays (stream_walk under k_query's ends:
+// k_probe_walk), the shade side with k_probe_shade.
 constexpr int kProbeIn = 22;   // dwords of a shading record: bounces, hit_info, pixel, gen, rng 6, beta 3, wo 3, p 3, n 3
 constexpr int kProbeOut = 27;  // dwords a shade writes: ray 6, shadow ray 6 + tmax + L 3 + target, beta 3, rng 6, bounces
 __global__ void __launch_bounds__(kBlock)
@@ -204,6 +206,21 @@ k_probe_dump_rays(DPools p, int n, float *__restrict__ c_o3, float *__restrict__
             a_excl[k] = p.starget(i);
         }
     }
+}
+// The pools name a shadow ray's excluded triangle in leaf order, a query names it in the caller's order: the dumped
+// indices are turned into what QueryParams::excluded takes, once, after the last dump.
+__global__ void k_probe_excl_to_caller(const int *__restrict__ order, int n_tris, int *__restrict__ excl, unsigned n) {
+    const unsigned k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const int e = excl[k];
+    excl[k] = (e >= 0 && e < n_tris) ? order[e] : -1;
+}
+// k_query (QueryEnds + stream_walk, the watertight build) at a register budget of MINW waves per SIMD: the product compiles
+// it at kQueryMinWaves only.
+template <int KIND, bool WIDE, int MINW>
+__global__ void __launch_bounds__(kBlock, MINW) k_probe_walk(DScene sc, QueryParams qp, int stack_cap, int *overflow) {
+    QueryEnds<KIND> ends{sc, qp};
+    stream_walk<KIND == Q_ANY, WIDE, false, false>(sc, ends, qp.n, qp.vstat, stack_cap, overflow);
 }
 // the slots the NEXT k_advance will shade (hit, bounce left: render.cuh:109,128-130), by material kind
 __global__ void __launch_bounds__(kBlock)
@@ -394,20 +411,18 @@ k_shade_table(int func, int n, int win, int wout, const uint32_t *__restrict__ i
 
 // ---- split probe: see the kernels (k_probe_*) for what is measured
 namespace {
-template <int MODE, bool WIDE, int MINW>
-int probe_trace_once(const rt_scene *scene, const TraceParams &tp, int stack_cap, int *d_over, int cus, hipEvent_t e0,
+template <int KIND, bool WIDE, int MINW>
+int probe_trace_once(const rt_scene *scene, const QueryParams &qp, int stack_cap, int *d_over, int cus, hipEvent_t e0,
                      hipEvent_t e1, double *seconds, double *blocks_per_cu) {
-    const size_t lds = sizeof(int) * kBlock * (size_t)(stack_cap + 2);
+    const size_t lds = sizeof(int) * kBlock * (size_t)(stack_cap + 1);
     int occ = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_trace<MODE, WIDE, MINW>, kBlock, lds));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_probe_walk<KIND, WIDE, MINW>, kBlock, lds));
     occ = std::max(1, occ);
-    const int grid = std::max(1, std::min(grid_for(tp.total), cus * occ));
+    const int grid = std::max(1, std::min(grid_for(qp.n), std::min(cus * occ, kOverStride / kBlock)));
     double best = 1e30;
-    DPools none{};
     for (int rep = 0; rep < 3; rep++) {
         HIP_TRY(hipEventRecord(e0, nullptr));
-        hipLaunchKernelGGL((k_trace<MODE, WIDE, MINW>), dim3(grid), dim3(kBlock), lds, nullptr, scene->dev(), none, tp,
-                           stack_cap, d_over);
+        hipLaunchKernelGGL((k_probe_walk<KIND, WIDE, MINW>), dim3(grid), dim3(kBlock), lds, nullptr, scene->dev(), qp, stack_cap, d_over);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(e1, nullptr));
         HIP_TRY(hipEventSynchronize(e1));
@@ -419,14 +434,14 @@ int probe_trace_once(const rt_scene *scene, const TraceParams &tp, int stack_cap
     *blocks_per_cu = occ;
     return 0;
 }
-template <int MODE, bool WIDE>
-int probe_trace(const rt_scene *scene, const TraceParams &tp, int stack_cap, int *d_over, int cus, hipEvent_t e0, hipEvent_t e1,
+template <int KIND, bool WIDE>
+int probe_trace(const rt_scene *scene, const QueryParams &qp, int stack_cap, int *d_over, int cus, hipEvent_t e0, hipEvent_t e1,
                 int minw, double *seconds, double *blocks_per_cu) {
     switch (minw) {
-        case 8: return probe_trace_once<MODE, WIDE, 8>(scene, tp, stack_cap, d_over, cus, e0, e1, seconds, blocks_per_cu);
-        case 6: return probe_trace_once<MODE, WIDE, 6>(scene, tp, stack_cap, d_over, cus, e0, e1, seconds, blocks_per_cu);
-        case 5: return probe_trace_once<MODE, WIDE, 5>(scene, tp, stack_cap, d_over, cus, e0, e1, seconds, blocks_per_cu);
-        default: return probe_trace_once<MODE, WIDE, 4>(scene, tp, stack_cap, d_over, cus, e0, e1, seconds, blocks_per_cu);
+        case 8: return probe_trace_once<KIND, WIDE, 8>(scene, qp, stack_cap, d_over, cus, e0, e1, seconds, blocks_per_cu);
+        case 6: return probe_trace_once<KIND, WIDE, 6>(scene, qp, stack_cap, d_over, cus, e0, e1, seconds, blocks_per_cu);
+        case 5: return probe_trace_once<KIND, WIDE, 5>(scene, qp, stack_cap, d_over, cus, e0, e1, seconds, blocks_per_cu);
+        default: return probe_trace_once<KIND, WIDE, 4>(scene, qp, stack_cap, d_over, cus, e0, e1, seconds, blocks_per_cu);
     }
 }
 }  // namespace
@@ -578,12 +593,12 @@ int rt_split_probe(const rt_scene *scene, const rt_camera *camera, int width, in
     HIP_TRY(hipEventCreate(&pb.e1));
     const unsigned cap = (unsigned)(target_rays + 2 * (long long)kW);
     float *c_o3, *c_d3, *c_tmax, *a_o3, *a_d3, *a_tmax, *rec, *outp, *fb, *o_t, *o_u, *o_v;
-    int *a_excl, *o_i;
+    int *a_excl, *o_i, *inverse;
     unsigned *d_counts;
     if (pb.alloc(c_o3, 3 * (size_t)cap) || pb.alloc(c_d3, 3 * (size_t)cap) || pb.alloc(c_tmax, cap) || pb.alloc(a_o3, 3 * (size_t)cap) ||
         pb.alloc(a_d3, 3 * (size_t)cap) || pb.alloc(a_tmax, cap) || pb.alloc(a_excl, cap) || pb.alloc(rec, 3 * (size_t)kProbeIn * cap) ||
         pb.alloc(outp, (size_t)kProbeOut * cap) || pb.alloc(fb, 3 * (size_t)width * height) || pb.alloc(o_i, cap) || pb.alloc(o_t, cap) ||
-        pb.alloc(o_u, cap) || pb.alloc(o_v, cap) || pb.alloc(d_counts, 8))
+        pb.alloc(o_u, cap) || pb.alloc(o_v, cap) || pb.alloc(d_counts, 8) || pb.alloc(inverse, (size_t)scene->n_tris))
         return 1;
     HIP_TRY(hipMemset(d_counts, 0, sizeof(unsigned) * 8));
     HIP_TRY(hipMemset(fb, 0, sizeof(float) * 3 * (size_t)width * height));
@@ -614,7 +629,7 @@ int rt_split_probe(const rt_scene *scene, const rt_camera *camera, int width, in
     const size_t lds_bytes = sizeof(int) * (size_t)kBlock * (size_t)(stack_cap + 2);
     if (ensure_overflow(c.d_over, c.over_levels, scene->stack_bound - std::min(stack_cap, lds_stack_cap(scene, kPathsLdsStack)))) return 1;
     const AdvanceKernel advance = advance_kernel(lds_tables);
-    const TraceKernel trace = trace_kernel<MODE_POOL>(false, false, scene->wide);  // (the watertight build)
+    const TraceKernel trace = trace_kernel(false, false, scene->wide);  // (the watertight build)
     int occ_c = 0;
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_c, trace, kBlock, lds_bytes));
     const dim3 grid(grid_for(n)), block(kBlock), grid_trace(std::min(grid_for(n), std::max(1, cus * std::max(1, occ_c))));
@@ -662,36 +677,27 @@ int rt_split_probe(const rt_scene *scene, const rt_camera *camera, int width, in
     out[RT_PROBE_S_ADVANCE_ROUND0] = t_adv0;
     out[RT_PROBE_S_ADVANCE] = t_adv;
     out[RT_PROBE_S_TRACE_POOL] = t_trace;
-    // ---- trace only: the stage-level modes of k_trace on the dense ray arrays, at four register budgets
+    // ---- trace only: the dense-array walker (k_probe_walk) on the dumped rays, at four register budgets
     {
-        TraceParams tc{};
-        tc.total = (int)n_c;
-        tc.o3 = c_o3;
-        tc.d3 = c_d3;
-        tc.tmax = c_tmax;
-        tc.order = scene->d_order;
-        tc.out_i = o_i;
-        tc.out_t = o_t;
-        tc.out_u = o_u;
-        tc.out_v = o_v;
-        TraceParams ta{};
-        ta.total = (int)n_a;
-        ta.o3 = a_o3;
-        ta.d3 = a_d3;
-        ta.tmax = a_tmax;
-        ta.excluded = a_excl;
-        ta.out_i = o_i;
+        if (n_a > 0) {
+            hipLaunchKernelGGL(k_query_inverse, dim3((scene->n_tris + 255) / 256), dim3(256), 0, nullptr, scene->d_order, scene->n_tris, inverse);
+            hipLaunchKernelGGL(k_probe_excl_to_caller, dim3((n_a + 255) / 256), dim3(256), 0, nullptr, scene->d_order, scene->n_tris, a_excl, n_a);
+            HIP_TRY(hipGetLastError());
+        }
+        // (n, n_tris, o3, d3, tmax, excluded, inverse, out_i, out_t, out_u, out_v, vstat: the watertight build counts nothing)
+        const QueryParams tc{(int)n_c, scene->n_tris, c_o3, c_d3, c_tmax, nullptr, nullptr, o_i, o_t, o_u, o_v, &c.d_ctr->vstat[0]};
+        const QueryParams ta{(int)n_a, scene->n_tris, a_o3, a_d3, a_tmax, a_excl, inverse, o_i, nullptr, nullptr, nullptr, &c.d_ctr->vstat[0]};
         const int budgets[4] = {8, 6, 5, 4};
         for (int v = 0; v < 4; v++) {
             double sc_s = 0.0, sa_s = 0.0, bc = 0.0, ba = 0.0;
             if (n_c > 0) {
-                if (scene->wide ? probe_trace<MODE_TEST_CLOSEST, true>(scene, tc, stack_cap, c.d_over, cus, pb.e0, pb.e1, budgets[v], &sc_s, &bc)
-                                : probe_trace<MODE_TEST_CLOSEST, false>(scene, tc, stack_cap, c.d_over, cus, pb.e0, pb.e1, budgets[v], &sc_s, &bc))
+                if (scene->wide ? probe_trace<Q_CLOSEST, true>(scene, tc, stack_cap, c.d_over, cus, pb.e0, pb.e1, budgets[v], &sc_s, &bc)
+                                : probe_trace<Q_CLOSEST, false>(scene, tc, stack_cap, c.d_over, cus, pb.e0, pb.e1, budgets[v], &sc_s, &bc))
                     return 1;
             }
             if (n_a > 0) {
-                if (scene->wide ? probe_trace<MODE_TEST_ANY, true>(scene, ta, stack_cap, c.d_over, cus, pb.e0, pb.e1, budgets[v], &sa_s, &ba)
-                                : probe_trace<MODE_TEST_ANY, false>(scene, ta, stack_cap, c.d_over, cus, pb.e0, pb.e1, budgets[v], &sa_s, &ba))
+                if (scene->wide ? probe_trace<Q_ANY, true>(scene, ta, stack_cap, c.d_over, cus, pb.e0, pb.e1, budgets[v], &sa_s, &ba)
+                                : probe_trace<Q_ANY, false>(scene, ta, stack_cap, c.d_over, cus, pb.e0, pb.e1, budgets[v], &sa_s, &ba))
                     return 1;
             }
             out[RT_PROBE_S_TRACE_CLOSEST + v] = sc_s;

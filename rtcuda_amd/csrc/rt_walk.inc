@@ -1,9 +1,9 @@
 // rt_walk.inc -- the walk every ray kernel shares: the box test, the traversal stack, the node step, the literal reference walk
 // and the VERIFY procedure (the reference's decisions on the product's walk).  Included by rtcuda_amd.hip, once.
 // ============================================================================ traversal
-// One wave-wide traversal engine serves the four trace entry points (closest-hit over the path
-// pools = ch(), render.cuh:297-328; any-hit over the shadow queue = ah(), :278-294; and the two
-// stage-level test hooks), so the parity tests exercise exactly the code the renderer runs.
+// One wave-wide traversal engine serves every ray kernel (closest-hit over the path pools = ch(),
+// render.cuh:297-328; any-hit over the shadow queue = ah(), :278-294; the queries and the trace
+// hooks on top of them), so the parity tests exercise exactly the code the renderer runs.
 //
 // Structure (wave64, persistent):
 //   * every wave owns 64 lanes = 64 rays in flight and keeps pulling ray indices from a global
@@ -493,11 +493,12 @@ __device__ __forceinline__ bool ref_visible(const DScene &sc, V3 o, V3 d, const 
 }
 
 // ---- the two hit rules and the closest hit's finalisation, as the stream walker (k_query, k_aov: rt_stream_kernels.inc) applies
-// them.  k_trace and k_paths hold the same rules in their own text: k_trace's lanes carry their ray kind at run time and
+// them.  k_trace and k_paths hold the hit rules in their own text: k_trace's lanes carry their ray kind at run time and
 // k_paths' triangle block tests two triangles per step beside a speculated leaf, its finalisation sits between the ADV block's
-// reloads of the slot state -- and with these helpers in place neither kernel's instances compile to the instructions they had
-// (profiles/stream_walk.md), which is the bar for touching them.  A change to a rule is made here, in k_trace's refill and leaf
-// phases, and in the ADV and triangle blocks of rt_frame_kernels.inc.
+// reloads of the slot state -- and with leaf_hits in place neither kernel's instances compile to the instructions they had
+// (profiles/stream_walk.md), which is the bar for touching them.  k_trace, pool-only, does share verify_closest
+// (profiles/trace_hooks.md).  A change to a rule is made here, in k_trace's leaf phase, and in the ADV and triangle blocks of
+// rt_frame_kernels.inc.
 // The triangles of leaf `ref` (= ~cur: first << 3 | count) against the lane's ray (triangle.cuh:39-58).  `tri` / `tmax`: best hit
 // so far (closest) or the excluded triangle (any hit).  True: the ray is finished -- an any-hit ray found its occluder, hu = 1.
 //   any hit: bvh.cuh:243, the first accepted hit that is not the excluded triangle (VERIFY: and that the reference's walk can

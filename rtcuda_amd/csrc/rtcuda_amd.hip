@@ -2,12 +2,13 @@
 // The root of the one translation unit.  Here: the constants, the device structures and wave helpers, RNG and pool initialisation,
 // the table builders, gen_core / advance_core, the k_paths knobs, the post-process kernels and the C-ABI.  Included, in this order:
 //   rt_walk.inc            box test, traversal stack, inner_step; reference_walk; VERIFY (ref_visible); leaf_hits, verify_closest
-//   rt_stream_kernels.inc  k_trace; the query prepasses; stream_walk, the persistent loop of k_query and k_aov; k_aov_resolve
+//   rt_stream_kernels.inc  k_trace (the pools of a round); the query prepasses; stream_walk, the persistent loop of every dense ray
+//                          array, under k_query (queries and trace hooks) and k_aov; k_aov_resolve
 //   rt_frame_kernels.inc   k_advance and k_paths, once per source of camera rays
 //   rt_build_kernels.inc   device BVH: the leaf-order arrays, the refit (k_refit_*), the build (k_ploc_*)
 //   rt_host_scene.inc      rt_scene and the one way a tree gets into it: build (host SAH, device PLOC), emit, adopt; the entry
 //                          points on top of it (create, update, rebuild, the edits); what the ray entry points share
-//   rt_host_render.inc     Context, kernel selection, frames, test rays, queries, ray tables, AOVs
+//   rt_host_render.inc     Context, kernel selection, frames, queries and their host-pointer form (the trace hooks), ray tables, AOVs
 //   rt_denoise_kernels.inc the denoisers' kernels: one tap loop (dn_filter_pixel) and two pass bodies (dn_pass_direct, dn_pass_lds) under
 //                          k_atrous* / k_atrous_var*; prepare, finish, k_dn_var_blur (arithmetic: rt_denoise.h, shared with the CPU twin)
 //   rt_host_denoise.inc    rt_denoise_fixed and rt_denoise_dual_fixed: one set of checks (dn_check), one pass launcher, one run (dn_run)
@@ -41,11 +42,12 @@
 //   k_trace      SoA pools; ch() + ah() of a round (render.cuh:278-328) with persistent waves, ballot +
 //                mbcnt compaction into a per-wave LDS queue instead of flag arrays + CUB select
 //                (render.cuh:348-364), while-while traversal, LDS stack.  Used for the lockstep final
-//                generation, by the stage-level test entry points, and (RT_PERSISTENT=0) for whole frames.
+//                generation and (RT_PERSISTENT=0) for whole frames: it walks pools and nothing else.
 //   advance_core / inner_step / tri_intersect / box_hit are the shared device functions: one copy of
 //   the estimator and of the traversal for both pipelines.
-//   k_query      the caller's rays from device buffers, and the first-hit feature buffers: two pairs of ends on one persistent
-//   k_aov        loop over a stream of ray ids (stream_walk, rt_stream_kernels.inc).
+//   k_query      the caller's rays from device buffers (rt_query_*_device, and rt_trace_* with host pointers), and the first-hit
+//   k_aov        feature buffers: two pairs of ends on one persistent loop over a stream of ray ids (stream_walk,
+//                rt_stream_kernels.inc), the walker of every dense ray array.
 //   * BVH: 64-byte node records with full-precision padded boxes -- a 4-wide node as two consecutive
 //     records (default), or 2-wide nodes of one record (RT_BVH_WIDE=0) --
 //     and 48-byte {p0,e1,e2,n} triangle records in leaf order (rt_bvh.h: SAH sweep + insertion-based
@@ -877,7 +879,7 @@ __global__ void k_test_draw(DPools p, int n, int draws, uint32_t *__restrict__ s
 #include "rt_denoise_kernels.inc"  // dn_filter_pixel under k_atrous* and k_atrous_var*; k_dn_prepare*, k_dn_var_blur, k_dn_finish*
 
 #include "rt_host_scene.inc"   // (opens the anonymous namespace that is closed below) rt_scene: reference tree, checks, build / emit / adopt, create, update, rebuild, edits; what the ray entry points share
-#include "rt_host_render.inc"  // Context, kernel selection, frames, test rays, queries, ray tables, AOVs
+#include "rt_host_render.inc"  // Context, kernel selection, frames, queries and trace hooks, ray tables, AOVs
 #include "rt_host_denoise.inc"  // rt_denoise_fixed, rt_denoise_dual_fixed
 }  // namespace
 
@@ -1370,22 +1372,7 @@ int rt_trace_closest_flags(const rt_scene *scene, uint32_t flags, int n, const f
     if (!scene || n < 0 || (n > 0 && (!origin_xyz || !dir_xyz || !tmax || !hit_tri || !t || !u || !v)))
         return fail("rt_trace_closest: bad argument");
     if (n == 0) return 0;
-    float *d_t, *d_u, *d_v;
-    int *d_h;
-    DevScope tmp;
-    if (tmp.alloc(d_t, (size_t)n) || tmp.alloc(d_u, (size_t)n) || tmp.alloc(d_v, (size_t)n) || tmp.alloc(d_h, (size_t)n)) return 1;
-    TraceParams tp{};
-    tp.order = scene->d_order;
-    tp.out_i = d_h;
-    tp.out_t = d_t;
-    tp.out_u = d_u;
-    tp.out_v = d_v;
-    if (int rc = trace_test_rays<MODE_TEST_CLOSEST>(scene, flags, n, origin_xyz, dir_xyz, tmax, tp, tmp)) return rc;
-    HIP_TRY(hipMemcpy(hit_tri, d_h, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(t, d_t, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(u, d_u, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(v, d_v, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
-    return 0;
+    return trace_hook<Q_CLOSEST>(scene, flags, n, origin_xyz, dir_xyz, tmax, nullptr, hit_tri, t, u, v);
 }
 
 int rt_trace_any(const rt_scene *scene, int n, const float *origin_xyz, const float *dir_xyz, const float *tmax,
@@ -1398,21 +1385,7 @@ int rt_trace_any_flags(const rt_scene *scene, uint32_t flags, int n, const float
     if (!scene || n < 0 || (n > 0 && (!origin_xyz || !dir_xyz || !tmax || !excluded_tri || !occluded)))
         return fail("rt_trace_any: bad argument");
     if (n == 0) return 0;
-    std::vector<int> excl(n);
-    for (int i = 0; i < n; i++) {
-        int e = excluded_tri[i];
-        excl[i] = (e >= 0 && e < scene->n_tris) ? scene->h_inverse[e] : -1;
-    }
-    int *d_e, *d_occ;
-    DevScope tmp;
-    if (tmp.alloc(d_e, (size_t)n) || tmp.alloc(d_occ, (size_t)n)) return 1;
-    HIP_TRY(hipMemcpy(d_e, excl.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
-    TraceParams tp{};
-    tp.excluded = d_e;
-    tp.out_i = d_occ;
-    if (int rc = trace_test_rays<MODE_TEST_ANY>(scene, flags, n, origin_xyz, dir_xyz, tmax, tp, tmp)) return rc;
-    HIP_TRY(hipMemcpy(occluded, d_occ, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
-    return 0;
+    return trace_hook<Q_ANY>(scene, flags, n, origin_xyz, dir_xyz, tmax, excluded_tri, occluded, nullptr, nullptr, nullptr);
 }
 
 int rt_query_closest_device(const rt_scene *scene, uint32_t flags, int n, const float *d_origin_xyz, const float *d_dir_xyz,

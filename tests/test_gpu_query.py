@@ -372,3 +372,130 @@ def test_empty_batch_and_optional_outputs(api, oracle, bunny_matte):
     gpu.query_closest_device(o_dev.data_ptr(), d_dev.data_ptr(), 0, n, hit.data_ptr())  # only the triangle
     assert np.array_equal(hit.cpu().numpy(), want[0])
     gpu.close()
+
+
+# ---- 10: the host-pointer form (rt_trace_closest / rt_trace_any) is the device query's kernel behind copies
+HOOK_SIZES = (1, 63, 64, 65, 4099)  # one lane; one short of a chunk, one chunk, one over; several chunks and a ragged tail
+
+
+_hook_cases = {}
+
+
+def _hook_case(oracle, bunny_matte, name):
+    """(arrays, literal oracle scene, closest-hit rays, any-hit batch) of the bare Cornell box / the box with the bunny.  The
+    4099 camera rays of this seed hold a hit and a miss among the first 63 on both scenes in all three hit modes, and the
+    any-hit batch made from them an occluded and a free ray (checked on the CPU oracle when the seeds were chosen; asserted
+    again by the test that relies on it)."""
+    if name not in _hook_cases:
+        from rtcuda_amd import scenes
+        arrays = scenes.cornell_bunny("matte", bunny=False) if name == "box" else bunny_matte
+        cpu = oracle.scene(arrays) if name == "box" else oracle_scene(oracle, "matte", False)
+        o, d = raygen.camera_rays(default_camera(oracle, 16 / 9), 1920, 1080, HOOK_SIZES[-1], seed=81)
+        batch = tuple(np.ascontiguousarray(x[np.arange(len(o)) % len(x)]) for x in _any_batch(cpu, arrays, o, d, seed=82))
+        _hook_cases[name] = arrays, cpu, (o, d), batch
+    return _hook_cases[name]
+
+
+both_scenes = pytest.mark.parametrize("name", ["box", "bunny"])
+
+
+@both_scenes
+def test_hooks_give_the_device_queries_answers(api, oracle, bunny_matte, name):
+    arrays, _, (o_all, d_all), (o2_all, d2_all, tm_all, excl_all) = _hook_case(oracle, bunny_matte, name)
+    gpu = api.Scene(arrays)
+    for flags, _ in _flag_modes(api):
+        for n in HOOK_SIZES:
+            o, d = o_all[:n], d_all[:n]
+            tm = np.full(n, FLT_MAX, np.float32)
+            q_hit, q_t, q_u, q_v = (x.cpu().numpy() for x in gpu.query_closest(_dev(o), _dev(d), _dev(tm), flags=flags))
+            h_hit, h_t, h_u, h_v = gpu.trace_closest(o, d, tm, flags=flags)
+            assert np.array_equal(h_hit, q_hit), (flags, n)
+            h = q_hit >= 0
+            for what, got, ref in (("t", h_t, q_t), ("u", h_u, q_u), ("v", h_v, q_v)):
+                assert np.array_equal(_bits(got[h]), _bits(ref[h])), f"flags {flags}, {n} rays: {what} differs on a hit"
+                assert not _bits(got[~h]).any(), f"flags {flags}, {n} rays: the hook's {what} is not zero on a miss"
+            o2, d2, tm2, excl = o2_all[:n], d2_all[:n], tm_all[:n], excl_all[:n]
+            q_occ = gpu.query_any(_dev(o2), _dev(d2), _dev(tm2), _dev(excl), flags=flags).cpu().numpy()
+            h_occ = gpu.trace_any(o2, d2, tm2, excl, flags=flags)
+            assert np.array_equal(h_occ, q_occ), (flags, n)
+            if n >= 63:
+                assert h.any() and not h.all(), (flags, n)
+                assert q_occ.any() and not q_occ.all(), (flags, n)
+    gpu.close()
+
+
+@both_scenes
+def test_hook_exclusions_out_of_range_exclude_nothing(api, oracle, bunny_matte, name):
+    """Shadow-ray style rays, each starting ON the triangle it names, so that whether the exclusion is honoured decides the answer."""
+    arrays, cpu, (o, d), _ = _hook_case(oracle, bunny_matte, name)
+    gpu = api.Scene(arrays)
+    c = cpu.trace_closest(o, d, np.full(len(o), FLT_MAX, np.float32))
+    h = c[0] >= 0
+    o6, d6 = raygen.bounce_rays(o, d, c[1], h, seed=83, eps=0.0)
+    own = c[0][h].astype(np.int32)
+    n = len(o6)
+    tm = np.full(n, FLT_MAX, np.float32)
+    n_tris = len(arrays.tris)
+    free = gpu.query_any(_dev(o6), _dev(d6), _dev(tm), None).cpu().numpy()
+    for value in (-1, n_tris, np.iinfo(np.int32).min, np.iinfo(np.int32).max):
+        assert np.array_equal(gpu.trace_any(o6, d6, tm, np.full(n, value, np.int32)), free), value
+    in_range = gpu.query_any(_dev(o6), _dev(d6), _dev(tm), _dev(own)).cpu().numpy()
+    assert np.array_equal(gpu.trace_any(o6, d6, tm, own), in_range)
+    assert np.array_equal(in_range, cpu.trace_any(o6, d6, tm, own))
+    assert (in_range != free).any()  # (the exclusion matters on these rays)
+    mixed = own.copy()
+    mixed[1::4], mixed[2::4], mixed[3::4] = n_tris, np.iinfo(np.int32).min, np.iinfo(np.int32).max
+    assert np.array_equal(gpu.trace_any(o6, d6, tm, mixed), np.where(np.arange(n) % 4 == 0, in_range, free))
+    gpu.close()
+
+
+def test_hooks_leave_the_last_querys_counters(api, oracle, bunny_matte):
+    """rt_query_last_counters speaks of the last QUERY: the known-miss ray leaves a re-trace there, a hook call on other rays
+    (which re-traces nothing) does not take it away."""
+    _, _, (o, d), (o2, d2, tm, excl) = _hook_case(oracle, bunny_matte, "bunny")
+    gpu = api.Scene(bunny_matte)
+    gpu.query_closest(_dev(KNOWN_MISS_O), _dev(KNOWN_MISS_D))
+    before = gpu.query_counters()
+    assert before["retraced"] == 1 and before["lost"] >= 1
+    gpu.trace_closest(o, d, np.full(len(o), FLT_MAX, np.float32))
+    assert gpu.query_counters() == before
+    gpu.trace_any(o2, d2, tm, excl)
+    assert gpu.query_counters() == before
+    gpu.close()
+
+
+@both_scenes
+def test_hook_query_hook_share_the_scenes_scratch(api, oracle, bunny_matte, name):
+    """The inverse leaf order, the overflow stacks and the scratch words are the scene's, made by whichever call comes first:
+    a hook, a device query, a hook again on a fresh scene, each the oracle's."""
+    arrays, cpu, (o, d), (o2, d2, tm, excl) = _hook_case(oracle, bunny_matte, name)
+    gpu = api.Scene(arrays)
+    want_occ = cpu.trace_any(o2, d2, tm, excl)
+    assert np.array_equal(gpu.trace_any(o2, d2, tm, excl), want_occ)
+    _check_any(gpu, cpu, o2, d2, tm, excl)
+    full = np.full(len(o), FLT_MAX, np.float32)
+    want = cpu.trace_closest(o, d, full)
+    hit, t, u, v = gpu.trace_closest(o, d, full)
+    assert np.array_equal(hit, want[0])
+    h = want[0] >= 0
+    for got, ref in ((t, want[1]), (u, want[2]), (v, want[3])):
+        assert np.array_equal(_bits(got[h]), _bits(ref[h]))
+    assert np.array_equal(gpu.trace_any(o2, d2, tm, excl), want_occ)
+    gpu.close()
+
+
+def test_hook_through_the_overflow_stack(api, oracle, bunny_matte, monkeypatch):
+    """RT_STACK_CAP=2 sends every traversal of the bunny's tree through the overflow columns of the scene's query state."""
+    _, _, (o, d), (o2, d2, tm, excl) = _hook_case(oracle, bunny_matte, "bunny")
+    full = np.full(len(o), FLT_MAX, np.float32)
+    gpu = api.Scene(bunny_matte)
+    plain = gpu.trace_closest(o, d, full), gpu.trace_any(o2, d2, tm, excl)
+    gpu.close()
+    monkeypatch.setenv("RT_STACK_CAP", "2")
+    small = api.Scene(bunny_matte)
+    got = small.trace_closest(o, d, full), small.trace_any(o2, d2, tm, excl)
+    small.close()
+    assert np.array_equal(got[0][0], plain[0][0])
+    for a, b in zip(got[0][1:], plain[0][1:]):
+        assert np.array_equal(_bits(a), _bits(b))
+    assert np.array_equal(got[1], plain[1])

@@ -3,12 +3,15 @@
 
     hipcc --offload-arch=gfx950 <the Makefile's FLAGS> --cuda-device-only -S -o A.s rtcuda_amd.hip     (one commit)
     hipcc ... -o B.s rtcuda_amd.hip                                                                    (another)
-    python tools/device_code_diff.py A.s B.s
+    python tools/device_code_diff.py A.s B.s [--rename OLD=NEW ...]
 
 Both assembly files are split per function (from the function's label to its .Lfunc_end), comments and directives are
 dropped, and local labels (.LBB..., .Ltmp...) are renumbered in order of appearance, so that what is left of a function is
 its instructions and its branch structure.  Prints how many functions and lines were compared and every function that
 differs, is missing from B or is new in B; exits 1 if any function differs or is missing (new ones alone are no failure).
+--rename OLD=NEW (any number, applied in order): in the NAMES of A's functions every substring OLD becomes NEW before the two
+files are matched, so that a kernel whose template parameters changed -- and with them its mangled name -- is compared body
+against body with its successor.  The bodies are not touched.
 It compares text: what the lines say is none of its business."""
 import re
 import sys
@@ -51,11 +54,28 @@ def renumber(body):
     return [LOCAL.sub(sub, l) for l in body]
 
 
+def renamed(funcs, pairs):
+    out = {}
+    for name, body in funcs.items():
+        for old, new in pairs:
+            name = name.replace(old, new)
+        if name in out:
+            raise SystemExit(f"--rename maps two functions onto {name}")
+        out[name] = body
+    return out
+
+
 def main(argv):
+    pairs = []
+    while "--rename" in argv:
+        k = argv.index("--rename")
+        stop = next((i for i in range(k + 1, len(argv)) if "=" not in argv[i]), len(argv))
+        pairs += [tuple(x.split("=", 1)) for x in argv[k + 1:stop]]
+        argv = argv[:k] + argv[stop:]
     if len(argv) != 3:
         print(__doc__)
         return 2
-    a, b = functions(argv[1]), functions(argv[2])
+    a, b = renamed(functions(argv[1]), pairs), functions(argv[2])
     differ = [n for n in a if n in b and a[n] != b[n]]
     missing = [n for n in a if n not in b]
     new = [n for n in b if n not in a]

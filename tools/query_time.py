@@ -12,6 +12,10 @@ shadow-style rays (any hit: bounce rays, tmax uniform in (0.05, 1.2), nothing ex
                dispatches, on the same rays: each from a rocprofv3 --kernel-trace run of its own (no counters), 7 repetitions
                after a warm-up; `kernel_spread_parent_ms` = max - min of the parent's 7, the margin k_query is held to
 
+The hooks have since become the host-pointer form of the queries (upload, k_query, download) and k_trace walks pools only:
+hook_ms, and the `k_trace<` dispatches kernel_parent_ms is made from, mean what is said above only with --parent-lib of a commit
+up to 78db776, where the hooks still ran k_trace's dense-array modes.  A later library's hook launches k_query and no k_trace.
+
   python tools/query_time.py --parent-lib <parent build>/librtcuda_amd.so --trace-dir <dir> --out profiles/query_time.json
 """
 import argparse

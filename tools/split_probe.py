@@ -4,7 +4,9 @@
 Runs rt_split_probe (include/rtcuda_amd_tools.h) on BASELINE configs[1]'s frame (C2: bun_zipper.ply, full BSDF set,
 1920x1080x256): >= 64 M real rays of the frame's first generations are dumped from the round pipeline into dense
 device arrays, then
-  A  the trace kernel alone on them (device-resident, no PCIe), at 8 / 6 / 5 / 4 waves per SIMD -> Grays/s
+  A  the trace kernel alone on them (device-resident, no PCIe), at 8 / 6 / 5 / 4 waves per SIMD -> Grays/s.  The kernel is
+     the walker the project ships for dense ray arrays (k_query's: stream_walk under QueryEnds, watertight build), compiled at
+     each budget; up to commit 78db776 it was k_trace's dense-array modes, and profiles/r03_split_probe.json is of that kernel
   B  the shading code alone on the dumped shading records, 64 of 64 lanes shading, one material kind per launch
      -> Gshades/s; and gen() alone (round 0 of the pipeline: every slot generates)
   C  the frame's event totals (rays, shades, camera rays: the committed full-size parity record) divided by A and B:
