@@ -17,6 +17,7 @@
 //     the decisions, as the kernel makes them.
 //   * hc_denoise / hc_expnegf  the CPU twin of rt_denoise_fixed: a serial loop over rt_denoise.h, the arithmetic of the kernels.
 //   * hc_denoise_dual   the CPU twin of rt_denoise_dual_fixed, likewise; both walk the pixels with dn_walk, the twins' own loop.
+//   * hc_merge_shard_stats  the merge of the shards' rt_stats (rt_stats_merge.h), the library's own function.
 #include <cfloat>
 #include <cmath>
 #include <cstdint>
@@ -31,6 +32,7 @@
 #include "rt_ploc.h"
 #include "rt_ref_tree.h"
 #include "rt_slot_chunks.h"
+#include "rt_stats_merge.h"
 
 namespace {
 struct V3 { float x, y, z; };
@@ -1031,4 +1033,6 @@ int hc_denoise_dual(const int64_t *sum_a, int samples_a, const int64_t *sum_b, i
     }
     return 0;
 }
+// The stats of a frame from its n shards' (rt_stats_merge.h), as RT_SPLIT (sub_shards != 0) and rt_render_multi merge them
+void hc_merge_shard_stats(const rt_stats *sub, int n, int sub_shards, rt_stats *out) { *out = merge_shard_stats(sub, n, sub_shards != 0); }
 }

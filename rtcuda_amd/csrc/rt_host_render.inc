@@ -77,6 +77,27 @@ void *out_buffer(int device, int slot, size_t bytes) {
     return b.ptr;
 }
 
+// rt_shutdown: releases every device allocation the library holds behind the scenes -- the per-device render contexts (path
+// pools, RNG states, counters, overflow stacks, events) and the cached output buffers of rt_render / rt_render_multi.  Scenes are
+// the caller's (rt_scene_destroy).  No render may be in flight.  The library works again afterwards (everything is re-created
+// on demand).  (The reference frees nothing at all: render.cuh:374-391, bvh.cuh:211-217.)
+void shutdown_impl() {
+    int saved = 0;
+    const bool have = hipGetDevice(&saved) == hipSuccess;
+    {
+        std::lock_guard<std::mutex> lock(g_ctx_mutex);
+        g_contexts.clear();  // (~Context frees on the context's own device)
+    }
+    {
+        std::lock_guard<std::mutex> list_lock(g_out_mutex);
+        for (OutBuffer &b : g_out_buffers) {
+            if (hipSetDevice(b.device) == hipSuccess) (void)hipFree(b.ptr);
+        }
+        g_out_buffers.clear();
+    }
+    if (have) (void)hipSetDevice(saved);
+}
+
 template <typename T>
 int dev_alloc(Context &c, T *&ptr, size_t count) {
     void *raw = nullptr;
@@ -663,65 +684,6 @@ int render_shard_impl(const rt_scene *scene, const rt_camera *camera, int width,
     return f.frame_stats(stats);
 }
 
-// A shard may be rendered as `split` interleaved sub-shards on separate HIP streams (one host thread
-// each): slot sets are independent, so the sub-shards only meet in the framebuffer atomics, and the
-// tail of one sub-shard's persistent trace kernel overlaps the head of the other's.
-int render_overlapped(const rt_scene *scene, const rt_camera *camera, int width, int height, int spp,
-                      int max_bounces, uint64_t seed, int shard_index, int shard_count, uint32_t flags,
-                      float *d_sum, hipStream_t st, rt_stats *stats) {
-    int split = 1;
-    if (const char *e = knob("RT_SPLIT")) split = std::max(1, std::min(8, atoi(e)));
-    while (split > 1 && (shard_count <= 0 || kW % (shard_count * split) != 0 || kW / (shard_count * split) < 4096)) split >>= 1;
-    if (split <= 1)
-        return render_shard_impl(scene, camera, width, height, spp, max_bounces, seed, shard_index, shard_count, flags,
-                                 d_sum, st, stats);
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    HIP_TRY(hipStreamSynchronize(st));  // the caller zeroed d_sum on its stream
-    std::vector<rt_stats> sub(split);
-    std::vector<int> rc(split, 0);
-    std::vector<std::string> err(split);
-    std::vector<std::thread> th;
-    for (int k = 0; k < split; k++)
-        th.emplace_back([&, k] {
-            if (hipSetDevice(dev) != hipSuccess) { rc[k] = 1; err[k] = "hipSetDevice failed"; return; }
-            hipStream_t s2;
-            if (hipStreamCreateWithFlags(&s2, hipStreamNonBlocking) != hipSuccess) { rc[k] = 1; err[k] = "stream create failed"; return; }
-            rc[k] = render_shard_impl(scene, camera, width, height, spp, max_bounces, seed, shard_index * split + k,
-                                      shard_count * split, flags, d_sum, s2, &sub[k], k + 1);
-            if (rc[k]) err[k] = g_last_error;
-            (void)hipStreamSynchronize(s2);
-            (void)hipStreamDestroy(s2);
-        });
-    for (auto &t : th) t.join();
-    for (int k = 0; k < split; k++)
-        if (rc[k]) return fail(err[k]);
-    if (stats) {
-        rt_stats tot = sub[0];
-        for (int k = 1; k < split; k++) {
-            tot.camera_rays += sub[k].camera_rays;
-            tot.shade_events += sub[k].shade_events;
-            tot.closest_rays += sub[k].closest_rays;
-            tot.any_rays += sub[k].any_rays;
-            tot.emission_adds += sub[k].emission_adds;
-            tot.shadow_adds += sub[k].shadow_adds;
-            tot.rr_draws += sub[k].rr_draws;
-            tot.iterations += sub[k].iterations;
-            tot.launches_trace += sub[k].launches_trace;
-            tot.seconds_trace += sub[k].seconds_trace;
-            tot.seconds_advance += sub[k].seconds_advance;
-            tot.seconds_render = std::max(tot.seconds_render, sub[k].seconds_render);
-            tot.seconds_rng_init = std::max(tot.seconds_rng_init, sub[k].seconds_rng_init);
-            tot.seconds_reference_tree = std::max(tot.seconds_reference_tree, sub[k].seconds_reference_tree);
-            tot.reserved[0] += sub[k].reserved[0];
-            tot.reserved[2] = std::max(tot.reserved[2], sub[k].reserved[2]);
-            for (int q = 4; q < 7; q++) tot.reserved[q] += sub[k].reserved[q];
-        }
-        *stats = tot;
-    }
-    return 0;
-}
-
 // A persistent query-style grid: what the device holds at once (never more lanes than the overflow stacks' columns) or n needs.
 template <class KERNEL>
 static int resident_grid(KERNEL kernel, size_t lds_bytes, int cus, int n, int *grid) {
@@ -845,6 +807,21 @@ static int trace_hook(const rt_scene *scene, uint32_t flags, int n, const float 
         HIP_TRY(hipMemcpy(v, qp.out_v, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
     }
     return 0;
+}
+// rt_trace_closest[_flags] and rt_trace_any[_flags]: the pointer checks, then the hook
+static int trace_closest_impl(const rt_scene *scene, uint32_t flags, int n, const float *origin_xyz, const float *dir_xyz, const float *tmax,
+                              int32_t *hit_tri, float *t, float *u, float *v) {
+    if (!scene || n < 0 || (n > 0 && (!origin_xyz || !dir_xyz || !tmax || !hit_tri || !t || !u || !v)))
+        return fail("rt_trace_closest: bad argument");
+    if (n == 0) return 0;
+    return trace_hook<Q_CLOSEST>(scene, flags, n, origin_xyz, dir_xyz, tmax, nullptr, hit_tri, t, u, v);
+}
+static int trace_any_impl(const rt_scene *scene, uint32_t flags, int n, const float *origin_xyz, const float *dir_xyz, const float *tmax,
+                          const int32_t *excluded_tri, int32_t *occluded) {
+    if (!scene || n < 0 || (n > 0 && (!origin_xyz || !dir_xyz || !tmax || !excluded_tri || !occluded)))
+        return fail("rt_trace_any: bad argument");
+    if (n == 0) return 0;
+    return trace_hook<Q_ANY>(scene, flags, n, origin_xyz, dir_xyz, tmax, excluded_tri, occluded, nullptr, nullptr, nullptr);
 }
 
 // rt_render_rays_device / rt_render_rays_fixed_device: host-side argument checks, the table's validation on the device

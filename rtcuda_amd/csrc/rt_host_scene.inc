@@ -498,6 +498,11 @@ struct DeviceGuard {
         current = device;
         return 0;
     }
+    int select(int device) {  // (after enter: a call that works on several devices in turn, rt_render_multi)
+        HIP_TRY(hipSetDevice(device));
+        current = device;
+        return 0;
+    }
     ~DeviceGuard() {
         if (current != saved) (void)hipSetDevice(saved);
     }
@@ -1080,6 +1085,29 @@ int scene_create_impl(const float *tri_p0p1p2, int n_tris, const int32_t *tri_ma
     HIP_TRY(hipDeviceSynchronize());
     *out_scene = sc.release();
     return 0;
+}
+
+// rt_render_multi: the scene as it exists on `device` -- the scene itself, or a replica created there from the host copies
+// (once per device, under the scene's replica_mutex).  Null, with the error set, if that fails.
+const rt_scene *scene_on_device(const rt_scene *scene, int device) {
+    if (scene->device == device) return scene;
+    std::lock_guard<std::mutex> lock(scene->replica_mutex);
+    for (const rt_scene *r : scene->replicas)
+        if (r->device == device) return r;
+    DeviceGuard dev;
+    if (dev.enter(device)) {
+        fail("rt_render_multi: cannot select device " + std::to_string(device));
+        return nullptr;
+    }
+    rt_scene *rep = nullptr;
+    // (a scene whose tree was built on the device gets one built on the replica's device)
+    const int rc = scene_create_impl(scene->h_tri9.data(), scene->n_tris, scene->h_tri_material.data(),
+                                     scene->h_tri_light.empty() ? nullptr : scene->h_tri_light.data(), scene->h_materials.data(),
+                                     scene->n_mats, scene->h_lights.data(), scene->n_lights,
+                                     scene->builder == 2 ? (uint32_t)RT_SCENE_DEVICE_BVH : 0u, &rep);
+    if (rc != 0) return nullptr;
+    scene->replicas.push_back(rep);
+    return rep;
 }
 
 // rt_scene_rebuild / rt_scene_rebuild_device: a new tree for the scene's current or new vertices (build_ploc_device), and

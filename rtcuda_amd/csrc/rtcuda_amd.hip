@@ -8,11 +8,15 @@
 //   rt_build_kernels.inc   device BVH: the leaf-order arrays, the refit (k_refit_*), the build (k_ploc_*)
 //   rt_host_scene.inc      rt_scene and the one way a tree gets into it: build (host SAH, device PLOC), emit, adopt; the entry
 //                          points on top of it (create, update, rebuild, the edits); what the ray entry points share
-//   rt_host_render.inc     Context, kernel selection, frames, queries and their host-pointer form (the trace hooks), ray tables, AOVs
+//   rt_host_render.inc     Context and the cached output buffers (and their release, rt_shutdown), kernel selection, one shard of a
+//                          frame (render_shard_impl), queries and their host-pointer form (the trace hooks), ray tables, AOVs
+//   rt_host_frame.inc      whole frames: shards side by side on host threads (run_shard_jobs: RT_SPLIT, rt_render_multi), their
+//                          stats merged (rt_stats_merge.h), the post-process, finish_frame, rt_render and rt_render_multi
 //   rt_denoise_kernels.inc the denoisers' kernels: one tap loop (dn_filter_pixel) and two pass bodies (dn_pass_direct, dn_pass_lds) under
 //                          k_atrous* / k_atrous_var*; prepare, finish, k_dn_var_blur (arithmetic: rt_denoise.h, shared with the CPU twin)
 //   rt_host_denoise.inc    rt_denoise_fixed and rt_denoise_dual_fixed: one set of checks (dn_check), one pass launcher, one run (dn_run)
-// The C-ABI below them only checks arguments and forwards.
+// The C-ABI below them only checks arguments and forwards, and calls none of its own entry points.  Two bodies stay in it:
+// rt_camera_make (host arithmetic, nothing shared) and rt_xorwow_states (a test hook around k_rng_init / k_test_draw).
 //
 // The hot path of lashhw/rtcuda (render.cuh:61-457) re-designed for CDNA4:
 //
@@ -82,6 +86,7 @@
 #include "rt_ploc.h"
 #include "rt_ref_tree.h"
 #include "rt_slot_chunks.h"
+#include "rt_stats_merge.h"
 
 using namespace rt;
 
@@ -879,7 +884,8 @@ __global__ void k_test_draw(DPools p, int n, int draws, uint32_t *__restrict__ s
 #include "rt_denoise_kernels.inc"  // dn_filter_pixel under k_atrous* and k_atrous_var*; k_dn_prepare*, k_dn_var_blur, k_dn_finish*
 
 #include "rt_host_scene.inc"   // (opens the anonymous namespace that is closed below) rt_scene: reference tree, checks, build / emit / adopt, create, update, rebuild, edits; what the ray entry points share
-#include "rt_host_render.inc"  // Context, kernel selection, frames, queries and trace hooks, ray tables, AOVs
+#include "rt_host_render.inc"  // Context, cached output buffers, kernel selection, one shard of a frame, queries and trace hooks, ray tables, AOVs
+#include "rt_host_frame.inc"   // whole frames: the shard fan-out (RT_SPLIT, rt_render_multi), finish_frame, rt_render, rt_render_multi
 #include "rt_host_denoise.inc"  // rt_denoise_fixed, rt_denoise_dual_fixed
 }  // namespace
 
@@ -897,7 +903,7 @@ const char *rt_build_id(void) { return RT_BUILD_ID; }
 int rt_scene_create(const float *tri_p0p1p2, int n_tris, const int32_t *tri_material, const int32_t *tri_light,
                     const rt_material *materials, int n_materials, const rt_light *lights, int n_lights,
                     rt_scene **out_scene) {
-    return rt_scene_create_flags(tri_p0p1p2, n_tris, tri_material, tri_light, materials, n_materials, lights, n_lights, 0u, out_scene);
+    return scene_create_impl(tri_p0p1p2, n_tris, tri_material, tri_light, materials, n_materials, lights, n_lights, 0u, out_scene);
 }
 
 int rt_scene_create_flags(const float *tri_p0p1p2, int n_tris, const int32_t *tri_material, const int32_t *tri_light,
@@ -1061,12 +1067,7 @@ int rt_render_rays_fixed_device(const rt_scene *scene, int64_t n_rays, const flo
 int rt_post_process_fixed(const int64_t *d_sum_fixed, float *d_rgb_out, int num_pixels, int num_samples, void *stream) {
     if (!d_sum_fixed || !d_rgb_out || num_pixels <= 0 || num_samples <= 0) return fail("rt_post_process_fixed: bad argument");
     if (num_pixels > 0x7fffffff / 3) return fail("rt_post_process_fixed: more than 715827882 pixels");
-    int nv = num_pixels * 3;
-    float inv = 1.f / (float)num_samples;
-    hipLaunchKernelGGL(k_post_process_fixed, dim3((nv + 255) / 256), dim3(256), 0, (hipStream_t)stream,
-                       (const long long *)d_sum_fixed, d_rgb_out, nv, inv);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return post_process_impl((const long long *)d_sum_fixed, d_rgb_out, num_pixels, num_samples, (hipStream_t)stream);
 }
 
 int rt_render_aov_fixed(const rt_scene *scene, const rt_camera *camera, int width, int height, int num_samples, uint64_t seed,
@@ -1127,265 +1128,40 @@ int rt_denoise_dual_fixed(const int64_t *d_sum_a, int samples_a, const int64_t *
 int rt_post_process(float *d_rgb, int num_pixels, int num_samples, void *stream) {
     if (!d_rgb || num_pixels <= 0 || num_samples <= 0) return fail("rt_post_process: bad argument");
     if (num_pixels > 0x7fffffff / 3) return fail("rt_post_process: more than 715827882 pixels");
-    int nv = num_pixels * 3;
-    float inv = 1.f / (float)num_samples;
-    hipLaunchKernelGGL(k_post_process, dim3((nv + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_rgb, nv, inv);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return post_process_impl(nullptr, d_rgb, num_pixels, num_samples, (hipStream_t)stream);
 }
 
 int rt_render(const rt_scene *scene, const rt_camera *camera, int width, int height, int num_samples,
               int max_bounces, uint64_t seed, uint32_t flags, float *out_rgb, rt_stats *stats) {
-    if (!out_rgb) return fail("rt_render: out_rgb is null");
-    if (width <= 0 || height <= 0) return fail("rt_render: bad dimensions");
-    if ((long long)width * height > (long long)(0x7fffffff / 3)) return fail("rt_render: width*height exceeds 715827882 pixels");
-    const bool fixed = (flags & RT_FLAG_DETERMINISTIC) != 0;
-    const size_t n_values = 3 * (size_t)width * height;
-    const size_t bytes = sizeof(float) * n_values;
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    if (dev < 0 || dev >= kMaxDevices) return fail("rt_render: device ordinal out of range");
-    std::lock_guard<std::mutex> out_lock(g_dev_busy[dev]);  // (this device's cached buffers serve one host-output call at a time)
-    float *d_fb = (float *)out_buffer(dev, 0, bytes);
-    long long *d_fixed = fixed ? (long long *)out_buffer(dev, 1, sizeof(long long) * n_values) : nullptr;
-    if (!d_fb || (fixed && !d_fixed)) return fail("rt_render: out of device memory");
-    int rc = 0;
-    if (fixed) {
-        HIP_TRY(hipMemsetAsync(d_fixed, 0, sizeof(long long) * n_values, nullptr));
-        rc = render_overlapped(scene, camera, width, height, num_samples, max_bounces, seed, 0, 1,
-                               (flags & ~kFlagFixedFb) | kFlagFixedFb, (float *)d_fixed, nullptr, stats);
-        if (rc) return rc;
-        rc = rt_post_process_fixed((const int64_t *)d_fixed, d_fb, width * height, num_samples, nullptr);
-    } else {
-        HIP_TRY(hipMemsetAsync(d_fb, 0, bytes, nullptr));
-        rc = render_overlapped(scene, camera, width, height, num_samples, max_bounces, seed, 0, 1, flags & ~kFlagFixedFb,
-                               d_fb, nullptr, stats);
-        if (rc) return rc;
-        rc = rt_post_process(d_fb, width * height, num_samples, nullptr);
-    }
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(out_rgb, d_fb, bytes, hipMemcpyDeviceToHost));
-    return 0;
+    return render_impl(scene, camera, width, height, num_samples, max_bounces, seed, flags, out_rgb, stats);
 }
 
-// Releases every device allocation the library holds behind the scenes -- the per-device render contexts (path pools, RNG
-// states, counters, overflow stacks, events) and the cached output buffers of rt_render / rt_render_multi.  Scenes are the
-// caller's (rt_scene_destroy).  No render may be in flight.  The library works again afterwards (everything is re-created on
-// demand).  (The reference frees nothing at all: render.cuh:374-391, bvh.cuh:211-217.)
-void rt_shutdown(void) {
-    int saved = 0;
-    const bool have = hipGetDevice(&saved) == hipSuccess;
-    {
-        std::lock_guard<std::mutex> lock(g_ctx_mutex);
-        g_contexts.clear();  // (~Context frees on the context's own device)
-    }
-    {
-        std::lock_guard<std::mutex> list_lock(g_out_mutex);
-        for (OutBuffer &b : g_out_buffers) {
-            if (hipSetDevice(b.device) == hipSuccess) (void)hipFree(b.ptr);
-        }
-        g_out_buffers.clear();
-    }
-    if (have) (void)hipSetDevice(saved);
-}
-
-// The scene as it exists on `device`: the scene itself, or a replica created there from the host copies (once per device).
-static const rt_scene *scene_on_device(const rt_scene *scene, int device) {
-    if (scene->device == device) return scene;
-    std::lock_guard<std::mutex> lock(scene->replica_mutex);
-    for (const rt_scene *r : scene->replicas)
-        if (r->device == device) return r;
-    DeviceGuard dev;
-    if (dev.enter(device)) {
-        fail("rt_render_multi: cannot select device " + std::to_string(device));
-        return nullptr;
-    }
-    rt_scene *rep = nullptr;
-    // (a scene whose tree was built on the device gets one built on the replica's device)
-    const int rc = rt_scene_create_flags(scene->h_tri9.data(), scene->n_tris, scene->h_tri_material.data(),
-                                         scene->h_tri_light.empty() ? nullptr : scene->h_tri_light.data(), scene->h_materials.data(),
-                                         scene->n_mats, scene->h_lights.data(), scene->n_lights,
-                                         scene->builder == 2 ? (uint32_t)RT_SCENE_DEVICE_BVH : 0u, &rep);
-    if (rc != 0) return nullptr;
-    scene->replicas.push_back(rep);
-    return rep;
-}
+void rt_shutdown(void) { shutdown_impl(); }
 
 int rt_render_multi(const rt_scene *scene, const rt_camera *camera, int width, int height, int num_samples,
                     int max_bounces, uint64_t seed, uint32_t flags, const int *devices, int n_devices, float *out_rgb,
                     rt_stats *stats) {
-    if (!scene || !camera || !out_rgb) return fail("rt_render_multi: null argument");
-    if (!devices || n_devices < 1) return fail("rt_render_multi: empty device list");
-    if (width <= 0 || height <= 0) return fail("rt_render_multi: bad dimensions");
-    if ((long long)width * height > (long long)(0x7fffffff / 3)) return fail("rt_render_multi: width*height exceeds 715827882 pixels");
-    if (kW % n_devices != 0) return fail("rt_render_multi: the number of devices must divide 1048576 (1, 2, 4, 8, ...)");
-    int n_visible = 0;
-    HIP_TRY(hipGetDeviceCount(&n_visible));
-    for (int k = 0; k < n_devices; k++)
-        if (devices[k] < 0 || devices[k] >= n_visible)
-            return fail("rt_render_multi: devices[" + std::to_string(k) + "] = " + std::to_string(devices[k]) + " but " +
-                        std::to_string(n_visible) + " device(s) are visible");
-    const bool fixed = (flags & RT_FLAG_DETERMINISTIC) != 0;
-    const uint32_t shard_flags = (flags & ~kFlagFixedFb) | (fixed ? kFlagFixedFb : 0u);
-    const size_t n_values = 3 * (size_t)width * height;
-    const size_t sum_bytes = n_values * (fixed ? sizeof(long long) : sizeof(float));
-    int caller_device = 0;
-    HIP_TRY(hipGetDevice(&caller_device));
-    // every device's copy of the scene, before any thread starts (replicas are created under the scene's lock)
-    std::vector<const rt_scene *> on_dev(n_devices, nullptr);
-    for (int k = 0; k < n_devices; k++) {
-        on_dev[k] = scene_on_device(scene, devices[k]);
-        if (!on_dev[k]) return 1;
-    }
-    // device buffers: cached per (device, slot) like rt_render's; slot 2 + 2k = shard k's sums on its device, 3 + 2k = its
-    // staging copy on devices[0], slot 1 = the post-processed image (fixed-point mode)
-    std::vector<int> distinct(devices, devices + n_devices);
-    std::sort(distinct.begin(), distinct.end());
-    distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
-    if (distinct.back() >= kMaxDevices) return fail("rt_render_multi: device ordinal out of range");
-    std::vector<std::unique_lock<std::mutex>> out_locks;  // (ascending device order: two concurrent calls cannot deadlock)
-    for (int d : distinct) out_locks.emplace_back(g_dev_busy[d]);
-    struct Home {  // the calling thread's device is restored on every return path
-        int device;
-        ~Home() { (void)hipSetDevice(device); }
-    } home{caller_device};
-    struct {
-        void *alloc(int device, int slot, size_t bytes) { return hipSetDevice(device) == hipSuccess ? out_buffer(device, slot, bytes) : nullptr; }
-    } buf;
-    const int dev0 = devices[0];
-    // Peer access between devices[0] and every other listed device, once per pair and process: with it the shards' sums travel
-    // over xGMI straight into devices[0]'s memory; without it hipMemcpyPeerAsync still works, staged through host memory by
-    // the runtime.  (Nothing of this has run on two PHYSICAL devices yet -- one-GPU boxes list a device twice; the first
-    // multi-GPU run is the driver's scaling run, where bench.py's probe records what happened here: `peer_access`.)
-    {
-        static std::mutex peer_mutex;
-        static std::vector<std::pair<int, int>> peer_done;
-        std::lock_guard<std::mutex> peer_lock(peer_mutex);
-        for (int k = 1; k < n_devices; k++) {
-            const int dk = devices[k];
-            if (dk == dev0 || std::find(peer_done.begin(), peer_done.end(), std::make_pair(dev0, dk)) != peer_done.end()) continue;
-            peer_done.push_back({dev0, dk});
-            int can01 = 0, can10 = 0;
-            std::string why;
-            if (hipDeviceCanAccessPeer(&can01, dev0, dk) != hipSuccess || hipDeviceCanAccessPeer(&can10, dk, dev0) != hipSuccess) why = "hipDeviceCanAccessPeer failed";
-            else if (!can01 || !can10) why = "the devices report no peer access";
-            else {
-                hipError_t e1 = hipSetDevice(dev0) == hipSuccess ? hipDeviceEnablePeerAccess(dk, 0) : hipErrorInvalidDevice;
-                hipError_t e2 = hipSetDevice(dk) == hipSuccess ? hipDeviceEnablePeerAccess(dev0, 0) : hipErrorInvalidDevice;
-                if (e1 == hipErrorPeerAccessAlreadyEnabled) e1 = hipSuccess;  // (PyTorch, or an earlier library in the process, got there first)
-                if (e2 == hipErrorPeerAccessAlreadyEnabled) e2 = hipSuccess;
-                (void)hipGetLastError();
-                if (e1 != hipSuccess || e2 != hipSuccess) why = std::string("hipDeviceEnablePeerAccess: ") + hipGetErrorString(e1 != hipSuccess ? e1 : e2);
-            }
-            g_peer_log += "devices " + std::to_string(dev0) + " <-> " + std::to_string(dk) + ": " + (why.empty() ? "peer access enabled" : "NO peer access (" + why + "): copies go through host memory") + "; ";
-            if (!why.empty())
-                fprintf(stderr, "rtcuda_amd: rt_render_multi: no peer access between devices %d and %d (%s): the shard's sums are copied through host memory\n", dev0, dk, why.c_str());
-        }
-        (void)hipSetDevice(caller_device);
-    }
-    // shard k renders into its own raw-sum buffer on ITS device; shards 1.. land in a staging buffer on devices[0]
-    std::vector<void *> d_sum(n_devices, nullptr), d_stage(n_devices, nullptr);
-    for (int k = 0; k < n_devices; k++) {
-        d_sum[k] = buf.alloc(devices[k], 2 + 2 * k, sum_bytes);
-        if (!d_sum[k]) return fail("rt_render_multi: out of device memory on device " + std::to_string(devices[k]));
-        if (k > 0) {
-            d_stage[k] = devices[k] == dev0 ? d_sum[k] : buf.alloc(dev0, 3 + 2 * k, sum_bytes);  // (same device: the buffer is its own staging)
-            if (!d_stage[k]) return fail("rt_render_multi: out of device memory on device " + std::to_string(dev0));
-        }
-    }
-    float *d_out = fixed ? (float *)buf.alloc(dev0, 1, n_values * sizeof(float)) : (float *)d_sum[0];
-    if (!d_out) return fail("rt_render_multi: out of device memory");
-    // ---- one host thread per device (render.cuh's render() is one thread on one device: this is the multi-device form of
-    // the same call): select the device, zero the shard's sums, render slot shard k of n, hand the sums to devices[0]
-    std::vector<rt_stats> sub(n_devices);
-    std::vector<int> rc(n_devices, 0);
-    std::vector<std::string> err(n_devices);
-    std::vector<std::thread> th;
-    for (int k = 0; k < n_devices; k++)
-        th.emplace_back([&, k] {
-            auto bail = [&](const char *what) { rc[k] = 1; err[k] = std::string("rt_render_multi: ") + what + " (device " + std::to_string(devices[k]) + ")"; };
-            if (hipSetDevice(devices[k]) != hipSuccess) return bail("hipSetDevice failed");
-            hipStream_t st;
-            if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) return bail("stream create failed");
-            if (hipMemsetAsync(d_sum[k], 0, sum_bytes, st) != hipSuccess) {
-                bail("memset failed");
-            } else {
-                rc[k] = render_shard_impl(on_dev[k], camera, width, height, num_samples, max_bounces, seed, k, n_devices, shard_flags,
-                                          (float *)d_sum[k], st, &sub[k], /* a context of its own per shard: */ 8 + k);
-                if (rc[k]) err[k] = g_last_error;
-                else if (k > 0 && d_stage[k] != d_sum[k]) {
-                    const hipError_t pe = hipMemcpyPeerAsync(d_stage[k], dev0, d_sum[k], devices[k], sum_bytes, st);
-                    if (pe != hipSuccess) bail((std::string("peer copy of the shard's sums failed: ") + hipGetErrorString(pe)).c_str());
-                }
-            }
-            if (hipStreamSynchronize(st) != hipSuccess && rc[k] == 0) bail("stream synchronise failed");
-            (void)hipStreamDestroy(st);
-        });
-    for (auto &t : th) t.join();
-    for (int k = 0; k < n_devices; k++)
-        if (rc[k]) return fail(err[k]);
-    // ---- on devices[0]: add the shards' sums in shard order (a fixed order: the result does not depend on which device
-    // finished first), post-process (render.cuh:330-338), copy out
-    HIP_TRY(hipSetDevice(dev0));
-    const int nv = (int)n_values;
-    for (int k = 1; k < n_devices; k++) {
-        if (fixed) hipLaunchKernelGGL(k_accumulate_i64, dim3((nv + 255) / 256), dim3(256), 0, nullptr, (long long *)d_sum[0], (const long long *)d_stage[k], nv);
-        else hipLaunchKernelGGL(k_accumulate_f32, dim3((nv + 255) / 256), dim3(256), 0, nullptr, (float *)d_sum[0], (const float *)d_stage[k], nv);
-    }
-    HIP_TRY(hipGetLastError());
-    int prc = fixed ? rt_post_process_fixed((const int64_t *)d_sum[0], d_out, width * height, num_samples, nullptr)
-                    : rt_post_process(d_out, width * height, num_samples, nullptr);
-    if (prc) return prc;
-    HIP_TRY(hipMemcpy(out_rgb, d_out, n_values * sizeof(float), hipMemcpyDeviceToHost));
-    if (stats) {
-        rt_stats tot = sub[0];
-        for (int k = 1; k < n_devices; k++) {
-            tot.camera_rays += sub[k].camera_rays;
-            tot.shade_events += sub[k].shade_events;
-            tot.closest_rays += sub[k].closest_rays;
-            tot.any_rays += sub[k].any_rays;
-            tot.emission_adds += sub[k].emission_adds;
-            tot.shadow_adds += sub[k].shadow_adds;
-            tot.rr_draws += sub[k].rr_draws;
-            tot.iterations = std::max(tot.iterations, sub[k].iterations);
-            tot.launches_trace += sub[k].launches_trace;
-            tot.seconds_trace = std::max(tot.seconds_trace, sub[k].seconds_trace);
-            tot.seconds_advance = std::max(tot.seconds_advance, sub[k].seconds_advance);
-            tot.seconds_render = std::max(tot.seconds_render, sub[k].seconds_render);  // the devices render side by side
-            tot.seconds_rng_init = std::max(tot.seconds_rng_init, sub[k].seconds_rng_init);
-            tot.seconds_reference_tree = std::max(tot.seconds_reference_tree, sub[k].seconds_reference_tree);
-            for (int q = 4; q < 7; q++) tot.reserved[q] += sub[k].reserved[q];
-        }
-        tot.reserved[3] = n_devices;
-        *stats = tot;
-    }
-    return 0;
+    return render_multi_impl(scene, camera, width, height, num_samples, max_bounces, seed, flags, devices, n_devices, out_rgb, stats);
 }
 
 int rt_trace_closest(const rt_scene *scene, int n, const float *origin_xyz, const float *dir_xyz, const float *tmax,
                      int32_t *hit_tri, float *t, float *u, float *v) {
-    return rt_trace_closest_flags(scene, 0u, n, origin_xyz, dir_xyz, tmax, hit_tri, t, u, v);
+    return trace_closest_impl(scene, 0u, n, origin_xyz, dir_xyz, tmax, hit_tri, t, u, v);
 }
 
 int rt_trace_closest_flags(const rt_scene *scene, uint32_t flags, int n, const float *origin_xyz, const float *dir_xyz,
                            const float *tmax, int32_t *hit_tri, float *t, float *u, float *v) {
-    if (!scene || n < 0 || (n > 0 && (!origin_xyz || !dir_xyz || !tmax || !hit_tri || !t || !u || !v)))
-        return fail("rt_trace_closest: bad argument");
-    if (n == 0) return 0;
-    return trace_hook<Q_CLOSEST>(scene, flags, n, origin_xyz, dir_xyz, tmax, nullptr, hit_tri, t, u, v);
+    return trace_closest_impl(scene, flags, n, origin_xyz, dir_xyz, tmax, hit_tri, t, u, v);
 }
 
 int rt_trace_any(const rt_scene *scene, int n, const float *origin_xyz, const float *dir_xyz, const float *tmax,
                  const int32_t *excluded_tri, int32_t *occluded) {
-    return rt_trace_any_flags(scene, 0u, n, origin_xyz, dir_xyz, tmax, excluded_tri, occluded);
+    return trace_any_impl(scene, 0u, n, origin_xyz, dir_xyz, tmax, excluded_tri, occluded);
 }
 
 int rt_trace_any_flags(const rt_scene *scene, uint32_t flags, int n, const float *origin_xyz, const float *dir_xyz,
                        const float *tmax, const int32_t *excluded_tri, int32_t *occluded) {
-    if (!scene || n < 0 || (n > 0 && (!origin_xyz || !dir_xyz || !tmax || !excluded_tri || !occluded)))
-        return fail("rt_trace_any: bad argument");
-    if (n == 0) return 0;
-    return trace_hook<Q_ANY>(scene, flags, n, origin_xyz, dir_xyz, tmax, excluded_tri, occluded, nullptr, nullptr, nullptr);
+    return trace_any_impl(scene, flags, n, origin_xyz, dir_xyz, tmax, excluded_tri, occluded);
 }
 
 int rt_query_closest_device(const rt_scene *scene, uint32_t flags, int n, const float *d_origin_xyz, const float *d_dir_xyz,

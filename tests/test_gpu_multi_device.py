@@ -138,6 +138,92 @@ def test_shutdown_releases_the_hidden_allocations_and_the_library_keeps_working(
     api.shutdown()  # (idempotent)
 
 
+SUMMED = KEYS + ("launches_trace", "literal_retraces", "reference_lost_hits", "exact_ties")
+
+
+def test_merged_stats_are_the_shards_stats(api, gpu_full, monkeypatch):
+    """256 x 256 x 20 = 1.25 generations: the persistent kernel and the lockstep final generation both run.  The device shards
+    (0, 2) and (1, 2) of rt_render_multi [0, 0] are the sub-shards of RT_SPLIT=2 on shard (0, 1): both frames' stats are merged
+    from the same two shards' stats, by the two columns of rt_stats_merge.h."""
+    import torch
+    w, h, spp = 256, 256, 20
+    F = api.FLAG_DETERMINISTIC
+    cam = api.make_camera(aspect=w / h)
+    acc = torch.zeros(h * w * 3, dtype=torch.int64, device="cuda")
+    sub = [gpu_full.render_shard_fixed(cam, w, h, spp, r, 2, acc.data_ptr(), flags=F) for r in (0, 1)]
+    assert sum(s["camera_rays"] for s in sub) == w * h * spp
+    _, multi = gpu_full.render_multi(cam, w, h, spp, [0, 0], flags=F)
+    for k in SUMMED:
+        assert multi[k] == sub[0][k] + sub[1][k], k
+    assert multi["iterations"] == max(sub[0]["iterations"], sub[1]["iterations"])
+    assert multi["device_shards"] == 2
+    split_sum = torch.zeros_like(acc)
+    monkeypatch.setenv("RT_SPLIT", "2")
+    split = gpu_full.render_shard_fixed(cam, w, h, spp, 0, 1, split_sum.data_ptr(), flags=F)
+    monkeypatch.delenv("RT_SPLIT")
+    for k in SUMMED:
+        assert split[k] == sub[0][k] + sub[1][k], k
+    assert split["iterations"] == sub[0]["iterations"] + sub[1]["iterations"]
+    torch.cuda.synchronize()
+    assert torch.equal(split_sum, acc)
+
+
+def test_whole_frame_calls_refuse_bad_arguments_with_their_own_texts(api, gpu_full):
+    """rt_render and rt_render_multi through the raw handle: every refusal comes before any launch, says exactly this, and
+    leaves the library usable."""
+    import ctypes
+    import torch
+    L = api.lib()
+    cam = api.make_camera(aspect=1.0)
+    out = np.zeros((32, 32, 3), np.float32)
+    dev = np.array([0, 0, 0, 99], np.int32)
+    cp, op, dp = cam.ctypes.data, out.ctypes.data, dev.ctypes.data
+
+    def render(width=32, height=32, out_rgb=op):
+        return L.rt_render(gpu_full.h, cp, width, height, 4, 10, 1, 0, out_rgb, None)
+
+    def multi(scene=gpu_full.h, width=32, height=32, devices=dp, n=2, out_rgb=op):
+        return L.rt_render_multi(scene, cp, width, height, 4, 10, 1, 0, devices, n, out_rgb, None)
+    n_visible = torch.cuda.device_count()
+    for call, text in ((lambda: render(out_rgb=None), "rt_render: out_rgb is null"),
+                       (lambda: render(width=0), "rt_render: bad dimensions"),
+                       (lambda: multi(scene=None), "rt_render_multi: null argument"),
+                       (lambda: multi(out_rgb=None), "rt_render_multi: null argument"),
+                       (lambda: multi(devices=None), "rt_render_multi: empty device list"),
+                       (lambda: multi(n=0), "rt_render_multi: empty device list"),
+                       (lambda: multi(height=-1), "rt_render_multi: bad dimensions"),
+                       (lambda: multi(n=3), "rt_render_multi: the number of devices must divide 1048576 (1, 2, 4, 8, ...)"),
+                       (lambda: multi(devices=dp + 12, n=1), f"rt_render_multi: devices[0] = 99 but {n_visible} device(s) are visible")):
+        assert call() != 0
+        assert L.rt_last_error().decode() == text
+        out[:] = -1.0
+        assert (render() if text.startswith("rt_render:") else multi()) == 0
+        assert np.isfinite(out).all() and (out >= 0).all()
+
+
+def test_cached_buffers_serve_both_whole_frame_calls_in_turn(api, gpu_full):
+    """Slot 1 of the cached output buffers is rt_render's fixed-point sums and rt_render_multi's image; the calls alternate
+    at two sizes (the buffers grow, then serve the smaller frame again) and each still renders its own frame."""
+    import torch
+    F = api.FLAG_DETERMINISTIC
+    small, large = (32, 32, 4), (96, 54, 8)
+    cams = {small: api.make_camera(aspect=1.0), large: api.make_camera(aspect=96 / 54)}
+    device = torch.cuda.current_device()
+    images = []
+    for call, size in (("render", small), ("render_multi", large), ("render", large), ("render_multi", small), ("render", small)):
+        w, h, spp = size
+        if call == "render":
+            img, _ = gpu_full.render(cams[size], w, h, spp, flags=F)
+        else:
+            img, _ = gpu_full.render_multi(cams[size], w, h, spp, [0, 0], flags=F)
+        assert torch.cuda.current_device() == device
+        images.append(img.view(np.uint32))
+    first_small, multi_large, single_large, multi_small, last_small = images
+    assert np.array_equal(multi_large, single_large)
+    assert np.array_equal(multi_small, first_small)
+    assert np.array_equal(last_small, first_small)
+
+
 def test_peer_access_log_is_empty_until_two_different_devices_are_listed(api, gpu_full):
     """rt_render_multi enables peer access devices[0] <-> devices[k] once per pair and says what became of it
     (rt_peer_access_log).  A one-GPU box can only list device 0 several times: nothing to enable, an empty log -- the copy
