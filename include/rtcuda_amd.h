@@ -79,7 +79,8 @@ typedef struct rt_stats {
     int64_t reserved[7];     /* reserved[0] = launches actually sampled by the event timer;
                                 reserved[1] = nonzero when the frame ran as one persistent k_paths launch (then
                                 seconds_trace is that launch's duration and launches_trace is 1): 1 + the camera rays
-                                per task of the chunked deal of slots to lanes, so 1 = the static deal;
+                                per task of the chunked deal of slots to lanes in its low 32 bits, so 1 = the static deal,
+                                and in the high 32 bits the slot sets a lane ran statically before that deal began;
                                 reserved[2] = BVH node records that launch staged in LDS (small shards only);
                                 reserved[3] = rt_render_multi: number of device shards behind these totals;
                                 default kernels (no RT_FLAG_WATERTIGHT): reserved[4] = rays re-traced through the reference's

@@ -6,7 +6,12 @@
 //   RT_PATHS_CHUNKS            1: RT_K_PATHS is the build with the chunked deal (rt_slot_chunks.h), a kernel of its own name so
 //                              that the static deal keeps its code, instruction for instruction; only its 4-waves-per-SIMD
 //                              reference-mode instances are ever launched
+//   RT_CHUNK_RELEASE_WAIT      (experiment define) 0: the chunked deal's release leaves the wait for the state's stores to the
+//                              compiler's memory model, which has none at workgroup scope
 // No include guard: meant to be included more than once.
+#ifndef RT_CHUNK_RELEASE_WAIT
+#define RT_CHUNK_RELEASE_WAIT 1
+#endif
 
 // k_advance: one slot per thread, state in the pools.
 // Every per-slot input is indexed by the slot id, so all of a lane's loads are issued together
@@ -164,21 +169,30 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
     // the BVH is staged in LDS, so the first levels of every traversal do not leave the CU
     const float4 *s_top = (const float4 *)(s_tab + (LDS_TABLES ? ((sc.tab_dwords + 3) & ~3) : 0));  // (tables: what the scene needs)
     // The chunked deal (rt_slot_chunks.h) of the 4-waves-per-SIMD reference-mode builds: G > 0 camera rays per task, 0 = the
-    // static deal.  These builds keep no records of the tree in LDS, so G travels in `top_n`.
+    // static deal.  These builds keep no records of the tree in LDS, so G travels in `top_n`, and above G's bits the static
+    // head: the slot sets a lane runs as in the static deal before it draws its first task.
     constexpr bool CHUNKS = RT_PATHS_CHUNKS && SPLIT_GEN && !DRAW_CIDS;
-    // [0]: the workgroup's next task; [1]: G; [2 .. 4]: rtchunks::multiple_of(G).  The GEN block reads G and the three words
-    // from here: as scalars kept across the main loop they pushed other scalars out into VGPR lanes (53 more v_readlane in
-    // the default build, and the static deal 2.5 % slower than without this code).
+    // [0]: the workgroup's next task; [1]: G; [2 .. 4]: rtchunks::multiple_of(G); [5]: the static head.  The GEN block reads G,
+    // the three words and the head from here: as scalars kept across the main loop they pushed other scalars out into VGPR
+    // lanes (53 more v_readlane in the default build, and the static deal 2.5 % slower than without this code).
     __shared__ __attribute__((aligned(16))) unsigned s_task[CHUNKS ? 8 : 1];
-    if (CHUNKS && threadIdx.x == 0) {
-        const rtchunks::Multiple m = rtchunks::multiple_of(top_n > 0 ? (unsigned)top_n : 1u);
-        s_task[0] = 0u;
-        s_task[1] = top_n > 0 ? (unsigned)top_n : 0u;
-        s_task[2] = m.inv;
-        s_task[3] = m.shift;
-        s_task[4] = m.limit;
+    // the semaphores of the workgroup's dealt entries, two 16-bit fields to a word (rt_slot_chunks.h): all banked
+    __shared__ unsigned s_sem[CHUNKS ? rtchunks::kSemWords : 1];
+    const unsigned chunk_g0 = (CHUNKS && top_n > 0) ? (unsigned)top_n & ((1u << rtplan::kChunkHeadShift) - 1u) : 0u;
+    const unsigned chunk_head0 = (CHUNKS && top_n > 0) ? (unsigned)top_n >> rtplan::kChunkHeadShift : 0u;  // (both only used before the main loop)
+    if (CHUNKS) {
+        for (unsigned k = threadIdx.x; k < rtchunks::kSemWords; k += kBlock) s_sem[k] = rtchunks::kSemWordInit;
+        if (threadIdx.x == 0) {
+            const rtchunks::Multiple m = rtchunks::multiple_of(chunk_g0 ? chunk_g0 : 1u);
+            s_task[0] = 0u;
+            s_task[1] = chunk_g0;
+            s_task[2] = m.inv;
+            s_task[3] = m.shift;
+            s_task[4] = m.limit;
+            s_task[5] = chunk_head0;
+        }
     }
-    const bool chunk_start = CHUNKS && top_n > 0;  // (only used before the main loop)
+    const bool chunk_start = CHUNKS && chunk_g0 && chunk_head0 == 0u;  // no static head: the lane starts without a slot
     if (MIN_WAVES != 2) top_n = 0;
     for (int k = threadIdx.x; k < top_n * 4; k += kBlock) ((float4 *)s_top)[k] = sc.nodes[k];
     if (LDS_TABLES) {
@@ -332,6 +346,7 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
 #ifdef RT_TRACE_PROFILE
     unsigned long long pf[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long pf_gen_cycles = 0, pf_fin_cycles = 0, pf_fin_lanes = 0, pf_fin_iters = 0;
+    unsigned long long pf_handovers = 0, pf_handover_blocks = 0;  // releases at a chunk's end (lanes), and the GEN blocks that made one
     const unsigned long long pf_t0 = __builtin_readcyclecounter();
     // per lane: the start (cycles since pf_t0) of the last fin section it left with work in hand; from there to the wave's
     // exit the lane sits through whole-wave blocks that do nothing for it (the lane-idle tail)
@@ -429,31 +444,57 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
                 }
             }
             const unsigned chunk_g = CHUNKS ? __builtin_amdgcn_readfirstlane(s_task[1]) : 0u;
+            // The camera ray that ended: its sum goes to its pixel AFTER the hand-over (whose waits for the state's stores and
+            // loads would otherwise also sit through the float atomics' acknowledgements), so the pixel is read before the
+            // hand-over puts another slot's state into the lane's column.  A lane that comes without a slot has an empty sum.
+            const bool chunk_was_gen = CHUNKS && phase == PH_GEN;
+            const int chunk_acc_pixel = CHUNKS ? cold[1 * kBlock] : 0;
             if (CHUNKS && chunk_g) {
                 const rtchunks::Multiple chunk_m{s_task[2], s_task[3], s_task[4]};
-                // A lane without a slot takes one; a lane whose slot stands at a chunk's end banks it (or keeps it, if another
-                // lane has left a claim) -- rt_slot_chunks.h.  Behind a wave vote: once per G camera rays of a lane.
+                const unsigned chunk_head = __builtin_amdgcn_readfirstlane(s_task[5]);
+                // A lane past its static head: without a slot it takes one; with its slot at a chunk's end it banks it (or keeps
+                // it, if another lane has left a claim) -- rt_slot_chunks.h.  Behind a wave vote: once per G camera rays of a lane.
+                // (a lane inside its static head, slot_set < head, has a slot until the head is done and is at no chunk's end)
                 bool need = phase == PH_GEN && i >= ap_n;
-                const bool at_end = phase == PH_GEN && i < ap_n &&
+                const bool at_end = phase == PH_GEN && i < ap_n && slot_set >= (int)chunk_head &&
                                     rtchunks::chunk_ends((unsigned)cold[2 * kBlock], chunk_m, cold[0 * kBlock] == kChunkFresh);
                 if (wave_ballot(need || at_end)) {
+#ifdef RT_TRACE_PROFILE
+                    bool pf_released = false;
+#endif
                     if (at_end) {
                         cold_load();
                         // (a chain at its end is not banked: gen() below hands the slot back for good)
                         const bool ends = gen == ap.last_gen || (long long)gen * kW + (ap.slot_lo + i) >= ap.cam_end;
                         if (!ends) {
-                            acc_flush(acc, fb, ap_fb_fixed, pixel);  // the camera ray that ended: its sum -> its pixel
-                            bounces = ap_max_bounces;                // alive, starts with gen() (as k_pool_init leaves a slot)
+                            bounces = ap_max_bounces;  // alive, starts with gen() (as k_pool_init leaves a slot)
                             store_slot(i);
-                            const int old = __hip_atomic_fetch_add(&p.sem(i), 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-                            if (!rtchunks::runner_keeps(old)) {
+                            // the slot's entry among the workgroup's dealt ones
+                            const rtchunks::Owner own = rtchunks::owner_of((unsigned)i, (unsigned)lanes_in_grid, (unsigned)rot_wave, (unsigned)rot_set);
+                            const unsigned idx = (own.set - chunk_head) * rtchunks::kLanes + (own.lane_in_grid & (rtchunks::kLanes - 1u));
+#if RT_CHUNK_RELEASE_WAIT
+                            // vmcnt(0): the state's stores are acknowledged before the semaphore says so.  (At workgroup scope
+                            // the compiler's release does not wait for them: it relies on one CU's vector memory operations
+                            // reaching its L1 in the order they were issued.  The semaphore goes through the LDS, not that queue.)
+                            __builtin_amdgcn_s_waitcnt(0x0f70);
+#endif
+                            const unsigned old = __hip_atomic_fetch_add(&s_sem[rtchunks::sem_word(idx) & (rtchunks::kSemWords - 1u)], rtchunks::sem_unit(idx),
+                                                                        __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+                            if (!rtchunks::runner_keeps(rtchunks::sem_value(old, idx))) {
                                 i = ap_n;
                                 need = true;
                             }
+#ifdef RT_TRACE_PROFILE
+                            pf_released = true;
+#endif
                         }
                     }
-                    // slots per lane (lanes_in_grid divides the shard); a slot's chain in this kernel: generations 0 .. last_gen - 1
-                    const unsigned chunk_sets = (unsigned)ap_n / (unsigned)lanes_in_grid;
+#ifdef RT_TRACE_PROFILE
+                    pf_handovers += wave_count(pf_released);
+                    pf_handover_blocks += wave_ballot(pf_released) != 0 ? 1 : 0;
+#endif
+                    // dealt slots per lane (lanes_in_grid divides the shard); a slot's chain in this kernel: generations 0 .. last_gen - 1
+                    const unsigned chunk_sets = (unsigned)ap_n / (unsigned)lanes_in_grid - chunk_head;
                     const unsigned chunk_tasks = rtchunks::task_count(chunk_sets, (unsigned)ap.last_gen, (unsigned)chunk_g);
                     // (every turn of this loop deals tasks: it ends when the lanes have a slot each or the tasks are out)
                     unsigned long long m;
@@ -467,9 +508,12 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
                                 phase = PH_IDLE;  // out of tasks: this lane is done (i = ap_n)
                             } else {
                                 const rtchunks::Entry e = rtchunks::task_entry(t, chunk_sets);
-                                const int k = slot_of((int)e.set, e.lane);
-                                const int old = k < ap_n ? __hip_atomic_fetch_sub(&p.sem(k), 1, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) : 0;
-                                if (rtchunks::taker_runs(old)) {
+                                const int k = slot_of((int)(e.set + chunk_head), e.lane);
+                                const unsigned idx = e.set * rtchunks::kLanes + e.lane;
+                                const unsigned old = k < ap_n ? __hip_atomic_fetch_sub(&s_sem[rtchunks::sem_word(idx) & (rtchunks::kSemWords - 1u)], rtchunks::sem_unit(idx),
+                                                                                       __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)
+                                                              : rtchunks::kSemBias;  // (no such slot: as a claim)
+                                if (rtchunks::taker_runs(rtchunks::sem_value(old, idx))) {
                                     i = k;
                                     load_slot(i);
                                     cold_save();
@@ -484,6 +528,15 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
                     }
                 }
             }
+            if (CHUNKS) {
+                // (vmcnt(0), nothing else.  The compiler cannot tell at this merge whether the hand-over's loads are in, and waits
+                // for them at the first use of a register they wrote: left alone that is BEHIND the atomics below, whose
+                // acknowledgements every GEN block would then sit through.  Here it costs what the same wait cost in front
+                // of the flush before: nothing, unless a hand-over has just been made.)
+                __builtin_amdgcn_s_waitcnt(0x0f70);
+                // (also for a lane that banked its slot and found the tasks out: it is idle from here on)
+                if (chunk_was_gen) acc_flush(acc, fb, ap_fb_fixed, chunk_acc_pixel);
+            }
             if (phase == PH_GEN) {
                 SlotState st;
                 st.gen = cold[2 * kBlock];
@@ -493,7 +546,7 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
                 st.pixel = 0;
                 st.beta = mk(0, 0, 0);
                 int pxy = cold[12 * kBlock];
-                acc_flush(acc, fb, ap_fb_fixed, cold[1 * kBlock]);  // the camera ray that ended: its sum -> its pixel
+                if (!CHUNKS) acc_flush(acc, fb, ap_fb_fixed, cold[1 * kBlock]);  // the camera ray that ended: its sum -> its pixel
                 gen_core<true>(cam, ap, ap.slot_lo + i, st, out, &pxy, my_cid);
                 // the slot state gen() leaves: bounces (0, or the kDone / kParked sentinel), gen, the RNG; a new path also
                 // has its pixel and beta = 1
@@ -528,12 +581,15 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
                 if (hand_back) {
                     if (draw_cids) {
                         phase = PH_IDLE;  // (the frame's counter has run out: nothing is tied to this lane's slot)
-                    } else if (CHUNKS && chunk_g) {
-                        cold_load();  // the slot is finished: its final state goes to the pools, the lane draws a task next
+                    } else if (CHUNKS && chunk_g && slot_set + 1 >= (int)s_task[5]) {
+                        // a dealt slot, or the last one of the static head, is finished: its final state goes to the pools, the
+                        // lane draws a task next
+                        cold_load();
                         store_slot(i);
                         i = ap_n;
                         tri = -1;
-                    } else {
+                        slot_set = (int)s_task[5];
+                    } else {  // (the static deal, or the static head of the chunked one: the lane's own next slot)
                         next_slot(PH_GEN);
                     }
                 }
@@ -887,6 +943,7 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
     if (prof && lane_id() == 0)
         { pf[11] = pf_life; for (int k = 0; k < 16; k++) atomicAdd(&prof[k], pf[k]); atomicMax(&prof[13], pf[11]); atomicAdd(&prof[14], 1ull); atomicAdd(&prof[16], pf_gen_cycles);
           atomicAdd(&prof[20], pf_idle); atomicAdd(&prof[21], pf_idle_max);
+          atomicAdd(&prof[22], pf_handovers); atomicAdd(&prof[23], pf_handover_blocks);
           // per-wave record: where it ran and for how long
           unsigned long long *rec = prof + 24 + kProfRec * (size_t)((blockIdx.x * kBlock + threadIdx.x) >> 6);
           rec[0] = __builtin_amdgcn_s_getreg((31 << 11) | 4);   // HW_ID

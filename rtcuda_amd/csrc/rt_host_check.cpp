@@ -971,6 +971,34 @@ int rt_slot_chunk_runner_keeps(int old_sem) { return rtchunks::runner_keeps(old_
 int rt_plan_slot_chunk(int n, int cus, int chain) {
     return rtplan::slot_chunk_for(rtplan::plan_paths_launch(n, cus, true, 70000, 10, true, 1920, 256, 0), chain);
 }
+// The static head and the packed semaphores of the chunked deal (tests/test_slot_chunks_head_host.py).
+// the head the plan picks for a shard of n slots (n / (workgroups x 256) slot sets per lane); *sets_out: those sets
+int rt_plan_slot_head(int n, int cus, int *sets_out) {
+    const rtplan::PathsLaunch p = rtplan::plan_paths_launch(n, cus, true, 70000, 10, true, 1920, 256, 0);
+    const int sets = n / (p.blocks * rtplan::kBlock);
+    if (sets_out) *sets_out = sets;
+    return rtplan::slot_head_for(p, sets);
+}
+int rt_plan_slot_chunk_if_resident(int chunk, int workgroups_per_cu) { return rtplan::slot_chunk_if_resident(chunk, workgroups_per_cu); }
+// the dealt entry (head + set, lane) of a task, as k_paths_chunked maps it: the slot, the level and the entry's index
+void rt_slot_chunk_head_tasks(int block, int sets, int head, int lanes_in_grid, int rot_wave, int rot_set, uint32_t t0, int count, int32_t *slots, int32_t *levels, int32_t *idx) {
+    for (int k = 0; k < count; k++) {
+        const rtchunks::Entry e = rtchunks::task_entry(t0 + (uint32_t)k, (unsigned)(sets - head));
+        slots[k] = rtchunks::slot_of(e.set + (unsigned)head, (unsigned)block * rtchunks::kLanes + e.lane, (unsigned)lanes_in_grid, (unsigned)rot_wave, (unsigned)rot_set);
+        levels[k] = (int32_t)e.level;
+        idx[k] = (int32_t)(e.set * rtchunks::kLanes + e.lane);
+    }
+}
+// the inverse of the static deal: out2 = {slot set, lane of the grid}
+void rt_slot_chunk_owner(int slot, int lanes_in_grid, int rot_wave, int rot_set, int32_t *out2) {
+    const rtchunks::Owner o = rtchunks::owner_of((unsigned)slot, (unsigned)lanes_in_grid, (unsigned)rot_wave, (unsigned)rot_set);
+    out2[0] = (int32_t)o.set;
+    out2[1] = (int32_t)o.lane_in_grid;
+}
+uint32_t rt_slot_chunk_sem_word(uint32_t idx) { return rtchunks::sem_word(idx); }
+uint32_t rt_slot_chunk_sem_unit(uint32_t idx) { return rtchunks::sem_unit(idx); }
+int rt_slot_chunk_sem_value(uint32_t word, uint32_t idx) { return rtchunks::sem_value(word, idx); }
+uint32_t rt_slot_chunk_sem_init() { return rtchunks::kSemWordInit; }
 // The CPU twin of rt_denoise_fixed (tests/test_denoise_host.py): a plain serial loop over the arithmetic the kernels use
 // (rt_denoise.h), host buffers throughout, the same checks of the parameters.  Returns 0, or 1 and writes nothing.
 int hc_denoise(const int64_t *sum_fixed, int num_samples, const int64_t *aov_fixed, int aov_samples, int width, int height, int passes,

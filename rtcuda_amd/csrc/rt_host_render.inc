@@ -284,7 +284,7 @@ struct FrameRun {
     bool per_sample;
     HitMode mode;
     bool lds_tables = false, persistent = true, finished = false, ran_lockstep = false;
-    int cus = 0, stack_cap = 0, top_records_in_lds = 0, slot_chunk = 0, lock_enqueued = 0;
+    int cus = 0, stack_cap = 0, top_records_in_lds = 0, slot_chunk = 0, slot_head = 0, lock_enqueued = 0;
     DScene sc{};
     Camera cam{};
     AdvanceParams ap{};
@@ -327,6 +327,8 @@ static int report_paths_profile(unsigned long long *paths_prof, int paths_blocks
             100.0 * h[10] / h[11], h[4] ? (double)h[10] / h[4] : 0.0, 100.0 * (double)(h[11] - h[8] - h[9] - h[10]) / h[11]);
     fprintf(stderr, "k_paths GEN blocks: %llu avg lanes %.1f, %.1f %% of wave time (%.0f cycles / block; inside `rest` above)\n", h[12],
             h[12] ? (double)h[15] / h[12] : 0.0, 100.0 * h[16] / h[11], h[12] ? (double)h[16] / h[12] : 0.0);
+    fprintf(stderr, "k_paths GEN cycles per wave %.0f; chunked deal: %.2f hand-overs per lane, made in %.2f %% of the GEN blocks\n", h[14] ? (double)h[16] / h[14] : 0.0,
+            h[14] ? (double)h[22] / (64.0 * h[14]) : 0.0, h[12] ? 100.0 * h[23] / h[12] : 0.0);
     fprintf(stderr, "k_paths waves: %llu, mean lifetime %.0f cycles, longest %.0f cycles (x%.3f)\n", h[14], (double)h[11] / h[14], (double)h[13],
             (double)h[13] * h[14] / h[11]);
     // lane-idle tail: per wave, the lane-cycles between each lane's last work and the wave's exit -- whole-wave blocks issued
@@ -386,11 +388,20 @@ int FrameRun::run_persistent() {
     // (a chunk > 0 launches k_paths_chunked, 4-waves-per-SIMD reference-mode builds that keep no records in LDS: their `top_n`
     // carries the chunk; a frame of one generation runs no chain in k_paths -- every slot parks at once -- and keeps the static
     // deal, and so do ray tables)
-    const int chunk = (rays || p.few_blocks || per_sample || ap.last_gen < 1 || ap.n != c.n) ? 0 : rtplan::slot_chunk_for(p, ap.last_gen);
+    int chunk = (rays || p.few_blocks || per_sample || ap.last_gen < 1 || ap.n != c.n) ? 0 : rtplan::slot_chunk_for(p, ap.last_gen);
+    const PathsKernel chunked = paths_chunked_kernel(lds_tables, scene->wide, mode.literal, mode.verify);
+    if (chunk > 0) {  // (its semaphores are 2 KB of static LDS: beside large tables in LDS they would cost a resident workgroup)
+        int per_cu = 0;
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, chunked, kBlock, p.lds_bytes));
+        chunk = rtplan::slot_chunk_if_resident(chunk, per_cu);
+    }
+    // (the static head travels above G's 21 bits)
+    slot_head = chunk > 0 ? rtplan::slot_head_for(p, ap.n / (p.blocks * kBlock)) : 0;
+    static_assert(rtplan::kDealtSetsMax == (int)rtchunks::kDealtSetsMax, "the plan deals what the semaphores hold");
     slot_chunk = chunk;
     if (rays && rays->keyed) launch_paths(paths_keyed_kernel(lds_tables, p.few_blocks), rays->keyed_table, p.top_n);
     else if (rays) launch_paths(paths_rays_kernel(lds_tables, p.few_blocks, mode.verify), rays->table, p.top_n);
-    else if (chunk > 0) launch_paths(paths_chunked_kernel(lds_tables, scene->wide, mode.literal, mode.verify), cam, chunk);
+    else if (chunk > 0) launch_paths(chunked, cam, chunk | (slot_head << rtplan::kChunkHeadShift));
     else launch_paths(paths_kernel(lds_tables, scene->wide, p.few_blocks, per_sample, mode.literal, mode.verify), cam, mode.literal ? 0 : p.top_n);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(c.ev_b, st));
@@ -550,7 +561,7 @@ int FrameRun::frame_stats(rt_stats *stats) {
         stats->seconds_advance = 0.0;
         stats->launches_trace = 1;
         stats->reserved[0] = 1;
-        stats->reserved[1] = 1 + slot_chunk;
+        stats->reserved[1] = 1 + slot_chunk + ((int64_t)slot_head << 32);
         stats->reserved[2] = top_records_in_lds;
     }
     rare_path_counters(h_final.vstat, &stats->reserved[4]);

@@ -18,6 +18,7 @@ struct PathsLaunch {
     int top_n, adv_batch, gen_batch, tri_follow, prio_rotate, rot_wave, rot_set;  // (see where they are set)
     int slot_chunk;    // camera rays per task of the chunked deal (rt_slot_chunks.h); 0: the static deal; kSlotChunkAuto: by the
                        // length of the frame's chains (slot_chunk_for)
+    int slot_head;     // slot sets a lane runs as the static deal does before the deal begins; kSlotHeadAuto: slot_head_for's default
 };
 // The hand-over costs the same per chunk whatever the frame, and what it buys -- the spread of the lanes' totals -- shrinks
 // relative to a lane's work as the chains get longer: the best chunk grows with the chain, kChunksPerSlot tasks per slot (the
@@ -28,6 +29,14 @@ struct PathsLaunch {
 // kernel.  The two edges are NOT measured: they are the range of G that was flat at 506 rays (48 .. 96) turned into chain
 // lengths at 8 tasks per slot; the gain must fall to the loss seen at 1 012 rays somewhere above 506, possibly before 768.
 constexpr int kSlotChunkAuto = -1, kChunksPerSlot = 8, kChunkChainLo = 384, kChunkChainHi = 768;
+// A lane's totals differ from its neighbours' only at the end, and a hand-over balances something only while a lane has at
+// least two dealt slots: the last kDealtSetsDefault sets are dealt, the sets before them run as in the static deal (half the
+// hand-overs of a full pool's frame; the 2-shard frame, two sets, is dealt whole).  The workgroup's semaphores (2 KB of static
+// LDS in k_paths_chunked, rtchunks::kSemWords) hold kDealtSetsMax dealt sets; with them a workgroup must still be one of
+// kChunkWorkgroupsPerCu on its CU, or the frame keeps the static deal (slot_chunk_if_resident).
+constexpr int kSlotHeadAuto = -1, kDealtSetsDefault = 2, kDealtSetsMax = 4, kChunkWorkgroupsPerCu = 4;
+// G (at most 2^20) and the head reach the kernel in one int: the head above G's kChunkHeadShift bits, so at most kChunkSetsMax sets
+constexpr int kChunkHeadShift = 21, kChunkSetsMax = 1 << (31 - kChunkHeadShift);
 
 // `n`: slots of the shard; `paths_cap`: stack entries of a lane kept in LDS; `lattice`: the rays follow the camera's pixel
 // lattice (not a table's); `fixed_lds_bytes`: the shading tables (if staged in LDS) + the camera + the frame's parameters.
@@ -97,8 +106,20 @@ inline PathsLaunch plan_paths_launch(int n, int cus, bool wide, int n_nodes, int
     p.slot_chunk = (p.few_blocks || n / (p.blocks * kBlock) < 2) ? 0 : kSlotChunkAuto;
     if (const char *e = knob("RT_SLOT_CHUNK")) p.slot_chunk = p.few_blocks ? 0 : std::max(0, std::min(1 << 20, atoi(e)));
     if (n % (p.blocks * kBlock) != 0) p.slot_chunk = 0;
+    if (n / (p.blocks * kBlock) > kChunkSetsMax) p.slot_chunk = 0;  // (RT_PATHS_BLOCKS far below its default)
+    p.slot_head = kSlotHeadAuto;
+    if (const char *e = knob("RT_SLOT_HEAD")) p.slot_head = std::max(0, atoi(e));
     return p;
 }
+// The static head of the chunked deal for a shard of `sets` slots per lane: 0 .. sets - 1 (at least one set is dealt), and never
+// more dealt sets than the semaphores hold.
+inline int slot_head_for(const PathsLaunch &p, int sets) {
+    const int head = p.slot_head == kSlotHeadAuto ? sets - kDealtSetsDefault : p.slot_head;
+    return std::max(std::max(0, sets - kDealtSetsMax), std::min(head, sets - 1));
+}
+// k_paths_chunked's static LDS must leave the workgroups as resident as the plan assumes (`workgroups_per_cu`: the device's
+// answer for that kernel at p.lds_bytes of dynamic LDS); scenes whose tables in LDS leave no room keep the static deal.
+inline int slot_chunk_if_resident(int chunk, int workgroups_per_cu) { return workgroups_per_cu >= kChunkWorkgroupsPerCu ? chunk : 0; }
 // G for a frame whose slots run `chain` camera rays each inside k_paths (= the index of the final generation)
 inline int slot_chunk_for(const PathsLaunch &p, int chain) {
     if (p.slot_chunk != kSlotChunkAuto) return p.slot_chunk;

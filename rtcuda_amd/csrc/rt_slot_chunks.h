@@ -1,13 +1,17 @@
-// rt_slot_chunks.h -- the chunked deal of a workgroup's slots to its lanes (k_paths, reference mode, 4 waves per SIMD): the
-// pure decisions, shared by the kernel and by host programs (rt_host_check.cpp exports the mapping; tests/cpp/slot_chunks_check.cpp
-// plays the protocol with std::atomic).
+// rt_slot_chunks.h -- the chunked deal of a workgroup's slots to its lanes (k_paths_chunked, reference mode, 4 waves per SIMD):
+// the pure decisions, shared by the kernel and by host programs (rt_host_check.cpp exports the mapping;
+// tests/cpp/slot_chunks_check.cpp and slot_chunks_head_check.cpp play the protocol with std::atomic).
 //
-// A workgroup keeps exactly the slots the static deal gives it: S = sets x 256, entry idx <-> (set = idx / 256, lane of the
-// workgroup = idx % 256) <-> slot_of(set, that lane).  Its lanes take them G camera rays at a time: task t of the workgroup
-// means "run up to G camera rays of entry t % S" (level t / S, level-major), tasks are dealt from one counter, and a slot's
-// chain changes lanes only between two camera rays -- where its live state is gen and the six RNG words.
+// A workgroup keeps exactly the slots the static deal gives it: sets x 256, (set, lane of the workgroup) <-> slot_of(set, that
+// lane).  Static head, dealt tail: a lane first runs its own slots of the sets 0 .. head - 1 for their whole chains, exactly as
+// the static deal does -- no task, no semaphore, no test for a chunk's end.  Only the sets head .. sets - 1 are dealt (a lane's
+// totals differ only at the end, and at least two dealt slots per lane are what makes a hand-over balance anything): S =
+// (sets - head) x 256 entries, entry idx <-> (set = head + idx / 256, lane = idx % 256).  The lanes take them G camera rays at
+// a time: task t of the workgroup means "run up to G camera rays of entry t % S" (level t / S, level-major), tasks are dealt
+// from one counter, and a slot's chain changes lanes only between two camera rays -- where its live state is gen and the six
+// RNG words.
 //
-// Hand-over without waiting: one int per slot (1 = banked: the state is stored and nobody runs the slot).
+// Hand-over without waiting: one semaphore per entry (1 = banked: the state is stored and nobody runs the slot).
 //   taker            old = fetch_sub(sem, 1, acquire);  taker_runs(old): load the state and run; otherwise the -1 stays as a
 //                    claim and the taker draws its next task at once
 //   runner, at a     (chunk_ends) stores the state, then old = fetch_add(sem, 1, release);  runner_keeps(old): a claim was
@@ -16,6 +20,11 @@
 // A runner that finds the slot's chain at its end does not bank it (the final state is stored as in the static deal), so a
 // banked slot always has a ray left and every chunk that is started consumes one task: ceil(rays / G) tasks per slot are
 // enough, surplus tasks leave claims nobody needs.  Nobody ever waits: every decision is one atomic.
+//
+// Only the lanes of the workgroup touch its semaphores, so they live in its LDS (workgroup scope; the release still orders the
+// runner's global stores of the state before it): 16-bit fields, two to a word, biased so that a field never borrows from or
+// carries into its neighbour -- sem_word / sem_unit / sem_value below.  The ended camera ray's sum goes to the framebuffer
+// after the hand-over, so that no hand-over waits for a float atomic's acknowledgement.
 #pragma once
 
 #if defined(__HIPCC__)
@@ -50,6 +59,36 @@ RT_CHUNKS_FN int slot_of(unsigned set, unsigned lane_in_grid, unsigned lanes_in_
 
 RT_CHUNKS_FN bool taker_runs(int old_sem) { return old_sem >= 1; }
 RT_CHUNKS_FN bool runner_keeps(int old_sem) { return old_sem < 0; }
+
+// The semaphores of a workgroup's dealt entries, packed: entry idx is the 16-bit field idx & 1 of word idx >> 1, and holds
+// kSemBias + the semaphore's value.  The atomics add or subtract sem_unit(idx); sem_value(old word, idx) is the `old_sem` of
+// the two decisions above.
+// Bound: a field starts at kSemBias + 1 (banked) and never exceeds it (a release follows a take or a claim).  It is lowered
+// once per task of its slot at most (the take or the claim of that task), and a slot has at most 2 047 tasks: levels(rays, G)
+// <= rays <= 2 047, because render_shard_impl refuses frames whose camera-ray ids come within 13 W of 2^31.  So a field stays
+// within [kSemBias - 2 046, kSemBias + 1], inside (0, 0xffff): no borrow, no carry.
+constexpr unsigned kSemBias = 0x4000u, kSemBanked = kSemBias + 1u;
+constexpr unsigned kSemWordInit = kSemBanked | (kSemBanked << 16);  // both fields banked
+constexpr unsigned kDealtSetsMax = 4;                               // dealt sets of a workgroup: 1 024 fields, 2 KB of LDS
+constexpr unsigned kSemWords = kDealtSetsMax * kLanes / 2u;
+static_assert(kSemBias > 2046u && kSemBias + 1u < 0x10000u, "a field must hold [bias - 2046, bias + 1]");
+RT_CHUNKS_FN unsigned sem_word(unsigned idx) { return idx >> 1; }
+RT_CHUNKS_FN unsigned sem_unit(unsigned idx) { return 1u << (16u * (idx & 1u)); }
+RT_CHUNKS_FN int sem_value(unsigned word, unsigned idx) { return (int)((word >> (16u * (idx & 1u))) & 0xffffu) - (int)kSemBias; }
+
+// The inverse of slot_of: the (slot set, lane of the grid) whose slot `slot` is.  A runner finds its slot's semaphore with it
+// at a chunk's end, so that no entry index lives in a register across the kernel's main loop.  `rot_wave`: a multiple of 4
+// (rt_launch_plan.h), so the low two bits of the wave are those of b - set * rot_set.
+struct Owner {
+    unsigned set, lane_in_grid;
+};
+RT_CHUNKS_FN Owner owner_of(unsigned slot, unsigned lanes_in_grid, unsigned rot_wave, unsigned rot_set) {
+    const unsigned mask = (lanes_in_grid >> 6) - 1u;
+    const unsigned set = slot >> (31u - (unsigned)__builtin_clz(lanes_in_grid)), b = (slot >> 6) & mask;
+    const unsigned low = (b - set * rot_set) & 3u;
+    const unsigned wave = (b - low * rot_wave - set * rot_set) & mask;
+    return Owner{set, wave * 64u + (slot & 63u)};
+}
 
 // "gen is a multiple of G" without a division in the GEN block: gen * (odd part of G)^-1 mod 2^32, rotated right by G's
 // trailing zeros, is at most (2^32 - 1) / G exactly for the multiples (Lemire, Kaser, Kurz 2019).

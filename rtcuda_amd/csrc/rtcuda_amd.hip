@@ -168,8 +168,7 @@ inline int tab_dwords(int n_mats, int n_lights) { return kTabPerMat * n_mats + k
 //   pixel, gen        pixel of the current camera ray; index of the slot's NEXT generation
 //   rd, r0..r4        XORWOW state
 //   sox..slb, starget shadow ray of the slot for this round (stmax < 0: none) + radiance + excluded triangle
-//   sem               k_paths' chunked deal (rt_slot_chunks.h): 1 = the slot's state is stored here and no lane runs it
-enum { A_OX, A_OY, A_OZ, A_DX, A_DY, A_DZ, A_HPX, A_HPY, A_HPZ, A_HNX, A_HNY, A_HNZ, A_BR, A_BG, A_BB, A_SOX, A_SOY, A_SOZ, A_SDX, A_SDY, A_SDZ, A_STMAX, A_SLR, A_SLG, A_SLB, A_HIT_INFO, A_BOUNCES, A_PIXEL, A_GEN, A_STARGET, A_RD, A_R0, A_R1, A_R2, A_R3, A_R4, A_SEM, A_COUNT };
+enum { A_OX, A_OY, A_OZ, A_DX, A_DY, A_DZ, A_HPX, A_HPY, A_HPZ, A_HNX, A_HNY, A_HNZ, A_BR, A_BG, A_BB, A_SOX, A_SOY, A_SOZ, A_SDX, A_SDY, A_SDZ, A_STMAX, A_SLR, A_SLG, A_SLB, A_HIT_INFO, A_BOUNCES, A_PIXEL, A_GEN, A_STARGET, A_RD, A_R0, A_R1, A_R2, A_R3, A_R4, A_COUNT };
 struct DPools {
     float *base;
     int n;
@@ -209,7 +208,6 @@ struct DPools {
     __device__ __forceinline__ uint32_t &r2(int i) const { return ((uint32_t *)base)[(unsigned)(A_R2 * n + i)]; }
     __device__ __forceinline__ uint32_t &r3(int i) const { return ((uint32_t *)base)[(unsigned)(A_R3 * n + i)]; }
     __device__ __forceinline__ uint32_t &r4(int i) const { return ((uint32_t *)base)[(unsigned)(A_R4 * n + i)]; }
-    __device__ __forceinline__ int &sem(int i) const { return ((int *)base)[(unsigned)(A_SEM * n + i)]; }
     // host-side address of array k
     float *array(int k) const { return base + (size_t)k * n; }
 };
@@ -308,7 +306,6 @@ __global__ void k_pool_init(DPools p, int n, int max_bounces) {
     p.bounces(i) = max_bounces;
     p.gen(i) = 0;
     p.pixel(i) = 0;
-    p.sem(i) = 1;
 }
 
 // ============================================================================ k_advance
