@@ -127,6 +127,10 @@ typedef struct rt_stats {
  *   RT_FLAG_WATERTIGHT: the triangle-list definition instead -- an accepted hit is never lost to a box test, ties go to the
  *       larger caller index: what exhaustive search over all triangles returns.  About 1 path in 4 * 10^6 differs from the
  *       reference's image (on BASELINE config 5 those paths carry whole light deposits: RMS 3.2e-4); 3 - 4 % faster.
+ *       LIMIT of that promise: a triangle the ray sees nearer to edge-on than cos(d, n) = 2^-11 (about 2 hits in 10^7) has an
+ *       fp32 t made of rounding noise, which can lie in front of its own box by any amount; if another triangle's hit lies in
+ *       between, the walk may return that one where exhaustive search returns the edge-on one.  Down to that angle the distance
+ *       limit of the box test is widened for it (rt_bvh.h, kCullTmaxWiden; profiles/ray_families.md).
  *
  * FAR-OFF AND DUPLICATED GEOMETRY.  The rate of the rare path is a property of where the scene sits: the reference's slab test
  * loses hits in proportion to the size of the coordinates, so a scene shifted by 1e4 sends 42 of 20 000 camera rays (and 20 to 30
@@ -327,7 +331,8 @@ int rt_post_process(float *d_rgb, int num_pixels, int num_samples, void *stream)
  * flags: 0, RT_FLAG_WATERTIGHT, RT_FLAG_TIME_KERNELS.  Out of scope (an error that names the flag): RT_FLAG_REFERENCE_WALK and
  * RT_FLAG_RNG_PER_SAMPLE -- each would be further builds of the persistent kernel.  No shard parameters either: one device,
  * all W slots.  (A table with a stream per RAY, which splits over calls and devices: rt_render_rays_keyed_device below.)
- * CHECKED ON THE DEVICE BEFORE ANYTHING IS WRITTEN: every direction component finite and below 2^126 in magnitude, every
+ * CHECKED ON THE DEVICE BEFORE ANYTHING IS WRITTEN: every direction component finite and below 2^126 in magnitude, no
+ * direction other than zero with every component below 2^-60 (as for rt_query_closest_device), every
  * d_pixel[c] in [0, n_pixels) -- the error names the number of offending rays.  Origins outside the radius the scene's
  * records are padded for widen the padding once, as for the queries; a non-finite ORIGIN is legal: that ray misses.
  * Host-side: non-null scene / origins / directions / sum buffer, 1 <= n_rays (below the int32 camera-ray range of
@@ -574,7 +579,10 @@ int rt_denoise_dual_fixed(const int64_t *d_sum_a, int samples_a, const int64_t *
  *       < 0 or >= n_tris excludes nothing, and so does d_excluded_tri = NULL.
  * Directions are unit vectors; what is CHECKED, on the device before anything is written, is that every component is finite
  * and below 2^126 in magnitude (beyond that the reference's slab arithmetic overflows and a visibility decision would not be
- * the reference's): otherwise the call fails and names the number of offending rays.  A non-finite ORIGIN is legal: the ray
+ * the reference's): otherwise the call fails and names the number of offending rays.  Directions need not have unit length: a
+ * direction scaled by s gives the same hits at t / s.  One whose largest component is below 2^-60 in magnitude and that is not
+ * zero is refused in the same way, with the number of such rays (the traversal keeps 1 / d finite by a floor of 2^-90 under
+ * each component, which such a ray would feel; a zero direction hits nothing).  A non-finite ORIGIN is legal: the ray
  * misses.  0 <= n <= 2^30; n = 0 succeeds and touches nothing.
  * The work is ordered on `stream` (NULL = default stream) and the call is synchronous on that stream when it returns, as
  * rt_scene_update_device and rt_render_shard are.  The calling thread's current device is left as it was.  The steady path
@@ -609,7 +617,8 @@ int rt_trace_any(const rt_scene *scene, int n, const float *origin_xyz, const fl
                  const float *tmax, const int32_t *excluded_tri, int32_t *occluded);
 /* The same two entry points with a flags word (RT_FLAG_REFERENCE_WALK / RT_FLAG_WATERTIGHT: see the flags).  flags = 0 is
  * rt_trace_closest / rt_trace_any: hit_tri, t, u, v and occluded are the reference's answers, ties and lost hits included.
- * Directions are unit vectors (finite, every component below 2^126 in magnitude). */
+ * Directions are unit vectors.  PRECONDITION, not checked here: every component finite and below 2^126 in magnitude, and the
+ * largest component at least 2^-60 (or the direction zero) -- what rt_query_*_device refuse. */
 int rt_trace_closest_flags(const rt_scene *scene, uint32_t flags, int n, const float *origin_xyz, const float *dir_xyz,
                            const float *tmax, int32_t *hit_tri, float *t, float *u, float *v);
 int rt_trace_any_flags(const rt_scene *scene, uint32_t flags, int n, const float *origin_xyz, const float *dir_xyz,

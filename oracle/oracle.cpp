@@ -504,19 +504,26 @@ struct AabbIsect {  // aabb_intersector.cuh:14-36
     int ox, oy, oz;
     V3 inv, so;
     bool watertight = false;
-    double wo[3], winv[3];
+    double wo[3], wd[3];
     AabbIsect(const Ray &ray, bool wt) : AabbIsect(ray) {
         watertight = wt;
         wo[0] = ray.o.x; wo[1] = ray.o.y; wo[2] = ray.o.z;
-        winv[0] = inv.x; winv[1] = inv.y; winv[2] = inv.z;
+        wd[0] = ray.d.x; wd[1] = ray.d.y; wd[2] = ray.d.z;
     }
+    // The TRUE ray against the widened box, in double: 1 / d of the direction as given, not the reference's clamped one (a ray
+    // along an axis culled with a clamped 1 / d leaves the true ray by FLT_EPSILON * t: more than the widening).  A zero
+    // component: the ray stays between the two planes of that axis or never gets there.
     bool hit_conservative(const BBox &bb) const {
         double t_in = -1e300, t_out = 1e300;
         for (int a = 0; a < 3; a++) {
             double lo = bb.b[2 * a], hi = bb.b[2 * a + 1];
             lo -= fabs(lo) * 1e-6 + 1e-7;
             hi += fabs(hi) * 1e-6 + 1e-7;
-            double t0 = (lo - wo[a]) * winv[a], t1 = (hi - wo[a]) * winv[a];
+            if (wd[a] == 0.0) {
+                if (wo[a] < lo || wo[a] > hi) return false;
+                continue;
+            }
+            double t0 = (lo - wo[a]) / wd[a], t1 = (hi - wo[a]) / wd[a];
             t_in = std::max(t_in, std::min(t0, t1));
             t_out = std::min(t_out, std::max(t0, t1));
         }
@@ -945,13 +952,26 @@ inline long long to_fixed(float x) {
     if (!(fabsf(x) <= 2147483648.f)) x = (x == x) ? copysignf(2147483648.f, x) : 0.f;
     return llrintf(x * 1073741824.f);
 }
+// The TABLE form of both renders (the product's rt_render_rays*_device, include/rtcuda_amd.h): camera ray c takes its ray and
+// its pixel from a table instead of camera_get_ray and c / spp.  Everything else is the camera form's text: the two jitter draws
+// are still made, and thrown away; n_rays rays over n_pixels pixels (width = n_pixels, height = 1 below).
+struct RayTable {
+    const float *o3, *d3;
+    const int32_t *pixel;  // or null: c / rays_per_pixel
+    int n_rays, rays_per_pixel;
+    Ray ray(int64_t c) const {
+        return Ray{mk(o3[3 * c], o3[3 * c + 1], o3[3 * c + 2]), mk(d3[3 * c], d3[3 * c + 1], d3[3 * c + 2]), FLT_MAX};
+    }
+    int pixel_of(int64_t c) const { return pixel ? pixel[c] : (int)(c / rays_per_pixel); }
+};
 void render_literal(const Scene &sc, const Camera &cam, int width, int height, int spp, int max_bounces,
                     uint64_t seed, int slot_lo, int slot_hi, int threads, float *fb_sum, float *fb_out,
-                    RenderStats *stats, int32_t *iter_counts, int iter_cap, long long *fb_fixed = nullptr) {
+                    RenderStats *stats, int32_t *iter_counts, int iter_cap, long long *fb_fixed = nullptr,
+                    const RayTable *table = nullptr) {
     const int W = kW;
     const int P = width * height;
     int cam_start = 0;
-    const int cam_end = P * spp;
+    const int cam_end = table ? table->n_rays : P * spp;
     const int num_lights = (int)sc.lights.size();
     Pools p;
     p.pixel_idx.assign(3 * (size_t)W, 0);
@@ -1187,7 +1207,7 @@ void render_literal(const Scene &sc, const Camera &cam, int width, int height, i
                 p.hit[s] = 0;
                 continue;
             }
-            int pixel = cid / spp;
+            int pixel = table ? table->pixel_of(cid) : cid / spp;
             int i = pixel % width;
             int j = pixel / width;
             Xorwow rs = p.rng[s];
@@ -1195,7 +1215,7 @@ void render_literal(const Scene &sc, const Camera &cam, int width, int height, i
             if (fb_fixed) acc_direct[s] = (cid / W == last_gen) ? 1 : 0;
             float jx = rnd(rs);  // x first, then y
             float jy = rnd(rs);
-            p.ray[s] = camera_get_ray(cam, (i + jx) / width, (j + jy) / height);
+            p.ray[s] = table ? table->ray(cid) : camera_get_ray(cam, (i + jx) / width, (j + jy) / height);
             p.bounces[s] = 0;
             p.beta[s] = mk(1.f, 1.f, 1.f);
             p.rng[s] = rs;
@@ -1470,12 +1490,13 @@ StepOut mat_step(const Scene &sc, int max_bounces, const StepIn &in, V3 &beta, i
 }
 
 // One camera ray from gen() to the end of its path; returns the float sum of its contributions.
+// (`table_ray`: the table form -- the ray is given, the jitter draws are made and thrown away)
 V3 per_sample_path(const Scene &sc, const Camera &cam, int width, int height, int pixel, int max_bounces, Xorwow rs,
-                   PathTotals &tot) {
+                   PathTotals &tot, const Ray *table_ray = nullptr) {
     const int i = pixel % width, j = pixel / width;
     const float jx = rnd(rs);  // x first, then y
     const float jy = rnd(rs);
-    Ray ray = camera_get_ray(cam, (i + jx) / width, (j + jy) / height);
+    Ray ray = table_ray ? *table_ray : camera_get_ray(cam, (i + jx) / width, (j + jy) / height);
     V3 beta = mk(1.f, 1.f, 1.f);
     V3 sum = mk(0, 0, 0);
     int bounces = 0;
@@ -1536,7 +1557,7 @@ V3 per_sample_path(const Scene &sc, const Camera &cam, int width, int height, in
 // count.  fb_sum (optional): float sums; fb_out (optional): post-processed; fb_fixed (optional, zeroed by the caller).
 void render_per_sample(const Scene &sc_in, const Camera &cam, int width, int height, int spp, int max_bounces, uint64_t seed,
                        int shard_index, int shard_count, int threads, float *fb_sum, float *fb_out, RenderStats *stats,
-                       long long *fb_fixed) {
+                       long long *fb_fixed, const RayTable *table = nullptr, uint64_t key_first = 0, uint64_t key_stride = 1) {
     Scene sc_wt;
     const Scene *scp = &sc_in;
     if (!sc_in.watertight) {  // the mode keeps the triangle-list definition of the hits
@@ -1549,9 +1570,30 @@ void render_per_sample(const Scene &sc_in, const Camera &cam, int width, int hei
     std::vector<V3> fb(P, mk(0, 0, 0));
     const double t0 = now_s();
     int64_t n_rays = 0, shades = 0, any_rays = 0, closest_rays = 0, emission = 0, ah_adds = 0, ch_adds = 0, rr_draws = 0, rr_kills = 0;
+    if (table) {  // row c: the stream of key_first + c * key_stride, its pixel from the table; integer sums, so any order of the rows
+        PathTotals tot;
+        for (int c = 0; c < table->n_rays; c++) {
+            const Ray r = table->ray(c);
+            const uint64_t key = key_first + (uint64_t)c * key_stride;
+            const int pixel = table->pixel ? table->pixel[c] : (int)(key / (uint64_t)table->rays_per_pixel);  // (the KEY's pixel)
+            n_rays++;
+            const V3 s = per_sample_path(sc, cam, width, height, pixel, max_bounces, sample_stream(seed, key), tot, &r);
+            if (s.x != 0.f || s.y != 0.f || s.z != 0.f) {
+                fb[pixel] = add(fb[pixel], s);
+                if (fb_fixed) {
+                    long long *q = fb_fixed + 3 * (size_t)pixel;
+                    q[0] += to_fixed(s.x);
+                    q[1] += to_fixed(s.y);
+                    q[2] += to_fixed(s.z);
+                }
+            }
+        }
+        shades = tot.shades; any_rays = tot.any_rays; closest_rays = tot.closest_rays; emission = tot.emission_adds;
+        ah_adds = tot.ah_adds; ch_adds = tot.ch_adds; rr_draws = tot.rr_draws; rr_kills = tot.rr_kills;
+    }
 #pragma omp parallel for num_threads(threads) schedule(dynamic, 16) \
     reduction(+ : n_rays, shades, any_rays, closest_rays, emission, ah_adds, ch_adds, rr_draws, rr_kills)
-    for (int pixel = 0; pixel < P; pixel++) {
+    for (int pixel = 0; pixel < (table ? 0 : P); pixel++) {
         PathTotals tot;
         for (int k = 0; k < spp; k++) {
             const uint64_t G = (uint64_t)pixel * (uint64_t)spp + (uint64_t)k;
@@ -2062,6 +2104,37 @@ void orc_render(orc_scene *h, const float *cam12, int width, int height, int spp
         o[18] = (double)st.max_stack;
         o[19] = (double)st.n_iter_records;
     }
+}
+
+// The table form of orc_render (keyed == 0: slots and generations, as rt_render_rays_fixed_device) and of orc_render_per_sample
+// (keyed != 0: row c has the stream of key_first + c * key_stride, as rt_render_rays_keyed_fixed_device).  pixel may be null
+// (row c lands on c / rays_per_pixel).  fb_fixed: n_pixels * 3 int64, zeroed by the caller.  stats_out as orc_render's.
+void orc_render_table(orc_scene *h, int keyed, int n_rays, const float *o3, const float *d3, const int32_t *pixel, int rays_per_pixel,
+                      int n_pixels, int max_bounces, uint64_t seed, uint64_t key_first, uint64_t key_stride, int threads,
+                      double *stats_out, long long *fb_fixed) {
+    const RayTable table{o3, d3, pixel, n_rays, rays_per_pixel < 1 ? 1 : rays_per_pixel};
+    Camera c;
+    memset(&c, 0, sizeof(c));
+    RenderStats st;
+    memset(&st, 0, sizeof(st));
+    if (threads < 1) threads = 1;
+    if (keyed) {
+        render_per_sample(h->sc, c, n_pixels, 1, 1, max_bounces, seed, 0, 1, threads, nullptr, nullptr, &st, fb_fixed, &table, key_first, key_stride);
+    } else {
+        h->sc.collect_stats = false;
+        render_literal(h->sc, c, n_pixels, 1, 1, max_bounces, seed, 0, kW, threads, nullptr, nullptr, &st, nullptr, 0, fb_fixed, &table);
+    }
+    for (int k = 0; k < 20; k++) stats_out[k] = 0.0;
+    stats_out[0] = (double)st.iterations;
+    stats_out[1] = (double)st.sum_mat;
+    stats_out[2] = (double)st.sum_gen;
+    stats_out[3] = (double)st.sum_ah;
+    stats_out[4] = (double)st.sum_ch;
+    stats_out[5] = (double)st.emission_adds;
+    stats_out[6] = (double)st.ah_adds;
+    stats_out[7] = (double)st.ch_adds;
+    stats_out[8] = (double)st.rr_draws;
+    stats_out[9] = (double)st.rr_kills;
 }
 
 // RT_FLAG_RNG_PER_SAMPLE: the XORWOW state camera ray `key` of a frame starts from (6 words: d, v0..v4)

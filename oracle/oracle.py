@@ -122,6 +122,9 @@ class Oracle:
                                             ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _fp, _fp, _fp,
                                             ctypes.c_void_p]
 
+        L.orc_render_table.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, _fp, _fp, _fp, ctypes.c_int, ctypes.c_int,
+                                       ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, _fp, _fp]
+
     # ------------------------------------------------------------------ RNG
     def sample_stream(self, seed: int, key: int) -> np.ndarray:
         """RT_FLAG_RNG_PER_SAMPLE: the XORWOW state (d, v0..v4) that camera ray ``key`` of a frame starts from."""
@@ -433,6 +436,29 @@ class OracleScene:
         stats = {k: (float(v) if k.startswith("seconds") else int(v)) for k, v in zip(names, st)}
         stats["iter_counts"] = it[: stats["n_iter_records"]].copy()
         return fb_out, fb_sum, stats
+
+
+    def render_table(self, o3, d3, n_pixels, pixel=None, rays_per_pixel=1, max_bounces=10, seed=1, keyed=False, key_first=0,
+                     key_stride=1, threads=1):
+        """The table form of ``render``: row c of (o3, d3) is camera ray c, landing on pixel[c] (or c // rays_per_pixel).
+        keyed=False: the reference's slots and generations (rt_render_rays_fixed_device; literal or watertight hits by
+        set_watertight).  keyed=True: the per-sample mode, row c on the stream of key_first + c * key_stride
+        (rt_render_rays_keyed_fixed_device; watertight hits).  The jitter draws are made and thrown away in both.
+        -> (fixed-point sums (n_pixels, 3) int64, stats as ``render``'s)."""
+        o3, d3 = np.ascontiguousarray(o3, np.float32), np.ascontiguousarray(d3, np.float32)
+        n = o3.shape[0]
+        assert o3.shape == (n, 3) and d3.shape == (n, 3) and 0 < n < (1 << 31)
+        pix = None if pixel is None else np.ascontiguousarray(pixel, np.int32)
+        if pix is not None:
+            assert pix.shape == (n,) and pix.min() >= 0 and pix.max() < n_pixels
+        else:
+            assert rays_per_pixel >= 1 and (n - 1) // rays_per_pixel < n_pixels
+        fixed = np.zeros((n_pixels, 3), np.int64)
+        st = np.zeros(20, np.float64)
+        self.o.lib.orc_render_table(self.h, int(keyed), n, _ptr(o3), _ptr(d3), _ptr(pix), rays_per_pixel, n_pixels, max_bounces,
+                                    seed, key_first, key_stride, threads, _ptr(st), _ptr(fixed))
+        names = ["iterations", "sum_mat", "sum_gen", "sum_ah", "sum_ch", "emission_adds", "ah_adds", "ch_adds", "rr_draws", "rr_kills"]
+        return fixed, {k: int(v) for k, v in zip(names, st)}
 
 
 def fnv1a64_bytes(a: np.ndarray) -> int:

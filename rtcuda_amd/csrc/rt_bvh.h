@@ -63,6 +63,25 @@ struct Box {
 constexpr int32_t kNoChild = (int32_t)0x80000000;
 inline int32_t leaf_ref(int first, int count) { return ~((first << 3) | count); }
 
+// ---- what keeps the product's cull conservative for the ray the triangle test sees (inv_dir / inner_step in rt_walk.inc, their
+// twins in rt_host_check.cpp; profiles/ray_families.md has the measurements)
+// 1 / d for the cull.  The reference clamps a component below FLT_EPSILON to +-FLT_EPSILON (aabb_intersector.cuh:17-19); a cull
+// that does the same walks a ray that leaves the true one by FLT_EPSILON * t per axis -- more than the boxes' padding for a ray
+// along an axis, another ray altogether for a direction shorter than 2^-20.  The product's cull only keeps 1 / d finite: a
+// component below 2^-90 in magnitude becomes +-2^-90 (1 / d <= 2^90: the plane distances stay finite for coordinates below 2^37).
+constexpr float kCullDirFloor = 0x1p-90f;
+// A direction whose largest component is below 2^-60 (and not zero: a zero direction hits nothing anywhere) is refused by the
+// device entry points: above it a floored component turns the ray by at most 2^-30, 2^-27 of the scene's radius over a path
+// eight radii long, inside the 2^-23 radius the records are padded by (pad_quads_for_origins); below it it may not.
+constexpr float kMinDirLength = 0x1p-60f;
+// The distance limit of the cull.  A box is left out when the ray enters it beyond the best hit so far -- sound only if an
+// accepted hit's COMPUTED t is no smaller than its box's entry distance.  t = (c . n) / (d . n) carries about 8 roundings of
+// 2^-24 relative to |c| |n| and |d| |n|, so relative to t they grow by 1 / cos(d, n): a triangle seen edge-on at cos = 0.007 was
+// accepted 8.6e-6 t in front of the box that holds it, behind the hit of its neighbour.  The limit is widened by 2^-10, which
+// covers 8 * 2^-24 / cos for every triangle down to cos = 2^-11; nearer to edge-on than that (2 hits in 10^7 for directions
+// uniform about the normal) the fp32 t is noise and no finite factor bounds it.
+constexpr float kCullTmaxWiden = 1.f + 0x1p-10f;
+
 // A node of the collapsed 4-wide tree before it is written out as two pair-style records (see `quads`).
 struct WideNode {
     int32_t link[4];  // child k: a node index (>= 0), a leaf reference (< 0) or kNoChild
@@ -530,10 +549,14 @@ inline Result build(const float *verts, int n) {
             todo.push_back({bn, idx});
             return idx;
         };
+        // (2 ulps of a coordinate that is exactly 0 -- a wall in a coordinate plane -- are two denormals: nothing.  A ray IN that
+        // plane with a zero direction component is culled with 1 / d = +-2^90 (kCullDirFloor) and leaves such a box after
+        // t = 2^-59.  The 4-wide records carry an absolute pad of 2^-23 of the scene's radius; these get 2^-64, absorbed by any
+        // coordinate above 2^-40 and good for t up to 2^26)
         auto set_box = [&](float *dst, const Box &b) {
             for (int a = 0; a < 3; a++) {
-                dst[a] = pad_down(b.lo[a], 2);
-                dst[3 + a] = pad_up(b.hi[a], 2);
+                dst[a] = pad_down(b.lo[a], 2) - 0x1p-64f;
+                dst[3 + a] = pad_up(b.hi[a], 2) + 0x1p-64f;
             }
         };
         std::vector<std::pair<int, int>> todo;  // (binary node, pair index), depth-first

@@ -61,7 +61,7 @@ inline bool box_hit(V3 o, V3 inv, const float *lo, const float *hi, float tmax, 
     float t_out = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fmaxf(az, bz));
     entry = t_in;
     t_out = t_out * 1.000001f;
-    return t_in <= t_out && t_out >= 0.f && t_in <= tmax * 1.000001f;
+    return t_in <= t_out && t_out >= 0.f && t_in <= tmax * rtbvh::kCullTmaxWiden;
 }
 // The 4-wide node step of the kernels: plane distance as ONE fma, b * (1 / d) + s with s = -o * (1 / d) rounded on its own
 // (inner_step<true> in rt_walk.inc); the records it is given are padded for that (rt_bvh.h, pad_quads_for_origins)
@@ -74,10 +74,10 @@ inline bool box_hit_fma(V3 o, V3 inv, const float *lo, const float *hi, float tm
     float t_out = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fmaxf(az, bz));
     entry = t_in;
     t_out = t_out * 1.000001f;
-    return fmaxf(t_in, 0.f) <= fminf(t_out, fminf(tmax * 1.000001f, FLT_MAX));
+    return fmaxf(t_in, 0.f) <= fminf(t_out, fminf(tmax * rtbvh::kCullTmaxWiden, FLT_MAX));
 }
-inline V3 inv_dir(V3 d) {
-    auto clampinv = [](float x) { return 1.f / ((fabsf(x) < FLT_EPSILON) ? copysignf(FLT_EPSILON, x) : x); };
+inline V3 inv_dir(V3 d) {  // the cull's 1 / d: the true direction's, kept finite (rt_bvh.h, kCullDirFloor)
+    auto clampinv = [](float x) { return 1.f / ((fabsf(x) < rtbvh::kCullDirFloor) ? copysignf(rtbvh::kCullDirFloor, x) : x); };
     return V3{clampinv(d.x), clampinv(d.y), clampinv(d.z)};
 }
 std::vector<Tri> leaf_order_triangles(const float *verts, const rtbvh::Result &r, int n) {
@@ -114,7 +114,8 @@ inline bool is_neg_zero(float x) { uint32_t b; memcpy(&b, &x, 4); return b == 0x
 inline RefSlab ref_slab(V3 o, V3 d) {
     RefSlab s;
     s.nx = d.x < 0; s.ny = d.y < 0; s.nz = d.z < 0;
-    s.inv = inv_dir(d);
+    auto refinv = [](float x) { return 1.f / ((fabsf(x) < FLT_EPSILON) ? copysignf(FLT_EPSILON, x) : x); };  // aabb_intersector.cuh:17-19
+    s.inv = V3{refinv(d.x), refinv(d.y), refinv(d.z)};
     s.so = V3{(-o.x) * s.inv.x, (-o.y) * s.inv.y, (-o.z) * s.inv.z};
     s.neg_zero = is_neg_zero(d.x) || is_neg_zero(d.y) || is_neg_zero(d.z);
     return s;

@@ -583,6 +583,8 @@ int validate_table(const rt_scene *scene, const std::string &w, int n, const flo
     HIP_TRY(hipStreamSynchronize(st));
     if (q.h_words->bad_dirs != 0)
         return fail(w + ": " + std::to_string(q.h_words->bad_dirs) + " of " + std::to_string(n) + " directions are not finite or reach 2^126");
+    if (q.h_words->short_dirs != 0)
+        return fail(w + ": " + std::to_string(q.h_words->short_dirs) + " of " + std::to_string(n) + " directions are shorter than 2^-60 in every component");
     if (q.h_words->bad_pixels != 0)
         return fail(w + ": " + std::to_string(q.h_words->bad_pixels) + " of " + std::to_string(n) + " pixel indices are outside 0 .. " + std::to_string(n_pixels - 1));
     float need[3];

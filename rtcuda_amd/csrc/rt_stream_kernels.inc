@@ -249,7 +249,7 @@ struct QueryWords {           // the scratch of one query call (rt_scene::QueryS
     unsigned radius_bits[3];  // per axis: max |origin| over the finite origin components, as the bits of that float
     unsigned bad_dirs;        // rays with a direction component that is not finite or reaches 2^126
     unsigned bad_pixels;      // rt_render_rays_*: rays whose pixel index is outside the sum buffer (k_pixel_prepass)
-    unsigned pad;
+    unsigned short_dirs;      // rays whose direction is not zero and has no component of 2^-60 or more (rt_bvh.h, kMinDirLength)
     unsigned long long vstat[4];  // V_OWN_FAIL, V_LOST, V_TIE, V_LITERAL of this call (rt_query_last_counters)
 };
 struct QueryParams {
@@ -263,12 +263,13 @@ struct QueryParams {
 
 // One pass over the rays before the walk: what ensure_origin_radius needs to know about the origins, and whether every
 // direction keeps the precondition of the walk (finite, every component below 2^126 in magnitude: 1 / d and the slab
-// products of the reference's box test stay finite).  A non-negative float orders like its bit pattern, so the maximum is
+// products of the reference's box test stay finite; not shorter than rtbvh::kMinDirLength, or the cull's floor under 1 / d would
+// walk another ray than the triangle test sees).  A non-negative float orders like its bit pattern, so the maximum is
 // an integer atomicMax: one per wave and axis after a wave reduction.
 __global__ void __launch_bounds__(kBlock) k_query_prepass(const float *__restrict__ o3, const float *__restrict__ d3, int n,
                                                           QueryWords *__restrict__ words) {
     float mx = 0.f, my = 0.f, mz = 0.f;
-    unsigned bad = 0;
+    unsigned bad = 0, shrt = 0;
     const size_t stride = (size_t)gridDim.x * kBlock;
     for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < (size_t)n; i += stride) {
         const float ox = fabsf(o3[3 * i]), oy = fabsf(o3[3 * i + 1]), oz = fabsf(o3[3 * i + 2]);
@@ -278,18 +279,21 @@ __global__ void __launch_bounds__(kBlock) k_query_prepass(const float *__restric
         const float dm = fmaxf(fabsf(d3[3 * i]), fmaxf(fabsf(d3[3 * i + 1]), fabsf(d3[3 * i + 2])));
         const bool nan = d3[3 * i] != d3[3 * i] || d3[3 * i + 1] != d3[3 * i + 1] || d3[3 * i + 2] != d3[3 * i + 2];
         bad += (nan || !(dm < 0x1p126f)) ? 1u : 0u;
+        shrt += (dm > 0.f && dm < rtbvh::kMinDirLength) ? 1u : 0u;
     }
     for (int off = 32; off > 0; off >>= 1) {
         mx = fmaxf(mx, __shfl_xor(mx, off));
         my = fmaxf(my, __shfl_xor(my, off));
         mz = fmaxf(mz, __shfl_xor(mz, off));
         bad += __shfl_xor(bad, off);
+        shrt += __shfl_xor(shrt, off);
     }
     if (lane_id() == 0) {
         if (mx > 0.f) atomicMax(&words->radius_bits[0], __float_as_uint(mx));
         if (my > 0.f) atomicMax(&words->radius_bits[1], __float_as_uint(my));
         if (mz > 0.f) atomicMax(&words->radius_bits[2], __float_as_uint(mz));
         if (bad) atomicAdd(&words->bad_dirs, bad);
+        if (shrt) atomicAdd(&words->short_dirs, shrt);
     }
 }
 // rt_render_rays_*: every pixel index of the table inside the sum buffer?  The same pass for the d_pixel array.

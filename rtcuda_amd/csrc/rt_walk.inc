@@ -16,19 +16,23 @@
 //   * the traversal stack is a column of LDS per lane (replaces device_stack.cuh's int[29] in
 //     scratch memory); entries are inner pair indices (>= 0) or leaf references (< 0).
 //
-// The box test only culls: it is conservative (boxes padded by the builder, exit distance widened
-// by 8 ulp) and may use any arithmetic.  The triangle test is the reference's, bit for bit.
+// The box test only culls: it is conservative for the ray the triangle test sees (boxes padded by the builder, exit distance
+// widened by 8 ulp, 1 / d of the true direction, distance limit widened for edge-on triangles: rt_bvh.h) and may use any
+// arithmetic.  The triangle test is the reference's, bit for bit.
 struct RayPrep {
     V3 o, d, inv;
 };
 __device__ __forceinline__ V3 inv_dir(V3 d) {
-    // aabb_intersector.cuh:17-19 clamps |d| away from 0 the same way before inverting.  The reciprocal itself is the
+    // 1 / d of the TRUE direction: the cull must be conservative for the ray the triangle test sees, so a component is only kept
+    // away from 0 far enough for 1 / d to stay finite (rt_bvh.h, kCullDirFloor) -- the reference's clamp to FLT_EPSILON
+    // (aabb_intersector.cuh:17-19) is restated where its decisions are: ref_slab / ref_visible.  The reciprocal itself is the
     // hardware's v_rcp_f32 (1 ulp) rather than an IEEE division (11 instructions each, three per ray): 1 / d only feeds
     // the box test, which only culls -- box_hit / inner_step widen the exit distance by 8 ulps, which covers the 1 ulp
     // per axis this costs on top of the rounding of the slab arithmetic (the builder pads every box by 2 ulps)
-    float ix = __builtin_amdgcn_rcpf((fabsf(d.x) < kFltEps) ? copysignf(kFltEps, d.x) : d.x);
-    float iy = __builtin_amdgcn_rcpf((fabsf(d.y) < kFltEps) ? copysignf(kFltEps, d.y) : d.y);
-    float iz = __builtin_amdgcn_rcpf((fabsf(d.z) < kFltEps) ? copysignf(kFltEps, d.z) : d.z);
+    constexpr float f = rtbvh::kCullDirFloor;
+    float ix = __builtin_amdgcn_rcpf((fabsf(d.x) < f) ? copysignf(f, d.x) : d.x);
+    float iy = __builtin_amdgcn_rcpf((fabsf(d.y) < f) ? copysignf(f, d.y) : d.y);
+    float iz = __builtin_amdgcn_rcpf((fabsf(d.z) < f) ? copysignf(f, d.z) : d.z);
     return mk(ix, iy, iz);
 }
 __device__ __forceinline__ bool box_hit(V3 o, V3 inv, float lox, float loy, float loz, float hix, float hiy,
@@ -40,7 +44,7 @@ __device__ __forceinline__ bool box_hit(V3 o, V3 inv, float lox, float loy, floa
     float t_out = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fmaxf(az, bz));
     entry = t_in;
     t_out = t_out * 1.000001f;
-    return t_in <= t_out && t_out >= 0.f && t_in <= tmax * 1.000001f;  // (tmax widened like t_out: see inner_step)
+    return t_in <= t_out && t_out >= 0.f && t_in <= tmax * rtbvh::kCullTmaxWiden;  // (see inner_step)
 }
 
 typedef float v2f __attribute__((ext_vector_type(2)));  // packed fp32 (v_pk_*_f32 on gfx950)
@@ -185,10 +189,11 @@ __device__ __forceinline__ void inner_step(const DScene &sc, V3 o, V3 inv, float
         v2f t_out = {fminf(fminf(fmaxf(ax.x, bx.x), fmaxf(ay.x, by.x)), fmaxf(az.x, bz.x)),
                      fminf(fminf(fmaxf(ax.y, bx.y), fmaxf(ay.y, by.y)), fmaxf(az.y, bz.y))};
         t_out = t_out * v2f{1.000001f, 1.000001f};
-        // (tmax is widened like the exit distance: the entry distance carries the same few ulps of rounding, and a
-        // shadow ray that ends ON a triangle coplanar with an occluder -- light quads -- has entry = t = tmax to the
-        // last bit; unwidened, the full-size audit of the sixteen-light scene lost 1 occluder in 9.8e8 shadow rays)
-        const float tmax_w = tmax * 1.000001f;
+        // (tmax is widened: the entry distance carries a few ulps of rounding, and a shadow ray that ends ON a triangle
+        // coplanar with an occluder -- light quads -- has entry = t = tmax to the last bit; unwidened, the full-size audit of
+        // the sixteen-light scene lost 1 occluder in 9.8e8 shadow rays.  By more than the exit distance: the t of a triangle
+        // seen edge-on is computed in FRONT of its box, rt_bvh.h kCullTmaxWiden)
+        const float tmax_w = tmax * rtbvh::kCullTmaxWiden;
         bool hl = el <= t_out.x && t_out.x >= 0.f && el <= tmax_w && cl != kEntryDone;
         bool hr = er <= t_out.y && t_out.y >= 0.f && er <= tmax_w && cr != kEntryDone;
         // What comes next, with as little divergent control flow as the three outcomes allow (every divergent branch
@@ -219,7 +224,7 @@ __device__ __forceinline__ void inner_step(const DScene &sc, V3 o, V3 inv, float
         const v2f ix = {inv.x, inv.x}, iy = {inv.y, inv.y}, iz = {inv.z, inv.z};
         // (clamped to a finite value: an absent child has an all-+inf box -- rt_bvh.h -- whose entry distance is +inf or
         // whose exit distance is -inf whatever the ray, so the one comparison below rejects it without a look at its link)
-        const float tmax_w = fminf(tmax * 1.000001f, kFltMax);
+        const float tmax_w = fminf(tmax * rtbvh::kCullTmaxWiden, kFltMax);
         float e[4];
         bool h[4];
         // entered <=> entry <= exit, exit >= 0, entry <= tmax: max(entry, 0) <= min(exit, tmax) -- one comparison per child
