@@ -562,6 +562,36 @@ inline void denoise_dual(const int64_t *d_sum_a, int samples_a, const int64_t *d
                                                d_scratch, d_rgb_out, stream), "denoise_dual");
 }
 
+// Temporal accumulation (rt_render_motion / rt_temporal_accumulate_fixed, which document both definitions and the errors).
+// render_motion: per pixel where its first hit lay in prev_camera's image one frame ago, {sx, sy, dist, bits of the triangle},
+// width * height * 4 floats in d_motion (DEVICE, 16-byte aligned); d_prev_tri_p0p1p2: last frame's vertices (DEVICE, n_tris x 9,
+// the caller's order) or nullptr when they did not move.  temporal_accumulate: this frame's sums blended into the reprojected
+// history; the outputs are sums of ONE sample of the accumulated mean, which denoise(..., 1, ...) and denoise_dual(..., 1, ..., 1,
+// ...) take as they are, and next frame's `in` buffers.  d_sum_b, d_hist_b_in and d_hist_b_out are nullptr together (one buffer);
+// the three `in` pointers and d_prev_aov_fixed are nullptr on the first frame.
+inline rt_stats render_motion(const Scene &scene, const Camera &camera, int width, int height, const Camera &prev_camera,
+                              const float *d_prev_tri_p0p1p2, float *d_motion, uint32_t flags = 0, void *stream = nullptr) {
+    rt_scene *h = scene.bvh.handle ? rtcuda_detail::realise(scene) : nullptr;
+    rt_stats st{};
+    rtcuda_detail::check(rt_render_motion(h, &camera.pod, width, height, &prev_camera.pod, d_prev_tri_p0p1p2, flags, d_motion, stream, &st),
+                         "render_motion");
+    return st;
+}
+inline rt_temporal_params temporal_default_params() {
+    rt_temporal_params p{};
+    rtcuda_detail::check(rt_temporal_default_params(&p), "temporal_default_params");
+    return p;
+}
+inline void temporal_accumulate(const int64_t *d_sum_a, int samples_a, const int64_t *d_sum_b, int samples_b, const int64_t *d_aov_fixed,
+                                int aov_samples, const float *d_motion, const int64_t *d_hist_a_in, const int64_t *d_hist_b_in,
+                                const int32_t *d_len_in, const int64_t *d_prev_aov_fixed, int prev_aov_samples, int width, int height,
+                                int64_t *d_hist_a_out, int64_t *d_hist_b_out, int32_t *d_len_out, const rt_temporal_params *params = nullptr,
+                                void *stream = nullptr) {
+    rtcuda_detail::check(rt_temporal_accumulate_fixed(d_sum_a, samples_a, d_sum_b, samples_b, d_aov_fixed, aov_samples, d_motion, d_hist_a_in,
+                                                      d_hist_b_in, d_len_in, d_prev_aov_fixed, prev_aov_samples, width, height, params,
+                                                      d_hist_a_out, d_hist_b_out, d_len_out, stream), "temporal_accumulate");
+}
+
 // A driver that must keep the reference's exact call (main.cu:173) can still reach several GPUs: RTCUDA_DEVICES="0,1,2,3" in
 // the environment sends the seven-argument render() below through the multi-device path (rt_render_multi).
 inline std::vector<int> devices_from_env() {

@@ -566,6 +566,105 @@ int rt_denoise_dual_fixed(const int64_t *d_sum_a, int samples_a, const int64_t *
                           const rt_denoise_dual_params *params /* NULL = defaults */, void *d_scratch,
                           float *d_rgb_out /* width * height * 3 */, void *stream);
 
+/* ---- temporal accumulation: a motion buffer and the reprojected history ----------------------------------------------------------
+ * The temporal part of SVGF (Schied et al. 2017) for a sequence of frames: where the surface point under a pixel was one frame ago
+ * (rt_render_motion), and the blend of the new frame into the history found there (rt_temporal_accumulate_fixed).  No reference
+ * counterpart.  THE ACCUMULATED FRAME HAS THE FORMAT OF A RENDERED FRAME: int64 sums in units of 2^-30 that stand for ONE sample
+ * of the accumulated mean, so both denoisers run on it unchanged with num_samples = 1, and two half frames accumulated with the
+ * same taps and weights stay two independent estimates of one mean: rt_denoise_dual_fixed(hist_a, 1, hist_b, 1, ...) sees the
+ * variance shrink as the history grows.  The loop of one frame:
+ *     rt_render_shard_fixed  (RT_FLAG_RNG_PER_SAMPLE, shards (0, 2) and (1, 2) into two zeroed buffers, a new seed per frame)
+ *       -> rt_render_aov_fixed
+ *       -> rt_render_motion
+ *       -> rt_temporal_accumulate_fixed
+ *       -> rt_denoise_dual_fixed(hist_a_out, 1, hist_b_out, 1, aov, ...)
+ * (with one buffer the last stage is rt_denoise_fixed(hist_a_out, 1, ...)); the `out` buffers of frame N, and its AOV sums, are
+ * the `in` buffers of frame N + 1: the caller ping-pongs two sets.
+ * Both definitions are ONE STATED SEQUENCE of individually rounded fp32 operations (no FMA), every max or min a comparison and
+ * selection, dot(a, b) = (a.x * b.x + a.y * b.y) + a.z * b.z as everywhere, cross as rt_device.h's (a.y * b.z - a.z * b.y, ...);
+ * the kernels, the CPU twins (hc_motion_records, hc_temporal_accumulate of librt_hostcheck.so: rt_temporal.h is their shared
+ * arithmetic) and the numpy restatement of the tests agree in every bit.
+ *
+ * rt_render_motion.  Pixel p = py * width + px of d_motion (width * height records of 4 floats, 16-byte aligned):
+ *   1. THE RAY is camera.get_ray((px + 0.5f) / width, (py + 0.5f) / height): the operations of rt_render_aov_fixed's ray with
+ *      both jitters equal to 0.5f.  No stream is drawn.
+ *   2. THE HIT is the closest hit with tmax = FLT_MAX under `flags`, exactly as rt_query_closest_device defines it: 0,
+ *      RT_FLAG_REFERENCE_WALK or RT_FLAG_WATERTIGHT; RT_FLAG_TIME_KERNELS is accepted and changes nothing; both hit flags
+ *      together, or any other bit, is an error.  Both tree widths are served.
+ *   3. A MISS writes {0.f, 0.f, 0.f, the bits of int32 -1}.
+ *   4. A HIT on triangle k (the caller's order) with barycentrics (u, v): the PREVIOUS position of that surface point is
+ *      tri_point on the previous vertices q0, q1, q2 = row k of d_prev_tri_p0p1p2: e1 = q0 - q1, e2 = q2 - q0 per component, then
+ *      P = (q0 - e1 * u) + e2 * v.  With d_prev_tri_p0p1p2 NULL (the vertices did not move) the scene's own stored record
+ *      {p0, e1, e2} is used: the same operations on the current vertices.
+ *   5. THE PROJECTION into prev_camera (primed: its fields):  a = P - lookfrom';  A = upper_left' - lookfrom';
+ *      m = cross(horizontal', vertical');  lam = dot(A, m) / dot(a, m);  r = a * lam - A;
+ *      sx = (dot(r, horizontal') / dot(horizontal', horizontal')) * float(width);
+ *      sy = (dot(r, vertical') / dot(vertical', vertical')) * float(height);  dist = sqrt(dot(a, a)).
+ *   6. VALIDITY: if lam > 0 and lam is finite the record is {sx, sy, dist, the bits of k}; otherwise the point is behind or beside
+ *      the previous pinhole and the record is {-1.f, -1.f, dist, the bits of k}.
+ *   7. sx and sy are continuous pixel coordinates: the centre of pixel (x, y) is (x + 0.5, y + 0.5).
+ * Every record is written with a plain store.  stats (may be NULL) is filled as rt_render_aov_fixed fills it, for width * height
+ * rays.  The contract is the AOV entry points': device buffers on the scene's device, ordered on `stream` (NULL = default stream)
+ * and synchronous on it at return, the current device left as it was, nothing allocated on the steady path -- the scratch words,
+ * the overflow stacks and the timing events belong to the scene's query state, so MOTION CALLS, QUERIES AND AOV CALLS OF ONE SCENE
+ * TAKE TURNS -- and a camera whose lookfrom lies outside the radius the records are padded for widens the padding once.
+ * ERRORS return non-zero, begin "rt_render_motion: " in rt_last_error() and write nothing: a null scene, camera, prev_camera or
+ * d_motion; width or height < 1; more than 715827882 pixels; the flags above; a d_motion that is not 16-byte aligned.  (Previous
+ * vertices are read by the caller's index, so a 2-wide RT_BVH_WIDE=0 scene serves them too.)
+ * OUT OF SCOPE: ray-table cameras; a previous triangle set of another count (d_prev_tri_p0p1p2 has the scene's count); following
+ * mirror or glass to the first diffuse vertex (the record is the first hit's, as the AOVs' are).
+ *
+ * rt_temporal_accumulate_fixed.  Per pixel p = (x, y), for each supplied colour buffer k in {a, b} (d_sum_b, d_hist_b_in -- when
+ * history is given -- and d_hist_b_out are NULL together):
+ *   1. INPUTS.  c_k = float(double(sum_k) * 2^-30) * (1.f / samples_k) per channel.  n_p is the mean normal of this frame's AOV
+ *      sums, exactly as rt_aov_resolve forms it for aov_samples.  (sx, sy, dist, tri) is the pixel's motion record.
+ *   2. NO HISTORY: the output is to_fixed(c_k) per channel and len = 1 when the history pointers are NULL (the first frame), when
+ *      tri < 0, or when step 3 leaves sw = 0.
+ *   3. TAPS.  fx = sx - 0.5f, fy = sy - 0.5f.  Unless fx >= -1.f, fx < float(width), fy >= -1.f and fy < float(height) all hold
+ *      there is no history (so a NaN gives none).  x0 = floor(fx), ax = fx - x0, likewise y0 and ay.  The four taps are
+ *      q = (x0 + i, y0 + j), j outer and i inner, with the weight b = (i ? ax : 1.f - ax) * (j ? ay : 1.f - ay).  A tap is
+ *      ACCEPTED when it lies inside the image, len_in[q] >= 1, the previous AOV sums at q have hits > 0, the resolved mean depth
+ *      z_q there (sum / float(hits)) has, with dz = z_q - dist, (dz < 0 ? -dz : dz) <= depth_tolerance * dist, and
+ *      dot(n_p, n_q) >= normal_cos_min with n_q resolved from the previous AOV sums with prev_aov_samples.  Over the accepted
+ *      taps in order, from 0.f: sw = sw + b, and per channel and buffer sh_k = sh_k + b * h, h = float(double(hist_k_in[q]) * 2^-30).
+ *      N_prev is the minimum of len_in[q] over the accepted taps (a tap of weight 0 counts).
+ *   4. BLEND, when sw > 0: hbar_k = sh_k / sw; N = min(N_prev + 1, max_history); alpha = 1.f / float(N), then
+ *      alpha = alpha > alpha_min ? alpha : alpha_min; out_k = (c_k - hbar_k) * alpha + hbar_k; hist_k_out = to_fixed(out_k) and
+ *      len_out = N.
+ * to_fixed is the kernels' own: magnitudes clamped at 2^31, NaN to 0, x * 2^30 rounded to the nearest integer, ties to even.
+ * FINITENESS.  All inputs are finite sums: |c|, |h| <= 2^33.  ax and ay lie in [0, 1] (fx - floor(fx) is exact or rounds to 1),
+ * so every b lies in [0, 1]; a motion coordinate is a float, so a b that is not 0 is at least 2^-50 and so is sw, while
+ * |sh| <= 4 * 2^33: hbar is a convex mean of the taps' h up to rounding, and the blend of two finite values with alpha in
+ * (0, 1] is finite.  A dist that is NaN or infinite fails the depth stop of every tap.  No NaN can arise.
+ * Every pixel of every output buffer is written; inputs are only read.  An output buffer that overlaps any input range (or
+ * another output) is an argument error.  rt_temporal_params: NULL = the defaults, which rt_temporal_default_params writes (chosen
+ * on the CPU against 1024-spp frames: profiles/temporal_quality.json).
+ * The contract is the denoisers': device buffers on the current device, ordered on `stream` and synchronous on it at return, the
+ * current device left as it was, nothing allocated.  ERRORS return non-zero, begin "rt_temporal_accumulate_fixed: " in
+ * rt_last_error() and write nothing: a null d_sum_a, d_aov_fixed, d_motion, d_hist_a_out or d_len_out; width or height < 1 or more
+ * than 715827882 pixels; samples_a, aov_samples, samples_b (with d_sum_b) or prev_aov_samples (with history) < 1; d_sum_b and
+ * d_hist_b_out not NULL together; d_hist_a_in, d_len_in and d_prev_aov_fixed (and d_hist_b_in with d_sum_b) not all NULL or all
+ * set; a d_motion that is not 16-byte aligned; flags != 0; max_history < 1; alpha_min outside (0, 1]; a depth_tolerance that is
+ * not finite and positive; normal_cos_min outside [-1, 1]; an overlap; a frame so narrow or so flat that it needs more than
+ * 16777215 workgroups of 32 x 8 pixels. */
+int rt_render_motion(const rt_scene *scene, const rt_camera *camera, int width, int height, const rt_camera *prev_camera,
+                     const float *d_prev_tri_p0p1p2 /* n_tris x 9, caller's order; NULL = vertices did not move */, uint32_t flags,
+                     float *d_motion /* width * height x 4 */, void *stream, rt_stats *stats /* may be NULL */);
+typedef struct rt_temporal_params {
+    int32_t max_history;      /* >= 1: the history length is capped here */
+    float   alpha_min;        /* in (0, 1]: floor of the blend factor */
+    float   depth_tolerance;  /* > 0, finite: relative */
+    float   normal_cos_min;   /* in [-1, 1] */
+    uint32_t flags;           /* must be 0 */
+} rt_temporal_params;
+int rt_temporal_default_params(rt_temporal_params *out);
+int rt_temporal_accumulate_fixed(const int64_t *d_sum_a, int samples_a, const int64_t *d_sum_b /* may be NULL */, int samples_b,
+                                 const int64_t *d_aov_fixed, int aov_samples, const float *d_motion,
+                                 const int64_t *d_hist_a_in, const int64_t *d_hist_b_in, const int32_t *d_len_in /* all NULL = first frame */,
+                                 const int64_t *d_prev_aov_fixed, int prev_aov_samples, int width, int height,
+                                 const rt_temporal_params *params /* NULL = defaults */, int64_t *d_hist_a_out,
+                                 int64_t *d_hist_b_out /* NULL iff d_sum_b is */, int32_t *d_len_out, void *stream);
+
 /* ---- ray queries (no reference counterpart: its Bvh::traverse is reachable only from render()) ----------------------------
  * "Trace my rays, from my buffers, on my stream."  All pointers are DEVICE buffers on the scene's device (a buffer on another
  * device or on the host cannot be told apart from a good one: the call faults instead of failing); origins and directions are

@@ -41,6 +41,7 @@ EXPORTS = [
     "rt_render_aov_fixed", "rt_render_aov_rays_fixed_device", "rt_aov_resolve",
     "rt_denoise_scratch_bytes", "rt_denoise_default_params", "rt_denoise_fixed",
     "rt_denoise_dual_scratch_bytes", "rt_denoise_dual_default_params", "rt_denoise_dual_fixed",
+    "rt_render_motion", "rt_temporal_default_params", "rt_temporal_accumulate_fixed",
     "rt_xorwow_states", "rt_shutdown", "rt_peer_access_log", "rt_last_error", "rt_version", "rt_build_id",
 ]
 # the lab (include/rtcuda_amd_tools.h, librtcuda_amd_tools.so): measurement tools, not part of the drop-in C-ABI
@@ -83,6 +84,11 @@ class RtDenoiseParams(ctypes.Structure):
 class RtDenoiseDualParams(ctypes.Structure):
     _fields_ = [("passes", ctypes.c_int32), ("sigma_variance", ctypes.c_float), ("sigma_depth", ctypes.c_float),
                 ("normal_power_log2", ctypes.c_int32), ("flags", ctypes.c_uint32)]
+
+
+class RtTemporalParams(ctypes.Structure):
+    _fields_ = [("max_history", ctypes.c_int32), ("alpha_min", ctypes.c_float), ("depth_tolerance", ctypes.c_float),
+                ("normal_cos_min", ctypes.c_float), ("flags", ctypes.c_uint32)]
 
 
 def build(verbose: bool = False) -> str:
@@ -184,6 +190,10 @@ def _bind(L):
     L.rt_denoise_dual_scratch_bytes.restype = ctypes.c_int64
     L.rt_denoise_dual_default_params.argtypes = [ctypes.POINTER(RtDenoiseDualParams)]
     L.rt_denoise_dual_fixed.argtypes = [vp, ci, vp, ci, vp, ci, ci, ci, ctypes.POINTER(RtDenoiseDualParams), vp, vp, vp]
+    L.rt_render_motion.argtypes = [vp, vp, ci, ci, vp, vp, ctypes.c_uint32, vp, vp, ctypes.POINTER(RtStats)]
+    L.rt_temporal_default_params.argtypes = [ctypes.POINTER(RtTemporalParams)]
+    L.rt_temporal_accumulate_fixed.argtypes = [vp, ci, vp, ci, vp, ci, vp, vp, vp, vp, vp, ci, ci, ci, ctypes.POINTER(RtTemporalParams),
+                                               vp, vp, vp, vp]
     L.rt_trace_closest.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp]
     L.rt_trace_any.argtypes = [vp, ci, vp, vp, vp, vp, vp]
     L.rt_trace_closest_flags.argtypes = [vp, ctypes.c_uint32, ci, vp, vp, vp, vp, vp, vp, vp]
@@ -656,6 +666,47 @@ class Scene:
                                                       ctypes.byref(st)), "rt_render_aov_rays_fixed_device", self.L)
         return out, ids, st.as_dict()
 
+    # ---- where every pixel's first hit was one frame ago (rt_render_motion)
+    def render_motion(self, camera: np.ndarray, width: int, height: int, prev_camera: np.ndarray, prev_tris=None, flags: int = 0,
+                      out=None, stream=None):
+        """The motion buffer of the camera's frame -> (records, stats): a (width * height, 4) float32 tensor on the current
+        device, per pixel {sx, sy, dist, bits of the hit triangle}: where the first hit of the ray through the pixel centre lay
+        in ``prev_camera``'s image (continuous pixel coordinates; -1, -1 when it was behind that camera), its distance from
+        that camera, and the triangle in the caller's order (``records[:, 3].view(torch.int32)``; -1 and zeros on a miss).
+        ``prev_tris``: the vertices of one frame ago, an (n_tris, 9) or (n_tris, 3, 3) float32 tensor on the scene's device, or
+        None when they did not move.  ``flags``: 0, FLAG_REFERENCE_WALK or FLAG_WATERTIGHT.  ``out``: the tensor to fill."""
+        import torch
+        what = "render_motion"
+        for name, v in (("width", width), ("height", height)):
+            if not isinstance(v, int) or isinstance(v, bool) or v < 1:
+                raise RtError(f"{what}: {name} must be a positive int, it is {v!r}")
+        cams = []
+        for name, c in (("camera", camera), ("prev_camera", prev_camera)):
+            c = np.ascontiguousarray(c, np.float32)
+            if c.shape != (12,):
+                raise RtError(f"{what}: {name} must be the 12 floats of make_camera(), it has shape {c.shape}")
+            cams.append(c)
+        n = width * height
+        if out is None:
+            out = torch.empty((n, 4), dtype=torch.float32, device=torch.device("cuda", torch.cuda.current_device()))
+        elif not isinstance(out, torch.Tensor) or not out.is_cuda:
+            raise RtError(f"{what}: out must be a torch tensor on the scene's GPU")
+        elif out.dtype != torch.float32 or tuple(out.shape) != (n, 4) or not out.is_contiguous():
+            raise RtError(f"{what}: out must be a contiguous ({n}, 4) torch.float32 tensor, it is {tuple(out.shape)} {out.dtype}")
+        if prev_tris is not None:
+            if not isinstance(prev_tris, torch.Tensor) or not prev_tris.is_cuda or prev_tris.device != out.device:
+                raise RtError(f"{what}: prev_tris must be a torch tensor on the scene's GPU")
+            nt = self.n_tris()
+            if prev_tris.dtype != torch.float32 or tuple(prev_tris.shape) not in ((nt, 9), (nt, 3, 3)) or not prev_tris.is_contiguous():
+                raise RtError(f"{what}: prev_tris must be a contiguous ({nt}, 9) or ({nt}, 3, 3) torch.float32 tensor, it is "
+                              f"{tuple(prev_tris.shape)} {prev_tris.dtype}")
+        s = torch.cuda.current_stream(out.device) if stream is None else stream
+        c = ctypes.c_void_p
+        st = RtStats()
+        _check(self.L.rt_render_motion(self.h, _p(cams[0]), width, height, _p(cams[1]), c(None if prev_tris is None else prev_tris.data_ptr()),
+                                       flags, c(out.data_ptr()), c(s.cuda_stream or None), ctypes.byref(st)), "rt_render_motion", self.L)
+        return out, st.as_dict()
+
     # ---- ray queries on device buffers (rt_query_*_device)
     def query_closest_device(self, o_ptr: int, d_ptr: int, tmax_ptr: int, n: int, hit_ptr: int, t_ptr: int = 0, u_ptr: int = 0,
                              v_ptr: int = 0, flags: int = 0, stream: int = 0) -> None:
@@ -932,6 +983,87 @@ def denoise_dual(beauty_a, spp_a: int, beauty_b, spp_b: int, aov_sums, aov_spp: 
                                            ctypes.c_void_p(scratch.data_ptr()), ctypes.c_void_p(out.data_ptr()),
                                            ctypes.c_void_p(s.cuda_stream or None)), "rt_denoise_dual_fixed")
     return out
+
+
+def temporal_default_params() -> dict:
+    """The parameters rt_temporal_accumulate_fixed uses when it is given none (rt_temporal_default_params)."""
+    prm = RtTemporalParams()
+    _check(lib().rt_temporal_default_params(ctypes.byref(prm)), "rt_temporal_default_params")
+    return {"max_history": int(prm.max_history), "alpha_min": float(prm.alpha_min), "depth_tolerance": float(prm.depth_tolerance),
+            "normal_cos_min": float(prm.normal_cos_min)}
+
+
+def temporal_accumulate(beauty_a, spp_a: int, beauty_b, spp_b: int, aov_sums, aov_spp: int, motion, history, width: int, height: int, *,
+                        max_history=None, alpha_min=None, depth_tolerance=None, normal_cos_min=None, out=None, stream=None):
+    """This frame blended into the reprojected history (rt_temporal_accumulate_fixed) -> (hist_a, hist_b or None, length).
+    ``beauty_a`` / ``beauty_b``: (h * w, 3) int64 fixed-point sums of ``spp_a`` / ``spp_b`` samples (``beauty_b`` may be None: one
+    buffer); ``aov_sums``: (h * w, 11) int64 of this frame, ``aov_spp`` samples; ``motion``: (h * w, 4) float32, as
+    Scene.render_motion leaves it.  ``history``: None on the first frame, else the tuple (hist_a, hist_b or None, length,
+    prev_aov_sums, prev_aov_spp) of the previous call's results and the previous frame's AOV sums.  The results are (h * w, 3)
+    int64 sums that stand for ONE sample of the accumulated mean -- denoise(hist_a, 1, ...) and denoise_dual(hist_a, 1, hist_b, 1,
+    ...) take them as they are -- and the (h * w,) int32 history length per pixel.  ``out``: a tuple (hist_a, hist_b or None,
+    length) of tensors to fill, none of which may be an input (ping-pong two sets).  Parameters left at None are the library's
+    defaults (temporal_default_params)."""
+    import torch
+    me = "temporal_accumulate"
+    two = beauty_b is not None
+    _dn_positive_ints(me, (("width", width), ("height", height), ("spp_a", spp_a), ("aov_spp", aov_spp)) + ((("spp_b", spp_b),) if two else ()))
+    n = width * height
+    named = [("beauty_a", beauty_a, 3)] + ([("beauty_b", beauty_b, 3)] if two else []) + [("aov_sums", aov_sums, AOV_CHANNELS)]
+    hist_a = hist_b = length = prev_aov = None
+    prev_spp = 1
+    if history is not None:
+        if not isinstance(history, (tuple, list)) or len(history) != 5:
+            raise RtError(f"{me}: history must be None or (hist_a, hist_b or None, length, prev_aov_sums, prev_aov_spp)")
+        hist_a, hist_b, length, prev_aov, prev_spp = history
+        if (hist_b is not None) != two:
+            raise RtError(f"{me}: history's hist_b and beauty_b must be None together")
+        _dn_positive_ints(me, (("prev_aov_spp", prev_spp),))
+        named += [("history hist_a", hist_a, 3)] + ([("history hist_b", hist_b, 3)] if two else []) + [("history prev_aov_sums", prev_aov, AOV_CHANNELS)]
+    device = _dn_sums(me, n, tuple(named))
+
+    def plain(name, t, dtype, shape):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != device:
+            raise RtError(f"{me}: {name} must be a torch tensor on the GPU of the sums")
+        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+            raise RtError(f"{me}: {name} must be a contiguous {shape} {dtype} tensor, it is {tuple(t.shape)} {t.dtype}")
+
+    plain("motion", motion, torch.float32, (n, 4))
+    if history is not None:
+        plain("history length", length, torch.int32, (n,))
+    prm = RtTemporalParams()
+    _check(lib().rt_temporal_default_params(ctypes.byref(prm)), "rt_temporal_default_params")
+    if max_history is not None:
+        if not isinstance(max_history, int) or isinstance(max_history, bool) or not 1 <= max_history <= 0x7FFFFFFF:
+            raise RtError(f"{me}: max_history must be an int in 1 .. 2^31 - 1, it is {max_history!r}")
+        prm.max_history = max_history
+    for name, v in (("alpha_min", alpha_min), ("depth_tolerance", depth_tolerance), ("normal_cos_min", normal_cos_min)):
+        if v is not None:
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.floating)) or not np.isfinite(v):
+                raise RtError(f"{me}: {name} must be a finite number, it is {v!r}")
+            setattr(prm, name, float(v))
+    if out is None:
+        out = (torch.empty((n, 3), dtype=torch.int64, device=device), torch.empty((n, 3), dtype=torch.int64, device=device) if two else None,
+               torch.empty(n, dtype=torch.int32, device=device))
+    else:
+        if not isinstance(out, (tuple, list)) or len(out) != 3 or (out[1] is not None) != two:
+            raise RtError(f"{me}: out must be (hist_a, hist_b or None as beauty_b, length)")
+        _dn_sums(me, n, tuple([("out hist_a", out[0], 3)] + ([("out hist_b", out[1], 3)] if two else [])))
+        plain("out length", out[2], torch.int32, (n,))
+        if out[0].device != device:
+            raise RtError(f"{me}: out is on {out[0].device}, beauty_a on {device}")
+    s = torch.cuda.current_stream(device) if stream is None else stream
+    c = ctypes.c_void_p
+
+    def ptr(t):
+        return c(None if t is None else t.data_ptr())
+
+    with torch.cuda.device(device):
+        _check(lib().rt_temporal_accumulate_fixed(ptr(beauty_a), spp_a, ptr(beauty_b), spp_b if two else 0, ptr(aov_sums), aov_spp, ptr(motion),
+                                                  ptr(hist_a), ptr(hist_b), ptr(length), ptr(prev_aov), prev_spp, width, height,
+                                                  ctypes.byref(prm), ptr(out[0]), ptr(out[1]), ptr(out[2]), c(s.cuda_stream or None)),
+               "rt_temporal_accumulate_fixed")
+    return tuple(out)
 
 
 def xorwow_states(seed: int, first: int, count: int, draws: int = 0):

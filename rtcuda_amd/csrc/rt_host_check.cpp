@@ -33,6 +33,7 @@
 #include "rt_ref_tree.h"
 #include "rt_slot_chunks.h"
 #include "rt_stats_merge.h"
+#include "rt_temporal.h"
 
 namespace {
 struct V3 { float x, y, z; };
@@ -1060,6 +1061,52 @@ int hc_denoise_dual(const int64_t *sum_a, int samples_a, const int64_t *sum_b, i
         dn_finish(&uv[4 * p], px[p].d, px[p].e, rgb_out + 3 * p);
         if (var_out) var_out[p] = uv[4 * p + 3];
     }
+    return 0;
+}
+// The CPU twin of k_motion's finish (tests/test_temporal_host.py, tools/temporal_quality.py): the previous position and the
+// projection of rt_render_motion on GIVEN hits -- tri (the caller's order, < 0: a miss), u, v per pixel; the hits themselves are
+// the walk's and are pinned elsewhere.  prev_tris: n_tris x 9, the vertices of one frame ago (pass the current ones when nothing
+// moved: tri_point on a row is the operations of the scene's stored record).  Returns 0, or 1 and writes nothing.
+int hc_motion_records(int n, const int32_t *tri, const float *u, const float *v, const float *prev_tris, int n_tris, const float *prev_cam12,
+                      int width, int height, float *motion4) {
+    if (n < 0 || !tri || !u || !v || !prev_tris || !prev_cam12 || !motion4 || width < 1 || height < 1) return 1;
+    for (int p = 0; p < n; p++)
+        if (tri[p] >= n_tris) return 1;
+    TmCamera c;
+    tm_camera(prev_cam12, width, height, &c);
+    for (int p = 0; p < n; p++) {
+        float *rec = motion4 + 4 * (size_t)p;
+        const int32_t k = tri[p] < 0 ? -1 : tri[p];
+        rec[0] = rec[1] = rec[2] = 0.f;
+        if (k >= 0) {
+            float P[3];
+            tm_point_of_vertices(prev_tris + 9 * (size_t)k, u[p], v[p], P);
+            tm_project(&c, P, rec);
+        }
+        memcpy(rec + 3, &k, 4);
+    }
+    return 0;
+}
+// The CPU twin of rt_temporal_accumulate_fixed: a serial loop over rt_temporal.h, host buffers throughout, the same checks of the
+// parameters (not the overlap check: the caller's).  Returns 0, or 1 and writes nothing.
+int hc_temporal_accumulate(const int64_t *sum_a, int samples_a, const int64_t *sum_b, int samples_b, const int64_t *aov_fixed, int aov_samples,
+                           const float *motion4, const int64_t *hist_a_in, const int64_t *hist_b_in, const int32_t *len_in,
+                           const int64_t *prev_aov_fixed, int prev_aov_samples, int width, int height, int max_history, float alpha_min,
+                           float depth_tolerance, float normal_cos_min, int64_t *hist_a_out, int64_t *hist_b_out, int32_t *len_out) {
+    if (!sum_a || !aov_fixed || !motion4 || !hist_a_out || !len_out || width < 1 || height < 1 || samples_a < 1 || aov_samples < 1) return 1;
+    const bool two = sum_b != nullptr, history = hist_a_in != nullptr;
+    if (two != (hist_b_out != nullptr) || (two && samples_b < 1)) return 1;
+    if (!history && (hist_b_in || len_in || prev_aov_fixed)) return 1;
+    if (history && (!len_in || !prev_aov_fixed || prev_aov_samples < 1 || two != (hist_b_in != nullptr))) return 1;
+    if (max_history < 1 || !(alpha_min > 0.f && alpha_min <= 1.f) || !(std::isfinite(depth_tolerance) && depth_tolerance > 0.f)) return 1;
+    if (!(normal_cos_min >= -1.f && normal_cos_min <= 1.f)) return 1;
+    const float inv_a = 1.f / (float)samples_a, inv_b = two ? 1.f / (float)samples_b : 0.f, inv_aov = 1.f / (float)aov_samples;
+    const float inv_prev = history ? 1.f / (float)prev_aov_samples : 0.f;
+    for (int y = 0; y < height; y++)
+        for (int x = 0; x < width; x++)
+            tm_accumulate_pixel(x, y, width, height, sum_a, inv_a, sum_b, inv_b, aov_fixed, inv_aov, motion4 + 4 * ((size_t)y * width + x), hist_a_in,
+                                hist_b_in, len_in, prev_aov_fixed, inv_prev, max_history, alpha_min, depth_tolerance, normal_cos_min, hist_a_out,
+                                hist_b_out, len_out);
     return 0;
 }
 // The stats of a frame from its n shards' (rt_stats_merge.h), as RT_SPLIT (sub_shards != 0) and rt_render_multi merge them

@@ -897,7 +897,7 @@ static int render_rays_keyed_impl(const rt_scene *scene, int64_t n_rays, const f
     return 0;
 }
 
-// rt_render_aov_fixed / rt_render_aov_rays_fixed_device: the entry points check their arguments (and, for a table, run the
+// rt_render_aov_fixed / rt_render_aov_rays_fixed_device / rt_render_motion: the entry points check their arguments (and, for a table, run the
 // device prepasses) and hand the ray source over; this is the one body behind both -- the reference's tree where the hit
 // definition needs it, the overflow stacks, the launch sized from the device, the kernel's time and the rare-path counters.
 // The caller holds the scene's query lock and has entered the scene's device; q.d_words is zeroed on `st`.
@@ -914,25 +914,19 @@ static int aov_flags(const std::string &w, uint32_t flags) {
         return fail(w + ": flags other than RT_FLAG_WATERTIGHT / RT_FLAG_REFERENCE_WALK / RT_FLAG_TIME_KERNELS");
     return refuse_both_hit_flags(w, flags);
 }
-template <class SRC>
-static int aov_launch(const rt_scene *scene, const SRC &src, int n, uint32_t flags, int64_t *d_aov, int32_t *d_ids, hipStream_t st,
-                      rt_stats *stats) {
+// The launch behind the AOV entry points and rt_render_motion: `kernel` is a stream-walker kernel, launch(grid, lds, stack_cap,
+// overflow) enqueues it with its own parameters (which hold q.d_words->vstat), n is the number of rays.
+template <class KERNEL, class LAUNCH>
+static int walker_launch(const rt_scene *scene, const HitMode &mode, KERNEL kernel, int n, hipStream_t st, rt_stats *stats, LAUNCH launch) {
     rt_scene::QueryState &q = scene->query;
-    const HitMode mode = hit_mode(flags);
     if (mode.ref_tree() && ensure_ref_tree(scene)) return 1;
     const int stack_cap = lds_stack_cap(scene, kLdsStack);
     if (ensure_overflow(q.d_over, q.over_levels, std::max(scene->stack_bound, 32) - stack_cap)) return 1;
-    AovParams ap{};
-    ap.n = n;
-    ap.sums = (unsigned long long *)d_aov;
-    ap.ids = d_ids;
-    ap.vstat = q.d_words->vstat;
-    const AovKernel<SRC> kernel = aov_kernel<SRC>(mode.literal, mode.verify, scene->wide);
     const size_t lds = sizeof(int) * kBlock * (size_t)(stack_cap + 1);
     int grid = 0;
     if (resident_grid(kernel, lds, q.cus, n, &grid)) return 1;
     HIP_TRY(hipEventRecord(q.ev_a, st));
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, st, scene->dev(), src, ap, stack_cap, q.d_over);
+    launch(grid, lds, stack_cap, q.d_over);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(q.ev_b, st));
     HIP_TRY(hipMemcpyAsync(q.h_words->vstat, q.d_words->vstat, sizeof(q.h_words->vstat), hipMemcpyDeviceToHost, st));
@@ -951,6 +945,20 @@ static int aov_launch(const rt_scene *scene, const SRC &src, int n, uint32_t fla
         rare_path_counters(q.h_words->vstat, &stats->reserved[4]);
     }
     return 0;
+}
+template <class SRC>
+static int aov_launch(const rt_scene *scene, const SRC &src, int n, uint32_t flags, int64_t *d_aov, int32_t *d_ids, hipStream_t st,
+                      rt_stats *stats) {
+    const HitMode mode = hit_mode(flags);
+    AovParams ap{};
+    ap.n = n;
+    ap.sums = (unsigned long long *)d_aov;
+    ap.ids = d_ids;
+    ap.vstat = scene->query.d_words->vstat;
+    const AovKernel<SRC> kernel = aov_kernel<SRC>(mode.literal, mode.verify, scene->wide);
+    return walker_launch(scene, mode, kernel, n, st, stats, [&](int grid, size_t lds, int stack_cap, int *d_over) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, st, scene->dev(), src, ap, stack_cap, d_over);
+    });
 }
 
 static int render_aov_impl(const rt_scene *scene, const rt_camera *camera, int width, int height, int spp, uint64_t seed,
@@ -1006,5 +1014,45 @@ static int render_aov_rays_impl(const rt_scene *scene, int64_t n_rays, const flo
     if (ensure_query_state(scene, true)) return 1;
     if (int rc = validate_table(scene, w, (int)n_rays, d_o, d_d, d_pixel, n_pixels, st)) return rc;
     return aov_launch(scene, src, (int)n_rays, flags, d_aov, d_ids, st, stats);
+}
+
+// rt_render_motion: the AOV entry point's checks where they apply, the same query state and launch, k_motion's parameters.
+using MotionKernel = void (*)(DScene, MotionParams, int, int *);
+static MotionKernel motion_kernel(bool literal, bool verify, bool wide) {
+    if (literal) return k_motion<false, true, false>;
+    if (verify) return wide ? k_motion<true, false, true> : k_motion<false, false, true>;
+    return wide ? k_motion<true, false, false> : k_motion<false, false, false>;
+}
+static int render_motion_impl(const rt_scene *scene, const rt_camera *camera, int width, int height, const rt_camera *prev_camera,
+                              const float *d_prev_tris, uint32_t flags, float *d_motion, hipStream_t st, rt_stats *stats) {
+    const std::string w("rt_render_motion");
+    if (!scene) return fail(w + ": null scene");
+    if (!camera || !prev_camera || !d_motion) return fail(w + ": null " + (!camera ? "camera" : !prev_camera ? "prev_camera" : "d_motion"));
+    if (aov_flags(w, flags)) return 1;
+    if (width < 1 || height < 1)
+        return fail(w + ": width and height must be at least 1 (" + std::to_string(width) + " x " + std::to_string(height) + ")");
+    if ((long long)width * height > (long long)(0x7fffffff / 3)) return fail(w + ": width*height exceeds 715827882 pixels");
+    if ((uintptr_t)d_motion % 16) return fail(w + ": d_motion must be 16-byte aligned");
+    DeviceGuard dev;
+    if (dev.enter(scene->device)) return 1;
+    if (int rc = ensure_origin_radius(scene, camera->lookfrom)) return rc;  // (camera rays start at lookfrom: as render_shard_impl)
+    rt_scene::QueryState &q = scene->query;
+    std::lock_guard<std::mutex> lock(q.mutex);
+    if (ensure_query_state(scene, true)) return 1;
+    HIP_TRY(hipMemsetAsync(q.d_words, 0, sizeof(QueryWords), st));
+    const HitMode mode = hit_mode(flags);
+    MotionParams mp{};
+    memcpy(&mp.cam, camera, sizeof(Camera));
+    tm_camera(prev_camera->lookfrom, width, height, &mp.prev);  // (rt_camera is twelve consecutive floats)
+    mp.n = width * height;
+    mp.width = width;
+    mp.height = height;
+    mp.prev_tris = d_prev_tris;
+    mp.out = (float4 *)d_motion;
+    mp.vstat = q.d_words->vstat;
+    const MotionKernel kernel = motion_kernel(mode.literal, mode.verify, scene->wide);
+    return walker_launch(scene, mode, kernel, mp.n, st, stats, [&](int grid, size_t lds, int stack_cap, int *d_over) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, st, scene->dev(), mp, stack_cap, d_over);
+    });
 }
 

@@ -1,6 +1,6 @@
 // rt_stream_kernels.inc -- the kernels that walk a stream of rays: k_trace (the pools of a round), the query prepasses, the
-// stream walker of every dense ray array with its two kernels, k_query (rays from device buffers: the queries and their
-// host-pointer form, the trace hooks) and k_aov (first-hit feature buffers).  Included by rtcuda_amd.hip, once, after rt_walk.inc.
+// stream walker of every dense ray array with its three kernels, k_query (rays from device buffers: the queries and their
+// host-pointer form, the trace hooks), k_aov (first-hit feature buffers) and k_motion (rt_render_motion).  Included by rtcuda_amd.hip, once, after rt_walk.inc.
 struct TraceParams {
     int total;             // number of slots
     int debug_no_deposit;  // perf experiments only: skip the framebuffer atomics
@@ -626,6 +626,60 @@ template <class SRC, bool WIDE, bool LITERAL, bool VERIFY>
 __global__ void __launch_bounds__(kBlock, kQueryMinWaves) k_aov(DScene sc, SRC src, AovParams ap, int stack_cap, int *overflow) {
     AovEnds<SRC> ends{sc, src, ap};
     stream_walk<false, WIDE, LITERAL, VERIFY>(sc, ends, ap.n, ap.vstat, stack_cap, overflow);
+}
+
+// ============================================================================ k_motion: where a pixel's first hit was one frame ago
+// rt_render_motion (DESIGN.md section 2.9): the third pair of ends on the stream walker.  Ray `id` is the ray through the centre
+// of pixel `id` (the AOV ray with both jitters 0.5f, no stream drawn); a finished lane maps its hit to the caller's order, forms
+// the point (u, v) of that triangle on the PREVIOUS vertices -- row k of the caller's array, or the scene's own record when the
+// vertices did not move --, projects it into the previous camera (tm_project, rt_temporal.h: shared with the CPU twin and stated
+// in the header) and writes {sx, sy, dist, bits of k} as one 16-byte store; a miss writes {0, 0, 0, bits of -1}.
+// Nothing is carried per lane but the id.  Registers (profiles/motion_resources.md): no spill and no scratch, 74 - 77 VGPRs in the
+// 4-wide builds against k_query's 71 - 72 -- one step past the seven-wave budget, so six waves per SIMD where k_query has seven.
+struct MotionParams {
+    Camera cam;
+    TmCamera prev;             // the previous camera, prepared on the host (tm_camera)
+    int n, width, height;
+    const float *prev_tris;    // n_tris x 9 in the caller's order, or null: the scene's records
+    float4 *out;               // n records
+    unsigned long long *vstat;
+};
+struct MotionEnds {
+    const DScene &sc;
+    const MotionParams &mp;
+    __device__ __forceinline__ float restart_tmax(int) const { return kFltMax; }
+    __device__ __forceinline__ void take(int id, V3 &o, V3 &d, float &tmax, int &tri) const {
+        const int py = (int)((unsigned)id / (unsigned)mp.width);
+        const int px = id - py * mp.width;
+        camera_get_ray(mp.cam, (px + 0.5f) / mp.width, (py + 0.5f) / mp.height, o, d);
+        tmax = kFltMax;
+        tri = -1;
+    }
+    __device__ __forceinline__ void finish(bool fin, int id, V3, float, int tri, float hu, float hv) const {
+        if (!fin) return;
+        float4 rec = make_float4(0.f, 0.f, 0.f, __int_as_float(-1));
+        if (tri >= 0) {
+            const int k = sc.order[(unsigned)tri];
+            float P[3], r3[3];
+            if (mp.prev_tris) {
+                const float *q = mp.prev_tris + 9 * (size_t)(unsigned)k;
+                const float q9[9] = {q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7], q[8]};
+                tm_point_of_vertices(q9, hu, hv, P);
+            } else {
+                const Tri tr = load_tri(sc.tris, tri);
+                const float q0[3] = {tr.p0.x, tr.p0.y, tr.p0.z}, e1[3] = {tr.e1.x, tr.e1.y, tr.e1.z}, e2[3] = {tr.e2.x, tr.e2.y, tr.e2.z};
+                tm_point(q0, e1, e2, hu, hv, P);
+            }
+            tm_project(&mp.prev, P, r3);
+            rec = make_float4(r3[0], r3[1], r3[2], __int_as_float(k));
+        }
+        mp.out[(unsigned)id] = rec;
+    }
+};
+template <bool WIDE, bool LITERAL, bool VERIFY>
+__global__ void __launch_bounds__(kBlock, kQueryMinWaves) k_motion(DScene sc, MotionParams mp, int stack_cap, int *overflow) {
+    MotionEnds ends{sc, mp};
+    stream_walk<false, WIDE, LITERAL, VERIFY>(sc, ends, mp.n, mp.vstat, stack_cap, overflow);
 }
 
 // rt_aov_resolve: sums -> floats, one thread per value.  s = float(double(sum) * 2^-30) as k_post_process_fixed forms it;

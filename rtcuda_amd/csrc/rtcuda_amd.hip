@@ -3,7 +3,7 @@
 // the table builders, gen_core / advance_core, the k_paths knobs, the post-process kernels and the C-ABI.  Included, in this order:
 //   rt_walk.inc            box test, traversal stack, inner_step; reference_walk; VERIFY (ref_visible); leaf_hits, verify_closest
 //   rt_stream_kernels.inc  k_trace (the pools of a round); the query prepasses; stream_walk, the persistent loop of every dense ray
-//                          array, under k_query (queries and trace hooks) and k_aov; k_aov_resolve
+//                          array, under k_query (queries and trace hooks), k_aov and k_motion; k_aov_resolve
 //   rt_frame_kernels.inc   k_advance and k_paths, once per source of camera rays
 //   rt_build_kernels.inc   device BVH: the leaf-order arrays, the refit (k_refit_*), the build (k_ploc_*)
 //   rt_host_scene.inc      rt_scene and the one way a tree gets into it: build (host SAH, device PLOC), emit, adopt; the entry
@@ -15,6 +15,8 @@
 //   rt_denoise_kernels.inc the denoisers' kernels: one tap loop (dn_filter_pixel) and two pass bodies (dn_pass_direct, dn_pass_lds) under
 //                          k_atrous* / k_atrous_var*; prepare, finish, k_dn_var_blur (arithmetic: rt_denoise.h, shared with the CPU twin)
 //   rt_host_denoise.inc    rt_denoise_fixed and rt_denoise_dual_fixed: one set of checks (dn_check), one pass launcher, one run (dn_run)
+//   rt_temporal_kernels.inc k_temporal_accumulate (arithmetic: rt_temporal.h, shared with k_motion and the CPU twins)
+//   rt_host_temporal.inc   rt_temporal_accumulate_fixed: the checks and the launch
 // The C-ABI below them only checks arguments and forwards, and calls none of its own entry points.  Two bodies stay in it:
 // rt_camera_make (host arithmetic, nothing shared) and rt_xorwow_states (a test hook around k_rng_init / k_test_draw).
 //
@@ -87,6 +89,7 @@
 #include "rt_ref_tree.h"
 #include "rt_slot_chunks.h"
 #include "rt_stats_merge.h"
+#include "rt_temporal.h"
 
 using namespace rt;
 
@@ -732,7 +735,7 @@ __device__ __forceinline__ void advance_core(const DScene &sc, const float *tab,
 // k_advance (init() + mat() + gen() for all slots of a round) is defined with k_paths in rt_frame_kernels.inc.
 
 #include "rt_walk.inc"            // traversal: box test, stack, inner_step; reference_walk; VERIFY (ref_visible)
-#include "rt_stream_kernels.inc"  // k_trace, the query prepasses, k_query, k_aov, k_aov_resolve
+#include "rt_stream_kernels.inc"  // k_trace, the query prepasses, k_query, k_aov, k_motion, k_aov_resolve
 
 // ============================================================================ k_paths
 // The whole asynchronous part of a frame in ONE launch.  A lane owns one path slot for the entire
@@ -879,11 +882,13 @@ __global__ void k_test_draw(DPools p, int n, int draws, uint32_t *__restrict__ s
 }
 #include "rt_build_kernels.inc"   // device BVH: the leaf-order arrays, refit (k_refit_*), build (k_ploc_*)
 #include "rt_denoise_kernels.inc"  // dn_filter_pixel under k_atrous* and k_atrous_var*; k_dn_prepare*, k_dn_var_blur, k_dn_finish*
+#include "rt_temporal_kernels.inc"  // k_temporal_accumulate
 
 #include "rt_host_scene.inc"   // (opens the anonymous namespace that is closed below) rt_scene: reference tree, checks, build / emit / adopt, create, update, rebuild, edits; what the ray entry points share
 #include "rt_host_render.inc"  // Context, cached output buffers, kernel selection, one shard of a frame, queries and trace hooks, ray tables, AOVs
 #include "rt_host_frame.inc"   // whole frames: the shard fan-out (RT_SPLIT, rt_render_multi), finish_frame, rt_render, rt_render_multi
 #include "rt_host_denoise.inc"  // rt_denoise_fixed, rt_denoise_dual_fixed
+#include "rt_host_temporal.inc"  // rt_temporal_accumulate_fixed
 }  // namespace
 
 // ============================================================================ C-ABI
@@ -1120,6 +1125,27 @@ int rt_denoise_dual_fixed(const int64_t *d_sum_a, int samples_a, const int64_t *
                           float *d_rgb_out, void *stream) {
     return denoise_dual_impl(d_sum_a, samples_a, d_sum_b, samples_b, d_aov_fixed, aov_samples, width, height, params, d_scratch,
                              d_rgb_out, (hipStream_t)stream);
+}
+
+int rt_render_motion(const rt_scene *scene, const rt_camera *camera, int width, int height, const rt_camera *prev_camera,
+                     const float *d_prev_tri_p0p1p2, uint32_t flags, float *d_motion, void *stream, rt_stats *stats) {
+    return render_motion_impl(scene, camera, width, height, prev_camera, d_prev_tri_p0p1p2, flags, d_motion, (hipStream_t)stream, stats);
+}
+
+int rt_temporal_default_params(rt_temporal_params *out) {
+    if (!out) return fail("rt_temporal_default_params: null out");
+    *out = temporal_defaults();
+    return 0;
+}
+
+int rt_temporal_accumulate_fixed(const int64_t *d_sum_a, int samples_a, const int64_t *d_sum_b, int samples_b, const int64_t *d_aov_fixed,
+                                 int aov_samples, const float *d_motion, const int64_t *d_hist_a_in, const int64_t *d_hist_b_in,
+                                 const int32_t *d_len_in, const int64_t *d_prev_aov_fixed, int prev_aov_samples, int width, int height,
+                                 const rt_temporal_params *params, int64_t *d_hist_a_out, int64_t *d_hist_b_out, int32_t *d_len_out,
+                                 void *stream) {
+    return temporal_accumulate_impl(d_sum_a, samples_a, d_sum_b, samples_b, d_aov_fixed, aov_samples, d_motion, d_hist_a_in, d_hist_b_in,
+                                    d_len_in, d_prev_aov_fixed, prev_aov_samples, width, height, params, d_hist_a_out, d_hist_b_out,
+                                    d_len_out, (hipStream_t)stream);
 }
 
 int rt_post_process(float *d_rgb, int num_pixels, int num_samples, void *stream) {
