@@ -592,6 +592,34 @@ inline void temporal_accumulate(const int64_t *d_sum_a, int samples_a, const int
                                                       d_hist_a_out, d_hist_b_out, d_len_out, stream), "temporal_accumulate");
 }
 
+// The single-buffer loop (rt_temporal_accumulate_moments_fixed / rt_denoise_variance_fixed, which document both).
+// temporal_accumulate_moments: temporal_accumulate with an emission stop, a triangle stop (d_prev_motion: last frame's motion
+// buffer, or nullptr) and, with d_moments_out / d_variance_out, temporally accumulated moments (width * height * 4 floats, 16-byte
+// aligned; d_moments_in: last frame's, nullptr on the first frame) and the variance of the mean (width * height floats).
+// denoise_variance: denoise_dual's filter on ONE frame's sums and that variance; scratch and params are denoise_dual's.
+inline rt_temporal_moments_params temporal_moments_default_params() {
+    rt_temporal_moments_params p{};
+    rtcuda_detail::check(rt_temporal_moments_default_params(&p), "temporal_moments_default_params");
+    return p;
+}
+inline void temporal_accumulate_moments(const int64_t *d_sum_a, int samples_a, const int64_t *d_sum_b, int samples_b, const int64_t *d_aov_fixed,
+                                        int aov_samples, const float *d_motion, const int64_t *d_hist_a_in, const int64_t *d_hist_b_in,
+                                        const int32_t *d_len_in, const int64_t *d_prev_aov_fixed, int prev_aov_samples, const float *d_prev_motion,
+                                        const float *d_moments_in, int width, int height, int64_t *d_hist_a_out, int64_t *d_hist_b_out,
+                                        int32_t *d_len_out, float *d_moments_out, float *d_variance_out,
+                                        const rt_temporal_moments_params *params = nullptr, void *stream = nullptr) {
+    rtcuda_detail::check(rt_temporal_accumulate_moments_fixed(d_sum_a, samples_a, d_sum_b, samples_b, d_aov_fixed, aov_samples, d_motion,
+                                                              d_hist_a_in, d_hist_b_in, d_len_in, d_prev_aov_fixed, prev_aov_samples, d_prev_motion,
+                                                              d_moments_in, width, height, params, d_hist_a_out, d_hist_b_out, d_len_out,
+                                                              d_moments_out, d_variance_out, stream), "temporal_accumulate_moments");
+}
+inline void denoise_variance(const int64_t *d_sum_fixed, int num_samples, const float *d_variance, const int64_t *d_aov_fixed, int aov_samples,
+                             int width, int height, void *d_scratch, float *d_rgb_out, const rt_denoise_dual_params *params = nullptr,
+                             void *stream = nullptr) {
+    rtcuda_detail::check(rt_denoise_variance_fixed(d_sum_fixed, num_samples, d_variance, d_aov_fixed, aov_samples, width, height, params,
+                                                   d_scratch, d_rgb_out, stream), "denoise_variance");
+}
+
 // A driver that must keep the reference's exact call (main.cu:173) can still reach several GPUs: RTCUDA_DEVICES="0,1,2,3" in
 // the environment sends the seven-argument render() below through the multi-device path (rt_render_multi).
 inline std::vector<int> devices_from_env() {

@@ -665,6 +665,94 @@ int rt_temporal_accumulate_fixed(const int64_t *d_sum_a, int samples_a, const in
                                  const rt_temporal_params *params /* NULL = defaults */, int64_t *d_hist_a_out,
                                  int64_t *d_hist_b_out /* NULL iff d_sum_b is */, int32_t *d_len_out, void *stream);
 
+/* ---- temporal moments and two more stops; the dual filter fed from a variance buffer -----------------------------------------------
+ * The single-buffer form of the loop above (SVGF proper: the variance comes from temporally accumulated first and second moments
+ * of ONE frame sequence, from a spatial estimate where history is short), and stops that see an edge which depth and normal do
+ * not -- an area light in the plane of its ceiling:
+ *     rt_render_shard_fixed  (ONE call)
+ *       -> rt_render_aov_fixed
+ *       -> rt_render_motion
+ *       -> rt_temporal_accumulate_moments_fixed
+ *       -> rt_denoise_variance_fixed(hist_a_out, 1, variance_out, aov, ...)
+ * The caller ping-pongs, next to the sets of rt_temporal_accumulate_fixed, the moments and the MOTION buffer (last frame's motion
+ * buffer is "last frame's triangle ids").  Both definitions are ONE STATED SEQUENCE of individually rounded fp32 operations (no
+ * FMA), every max or min a comparison and selection, dot as everywhere; the kernels, the CPU twins (hc_temporal_accumulate_moments,
+ * hc_denoise_variance: rt_temporal.h and rt_denoise.h are the shared arithmetic) and the numpy restatement of the tests agree in
+ * every bit.
+ *
+ * rt_temporal_accumulate_moments_fixed.  rt_temporal_accumulate_fixed's steps 1 - 4 for the hist and len outputs, with:
+ *   EMISSION STOP, part of step 3's acceptance after the normal stop.  e_p[k] = float(double(aov[RT_AOV_EMISSION + k]) * 2^-30) *
+ *      (1.f / aov_samples), e_q[k] the same of the previous AOV sums at q with prev_aov_samples; a[k] = |e_p[k] - e_q[k]| (the
+ *      difference rounded, then d < 0 ? -d : d); de = a[0], then de = a[k] > de ? a[k] : de for k = 1, 2.  The tap is accepted iff
+ *      de <= emission_tolerance.  All sums are finite, so +inf accepts every tap.
+ *   TRIANGLE STOP, only with d_prev_motion: the tap is accepted iff the int32 bits of d_prev_motion[4 q + 3] equal this pixel's
+ *      tri.  (A tap's id of -1, a miss, never equals: tri >= 0 wherever taps are visited.)
+ *   MOMENTS, only with d_moments_out.  S = sum_a, or sum_a + sum_b as rt_denoise_dual_fixed's wrapping add with n = samples_a +
+ *      samples_b (n = samples_a with one buffer).  u_p is steps 1 and 2 of rt_denoise_fixed for (S, n) and this frame's AOV sums.
+ *      The frame's moments are f = {u.x, u.y, u.z, (u.x * u.x + u.y * u.y) + u.z * u.z}.  With d_moments_in, over the accepted
+ *      taps in step 3's order and with its b, from 0.f: sm[j] = sm[j] + b * m_q[j], m_q = d_moments_in[4 q ..].  When sw > 0 and
+ *      d_moments_in is given: mbar[j] = sm[j] / sw and m_out[j] = (f[j] - mbar[j]) * alpha + mbar[j] with step 4's alpha.
+ *      Otherwise m_out = f.
+ *   VARIANCE of the mean of demodulated radiance, summed over the channels (rt_denoise_dual_fixed's step-2 quantity), written
+ *      with the moments.  N is the pixel's len_out.
+ *      Temporal, when N >= variance_min_history: m1 = m_out[0 .. 2]; t = m_out[3] - dot(m1, m1); v = (t > 0 ? t : 0) / float(N).
+ *      Spatial, of this frame, otherwise: visit the 5 x 5 window at stride 1 around p, dy outer and dx inner, both from -2 to 2,
+ *      taps outside the image skipped.  The centre counts.  Another tap q counts iff its AOV hits are > 0, with dz = z_q - z_p
+ *      (dz < 0 ? -dz : dz) <= depth_tolerance * z_p, and dot(n_p, n_q) >= normal_cos_min (z and n of this frame's AOV sums, as
+ *      rt_aov_resolve forms them).  Over the counted taps, from 0.f: cnt = cnt + 1.f, s[j] = s[j] + f_q[j].  M[j] = s[j] / cnt;
+ *      t = M[3] - dot(M1, M1); v = (t > 0 ? t : 0) / float(N).
+ * FINITENESS.  0 <= u <= 2^43 (rt_denoise_dual_fixed), so every square is at most 2^86 and every dot(u, u) at most 3 * 2^86 <
+ * 2^89; b lies in [0, 1] and sw >= 2^-50 where it is not 0, so mbar is a convex mean of previous moments up to rounding and the
+ * blend with alpha in (0, 1] stays within the same bounds: moments that are previous outputs of this entry point stay below 2^89,
+ * dot(m1, m1) < 2^89, t is finite, and the spatial sums hold at most 25 terms below 2^89.  No NaN and no infinity can arise from
+ * finite sums and such moments.  A d_moments_in that is NOT a previous output of this entry point (a NaN, an infinity) may
+ * carry a NaN or +inf into d_moments_out and +inf into d_variance_out (a NaN t gives v = 0); rt_denoise_variance_fixed's step 2
+ * absorbs either.  The hist and len outputs do not depend on the moments.
+ * With emission_tolerance = +inf, d_prev_motion = NULL and d_moments_out = NULL the outputs are rt_temporal_accumulate_fixed's,
+ * bit for bit.  rt_temporal_moments_params: NULL = the defaults, which rt_temporal_moments_default_params writes (chosen on the CPU
+ * against 1024-spp frames: profiles/temporal_moments_quality.json).
+ * The contract is rt_temporal_accumulate_fixed's; every pixel of every supplied output is written.  ERRORS return non-zero, begin
+ * "rt_temporal_accumulate_moments_fixed: " in rt_last_error() and write nothing: that entry point's list, and also d_moments_in or
+ * d_prev_motion without history; d_moments_out and d_variance_out not NULL together; d_moments_in without d_moments_out; with
+ * moments and two buffers, samples_a + samples_b beyond int32; a d_prev_motion, d_moments_in or d_moments_out that is not 16-byte
+ * aligned; an emission_tolerance that is negative or NaN; variance_min_history < 1; an overlap of any output (the two new ones
+ * included) with any input or another output.
+ *
+ * rt_denoise_variance_fixed.
+ *   1. c, d, e, z, n and u are exactly steps 1 and 2 of rt_denoise_fixed for (d_sum_fixed, num_samples).
+ *   2. With x = d_variance[p]: v = x > 0 ? (x < 2^87 ? x : 2^87) : 0.  A NaN or a negative x gives 0; v <= 2^87 is the bound
+ *      rt_denoise_dual_fixed's FINITENESS paragraph starts from, so that paragraph holds here unchanged.
+ *   3., 4.  rt_denoise_dual_fixed's steps 3 and 4: its text, its kernels, its parameters and defaults, its scratch
+ *      (rt_denoise_dual_scratch_bytes).
+ * v is the variance of the MEAN of demodulated radiance summed over the three channels, the quantity of rt_denoise_dual_fixed's
+ * step 2: with d_variance holding that v, sum = a + b and num_samples = samples_a + samples_b the output is
+ * rt_denoise_dual_fixed's, bit for bit.  ERRORS begin "rt_denoise_variance_fixed: ": rt_denoise_dual_fixed's list with d_variance
+ * among the pointers that may not be null and num_samples in the place of the two sample counts. */
+typedef struct rt_temporal_moments_params {
+    int32_t max_history;           /* as rt_temporal_params */
+    float   alpha_min;
+    float   depth_tolerance;
+    float   normal_cos_min;
+    float   emission_tolerance;    /* >= 0 or +inf; +inf: the stop passes every tap */
+    int32_t variance_min_history;  /* >= 1: below it the variance is the spatial estimate */
+    uint32_t flags;                /* must be 0 */
+} rt_temporal_moments_params;
+int rt_temporal_moments_default_params(rt_temporal_moments_params *out);
+int rt_temporal_accumulate_moments_fixed(const int64_t *d_sum_a, int samples_a, const int64_t *d_sum_b /* may be NULL */, int samples_b,
+                                         const int64_t *d_aov_fixed, int aov_samples, const float *d_motion,
+                                         const int64_t *d_hist_a_in, const int64_t *d_hist_b_in, const int32_t *d_len_in /* all NULL = first frame */,
+                                         const int64_t *d_prev_aov_fixed, int prev_aov_samples,
+                                         const float *d_prev_motion /* may be NULL: no triangle stop */,
+                                         const float *d_moments_in /* width * height x 4; NULL on the first frame or without moments */,
+                                         int width, int height, const rt_temporal_moments_params *params /* NULL = defaults */,
+                                         int64_t *d_hist_a_out, int64_t *d_hist_b_out /* NULL iff d_sum_b is */, int32_t *d_len_out,
+                                         float *d_moments_out /* width * height x 4, may be NULL */,
+                                         float *d_variance_out /* width * height; NULL together with d_moments_out */, void *stream);
+int rt_denoise_variance_fixed(const int64_t *d_sum_fixed, int num_samples, const float *d_variance /* width * height */,
+                              const int64_t *d_aov_fixed, int aov_samples, int width, int height,
+                              const rt_denoise_dual_params *params /* NULL = rt_denoise_dual_fixed's defaults */,
+                              void *d_scratch /* rt_denoise_dual_scratch_bytes */, float *d_rgb_out /* width * height * 3 */, void *stream);
+
 /* ---- ray queries (no reference counterpart: its Bvh::traverse is reachable only from render()) ----------------------------
  * "Trace my rays, from my buffers, on my stream."  All pointers are DEVICE buffers on the scene's device (a buffer on another
  * device or on the host cannot be told apart from a good one: the call faults instead of failing); origins and directions are

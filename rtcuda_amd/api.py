@@ -42,6 +42,7 @@ EXPORTS = [
     "rt_denoise_scratch_bytes", "rt_denoise_default_params", "rt_denoise_fixed",
     "rt_denoise_dual_scratch_bytes", "rt_denoise_dual_default_params", "rt_denoise_dual_fixed",
     "rt_render_motion", "rt_temporal_default_params", "rt_temporal_accumulate_fixed",
+    "rt_temporal_moments_default_params", "rt_temporal_accumulate_moments_fixed", "rt_denoise_variance_fixed",
     "rt_xorwow_states", "rt_shutdown", "rt_peer_access_log", "rt_last_error", "rt_version", "rt_build_id",
 ]
 # the lab (include/rtcuda_amd_tools.h, librtcuda_amd_tools.so): measurement tools, not part of the drop-in C-ABI
@@ -89,6 +90,12 @@ class RtDenoiseDualParams(ctypes.Structure):
 class RtTemporalParams(ctypes.Structure):
     _fields_ = [("max_history", ctypes.c_int32), ("alpha_min", ctypes.c_float), ("depth_tolerance", ctypes.c_float),
                 ("normal_cos_min", ctypes.c_float), ("flags", ctypes.c_uint32)]
+
+
+class RtTemporalMomentsParams(ctypes.Structure):
+    _fields_ = [("max_history", ctypes.c_int32), ("alpha_min", ctypes.c_float), ("depth_tolerance", ctypes.c_float),
+                ("normal_cos_min", ctypes.c_float), ("emission_tolerance", ctypes.c_float), ("variance_min_history", ctypes.c_int32),
+                ("flags", ctypes.c_uint32)]
 
 
 def build(verbose: bool = False) -> str:
@@ -194,6 +201,10 @@ def _bind(L):
     L.rt_temporal_default_params.argtypes = [ctypes.POINTER(RtTemporalParams)]
     L.rt_temporal_accumulate_fixed.argtypes = [vp, ci, vp, ci, vp, ci, vp, vp, vp, vp, vp, ci, ci, ci, ctypes.POINTER(RtTemporalParams),
                                                vp, vp, vp, vp]
+    L.rt_temporal_moments_default_params.argtypes = [ctypes.POINTER(RtTemporalMomentsParams)]
+    L.rt_temporal_accumulate_moments_fixed.argtypes = [vp, ci, vp, ci, vp, ci, vp, vp, vp, vp, vp, ci, vp, vp, ci, ci,
+                                                       ctypes.POINTER(RtTemporalMomentsParams), vp, vp, vp, vp, vp, vp]
+    L.rt_denoise_variance_fixed.argtypes = [vp, ci, vp, vp, ci, ci, ci, ctypes.POINTER(RtDenoiseDualParams), vp, vp, vp]
     L.rt_trace_closest.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp]
     L.rt_trace_any.argtypes = [vp, ci, vp, vp, vp, vp, vp]
     L.rt_trace_closest_flags.argtypes = [vp, ctypes.c_uint32, ci, vp, vp, vp, vp, vp, vp, vp]
@@ -879,9 +890,11 @@ def _dn_sums(me: str, n: int, named):
     return device
 
 
-def _dn_params(me: str, prm, ints, sigmas):
-    """``prm`` (a ctypes parameter struct) as the library's defaults, overwritten by the (name, value) pairs that are not None."""
-    _check(getattr(lib(), f"rt_{me}_default_params")(ctypes.byref(prm)), f"rt_{me}_default_params")
+def _dn_params(me: str, prm, ints, sigmas, defaults_of=None):
+    """``prm`` (a ctypes parameter struct) as the library's defaults (``defaults_of``: the entry point whose defaults they are, if
+    not ``me``'s own), overwritten by the (name, value) pairs that are not None."""
+    owner = defaults_of or me
+    _check(getattr(lib(), f"rt_{owner}_default_params")(ctypes.byref(prm)), f"rt_{owner}_default_params")
     for name, v in ints:
         if v is not None:
             if not isinstance(v, int) or isinstance(v, bool) or not 0 <= v <= 8:
@@ -1064,6 +1077,136 @@ def temporal_accumulate(beauty_a, spp_a: int, beauty_b, spp_b: int, aov_sums, ao
                                                   ctypes.byref(prm), ptr(out[0]), ptr(out[1]), ptr(out[2]), c(s.cuda_stream or None)),
                "rt_temporal_accumulate_fixed")
     return tuple(out)
+
+
+def temporal_moments_default_params() -> dict:
+    """The parameters rt_temporal_accumulate_moments_fixed uses when it is given none (rt_temporal_moments_default_params)."""
+    prm = RtTemporalMomentsParams()
+    _check(lib().rt_temporal_moments_default_params(ctypes.byref(prm)), "rt_temporal_moments_default_params")
+    return {"max_history": int(prm.max_history), "alpha_min": float(prm.alpha_min), "depth_tolerance": float(prm.depth_tolerance),
+            "normal_cos_min": float(prm.normal_cos_min), "emission_tolerance": float(prm.emission_tolerance),
+            "variance_min_history": int(prm.variance_min_history)}
+
+
+def temporal_accumulate_moments(beauty_a, spp_a: int, beauty_b, spp_b: int, aov_sums, aov_spp: int, motion, history, width: int, height: int, *,
+                                moments: bool = True, max_history=None, alpha_min=None, depth_tolerance=None, normal_cos_min=None,
+                                emission_tolerance=None, variance_min_history=None, out=None, stream=None):
+    """``temporal_accumulate`` with an emission stop, a triangle stop and temporally accumulated moments
+    (rt_temporal_accumulate_moments_fixed) -> (hist_a, hist_b or None, length, moments or None, variance or None).
+    The arguments are temporal_accumulate's; ``history`` is None on the first frame, else (hist_a, hist_b or None, length,
+    prev_aov_sums, prev_aov_spp, prev_motion or None, prev_moments or None): the previous call's results, the previous frame's
+    AOV sums and MOTION buffer ((h * w, 4) float32; None: no triangle stop) and the previous call's moments ((h * w, 4) float32;
+    None: the moments start again).  With ``moments`` (the default) the call also returns the moments, for the next frame, and
+    the (h * w,) float32 variance of the mean of demodulated radiance, which ``denoise_variance`` takes.  ``emission_tolerance``
+    may be float('inf') (the stop passes every tap).  ``out``: a tuple of the five results' tensors to fill (None where a result
+    is None), none of which may be an input.  Parameters left at None are the library's defaults
+    (temporal_moments_default_params)."""
+    import torch
+    me = "temporal_accumulate_moments"
+    two = beauty_b is not None
+    _dn_positive_ints(me, (("width", width), ("height", height), ("spp_a", spp_a), ("aov_spp", aov_spp)) + ((("spp_b", spp_b),) if two else ()))
+    n = width * height
+    named = [("beauty_a", beauty_a, 3)] + ([("beauty_b", beauty_b, 3)] if two else []) + [("aov_sums", aov_sums, AOV_CHANNELS)]
+    hist_a = hist_b = length = prev_aov = prev_motion = prev_moments = None
+    prev_spp = 1
+    if history is not None:
+        if not isinstance(history, (tuple, list)) or len(history) != 7:
+            raise RtError(f"{me}: history must be None or (hist_a, hist_b or None, length, prev_aov_sums, prev_aov_spp, prev_motion or None, "
+                          "prev_moments or None)")
+        hist_a, hist_b, length, prev_aov, prev_spp, prev_motion, prev_moments = history
+        if (hist_b is not None) != two:
+            raise RtError(f"{me}: history's hist_b and beauty_b must be None together")
+        if prev_moments is not None and not moments:
+            raise RtError(f"{me}: history's prev_moments needs moments=True")
+        _dn_positive_ints(me, (("prev_aov_spp", prev_spp),))
+        named += [("history hist_a", hist_a, 3)] + ([("history hist_b", hist_b, 3)] if two else []) + [("history prev_aov_sums", prev_aov, AOV_CHANNELS)]
+    device = _dn_sums(me, n, tuple(named))
+
+    def plain(name, t, dtype, shape):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != device:
+            raise RtError(f"{me}: {name} must be a torch tensor on the GPU of the sums")
+        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+            raise RtError(f"{me}: {name} must be a contiguous {shape} {dtype} tensor, it is {tuple(t.shape)} {t.dtype}")
+
+    plain("motion", motion, torch.float32, (n, 4))
+    if history is not None:
+        plain("history length", length, torch.int32, (n,))
+        if prev_motion is not None:
+            plain("history prev_motion", prev_motion, torch.float32, (n, 4))
+        if prev_moments is not None:
+            plain("history prev_moments", prev_moments, torch.float32, (n, 4))
+    prm = RtTemporalMomentsParams()
+    _check(lib().rt_temporal_moments_default_params(ctypes.byref(prm)), "rt_temporal_moments_default_params")
+    for name, v in (("max_history", max_history), ("variance_min_history", variance_min_history)):
+        if v is not None:
+            if not isinstance(v, int) or isinstance(v, bool) or not 1 <= v <= 0x7FFFFFFF:
+                raise RtError(f"{me}: {name} must be an int in 1 .. 2^31 - 1, it is {v!r}")
+            setattr(prm, name, v)
+    for name, v in (("alpha_min", alpha_min), ("depth_tolerance", depth_tolerance), ("normal_cos_min", normal_cos_min)):
+        if v is not None:
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.floating)) or not np.isfinite(v):
+                raise RtError(f"{me}: {name} must be a finite number, it is {v!r}")
+            setattr(prm, name, float(v))
+    if emission_tolerance is not None:
+        if isinstance(emission_tolerance, bool) or not isinstance(emission_tolerance, (int, float, np.floating)):
+            raise RtError(f"{me}: emission_tolerance must be a number, it is {emission_tolerance!r}")
+        prm.emission_tolerance = float(emission_tolerance)  # (a NaN or a negative one is the library's to refuse)
+    if out is None:
+        out = (torch.empty((n, 3), dtype=torch.int64, device=device), torch.empty((n, 3), dtype=torch.int64, device=device) if two else None,
+               torch.empty(n, dtype=torch.int32, device=device), torch.empty((n, 4), dtype=torch.float32, device=device) if moments else None,
+               torch.empty(n, dtype=torch.float32, device=device) if moments else None)
+    else:
+        if (not isinstance(out, (tuple, list)) or len(out) != 5 or (out[1] is not None) != two or (out[3] is not None) != moments
+                or (out[4] is not None) != moments):
+            raise RtError(f"{me}: out must be (hist_a, hist_b or None as beauty_b, length, moments and variance or None as ``moments``)")
+        _dn_sums(me, n, tuple([("out hist_a", out[0], 3)] + ([("out hist_b", out[1], 3)] if two else [])))
+        plain("out length", out[2], torch.int32, (n,))
+        if moments:
+            plain("out moments", out[3], torch.float32, (n, 4))
+            plain("out variance", out[4], torch.float32, (n,))
+        if out[0].device != device:
+            raise RtError(f"{me}: out is on {out[0].device}, beauty_a on {device}")
+    s = torch.cuda.current_stream(device) if stream is None else stream
+    c = ctypes.c_void_p
+
+    def ptr(t):
+        return c(None if t is None else t.data_ptr())
+
+    with torch.cuda.device(device):
+        _check(lib().rt_temporal_accumulate_moments_fixed(ptr(beauty_a), spp_a, ptr(beauty_b), spp_b if two else 0, ptr(aov_sums), aov_spp, ptr(motion),
+                                                          ptr(hist_a), ptr(hist_b), ptr(length), ptr(prev_aov), prev_spp, ptr(prev_motion),
+                                                          ptr(prev_moments), width, height, ctypes.byref(prm), ptr(out[0]), ptr(out[1]), ptr(out[2]),
+                                                          ptr(out[3]), ptr(out[4]), c(s.cuda_stream or None)),
+               "rt_temporal_accumulate_moments_fixed")
+    return tuple(out)
+
+
+def denoise_variance(beauty_sums, spp: int, variance, aov_sums, aov_spp: int, width: int, height: int, *, passes=None, sigma_variance=None,
+                     sigma_depth=None, normal_power_log2=None, scratch=None, out=None, stream=None):
+    """``denoise_dual``'s filter on ONE frame and a variance buffer (rt_denoise_variance_fixed).  ``beauty_sums``: (h * w, 3) int64
+    sums of ``spp`` samples -- hist_a of temporal_accumulate_moments with spp = 1; ``variance``: (h * w,) float32 on the same
+    GPU, the variance of the mean of demodulated radiance summed over the channels, as temporal_accumulate_moments returns it (a
+    NaN or a negative value counts as 0, the top is 2^87); ``aov_sums``: (h * w, 11) int64 -> (h * w, 3) float32 tensor of LINEAR
+    mean radiance.  Parameters, defaults and scratch are denoise_dual's (denoise_dual_default_params,
+    denoise_dual_scratch_bytes)."""
+    import torch
+    me = "denoise_variance"
+    _dn_positive_ints(me, (("width", width), ("height", height), ("spp", spp), ("aov_spp", aov_spp)))
+    n = width * height
+    device = _dn_sums(me, n, (("beauty_sums", beauty_sums, 3), ("aov_sums", aov_sums, AOV_CHANNELS)))
+    if not isinstance(variance, torch.Tensor) or not variance.is_cuda or variance.device != device:
+        raise RtError(f"{me}: variance must be a torch tensor on the GPU of the sums")
+    if variance.dtype != torch.float32 or tuple(variance.shape) != (n,) or not variance.is_contiguous():
+        raise RtError(f"{me}: variance must be a contiguous ({n},) torch.float32 tensor, it is {tuple(variance.shape)} {variance.dtype}")
+    prm = _dn_params(me, RtDenoiseDualParams(), (("passes", passes), ("normal_power_log2", normal_power_log2)),
+                     (("sigma_variance", sigma_variance), ("sigma_depth", sigma_depth)), defaults_of="denoise_dual")
+    scratch, out, s = _dn_buffers(me, denoise_dual_scratch_bytes(width, height), n, device, scratch, out, stream)
+    with torch.cuda.device(device):
+        _check(lib().rt_denoise_variance_fixed(ctypes.c_void_p(beauty_sums.data_ptr()), spp, ctypes.c_void_p(variance.data_ptr()),
+                                               ctypes.c_void_p(aov_sums.data_ptr()), aov_spp, width, height, ctypes.byref(prm),
+                                               ctypes.c_void_p(scratch.data_ptr()), ctypes.c_void_p(out.data_ptr()),
+                                               ctypes.c_void_p(s.cuda_stream or None)), "rt_denoise_variance_fixed")
+    return out
 
 
 def xorwow_states(seed: int, first: int, count: int, draws: int = 0):

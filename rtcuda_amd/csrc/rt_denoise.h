@@ -118,4 +118,14 @@ RT_HD float dn_var_rcp(float ks, float g) { return 1.f / (ks * g + DN_VAR_EPS); 
 // One tap that is not the centre is dn_tap_weight with the pixel's r in the place of the pass's kc -- x_v = (|du|^2) * r is the
 // same three operations as x_c.
 
+// ---- rt_denoise_variance_fixed (include/rtcuda_amd.h): rt_denoise_dual_fixed's passes on ONE frame and a variance the caller
+// brings.  Shared by k_dn_prepare_var and the CPU twin hc_denoise_variance.
+#define DN_VAR_MAX 154742504910672534362390528.f  // 2^87: above every v that dn_prepare_dual can form
+
+// Steps 1 and 2: dn_prepare's pixel of (sum, n), and the caller's x made a legal v: a NaN or a negative x gives 0, the top is 2^87.
+RT_HD float dn_prepare_var(const int64_t *sum3, const int64_t *aov11, float x, float inv_spp, float inv_aov, DnPixel *px) {
+    dn_prepare(sum3, aov11, inv_spp, inv_aov, px);
+    return x > 0.f ? (x < DN_VAR_MAX ? x : DN_VAR_MAX) : 0.f;
+}
+
 #endif  // RT_DENOISE_H

@@ -168,6 +168,19 @@ __global__ void __launch_bounds__(kBlock) k_dn_prepare_dual(const long long *__r
     nz[p] = make_float4(px.n[0], px.n[1], px.n[2], px.z);
 }
 
+// rt_denoise_variance_fixed: the same two records from one frame's sums and the caller's variance buffer; the passes are the dual
+// filter's, the finish is k_dn_finish (it reads u and forms d and e from the one sum again).
+__global__ void __launch_bounds__(kBlock) k_dn_prepare_var(const long long *__restrict__ sums, const float *__restrict__ variance,
+                                                            const long long *__restrict__ aov, long long n_pixels, float inv_spp,
+                                                            float inv_aov, float4 *__restrict__ uv, float4 *__restrict__ nz) {
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_pixels) return;
+    DnPixel px;
+    const float v = dn_prepare_var((const int64_t *)sums + 3 * p, (const int64_t *)aov + DN_AOV_CHANNELS * p, variance[p], inv_spp, inv_aov, &px);
+    uv[p] = make_float4(px.u[0], px.u[1], px.u[2], v);
+    nz[p] = make_float4(px.n[0], px.n[1], px.n[2], px.z);
+}
+
 __global__ void __launch_bounds__(kBlock) k_dn_var_blur(const float4 *__restrict__ src, float *__restrict__ r_out, int width, int height,
                                                          long long n_pixels, float ks) {
     const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;

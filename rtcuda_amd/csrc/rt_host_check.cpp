@@ -1109,6 +1109,67 @@ int hc_temporal_accumulate(const int64_t *sum_a, int samples_a, const int64_t *s
                                 hist_b_out, len_out);
     return 0;
 }
+// The CPU twin of rt_temporal_accumulate_moments_fixed (tests/test_temporal_moments_host.py, tools/temporal_moments_quality.py):
+// a serial loop over rt_temporal.h's tm_accumulate_moments_pixel, host buffers throughout, the same checks of the parameters and
+// of which pointers go together (not the alignment and overlap checks: the caller's).  Returns 0, or 1 and writes nothing.
+int hc_temporal_accumulate_moments(const int64_t *sum_a, int samples_a, const int64_t *sum_b, int samples_b, const int64_t *aov_fixed,
+                                   int aov_samples, const float *motion4, const int64_t *hist_a_in, const int64_t *hist_b_in,
+                                   const int32_t *len_in, const int64_t *prev_aov_fixed, int prev_aov_samples, const float *prev_motion4,
+                                   const float *moments_in, int width, int height, int max_history, float alpha_min, float depth_tolerance,
+                                   float normal_cos_min, float emission_tolerance, int variance_min_history, int64_t *hist_a_out,
+                                   int64_t *hist_b_out, int32_t *len_out, float *moments_out, float *variance_out) {
+    if (!sum_a || !aov_fixed || !motion4 || !hist_a_out || !len_out || width < 1 || height < 1 || samples_a < 1 || aov_samples < 1) return 1;
+    const bool two = sum_b != nullptr, history = hist_a_in != nullptr, moments = moments_out != nullptr;
+    if (two != (hist_b_out != nullptr) || (two && samples_b < 1)) return 1;
+    if (!history && (hist_b_in || len_in || prev_aov_fixed || moments_in || prev_motion4)) return 1;
+    if (history && (!len_in || !prev_aov_fixed || prev_aov_samples < 1 || two != (hist_b_in != nullptr))) return 1;
+    if (moments != (variance_out != nullptr) || (moments_in && !moments)) return 1;
+    if (moments && two && (long long)samples_a + samples_b > 0x7fffffffll) return 1;
+    if (max_history < 1 || !(alpha_min > 0.f && alpha_min <= 1.f) || !(std::isfinite(depth_tolerance) && depth_tolerance > 0.f)) return 1;
+    if (!(normal_cos_min >= -1.f && normal_cos_min <= 1.f) || !(emission_tolerance >= 0.f) || variance_min_history < 1) return 1;
+    TmMoments t{};
+    t.sum_a = sum_a, t.sum_b = sum_b, t.aov = aov_fixed, t.hist_a_in = hist_a_in, t.hist_b_in = hist_b_in, t.prev_aov = prev_aov_fixed;
+    t.motion = motion4, t.prev_motion = prev_motion4, t.moments_in = moments_in, t.len_in = len_in;
+    t.out_a = hist_a_out, t.out_b = hist_b_out, t.len_out = len_out, t.moments_out = moments_out, t.variance_out = variance_out;
+    t.width = width, t.height = height, t.tiles_x = 0;
+    t.max_history = max_history, t.variance_min_history = variance_min_history;
+    t.use_emission = emission_tolerance <= 3.402823466e+38f;
+    t.inv_a = 1.f / (float)samples_a;
+    t.inv_b = two ? 1.f / (float)samples_b : 0.f;
+    t.inv_n = 1.f / (float)(two && moments ? samples_a + samples_b : samples_a);
+    t.inv_aov = 1.f / (float)aov_samples;
+    t.inv_prev_aov = history ? 1.f / (float)prev_aov_samples : 0.f;
+    t.alpha_min = alpha_min, t.depth_tolerance = depth_tolerance, t.normal_cos_min = normal_cos_min, t.emission_tolerance = emission_tolerance;
+    for (int y = 0; y < height; y++)
+        for (int x = 0; x < width; x++) tm_accumulate_moments_pixel(&t, x, y, motion4 + 4 * ((size_t)y * width + x));
+    return 0;
+}
+// The CPU twin of rt_denoise_variance_fixed (tests/test_denoise_variance_host.py, tools/temporal_moments_quality.py): hc_denoise_dual's
+// walk on one frame's sums and the caller's variance.  var_out (may be null): the final v per pixel.  Returns 0, or 1 and writes nothing.
+int hc_denoise_variance(const int64_t *sum_fixed, int num_samples, const float *variance, const int64_t *aov_fixed, int aov_samples, int width,
+                        int height, int passes, float sigma_variance, float sigma_depth, int normal_power_log2, float *rgb_out, float *var_out) {
+    if (!sum_fixed || !variance || !aov_fixed || !rgb_out || width < 1 || height < 1 || num_samples < 1 || aov_samples < 1) return 1;
+    if (passes < 0 || passes > DN_MAX_PASSES || normal_power_log2 < 0 || normal_power_log2 > DN_MAX_NORMAL_POWER_LOG2) return 1;
+    if (!(std::isfinite(sigma_variance) && sigma_variance > 0.f && std::isfinite(sigma_depth) && sigma_depth > 0.f)) return 1;
+    const float ks = sigma_variance * sigma_variance, sd2 = sigma_depth * sigma_depth;
+    const float kz = 1.f / sd2;
+    if (!(std::isfinite(ks) && ks > 0.f && std::isfinite(kz) && kz > 0.f)) return 1;
+    const float inv_spp = 1.f / (float)num_samples, inv_aov = 1.f / (float)aov_samples;
+    const size_t n = (size_t)width * (size_t)height;
+    std::vector<DnPixel> px(n);
+    std::vector<float> uv(4 * n);
+    for (size_t p = 0; p < n; p++) {
+        uv[4 * p + 3] = dn_prepare_var(sum_fixed + 3 * p, aov_fixed + DN_AOV_CHANNELS * p, variance[p], inv_spp, inv_aov, &px[p]);
+        for (int k = 0; k < 3; k++) uv[4 * p + k] = px[p].u[k];
+    }
+    const float k[DN_MAX_PASSES] = {ks, ks, ks, ks, ks, ks, ks, ks};
+    dn_walk<true>(uv, px, width, height, passes, k, kz, normal_power_log2);
+    for (size_t p = 0; p < n; p++) {
+        dn_finish(&uv[4 * p], px[p].d, px[p].e, rgb_out + 3 * p);
+        if (var_out) var_out[p] = uv[4 * p + 3];
+    }
+    return 0;
+}
 // The stats of a frame from its n shards' (rt_stats_merge.h), as RT_SPLIT (sub_shards != 0) and rt_render_multi merge them
 void hc_merge_shard_stats(const rt_stats *sub, int n, int sub_shards, rt_stats *out) { *out = merge_shard_stats(sub, n, sub_shards != 0); }
 }

@@ -209,3 +209,28 @@ int denoise_dual_impl(const int64_t *d_sum_a, int samples_a, const int64_t *d_su
                                (const long long *)d_sum_b, (const long long *)d_aov_fixed, n, inv_n, inv_aov, d_rgb_out);
         });
 }
+
+// ---- rt_denoise_variance_fixed: the dual filter's checks, scratch, forms and passes on one frame; v comes from the caller
+int denoise_variance_impl(const int64_t *d_sum_fixed, int num_samples, const float *d_variance, const int64_t *d_aov_fixed, int aov_samples,
+                          int width, int height, const rt_denoise_dual_params *params, void *d_scratch, float *d_rgb_out, hipStream_t stream) {
+    const std::string me = "rt_denoise_variance_fixed: ";
+    const rt_denoise_dual_params prm = params ? *params : denoise_dual_defaults();
+    if (dn_check(me, !d_sum_fixed ? "d_sum_fixed" : !d_variance ? "d_variance" : !d_aov_fixed ? "d_aov_fixed" : !d_scratch ? "d_scratch" : !d_rgb_out ? "d_rgb_out" : nullptr,
+                 width, height, num_samples < 1 || aov_samples < 1 ? "num_samples and aov_samples must be at least 1" : nullptr, d_scratch,
+                 prm.flags, prm.passes, prm.normal_power_log2, "sigma_variance", prm.sigma_variance, prm.sigma_depth))
+        return 1;
+    const float ks = prm.sigma_variance * prm.sigma_variance;
+    if (!(std::isfinite(ks) && ks > 0.f)) return fail(me + "sigma_variance gives a variance constant that is not finite and positive");
+    const float k[DN_MAX_PASSES] = {ks, ks, ks, ks, ks, ks, ks, ks};
+    const float inv_spp = 1.f / (float)num_samples, inv_aov = 1.f / (float)aov_samples;
+    return dn_run(
+        me, true, width, height, prm.passes, k, prm.sigma_depth, prm.normal_power_log2, d_scratch, stream,
+        [&](unsigned blocks, long long n, float4 *uv, float4 *nz) {
+            hipLaunchKernelGGL(k_dn_prepare_var, dim3(blocks), dim3(kBlock), 0, stream, (const long long *)d_sum_fixed, d_variance,
+                               (const long long *)d_aov_fixed, n, inv_spp, inv_aov, uv, nz);
+        },
+        [&](unsigned blocks, long long n, const float4 *uv) {
+            hipLaunchKernelGGL(k_dn_finish, dim3(blocks), dim3(kBlock), 0, stream, uv, (const long long *)d_sum_fixed,
+                               (const long long *)d_aov_fixed, n, inv_spp, inv_aov, d_rgb_out);
+        });
+}

@@ -172,4 +172,197 @@ RT_HD void tm_accumulate_pixel(int x, int y, int width, int height, const int64_
     }
 }
 
+// ---- rt_temporal_accumulate_moments_fixed: the accumulator above with two more stops, temporally accumulated first and second
+// moments of demodulated radiance, and the variance of the mean they give.  What one call is handed, the kernel's parameter block
+// and the twin's alike (host or device pointers; the optional ones null).
+typedef struct TmMoments {
+    const int64_t *sum_a, *sum_b, *aov, *hist_a_in, *hist_b_in, *prev_aov;
+    const float *motion, *prev_motion, *moments_in;
+    const int32_t *len_in;
+    int64_t *out_a, *out_b;
+    int32_t *len_out;
+    float *moments_out, *variance_out;
+    int width, height, tiles_x;
+    int32_t max_history, variance_min_history;
+    int use_emission;  // emission_tolerance < +inf: the previous frame's emission sums are read at all
+    float inv_a, inv_b, inv_n, inv_aov, inv_prev_aov, alpha_min, depth_tolerance, normal_cos_min, emission_tolerance;
+} TmMoments;
+
+// a moments record is one 16-byte access on the device (the entry point checks the alignment; the twin's host buffers need none)
+#ifdef __HIP_DEVICE_COMPILE__
+#define TM_RECORD(p) __builtin_assume_aligned(p, 16)
+#else
+#define TM_RECORD(p) (p)
+#endif
+
+RT_HD void tm_emission(const int64_t *aov11, float inv_aov, float *e3) {
+    for (int k = 0; k < 3; k++) e3[k] = dn_fixed_to_float(aov11[DN_EMISSION + k]) * inv_aov;
+}
+
+// the emission stop: the largest channel difference, by comparison and selection from channel 0, against the tolerance
+RT_HD bool tm_emission_accept(const float *e_p, const int64_t *prev_aov11, float inv_prev_aov, float emission_tolerance) {
+    float e_q[3];
+    tm_emission(prev_aov11, inv_prev_aov, e_q);
+    float de = 0.f;
+    for (int k = 0; k < 3; k++) {
+        const float d = e_p[k] - e_q[k];
+        const float ad = d < 0.f ? -d : d;
+        de = k == 0 ? ad : (ad > de ? ad : de);
+    }
+    return de <= emission_tolerance;
+}
+
+// The frame's moments of pixel q: u is the dual denoiser's step-1 demodulated radiance of the (wrapped) sum of the supplied
+// buffers, f = {u.x, u.y, u.z, dot(u, u)}.  Also the features the spatial estimate's stops need (dn_prepare forms n and z as
+// tm_features does).  Returns the hit count.
+RT_HD int64_t tm_frame_moments(const TmMoments *t, long long q, float *f4, float *n3, float *z) {
+    int64_t s[3];
+    for (int k = 0; k < 3; k++) s[k] = t->sum_b ? (int64_t)((uint64_t)t->sum_a[3 * q + k] + (uint64_t)t->sum_b[3 * q + k]) : t->sum_a[3 * q + k];
+    DnPixel px;
+    dn_prepare(s, t->aov + DN_AOV_CHANNELS * q, t->inv_n, t->inv_aov, &px);
+    for (int k = 0; k < 3; k++) f4[k] = px.u[k], n3[k] = px.n[k];
+    f4[3] = tm_dot(px.u, px.u);
+    *z = px.z;
+    return t->aov[DN_AOV_CHANNELS * q + DN_HITS];
+}
+
+RT_HD float tm_variance_of(const float *m4, int32_t n) {
+    const float t = m4[3] - tm_dot(m4, m4);
+    return (t > 0.f ? t : 0.f) / (float)n;
+}
+
+// The spatial estimate of this frame at (x, y): the moments' mean over the 5 x 5 window's taps that pass the depth and normal
+// stops against the centre (which always counts).  tap(dx, dy, q, f_q, n_q, &z_q) hands back the moments and features of the
+// neighbour (dx, dy), which is pixel q of the frame, and whether it has hits: from global memory (tm_spatial_variance) or from a
+// staged tile (k_temporal_accumulate_moments) -- the one use of C++ in this header.
+template <typename Tap>
+RT_HD float tm_spatial_variance_of(const TmMoments *t, int x, int y, const float *f_p, const float *n_p, float z_p, int32_t n, Tap tap) {
+    float cnt = 0.f, s[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int dy = -2; dy <= 2; dy++) {
+        const int yy = y + dy;
+        if (yy < 0 || yy >= t->height) continue;
+        for (int dx = -2; dx <= 2; dx++) {
+            const int xx = x + dx;
+            if (xx < 0 || xx >= t->width) continue;
+            float f_q[4] = {f_p[0], f_p[1], f_p[2], f_p[3]};
+            if (dx != 0 || dy != 0) {
+                float n_q[3], z_q;
+                if (!tap(dx, dy, (long long)yy * t->width + xx, f_q, n_q, &z_q)) continue;
+                const float dz = z_q - z_p;
+                if (!((dz < 0.f ? -dz : dz) <= t->depth_tolerance * z_p)) continue;
+                if (!(tm_dot(n_p, n_q) >= t->normal_cos_min)) continue;
+            }
+            cnt = cnt + 1.f;
+            for (int j = 0; j < 4; j++) s[j] = s[j] + f_q[j];
+        }
+    }
+    float m[4];
+    for (int j = 0; j < 4; j++) m[j] = s[j] / cnt;
+    return tm_variance_of(m, n);
+}
+// the CPU twin's: a tap is the neighbour's beauty and AOV sums, demodulated here
+RT_HD float tm_spatial_variance(const TmMoments *t, int x, int y, const float *f_p, const float *n_p, float z_p, int32_t n) {
+    return tm_spatial_variance_of(t, x, y, f_p, n_p, z_p, n, [t](int, int, long long q, float *f_q, float *n_q, float *z_q) {
+        return tm_frame_moments(t, q, f_q, n_q, z_q) > 0;
+    });
+}
+
+// One pixel (x, y).  tm_accumulate_pixel's steps with the emission stop, the triangle stop (prev_motion given) and, with
+// moments_out given, the moments through the same taps and weights and the variance of the mean -- all but the spatial estimate:
+// returns true where that is still owed (variance_out[p] not written), with what it needs: the frame's moments f, n_p, z_p and N.
+RT_HD bool tm_accumulate_moments_front(const TmMoments *t, int x, int y, const float *mo, float *f, float *n_p, float *z_p_out, int32_t *n_out) {
+    const int width = t->width, height = t->height;
+    const long long p = (long long)y * width + x;
+    const bool two = t->sum_b != 0, moments = t->moments_out != 0;
+    float ca[3], cb[3] = {0.f, 0.f, 0.f};
+    for (int k = 0; k < 3; k++) {
+        ca[k] = dn_fixed_to_float(t->sum_a[3 * p + k]) * t->inv_a;
+        if (two) cb[k] = dn_fixed_to_float(t->sum_b[3 * p + k]) * t->inv_b;
+    }
+    float z_p = 0.f;
+    for (int k = 0; k < 4; k++) f[k] = 0.f;
+    for (int k = 0; k < 3; k++) n_p[k] = 0.f;
+    if (moments) (void)tm_frame_moments(t, p, f, n_p, &z_p);
+    float sw = 0.f, sa[3] = {0.f, 0.f, 0.f}, sb[3] = {0.f, 0.f, 0.f}, sm[4] = {0.f, 0.f, 0.f, 0.f};
+    int32_t n_prev = 0x7fffffff;
+    int32_t tri;
+    {
+        union { float f; int32_t i; } bits;
+        bits.f = mo[3];
+        tri = bits.i;
+    }
+    if (t->hist_a_in && tri >= 0) {
+        const float fx = mo[0] - 0.5f, fy = mo[1] - 0.5f, dist = mo[2];
+        if (fx >= -1.f && fx < (float)width && fy >= -1.f && fy < (float)height) {  // (false for a NaN)
+            float e_p[3] = {0.f, 0.f, 0.f};
+            if (!moments) (void)tm_features(t->aov + DN_AOV_CHANNELS * p, t->inv_aov, n_p, &z_p);
+            if (t->use_emission) tm_emission(t->aov + DN_AOV_CHANNELS * p, t->inv_aov, e_p);
+            const float flx = floorf(fx), fly = floorf(fy);
+            const int x0 = (int)flx, y0 = (int)fly;
+            const float ax = fx - flx, ay = fy - fly;
+            for (int j = 0; j < 2; j++) {
+                const int yy = y0 + j;
+                if (yy < 0 || yy >= height) continue;
+                for (int i = 0; i < 2; i++) {
+                    const int xx = x0 + i;
+                    if (xx < 0 || xx >= width) continue;
+                    const long long q = (long long)yy * width + xx;
+                    const int32_t len_q = t->len_in[q];
+                    const int64_t *aov_q = t->prev_aov + DN_AOV_CHANNELS * q;
+                    if (!tm_tap_accept(len_q, aov_q, t->inv_prev_aov, n_p, dist, t->depth_tolerance, t->normal_cos_min)) continue;
+                    if (t->use_emission && !tm_emission_accept(e_p, aov_q, t->inv_prev_aov, t->emission_tolerance)) continue;
+                    if (t->prev_motion) {
+                        union { float f; int32_t i; } bits;
+                        bits.f = t->prev_motion[4 * q + 3];
+                        if (bits.i != tri) continue;
+                    }
+                    const float b = (i ? ax : 1.f - ax) * (j ? ay : 1.f - ay);
+                    sw = sw + b;
+                    for (int k = 0; k < 3; k++) {
+                        sa[k] = sa[k] + b * dn_fixed_to_float(t->hist_a_in[3 * q + k]);
+                        if (two) sb[k] = sb[k] + b * dn_fixed_to_float(t->hist_b_in[3 * q + k]);
+                    }
+                    if (moments && t->moments_in) {
+                        const float *m_q = (const float *)TM_RECORD(t->moments_in) + 4 * q;
+                        for (int k = 0; k < 4; k++) sm[k] = sm[k] + b * m_q[k];
+                    }
+                    n_prev = len_q < n_prev ? len_q : n_prev;
+                }
+            }
+        }
+    }
+    int32_t n = 1;
+    float m[4] = {f[0], f[1], f[2], f[3]};
+    if (sw > 0.f) {
+        n = tm_history_length(n_prev, t->max_history);
+        const float alpha = tm_alpha(n, t->alpha_min);
+        for (int k = 0; k < 3; k++) {
+            t->out_a[3 * p + k] = tm_to_fixed(tm_blend(ca[k], sa[k] / sw, alpha));
+            if (two) t->out_b[3 * p + k] = tm_to_fixed(tm_blend(cb[k], sb[k] / sw, alpha));
+        }
+        if (moments && t->moments_in)
+            for (int k = 0; k < 4; k++) m[k] = tm_blend(f[k], sm[k] / sw, alpha);
+    } else {
+        for (int k = 0; k < 3; k++) {
+            t->out_a[3 * p + k] = tm_to_fixed(ca[k]);
+            if (two) t->out_b[3 * p + k] = tm_to_fixed(cb[k]);
+        }
+    }
+    t->len_out[p] = n;
+    *z_p_out = z_p;
+    *n_out = n;
+    if (!moments) return false;
+    float *m_out = (float *)TM_RECORD(t->moments_out) + 4 * p;
+    for (int k = 0; k < 4; k++) m_out[k] = m[k];
+    if (n < t->variance_min_history) return true;
+    t->variance_out[p] = tm_variance_of(m, n);
+    return false;
+}
+RT_HD void tm_accumulate_moments_pixel(const TmMoments *t, int x, int y, const float *mo) {
+    float f[4], n_p[3], z_p;
+    int32_t n;
+    if (tm_accumulate_moments_front(t, x, y, mo, f, n_p, &z_p, &n))
+        t->variance_out[(long long)y * t->width + x] = tm_spatial_variance(t, x, y, f, n_p, z_p, n);
+}
+
 #endif  // RT_TEMPORAL_H

@@ -14,9 +14,10 @@
 //                          stats merged (rt_stats_merge.h), the post-process, finish_frame, rt_render and rt_render_multi
 //   rt_denoise_kernels.inc the denoisers' kernels: one tap loop (dn_filter_pixel) and two pass bodies (dn_pass_direct, dn_pass_lds) under
 //                          k_atrous* / k_atrous_var*; prepare, finish, k_dn_var_blur (arithmetic: rt_denoise.h, shared with the CPU twin)
-//   rt_host_denoise.inc    rt_denoise_fixed and rt_denoise_dual_fixed: one set of checks (dn_check), one pass launcher, one run (dn_run)
-//   rt_temporal_kernels.inc k_temporal_accumulate (arithmetic: rt_temporal.h, shared with k_motion and the CPU twins)
-//   rt_host_temporal.inc   rt_temporal_accumulate_fixed: the checks and the launch
+//   rt_host_denoise.inc    rt_denoise_fixed, rt_denoise_dual_fixed and rt_denoise_variance_fixed: one set of checks (dn_check), one pass
+//                          launcher, one run (dn_run)
+//   rt_temporal_kernels.inc k_temporal_accumulate, k_temporal_accumulate_moments (arithmetic: rt_temporal.h, shared with k_motion and the CPU twins)
+//   rt_host_temporal.inc   rt_temporal_accumulate_fixed and rt_temporal_accumulate_moments_fixed: the checks and the launch
 // The C-ABI below them only checks arguments and forwards, and calls none of its own entry points.  Two bodies stay in it:
 // rt_camera_make (host arithmetic, nothing shared) and rt_xorwow_states (a test hook around k_rng_init / k_test_draw).
 //
@@ -1146,6 +1147,29 @@ int rt_temporal_accumulate_fixed(const int64_t *d_sum_a, int samples_a, const in
     return temporal_accumulate_impl(d_sum_a, samples_a, d_sum_b, samples_b, d_aov_fixed, aov_samples, d_motion, d_hist_a_in, d_hist_b_in,
                                     d_len_in, d_prev_aov_fixed, prev_aov_samples, width, height, params, d_hist_a_out, d_hist_b_out,
                                     d_len_out, (hipStream_t)stream);
+}
+
+int rt_temporal_moments_default_params(rt_temporal_moments_params *out) {
+    if (!out) return fail("rt_temporal_moments_default_params: null out");
+    *out = temporal_moments_defaults();
+    return 0;
+}
+
+int rt_temporal_accumulate_moments_fixed(const int64_t *d_sum_a, int samples_a, const int64_t *d_sum_b, int samples_b, const int64_t *d_aov_fixed,
+                                         int aov_samples, const float *d_motion, const int64_t *d_hist_a_in, const int64_t *d_hist_b_in,
+                                         const int32_t *d_len_in, const int64_t *d_prev_aov_fixed, int prev_aov_samples, const float *d_prev_motion,
+                                         const float *d_moments_in, int width, int height, const rt_temporal_moments_params *params,
+                                         int64_t *d_hist_a_out, int64_t *d_hist_b_out, int32_t *d_len_out, float *d_moments_out,
+                                         float *d_variance_out, void *stream) {
+    return temporal_accumulate_moments_impl(d_sum_a, samples_a, d_sum_b, samples_b, d_aov_fixed, aov_samples, d_motion, d_hist_a_in, d_hist_b_in,
+                                            d_len_in, d_prev_aov_fixed, prev_aov_samples, d_prev_motion, d_moments_in, width, height, params,
+                                            d_hist_a_out, d_hist_b_out, d_len_out, d_moments_out, d_variance_out, (hipStream_t)stream);
+}
+
+int rt_denoise_variance_fixed(const int64_t *d_sum_fixed, int num_samples, const float *d_variance, const int64_t *d_aov_fixed, int aov_samples,
+                              int width, int height, const rt_denoise_dual_params *params, void *d_scratch, float *d_rgb_out, void *stream) {
+    return denoise_variance_impl(d_sum_fixed, num_samples, d_variance, d_aov_fixed, aov_samples, width, height, params, d_scratch, d_rgb_out,
+                                 (hipStream_t)stream);
 }
 
 int rt_post_process(float *d_rgb, int num_pixels, int num_samples, void *stream) {
