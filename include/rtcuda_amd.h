@@ -55,7 +55,10 @@ typedef struct rt_camera {
 
 typedef struct rt_scene rt_scene;
 
-/* Per-render counters (the reference has only stdout).  All counts are for THIS shard. */
+/* Per-render counters (the reference has only stdout).  All counts are for THIS shard.
+ * camera_rays and closest_rays count every camera ray the reference generates and traces, including those of background
+ * pixels -- pixels outside the rectangle the scene's bounds project to, whose rays cannot hit anything -- which the persistent
+ * kernel counts, draws the jitter of, and no longer walks.  bench.py's grays_per_s therefore includes them. */
 typedef struct rt_stats {
     int64_t camera_rays;     /* gen events      (render.cuh:250)  */
     int64_t shade_events;    /* mat events      (render.cuh:139)  */
@@ -80,7 +83,8 @@ typedef struct rt_stats {
                                 reserved[1] = nonzero when the frame ran as one persistent k_paths launch (then
                                 seconds_trace is that launch's duration and launches_trace is 1): 1 + the camera rays
                                 per task of the chunked deal of slots to lanes in its low 32 bits, so 1 = the static deal,
-                                and in the high 32 bits the slot sets a lane ran statically before that deal began;
+                                and in bits 32 .. 47 the slot sets a lane ran statically before that deal began; bit 48: the launch
+                                was a build that makes no camera ray for background pixels (k_paths_bg / k_paths_chunked_bg);
                                 reserved[2] = BVH node records that launch staged in LDS (small shards only);
                                 reserved[3] = rt_render_multi: number of device shards behind these totals;
                                 default kernels (no RT_FLAG_WATERTIGHT): reserved[4] = rays re-traced through the reference's

@@ -115,7 +115,8 @@ RT_DEV Rng rng_sample_stream(uint32_t seed_lo, uint32_t seed_hi, unsigned long l
     return r;
 }
 // curand_uniform: (0, 1]
-RT_DEV float rng_uniform(Rng &s) { return (float)rng_next(s) * 2.3283064e-10f + (2.3283064e-10f / 2.0f); }
+RT_DEV float rng_to_uniform(uint32_t draw) { return (float)draw * 2.3283064e-10f + (2.3283064e-10f / 2.0f); }
+RT_DEV float rng_uniform(Rng &s) { return rng_to_uniform(rng_next(s)); }
 
 // ------------------------------------------------------------------ triangle (triangle.cuh)
 struct Tri {

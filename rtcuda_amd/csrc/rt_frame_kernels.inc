@@ -2,6 +2,8 @@
 // persistent kernel).  Included by rtcuda_amd.hip once per source of camera rays, with
 //   RT_FRAME_SRC               Camera (gen()'s pinhole), RayTable (the caller's rays, rt_render_rays_*) or KeyedRayTable (the
 //                              caller's rays with a per-sample stream each, rt_render_rays_keyed_*): see gen_core
+//   RT_PATHS_BG                1 (RT_FRAME_SRC = Camera only): RT_K_PATHS is the build whose gen() passes over background pixels
+//                              (gen_background), a kernel of its own name for the same reason
 //   RT_K_ADVANCE / RT_K_PATHS  the names of the two kernels of that compilation
 //   RT_PATHS_CHUNKS            1: RT_K_PATHS is the build with the chunked deal (rt_slot_chunks.h), a kernel of its own name so
 //                              that the static deal keeps its code, instruction for instruction; only its 4-waves-per-SIMD
@@ -343,6 +345,7 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
     }
     // wave-uniform event counters
     unsigned long long n_gen = 0, n_shade = 0, n_traced = 0, n_shadow = 0, n_emit = 0, n_deposit = 0, n_rr = 0;
+    unsigned n_bg_lane = 0;  // per lane: background camera rays the GEN block passed over (below 2^31 in a frame)
 #ifdef RT_TRACE_PROFILE
     unsigned long long pf[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long pf_gen_cycles = 0, pf_fin_cycles = 0, pf_fin_lanes = 0, pf_fin_iters = 0;
@@ -537,6 +540,124 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
                 // (also for a lane that banked its slot and found the tasks out: it is idle from here on)
                 if (chunk_was_gen) acc_flush(acc, fb, ap_fb_fixed, chunk_acc_pixel);
             }
+#if RT_PATHS_BG
+            {
+                // The pinhole's gen(), as a wave-level loop that passes over background pixels (gen_background): a lane whose
+                // next camera ray cannot hit anything counts it, makes its two jitter draws and takes its slot's next generation
+                // in the same visit -- no ray, no scheduling round, no root node step, no second visit.  A turn of the loop is
+                // the same few instructions for every lane in it: the generation counter, the pixel stepped by (dpx, dpy), the
+                // two draws (kept: they are the jitter if the pixel is not background), the tests.  Everything else of gen() --
+                // divisions, camera.get_ray -- stands outside it, and the frame's words come out of the LDS once, as scalars.
+                // A lane leaves the loop with a ray to make; at the end of its chain (kDone / kParked: hand_back below); where
+                // its dealt chain reaches a chunk's end (it keeps PH_GEN: the next GEN block makes the hand-over, so the
+                // semaphores see what they saw without the loop); after one turn where the pixel cannot be stepped (dpy < 0: it
+                // keeps PH_GEN) or in the per-sample mode, where a background id is dropped without starting its stream and the
+                // lane draws another id in the next GEN block.
+                static_assert((kW & (kW - 1)) == 0, "a slot's camera rays are counted with a shift");
+                const bool was_gen = phase == PH_GEN;
+                const int f_width = __builtin_amdgcn_readfirstlane(ap.width), f_dpx = __builtin_amdgcn_readfirstlane(ap.dpx);
+                const int f_dpy = __builtin_amdgcn_readfirstlane(ap.dpy), f_last_gen = __builtin_amdgcn_readfirstlane(ap.last_gen);
+                const int f_cam_end = __builtin_amdgcn_readfirstlane((int)ap.cam_end);  // (below 2^31 - 13 W: render_shard_impl)
+                const int f_slot_lo = __builtin_amdgcn_readfirstlane(ap.slot_lo);
+                const int f_x0 = __builtin_amdgcn_readfirstlane(ap.bg_x0), f_y0 = __builtin_amdgcn_readfirstlane(ap.bg_y0);
+                const unsigned f_w = (unsigned)__builtin_amdgcn_readfirstlane(ap.bg_w), f_h = (unsigned)__builtin_amdgcn_readfirstlane(ap.bg_h);
+                const bool can_loop = !draw_cids && f_dpy >= 0;
+                // (scalars of this block only: nothing of the deal lives across the main loop)
+                const rtchunks::Multiple bg_m{CHUNKS ? __builtin_amdgcn_readfirstlane(s_task[2]) : 1u, CHUNKS ? __builtin_amdgcn_readfirstlane(s_task[3]) : 0u,
+                                              CHUNKS ? __builtin_amdgcn_readfirstlane(s_task[4]) : 0u};
+                const bool dealt = CHUNKS && chunk_g && slot_set >= (int)__builtin_amdgcn_readfirstlane(s_task[5]);
+                Rng g_rs{0, 0, 0, 0, 0, 0};
+                int g_gen = 0, g_stop = 0, px = 0, py = 0;
+                uint32_t draw_x = 0, draw_y = 0;
+                bool looking = false, made = false;  // made: the pixel the lane stopped at is not background
+                if (was_gen) {
+                    g_gen = cold[2 * kBlock];
+                    g_rs = Rng{(uint32_t)cold[3 * kBlock], (uint32_t)cold[4 * kBlock], (uint32_t)cold[5 * kBlock],
+                               (uint32_t)cold[6 * kBlock], (uint32_t)cold[7 * kBlock], (uint32_t)cold[8 * kBlock]};
+                    const int pxy = cold[12 * kBlock];
+                    if (!CHUNKS) acc_flush(acc, fb, ap_fb_fixed, cold[1 * kBlock]);  // the camera ray that ended: its sum -> its pixel
+                    // the generation at which gen()'s end tests stop the slot: its camera rays run out (gen W + slot >= cam_end)
+                    // or the lockstep final generation begins; a drawn id stops the lane if it lies past the frame
+                    const int slot = f_slot_lo + i;
+                    if (draw_cids) g_stop = my_cid >= (long long)f_cam_end ? g_gen : 0x7fffffff;
+                    else g_stop = min(f_last_gen, (f_cam_end - slot + (kW - 1)) >> __builtin_ctz((unsigned)kW));
+                    looking = g_gen < g_stop;
+                    px = pxy & 0xffff;
+                    py = pxy >> 16;
+                    if (looking && (pxy < 0 || !can_loop)) {
+                        // no previous pixel on this lane, or none to step from (odd spp, a frame too large, a drawn id): the next
+                        // pixel by gen()'s divisions, stepped BACK once -- the loop's first turn steps it forward again
+                        SlotState t;
+                        t.gen = g_gen + 1;
+                        int qx, qy;
+                        gen_pixel(ap, slot, t, nullptr, my_cid, my_cid >= 0 ? my_cid : (long long)g_gen * kW + slot, qx, qy);
+                        px = qx - f_dpx;
+                        py = qy - f_dpy;
+                        if (px < 0) {
+                            px += f_width;
+                            py--;
+                        }
+                    }
+                }
+                if (looking) {
+                    // (a lane's own loop: the lanes that are through drop out of the execution mask, and a turn moves no register
+                    // for them -- as `while (wave_ballot(looking)) if (looking) ...` it cost 25 register moves per turn)
+                    bool bg;
+                    do {
+                        g_gen++;
+                        px += f_dpx;
+                        py += f_dpy;
+                        if (px >= f_width) {
+                            px -= f_width;
+                            py++;
+                        }
+                        bg = (unsigned)(px - f_x0) >= f_w || (unsigned)(py - f_y0) >= f_h;  // gen_background
+                        if (draw_cids) {  // (every camera ray starts a stream of its own: none for a background id)
+                            if (!bg) {
+                                g_rs = rng_sample_stream(ap.seed_lo, ap.seed_hi, (unsigned long long)my_cid * (unsigned)ap.key_mul + (unsigned)ap.key_add);
+                                draw_x = rng_next(g_rs);
+                                draw_y = rng_next(g_rs);
+                            }
+                        } else {  // x first, then y (Appendix A.7): the slot's stream moves on as the reference's does
+                            draw_x = rng_next(g_rs);
+                            draw_y = rng_next(g_rs);
+                        }
+                        n_bg_lane += bg ? 1u : 0u;  // counted as the camera ray it is (camera_rays, closest_rays): summed at the exit
+                    } while (bg && can_loop && g_gen < g_stop && !(dealt && rtchunks::chunk_ends((unsigned)g_gen, bg_m, false)));
+                    made = !bg;
+                }
+                if (made) {
+                    camera_get_ray(cam, (px + rng_to_uniform(draw_x)) / ap.width, (py + rng_to_uniform(draw_y)) / ap.height, out.ray_o, out.ray_d);
+                    out.new_ray = true;
+                    out.did_gen = true;
+                }
+                if (was_gen) {
+                    // the slot state gen() leaves: bounces (0, or the kDone / kParked sentinel), gen, the RNG, the stepped pixel
+                    // coordinates; a new path also has its pixel and beta = 1
+                    int b = 0;
+                    if (!made && g_gen >= g_stop) {  // gen()'s end tests, in their order
+                        const long long cid = my_cid >= 0 ? my_cid : (long long)g_gen * kW + (f_slot_lo + i);
+                        b = cid >= ap.cam_end ? kDone : kParked;
+                        hand_back = true;  // (otherwise, without a ray: the lane keeps PH_GEN)
+                    }
+                    cold[0 * kBlock] = b;
+                    cold[2 * kBlock] = g_gen;
+                    cold[3 * kBlock] = (int)g_rs.d;
+                    cold[4 * kBlock] = (int)g_rs.v0;
+                    cold[5 * kBlock] = (int)g_rs.v1;
+                    cold[6 * kBlock] = (int)g_rs.v2;
+                    cold[7 * kBlock] = (int)g_rs.v3;
+                    cold[8 * kBlock] = (int)g_rs.v4;
+                    cold[12 * kBlock] = px | (py << 16);
+                    if (made) {
+                        cold[1 * kBlock] = py * f_width + px;
+                        cold[9 * kBlock] = __float_as_int(1.f);
+                        cold[10 * kBlock] = __float_as_int(1.f);
+                        cold[11 * kBlock] = __float_as_int(1.f);
+                    }
+                }
+            }
+#else
             if (phase == PH_GEN) {
                 SlotState st;
                 st.gen = cold[2 * kBlock];
@@ -568,6 +689,7 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
                     hand_back = true;  // out of camera rays, or parked for the lockstep final generation
                 }
             }
+#endif
             const bool nr = out.new_ray;
             o = out.ray_o;
             d = out.ray_d;
@@ -612,6 +734,7 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
             AdvanceOut out;
             out.did_gen = out.did_shade = out.has_shadow = out.did_emit = out.new_ray = false;
             out.rr_draws = 0;
+            out.bg_skipped = 0;
             if (phase == PH_ADV) {
                 // the slot state is only live between cold_load() and cold_save() below
                 cold_load();
@@ -654,7 +777,7 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
                 st.gen = gen;
                 st.rs = rs;
                 st.beta = beta;
-                advance_core<SPLIT_GEN, true, true>(sc, tab, cam, ap, ap.slot_lo + i, st, out, fb, acc);
+                advance_core<SPLIT_GEN, true, true, RT_PATHS_BG != 0>(sc, tab, cam, ap, ap.slot_lo + i, st, out, fb, acc);
                 RT_MARK("adv.tail");
                 bounces = st.bounces;
                 pixel = st.pixel;
@@ -704,6 +827,15 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
             // between a build with and without spills when the kernel sat at 128 VGPRs)
             inv = inv_dir(d);
             if (!SPLIT_GEN) n_gen += wave_count((out.did_gen));
+            if (!SPLIT_GEN && RT_PATHS_BG) {
+                // the background camera rays gen() passed over inside advance_core: camera rays like the others
+                int bg = out.bg_skipped;
+                if (wave_ballot(bg != 0)) {
+                    for (int off = 32; off > 0; off >>= 1) bg += __shfl_xor(bg, off);
+                    n_gen += (unsigned long long)bg;
+                    n_traced += (unsigned long long)bg;
+                }
+            }
             n_shade += wave_count((out.did_shade));
             n_traced += wave_count((out.new_ray));
             n_shadow += wave_count((out.has_shadow));
@@ -952,6 +1084,14 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
           rec[3] = pf[0] + pf[2] + pf[4];
           rec[4] = pf_idle;
           rec[5] = pf_idle_max; }
+#endif
+#if RT_PATHS_BG
+    if (SPLIT_GEN) {
+        unsigned long long bg = n_bg_lane;
+        for (int off = 32; off > 0; off >>= 1) bg += __shfl_xor(bg, off);
+        n_gen += bg;
+        n_traced += bg;
+    }
 #endif
     unsigned long long v[C_COUNT] = {n_gen, n_shade, n_traced, n_shadow, n_emit, n_deposit, n_rr, 0ull};
     row_add(rows, v);

@@ -15,6 +15,7 @@
 //   * rt_plan_paths_launch  the launch geometry of the persistent frame kernels (rt_launch_plan.h), as the library computes it.
 //   * rt_slot_chunk_*   the chunked deal of k_paths (rt_slot_chunks.h): task -> slot, the static deal's slots, the counts and
 //     the decisions, as the kernel makes them.
+//   * rt_background_rect  the pixel rectangle outside which k_paths makes no camera ray (rt_background.h), as the library computes it.
 //   * hc_denoise / hc_expnegf  the CPU twin of rt_denoise_fixed: a serial loop over rt_denoise.h, the arithmetic of the kernels.
 //   * hc_denoise_dual   the CPU twin of rt_denoise_dual_fixed, likewise; both walk the pixels with dn_walk, the twins' own loop.
 //   * hc_merge_shard_stats  the merge of the shards' rt_stats (rt_stats_merge.h), the library's own function.
@@ -26,6 +27,7 @@
 #include <cstdlib>
 #include <vector>
 
+#include "rt_background.h"
 #include "rt_bvh.h"
 #include "rt_denoise.h"
 #include "rt_launch_plan.h"
@@ -1001,6 +1003,18 @@ uint32_t rt_slot_chunk_sem_word(uint32_t idx) { return rtchunks::sem_word(idx); 
 uint32_t rt_slot_chunk_sem_unit(uint32_t idx) { return rtchunks::sem_unit(idx); }
 int rt_slot_chunk_sem_value(uint32_t word, uint32_t idx) { return rtchunks::sem_value(word, idx); }
 uint32_t rt_slot_chunk_sem_init() { return rtchunks::kSemWordInit; }
+// The pixel rectangle outside which k_paths makes no camera ray (rt_background.h, tests/test_background_rect_host.py), as
+// render_shard_impl computes it from the bounds lo / hi of the scene's records; out4 = {x0, y0, x1, y1}.  Returns 0, or 1
+// (and writes nothing) for a null argument or a frame without pixels.
+int rt_background_rect(const float cam12[12], int width, int height, const float lo[3], const float hi[3], int out4[4]) {
+    if (!cam12 || !lo || !hi || !out4 || width <= 0 || height <= 0) return 1;
+    const rtbg::Rect r = rtbg::background_rect(cam12, width, height, lo, hi);
+    out4[0] = r.x0;
+    out4[1] = r.y0;
+    out4[2] = r.x1;
+    out4[3] = r.y1;
+    return 0;
+}
 // The CPU twin of rt_denoise_fixed (tests/test_denoise_host.py): a plain serial loop over the arithmetic the kernels use
 // (rt_denoise.h), host buffers throughout, the same checks of the parameters.  Returns 0, or 1 and writes nothing.
 int hc_denoise(const int64_t *sum_fixed, int num_samples, const int64_t *aov_fixed, int aov_samples, int width, int height, int passes,

@@ -172,24 +172,42 @@ static TraceKernel trace_kernel(bool literal, bool verify, bool wide) {
 // block is the reference's own walk (full pool: the 4-wave build although it spills 53 VGPRs -- measured 1 082 ms for C2's
 // frame against 1 412 ms for the spill-free 2-wave build at half the occupancy).  Per-sample streams on the full pool: the
 // build in which the waves draw their camera rays from the frame's counter.
-template <bool LDS_TABLES, bool WIDE>
-static PathsKernel paths_kernel_of(bool few_blocks, bool per_sample, bool literal, bool verify) {
-    if (literal) return few_blocks ? k_paths<LDS_TABLES, false, 2, false, true, false> : k_paths<LDS_TABLES, false, 4, false, true, false>;
-    if (per_sample && !few_blocks) return k_paths<LDS_TABLES, WIDE, 4, true, false, false>;
-    if (few_blocks) return verify ? k_paths<LDS_TABLES, WIDE, 2, false, false, true> : k_paths<LDS_TABLES, WIDE, 2, false, false, false>;
-    return verify ? k_paths<LDS_TABLES, WIDE, 4, false, false, true> : k_paths<LDS_TABLES, WIDE, 4, false, false, false>;
-}
+// `bg`: the builds that pass over background pixels (k_paths_bg / k_paths_chunked_bg: rt_background.h), for a frame whose rectangle
+// is smaller than the frame; every other frame runs k_paths / k_paths_chunked, which carry nothing of it.
+#define RT_PATHS_KERNELS_OF(NAME, K_PATHS)                                                                                          \
+    template <bool LDS_TABLES, bool WIDE>                                                                                             \
+    static PathsKernel NAME(bool few_blocks, bool per_sample, bool literal, bool verify) {                                            \
+        if (literal) return few_blocks ? K_PATHS<LDS_TABLES, false, 2, false, true, false> : K_PATHS<LDS_TABLES, false, 4, false, true, false>; \
+        if (per_sample && !few_blocks) return K_PATHS<LDS_TABLES, WIDE, 4, true, false, false>;                                       \
+        if (few_blocks) return verify ? K_PATHS<LDS_TABLES, WIDE, 2, false, false, true> : K_PATHS<LDS_TABLES, WIDE, 2, false, false, false>; \
+        return verify ? K_PATHS<LDS_TABLES, WIDE, 4, false, false, true> : K_PATHS<LDS_TABLES, WIDE, 4, false, false, false>;         \
+    }
+RT_PATHS_KERNELS_OF(paths_kernel_of, k_paths)
+RT_PATHS_KERNELS_OF(paths_bg_kernel_of, k_paths_bg)
+#undef RT_PATHS_KERNELS_OF
 // the same 4-waves-per-SIMD reference-mode builds with the chunked deal compiled in (k_paths_chunked: rt_slot_chunks.h)
-template <bool LDS_TABLES, bool WIDE>
-static PathsKernel paths_chunked_kernel_of(bool literal, bool verify) {
-    if (literal) return k_paths_chunked<LDS_TABLES, false, 4, false, true, false>;
-    return verify ? k_paths_chunked<LDS_TABLES, WIDE, 4, false, false, true> : k_paths_chunked<LDS_TABLES, WIDE, 4, false, false, false>;
-}
-static PathsKernel paths_chunked_kernel(bool lds_tables, bool wide, bool literal, bool verify) {
+#define RT_PATHS_CHUNKED_KERNELS_OF(NAME, K_PATHS)                                                                                  \
+    template <bool LDS_TABLES, bool WIDE>                                                                                             \
+    static PathsKernel NAME(bool literal, bool verify) {                                                                              \
+        if (literal) return K_PATHS<LDS_TABLES, false, 4, false, true, false>;                                                        \
+        return verify ? K_PATHS<LDS_TABLES, WIDE, 4, false, false, true> : K_PATHS<LDS_TABLES, WIDE, 4, false, false, false>;         \
+    }
+RT_PATHS_CHUNKED_KERNELS_OF(paths_chunked_kernel_of, k_paths_chunked)
+RT_PATHS_CHUNKED_KERNELS_OF(paths_chunked_bg_kernel_of, k_paths_chunked_bg)
+#undef RT_PATHS_CHUNKED_KERNELS_OF
+static PathsKernel paths_chunked_kernel(bool lds_tables, bool wide, bool literal, bool verify, bool bg) {
+    if (bg) {
+        if (lds_tables) return (wide ? paths_chunked_bg_kernel_of<true, true> : paths_chunked_bg_kernel_of<true, false>)(literal, verify);
+        return (wide ? paths_chunked_bg_kernel_of<false, true> : paths_chunked_bg_kernel_of<false, false>)(literal, verify);
+    }
     if (lds_tables) return (wide ? paths_chunked_kernel_of<true, true> : paths_chunked_kernel_of<true, false>)(literal, verify);
     return (wide ? paths_chunked_kernel_of<false, true> : paths_chunked_kernel_of<false, false>)(literal, verify);
 }
-static PathsKernel paths_kernel(bool lds_tables, bool wide, bool few_blocks, bool per_sample, bool literal, bool verify) {
+static PathsKernel paths_kernel(bool lds_tables, bool wide, bool few_blocks, bool per_sample, bool literal, bool verify, bool bg) {
+    if (bg) {
+        if (lds_tables) return (wide ? paths_bg_kernel_of<true, true> : paths_bg_kernel_of<true, false>)(few_blocks, per_sample, literal, verify);
+        return (wide ? paths_bg_kernel_of<false, true> : paths_bg_kernel_of<false, false>)(few_blocks, per_sample, literal, verify);
+    }
     if (lds_tables) return (wide ? paths_kernel_of<true, true> : paths_kernel_of<true, false>)(few_blocks, per_sample, literal, verify);
     return (wide ? paths_kernel_of<false, true> : paths_kernel_of<false, false>)(few_blocks, per_sample, literal, verify);
 }
@@ -285,6 +303,7 @@ struct FrameRun {
     HitMode mode;
     bool lds_tables = false, persistent = true, finished = false, ran_lockstep = false;
     int cus = 0, stack_cap = 0, top_records_in_lds = 0, slot_chunk = 0, slot_head = 0, lock_enqueued = 0;
+    bool ran_bg = false;  // the persistent launch was k_paths_bg / k_paths_chunked_bg (a rectangle smaller than the frame)
     DScene sc{};
     Camera cam{};
     AdvanceParams ap{};
@@ -389,7 +408,10 @@ int FrameRun::run_persistent() {
     // carries the chunk; a frame of one generation runs no chain in k_paths -- every slot parks at once -- and keeps the static
     // deal, and so do ray tables)
     int chunk = (rays || p.few_blocks || per_sample || ap.last_gen < 1 || ap.n != c.n) ? 0 : rtplan::slot_chunk_for(p, ap.last_gen);
-    const PathsKernel chunked = paths_chunked_kernel(lds_tables, scene->wide, mode.literal, mode.verify);
+    // (a rectangle smaller than the frame: the builds that pass over background pixels)
+    const bool bg = !rays && (long long)ap.bg_w * ap.bg_h < (long long)ap.width * ap.height;
+    ran_bg = bg;
+    const PathsKernel chunked = paths_chunked_kernel(lds_tables, scene->wide, mode.literal, mode.verify, bg);
     if (chunk > 0) {  // (its semaphores are 2 KB of static LDS: beside large tables in LDS they would cost a resident workgroup)
         int per_cu = 0;
         HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, chunked, kBlock, p.lds_bytes));
@@ -402,7 +424,7 @@ int FrameRun::run_persistent() {
     if (rays && rays->keyed) launch_paths(paths_keyed_kernel(lds_tables, p.few_blocks), rays->keyed_table, p.top_n);
     else if (rays) launch_paths(paths_rays_kernel(lds_tables, p.few_blocks, mode.verify), rays->table, p.top_n);
     else if (chunk > 0) launch_paths(chunked, cam, chunk | (slot_head << rtplan::kChunkHeadShift));
-    else launch_paths(paths_kernel(lds_tables, scene->wide, p.few_blocks, per_sample, mode.literal, mode.verify), cam, mode.literal ? 0 : p.top_n);
+    else launch_paths(paths_kernel(lds_tables, scene->wide, p.few_blocks, per_sample, mode.literal, mode.verify, bg), cam, mode.literal ? 0 : p.top_n);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(c.ev_b, st));
     HIP_TRY(hipEventSynchronize(c.ev_b));
@@ -561,7 +583,7 @@ int FrameRun::frame_stats(rt_stats *stats) {
         stats->seconds_advance = 0.0;
         stats->launches_trace = 1;
         stats->reserved[0] = 1;
-        stats->reserved[1] = 1 + slot_chunk + ((int64_t)slot_head << 32);
+        stats->reserved[1] = 1 + slot_chunk + ((int64_t)slot_head << 32) + ((int64_t)(ran_bg ? 1 : 0) << 48);
         stats->reserved[2] = top_records_in_lds;
     }
     rare_path_counters(h_final.vstat, &stats->reserved[4]);
@@ -658,6 +680,26 @@ int render_shard_impl(const rt_scene *scene, const rt_camera *camera, int width,
     ap.w_over_spp = (kW % spp == 0 && !rays) ? kW / spp : 0;  // (the pixel stepping is the camera frames')
     ap.dpx = ap.w_over_spp % width;
     ap.dpy = (ap.w_over_spp > 0 && width < 32768 && height < 32768) ? ap.w_over_spp / width : -1;
+    // The pixels whose camera rays can hit something (rt_background.h): k_paths_bg / k_paths_chunked_bg make no ray outside them.  Per
+    // call, from the bounds of the records as they are now (after a refit, a rebuild or an edit: the new ones) and the radius they
+    // are padded for.  Camera frames of 4-wide scenes; the whole frame otherwise, and with RT_BG_SKIP=0 (an experiment knob).
+    ap.bg_x0 = ap.bg_y0 = 0;
+    ap.bg_w = width;
+    ap.bg_h = height;
+    if (!rays && scene->wide) {
+        bool skip = true;
+        if (const char *e = knob("RT_BG_SKIP")) skip = atoi(e) != 0;
+        std::lock_guard<std::mutex> pad_lock(scene->pad_mutex);  // (h_quads and origin_radius: their writers hold it)
+        if (skip && scene->h_quads.size() >= 2) {
+            float lo[3], hi[3];
+            rtbg::root_bounds(scene->h_quads.data(), (int)rtbvh::kNoChild, lo, hi);  // (no child: lo > hi, the empty rectangle)
+            const rtbg::Rect r = rtbg::background_rect((const float *)camera, width, height, lo, hi, scene->origin_radius);
+            ap.bg_x0 = r.x0;
+            ap.bg_y0 = r.y0;
+            ap.bg_w = r.x1 - r.x0;
+            ap.bg_h = r.y1 - r.y0;
+        }
+    }
     f.lds_tables = scene->n_mats <= kLdsTable && scene->n_lights <= kLdsTable;
 
     HIP_TRY(hipEventCreate(&f.ev_start));

@@ -82,6 +82,7 @@
 #include <vector>
 
 #include "../../include/rtcuda_amd.h"
+#include "rt_background.h"
 #include "rt_bvh.h"
 #include "rt_denoise.h"
 #include "rt_device.h"
@@ -330,6 +331,11 @@ struct AdvanceParams {
     // (rank `key_add` of `key_mul` renders the frame at spp / key_mul with the full slot pool); no slot parks
     int per_sample, key_mul, key_add;
     uint32_t seed_lo, seed_hi;
+    // The pixels [bg_x0, bg_x0 + bg_w) x [bg_y0, bg_y0 + bg_h) outside which no camera ray of the frame can hit the scene
+    // (rt_background.h; the whole frame where nothing is known, bg_w = 0 where nothing can be hit).  Read by k_paths_bg /
+    // k_paths_chunked_bg only, which a frame runs if the rectangle is smaller than it: they make no ray for a pixel outside it
+    // (gen_background).
+    int bg_x0, bg_y0, bg_w, bg_h;
 };
 
 constexpr int kLdsTable = 64;                   // materials / lights staged in LDS per workgroup
@@ -463,6 +469,7 @@ struct AdvanceOut {
     bool did_gen, did_shade, has_shadow, did_emit, new_ray;
     bool wants_gen;             // advance_core<DEFER_GEN = true> only: the slot's next step is gen()
     int rr_draws;
+    int bg_skipped;             // advance_core of k_paths' 2-waves-per-SIMD camera builds only: background camera rays gen() passed over
     V3 ray_o, ray_d;            // next path ray (valid when new_ray)
     V3 s_o, s_d, s_L;           // shadow ray + radiance to deposit if unoccluded (valid when has_shadow)
     float s_tmax;
@@ -508,20 +515,91 @@ __device__ __forceinline__ T table_load(const T *q) {
 // the wave drew from the frame's counter -- with a stream of its own per camera ray, any lane can take any camera ray.
 // SRC: where camera ray `cid` comes from -- Camera: gen()'s pinhole; RayTable: the caller's table (rt_render_rays_*).  A
 // property of the kernel build (a type, so a compile-time choice): the camera builds carry nothing of the table.
-template <bool NEVER_LOCKSTEP = false, class SRC>
-__device__ __forceinline__ void gen_core(const SRC &cam, const AdvanceParams &ap, int slot_global, SlotState &st,
-                                         AdvanceOut &out, int *pxy = nullptr, long long cid_given = -1) {
+// The pieces of gen()'s pinhole, in the order gen_core runs them (k_paths' GEN block runs them itself, as a wave-level loop
+// that passes over background pixels).
+// gen_begin: the end tests, then the slot's generation counter moves on.  false: no ray (st.bounces = kDone / kParked).
+template <bool NEVER_LOCKSTEP>
+__device__ __forceinline__ bool gen_begin(const AdvanceParams &ap, int slot_global, SlotState &st, long long cid_given, long long &cid) {
     const bool lockstep = NEVER_LOCKSTEP ? false : (ap.lockstep != 0);
-    long long cid = cid_given >= 0 ? cid_given : (long long)st.gen * kW + slot_global;
+    cid = cid_given >= 0 ? cid_given : (long long)st.gen * kW + slot_global;
     if (cid >= ap.cam_end) {
         st.bounces = kDone;
-        return;
+        return false;
     }
     if (!lockstep && st.gen == ap.last_gen) {
         st.bounces = kParked;
-        return;
+        return false;
     }
     st.gen = st.gen + 1;
+    return true;
+}
+// gen_pixel: the pixel of camera ray `cid` (st.gen already counts it) into st.pixel and (px, py); *pxy follows.
+__device__ __forceinline__ void gen_pixel(const AdvanceParams &ap, int slot_global, SlotState &st, int *pxy, long long cid_given,
+                                          long long cid, int &px, int &py) {
+    // pixel = camera_ray_id / spp (render.cuh:254-256).  cid = gen * W + slot, so when spp divides W the quotient
+    // splits exactly into two 32-bit terms; the general case keeps the 64-bit division.
+    if (cid_given >= 0) {
+        st.pixel = (int)((unsigned)cid / (unsigned)ap.spp);  // (camera-ray ids stay below 2^31: rt_render_shard checks)
+        py = (int)((unsigned)st.pixel / (unsigned)ap.width);
+        px = st.pixel - py * ap.width;
+    } else if (pxy && ap.dpy >= 0 && *pxy >= 0) {
+        px = (*pxy & 0xffff) + ap.dpx;
+        py = (*pxy >> 16) + ap.dpy;
+        if (px >= ap.width) {
+            px -= ap.width;
+            py++;
+        }
+        st.pixel = py * ap.width + px;
+    } else {
+        if (ap.w_over_spp) st.pixel = (st.gen - 1) * ap.w_over_spp + (int)((unsigned)slot_global / (unsigned)ap.spp);  // (gen already counts this ray)
+        else st.pixel = (int)(cid / ap.spp);
+        py = (int)((unsigned)st.pixel / (unsigned)ap.width);  // (both non-negative: the unsigned divide is the cheaper one)
+        px = st.pixel - py * ap.width;
+    }
+    if (pxy) *pxy = px | (py << 16);
+}
+// gen_background (k_paths' camera builds): no ray through this pixel can hit the scene (AdvanceParams::bg_*, rt_background.h).
+// Such a camera ray is counted and its two jitter draws are made -- the slot's stream stays where the reference's is -- but
+// no ray is made or walked: it would miss, deposit nothing and use no further draw.
+__device__ __forceinline__ bool gen_background(const AdvanceParams &ap, int px, int py) {
+    return (unsigned)(px - ap.bg_x0) >= (unsigned)ap.bg_w || (unsigned)(py - ap.bg_y0) >= (unsigned)ap.bg_h;
+}
+// gen_camera_ray: the stream (per-sample mode), the two jitter draws, camera.get_ray; the slot starts a new path.
+__device__ __forceinline__ void gen_camera_ray(const Camera &cam, const AdvanceParams &ap, long long cid, int px, int py, SlotState &st,
+                                               AdvanceOut &out) {
+    if (ap.per_sample) st.rs = rng_sample_stream(ap.seed_lo, ap.seed_hi, (unsigned long long)cid * (unsigned)ap.key_mul + (unsigned)ap.key_add);
+    float jx = rng_uniform(st.rs);  // x first, then y (Appendix A.7)
+    float jy = rng_uniform(st.rs);
+    camera_get_ray(cam, (px + jx) / ap.width, (py + jy) / ap.height, out.ray_o, out.ray_d);
+    out.new_ray = true;
+    st.bounces = 0;
+    st.beta = mk(1.f, 1.f, 1.f);
+    out.did_gen = true;
+}
+
+// BG_SKIP (advance_core of k_paths_bg's 2-waves-per-SIMD builds, where gen() stays inside the ADV block): a background
+// camera ray (gen_background) is passed over on the spot -- counted in out.bg_skipped, its two draws made unless every
+// camera ray starts a stream of its own -- and the lane takes its slot's next generation.
+template <bool NEVER_LOCKSTEP = false, bool BG_SKIP = false, class SRC>
+__device__ __forceinline__ void gen_core(const SRC &cam, const AdvanceParams &ap, int slot_global, SlotState &st,
+                                         AdvanceOut &out, int *pxy = nullptr, long long cid_given = -1) {
+    long long cid;
+    if constexpr (BG_SKIP && std::is_same<SRC, Camera>::value) {
+        int px, py;
+        while (true) {
+            if (!gen_begin<NEVER_LOCKSTEP>(ap, slot_global, st, cid_given, cid)) return;
+            gen_pixel(ap, slot_global, st, pxy, cid_given, cid, px, py);
+            if (!gen_background(ap, px, py)) break;
+            if (!ap.per_sample) {
+                rng_next(st.rs);
+                rng_next(st.rs);
+            }
+            out.bg_skipped++;
+        }
+        gen_camera_ray(cam, ap, cid, px, py, st, out);
+        return;
+    }
+    if (!gen_begin<NEVER_LOCKSTEP>(ap, slot_global, st, cid_given, cid)) return;
     if constexpr (std::is_same<SRC, KeyedRayTable>::value) {
         // Keyed ray-table frames: row `cid` starts the per-sample stream of its key (whatever stream the lane held), gen()'s
         // two jitter draws are made and dropped -- a pinhole's own table reproduces the RT_FLAG_RNG_PER_SAMPLE frame draw for
@@ -565,41 +643,14 @@ __device__ __forceinline__ void gen_core(const SRC &cam, const AdvanceParams &ap
         out.did_gen = true;
         return;
     } else {
-    // pixel = camera_ray_id / spp (render.cuh:254-256).  cid = gen * W + slot, so when spp divides W the quotient
-    // splits exactly into two 32-bit terms; the general case keeps the 64-bit division.
-    int px, py;
-    if (cid_given >= 0) {
-        st.pixel = (int)((unsigned)cid / (unsigned)ap.spp);  // (camera-ray ids stay below 2^31: rt_render_shard checks)
-        py = (int)((unsigned)st.pixel / (unsigned)ap.width);
-        px = st.pixel - py * ap.width;
-    } else if (pxy && ap.dpy >= 0 && *pxy >= 0) {
-        px = (*pxy & 0xffff) + ap.dpx;
-        py = (*pxy >> 16) + ap.dpy;
-        if (px >= ap.width) {
-            px -= ap.width;
-            py++;
-        }
-        st.pixel = py * ap.width + px;
-    } else {
-        if (ap.w_over_spp) st.pixel = (st.gen - 1) * ap.w_over_spp + (int)((unsigned)slot_global / (unsigned)ap.spp);  // (gen already counts this ray)
-        else st.pixel = (int)(cid / ap.spp);
-        py = (int)((unsigned)st.pixel / (unsigned)ap.width);  // (both non-negative: the unsigned divide is the cheaper one)
-        px = st.pixel - py * ap.width;
-    }
-    if (pxy) *pxy = px | (py << 16);
-    if (ap.per_sample) st.rs = rng_sample_stream(ap.seed_lo, ap.seed_hi, (unsigned long long)cid * (unsigned)ap.key_mul + (unsigned)ap.key_add);
-    float jx = rng_uniform(st.rs);  // x first, then y (Appendix A.7)
-    float jy = rng_uniform(st.rs);
-    camera_get_ray(cam, (px + jx) / ap.width, (py + jy) / ap.height, out.ray_o, out.ray_d);
-    out.new_ray = true;
-    st.bounces = 0;
-    st.beta = mk(1.f, 1.f, 1.f);
-    out.did_gen = true;
+        int px, py;
+        gen_pixel(ap, slot_global, st, pxy, cid_given, cid, px, py);
+        gen_camera_ray(cam, ap, cid, px, py, st, out);
     }
 }
 
 // `acc` (USE_ACC, k_paths only): the lane's sample accumulator; otherwise contributions go straight into the framebuffer.
-template <bool DEFER_GEN, bool NEVER_LOCKSTEP = false, bool USE_ACC = false, class SRC>
+template <bool DEFER_GEN, bool NEVER_LOCKSTEP = false, bool USE_ACC = false, bool BG_SKIP = false, class SRC>
 __device__ __forceinline__ void advance_core(const DScene &sc, const float *tab, const SRC &cam,
                                              const AdvanceParams &ap, int slot_global, SlotState &st, AdvanceOut &out,
                                              float *__restrict__ fb, float *acc = nullptr) {
@@ -608,6 +659,7 @@ __device__ __forceinline__ void advance_core(const DScene &sc, const float *tab,
     const int off_lpre = tab_off_lpre(sc.num_mats, sc.num_lights);
     out.did_gen = out.did_shade = out.has_shadow = out.did_emit = out.new_ray = out.wants_gen = false;
     out.rr_draws = 0;
+    out.bg_skipped = 0;
     const bool hit = st.hit_info >= 0;
     const int light_of_hit = hit ? ((st.hit_info >> 16) & 0xffff) - 1 : -1;
     // Emulate consecutive init() calls (render.cuh:84-137) until one of them ends in mat() or gen(): a slot whose
@@ -656,7 +708,7 @@ __device__ __forceinline__ void advance_core(const DScene &sc, const float *tab,
             return;
         }
         if (USE_ACC) acc_flush(acc, fb, ap.fb_fixed, st.pixel);  // the camera ray that ends here: its sum -> its pixel
-        gen_core<NEVER_LOCKSTEP>(cam, ap, slot_global, st, out);
+        gen_core<NEVER_LOCKSTEP, BG_SKIP>(cam, ap, slot_global, st, out);
         return;
     }
     // ---- mat() :139-248
@@ -809,6 +861,7 @@ constexpr bool kSpeculate = RT_SPECULATE != 0;  // k_paths: postpone a leaf reac
 constexpr int kProfRec = 6;  // qwords of k_paths' per-wave record (behind the 24 totals)
 #endif
 #define RT_PATHS_CHUNKS 0
+#define RT_PATHS_BG 0
 #define RT_FRAME_SRC Camera
 #define RT_K_ADVANCE k_advance
 #define RT_K_PATHS k_paths
@@ -845,6 +898,29 @@ constexpr int kProfRec = 6;  // qwords of k_paths' per-wave record (behind the 2
 #undef RT_K_ADVANCE
 #undef RT_K_PATHS
 #undef RT_PATHS_CHUNKS
+// and both camera builds once more with the background skip compiled into gen() (rt_background.h; gen_background): k_paths_bg and
+// k_paths_chunked_bg, launched instead of k_paths / k_paths_chunked when the frame's rectangle is smaller than the frame (their
+// k_advance twins are never instantiated).  Kernels of their own name so that a frame with nothing to skip keeps its code,
+// instruction for instruction: the skipping GEN block with a whole-frame rectangle cost C2 3 %.
+#undef RT_PATHS_BG
+#define RT_PATHS_BG 1
+#define RT_PATHS_CHUNKS 0
+#define RT_FRAME_SRC Camera
+#define RT_K_ADVANCE k_advance_bg_unused
+#define RT_K_PATHS k_paths_bg
+#include "rt_frame_kernels.inc"
+#undef RT_K_ADVANCE
+#undef RT_K_PATHS
+#undef RT_PATHS_CHUNKS
+#define RT_PATHS_CHUNKS 1
+#define RT_K_ADVANCE k_advance_chunked_bg_unused
+#define RT_K_PATHS k_paths_chunked_bg
+#include "rt_frame_kernels.inc"
+#undef RT_FRAME_SRC
+#undef RT_K_ADVANCE
+#undef RT_K_PATHS
+#undef RT_PATHS_CHUNKS
+#undef RT_PATHS_BG
 
 // post_process_framebuffer (render.cuh:330-338): c = sqrt(c * (1/spp))
 __global__ void k_post_process(float *fb, int n_values, float inv_spp) {

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A/B timing of the frame under environment knobs, in ONE process on ONE box (boxes differ by a percent or two).
 
-usage: ab_bench.py [--scene full_bsdf] [--spp 256] [--reps 3] [--shards 1] "K1=V1,K2=V2" "K1=V3" ...
+usage: ab_bench.py [--scene full_bsdf] [--spp 256] [--reps 3] [--shards 1] [--lookfrom x,y,z] [--lookat x,y,z] "K1=V1,K2=V2" "K1=V3" ...
        (an empty string "" = the defaults; knobs read at scene creation -- RT_BVH_* -- get a scene of their own)
 
 Prints one line per setting: frame time (best and mean of `reps` after one warm-up), the kernel's own time, and the
@@ -16,14 +16,15 @@ import torch  # noqa: E402
 from rtcuda_amd import api, scenes  # noqa: E402
 
 args = sys.argv[1:]
-opts = {"--scene": "full_bsdf", "--spp": "256", "--reps": "3", "--shards": "1"}
+opts = {"--scene": "full_bsdf", "--spp": "256", "--reps": "3", "--shards": "1", "--lookfrom": "0.5,0.5,1.5", "--lookat": "0.5,0.5,0"}
 while args and args[0] in opts:
     opts[args[0]] = args[1]
     args = args[2:]
 variant, spp, reps, shards = opts["--scene"], int(opts["--spp"]), int(opts["--reps"]), int(opts["--shards"])
 w, h = 1920, 1080
 arrays = scenes.cornell_bunny(variant)
-cam = api.make_camera(aspect=w / h)
+cam = api.make_camera(lookfrom=tuple(float(v) for v in opts["--lookfrom"].split(",")),
+                      lookat=tuple(float(v) for v in opts["--lookat"].split(",")), aspect=w / h)
 fb = torch.zeros(h * w * 3, dtype=torch.float32, device="cuda")
 base = None
 for setting in (args or [""]):
