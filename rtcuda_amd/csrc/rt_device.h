@@ -84,14 +84,20 @@ RT_DEV V3 refract4(V3 unit_v, V3 unit_n, float eta_ratio, float cos_theta) {  //
 struct Rng {
     uint32_t d, v0, v1, v2, v3, v4;
 };
-RT_DEV uint32_t rng_next(Rng &s) {
+constexpr uint32_t kRngWeyl = 362437u;
+// one step of the shift register alone: a draw is its newest word, v4, plus the Weyl word d (rng_next).  For a caller that
+// makes many draws and adds up d's steps itself.
+RT_DEV void rng_step(Rng &s) {
     uint32_t t = s.v0 ^ (s.v0 >> 2);
     s.v0 = s.v1;
     s.v1 = s.v2;
     s.v2 = s.v3;
     s.v3 = s.v4;
     s.v4 = (s.v4 ^ (s.v4 << 4)) ^ (t ^ (t << 1));
-    s.d += 362437u;
+}
+RT_DEV uint32_t rng_next(Rng &s) {
+    rng_step(s);
+    s.d += kRngWeyl;
     return s.v4 + s.d;
 }
 // RT_FLAG_RNG_PER_SAMPLE: the stream of ONE camera ray, keyed by (seed, global camera-ray id) -- not the reference's

@@ -14,6 +14,13 @@
 #ifndef RT_CHUNK_RELEASE_WAIT
 #define RT_CHUNK_RELEASE_WAIT 1
 #endif
+// the chunked deal's static head in the GEN block of RT_K_PATHS: the skipping build has read it once, as a scalar (tk_head)
+#undef RT_GEN_CHUNK_HEAD
+#if RT_PATHS_BG
+#define RT_GEN_CHUNK_HEAD (int)tk_head
+#else
+#define RT_GEN_CHUNK_HEAD (int)s_task[5]
+#endif
 
 // k_advance: one slot per thread, state in the pools.
 // Every per-slot input is indexed by the slot id, so all of a lane's loads are issued together
@@ -174,9 +181,10 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
     // static deal.  These builds keep no records of the tree in LDS, so G travels in `top_n`, and above G's bits the static
     // head: the slot sets a lane runs as in the static deal before it draws its first task.
     constexpr bool CHUNKS = RT_PATHS_CHUNKS && SPLIT_GEN && !DRAW_CIDS;
-    // [0]: the workgroup's next task; [1]: G; [2 .. 4]: rtchunks::multiple_of(G); [5]: the static head.  The GEN block reads G,
-    // the three words and the head from here: as scalars kept across the main loop they pushed other scalars out into VGPR
-    // lanes (53 more v_readlane in the default build, and the static deal 2.5 % slower than without this code).
+    // [0]: the workgroup's next task; [1]: G; [2 .. 4]: rtchunks::multiple_of(G); [5]: the static head; [6] (the skipping build):
+    // rtchunks::next_multiple_mul(G).  The GEN block reads G, the words and the head from here: as scalars kept across the main
+    // loop they pushed other scalars out into VGPR lanes (53 more v_readlane in the default build, and the static deal 2.5 %
+    // slower than without this code).
     __shared__ __attribute__((aligned(16))) unsigned s_task[CHUNKS ? 8 : 1];
     // the semaphores of the workgroup's dealt entries, two 16-bit fields to a word (rt_slot_chunks.h): all banked
     __shared__ unsigned s_sem[CHUNKS ? rtchunks::kSemWords : 1];
@@ -192,6 +200,9 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
             s_task[3] = m.shift;
             s_task[4] = m.limit;
             s_task[5] = chunk_head0;
+#if RT_PATHS_BG
+            s_task[6] = rtchunks::next_multiple_mul(chunk_g0 ? chunk_g0 : 1u);  // [6]: for the limit of a run over background pixels
+#endif
         }
     }
     const bool chunk_start = CHUNKS && chunk_g0 && chunk_head0 == 0u;  // no static head: the lane starts without a slot
@@ -447,14 +458,32 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
                 }
             }
             const unsigned chunk_g = CHUNKS ? __builtin_amdgcn_readfirstlane(s_task[1]) : 0u;
+#if RT_PATHS_BG
+            // the deal's other words, out of the LDS once per block and as scalars: [2 .. 3] and [4 .. 7] in one read each
+            unsigned tk_inv = 1u, tk_shift = 0u, tk_limit = 0u, tk_head = 0u, tk_mul = 0u;
+            if (CHUNKS) {
+                const uint2 lo = *(const uint2 *)&s_task[2];
+                const uint4 hi = *(const uint4 *)&s_task[4];
+                tk_inv = __builtin_amdgcn_readfirstlane(lo.x);
+                tk_shift = __builtin_amdgcn_readfirstlane(lo.y);
+                tk_limit = __builtin_amdgcn_readfirstlane(hi.x);
+                tk_head = __builtin_amdgcn_readfirstlane(hi.y);
+                tk_mul = __builtin_amdgcn_readfirstlane(hi.z);
+            }
+#endif
             // The camera ray that ended: its sum goes to its pixel AFTER the hand-over (whose waits for the state's stores and
             // loads would otherwise also sit through the float atomics' acknowledgements), so the pixel is read before the
             // hand-over puts another slot's state into the lane's column.  A lane that comes without a slot has an empty sum.
             const bool chunk_was_gen = CHUNKS && phase == PH_GEN;
             const int chunk_acc_pixel = CHUNKS ? cold[1 * kBlock] : 0;
             if (CHUNKS && chunk_g) {
+#if RT_PATHS_BG
+                const rtchunks::Multiple chunk_m{tk_inv, tk_shift, tk_limit};
+                const unsigned chunk_head = tk_head;
+#else
                 const rtchunks::Multiple chunk_m{s_task[2], s_task[3], s_task[4]};
                 const unsigned chunk_head = __builtin_amdgcn_readfirstlane(s_task[5]);
+#endif
                 // A lane past its static head: without a slot it takes one; with its slot at a chunk's end it banks it (or keeps
                 // it, if another lane has left a claim) -- rt_slot_chunks.h.  Behind a wave vote: once per G camera rays of a lane.
                 // (a lane inside its static head, slot_set < head, has a slot until the head is done and is at no chunk's end)
@@ -544,15 +573,21 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
             {
                 // The pinhole's gen(), as a wave-level loop that passes over background pixels (gen_background): a lane whose
                 // next camera ray cannot hit anything counts it, makes its two jitter draws and takes its slot's next generation
-                // in the same visit -- no ray, no scheduling round, no root node step, no second visit.  A turn of the loop is
-                // the same few instructions for every lane in it: the generation counter, the pixel stepped by (dpx, dpy), the
-                // two draws (kept: they are the jitter if the pixel is not background), the tests.  Everything else of gen() --
-                // divisions, camera.get_ray -- stands outside it, and the frame's words come out of the LDS once, as scalars.
+                // in the same visit -- no ray, no scheduling round, no root node step, no second visit.  The block waits for
+                // the lane with the longest run, so a turn of the loop is kept to what changes from one camera ray to the next:
+                // the generation counter, the pixel stepped by (dpx, dpy), the rectangle test, the two steps of the XORWOW shift
+                // register, and ONE stop test, `background and below g_limit`.  Everything that can end a run but a pixel inside
+                // the rectangle is folded into g_limit before the loop (rtchunks::run_limit): the end of the slot's chain
+                // (g_stop), for a dealt lane the next chunk's end, and one turn where the pixel cannot be stepped (dpy < 0) or
+                // in the per-sample mode.  What the turns add up to is taken after the loop from the number of turns: the Weyl
+                // word of the stream, the two draws (the last two words of the register: the jitter if the pixel is not
+                // background) and the count of passed rays.  The rest of gen() -- divisions, camera.get_ray -- stands outside
+                // too, and the frame's words come out of the LDS once, as scalars.
                 // A lane leaves the loop with a ray to make; at the end of its chain (kDone / kParked: hand_back below); where
                 // its dealt chain reaches a chunk's end (it keeps PH_GEN: the next GEN block makes the hand-over, so the
-                // semaphores see what they saw without the loop); after one turn where the pixel cannot be stepped (dpy < 0: it
-                // keeps PH_GEN) or in the per-sample mode, where a background id is dropped without starting its stream and the
-                // lane draws another id in the next GEN block.
+                // semaphores see what they saw without the loop); after its one turn where it has no more (it keeps PH_GEN; in
+                // the per-sample mode a background id is dropped without starting its stream and the lane draws another id in
+                // the next GEN block).
                 static_assert((kW & (kW - 1)) == 0, "a slot's camera rays are counted with a shift");
                 const bool was_gen = phase == PH_GEN;
                 const int f_width = __builtin_amdgcn_readfirstlane(ap.width), f_dpx = __builtin_amdgcn_readfirstlane(ap.dpx);
@@ -562,12 +597,10 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
                 const int f_x0 = __builtin_amdgcn_readfirstlane(ap.bg_x0), f_y0 = __builtin_amdgcn_readfirstlane(ap.bg_y0);
                 const unsigned f_w = (unsigned)__builtin_amdgcn_readfirstlane(ap.bg_w), f_h = (unsigned)__builtin_amdgcn_readfirstlane(ap.bg_h);
                 const bool can_loop = !draw_cids && f_dpy >= 0;
-                // (scalars of this block only: nothing of the deal lives across the main loop)
-                const rtchunks::Multiple bg_m{CHUNKS ? __builtin_amdgcn_readfirstlane(s_task[2]) : 1u, CHUNKS ? __builtin_amdgcn_readfirstlane(s_task[3]) : 0u,
-                                              CHUNKS ? __builtin_amdgcn_readfirstlane(s_task[4]) : 0u};
-                const bool dealt = CHUNKS && chunk_g && slot_set >= (int)__builtin_amdgcn_readfirstlane(s_task[5]);
+                // (the deal's words are scalars of this block only: nothing of the deal lives across the main loop)
+                const bool dealt = CHUNKS && chunk_g && slot_set >= (int)tk_head;
                 Rng g_rs{0, 0, 0, 0, 0, 0};
-                int g_gen = 0, g_stop = 0, px = 0, py = 0;
+                int g_gen = 0, g_stop = 0, g_limit = 0, px = 0, py = 0;
                 uint32_t draw_x = 0, draw_y = 0;
                 bool looking = false, made = false;  // made: the pixel the lane stopped at is not background
                 if (was_gen) {
@@ -582,15 +615,19 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
                     if (draw_cids) g_stop = my_cid >= (long long)f_cam_end ? g_gen : 0x7fffffff;
                     else g_stop = min(f_last_gen, (f_cam_end - slot + (kW - 1)) >> __builtin_ctz((unsigned)kW));
                     looking = g_gen < g_stop;
+                    g_limit = (int)rtchunks::run_limit((unsigned)g_gen, (unsigned)g_stop, dealt, can_loop, chunk_g, tk_mul);
                     px = pxy & 0xffff;
                     py = pxy >> 16;
                     if (looking && (pxy < 0 || !can_loop)) {
                         // no previous pixel on this lane, or none to step from (odd spp, a frame too large, a drawn id): the next
-                        // pixel by gen()'s divisions, stepped BACK once -- the loop's first turn steps it forward again
+                        // pixel by gen()'s divisions, stepped BACK once -- the loop's first turn steps it forward again.  The id
+                        // is below cam_end here (g_gen < g_stop), so below 2^31, and gen_pixel's form for a given id divides in
+                        // 32 bits: the same integers as the 64-bit quotient.
                         SlotState t;
                         t.gen = g_gen + 1;
                         int qx, qy;
-                        gen_pixel(ap, slot, t, nullptr, my_cid, my_cid >= 0 ? my_cid : (long long)g_gen * kW + slot, qx, qy);
+                        const unsigned cid32 = draw_cids ? (unsigned)my_cid : (unsigned)g_gen * (unsigned)kW + (unsigned)slot;
+                        gen_pixel(ap, slot, t, nullptr, (long long)cid32, (long long)cid32, qx, qy);
                         px = qx - f_dpx;
                         py = qy - f_dpy;
                         if (px < 0) {
@@ -603,28 +640,43 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
                     // (a lane's own loop: the lanes that are through drop out of the execution mask, and a turn moves no register
                     // for them -- as `while (wave_ballot(looking)) if (looking) ...` it cost 25 register moves per turn)
                     bool bg;
+                    const int g_entry = g_gen;
+                    RT_MARK("gen.loop.begin");
                     do {
                         g_gen++;
+                        // the pixel stepped by (dpx, dpy) with the carry of a row's end: px + dpx < 2 width, so the wrapped
+                        // column is the smaller of the two as unsigned numbers
                         px += f_dpx;
-                        py += f_dpy;
-                        if (px >= f_width) {
-                            px -= f_width;
-                            py++;
+                        const bool wrap = px >= f_width;
+                        px = (int)min((unsigned)px, (unsigned)(px - f_width));
+                        py += f_dpy + (wrap ? 1 : 0);
+                        bg = ((unsigned)(px - f_x0) >= f_w) | ((unsigned)(py - f_y0) >= f_h);  // gen_background
+                        if (!draw_cids) {  // x first, then y (Appendix A.7): the slot's stream moves on as the reference's does
+                            rng_step(g_rs);
+                            rng_step(g_rs);
                         }
-                        bg = (unsigned)(px - f_x0) >= f_w || (unsigned)(py - f_y0) >= f_h;  // gen_background
-                        if (draw_cids) {  // (every camera ray starts a stream of its own: none for a background id)
-                            if (!bg) {
-                                g_rs = rng_sample_stream(ap.seed_lo, ap.seed_hi, (unsigned long long)my_cid * (unsigned)ap.key_mul + (unsigned)ap.key_add);
-                                draw_x = rng_next(g_rs);
-                                draw_y = rng_next(g_rs);
-                            }
-                        } else {  // x first, then y (Appendix A.7): the slot's stream moves on as the reference's does
+                    } while (!draw_cids && (bg & (g_gen < g_limit)));  // (per-sample mode: one turn, known when compiled)
+                    RT_MARK("gen.loop.end");
+                    // (the test again, on the pixel the lane stopped at: carried out of the loop, the bit costs every turn three
+                    // scalar instructions that keep it for the lanes already through.  The empty statement emits nothing: it
+                    // keeps the compiler from finding the loop's own test in this one and carrying the bit after all.)
+                    __asm__ volatile("" : "+v"(px), "+v"(py));
+                    made = !(((unsigned)(px - f_x0) >= f_w) | ((unsigned)(py - f_y0) >= f_h));
+                    const uint32_t turns = (uint32_t)(g_gen - g_entry);
+                    // counted as the camera rays they are (camera_rays, closest_rays): summed at the exit
+                    n_bg_lane += turns - (made ? 1u : 0u);
+                    if (draw_cids) {  // (every camera ray starts a stream of its own: none for a background id)
+                        if (made) {
+                            g_rs = rng_sample_stream(ap.seed_lo, ap.seed_hi, (unsigned long long)my_cid * (unsigned)ap.key_mul + (unsigned)ap.key_add);
                             draw_x = rng_next(g_rs);
                             draw_y = rng_next(g_rs);
                         }
-                        n_bg_lane += bg ? 1u : 0u;  // counted as the camera ray it is (camera_rays, closest_rays): summed at the exit
-                    } while (bg && can_loop && g_gen < g_stop && !(dealt && rtchunks::chunk_ends((unsigned)g_gen, bg_m, false)));
-                    made = !bg;
+                    } else {  // rng_next's Weyl word for 2 draws a turn; a draw is the register's newest word plus the Weyl word then
+                        static_assert(2u * kRngWeyl < (1u << 24), "a 24-bit multiply");  // (turns <= 2 047)
+                        g_rs.d += __umul24(turns, 2u * kRngWeyl);
+                        draw_x = g_rs.v3 + (g_rs.d - kRngWeyl);
+                        draw_y = g_rs.v4 + g_rs.d;
+                    }
                 }
                 if (made) {
                     camera_get_ray(cam, (px + rng_to_uniform(draw_x)) / ap.width, (py + rng_to_uniform(draw_y)) / ap.height, out.ray_o, out.ray_d);
@@ -703,14 +755,14 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
                 if (hand_back) {
                     if (draw_cids) {
                         phase = PH_IDLE;  // (the frame's counter has run out: nothing is tied to this lane's slot)
-                    } else if (CHUNKS && chunk_g && slot_set + 1 >= (int)s_task[5]) {
+                    } else if (CHUNKS && chunk_g && slot_set + 1 >= RT_GEN_CHUNK_HEAD) {
                         // a dealt slot, or the last one of the static head, is finished: its final state goes to the pools, the
                         // lane draws a task next
                         cold_load();
                         store_slot(i);
                         i = ap_n;
                         tri = -1;
-                        slot_set = (int)s_task[5];
+                        slot_set = RT_GEN_CHUNK_HEAD;
                     } else {  // (the static deal, or the static head of the chunked one: the lane's own next slot)
                         next_slot(PH_GEN);
                     }

@@ -969,6 +969,54 @@ int rt_slot_chunk_static_slot(int set, int lane_in_grid, int lanes_in_grid, int 
 uint32_t rt_slot_chunk_levels(uint32_t rays, uint32_t G) { return rtchunks::levels(rays, G); }
 uint32_t rt_slot_chunk_task_count(uint32_t sets, uint32_t rays, uint32_t G) { return rtchunks::task_count(sets, rays, G); }
 int rt_slot_chunk_ends(uint32_t gen, uint32_t G, int fresh) { return rtchunks::chunk_ends(gen, rtchunks::multiple_of(G), fresh != 0); }
+// the limit of a run over background pixels in k_paths_bg's GEN block (tests/test_chunk_limit_host.py)
+uint32_t rt_slot_chunk_next_multiple(uint32_t gen, uint32_t G) { return rtchunks::next_multiple(gen, G, rtchunks::next_multiple_mul(G)); }
+uint32_t rt_slot_chunk_run_limit(uint32_t gen, uint32_t g_stop, int dealt, int can_loop, uint32_t G) {
+    return rtchunks::run_limit(gen, g_stop, dealt != 0, can_loop != 0, G, rtchunks::next_multiple_mul(G));
+}
+// Every run the GEN block can be asked for with G in [g_lo, g_hi]: gen in 0 .. 2 047, g_stop in {gen + 1, the next multiple of
+// G above gen - 1, that multiple, that multiple + 1, 2 047} (where gen < g_stop: only such a lane runs), dealt and not, can_loop
+// and not.  Over background pixels only, a run is walked twice: with the stop tests made turn by turn -- can_loop, gen < g_stop,
+// chunk_ends(gen, multiple_of(G), false) -- and against run_limit, fixed before the first turn.  out4: [runs walked, runs whose
+// two walks stop at different generations, G and gen of the first such run].  (The multiple in g_stop is found by counting.)
+void rt_slot_chunk_run_limit_check(uint32_t g_lo, uint32_t g_hi, int64_t *out4) {
+    int64_t runs = 0, bad = 0, first_G = -1, first_gen = -1;
+#pragma omp parallel for schedule(dynamic, 8) reduction(+ : runs, bad)
+    for (int64_t G = g_lo; G <= (int64_t)g_hi; G++) {
+        const rtchunks::Multiple m = rtchunks::multiple_of((uint32_t)G);
+        const uint32_t mul = rtchunks::next_multiple_mul((uint32_t)G);
+        uint32_t next = 0;  // the smallest multiple of G above gen
+        for (uint32_t gen = 0; gen <= 2047u; gen++) {
+            if (next <= gen) next += (uint32_t)G;
+            const uint32_t stops[5] = {gen + 1u, next - 1u, next, next + 1u, 2047u};
+            for (uint32_t g_stop : stops) {
+                if (!(gen < g_stop)) continue;
+                for (int dealt = 0; dealt < 2; dealt++)
+                    for (int can_loop = 0; can_loop < 2; can_loop++) {
+                        uint32_t a = gen, b = gen;
+                        do a++;
+                        while (can_loop && a < g_stop && !(dealt && rtchunks::chunk_ends(a, m, false)));
+                        const uint32_t limit = rtchunks::run_limit(gen, g_stop, dealt != 0, can_loop != 0, (uint32_t)G, mul);
+                        do b++;
+                        while (b < limit);
+                        runs++;
+                        if (a != b) {
+                            bad++;
+#pragma omp critical
+                            if (first_G < 0 || G < first_G) {
+                                first_G = G;
+                                first_gen = gen;
+                            }
+                        }
+                    }
+            }
+        }
+    }
+    out4[0] = runs;
+    out4[1] = bad;
+    out4[2] = first_G;
+    out4[3] = first_gen;
+}
 int rt_slot_chunk_taker_runs(int old_sem) { return rtchunks::taker_runs(old_sem); }
 int rt_slot_chunk_runner_keeps(int old_sem) { return rtchunks::runner_keeps(old_sem); }
 // G as the launch plan picks it for a frame whose slots run `chain` camera rays in k_paths (0: the static deal)

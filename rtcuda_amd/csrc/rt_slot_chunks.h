@@ -110,4 +110,26 @@ RT_CHUNKS_FN bool is_multiple(unsigned gen, const Multiple &m) {
 // the runner's test in the GEN block: the slot has made at least one ray on this lane (`fresh`: none yet) and stands at a
 // multiple of G
 RT_CHUNKS_FN bool chunk_ends(unsigned gen, const Multiple &m, bool fresh) { return !fresh && is_multiple(gen, m); }
+
+// The smallest multiple of G above gen, without a division: floor(gen / G) = floor((gen + 1/2) / G) is the high word of
+// (2 gen + 1) * ceil(2^31 / G).  Exact for gen, G <= 2 047: the constant exceeds 2^31 / G by less than G / 2^31 of itself,
+// which moves the quotient by less than (2 gen + 1) G / 2^32 < 1 / (2 G) -- the distance (gen + 1/2) / G keeps from the next
+// integer.  (The half is what lets G = 1 in: its constant is 2^31, not 2^32.)
+RT_CHUNKS_FN unsigned next_multiple_mul(unsigned G) { return (0x80000000u + G - 1u) / G; }
+RT_CHUNKS_FN unsigned next_multiple(unsigned gen, unsigned G, unsigned mul) {
+    return ((unsigned)(((unsigned long long)(2u * gen + 1u) * mul) >> 32) + 1u) * G;
+}
+// Where a lane's run over background pixels ends at the latest (the GEN block of k_paths_bg), fixed before the run: the run
+// goes on while gen < run_limit.  g_stop: the generation at which the slot's chain ends; a dealt lane also stops at the next
+// chunk's end (the generation the per-turn test chunk_ends(gen, m, false) would stop it at: gen reaches a multiple of G exactly
+// when it reaches the next one); a lane that cannot step its pixel takes one turn.
+RT_CHUNKS_FN unsigned run_limit(unsigned gen, unsigned g_stop, bool dealt, bool can_loop, unsigned G, unsigned mul) {
+    unsigned limit = g_stop;
+    if (dealt) {
+        const unsigned e = next_multiple(gen, G, mul);
+        limit = e < limit ? e : limit;
+    }
+    if (!can_loop) limit = gen + 1u < limit ? gen + 1u : limit;
+    return limit;
+}
 }  // namespace rtchunks
