@@ -999,6 +999,86 @@ def denoise_dual(beauty_a, spp_a: int, beauty_b, spp_b: int, aov_sums, aov_spp: 
     return out
 
 
+def _temporal(me, prm, defaults, entry, history_names, n_out, out_names, beauty_a, spp_a, beauty_b, spp_b, aov_sums, aov_spp, motion, history, width,
+              height, moments, ints, floats, emission_tolerance, out, stream):
+    """What temporal_accumulate and temporal_accumulate_moments do: the checks, the parameters (``prm``: the entry point's struct,
+    which ``defaults`` fills; ``ints`` / ``floats``: (name, value or None) of the caller's), the outputs and the call of ``entry``.
+    The older entry point has no previous motion, no moments (a history of ``n_out`` + 2 items, ``n_out`` results) and no
+    emission_tolerance."""
+    import torch
+    two = beauty_b is not None
+    _dn_positive_ints(me, (("width", width), ("height", height), ("spp_a", spp_a), ("aov_spp", aov_spp)) + ((("spp_b", spp_b),) if two else ()))
+    n = width * height
+    named = [("beauty_a", beauty_a, 3)] + ([("beauty_b", beauty_b, 3)] if two else []) + [("aov_sums", aov_sums, AOV_CHANNELS)]
+    hist_a = hist_b = length = prev_aov = prev_motion = prev_moments = None
+    prev_spp = 1
+    if history is not None:
+        if not isinstance(history, (tuple, list)) or len(history) != n_out + 2:
+            raise RtError(f"{me}: history must be None or {history_names}")
+        hist_a, hist_b, length, prev_aov, prev_spp, prev_motion, prev_moments = tuple(history) + (None,) * (5 - n_out)
+        if (hist_b is not None) != two:
+            raise RtError(f"{me}: history's hist_b and beauty_b must be None together")
+        if prev_moments is not None and not moments:
+            raise RtError(f"{me}: history's prev_moments needs moments=True")
+        _dn_positive_ints(me, (("prev_aov_spp", prev_spp),))
+        named += [("history hist_a", hist_a, 3)] + ([("history hist_b", hist_b, 3)] if two else []) + [("history prev_aov_sums", prev_aov, AOV_CHANNELS)]
+    device = _dn_sums(me, n, tuple(named))
+
+    def plain(name, t, dtype, shape):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != device:
+            raise RtError(f"{me}: {name} must be a torch tensor on the GPU of the sums")
+        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+            raise RtError(f"{me}: {name} must be a contiguous {shape} {dtype} tensor, it is {tuple(t.shape)} {t.dtype}")
+
+    plain("motion", motion, torch.float32, (n, 4))
+    if history is not None:
+        plain("history length", length, torch.int32, (n,))
+        if prev_motion is not None:
+            plain("history prev_motion", prev_motion, torch.float32, (n, 4))
+        if prev_moments is not None:
+            plain("history prev_moments", prev_moments, torch.float32, (n, 4))
+    _check(getattr(lib(), defaults)(ctypes.byref(prm)), defaults)
+    for name, v in ints:
+        if v is not None:
+            if not isinstance(v, int) or isinstance(v, bool) or not 1 <= v <= 0x7FFFFFFF:
+                raise RtError(f"{me}: {name} must be an int in 1 .. 2^31 - 1, it is {v!r}")
+            setattr(prm, name, v)
+    for name, v in floats:
+        if v is not None:
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.floating)) or not np.isfinite(v):
+                raise RtError(f"{me}: {name} must be a finite number, it is {v!r}")
+            setattr(prm, name, float(v))
+    if emission_tolerance is not None:
+        if isinstance(emission_tolerance, bool) or not isinstance(emission_tolerance, (int, float, np.floating)):
+            raise RtError(f"{me}: emission_tolerance must be a number, it is {emission_tolerance!r}")
+        prm.emission_tolerance = float(emission_tolerance)  # (a NaN or a negative one is the library's to refuse)
+    if out is None:
+        out = (torch.empty((n, 3), dtype=torch.int64, device=device), torch.empty((n, 3), dtype=torch.int64, device=device) if two else None,
+               torch.empty(n, dtype=torch.int32, device=device), torch.empty((n, 4), dtype=torch.float32, device=device) if moments else None,
+               torch.empty(n, dtype=torch.float32, device=device) if moments else None)[:n_out]
+    else:
+        if not isinstance(out, (tuple, list)) or len(out) != n_out or (out[1] is not None) != two or any((t is not None) != moments for t in out[3:]):
+            raise RtError(f"{me}: out must be {out_names}")
+        _dn_sums(me, n, tuple([("out hist_a", out[0], 3)] + ([("out hist_b", out[1], 3)] if two else [])))
+        plain("out length", out[2], torch.int32, (n,))
+        if moments:
+            plain("out moments", out[3], torch.float32, (n, 4))
+            plain("out variance", out[4], torch.float32, (n,))
+        if out[0].device != device:
+            raise RtError(f"{me}: out is on {out[0].device}, beauty_a on {device}")
+    s = torch.cuda.current_stream(device) if stream is None else stream
+    c = ctypes.c_void_p
+
+    def ptr(t):
+        return c(None if t is None else t.data_ptr())
+
+    with torch.cuda.device(device):
+        _check(getattr(lib(), entry)(ptr(beauty_a), spp_a, ptr(beauty_b), spp_b if two else 0, ptr(aov_sums), aov_spp, ptr(motion), ptr(hist_a),
+                                     ptr(hist_b), ptr(length), ptr(prev_aov), prev_spp, *((ptr(prev_motion), ptr(prev_moments)) if n_out == 5 else ()),
+                                     width, height, ctypes.byref(prm), *map(ptr, out), c(s.cuda_stream or None)), entry)
+    return tuple(out)
+
+
 def temporal_default_params() -> dict:
     """The parameters rt_temporal_accumulate_fixed uses when it is given none (rt_temporal_default_params)."""
     prm = RtTemporalParams()
@@ -1018,66 +1098,10 @@ def temporal_accumulate(beauty_a, spp_a: int, beauty_b, spp_b: int, aov_sums, ao
     ...) take them as they are -- and the (h * w,) int32 history length per pixel.  ``out``: a tuple (hist_a, hist_b or None,
     length) of tensors to fill, none of which may be an input (ping-pong two sets).  Parameters left at None are the library's
     defaults (temporal_default_params)."""
-    import torch
-    me = "temporal_accumulate"
-    two = beauty_b is not None
-    _dn_positive_ints(me, (("width", width), ("height", height), ("spp_a", spp_a), ("aov_spp", aov_spp)) + ((("spp_b", spp_b),) if two else ()))
-    n = width * height
-    named = [("beauty_a", beauty_a, 3)] + ([("beauty_b", beauty_b, 3)] if two else []) + [("aov_sums", aov_sums, AOV_CHANNELS)]
-    hist_a = hist_b = length = prev_aov = None
-    prev_spp = 1
-    if history is not None:
-        if not isinstance(history, (tuple, list)) or len(history) != 5:
-            raise RtError(f"{me}: history must be None or (hist_a, hist_b or None, length, prev_aov_sums, prev_aov_spp)")
-        hist_a, hist_b, length, prev_aov, prev_spp = history
-        if (hist_b is not None) != two:
-            raise RtError(f"{me}: history's hist_b and beauty_b must be None together")
-        _dn_positive_ints(me, (("prev_aov_spp", prev_spp),))
-        named += [("history hist_a", hist_a, 3)] + ([("history hist_b", hist_b, 3)] if two else []) + [("history prev_aov_sums", prev_aov, AOV_CHANNELS)]
-    device = _dn_sums(me, n, tuple(named))
-
-    def plain(name, t, dtype, shape):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != device:
-            raise RtError(f"{me}: {name} must be a torch tensor on the GPU of the sums")
-        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
-            raise RtError(f"{me}: {name} must be a contiguous {shape} {dtype} tensor, it is {tuple(t.shape)} {t.dtype}")
-
-    plain("motion", motion, torch.float32, (n, 4))
-    if history is not None:
-        plain("history length", length, torch.int32, (n,))
-    prm = RtTemporalParams()
-    _check(lib().rt_temporal_default_params(ctypes.byref(prm)), "rt_temporal_default_params")
-    if max_history is not None:
-        if not isinstance(max_history, int) or isinstance(max_history, bool) or not 1 <= max_history <= 0x7FFFFFFF:
-            raise RtError(f"{me}: max_history must be an int in 1 .. 2^31 - 1, it is {max_history!r}")
-        prm.max_history = max_history
-    for name, v in (("alpha_min", alpha_min), ("depth_tolerance", depth_tolerance), ("normal_cos_min", normal_cos_min)):
-        if v is not None:
-            if isinstance(v, bool) or not isinstance(v, (int, float, np.floating)) or not np.isfinite(v):
-                raise RtError(f"{me}: {name} must be a finite number, it is {v!r}")
-            setattr(prm, name, float(v))
-    if out is None:
-        out = (torch.empty((n, 3), dtype=torch.int64, device=device), torch.empty((n, 3), dtype=torch.int64, device=device) if two else None,
-               torch.empty(n, dtype=torch.int32, device=device))
-    else:
-        if not isinstance(out, (tuple, list)) or len(out) != 3 or (out[1] is not None) != two:
-            raise RtError(f"{me}: out must be (hist_a, hist_b or None as beauty_b, length)")
-        _dn_sums(me, n, tuple([("out hist_a", out[0], 3)] + ([("out hist_b", out[1], 3)] if two else [])))
-        plain("out length", out[2], torch.int32, (n,))
-        if out[0].device != device:
-            raise RtError(f"{me}: out is on {out[0].device}, beauty_a on {device}")
-    s = torch.cuda.current_stream(device) if stream is None else stream
-    c = ctypes.c_void_p
-
-    def ptr(t):
-        return c(None if t is None else t.data_ptr())
-
-    with torch.cuda.device(device):
-        _check(lib().rt_temporal_accumulate_fixed(ptr(beauty_a), spp_a, ptr(beauty_b), spp_b if two else 0, ptr(aov_sums), aov_spp, ptr(motion),
-                                                  ptr(hist_a), ptr(hist_b), ptr(length), ptr(prev_aov), prev_spp, width, height,
-                                                  ctypes.byref(prm), ptr(out[0]), ptr(out[1]), ptr(out[2]), c(s.cuda_stream or None)),
-               "rt_temporal_accumulate_fixed")
-    return tuple(out)
+    return _temporal("temporal_accumulate", RtTemporalParams(), "rt_temporal_default_params", "rt_temporal_accumulate_fixed",
+                     "(hist_a, hist_b or None, length, prev_aov_sums, prev_aov_spp)", 3, "(hist_a, hist_b or None as beauty_b, length)", beauty_a, spp_a, beauty_b, spp_b, aov_sums, aov_spp, motion, history, width,
+                     height, False, (("max_history", max_history),),
+                     (("alpha_min", alpha_min), ("depth_tolerance", depth_tolerance), ("normal_cos_min", normal_cos_min)), None, out, stream)
 
 
 def temporal_moments_default_params() -> dict:
@@ -1102,84 +1126,12 @@ def temporal_accumulate_moments(beauty_a, spp_a: int, beauty_b, spp_b: int, aov_
     may be float('inf') (the stop passes every tap).  ``out``: a tuple of the five results' tensors to fill (None where a result
     is None), none of which may be an input.  Parameters left at None are the library's defaults
     (temporal_moments_default_params)."""
-    import torch
-    me = "temporal_accumulate_moments"
-    two = beauty_b is not None
-    _dn_positive_ints(me, (("width", width), ("height", height), ("spp_a", spp_a), ("aov_spp", aov_spp)) + ((("spp_b", spp_b),) if two else ()))
-    n = width * height
-    named = [("beauty_a", beauty_a, 3)] + ([("beauty_b", beauty_b, 3)] if two else []) + [("aov_sums", aov_sums, AOV_CHANNELS)]
-    hist_a = hist_b = length = prev_aov = prev_motion = prev_moments = None
-    prev_spp = 1
-    if history is not None:
-        if not isinstance(history, (tuple, list)) or len(history) != 7:
-            raise RtError(f"{me}: history must be None or (hist_a, hist_b or None, length, prev_aov_sums, prev_aov_spp, prev_motion or None, "
-                          "prev_moments or None)")
-        hist_a, hist_b, length, prev_aov, prev_spp, prev_motion, prev_moments = history
-        if (hist_b is not None) != two:
-            raise RtError(f"{me}: history's hist_b and beauty_b must be None together")
-        if prev_moments is not None and not moments:
-            raise RtError(f"{me}: history's prev_moments needs moments=True")
-        _dn_positive_ints(me, (("prev_aov_spp", prev_spp),))
-        named += [("history hist_a", hist_a, 3)] + ([("history hist_b", hist_b, 3)] if two else []) + [("history prev_aov_sums", prev_aov, AOV_CHANNELS)]
-    device = _dn_sums(me, n, tuple(named))
-
-    def plain(name, t, dtype, shape):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != device:
-            raise RtError(f"{me}: {name} must be a torch tensor on the GPU of the sums")
-        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
-            raise RtError(f"{me}: {name} must be a contiguous {shape} {dtype} tensor, it is {tuple(t.shape)} {t.dtype}")
-
-    plain("motion", motion, torch.float32, (n, 4))
-    if history is not None:
-        plain("history length", length, torch.int32, (n,))
-        if prev_motion is not None:
-            plain("history prev_motion", prev_motion, torch.float32, (n, 4))
-        if prev_moments is not None:
-            plain("history prev_moments", prev_moments, torch.float32, (n, 4))
-    prm = RtTemporalMomentsParams()
-    _check(lib().rt_temporal_moments_default_params(ctypes.byref(prm)), "rt_temporal_moments_default_params")
-    for name, v in (("max_history", max_history), ("variance_min_history", variance_min_history)):
-        if v is not None:
-            if not isinstance(v, int) or isinstance(v, bool) or not 1 <= v <= 0x7FFFFFFF:
-                raise RtError(f"{me}: {name} must be an int in 1 .. 2^31 - 1, it is {v!r}")
-            setattr(prm, name, v)
-    for name, v in (("alpha_min", alpha_min), ("depth_tolerance", depth_tolerance), ("normal_cos_min", normal_cos_min)):
-        if v is not None:
-            if isinstance(v, bool) or not isinstance(v, (int, float, np.floating)) or not np.isfinite(v):
-                raise RtError(f"{me}: {name} must be a finite number, it is {v!r}")
-            setattr(prm, name, float(v))
-    if emission_tolerance is not None:
-        if isinstance(emission_tolerance, bool) or not isinstance(emission_tolerance, (int, float, np.floating)):
-            raise RtError(f"{me}: emission_tolerance must be a number, it is {emission_tolerance!r}")
-        prm.emission_tolerance = float(emission_tolerance)  # (a NaN or a negative one is the library's to refuse)
-    if out is None:
-        out = (torch.empty((n, 3), dtype=torch.int64, device=device), torch.empty((n, 3), dtype=torch.int64, device=device) if two else None,
-               torch.empty(n, dtype=torch.int32, device=device), torch.empty((n, 4), dtype=torch.float32, device=device) if moments else None,
-               torch.empty(n, dtype=torch.float32, device=device) if moments else None)
-    else:
-        if (not isinstance(out, (tuple, list)) or len(out) != 5 or (out[1] is not None) != two or (out[3] is not None) != moments
-                or (out[4] is not None) != moments):
-            raise RtError(f"{me}: out must be (hist_a, hist_b or None as beauty_b, length, moments and variance or None as ``moments``)")
-        _dn_sums(me, n, tuple([("out hist_a", out[0], 3)] + ([("out hist_b", out[1], 3)] if two else [])))
-        plain("out length", out[2], torch.int32, (n,))
-        if moments:
-            plain("out moments", out[3], torch.float32, (n, 4))
-            plain("out variance", out[4], torch.float32, (n,))
-        if out[0].device != device:
-            raise RtError(f"{me}: out is on {out[0].device}, beauty_a on {device}")
-    s = torch.cuda.current_stream(device) if stream is None else stream
-    c = ctypes.c_void_p
-
-    def ptr(t):
-        return c(None if t is None else t.data_ptr())
-
-    with torch.cuda.device(device):
-        _check(lib().rt_temporal_accumulate_moments_fixed(ptr(beauty_a), spp_a, ptr(beauty_b), spp_b if two else 0, ptr(aov_sums), aov_spp, ptr(motion),
-                                                          ptr(hist_a), ptr(hist_b), ptr(length), ptr(prev_aov), prev_spp, ptr(prev_motion),
-                                                          ptr(prev_moments), width, height, ctypes.byref(prm), ptr(out[0]), ptr(out[1]), ptr(out[2]),
-                                                          ptr(out[3]), ptr(out[4]), c(s.cuda_stream or None)),
-               "rt_temporal_accumulate_moments_fixed")
-    return tuple(out)
+    return _temporal("temporal_accumulate_moments", RtTemporalMomentsParams(), "rt_temporal_moments_default_params",
+                     "rt_temporal_accumulate_moments_fixed",
+                     "(hist_a, hist_b or None, length, prev_aov_sums, prev_aov_spp, prev_motion or None, prev_moments or None)", 5,
+                     "(hist_a, hist_b or None as beauty_b, length, moments and variance or None as ``moments``)", beauty_a, spp_a, beauty_b, spp_b,
+                     aov_sums, aov_spp, motion, history, width, height, moments, (("max_history", max_history), ("variance_min_history", variance_min_history)),
+                     (("alpha_min", alpha_min), ("depth_tolerance", depth_tolerance), ("normal_cos_min", normal_cos_min)), emission_tolerance, out, stream)
 
 
 def denoise_variance(beauty_sums, spp: int, variance, aov_sums, aov_spp: int, width: int, height: int, *, passes=None, sigma_variance=None,

@@ -1149,28 +1149,6 @@ int hc_motion_records(int n, const int32_t *tri, const float *u, const float *v,
     }
     return 0;
 }
-// The CPU twin of rt_temporal_accumulate_fixed: a serial loop over rt_temporal.h, host buffers throughout, the same checks of the
-// parameters (not the overlap check: the caller's).  Returns 0, or 1 and writes nothing.
-int hc_temporal_accumulate(const int64_t *sum_a, int samples_a, const int64_t *sum_b, int samples_b, const int64_t *aov_fixed, int aov_samples,
-                           const float *motion4, const int64_t *hist_a_in, const int64_t *hist_b_in, const int32_t *len_in,
-                           const int64_t *prev_aov_fixed, int prev_aov_samples, int width, int height, int max_history, float alpha_min,
-                           float depth_tolerance, float normal_cos_min, int64_t *hist_a_out, int64_t *hist_b_out, int32_t *len_out) {
-    if (!sum_a || !aov_fixed || !motion4 || !hist_a_out || !len_out || width < 1 || height < 1 || samples_a < 1 || aov_samples < 1) return 1;
-    const bool two = sum_b != nullptr, history = hist_a_in != nullptr;
-    if (two != (hist_b_out != nullptr) || (two && samples_b < 1)) return 1;
-    if (!history && (hist_b_in || len_in || prev_aov_fixed)) return 1;
-    if (history && (!len_in || !prev_aov_fixed || prev_aov_samples < 1 || two != (hist_b_in != nullptr))) return 1;
-    if (max_history < 1 || !(alpha_min > 0.f && alpha_min <= 1.f) || !(std::isfinite(depth_tolerance) && depth_tolerance > 0.f)) return 1;
-    if (!(normal_cos_min >= -1.f && normal_cos_min <= 1.f)) return 1;
-    const float inv_a = 1.f / (float)samples_a, inv_b = two ? 1.f / (float)samples_b : 0.f, inv_aov = 1.f / (float)aov_samples;
-    const float inv_prev = history ? 1.f / (float)prev_aov_samples : 0.f;
-    for (int y = 0; y < height; y++)
-        for (int x = 0; x < width; x++)
-            tm_accumulate_pixel(x, y, width, height, sum_a, inv_a, sum_b, inv_b, aov_fixed, inv_aov, motion4 + 4 * ((size_t)y * width + x), hist_a_in,
-                                hist_b_in, len_in, prev_aov_fixed, inv_prev, max_history, alpha_min, depth_tolerance, normal_cos_min, hist_a_out,
-                                hist_b_out, len_out);
-    return 0;
-}
 // The CPU twin of rt_temporal_accumulate_moments_fixed (tests/test_temporal_moments_host.py, tools/temporal_moments_quality.py):
 // a serial loop over rt_temporal.h's tm_accumulate_moments_pixel, host buffers throughout, the same checks of the parameters and
 // of which pointers go together (not the alignment and overlap checks: the caller's).  Returns 0, or 1 and writes nothing.
@@ -1190,21 +1168,22 @@ int hc_temporal_accumulate_moments(const int64_t *sum_a, int samples_a, const in
     if (max_history < 1 || !(alpha_min > 0.f && alpha_min <= 1.f) || !(std::isfinite(depth_tolerance) && depth_tolerance > 0.f)) return 1;
     if (!(normal_cos_min >= -1.f && normal_cos_min <= 1.f) || !(emission_tolerance >= 0.f) || variance_min_history < 1) return 1;
     TmMoments t{};
-    t.sum_a = sum_a, t.sum_b = sum_b, t.aov = aov_fixed, t.hist_a_in = hist_a_in, t.hist_b_in = hist_b_in, t.prev_aov = prev_aov_fixed;
-    t.motion = motion4, t.prev_motion = prev_motion4, t.moments_in = moments_in, t.len_in = len_in;
-    t.out_a = hist_a_out, t.out_b = hist_b_out, t.len_out = len_out, t.moments_out = moments_out, t.variance_out = variance_out;
-    t.width = width, t.height = height, t.tiles_x = 0;
-    t.max_history = max_history, t.variance_min_history = variance_min_history;
-    t.use_emission = emission_tolerance <= 3.402823466e+38f;
-    t.inv_a = 1.f / (float)samples_a;
-    t.inv_b = two ? 1.f / (float)samples_b : 0.f;
-    t.inv_n = 1.f / (float)(two && moments ? samples_a + samples_b : samples_a);
-    t.inv_aov = 1.f / (float)aov_samples;
-    t.inv_prev_aov = history ? 1.f / (float)prev_aov_samples : 0.f;
-    t.alpha_min = alpha_min, t.depth_tolerance = depth_tolerance, t.normal_cos_min = normal_cos_min, t.emission_tolerance = emission_tolerance;
+    tm_moments_fill(&t, sum_a, samples_a, sum_b, samples_b, aov_fixed, aov_samples, motion4, hist_a_in, hist_b_in, len_in, prev_aov_fixed,
+                    prev_aov_samples, prev_motion4, moments_in, width, height, 0, max_history, alpha_min, depth_tolerance, normal_cos_min,
+                    emission_tolerance, variance_min_history, hist_a_out, hist_b_out, len_out, moments_out, variance_out);
     for (int y = 0; y < height; y++)
         for (int x = 0; x < width; x++) tm_accumulate_moments_pixel(&t, x, y, motion4 + 4 * ((size_t)y * width + x));
     return 0;
+}
+// The CPU twin of rt_temporal_accumulate_fixed (tests/test_temporal_host.py, tools/temporal_quality.py), as the entry point is: the
+// twin above with the emission stop, the triangle stop and the moments off.
+int hc_temporal_accumulate(const int64_t *sum_a, int samples_a, const int64_t *sum_b, int samples_b, const int64_t *aov_fixed, int aov_samples,
+                           const float *motion4, const int64_t *hist_a_in, const int64_t *hist_b_in, const int32_t *len_in,
+                           const int64_t *prev_aov_fixed, int prev_aov_samples, int width, int height, int max_history, float alpha_min,
+                           float depth_tolerance, float normal_cos_min, int64_t *hist_a_out, int64_t *hist_b_out, int32_t *len_out) {
+    return hc_temporal_accumulate_moments(sum_a, samples_a, sum_b, samples_b, aov_fixed, aov_samples, motion4, hist_a_in, hist_b_in, len_in,
+                                          prev_aov_fixed, prev_aov_samples, nullptr, nullptr, width, height, max_history, alpha_min,
+                                          depth_tolerance, normal_cos_min, INFINITY, 1, hist_a_out, hist_b_out, len_out, nullptr, nullptr);
 }
 // The CPU twin of rt_denoise_variance_fixed (tests/test_denoise_variance_host.py, tools/temporal_moments_quality.py): hc_denoise_dual's
 // walk on one frame's sums and the caller's variance.  var_out (may be null): the final v per pixel.  Returns 0, or 1 and writes nothing.

@@ -1,4 +1,5 @@
-// ---- rt_temporal_accumulate_fixed: argument checks and the one launch (kernel: rt_temporal_kernels.inc)
+// ---- the temporal accumulator: two sets of defaults (two sweeps), one set of argument checks, one launch (kernels:
+// rt_temporal_kernels.inc).  rt_temporal_accumulate_fixed is temporal_run with the newer features off (rtcuda_amd.hip).
 rt_temporal_params temporal_defaults() {
     rt_temporal_params p{};
     p.max_history = 4;  // (the sweep of tools/temporal_quality.py: profiles/temporal_quality.json)
@@ -9,81 +10,6 @@ rt_temporal_params temporal_defaults() {
     return p;
 }
 
-int temporal_accumulate_impl(const int64_t *d_sum_a, int samples_a, const int64_t *d_sum_b, int samples_b, const int64_t *d_aov, int aov_samples,
-                             const float *d_motion, const int64_t *d_hist_a_in, const int64_t *d_hist_b_in, const int32_t *d_len_in,
-                             const int64_t *d_prev_aov, int prev_aov_samples, int width, int height, const rt_temporal_params *params,
-                             int64_t *d_hist_a_out, int64_t *d_hist_b_out, int32_t *d_len_out, hipStream_t stream) {
-    const std::string me = "rt_temporal_accumulate_fixed: ";
-    const rt_temporal_params prm = params ? *params : temporal_defaults();
-    const char *null_arg = !d_sum_a ? "d_sum_a" : !d_aov ? "d_aov_fixed" : !d_motion ? "d_motion" : !d_hist_a_out ? "d_hist_a_out" : !d_len_out ? "d_len_out" : nullptr;
-    if (null_arg) return fail(me + "null " + null_arg);
-    if (width < 1 || height < 1) return fail(me + "width and height must be at least 1");
-    if ((long long)width * height > kDnMaxPixels) return fail(me + "more than 715827882 pixels");
-    const bool two = d_sum_b != nullptr, history = d_hist_a_in != nullptr;
-    if (samples_a < 1 || aov_samples < 1 || (two && samples_b < 1)) return fail(me + "samples_a, samples_b (with d_sum_b) and aov_samples must be at least 1");
-    if (two != (d_hist_b_out != nullptr)) return fail(me + "d_sum_b and d_hist_b_out must be null together");
-    if (!history && (d_hist_b_in || d_len_in || d_prev_aov)) return fail(me + "the history pointers (d_hist_a_in, d_len_in, d_prev_aov_fixed, and d_hist_b_in with d_sum_b) must be all null or all set");
-    if (history && (!d_len_in || !d_prev_aov)) return fail(me + "the history pointers (d_hist_a_in, d_len_in, d_prev_aov_fixed, and d_hist_b_in with d_sum_b) must be all null or all set");
-    if (history && two != (d_hist_b_in != nullptr)) return fail(me + "d_sum_b and d_hist_b_in must be null together when history is given");
-    if (history && prev_aov_samples < 1) return fail(me + "prev_aov_samples must be at least 1");
-    if ((uintptr_t)d_motion % 16) return fail(me + "d_motion must be 16-byte aligned");
-    if (prm.flags) return fail(me + "flags must be 0");
-    if (prm.max_history < 1) return fail(me + "max_history must be at least 1, it is " + std::to_string(prm.max_history));
-    if (!(prm.alpha_min > 0.f && prm.alpha_min <= 1.f)) return fail(me + "alpha_min must be in (0, 1]");
-    if (!(std::isfinite(prm.depth_tolerance) && prm.depth_tolerance > 0.f)) return fail(me + "depth_tolerance must be finite and positive");
-    if (!(prm.normal_cos_min >= -1.f && prm.normal_cos_min <= 1.f)) return fail(me + "normal_cos_min must be in [-1, 1]");
-    const long long blocks = dn_pass_blocks(width, height, 1, 1);
-    if (blocks > kDnMaxBlocks)
-        return fail(me + "a " + std::to_string(width) + " x " + std::to_string(height) + " frame needs more than 16777215 workgroups (a frame this narrow or this flat is not served)");
-    // no output range may touch an input range (or another output): the caller ping-pongs
-    const long long n = (long long)width * height;
-    struct Range {
-        const char *name;
-        uintptr_t lo, hi;
-    };
-    auto range = [&](const char *name, const void *p, long long bytes) { return Range{name, (uintptr_t)p, p ? (uintptr_t)p + (uintptr_t)bytes : (uintptr_t)p}; };
-    const Range outs[3] = {range("d_hist_a_out", d_hist_a_out, 24 * n), range("d_hist_b_out", d_hist_b_out, 24 * n), range("d_len_out", d_len_out, 4 * n)};
-    const Range ins[8] = {range("d_sum_a", d_sum_a, 24 * n), range("d_sum_b", d_sum_b, 24 * n), range("d_aov_fixed", d_aov, 8 * RT_AOV_CHANNELS * n),
-                          range("d_motion", d_motion, 16 * n), range("d_hist_a_in", d_hist_a_in, 24 * n), range("d_hist_b_in", d_hist_b_in, 24 * n),
-                          range("d_len_in", d_len_in, 4 * n), range("d_prev_aov_fixed", d_prev_aov, 8 * RT_AOV_CHANNELS * n)};
-    for (int o = 0; o < 3; o++) {
-        if (outs[o].lo == outs[o].hi) continue;
-        for (int i = 0; i < 8; i++)
-            if (ins[i].lo < outs[o].hi && outs[o].lo < ins[i].hi) return fail(me + outs[o].name + " overlaps " + ins[i].name);
-        for (int i = o + 1; i < 3; i++)
-            if (outs[i].lo < outs[o].hi && outs[o].lo < outs[i].hi) return fail(me + outs[o].name + " overlaps " + outs[i].name);
-    }
-
-    TemporalParams tp{};
-    tp.sum_a = (const long long *)d_sum_a;
-    tp.sum_b = (const long long *)d_sum_b;
-    tp.aov = (const long long *)d_aov;
-    tp.hist_a_in = (const long long *)d_hist_a_in;
-    tp.hist_b_in = (const long long *)d_hist_b_in;
-    tp.prev_aov = (const long long *)d_prev_aov;
-    tp.motion = (const float4 *)d_motion;
-    tp.len_in = d_len_in;
-    tp.out_a = (long long *)d_hist_a_out;
-    tp.out_b = (long long *)d_hist_b_out;
-    tp.len_out = d_len_out;
-    tp.width = width;
-    tp.height = height;
-    tp.tiles_x = (width + kDnTileW - 1) / kDnTileW;
-    tp.max_history = prm.max_history;
-    tp.inv_a = 1.f / (float)samples_a;
-    tp.inv_b = two ? 1.f / (float)samples_b : 0.f;
-    tp.inv_aov = 1.f / (float)aov_samples;
-    tp.inv_prev_aov = history ? 1.f / (float)prev_aov_samples : 0.f;
-    tp.alpha_min = prm.alpha_min;
-    tp.depth_tolerance = prm.depth_tolerance;
-    tp.normal_cos_min = prm.normal_cos_min;
-    hipLaunchKernelGGL(k_temporal_accumulate, dim3((unsigned)blocks), dim3(kBlock), 0, stream, tp);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(stream));
-    return 0;
-}
-
-// ---- rt_temporal_accumulate_moments_fixed: the checks above and its own, one launch of k_temporal_accumulate_moments
 rt_temporal_moments_params temporal_moments_defaults() {
     rt_temporal_moments_params p{};
     p.max_history = 4;  // (the sweep of tools/temporal_moments_quality.py: profiles/temporal_moments_quality.json)
@@ -96,12 +22,12 @@ rt_temporal_moments_params temporal_moments_defaults() {
     return p;
 }
 
-int temporal_accumulate_moments_impl(const int64_t *d_sum_a, int samples_a, const int64_t *d_sum_b, int samples_b, const int64_t *d_aov, int aov_samples,
-                                     const float *d_motion, const int64_t *d_hist_a_in, const int64_t *d_hist_b_in, const int32_t *d_len_in,
-                                     const int64_t *d_prev_aov, int prev_aov_samples, const float *d_prev_motion, const float *d_moments_in, int width,
-                                     int height, const rt_temporal_moments_params *params, int64_t *d_hist_a_out, int64_t *d_hist_b_out,
-                                     int32_t *d_len_out, float *d_moments_out, float *d_variance_out, hipStream_t stream) {
-    const std::string me = "rt_temporal_accumulate_moments_fixed: ";
+// me: the entry point's name, the head of every message; kernel: its instantiation of the pixel body
+int temporal_run(const std::string &me, void (*kernel)(TmMoments), const int64_t *d_sum_a, int samples_a, const int64_t *d_sum_b, int samples_b, const int64_t *d_aov,
+                 int aov_samples, const float *d_motion, const int64_t *d_hist_a_in, const int64_t *d_hist_b_in, const int32_t *d_len_in,
+                 const int64_t *d_prev_aov, int prev_aov_samples, const float *d_prev_motion, const float *d_moments_in, int width, int height,
+                 const rt_temporal_moments_params *params, int64_t *d_hist_a_out, int64_t *d_hist_b_out, int32_t *d_len_out,
+                 float *d_moments_out, float *d_variance_out, hipStream_t stream) {
     const rt_temporal_moments_params prm = params ? *params : temporal_moments_defaults();
     const char *null_arg = !d_sum_a ? "d_sum_a" : !d_aov ? "d_aov_fixed" : !d_motion ? "d_motion" : !d_hist_a_out ? "d_hist_a_out" : !d_len_out ? "d_len_out" : nullptr;
     if (null_arg) return fail(me + "null " + null_arg);
@@ -155,23 +81,11 @@ int temporal_accumulate_moments_impl(const int64_t *d_sum_a, int samples_a, cons
     }
 
     TmMoments tm{};
-    tm.sum_a = d_sum_a, tm.sum_b = d_sum_b, tm.aov = d_aov;
-    tm.hist_a_in = d_hist_a_in, tm.hist_b_in = d_hist_b_in, tm.prev_aov = d_prev_aov;
-    tm.motion = d_motion, tm.prev_motion = d_prev_motion, tm.moments_in = d_moments_in;
-    tm.len_in = d_len_in;
-    tm.out_a = d_hist_a_out, tm.out_b = d_hist_b_out, tm.len_out = d_len_out;
-    tm.moments_out = d_moments_out, tm.variance_out = d_variance_out;
-    tm.width = width, tm.height = height, tm.tiles_x = (width + kDnTileW - 1) / kDnTileW;
-    tm.max_history = prm.max_history, tm.variance_min_history = prm.variance_min_history;
-    tm.use_emission = prm.emission_tolerance <= 3.402823466e+38f;
-    tm.inv_a = 1.f / (float)samples_a;
-    tm.inv_b = two ? 1.f / (float)samples_b : 0.f;
-    tm.inv_n = 1.f / (float)(two && moments ? samples_a + samples_b : samples_a);
-    tm.inv_aov = 1.f / (float)aov_samples;
-    tm.inv_prev_aov = history ? 1.f / (float)prev_aov_samples : 0.f;
-    tm.alpha_min = prm.alpha_min, tm.depth_tolerance = prm.depth_tolerance, tm.normal_cos_min = prm.normal_cos_min;
-    tm.emission_tolerance = prm.emission_tolerance;
-    hipLaunchKernelGGL(k_temporal_accumulate_moments, dim3((unsigned)blocks), dim3(kBlock), 0, stream, tm);
+    tm_moments_fill(&tm, d_sum_a, samples_a, d_sum_b, samples_b, d_aov, aov_samples, d_motion, d_hist_a_in, d_hist_b_in, d_len_in, d_prev_aov,
+                    prev_aov_samples, d_prev_motion, d_moments_in, width, height, (width + kDnTileW - 1) / kDnTileW, prm.max_history,
+                    prm.alpha_min, prm.depth_tolerance, prm.normal_cos_min, prm.emission_tolerance, prm.variance_min_history, d_hist_a_out,
+                    d_hist_b_out, d_len_out, d_moments_out, d_variance_out);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kBlock), 0, stream, tm);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(stream));
     return 0;

@@ -1,8 +1,9 @@
-// rt_temporal.h -- the per-pixel arithmetic of rt_render_motion and rt_temporal_accumulate_fixed (include/rtcuda_amd.h, DESIGN.md
-// section 2.9), as a fixed sequence of individually rounded fp32 operations (no FMA: every translation unit that includes it is
-// compiled with -ffp-contract=off).  The kernels (k_motion: rt_stream_kernels.inc; k_temporal_accumulate: rt_temporal_kernels.inc)
-// and the CPU twins (hc_motion_records, hc_temporal_accumulate: rt_host_check.cpp) call these functions and differ only in who
-// walks the pixels.
+// rt_temporal.h -- the per-pixel arithmetic of rt_render_motion and of the temporal accumulator (rt_temporal_accumulate_moments_fixed,
+// and rt_temporal_accumulate_fixed, which is the same call with the newer features off: include/rtcuda_amd.h, DESIGN.md sections
+// 2.9 and 2.10), as a fixed sequence of individually rounded fp32 operations (no FMA: every translation unit that includes it is
+// compiled with -ffp-contract=off).  The kernels (k_motion: rt_stream_kernels.inc; k_temporal_accumulate_moments:
+// rt_temporal_kernels.inc) and the CPU twins (hc_motion_records, hc_temporal_accumulate_moments: rt_host_check.cpp) call these
+// functions and differ only in who walks the pixels.
 //
 // Plain C subset; usable from g++ (host) and hipcc (device).
 #ifndef RT_TEMPORAL_H
@@ -79,7 +80,7 @@ RT_HD void tm_project(const TmCamera *c, const float *P, float *rec3) {
     rec3[2] = sqrtf(tm_dot(a, a));
 }
 
-// ---- rt_temporal_accumulate_fixed
+// ---- the temporal accumulator (both entry points)
 // the mean normal, the mean depth over the hits and the hit count of a pixel's AOV sums, exactly as rt_aov_resolve forms them
 RT_HD int64_t tm_features(const int64_t *aov11, float inv_aov, float *n3, float *z) {
     const int64_t hits = aov11[DN_HITS];
@@ -107,74 +108,10 @@ RT_HD float tm_alpha(int32_t n, float alpha_min) {
 }
 RT_HD float tm_blend(float c, float hbar, float alpha) { return (c - hbar) * alpha + hbar; }
 
-// One pixel (x, y), both colour buffers in one pass over the taps.  sum_b, hist_b_in and out_b are null together; hist_a_in null:
-// the first frame.  mo: the pixel's motion record.  Writes out_a[3 p ..], out_b[3 p ..] and len_out[p].
-RT_HD void tm_accumulate_pixel(int x, int y, int width, int height, const int64_t *sum_a, float inv_a, const int64_t *sum_b, float inv_b,
-                               const int64_t *aov, float inv_aov, const float *mo, const int64_t *hist_a_in, const int64_t *hist_b_in,
-                               const int32_t *len_in, const int64_t *prev_aov, float inv_prev_aov, int32_t max_history, float alpha_min,
-                               float depth_tolerance, float normal_cos_min, int64_t *out_a, int64_t *out_b, int32_t *len_out) {
-    const long long p = (long long)y * width + x;
-    float ca[3], cb[3] = {0.f, 0.f, 0.f};
-    for (int k = 0; k < 3; k++) {
-        ca[k] = dn_fixed_to_float(sum_a[3 * p + k]) * inv_a;
-        if (sum_b) cb[k] = dn_fixed_to_float(sum_b[3 * p + k]) * inv_b;
-    }
-    float sw = 0.f, sa[3] = {0.f, 0.f, 0.f}, sb[3] = {0.f, 0.f, 0.f};
-    int32_t n_prev = 0x7fffffff;
-    int32_t tri;
-    {
-        union { float f; int32_t i; } bits;  // (the triangle id rides in the record's fourth float)
-        bits.f = mo[3];
-        tri = bits.i;
-    }
-    if (hist_a_in && tri >= 0) {
-        const float fx = mo[0] - 0.5f, fy = mo[1] - 0.5f, dist = mo[2];
-        if (fx >= -1.f && fx < (float)width && fy >= -1.f && fy < (float)height) {  // (false for a NaN)
-            float n_p[3], z_p;
-            (void)tm_features(aov + DN_AOV_CHANNELS * p, inv_aov, n_p, &z_p);
-            const float flx = floorf(fx), fly = floorf(fy);
-            const int x0 = (int)flx, y0 = (int)fly;
-            const float ax = fx - flx, ay = fy - fly;
-            for (int j = 0; j < 2; j++) {
-                const int yy = y0 + j;
-                if (yy < 0 || yy >= height) continue;
-                for (int i = 0; i < 2; i++) {
-                    const int xx = x0 + i;
-                    if (xx < 0 || xx >= width) continue;
-                    const long long q = (long long)yy * width + xx;
-                    const int32_t len_q = len_in[q];
-                    if (!tm_tap_accept(len_q, prev_aov + DN_AOV_CHANNELS * q, inv_prev_aov, n_p, dist, depth_tolerance, normal_cos_min)) continue;
-                    const float b = (i ? ax : 1.f - ax) * (j ? ay : 1.f - ay);
-                    sw = sw + b;
-                    for (int k = 0; k < 3; k++) {
-                        sa[k] = sa[k] + b * dn_fixed_to_float(hist_a_in[3 * q + k]);
-                        if (sum_b) sb[k] = sb[k] + b * dn_fixed_to_float(hist_b_in[3 * q + k]);
-                    }
-                    n_prev = len_q < n_prev ? len_q : n_prev;
-                }
-            }
-        }
-    }
-    if (sw > 0.f) {
-        const int32_t n = tm_history_length(n_prev, max_history);
-        const float alpha = tm_alpha(n, alpha_min);
-        for (int k = 0; k < 3; k++) {
-            out_a[3 * p + k] = tm_to_fixed(tm_blend(ca[k], sa[k] / sw, alpha));
-            if (sum_b) out_b[3 * p + k] = tm_to_fixed(tm_blend(cb[k], sb[k] / sw, alpha));
-        }
-        len_out[p] = n;
-    } else {
-        for (int k = 0; k < 3; k++) {
-            out_a[3 * p + k] = tm_to_fixed(ca[k]);
-            if (sum_b) out_b[3 * p + k] = tm_to_fixed(cb[k]);
-        }
-        len_out[p] = 1;
-    }
-}
-
-// ---- rt_temporal_accumulate_moments_fixed: the accumulator above with two more stops, temporally accumulated first and second
-// moments of demodulated radiance, and the variance of the mean they give.  What one call is handed, the kernel's parameter block
-// and the twin's alike (host or device pointers; the optional ones null).
+// The accumulator: the four taps with the depth and normal stops, and optionally an emission stop (use_emission), a triangle stop
+// (prev_motion given), temporally accumulated first and second moments of demodulated radiance and the variance of the mean they
+// give (moments_out given).  What one call is handed, the kernel's parameter block and the twin's alike (host or device pointers;
+// the optional ones null).
 typedef struct TmMoments {
     const int64_t *sum_a, *sum_b, *aov, *hist_a_in, *hist_b_in, *prev_aov;
     const float *motion, *prev_motion, *moments_in;
@@ -188,12 +125,43 @@ typedef struct TmMoments {
     float inv_a, inv_b, inv_n, inv_aov, inv_prev_aov, alpha_min, depth_tolerance, normal_cos_min, emission_tolerance;
 } TmMoments;
 
+// The whole block from an entry point's arguments (rt_temporal_accumulate_moments_fixed's, in its order; checked by the caller).
+// tiles_x: the kernel's tiles per row (the twin walks rows: 0).
+RT_HD void tm_moments_fill(TmMoments *t, const int64_t *sum_a, int samples_a, const int64_t *sum_b, int samples_b, const int64_t *aov,
+                           int aov_samples, const float *motion, const int64_t *hist_a_in, const int64_t *hist_b_in, const int32_t *len_in,
+                           const int64_t *prev_aov, int prev_aov_samples, const float *prev_motion, const float *moments_in, int width,
+                           int height, int tiles_x, int32_t max_history, float alpha_min, float depth_tolerance, float normal_cos_min,
+                           float emission_tolerance, int32_t variance_min_history, int64_t *out_a, int64_t *out_b, int32_t *len_out,
+                           float *moments_out, float *variance_out) {
+    const bool two = sum_b != 0, moments = moments_out != 0;
+    t->sum_a = sum_a, t->sum_b = sum_b, t->aov = aov, t->hist_a_in = hist_a_in, t->hist_b_in = hist_b_in, t->prev_aov = prev_aov;
+    t->motion = motion, t->prev_motion = prev_motion, t->moments_in = moments_in, t->len_in = len_in;
+    t->out_a = out_a, t->out_b = out_b, t->len_out = len_out, t->moments_out = moments_out, t->variance_out = variance_out;
+    t->width = width, t->height = height, t->tiles_x = tiles_x;
+    t->max_history = max_history, t->variance_min_history = variance_min_history;
+    t->use_emission = emission_tolerance <= 3.402823466e+38f;
+    t->inv_a = 1.f / (float)samples_a;
+    t->inv_b = two ? 1.f / (float)samples_b : 0.f;
+    t->inv_n = 1.f / (float)(two && moments ? samples_a + samples_b : samples_a);
+    t->inv_aov = 1.f / (float)aov_samples;
+    t->inv_prev_aov = hist_a_in ? 1.f / (float)prev_aov_samples : 0.f;
+    t->alpha_min = alpha_min, t->depth_tolerance = depth_tolerance, t->normal_cos_min = normal_cos_min;
+    t->emission_tolerance = emission_tolerance;
+}
+
 // a moments record is one 16-byte access on the device (the entry point checks the alignment; the twin's host buffers need none)
 #ifdef __HIP_DEVICE_COMPILE__
 #define TM_RECORD(p) __builtin_assume_aligned(p, 16)
 #else
 #define TM_RECORD(p) (p)
 #endif
+
+// the triangle id rides in a motion record's fourth float
+RT_HD int32_t tm_tri_of(float w) {
+    union { float f; int32_t i; } bits;
+    bits.f = w;
+    return bits.i;
+}
 
 RT_HD void tm_emission(const int64_t *aov11, float inv_aov, float *e3) {
     for (int k = 0; k < 3; k++) e3[k] = dn_fixed_to_float(aov11[DN_EMISSION + k]) * inv_aov;
@@ -234,7 +202,7 @@ RT_HD float tm_variance_of(const float *m4, int32_t n) {
 // The spatial estimate of this frame at (x, y): the moments' mean over the 5 x 5 window's taps that pass the depth and normal
 // stops against the centre (which always counts).  tap(dx, dy, q, f_q, n_q, &z_q) hands back the moments and features of the
 // neighbour (dx, dy), which is pixel q of the frame, and whether it has hits: from global memory (tm_spatial_variance) or from a
-// staged tile (k_temporal_accumulate_moments) -- the one use of C++ in this header.
+// staged tile (k_temporal_accumulate_moments) -- with the front's one bool the use of C++ in this header.
 template <typename Tap>
 RT_HD float tm_spatial_variance_of(const TmMoments *t, int x, int y, const float *f_p, const float *n_p, float z_p, int32_t n, Tap tap) {
     float cnt = 0.f, s[4] = {0.f, 0.f, 0.f, 0.f};
@@ -267,13 +235,16 @@ RT_HD float tm_spatial_variance(const TmMoments *t, int x, int y, const float *f
     });
 }
 
-// One pixel (x, y).  tm_accumulate_pixel's steps with the emission stop, the triangle stop (prev_motion given) and, with
-// moments_out given, the moments through the same taps and weights and the variance of the mean -- all but the spatial estimate:
+// One pixel (x, y), both colour buffers in one pass over the taps (sum_b, hist_b_in and out_b are null together; hist_a_in null: the
+// first frame; mo: the pixel's motion record), with the emission stop (use_emission), the triangle stop (prev_motion given) and,
+// with moments_out given, the moments through the same taps and weights and the variance of the mean -- all but the spatial estimate:
 // returns true where that is still owed (variance_out[p] not written), with what it needs: the frame's moments f, n_p, z_p and N.
+// FEATURES false: the three are compiled out whatever t says (k_temporal_accumulate's instantiation), and the answer is false.
+template <bool FEATURES>
 RT_HD bool tm_accumulate_moments_front(const TmMoments *t, int x, int y, const float *mo, float *f, float *n_p, float *z_p_out, int32_t *n_out) {
     const int width = t->width, height = t->height;
     const long long p = (long long)y * width + x;
-    const bool two = t->sum_b != 0, moments = t->moments_out != 0;
+    const bool two = t->sum_b != 0, moments = FEATURES && t->moments_out != 0;
     float ca[3], cb[3] = {0.f, 0.f, 0.f};
     for (int k = 0; k < 3; k++) {
         ca[k] = dn_fixed_to_float(t->sum_a[3 * p + k]) * t->inv_a;
@@ -285,18 +256,13 @@ RT_HD bool tm_accumulate_moments_front(const TmMoments *t, int x, int y, const f
     if (moments) (void)tm_frame_moments(t, p, f, n_p, &z_p);
     float sw = 0.f, sa[3] = {0.f, 0.f, 0.f}, sb[3] = {0.f, 0.f, 0.f}, sm[4] = {0.f, 0.f, 0.f, 0.f};
     int32_t n_prev = 0x7fffffff;
-    int32_t tri;
-    {
-        union { float f; int32_t i; } bits;
-        bits.f = mo[3];
-        tri = bits.i;
-    }
+    const int32_t tri = tm_tri_of(mo[3]);
     if (t->hist_a_in && tri >= 0) {
         const float fx = mo[0] - 0.5f, fy = mo[1] - 0.5f, dist = mo[2];
         if (fx >= -1.f && fx < (float)width && fy >= -1.f && fy < (float)height) {  // (false for a NaN)
             float e_p[3] = {0.f, 0.f, 0.f};
             if (!moments) (void)tm_features(t->aov + DN_AOV_CHANNELS * p, t->inv_aov, n_p, &z_p);
-            if (t->use_emission) tm_emission(t->aov + DN_AOV_CHANNELS * p, t->inv_aov, e_p);
+            if (FEATURES && t->use_emission) tm_emission(t->aov + DN_AOV_CHANNELS * p, t->inv_aov, e_p);
             const float flx = floorf(fx), fly = floorf(fy);
             const int x0 = (int)flx, y0 = (int)fly;
             const float ax = fx - flx, ay = fy - fly;
@@ -310,12 +276,8 @@ RT_HD bool tm_accumulate_moments_front(const TmMoments *t, int x, int y, const f
                     const int32_t len_q = t->len_in[q];
                     const int64_t *aov_q = t->prev_aov + DN_AOV_CHANNELS * q;
                     if (!tm_tap_accept(len_q, aov_q, t->inv_prev_aov, n_p, dist, t->depth_tolerance, t->normal_cos_min)) continue;
-                    if (t->use_emission && !tm_emission_accept(e_p, aov_q, t->inv_prev_aov, t->emission_tolerance)) continue;
-                    if (t->prev_motion) {
-                        union { float f; int32_t i; } bits;
-                        bits.f = t->prev_motion[4 * q + 3];
-                        if (bits.i != tri) continue;
-                    }
+                    if (FEATURES && t->use_emission && !tm_emission_accept(e_p, aov_q, t->inv_prev_aov, t->emission_tolerance)) continue;
+                    if (FEATURES && t->prev_motion && tm_tri_of(t->prev_motion[4 * q + 3]) != tri) continue;
                     const float b = (i ? ax : 1.f - ax) * (j ? ay : 1.f - ay);
                     sw = sw + b;
                     for (int k = 0; k < 3; k++) {
@@ -361,7 +323,7 @@ RT_HD bool tm_accumulate_moments_front(const TmMoments *t, int x, int y, const f
 RT_HD void tm_accumulate_moments_pixel(const TmMoments *t, int x, int y, const float *mo) {
     float f[4], n_p[3], z_p;
     int32_t n;
-    if (tm_accumulate_moments_front(t, x, y, mo, f, n_p, &z_p, &n))
+    if (tm_accumulate_moments_front<true>(t, x, y, mo, f, n_p, &z_p, &n))
         t->variance_out[(long long)y * t->width + x] = tm_spatial_variance(t, x, y, f, n_p, z_p, n);
 }
 

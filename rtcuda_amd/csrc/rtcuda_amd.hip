@@ -16,8 +16,8 @@
 //                          k_atrous* / k_atrous_var*; prepare, finish, k_dn_var_blur (arithmetic: rt_denoise.h, shared with the CPU twin)
 //   rt_host_denoise.inc    rt_denoise_fixed, rt_denoise_dual_fixed and rt_denoise_variance_fixed: one set of checks (dn_check), one pass
 //                          launcher, one run (dn_run)
-//   rt_temporal_kernels.inc k_temporal_accumulate, k_temporal_accumulate_moments (arithmetic: rt_temporal.h, shared with k_motion and the CPU twins)
-//   rt_host_temporal.inc   rt_temporal_accumulate_fixed and rt_temporal_accumulate_moments_fixed: the checks and the launch
+//   rt_temporal_kernels.inc k_temporal_accumulate_moments, k_temporal_accumulate: one pixel body with its features and without (arithmetic: rt_temporal.h, shared with k_motion and the CPU twins)
+//   rt_host_temporal.inc   rt_temporal_accumulate_moments_fixed, and rt_temporal_accumulate_fixed as that with the features off: the checks and the launch
 // The C-ABI below them only checks arguments and forwards, and calls none of its own entry points.  Two bodies stay in it:
 // rt_camera_make (host arithmetic, nothing shared) and rt_xorwow_states (a test hook around k_rng_init / k_test_draw).
 //
@@ -959,13 +959,13 @@ __global__ void k_test_draw(DPools p, int n, int draws, uint32_t *__restrict__ s
 }
 #include "rt_build_kernels.inc"   // device BVH: the leaf-order arrays, refit (k_refit_*), build (k_ploc_*)
 #include "rt_denoise_kernels.inc"  // dn_filter_pixel under k_atrous* and k_atrous_var*; k_dn_prepare*, k_dn_var_blur, k_dn_finish*
-#include "rt_temporal_kernels.inc"  // k_temporal_accumulate
+#include "rt_temporal_kernels.inc"  // k_temporal_accumulate_moments, k_temporal_accumulate
 
 #include "rt_host_scene.inc"   // (opens the anonymous namespace that is closed below) rt_scene: reference tree, checks, build / emit / adopt, create, update, rebuild, edits; what the ray entry points share
 #include "rt_host_render.inc"  // Context, cached output buffers, kernel selection, one shard of a frame, queries and trace hooks, ray tables, AOVs
 #include "rt_host_frame.inc"   // whole frames: the shard fan-out (RT_SPLIT, rt_render_multi), finish_frame, rt_render, rt_render_multi
 #include "rt_host_denoise.inc"  // rt_denoise_fixed, rt_denoise_dual_fixed
-#include "rt_host_temporal.inc"  // rt_temporal_accumulate_fixed
+#include "rt_host_temporal.inc"  // rt_temporal_accumulate_fixed, rt_temporal_accumulate_moments_fixed
 }  // namespace
 
 // ============================================================================ C-ABI
@@ -1220,9 +1220,21 @@ int rt_temporal_accumulate_fixed(const int64_t *d_sum_a, int samples_a, const in
                                  const int32_t *d_len_in, const int64_t *d_prev_aov_fixed, int prev_aov_samples, int width, int height,
                                  const rt_temporal_params *params, int64_t *d_hist_a_out, int64_t *d_hist_b_out, int32_t *d_len_out,
                                  void *stream) {
-    return temporal_accumulate_impl(d_sum_a, samples_a, d_sum_b, samples_b, d_aov_fixed, aov_samples, d_motion, d_hist_a_in, d_hist_b_in,
-                                    d_len_in, d_prev_aov_fixed, prev_aov_samples, width, height, params, d_hist_a_out, d_hist_b_out,
-                                    d_len_out, (hipStream_t)stream);
+    // The accumulator with the newer features off, on the instantiation that has them compiled out.  Of temporal_run's checks those
+    // this entry point never had cannot fire: the four pointers are null (together, and 16-byte aligned), +inf >= 0 and 1 >= 1; the
+    // others are its own, in its order.
+    const rt_temporal_params old = params ? *params : temporal_defaults();
+    rt_temporal_moments_params prm{};
+    prm.max_history = old.max_history;
+    prm.alpha_min = old.alpha_min;
+    prm.depth_tolerance = old.depth_tolerance;
+    prm.normal_cos_min = old.normal_cos_min;
+    prm.emission_tolerance = INFINITY;
+    prm.variance_min_history = 1;
+    prm.flags = old.flags;
+    return temporal_run("rt_temporal_accumulate_fixed: ", k_temporal_accumulate, d_sum_a, samples_a, d_sum_b, samples_b, d_aov_fixed, aov_samples,
+                        d_motion, d_hist_a_in, d_hist_b_in, d_len_in, d_prev_aov_fixed, prev_aov_samples, nullptr, nullptr, width, height, &prm,
+                        d_hist_a_out, d_hist_b_out, d_len_out, nullptr, nullptr, (hipStream_t)stream);
 }
 
 int rt_temporal_moments_default_params(rt_temporal_moments_params *out) {
@@ -1237,9 +1249,9 @@ int rt_temporal_accumulate_moments_fixed(const int64_t *d_sum_a, int samples_a, 
                                          const float *d_moments_in, int width, int height, const rt_temporal_moments_params *params,
                                          int64_t *d_hist_a_out, int64_t *d_hist_b_out, int32_t *d_len_out, float *d_moments_out,
                                          float *d_variance_out, void *stream) {
-    return temporal_accumulate_moments_impl(d_sum_a, samples_a, d_sum_b, samples_b, d_aov_fixed, aov_samples, d_motion, d_hist_a_in, d_hist_b_in,
-                                            d_len_in, d_prev_aov_fixed, prev_aov_samples, d_prev_motion, d_moments_in, width, height, params,
-                                            d_hist_a_out, d_hist_b_out, d_len_out, d_moments_out, d_variance_out, (hipStream_t)stream);
+    return temporal_run("rt_temporal_accumulate_moments_fixed: ", k_temporal_accumulate_moments, d_sum_a, samples_a, d_sum_b, samples_b, d_aov_fixed,
+                        aov_samples, d_motion, d_hist_a_in, d_hist_b_in, d_len_in, d_prev_aov_fixed, prev_aov_samples, d_prev_motion, d_moments_in,
+                        width, height, params, d_hist_a_out, d_hist_b_out, d_len_out, d_moments_out, d_variance_out, (hipStream_t)stream);
 }
 
 int rt_denoise_variance_fixed(const int64_t *d_sum_fixed, int num_samples, const float *d_variance, const int64_t *d_aov_fixed, int aov_samples,

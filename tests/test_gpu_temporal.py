@@ -75,6 +75,17 @@ def test_synthetic_cases_equal_the_restatement(api, torch, w, h, two):
     _assert_same(_run(api, torch, case, w, h, te.PARAMS, history=None), te.run_case(te.accumulate, case, w, h, te.PARAMS, history=None), "first frame")
 
 
+@pytest.mark.parametrize("w,h", [(4, 1), (70, 30)])
+@pytest.mark.parametrize("two", [True, False], ids=["two-buffers", "one-buffer"])
+def test_tiles_mostly_outside_the_image_and_ragged_edges(api, torch, w, h, two):
+    """The sizes test_gpu_temporal_moments.py runs for the tiles' sake, on this entry point's instantiation of the same pixel body.
+    4 x 1: one 32 x 8 tile of which 4 lanes have a pixel; 70 x 30: three tile columns and four tile rows, so interior tile rows,
+    and a ragged right (70 = 2 * 32 + 6) and bottom (30 = 3 * 8 + 6) edge."""
+    case = te.synthetic_case(w, h, two=two)
+    _assert_same(_run(api, torch, case, w, h, te.PARAMS), te.run_case(te.accumulate, case, w, h, te.PARAMS), (w, h, two, "history"))
+    _assert_same(_run(api, torch, case, w, h, te.PARAMS, history=None), te.run_case(te.accumulate, case, w, h, te.PARAMS, history=None), (w, h, two, "first frame"))
+
+
 def test_stops_on_either_side_of_equality(api, torch):
     case, sets = te.equality_stops()
     for prm, lengths in sets:

@@ -14,6 +14,7 @@ import pytest
 from conftest import ROOT, default_camera, oracle_scene
 import aov_expected as ae
 import temporal_expected as te
+import temporal_moments_expected as tm
 
 NEW = ("rt_render_motion", "rt_temporal_default_params", "rt_temporal_accumulate_fixed")
 F32 = np.float32
@@ -141,6 +142,24 @@ def test_one_buffer_equals_the_two_buffer_a(hc):
         hist = (case["history"][0], None) + tuple(case["history"][2:])
         one = twin_accumulate(hc, case["sum_a"], 2, None, 0, case["aov"], 4, case["motion"], hist, w, h, **te.PARAMS)
         assert one[1] is None and np.array_equal(one[0], two[0]) and np.array_equal(one[2], two[2])
+
+
+def test_forwarded_twin_has_the_emission_stop_off(hc):
+    """hc_temporal_accumulate is hc_temporal_accumulate_moments with emission_tolerance = +inf.  temporal_expected.synthetic_case
+    cannot see a forward that left the stop on: unit_aov writes no emission, so both frames' emission is 0 everywhere and the stop
+    passes every tap at any tolerance >= 0.  temporal_moments_expected.synthetic_case gives both AOV frames first-hit emission that
+    differs by far more than any tolerance in use; on it the twin (which never reads a previous motion buffer or moments) must still equal
+    temporal_expected.accumulate, which knows no emission."""
+    for w, h in ((33, 9), (97, 19)):
+        for two in (True, False):
+            case = tm.synthetic_case(w, h, two=two)
+            case = dict(case, history=case["history"][:5])
+            assert (tm.emission(case["aov"], case["aov_spp"]) != 0).any() and (tm.emission(case["history"][3], case["history"][4]) > 1).any()
+            want = te.run_case(te.accumulate, case, w, h, te.PARAMS)
+            shut = dict(te.PARAMS, emission_tolerance=tm.EMISSION_TOLERANCE, variance_min_history=1)
+            stopped = tm.run_case(tm.accumulate_moments, case, w, h, shut, history=case["history"] + (None, None), moments=False)
+            assert (stopped[2] != want[2]).any()  # (the case tells the two apart: a stop left on loses taps)
+            assert_same(twin_case(hc, case, w, h, te.PARAMS), want)
 
 
 def test_identity_motion_grows_the_history_to_its_cap(hc):

@@ -4,7 +4,8 @@ stands beside.  C2 (full_bsdf) at 1920 x 1080, warm, medians of 7 with min and m
 every call between HIP events on the current stream with its outputs allocated before the clock (tools/temporal_time.py's method):
 
   accumulate_off      the new entry point with everything off (emission_tolerance = +inf, no previous motion, no moments) against
-                      rt_temporal_accumulate_fixed on the same buffers, two buffers and one: the same arithmetic, another kernel
+                      rt_temporal_accumulate_fixed on the same buffers, two buffers and one: the same pixel body, the instantiation
+                      with the features against the one without
   accumulate_on       the new entry point on the second frame of an orbit pair: two buffers with both stops; one buffer with both
                       stops and moments at variance_min_history = 1 (no pixel takes the spatial estimate) and at a
                       variance_min_history beyond every length (every pixel takes it)
