@@ -529,6 +529,29 @@ inline rt_stats render_aov_rays(const Scene &scene, int64_t n_rays, const float 
                                                          key_stride, flags, d_aov_fixed, d_ids, stream, &st), "render_aov_rays");
     return st;
 }
+// The same buffers with mirror and glass followed to the first non-specular vertex, for up to max_specular (0 ..
+// RT_AOV_FOLLOW_MAX) vertices -- rt_render_aov_follow_fixed / rt_render_aov_follow_rays_fixed_device, which document the followed
+// path and the deposit.  max_specular = 0 is render_aov / render_aov_rays.
+inline rt_stats render_aov_follow(const Scene &scene, const Camera &camera, int width, int height, int num_samples, int max_specular,
+                                  int64_t *d_aov_fixed, int32_t *d_ids = nullptr, uint64_t seed = 1, uint32_t flags = 0,
+                                  int shard_index = 0, int shard_count = 1, void *stream = nullptr) {
+    rt_scene *h = scene.bvh.handle ? rtcuda_detail::realise(scene) : nullptr;
+    rt_stats st{};
+    rtcuda_detail::check(rt_render_aov_follow_fixed(h, &camera.pod, width, height, num_samples, seed, shard_index, shard_count, flags,
+                                                    max_specular, d_aov_fixed, d_ids, stream, &st), "render_aov_follow");
+    return st;
+}
+inline rt_stats render_aov_follow_rays(const Scene &scene, int64_t n_rays, const float *d_origin, const float *d_dir,
+                                       const int32_t *d_pixel, int rays_per_pixel, int n_pixels, int max_specular, int64_t *d_aov_fixed,
+                                       int32_t *d_ids = nullptr, uint64_t seed = 1, uint64_t key_first = 0, uint32_t key_stride = 1,
+                                       uint32_t flags = 0, void *stream = nullptr) {
+    rt_scene *h = scene.bvh.handle ? rtcuda_detail::realise(scene) : nullptr;
+    rt_stats st{};
+    rtcuda_detail::check(rt_render_aov_follow_rays_fixed_device(h, n_rays, d_origin, d_dir, d_pixel, rays_per_pixel, n_pixels, seed,
+                                                                key_first, key_stride, flags, max_specular, d_aov_fixed, d_ids, stream,
+                                                                &st), "render_aov_follow_rays");
+    return st;
+}
 inline void aov_resolve(const int64_t *d_aov_fixed, float *d_out, int n_pixels, int num_samples, void *stream = nullptr) {
     rtcuda_detail::check(rt_aov_resolve(d_aov_fixed, d_out, n_pixels, num_samples, stream), "aov_resolve");
 }

@@ -407,8 +407,8 @@ int rt_render_rays_keyed_fixed_device(const rt_scene *scene, int64_t n_rays, con
  *      value is 0 is not added.
  *   5. IDS (d_ids may be NULL): n_pixels x 2 int32.  The sample with G % num_samples == 0 writes {triangle in the caller's
  *      order, material index} of its hit, or {-1, -1} on a miss, with a plain store.  Such a sample belongs to shard 0, so
- *      the other shards write nothing there.  (Mirror and glass are not followed to the first diffuse vertex: the material
- *      index tells the caller that a pixel is specular.)
+ *      the other shards write nothing there.  (Mirror and glass are not followed to the first diffuse vertex here: the material
+ *      index tells the caller that a pixel is specular, and rt_render_aov_follow_fixed below follows them.)
  *   6. THE RAY-TABLE FORM (rt_render_aov_rays_fixed_device): row c has the key K = key_first + c * key_stride, exactly as
  *      rt_render_rays_keyed_device defines keys and their checks.  Origin and direction are row c; no stream is needed.  The
  *      pixel is d_pixel[c], else K / rays_per_pixel.  Ids are written by the rows with K % rays_per_pixel == 0, and only when
@@ -443,6 +443,49 @@ int rt_render_aov_rays_fixed_device(const rt_scene *scene, int64_t n_rays, const
                                     uint64_t key_first, uint32_t key_stride, uint32_t flags, int64_t *d_aov_fixed,
                                     int32_t *d_ids /* may be NULL */, void *stream, rt_stats *stats /* may be NULL */);
 int rt_aov_resolve(const int64_t *d_aov_fixed, float *d_out, int n_pixels, int num_samples, void *stream);
+
+/* ---- followed AOVs: the features of the first non-specular vertex behind mirror and glass -----------------------------------
+ * The same eleven channels, so every consumer of an AOV buffer (rt_denoise_fixed, rt_denoise_dual_fixed,
+ * rt_denoise_variance_fixed, both temporal accumulators, rt_aov_resolve) takes them unchanged -- but on a mirror or a glass
+ * surface the guides describe what is SEEN in it.  Samples, rays, shards, keys, hit flags, the
+ * fixed-point conversion, "a zero channel is not added", the device checks, the errors and the stream / thread contract are
+ * those of rt_render_aov_fixed / rt_render_aov_rays_fixed_device above.  New:
+ *   1. THE FOLLOWED PATH of sample G is the path of sample G of the RT_FLAG_RNG_PER_SAMPLE beauty frame of the same seed, draw
+ *      for draw.  Vertex 0 is the first hit.  While the material at vertex j is MIRROR or GLASS and j < max_specular, the
+ *      sample takes the step mat() takes there (render.cuh:139-248): n = -unit(tri.n) of the hit triangle,
+ *      f = sample_f(material, wo = d_j, stream, n, wi, pdf), the next ray starts at offset_ray_origin(p(u, v), n) with
+ *      direction wi and tmax = FLT_MAX, and beta = beta * ((f * dot(wi, n)) / pdf), from beta = (1, 1, 1).
+ *   2. THE STREAM is that of (seed, G), continued after the two jitter draws; in the table form that of (seed, K) with its first
+ *      two draws made and thrown away, as rt_render_rays_keyed_device does.  After sample_f the stream is advanced by the draws
+ *      that mat() makes at that vertex and whose values the features do not need: none in a scene without lights; otherwise
+ *      the light-pick draw (its value selects the light), and for an area light the two draws of Triangle::sample_p and the
+ *      draws of the second sample_f call (none for a mirror; one for glass that can refract).  A point light draws no more.
+ *   3. NO RUSSIAN ROULETTE: init() first rolls at bounces > RR_START = 4, and the last vertex shaded here has
+ *      bounces = max_specular - 1 <= 4.  That is why RT_AOV_FOLLOW_MAX is 5.
+ *   4. THE NEXT HIT is the closest hit under the call's hit flags; with RT_FLAG_WATERTIGHT the chain is the beauty frame's own.
+ *   5. THE DEPOSIT of a sample whose chain ends at vertex j -- the material there is not specular, or j == max_specular:
+ *        albedo    beta * albedo(material_j), one rounded product per channel (j = 0: beta is exactly 1, today's bits)
+ *        normal    -unit(tri.n) of vertex j, faced against the arriving direction d_j by rule 4 of the first-hit buffers
+ *        depth     ((t_0 + t_1) + ...) + t_j in fp32: the length of the path
+ *        hits      1
+ *        emission  L of the area light that the FIRST hit's triangle carries (the estimator adds emission at bounce 0 only)
+ *      A chain that leaves the scene behind a specular vertex deposits that emission and nothing else: hits is not incremented
+ *      (its beauty sample carries nothing but that emission).  A first ray that misses deposits nothing.
+ *   6. IDS keep {triangle, material} of the FIRST hit: the material index still tells the caller that a pixel is specular.
+ *   7. max_specular = 0 is rt_render_aov_fixed / rt_render_aov_rays_fixed_device bit for bit, sums and ids (the same kernel;
+ *      the table form's seed is then not used).  max_specular outside 0 .. RT_AOV_FOLLOW_MAX is an error.
+ * stats: camera_rays = the samples of this call, closest_rays = all rays traced, chain rays included; the rest as above.
+ * Motion vectors are NOT followed: rt_render_motion reprojects the surface a pixel is seen on. */
+#define RT_AOV_FOLLOW_MAX 5
+int rt_render_aov_follow_fixed(const rt_scene *scene, const rt_camera *camera, int width, int height, int num_samples,
+                               uint64_t seed, int shard_index, int shard_count, uint32_t flags, int max_specular,
+                               int64_t *d_aov_fixed, int32_t *d_ids /* may be NULL */, void *stream,
+                               rt_stats *stats /* may be NULL */);
+int rt_render_aov_follow_rays_fixed_device(const rt_scene *scene, int64_t n_rays, const float *d_origin_xyz,
+                                           const float *d_dir_xyz, const int32_t *d_pixel /* may be NULL */, int rays_per_pixel,
+                                           int n_pixels, uint64_t seed, uint64_t key_first, uint32_t key_stride, uint32_t flags,
+                                           int max_specular, int64_t *d_aov_fixed, int32_t *d_ids /* may be NULL */, void *stream,
+                                           rt_stats *stats /* may be NULL */);
 
 /* ---- the denoiser: an AOV-guided a-trous wavelet filter on fixed-point frames ----------------------------------------------
  * One more call after rt_render_shard_fixed and rt_render_aov_fixed: the beauty sums and the feature sums of one view become

@@ -29,6 +29,7 @@ FLAG_REFERENCE_WALK = 8  # cross-check mode: every ray walks the reference's own
 SCENE_DEVICE_BVH = 1     # rt_scene_create_flags: build the BVH on the device (PLOC)
 FLAG_WATERTIGHT = 16     # the triangle-list definition (no hit lost to a box test, ties by caller index) instead of the reference's
 AOV_CHANNELS = 11        # rt_render_aov_*: int64 sums per pixel, interleaved
+AOV_FOLLOW_MAX = 5       # RT_AOV_FOLLOW_MAX: the largest max_specular of the followed AOVs
 AOV_ALBEDO, AOV_NORMAL, AOV_EMISSION, AOV_DEPTH, AOV_HITS = 0, 3, 6, 9, 10  # first channel of each feature
 
 EXPORTS = [
@@ -39,6 +40,7 @@ EXPORTS = [
     "rt_render_rays_keyed_device", "rt_render_rays_keyed_fixed_device", "rt_post_process", "rt_post_process_fixed", "rt_trace_closest", "rt_trace_any",
     "rt_trace_closest_flags", "rt_trace_any_flags", "rt_query_closest_device", "rt_query_any_device", "rt_query_last_counters",
     "rt_render_aov_fixed", "rt_render_aov_rays_fixed_device", "rt_aov_resolve",
+    "rt_render_aov_follow_fixed", "rt_render_aov_follow_rays_fixed_device",
     "rt_denoise_scratch_bytes", "rt_denoise_default_params", "rt_denoise_fixed",
     "rt_denoise_dual_scratch_bytes", "rt_denoise_dual_default_params", "rt_denoise_dual_fixed",
     "rt_render_motion", "rt_temporal_default_params", "rt_temporal_accumulate_fixed",
@@ -187,6 +189,9 @@ def _bind(L):
                                               ctypes.c_uint32, vp, vp, ctypes.POINTER(RtStats)]
     L.rt_render_rays_keyed_fixed_device.argtypes = L.rt_render_rays_keyed_device.argtypes
     L.rt_render_aov_fixed.argtypes = [vp, vp, ci, ci, ci, ctypes.c_uint64, ci, ci, ctypes.c_uint32, vp, vp, vp, ctypes.POINTER(RtStats)]
+    L.rt_render_aov_follow_fixed.argtypes = [vp, vp, ci, ci, ci, ctypes.c_uint64, ci, ci, ctypes.c_uint32, ci, vp, vp, vp, ctypes.POINTER(RtStats)]
+    L.rt_render_aov_follow_rays_fixed_device.argtypes = [vp, ctypes.c_int64, vp, vp, vp, ci, ci, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32,
+                                                         ctypes.c_uint32, ci, vp, vp, vp, ctypes.POINTER(RtStats)]
     L.rt_render_aov_rays_fixed_device.argtypes = [vp, ctypes.c_int64, vp, vp, vp, ci, ci, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
                                                   vp, vp, vp, ctypes.POINTER(RtStats)]
     L.rt_aov_resolve.argtypes = [vp, vp, ci, ci, vp]
@@ -631,8 +636,19 @@ class Scene:
         write into) {triangle, material} of every pixel's first sample, -1 on a miss.  ``shard=(r, R)``: the samples G with
         G % R == r (spp % R == 0); the shards' sums add up to the whole frame's.  Sample G is camera ray G of a
         FLAG_RNG_PER_SAMPLE frame of the same seed.  ``flags``: 0, FLAG_REFERENCE_WALK or FLAG_WATERTIGHT."""
+        return self._render_aov("render_aov", None, camera, width, height, spp, seed, flags, shard, ids, out, stream)
+
+    def render_aov_follow(self, camera: np.ndarray, width: int, height: int, spp: int, max_specular: int, seed: int = 1, flags: int = 0,
+                          shard=(0, 1), ids=False, out=None, stream=None):
+        """render_aov with mirror and glass followed to the first non-specular vertex (rt_render_aov_follow_fixed): a sample whose
+        hit is specular goes on as sample G of the FLAG_RNG_PER_SAMPLE beauty frame does, for up to ``max_specular`` (0 ..
+        AOV_FOLLOW_MAX) vertices, and deposits beta * albedo, the faced normal and the path length of the vertex its chain ends
+        on; emission and ``ids`` stay the first hit's.  max_specular = 0 is render_aov, bit for bit.  stats["closest_rays"]
+        counts the chain rays too."""
+        return self._render_aov("render_aov_follow", max_specular, camera, width, height, spp, seed, flags, shard, ids, out, stream)
+
+    def _render_aov(self, what, max_specular, camera, width, height, spp, seed, flags, shard, ids, out, stream):
         import torch
-        what = "render_aov"
         for name, v in (("width", width), ("height", height), ("spp", spp)):
             if not isinstance(v, int) or v < 1:
                 raise RtError(f"{what}: {name} must be a positive int, it is {v!r}")
@@ -646,9 +662,14 @@ class Scene:
         s = torch.cuda.current_stream(out.device) if stream is None else stream
         c = ctypes.c_void_p
         st = RtStats()
-        _check(self.L.rt_render_aov_fixed(self.h, _p(cam), width, height, spp, seed, int(r), int(R), flags, c(out.data_ptr()),
-                                          c(None if ids is None else ids.data_ptr()), c(s.cuda_stream or None), ctypes.byref(st)),
-               "rt_render_aov_fixed", self.L)
+        tail = (c(out.data_ptr()), c(None if ids is None else ids.data_ptr()), c(s.cuda_stream or None), ctypes.byref(st))
+        if max_specular is None:
+            _check(self.L.rt_render_aov_fixed(self.h, _p(cam), width, height, spp, seed, int(r), int(R), flags, *tail), "rt_render_aov_fixed", self.L)
+        else:
+            if not isinstance(max_specular, int) or isinstance(max_specular, bool):
+                raise RtError(f"{what}: max_specular must be an int, it is {max_specular!r}")
+            _check(self.L.rt_render_aov_follow_fixed(self.h, _p(cam), width, height, spp, seed, int(r), int(R), flags, max_specular, *tail),
+                   "rt_render_aov_follow_fixed", self.L)
         return out, ids, st.as_dict()
 
     def render_aov_rays(self, origins, dirs, n_pixels: int, pixel=None, rays_per_pixel: int = 1, key_first: int = 0, key_stride: int = 1,
@@ -657,7 +678,21 @@ class Scene:
         key_first + c * key_stride and lands on pixel[c] or, without a pixel tensor, key // rays_per_pixel -> (sums, ids or
         None, stats) as render_aov.  ``ids`` needs pixel=None.  Chunks of one table, each with key_first = its first row,
         accumulate into one ``out``."""
-        what = "render_aov_rays"
+        return self._render_aov_rays("render_aov_rays", None, 0, origins, dirs, n_pixels, pixel, rays_per_pixel, key_first, key_stride, flags,
+                                     ids, out, stream)
+
+    def render_aov_follow_rays(self, origins, dirs, n_pixels: int, max_specular: int, seed: int = 1, pixel=None, rays_per_pixel: int = 1,
+                               key_first: int = 0, key_stride: int = 1, flags: int = 0, ids=False, out=None, stream=None):
+        """render_aov_rays with mirror and glass followed as render_aov_follow follows them
+        (rt_render_aov_follow_rays_fixed_device): row c continues on the stream of (seed, key_first + c * key_stride) behind its
+        first two draws, as render_rays_keyed's row does."""
+        if not isinstance(seed, int) or not 0 <= seed < 1 << 64:
+            raise RtError(f"render_aov_follow_rays: seed must be an int in 0 .. 2^64 - 1, it is {seed!r}")
+        return self._render_aov_rays("render_aov_follow_rays", max_specular, seed, origins, dirs, n_pixels, pixel, rays_per_pixel, key_first,
+                                     key_stride, flags, ids, out, stream)
+
+    def _render_aov_rays(self, what, max_specular, seed, origins, dirs, n_pixels, pixel, rays_per_pixel, key_first, key_stride, flags, ids,
+                         out, stream):
         n, device = self._query_rays(what, origins, dirs, None)
         if pixel is not None:
             self._query_rays(what, origins, dirs, None, pixel, "pixel")
@@ -671,11 +706,15 @@ class Scene:
         s = torch.cuda.current_stream(device) if stream is None else stream
         c = ctypes.c_void_p
         st = RtStats()
-        _check(self.L.rt_render_aov_rays_fixed_device(self.h, n, c(origins.data_ptr()), c(dirs.data_ptr()),
-                                                      c(None if pixel is None else pixel.data_ptr()), int(rays_per_pixel), n_pixels,
-                                                      key_first, key_stride, flags, c(out.data_ptr()),
-                                                      c(None if ids is None else ids.data_ptr()), c(s.cuda_stream or None),
-                                                      ctypes.byref(st)), "rt_render_aov_rays_fixed_device", self.L)
+        head = (self.h, n, c(origins.data_ptr()), c(dirs.data_ptr()), c(None if pixel is None else pixel.data_ptr()), int(rays_per_pixel), n_pixels)
+        tail = (c(out.data_ptr()), c(None if ids is None else ids.data_ptr()), c(s.cuda_stream or None), ctypes.byref(st))
+        if max_specular is None:
+            _check(self.L.rt_render_aov_rays_fixed_device(*head, key_first, key_stride, flags, *tail), "rt_render_aov_rays_fixed_device", self.L)
+        else:
+            if not isinstance(max_specular, int) or isinstance(max_specular, bool):
+                raise RtError(f"{what}: max_specular must be an int, it is {max_specular!r}")
+            _check(self.L.rt_render_aov_follow_rays_fixed_device(*head, seed, key_first, key_stride, flags, max_specular, *tail),
+                   "rt_render_aov_follow_rays_fixed_device", self.L)
         return out, ids, st.as_dict()
 
     # ---- where every pixel's first hit was one frame ago (rt_render_motion)

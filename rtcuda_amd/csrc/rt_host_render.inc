@@ -939,7 +939,7 @@ static int render_rays_keyed_impl(const rt_scene *scene, int64_t n_rays, const f
     return 0;
 }
 
-// rt_render_aov_fixed / rt_render_aov_rays_fixed_device / rt_render_motion: the entry points check their arguments (and, for a table, run the
+// rt_render_aov_fixed / rt_render_aov_rays_fixed_device, their followed forms (rt_render_aov_follow_*) / rt_render_motion: the entry points check their arguments (and, for a table, run the
 // device prepasses) and hand the ray source over; this is the one body behind both -- the reference's tree where the hit
 // definition needs it, the overflow stacks, the launch sized from the device, the kernel's time and the rare-path counters.
 // The caller holds the scene's query lock and has entered the scene's device; q.d_words is zeroed on `st`.
@@ -971,14 +971,16 @@ static int walker_launch(const rt_scene *scene, const HitMode &mode, KERNEL kern
     launch(grid, lds, stack_cap, q.d_over);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(q.ev_b, st));
-    HIP_TRY(hipMemcpyAsync(q.h_words->vstat, q.d_words->vstat, sizeof(q.h_words->vstat), hipMemcpyDeviceToHost, st));
+    // (the rare-path counters and, behind them, the chain rays of k_aov_follow: zero after every other kernel)
+    static_assert(offsetof(QueryWords, chain_rays) == offsetof(QueryWords, vstat) + sizeof(QueryWords::vstat), "one copy");
+    HIP_TRY(hipMemcpyAsync(q.h_words->vstat, q.d_words->vstat, sizeof(q.h_words->vstat) + sizeof(q.h_words->chain_rays), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     float ms = 0.f;
     HIP_TRY(hipEventElapsedTime(&ms, q.ev_a, q.ev_b));
     if (stats) {
         memset(stats, 0, sizeof(*stats));
         stats->camera_rays = n;
-        stats->closest_rays = n;
+        stats->closest_rays = n + (long long)q.h_words->chain_rays;
         stats->bvh_nodes = scene->n_nodes;
         stats->bvh_depth = scene->max_depth;
         stats->seconds_render = ms * 1e-3;
@@ -989,24 +991,51 @@ static int walker_launch(const rt_scene *scene, const HitMode &mode, KERNEL kern
     return 0;
 }
 template <class SRC>
-static int aov_launch(const rt_scene *scene, const SRC &src, int n, uint32_t flags, int64_t *d_aov, int32_t *d_ids, hipStream_t st,
-                      rt_stats *stats) {
+using AovFollowKernel = void (*)(DScene, SRC, AovParams, AovFollowParams, int, int *);
+template <class SRC>
+static AovFollowKernel<SRC> aov_follow_kernel(bool literal, bool verify, bool wide) {
+    if (literal) return k_aov_follow<SRC, false, true, false>;
+    if (verify) return wide ? k_aov_follow<SRC, true, false, true> : k_aov_follow<SRC, false, false, true>;
+    return wide ? k_aov_follow<SRC, true, false, false> : k_aov_follow<SRC, false, false, false>;
+}
+// max_specular = 0: k_aov (the first-hit entry points, and the followed ones at a cap of 0); 1 .. RT_AOV_FOLLOW_MAX: k_aov_follow.
+template <class SRC>
+static int aov_launch(const rt_scene *scene, const SRC &src, int n, uint32_t flags, uint64_t seed, int max_specular, int64_t *d_aov,
+                      int32_t *d_ids, hipStream_t st, rt_stats *stats) {
     const HitMode mode = hit_mode(flags);
     AovParams ap{};
     ap.n = n;
     ap.sums = (unsigned long long *)d_aov;
     ap.ids = d_ids;
     ap.vstat = scene->query.d_words->vstat;
+    if (max_specular > 0) {
+        AovFollowParams fp{};
+        fp.seed_lo = (uint32_t)seed;
+        fp.seed_hi = (uint32_t)(seed >> 32);
+        fp.max_specular = max_specular;
+        fp.chain_rays = &scene->query.d_words->chain_rays;
+        const AovFollowKernel<SRC> kernel = aov_follow_kernel<SRC>(mode.literal, mode.verify, scene->wide);
+        return walker_launch(scene, mode, kernel, n, st, stats, [&](int grid, size_t lds, int stack_cap, int *d_over) {
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, st, scene->dev(), src, ap, fp, stack_cap, d_over);
+        });
+    }
     const AovKernel<SRC> kernel = aov_kernel<SRC>(mode.literal, mode.verify, scene->wide);
     return walker_launch(scene, mode, kernel, n, st, stats, [&](int grid, size_t lds, int stack_cap, int *d_over) {
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, st, scene->dev(), src, ap, stack_cap, d_over);
     });
 }
+// the followed entry points' own check, after the argument checks they share with the first-hit ones
+static int aov_follow_cap(const std::string &w, int max_specular) {
+    if (max_specular < 0 || max_specular > RT_AOV_FOLLOW_MAX)
+        return fail(w + ": max_specular = " + std::to_string(max_specular) + " is outside 0 .. RT_AOV_FOLLOW_MAX (" + std::to_string(RT_AOV_FOLLOW_MAX) + ")");
+    return 0;
+}
 
-static int render_aov_impl(const rt_scene *scene, const rt_camera *camera, int width, int height, int spp, uint64_t seed,
-                           int shard_index, int shard_count, uint32_t flags, int64_t *d_aov, int32_t *d_ids, hipStream_t st,
-                           rt_stats *stats) {
-    const std::string w("rt_render_aov_fixed");
+// `name`, max_specular: rt_render_aov_fixed (0) or rt_render_aov_follow_fixed
+static int render_aov_impl(const char *name, const rt_scene *scene, const rt_camera *camera, int width, int height, int spp, uint64_t seed,
+                           int shard_index, int shard_count, uint32_t flags, int max_specular, int64_t *d_aov, int32_t *d_ids,
+                           hipStream_t st, rt_stats *stats) {
+    const std::string w(name);
     if (!scene) return fail(w + ": null scene");
     if (!camera || !d_aov) return fail(w + ": null " + (!camera ? "camera" : "d_aov_fixed"));
     if (aov_flags(w, flags)) return 1;
@@ -1018,6 +1047,7 @@ static int render_aov_impl(const rt_scene *scene, const rt_camera *camera, int w
         return fail(w + ": shard_index = " + std::to_string(shard_index) + " is outside 0 .. shard_count - 1 (shard_count = " + std::to_string(shard_count) + ")");
     if (spp % shard_count != 0)
         return fail(w + ": num_samples = " + std::to_string(spp) + " is not divisible by shard_count = " + std::to_string(shard_count));
+    if (aov_follow_cap(w, max_specular)) return 1;
     DeviceGuard dev;
     if (dev.enter(scene->device)) return 1;
     // (camera rays start at lookfrom: as render_shard_impl)
@@ -1037,25 +1067,28 @@ static int render_aov_impl(const rt_scene *scene, const rt_camera *camera, int w
     src.seed_hi = (uint32_t)(seed >> 32);
     const int n = (int)((long long)width * height * (spp / shard_count));
     // the sample with G % num_samples == 0 has G % shard_count == 0: it is shard 0's
-    return aov_launch(scene, src, n, flags, d_aov, shard_index == 0 ? d_ids : nullptr, st, stats);
+    return aov_launch(scene, src, n, flags, seed, max_specular, d_aov, shard_index == 0 ? d_ids : nullptr, st, stats);
 }
 
-static int render_aov_rays_impl(const rt_scene *scene, int64_t n_rays, const float *d_o, const float *d_d, const int32_t *d_pixel,
-                                int rays_per_pixel, int n_pixels, uint64_t key_first, uint32_t key_stride, uint32_t flags,
-                                int64_t *d_aov, int32_t *d_ids, hipStream_t st, rt_stats *stats) {
-    const std::string w("rt_render_aov_rays_fixed_device");
+// `name`, seed, max_specular: rt_render_aov_rays_fixed_device (no stream: 0, 0) or rt_render_aov_follow_rays_fixed_device
+static int render_aov_rays_impl(const char *name, const rt_scene *scene, int64_t n_rays, const float *d_o, const float *d_d,
+                                const int32_t *d_pixel, int rays_per_pixel, int n_pixels, uint64_t seed, uint64_t key_first,
+                                uint32_t key_stride, uint32_t flags, int max_specular, int64_t *d_aov, int32_t *d_ids, hipStream_t st,
+                                rt_stats *stats) {
+    const std::string w(name);
     if (check_table_pointers(w, scene, d_o, d_d, d_aov, "d_aov_fixed")) return 1;
     if (aov_flags(w, flags)) return 1;
     if (d_ids && d_pixel) return fail(w + ": d_ids together with d_pixel (ids belong to the pixels of the key rule: pass d_pixel = NULL)");
     if (check_table_args(w, n_rays, "the int32 camera-ray range of one call", n_pixels, nullptr)) return 1;
     KeyedRayTable src;
     if (check_key_range(w, "key", n_rays, key_first, key_stride, d_o, d_d, d_pixel, rays_per_pixel, n_pixels, &src)) return 1;
+    if (aov_follow_cap(w, max_specular)) return 1;
     DeviceGuard dev;
     if (dev.enter(scene->device)) return 1;
     std::lock_guard<std::mutex> lock(scene->query.mutex);
     if (ensure_query_state(scene, true)) return 1;
     if (int rc = validate_table(scene, w, (int)n_rays, d_o, d_d, d_pixel, n_pixels, st)) return rc;
-    return aov_launch(scene, src, (int)n_rays, flags, d_aov, d_ids, st, stats);
+    return aov_launch(scene, src, (int)n_rays, flags, seed, max_specular, d_aov, d_ids, st, stats);
 }
 
 // rt_render_motion: the AOV entry point's checks where they apply, the same query state and launch, k_motion's parameters.

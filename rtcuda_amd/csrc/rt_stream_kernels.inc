@@ -1,6 +1,7 @@
 // rt_stream_kernels.inc -- the kernels that walk a stream of rays: k_trace (the pools of a round), the query prepasses, the
-// stream walker of every dense ray array with its three kernels, k_query (rays from device buffers: the queries and their
-// host-pointer form, the trace hooks), k_aov (first-hit feature buffers) and k_motion (rt_render_motion).  Included by rtcuda_amd.hip, once, after rt_walk.inc.
+// stream walker of every dense ray array with its four kernels, k_query (rays from device buffers: the queries and their
+// host-pointer form, the trace hooks), k_aov (first-hit feature buffers), k_aov_follow (the same behind mirror and glass) and
+// k_motion (rt_render_motion).  Included by rtcuda_amd.hip, once, after rt_walk.inc.
 struct TraceParams {
     int total;             // number of slots
     int debug_no_deposit;  // perf experiments only: skip the framebuffer atomics
@@ -251,6 +252,7 @@ struct QueryWords {           // the scratch of one query call (rt_scene::QueryS
     unsigned bad_pixels;      // rt_render_rays_*: rays whose pixel index is outside the sum buffer (k_pixel_prepass)
     unsigned short_dirs;      // rays whose direction is not zero and has no component of 2^-60 or more (rt_bvh.h, kMinDirLength)
     unsigned long long vstat[4];  // V_OWN_FAIL, V_LOST, V_TIE, V_LITERAL of this call (rt_query_last_counters)
+    unsigned long long chain_rays;  // k_aov_follow: rays traced beyond the first of each sample (directly behind vstat: one copy)
 };
 struct QueryParams {
     int n, n_tris;
@@ -328,6 +330,11 @@ __global__ void k_query_inverse(const int *__restrict__ order, int n, int *__res
 //                                             across the wave (aov_deposit).
 // A refill pass, in this order: the VERIFY finalisation of finished closest-hit lanes, finish, the lane gives up its id, up to
 // two refill tries, the termination test.
+// An end that declares `static constexpr bool kRearms = true` (k_aov_follow's) has, in place of finish,
+//   finish_or_rearm(fin, id, o, d, tmax, tri, hu, hv) -> bool   called like finish; true (only where fin): the lane KEEPS its id
+//                                             and walks the ray the end has written into o, d, tmax and tri (-1) from the root.
+// The walker does not bound the re-arming: the end must (k_aov_follow: a counter per lane that only grows, below a cap).  For
+// every other end the branch does not exist (if constexpr): their kernels are instruction for instruction what they were.
 // LDS (dynamic): the stack columns, (stack_cap + 1) x kBlock ints (push_if).
 // Registers: no pool, shading or camera state is carried, but the VERIFY finalisation (ref_visible + the literal re-trace)
 // and the 4-wide node step with its seven 16-byte loads in flight want 71 VGPRs -- over the 64 of 8 waves per SIMD, where
@@ -344,6 +351,10 @@ __global__ void k_query_inverse(const int *__restrict__ order, int n, int *__res
 #endif
 constexpr int kQueryMinWaves = RT_QUERY_MIN_WAVES;
 constexpr int kQueryRefillAt = RT_QUERY_REFILL_AT;
+template <class ENDS, class = void>
+struct ends_rearm : std::false_type {};
+template <class ENDS>
+struct ends_rearm<ENDS, std::void_t<decltype(ENDS::kRearms)>> : std::bool_constant<ENDS::kRearms> {};
 template <bool ANY, bool WIDE, bool LITERAL, bool VERIFY, class ENDS>
 __device__ __forceinline__ void stream_walk(const DScene &sc, ENDS &ends, int n, unsigned long long *vstat, int stack_cap,
                                             int *overflow) {
@@ -368,8 +379,20 @@ __device__ __forceinline__ void stream_walk(const DScene &sc, ENDS &ends, int n,
             const bool fin = id >= 0 && cur == kEntryDone;
             if (!ANY && VERIFY && !LITERAL && fin && tri >= 0)
                 verify_closest(sc, o, d, [&] { return ends.restart_tmax(id); }, tmax, tri, hu, hv, vstat, stack, over, stack_cap);
-            ends.finish(fin, id, d, tmax, tri, hu, hv);
-            if (fin) id = -1;
+            if constexpr (ends_rearm<ENDS>::value) {
+                // the lane keeps its id and walks the ray the end has put into (o, d, tmax, tri)
+                if (ends.finish_or_rearm(fin, id, o, d, tmax, tri, hu, hv)) {
+                    inv = inv_dir(d);
+                    cur = 0;  // root
+                    sp = 0;
+                    hu = hv = 0.f;
+                } else if (fin) {
+                    id = -1;
+                }
+            } else {
+                ends.finish(fin, id, d, tmax, tri, hu, hv);
+                if (fin) id = -1;
+            }
             // ---- refill idle lanes (a second chunk when the current one runs out half-way)
             for (int tries = 0; tries < 2; tries++) {
                 const unsigned long long idle = wave_ballot(id < 0);
@@ -478,7 +501,8 @@ struct AovParams {
     int *ids;                    // n_pixels x 2 {triangle in the caller's order, material}, or null
     unsigned long long *vstat;
 };
-__device__ __forceinline__ void aov_ray(const AovCamera &s, int id, V3 &o, V3 &d) {
+// -> the sample's stream after the two jitter draws (k_aov_follow goes on with it; k_aov drops it)
+__device__ __forceinline__ Rng aov_ray_stream(const AovCamera &s, int id, V3 &o, V3 &d) {
     // gen_core, per-sample streams: pixel = id / spp, the stream of the global id, jitter x then y, camera.get_ray
     const int pixel = (int)((unsigned)id / s.spp);
     const int py = (int)((unsigned)pixel / (unsigned)s.width);
@@ -487,7 +511,9 @@ __device__ __forceinline__ void aov_ray(const AovCamera &s, int id, V3 &o, V3 &d
     const float jx = rng_uniform(rs);  // x first, then y (Appendix A.7)
     const float jy = rng_uniform(rs);
     camera_get_ray(s.cam, (px + jx) / s.width, (py + jy) / s.height, o, d);
+    return rs;
 }
+__device__ __forceinline__ void aov_ray(const AovCamera &s, int id, V3 &o, V3 &d) { (void)aov_ray_stream(s, id, o, d); }
 __device__ __forceinline__ void aov_ray(const KeyedRayTable &s, int id, V3 &o, V3 &d) {
     const float *o3 = s.o3 + 3 * (size_t)id, *d3 = s.d3 + 3 * (size_t)id;
     o = mk(table_load(o3), table_load(o3 + 1), table_load(o3 + 2));
@@ -531,11 +557,12 @@ __device__ __forceinline__ long long aov_push(int to_lane, long long x) {  // th
     const int hi = __builtin_amdgcn_ds_permute(to_lane << 2, (int)(unsigned)((unsigned long long)x >> 32));
     return (long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
 }
-__device__ __forceinline__ void aov_deposit(const AovParams &ap, bool dep, int pixel, long long (&val)[RT_AOV_HITS]) {
+// `hit`: what a depositing lane adds to the hit count (k_aov_follow: 0 for a chain that left the scene behind a specular vertex).
+__device__ __forceinline__ void aov_deposit(const AovParams &ap, bool dep, int pixel, long long (&val)[RT_AOV_HITS], int hit = 1) {
 #ifdef RT_AOV_NO_DEPOSIT
     if (ap.n != 0x7fffffff) return;  // measurement build (tools/aov_time.py): always taken, the host refuses such a frame
 #endif
-    int hits = dep ? 1 : 0;
+    int hits = dep ? hit : 0;
     if (RT_AOV_PRE_REDUCE) {
         const unsigned long long dm = wave_ballot(dep);
         if (dm == 0) return;
@@ -626,6 +653,135 @@ template <class SRC, bool WIDE, bool LITERAL, bool VERIFY>
 __global__ void __launch_bounds__(kBlock, kQueryMinWaves) k_aov(DScene sc, SRC src, AovParams ap, int stack_cap, int *overflow) {
     AovEnds<SRC> ends{sc, src, ap};
     stream_walk<false, WIDE, LITERAL, VERIFY>(sc, ends, ap.n, ap.vstat, stack_cap, overflow);
+}
+
+// ============================================================================ k_aov_follow: features of the first diffuse vertex
+// rt_render_aov_follow_fixed / rt_render_aov_follow_rays_fixed_device (DESIGN.md section 2.11): k_aov's buffers, but a sample
+// whose hit is a mirror or glass goes on as sample G of the RT_FLAG_RNG_PER_SAMPLE beauty frame goes on -- mat()'s step there,
+// draw for draw -- for up to max_specular vertices, and deposits the features of the vertex its chain ends on.  The fourth pair
+// of ends on the stream walker, and the one that re-arms: a finished lane whose hit is specular with j < max_specular keeps its
+// id and takes the next ray of its chain in place.  j grows by one with every re-arm and the host refuses a cap above
+// RT_AOV_FOLLOW_MAX, so a lane re-arms at most five times.
+// Carried per lane (12 registers more than k_aov): the stream (6 words), beta, the path length, and one word that holds j and
+// the first hit's light.  (Re-deriving the stream from the key and a draw count would carry 1 word for 6 and pay a
+// rng_sample_stream and up to 17 steps per vertex; not built.)
+struct AovFollowParams {
+    uint32_t seed_lo, seed_hi;       // the table form's streams (the camera form's seed travels in AovCamera)
+    int max_specular;                // 1 .. RT_AOV_FOLLOW_MAX (0 is served by k_aov)
+    unsigned long long *chain_rays;  // QueryWords::chain_rays: the rays traced beyond the first of each sample
+};
+__device__ __forceinline__ Rng aov_ray_stream(const KeyedRayTable &s, const AovFollowParams &fp, int id, V3 &o, V3 &d) {
+    aov_ray(s, id, o, d);
+    Rng rs = rng_sample_stream(fp.seed_lo, fp.seed_hi, s.key_first + (unsigned long long)(unsigned)id * s.key_stride);
+    rng_next(rs);  // the two jitter draws, made and thrown away (gen_core's keyed branch)
+    rng_next(rs);
+    return rs;
+}
+__device__ __forceinline__ Rng aov_ray_stream(const AovCamera &s, const AovFollowParams &, int id, V3 &o, V3 &d) {
+    return aov_ray_stream(s, id, o, d);
+}
+template <class SRC>
+struct AovFollowEnds {
+    static constexpr bool kRearms = true;
+    const DScene &sc;
+    const SRC &src;
+    const AovParams &ap;
+    const AovFollowParams &fp;
+    // per lane, from take() to the deposit
+    Rng rs;
+    V3 beta;
+    float path;  // ((t_0 + t_1) + ...) + t_j
+    int jl;      // j | (light of the first hit + 1) << 8
+    // per wave
+    unsigned long long rearmed = 0;
+    __device__ __forceinline__ float restart_tmax(int) const { return kFltMax; }
+    __device__ __forceinline__ void take(int id, V3 &o, V3 &d, float &tmax, int &tri) {
+        rs = aov_ray_stream(src, fp, id, o, d);
+        beta = mk(1.f, 1.f, 1.f);
+        path = 0.f;
+        jl = 0;
+        tmax = kFltMax;
+        tri = -1;
+    }
+    __device__ __forceinline__ bool finish_or_rearm(bool fin, int id, V3 &o, V3 &d, float &tmax, int &tri, float hu, float hv) {
+        bool first = false, again = false;
+        int pixel = -1, mat = -1, hit = 0;
+        long long val[RT_AOV_HITS];
+#pragma unroll
+        for (int c = 0; c < RT_AOV_HITS; c++) val[c] = 0;
+        if (fin) pixel = aov_pixel(src, id, first);
+        const int j = jl & 0xff, hit_tri = tri;
+        if (fin && tri >= 0) {
+            const float4 sh = sc.tri_shade[(unsigned)tri];
+            const int info = __float_as_int(sh.w);
+            mat = info & 0xffff;
+            if (j == 0) jl = ((info >> 16) & 0xffff) << 8;  // the light of the first hit (+ 1)
+            V3 n = mk(sh.x, sh.y, sh.z);
+            const Material m = tab_material(sc.tables, mat);
+            path = path + tmax;  // (0.f + t_0 is t_0)
+            if (m.type != 0 && j < fp.max_specular) {
+                // ---- mat() :139-248 at this vertex: the new ray, beta, and the stream behind everything mat() draws there
+                const Tri tr = load_tri(sc.tris, tri);
+                V3 wi;
+                float pdf;
+                int again_draws;
+                const V3 f = mat_sample_f(m, d, rs, n, wi, pdf, again_draws);
+                o = offset_ray_origin(tri_point(tr, hu, hv), n);
+                beta = mul(beta, divf(scale(f, dot(wi, n)), pdf));  // :166
+                d = wi;
+                if (sc.num_lights > 0) {
+                    const int light_idx = min((int)(rng_uniform(rs) * sc.num_lights), sc.num_lights - 1);  // :178
+                    if (tab_light(sc.tables, sc.num_mats, light_idx).type != 0) {
+                        rng_next(rs);  // Triangle::sample_p
+                        rng_next(rs);
+                        if (again_draws >= 1) rng_next(rs);  // the second sample_f call
+                        if (again_draws >= 2) rng_next(rs);
+                    }
+                }
+                tmax = kFltMax;
+                tri = -1;
+                jl += 1;
+                again = true;
+            } else {
+                if (dot(n, d) > 0.f) n = neg(n);  // faced against the arriving direction
+                val[RT_AOV_ALBEDO + 0] = to_fixed(beta.x * m.ax);
+                val[RT_AOV_ALBEDO + 1] = to_fixed(beta.y * m.ay);
+                val[RT_AOV_ALBEDO + 2] = to_fixed(beta.z * m.az);
+                val[RT_AOV_NORMAL + 0] = to_fixed(n.x);
+                val[RT_AOV_NORMAL + 1] = to_fixed(n.y);
+                val[RT_AOV_NORMAL + 2] = to_fixed(n.z);
+                val[RT_AOV_DEPTH] = to_fixed(path);
+                hit = 1;
+            }
+        }
+        if (fin && j == 0 && ap.ids && first) {  // the ids stay the first hit's
+            ap.ids[2 * (size_t)(unsigned)pixel] = hit_tri >= 0 ? sc.order[(unsigned)hit_tri] : -1;
+            ap.ids[2 * (size_t)(unsigned)pixel + 1] = mat;
+        }
+        const int light = (jl >> 8) - 1;
+        const bool ends_here = fin && !again;
+        if (ends_here && light >= 0) {  // render.cuh:98-103: the first hit's, wherever the chain ends
+            const Light l = tab_light(sc.tables, sc.num_mats, light);
+            val[RT_AOV_EMISSION + 0] = to_fixed(l.lx);
+            val[RT_AOV_EMISSION + 1] = to_fixed(l.ly);
+            val[RT_AOV_EMISSION + 2] = to_fixed(l.lz);
+        }
+        // a chain that left the scene behind a specular vertex: its emission, no hit
+        const bool dep = ends_here && (hit != 0 || light >= 0);
+        aov_deposit(ap, dep, dep ? pixel : -1, val, hit);
+        rearmed += wave_count((again));
+        return again;
+    }
+};
+// Registers (profiles/aov_follow_resources.md): under k_aov's budget of 4 waves per SIMD (128 VGPRs, which k_aov's deposit
+// fills to 113 - 124) the twelve words more spill 1 to 4 VGPRs in every build but the literal ones; at 3 waves nothing spills.
+constexpr int kAovFollowMinWaves = 3;
+template <class SRC, bool WIDE, bool LITERAL, bool VERIFY>
+__global__ void __launch_bounds__(kBlock, kAovFollowMinWaves) k_aov_follow(DScene sc, SRC src, AovParams ap, AovFollowParams fp, int stack_cap,
+                                                                      int *overflow) {
+    AovFollowEnds<SRC> ends{sc, src, ap, fp};
+    stream_walk<false, WIDE, LITERAL, VERIFY>(sc, ends, ap.n, ap.vstat, stack_cap, overflow);
+    if (lane_id() == 0 && ends.rearmed != 0) atomicAdd(fp.chain_rays, ends.rearmed);
 }
 
 // ============================================================================ k_motion: where a pixel's first hit was one frame ago

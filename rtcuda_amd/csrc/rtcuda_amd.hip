@@ -1152,16 +1152,30 @@ int rt_post_process_fixed(const int64_t *d_sum_fixed, float *d_rgb_out, int num_
 int rt_render_aov_fixed(const rt_scene *scene, const rt_camera *camera, int width, int height, int num_samples, uint64_t seed,
                         int shard_index, int shard_count, uint32_t flags, int64_t *d_aov_fixed, int32_t *d_ids, void *stream,
                         rt_stats *stats) {
-    return render_aov_impl(scene, camera, width, height, num_samples, seed, shard_index, shard_count, flags, d_aov_fixed, d_ids,
-                           (hipStream_t)stream, stats);
+    return render_aov_impl("rt_render_aov_fixed", scene, camera, width, height, num_samples, seed, shard_index, shard_count, flags, 0,
+                           d_aov_fixed, d_ids, (hipStream_t)stream, stats);
+}
+int rt_render_aov_follow_fixed(const rt_scene *scene, const rt_camera *camera, int width, int height, int num_samples, uint64_t seed,
+                               int shard_index, int shard_count, uint32_t flags, int max_specular, int64_t *d_aov_fixed,
+                               int32_t *d_ids, void *stream, rt_stats *stats) {
+    return render_aov_impl("rt_render_aov_follow_fixed", scene, camera, width, height, num_samples, seed, shard_index, shard_count,
+                           flags, max_specular, d_aov_fixed, d_ids, (hipStream_t)stream, stats);
 }
 
 int rt_render_aov_rays_fixed_device(const rt_scene *scene, int64_t n_rays, const float *d_origin_xyz, const float *d_dir_xyz,
                                     const int32_t *d_pixel, int rays_per_pixel, int n_pixels, uint64_t key_first,
                                     uint32_t key_stride, uint32_t flags, int64_t *d_aov_fixed, int32_t *d_ids, void *stream,
                                     rt_stats *stats) {
-    return render_aov_rays_impl(scene, n_rays, d_origin_xyz, d_dir_xyz, d_pixel, rays_per_pixel, n_pixels, key_first, key_stride,
-                                flags, d_aov_fixed, d_ids, (hipStream_t)stream, stats);
+    return render_aov_rays_impl("rt_render_aov_rays_fixed_device", scene, n_rays, d_origin_xyz, d_dir_xyz, d_pixel, rays_per_pixel,
+                                n_pixels, 0, key_first, key_stride, flags, 0, d_aov_fixed, d_ids, (hipStream_t)stream, stats);
+}
+int rt_render_aov_follow_rays_fixed_device(const rt_scene *scene, int64_t n_rays, const float *d_origin_xyz, const float *d_dir_xyz,
+                                           const int32_t *d_pixel, int rays_per_pixel, int n_pixels, uint64_t seed,
+                                           uint64_t key_first, uint32_t key_stride, uint32_t flags, int max_specular,
+                                           int64_t *d_aov_fixed, int32_t *d_ids, void *stream, rt_stats *stats) {
+    return render_aov_rays_impl("rt_render_aov_follow_rays_fixed_device", scene, n_rays, d_origin_xyz, d_dir_xyz, d_pixel,
+                                rays_per_pixel, n_pixels, seed, key_first, key_stride, flags, max_specular, d_aov_fixed, d_ids,
+                                (hipStream_t)stream, stats);
 }
 
 int rt_aov_resolve(const int64_t *d_aov_fixed, float *d_out, int n_pixels, int num_samples, void *stream) {
