@@ -361,6 +361,7 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
     unsigned long long pf[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long pf_gen_cycles = 0, pf_fin_cycles = 0, pf_fin_lanes = 0, pf_fin_iters = 0;
     unsigned long long pf_handovers = 0, pf_handover_blocks = 0;  // releases at a chunk's end (lanes), and the GEN blocks that made one
+    unsigned long long pf_rr_turns = 0, pf_rr_blocks = 0;  // turns of the Russian-roulette chain the wave went round (a block's longest chain), and the ADV blocks that went round at all
     const unsigned long long pf_t0 = __builtin_readcyclecounter();
     // per lane: the start (cycles since pf_t0) of the last fin section it left with work in hand; from there to the wave's
     // exit the lane sits through whole-wave blocks that do nothing for it (the lane-idle tail)
@@ -899,6 +900,12 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
             }
 #ifdef RT_TRACE_PROFILE
             pf[8] += __builtin_readcyclecounter() - pf_ta;
+            {  // (behind the block's clock: the chain's turns are the longest lane's rolls)
+                int turns = out.rr_draws;
+                for (int off = 32; off > 0; off >>= 1) turns = max(turns, __shfl_xor(turns, off));
+                pf_rr_turns += (unsigned long long)turns;
+                pf_rr_blocks += turns != 0 ? 1 : 0;
+            }
 #endif
             retake();
             RT_MARK("adv.after");
@@ -1128,8 +1135,9 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
         { pf[11] = pf_life; for (int k = 0; k < 16; k++) atomicAdd(&prof[k], pf[k]); atomicMax(&prof[13], pf[11]); atomicAdd(&prof[14], 1ull); atomicAdd(&prof[16], pf_gen_cycles);
           atomicAdd(&prof[20], pf_idle); atomicAdd(&prof[21], pf_idle_max);
           atomicAdd(&prof[22], pf_handovers); atomicAdd(&prof[23], pf_handover_blocks);
+          atomicAdd(&prof[24], pf_rr_turns); atomicAdd(&prof[25], pf_rr_blocks);
           // per-wave record: where it ran and for how long
-          unsigned long long *rec = prof + 24 + kProfRec * (size_t)((blockIdx.x * kBlock + threadIdx.x) >> 6);
+          unsigned long long *rec = prof + kProfHead + kProfRec * (size_t)((blockIdx.x * kBlock + threadIdx.x) >> 6);
           rec[0] = __builtin_amdgcn_s_getreg((31 << 11) | 4);   // HW_ID
           rec[1] = __builtin_amdgcn_s_getreg((31 << 11) | 20);  // XCC_ID
           rec[2] = pf[11];

@@ -339,8 +339,8 @@ struct FrameRun {
 
 #ifdef RT_TRACE_PROFILE
 static int report_paths_profile(unsigned long long *paths_prof, int paths_blocks) {
-    unsigned long long h[24];
-    HIP_TRY(hipMemcpy(h, paths_prof, 192, hipMemcpyDeviceToHost));
+    unsigned long long h[kProfHead];
+    HIP_TRY(hipMemcpy(h, paths_prof, sizeof(h), hipMemcpyDeviceToHost));
     fprintf(stderr, "k_paths cycles: ADV %.1f%% (%.0f / block) node %.1f%% (%.0f) tri %.1f%% (%.0f) rest %.1f%%\n",
             100.0 * h[8] / h[11], h[0] ? (double)h[8] / h[0] : 0.0, 100.0 * h[9] / h[11], h[2] ? (double)h[9] / h[2] : 0.0,
             100.0 * h[10] / h[11], h[4] ? (double)h[10] / h[4] : 0.0, 100.0 * (double)(h[11] - h[8] - h[9] - h[10]) / h[11]);
@@ -360,9 +360,11 @@ static int report_paths_profile(unsigned long long *paths_prof, int paths_blocks
     fprintf(stderr, "k_paths profile: ADV blocks %llu avg lanes %.1f | node steps %llu avg lanes %.1f (ADV-waiting %.1f) | tri steps %llu avg lanes %.1f (ADV-waiting %.1f)\n",
             h[0], h[0] ? (double)h[1] / h[0] : 0.0, h[2], h[2] ? (double)h[3] / h[2] : 0.0, h[2] ? (double)h[6] / h[2] : 0.0, h[4],
             h[4] ? (double)h[5] / h[4] : 0.0, h[4] ? (double)h[7] / h[4] : 0.0);
+    fprintf(stderr, "k_paths Russian-roulette chain: %.2f turns per ADV block (the longest lane's rolls), %.1f %% of the ADV blocks went round at all (%.2f turns each)\n",
+            h[0] ? (double)h[24] / h[0] : 0.0, h[0] ? 100.0 * h[25] / h[0] : 0.0, h[25] ? (double)h[24] / h[25] : 0.0);
     if (const char *dump = knob("RT_PROF_DUMP")) {  // per-wave records: hw_id xcc_id cycles blocks idle_lane_cycles longest_lane_tail
         std::vector<unsigned long long> recs(kProfRec * (size_t)paths_blocks * (kBlock / 64));
-        HIP_TRY(hipMemcpy(recs.data(), paths_prof + 24, recs.size() * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(recs.data(), paths_prof + kProfHead, recs.size() * 8, hipMemcpyDeviceToHost));
         if (FILE *f = fopen(dump, "w")) {
             for (size_t k = 0; k < recs.size(); k += kProfRec)
                 fprintf(f, "%zu %llu %llu %llu %llu %llu %llu\n", k / kProfRec, recs[k], recs[k + 1], recs[k + 2], recs[k + 3], recs[k + 4], recs[k + 5]);
@@ -393,7 +395,7 @@ int FrameRun::run_persistent() {
     top_records_in_lds = p.top_n;
     unsigned long long *paths_prof = nullptr;
 #ifdef RT_TRACE_PROFILE
-    const size_t prof_bytes = 192 + 8 * kProfRec * (size_t)(grid_for(c.n) * (kBlock / 64));
+    const size_t prof_bytes = 8 * kProfHead + 8 * kProfRec * (size_t)(grid_for(c.n) * (kBlock / 64));
     HIP_TRY(hipMalloc((void **)&paths_prof, prof_bytes));
     HIP_TRY(hipMemset(paths_prof, 0, prof_bytes));
 #endif

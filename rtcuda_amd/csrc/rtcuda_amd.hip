@@ -677,19 +677,31 @@ __device__ __forceinline__ void advance_core(const DScene &sc, const float *tab,
     if (cont && hit) {
         bool shade = true;
         if (st.bounces > kRrStart && max3(st.beta) < kRrThreshold) {  // :112-124
+            // The chain is a lane's own loop inside a whole-wave block: a turn is paid by the wave for as long as its longest
+            // lane rolls, so the turn holds only the draw and ONE stop test.  The rolls a lane may make are known before the
+            // loop (`cont` holds: at least one); bounces, rr_draws, the survivor bit and the survivor's beta follow from the
+            // number of rolls behind it.  beta is neither read nor written in the loop.
             const float pt = fmaxf(0.05f, 1 - max3(st.beta));
-            shade = false;
-            while (true) {
-                out.rr_draws++;
-                const bool kill = rng_uniform(st.rs) < pt;
-                st.bounces = st.bounces + 1;  // :126
-                if (!kill) {
-                    st.beta = divf(st.beta, 1 - pt);
-                    shade = true;
-                    break;
-                }
-                if (lockstep || !(st.bounces < ap.max_bounces)) break;
-            }
+            const int limit = lockstep ? 1 : ap.max_bounces - st.bounces;
+            int n = 0;
+            uint32_t draw;
+            bool kill;
+            RT_MARK("adv.rr.begin");
+            do {
+                n++;  // :126
+                rng_step(st.rs);
+                st.rs.d += kRngWeyl;
+                draw = st.rs.v4 + st.rs.d;  // (rng_next)
+                kill = rng_to_uniform(draw) < pt;  // (a draw equal to pt survives)
+            } while (kill & (n < limit));
+            RT_MARK("adv.rr.end");
+            // (the test again, on the lane's last draw: carried out of the loop, the bit is kept every turn for the lanes
+            // already through -- see gen.loop.end.  The empty statement emits nothing.)
+            __asm__ volatile("" : "+v"(draw));
+            shade = !(rng_to_uniform(draw) < pt);
+            st.bounces = st.bounces + n;
+            out.rr_draws = n;
+            if (shade) st.beta = divf(st.beta, 1 - pt);
         } else {
             st.bounces = st.bounces + 1;  // :126
         }
@@ -858,7 +870,8 @@ constexpr bool kSpeculate = RT_SPECULATE != 0;  // k_paths: postpone a leaf reac
 // k_paths_rays.  Two compilations of one text rather than a template parameter or a shared device function: the camera
 // builds keep their symbols, their arguments and -- instruction for instruction -- their code.
 #ifdef RT_TRACE_PROFILE
-constexpr int kProfRec = 6;  // qwords of k_paths' per-wave record (behind the 24 totals)
+constexpr int kProfHead = 26;  // qwords of k_paths' totals
+constexpr int kProfRec = 6;    // qwords of k_paths' per-wave record (behind the totals)
 #endif
 #define RT_PATHS_CHUNKS 0
 #define RT_PATHS_BG 0
