@@ -505,6 +505,35 @@ inline rt_stats render_rays_keyed_fixed(const Scene &scene, int64_t n_rays, cons
     return st;
 }
 
+// A sample count per pixel (rt_render_counts_fixed, which documents the samples, the promises, the flags and the errors): pixel p
+// renders the samples d_first[p] .. d_first[p] + d_count[p] - 1 (d_first nullptr: from 0) of the RT_FLAG_RNG_PER_SAMPLE frame with
+// sample_stride samples per pixel; the int64 sums are ADDED into d_sum_fixed and the counts into d_samples (if given).  Calls whose
+// ranges tile [0, sample_stride) add up to exactly the whole frame's sums.
+inline rt_stats render_counts(const Scene &scene, const Camera &camera, int width, int height, int sample_stride, const int32_t *d_first,
+                              const int32_t *d_count, int64_t *d_sum_fixed, int32_t *d_samples = nullptr, int max_bounces = 10,
+                              uint64_t seed = 1, uint32_t flags = 0, void *stream = nullptr) {
+    rt_scene *h = scene.bvh.handle ? rtcuda_detail::realise(scene) : nullptr;
+    rt_stats st{};
+    rtcuda_detail::check(rt_render_counts_fixed(h, &camera.pod, width, height, sample_stride, d_first, d_count, max_bounces, seed, flags,
+                                                d_sum_fixed, d_samples, stream, &st), "render_counts");
+    return st;
+}
+// What a counted frame is used with (rt_normalize_counts_fixed / rt_post_process_counts_fixed / rt_sample_allocate, which document
+// the arithmetic and the errors): sums over a per-pixel divisor as int64 sums of one sample of the mean (in place allowed), the
+// post-processed image with the pixel's own count, and counts from a weight map under a budget (returns the total placed).
+inline void normalize_counts(const int64_t *d_sum_fixed, const int32_t *d_samples, int num_pixels, int64_t *d_out_fixed, void *stream = nullptr) {
+    rtcuda_detail::check(rt_normalize_counts_fixed(d_sum_fixed, d_samples, num_pixels, d_out_fixed, stream), "normalize_counts");
+}
+inline void post_process_counts(const int64_t *d_sum_fixed, const int32_t *d_samples, int num_pixels, float *d_rgb_out, void *stream = nullptr) {
+    rtcuda_detail::check(rt_post_process_counts_fixed(d_sum_fixed, d_samples, num_pixels, d_rgb_out, stream), "post_process_counts");
+}
+inline int64_t sample_allocate(const float *d_weight, int num_pixels, int min_count, int max_count, int64_t budget, int32_t *d_count_out,
+                               void *stream = nullptr) {
+    int64_t total = 0;
+    rtcuda_detail::check(rt_sample_allocate(d_weight, num_pixels, min_count, max_count, budget, d_count_out, &total, stream), "sample_allocate");
+    return total;
+}
+
 // First-hit feature buffers (no reference counterpart): albedo, normal, emission, depth and hit count per pixel as int64
 // fixed-point sums ADDED into d_aov_fixed (n_pixels x RT_AOV_CHANNELS), optionally {triangle, material} of every pixel's first
 // sample in d_ids (n_pixels x 2) -- rt_render_aov_fixed / rt_render_aov_rays_fixed_device / rt_aov_resolve, which document the

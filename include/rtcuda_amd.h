@@ -381,6 +381,69 @@ int rt_render_rays_keyed_fixed_device(const rt_scene *scene, int64_t n_rays, con
                                       uint64_t seed, uint64_t key_first, uint32_t key_stride, uint32_t flags,
                                       int64_t *d_sum_fixed, void *stream, rt_stats *stats);
 
+/* ---- counted frames: a sample count per pixel, so samples go where the error is and the passes add up exactly --------------
+ * Every entry point above takes one num_samples for the whole image.  Here pixel p (0 <= p < width * height) renders the
+ * samples k = d_first[p] .. d_first[p] + d_count[p] - 1 (d_first NULL: all 0) of the RT_FLAG_RNG_PER_SAMPLE frame
+ * (width, height, num_samples = sample_stride, seed):
+ *   - sample k of pixel p IS camera ray G = p * sample_stride + k of that frame: its stream is the per-sample stream of
+ *     (seed, G) with a 64-bit key (sample_stride may be as large as 2^31 - 1), it draws jitter x then y, makes the pinhole ray,
+ *     runs its path to its own end with RT_FLAG_WATERTIGHT's hits, sums its contributions in float in path order and adds them
+ *     to its pixel once;
+ *   - d_first and d_count are device arrays of width * height int32; d_sum_fixed is width * height * 3 int64 in units of 2^-30
+ *     and is ADDED to; d_samples, if given, is width * height int32 and gets d_count[p] ADDED: the divisor a caller keeps over
+ *     several passes (rt_normalize_counts_fixed, rt_post_process_counts_fixed below).
+ * Three promises follow from the definition, and the tests hold them:
+ *   WHOLE FRAME  with d_first NULL and every count equal to sample_stride, the sums and the six event totals are those of
+ *                rt_render_shard_fixed(..., num_samples = sample_stride, shard 0 of 1, RT_FLAG_RNG_PER_SAMPLE), bit for bit;
+ *   TILING       any set of calls whose ranges [first, first + count) tile [0, sample_stride) for every pixel gives exactly
+ *                those sums, in any order: progressive passes, a base pass and an adaptive one, rank r of R on another device;
+ *   KEYED TABLE  a call equals rt_render_rays_keyed_fixed_device on the table that lists the same keys.
+ * rt_stats: camera_rays is the sum of the counts; the samples of a pixel through which no ray can hit the scene are counted as
+ * in the per-sample camera path (camera_rays, closest_rays) and passed over without a stream or a ray; everything else is the
+ * per-sample mode's.
+ * flags: 0, RT_FLAG_TIME_KERNELS; RT_FLAG_RNG_PER_SAMPLE and RT_FLAG_WATERTIGHT are accepted and change nothing (both are what
+ * the mode is); RT_FLAG_REFERENCE_WALK and any other bit is an error that names the flag.  A scene with 2-wide nodes
+ * (RT_BVH_WIDE=0), or a process without the persistent kernel (RT_PERSISTENT=0), is an error, as for the keyed tables.
+ * Checks.  Host-side: non-null scene, camera, d_count and d_sum_fixed; 1 <= sample_stride <= 2^31 - 1; width, height >= 1 and
+ * width * height <= 715827882; 0 <= max_bounces <= 2^24.  On the device, before anything is written: d_count[p] >= 0,
+ * d_first[p] >= 0 and d_first[p] + d_count[p] <= sample_stride (without int32 overflow) for every pixel -- the error names the
+ * number of offending pixels -- and the sum of the counts stays below the camera-ray range of rt_render_shard (ids within
+ * 13 * 2^20 of 2^31).  Every error returns non-zero, names rt_render_counts_fixed in rt_last_error() and writes nothing.
+ * A sum of 0 is legal: the call returns 0, writes nothing and reports zero events.
+ * The work is ordered on `stream` and complete when the call returns; the current device is left as it was; once the render
+ * context owns its scratch for this image size (width * height + 1 words) the call allocates nothing.
+ * Out of scope: count maps for ray tables and for the AOV, follow and motion kernels; a float-atomic framebuffer variant;
+ * a helper that splits a count map over ranks (a rank passes its own d_first / d_count). */
+int rt_render_counts_fixed(const rt_scene *scene, const rt_camera *camera, int width, int height, int sample_stride,
+                           const int32_t *d_first /* may be NULL: all 0 */, const int32_t *d_count, int max_bounces,
+                           uint64_t seed, uint32_t flags, int64_t *d_sum_fixed, int32_t *d_samples /* may be NULL */,
+                           void *stream, rt_stats *stats);
+
+/* Sums with a per-pixel divisor -> the format the temporal accumulators emit: int64 sums of ONE sample of the mean, so that
+ * rt_denoise_fixed(out, 1, aov, aov_spp, ...), rt_denoise_variance_fixed and the accumulators take an adaptive frame unchanged.
+ * Per channel, with n = d_samples[p]: n == 0 gives 0, otherwise sign(s) * ((|s| + (n >> 1)) / n) in exact 64-bit integer
+ * arithmetic (n == 1: the identity).  In place (d_out_fixed == d_sum_fixed) is allowed.  A negative n is an error, checked on
+ * the device before anything is written (the message names the number of such pixels); the call waits for that check. */
+int rt_normalize_counts_fixed(const int64_t *d_sum_fixed, const int32_t *d_samples, int num_pixels, int64_t *d_out_fixed,
+                              void *stream);
+/* rt_post_process_fixed with the pixel's own count where that has num_samples: sqrt(float(sum * 2^-30) * (1 / float(n))), the
+ * same operations in the same order; n <= 0 gives 0.  Asynchronous on `stream`. */
+int rt_post_process_counts_fixed(const int64_t *d_sum_fixed, const int32_t *d_samples, int num_pixels, float *d_rgb_out,
+                                 void *stream);
+
+/* From a weight map to counts under a budget, in exact integer arithmetic (what the weight means stays with the caller: the
+ * documented loop uses the relative standard deviation from rt_temporal_accumulate_moments_fixed's variance plus a floor):
+ *   q[p]     = 0 unless w > 0 (NaN, zero, negatives), else (uint64) floorf(fminf(w, 4096.f) * 1048576.f): exact in fp32, <= 2^32
+ *   T        = the sum of q[p] as a 64-bit integer
+ *   extra    = budget - num_pixels * min_count
+ *   count[p] = min(max_count, min_count + (T ? (extra * q[p]) / T : extra / num_pixels))
+ *   *total_out (host) = the sum of count[p] <= budget.
+ * What flooring and the cap leave over is NOT redistributed: *total_out says how much of the budget was placed.
+ * Errors (nothing is written): a null pointer, num_pixels < 1, min_count < 0, max_count < min_count, extra < 0, extra >= 2^31.
+ * Ordered on `stream`; the call waits for the total. */
+int rt_sample_allocate(const float *d_weight, int num_pixels, int min_count, int max_count, int64_t budget,
+                       int32_t *d_count_out, int64_t *total_out /* host */, void *stream);
+
 /* ---- first-hit feature buffers (AOVs): albedo, normal, emission, depth, coverage per pixel, and object ids ----------------
  * What a denoiser, a compositor or a learning pipeline takes next to the noisy image, from one kernel that makes the ray,
  * finds the hit and deposits the features: no ray table, no round trip (no reference counterpart: its render() writes

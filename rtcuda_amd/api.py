@@ -41,6 +41,7 @@ EXPORTS = [
     "rt_trace_closest_flags", "rt_trace_any_flags", "rt_query_closest_device", "rt_query_any_device", "rt_query_last_counters",
     "rt_render_aov_fixed", "rt_render_aov_rays_fixed_device", "rt_aov_resolve",
     "rt_render_aov_follow_fixed", "rt_render_aov_follow_rays_fixed_device",
+    "rt_render_counts_fixed", "rt_normalize_counts_fixed", "rt_post_process_counts_fixed", "rt_sample_allocate",
     "rt_denoise_scratch_bytes", "rt_denoise_default_params", "rt_denoise_fixed",
     "rt_denoise_dual_scratch_bytes", "rt_denoise_dual_default_params", "rt_denoise_dual_fixed",
     "rt_render_motion", "rt_temporal_default_params", "rt_temporal_accumulate_fixed",
@@ -188,6 +189,10 @@ def _bind(L):
     L.rt_render_rays_keyed_device.argtypes = [vp, ctypes.c_int64, vp, vp, vp, ci, ci, ci, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32,
                                               ctypes.c_uint32, vp, vp, ctypes.POINTER(RtStats)]
     L.rt_render_rays_keyed_fixed_device.argtypes = L.rt_render_rays_keyed_device.argtypes
+    L.rt_render_counts_fixed.argtypes = [vp, vp, ci, ci, ci, vp, vp, ci, ctypes.c_uint64, ctypes.c_uint32, vp, vp, vp, ctypes.POINTER(RtStats)]
+    L.rt_normalize_counts_fixed.argtypes = [vp, vp, ci, vp, vp]
+    L.rt_post_process_counts_fixed.argtypes = [vp, vp, ci, vp, vp]
+    L.rt_sample_allocate.argtypes = [vp, ci, ci, ci, ctypes.c_int64, vp, ctypes.POINTER(ctypes.c_int64), vp]
     L.rt_render_aov_fixed.argtypes = [vp, vp, ci, ci, ci, ctypes.c_uint64, ci, ci, ctypes.c_uint32, vp, vp, vp, ctypes.POINTER(RtStats)]
     L.rt_render_aov_follow_fixed.argtypes = [vp, vp, ci, ci, ci, ctypes.c_uint64, ci, ci, ctypes.c_uint32, ci, vp, vp, vp, ctypes.POINTER(RtStats)]
     L.rt_render_aov_follow_rays_fixed_device.argtypes = [vp, ctypes.c_int64, vp, vp, vp, ci, ci, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32,
@@ -604,6 +609,52 @@ class Scene:
                                            out.data_ptr(), rays_per_pixel, key_first, key_stride, max_bounces, seed, 0, fixed, s.cuda_stream)
         return out, st
 
+    # ---- a sample count per pixel (rt_render_counts_fixed)
+    def render_counts(self, camera: np.ndarray, width: int, height: int, sample_stride: int, count, first=None, samples=None,
+                      max_bounces: int = 10, seed: int = 1, flags: int = 0, out=None, stream=None):
+        """The samples first[p] .. first[p] + count[p] - 1 of every pixel p of the FLAG_RNG_PER_SAMPLE frame (width, height,
+        sample_stride, seed) -> (sums, stats): sample k of pixel p is camera ray p * sample_stride + k of that frame.  ``count``
+        and ``first`` (None: all 0) are (width * height,) int32 tensors on one GPU; the (width * height, 3) int64 fixed-point sums
+        (units of 2^-30) are ADDED into ``out`` when one is given, and ``samples`` (a (width * height,) int32 tensor) gets the
+        counts ADDED: the divisor for normalize_counts / post_process_counts.  Calls whose ranges tile [0, sample_stride) add up
+        to exactly the whole frame's sums, in any order.  ``stream``: a torch stream (default: the current one)."""
+        import torch
+        me = "render_counts"
+        for name, v in (("width", width), ("height", height), ("sample_stride", sample_stride)):
+            if not isinstance(v, int) or isinstance(v, bool) or v < 1:
+                raise RtError(f"{me}: {name} must be a positive int, it is {v!r}")
+        if not isinstance(seed, int) or not 0 <= seed < 1 << 64:
+            raise RtError(f"{me}: seed must be an int in 0 .. 2^64 - 1, it is {seed!r}")
+        cam = np.ascontiguousarray(camera, np.float32)
+        if cam.shape != (12,):
+            raise RtError(f"{me}: camera must be the 12 floats of make_camera(), it has shape {cam.shape}")
+        n = width * height
+        if not isinstance(count, torch.Tensor) or not count.is_cuda:
+            raise RtError(f"{me}: count must be a torch tensor on a GPU")
+        device = count.device
+        for name, t in (("count", count), ("first", first), ("samples", samples)):
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != device:
+                raise RtError(f"{me}: {name} must be a torch tensor on the GPU of count")
+            if t.dtype != torch.int32 or tuple(t.shape) != (n,) or not t.is_contiguous():
+                raise RtError(f"{me}: {name} must be a contiguous ({n},) torch.int32 tensor, it is {tuple(t.shape)} {t.dtype}")
+        if out is None:
+            out = torch.zeros((n, 3), dtype=torch.int64, device=device)
+        else:
+            if not isinstance(out, torch.Tensor) or not out.is_cuda or out.device != device:
+                raise RtError(f"{me}: out must be a torch tensor on the GPU of count")
+            if out.dtype != torch.int64 or tuple(out.shape) != (n, 3) or not out.is_contiguous():
+                raise RtError(f"{me}: out must be a contiguous ({n}, 3) torch.int64 tensor, it is {tuple(out.shape)} {out.dtype}")
+        s = torch.cuda.current_stream(device) if stream is None else stream
+        c = ctypes.c_void_p
+        st = RtStats()
+        _check(self.L.rt_render_counts_fixed(self.h, _p(cam), width, height, sample_stride, c(None if first is None else first.data_ptr()),
+                                             c(count.data_ptr()), int(max_bounces), seed, flags, c(out.data_ptr()),
+                                             c(None if samples is None else samples.data_ptr()), c(s.cuda_stream or None), ctypes.byref(st)),
+               "rt_render_counts_fixed", self.L)
+        return out, st.as_dict()
+
     # ---- first-hit feature buffers (rt_render_aov_fixed / rt_render_aov_rays_fixed_device)
     @staticmethod
     def _aov_buffers(what, n_pixels, ids, out, device):
@@ -873,6 +924,91 @@ def post_process(d_ptr: int, num_pixels: int, spp: int, stream: int = 0) -> None
 def post_process_fixed(d_fixed_ptr: int, d_out_ptr: int, num_pixels: int, spp: int, stream: int = 0) -> None:
     _check(lib().rt_post_process_fixed(ctypes.c_void_p(d_fixed_ptr), ctypes.c_void_p(d_out_ptr), num_pixels, spp,
                                        ctypes.c_void_p(stream)), "rt_post_process_fixed")
+
+
+def _counts_tensors(me: str, sums, samples):
+    """The checks of an (n, 3) int64 sums tensor and its (n,) int32 divisor, both on one GPU -> n."""
+    import torch
+    if not isinstance(sums, torch.Tensor) or not sums.is_cuda:
+        raise RtError(f"{me}: sums must be a torch tensor on a GPU")
+    if sums.dtype != torch.int64 or sums.dim() != 2 or sums.shape[1] != 3 or sums.shape[0] < 1 or not sums.is_contiguous():
+        raise RtError(f"{me}: sums must be a contiguous (n_pixels, 3) torch.int64 tensor, it is {tuple(sums.shape)} {sums.dtype}")
+    n = int(sums.shape[0])
+    if not isinstance(samples, torch.Tensor) or not samples.is_cuda or samples.device != sums.device:
+        raise RtError(f"{me}: samples must be a torch tensor on the GPU of the sums")
+    if samples.dtype != torch.int32 or tuple(samples.shape) != (n,) or not samples.is_contiguous():
+        raise RtError(f"{me}: samples must be a contiguous ({n},) torch.int32 tensor, it is {tuple(samples.shape)} {samples.dtype}")
+    return n
+
+
+def normalize_counts(sums, samples, out=None, stream=None):
+    """Sums with a per-pixel divisor -> int64 sums of ONE sample of the mean (rt_normalize_counts_fixed): per channel
+    sign(s) * ((|s| + (n >> 1)) // n) with n = samples[p], 0 where n == 0.  ``out``: a tensor like ``sums`` to write into
+    (``sums`` itself: in place).  The result feeds denoise(out, 1, ...), denoise_variance and the temporal accumulators."""
+    import torch
+    me = "normalize_counts"
+    n = _counts_tensors(me, sums, samples)
+    if out is None:
+        out = torch.empty_like(sums)
+    elif not isinstance(out, torch.Tensor) or not out.is_cuda or out.device != sums.device:
+        raise RtError(f"{me}: out must be a torch tensor on the GPU of the sums")
+    elif out.dtype != torch.int64 or tuple(out.shape) != (n, 3) or not out.is_contiguous():
+        raise RtError(f"{me}: out must be a contiguous ({n}, 3) torch.int64 tensor, it is {tuple(out.shape)} {out.dtype}")
+    s = torch.cuda.current_stream(sums.device) if stream is None else stream
+    with torch.cuda.device(sums.device):
+        _check(lib().rt_normalize_counts_fixed(ctypes.c_void_p(sums.data_ptr()), ctypes.c_void_p(samples.data_ptr()), n,
+                                               ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(s.cuda_stream or None)), "rt_normalize_counts_fixed")
+    return out
+
+
+def post_process_counts(sums, samples, out=None, stream=None):
+    """post_process_fixed with the pixel's own count (rt_post_process_counts_fixed) -> (n_pixels, 3) float32 tensor; 0 where the
+    count is 0."""
+    import torch
+    me = "post_process_counts"
+    n = _counts_tensors(me, sums, samples)
+    if out is None:
+        out = torch.empty((n, 3), dtype=torch.float32, device=sums.device)
+    elif not isinstance(out, torch.Tensor) or not out.is_cuda or out.device != sums.device:
+        raise RtError(f"{me}: out must be a torch tensor on the GPU of the sums")
+    elif out.dtype != torch.float32 or tuple(out.shape) != (n, 3) or not out.is_contiguous():
+        raise RtError(f"{me}: out must be a contiguous ({n}, 3) torch.float32 tensor, it is {tuple(out.shape)} {out.dtype}")
+    s = torch.cuda.current_stream(sums.device) if stream is None else stream
+    with torch.cuda.device(sums.device):
+        _check(lib().rt_post_process_counts_fixed(ctypes.c_void_p(sums.data_ptr()), ctypes.c_void_p(samples.data_ptr()), n,
+                                                  ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(s.cuda_stream or None)),
+               "rt_post_process_counts_fixed")
+    return out
+
+
+def sample_allocate(weight, min_count: int, max_count: int, budget: int, out=None, stream=None):
+    """From a weight map to counts under a budget, in exact integers (rt_sample_allocate) -> (counts, total): ``weight`` is an
+    (n_pixels,) float32 tensor on a GPU; count[p] = min(max_count, min_count + extra * q[p] // T) with q the weight quantised
+    to 2^-20 (0 for NaN, zero and negatives; capped at 4096), T its sum and extra = budget - n_pixels * min_count (an even
+    split where T == 0).  ``total`` = the sum of the counts <= budget: what flooring and the cap leave over is not
+    redistributed."""
+    import torch
+    me = "sample_allocate"
+    if not isinstance(weight, torch.Tensor) or not weight.is_cuda:
+        raise RtError(f"{me}: weight must be a torch tensor on a GPU")
+    if weight.dtype != torch.float32 or weight.dim() != 1 or weight.shape[0] < 1 or not weight.is_contiguous():
+        raise RtError(f"{me}: weight must be a contiguous (n_pixels,) torch.float32 tensor, it is {tuple(weight.shape)} {weight.dtype}")
+    n = int(weight.shape[0])
+    for name, v, top in (("min_count", min_count, 1 << 31), ("max_count", max_count, 1 << 31), ("budget", budget, 1 << 63)):
+        if not isinstance(v, int) or isinstance(v, bool) or not -top <= v < top:  # (ctypes would wrap it silently)
+            raise RtError(f"{me}: {name} must be an int of the C type's range, it is {v!r}")
+    if out is None:
+        out = torch.empty((n,), dtype=torch.int32, device=weight.device)
+    elif not isinstance(out, torch.Tensor) or not out.is_cuda or out.device != weight.device:
+        raise RtError(f"{me}: out must be a torch tensor on the GPU of the weights")
+    elif out.dtype != torch.int32 or tuple(out.shape) != (n,) or not out.is_contiguous():
+        raise RtError(f"{me}: out must be a contiguous ({n},) torch.int32 tensor, it is {tuple(out.shape)} {out.dtype}")
+    s = torch.cuda.current_stream(weight.device) if stream is None else stream
+    total = ctypes.c_int64(0)
+    with torch.cuda.device(weight.device):
+        _check(lib().rt_sample_allocate(ctypes.c_void_p(weight.data_ptr()), n, min_count, max_count, budget, ctypes.c_void_p(out.data_ptr()),
+                                        ctypes.byref(total), ctypes.c_void_p(s.cuda_stream or None)), "rt_sample_allocate")
+    return out, int(total.value)
 
 
 def aov_resolve(sums, spp: int, stream=None):

@@ -4,6 +4,8 @@
 //                              caller's rays with a per-sample stream each, rt_render_rays_keyed_*): see gen_core
 //   RT_PATHS_BG                1 (RT_FRAME_SRC = Camera only): RT_K_PATHS is the build whose gen() passes over background pixels
 //                              (gen_background), a kernel of its own name for the same reason
+//   RT_PATHS_COUNTS            1 (RT_FRAME_SRC = CountsCamera, with RT_PATHS_BG = 1): RT_K_PATHS is the build of a counted frame
+//                              (rt_render_counts_fixed): a drawn id's pixel and sample come from the count map's prefix sum
 //   RT_K_ADVANCE / RT_K_PATHS  the names of the two kernels of that compilation
 //   RT_PATHS_CHUNKS            1: RT_K_PATHS is the build with the chunked deal (rt_slot_chunks.h), a kernel of its own name so
 //                              that the static deal keeps its code, instruction for instruction; only its 4-waves-per-SIMD
@@ -13,6 +15,9 @@
 // No include guard: meant to be included more than once.
 #ifndef RT_CHUNK_RELEASE_WAIT
 #define RT_CHUNK_RELEASE_WAIT 1
+#endif
+#ifndef RT_PATHS_COUNTS
+#define RT_PATHS_COUNTS 0
 #endif
 // the chunked deal's static head in the GEN block of RT_K_PATHS: the skipping build has read it once, as a scalar (tk_head)
 #undef RT_GEN_CHUNK_HEAD
@@ -239,6 +244,16 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
     // (a build of its own -- DRAW_CIDS -- so that the reference-mode kernel carries none of it)
     constexpr bool draw_cids = DRAW_CIDS && SPLIT_GEN;
     int cid_next = 0, cid_end = 0;
+#if RT_PATHS_COUNTS
+    // A counted frame: the pixels of the first and of the last id of the wave's chunk, found once when the chunk is drawn, by
+    // all lanes together.  A lane looks for its id's pixel between them: at most kCidChunk pixels with samples, plus whatever
+    // runs of pixels without samples lie among them (counts_find takes the last pixel of such a run).
+    // cid_win: lane j's copy of the offset of pixel cid_plo + j, read once per chunk -- the window in which a lane finds its id's
+    // pixel by shuffles instead of loads; only the ids whose pixel lies beyond the window's 64 pixels (fewer than 8 samples to
+    // a pixel, or a run without samples inside the chunk) go on to search memory, between the window's last pixel and cid_phi.
+    int cid_plo = 0, cid_phi = 0;
+    unsigned cid_win = 0u;
+#endif
     // A lane works through the slots i, i + G, i + 2G, ... (G = lanes of the grid), each for the whole
     // frame, one after the other: with G dividing the slot count every lane gets the same number of
     // slots, so all lanes -- and all workgroups, which are all resident -- finish together.
@@ -437,6 +452,9 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
             out.ray_d = d;
             bool hand_back = false;
             long long my_cid = -1;
+#if RT_PATHS_COUNTS
+            int my_plo = 0, my_phi = 0;
+#endif
             if (draw_cids) {
                 const unsigned long long m = wave_ballot(phase == PH_GEN);
                 const int need = (int)__popcll(m), rank = (int)prefix_popc(m);
@@ -451,9 +469,33 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
                         static_assert(0x7ffff000u + (unsigned)kCidChunk < 0x7fffffffu, "cid_end must not overflow int");
                         cid_next = (int)min(__builtin_amdgcn_readfirstlane(base), 0x7ffff000u);
                         cid_end = cid_next + kCidChunk;
+#if RT_PATHS_COUNTS
+                        const int ids = __builtin_amdgcn_readfirstlane((int)ap.cam_end);  // (below 2^31 - 13 W: render_shard_impl)
+                        if (cid_next < ids) {  // (a chunk past the frame's end is not looked up: its lanes stop)
+                            const int n_px = __builtin_amdgcn_readfirstlane(cam.n_pixels);
+                            cid_plo = __builtin_amdgcn_readfirstlane(counts_find_wave(cam.offset, 0, n_px - 1, (unsigned)cid_next));
+                            cid_phi = __builtin_amdgcn_readfirstlane(counts_find_wave(cam.offset, cid_plo, n_px - 1, (unsigned)(min(cid_end, ids) - 1)));
+                            cid_win = cam.offset[min(cid_plo + (int)lane_id(), n_px)];  // (offset[n_px]: the total, above every id)
+                        }
+#endif
                     }
                     const int take = min(need - served, cid_end - cid_next);
+#if RT_PATHS_COUNTS
+                    // (every lane of the wave makes the six shuffles, also those that take no id here: their result is dropped.
+                    // The window's offsets do not decrease and its first is at most the chunk's first id, so the last lane whose
+                    // offset is at most c holds c's pixel -- unless that is the window's last lane.)
+                    const int c_here = cid_next + max(rank - served, 0);
+                    int win_at = 0;
+#pragma unroll
+                    for (int s = 32; s > 0; s >>= 1) win_at = __shfl(cid_win, win_at + s) <= (unsigned)c_here ? win_at + s : win_at;
+                    if (phase == PH_GEN && rank >= served && rank < served + take) {
+                        my_cid = c_here;
+                        my_plo = min(cid_plo + win_at, cid_phi);
+                        my_phi = win_at < 63 ? my_plo : cid_phi;
+                    }
+#else
                     if (phase == PH_GEN && rank >= served && rank < served + take) my_cid = cid_next + (rank - served);
+#endif
                     cid_next += take;
                     served += take;
                 }
@@ -604,6 +646,9 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
                 int g_gen = 0, g_stop = 0, g_limit = 0, px = 0, py = 0;
                 uint32_t draw_x = 0, draw_y = 0;
                 bool looking = false, made = false;  // made: the pixel the lane stopped at is not background
+#if RT_PATHS_COUNTS
+                unsigned long long my_key = 0;  // p * stride + k of the lane's drawn id
+#endif
                 if (was_gen) {
                     g_gen = cold[2 * kBlock];
                     g_rs = Rng{(uint32_t)cold[3 * kBlock], (uint32_t)cold[4 * kBlock], (uint32_t)cold[5 * kBlock],
@@ -628,7 +673,12 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
                         t.gen = g_gen + 1;
                         int qx, qy;
                         const unsigned cid32 = draw_cids ? (unsigned)my_cid : (unsigned)g_gen * (unsigned)kW + (unsigned)slot;
+#if RT_PATHS_COUNTS
+                        static_assert(DRAW_CIDS || !SPLIT_GEN, "a counted frame's GEN block serves drawn ids only");
+                        counts_locate(cam, cid32, my_plo, my_phi, f_width, t.pixel, qx, qy, my_key);
+#else
                         gen_pixel(ap, slot, t, nullptr, (long long)cid32, (long long)cid32, qx, qy);
+#endif
                         px = qx - f_dpx;
                         py = qy - f_dpy;
                         if (px < 0) {
@@ -668,7 +718,11 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
                     n_bg_lane += turns - (made ? 1u : 0u);
                     if (draw_cids) {  // (every camera ray starts a stream of its own: none for a background id)
                         if (made) {
+#if RT_PATHS_COUNTS
+                            g_rs = rng_sample_stream(ap.seed_lo, ap.seed_hi, my_key);
+#else
                             g_rs = rng_sample_stream(ap.seed_lo, ap.seed_hi, (unsigned long long)my_cid * (unsigned)ap.key_mul + (unsigned)ap.key_add);
+#endif
                             draw_x = rng_next(g_rs);
                             draw_y = rng_next(g_rs);
                         }

@@ -22,6 +22,11 @@ struct Context {
     int lock_cap = 0;
     int *d_over = nullptr;  // overflow part of the traversal stacks of this context's grids (ensure_overflow)
     int over_levels = 0;
+    // a counted frame's prepass (counts_prepass): the prefix sum of the count map, pixels + 1 words, and the tiles' words; grown
+    // once per image size
+    uint32_t *d_counts_offset = nullptr;
+    unsigned long long *d_counts_words = nullptr;
+    size_t counts_pixels = 0;
     std::mutex busy;  // a context (pools, counters, events) serves one render at a time
     Context() = default;
     Context(const Context &) = delete;
@@ -32,6 +37,8 @@ struct Context {
         for (void *q : allocs) (void)hipFree(q);
         (void)hipFree(d_lock);
         (void)hipFree(d_over);
+        (void)hipFree(d_counts_offset);
+        (void)hipFree(d_counts_words);
         if (h_ctr) (void)hipHostFree(h_ctr);
         for (hipEvent_t e : ev_ring) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : {ev_a, ev_b, ev_c}) if (e) (void)hipEventDestroy(e);
@@ -233,6 +240,14 @@ static PathsKeyedKernel paths_keyed_kernel(bool lds_tables, bool few_blocks) {
     return lds_tables ? k_paths_keyed<true, true, 4, true, false, false> : k_paths_keyed<false, true, 4, true, false, false>;
 }
 
+// Counted frames: k_paths_counts (4-wide tree, the triangle-list definition of a hit, per-sample streams), the two builds the
+// per-sample camera path runs.
+using PathsCountsKernel = decltype(&k_paths_counts<false, true, 4, true, false, false>);
+static PathsCountsKernel paths_counts_kernel(bool lds_tables, bool few_blocks) {
+    if (few_blocks) return lds_tables ? k_paths_counts<true, true, 2, false, false, false> : k_paths_counts<false, true, 2, false, false, false>;
+    return lds_tables ? k_paths_counts<true, true, 4, true, false, false> : k_paths_counts<false, true, 4, true, false, false>;
+}
+
 // Global overflow part of the traversal stacks: `levels` entries for each of kOverStride lanes.  Every OWNER of
 // concurrently running grids has its own buffer -- a render context (one render at a time: Context::busy), or a
 // scene's query state (queries, trace hooks and AOVs of one scene take turns: QueryState::mutex) -- because a lane
@@ -290,6 +305,13 @@ struct RayFrame {
     bool keyed = false;
     KeyedRayTable keyed_table{};
 };
+// A counted frame (rt_render_counts_fixed): the camera's frame in the per-sample mode, `spp` the sample stride, and of it the
+// samples first[p] .. first[p] + count[p] - 1 of every pixel.  render_shard_impl runs the prepass (counts_prepass) once it holds
+// the context, whose scratch the prefix sum lives in; the frame's camera rays are the sum of the counts.
+struct CountsFrame {
+    const int32_t *d_first, *d_count;
+    int32_t *d_samples;
+};
 // What the phases of one frame share: the context, the kernels' arguments, the round pipeline's launch (k_advance +
 // k_trace: RT_PERSISTENT=0 frames and the lockstep final generation) and what the stats are made from.
 struct FrameRun {
@@ -304,6 +326,8 @@ struct FrameRun {
     bool lds_tables = false, persistent = true, finished = false, ran_lockstep = false;
     int cus = 0, stack_cap = 0, top_records_in_lds = 0, slot_chunk = 0, slot_head = 0, lock_enqueued = 0;
     bool ran_bg = false;  // the persistent launch was k_paths_bg / k_paths_chunked_bg (a rectangle smaller than the frame)
+    bool counted = false;  // a counted frame: k_paths_counts on counts_src (its camera is `cam`)
+    CountsCamera counts_src{};
     DScene sc{};
     Camera cam{};
     AdvanceParams ap{};
@@ -390,7 +414,8 @@ static int report_trace_profile(unsigned long long *d_prof) {
 // by rt_launch_plan.h
 int FrameRun::run_persistent() {
     const int paths_cap = lds_stack_cap(scene, kPathsLdsStack);
-    const size_t fixed_lds = (lds_tables ? sizeof(float) * (size_t)((scene->tab_dwords + 3) & ~3) : 0) + sizeof(Camera) + sizeof(AdvanceParams);
+    // (the uniforms hold the source of camera rays: a Camera or a table no larger, or a counted frame's CountsCamera)
+    const size_t fixed_lds = (lds_tables ? sizeof(float) * (size_t)((scene->tab_dwords + 3) & ~3) : 0) + (counted ? sizeof(CountsCamera) : sizeof(Camera)) + sizeof(AdvanceParams);
     const rtplan::PathsLaunch p = rtplan::plan_paths_launch(c.n, cus, scene->wide, scene->n_nodes, paths_cap, !rays, ap.width, ap.spp, fixed_lds);
     top_records_in_lds = p.top_n;
     unsigned long long *paths_prof = nullptr;
@@ -425,6 +450,7 @@ int FrameRun::run_persistent() {
     slot_chunk = chunk;
     if (rays && rays->keyed) launch_paths(paths_keyed_kernel(lds_tables, p.few_blocks), rays->keyed_table, p.top_n);
     else if (rays) launch_paths(paths_rays_kernel(lds_tables, p.few_blocks, mode.verify), rays->table, p.top_n);
+    else if (counted) launch_paths(paths_counts_kernel(lds_tables, p.few_blocks), counts_src, p.top_n);
     else if (chunk > 0) launch_paths(chunked, cam, chunk | (slot_head << rtplan::kChunkHeadShift));
     else launch_paths(paths_kernel(lds_tables, scene->wide, p.few_blocks, per_sample, mode.literal, mode.verify, bg), cam, mode.literal ? 0 : p.top_n);
     HIP_TRY(hipGetLastError());
@@ -592,9 +618,46 @@ int FrameRun::frame_stats(rt_stats *stats) {
     return 0;
 }
 
+// The prepass of a counted frame on `st`, in the context's scratch (the caller holds c.busy): the (first, count) pairs are checked
+// and the offenders counted before anything is written; then the prefix sum of the counts into c.d_counts_offset, the caller's
+// d_samples add, and the sum of the counts into *total (held to the camera-ray range of a frame).
+static int counts_prepass(Context &c, const CountsFrame &cf, int n_pixels, uint32_t stride, hipStream_t st, long long *total) {
+    const int n_tiles = (n_pixels + kCountsTile - 1) / kCountsTile;
+    if (c.counts_pixels < (size_t)n_pixels) {
+        HIP_TRY(hipStreamSynchronize(st));
+        (void)hipFree(c.d_counts_offset);
+        (void)hipFree(c.d_counts_words);
+        c.d_counts_offset = nullptr;
+        c.d_counts_words = nullptr;
+        c.counts_pixels = 0;
+        HIP_TRY(hipMalloc((void **)&c.d_counts_offset, sizeof(uint32_t) * ((size_t)n_pixels + 1)));
+        HIP_TRY(hipMalloc((void **)&c.d_counts_words, sizeof(unsigned long long) * ((size_t)n_tiles + 2)));
+        c.counts_pixels = (size_t)n_pixels;
+    }
+    HIP_TRY(hipMemsetAsync(c.d_counts_words, 0, sizeof(unsigned long long) * 2, st));
+    hipLaunchKernelGGL(k_counts_sums, dim3(n_tiles), dim3(256), 0, st, cf.d_first, cf.d_count, n_pixels, stride, c.d_counts_words);
+    hipLaunchKernelGGL(k_counts_scan, dim3(1), dim3(256), 0, st, c.d_counts_words, n_tiles);
+    HIP_TRY(hipGetLastError());
+    unsigned long long *h = (unsigned long long *)&c.h_ctr[1];  // (pinned; the frame's own use of the ring starts after this)
+    static_assert(sizeof(DCounters) >= 2 * sizeof(unsigned long long), "two words of staging");
+    HIP_TRY(hipMemcpyAsync(h, c.d_counts_words, sizeof(unsigned long long) * 2, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (h[0])
+        return fail("rt_render_shard: " + std::to_string(h[0]) + " pixel(s) with count < 0, first < 0 or first + count > sample_stride (" + std::to_string(stride) + ")");
+    if ((long long)h[1] + 13LL * kW >= (1LL << 31))
+        return fail("rt_render_shard: the counts add up to " + std::to_string(h[1]) + " camera rays, beyond the int32 camera-ray range of one call");
+    *total = (long long)h[1];
+    if (h[1] == 0) return 0;  // (nothing to add to d_samples either)
+    hipLaunchKernelGGL(k_counts_offsets, dim3(n_tiles), dim3(256), 0, st, cf.d_count, n_pixels, (const unsigned long long *)c.d_counts_words, c.d_counts_offset,
+                       cf.d_samples);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 int render_shard_impl(const rt_scene *scene, const rt_camera *camera, int width, int height, int spp,
                       int max_bounces, uint64_t seed, int shard_index, int shard_count, uint32_t flags,
-                      float *d_sum, hipStream_t st, rt_stats *stats, int ctx_lane = 0, const RayFrame *rays = nullptr) {
+                      float *d_sum, hipStream_t st, rt_stats *stats, int ctx_lane = 0, const RayFrame *rays = nullptr,
+                      const CountsFrame *counts = nullptr) {
     if (!scene || (!camera && !rays) || !d_sum) return fail("rt_render_shard: null argument");
     if (width <= 0 || height <= 0 || spp <= 0 || max_bounces < 0) return fail("rt_render_shard: bad dimensions");
     if (max_bounces > (1 << 24)) return fail("rt_render_shard: max_bounces exceeds 16777216");
@@ -616,7 +679,8 @@ int render_shard_impl(const rt_scene *scene, const rt_camera *camera, int width,
         if (spp % shard_count != 0) return fail("rt_render_shard: RT_FLAG_RNG_PER_SAMPLE needs num_samples divisible by shard_count");
         spp /= shard_count;
     }
-    const long long cam_end = rays ? rays->n_rays : (long long)width * height * spp;
+    // (a counted frame's camera rays are the sum of its counts: known, and held to the same range, after the prepass below)
+    long long cam_end = rays ? rays->n_rays : counts ? 0 : (long long)width * height * spp;
     if (cam_end + 13LL * kW >= (1LL << 31))  // the reference's int32 camera_ray ids (render.cuh:370-371,440)
         return fail("rt_render_shard: width*height*spp exceeds the reference's int32 camera-ray range");
     int dev = 0;
@@ -636,10 +700,27 @@ int render_shard_impl(const rt_scene *scene, const rt_camera *camera, int width,
     std::lock_guard<std::mutex> busy_lock(c.busy);  // concurrent callers with the same (device, n) queue up here
     FrameRun f{c, scene, rays, st, d_sum, flags, per_sample, mode};
     f.ref_tree_seconds = ref_tree_seconds;
+    if (counts) {
+        if (int rc = counts_prepass(c, *counts, width * height, (uint32_t)spp, st, &cam_end)) return rc;
+        if (cam_end == 0) {  // nothing to render: no event, nothing written
+            if (stats) {
+                memset(stats, 0, sizeof(*stats));
+                stats->bvh_nodes = scene->n_nodes;
+                stats->bvh_depth = scene->max_depth;
+            }
+            return 0;
+        }
+        f.counted = true;
+        f.counts_src.offset = c.d_counts_offset;
+        f.counts_src.first = counts->d_first;
+        f.counts_src.stride = (uint32_t)spp;
+        f.counts_src.n_pixels = width * height;
+    }
     if (ensure_rng(c, seed, slot_lo, st, &f.rng_seconds)) return 1;
 
     f.sc = scene->dev();
     if (!rays) memcpy(&f.cam, camera, sizeof(Camera));
+    f.counts_src.cam = f.cam;
     {
         DCounters zero{};
         zero.last_live_round = -1;
@@ -679,7 +760,7 @@ int render_shard_impl(const rt_scene *scene, const rt_camera *camera, int width,
     ap.seed_hi = (uint32_t)(seed >> 32);
     ap.batch_mask = 7;  // (round and lockstep start at 0)
     ap.fb_fixed = (flags & kFlagFixedFb) ? 1 : 0;
-    ap.w_over_spp = (kW % spp == 0 && !rays) ? kW / spp : 0;  // (the pixel stepping is the camera frames')
+    ap.w_over_spp = (kW % spp == 0 && !rays && !counts) ? kW / spp : 0;  // (the pixel stepping is the camera frames')
     ap.dpx = ap.w_over_spp % width;
     ap.dpy = (ap.w_over_spp > 0 && width < 32768 && height < 32768) ? ap.w_over_spp / width : -1;
     // The pixels whose camera rays can hit something (rt_background.h): k_paths_bg / k_paths_chunked_bg make no ray outside them.  Per
@@ -1133,3 +1214,33 @@ static int render_motion_impl(const rt_scene *scene, const rt_camera *camera, in
     });
 }
 
+
+// rt_render_counts_fixed: the host-side checks, then the frame through render_shard_impl in the per-sample mode as one more source
+// of camera rays (CountsFrame): the prepass on the device, k_paths_counts.
+static int render_counts_impl(const rt_scene *scene, const rt_camera *camera, int width, int height, int sample_stride, const int32_t *d_first,
+                              const int32_t *d_count, int max_bounces, uint64_t seed, uint32_t flags, int64_t *d_sum_fixed, int32_t *d_samples,
+                              hipStream_t st, rt_stats *stats) {
+    const std::string w("rt_render_counts_fixed");
+    if (!scene) return fail(w + ": null scene");
+    if (!camera || !d_count || !d_sum_fixed) return fail(w + ": null " + (!camera ? "camera" : !d_count ? "d_count" : "d_sum_fixed"));
+    if (flags & RT_FLAG_REFERENCE_WALK) return fail(w + ": RT_FLAG_REFERENCE_WALK is not supported for counted frames");
+    // (RT_FLAG_RNG_PER_SAMPLE and RT_FLAG_WATERTIGHT are what the mode is: accepted, and change nothing)
+    if (flags & ~(uint32_t)(RT_FLAG_RNG_PER_SAMPLE | RT_FLAG_WATERTIGHT | RT_FLAG_TIME_KERNELS))
+        return fail(w + ": flags other than RT_FLAG_RNG_PER_SAMPLE / RT_FLAG_WATERTIGHT / RT_FLAG_TIME_KERNELS");
+    if (width < 1 || height < 1) return fail(w + ": width and height must be at least 1 (" + std::to_string(width) + " x " + std::to_string(height) + ")");
+    if ((long long)width * height > (long long)(0x7fffffff / 3)) return fail(w + ": width*height exceeds 715827882 pixels");
+    if (sample_stride < 1) return fail(w + ": sample_stride = " + std::to_string(sample_stride) + " is outside 1 .. 2147483647");
+    if (max_bounces < 0 || max_bounces > (1 << 24)) return fail(w + ": max_bounces = " + std::to_string(max_bounces) + " is outside 0 .. 16777216");
+    if (!scene->wide) return fail(w + ": counted frames need the 4-wide tree (the scene was created with RT_BVH_WIDE=0)");
+    if (const char *e = knob("RT_PERSISTENT"))
+        if (atoi(e) == 0) return fail(w + ": counted frames run on the persistent kernel only (RT_PERSISTENT=0 is set)");
+    DeviceGuard dev;
+    if (dev.enter(scene->device)) return 1;
+    const CountsFrame counts{d_first, d_count, d_samples};
+    const uint32_t mode = (flags & RT_FLAG_TIME_KERNELS) | kFlagFixedFb | RT_FLAG_RNG_PER_SAMPLE;
+    if (int rc = render_shard_impl(scene, camera, width, height, sample_stride, max_bounces, seed, 0, 1, mode, (float *)d_sum_fixed, st, stats, 0, nullptr, &counts)) {
+        fail(w + ": " + g_last_error);  // (what the frame itself refused, under this entry point's name)
+        return rc;
+    }
+    return 0;
+}

@@ -497,6 +497,59 @@ struct KeyedRayTable {
     uint32_t rem_first;
 };
 static_assert(sizeof(KeyedRayTable) <= sizeof(Camera), "k_paths' dynamic LDS is sized for a Camera in the uniforms");
+// The camera rays of a COUNTED frame (rt_render_counts_fixed): pixel p renders the samples first[p] .. first[p] + count[p] - 1
+// of the RT_FLAG_RNG_PER_SAMPLE frame with `stride` samples per pixel.  Camera ray c of the call, 0 <= c < sum of the counts,
+// belongs to the pixel p with offset[p] <= c < offset[p + 1] (offset: the exclusive prefix sum of the counts, n_pixels + 1
+// words, made by the prepass k_counts_*), is that pixel's sample k = first[p] + c - offset[p], and has the 64-bit key
+// p * stride + k: the stream, the jitter and the ray of camera ray G = key of the whole frame.
+// Larger than a Camera: k_paths_counts' launch sizes the dynamic LDS for it (FrameRun::run_persistent).
+struct CountsCamera {
+    Camera cam;
+    const uint32_t *offset;
+    const int32_t *first;  // null: all 0
+    uint32_t stride;
+    int n_pixels;
+};
+__device__ __forceinline__ void camera_get_ray(const CountsCamera &s, float x, float y, V3 &o, V3 &d) { camera_get_ray(s.cam, x, y, o, d); }
+// the largest p in [lo, hi] with offset[p] <= c, given offset[lo] <= c: the pixel of camera ray c if that pixel is at most hi.
+// Runs of pixels without samples repeat an offset, and the LAST pixel of such a run is the one that holds the ray.
+__device__ __forceinline__ int counts_find(const uint32_t *__restrict__ offset, int lo, int hi, unsigned c) {
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo + 1) >> 1);  // (lo < mid <= hi)
+        const bool below = offset[mid] <= c;
+        lo = below ? mid : lo;
+        hi = below ? hi : mid - 1;
+    }
+    return lo;
+}
+// counts_find for a whole wave that looks for ONE c (lo, hi and c are wave-uniform, every lane of the wave is here): the 64 lanes
+// probe 64 evenly spaced pixels of the range at once -- the offsets do not decrease, so the lanes that find offset <= c are the
+// first ones, and the last of them names the next range -- and 2^21 pixels take 4 rounds of one load where a lane alone makes 21
+// loads one after the other.
+__device__ __forceinline__ int counts_find_wave(const uint32_t *__restrict__ offset, int lo, int hi, unsigned c) {
+    const int lane = (int)lane_id();
+    while (true) {
+        const int step = (hi - lo) / 64 + 1;  // (the 64 probes lo + j * step cover [lo, hi]; step = 1: every pixel of it)
+        const int probe = min(lo + lane * step, hi);  // (lo + 63 * step <= lo + 63 * (hi - lo) / 64 + 63: no overflow, hi < 2^30)
+        const unsigned long long below = wave_ballot(offset[probe] <= c);  // (lane 0: offset[lo] <= c)
+        const int j = (int)__popcll(below) - 1;
+        const int at = min(lo + j * step, hi);
+        if (step == 1) return at;
+        hi = min(at + step - 1, hi);
+        lo = at;
+    }
+}
+// camera ray c of a counted frame, its pixel known to lie in [lo, hi]: the pixel, its coordinates and the ray's key
+__device__ __forceinline__ void counts_locate(const CountsCamera &s, unsigned c, int lo, int hi, int width, int &pixel, int &px, int &py,
+                                              unsigned long long &key) {
+    const uint32_t *offset = s.offset;
+    const int32_t *first = s.first;
+    pixel = counts_find(offset, lo, hi, c);
+    const unsigned k = (first ? (unsigned)first[pixel] : 0u) + (c - offset[pixel]);  // (below stride: the prepass has checked)
+    key = (unsigned long long)(unsigned)pixel * s.stride + k;
+    py = (int)((unsigned)pixel / (unsigned)width);
+    px = pixel - py * width;
+}
 #ifndef RT_RAYS_NONTEMPORAL
 #define RT_RAYS_NONTEMPORAL 1
 #endif
@@ -599,6 +652,28 @@ __device__ __forceinline__ void gen_core(const SRC &cam, const AdvanceParams &ap
         gen_camera_ray(cam, ap, cid, px, py, st, out);
         return;
     }
+    if constexpr (std::is_same<SRC, CountsCamera>::value) {
+        // Counted frames (k_paths_counts' 2-waves-per-SIMD builds, where ids are tied to slots): camera ray `cid` of the call is
+        // found in the prefix sum over the whole image; a background pixel's ray is counted and passed over without a stream
+        // or a ray, as in the per-sample camera path; then the stream of the ray's 64-bit key, the two draws, the pinhole.
+        int px, py;
+        unsigned long long key;
+        while (true) {
+            if (!gen_begin<NEVER_LOCKSTEP>(ap, slot_global, st, cid_given, cid)) return;
+            counts_locate(cam, (unsigned)cid, 0, cam.n_pixels - 1, ap.width, st.pixel, px, py, key);  // (cid < cam_end < 2^31)
+            if (!BG_SKIP || !gen_background(ap, px, py)) break;
+            out.bg_skipped++;
+        }
+        st.rs = rng_sample_stream(ap.seed_lo, ap.seed_hi, key);
+        const float jx = rng_uniform(st.rs);  // x first, then y (Appendix A.7)
+        const float jy = rng_uniform(st.rs);
+        camera_get_ray(cam.cam, (px + jx) / ap.width, (py + jy) / ap.height, out.ray_o, out.ray_d);
+        out.new_ray = true;
+        st.bounces = 0;
+        st.beta = mk(1.f, 1.f, 1.f);
+        out.did_gen = true;
+        return;
+    }
     if (!gen_begin<NEVER_LOCKSTEP>(ap, slot_global, st, cid_given, cid)) return;
     if constexpr (std::is_same<SRC, KeyedRayTable>::value) {
         // Keyed ray-table frames: row `cid` starts the per-sample stream of its key (whatever stream the lane held), gen()'s
@@ -642,6 +717,8 @@ __device__ __forceinline__ void gen_core(const SRC &cam, const AdvanceParams &ap
         st.beta = mk(1.f, 1.f, 1.f);
         out.did_gen = true;
         return;
+    } else if constexpr (std::is_same<SRC, CountsCamera>::value) {
+        // (not reached: the counted frame's branch above has returned)
     } else {
         int px, py;
         gen_pixel(ap, slot_global, st, pxy, cid_given, cid, px, py);
@@ -933,7 +1010,165 @@ constexpr int kProfRec = 6;    // qwords of k_paths' per-wave record (behind the
 #undef RT_K_ADVANCE
 #undef RT_K_PATHS
 #undef RT_PATHS_CHUNKS
+// and the skipping text once more for a counted frame (rt_render_counts_fixed; RT_FRAME_SRC = CountsCamera) as k_paths_counts:
+// its GEN block finds a drawn id's pixel and sample in the prefix sum of the count map (RT_PATHS_COUNTS).  Per-sample streams,
+// so the persistent kernel only, and of it the two per-sample builds (k_advance_counts_unused is never instantiated).
+#define RT_PATHS_CHUNKS 0
+#undef RT_PATHS_COUNTS
+#define RT_PATHS_COUNTS 1
+#define RT_FRAME_SRC CountsCamera
+#define RT_K_ADVANCE k_advance_counts_unused
+#define RT_K_PATHS k_paths_counts
+#include "rt_frame_kernels.inc"
+#undef RT_FRAME_SRC
+#undef RT_K_ADVANCE
+#undef RT_K_PATHS
+#undef RT_PATHS_CHUNKS
+#undef RT_PATHS_COUNTS
 #undef RT_PATHS_BG
+
+// The prepass of a counted frame, three kernels on the caller's stream.  A workgroup serves kCountsTile consecutive pixels, a lane
+// kCountsItems consecutive ones of them.  words[0]: pixels whose (first, count) the call refuses; words[1]: the sum of the counts;
+// words[2 + b]: the sum over tile b, then (k_counts_scan) the sum over the tiles before b.
+// k_counts_sums writes the words only; the host reads words[0 .. 1] and decides; k_counts_offsets then writes the prefix sum the
+// frame kernel searches and makes the caller's d_samples add.
+constexpr int kCountsItems = 4, kCountsTile = kCountsItems * 256;
+__global__ void __launch_bounds__(256)
+k_counts_sums(const int32_t *__restrict__ first, const int32_t *__restrict__ count, int n, uint32_t stride, unsigned long long *__restrict__ words) {
+    __shared__ unsigned long long s_sum[4];
+    __shared__ unsigned s_bad[4];
+    const unsigned base = (blockIdx.x * 256u + threadIdx.x) * (unsigned)kCountsItems;  // (n + kCountsTile < 2^31)
+    unsigned long long sum = 0;
+    unsigned bad = 0;
+    for (unsigned k = 0; k < (unsigned)kCountsItems; k++) {
+        const unsigned p = base + k;
+        if (p < (unsigned)n) {
+            const long long c = count[p], f = first ? first[p] : 0;
+            const bool b = c < 0 || f < 0 || f + c > (long long)stride;  // (64-bit: no int32 overflow)
+            bad += b ? 1u : 0u;
+            sum += b ? 0ull : (unsigned long long)c;
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        sum += __shfl_xor(sum, off);
+        bad += __shfl_xor(bad, off);
+    }
+    if ((threadIdx.x & 63u) == 0u) {
+        s_sum[threadIdx.x >> 6] = sum;
+        s_bad[threadIdx.x >> 6] = bad;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        words[2 + blockIdx.x] = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
+        const unsigned b = s_bad[0] + s_bad[1] + s_bad[2] + s_bad[3];
+        if (b) atomicAdd(&words[0], (unsigned long long)b);
+    }
+}
+// an inclusive scan over the 256 values of a workgroup, one per lane, through `s` (256 words)
+template <class T>
+__device__ __forceinline__ T counts_block_scan(T *s, T v) {
+    s[threadIdx.x] = v;
+    __syncthreads();
+    for (unsigned off = 1; off < 256u; off <<= 1) {
+        const T t = threadIdx.x >= off ? s[threadIdx.x - off] : (T)0;
+        __syncthreads();
+        s[threadIdx.x] += t;
+        __syncthreads();
+    }
+    return s[threadIdx.x];
+}
+// one workgroup: the tiles' sums -> the sums before each tile, and the total
+__global__ void __launch_bounds__(256) k_counts_scan(unsigned long long *__restrict__ words, int n_tiles) {
+    __shared__ unsigned long long s[256];
+    unsigned long long carry = 0;
+    for (int base = 0; base < n_tiles; base += 256) {
+        const int i = base + (int)threadIdx.x;
+        const unsigned long long v = i < n_tiles ? words[2 + i] : 0ull;
+        const unsigned long long incl = counts_block_scan(s, v);
+        const unsigned long long tile_total = s[255];
+        if (i < n_tiles) words[2 + i] = carry + incl - v;
+        carry += tile_total;
+        __syncthreads();  // (s is written again in the next turn)
+    }
+    if (threadIdx.x == 0) words[1] = carry;
+}
+// (every (first, count) has passed and the total is below 2^31: the host has looked)
+__global__ void __launch_bounds__(256)
+k_counts_offsets(const int32_t *__restrict__ count, int n, const unsigned long long *__restrict__ words, uint32_t *__restrict__ offset,
+                 int32_t *__restrict__ samples) {
+    __shared__ unsigned s[256];
+    const unsigned base = (blockIdx.x * 256u + threadIdx.x) * (unsigned)kCountsItems;
+    unsigned c[kCountsItems], mine = 0;
+    for (unsigned k = 0; k < (unsigned)kCountsItems; k++) {
+        c[k] = base + k < (unsigned)n ? (unsigned)count[base + k] : 0u;
+        mine += c[k];
+    }
+    unsigned at = (unsigned)words[2 + blockIdx.x] + (counts_block_scan(s, mine) - mine);
+    for (unsigned k = 0; k < (unsigned)kCountsItems; k++) {
+        const unsigned p = base + k;
+        if (p < (unsigned)n) {
+            offset[p] = at;
+            if (samples && c[k]) samples[p] += (int32_t)c[k];
+        }
+        at += c[k];
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) offset[n] = (unsigned)words[1];
+}
+
+// rt_normalize_counts_fixed: sums with a per-pixel divisor -> sums of ONE sample of the mean, sign(s) * ((|s| + (n >> 1)) / n) in
+// 64-bit integers; n == 0 gives 0.  k_counts_negative counts the pixels with a negative divisor first (nothing is written then).
+__global__ void k_counts_negative(const int32_t *__restrict__ samples, int n, unsigned long long *__restrict__ words) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const unsigned long long m = wave_ballot(i < n && samples[i] < 0);
+    if (m != 0ull && lane_id() == 0) atomicAdd(&words[0], (unsigned long long)__popcll(m));
+}
+__global__ void k_normalize_counts(const long long *__restrict__ sums, const int32_t *__restrict__ samples, int n_values, long long *__restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_values) return;
+    const long long s = sums[i];
+    const unsigned long long n = (unsigned long long)samples[(unsigned)i / 3u];
+    long long r = 0;
+    if (n) {
+        const unsigned long long a = s < 0 ? 0ull - (unsigned long long)s : (unsigned long long)s;
+        const long long q = (long long)((a + (n >> 1)) / n);
+        r = s < 0 ? -q : q;
+    }
+    out[i] = r;
+}
+// rt_post_process_counts_fixed: k_post_process_fixed with the pixel's own count; n == 0 gives 0
+__global__ void k_post_process_counts(const long long *__restrict__ sums, const int32_t *__restrict__ samples, float *__restrict__ out, int n_values) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_values) return;
+    const int n = samples[(unsigned)i / 3u];
+    out[i] = n > 0 ? sqrtf((float)((double)sums[i] * (1.0 / 1073741824.0)) * (1.f / (float)n)) : 0.f;
+}
+
+// rt_sample_allocate.  The quantised weight: 0 unless w > 0 (NaN, zero, negatives), else floor(min(w, 4096) * 2^20), every step
+// exact in fp32 and at most 2^32.  k_allocate_total: words[0] = T, the sum of the quantised weights (64-bit integer adds: any order).
+// k_allocate_counts: count = min(max_count, min_count + (T ? extra * q / T : extra / n)) and words[1] = the sum of the counts.
+__device__ __forceinline__ unsigned long long allocate_weight(float w) {
+    return w > 0.f ? (unsigned long long)floorf(fminf(w, 4096.f) * 1048576.f) : 0ull;
+}
+__device__ __forceinline__ void allocate_wave_add(unsigned long long v, unsigned long long *word) {
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    if (v != 0ull && lane_id() == 0) atomicAdd(word, v);
+}
+__global__ void k_allocate_total(const float *__restrict__ weight, int n, unsigned long long *__restrict__ words) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    allocate_wave_add(i < n ? allocate_weight(weight[i]) : 0ull, &words[0]);
+}
+__global__ void k_allocate_counts(const float *__restrict__ weight, int n, int min_count, int max_count, unsigned long long extra,
+                                  unsigned long long *__restrict__ words, int32_t *__restrict__ count) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const unsigned long long total = words[0];
+    unsigned long long c = 0;
+    if (i < n) {
+        const unsigned long long more = total ? extra * allocate_weight(weight[i]) / total : extra / (unsigned long long)n;  // (extra < 2^31, q <= 2^32)
+        c = min((unsigned long long)max_count, (unsigned long long)min_count + more);
+        count[i] = (int32_t)c;
+    }
+    allocate_wave_add(c, &words[1]);
+}
 
 // post_process_framebuffer (render.cuh:330-338): c = sqrt(c * (1/spp))
 __global__ void k_post_process(float *fb, int n_values, float inv_spp) {
@@ -979,6 +1214,7 @@ __global__ void k_test_draw(DPools p, int n, int draws, uint32_t *__restrict__ s
 #include "rt_host_frame.inc"   // whole frames: the shard fan-out (RT_SPLIT, rt_render_multi), finish_frame, rt_render, rt_render_multi
 #include "rt_host_denoise.inc"  // rt_denoise_fixed, rt_denoise_dual_fixed
 #include "rt_host_temporal.inc"  // rt_temporal_accumulate_fixed, rt_temporal_accumulate_moments_fixed
+#include "rt_host_counts.inc"  // rt_normalize_counts_fixed, rt_post_process_counts_fixed, rt_sample_allocate
 }  // namespace
 
 // ============================================================================ C-ABI
@@ -1154,6 +1390,27 @@ int rt_render_rays_fixed_device(const rt_scene *scene, int64_t n_rays, const flo
     if (flags & kFlagFixedFb) return fail("rt_render_rays_fixed_device: unknown flag 0x200");
     return render_rays_impl(scene, n_rays, d_origin_xyz, d_dir_xyz, d_pixel, rays_per_pixel, n_pixels, max_bounces, seed, flags | kFlagFixedFb,
                             (float *)d_sum_fixed, (hipStream_t)stream, stats);
+}
+
+int rt_render_counts_fixed(const rt_scene *scene, const rt_camera *camera, int width, int height, int sample_stride, const int32_t *d_first,
+                           const int32_t *d_count, int max_bounces, uint64_t seed, uint32_t flags, int64_t *d_sum_fixed, int32_t *d_samples,
+                           void *stream, rt_stats *stats) {
+    if (flags & kFlagFixedFb) return fail("rt_render_counts_fixed: unknown flag 0x200");
+    return render_counts_impl(scene, camera, width, height, sample_stride, d_first, d_count, max_bounces, seed, flags, d_sum_fixed, d_samples,
+                              (hipStream_t)stream, stats);
+}
+
+int rt_normalize_counts_fixed(const int64_t *d_sum_fixed, const int32_t *d_samples, int num_pixels, int64_t *d_out_fixed, void *stream) {
+    return normalize_counts_impl(d_sum_fixed, d_samples, num_pixels, d_out_fixed, (hipStream_t)stream);
+}
+
+int rt_post_process_counts_fixed(const int64_t *d_sum_fixed, const int32_t *d_samples, int num_pixels, float *d_rgb_out, void *stream) {
+    return post_process_counts_impl(d_sum_fixed, d_samples, num_pixels, d_rgb_out, (hipStream_t)stream);
+}
+
+int rt_sample_allocate(const float *d_weight, int num_pixels, int min_count, int max_count, int64_t budget, int32_t *d_count_out,
+                       int64_t *total_out, void *stream) {
+    return sample_allocate_impl(d_weight, num_pixels, min_count, max_count, budget, d_count_out, total_out, (hipStream_t)stream);
 }
 
 int rt_post_process_fixed(const int64_t *d_sum_fixed, float *d_rgb_out, int num_pixels, int num_samples, void *stream) {
