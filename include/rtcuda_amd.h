@@ -84,7 +84,7 @@ typedef struct rt_stats {
                                 seconds_trace is that launch's duration and launches_trace is 1): 1 + the camera rays
                                 per task of the chunked deal of slots to lanes in its low 32 bits, so 1 = the static deal,
                                 and in bits 32 .. 47 the slot sets a lane ran statically before that deal began; bit 48: the launch
-                                was a build that makes no camera ray for background pixels (k_paths_bg / k_paths_chunked_bg);
+                                was a build that makes no camera ray for background pixels (k_paths<PathsBg> / k_paths<PathsChunkedBg>);
                                 reserved[2] = BVH node records that launch staged in LDS (small shards only);
                                 reserved[3] = rt_render_multi: number of device shards behind these totals;
                                 default kernels (no RT_FLAG_WATERTIGHT): reserved[4] = rays re-traced through the reference's

@@ -72,9 +72,9 @@ class RtStats(ctypes.Structure):
     def as_dict(self) -> dict:
         d = {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
         d["lds_top_records"] = int(self.reserved[2])  # BVH records the persistent kernel staged in LDS
-        d["slot_chunk"] = max((int(self.reserved[1]) & 0xffffffff) - 1, 0)  # camera rays per task of k_paths_chunked's deal; 0: the static deal
+        d["slot_chunk"] = max((int(self.reserved[1]) & 0xffffffff) - 1, 0)  # camera rays per task of k_paths<PathsChunked>'s deal; 0: the static deal
         d["slot_head"] = (int(self.reserved[1]) >> 32) & 0xffff  # slot sets a lane ran as in the static deal before that deal began
-        d["background_skip"] = (int(self.reserved[1]) >> 48) & 1  # the launch was k_paths_bg / k_paths_chunked_bg
+        d["background_skip"] = (int(self.reserved[1]) >> 48) & 1  # the launch was k_paths<PathsBg> / k_paths<PathsChunkedBg>
         # default kernels (no RT_FLAG_WATERTIGHT): closest hits re-traced through the reference's own tree, accepted hits the
         # reference's box test loses, exact ties at the final distance
         d["literal_retraces"], d["reference_lost_hits"], d["exact_ties"] = (int(self.reserved[k]) for k in (4, 5, 6))

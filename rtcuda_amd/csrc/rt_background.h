@@ -1,5 +1,5 @@
 // rt_background.h -- the pixel rectangle outside which no camera ray of a pinhole frame can hit the scene (host only; shared
-// by render_shard_impl, which hands it to k_paths / k_paths_chunked in AdvanceParams, and by rt_host_check.cpp, which exports
+// by render_shard_impl, which hands it to k_paths / k_paths<PathsChunked> in AdvanceParams, and by rt_host_check.cpp, which exports
 // it for the tests as rt_background_rect).
 //
 // Guarantee.  For every pixel (px, py) outside [x0, x1) x [y0, y1) and every jitter (jx, jy) in [0, 1)^2, the ray gen_core

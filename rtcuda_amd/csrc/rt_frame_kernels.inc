@@ -1,30 +1,20 @@
 // The kernels of a frame: k_advance (one round of init() + mat() + gen() for all slots, state in the pools) and k_paths (the
-// persistent kernel).  Included by rtcuda_amd.hip once per source of camera rays, with
-//   RT_FRAME_SRC               Camera (gen()'s pinhole), RayTable (the caller's rays, rt_render_rays_*) or KeyedRayTable (the
-//                              caller's rays with a per-sample stream each, rt_render_rays_keyed_*): see gen_core
-//   RT_PATHS_BG                1 (RT_FRAME_SRC = Camera only): RT_K_PATHS is the build whose gen() passes over background pixels
-//                              (gen_background), a kernel of its own name for the same reason
-//   RT_PATHS_COUNTS            1 (RT_FRAME_SRC = CountsCamera, with RT_PATHS_BG = 1): RT_K_PATHS is the build of a counted frame
-//                              (rt_render_counts_fixed): a drawn id's pixel and sample come from the count map's prefix sum
-//   RT_K_ADVANCE / RT_K_PATHS  the names of the two kernels of that compilation
-//   RT_PATHS_CHUNKS            1: RT_K_PATHS is the build with the chunked deal (rt_slot_chunks.h), a kernel of its own name so
-//                              that the static deal keeps its code, instruction for instruction; only its 4-waves-per-SIMD
-//                              reference-mode instances are ever launched
+// persistent kernel).  Two templates, included by rtcuda_amd.hip once:
+//   k_advance<SRC, LDS_TABLES>   SRC: the source of camera rays -- Camera (gen()'s pinhole) or RayTable (the caller's rays,
+//                                rt_render_rays_*): see gen_core
+//   k_paths<BUILD, ...>          BUILD: one of the tags defined in front of the include (PathsCamera, PathsRays, PathsKeyed,
+//                                PathsChunked, PathsBg, PathsChunkedBg, PathsCounts), which carries
+//     BUILD::Src                 the source type: Camera, RayTable, KeyedRayTable (a per-sample stream per row) or CountsCamera
+//     BUILD::kChunks             the chunked deal (rt_slot_chunks.h) is compiled in; only 4-waves-per-SIMD reference-mode instances
+//                                of such a build are ever launched
+//     BUILD::kBg                 gen() passes over background pixels (gen_background)
+//     BUILD::kCounts             (with kBg) a counted frame (rt_render_counts_fixed): a drawn id's pixel and sample come from the
+//                                count map's prefix sum
+// What a build does not have is discarded by `if constexpr` when it is instantiated: it carries no instruction of it.
 //   RT_CHUNK_RELEASE_WAIT      (experiment define) 0: the chunked deal's release leaves the wait for the state's stores to the
 //                              compiler's memory model, which has none at workgroup scope
-// No include guard: meant to be included more than once.
 #ifndef RT_CHUNK_RELEASE_WAIT
 #define RT_CHUNK_RELEASE_WAIT 1
-#endif
-#ifndef RT_PATHS_COUNTS
-#define RT_PATHS_COUNTS 0
-#endif
-// the chunked deal's static head in the GEN block of RT_K_PATHS: the skipping build has read it once, as a scalar (tk_head)
-#undef RT_GEN_CHUNK_HEAD
-#if RT_PATHS_BG
-#define RT_GEN_CHUNK_HEAD (int)tk_head
-#else
-#define RT_GEN_CHUNK_HEAD (int)s_task[5]
 #endif
 
 // k_advance: one slot per thread, state in the pools.
@@ -40,9 +30,9 @@
 // slot order (profiles/r04_experiments.md) -- the kernel streams 36 arrays of slot state and is bound by that traffic; the
 // sort costs a dependent load phase and two barriers in front of it, while the divergence it removes was not what the
 // kernel waited for.
-template <bool LDS_TABLES>
+template <class SRC, bool LDS_TABLES>
 __global__ void __launch_bounds__(kBlock)
-RT_K_ADVANCE(DScene sc, DPools p, RT_FRAME_SRC cam, AdvanceParams ap, float *__restrict__ fb, DCounters *__restrict__ ctr,
+k_advance(DScene sc, DPools p, SRC cam, AdvanceParams ap, float *__restrict__ fb, DCounters *__restrict__ ctr,
              DWaveRow *__restrict__ rows, unsigned int *__restrict__ lock_shades) {
     // Lockstep rounds (final generation): the reference's host loop ends at the first iteration in which nothing shades
     // (render.cuh:436).  The rounds are all enqueued at once; lock_shades[j] counts the mat() events of round j, and a round
@@ -157,12 +147,13 @@ RT_K_ADVANCE(DScene sc, DPools p, RT_FRAME_SRC cam, AdvanceParams ap, float *__r
     }
 }
 
-template <bool LDS_TABLES, bool WIDE, int MIN_WAVES, bool DRAW_CIDS = false, bool LITERAL = false, bool VERIFY = false>
+template <class BUILD, bool LDS_TABLES, bool WIDE, int MIN_WAVES, bool DRAW_CIDS = false, bool LITERAL = false, bool VERIFY = false>
 __global__ void __launch_bounds__(kBlock, MIN_WAVES)
-RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, float *__restrict__ fb, DWaveRow *__restrict__ rows,
-           int stack_cap, int *overflow, int adv_batch, int debug_no_deposit, unsigned long long *prof, int top_n,
-           int prio_period, int rot_wave, int rot_set, int gen_batch, int tri_follow, unsigned int *__restrict__ next_cid,
-           unsigned long long *__restrict__ vstat) {
+k_paths(DScene sc, DPools p, typename BUILD::Src cam_arg, AdvanceParams ap_arg, float *__restrict__ fb, DWaveRow *__restrict__ rows,
+        int stack_cap, int *overflow, int adv_batch, int debug_no_deposit, unsigned long long *prof, int top_n,
+        int prio_period, int rot_wave, int rot_set, int gen_batch, int tri_follow, unsigned int *__restrict__ next_cid,
+        unsigned long long *__restrict__ vstat) {
+    using SRC = typename BUILD::Src;
     // The GEN block exists where the chip is short of issue slots (4 waves per SIMD): there it takes a third of the
     // lanes out of the long ADV block (+3 %, and the ADV block no longer spills).  On small shards (2 waves per
     // SIMD) a slot-round is a latency chain and one more block in it costs 5 %: gen() stays inside ADV there.
@@ -185,7 +176,7 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
     // The chunked deal (rt_slot_chunks.h) of the 4-waves-per-SIMD reference-mode builds: G > 0 camera rays per task, 0 = the
     // static deal.  These builds keep no records of the tree in LDS, so G travels in `top_n`, and above G's bits the static
     // head: the slot sets a lane runs as in the static deal before it draws its first task.
-    constexpr bool CHUNKS = RT_PATHS_CHUNKS && SPLIT_GEN && !DRAW_CIDS;
+    constexpr bool CHUNKS = BUILD::kChunks && SPLIT_GEN && !DRAW_CIDS;
     // [0]: the workgroup's next task; [1]: G; [2 .. 4]: rtchunks::multiple_of(G); [5]: the static head; [6] (the skipping build):
     // rtchunks::next_multiple_mul(G).  The GEN block reads G, the words and the head from here: as scalars kept across the main
     // loop they pushed other scalars out into VGPR lanes (53 more v_readlane in the default build, and the static deal 2.5 %
@@ -205,9 +196,7 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
             s_task[3] = m.shift;
             s_task[4] = m.limit;
             s_task[5] = chunk_head0;
-#if RT_PATHS_BG
-            s_task[6] = rtchunks::next_multiple_mul(chunk_g0 ? chunk_g0 : 1u);  // [6]: for the limit of a run over background pixels
-#endif
+            if constexpr (BUILD::kBg) s_task[6] = rtchunks::next_multiple_mul(chunk_g0 ? chunk_g0 : 1u);  // [6]: for the limit of a run over background pixels
         }
     }
     const bool chunk_start = CHUNKS && chunk_g0 && chunk_head0 == 0u;  // no static head: the lane starts without a slot
@@ -221,7 +210,7 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
     // they occupy ~30 SGPRs for the whole loop and push other scalars out into VGPR lanes (v_readlane /
     // v_writelane are VALU work).  Staged in LDS they are read where they are used.
     struct Uniforms {
-        RT_FRAME_SRC cam;
+        SRC cam;
         AdvanceParams ap;
     };
     static_assert(sizeof(Uniforms) % 4 == 0, "dword copy");
@@ -234,7 +223,7 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
         for (int k = threadIdx.x; k < (int)(sizeof(Uniforms) / 4); k += kBlock) ((int *)s_uni)[k] = srcw[k];
     }
     __syncthreads();
-    const RT_FRAME_SRC &cam = s_uni->cam;
+    const SRC &cam = s_uni->cam;
     const AdvanceParams &ap = s_uni->ap;
     // what the scheduling loop itself needs stays scalar
     const int ap_n = ap_arg.n, ap_max_bounces = ap_arg.max_bounces, ap_fb_fixed = ap_arg.fb_fixed;
@@ -244,8 +233,7 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
     // (a build of its own -- DRAW_CIDS -- so that the reference-mode kernel carries none of it)
     constexpr bool draw_cids = DRAW_CIDS && SPLIT_GEN;
     int cid_next = 0, cid_end = 0;
-#if RT_PATHS_COUNTS
-    // A counted frame: the pixels of the first and of the last id of the wave's chunk, found once when the chunk is drawn, by
+    // A counted frame (BUILD::kCounts): the pixels of the first and of the last id of the wave's chunk, found once when the chunk is drawn, by
     // all lanes together.  A lane looks for its id's pixel between them: at most kCidChunk pixels with samples, plus whatever
     // runs of pixels without samples lie among them (counts_find takes the last pixel of such a run).
     // cid_win: lane j's copy of the offset of pixel cid_plo + j, read once per chunk -- the window in which a lane finds its id's
@@ -253,7 +241,6 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
     // a pixel, or a run without samples inside the chunk) go on to search memory, between the window's last pixel and cid_phi.
     int cid_plo = 0, cid_phi = 0;
     unsigned cid_win = 0u;
-#endif
     // A lane works through the slots i, i + G, i + 2G, ... (G = lanes of the grid), each for the whole
     // frame, one after the other: with G dividing the slot count every lane gets the same number of
     // slots, so all lanes -- and all workgroups, which are all resident -- finish together.
@@ -315,13 +302,28 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
         cold[10 * kBlock] = __float_as_int(beta.y);
         cold[11 * kBlock] = __float_as_int(beta.z);
     };
+    auto cold_rng = [&]() {
+        return Rng{(uint32_t)cold[3 * kBlock], (uint32_t)cold[4 * kBlock], (uint32_t)cold[5 * kBlock],
+                   (uint32_t)cold[6 * kBlock], (uint32_t)cold[7 * kBlock], (uint32_t)cold[8 * kBlock]};
+    };
     auto cold_load = [&]() {
         bounces = cold[0 * kBlock];
         pixel = cold[1 * kBlock];
         gen = cold[2 * kBlock];
-        rs = Rng{(uint32_t)cold[3 * kBlock], (uint32_t)cold[4 * kBlock], (uint32_t)cold[5 * kBlock],
-                 (uint32_t)cold[6 * kBlock], (uint32_t)cold[7 * kBlock], (uint32_t)cold[8 * kBlock]};
+        rs = cold_rng();
         beta = mk(__int_as_float(cold[9 * kBlock]), __int_as_float(cold[10 * kBlock]), __int_as_float(cold[11 * kBlock]));
+    };
+    // the GEN block's view of the column: it reads the generation counter and the RNG, and writes back what gen() leaves in any
+    // case -- bounces (0, or the kDone / kParked sentinel), gen, the RNG
+    auto cold_save_gen = [&](int b, int g, const Rng &r) {
+        cold[0 * kBlock] = b;
+        cold[2 * kBlock] = g;
+        cold[3 * kBlock] = (int)r.d;
+        cold[4 * kBlock] = (int)r.v0;
+        cold[5 * kBlock] = (int)r.v1;
+        cold[6 * kBlock] = (int)r.v2;
+        cold[7 * kBlock] = (int)r.v3;
+        cold[8 * kBlock] = (int)r.v4;
     };
     int phase = PH_IDLE;
     int tri = -1;
@@ -452,9 +454,7 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
             out.ray_d = d;
             bool hand_back = false;
             long long my_cid = -1;
-#if RT_PATHS_COUNTS
-            int my_plo = 0, my_phi = 0;
-#endif
+            int my_plo = 0, my_phi = 0;  // (a counted frame: where the lane's drawn id's pixel lies)
             if (draw_cids) {
                 const unsigned long long m = wave_ballot(phase == PH_GEN);
                 const int need = (int)__popcll(m), rank = (int)prefix_popc(m);
@@ -469,42 +469,42 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
                         static_assert(0x7ffff000u + (unsigned)kCidChunk < 0x7fffffffu, "cid_end must not overflow int");
                         cid_next = (int)min(__builtin_amdgcn_readfirstlane(base), 0x7ffff000u);
                         cid_end = cid_next + kCidChunk;
-#if RT_PATHS_COUNTS
-                        const int ids = __builtin_amdgcn_readfirstlane((int)ap.cam_end);  // (below 2^31 - 13 W: render_shard_impl)
-                        if (cid_next < ids) {  // (a chunk past the frame's end is not looked up: its lanes stop)
-                            const int n_px = __builtin_amdgcn_readfirstlane(cam.n_pixels);
-                            cid_plo = __builtin_amdgcn_readfirstlane(counts_find_wave(cam.offset, 0, n_px - 1, (unsigned)cid_next));
-                            cid_phi = __builtin_amdgcn_readfirstlane(counts_find_wave(cam.offset, cid_plo, n_px - 1, (unsigned)(min(cid_end, ids) - 1)));
-                            cid_win = cam.offset[min(cid_plo + (int)lane_id(), n_px)];  // (offset[n_px]: the total, above every id)
+                        if constexpr (BUILD::kCounts) {
+                            const int ids = __builtin_amdgcn_readfirstlane((int)ap.cam_end);  // (below 2^31 - 13 W: render_shard_impl)
+                            if (cid_next < ids) {  // (a chunk past the frame's end is not looked up: its lanes stop)
+                                const int n_px = __builtin_amdgcn_readfirstlane(cam.n_pixels);
+                                cid_plo = __builtin_amdgcn_readfirstlane(counts_find_wave(cam.offset, 0, n_px - 1, (unsigned)cid_next));
+                                cid_phi = __builtin_amdgcn_readfirstlane(counts_find_wave(cam.offset, cid_plo, n_px - 1, (unsigned)(min(cid_end, ids) - 1)));
+                                cid_win = cam.offset[min(cid_plo + (int)lane_id(), n_px)];  // (offset[n_px]: the total, above every id)
+                            }
                         }
-#endif
                     }
                     const int take = min(need - served, cid_end - cid_next);
-#if RT_PATHS_COUNTS
-                    // (every lane of the wave makes the six shuffles, also those that take no id here: their result is dropped.
-                    // The window's offsets do not decrease and its first is at most the chunk's first id, so the last lane whose
-                    // offset is at most c holds c's pixel -- unless that is the window's last lane.)
-                    const int c_here = cid_next + max(rank - served, 0);
-                    int win_at = 0;
+                    if constexpr (BUILD::kCounts) {
+                        // (every lane of the wave makes the six shuffles, also those that take no id here: their result is dropped.
+                        // The window's offsets do not decrease and its first is at most the chunk's first id, so the last lane whose
+                        // offset is at most c holds c's pixel -- unless that is the window's last lane.)
+                        const int c_here = cid_next + max(rank - served, 0);
+                        int win_at = 0;
 #pragma unroll
-                    for (int s = 32; s > 0; s >>= 1) win_at = __shfl(cid_win, win_at + s) <= (unsigned)c_here ? win_at + s : win_at;
-                    if (phase == PH_GEN && rank >= served && rank < served + take) {
-                        my_cid = c_here;
-                        my_plo = min(cid_plo + win_at, cid_phi);
-                        my_phi = win_at < 63 ? my_plo : cid_phi;
+                        for (int s = 32; s > 0; s >>= 1) win_at = __shfl(cid_win, win_at + s) <= (unsigned)c_here ? win_at + s : win_at;
+                        if (phase == PH_GEN && rank >= served && rank < served + take) {
+                            my_cid = c_here;
+                            my_plo = min(cid_plo + win_at, cid_phi);
+                            my_phi = win_at < 63 ? my_plo : cid_phi;
+                        }
+                    } else {
+                        if (phase == PH_GEN && rank >= served && rank < served + take) my_cid = cid_next + (rank - served);
                     }
-#else
-                    if (phase == PH_GEN && rank >= served && rank < served + take) my_cid = cid_next + (rank - served);
-#endif
                     cid_next += take;
                     served += take;
                 }
             }
             const unsigned chunk_g = CHUNKS ? __builtin_amdgcn_readfirstlane(s_task[1]) : 0u;
-#if RT_PATHS_BG
-            // the deal's other words, out of the LDS once per block and as scalars: [2 .. 3] and [4 .. 7] in one read each
+            // the skipping build: the deal's other words, out of the LDS once per block and as scalars: [2 .. 3] and [4 .. 7] in one
+            // read each
             unsigned tk_inv = 1u, tk_shift = 0u, tk_limit = 0u, tk_head = 0u, tk_mul = 0u;
-            if (CHUNKS) {
+            if constexpr (BUILD::kBg && CHUNKS) {
                 const uint2 lo = *(const uint2 *)&s_task[2];
                 const uint4 hi = *(const uint4 *)&s_task[4];
                 tk_inv = __builtin_amdgcn_readfirstlane(lo.x);
@@ -513,20 +513,16 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
                 tk_head = __builtin_amdgcn_readfirstlane(hi.y);
                 tk_mul = __builtin_amdgcn_readfirstlane(hi.z);
             }
-#endif
+            // the chunked deal's static head where the block needs it again: the skipping build has read it once, as a scalar
+            auto gen_chunk_head = [&]() { return BUILD::kBg ? (int)tk_head : (int)s_task[5]; };
             // The camera ray that ended: its sum goes to its pixel AFTER the hand-over (whose waits for the state's stores and
             // loads would otherwise also sit through the float atomics' acknowledgements), so the pixel is read before the
             // hand-over puts another slot's state into the lane's column.  A lane that comes without a slot has an empty sum.
             const bool chunk_was_gen = CHUNKS && phase == PH_GEN;
             const int chunk_acc_pixel = CHUNKS ? cold[1 * kBlock] : 0;
             if (CHUNKS && chunk_g) {
-#if RT_PATHS_BG
-                const rtchunks::Multiple chunk_m{tk_inv, tk_shift, tk_limit};
-                const unsigned chunk_head = tk_head;
-#else
-                const rtchunks::Multiple chunk_m{s_task[2], s_task[3], s_task[4]};
-                const unsigned chunk_head = __builtin_amdgcn_readfirstlane(s_task[5]);
-#endif
+                const rtchunks::Multiple chunk_m = BUILD::kBg ? rtchunks::Multiple{tk_inv, tk_shift, tk_limit} : rtchunks::Multiple{s_task[2], s_task[3], s_task[4]};
+                const unsigned chunk_head = BUILD::kBg ? tk_head : __builtin_amdgcn_readfirstlane(s_task[5]);
                 // A lane past its static head: without a slot it takes one; with its slot at a chunk's end it banks it (or keeps
                 // it, if another lane has left a claim) -- rt_slot_chunks.h.  Behind a wave vote: once per G camera rays of a lane.
                 // (a lane inside its static head, slot_set < head, has a slot until the head is done and is at no chunk's end)
@@ -612,8 +608,7 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
                 // (also for a lane that banked its slot and found the tasks out: it is idle from here on)
                 if (chunk_was_gen) acc_flush(acc, fb, ap_fb_fixed, chunk_acc_pixel);
             }
-#if RT_PATHS_BG
-            {
+            if constexpr (BUILD::kBg) {
                 // The pinhole's gen(), as a wave-level loop that passes over background pixels (gen_background): a lane whose
                 // next camera ray cannot hit anything counts it, makes its two jitter draws and takes its slot's next generation
                 // in the same visit -- no ray, no scheduling round, no root node step, no second visit.  The block waits for
@@ -646,13 +641,10 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
                 int g_gen = 0, g_stop = 0, g_limit = 0, px = 0, py = 0;
                 uint32_t draw_x = 0, draw_y = 0;
                 bool looking = false, made = false;  // made: the pixel the lane stopped at is not background
-#if RT_PATHS_COUNTS
-                unsigned long long my_key = 0;  // p * stride + k of the lane's drawn id
-#endif
+                unsigned long long my_key = 0;  // (a counted frame) p * stride + k of the lane's drawn id
                 if (was_gen) {
                     g_gen = cold[2 * kBlock];
-                    g_rs = Rng{(uint32_t)cold[3 * kBlock], (uint32_t)cold[4 * kBlock], (uint32_t)cold[5 * kBlock],
-                               (uint32_t)cold[6 * kBlock], (uint32_t)cold[7 * kBlock], (uint32_t)cold[8 * kBlock]};
+                    g_rs = cold_rng();
                     const int pxy = cold[12 * kBlock];
                     if (!CHUNKS) acc_flush(acc, fb, ap_fb_fixed, cold[1 * kBlock]);  // the camera ray that ended: its sum -> its pixel
                     // the generation at which gen()'s end tests stop the slot: its camera rays run out (gen W + slot >= cam_end)
@@ -673,12 +665,12 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
                         t.gen = g_gen + 1;
                         int qx, qy;
                         const unsigned cid32 = draw_cids ? (unsigned)my_cid : (unsigned)g_gen * (unsigned)kW + (unsigned)slot;
-#if RT_PATHS_COUNTS
-                        static_assert(DRAW_CIDS || !SPLIT_GEN, "a counted frame's GEN block serves drawn ids only");
-                        counts_locate(cam, cid32, my_plo, my_phi, f_width, t.pixel, qx, qy, my_key);
-#else
-                        gen_pixel(ap, slot, t, nullptr, (long long)cid32, (long long)cid32, qx, qy);
-#endif
+                        if constexpr (BUILD::kCounts) {
+                            static_assert(DRAW_CIDS || !SPLIT_GEN, "a counted frame's GEN block serves drawn ids only");
+                            counts_locate(cam, cid32, my_plo, my_phi, f_width, t.pixel, qx, qy, my_key);
+                        } else {
+                            gen_pixel(ap, slot, t, nullptr, (long long)cid32, (long long)cid32, qx, qy);
+                        }
                         px = qx - f_dpx;
                         py = qy - f_dpy;
                         if (px < 0) {
@@ -718,11 +710,8 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
                     n_bg_lane += turns - (made ? 1u : 0u);
                     if (draw_cids) {  // (every camera ray starts a stream of its own: none for a background id)
                         if (made) {
-#if RT_PATHS_COUNTS
-                            g_rs = rng_sample_stream(ap.seed_lo, ap.seed_hi, my_key);
-#else
-                            g_rs = rng_sample_stream(ap.seed_lo, ap.seed_hi, (unsigned long long)my_cid * (unsigned)ap.key_mul + (unsigned)ap.key_add);
-#endif
+                            if constexpr (BUILD::kCounts) g_rs = rng_sample_stream(ap.seed_lo, ap.seed_hi, my_key);
+                            else g_rs = rng_sample_stream(ap.seed_lo, ap.seed_hi, (unsigned long long)my_cid * (unsigned)ap.key_mul + (unsigned)ap.key_add);
                             draw_x = rng_next(g_rs);
                             draw_y = rng_next(g_rs);
                         }
@@ -739,22 +728,15 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
                     out.did_gen = true;
                 }
                 if (was_gen) {
-                    // the slot state gen() leaves: bounces (0, or the kDone / kParked sentinel), gen, the RNG, the stepped pixel
-                    // coordinates; a new path also has its pixel and beta = 1
+                    // the slot state gen() leaves (cold_save_gen), and the stepped pixel coordinates; a new path also has its pixel and
+                    // beta = 1
                     int b = 0;
                     if (!made && g_gen >= g_stop) {  // gen()'s end tests, in their order
                         const long long cid = my_cid >= 0 ? my_cid : (long long)g_gen * kW + (f_slot_lo + i);
                         b = cid >= ap.cam_end ? kDone : kParked;
                         hand_back = true;  // (otherwise, without a ray: the lane keeps PH_GEN)
                     }
-                    cold[0 * kBlock] = b;
-                    cold[2 * kBlock] = g_gen;
-                    cold[3 * kBlock] = (int)g_rs.d;
-                    cold[4 * kBlock] = (int)g_rs.v0;
-                    cold[5 * kBlock] = (int)g_rs.v1;
-                    cold[6 * kBlock] = (int)g_rs.v2;
-                    cold[7 * kBlock] = (int)g_rs.v3;
-                    cold[8 * kBlock] = (int)g_rs.v4;
+                    cold_save_gen(b, g_gen, g_rs);
                     cold[12 * kBlock] = px | (py << 16);
                     if (made) {
                         cold[1 * kBlock] = py * f_width + px;
@@ -763,29 +745,18 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
                         cold[11 * kBlock] = __float_as_int(1.f);
                     }
                 }
-            }
-#else
-            if (phase == PH_GEN) {
+            } else if (phase == PH_GEN) {
                 SlotState st;
                 st.gen = cold[2 * kBlock];
-                st.rs = Rng{(uint32_t)cold[3 * kBlock], (uint32_t)cold[4 * kBlock], (uint32_t)cold[5 * kBlock],
-                            (uint32_t)cold[6 * kBlock], (uint32_t)cold[7 * kBlock], (uint32_t)cold[8 * kBlock]};
+                st.rs = cold_rng();
                 st.bounces = 0;
                 st.pixel = 0;
                 st.beta = mk(0, 0, 0);
                 int pxy = cold[12 * kBlock];
                 if (!CHUNKS) acc_flush(acc, fb, ap_fb_fixed, cold[1 * kBlock]);  // the camera ray that ended: its sum -> its pixel
                 gen_core<true>(cam, ap, ap.slot_lo + i, st, out, &pxy, my_cid);
-                // the slot state gen() leaves: bounces (0, or the kDone / kParked sentinel), gen, the RNG; a new path also
-                // has its pixel and beta = 1
-                cold[0 * kBlock] = st.bounces;
-                cold[2 * kBlock] = st.gen;
-                cold[3 * kBlock] = (int)st.rs.d;
-                cold[4 * kBlock] = (int)st.rs.v0;
-                cold[5 * kBlock] = (int)st.rs.v1;
-                cold[6 * kBlock] = (int)st.rs.v2;
-                cold[7 * kBlock] = (int)st.rs.v3;
-                cold[8 * kBlock] = (int)st.rs.v4;
+                // the slot state gen() leaves (cold_save_gen); a new path also has its pixel and beta = 1
+                cold_save_gen(st.bounces, st.gen, st.rs);
                 if (out.new_ray) {
                     cold[1 * kBlock] = st.pixel;
                     cold[9 * kBlock] = __float_as_int(st.beta.x);
@@ -796,7 +767,6 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
                     hand_back = true;  // out of camera rays, or parked for the lockstep final generation
                 }
             }
-#endif
             const bool nr = out.new_ray;
             o = out.ray_o;
             d = out.ray_d;
@@ -810,14 +780,14 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
                 if (hand_back) {
                     if (draw_cids) {
                         phase = PH_IDLE;  // (the frame's counter has run out: nothing is tied to this lane's slot)
-                    } else if (CHUNKS && chunk_g && slot_set + 1 >= RT_GEN_CHUNK_HEAD) {
+                    } else if (CHUNKS && chunk_g && slot_set + 1 >= gen_chunk_head()) {
                         // a dealt slot, or the last one of the static head, is finished: its final state goes to the pools, the
                         // lane draws a task next
                         cold_load();
                         store_slot(i);
                         i = ap_n;
                         tri = -1;
-                        slot_set = RT_GEN_CHUNK_HEAD;
+                        slot_set = gen_chunk_head();
                     } else {  // (the static deal, or the static head of the chunked one: the lane's own next slot)
                         next_slot(PH_GEN);
                     }
@@ -884,7 +854,7 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
                 st.gen = gen;
                 st.rs = rs;
                 st.beta = beta;
-                advance_core<SPLIT_GEN, true, true, RT_PATHS_BG != 0>(sc, tab, cam, ap, ap.slot_lo + i, st, out, fb, acc);
+                advance_core<SPLIT_GEN, true, true, BUILD::kBg>(sc, tab, cam, ap, ap.slot_lo + i, st, out, fb, acc);
                 RT_MARK("adv.tail");
                 bounces = st.bounces;
                 pixel = st.pixel;
@@ -934,7 +904,7 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
             // between a build with and without spills when the kernel sat at 128 VGPRs)
             inv = inv_dir(d);
             if (!SPLIT_GEN) n_gen += wave_count((out.did_gen));
-            if (!SPLIT_GEN && RT_PATHS_BG) {
+            if (!SPLIT_GEN && BUILD::kBg) {
                 // the background camera rays gen() passed over inside advance_core: camera rays like the others
                 int bg = out.bg_skipped;
                 if (wave_ballot(bg != 0)) {
@@ -1199,14 +1169,12 @@ RT_K_PATHS(DScene sc, DPools p, RT_FRAME_SRC cam_arg, AdvanceParams ap_arg, floa
           rec[4] = pf_idle;
           rec[5] = pf_idle_max; }
 #endif
-#if RT_PATHS_BG
-    if (SPLIT_GEN) {
+    if constexpr (BUILD::kBg && SPLIT_GEN) {
         unsigned long long bg = n_bg_lane;
         for (int off = 32; off > 0; off >>= 1) bg += __shfl_xor(bg, off);
         n_gen += bg;
         n_traced += bg;
     }
-#endif
     unsigned long long v[C_COUNT] = {n_gen, n_shade, n_traced, n_shadow, n_emit, n_deposit, n_rr, 0ull};
     row_add(rows, v);
 }

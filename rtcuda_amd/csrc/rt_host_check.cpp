@@ -969,7 +969,7 @@ int rt_slot_chunk_static_slot(int set, int lane_in_grid, int lanes_in_grid, int 
 uint32_t rt_slot_chunk_levels(uint32_t rays, uint32_t G) { return rtchunks::levels(rays, G); }
 uint32_t rt_slot_chunk_task_count(uint32_t sets, uint32_t rays, uint32_t G) { return rtchunks::task_count(sets, rays, G); }
 int rt_slot_chunk_ends(uint32_t gen, uint32_t G, int fresh) { return rtchunks::chunk_ends(gen, rtchunks::multiple_of(G), fresh != 0); }
-// the limit of a run over background pixels in k_paths_bg's GEN block (tests/test_chunk_limit_host.py)
+// the limit of a run over background pixels in k_paths<PathsBg>'s GEN block (tests/test_chunk_limit_host.py)
 uint32_t rt_slot_chunk_next_multiple(uint32_t gen, uint32_t G) { return rtchunks::next_multiple(gen, G, rtchunks::next_multiple_mul(G)); }
 uint32_t rt_slot_chunk_run_limit(uint32_t gen, uint32_t g_stop, int dealt, int can_loop, uint32_t G) {
     return rtchunks::run_limit(gen, g_stop, dealt != 0, can_loop != 0, G, rtchunks::next_multiple_mul(G));
@@ -1032,7 +1032,7 @@ int rt_plan_slot_head(int n, int cus, int *sets_out) {
     return rtplan::slot_head_for(p, sets);
 }
 int rt_plan_slot_chunk_if_resident(int chunk, int workgroups_per_cu) { return rtplan::slot_chunk_if_resident(chunk, workgroups_per_cu); }
-// the dealt entry (head + set, lane) of a task, as k_paths_chunked maps it: the slot, the level and the entry's index
+// the dealt entry (head + set, lane) of a task, as k_paths<PathsChunked> maps it: the slot, the level and the entry's index
 void rt_slot_chunk_head_tasks(int block, int sets, int head, int lanes_in_grid, int rot_wave, int rot_set, uint32_t t0, int count, int32_t *slots, int32_t *levels, int32_t *idx) {
     for (int k = 0; k < count; k++) {
         const rtchunks::Entry e = rtchunks::task_entry(t0 + (uint32_t)k, (unsigned)(sets - head));

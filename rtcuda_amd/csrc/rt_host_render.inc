@@ -157,13 +157,18 @@ static int lds_stack_cap(const rt_scene *scene, int limit) {
     return cap;
 }
 
-// Kernel selection: every build of one kernel template has the same signature, so the flags pick a function pointer and
-// the caller launches (and sizes the grid with) that pointer.
-using AdvanceKernel = decltype(&k_advance<false>);
+// Kernel selection: the builds of a kernel template that share a source of camera rays have the same signature, so the flags pick a
+// function pointer and the caller launches (and sizes the grid with) that pointer.
+template <class SRC>
+using AdvanceKernel = decltype(&k_advance<SRC, false>);
 using TraceKernel = decltype(&k_trace<false>);
-using PathsKernel = decltype(&k_paths<false, false, 4, false, false, false>);
+template <class SRC>
+using PathsKernel = void (*)(DScene, DPools, SRC, AdvanceParams, float *, DWaveRow *, int, int *, int, int, unsigned long long *, int, int, int, int, int, int,
+                             unsigned int *, unsigned long long *);
 
-static AdvanceKernel advance_kernel(bool lds_tables) { return lds_tables ? k_advance<true> : k_advance<false>; }
+// (Camera and RayTable: the sources whose frames can run on the round pipeline)
+template <class SRC>
+static AdvanceKernel<SRC> advance_kernel(bool lds_tables) { return lds_tables ? k_advance<SRC, true> : k_advance<SRC, false>; }
 
 // k_trace: with RT_FLAG_REFERENCE_WALK the build that walks the reference's tree (the node format does not matter
 // then); `verify`: the default build -- the product's walk with the reference's decisions (ref_visible); neither:
@@ -174,78 +179,51 @@ static TraceKernel trace_kernel(bool literal, bool verify, bool wide) {
     return wide ? k_trace<true> : k_trace<false>;
 }
 
-// k_paths: MIN_WAVES = 4 waves per SIMD (at most 128 VGPRs) when the grid fills the chip, 2 (up to 256 VGPRs) when the
-// shard is so small that only 2 workgroups per CU exist anyway (8-GPU runs).  RT_FLAG_REFERENCE_WALK: the build whose node
-// block is the reference's own walk (full pool: the 4-wave build although it spills 53 VGPRs -- measured 1 082 ms for C2's
-// frame against 1 412 ms for the spill-free 2-wave build at half the occupancy).  Per-sample streams on the full pool: the
-// build in which the waves draw their camera rays from the frame's counter.
-// `bg`: the builds that pass over background pixels (k_paths_bg / k_paths_chunked_bg: rt_background.h), for a frame whose rectangle
-// is smaller than the frame; every other frame runs k_paths / k_paths_chunked, which carry nothing of it.
-#define RT_PATHS_KERNELS_OF(NAME, K_PATHS)                                                                                          \
-    template <bool LDS_TABLES, bool WIDE>                                                                                             \
-    static PathsKernel NAME(bool few_blocks, bool per_sample, bool literal, bool verify) {                                            \
-        if (literal) return few_blocks ? K_PATHS<LDS_TABLES, false, 2, false, true, false> : K_PATHS<LDS_TABLES, false, 4, false, true, false>; \
-        if (per_sample && !few_blocks) return K_PATHS<LDS_TABLES, WIDE, 4, true, false, false>;                                       \
-        if (few_blocks) return verify ? K_PATHS<LDS_TABLES, WIDE, 2, false, false, true> : K_PATHS<LDS_TABLES, WIDE, 2, false, false, false>; \
-        return verify ? K_PATHS<LDS_TABLES, WIDE, 4, false, false, true> : K_PATHS<LDS_TABLES, WIDE, 4, false, false, false>;         \
+// k_paths<BUILD, ...>: the instances of a build tag (rtcuda_amd.hip) that a frame can select, and which of them.
+// MIN_WAVES = 4 waves per SIMD (at most 128 VGPRs) when the grid fills the chip, 2 (up to 256 VGPRs) when the shard is so small
+// that only 2 workgroups per CU exist anyway (8-GPU runs).  RT_FLAG_REFERENCE_WALK: the build whose node block is the reference's
+// own walk (full pool: the 4-wave build although it spills 53 VGPRs -- measured 1 082 ms for C2's frame against 1 412 ms for the
+// spill-free 2-wave build at half the occupancy).  Per-sample streams on the full pool: the build in which the waves draw their
+// camera rays (rows, ids) from the frame's counter; on few blocks they are tied to slots and gen() stays inside ADV.
+//   PathsCamera, PathsBg          all of the above, on either node format
+//   PathsChunked, PathsChunkedBg  the 4-waves-per-SIMD reference-mode instances only (the caller asks for nothing else)
+//   PathsRays                     4-wide tree only (a 2-wide scene runs such a frame on the round pipeline); no reference walk
+//   PathsKeyed, PathsCounts       4-wide tree, the triangle-list definition of a hit, per-sample streams: one instance per pool size
+struct PathsPick {
+    bool few_blocks, per_sample, literal, verify;
+};
+template <class BUILD, bool LDS_TABLES, bool WIDE>
+static PathsKernel<typename BUILD::Src> paths_kernel_of(const PathsPick &f) {
+    constexpr bool kCamera = std::is_same<typename BUILD::Src, Camera>::value;  // (the tags that have a reference-walk build)
+    constexpr bool kStreams = std::is_same<BUILD, PathsKeyed>::value || std::is_same<BUILD, PathsCounts>::value;
+    if constexpr (kStreams) {
+        if (f.few_blocks) return k_paths<BUILD, LDS_TABLES, WIDE, 2, false, false, false>;
+        return k_paths<BUILD, LDS_TABLES, WIDE, 4, true, false, false>;
+    } else {
+        if constexpr (kCamera) {
+            if (f.literal) {
+                if constexpr (!BUILD::kChunks) {
+                    if (f.few_blocks) return k_paths<BUILD, LDS_TABLES, false, 2, false, true, false>;
+                }
+                return k_paths<BUILD, LDS_TABLES, false, 4, false, true, false>;
+            }
+        }
+        if constexpr (kCamera && !BUILD::kChunks) {
+            if (f.per_sample && !f.few_blocks) return k_paths<BUILD, LDS_TABLES, WIDE, 4, true, false, false>;
+        }
+        if constexpr (!BUILD::kChunks) {
+            if (f.few_blocks) return f.verify ? k_paths<BUILD, LDS_TABLES, WIDE, 2, false, false, true> : k_paths<BUILD, LDS_TABLES, WIDE, 2, false, false, false>;
+        }
+        return f.verify ? k_paths<BUILD, LDS_TABLES, WIDE, 4, false, false, true> : k_paths<BUILD, LDS_TABLES, WIDE, 4, false, false, false>;
     }
-RT_PATHS_KERNELS_OF(paths_kernel_of, k_paths)
-RT_PATHS_KERNELS_OF(paths_bg_kernel_of, k_paths_bg)
-#undef RT_PATHS_KERNELS_OF
-// the same 4-waves-per-SIMD reference-mode builds with the chunked deal compiled in (k_paths_chunked: rt_slot_chunks.h)
-#define RT_PATHS_CHUNKED_KERNELS_OF(NAME, K_PATHS)                                                                                  \
-    template <bool LDS_TABLES, bool WIDE>                                                                                             \
-    static PathsKernel NAME(bool literal, bool verify) {                                                                              \
-        if (literal) return K_PATHS<LDS_TABLES, false, 4, false, true, false>;                                                        \
-        return verify ? K_PATHS<LDS_TABLES, WIDE, 4, false, false, true> : K_PATHS<LDS_TABLES, WIDE, 4, false, false, false>;         \
+}
+// (tables, keyed tables and counted frames walk 4-wide nodes only: their 2-wide instances do not exist)
+template <class BUILD>
+static PathsKernel<typename BUILD::Src> paths_kernel(bool lds_tables, bool wide, const PathsPick &f) {
+    if constexpr (std::is_same<typename BUILD::Src, Camera>::value) {
+        if (!wide) return lds_tables ? paths_kernel_of<BUILD, true, false>(f) : paths_kernel_of<BUILD, false, false>(f);
     }
-RT_PATHS_CHUNKED_KERNELS_OF(paths_chunked_kernel_of, k_paths_chunked)
-RT_PATHS_CHUNKED_KERNELS_OF(paths_chunked_bg_kernel_of, k_paths_chunked_bg)
-#undef RT_PATHS_CHUNKED_KERNELS_OF
-static PathsKernel paths_chunked_kernel(bool lds_tables, bool wide, bool literal, bool verify, bool bg) {
-    if (bg) {
-        if (lds_tables) return (wide ? paths_chunked_bg_kernel_of<true, true> : paths_chunked_bg_kernel_of<true, false>)(literal, verify);
-        return (wide ? paths_chunked_bg_kernel_of<false, true> : paths_chunked_bg_kernel_of<false, false>)(literal, verify);
-    }
-    if (lds_tables) return (wide ? paths_chunked_kernel_of<true, true> : paths_chunked_kernel_of<true, false>)(literal, verify);
-    return (wide ? paths_chunked_kernel_of<false, true> : paths_chunked_kernel_of<false, false>)(literal, verify);
-}
-static PathsKernel paths_kernel(bool lds_tables, bool wide, bool few_blocks, bool per_sample, bool literal, bool verify, bool bg) {
-    if (bg) {
-        if (lds_tables) return (wide ? paths_bg_kernel_of<true, true> : paths_bg_kernel_of<true, false>)(few_blocks, per_sample, literal, verify);
-        return (wide ? paths_bg_kernel_of<false, true> : paths_bg_kernel_of<false, false>)(few_blocks, per_sample, literal, verify);
-    }
-    if (lds_tables) return (wide ? paths_kernel_of<true, true> : paths_kernel_of<true, false>)(few_blocks, per_sample, literal, verify);
-    return (wide ? paths_kernel_of<false, true> : paths_kernel_of<false, false>)(few_blocks, per_sample, literal, verify);
-}
-
-// Ray-table frames: k_advance_rays / k_paths_rays (4-wide tree only; a 2-wide scene runs such a frame on the round pipeline).
-using AdvanceRaysKernel = decltype(&k_advance_rays<false>);
-using PathsRaysKernel = decltype(&k_paths_rays<false, true, 4, false, false, false>);
-static AdvanceRaysKernel advance_rays_kernel(bool lds_tables) { return lds_tables ? k_advance_rays<true> : k_advance_rays<false>; }
-template <bool LDS_TABLES>
-static PathsRaysKernel paths_rays_kernel_of(bool few_blocks, bool verify) {
-    if (few_blocks) return verify ? k_paths_rays<LDS_TABLES, true, 2, false, false, true> : k_paths_rays<LDS_TABLES, true, 2, false, false, false>;
-    return verify ? k_paths_rays<LDS_TABLES, true, 4, false, false, true> : k_paths_rays<LDS_TABLES, true, 4, false, false, false>;
-}
-static PathsRaysKernel paths_rays_kernel(bool lds_tables, bool few_blocks, bool verify) {
-    return (lds_tables ? paths_rays_kernel_of<true> : paths_rays_kernel_of<false>)(few_blocks, verify);
-}
-
-// Keyed ray-table frames: k_paths_keyed (4-wide tree, the triangle-list definition of a hit, per-sample streams).  Full pool:
-// the build in which the waves draw their rows from the frame's counter; few blocks: rows tied to slots, gen() inside ADV.
-using PathsKeyedKernel = decltype(&k_paths_keyed<false, true, 4, true, false, false>);
-static PathsKeyedKernel paths_keyed_kernel(bool lds_tables, bool few_blocks) {
-    if (few_blocks) return lds_tables ? k_paths_keyed<true, true, 2, false, false, false> : k_paths_keyed<false, true, 2, false, false, false>;
-    return lds_tables ? k_paths_keyed<true, true, 4, true, false, false> : k_paths_keyed<false, true, 4, true, false, false>;
-}
-
-// Counted frames: k_paths_counts (4-wide tree, the triangle-list definition of a hit, per-sample streams), the two builds the
-// per-sample camera path runs.
-using PathsCountsKernel = decltype(&k_paths_counts<false, true, 4, true, false, false>);
-static PathsCountsKernel paths_counts_kernel(bool lds_tables, bool few_blocks) {
-    if (few_blocks) return lds_tables ? k_paths_counts<true, true, 2, false, false, false> : k_paths_counts<false, true, 2, false, false, false>;
-    return lds_tables ? k_paths_counts<true, true, 4, true, false, false> : k_paths_counts<false, true, 4, true, false, false>;
+    return lds_tables ? paths_kernel_of<BUILD, true, true>(f) : paths_kernel_of<BUILD, false, true>(f);
 }
 
 // Global overflow part of the traversal stacks: `levels` entries for each of kOverStride lanes.  Every OWNER of
@@ -298,7 +276,7 @@ int ensure_rng(Context &c, uint64_t seed, int slot_lo, hipStream_t st, double *s
 // validated the table on the device; `camera` is not looked at): camera ray c is row c of the table, the frame is
 // rays->n_rays camera rays over width * height = n_pixels x 1 pixels, and `spp` is the rays_per_pixel of the c / spp rule.
 // Everything else is one body: render_shard_impl checks and sets up a FrameRun, whose phases run and read the frame back.
-// `keyed` (rt_render_rays_keyed_*; the caller sets RT_FLAG_RNG_PER_SAMPLE): `keyed_table` instead of `table`, k_paths_keyed.
+// `keyed` (rt_render_rays_keyed_*; the caller sets RT_FLAG_RNG_PER_SAMPLE): `keyed_table` instead of `table`, k_paths<PathsKeyed>.
 struct RayFrame {
     RayTable table;
     long long n_rays;
@@ -325,8 +303,8 @@ struct FrameRun {
     HitMode mode;
     bool lds_tables = false, persistent = true, finished = false, ran_lockstep = false;
     int cus = 0, stack_cap = 0, top_records_in_lds = 0, slot_chunk = 0, slot_head = 0, lock_enqueued = 0;
-    bool ran_bg = false;  // the persistent launch was k_paths_bg / k_paths_chunked_bg (a rectangle smaller than the frame)
-    bool counted = false;  // a counted frame: k_paths_counts on counts_src (its camera is `cam`)
+    bool ran_bg = false;  // the persistent launch was k_paths<PathsBg> / k_paths<PathsChunkedBg> (a rectangle smaller than the frame)
+    bool counted = false;  // a counted frame: k_paths<PathsCounts> on counts_src (its camera is `cam`)
     CountsCamera counts_src{};
     DScene sc{};
     Camera cam{};
@@ -345,8 +323,8 @@ struct FrameRun {
     }
     void launch_advance() {
         const dim3 grid(grid_for(ap.n)), block(kBlock);
-        if (rays) hipLaunchKernelGGL(advance_rays_kernel(lds_tables), grid, block, 0, st, sc, c.pools, rays->table, ap, d_sum, c.d_ctr, c.d_rows, c.d_lock);
-        else hipLaunchKernelGGL(advance_kernel(lds_tables), grid, block, 0, st, sc, c.pools, cam, ap, d_sum, c.d_ctr, c.d_rows, c.d_lock);
+        if (rays) hipLaunchKernelGGL(advance_kernel<RayTable>(lds_tables), grid, block, 0, st, sc, c.pools, rays->table, ap, d_sum, c.d_ctr, c.d_rows, c.d_lock);
+        else hipLaunchKernelGGL(advance_kernel<Camera>(lds_tables), grid, block, 0, st, sc, c.pools, cam, ap, d_sum, c.d_ctr, c.d_rows, c.d_lock);
     }
     void launch_trace() { hipLaunchKernelGGL(trace, grid_trace, dim3(kBlock), lds_bytes, st, sc, c.pools, tpp, stack_cap, c.d_over); }
     int run_persistent(), run_rounds(), run_lockstep(), frame_stats(rt_stats *stats);  // the phases, in this order
@@ -410,7 +388,7 @@ static int report_trace_profile(unsigned long long *d_prof) {
 }
 #endif
 
-// ---- asynchronous part of the frame: ONE persistent launch (k_paths, or a table's k_paths_rays / k_paths_keyed), sized
+// ---- asynchronous part of the frame: ONE persistent launch (k_paths, or a table's k_paths<PathsRays> / k_paths<PathsKeyed>), sized
 // by rt_launch_plan.h
 int FrameRun::run_persistent() {
     const int paths_cap = lds_stack_cap(scene, kPathsLdsStack);
@@ -431,14 +409,15 @@ int FrameRun::run_persistent() {
     };
     HIP_TRY(hipEventRecord(c.ev_a, st));
     // (the reference-walk build is passed top_n = 0, while top_n * 64 bytes of LDS stay reserved and reported in reserved[2])
-    // (a chunk > 0 launches k_paths_chunked, 4-waves-per-SIMD reference-mode builds that keep no records in LDS: their `top_n`
+    // (a chunk > 0 launches k_paths<PathsChunked>, 4-waves-per-SIMD reference-mode builds that keep no records in LDS: their `top_n`
     // carries the chunk; a frame of one generation runs no chain in k_paths -- every slot parks at once -- and keeps the static
     // deal, and so do ray tables)
     int chunk = (rays || p.few_blocks || per_sample || ap.last_gen < 1 || ap.n != c.n) ? 0 : rtplan::slot_chunk_for(p, ap.last_gen);
     // (a rectangle smaller than the frame: the builds that pass over background pixels)
     const bool bg = !rays && (long long)ap.bg_w * ap.bg_h < (long long)ap.width * ap.height;
     ran_bg = bg;
-    const PathsKernel chunked = paths_chunked_kernel(lds_tables, scene->wide, mode.literal, mode.verify, bg);
+    const PathsPick pick{p.few_blocks, per_sample, mode.literal, mode.verify};
+    const PathsKernel<Camera> chunked = bg ? paths_kernel<PathsChunkedBg>(lds_tables, scene->wide, pick) : paths_kernel<PathsChunked>(lds_tables, scene->wide, pick);
     if (chunk > 0) {  // (its semaphores are 2 KB of static LDS: beside large tables in LDS they would cost a resident workgroup)
         int per_cu = 0;
         HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, chunked, kBlock, p.lds_bytes));
@@ -448,11 +427,12 @@ int FrameRun::run_persistent() {
     slot_head = chunk > 0 ? rtplan::slot_head_for(p, ap.n / (p.blocks * kBlock)) : 0;
     static_assert(rtplan::kDealtSetsMax == (int)rtchunks::kDealtSetsMax, "the plan deals what the semaphores hold");
     slot_chunk = chunk;
-    if (rays && rays->keyed) launch_paths(paths_keyed_kernel(lds_tables, p.few_blocks), rays->keyed_table, p.top_n);
-    else if (rays) launch_paths(paths_rays_kernel(lds_tables, p.few_blocks, mode.verify), rays->table, p.top_n);
-    else if (counted) launch_paths(paths_counts_kernel(lds_tables, p.few_blocks), counts_src, p.top_n);
+    if (rays && rays->keyed) launch_paths(paths_kernel<PathsKeyed>(lds_tables, true, pick), rays->keyed_table, p.top_n);
+    else if (rays) launch_paths(paths_kernel<PathsRays>(lds_tables, true, pick), rays->table, p.top_n);
+    else if (counted) launch_paths(paths_kernel<PathsCounts>(lds_tables, true, pick), counts_src, p.top_n);
     else if (chunk > 0) launch_paths(chunked, cam, chunk | (slot_head << rtplan::kChunkHeadShift));
-    else launch_paths(paths_kernel(lds_tables, scene->wide, p.few_blocks, per_sample, mode.literal, mode.verify, bg), cam, mode.literal ? 0 : p.top_n);
+    else if (bg) launch_paths(paths_kernel<PathsBg>(lds_tables, scene->wide, pick), cam, mode.literal ? 0 : p.top_n);
+    else launch_paths(paths_kernel<PathsCamera>(lds_tables, scene->wide, pick), cam, mode.literal ? 0 : p.top_n);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(c.ev_b, st));
     HIP_TRY(hipEventSynchronize(c.ev_b));
@@ -763,7 +743,7 @@ int render_shard_impl(const rt_scene *scene, const rt_camera *camera, int width,
     ap.w_over_spp = (kW % spp == 0 && !rays && !counts) ? kW / spp : 0;  // (the pixel stepping is the camera frames')
     ap.dpx = ap.w_over_spp % width;
     ap.dpy = (ap.w_over_spp > 0 && width < 32768 && height < 32768) ? ap.w_over_spp / width : -1;
-    // The pixels whose camera rays can hit something (rt_background.h): k_paths_bg / k_paths_chunked_bg make no ray outside them.  Per
+    // The pixels whose camera rays can hit something (rt_background.h): k_paths<PathsBg> / k_paths<PathsChunkedBg> make no ray outside them.  Per
     // call, from the bounds of the records as they are now (after a refit, a rebuild or an edit: the new ones) and the radius they
     // are padded for.  Camera frames of 4-wide scenes; the whole frame otherwise, and with RT_BG_SKIP=0 (an experiment knob).
     ap.bg_x0 = ap.bg_y0 = 0;
@@ -811,7 +791,7 @@ int render_shard_impl(const rt_scene *scene, const rt_camera *camera, int width,
 #endif
     // ONE persistent launch, or -- RT_PERSISTENT=0 -- the round-per-launch pipeline that the lockstep final generation also uses
     if (const char *e = knob("RT_PERSISTENT")) f.persistent = atoi(e) != 0;
-    if (rays && !scene->wide) f.persistent = false;  // (k_paths_rays walks 4-wide nodes; the round pipeline walks either format)
+    if (rays && !scene->wide) f.persistent = false;  // (k_paths<PathsRays> walks 4-wide nodes; the round pipeline walks either format)
     if (per_sample && !f.persistent) return fail("rt_render_shard: RT_FLAG_RNG_PER_SAMPLE runs on the persistent kernel only");
     if (f.persistent ? f.run_persistent() : f.run_rounds()) return 1;
     if (f.run_lockstep()) return 1;
@@ -988,7 +968,7 @@ static int render_rays_impl(const rt_scene *scene, int64_t n_rays, const float *
 
 // rt_render_rays_keyed_device / rt_render_rays_keyed_fixed_device: render_rays_impl's checks and validation, the checks of
 // the keys, then the frame through render_shard_impl in the per-sample mode (full pool, no parking, no lockstep final
-// generation) with k_paths_keyed: row c's stream is rng_sample_stream(seed, key_first + c * key_stride).
+// generation) with k_paths<PathsKeyed>: row c's stream is rng_sample_stream(seed, key_first + c * key_stride).
 static int render_rays_keyed_impl(const rt_scene *scene, int64_t n_rays, const float *d_o, const float *d_d, const int32_t *d_pixel,
                                   int rays_per_pixel, int n_pixels, int max_bounces, uint64_t seed, uint64_t key_first,
                                   uint32_t key_stride, uint32_t flags, float *d_sum, hipStream_t st, rt_stats *stats) {
@@ -1216,7 +1196,7 @@ static int render_motion_impl(const rt_scene *scene, const rt_camera *camera, in
 
 
 // rt_render_counts_fixed: the host-side checks, then the frame through render_shard_impl in the per-sample mode as one more source
-// of camera rays (CountsFrame): the prepass on the device, k_paths_counts.
+// of camera rays (CountsFrame): the prepass on the device, k_paths<PathsCounts>.
 static int render_counts_impl(const rt_scene *scene, const rt_camera *camera, int width, int height, int sample_stride, const int32_t *d_first,
                               const int32_t *d_count, int max_bounces, uint64_t seed, uint32_t flags, int64_t *d_sum_fixed, int32_t *d_samples,
                               hipStream_t st, rt_stats *stats) {

@@ -1,4 +1,4 @@
-// rt_launch_plan.h -- the launch geometry of the persistent frame kernels (k_paths / k_paths_rays / k_paths_keyed) as a pure
+// rt_launch_plan.h -- the launch geometry of the persistent frame kernels (k_paths / k_paths<PathsRays> / k_paths<PathsKeyed>) as a pure
 // function of plain numbers and the experiment knobs (rt_bvh.h): no HIP state is touched, so what the measured speed of a
 // frame rests on -- every number in the comments is a measurement -- is tested on a CPU (rt_host_check.cpp exports it).
 #pragma once
@@ -32,7 +32,7 @@ constexpr int kSlotChunkAuto = -1, kChunksPerSlot = 8, kChunkChainLo = 384, kChu
 // A lane's totals differ from its neighbours' only at the end, and a hand-over balances something only while a lane has at
 // least two dealt slots: the last kDealtSetsDefault sets are dealt, the sets before them run as in the static deal (half the
 // hand-overs of a full pool's frame; the 2-shard frame, two sets, is dealt whole).  The workgroup's semaphores (2 KB of static
-// LDS in k_paths_chunked, rtchunks::kSemWords) hold kDealtSetsMax dealt sets; with them a workgroup must still be one of
+// LDS in k_paths<PathsChunked>, rtchunks::kSemWords) hold kDealtSetsMax dealt sets; with them a workgroup must still be one of
 // kChunkWorkgroupsPerCu on its CU, or the frame keeps the static deal (slot_chunk_if_resident).
 constexpr int kSlotHeadAuto = -1, kDealtSetsDefault = 2, kDealtSetsMax = 4, kChunkWorkgroupsPerCu = 4;
 // G (at most 2^20) and the head reach the kernel in one int: the head above G's kChunkHeadShift bits, so at most kChunkSetsMax sets
@@ -117,7 +117,7 @@ inline int slot_head_for(const PathsLaunch &p, int sets) {
     const int head = p.slot_head == kSlotHeadAuto ? sets - kDealtSetsDefault : p.slot_head;
     return std::max(std::max(0, sets - kDealtSetsMax), std::min(head, sets - 1));
 }
-// k_paths_chunked's static LDS must leave the workgroups as resident as the plan assumes (`workgroups_per_cu`: the device's
+// k_paths<PathsChunked>'s static LDS must leave the workgroups as resident as the plan assumes (`workgroups_per_cu`: the device's
 // answer for that kernel at p.lds_bytes of dynamic LDS); scenes whose tables in LDS leave no room keep the static deal.
 inline int slot_chunk_if_resident(int chunk, int workgroups_per_cu) { return workgroups_per_cu >= kChunkWorkgroupsPerCu ? chunk : 0; }
 // G for a frame whose slots run `chain` camera rays each inside k_paths (= the index of the final generation)

@@ -1,4 +1,4 @@
-// rt_slot_chunks.h -- the chunked deal of a workgroup's slots to its lanes (k_paths_chunked, reference mode, 4 waves per SIMD):
+// rt_slot_chunks.h -- the chunked deal of a workgroup's slots to its lanes (k_paths<PathsChunked>, reference mode, 4 waves per SIMD):
 // the pure decisions, shared by the kernel and by host programs (rt_host_check.cpp exports the mapping;
 // tests/cpp/slot_chunks_check.cpp and slot_chunks_head_check.cpp play the protocol with std::atomic).
 //
@@ -119,7 +119,7 @@ RT_CHUNKS_FN unsigned next_multiple_mul(unsigned G) { return (0x80000000u + G - 
 RT_CHUNKS_FN unsigned next_multiple(unsigned gen, unsigned G, unsigned mul) {
     return ((unsigned)(((unsigned long long)(2u * gen + 1u) * mul) >> 32) + 1u) * G;
 }
-// Where a lane's run over background pixels ends at the latest (the GEN block of k_paths_bg), fixed before the run: the run
+// Where a lane's run over background pixels ends at the latest (the GEN block of k_paths<PathsBg>), fixed before the run: the run
 // goes on while gen < run_limit.  g_stop: the generation at which the slot's chain ends; a dealt lane also stops at the next
 // chunk's end (the generation the per-turn test chunk_ends(gen, m, false) would stop it at: gen reaches a multiple of G exactly
 // when it reaches the next one); a lane that cannot step its pixel takes one turn.

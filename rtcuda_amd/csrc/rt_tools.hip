@@ -628,7 +628,7 @@ int rt_split_probe(const rt_scene *scene, const rt_camera *camera, int width, in
     const int stack_cap = lds_stack_cap(scene, kLdsStack);
     const size_t lds_bytes = sizeof(int) * (size_t)kBlock * (size_t)(stack_cap + 2);
     if (ensure_overflow(c.d_over, c.over_levels, scene->stack_bound - std::min(stack_cap, lds_stack_cap(scene, kPathsLdsStack)))) return 1;
-    const AdvanceKernel advance = advance_kernel(lds_tables);
+    const AdvanceKernel<Camera> advance = advance_kernel<Camera>(lds_tables);
     const TraceKernel trace = trace_kernel(false, false, scene->wide);  // (the watertight build)
     int occ_c = 0;
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_c, trace, kBlock, lds_bytes));

@@ -4,7 +4,7 @@
 //   rt_walk.inc            box test, traversal stack, inner_step; reference_walk; VERIFY (ref_visible); leaf_hits, verify_closest
 //   rt_stream_kernels.inc  k_trace (the pools of a round); the query prepasses; stream_walk, the persistent loop of every dense ray
 //                          array, under k_query (queries and trace hooks), k_aov and k_motion; k_aov_resolve
-//   rt_frame_kernels.inc   k_advance and k_paths, once per source of camera rays
+//   rt_frame_kernels.inc   k_advance<SRC> and k_paths<BUILD>: templates over the source of camera rays and the build tag
 //   rt_build_kernels.inc   device BVH: the leaf-order arrays, the refit (k_refit_*), the build (k_ploc_*)
 //   rt_host_scene.inc      rt_scene and the one way a tree gets into it: build (host SAH, device PLOC), emit, adopt; the entry
 //                          points on top of it (create, update, rebuild, the edits); what the ray entry points share
@@ -238,7 +238,7 @@ struct DWaveRow {
 
 constexpr int kDone = -0x7fffffff;    // slot has no camera ray left
 constexpr int kParked = -0x7ffffffe;  // slot waits for the lockstep rounds of the final generation
-constexpr int kChunkFresh = 0x7ffffffe;  // k_paths_chunked, in the lane's LDS copy of `bounces` only: the lane has taken the slot and made no ray of it yet
+constexpr int kChunkFresh = 0x7ffffffe;  // k_paths<PathsChunked>, in the lane's LDS copy of `bounces` only: the lane has taken the slot and made no ray of it yet
 
 // ============================================================================ wave helpers
 __device__ __forceinline__ unsigned lane_id() {
@@ -332,8 +332,8 @@ struct AdvanceParams {
     int per_sample, key_mul, key_add;
     uint32_t seed_lo, seed_hi;
     // The pixels [bg_x0, bg_x0 + bg_w) x [bg_y0, bg_y0 + bg_h) outside which no camera ray of the frame can hit the scene
-    // (rt_background.h; the whole frame where nothing is known, bg_w = 0 where nothing can be hit).  Read by k_paths_bg /
-    // k_paths_chunked_bg only, which a frame runs if the rectangle is smaller than it: they make no ray for a pixel outside it
+    // (rt_background.h; the whole frame where nothing is known, bg_w = 0 where nothing can be hit).  Read by k_paths<PathsBg> /
+    // k_paths<PathsChunkedBg> only, which a frame runs if the rectangle is smaller than it: they make no ray for a pixel outside it
     // (gen_background).
     int bg_x0, bg_y0, bg_w, bg_h;
 };
@@ -487,7 +487,7 @@ struct RayTable {
 // by the row), which the host hands over as pix_first + (rem_first + c * key_stride) / rays_per_pixel with
 // pix_first = key_first / rays_per_pixel and rem_first = key_first % rays_per_pixel: the same quotient, and its dividend
 // fits 32 bits for every chunk of a stride-1 table (then the divide is the 32-bit one).
-// Travels in k_paths_keyed's uniforms where the camera builds keep the Camera: no larger than it.
+// Travels in k_paths<PathsKeyed>'s uniforms where the camera builds keep the Camera: no larger than it.
 struct KeyedRayTable {
     const float *o3, *d3;  // origins and directions, AoS triples
     const int *pixel;      // the pixel a ray deposits into; null: K / rays_per_pixel
@@ -502,7 +502,7 @@ static_assert(sizeof(KeyedRayTable) <= sizeof(Camera), "k_paths' dynamic LDS is 
 // belongs to the pixel p with offset[p] <= c < offset[p + 1] (offset: the exclusive prefix sum of the counts, n_pixels + 1
 // words, made by the prepass k_counts_*), is that pixel's sample k = first[p] + c - offset[p], and has the 64-bit key
 // p * stride + k: the stream, the jitter and the ray of camera ray G = key of the whole frame.
-// Larger than a Camera: k_paths_counts' launch sizes the dynamic LDS for it (FrameRun::run_persistent).
+// Larger than a Camera: k_paths<PathsCounts>' launch sizes the dynamic LDS for it (FrameRun::run_persistent).
 struct CountsCamera {
     Camera cam;
     const uint32_t *offset;
@@ -617,6 +617,22 @@ __device__ __forceinline__ void gen_pixel(const AdvanceParams &ap, int slot_glob
 __device__ __forceinline__ bool gen_background(const AdvanceParams &ap, int px, int py) {
     return (unsigned)(px - ap.bg_x0) >= (unsigned)ap.bg_w || (unsigned)(py - ap.bg_y0) >= (unsigned)ap.bg_h;
 }
+// gen_new_path: what every gen() that has made a ray leaves: the slot starts a new path.
+__device__ __forceinline__ void gen_new_path(SlotState &st, AdvanceOut &out) {
+    out.new_ray = true;
+    st.bounces = 0;
+    st.beta = mk(1.f, 1.f, 1.f);
+    out.did_gen = true;
+}
+// gen_table_ray: row c of a ray table (RayTable, KeyedRayTable) as the new path ray.  The lanes of a wave serve consecutive slots
+// (or hold consecutive ranks of a drawn chunk), so their rows are consecutive: 768 contiguous bytes per array and wave, read once
+// per frame -- streamed past the caches the BVH lives in (RT_RAYS_NONTEMPORAL).
+template <class TABLE>
+__device__ __forceinline__ void gen_table_ray(const TABLE &tab, unsigned c, AdvanceOut &out) {
+    const float *o3 = tab.o3 + 3 * (size_t)c, *d3 = tab.d3 + 3 * (size_t)c;
+    out.ray_o = mk(table_load(o3), table_load(o3 + 1), table_load(o3 + 2));
+    out.ray_d = mk(table_load(d3), table_load(d3 + 1), table_load(d3 + 2));
+}
 // gen_camera_ray: the stream (per-sample mode), the two jitter draws, camera.get_ray; the slot starts a new path.
 __device__ __forceinline__ void gen_camera_ray(const Camera &cam, const AdvanceParams &ap, long long cid, int px, int py, SlotState &st,
                                                AdvanceOut &out) {
@@ -624,13 +640,10 @@ __device__ __forceinline__ void gen_camera_ray(const Camera &cam, const AdvanceP
     float jx = rng_uniform(st.rs);  // x first, then y (Appendix A.7)
     float jy = rng_uniform(st.rs);
     camera_get_ray(cam, (px + jx) / ap.width, (py + jy) / ap.height, out.ray_o, out.ray_d);
-    out.new_ray = true;
-    st.bounces = 0;
-    st.beta = mk(1.f, 1.f, 1.f);
-    out.did_gen = true;
+    gen_new_path(st, out);
 }
 
-// BG_SKIP (advance_core of k_paths_bg's 2-waves-per-SIMD builds, where gen() stays inside the ADV block): a background
+// BG_SKIP (advance_core of k_paths<PathsBg>'s 2-waves-per-SIMD builds, where gen() stays inside the ADV block): a background
 // camera ray (gen_background) is passed over on the spot -- counted in out.bg_skipped, its two draws made unless every
 // camera ray starts a stream of its own -- and the lane takes its slot's next generation.
 template <bool NEVER_LOCKSTEP = false, bool BG_SKIP = false, class SRC>
@@ -650,10 +663,8 @@ __device__ __forceinline__ void gen_core(const SRC &cam, const AdvanceParams &ap
             out.bg_skipped++;
         }
         gen_camera_ray(cam, ap, cid, px, py, st, out);
-        return;
-    }
-    if constexpr (std::is_same<SRC, CountsCamera>::value) {
-        // Counted frames (k_paths_counts' 2-waves-per-SIMD builds, where ids are tied to slots): camera ray `cid` of the call is
+    } else if constexpr (std::is_same<SRC, CountsCamera>::value) {
+        // Counted frames (k_paths<PathsCounts>' 2-waves-per-SIMD builds, where ids are tied to slots): camera ray `cid` of the call is
         // found in the prefix sum over the whole image; a background pixel's ray is counted and passed over without a stream
         // or a ray, as in the per-sample camera path; then the stream of the ray's 64-bit key, the two draws, the pinhole.
         int px, py;
@@ -668,61 +679,41 @@ __device__ __forceinline__ void gen_core(const SRC &cam, const AdvanceParams &ap
         const float jx = rng_uniform(st.rs);  // x first, then y (Appendix A.7)
         const float jy = rng_uniform(st.rs);
         camera_get_ray(cam.cam, (px + jx) / ap.width, (py + jy) / ap.height, out.ray_o, out.ray_d);
-        out.new_ray = true;
-        st.bounces = 0;
-        st.beta = mk(1.f, 1.f, 1.f);
-        out.did_gen = true;
-        return;
-    }
-    if (!gen_begin<NEVER_LOCKSTEP>(ap, slot_global, st, cid_given, cid)) return;
-    if constexpr (std::is_same<SRC, KeyedRayTable>::value) {
-        // Keyed ray-table frames: row `cid` starts the per-sample stream of its key (whatever stream the lane held), gen()'s
-        // two jitter draws are made and dropped -- a pinhole's own table reproduces the RT_FLAG_RNG_PER_SAMPLE frame draw for
-        // draw --, the ray is the row.  Rows are read as in the RayTable branch below: the lanes of a wave hold consecutive
-        // ranks of a drawn chunk (or consecutive slots), so consecutive rows.
-        const unsigned c = (unsigned)cid;  // (below 2^31: the host checks the frame)
-        const unsigned long long ck = (unsigned long long)c * cam.key_stride;  // (no wrap: c < 2^31, key_stride < 2^32)
-        st.rs = rng_sample_stream(ap.seed_lo, ap.seed_hi, cam.key_first + ck);  // (the host refuses keys that wrap)
-        rng_next(st.rs);  // x first, then y (Appendix A.7)
-        rng_next(st.rs);
-        const float *o3 = cam.o3 + 3 * (size_t)c, *d3 = cam.d3 + 3 * (size_t)c;
-        out.ray_o = mk(table_load(o3), table_load(o3 + 1), table_load(o3 + 2));
-        out.ray_d = mk(table_load(d3), table_load(d3 + 1), table_load(d3 + 2));
-        if (cam.pixel) {
-            st.pixel = table_load(cam.pixel + c);
-        } else {
-            const unsigned long long t = cam.rem_first + ck;  // K / rays_per_pixel = pix_first + t / rays_per_pixel
-            const unsigned q = (t >> 32) ? (unsigned)(t / cam.rays_per_pixel) : (unsigned)t / cam.rays_per_pixel;
-            st.pixel = cam.pix_first + (int)q;  // (below n_pixels: the host checks the last key)
-        }
-        out.new_ray = true;
-        st.bounces = 0;
-        st.beta = mk(1.f, 1.f, 1.f);
-        out.did_gen = true;
-        return;
-    } else if constexpr (std::is_same<SRC, RayTable>::value) {
-        // Ray-table frames: gen()'s two jitter draws are made and dropped (the slot's stream stays where the reference's
-        // is), the ray and its pixel are row `cid` of the table.  No pixel coordinates, no stepping (`pxy` is left alone).
-        // The lanes of a wave serve consecutive slots, so their rows are consecutive: 768 contiguous bytes per array and
-        // wave, read once per frame -- streamed past the caches the BVH lives in (RT_RAYS_NONTEMPORAL).
-        const unsigned c = (unsigned)cid;  // (below 2^31: the host checks the frame)
-        rng_next(st.rs);  // x first, then y (Appendix A.7)
-        rng_next(st.rs);
-        const float *o3 = cam.o3 + 3 * (size_t)c, *d3 = cam.d3 + 3 * (size_t)c;
-        out.ray_o = mk(table_load(o3), table_load(o3 + 1), table_load(o3 + 2));
-        out.ray_d = mk(table_load(d3), table_load(d3 + 1), table_load(d3 + 2));
-        st.pixel = cam.pixel ? table_load(cam.pixel + c) : (int)(c / (unsigned)ap.spp);  // (render.cuh:254-256)
-        out.new_ray = true;
-        st.bounces = 0;
-        st.beta = mk(1.f, 1.f, 1.f);
-        out.did_gen = true;
-        return;
-    } else if constexpr (std::is_same<SRC, CountsCamera>::value) {
-        // (not reached: the counted frame's branch above has returned)
+        gen_new_path(st, out);
     } else {
-        int px, py;
-        gen_pixel(ap, slot_global, st, pxy, cid_given, cid, px, py);
-        gen_camera_ray(cam, ap, cid, px, py, st, out);
+        if (!gen_begin<NEVER_LOCKSTEP>(ap, slot_global, st, cid_given, cid)) return;
+        if constexpr (std::is_same<SRC, KeyedRayTable>::value) {
+            // Keyed ray-table frames: row `cid` starts the per-sample stream of its key (whatever stream the lane held), gen()'s
+            // two jitter draws are made and dropped -- a pinhole's own table reproduces the RT_FLAG_RNG_PER_SAMPLE frame draw for
+            // draw --, the ray is the row.
+            const unsigned c = (unsigned)cid;  // (below 2^31: the host checks the frame)
+            const unsigned long long ck = (unsigned long long)c * cam.key_stride;  // (no wrap: c < 2^31, key_stride < 2^32)
+            st.rs = rng_sample_stream(ap.seed_lo, ap.seed_hi, cam.key_first + ck);  // (the host refuses keys that wrap)
+            rng_next(st.rs);  // x first, then y (Appendix A.7)
+            rng_next(st.rs);
+            gen_table_ray(cam, c, out);
+            if (cam.pixel) {
+                st.pixel = table_load(cam.pixel + c);
+            } else {
+                const unsigned long long t = cam.rem_first + ck;  // K / rays_per_pixel = pix_first + t / rays_per_pixel
+                const unsigned q = (t >> 32) ? (unsigned)(t / cam.rays_per_pixel) : (unsigned)t / cam.rays_per_pixel;
+                st.pixel = cam.pix_first + (int)q;  // (below n_pixels: the host checks the last key)
+            }
+            gen_new_path(st, out);
+        } else if constexpr (std::is_same<SRC, RayTable>::value) {
+            // Ray-table frames: gen()'s two jitter draws are made and dropped (the slot's stream stays where the reference's
+            // is), the ray and its pixel are row `cid` of the table.  No pixel coordinates, no stepping (`pxy` is left alone).
+            const unsigned c = (unsigned)cid;  // (below 2^31: the host checks the frame)
+            rng_next(st.rs);  // x first, then y (Appendix A.7)
+            rng_next(st.rs);
+            gen_table_ray(cam, c, out);
+            st.pixel = cam.pixel ? table_load(cam.pixel + c) : (int)(c / (unsigned)ap.spp);  // (render.cuh:254-256)
+            gen_new_path(st, out);
+        } else {
+            int px, py;
+            gen_pixel(ap, slot_global, st, pxy, cid_given, cid, px, py);
+            gen_camera_ray(cam, ap, cid, px, py, st, out);
+        }
     }
 }
 
@@ -942,90 +933,57 @@ constexpr bool kSpeculate = RT_SPECULATE != 0;  // k_paths: postpone a leaf reac
 // ref_visible): a shadow ray's accepted hit counts only if the reference's walk can see its triangle (triangle block); a
 // path ray's closest hit is checked once, at the top of the ADV block that shades it -- visible, and no exact tie at the
 // final distance -- and the ~2 rays in 10^7 that fail are re-traced there by reference_walk.
-// The two kernels of a frame, once per source of camera rays (see gen_core): the text of rt_frame_kernels.inc compiled with
-// RT_FRAME_SRC = Camera as k_advance / k_paths and with RT_FRAME_SRC = RayTable (rt_render_rays_*) as k_advance_rays /
-// k_paths_rays.  Two compilations of one text rather than a template parameter or a shared device function: the camera
-// builds keep their symbols, their arguments and -- instruction for instruction -- their code.
 #ifdef RT_TRACE_PROFILE
 constexpr int kProfHead = 26;  // qwords of k_paths' totals
 constexpr int kProfRec = 6;    // qwords of k_paths' per-wave record (behind the totals)
 #endif
-#define RT_PATHS_CHUNKS 0
-#define RT_PATHS_BG 0
-#define RT_FRAME_SRC Camera
-#define RT_K_ADVANCE k_advance
-#define RT_K_PATHS k_paths
+// The two kernels of a frame are templates (rt_frame_kernels.inc): k_advance<SRC, LDS_TABLES> over the source of camera rays (see
+// gen_core) and k_paths<BUILD, ...> over a build tag.  A tag names the source type and the axes that are compiled in or out:
+// kChunks (the chunked deal, rt_slot_chunks.h), kBg (gen() passes over background pixels: rt_background.h, gen_background) and
+// kCounts (a counted frame's ids: the prefix sum of the count map).  One NAMED tag per build that is launched, so that a
+// profile's or a resource remark's kernel name says which build it is (k_paths<PathsChunkedBg, ...>); a new source or a new axis
+// is one more tag here and one more line in the host's selection (FrameRun::run_persistent).  An axis is a compile-time
+// constant and not a kernel argument so that a build carries nothing of what it does not run, instruction for instruction:
+// tools/device_code_diff.py on two builds' assembly is the check.
+// k_advance exists for the sources whose frames can run on the round pipeline: Camera and RayTable.  Per-sample streams (keyed
+// tables, counted frames) run on the persistent kernel only.
+struct PathsCamera {  // the camera's frame, static deal, nothing to skip: every frame that no other tag takes
+    using Src = Camera;
+    static constexpr bool kChunks = false, kBg = false, kCounts = false;
+};
+struct PathsRays {  // rt_render_rays_*: camera ray c is row c of the caller's table.  Tables keep the static deal: no table frame has
+    using Src = RayTable;  // been timed with the chunked one
+    static constexpr bool kChunks = false, kBg = false, kCounts = false;
+};
+struct PathsKeyed {  // rt_render_rays_keyed_*: a table with a per-sample stream per row
+    using Src = KeyedRayTable;
+    static constexpr bool kChunks = false, kBg = false, kCounts = false;
+};
+// The camera with the chunked deal compiled in: launched instead of the 4-waves-per-SIMD reference-mode PathsCamera builds when the
+// launch plan picks a chunk, and only those instances exist.  A tag of its own so that the static deal keeps its code: with the
+// deal's code in it the static deal was 2.5 % slower (see s_task in k_paths).
+struct PathsChunked {
+    using Src = Camera;
+    static constexpr bool kChunks = true, kBg = false, kCounts = false;
+};
+// Both camera builds with the background skip compiled into gen(): launched instead of PathsCamera / PathsChunked when the frame's
+// rectangle (AdvanceParams::bg_*) is smaller than the frame.  A frame with nothing to skip keeps a kernel of its own because the
+// skipping GEN block with a whole-frame rectangle cost C2 3 %.
+struct PathsBg {
+    using Src = Camera;
+    static constexpr bool kChunks = false, kBg = true, kCounts = false;
+};
+struct PathsChunkedBg {
+    using Src = Camera;
+    static constexpr bool kChunks = true, kBg = true, kCounts = false;
+};
+// rt_render_counts_fixed: the skipping text, whose GEN block finds a drawn id's pixel and sample in the prefix sum of the count
+// map.  Per-sample streams, so of it the two per-sample builds per table placement.
+struct PathsCounts {
+    using Src = CountsCamera;
+    static constexpr bool kChunks = false, kBg = true, kCounts = true;
+};
 #include "rt_frame_kernels.inc"
-#undef RT_FRAME_SRC
-#undef RT_K_ADVANCE
-#undef RT_K_PATHS
-#define RT_FRAME_SRC RayTable
-#define RT_K_ADVANCE k_advance_rays
-#define RT_K_PATHS k_paths_rays
-#include "rt_frame_kernels.inc"
-#undef RT_FRAME_SRC
-#undef RT_K_ADVANCE
-#undef RT_K_PATHS
-// and with RT_FRAME_SRC = KeyedRayTable (rt_render_rays_keyed_*) as k_paths_keyed: per-sample streams, so the persistent kernel
-// only (k_advance_keyed is never instantiated)
-#define RT_FRAME_SRC KeyedRayTable
-#define RT_K_ADVANCE k_advance_keyed
-#define RT_K_PATHS k_paths_keyed
-#include "rt_frame_kernels.inc"
-#undef RT_FRAME_SRC
-#undef RT_K_ADVANCE
-#undef RT_K_PATHS
-// and once more for the camera with the chunked deal compiled in (rt_slot_chunks.h): k_paths_chunked, launched instead of the
-// 4-waves-per-SIMD reference-mode k_paths when the launch plan picks a chunk (its k_advance twin is never instantiated).  Ray
-// tables keep the static deal: no table frame has been timed with the deal.
-#undef RT_PATHS_CHUNKS
-#define RT_PATHS_CHUNKS 1
-#define RT_FRAME_SRC Camera
-#define RT_K_ADVANCE k_advance_chunked_unused
-#define RT_K_PATHS k_paths_chunked
-#include "rt_frame_kernels.inc"
-#undef RT_FRAME_SRC
-#undef RT_K_ADVANCE
-#undef RT_K_PATHS
-#undef RT_PATHS_CHUNKS
-// and both camera builds once more with the background skip compiled into gen() (rt_background.h; gen_background): k_paths_bg and
-// k_paths_chunked_bg, launched instead of k_paths / k_paths_chunked when the frame's rectangle is smaller than the frame (their
-// k_advance twins are never instantiated).  Kernels of their own name so that a frame with nothing to skip keeps its code,
-// instruction for instruction: the skipping GEN block with a whole-frame rectangle cost C2 3 %.
-#undef RT_PATHS_BG
-#define RT_PATHS_BG 1
-#define RT_PATHS_CHUNKS 0
-#define RT_FRAME_SRC Camera
-#define RT_K_ADVANCE k_advance_bg_unused
-#define RT_K_PATHS k_paths_bg
-#include "rt_frame_kernels.inc"
-#undef RT_K_ADVANCE
-#undef RT_K_PATHS
-#undef RT_PATHS_CHUNKS
-#define RT_PATHS_CHUNKS 1
-#define RT_K_ADVANCE k_advance_chunked_bg_unused
-#define RT_K_PATHS k_paths_chunked_bg
-#include "rt_frame_kernels.inc"
-#undef RT_FRAME_SRC
-#undef RT_K_ADVANCE
-#undef RT_K_PATHS
-#undef RT_PATHS_CHUNKS
-// and the skipping text once more for a counted frame (rt_render_counts_fixed; RT_FRAME_SRC = CountsCamera) as k_paths_counts:
-// its GEN block finds a drawn id's pixel and sample in the prefix sum of the count map (RT_PATHS_COUNTS).  Per-sample streams,
-// so the persistent kernel only, and of it the two per-sample builds (k_advance_counts_unused is never instantiated).
-#define RT_PATHS_CHUNKS 0
-#undef RT_PATHS_COUNTS
-#define RT_PATHS_COUNTS 1
-#define RT_FRAME_SRC CountsCamera
-#define RT_K_ADVANCE k_advance_counts_unused
-#define RT_K_PATHS k_paths_counts
-#include "rt_frame_kernels.inc"
-#undef RT_FRAME_SRC
-#undef RT_K_ADVANCE
-#undef RT_K_PATHS
-#undef RT_PATHS_CHUNKS
-#undef RT_PATHS_COUNTS
-#undef RT_PATHS_BG
 
 // The prepass of a counted frame, three kernels on the caller's stream.  A workgroup serves kCountsTile consecutive pixels, a lane
 // kCountsItems consecutive ones of them.  words[0]: pixels whose (first, count) the call refuses; words[1]: the sum of the counts;

@@ -1,7 +1,7 @@
-"""The register budget of the builds that pass over background pixels (k_paths_bg, k_paths_chunked_bg: DESIGN section 5).  No GPU.
+"""The register budget of the builds that pass over background pixels (k_paths<PathsBg>, k_paths<PathsChunkedBg>: DESIGN section 5).  No GPU.
 
 They run every BASELINE frame, on the same 128-VGPR budget as the 4-waves-per-SIMD builds of k_paths (tests/test_host_logic.py)
-and k_paths_chunked (tests/test_slot_chunks_host.py): no VGPR spill and 4 waves per SIMD in every 4-wave instance the library
+and k_paths<PathsChunked> (tests/test_slot_chunks_host.py): no VGPR spill and 4 waves per SIMD in every 4-wave instance the library
 launches.  A build that tips into spills loses 4 - 6 % of the frame and nothing else shows it."""
 import os
 import re
@@ -12,12 +12,13 @@ import pytest
 
 from conftest import ROOT
 
-# mangled names: k_paths_bg<LDS_TABLES, WIDE, 4, DRAW_CIDS, LITERAL, VERIFY>, k_paths_chunked_bg<LDS_TABLES, WIDE, 4, false, ...>
+# mangled names: k_paths<PathsBg, LDS_TABLES, WIDE, 4, DRAW_CIDS, LITERAL, VERIFY>, k_paths<PathsChunkedBg, LDS_TABLES, WIDE, 4, false, ...>
+# (the keys stay the builds' short names: they are the test ids)
 BUILDS = {
     # both LDS_TABLES x (literal; per-sample, wide and not; default and watertight, wide and not) = 2 x 7
-    "k_paths_bg": (r"Function Name: _Z10k_paths_bgILb[01]ELb[01]ELi4ELb[01]E", 14),
+    "k_paths_bg": (r"Function Name: _Z7k_pathsI7PathsBgLb[01]ELb[01]ELi4ELb[01]E", 14),
     # both LDS_TABLES x (literal; default and watertight, wide and not) = 2 x 5
-    "k_paths_chunked_bg": (r"Function Name: _Z18k_paths_chunked_bgILb[01]ELb[01]ELi4ELb0E", 10),
+    "k_paths_chunked_bg": (r"Function Name: _Z7k_pathsI14PathsChunkedBgLb[01]ELb[01]ELi4ELb0E", 10),
 }
 
 

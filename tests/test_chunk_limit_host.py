@@ -1,4 +1,4 @@
-"""CPU tests of the limit of a run over background pixels in k_paths_bg's GEN block (rtcuda_amd/csrc/rt_slot_chunks.h through
+"""CPU tests of the limit of a run over background pixels in k_paths<PathsBg>'s GEN block (rtcuda_amd/csrc/rt_slot_chunks.h through
 librt_hostcheck.so): one generation fixed before the run, against the stop tests the loop used to make turn by turn."""
 import ctypes
 import os

@@ -1,4 +1,4 @@
-"""GPU tests of the background skip of k_paths / k_paths_chunked (rt_background.h): a camera ray whose pixel
+"""GPU tests of the background skip of k_paths / k_paths<PathsChunked> (rt_background.h): a camera ray whose pixel
 lies outside the rectangle the scene's bounds project to is counted, its two jitter draws are made, and no ray is made or
 walked.  Nothing else may change: RT_FLAG_DETERMINISTIC's int64 sums and every event total must EQUAL the CPU oracle's, those of
 the same frame with RT_BG_SKIP=0 (the rectangle is the whole frame: every ray is walked, as before).  Run with -m gpu.  Those
@@ -105,7 +105,7 @@ def _arrays():
 
 def _on_off(api, gpu, monkeypatch, w, h, spp, want=None, st_c=None, rounds=False, **kw):
     """The frame with the skip on (the default), held to the oracle's frame if given, and to RT_BG_SKIP=0; `rounds`: and to the
-    round pipeline.  The skipping frame's persistent launch must have been k_paths_bg / k_paths_chunked_bg
+    round pipeline.  The skipping frame's persistent launch must have been k_paths<PathsBg> / k_paths<PathsChunkedBg>
     (st["background_skip"]; without that the comparisons below would hold trivially), the RT_BG_SKIP=0 frame's and the rounds' not.
     Returns the frame."""
     what = (w, h, spp, tuple(sorted(kw.items(), key=lambda t: t[0])) if "cam" not in kw else "cam")
@@ -190,7 +190,7 @@ def test_camera_turned_away_from_the_scene(api, gpu, monkeypatch):
 
 
 def test_background_runs_across_chunk_ends(api, gpu, monkeypatch):
-    """1024 x 770 x 512: 385 generations, so chains of 384 rays in k_paths_chunked -- the shortest the launch plan deals -- and
+    """1024 x 770 x 512: 385 generations, so chains of 384 rays in k_paths<PathsChunked> -- the shortest the launch plan deals -- and
     G = 48.  (1024 x 768 x 512 is exactly 384 generations: its chains are 383 rays, the last generation runs in lockstep, and the
     plan keeps the static deal.)  A run of background generations crosses chunk ends and reaches the end of a slot's chain.
     Skip on against RT_BG_SKIP=0 (no oracle at this size), then the same with every set dealt 64 rays at a time."""
@@ -200,11 +200,11 @@ def test_background_runs_across_chunk_ends(api, gpu, monkeypatch):
         _knobs(monkeypatch, chunk=chunk, head=head)
         got, st = _sums(api, gpu, w, h, spp)
         assert st["slot_chunk"] == g, st["slot_chunk"]
-        assert st["background_skip"] == 1 and _expect_skip(api, w, h)  # (k_paths_chunked_bg)
+        assert st["background_skip"] == 1 and _expect_skip(api, w, h)  # (k_paths<PathsChunkedBg>)
         assert st["camera_rays"] == w * h * spp
         _knobs(monkeypatch, skip=False, chunk=chunk, head=head)
         off, st_off = _sums(api, gpu, w, h, spp)
-        assert st_off["slot_chunk"] == g and st_off["background_skip"] == 0  # (k_paths_chunked)
+        assert st_off["slot_chunk"] == g and st_off["background_skip"] == 0  # (k_paths<PathsChunked>)
         _same(got, st, off, st_off, ("skip on / off", chunk, head))
         if ref is not None:
             _same(got, st, ref[0], ref[1], "G = 48 / G = 64 head 0")

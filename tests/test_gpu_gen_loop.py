@@ -1,4 +1,4 @@
-"""GPU tests of the GEN block's run over background pixels in k_paths_bg / k_paths_chunked_bg: a lane's run
+"""GPU tests of the GEN block's run over background pixels in k_paths<PathsBg> / k_paths<PathsChunkedBg>: a lane's run
 ends at a pixel inside the rectangle or at ONE limit fixed before the run (rtchunks::run_limit: the end of the slot's chain, a
 dealt lane's next chunk's end, one turn where the pixel cannot be stepped).  The frames here put the three limits where a run
 meets them; RT_FLAG_DETERMINISTIC's int64 sums and every event total must EQUAL the CPU oracle's and those of the same frame
@@ -43,7 +43,7 @@ def _skipping(api, gpu, monkeypatch, w, h, spp, chunk, head, **kw):
     return got, st
 
 
-# 320 x 180 x 256: 14.06 generations, so chains of 14 camera rays in k_paths_chunked_bg.  G = 1: every turn of a run ends a
+# 320 x 180 x 256: 14.06 generations, so chains of 14 camera rays in k_paths<PathsChunkedBg>.  G = 1: every turn of a run ends a
 # chunk; 4 and 5 do not divide the chain; 13: a chunk's end one turn before the chain's.  RT_SLOT_HEAD unset: the plan's static
 # head (lanes inside it run to g_stop, lanes past it to the chunk's end, in one wave); 0: every set dealt.
 @pytest.mark.parametrize("head", [None, 0])

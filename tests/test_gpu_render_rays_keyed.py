@@ -4,7 +4,7 @@ Row c of a keyed table has the key K = key_first + c * key_stride and the stream
 frame, so a table that holds a pinhole camera's own per-sample rays (tests/raytable_keyed.py, held to the oracle by
 tests/test_render_rays_keyed_host.py) must give `oracle.render(..., rng_mode="per_sample")`: ALL int64 sums EQUAL and the six
 event totals EQUAL, no tolerance, no masked pixel -- for the whole table, for rank r of R, for chunks in any order, for keys
-beyond 2^32, through every build of k_paths_keyed.  Test 11 (rays no pinhole makes) is GPU against itself: a consistency
+beyond 2^32, through every build of k_paths<PathsKeyed>.  Test 11 (rays no pinhole makes) is GPU against itself: a consistency
 check of the partition invariance; tests 1 - 5 are the correctness pins."""
 import numpy as np
 import pytest

@@ -141,7 +141,7 @@ def test_knob_without_the_gate_changes_nothing(api, gpu, oracle, monkeypatch):
 
 def test_default_deal_on_the_headline_frame(api, gpu, monkeypatch):
     """C2 (1920 x 1080 x 256, chains of 506 rays) with no knob: the launch plan picks the chunked deal, G = ceil(506 / 8) = 64,
-    k_paths_chunked runs it, and the frame's event totals are the committed oracle totals.  One frame, 0.1 s of GPU."""
+    k_paths<PathsChunked> runs it, and the frame's event totals are the committed oracle totals.  One frame, 0.1 s of GPU."""
     import json
     import os
     monkeypatch.setenv("RTCUDA_EXPERIMENTAL", "0")

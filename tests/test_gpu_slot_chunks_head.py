@@ -1,4 +1,4 @@
-"""GPU tests of k_paths_chunked's static head and LDS semaphores (rt_slot_chunks.h): a lane runs its first
+"""GPU tests of k_paths<PathsChunked>'s static head and LDS semaphores (rt_slot_chunks.h): a lane runs its first
 `head` slot sets as the static deal does, and only the remaining sets are dealt G camera rays at a time, handed over through
 16-bit semaphore fields in the workgroup's LDS.  Nothing a ray does may change: for every head the event totals and
 RT_FLAG_DETERMINISTIC's int64 sums must EQUAL the CPU oracle's and those of RT_SLOT_CHUNK=0, the static deal -- every path,
@@ -88,7 +88,7 @@ def test_ragged_chains_behind_a_static_head(api, gpu, oracle, monkeypatch):
 
 @pytest.mark.parametrize("shard,head", [((0, 1), 2), ((3, 4), 0)])
 def test_long_chains_at_the_default_head(api, gpu, oracle, monkeypatch, shard, head):
-    """256 x 128 x 256: 8 generations, so chains of 7 rays inside k_paths_chunked (the eighth generation runs in lockstep) and 6
+    """256 x 128 x 256: 8 generations, so chains of 7 rays inside k_paths<PathsChunked> (the eighth generation runs in lockstep) and 6
     hand-overs per dealt slot at G = 1.  The whole frame has four
     slots per lane (default head 2); shard 3 of 4 has ONE slot per lane (head 0): every lane that runs ahead leaves a claim, and
     the claims pile up in neighbouring 16-bit fields."""

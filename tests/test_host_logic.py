@@ -250,7 +250,7 @@ def test_full_pool_k_paths_builds_do_not_spill_vector_registers():
     assert r.returncode == 0, r.stdout[-2000:]
     lines = r.stdout.splitlines()
     found = 0
-    # k_paths<LDS_TABLES = true, WIDE = true (bench) / false, MIN_WAVES = 4, DRAW_CIDS, LITERAL, VERIFY>:
+    # k_paths<PathsCamera, LDS_TABLES = true, WIDE = true (bench) / false, MIN_WAVES = 4, DRAW_CIDS, LITERAL, VERIFY>:
     #   (0, 0, 1) the DEFAULT build -- the one bench.py times: the reference's decisions on the product's walk;
     #   (0, 0, 0) RT_FLAG_WATERTIGHT;  (1, 0, 0) the per-sample-RNG build (fewer registers: at least 4 waves);
     #   (0, 1, 0) RT_FLAG_REFERENCE_WALK (round 4: 53 spilled registers -- its private stack had been promoted to 32 VGPRs;
@@ -261,7 +261,7 @@ def test_full_pool_k_paths_builds_do_not_spill_vector_registers():
             for wide in (1, 0):
                 if lit and wide:
                     continue  # (the literal walk does not look at the product's node format: one build)
-                if f"Function Name: _Z7k_pathsILb1ELb{wide}ELi4ELb{draw}ELb{lit}ELb{ver}EE" in line:
+                if f"Function Name: _Z7k_pathsI11PathsCameraLb1ELb{wide}ELi4ELb{draw}ELb{lit}ELb{ver}EE" in line:
                     block = "\n".join(lines[k:k + 12])
                     m_spill = re.search(r"VGPRs Spill: (\d+)", block)
                     m_occ = re.search(r"Occupancy \[waves/SIMD\]: (\d+)", block)

@@ -1,5 +1,5 @@
 """CPU tests of the persistent launch's geometry (rtcuda_amd/csrc/rt_launch_plan.h through librt_hostcheck.so's
-rt_plan_paths_launch): what render_shard_impl launches k_paths / k_paths_rays / k_paths_keyed with, for a given shard size,
+rt_plan_paths_launch): what render_shard_impl launches k_paths / k_paths<PathsRays> / k_paths<PathsKeyed> with, for a given shard size,
 device and scene.  Every expected value is worked out by hand from the rules as they stood inside render_shard_impl before
 they became a function of their own -- none comes from running the function."""
 import ctypes

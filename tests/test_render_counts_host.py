@@ -100,7 +100,7 @@ def test_symbol_table_has_the_four_builds_of_k_paths_counts(api):
     syms = subprocess.run(["nm", api.LIB_PATH], capture_output=True, text=True, check=True).stdout
     for lds in (0, 1):
         for waves, draw in ((4, 1), (2, 0)):
-            assert f" _Z14k_paths_countsILb{lds}ELb1ELi{waves}ELb{draw}ELb0ELb0EE" in syms, (lds, waves, draw)
+            assert f" _Z7k_pathsI11PathsCountsLb{lds}ELb1ELi{waves}ELb{draw}ELb0ELb0EE" in syms, (lds, waves, draw)
     for name in ("k_counts_sums", "k_counts_scan", "k_counts_offsets", "k_normalize_counts", "k_post_process_counts", "k_allocate_total", "k_allocate_counts"):
         assert re.search(rf" _Z\d+{name}", syms), name
 

@@ -115,17 +115,17 @@ def test_new_entry_points_are_declared_exported_and_bound(api):
 
 
 def test_symbol_table_has_the_keyed_builds_of_the_persistent_kernel(api):
-    """k_paths_keyed<LDS_TABLES, WIDE = true, MIN_WAVES, DRAW_CIDS, false, false>: the full-pool build draws its rows from the
+    """k_paths<PathsKeyed, LDS_TABLES, WIDE = true, MIN_WAVES, DRAW_CIDS, false, false>: the full-pool build draws its rows from the
     frame's counter (4, true), the few-blocks build ties them to slots (2, false); each with tables in LDS and in global memory."""
     syms = subprocess.run(["nm", api.LIB_PATH], capture_output=True, text=True, check=True).stdout
     for lds in (0, 1):
         for waves, draw in ((4, 1), (2, 0)):
-            assert f" _Z13k_paths_keyedILb{lds}ELb1ELi{waves}ELb{draw}ELb0ELb0EE" in syms, (lds, waves, draw)
+            assert f" _Z7k_pathsI10PathsKeyedLb{lds}ELb1ELi{waves}ELb{draw}ELb0ELb0EE" in syms, (lds, waves, draw)
 
 
 def test_full_pool_keyed_builds_do_not_spill_vector_registers():
     """As test_full_pool_k_paths_builds_do_not_spill_vector_registers reads the camera builds: the compiler's resource remarks
-    of the two 4-waves-per-SIMD k_paths_keyed builds report no VGPR spill and an occupancy of at least 4."""
+    of the two 4-waves-per-SIMD k_paths<PathsKeyed> builds report no VGPR spill and an occupancy of at least 4."""
     import shutil
     hipcc = "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc) and not shutil.which("hipcc"):
@@ -137,7 +137,7 @@ def test_full_pool_keyed_builds_do_not_spill_vector_registers():
     found = 0
     for k, line in enumerate(lines):
         for lds in (0, 1):
-            if f"Function Name: _Z13k_paths_keyedILb{lds}ELb1ELi4ELb1ELb0ELb0EE" in line:
+            if f"Function Name: _Z7k_pathsI10PathsKeyedLb{lds}ELb1ELi4ELb1ELb0ELb0EE" in line:
                 block = "\n".join(lines[k:k + 12])
                 m_spill = re.search(r"VGPRs Spill: (\d+)", block)
                 m_occ = re.search(r"Occupancy \[waves/SIMD\]: (\d+)", block)

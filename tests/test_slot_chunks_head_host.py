@@ -92,7 +92,7 @@ def test_head_knob_works_only_behind_the_gate(L, monkeypatch):
 
 
 def test_static_deal_where_the_semaphores_do_not_fit(L):
-    """The semaphores are 2 KB of static LDS in k_paths_chunked.  The host asks the device how many workgroups of that kernel a
+    """The semaphores are 2 KB of static LDS in k_paths<PathsChunked>.  The host asks the device how many workgroups of that kernel a
     CU holds at the plan's dynamic LDS; below the four the plan assumes, the frame keeps the static deal."""
     assert L.rt_plan_slot_chunk_if_resident(64, 4) == 64 and L.rt_plan_slot_chunk_if_resident(64, 5) == 64
     assert L.rt_plan_slot_chunk_if_resident(64, 3) == 0 and L.rt_plan_slot_chunk_if_resident(3, 0) == 0

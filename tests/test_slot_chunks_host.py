@@ -133,7 +133,7 @@ def test_knob_travels_through_the_launch_plan(L, monkeypatch):
 
 
 def test_chunked_kernels_do_not_spill_vector_registers():
-    """k_paths_chunked lives on the same 128-VGPR budget as the 4-waves-per-SIMD builds of k_paths (tests/test_host_logic.py): no
+    """k_paths<PathsChunked, ...> lives on the same 128-VGPR budget as the 4-waves-per-SIMD builds of k_paths (tests/test_host_logic.py): no
     VGPR spill and 4 waves per SIMD in each of the 10 instances the library launches."""
     import re
     import shutil
@@ -147,7 +147,7 @@ def test_chunked_kernels_do_not_spill_vector_registers():
     lines = r.stdout.splitlines()
     found = 0
     for k, line in enumerate(lines):
-        if re.search(r"Function Name: _Z15k_paths_chunkedILb[01]ELb[01]ELi4ELb0E", line):
+        if re.search(r"Function Name: _Z7k_pathsI12PathsChunkedLb[01]ELb[01]ELi4ELb0E", line):
             block = "\n".join(lines[k:k + 12])
             m_spill, m_occ = re.search(r"VGPRs Spill: (\d+)", block), re.search(r"Occupancy \[waves/SIMD\]: (\d+)", block)
             m_vgpr = re.search(r" VGPRs: (\d+)", block)

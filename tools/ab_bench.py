@@ -4,8 +4,8 @@
 usage: ab_bench.py [--scene full_bsdf] [--spp 256] [--reps 3] [--shards 1] [--lookfrom x,y,z] [--lookat x,y,z] "K1=V1,K2=V2" "K1=V3" ...
        (an empty string "" = the defaults; knobs read at scene creation -- RT_BVH_* -- get a scene of their own)
 
-Prints one line per setting: frame time (best and mean of `reps` after one warm-up), the kernel's own time, and the
-event totals (which must not move: every knob here is result-invariant)."""
+Prints one line per setting: frame time (best and mean of `reps` after one warm-up), the kernel's own time, which build of
+k_paths the launch plan picked (the chunk of the chunked deal, 0 = the static deal; the background skip), and the event totals (which must not move: every knob here is result-invariant)."""
 import os
 import sys
 import time
@@ -48,5 +48,5 @@ for setting in (args or [""]):
     best, mean = min(times) * 1e3, sum(times) / len(times) * 1e3
     base = base or best
     print(f"{setting or '(defaults)':40s} best {best:8.2f} ms  mean {mean:8.2f} ms  kernel {st['seconds_trace'] * 1e3:8.2f} ms  "
-          f"x{base / best:.3f}  events {st['camera_rays']} {st['shade_events']} {st['any_rays']} {st['shadow_adds']} {st['rr_draws']}  image sum {digest:.6f}",
+          f"x{base / best:.3f}  chunk {st['slot_chunk']} bg {st['background_skip']}  events {st['camera_rays']} {st['shade_events']} {st['any_rays']} {st['shadow_adds']} {st['rr_draws']}  image sum {digest:.6f}",
           flush=True)

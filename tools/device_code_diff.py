@@ -3,7 +3,7 @@
 
     hipcc --offload-arch=gfx950 <the Makefile's FLAGS> --cuda-device-only -S -o A.s rtcuda_amd.hip     (one commit)
     hipcc ... -o B.s rtcuda_amd.hip                                                                    (another)
-    python tools/device_code_diff.py A.s B.s [--rename OLD=NEW ...]
+    python tools/device_code_diff.py A.s B.s [--rename OLD=NEW ...] [--demangled]
 
 Both assembly files are split per function (from the function's label to its .Lfunc_end), comments and directives are
 dropped, and local labels (.LBB..., .Ltmp...) are renumbered in order of appearance, so that what is left of a function is
@@ -12,8 +12,14 @@ differs, is missing from B or is new in B; exits 1 if any function differs or is
 --rename OLD=NEW (any number, applied in order): in the NAMES of A's functions every substring OLD becomes NEW before the two
 files are matched, so that a kernel whose template parameters changed -- and with them its mangled name -- is compared body
 against body with its successor.  The bodies are not touched.
+--demangled: after the renames, the functions of both files are matched by their demangled names WITHOUT the parameter list
+(c++filt -p: `k_paths<PathsBg, true, true, 4, false, false, true>`).  For a kernel whose parameter types re-mangle although they
+did not change -- a parameter that became `typename BUILD::Src` is a substitution in the new name and spelt out in the old --
+no substring rename of the whole mangled name exists; a rename of its head (`_Z10k_paths_bgI=_Z7k_pathsI7PathsBg`) is enough
+here, since what follows the template arguments is dropped.  Two functions of one file with the same such name are an error.
 It compares text: what the lines say is none of its business."""
 import re
+import subprocess
 import sys
 
 LOCAL = re.compile(r"\.L[A-Za-z_$][\w$.]*")
@@ -65,8 +71,23 @@ def renamed(funcs, pairs):
     return out
 
 
+def demangled(funcs):
+    """The same functions under their demangled names without parameter lists (a name c++filt cannot read is kept)."""
+    names = list(funcs)
+    res = subprocess.run(["c++filt", "-p"], input="\n".join(names) + "\n", capture_output=True, text=True, check=True).stdout.splitlines()
+    assert len(res) == len(names)
+    out = {}
+    for old, new in zip(names, res):
+        if new in out:
+            raise SystemExit(f"--demangled maps two functions onto {new}")
+        out[new] = funcs[old]
+    return out
+
+
 def main(argv):
     pairs = []
+    by_demangled = "--demangled" in argv
+    argv = [x for x in argv if x != "--demangled"]
     while "--rename" in argv:
         k = argv.index("--rename")
         stop = next((i for i in range(k + 1, len(argv)) if "=" not in argv[i]), len(argv))
@@ -76,6 +97,8 @@ def main(argv):
         print(__doc__)
         return 2
     a, b = renamed(functions(argv[1]), pairs), functions(argv[2])
+    if by_demangled:
+        a, b = demangled(a), demangled(b)
     differ = [n for n in a if n in b and a[n] != b[n]]
     missing = [n for n in a if n not in b]
     new = [n for n in b if n not in a]

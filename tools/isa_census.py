@@ -23,7 +23,7 @@ import sys
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "rtcuda_amd", "csrc")
 FLAGS = "--offload-arch=gfx950 -O2 -std=c++17 -ffp-contract=off -fno-fast-math -fno-slp-vectorize -fPIC -Wno-unused-function -Wno-unused-result".split()
-DEFAULT = "_Z18k_paths_chunked_bgILb1ELb1ELi4ELb0ELb0ELb1EE"   # k_paths_chunked_bg<true, true, 4, false, false, true>
+DEFAULT = "_Z7k_pathsI14PathsChunkedBgLb1ELb1ELi4ELb0ELb0ELb1EE"   # k_paths<PathsChunkedBg, true, true, 4, false, false, true>
 
 CATS = [
     ("int xor/shift/add/logic (XORWOW, bit tricks, addresses)", r"^v_(xor|lshlrev|lshrrev|ashrrev|add_u32|sub_u32|subrev_u32|add3_u32|lshl_add_u32|xad_u32|and|or|or3|and_or|bfe|bfi|not|mul_u32_u24|mul_lo_u32|mad_u32_u24|mad_u64_u32|mul_hi_u32|add_co|addc_co|sub_co|subb_co|lshl_or|alignbit|perm|min_u32|max_u32|min_i32|max_i32|add_lshl|xor3|mbcnt|bcnt)"),

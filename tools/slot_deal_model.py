@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""A CPU MODEL (not a measurement) of k_paths_chunked's deal of a workgroup's slots to its lanes, to price a change to the
+"""A CPU MODEL (not a measurement) of k_paths<PathsChunked>'s deal of a workgroup's slots to its lanes, to price a change to the
 deal before it is built: the protocol of rtcuda_amd/csrc/rt_slot_chunks.h played for one workgroup in simulated time.
 
 The model: 256 lanes and `sets` x 256 chains of `rays` camera rays; a ray's cost is gamma distributed with coefficient of
