@@ -27,14 +27,19 @@ def events_of(st):
             "emission_adds": st["emission_adds"], "shadow_adds": st["ah_adds"], "rr_draws": st["rr_draws"]}
 
 
-def sample_frames(oracle, osc, tag, w, h, S, max_bounces=10, seed=1):
+def _camera(oracle, w, h, cam):
+    """The 12 floats of the frame's camera: `cam`, or the default view where it is None."""
+    return default_camera(oracle, w / h) if cam is None else np.ascontiguousarray(cam, np.float32)
+
+
+def sample_frames(oracle, osc, tag, w, h, S, max_bounces=10, seed=1, cam=None):
     """[frame_k for k in range(S)]: (w * h, 3) int64 sums of sample k of every pixel; computed once per argument tuple, read-only."""
-    key = (tag, w, h, S, max_bounces, seed)
+    key = (tag, w, h, S, max_bounces, seed, None if cam is None else _camera(oracle, w, h, cam).tobytes())
     if key not in _frames:
         out = []
         for k in range(S):
             f = np.zeros((h, w, 3), np.int64)
-            osc.render(default_camera(oracle, w / h), w, h, S, max_bounces=max_bounces, seed=seed, threads=usable_cpus(), fixed_out=f,
+            osc.render(_camera(oracle, w, h, cam), w, h, S, max_bounces=max_bounces, seed=seed, threads=usable_cpus(), fixed_out=f,
                        rng_mode="per_sample", shard=(k, S))
             f = f.reshape(-1, 3)
             f.setflags(write=False)
@@ -50,21 +55,22 @@ def _maps(w, h, first, count):
     return first, count
 
 
-def expected_by_frames(oracle, osc, tag, w, h, S, first, count, max_bounces=10, seed=1):
+def expected_by_frames(oracle, osc, tag, w, h, S, first, count, max_bounces=10, seed=1, cam=None):
     """(w * h, 3) int64 sums of the counted frame, by masking the sample frames."""
     first, count = _maps(w, h, first, count)
     assert (count >= 0).all() and (first >= 0).all() and (first + count <= S).all()
     want = np.zeros((w * h, 3), np.int64)
-    for k, f in enumerate(sample_frames(oracle, osc, tag, w, h, S, max_bounces, seed)):
+    for k, f in enumerate(sample_frames(oracle, osc, tag, w, h, S, max_bounces, seed, cam)):
         mask = (first <= k) & (k < first + count)
         want += f * mask[:, None]
     return want
 
 
-def expected_by_tables(oracle, osc, w, h, S, first, count, max_bounces=10, seed=1):
-    """((w * h, 3) int64 sums, the six event totals) of the counted frame, one keyed table per pixel run."""
+def expected_by_tables(oracle, osc, w, h, S, first, count, max_bounces=10, seed=1, cam=None):
+    """((w * h, 3) int64 sums, the six event totals) of the counted frame, one keyed table per pixel run.  `cam`: the frame's
+    camera (12 floats) where it is not the default view."""
     first, count = _maps(w, h, first, count)
-    cam = default_camera(oracle, w / h)
+    cam = _camera(oracle, w, h, cam)
     want = np.zeros((w * h, 3), np.int64)
     ev = {k: 0 for k in KEYS}
     for p in np.flatnonzero(count > 0):

@@ -7,6 +7,9 @@ with the reference's literal walk behind it (rt_hostwalk_trace_verified).  And t
 inside each of its edges that lies inside the frame some ray hits.
 
 The rays are formed as the kernels form them (gen_camera_ray / camera_get_ray of rt_device.h), in fp32, operation by operation.
+
+The last three tests take their inputs from tests/background_views.py -- oblique, rolled, near and far views, the scene scaled,
+shifted and stretched, the scene moved under a fixed camera -- which tests/test_gpu_background_views.py renders on the device.
 """
 import ctypes
 import functools
@@ -15,6 +18,7 @@ import os
 import numpy as np
 import pytest
 
+import background_views as bv
 from conftest import ROOT, default_camera
 from test_traversal_audit import HostWalk
 
@@ -220,3 +224,103 @@ def test_exported_function_refuses_bad_frames(oracle):
         assert (out == -7).all()
     out = np.full(4, -7, np.int32)
     assert lib.rt_background_rect(None, 8, 8, lo.ctypes.data, hi.ctypes.data, out.ctypes.data) == 1
+
+
+# ---- other views, placed scenes, moved scenes (tests/background_views.py; the device side: tests/test_gpu_background_views.py)
+def check_spare_pixel(walk, cam, w, h, r, seed):
+    """Step (3) of the chain in rt_background.h: the rectangle is floor(u0 width) - 1 .. ceil(u1 width) + 1, one whole pixel wider on
+    every side than the pixels the inflated bounds project to, against errors of about 1e-6 of a pixel.  So the outermost column
+    or row inside each edge that lies inside the frame is spare: no ray through it hits, under either walk.  (A rectangle one
+    pixel narrower still keeps the guarantee at these inputs; the spare pixel is what tells it from the one the chain asks for.)"""
+    x0, y0, x1, y1 = r
+    if x1 <= x0:
+        return
+    rng = np.random.default_rng(seed)
+    yy, xx = np.mgrid[y0:y1, x0:x1]
+    strips = {"left": (x0 > 0, xx == x0), "right": (x1 < w, xx == x1 - 1), "top": (y0 > 0, yy == y0), "bottom": (y1 < h, yy == y1 - 1)}
+    for name, (in_frame, strip) in strips.items():
+        if in_frame:
+            a = jittered(xx[strip].astype(np.int32), yy[strip].astype(np.int32), rng, 8)
+            for verified in (False, True):
+                got = hits(walk, cam, w, h, *a, verified=verified)
+                assert not got.any(), (r, name, "verified" if verified else "product", int(got.sum()))
+
+
+# What a view is in the table for, at 320 x 180 and at 97 x 131, stated on the computed rectangle r = (x0, y0, x1, y1).
+_VIEW_PROPERTY = {
+    ("oblique", 320): bv.strictly_inside, ("wide_fov", 320): bv.strictly_inside, ("from_above", 320): bv.strictly_inside,
+    ("rolled_oblique", 320): bv.strictly_inside,
+    ("rolled", 320): lambda r, w, h: r[1] == 0 and r[3] == h and 0 < r[0] and r[2] < w,
+    ("scene_left", 320): lambda r, w, h: r[0] == 0 and r[2] < w,
+    ("far_narrow", 320): lambda r, w, h: r[3] == h and r[1] > 0,
+    ("thin_column", 320): lambda r, w, h: r[0] == 0 and 0 < r[2] <= 12,
+    ("thin_column", 97): lambda r, w, h: bv.empty(r),
+    ("rolled", 97): bv.whole, ("scene_left", 97): bv.whole,
+}
+
+
+@pytest.mark.parametrize("w,h", [(320, 180), (97, 131)])
+@pytest.mark.parametrize("view", list(bv.VIEWS))
+def test_other_views(oracle, bunny_full_bsdf, walk_c2, view, w, h):
+    """Oblique, rolled, near and far cameras: rectangles with rows cut off, at the frame's first column and last row, a few
+    columns wide, empty, and the whole frame."""
+    cam = bv.view_camera(oracle.camera, view, w / h)
+    r = check_rectangle(walk_c2, cam, w, h, *bounds(bunny_full_bsdf), seed=4, n_random_pixels=20_000)
+    print(view, (w, h), r)
+    assert r == bv.rectangle(cam, w, h, bunny_full_bsdf)
+    check_spare_pixel(walk_c2, cam, w, h, r, seed=14)
+    holds = _VIEW_PROPERTY.get((view, w))
+    assert holds is None or holds(r, w, h), (view, w, h, r)
+
+
+_placed_walks = {}
+
+
+def _placed_walk(arrays, place):
+    if place not in _placed_walks:
+        moved = bv.placed(arrays, place)
+        _placed_walks[place] = (moved, HostWalk(moved))
+    return _placed_walks[place]
+
+
+_PLACE_PROPERTY = {
+    "shift_300": bv.whole, "stretch_x_1e3": bv.whole,
+    "squash_y_1e-3": lambda r, w, h: 0 < r[3] - r[1] <= 6,
+    "stretch_z_50_shift": lambda r, w, h: 0 < r[2] - r[0] <= 10 and 0 < r[3] - r[1] <= 10,
+}
+
+
+@pytest.mark.parametrize("view", list(bv.PLACED_VIEWS))
+@pytest.mark.parametrize("place", list(bv.PLACES))
+def test_placed_scenes(oracle, bunny_full_bsdf, place, view):
+    """The scene scaled, shifted and stretched, the camera moved with it: the margin terms of step (1) of the chain -- 1e-4 of
+    the extent, 2^-22 R, 2^-20 |bound|, 2^-17 D -- away from the unit scene, where each was sized."""
+    w, h = 320, 180
+    moved, walk = _placed_walk(bunny_full_bsdf, place)
+    cam = bv.placed_view(oracle.camera, place, view, w / h)
+    r = check_rectangle(walk, cam, w, h, *bounds(moved), seed=5, n_random_pixels=20_000)
+    print(place, view, r)
+    check_spare_pixel(walk, cam, w, h, r, seed=15)
+    holds = _PLACE_PROPERTY.get(place, lambda r, w, h: 0 < bv.area(r) < w * h)
+    assert holds(r, w, h), (place, view, r)
+
+
+_MOVE_PROPERTY = {
+    "right_0.6": lambda r, w, h: 35 < r[0] and r[2] == w and r[1] == 0 and r[3] == h,
+    "half": bv.strictly_inside,
+    "up_left": lambda r, w, h: r[0] == 0 and r[1] == 0 and r[2] < 125 and r[3] < h,
+    "double": bv.whole,
+}
+
+
+@pytest.mark.parametrize("move", list(bv.MOVES))
+def test_moved_scenes(oracle, bunny_full_bsdf, move):
+    """The scene moved under the fixed default camera (what update(), rebuild() and set_triangles() do to a scene on the device):
+    rectangles that end at the last column, start at the first column and row, and lie inside the old one."""
+    w, h = 160, 90
+    moved = bv.moved(bunny_full_bsdf, move)
+    walk = HostWalk(moved)
+    r = check_rectangle(walk, default_camera(oracle, w / h), w, h, *bounds(moved), seed=6, n_random_pixels=20_000)
+    print(move, r)
+    check_spare_pixel(walk, default_camera(oracle, w / h), w, h, r, seed=16)
+    assert _MOVE_PROPERTY[move](r, w, h), (move, r)

@@ -83,13 +83,14 @@ def _same_as_rounds(got, st, rnd, st_rnd, spp, max_bounces, what):
     assert not rnd[got == 0].any() and not got[rnd == 0].any(), what  # (a pixel nothing reaches is exactly zero in both)
 
 
-def _expect_skip(api, w, h, cam=None):
+def _expect_skip(api, w, h, cam=None, arrays=None):
     """Whether the frame's persistent launch must be a skipping build: the rectangle rt_background_rect gives for the camera and
     the scene's bounds (the library computes it from the root's child boxes, 2 ulps wider: the same pixels in these frames) is
-    smaller than the frame.  Every frame of this file has background, so every one must take the skipping kernel."""
+    smaller than the frame.  Every frame of this file has background, so every one must take the skipping kernel.  `arrays`: the
+    scene's, where it is not the full-BSDF bunny."""
     from test_background_rect_host import bounds, rect
     cam = api.make_camera(aspect=w / h) if cam is None else cam
-    x0, y0, x1, y1 = rect(cam, w, h, *bounds(_arrays()))
+    x0, y0, x1, y1 = rect(cam, w, h, *bounds(_arrays() if arrays is None else arrays))
     return (x1 - x0) * (y1 - y0) < w * h
 
 
@@ -103,15 +104,15 @@ def _arrays():
     return _arrays_cache[0]
 
 
-def _on_off(api, gpu, monkeypatch, w, h, spp, want=None, st_c=None, rounds=False, **kw):
+def _on_off(api, gpu, monkeypatch, w, h, spp, want=None, st_c=None, rounds=False, arrays=None, **kw):
     """The frame with the skip on (the default), held to the oracle's frame if given, and to RT_BG_SKIP=0; `rounds`: and to the
     round pipeline.  The skipping frame's persistent launch must have been k_paths<PathsBg> / k_paths<PathsChunkedBg>
     (st["background_skip"]; without that the comparisons below would hold trivially), the RT_BG_SKIP=0 frame's and the rounds' not.
-    Returns the frame."""
+    `arrays`: what `gpu` holds, where it is not the full-BSDF bunny.  Returns the frame."""
     what = (w, h, spp, tuple(sorted(kw.items(), key=lambda t: t[0])) if "cam" not in kw else "cam")
     _knobs(monkeypatch)
     got, st = _sums(api, gpu, w, h, spp, **kw)
-    assert _expect_skip(api, w, h, kw.get("cam")), what
+    assert _expect_skip(api, w, h, kw.get("cam"), arrays), what
     assert st["background_skip"] == 1, (what, "the frame did not run a skipping kernel")
     if want is not None:
         _check(got, st, want, st_c, f"skip on {what}")
@@ -130,7 +131,9 @@ def _on_off(api, gpu, monkeypatch, w, h, spp, want=None, st_c=None, rounds=False
     return got, st
 
 
-# 160 x 90 x 256: 3.5 generations, the rectangle's four edges inside the frame.  96 x 54 x 509: an odd spp (no pixel stepping:
+# 160 x 90 x 256: 3.5 generations; the rectangle is columns 35 .. 124 of every row, (35, 0, 125, 90): its left and right edges lie
+# inside the frame, its top and bottom edges are the frame's (at no size of this file is a row skipped: the views that cut rows off,
+# start at column 0 or end at the last row are in test_gpu_background_views.py).  96 x 54 x 509: an odd spp (no pixel stepping:
 # the division path).  200 x 120 x 16 and 640 x 360 x 16 (3.5 generations): a wave's 64 slots span four pixels, so lanes of one
 # wave stand on both sides of an edge.
 @pytest.mark.parametrize("w,h,spp", [(160, 90, 256), (96, 54, 509), (200, 120, 16), (640, 360, 16)])

@@ -29,15 +29,17 @@ def gpu(api):
 
 
 def _skipping(api, gpu, monkeypatch, w, h, spp, chunk, head, **kw):
-    """The frame with the skip on and with RT_BG_SKIP=0 under the same deal; both must report the deal, the first the skip."""
+    """The frame with the skip on and with RT_BG_SKIP=0 under the same deal; both must report the deal, the first the skip.
+    chunk None: no RT_SLOT_CHUNK, the launch plan's own deal, whatever it is -- the same in both frames."""
     _knobs(monkeypatch, chunk=chunk, head=head)
     got, st = _sums(api, gpu, w, h, spp, **kw)
     assert _expect_skip(api, w, h, kw.get("cam"))
     assert st["background_skip"] == 1, "the frame did not run a skipping kernel"
-    assert st["slot_chunk"] == chunk, (st["slot_chunk"], chunk)
+    dealt = st["slot_chunk"] if chunk is None else chunk
+    assert st["slot_chunk"] == dealt, (st["slot_chunk"], chunk)
     _knobs(monkeypatch, skip=False, chunk=chunk, head=head)
     off, st_off = _sums(api, gpu, w, h, spp, **kw)
-    assert st_off["background_skip"] == 0 and st_off["slot_chunk"] == chunk
+    assert st_off["background_skip"] == 0 and st_off["slot_chunk"] == dealt
     _knobs(monkeypatch)
     _same(got, st, off, st_off, ("skip on / off", chunk, head))
     return got, st
