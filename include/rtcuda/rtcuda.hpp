@@ -672,6 +672,29 @@ inline void denoise_variance(const int64_t *d_sum_fixed, int num_samples, const 
                                                    d_scratch, d_rgb_out, stream), "denoise_variance");
 }
 
+// AOV-guided upsampling (rt_upsample_fixed / rt_upsample_rgb, which document the filter): a low_width x low_height beauty frame
+// -- fixed-point sums, or float linear mean radiance -- with its AOV sums, and the AOV sums of the same rt_camera at factor (2, 3
+// or 4) times the width and the height, all DEVICE buffers, become the full-size frame: d_rgb_out (3 floats per pixel, linear
+// mean radiance) and / or d_out_fixed (3 int64 per pixel, sums of ONE sample: what denoise(..., 1, ...), denoise_variance and the
+// accumulators take).  One of the two outputs may be nullptr.  No scratch.  params = nullptr: the library's defaults.
+inline rt_upsample_params upsample_default_params() {
+    rt_upsample_params p{};
+    rtcuda_detail::check(rt_upsample_default_params(&p), "upsample_default_params");
+    return p;
+}
+inline void upsample(const int64_t *d_sum_lo, int num_samples, const int64_t *d_aov_lo, int aov_samples_lo, int low_width, int low_height,
+                     int factor, const int64_t *d_aov_hi, int aov_samples_hi, float *d_rgb_out, int64_t *d_out_fixed,
+                     const rt_upsample_params *params = nullptr, void *stream = nullptr) {
+    rtcuda_detail::check(rt_upsample_fixed(d_sum_lo, num_samples, d_aov_lo, aov_samples_lo, low_width, low_height, factor, d_aov_hi,
+                                           aov_samples_hi, params, d_rgb_out, d_out_fixed, stream), "upsample");
+}
+inline void upsample_rgb(const float *d_rgb_lo, const int64_t *d_aov_lo, int aov_samples_lo, int low_width, int low_height, int factor,
+                         const int64_t *d_aov_hi, int aov_samples_hi, float *d_rgb_out, int64_t *d_out_fixed,
+                         const rt_upsample_params *params = nullptr, void *stream = nullptr) {
+    rtcuda_detail::check(rt_upsample_rgb(d_rgb_lo, d_aov_lo, aov_samples_lo, low_width, low_height, factor, d_aov_hi, aov_samples_hi, params,
+                                         d_rgb_out, d_out_fixed, stream), "upsample_rgb");
+}
+
 // A driver that must keep the reference's exact call (main.cu:173) can still reach several GPUs: RTCUDA_DEVICES="0,1,2,3" in
 // the environment sends the seven-argument render() below through the multi-device path (rt_render_multi).
 inline std::vector<int> devices_from_env() {

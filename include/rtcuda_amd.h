@@ -863,6 +863,67 @@ int rt_denoise_variance_fixed(const int64_t *d_sum_fixed, int num_samples, const
                               const rt_denoise_dual_params *params /* NULL = rt_denoise_dual_fixed's defaults */,
                               void *d_scratch /* rt_denoise_dual_scratch_bytes */, float *d_rgb_out /* width * height * 3 */, void *stream);
 
+/* ---- AOV-guided upsampling: a low-resolution frame and full-resolution features become a full-resolution frame -----------------
+ * The beauty frame is where the time goes and its feature buffers are noise-free at any sample count, so a path-tracing budget
+ * is spent best on radiance at half or quarter resolution and on features at full resolution (no reference counterpart).  This is
+ * the call that joins the two: joint bilateral upsampling (Kopf et al. 2007) on albedo-demodulated radiance, as SVGF-style
+ * pipelines do it.  The loop is
+ *   rt_render_shard_fixed (low size)  +  rt_render_aov_fixed (low size)  +  rt_render_aov_fixed (full size), one rt_camera
+ *       -> rt_upsample_fixed(sum_lo, spp, aov_lo, ..., aov_hi, ..., d_rgb_out, d_out_fixed)
+ *       -> rt_denoise_fixed(d_out_fixed, 1, aov_hi, ...) | rt_denoise_variance_fixed | a temporal accumulator
+ * and rt_upsample_rgb takes a float frame in the place of the sums, for example a denoiser's output at the low size.  The full
+ * frame is width = factor * low_width by height = factor * low_height -- exactly the case in which a pinhole frame of the same
+ * rt_camera covers the same frustum at both sizes.  factor is 2, 3 or 4.
+ * Like rt_denoise_fixed the whole filter is ONE STATED SEQUENCE of individually rounded fp32 operations (no FMA, sums start at
+ * 0.f, "x > t ? x : t" is that selection): the kernel, the CPU twin (hc_upsample of librt_hostcheck.so) and the numpy restatement
+ * of the tests agree in every bit of every pixel.
+ *   1. LOW PIXEL q.  Steps 1 and 2 of rt_denoise_fixed for (d_sum_lo[q], num_samples) and (d_aov_lo[q], aov_samples_lo) give
+ *      u_q, z_q, n_q.  In rt_upsample_rgb c is the given float, and a c that is NaN or infinite is taken as 0.f (so that no
+ *      0 * inf can arise); everything after c is the same text.  (A finite c of 2^118 or more can still overflow u over the
+ *      albedo floor 2^-10; the output of such a frame is undefined.  Radiance this renderer forms stays below 2^31.)
+ *   2. FULL PIXEL p = (x, y).  z_p, n_p, d_p, e_p are exactly those steps' for d_aov_hi[p] and aov_samples_hi.  If the hits
+ *      channel of d_aov_hi[p] is <= 0, u_p = 0 on every channel and no tap is visited: a pixel no sample hit has no radiance in
+ *      this renderer.
+ *   3. POSITION, per axis, in integers: a = 2 * x + 1 - factor; X0 = floor(a / (2 * factor)), rounding toward minus infinity;
+ *      r = a - 2 * factor * X0; fx = float(r) / float(2 * factor), a true division.  The same in y (Y0, fy).
+ *   4. TAPS.  jy outer and jx inner, both from -1 to 2; the low pixel is (X0 + jx, Y0 + jy); a tap outside the low image is
+ *      skipped.  t = float(j) - f; k = 1.f - 0.5f * (t < 0 ? -t : t); h = ky * kx: a tent of radius 2.  At least one tap with
+ *      k >= 0.5 lies inside the image on each axis, so the sum of h is positive.
+ *      w = (h * rt_expnegf(-x_z)) * w_n, rt_denoise_fixed's tap weight with both colour arguments equal and kc = 0 (its colour
+ *      term is exactly +0): x_z = (dz * dz) * kz, dz = z_q - z_p, kz = 1.f / (sigma_depth * sigma_depth) made on the host, w_n
+ *      from n_p . n_q clamped to 0 .. 1 and squared normal_power_log2 times.
+ *      Four running sums in tap order: sw = sw + w, su = su + w * u_q, sh = sh + h, sb = sb + h * u_q.
+ *   5. RESULT.  u_p = sw > 0.f ? su / sw : sb / sh per channel.  The second form is the plain tent filter: it serves a pixel
+ *      whose features no low tap shares, a thin edge for example.
+ *   6. REMODULATE with the full-resolution features: out = u_p * d_p + e_p per channel, LINEAR MEAN RADIANCE, what the
+ *      denoisers write.  d_out_fixed is the accumulators' to_fixed of it (magnitudes clamped to 2^31, NaN to 0, units of 2^-30,
+ *      round to nearest even): int64 sums of ONE sample of the mean, the format the accumulators emit, so rt_denoise_fixed(out, 1,
+ *      aov_hi, ...), rt_denoise_variance_fixed and both accumulators take an upsampled frame unchanged.
+ * rt_upsample_params: NULL = the defaults, which rt_upsample_default_params writes (profiles/upsample_quality.json).
+ * No scratch is needed.  rt_render_aov_follow_fixed's buffers have the same layout and may be passed as either feature buffer.
+ * The contract is the denoisers': device buffers on the current device, ordered on `stream` and synchronous on it at return, the
+ * current device left as it was, nothing allocated, inputs only read, every pixel of each non-null output written; outputs
+ * that overlap inputs are undefined.  ERRORS return non-zero, begin "rt_upsample_fixed: " / "rt_upsample_rgb: " in
+ * rt_last_error() and write nothing: a null pointer other than params and ONE of the two outputs (both null is an error);
+ * factor outside 2 .. 4; a low size below 1, or a full frame of more than 715827882 pixels; a sample count below 1;
+ * normal_power_log2 outside 0 .. 8; a sigma_depth that is not finite and positive, or whose kz is not; flags != 0; a full frame
+ * that would need more than 16777215 workgroups of 32 x 8 pixels. */
+typedef struct rt_upsample_params {
+    float   sigma_depth;        /* > 0; scene units */
+    int32_t normal_power_log2;  /* 0 .. 8: w_n = min(max(0, n_p . n_q), 1) squared this many times */
+    uint32_t flags;             /* must be 0 */
+} rt_upsample_params;
+int rt_upsample_default_params(rt_upsample_params *out);
+int rt_upsample_fixed(const int64_t *d_sum_lo /* low_width * low_height * 3 */, int num_samples,
+                      const int64_t *d_aov_lo /* low_width * low_height * 11 */, int aov_samples_lo, int low_width, int low_height,
+                      int factor, const int64_t *d_aov_hi /* factor^2 * low_width * low_height * 11 */, int aov_samples_hi,
+                      const rt_upsample_params *params /* NULL = defaults */, float *d_rgb_out /* full size * 3, may be NULL */,
+                      int64_t *d_out_fixed /* full size * 3, may be NULL */, void *stream);
+int rt_upsample_rgb(const float *d_rgb_lo /* low_width * low_height * 3, linear mean radiance, e.g. a denoiser's output */,
+                    const int64_t *d_aov_lo, int aov_samples_lo, int low_width, int low_height, int factor,
+                    const int64_t *d_aov_hi, int aov_samples_hi, const rt_upsample_params *params /* NULL = defaults */,
+                    float *d_rgb_out /* may be NULL */, int64_t *d_out_fixed /* may be NULL */, void *stream);
+
 /* ---- ray queries (no reference counterpart: its Bvh::traverse is reachable only from render()) ----------------------------
  * "Trace my rays, from my buffers, on my stream."  All pointers are DEVICE buffers on the scene's device (a buffer on another
  * device or on the host cannot be told apart from a good one: the call faults instead of failing); origins and directions are

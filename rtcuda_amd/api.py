@@ -46,6 +46,7 @@ EXPORTS = [
     "rt_denoise_dual_scratch_bytes", "rt_denoise_dual_default_params", "rt_denoise_dual_fixed",
     "rt_render_motion", "rt_temporal_default_params", "rt_temporal_accumulate_fixed",
     "rt_temporal_moments_default_params", "rt_temporal_accumulate_moments_fixed", "rt_denoise_variance_fixed",
+    "rt_upsample_default_params", "rt_upsample_fixed", "rt_upsample_rgb",
     "rt_xorwow_states", "rt_shutdown", "rt_peer_access_log", "rt_last_error", "rt_version", "rt_build_id",
 ]
 # the lab (include/rtcuda_amd_tools.h, librtcuda_amd_tools.so): measurement tools, not part of the drop-in C-ABI
@@ -89,6 +90,10 @@ class RtDenoiseParams(ctypes.Structure):
 class RtDenoiseDualParams(ctypes.Structure):
     _fields_ = [("passes", ctypes.c_int32), ("sigma_variance", ctypes.c_float), ("sigma_depth", ctypes.c_float),
                 ("normal_power_log2", ctypes.c_int32), ("flags", ctypes.c_uint32)]
+
+
+class RtUpsampleParams(ctypes.Structure):
+    _fields_ = [("sigma_depth", ctypes.c_float), ("normal_power_log2", ctypes.c_int32), ("flags", ctypes.c_uint32)]
 
 
 class RtTemporalParams(ctypes.Structure):
@@ -216,6 +221,9 @@ def _bind(L):
     L.rt_temporal_accumulate_moments_fixed.argtypes = [vp, ci, vp, ci, vp, ci, vp, vp, vp, vp, vp, ci, vp, vp, ci, ci,
                                                        ctypes.POINTER(RtTemporalMomentsParams), vp, vp, vp, vp, vp, vp]
     L.rt_denoise_variance_fixed.argtypes = [vp, ci, vp, vp, ci, ci, ci, ctypes.POINTER(RtDenoiseDualParams), vp, vp, vp]
+    L.rt_upsample_default_params.argtypes = [ctypes.POINTER(RtUpsampleParams)]
+    L.rt_upsample_fixed.argtypes = [vp, ci, vp, ci, ci, ci, ci, vp, ci, ctypes.POINTER(RtUpsampleParams), vp, vp, vp]
+    L.rt_upsample_rgb.argtypes = [vp, vp, ci, ci, ci, ci, vp, ci, ctypes.POINTER(RtUpsampleParams), vp, vp, vp]
     L.rt_trace_closest.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp]
     L.rt_trace_any.argtypes = [vp, ci, vp, vp, vp, vp, vp]
     L.rt_trace_closest_flags.argtypes = [vp, ctypes.c_uint32, ci, vp, vp, vp, vp, vp, vp, vp]
@@ -1335,6 +1343,81 @@ def denoise_variance(beauty_sums, spp: int, variance, aov_sums, aov_spp: int, wi
                                                ctypes.c_void_p(scratch.data_ptr()), ctypes.c_void_p(out.data_ptr()),
                                                ctypes.c_void_p(s.cuda_stream or None)), "rt_denoise_variance_fixed")
     return out
+
+
+def upsample_default_params() -> dict:
+    """The parameters rt_upsample_fixed and rt_upsample_rgb use when they are given none (rt_upsample_default_params)."""
+    prm = RtUpsampleParams()
+    _check(lib().rt_upsample_default_params(ctypes.byref(prm)), "rt_upsample_default_params")
+    return {"sigma_depth": float(prm.sigma_depth), "normal_power_log2": int(prm.normal_power_log2)}
+
+
+def _upsample(me: str, entry: str, low, low_channels_dtype, spp, aov_lo, aov_spp_lo: int, low_width: int, low_height: int, factor: int, aov_hi,
+              aov_spp_hi: int, sigma_depth, normal_power_log2, out, out_fixed, want_rgb: bool, want_fixed: bool, stream):
+    """What upsample and upsample_rgb share: the checks of the tensors, the parameters, the outputs made or checked, the call."""
+    import torch
+    _dn_positive_ints(me, (("low_width", low_width), ("low_height", low_height), ("aov_spp_lo", aov_spp_lo), ("aov_spp_hi", aov_spp_hi)) +
+                      ((("spp", spp),) if spp is not None else ()))
+    if not isinstance(factor, int) or isinstance(factor, bool) or not 2 <= factor <= 4:
+        raise RtError(f"{me}: factor must be 2, 3 or 4, it is {factor!r}")
+    n_lo, n = low_width * low_height, factor * factor * low_width * low_height
+    low_name, low_dtype = low_channels_dtype
+    if low_dtype == torch.int64:
+        device = _dn_sums(me, n_lo, ((low_name, low, 3), ("aov_lo", aov_lo, AOV_CHANNELS)))
+    else:
+        if not isinstance(low, torch.Tensor) or not low.is_cuda:
+            raise RtError(f"{me}: {low_name} must be a torch tensor on a GPU")
+        if low.dtype != torch.float32 or tuple(low.shape) != (n_lo, 3) or not low.is_contiguous():
+            raise RtError(f"{me}: {low_name} must be a contiguous ({n_lo}, 3) torch.float32 tensor, it is {tuple(low.shape)} {low.dtype}")
+        device = _dn_sums(me, n_lo, (("aov_lo", aov_lo, AOV_CHANNELS),))
+        if low.device != device:
+            raise RtError(f"{me}: {low_name} is on {low.device}, aov_lo on {device}")
+    if _dn_sums(me, n, (("aov_hi", aov_hi, AOV_CHANNELS),)) != device:
+        raise RtError(f"{me}: aov_hi is on {aov_hi.device}, aov_lo on {device}")
+    prm = _dn_params(me, RtUpsampleParams(), (("normal_power_log2", normal_power_log2),), (("sigma_depth", sigma_depth),), defaults_of="upsample")
+    if not (want_rgb or want_fixed or out is not None or out_fixed is not None):
+        raise RtError(f"{me}: at least one of the two outputs must be asked for")
+    for name, t, dtype, want in (("out", out, torch.float32, want_rgb), ("out_fixed", out_fixed, torch.int64, want_fixed)):
+        if t is not None:
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != device:
+                raise RtError(f"{me}: {name} must be a torch tensor on the GPU of the inputs")
+            if t.dtype != dtype or tuple(t.shape) != (n, 3) or not t.is_contiguous():
+                raise RtError(f"{me}: {name} must be a contiguous ({n}, 3) {dtype} tensor, it is {tuple(t.shape)} {t.dtype}")
+    if out is None and want_rgb:
+        out = torch.empty((n, 3), dtype=torch.float32, device=device)
+    if out_fixed is None and want_fixed:
+        out_fixed = torch.empty((n, 3), dtype=torch.int64, device=device)
+    s = torch.cuda.current_stream(device) if stream is None else stream
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    head = (ptr(low),) + ((spp,) if spp is not None else ())
+    with torch.cuda.device(device):
+        _check(getattr(lib(), entry)(*head, ptr(aov_lo), aov_spp_lo, low_width, low_height, factor, ptr(aov_hi), aov_spp_hi, ctypes.byref(prm),
+                                     ptr(out), ptr(out_fixed), ctypes.c_void_p(s.cuda_stream or None)), entry)
+    return out, out_fixed
+
+
+def upsample(beauty_lo, spp: int, aov_lo, aov_spp_lo: int, low_width: int, low_height: int, factor: int, aov_hi, aov_spp_hi: int, *,
+             sigma_depth=None, normal_power_log2=None, out=None, out_fixed=None, rgb=True, fixed=True, stream=None):
+    """A full-resolution frame from a LOW-RESOLUTION beauty frame and FULL-RESOLUTION features (rt_upsample_fixed: joint bilateral
+    upsampling of albedo-demodulated radiance, guided by first-hit normal and depth).  ``beauty_lo``: (low_height * low_width, 3)
+    int64 sums of ``spp`` samples; ``aov_lo``: the (low_height * low_width, 11) int64 AOV sums of the same view at the low size;
+    ``aov_hi``: those at ``factor`` (2, 3 or 4) times the width and the height, same camera.  Returns ``(out, out_fixed)``: the
+    (n, 3) float32 LINEAR mean radiance and the (n, 3) int64 sums of ONE sample of it, which denoise(out_fixed, 1, aov_hi, ...),
+    denoise_variance and the temporal accumulators take; ``rgb=False`` / ``fixed=False`` leaves one of them out (None in its
+    place), ``out`` / ``out_fixed`` are tensors to fill.  Parameters left at None are the library's defaults
+    (upsample_default_params); ``stream``: a torch.cuda.Stream (the current one otherwise)."""
+    import torch
+    return _upsample("upsample", "rt_upsample_fixed", beauty_lo, ("beauty_lo", torch.int64), spp, aov_lo, aov_spp_lo, low_width, low_height, factor,
+                     aov_hi, aov_spp_hi, sigma_depth, normal_power_log2, out, out_fixed, rgb, fixed, stream)
+
+
+def upsample_rgb(rgb_lo, aov_lo, aov_spp_lo: int, low_width: int, low_height: int, factor: int, aov_hi, aov_spp_hi: int, *, sigma_depth=None,
+                 normal_power_log2=None, out=None, out_fixed=None, rgb=True, fixed=True, stream=None):
+    """``upsample`` of a FLOAT frame (rt_upsample_rgb): ``rgb_lo`` is (low_height * low_width, 3) float32 linear mean radiance, a
+    denoiser's output at the low size for example; a value that is NaN or infinite counts as 0.  Everything else is upsample's."""
+    import torch
+    return _upsample("upsample_rgb", "rt_upsample_rgb", rgb_lo, ("rgb_lo", torch.float32), None, aov_lo, aov_spp_lo, low_width, low_height, factor,
+                     aov_hi, aov_spp_hi, sigma_depth, normal_power_log2, out, out_fixed, rgb, fixed, stream)
 
 
 def xorwow_states(seed: int, first: int, count: int, draws: int = 0):

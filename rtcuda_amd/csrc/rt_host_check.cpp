@@ -18,6 +18,7 @@
 //   * rt_background_rect  the pixel rectangle outside which k_paths makes no camera ray (rt_background.h), as the library computes it.
 //   * hc_denoise / hc_expnegf  the CPU twin of rt_denoise_fixed: a serial loop over rt_denoise.h, the arithmetic of the kernels.
 //   * hc_denoise_dual   the CPU twin of rt_denoise_dual_fixed, likewise; both walk the pixels with dn_walk, the twins' own loop.
+//   * hc_upsample       the CPU twin of rt_upsample_fixed and rt_upsample_rgb: a serial loop over rt_upsample.h.
 //   * hc_merge_shard_stats  the merge of the shards' rt_stats (rt_stats_merge.h), the library's own function.
 #include <cfloat>
 #include <cmath>
@@ -36,6 +37,7 @@
 #include "rt_slot_chunks.h"
 #include "rt_stats_merge.h"
 #include "rt_temporal.h"
+#include "rt_upsample.h"
 
 namespace {
 struct V3 { float x, y, z; };
@@ -1209,6 +1211,45 @@ int hc_denoise_variance(const int64_t *sum_fixed, int num_samples, const float *
         dn_finish(&uv[4 * p], px[p].d, px[p].e, rgb_out + 3 * p);
         if (var_out) var_out[p] = uv[4 * p + 3];
     }
+    return 0;
+}
+// The CPU twin of rt_upsample_fixed (sum_lo) and rt_upsample_rgb (rgb_lo; exactly one of the two is given) (tests/test_upsample_host.py,
+// tools/upsample_quality.py): a serial loop over rt_upsample.h, host buffers throughout, the same checks of the parameters.
+// rgb_out, out_fixed: at least one; form_out (may be null): UP_GUIDED / UP_TENT / UP_SHORTCUT per full pixel.  Returns 0, or 1 and
+// writes nothing.
+int hc_upsample(const int64_t *sum_lo, const float *rgb_lo, int num_samples, const int64_t *aov_lo, int aov_samples_lo, int low_width,
+                int low_height, int factor, const int64_t *aov_hi, int aov_samples_hi, float sigma_depth, int normal_power_log2, float *rgb_out,
+                int64_t *out_fixed, uint8_t *form_out) {
+    if ((sum_lo != nullptr) == (rgb_lo != nullptr) || !aov_lo || !aov_hi || (!rgb_out && !out_fixed)) return 1;
+    if (factor < UP_MIN_FACTOR || factor > UP_MAX_FACTOR || low_width < 1 || low_height < 1) return 1;
+    if ((long long)low_width * low_height > (0x7fffffff / 3) / ((long long)factor * factor)) return 1;
+    if ((sum_lo && num_samples < 1) || aov_samples_lo < 1 || aov_samples_hi < 1) return 1;
+    if (normal_power_log2 < 0 || normal_power_log2 > DN_MAX_NORMAL_POWER_LOG2 || !(std::isfinite(sigma_depth) && sigma_depth > 0.f)) return 1;
+    const float sd2 = sigma_depth * sigma_depth;
+    const float kz = 1.f / sd2;
+    if (!(std::isfinite(kz) && kz > 0.f)) return 1;
+    const float inv_spp = 1.f / (float)num_samples, inv_lo = 1.f / (float)aov_samples_lo, inv_hi = 1.f / (float)aov_samples_hi;
+    const size_t n_lo = (size_t)low_width * (size_t)low_height;
+    std::vector<UpLow> lo(n_lo);
+    for (size_t q = 0; q < n_lo; q++) {
+        if (sum_lo)
+            up_low_of_sums(sum_lo + 3 * q, aov_lo + DN_AOV_CHANNELS * q, inv_spp, inv_lo, &lo[q]);
+        else
+            up_low_of_rgb(rgb_lo + 3 * q, aov_lo + DN_AOV_CHANNELS * q, inv_lo, &lo[q]);
+    }
+    const int width = factor * low_width, height = factor * low_height;
+    for (int y = 0; y < height; y++)
+        for (int x = 0; x < width; x++) {
+            const size_t p = (size_t)y * (size_t)width + (size_t)x;
+            float out[3];
+            const int form = up_full_pixel(x, y, factor, low_width, low_height, aov_hi + DN_AOV_CHANNELS * p, inv_hi, kz, normal_power_log2,
+                                           [&](int qx, int qy, UpLow *q) { *q = lo[(size_t)qy * (size_t)low_width + (size_t)qx]; }, out);
+            for (int k = 0; k < 3; k++) {
+                if (rgb_out) rgb_out[3 * p + k] = out[k];
+                if (out_fixed) out_fixed[3 * p + k] = tm_to_fixed(out[k]);
+            }
+            if (form_out) form_out[p] = (uint8_t)form;
+        }
     return 0;
 }
 // The stats of a frame from its n shards' (rt_stats_merge.h), as RT_SPLIT (sub_shards != 0) and rt_render_multi merge them

@@ -234,3 +234,50 @@ int denoise_variance_impl(const int64_t *d_sum_fixed, int num_samples, const flo
                                (const long long *)d_aov_fixed, n, inv_spp, inv_aov, d_rgb_out);
         });
 }
+
+// ---- rt_upsample_fixed / rt_upsample_rgb: dn_check's checks, no scratch, no passes, one launch (kernel: rt_upsample_kernels.inc)
+rt_upsample_params upsample_defaults() {
+    rt_upsample_params p{};
+    p.sigma_depth = 0.03125f;  // (the sweep of tools/upsample_quality.py: profiles/upsample_quality.json)
+    p.normal_power_log2 = 5;
+    p.flags = 0u;
+    return p;
+}
+
+// low: d_sum_lo (rgb = false, num_samples its samples) or d_rgb_lo (rgb = true).  What of the sizes dn_check does not know --
+// the factor, the low size, the full frame's pixel count -- is found first and handed to it in the place of the sample fault, so
+// the order is: pointers, factor, sizes, samples, flags, normal_power_log2, sigma_depth.
+int upsample_impl(const std::string &me, bool rgb, const void *low, const char *low_name, int num_samples, const int64_t *d_aov_lo,
+                  int aov_samples_lo, int low_width, int low_height, int factor, const int64_t *d_aov_hi, int aov_samples_hi,
+                  const rt_upsample_params *params, float *d_rgb_out, int64_t *d_out_fixed, hipStream_t stream) {
+    const rt_upsample_params prm = params ? *params : upsample_defaults();
+    const bool factor_ok = factor >= UP_MIN_FACTOR && factor <= UP_MAX_FACTOR, size_ok = low_width >= 1 && low_height >= 1;
+    const char *fault = !factor_ok ? "factor must be 2, 3 or 4"
+                        : !size_ok ? "low_width and low_height must be at least 1"
+                        : (long long)low_width * low_height > kDnMaxPixels / ((long long)factor * factor) ? "more than 715827882 pixels in the full frame"
+                        : num_samples < 1 || aov_samples_lo < 1 || aov_samples_hi < 1 ? (rgb ? "aov_samples_lo and aov_samples_hi must be at least 1"
+                                                                                             : "num_samples, aov_samples_lo and aov_samples_hi must be at least 1")
+                                                                                      : nullptr;
+    if (dn_check(me, !low ? low_name : !d_aov_lo ? "d_aov_lo" : !d_aov_hi ? "d_aov_hi" : !d_rgb_out && !d_out_fixed ? "d_rgb_out and null d_out_fixed" : nullptr,
+                 1, 1, fault, nullptr, prm.flags, 0, prm.normal_power_log2, "sigma_depth", prm.sigma_depth, prm.sigma_depth))
+        return 1;
+    const float sd2 = prm.sigma_depth * prm.sigma_depth;
+    const float kz = 1.f / sd2;
+    if (!(std::isfinite(kz) && kz > 0.f)) return fail(me + "sigma_depth gives a depth constant that is not finite and positive");
+    const int width = factor * low_width, height = factor * low_height;
+    const int tiles_x = (width + kDnTileW - 1) / kDnTileW;
+    const long long blocks = dn_pass_blocks(width, height, 1, 1);
+    if (blocks > kDnMaxBlocks)
+        return fail(me + "a " + std::to_string(width) + " x " + std::to_string(height) +
+                    " frame needs more than 16777215 workgroups (a frame this narrow or this flat is not served)");
+    const float inv_spp = 1.f / (float)num_samples, inv_lo = 1.f / (float)aov_samples_lo, inv_hi = 1.f / (float)aov_samples_hi;
+    using Kernel = void (*)(const void *, const long long *, const long long *, int, int, int, float, float, float, float, int, float *, long long *);
+    static const Kernel kernels[2][UP_MAX_FACTOR - UP_MIN_FACTOR + 1] = {{k_upsample<2, false>, k_upsample<3, false>, k_upsample<4, false>},
+                                                                          {k_upsample<2, true>, k_upsample<3, true>, k_upsample<4, true>}};
+    hipLaunchKernelGGL(kernels[rgb][factor - UP_MIN_FACTOR], dim3((unsigned)blocks), dim3(kBlock), 0, stream, low, (const long long *)d_aov_lo,
+                       (const long long *)d_aov_hi, low_width, low_height, tiles_x, inv_spp, inv_lo, inv_hi, kz, prm.normal_power_log2, d_rgb_out,
+                       (long long *)d_out_fixed);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(stream));
+    return 0;
+}

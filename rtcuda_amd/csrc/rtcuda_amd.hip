@@ -15,8 +15,9 @@
 //   rt_denoise_kernels.inc the denoisers' kernels: one tap loop (dn_filter_pixel) and two pass bodies (dn_pass_direct, dn_pass_lds) under
 //                          k_atrous* / k_atrous_var*; prepare, finish, k_dn_var_blur (arithmetic: rt_denoise.h, shared with the CPU twin)
 //   rt_host_denoise.inc    rt_denoise_fixed, rt_denoise_dual_fixed and rt_denoise_variance_fixed: one set of checks (dn_check), one pass
-//                          launcher, one run (dn_run)
+//                          launcher, one run (dn_run); rt_upsample_fixed and rt_upsample_rgb behind the same checks (upsample_impl)
 //   rt_temporal_kernels.inc k_temporal_accumulate_moments, k_temporal_accumulate: one pixel body with its features and without (arithmetic: rt_temporal.h, shared with k_motion and the CPU twins)
+//   rt_upsample_kernels.inc k_upsample<F, kRgb>: AOV-guided upsampling, a tile of full pixels from its low-resolution footprint in LDS (arithmetic: rt_upsample.h, shared with the CPU twin)
 //   rt_host_temporal.inc   rt_temporal_accumulate_moments_fixed, and rt_temporal_accumulate_fixed as that with the features off: the checks and the launch
 // The C-ABI below them only checks arguments and forwards, and calls none of its own entry points.  Two bodies stay in it:
 // rt_camera_make (host arithmetic, nothing shared) and rt_xorwow_states (a test hook around k_rng_init / k_test_draw).
@@ -92,6 +93,7 @@
 #include "rt_slot_chunks.h"
 #include "rt_stats_merge.h"
 #include "rt_temporal.h"
+#include "rt_upsample.h"
 
 using namespace rt;
 
@@ -1166,11 +1168,12 @@ __global__ void k_test_draw(DPools p, int n, int draws, uint32_t *__restrict__ s
 #include "rt_build_kernels.inc"   // device BVH: the leaf-order arrays, refit (k_refit_*), build (k_ploc_*)
 #include "rt_denoise_kernels.inc"  // dn_filter_pixel under k_atrous* and k_atrous_var*; k_dn_prepare*, k_dn_var_blur, k_dn_finish*
 #include "rt_temporal_kernels.inc"  // k_temporal_accumulate_moments, k_temporal_accumulate
+#include "rt_upsample_kernels.inc"  // k_upsample<F, kRgb>: a tile of full pixels from its low-resolution footprint in LDS
 
 #include "rt_host_scene.inc"   // (opens the anonymous namespace that is closed below) rt_scene: reference tree, checks, build / emit / adopt, create, update, rebuild, edits; what the ray entry points share
 #include "rt_host_render.inc"  // Context, cached output buffers, kernel selection, one shard of a frame, queries and trace hooks, ray tables, AOVs
 #include "rt_host_frame.inc"   // whole frames: the shard fan-out (RT_SPLIT, rt_render_multi), finish_frame, rt_render, rt_render_multi
-#include "rt_host_denoise.inc"  // rt_denoise_fixed, rt_denoise_dual_fixed
+#include "rt_host_denoise.inc"  // rt_denoise_fixed, rt_denoise_dual_fixed, rt_denoise_variance_fixed, rt_upsample_fixed / rt_upsample_rgb
 #include "rt_host_temporal.inc"  // rt_temporal_accumulate_fixed, rt_temporal_accumulate_moments_fixed
 #include "rt_host_counts.inc"  // rt_normalize_counts_fixed, rt_post_process_counts_fixed, rt_sample_allocate
 }  // namespace
@@ -1444,6 +1447,26 @@ int rt_denoise_dual_fixed(const int64_t *d_sum_a, int samples_a, const int64_t *
                           float *d_rgb_out, void *stream) {
     return denoise_dual_impl(d_sum_a, samples_a, d_sum_b, samples_b, d_aov_fixed, aov_samples, width, height, params, d_scratch,
                              d_rgb_out, (hipStream_t)stream);
+}
+
+int rt_upsample_default_params(rt_upsample_params *out) {
+    if (!out) return fail("rt_upsample_default_params: null out");
+    *out = upsample_defaults();
+    return 0;
+}
+
+int rt_upsample_fixed(const int64_t *d_sum_lo, int num_samples, const int64_t *d_aov_lo, int aov_samples_lo, int low_width, int low_height,
+                      int factor, const int64_t *d_aov_hi, int aov_samples_hi, const rt_upsample_params *params, float *d_rgb_out,
+                      int64_t *d_out_fixed, void *stream) {
+    return upsample_impl("rt_upsample_fixed: ", false, d_sum_lo, "d_sum_lo", num_samples, d_aov_lo, aov_samples_lo, low_width, low_height, factor,
+                         d_aov_hi, aov_samples_hi, params, d_rgb_out, d_out_fixed, (hipStream_t)stream);
+}
+
+int rt_upsample_rgb(const float *d_rgb_lo, const int64_t *d_aov_lo, int aov_samples_lo, int low_width, int low_height, int factor,
+                    const int64_t *d_aov_hi, int aov_samples_hi, const rt_upsample_params *params, float *d_rgb_out, int64_t *d_out_fixed,
+                    void *stream) {
+    return upsample_impl("rt_upsample_rgb: ", true, d_rgb_lo, "d_rgb_lo", 1, d_aov_lo, aov_samples_lo, low_width, low_height, factor, d_aov_hi,
+                         aov_samples_hi, params, d_rgb_out, d_out_fixed, (hipStream_t)stream);
 }
 
 int rt_render_motion(const rt_scene *scene, const rt_camera *camera, int width, int height, const rt_camera *prev_camera,
